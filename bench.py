@@ -3,11 +3,17 @@
 
 A "step" is one pass of the hot path over one resident batch of synthetic input.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) measures the headline only: it sets up C2, runs the untimed
+pre-heat and the W warm-up steps, times exactly K steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints the line.  `--full` adds everything else below (the cold timing, the mixed-precision leg, CPU
+baselines, parity of the timed launches against the oracle, the host entry, the gathers and the secondary blocks).
+
   headline (`value`, every N)   BASELINE.json configs[1] = C2: plaid() on dense 20,000 genes x 10,000 samples per
                                 GPU x 5,000 gene sets: S = G^T X (1/|set| scaling) + normalize_medians()
                                 (R/plaid.R:60-87).  With --gpus N every rank holds its own 10,000-sample shard
                                 (weak scaling); the data-path collectives are the two scalar all-reduces
                                 normalize_medians needs across shards.
+  --full only:
   "c3" block (N = 1)            configs[2]: replaid.ssgsea(alpha = 0.25) on SPARSE 20,000 x 100,000 cells (5 % stored)
                                 x 50,000 sets, full size: sparse_colranks -> max(rX) -> scatter crossprod -> medians.
   "c4" block (N = 1)            configs[3]: replaid.ssgsea(alpha = 0.25) on DENSE 20,000 x 50,000 x 50,000, full size:
@@ -42,6 +48,8 @@ HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 LDS_PEAK_GBPS = 157286.4    # 256 CUs x 256 B/clk x 2.4 GHz (MI355X_MICROARCH.md, LDS: ds_read_b64/b128)
 FP64_PEAK_TFLOPS = 78.6     # vector FP64, FMA counted as 2 flop
 METRIC = "sample x geneset scores/sec at 20k genes (plaid(): crossprod + median normalisation)"
+DUMP_BUDGET = 48 * 10**6    # bytes --dump-outputs may write in all
+DUMP_SEED = 20251016        # the column sample of --dump-outputs: fixed, so two builds dump the same columns
 
 
 def parse(argv=None):
@@ -53,7 +61,7 @@ def parse(argv=None):
     ap.add_argument("--samples", type=int, default=10000, help="C2 samples per GPU")
     ap.add_argument("--sets", type=int, default=5000, help="C2 gene sets")
     ap.add_argument("--config", default="all", choices=["all", "c2", "c3", "c4", "ref", "c3real"],
-                    help="N = 1: which blocks to run next to the C2 headline (default: all)")
+                    help="with --full, N = 1: which blocks to run next to the C2 headline (default: all)")
     ap.add_argument("--profile", action="store_true",
                     help="profiling run (tools/profile_round.sh): ONLY the block --config names, no C2 headline, no pre-heat, "
                          "so that a rocprofv3 kernel-stats file holds one launch shape per kernel row")
@@ -71,6 +79,12 @@ def parse(argv=None):
     ap.add_argument("--no-mixed", action="store_true", help="skip the secondary mixed-precision (fp32-staged) measurement")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: rendezvous (gloo), the max-over-ranks reduction and the output line only (CPU test of the launcher)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the cold timing, the mixed-precision leg, CPU baselines, parity against "
+                         "the oracle, the host entry, the gathers and the c3 / c4 / ref / c3real / c5_shard blocks (--config picks them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed C2 step computed as DIR/<name>.npy (float64, at most "
+                         f"{DUMP_BUDGET // 10**6} MB: a fixed, seeded sample of the sample columns when the scores are larger)")
     return ap.parse_args(argv)
 
 
@@ -447,6 +461,29 @@ def np_f(t):
     return np.asfortranarray(t.cpu().numpy().T)
 
 
+def dump_outputs(torch, S, out_dir, name="scores"):
+    """--dump-outputs: the score matrix the timed step left in S (row-major (n, m) == R's m sets x n samples), as
+    out_dir/<name>.npy, float64, sets x samples.  Above DUMP_BUDGET bytes only a fixed, seeded sample of the sample
+    columns (sorted; rows too if one column alone is over the budget), so the same arguments dump the same entries."""
+    import numpy as np
+    n, m = S.shape
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.arange(m) if 8 * m <= DUMP_BUDGET else np.sort(rng.choice(m, size=DUMP_BUDGET // 8, replace=False))
+    k = min(n, DUMP_BUDGET // (8 * len(rows)))
+    cols = np.arange(n) if k == n else np.sort(rng.choice(n, size=k, replace=False))
+    if S.is_cuda:
+        torch.cuda.synchronize()
+    sub = S.index_select(0, torch.as_tensor(cols, device=S.device))
+    if len(rows) < m:
+        sub = sub.index_select(1, torch.as_tensor(rows, device=S.device))
+    arr = np.ascontiguousarray(sub.cpu().numpy().T, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, arr)
+    print(f"[bench] outputs: {path} ({arr.shape[0]} of {m} sets x {arr.shape[1]} of {n} samples, float64)",
+          file=sys.stderr, flush=True)
+
+
 def _parity_report(res, snap, n, m, extra=None):
     from oracle import fullsize
     out = {"launch": "full", "checked": "the S the last timed step produced",
@@ -574,7 +611,8 @@ def run_c2(a, env):
     info = gs.info()
     X = torch.empty((n, g), dtype=torch.float64, device=dev)      # row-major (n, g) == R's g x n
     col0 = rank * n                                               # this rank's sample shard
-    want_host = world == 1 and rank == 0 and a.cpu_sample > 0     # the host-entry leg needs the matrix in host memory
+    checks = a.full and world == 1 and rank == 0 and a.cpu_sample > 0   # CPU baseline, parity, host entry (--full)
+    want_host = checks                                            # the host-entry leg needs the matrix in host memory
     Xhost = np.empty((g, n), dtype=np.float64, order="F") if want_host else None
     for j0 in range(0, n, 1024):
         j1 = min(n, j0 + 1024)
@@ -606,8 +644,11 @@ def run_c2(a, env):
             ev.rec(k, 3)
 
     cold = {}
-    elapsed = _timed(torch, dist, use_dist, dev, a.steps, a.warmup, step, preheat=a.preheat_steps, cold_out=cold)
-    snap = _snapshot(torch, S, med, red[0:2], flags, n, m) if (rank == 0 and world == 1 and a.cpu_sample > 0) else None
+    elapsed = _timed(torch, dist, use_dist, dev, a.steps, a.warmup, step, preheat=a.preheat_steps,
+                     cold_out=cold if a.full else None)
+    if a.dump_outputs and rank == 0:       # before anything below writes into S again
+        dump_outputs(torch, S, a.dump_outputs)
+    snap = _snapshot(torch, S, med, red[0:2], flags, n, m) if checks else None
     ms_step = 1e3 * elapsed / a.steps
     spmm_ms, med_ms, shift_ms = ev.phase_ms(0), ev.phase_ms(1), ev.phase_ms(2)
     scores = float(world) * n * m
@@ -615,7 +656,7 @@ def run_c2(a, env):
 
     # secondary, never in `value`: the opt-in mixed-precision crossprod (fp32 operand staging, fp64 sums)
     mixed = None
-    if not a.no_mixed and world == 1:
+    if a.full and not a.no_mixed and world == 1:
         try:
             ctx.set_precision("mixed")
             msteps = max(3, min(a.steps, 10))
@@ -658,11 +699,11 @@ def run_c2(a, env):
         "shift_columns": _roof("shift_columns_kernel", 16.0 * m * n, shift_ms, _traffic("shift_columns_kernel", f"{n}x{m}")),
     }
 
-    gather = _bench_gather(env, S, world * n, ("device",)) if (use_dist and not a.no_gather) else None
+    gather = _bench_gather(env, S, world * n, ("device",)) if (a.full and use_dist and not a.no_gather) else None
 
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and a.cpu_sample > 0:
+    if checks:
         from oracle import c_oracle
         nc = min(a.cpu_sample, n)
         Xh = synth.dense_columns(g, 0, nc)
@@ -721,7 +762,8 @@ def run_c2(a, env):
             host_entry = {"error": str(exc)[:200]}
     del Xhost
     out = {
-        "value": value, "ms_per_step": ms_step, "ms_per_step_cold": 1e3 * cold["elapsed"] / a.steps,
+        "value": value, "ms_per_step": ms_step,
+        "ms_per_step_cold": 1e3 * cold["elapsed"] / a.steps if "elapsed" in cold else None,
         "roofline": roofline, "cpu_baseline": cpu, "parity": parity,
         "host_entry": host_entry,
         "gather": gather, "mixed_precision": mixed, "kernels": kernels, "pipeline": _pipeline(dict(kernels, crossprod=roofline), ms_step),
@@ -1359,6 +1401,8 @@ def main():
         return launch_ranks(a, sys.argv[1:])
     if a.dry_run:
         return dry_run(a)
+    if a.profile and a.config != "c2" and not a.full:
+        raise SystemExit(f"bench.py: --profile --config {a.config} profiles a block that only --full runs: add --full")
     import torch
     import torch.distributed as dist
 
@@ -1403,8 +1447,8 @@ def main():
     if a.profile:
         a.preheat_steps = 0
     c2 = None if profile_only else run_c2(a, env)
-    blocks = {}
-    if world == 1 and not use_dist:
+    blocks = {}                                # (a plain run: the headline alone)
+    if a.full and world == 1 and not use_dist:
         def ref_blocks():
             return {nm: run_ref_shape(a, env, nm) for nm in REF_PUBLISHED}
         for name, fn in (("c3", lambda: run_sparse_ssgsea(a, env, a.c3_cells, "C3", False)), ("c4", lambda: run_c4(a, env)),
@@ -1416,7 +1460,7 @@ def main():
                 except Exception as exc:  # a failing secondary block must not take the headline line with it
                     blocks[name] = {"error": f"{type(exc).__name__}: {str(exc)[:300]}"}
                     torch.cuda.empty_cache()
-    elif a.config in ("all", "c3"):
+    elif a.full and a.config in ("all", "c3"):
         try:
             blocks["c5_shard"] = run_sparse_ssgsea(a, env, a.c5_cells_per_gpu, "C5 shard", True)
         except Exception as exc:
@@ -1430,16 +1474,17 @@ def main():
             "metric": METRIC,
             "value": round(c2["value"], 1), "unit": "scores/s", "n_gpus": seen_world, "steps": a.steps,
             "warmup": a.warmup, "preheat_steps": a.preheat_steps, "ms_per_step": round(c2["ms_per_step"], 4),
-            "ms_per_step_cold": round(c2["ms_per_step_cold"], 4),
-            "value_cold": round(c2["config"]["samples_per_gpu"] * c2["config"]["sets"] * world / (c2["ms_per_step_cold"] * 1e-3), 1),
-            "cold_note": "ms_per_step_cold / value_cold: the same K steps timed right after the W warm-up steps, BEFORE the "
-                         "pre-heat (same process); ms_per_step / value: after `preheat_steps` more untimed steps (sustained clocks)",
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": c2["config"], "roofline": c2["roofline"], "cpu_baseline": c2["cpu_baseline"],
             "phases_ms": c2["phases_ms"], "kernels": c2["kernels"], "pipeline": c2.get("pipeline"), "parity": c2["parity"], "gather": c2["gather"],
             "mixed_precision": c2["mixed_precision"], "host_entry": c2["host_entry"],
         }
+        if c2["ms_per_step_cold"] is not None:      # --full
+            out["ms_per_step_cold"] = round(c2["ms_per_step_cold"], 4)
+            out["value_cold"] = round(c2["config"]["samples_per_gpu"] * c2["config"]["sets"] * world / (c2["ms_per_step_cold"] * 1e-3), 1)
+            out["cold_note"] = ("ms_per_step_cold / value_cold: the same K steps timed right after the W warm-up steps, BEFORE the "
+                                "pre-heat (same process); ms_per_step / value: after `preheat_steps` more untimed steps (sustained clocks)")
         out.update(blocks)
         rs = blocks.get("ref_shape", {})
         if isinstance(rs, dict) and any(isinstance(v, dict) and "vs_baseline" in v for v in rs.values()):

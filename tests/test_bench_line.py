@@ -1,9 +1,12 @@
 """bench.py's output contract, on the CPU: the ONE stdout line stays under 4 KB whatever the blocks hold (the driver
-could not parse round 4's ~23 KB line: BENCH_r04.json parsed = null), and `--gpus N` starts its own ranks."""
+could not parse round 4's ~23 KB line: BENCH_r04.json parsed = null), and `--gpus N` starts its own ranks; on the GPU, a
+plain run (no --full) and what --dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -113,3 +116,53 @@ def test_a_failing_rank_fails_the_launcher(tmp_path):
                        capture_output=True, text=True, timeout=240)
     assert p.returncode != 0, p.stdout[-500:]
     assert not any(ln.startswith('{"metric"') for ln in p.stdout.splitlines())
+
+
+def test_a_plain_run_is_the_default():
+    """`--full` (everything beyond the headline) is off unless asked for; --dump-outputs takes a directory"""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """the dump of a score matrix above the budget is a fixed sample of its columns, float64, within the budget, and the
+    same from call to call; below the budget it is the whole matrix in R layout (sets x samples)"""
+    import numpy as np
+    import torch
+    S = torch.arange(10000 * 5000, dtype=torch.float64).reshape(10000, 5000)     # (samples, sets) like the timed S
+    bench.dump_outputs(torch, S, str(tmp_path / "a"))
+    bench.dump_outputs(torch, S, str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert a.dtype == np.float64 and a.shape[0] == 5000 and 0 < a.shape[1] < 10000
+    assert os.path.getsize(tmp_path / "a" / "scores.npy") <= 64 * 10**6 and np.array_equal(a, b)
+    cols = (a[0] // 5000).astype(np.int64)
+    assert np.all(np.diff(cols) > 0) and np.array_equal(a, S.numpy()[cols].T)
+    small = torch.randn(300, 200, dtype=torch.float64)
+    bench.dump_outputs(torch, small, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "scores.npy"), small.numpy().T)
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_the_timed_step_computed(tmp_path):
+    """a plain run (no --full) prints the contract's keys, times exactly --steps steps, and --dump-outputs writes the
+    normalised scores of the last timed step: those of plaid() on the same synthetic inputs, by the oracle"""
+    import numpy as np
+    from oracle import c_oracle
+    from plaid_amd import synth
+    g, n, m = 2000, 600, 300
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["BENCH_DETAIL"] = str(tmp_path / "detail.json")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--preheat-steps", "0", "--genes", str(g), "--samples", str(n), "--sets", str(m),
+                        "--dump-outputs", str(tmp_path / "out")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["metric"] == bench.METRIC and d["unit"] == "scores/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["blocks"] == {}
+    got = np.load(tmp_path / "out" / "scores.npy")
+    Gp, Gi = synth.geneset_csc(g, m)
+    want = c_oracle.plaid_dense(synth.dense_columns(g, 0, n), Gp, Gi, "mean", True)
+    assert got.dtype == np.float64 and got.shape == (m, n)
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-9)

@@ -4,8 +4,8 @@ Every N > 1 run of earlier rounds went through gloo; what an 8-GPU node would ex
 device_id=...)`, int32 MAX / fp64 SUM all-reduces on device tensors, the gather -- had never run.  Both tests start FRESH
 child processes (subprocess, never exec: a process that has touched the GPU must not be replaced):
 
-  * bench.py with BENCH_FORCE_DIST=1: the driver's own N-GPU entry with a one-rank RCCL group (headline block, then the
-    sample-shard block whose three scalars go through all-reduces on device tensors);
+  * bench.py --full with BENCH_FORCE_DIST=1: the driver's own N-GPU entry with a one-rank RCCL group (headline block and
+    its gather, then the sample-shard block whose three scalars go through all-reduces on device tensors);
   * tests/helpers/rccl_one_rank_child.py: sharded_plaid / sharded_ssgsea / sharded_ssgsea_csc / sharded_plaid_csc and
     gather_scores(to="device" | "host") under a one-rank RCCL group, bit-identical to the calls without a group.
 
@@ -38,7 +38,7 @@ def test_bench_runs_its_rccl_branch_with_one_rank():
     env = _env(29541)
     env["BENCH_FORCE_DIST"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--preheat-steps", "0", "--config", "c2", "--cpu-sample", "0"], cwd=ROOT, env=env,
+                        "--preheat-steps", "0", "--config", "c2", "--cpu-sample", "0", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = _last_json(p.stdout)
@@ -52,7 +52,7 @@ def test_bench_shard_block_all_reduces_over_rccl():
     env["BENCH_FORCE_DIST"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
                         "--preheat-steps", "0", "--config", "c3", "--c5-cells-per-gpu", "8192", "--big-sets", "20000",
-                        "--block-steps", "2", "--cpu-sample", "0", "--no-gather"], cwd=ROOT, env=env,
+                        "--block-steps", "2", "--cpu-sample", "0", "--no-gather", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = _last_json(p.stdout)

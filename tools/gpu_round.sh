@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 python -m pytest tests -m gpu -x -q "$@" > $out/pytest.log 2>&1
 echo "pytest rc=$?" >> $out/pytest.log
 tail -5 $out/pytest.log
-python bench.py > $out/bench.json 2> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench rc=$?"; tail -c 600 $out/bench.err
 cp bench_detail.json $out/bench_detail.json 2>/dev/null
 python3 - <<PY

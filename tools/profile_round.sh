@@ -14,10 +14,10 @@
 out=${1:-gpurun_out/prof}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p $out
-BENCH_DETAIL=$PWD/$out/bench_detail.json python3 bench.py > $out/bench.json 2> $out/bench.err
+BENCH_DETAIL=$PWD/$out/bench_detail.json python3 bench.py --full > $out/bench.json 2> $out/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_c2 -- python3 bench.py --config c2 --preheat-steps 0 --cpu-sample 0 --no-mixed > $out/stats_c2.log 2>&1
 for cfg in c3 c4 ref; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$cfg -- python3 bench.py --profile --config $cfg --cpu-sample 0 --no-mixed > $out/stats_$cfg.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$cfg -- python3 bench.py --full --profile --config $cfg --cpu-sample 0 --no-mixed > $out/stats_$cfg.log 2>&1
 done
 SQSET="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_ANY"
 run_pmc() {   # tag, then bench_spmm.py arguments
