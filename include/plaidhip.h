@@ -414,8 +414,9 @@ int plaidhip_scse(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const
                   int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                   int remove_log2, int score_mean, double* S_out, int* removed_log2);
 
-/* replaid.gsva(X, matG, tau, rowtf), R/plaid.R:338-363, dense X: row transform (rowtf = 0: "z",
- * center + scale per gene; 1: "ecdf", the per-gene empirical CDF), signed average ranks per sample,
+/* replaid.gsva(X, matG, tau, rowtf), R/plaid.R:338-363, dense X (a dgCMatrix: plaidhip_gsva_csc
+ * below): row transform (rowtf = 0: "z", center + scale per gene; 1: "ecdf", the per-gene empirical
+ * CDF), signed average ranks per sample,
  * / max|rank|, sign * |.|^(1 + tau) for tau > 0, then plaid(mean, normalised).  The row transform
  * needs every sample of a gene, so this call does not shard by sample.                           */
 int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp,
@@ -431,6 +432,29 @@ int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, cons
 int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* y,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
                         int metap_method, double* out);
+
+/* The same two calls for a dgCMatrix X (g x n, slots Xp / Xi / Xx): replaid.gsva(X, ...) and plaid.test(X, ...) with
+ * the result of as.matrix(X) (R/plaid.R:341-343 / 365-370, 407-408 / 426), without a dense X on the host or the link.
+ * The slots go to the device and are transposed there into a row view (CSR), whose rows are in ascending column
+ * order whatever the scheduling; the row statistics sum each row in that order, with no floating-point atomics.
+ *   plaidhip_gsva_csc: "z": per-gene mean / sd from the stored values and the implicit zeros; "ecdf": #{x <= x_i}
+ *     per gene from the max-ranks of the stored values and the implicit zeros (integers: exact).  The dense zX is then
+ *     built on the device and the rest is plaidhip_gsva's own launch sequence.  Device memory: the CSC slots, the row
+ *     view (Rp, Rx, and for "ecdf" the CSC position of every entry: 12 or 16 bytes per stored value), two g x n doubles
+ *     (zX and its ranks: every gene is ranked in every sample) and S; no g x n buffer on the host.
+ *   plaidhip_plaid_test_csc: the logFC from the per-row group means of the row view, then plaidhip_plaid_test's
+ *     crossprod and host tail; with "lm" and gsetX == NULL, plaid(X, G) is computed from the CSC slots with the
+ *     kernels of plaidhip_plaid_csc (mean, normalised) and stays on the device.  Device memory: the CSC slots, the row
+ *     view (Rp, Rx, column indices: 12 bytes per stored value) and m x n doubles of scores with "lm"; no g x n buffer
+ *     anywhere.  Same y / tests / metap_method checks, messages and out as plaidhip_plaid_test.
+ * Guarantees: the same inputs give the same bits from run to run; two genes with identical rows get identical row
+ * statistics; "ecdf" gives the bits of plaidhip_gsva on as.matrix(X).  R: replaid.gsva / plaid.test with a dgCMatrix
+ * (R_plaidhip_gsva_csc, R_plaidhip_plaid_test_csc).                                                                   */
+int plaidhip_gsva_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                      const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out);
+int plaidhip_plaid_test_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g,
+                            int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                            const double* gsetX, int tests, int metap_method, double* out);
 
 /* plaid.test over SAMPLE SHARDS (one process per GPU): the statistics of R/plaid.R:407-431 are row-wise sums over the
  * samples, so every shard reduces its own columns on the device and the caller adds the shards' results (an all-reduce

@@ -101,6 +101,8 @@ SIGNATURES = {
     "plaidhip_scse": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, C.POINTER(_int)],
     "plaidhip_gsva": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp],
     "plaidhip_plaid_test": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _int, _int, _vp],
+    "plaidhip_gsva_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp],
+    "plaidhip_plaid_test_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _int, _int, _vp],
     "plaidhip_dev_row_group_sums": [_vp, _vp, _i64, _i32, _i32, _vp, _vp],
     "plaidhip_dev_row_group_ssd": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],

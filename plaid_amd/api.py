@@ -293,6 +293,16 @@ def replaid_scse(X, matG, removeLog2=None, scoreMean=False, ctx: Context | None 
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
+def _canonical_csc(V):
+    """V as a CSC matrix whose columns have sorted, distinct row indices (a dgCMatrix always does; scipy may not),
+    so that its slots mean what as.matrix() means.  A copy only when V is not already so."""
+    V = sp.csc_matrix(V)                                   # (shares the slots of a CSC matrix)
+    if not V.has_canonical_format:
+        V = V.copy()
+        V.sum_duplicates()
+    return V
+
+
 def replaid_gsva(X, matG, tau=0, rowtf="z", ctx: Context | None = None):
     """replaid.gsva(), R/plaid.R:338-363 (row z-transform variant; the result of plaid() on the rank matrix
     carries the dimnames of matG / X)."""
@@ -303,8 +313,11 @@ def replaid_gsva(X, matG, tau=0, rowtf="z", ctx: Context | None = None):
         _message("[plaid] ERROR. No overlapping features.")
         return None
     ctx = ctx or default_context()
-    Xv = X.values.toarray() if sp.issparse(X.values) else X.values
-    S = ctx.gsva(Xv, pat[0], pat[1], float(tau), rowtf)
+    if X.is_sparse:                                        # the CSC slots go to the device: no dense X on the host
+        V = _canonical_csc(X.values)
+        S = ctx.gsva_csc(V.indptr, V.indices, V.data, X.shape[0], pat[0], pat[1], float(tau), rowtf)
+    else:
+        S = ctx.gsva(X.values, pat[0], pat[1], float(tau), rowtf)
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
@@ -354,7 +367,13 @@ def plaid_test(X, y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fi
     Gp = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     Gi = Gs.indices[keep].astype(np.int32)
     Xv = X.values
-    Xs = np.asfortranarray(Xv[xrow, :].toarray() if sp.issparse(Xv) else np.asarray(Xv)[xrow, :], dtype=np.float64)
+    if sp.issparse(Xv):
+        Xs = sp.csc_matrix(Xv)
+        if not np.array_equal(xrow, np.arange(Xs.shape[0])):
+            Xs = Xs[xrow, :]                                          # X[gg, ] stays sparse
+        Xs = _canonical_csc(Xs)
+    else:
+        Xs = np.asfortranarray(np.asarray(Xv)[xrow, :], dtype=np.float64)
     sx = None
     if gsetX is not None:
         gx = as_named(gsetX)
@@ -364,7 +383,10 @@ def plaid_test(X, y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fi
         else:
             sx = np.asarray(gx.values)
     ctx = ctx or default_context()
-    out = ctx.plaid_test(Xs, y.astype(np.int32), Gp, Gi, sx, bits, mm)
+    if sp.issparse(Xs):
+        out = ctx.plaid_test_csc(Xs.indptr, Xs.indices, Xs.data, Xs.shape[0], y.astype(np.int32), Gp, Gi, sx, bits, mm)
+    else:
+        out = ctx.plaid_test(Xs, y.astype(np.int32), Gp, Gi, sx, bits, mm)
     cols, names = [0], ["gsetFC"]
     for t, c in (("one", 1), ("two", 2), ("lm", 3)):
         if t in tests:

@@ -1237,6 +1237,28 @@ int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
                                     metap_method, out);
 } catch (...) { return plaidhip::on_exception(); }
 
+// replaid.gsva from the row-transformed zX (dX: g x n, leading dimension ldg) on: the scores in dS (m x n), normalised.
+// dR: a second g x n buffer; dsmall: 64 + 16 n bytes.  Shared by the dense and the CSC entry.
+static int gsva_scores(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const double* dX, double* dR, int64_t ldg, int32_t g,
+                       int32_t n, int32_t m, double tau, double* dS, DevBuf& dsmall) {
+  uint32_t* d_flags = dsmall.as<uint32_t>();
+  double* d_red = reinterpret_cast<double*>(dsmall.as<char>() + 16);
+  double* d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
+  double* d_colmax = d_med + n;
+  double* d_gmax = d_red + 2;
+  // rX = colranks(zX, signed = TRUE, "average"); rX / max|rX|; sign * |rX|^(1 + tau)   (:352-358)
+  //    = sign * rank^(1+tau) / max(rank^(1+tau)): the power is fused into the rank kernel, the division into the
+  //    SpMM epilogue (alpha_div), by linearity of the mean statistic
+  PH_TRY(launch_colranks_dense_f64(ctx, dX, ldg, g, n, PLAIDHIP_TIES_AVERAGE, 1, tau > 0.0 ? 1.0 + tau : 1.0, dR, ldg,
+                                   d_colmax));
+  PH_TRY(launch_max(ctx, d_colmax, n, d_gmax));
+  PH_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
+  PH_TRY(launch_spmm_dense_f64(ctx, gs, dR, ldg, n, PLAIDHIP_STAT_MEAN, 1.0, d_gmax, 0.0, dS, m, d_flags,
+                               tau > 0.0 ? PLAIDHIP_X_ANY : PLAIDHIP_X_EXACT_F32));   // signed average ranks
+  PH_TRY(normalize_on_device(ctx, dS, m, n, PLAIDHIP_IGNORE_ZERO_AUTO, d_flags, true, d_med, d_red));   // :360 plaid()
+  return PLAIDHIP_OK;
+}
+
 int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi,
                   int32_t m, double tau, int rowtf, double* S_out) try {
   PH_CTX(ctx);
@@ -1255,11 +1277,6 @@ int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, cons
   PH_TRY(dmom.alloc((size_t)g * 4 * 8));
   PH_TRY(dws.alloc((size_t)row_group_ws_doubles(g, n) * 8));
   PH_TRY(dsmall.alloc(64 + (size_t)n * 16));
-  uint32_t* d_flags = dsmall.as<uint32_t>();
-  double* d_red = reinterpret_cast<double*>(dsmall.as<char>() + 16);
-  double* d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
-  double* d_colmax = d_med + n;
-  double* d_gmax = d_red + 2;
   PH_TRY(h2d_cols(ctx, dX.p, ldg, X, g, n));
   PH_HIP(hipMemsetAsync(dy.p, 0, (size_t)n * 4, ctx->stream));                         // one group: every sample
   if (rowtf == 0) {
@@ -1276,19 +1293,164 @@ int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, cons
     PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), n, n, g, dR.as<double>(), ldg));              // dR: g x n
     PH_HIP(hipMemcpyAsync(dX.p, dR.p, (size_t)ldg * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  // rX = colranks(zX, signed = TRUE, "average"); rX / max|rX|; sign * |rX|^(1 + tau)   (:352-358)
-  //    = sign * rank^(1+tau) / max(rank^(1+tau)): the power is fused into the rank kernel, the division into the
-  //    SpMM epilogue (alpha_div), by linearity of the mean statistic
-  PH_TRY(launch_colranks_dense_f64(ctx, dX.as<double>(), ldg, g, n, PLAIDHIP_TIES_AVERAGE, 1, tau > 0.0 ? 1.0 + tau : 1.0,
-                                   dR.as<double>(), ldg, d_colmax));
-  PH_TRY(launch_max(ctx, d_colmax, n, d_gmax));
-  PH_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
-  PH_TRY(launch_spmm_dense_f64(ctx, gh.gs, dR.as<double>(), ldg, n, PLAIDHIP_STAT_MEAN, 1.0, d_gmax, 0.0, dS.as<double>(),
-                               m, d_flags, tau > 0.0 ? PLAIDHIP_X_ANY : PLAIDHIP_X_EXACT_F32));   // signed average ranks
-  PH_TRY(normalize_on_device(ctx, dS.as<double>(), m, n, PLAIDHIP_IGNORE_ZERO_AUTO, d_flags, true, d_med, d_red));   // :360 plaid()
+  PH_TRY(gsva_scores(ctx, gh.gs, dX.as<double>(), dR.as<double>(), ldg, g, n, m, tau, dS.as<double>(), dsmall));
   PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
   PH_HIP(hipStreamSynchronize(ctx->stream));
   return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// ---- dgCMatrix input for replaid.gsva and plaid.test: the row view on the device (kernels_csr.hip) -----------------------
+
+// the CSC slots on the device (nnz = Xp[n] already validated) and their row view: Rp (g + 1 and one more int for the
+// longest row), Rx, Rj / perm when asked for.  Returns the longest row in *max_row (one 4-byte read-back).
+struct CscOnDevice {
+  DevBuf dXp, dXi, dXx, dRp, dRj, dRx, dperm;
+};
+static int upload_csc_as_rows(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                              bool want_rj, bool want_perm, CscOnDevice& d, int32_t* max_row) {
+  const int64_t zx = Xp[n];
+  PH_TRY(d.dXp.alloc((size_t)(n + 1) * 4));
+  PH_TRY(d.dXi.alloc((size_t)zx * 4));
+  PH_TRY(d.dXx.alloc((size_t)zx * 8));
+  PH_TRY(d.dRp.alloc((size_t)(g + 2) * 4));
+  PH_TRY(d.dRx.alloc((size_t)zx * 8));
+  if (want_rj) PH_TRY(d.dRj.alloc((size_t)zx * 4));
+  if (want_perm) PH_TRY(d.dperm.alloc((size_t)zx * 4));
+  PH_TRY(h2d(ctx, d.dXp.p, Xp, (size_t)(n + 1) * 4));
+  PH_TRY(h2d(ctx, d.dXi.p, Xi, (size_t)zx * 4));
+  PH_TRY(h2d(ctx, d.dXx.p, Xx, (size_t)zx * 8));
+  int32_t* d_maxlen = d.dRp.as<int32_t>() + g + 1;
+  PH_TRY(launch_csc_to_csr(ctx, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), g, n, d.dRp.as<int32_t>(),
+                           want_rj ? d.dRj.as<int32_t>() : nullptr, d.dRx.as<double>(),
+                           want_perm ? d.dperm.as<int32_t>() : nullptr, d_maxlen));
+  PH_HIP(hipMemcpyAsync(max_row, d_maxlen, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipStreamSynchronize(ctx->stream));   // (the rank kernels take the longest row from the host)
+  return PLAIDHIP_OK;
+}
+
+int plaidhip_gsva_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                      const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out) try {
+  PH_CTX(ctx);
+  PH_TRY(check_host_common(Gp, g, n, m));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Xp && S_out, "gsva_csc: null Xp/S_out");
+  PH_REQUIRE(rowtf == 0 || rowtf == 1, "Error: unknown row transform %d", rowtf);                   // R/plaid.R:348
+  PH_TRY(check_host_csc(Xp, Xi, g, n));
+  PH_REQUIRE(Xp[n] == 0 || (Xi && Xx), "gsva_csc: null Xi/Xx");
+  // (the ranks of the rows' stored values use a g x n buffer as scratch: a column repeating a row index could pass it)
+  PH_REQUIRE((int64_t)Xp[n] <= (int64_t)g * n, "gsva_csc: %d stored values in a %d x %d matrix (repeated row indices?)",
+             Xp[n], g, n);
+  GenesetHolder gh;
+  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
+  const int64_t ldg = even_ld(g);
+  CscOnDevice d;
+  int32_t max_row = 0;
+  PH_TRY(upload_csc_as_rows(ctx, Xp, Xi, Xx, g, n, /*want_rj=*/false, /*want_perm=*/rowtf == 1, d, &max_row));
+  DevBuf dX, dR, dS, dmom, ddef, dsmall;
+  PH_TRY(dX.alloc((size_t)ldg * n * 8));
+  PH_TRY(dR.alloc((size_t)ldg * n * 8));
+  PH_TRY(dS.alloc((size_t)m * n * 8));
+  PH_TRY(dmom.alloc((size_t)g * 4 * 8));
+  PH_TRY(ddef.alloc((size_t)g * 8));
+  PH_TRY(dsmall.alloc(64 + (size_t)n * 16));
+  double* d_mean = dmom.as<double>();
+  double* d_ssd = d_mean + 2 * (size_t)g;
+  if (rowtf == 0) {
+    // zX = (X - rowMeans(X)) / (1e-8 + rowSds(X)) (R/plaid.R:341-343): the moments of each row from its stored values
+    // and its implicit zeros, then every entry of the dense zX from them (a zero's value is the row's default)
+    PH_TRY(launch_csr_row_group_moments(ctx, d.dRp.as<int32_t>(), nullptr, d.dRx.as<double>(), g, max_row, nullptr, n, 0,
+                                        d_mean, d_ssd));
+    PH_TRY(launch_row_z_defaults(ctx, d_mean, d_ssd, g, n, ddef.as<double>()));
+    PH_TRY(launch_csc_expand(ctx, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), g, n, ldg, ddef.as<double>(),
+                             d_mean, d_ssd, dX.as<double>()));
+  } else {
+    // zX = t(apply(X, 1, function(x) ecdf(x)(x))) (:346) without the factor 1/n, as the dense entry: #{x <= x_i} per
+    // gene from the max-ranks of its stored values (rank scratch: dR) and its implicit zeros; the stored entries' values
+    // go back to CSC order (into the CSC value slot, no longer needed) and are expanded with the rows' zero values
+    PH_TRY(launch_csr_row_ecdf(ctx, d.dRp.as<int32_t>(), d.dRx.as<double>(), g, n, max_row, d.dperm.as<int32_t>(),
+                               dR.as<double>(), d.dXx.as<double>(), ddef.as<double>()));
+    PH_TRY(launch_csc_expand(ctx, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), g, n, ldg, ddef.as<double>(),
+                             nullptr, nullptr, dX.as<double>()));
+  }
+  PH_TRY(gsva_scores(ctx, gh.gs, dX.as<double>(), dR.as<double>(), ldg, g, n, m, tau, dS.as<double>(), dsmall));
+  PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_plaid_test_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                            const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX,
+                            int tests, int metap_method, double* out) try {
+  PH_CTX(ctx);
+  PH_TRY(check_host_common(Gp, g, n, m));
+  PH_REQUIRE(m == 0 || out, "plaid_test: null out");
+  PH_REQUIRE(Xp != nullptr && (n == 0 || y), "plaid_test: null X / y");
+  PH_REQUIRE((tests & 7) != 0 && (tests & ~7) == 0, "plaid_test: tests is a bit mask of 1 (one), 2 (two), 4 (lm)");
+  PH_REQUIRE(metap_method == 0 || metap_method == 1, "Invalid method: %d", metap_method);      // R/plaid.R:533
+  int64_t n0 = 0, n1 = 0;
+  for (int32_t c = 0; c < n; ++c) {
+    PH_REQUIRE(y[c] == 0 || y[c] == 1, "elements of y must be 0 or 1");                        // R/plaid.R:394
+    if (y[c]) ++n1; else ++n0;
+  }
+  PH_TRY(check_host_csc(Xp, Xi, g, n));
+  const int64_t zx = Xp[n];
+  PH_REQUIRE(zx == 0 || (Xi && Xx), "plaid_test: null Xi/Xx");
+  if (m == 0) return PLAIDHIP_OK;
+  GenesetHolder gh;
+  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
+  const int64_t ldg = even_ld(g);
+  CscOnDevice d;
+  DevBuf dy, dmean, dF, dT, dws, dS, dsm, dsmall;
+  PH_TRY(dy.alloc((size_t)n * 4));
+  PH_TRY(h2d(ctx, dy.p, y, (size_t)n * 4));
+  int32_t max_row = 0;
+  PH_TRY(upload_csc_as_rows(ctx, Xp, Xi, Xx, g, n, /*want_rj=*/true, /*want_perm=*/false, d, &max_row));
+  PH_TRY(dmean.alloc((size_t)g * 2 * 8));
+  PH_TRY(dF.alloc((size_t)ldg * 2 * 8));
+  PH_TRY(dT.alloc((size_t)m * 2 * 8));
+  // fc = rowMeans(X[, y == 1]) - rowMeans(X[, y == 0])   (R/plaid.R:407-409) over the rows' stored values; Gt fc and
+  // Gt fc^2 (:478-479) as in the dense entry
+  PH_TRY(launch_csr_row_group_moments(ctx, d.dRp.as<int32_t>(), d.dRj.as<int32_t>(), d.dRx.as<double>(), g, max_row,
+                                      dy.as<int32_t>(), n0, n1, dmean.as<double>(), nullptr));
+  PH_HIP(hipMemsetAsync(dF.p, 0, (size_t)ldg * 2 * 8, ctx->stream));
+  PH_TRY(launch_fold_change(ctx, dmean.as<double>(), g, ldg, dF.as<double>()));
+  PH_TRY(launch_spmm_dense_f64(ctx, gh.gs, dF.as<double>(), ldg, 2, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(),
+                               m, nullptr));
+  std::vector<double> T((size_t)m * 2), F((size_t)ldg * 2), SM;
+  PH_HIP(hipMemcpyAsync(T.data(), dT.p, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipMemcpyAsync(F.data(), dF.p, (size_t)ldg * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (tests & 4) {
+    // scores stay on the device: given (uploaded) or plaid(X, G) from the CSC slots with the kernels of plaidhip_plaid_csc
+    // -- the sparse crossprod that also classifies its scores, then normalize_medians (R/plaid.R:424-427, 554-575)
+    PH_TRY(dS.alloc((size_t)m * n * 8));
+    PH_TRY(dws.alloc((size_t)row_group_ws_doubles(m, n) * 8));
+    if (gsetX != nullptr) {
+      PH_TRY(h2d(ctx, dS.p, gsetX, (size_t)m * n * 8));
+    } else if (n > 0) {
+      PH_TRY(dsmall.alloc(64 + (size_t)n * 8));
+      uint32_t* d_flags = dsmall.as<uint32_t>();
+      double* d_red = reinterpret_cast<double*>(dsmall.as<char>() + 16);
+      double* d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
+      PH_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
+      const int64_t nnz_choice = (int64_t)((double)zx / (double)n * (double)n);   // (run_sharded's choice on one shard)
+      PH_TRY(launch_spmm_csc_fused_f64(ctx, gh.gs, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), n, zx,
+                                       PLAIDHIP_STAT_MEAN, 1.0, nullptr, 0.0, dS.as<double>(), m, d_flags, /*bounded=*/false,
+                                       nullptr, 0.0, nnz_choice));
+      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, n, PLAIDHIP_IGNORE_ZERO_AUTO, d_flags, d_med));
+      PH_TRY(launch_sum(ctx, d_med, n, d_red));
+      PH_TRY(launch_shift_columns(ctx, dS.as<double>(), m, m, n, d_med, 0.0, d_red));
+    }
+    PH_TRY(dsm.alloc((size_t)m * 4 * 8));
+    PH_TRY(launch_row_group_moments(ctx, dS.as<double>(), m, m, n, dy.as<int32_t>(), n0, n1, dsm.as<double>(),
+                                    dsm.as<double>() + 2 * (size_t)m, dws.as<double>()));
+    SM.resize((size_t)m * 4);
+    PH_HIP(hipMemcpyAsync(SM.data(), dsm.p, (size_t)m * 4 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  double tot1 = 0.0, tot2 = 0.0;
+  for (int32_t i = 0; i < g; ++i) { tot1 += F[i]; tot2 += F[(size_t)ldg + i]; }
+  return plaidhip_plaid_test_finish(g, m, Gp, T.data(), tot1, tot2, (tests & 4) ? SM.data() : nullptr, n0, n1, tests,
+                                    metap_method, out);
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

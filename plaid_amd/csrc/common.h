@@ -329,6 +329,26 @@ int launch_transpose_f64(plaidhip_ctx* ctx, const double* A, int64_t lda, int32_
                          int64_t ldb);
 int launch_fold_change(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, int64_t ld2, double* d_F);
 int64_t row_group_ws_doubles(int32_t rows, int32_t n);
+// kernels_csr.hip: the row view of a CSC matrix (replaid.gsva / plaid.test on a dgCMatrix).  All pointers are device
+// pointers.  Transpose: Rp g + 1, Rx / Rj / perm Xp[n] entries each (Rj, perm optional), within a row ascending column
+// order; *d_maxlen = the longest row.  Uses the context workspace.
+int launch_csc_to_csr(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                      int32_t* Rp, int32_t* Rj, double* Rx, int32_t* perm, int32_t* d_maxlen);
+// launch_row_group_moments over the CSR rows (implicit zeros counted); d_y null: every column in group 0 (Rj unused)
+int launch_csr_row_group_moments(plaidhip_ctx* ctx, const int32_t* Rp, const int32_t* Rj, const double* Rx, int32_t rows,
+                                 int32_t max_row_nnz, const int32_t* d_y, int64_t n0, int64_t n1, double* d_mean,
+                                 double* d_ssd);
+// #{x <= x_i} of every stored value (-> out[perm[p]], CSC order) and of each row's implicit zero (-> dflt[row]);
+// Rrank: Rp[rows] doubles of scratch
+int launch_csr_row_ecdf(plaidhip_ctx* ctx, const int32_t* Rp, const double* Rx, int32_t rows, int32_t n,
+                        int32_t max_row_nnz, const int32_t* perm, double* Rrank, double* out, double* dflt);
+// dflt[r] = the z transform (launch_row_ztransform) of a zero in row r
+int launch_row_z_defaults(plaidhip_ctx* ctx, const double* d_mean, const double* d_ssd, int32_t rows, int32_t n,
+                          double* dflt);
+// dense g x n (leading dimension ld) from row defaults and the stored entries: vals as they are, or z-transformed
+// when d_mean / d_ssd are given
+int launch_csc_expand(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* vals, int32_t g, int32_t n,
+                      int64_t ld, const double* dflt, const double* d_mean, const double* d_ssd, double* out);
 double onesample_p(double k, double s1, double s2, double* mean_out);
 double twosample_p(double g, double k, double s1, double s2, double tot1, double tot2, double* diff_out);
 double welch_p(double m0, double m1, double ssd0, double ssd1, double n0, double n1);

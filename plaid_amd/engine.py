@@ -486,8 +486,49 @@ def _gsva(self, X, Gp, Gi, tau=0.0, rowtf="z"):
     return S
 
 
+def _csc_args(Xp, Xi, Xx):
+    Xp, Xi = _as_i32(Xp), _as_i32(Xi)
+    Xx = np.ascontiguousarray(Xx, dtype=np.float64)
+    return Xp, Xi, Xx, len(Xp) - 1
+
+
+def _gsva_csc(self, Xp, Xi, Xx, g, Gp, Gi, tau=0.0, rowtf="z"):
+    """plaidhip_gsva_csc: replaid.gsva on the slots of a g x n CSC matrix (no dense X on the host)"""
+    if rowtf not in ("z", "ecdf"):
+        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
+    Xp, Xi, Xx, n = _csc_args(Xp, Xi, Xx)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    check(self.lib.plaidhip_gsva_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n, _np_ptr(Gp),
+                                     _np_ptr(Gi), m, float(tau), 0 if rowtf == "z" else 1, _np_ptr(S)))
+    return S
+
+
+def _plaid_test_csc(self, Xp, Xi, Xx, g, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
+    """plaidhip_plaid_test_csc: Context.plaid_test on the slots of a g x n CSC matrix"""
+    Xp, Xi, Xx, n = _csc_args(Xp, Xi, Xx)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.shape != (n,):
+        raise ValueError("y must have one entry per column of X")
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    sx = None
+    if gsetX is not None:
+        sx = _as_f64_fortran(gsetX)
+        if sx.shape != (m, n):
+            raise ValueError("gsetX must be sets x samples")
+    out = np.empty((m, 6), dtype=np.float64, order="F")
+    check(self.lib.plaidhip_plaid_test_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n, _np_ptr(y),
+                                           _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(sx) if sx is not None else None,
+                                           int(tests), int(metap_method), _np_ptr(out)))
+    return out
+
+
 Context.gsva = _gsva
+Context.gsva_csc = _gsva_csc
 Context.plaid_test = _plaid_test
+Context.plaid_test_csc = _plaid_test_csc
 Context.ucell = _ucell
 Context.aucell = _aucell
 Context.scse = _scse

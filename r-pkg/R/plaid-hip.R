@@ -289,14 +289,21 @@ plaid.test <- function(X, y, G, gsetX, tests = c("one", "two", "lm"),
   }
   if (!metap.method %in% c("fisher", "sumlog", "stouffer", "sumz")) stop("Invalid method: ", metap.method)
   gg <- intersect(rownames(G), rownames(X))
-  X <- as.matrix(X[gg, , drop = FALSE]); storage.mode(X) <- "double"
+  sparse <- inherits(X, "CsparseMatrix")
+  if (sparse) {
+    X <- methods::as(X[gg, , drop = FALSE], "generalMatrix")   # stays a dgCMatrix: its slots go to the device
+  } else {
+    X <- as.matrix(X[gg, , drop = FALSE]); storage.mode(X) <- "double"
+  }
   G <- G[gg, , drop = FALSE]
   pat <- .aligned_pattern(X, G)                           # stored zeros of G are dropped: set sizes count members only
   if (!is.null(gsetX)) { gsetX <- as.matrix(gsetX[colnames(G), , drop = FALSE]); storage.mode(gsetX) <- "double" }
   bits <- sum(c(one = 1L, two = 2L, lm = 4L)[intersect(tests, c("one", "two", "lm"))])
   .session()
-  r <- .Call("R_plaidhip_plaid_test", X, as.integer(y), pat$Gp, pat$Gi, gsetX, bits,
-             as.integer(metap.method %in% c("stouffer", "sumz")), PACKAGE = "plaidhip")
+  mm <- as.integer(metap.method %in% c("stouffer", "sumz"))
+  r <- if (sparse) .Call("R_plaidhip_plaid_test_csc", X@p, X@i, as.double(X@x), nrow(X), as.integer(y), pat$Gp, pat$Gi,
+                         gsetX, bits, mm, PACKAGE = "plaidhip")
+       else .Call("R_plaidhip_plaid_test", X, as.integer(y), pat$Gp, pat$Gi, gsetX, bits, mm, PACKAGE = "plaidhip")
   keep <- c(TRUE, "one" %in% tests, "two" %in% tests, "lm" %in% tests, TRUE, TRUE)
   res <- r[, keep, drop = FALSE]
   dimnames(res) <- list(colnames(G), c("gsetFC", "p.one", "p.two", "p.lm", "p.meta", "q.meta")[keep])
@@ -313,8 +320,15 @@ replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {
   pat <- .aligned_pattern(X, matG)
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
   .session()
-  D <- as.matrix(X); storage.mode(D) <- "double"
-  S <- .Call("R_plaidhip_gsva", D, pat$Gp, pat$Gi, as.numeric(tau), as.integer(rowtf == "ecdf"), PACKAGE = "plaidhip")
+  if (inherits(X, "CsparseMatrix")) {
+    ## the row statistics are taken from the CSC slots on the device (a row view built there): X stays sparse
+    X <- methods::as(X, "generalMatrix")
+    S <- .Call("R_plaidhip_gsva_csc", X@p, X@i, as.double(X@x), nrow(X), pat$Gp, pat$Gi, as.numeric(tau),
+               as.integer(rowtf == "ecdf"), PACKAGE = "plaidhip")
+  } else {
+    D <- as.matrix(X); storage.mode(D) <- "double"
+    S <- .Call("R_plaidhip_gsva", D, pat$Gp, pat$Gi, as.numeric(tau), as.integer(rowtf == "ecdf"), PACKAGE = "plaidhip")
+  }
   dimnames(S) <- list(colnames(matG), colnames(X))
   S
 }

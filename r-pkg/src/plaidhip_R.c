@@ -307,6 +307,29 @@ SEXP R_plaidhip_gsva(SEXP X, SEXP Gp, SEXP Gi, SEXP tau, SEXP rowtf) {
   return S;
 }
 
+/* the same two calls for a dgCMatrix: its slots, no dense X (plaidhip_plaid_test_csc / plaidhip_gsva_csc) */
+SEXP R_plaidhip_plaid_test_csc(SEXP Xp, SEXP Xi, SEXP Xx, SEXP g, SEXP y, SEXP Gp, SEXP Gi, SEXP gsetX, SEXP tests,
+                               SEXP metap) {
+  const int n = LENGTH(Xp) - 1, m = LENGTH(Gp) - 1;
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 6));
+  int rc = plaidhip_plaid_test_csc(ctx(), INTEGER(Xp), INTEGER(Xi), REAL(Xx), Rf_asInteger(g), n, INTEGER(y), INTEGER(Gp),
+                                   INTEGER(Gi), m, Rf_isNull(gsetX) ? NULL : REAL(gsetX), Rf_asInteger(tests),
+                                   Rf_asInteger(metap), REAL(out));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(1);
+  return out;
+}
+
+SEXP R_plaidhip_gsva_csc(SEXP Xp, SEXP Xi, SEXP Xx, SEXP g, SEXP Gp, SEXP Gi, SEXP tau, SEXP rowtf) {
+  const int n = LENGTH(Xp) - 1, m = LENGTH(Gp) - 1;
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, n));
+  int rc = plaidhip_gsva_csc(ctx(), INTEGER(Xp), INTEGER(Xi), REAL(Xx), Rf_asInteger(g), n, INTEGER(Gp), INTEGER(Gi), m,
+                             Rf_asReal(tau), Rf_asInteger(rowtf), REAL(S));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(1);
+  return S;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -331,6 +354,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gmt2mat_file", (DL_FUNC)&R_plaidhip_gmt2mat_file, 6},
     {"R_plaidhip_plaid_test", (DL_FUNC)&R_plaidhip_plaid_test, 7},
     {"R_plaidhip_gsva", (DL_FUNC)&R_plaidhip_gsva, 5},
+    {"R_plaidhip_plaid_test_csc", (DL_FUNC)&R_plaidhip_plaid_test_csc, 10},
+    {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {
