@@ -386,6 +386,33 @@ int plaidhip_sing_csc_multi(const int* devices, int ndev, const int32_t* Xp, con
 int plaidhip_ssgsea_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                           int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
                           double* S_out);
+/* replaid.ucell / aucell / scse / gsva over several devices: the arguments and results of plaidhip_ucell, plaidhip_aucell,
+ * plaidhip_scse and plaidhip_gsva (rowtf = 0, "z"), X dense or a dgCMatrix as above.  The argument checks run before any
+ * device is touched.  What couples the shards is combined on the host: max(rX) (R/plaid.R:278, 306, 354), the min / max
+ * behind removeLog2 = NULL (:160-161, decided ONCE for the whole matrix; its implicit zeros count), the per-gene mean
+ * and sd of the z row transform (:341-343, g values each), and the medians' flags and mean(medx).
+ * Result contract: for dense X every sharding equals the single-device entry bit for bit, removed_log2 included.
+ * replaid.gsva's row sums are chained: dense X is cut into shards of whole 128-column blocks (per = 128 *
+ * ceil(ceil(n / 128) / ndev) columns, not plaidhip_shard_bounds), and each shard continues the previous shard's running
+ * sums block by block, so the z transform adds exactly what the one-device call adds, in its order.  For a dgCMatrix
+ * the results agree with the single-device entry to the last bits only (the sparse crossprod adds in arrival order,
+ * the rows' moments of stored values are summed per shard) and are deterministic for a given sharding.
+ * Memory per shard (nloc = its columns): ucell / aucell the shard's X and its g x nloc average ranks; scse its X;
+ * gsva two g x nloc buffers (X or zX, ranks), plus, for a dgCMatrix, the shard's slots and their row view; every
+ * method the m x nloc scores.  rowtf = 1 ("ecdf") ranks all samples of a gene together and is not sharded: the call
+ * returns PLAIDHIP_EINVAL (use plaidhip_gsva / plaidhip_gsva_csc on one device).                                   */
+int plaidhip_ucell_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                         int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                         const double* k_full, double rmax, double* S_out);
+int plaidhip_aucell_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                          int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank,
+                          double* S_out);
+int plaidhip_scse_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                        int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int remove_log2,
+                        int score_mean, double* S_out, int* removed_log2);
+int plaidhip_gsva_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                        int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
+                        double* S_out);
 /* precision of the dense crossprod on the library-owned contexts of the *_multi entry points (plaidhip_set_precision's
  * counterpart; default PLAIDHIP_PRECISION_F64) */
 int plaidhip_multi_set_precision(int mode);
@@ -417,8 +444,9 @@ int plaidhip_scse(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const
 /* replaid.gsva(X, matG, tau, rowtf), R/plaid.R:338-363, dense X (a dgCMatrix: plaidhip_gsva_csc
  * below): row transform (rowtf = 0: "z", center + scale per gene; 1: "ecdf", the per-gene empirical
  * CDF), signed average ranks per sample,
- * / max|rank|, sign * |.|^(1 + tau) for tau > 0, then plaid(mean, normalised).  The row transform
- * needs every sample of a gene, so this call does not shard by sample.                           */
+ * / max|rank|, sign * |.|^(1 + tau) for tau > 0, then plaid(mean, normalised).  One device; the
+ * z transform over several devices is plaidhip_gsva_multi (ecdf needs every sample of a gene on one
+ * device and is not sharded).                                                                     */
 int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp,
                   const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out);
 

@@ -325,6 +325,15 @@ int launch_row_group_moments(plaidhip_ctx* ctx, const double* A, int64_t ld, int
                              double* ws);
 int launch_row_ztransform(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t n, const double* d_mean,
                           const double* d_ssd);
+// sample-sharded replaid.gsva (multi.cpp): the block partials of launch_row_group_moments over one shard, their group-0
+// reduction continued from a seed (shards chained in column order reproduce the one-shard sums bit for bit), and the z
+// transform of a shard whose moments were taken over n_total samples
+int launch_row_group_partials(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int32_t* d_y,
+                              const double* d_mean, double* ws);
+int launch_reduce_blocks_seeded(plaidhip_ctx* ctx, const double* ws, int32_t rows, int32_t n, const double* d_seed,
+                                double* d_out);
+int launch_row_ztransform_shard(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,
+                                const double* d_mean, const double* d_ssd);
 int launch_transpose_f64(plaidhip_ctx* ctx, const double* A, int64_t lda, int32_t rows, int32_t cols, double* B,
                          int64_t ldb);
 int launch_fold_change(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, int64_t ld2, double* d_F);
@@ -349,6 +358,14 @@ int launch_row_z_defaults(plaidhip_ctx* ctx, const double* d_mean, const double*
 // when d_mean / d_ssd are given
 int launch_csc_expand(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* vals, int32_t g, int32_t n,
                       int64_t ld, const double* dflt, const double* d_mean, const double* d_ssd, double* out);
+// the same over a column shard (ncols columns) of a matrix of n_total columns: the z transform's sd divides by n_total - 1
+int launch_csc_expand_shard(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* vals, int32_t g,
+                            int32_t ncols, int32_t n_total, int64_t ld, const double* dflt, const double* d_mean,
+                            const double* d_ssd, double* out);
+// the two passes of launch_csr_row_group_moments (one group) apart, over a column shard's rows: d_mean null: the sums of
+// the rows' stored values; else the sums over them of (x - d_mean[row])^2 (the implicit zeros are the caller's)
+int launch_csr_row_stored_moment(plaidhip_ctx* ctx, const int32_t* Rp, const double* Rx, int32_t rows, int32_t max_row_nnz,
+                                 const double* d_mean, double* d_out);
 double onesample_p(double k, double s1, double s2, double* mean_out);
 double twosample_p(double g, double k, double s1, double s2, double tot1, double tot2, double* diff_out);
 double welch_p(double m0, double m1, double ssd0, double ssd1, double n0, double n1);

@@ -212,6 +212,30 @@ csr_row_moments_kernel(const int32_t* __restrict__ Rp, const int32_t* __restrict
   });
 }
 
+// the two passes of csr_row_moments_kernel (every column in group 0) over a column shard, apart: mean == nullptr:
+// out[row] = the sum of the row's stored values; else out[row] = the sum over them of (x - mean[row])^2.  Same lanes and
+// group sums as csr_row_moments_kernel.  The caller adds the shards and the implicit zeros' (n - nnz) mean^2.
+template <int W>
+__global__ void __launch_bounds__(kCsrThreads)
+csr_row_stored_moment_kernel(const int32_t* __restrict__ Rp, const double* __restrict__ Rx, int32_t rows,
+                             const double* __restrict__ mean, double* __restrict__ out) {
+  __shared__ double sh_d[4];
+  for_each_row<W>(Rp, rows, [&](int row, int p0, int len, int lane) {
+    double s = 0.0;
+    if (mean == nullptr) {
+      for (int k = lane; k < len; k += W) s += Rx[p0 + k];
+    } else {
+      const double mu = mean[row];
+      for (int k = lane; k < len; k += W) {
+        const double d = Rx[p0 + k] - mu;
+        s += d * d;
+      }
+    }
+    s = group_sum_f64<W>(s, sh_d);
+    if (lane == 0) out[row] = s;
+  });
+}
+
 // ecdf(x)(x_i) * n = #{x <= x_i} from the max-ranks of the stored values among themselves (Rrank) and the row's
 // z0 = n - nnz implicit zeros, which lie below every stored value >= 0.  Stored values go to out[perm[p]] (CSC order);
 // the implicit zero's value, #{stored <= 0} + z0, to dflt[row].  Integers throughout: exact.
@@ -248,11 +272,13 @@ row_z_default_kernel(const double* __restrict__ mean, const double* __restrict__
 }
 
 // dense column-major out (g x n, leading dimension ld): row i of every column gets dflt[i] (the padding rows 0), then
-// the stored entries their value -- vals[q] itself (ecdf), or its z transform when mean / ssd are given.
-__global__ void __launch_bounds__(kCsrThreads)
-csc_expand_kernel(const int32_t* __restrict__ Xp, const int32_t* __restrict__ Xi, const double* __restrict__ vals,
-                  int32_t g, int32_t n, int64_t ld, const double* __restrict__ dflt, const double* __restrict__ mean,
-                  const double* __restrict__ ssd, double* __restrict__ out) {
+// the stored entries their value -- vals[q] itself (ecdf), or its z transform when mean / ssd are given (moments over
+// n_sd samples: n, or all columns of a sharded X).
+__device__ __forceinline__ void csc_expand_body(const int32_t* __restrict__ Xp, const int32_t* __restrict__ Xi,
+                                                const double* __restrict__ vals, int32_t g, int32_t n, int32_t n_sd,
+                                                int64_t ld, const double* __restrict__ dflt,
+                                                const double* __restrict__ mean, const double* __restrict__ ssd,
+                                                double* __restrict__ out) {
   const int tid = threadIdx.x;
   for (int c = blockIdx.x; c < n; c += gridDim.x) {
     double* oc = out + (int64_t)c * ld;
@@ -261,9 +287,23 @@ csc_expand_kernel(const int32_t* __restrict__ Xp, const int32_t* __restrict__ Xi
     const int q1 = Xp[c + 1];
     for (int q = Xp[c] + tid; q < q1; q += kCsrThreads) {
       const int r = Xi[q];
-      oc[r] = mean != nullptr ? ztransform(vals[q], mean[r], ssd[r], n) : vals[q];
+      oc[r] = mean != nullptr ? ztransform(vals[q], mean[r], ssd[r], n_sd) : vals[q];
     }
   }
+}
+
+__global__ void __launch_bounds__(kCsrThreads)
+csc_expand_kernel(const int32_t* __restrict__ Xp, const int32_t* __restrict__ Xi, const double* __restrict__ vals,
+                  int32_t g, int32_t n, int64_t ld, const double* __restrict__ dflt, const double* __restrict__ mean,
+                  const double* __restrict__ ssd, double* __restrict__ out) {
+  csc_expand_body(Xp, Xi, vals, g, n, n, ld, dflt, mean, ssd, out);
+}
+
+__global__ void __launch_bounds__(kCsrThreads)
+csc_expand_shard_kernel(const int32_t* __restrict__ Xp, const int32_t* __restrict__ Xi, const double* __restrict__ vals,
+                        int32_t g, int32_t ncols, int32_t n_total, int64_t ld, const double* __restrict__ dflt,
+                        const double* __restrict__ mean, const double* __restrict__ ssd, double* __restrict__ out) {
+  csc_expand_body(Xp, Xi, vals, g, ncols, n_total, ld, dflt, mean, ssd, out);
 }
 
 }  // namespace
@@ -308,6 +348,19 @@ int launch_csr_row_group_moments(plaidhip_ctx* ctx, const int32_t* Rp, const int
   return PLAIDHIP_OK;
 }
 
+int launch_csr_row_stored_moment(plaidhip_ctx* ctx, const int32_t* Rp, const double* Rx, int32_t rows, int32_t max_row_nnz,
+                                 const double* d_mean, double* d_out) {
+  if (rows <= 0) return PLAIDHIP_OK;
+  const int rows_per_block = kCsrThreads / 64;
+  hipLaunchKernelGGL(csr_row_stored_moment_kernel<64>, dim3((rows + rows_per_block - 1) / rows_per_block), dim3(kCsrThreads),
+                     0, ctx->stream, Rp, Rx, rows, d_mean, d_out);
+  if (max_row_nnz > kLongRow)
+    hipLaunchKernelGGL(csr_row_stored_moment_kernel<256>, dim3(std::min(rows, 2 * ctx->num_cu)), dim3(kCsrThreads), 0,
+                       ctx->stream, Rp, Rx, rows, d_mean, d_out);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
 int launch_csr_row_ecdf(plaidhip_ctx* ctx, const int32_t* Rp, const double* Rx, int32_t rows, int32_t n,
                         int32_t max_row_nnz, const int32_t* perm, double* Rrank, double* out, double* dflt) {
   if (rows <= 0) return PLAIDHIP_OK;
@@ -339,6 +392,17 @@ int launch_csc_expand(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, c
   const int cap = ctx->num_cu * 8;
   hipLaunchKernelGGL(csc_expand_kernel, dim3(n < cap ? n : cap), dim3(kCsrThreads), 0, ctx->stream, Xp, Xi, vals, g, n, ld,
                      dflt, d_mean, d_ssd, out);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+int launch_csc_expand_shard(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* vals, int32_t g,
+                            int32_t ncols, int32_t n_total, int64_t ld, const double* dflt, const double* d_mean,
+                            const double* d_ssd, double* out) {
+  if (g <= 0 || ncols <= 0) return PLAIDHIP_OK;
+  const int cap = ctx->num_cu * 8;
+  hipLaunchKernelGGL(csc_expand_shard_kernel, dim3(ncols < cap ? ncols : cap), dim3(kCsrThreads), 0, ctx->stream, Xp, Xi, vals,
+                     g, ncols, n_total, ld, dflt, d_mean, d_ssd, out);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

@@ -72,6 +72,20 @@ reduce_blocks_kernel(const double* __restrict__ part, int32_t rows, int32_t nblk
   out[i] = s * (i < rows ? scale0 : scale1);
 }
 
+// out[r] = seed[r] (0 without a seed) + part[0][0][r] + part[1][0][r] + ..., the blocks added in order: group 0 of
+// reduce_blocks_kernel, continued from where the previous column shard stopped.  A sample-sharded caller whose shards
+// start on block boundaries (multiples of kColBlock columns) and that chains them in column order adds exactly what
+// reduce_blocks_kernel adds over all columns, in the same order; the scale step stays with the caller.
+__global__ void __launch_bounds__(256)
+reduce_blocks_seeded_kernel(const double* __restrict__ part, int32_t rows, int32_t nblk, const double* __restrict__ seed,
+                            double* __restrict__ out) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  double s = seed != nullptr ? seed[r] : 0.0;
+  for (int b = 0; b < nblk; ++b) s += part[(int64_t)b * 2 * rows + r];
+  out[r] = s;
+}
+
 // fc = m1 - m0 and fc^2 as the two columns of a rows x 2 matrix with leading dimension ld2
 __global__ void __launch_bounds__(256)
 fold_change_kernel(const double* __restrict__ mean, int32_t rows, int64_t ld2, double* __restrict__ F) {
@@ -82,21 +96,35 @@ fold_change_kernel(const double* __restrict__ mean, int32_t rows, int64_t ld2, d
   F[ld2 + r] = fc * fc;
 }
 
-// replaid.gsva row transform, R/plaid.R:343: z = (x - rowMeans(X)) / (1e-8 + rowSds(X)), in place.
-// mom: [2][rows] group-0 means, ssd: [2][rows] group-0 sums of squared deviations (all samples in group 0)
-__global__ void __launch_bounds__(256)
-row_ztransform_kernel(double* __restrict__ A, int64_t ld, int32_t rows, int32_t n,
-                      const double* __restrict__ mean, const double* __restrict__ ssd) {
+// replaid.gsva row transform, R/plaid.R:343: z = (x - rowMeans(X)) / (1e-8 + rowSds(X)), in place, over the `ncols`
+// columns of A; n_sd: the number of samples the moments were taken over (ncols, or all columns of a sharded X)
+__device__ __forceinline__ void row_ztransform_body(double* __restrict__ A, int64_t ld, int32_t rows, int32_t ncols,
+                                                    int32_t n_sd, const double* __restrict__ mean,
+                                                    const double* __restrict__ ssd) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   const int c0 = blockIdx.y * kColBlock;
-  const int c1 = c0 + kColBlock < n ? c0 + kColBlock : n;
+  const int c1 = c0 + kColBlock < ncols ? c0 + kColBlock : ncols;
   if (r >= rows) return;
   const double mu = mean[r];
-  const double den = 1e-8 + sqrt(ssd[r] / (double)(n - 1));   // sd with n - 1 (NaN for a single sample, as in R)
+  const double den = 1e-8 + sqrt(ssd[r] / (double)(n_sd - 1));   // sd with n - 1 (NaN for a single sample, as in R)
   for (int c = c0; c < c1; ++c) {
     double* p = &A[(int64_t)c * ld + r];
     *p = (*p - mu) / den;   // a true division, as the reference does: ties between genes stay ties
   }
+}
+
+// mom: [2][rows] group-0 means, ssd: [2][rows] group-0 sums of squared deviations (all samples in group 0)
+__global__ void __launch_bounds__(256)
+row_ztransform_kernel(double* __restrict__ A, int64_t ld, int32_t rows, int32_t n,
+                      const double* __restrict__ mean, const double* __restrict__ ssd) {
+  row_ztransform_body(A, ld, rows, n, n, mean, ssd);
+}
+
+// the same on a column shard of X: the sd divides by n_total - 1
+__global__ void __launch_bounds__(256)
+row_ztransform_shard_kernel(double* __restrict__ A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,
+                            const double* __restrict__ mean, const double* __restrict__ ssd) {
+  row_ztransform_body(A, ld, rows, ncols, n_total, mean, ssd);
 }
 
 int launch_row_ztransform(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t n, const double* d_mean,
@@ -105,6 +133,16 @@ int launch_row_ztransform(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows
   const int nblk = (n + kColBlock - 1) / kColBlock;
   hipLaunchKernelGGL(row_ztransform_kernel, dim3((rows + 255) / 256, nblk), dim3(256), 0, ctx->stream, A, ld, rows, n,
                      d_mean, d_ssd);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+int launch_row_ztransform_shard(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,
+                                const double* d_mean, const double* d_ssd) {
+  if (rows == 0 || ncols == 0) return PLAIDHIP_OK;
+  const int nblk = (ncols + kColBlock - 1) / kColBlock;
+  hipLaunchKernelGGL(row_ztransform_shard_kernel, dim3((rows + 255) / 256, nblk), dim3(256), 0, ctx->stream, A, ld, rows,
+                     ncols, n_total, d_mean, d_ssd);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
@@ -170,6 +208,32 @@ int launch_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t
   if (n > 0) hipLaunchKernelGGL(row_group_ssd_kernel, grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_y, d_mean, ws);
   hipLaunchKernelGGL(reduce_blocks_kernel, dim3(red_blocks), dim3(256), 0, ctx->stream, ws, rows, n > 0 ? nblk : 0, 1.0, 1.0,
                      d_ssd);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+// the per-block partials of launch_row_group_moments over one column shard (sums; or, with d_mean, sums of squared
+// deviations from it), left in ws ([nblk][2][rows], nblk = ceil(n / kColBlock))
+int launch_row_group_partials(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int32_t* d_y,
+                              const double* d_mean, double* ws) {
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const dim3 grid((rows + 255) / 256, nblk);
+  if (d_mean == nullptr)
+    hipLaunchKernelGGL(row_group_sums_kernel, grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_y, ws);
+  else
+    hipLaunchKernelGGL(row_group_ssd_kernel, grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_y, d_mean, ws);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+// d_out[r] = d_seed[r] (0 when null) + group 0 of the partials in ws, blocks in order (reduce_blocks_seeded_kernel)
+int launch_reduce_blocks_seeded(plaidhip_ctx* ctx, const double* ws, int32_t rows, int32_t n, const double* d_seed,
+                                double* d_out) {
+  if (rows == 0) return PLAIDHIP_OK;
+  const int nblk = (n + kColBlock - 1) / kColBlock;
+  hipLaunchKernelGGL(reduce_blocks_seeded_kernel, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, ws, rows, nblk, d_seed,
+                     d_out);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

@@ -7,6 +7,8 @@
 // (R/plaid.R:251), min(x) == 0 (R/plaid.R:556-557) and mean(medx) (R/plaid.R:572) -- are combined on the host between
 // the phases.  No RCCL: nothing but those scalars crosses between devices.  (One process per GPU over RCCL is the
 // other form, plaid_amd/sharded.py.)  The single-device entry points run the same code with one shard.
+// replaid.ucell / aucell / scse / gsva (scorer_worker) add their own couplings: the min / max behind removeLog2 = NULL and
+// the per-gene mean and sd of gsva's z transform (g values each, chained from shard to shard for dense X).
 //
 // Uploads are pipelined: R hands over pageable memory, which the HIP runtime copies at ~21 GB/s; staged through
 // pinned buffers by a few feeder threads (memcpy at ~75 GB/s with four threads, tools/ubench/pcie.cpp) the DMA
@@ -276,10 +278,18 @@ struct Shared {
   uint32_t flags[4] = {0, 0, 0, 0};
   std::vector<double> med_all;     // medx of every sample column, global column order (each shard writes its block)
   std::atomic<int> abort{0};
+  // replaid.scse: min / max of X over all shards, in the comparisons of minmax_final_kernel (kernels_norm.hip)
+  double xmin = INFINITY, xmax = -INFINITY;
+  bool removed_log2 = false;
+  // replaid.gsva, dense X: the running row sums (then sums of squared deviations) handed from shard to shard
+  std::vector<double> chain_sum, chain_ssd;
+  // replaid.gsva, dgCMatrix: every shard's row sums of stored values, then of squared deviations, and row lengths
+  std::vector<std::vector<double>> row_sum, row_ssd;
+  std::vector<std::vector<int32_t>> row_len;
 };
 
 struct Call {
-  int method;   // 0 plaid, 1 sing, 2 ssgsea
+  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z)
   const int32_t* Xp;
   const int32_t* Xi;
   const double* X;   // dense values or CSC @x
@@ -290,7 +300,33 @@ struct Call {
   int stat, normalize;
   double alpha;
   double* S_out;
+  // methods 3 - 6: the parameters of the context entries
+  const double* k_full = nullptr;   // ucell: set sizes
+  double rmax = 0.0;                // ucell
+  double auc_max_rank = 0.0;        // aucell
+  int remove_log2 = -1;             // scse: < 0 decided from min / max of X
+  int score_mean = 0;               // scse
+  double tau = 0.0;                 // gsva
+  int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded
+  int* removed_log2 = nullptr;      // scse output (may be null)
 };
+
+// columns [lo, lo + nloc) of shard k.  Dense replaid.gsva cuts at multiples of kColBlock (kernels_stats.hip, 128 columns)
+// so that its chained row reductions add the block partials of the one-device call in the same order; everything else
+// takes plaidhip_shard_bounds.
+void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
+  int64_t lo64 = 0, hi64 = 0;
+  if (c.method == 6 && c.Xp == nullptr) {
+    constexpr int64_t kBlock = 128;
+    const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
+    lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
+    hi64 = std::min<int64_t>(c.n, lo64 + per);
+  } else {
+    plaidhip_shard_bounds(c.n, ndev, k, &lo64, &hi64);
+  }
+  *lo = (int32_t)lo64;
+  *nloc = (int32_t)(hi64 - lo64);
+}
 
 inline int64_t even_ld(int32_t g) { return (int64_t)g + (g & 1); }
 
@@ -549,6 +585,425 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   return rc;
 }
 
+
+// one device's part of a sharded replaid.ucell / aucell / scse / gsva (methods 3 - 6).  The same phases as the context
+// entries (api.cpp: plaidhip_ucell ...), with the quantities that couple the samples combined on the host in between:
+// max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the z
+// row transform (:341-343) and the medians' flags and mean(medx) (:554-575).
+int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  int rc = PLAIDHIP_OK;
+  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
+  auto step = [&](const std::function<int()>& fn) {
+    if (!live()) return;
+    try {
+      rc = fn();
+    } catch (...) {
+      rc = on_exception();
+    }
+    if (rc != PLAIDHIP_OK) sh.abort.store(1);
+  };
+  int32_t lo = 0, nloc = 0;
+  shard_columns(c, ndev, k, &lo, &nloc);
+  const int32_t g = c.g, m = c.m, n = c.n;
+  const bool sparse = c.Xp != nullptr;
+  const int method = c.method;
+  const bool ranked = method == 3 || method == 4;
+  // leading dimension of the staged X and of the ranks: that of the context entry (dense_average_ranks, plaidhip_scse:
+  // g; plaidhip_gsva: even), so that the crossprod sees the same layout
+  const int64_t ld = method == 6 ? even_ld(g) : (int64_t)g;
+  plaidhip_geneset* gs = nullptr;
+  CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dR{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
+  DevBuf dscratch, dcsc, drp, drows, dy, dadd;
+  HomeBuffer home;
+  uint32_t* d_flags = nullptr;
+  double *d_gmax = nullptr, *d_mm = nullptr, *d_med = nullptr, *d_colmax = nullptr, *d_colsum = nullptr;
+  double *d_mean = nullptr, *d_ssd = nullptr, *d_seed = nullptr, *d_run = nullptr;
+  int64_t zx = 0;
+  int32_t max_row = 0;
+  std::vector<int32_t> ploc;
+  const double n_inv = 1.0 / (double)n;   // (the scale of launch_row_group_moments' group 0)
+  // host sources of asynchronous uploads: they live until the worker's last synchronisation
+  std::vector<double> host_mean, host_ssd, row_nnz, add;
+
+  // ---- upload; the per-shard work up to the first coupling ------------------------------------------------------------
+  step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    const size_t nl = (size_t)std::max(nloc, 1);
+    PH_TRY(dsmall.alloc(64 + nl * 24));
+    d_flags = dsmall.as<uint32_t>();
+    d_gmax = reinterpret_cast<double*>(dsmall.as<char>() + 16);
+    d_mm = d_gmax + 1;   // {min, max}
+    d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
+    d_colmax = d_med + nl;
+    d_colsum = d_colmax + nl;
+    PH_HIP(hipMemsetAsync(dsmall.p, 0, 64, ctx->stream));
+    PH_TRY(dS.alloc((size_t)m * nl * 8));
+    if (method == 6) {   // [mean | group 1 (unused) | ssd | seed | running sums], g each
+      PH_TRY(drows.alloc((size_t)g * 5 * 8));
+      d_mean = drows.as<double>();
+      d_ssd = d_mean + 2 * (size_t)g;
+      d_seed = d_ssd + g;
+      d_run = d_seed + g;
+      PH_HIP(hipMemsetAsync(drows.p, 0, (size_t)g * 5 * 8, ctx->stream));
+    }
+    if (nloc == 0) return PLAIDHIP_OK;
+    if (!sparse) {
+      PH_TRY(dX.alloc((size_t)ld * nloc * 8));
+      if (method != 5) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
+      // ucell / aucell: the ranks of a column panel follow its DMA (dense_average_ranks' kernel and arguments)
+      auto on_panel = [&](int64_t c0, int64_t c1) -> int {
+        return launch_colranks_dense_f64(ctx, dX.as<double>() + c0 * ld, ld, g, (int32_t)(c1 - c0), PLAIDHIP_TIES_AVERAGE, 0,
+                                         1.0, dR.as<double>() + c0 * ld, ld, d_colmax + c0);
+      };
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
+                              (size_t)g * 8, nloc, ranked ? std::function<int(int64_t, int64_t)>(on_panel) : nullptr));
+      if (method == 6) {   // zX, step 1: the block partials of the row sums (every sample in group 0)
+        PH_TRY(dy.alloc((size_t)nloc * 4));
+        PH_HIP(hipMemsetAsync(dy.p, 0, (size_t)nloc * 4, ctx->stream));
+        PH_TRY(dscratch.alloc((size_t)row_group_ws_doubles(g, nloc) * 8));
+        PH_TRY(launch_row_group_partials(ctx, dX.as<double>(), ld, g, nloc, dy.as<int32_t>(), nullptr, dscratch.as<double>()));
+      }
+    } else {
+      const int64_t z0 = c.Xp[lo];
+      zx = (int64_t)c.Xp[lo + nloc] - z0;
+      ploc.resize((size_t)nloc + 1);
+      for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
+      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
+      PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
+      double* vals = nullptr;
+      if (method == 6) {
+        PH_TRY(dcsc.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+        vals = dcsc.as<double>();
+      } else {
+        PH_TRY(dX.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+        vals = dX.as<double>();
+      }
+      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
+      PH_TRY(upload_pipelined(ctx, reinterpret_cast<char*>(vals), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
+      if (ranked) {   // dense average ranks, zeros tie (dense_average_ranks' sparse branch)
+        PH_TRY(dR.alloc((size_t)ld * nloc * 8));
+        const int32_t max_nnz = host_max_col_nnz(ploc.data(), nloc);
+        if (max_nnz <= max_sparse_rank_column()) {
+          PH_TRY(dscratch.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+          PH_TRY(launch_colranks_csc_dense_nz_f64(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, max_nnz,
+                                                  PLAIDHIP_TIES_AVERAGE, 0, 1.0, dscratch.as<double>(), dR.as<double>(), ld,
+                                                  d_colmax));
+        } else {
+          PH_TRY(launch_colranks_csc_dense_f64(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, PLAIDHIP_TIES_AVERAGE,
+                                               0, 1.0, dR.as<double>(), ld, d_colmax));
+        }
+      } else if (method == 6) {
+        // the shard's row view, and pass A of its row moments: the sums of the stored values
+        PH_TRY(dX.alloc((size_t)ld * nloc * 8));
+        PH_TRY(dR.alloc((size_t)ld * nloc * 8));
+        PH_TRY(drp.alloc((size_t)(g + 2) * 4));
+        PH_TRY(dscratch.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+        PH_TRY(launch_csc_to_csr(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, drp.as<int32_t>(), nullptr,
+                                 dscratch.as<double>(), nullptr, drp.as<int32_t>() + g + 1));
+        std::vector<int32_t> rp((size_t)g + 2);
+        PH_HIP(hipMemcpyAsync(rp.data(), drp.p, (size_t)(g + 2) * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        max_row = rp[(size_t)g + 1];
+        PH_TRY(launch_csr_row_stored_moment(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, max_row, nullptr, d_run));
+        std::vector<double> sums((size_t)g);
+        std::vector<int32_t> len((size_t)g);
+        for (int32_t i = 0; i < g; ++i) len[(size_t)i] = rp[(size_t)i + 1] - rp[(size_t)i];
+        PH_HIP(hipMemcpyAsync(sums.data(), d_run, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        sh.row_sum[(size_t)k] = std::move(sums);   // (each shard writes its own slot)
+        sh.row_len[(size_t)k] = std::move(len);
+      }
+    }
+    // (the result's pages are made from here on, as in shard_worker)
+    home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
+    return PLAIDHIP_OK;
+  });
+
+  // ---- max over every shard of a device vector (launch_max, whose comparisons are repeated here) -------------------------
+  double gmax = -INFINITY;   // (the host copy of d_gmax: lives until the stream has been synchronised)
+  auto global_max = [&](const double* d_vec) {
+    double mine = -INFINITY;
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_TRY(launch_max(ctx, d_vec, nloc, d_gmax));
+      PH_HIP(hipMemcpyAsync(&mine, d_gmax, 8, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      if (nloc > 0 && rc == PLAIDHIP_OK) {
+        sh.gmax = (sh.gmax_set && !(mine > sh.gmax)) ? sh.gmax : mine;
+        sh.gmax_set = true;
+      }
+    }
+    sh.rv.arrive_and_wait();
+    gmax = sh.gmax_set ? sh.gmax : -INFINITY;
+    step([&]() -> int {   // every shard divides by / subtracts from the same device scalar
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(d_gmax, &gmax, 8, hipMemcpyHostToDevice, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+  };
+
+  // ---- replaid.gsva, z row transform: rowMeans and rowSds of ALL samples -----------------------------------------------
+  if (method == 6 && !sparse) {
+    // chained, ordered reductions: in round r only shard r works, continuing shard r - 1's running sums block by block
+    auto chain = [&](std::vector<double>& run) {
+      for (int r = 0; r < ndev; ++r) {
+        if (r == k)
+          step([&]() -> int {
+            if (nloc == 0) return PLAIDHIP_OK;
+            PH_HIP(hipMemcpyAsync(d_seed, run.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
+            PH_TRY(launch_reduce_blocks_seeded(ctx, dscratch.as<double>(), g, nloc, d_seed, d_run));
+            PH_HIP(hipMemcpyAsync(run.data(), d_run, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
+            PH_HIP(hipStreamSynchronize(ctx->stream));
+            return PLAIDHIP_OK;
+          });
+        sh.rv.arrive_and_wait();
+      }
+    };
+    chain(sh.chain_sum);
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      host_mean.resize((size_t)g);
+      for (int32_t i = 0; i < g; ++i) host_mean[(size_t)i] = sh.chain_sum[(size_t)i] * n_inv;   // reduce_blocks_kernel's scale
+      PH_HIP(hipMemcpyAsync(d_mean, host_mean.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
+      return launch_row_group_partials(ctx, dX.as<double>(), ld, g, nloc, dy.as<int32_t>(), d_mean, dscratch.as<double>());
+    });
+    chain(sh.chain_ssd);
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(d_ssd, sh.chain_ssd.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(launch_row_ztransform_shard(ctx, dX.as<double>(), ld, g, nloc, n, d_mean, d_ssd));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+  } else if (method == 6) {
+    // dgCMatrix: the shards' sums of stored values added in shard order, mean = s / n; then the same for the squared
+    // deviations, plus (n - nnz) mean^2 for the implicit zeros, once (csr_row_moments_kernel's expression)
+    host_mean.assign((size_t)g, 0.0);
+    host_ssd.assign((size_t)g, 0.0);
+    row_nnz.assign((size_t)g, 0.0);
+    sh.rv.arrive_and_wait();
+    if (live()) {
+      for (int32_t i = 0; i < g; ++i) {
+        double s = 0.0, z = 0.0;
+        for (int q = 0; q < ndev; ++q)
+          if (!sh.row_sum[(size_t)q].empty()) { s += sh.row_sum[(size_t)q][(size_t)i]; z += sh.row_len[(size_t)q][(size_t)i]; }
+        host_mean[(size_t)i] = s / (double)n;
+        row_nnz[(size_t)i] = z;
+      }
+    }
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(d_mean, host_mean.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(launch_csr_row_stored_moment(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, max_row, d_mean, d_run));
+      std::vector<double> q((size_t)g);
+      PH_HIP(hipMemcpyAsync(q.data(), d_run, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      sh.row_ssd[(size_t)k] = std::move(q);
+      return PLAIDHIP_OK;
+    });
+    sh.rv.arrive_and_wait();
+    if (live()) {
+      for (int32_t i = 0; i < g; ++i) {
+        double q = 0.0;
+        for (int s = 0; s < ndev; ++s)
+          if (!sh.row_ssd[(size_t)s].empty()) q += sh.row_ssd[(size_t)s][(size_t)i];
+        const double mu = host_mean[(size_t)i], z = (double)n - row_nnz[(size_t)i];
+        host_ssd[(size_t)i] = z > 0.0 ? q + z * (mu * mu) : q;
+      }
+    }
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(d_ssd, host_ssd.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
+      double* dflt = d_seed;
+      PH_TRY(launch_row_z_defaults(ctx, d_mean, d_ssd, g, n, dflt));   // (n: the sd's divisor alone)
+      PH_TRY(launch_csc_expand_shard(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), dcsc.as<double>(), g, nloc, n, ld, dflt, d_mean,
+                                     d_ssd, dX.as<double>()));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+  }
+  if (method == 6) {
+    // rX = colranks(zX, signed = TRUE, "average"), |rX|^(1 + tau) fused (gsva_scores, api.cpp)
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      return launch_colranks_dense_f64(ctx, dX.as<double>(), ld, g, nloc, PLAIDHIP_TIES_AVERAGE, 1,
+                                       c.tau > 0.0 ? 1.0 + c.tau : 1.0, dR.as<double>(), ld, d_colmax);
+    });
+  }
+
+  // ---- max(rX) (ucell / aucell: R/plaid.R:278, 306; gsva: max|rX|, :354) --------------------------------------------------
+  if (method != 5) global_max(d_colmax);
+  if (ranked)
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      return method == 3 ? launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 0, c.rmax + 1.0, d_gmax)      // :278
+                         : launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 1, c.auc_max_rank, d_gmax);   // :306
+    });
+
+  // ---- replaid.scse: removeLog2 = NULL decided once, from min / max of the whole matrix (R/plaid.R:160-161) -------------
+  bool remove_log2 = c.remove_log2 > 0;
+  if (method == 5 && c.remove_log2 < 0) {
+    double mm[2] = {INFINITY, -INFINITY};
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_TRY(launch_minmax(ctx, dX.as<double>(), sparse ? zx : (int64_t)g * nloc, d_mm));
+      PH_HIP(hipMemcpyAsync(mm, d_mm, 16, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      if (rc == PLAIDHIP_OK) {
+        sh.xmin = mm[0] < sh.xmin ? mm[0] : sh.xmin;
+        sh.xmax = mm[1] > sh.xmax ? mm[1] : sh.xmax;
+      }
+    }
+    sh.rv.arrive_and_wait();
+    double mn = sh.xmin, mx = sh.xmax;
+    if (sparse && (int64_t)c.Xp[n] < (int64_t)g * n) { mn = mn < 0.0 ? mn : 0.0; mx = mx > 0.0 ? mx : 0.0; }   // implicit zeros
+    remove_log2 = mn == 0.0 && mx < 20.0;
+  }
+  if (method == 5) {
+    if (k == 0) sh.removed_log2 = remove_log2;
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      if (remove_log2) PH_TRY(launch_map(ctx, dX.as<double>(), sparse ? zx : (int64_t)g * nloc, sparse ? 3 : 2, 0.0, nullptr));
+      return launch_col_abs_sums(ctx, dX.as<double>(), ld, g, sparse ? dXp.as<int32_t>() : nullptr, nloc, d_colsum);
+    });
+  }
+
+  // ---- crossprod --------------------------------------------------------------------------------------------------------
+  step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nloc == 0) return PLAIDHIP_OK;
+    if (method == 5) {
+      const int stat = c.score_mean ? PLAIDHIP_STAT_MEAN : PLAIDHIP_STAT_SUM;
+      if (sparse) {   // the kernel is chosen from the density of the whole matrix, as in shard_worker
+        const int64_t nnz_choice = (int64_t)((double)c.Xp[n] / (double)n * (double)nloc);
+        return launch_spmm_csc_f64(ctx, gs, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), nloc, nnz_choice, stat, 1.0,
+                                   nullptr, 0.0, dS.as<double>(), m, nullptr);
+      }
+      return launch_spmm_dense_f64(ctx, gs, dX.as<double>(), ld, nloc, stat, 1.0, nullptr, 0.0, dS.as<double>(), m, nullptr);
+    }
+    int x_kind = PLAIDHIP_X_ANY;
+    if (method == 3) {   // pmin(max(rX) - rX, rmax + 1) of average ranks: half-integers when rmax + 1 is one
+      const double cap2 = 2.0 * (c.rmax + 1.0);
+      x_kind = (cap2 == std::floor(cap2) && cap2 < 65536.0) ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
+    }
+    if (method == 6) x_kind = c.tau > 0.0 ? PLAIDHIP_X_ANY : PLAIDHIP_X_EXACT_F32;   // signed average ranks
+    return launch_spmm_dense_f64(ctx, gs, dR.as<double>(), ld, nloc, PLAIDHIP_STAT_MEAN, 1.0, method == 6 ? d_gmax : nullptr,
+                                 0.0, dS.as<double>(), m, d_flags, x_kind);
+  });
+
+  // ---- normalize_medians (R/plaid.R:554-575), as shard_worker: flags, medians, mean(medx) in the device's order -----------
+  if (method != 5) {
+    uint32_t fl[4] = {0, 0, 0, 0};
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(fl, d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      for (int q = 0; q < 4; ++q) sh.flags[q] |= fl[q];
+    }
+    sh.rv.arrive_and_wait();
+    const int ignore_zero = (sh.flags[1] != 0 && sh.flags[0] == 0) ? 1 : 0;
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, nloc, ignore_zero, nullptr, d_med));
+      PH_HIP(hipMemcpyAsync(sh.med_all.data() + lo, d_med, (size_t)nloc * 8, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    sh.rv.arrive_and_wait();
+    const double mean_med = live() ? mean_like_device_sum(sh.med_all.data(), n) : 0.0;
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      return launch_shift_columns(ctx, dS.as<double>(), m, m, nloc, d_med, mean_med, nullptr);
+    });
+  }
+
+  // ---- the affine steps of the context entries ----------------------------------------------------------------------------
+  step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    if (method == 3) {   // 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:280)
+      add.resize((size_t)m);
+      for (int32_t j = 0; j < m; ++j) add[(size_t)j] = 1.0 + (c.k_full[j] + 1.0) / (2.0 * c.rmax);
+      PH_TRY(dadd.alloc((size_t)m * 8));
+      PH_HIP(hipMemcpyAsync(dadd.p, add.data(), (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+      return launch_affine(ctx, dS.as<double>(), m, m, nloc, -1.0 / c.rmax, nullptr, 1.0, dadd.as<double>(), 0.0);
+    }
+    if (method == 5)   // mean: sX / (colMeans|X| + 1e-8) (:176-177); sum: sX / (colSums|X| + 1e-8) * 100 (:181-182)
+      return launch_affine(ctx, dS.as<double>(), m, m, nloc, c.score_mean ? 1.0 : 100.0, d_colsum,
+                           c.score_mean ? 1.0 / (double)g : 1.0, nullptr, 0.0);
+    return PLAIDHIP_OK;
+  });
+
+  // ---- the score shard goes home ----------------------------------------------------------------------------------------
+  step([&]() -> int {
+    if (nloc > 0) PH_TRY(home.copy(ctx, dS.p));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
+    hipStreamSynchronize(ctx->stream);
+    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
+  }
+  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
+// every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
+int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
+  Shared sh(ndev);
+  sh.med_all.assign((size_t)c.n, 0.0);
+  if (c.method == 6) {
+    sh.chain_sum.assign((size_t)c.g, 0.0);
+    sh.chain_ssd.assign((size_t)c.g, 0.0);
+    sh.row_sum.resize((size_t)ndev);
+    sh.row_ssd.resize((size_t)ndev);
+    sh.row_len.resize((size_t)ndev);
+  }
+  auto worker = [&](int k) {
+    return c.method <= 2 ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
+  };
+  int rc = PLAIDHIP_OK;
+  if (ndev == 1) {
+    rc = worker(0);
+  } else {
+    std::vector<int> rcs((size_t)ndev, PLAIDHIP_OK);
+    std::vector<std::string> errs((size_t)ndev);
+    std::vector<std::thread> th;
+    for (int k = 0; k < ndev; ++k)
+      th.emplace_back([&, k] {
+        rcs[(size_t)k] = worker(k);
+        if (rcs[(size_t)k] != PLAIDHIP_OK) errs[(size_t)k] = last_error_cstr();   // the worker's thread-local text
+      });
+    for (auto& t : th) t.join();
+    // report the failure that started it (the others only say "another shard failed")
+    for (int k = 0; k < ndev; ++k)
+      if (rcs[(size_t)k] != PLAIDHIP_OK && !errs[(size_t)k].empty()) {
+        rc = rcs[(size_t)k];
+        set_error("device %d: %s", ctxs[k]->device, errs[(size_t)k].c_str());
+        break;
+      }
+    if (rc == PLAIDHIP_OK)
+      for (int k = 0; k < ndev; ++k)
+        if (rcs[(size_t)k] != PLAIDHIP_OK) { rc = rcs[(size_t)k]; set_error("a device shard failed"); break; }
+  }
+  if (rc == PLAIDHIP_OK && c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = sh.removed_log2 ? 1 : 0;
+  return rc;
+}
+
 }  // namespace
 
 namespace plaidhip {
@@ -570,30 +1025,7 @@ int run_sharded(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* 
   PH_REQUIRE(S_out != nullptr, "null S_out");
   if (Xp != nullptr) PH_TRY(check_host_csc(Xp, Xi, g, n));
   Call c{method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, stat, normalize, alpha, S_out};
-  Shared sh(ndev);
-  sh.med_all.assign((size_t)n, 0.0);
-  if (ndev == 1) return shard_worker(ctxs[0], c, 1, 0, sh);
-  std::vector<int> rcs((size_t)ndev, PLAIDHIP_OK);
-  std::vector<std::string> errs((size_t)ndev);
-  std::vector<std::thread> th;
-  for (int k = 0; k < ndev; ++k)
-    th.emplace_back([&, k] {
-      rcs[(size_t)k] = shard_worker(ctxs[k], c, ndev, k, sh);
-      if (rcs[(size_t)k] != PLAIDHIP_OK) errs[(size_t)k] = last_error_cstr();   // the worker's thread-local text
-    });
-  for (auto& t : th) t.join();
-  // report the failure that started it (the others only say "another shard failed")
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < ndev; ++k)
-    if (rcs[(size_t)k] != PLAIDHIP_OK && !errs[(size_t)k].empty()) {
-      rc = rcs[(size_t)k];
-      set_error("device %d: %s", ctxs[k]->device, errs[(size_t)k].c_str());
-      break;
-    }
-  if (rc == PLAIDHIP_OK)
-    for (int k = 0; k < ndev; ++k)
-      if (rcs[(size_t)k] != PLAIDHIP_OK) { rc = rcs[(size_t)k]; set_error("a device shard failed"); break; }
-  return rc;
+  return run_call(ctxs, ndev, c);
 }
 
 }  // namespace plaidhip
@@ -623,6 +1055,47 @@ int multi_contexts(const int* devices, int ndev, std::vector<plaidhip_ctx*>& out
   return PLAIDHIP_OK;
 }
 
+// the argument checks of the context entries (api.cpp: plaidhip_ucell ...), before any device is touched
+int check_scorer_call(const Call& c) {
+  if (c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = c.remove_log2 > 0 ? 1 : 0;
+  PH_REQUIRE(c.method >= 3 && c.method <= 6, "sharded scorer: bad method %d", c.method);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  if (c.method == 3) PH_REQUIRE(c.rmax > 0, "ucell_multi: rmax must be positive");
+  if (c.method == 4) PH_REQUIRE(c.auc_max_rank > 0, "aucell_multi: aucMaxRank must be positive");
+  if (c.method == 6) {
+    PH_REQUIRE(c.rowtf == 0 || c.rowtf == 1, "Error: unknown row transform %d", c.rowtf);              // R/plaid.R:348
+    PH_REQUIRE(c.rowtf == 0, "gsva_multi: rowtf = \"ecdf\" ranks all samples of a gene together and is not sharded by "
+                             "sample; score it on one device (plaidhip_gsva / plaidhip_gsva_csc)");
+  }
+  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "null X");
+  PH_REQUIRE(c.S_out != nullptr, "null S_out");
+  if (c.method == 3) PH_REQUIRE(c.k_full != nullptr, "ucell_multi: null k_full");
+  if (c.Xp != nullptr) {
+    PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
+    PH_REQUIRE(c.Xp[c.n] == 0 || c.Xi != nullptr, "null Xi");
+    // (as plaidhip_gsva_csc: the row view's buffers hold at most g x n values)
+    if (c.method == 6)
+      PH_REQUIRE((int64_t)c.Xp[c.n] <= (int64_t)c.g * c.n, "gsva_multi: %d stored values in a %d x %d matrix (repeated row "
+                 "indices?)", c.Xp[c.n], c.g, c.n);
+  }
+  return PLAIDHIP_OK;
+}
+
+Call scorer_call(int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                 const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) {
+  return Call{method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, S_out};
+}
+
+// checks, then the contexts of `devices`, then the sharded call
+int run_scorer_multi(const int* devices, int ndev, const Call& c) {
+  PH_TRY(check_scorer_call(c));
+  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_call(ctxs.data(), ndev, c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -646,6 +1119,41 @@ int plaidhip_debug_sharded_on_one_device(int device, int nshards, int fail_shard
   const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
   for (plaidhip_ctx* c : ctxs)
     if (c) plaidhip_finalize(c);
+  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
+  return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h): plaidhip_{ucell,aucell,scse,gsva}_multi's engine with `nshards` contexts on
+// ONE device.  method 3 ucell (k_full, rmax), 4 aucell (auc_max_rank), 5 scse (remove_log2, score_mean, removed_log2),
+// 6 gsva (tau, rowtf); the parameters a method does not take are ignored.  fail_shard >= 0: that shard fails in its
+// crossprod phase.
+int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
+                                                const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full,
+                                                double rmax, double auc_max_rank, int remove_log2, int score_mean, double tau,
+                                                int rowtf, double* S_out, int* removed_log2) try {
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_scorer_sharded: nshards = %d", nshards);
+  Call c = scorer_call(method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
+  c.k_full = k_full;
+  c.rmax = rmax;
+  c.auc_max_rank = auc_max_rank;
+  c.remove_log2 = remove_log2;
+  c.score_mean = score_mean;
+  c.tau = tau;
+  c.rowtf = rowtf;
+  c.removed_log2 = removed_log2;
+  PH_TRY(check_scorer_call(c));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
+  int rc = PLAIDHIP_OK;
+  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
+    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
+    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
+  }
+  if (rc == PLAIDHIP_OK) rc = run_call(ctxs.data(), nshards, c);
+  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
+  for (plaidhip_ctx* cx : ctxs)
+    if (cx) plaidhip_finalize(cx);
   if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
   return rc;
 } catch (...) { return plaidhip::on_exception(); }
@@ -692,6 +1200,40 @@ int plaidhip_ssgsea_multi(const int* devices, int ndev, const int32_t* Xp, const
   std::vector<plaidhip_ctx*> ctxs;
   PH_TRY(multi_contexts(devices, ndev, ctxs));
   return run_sharded(ctxs.data(), ndev, 2, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, alpha, S_out);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_ucell_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                         int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full, double rmax,
+                         double* S_out) try {
+  Call c = scorer_call(3, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
+  c.k_full = k_full;
+  c.rmax = rmax;
+  return run_scorer_multi(devices, ndev, c);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_aucell_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                          int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank, double* S_out) try {
+  Call c = scorer_call(4, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
+  c.auc_max_rank = auc_max_rank;
+  return run_scorer_multi(devices, ndev, c);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_scse_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                        int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int remove_log2, int score_mean,
+                        double* S_out, int* removed_log2) try {
+  Call c = scorer_call(5, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
+  c.remove_log2 = remove_log2;
+  c.score_mean = score_mean;
+  c.removed_log2 = removed_log2;
+  return run_scorer_multi(devices, ndev, c);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsva_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                        int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out) try {
+  Call c = scorer_call(6, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
+  c.tau = tau;
+  c.rowtf = rowtf;
+  return run_scorer_multi(devices, ndev, c);
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -598,5 +598,63 @@ def ssgsea_multi(X, Gp, Gi, alpha=0.0, devices=1) -> np.ndarray:
     return S
 
 
+def ucell_multi(X, Gp, Gi, k_full, rmax=1500.0, devices=1) -> np.ndarray:
+    """replaid.ucell (Context.ucell) with the sample columns sharded over `devices`"""
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    kf = np.ascontiguousarray(k_full, dtype=np.float64)
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_ucell_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(kf), float(rmax),
+                                   _np_ptr(S)))
+    return S
+
+
+def aucell_multi(X, Gp, Gi, auc_max_rank, devices=1) -> np.ndarray:
+    """replaid.aucell (Context.aucell) with the sample columns sharded over `devices`"""
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_aucell_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(auc_max_rank), _np_ptr(S)))
+    return S
+
+
+def scse_multi(X, Gp, Gi, remove_log2=None, score_mean=False, devices=1):
+    """replaid.scse (Context.scse) with the sample columns sharded over `devices`: (S, removed_log2), the second
+    telling whether the 2 ** x transform ran (removeLog2 = NULL is decided once, for the whole matrix)"""
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    rl = -1 if remove_log2 is None else int(bool(remove_log2))
+    removed = C.c_int(0)
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_scse_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, rl, int(bool(score_mean)),
+                                  _np_ptr(S), C.byref(removed)))
+    return S, bool(removed.value)
+
+
+def gsva_multi(X, Gp, Gi, tau=0.0, rowtf="z", devices=1) -> np.ndarray:
+    """replaid.gsva (Context.gsva / gsva_csc) with the sample columns sharded over `devices`; rowtf "z" only -- "ecdf"
+    ranks all samples of a gene together and is refused (score it on one device)"""
+    if rowtf not in ("z", "ecdf"):
+        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_gsva_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(tau),
+                                  0 if rowtf == "z" else 1, _np_ptr(S)))
+    return S
+
+
 def multi_finalize():
     check(_lib.load().plaidhip_multi_finalize())

@@ -8,9 +8,11 @@
 ##   plaidhip.device     integer, the GPU ordinal the session context lives on (default 0; read when the
 ##                       context is first created)
 ##   plaidhip.devices    integer vector of GPU ordinals: with more than one, plaid() / replaid.sing() /
-##                       replaid.ssgsea() shard the sample columns over them (a host thread per device inside
-##                       the library, no process per GPU); one ordinal: that GPU is the session device; default: the
-##                       session device alone.  plaidhip.precision applies to every device of the list.
+##                       replaid.ssgsea() / replaid.ucell() / replaid.aucell() / replaid.scse() / replaid.gsva()
+##                       shard the sample columns over them (a host thread per device inside the library, no process
+##                       per GPU); replaid.gsva(rowtf = "ecdf") ranks all samples of a gene together and stays on the
+##                       session device.  One ordinal: that GPU is the session device; default: the session device
+##                       alone.  plaidhip.precision applies to every device of the list.
 ##   plaidhip.precision  "f64" (default: scores equal to the last bits) or "mixed" (dense crossprod stages the
 ##                       sample columns as fp32, sums fp64; ~1e-7 relative, inside the 1e-5 bar; ~1.5x faster)
 ## a single ordinal in plaidhip.devices IS the session device (it used to be ignored in favour of plaidhip.device)
@@ -226,8 +228,12 @@ replaid.ucell <- function(X, matG, rmax = 1500) {
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
   .session()
   xa <- .x_args(X)
-  S <- .Call("R_plaidhip_ucell", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi,
-             as.double(Matrix::colSums(matG != 0)), as.double(rmax), PACKAGE = "plaidhip")
+  kfull <- as.double(Matrix::colSums(matG != 0))
+  dev <- .devices()
+  S <- if (length(dev) > 1L) .Call("R_plaidhip_ucell_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp,
+                                   pat$Gi, kfull, as.double(rmax), PACKAGE = "plaidhip")
+       else .Call("R_plaidhip_ucell", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, kfull, as.double(rmax),
+                  PACKAGE = "plaidhip")
   dimnames(S) <- list(colnames(matG), colnames(X))
   S
 }
@@ -237,8 +243,11 @@ replaid.aucell <- function(X, matG, aucMaxRank = ceiling(0.05 * nrow(X))) {
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
   .session()
   xa <- .x_args(X)
-  S <- .Call("R_plaidhip_aucell", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi,
-             as.double(aucMaxRank), PACKAGE = "plaidhip")
+  dev <- .devices()
+  S <- if (length(dev) > 1L) .Call("R_plaidhip_aucell_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp,
+                                   pat$Gi, as.double(aucMaxRank), PACKAGE = "plaidhip")
+       else .Call("R_plaidhip_aucell", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, as.double(aucMaxRank),
+                  PACKAGE = "plaidhip")
   dimnames(S) <- list(colnames(matG), colnames(X))
   S
 }
@@ -248,9 +257,12 @@ replaid.scse <- function(X, matG, removeLog2 = NULL, scoreMean = FALSE) {
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
   .session()
   xa <- .x_args(X)
-  S <- .Call("R_plaidhip_scse", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi,
-             if (is.null(removeLog2)) NA else as.logical(removeLog2), as.logical(scoreMean),
-             PACKAGE = "plaidhip")
+  rl <- if (is.null(removeLog2)) NA else as.logical(removeLog2)
+  dev <- .devices()
+  S <- if (length(dev) > 1L) .Call("R_plaidhip_scse_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp,
+                                   pat$Gi, rl, as.logical(scoreMean), PACKAGE = "plaidhip")
+       else .Call("R_plaidhip_scse", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, rl, as.logical(scoreMean),
+                  PACKAGE = "plaidhip")
   if (isTRUE(attr(S, "removedLog2")))   ## R/plaid.R:163-164 (the NULL case is decided on the device)
     message("[replaid.scse] Converting data to linear scale (removing log2)...")
   attr(S, "removedLog2") <- NULL
@@ -320,7 +332,15 @@ replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {
   pat <- .aligned_pattern(X, matG)
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
   .session()
-  if (inherits(X, "CsparseMatrix")) {
+  dev <- .devices()
+  if (length(dev) > 1L && rowtf != "ecdf") {
+    ## sample shards over several GPUs (the per-gene mean and sd are combined across them); "ecdf" needs every
+    ## sample of a gene on one device and takes the single-device route below
+    if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
+    xa <- .x_args(X)
+    S <- .Call("R_plaidhip_gsva_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, as.numeric(tau),
+               0L, PACKAGE = "plaidhip")
+  } else if (inherits(X, "CsparseMatrix")) {
     ## the row statistics are taken from the CSC slots on the device (a row view built there): X stays sparse
     X <- methods::as(X, "generalMatrix")
     S <- .Call("R_plaidhip_gsva_csc", X@p, X@i, as.double(X@x), nrow(X), pat$Gp, pat$Gi, as.numeric(tau),

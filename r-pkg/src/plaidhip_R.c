@@ -194,6 +194,48 @@ SEXP R_plaidhip_ssgsea_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SE
   return S;
 }
 
+SEXP R_plaidhip_ucell_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP kfull,
+                            SEXP rmax) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_ucell_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g),
+                             nn, INTEGER(Gp), INTEGER(Gi), m, REAL(kfull), Rf_asReal(rmax), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
+SEXP R_plaidhip_aucell_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP auc_max_rank) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_aucell_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                              Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(auc_max_rank), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
+SEXP R_plaidhip_scse_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP remove_log2,
+                           SEXP score_mean) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  const int rl = Rf_asLogical(remove_log2);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  int removed = 0;
+  check(plaidhip_scse_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g),
+                            nn, INTEGER(Gp), INTEGER(Gi), m, rl == NA_LOGICAL ? -1 : rl, Rf_asLogical(score_mean), REAL(S),
+                            &removed));
+  Rf_setAttrib(S, Rf_install("removedLog2"), Rf_ScalarLogical(removed));   /* as R_plaidhip_scse */
+  UNPROTECT(1);
+  return S;
+}
+
+SEXP R_plaidhip_gsva_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP tau, SEXP rowtf) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_gsva_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g),
+                            nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(tau), Rf_asInteger(rowtf), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
 SEXP R_plaidhip_ucell(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP kfull, SEXP rmax) {
   const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
   SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
@@ -348,6 +390,10 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_sing_dense", (DL_FUNC)&R_plaidhip_sing_dense, 3},
     {"R_plaidhip_ssgsea_dense", (DL_FUNC)&R_plaidhip_ssgsea_dense, 4},
     {"R_plaidhip_ssgsea_csc", (DL_FUNC)&R_plaidhip_ssgsea_csc, 7},
+    {"R_plaidhip_ucell_multi", (DL_FUNC)&R_plaidhip_ucell_multi, 10},
+    {"R_plaidhip_aucell_multi", (DL_FUNC)&R_plaidhip_aucell_multi, 9},
+    {"R_plaidhip_scse_multi", (DL_FUNC)&R_plaidhip_scse_multi, 10},
+    {"R_plaidhip_gsva_multi", (DL_FUNC)&R_plaidhip_gsva_multi, 10},
     {"R_plaidhip_ucell", (DL_FUNC)&R_plaidhip_ucell, 9},
     {"R_plaidhip_aucell", (DL_FUNC)&R_plaidhip_aucell, 8},
     {"R_plaidhip_scse", (DL_FUNC)&R_plaidhip_scse, 9},
