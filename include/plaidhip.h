@@ -413,6 +413,23 @@ int plaidhip_scse_multi(const int* devices, int ndev, const int32_t* Xp, const i
 int plaidhip_gsva_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                         int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
                         double* S_out);
+/* plaid.test over several devices: the arguments, checks, error messages and `out` of plaidhip_plaid_test (X dense,
+ * Xp == NULL) and plaidhip_plaid_test_csc (a dgCMatrix: Xp, Xi, X_or_x = @x), y / tests / metap_method / gsetX as there.
+ * The checks run before any device is touched.  The shards are cut at whole 128-column blocks (as dense gsva above).
+ * Everything plaid.test reduces is a row sum over the samples, so the scores never leave their devices and only
+ * O(genes + sets) numbers cross between the shards: the two group sums of X (dense: chained from shard to shard in the
+ * one-device block order; a dgCMatrix: each shard's stored values per group, added on the host in shard order), then on
+ * shard 0 alone fc, fc^2 and Gt [fc, fc^2]; then the medians' flags and mean(medx) of plaid(X, G) (gsetX == NULL), and
+ * the chained group sums and sums of squared deviations of the score rows, which are normalised on load (the shifted
+ * scores are never written).  The p-values are computed on the host from those.
+ * Result contract: for dense X every sharding equals plaidhip_plaid_test bit for bit, NaNs included, with or without
+ * gsetX, for every `tests` and both metap_method values; for a dgCMatrix the sums are added in another order and the
+ * result agrees with plaidhip_plaid_test_csc to ~1e-9 relative.
+ * Memory per shard (nloc = its columns): dense X g x nloc, or the shard's slots and their row view; with "lm" the
+ * m x nloc scores; O(g + m) besides.  No shard holds X and S of all samples.                                       */
+int plaidhip_plaid_test_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                              const double* gsetX, int tests, int metap_method, double* out);
 /* precision of the dense crossprod on the library-owned contexts of the *_multi entry points (plaidhip_set_precision's
  * counterpart; default PLAIDHIP_PRECISION_F64) */
 int plaidhip_multi_set_precision(int mode);

@@ -334,6 +334,11 @@ int launch_reduce_blocks_seeded(plaidhip_ctx* ctx, const double* ws, int32_t row
                                 double* d_out);
 int launch_row_ztransform_shard(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,
                                 const double* d_mean, const double* d_ssd);
+// sample-sharded plaid.test (multi.cpp): launch_row_group_partials over a raw score shard with normalize_medians' shift
+// (S - d_med[c]) + add applied on load (d_med null: no shift); the shifted scores are not written
+int launch_row_group_shifted_partials(plaidhip_ctx* ctx, const double* S, int64_t ld, int32_t rows, int32_t n,
+                                      const int32_t* d_y, const double* d_med, double add, const double* d_mean,
+                                      double* ws);
 int launch_transpose_f64(plaidhip_ctx* ctx, const double* A, int64_t lda, int32_t rows, int32_t cols, double* B,
                          int64_t ldb);
 int launch_fold_change(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, int64_t ld2, double* d_F);
@@ -366,6 +371,10 @@ int launch_csc_expand_shard(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t*
 // the rows' stored values; else the sums over them of (x - d_mean[row])^2 (the implicit zeros are the caller's)
 int launch_csr_row_stored_moment(plaidhip_ctx* ctx, const int32_t* Rp, const double* Rx, int32_t rows, int32_t max_row_nnz,
                                  const double* d_mean, double* d_out);
+// sample-sharded plaid.test on a dgCMatrix: d_out[k][row] = the unscaled sum of the row's stored values in group k
+// (d_y indexed by Rj, the shard's column); the caller adds the shards and divides by the global group sizes
+int launch_csr_row_group_stored_sums(plaidhip_ctx* ctx, const int32_t* Rp, const int32_t* Rj, const double* Rx, int32_t rows,
+                                     int32_t max_row_nnz, const int32_t* d_y, double* d_out);
 double onesample_p(double k, double s1, double s2, double* mean_out);
 double twosample_p(double g, double k, double s1, double s2, double tot1, double tot2, double* diff_out);
 double welch_p(double m0, double m1, double ssd0, double ssd1, double n0, double n1);

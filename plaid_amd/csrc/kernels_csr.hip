@@ -236,6 +236,32 @@ csr_row_stored_moment_kernel(const int32_t* __restrict__ Rp, const double* __res
   });
 }
 
+// the unscaled first pass of csr_row_moments_kernel over a column shard's rows: out[k][row] = the sum of the row's stored
+// values in group k (y looked up through Rj, the shard's own column index).  Same lanes and group sums; the caller adds
+// the shards and divides by the global group sizes.
+template <int W>
+__global__ void __launch_bounds__(kCsrThreads)
+csr_row_group_stored_sums_kernel(const int32_t* __restrict__ Rp, const int32_t* __restrict__ Rj,
+                                 const double* __restrict__ Rx, int32_t rows, const int32_t* __restrict__ y,
+                                 double* __restrict__ out) {
+  __shared__ double sh_d[4];
+  for_each_row<W>(Rp, rows, [&](int row, int p0, int len, int lane) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = lane; k < len; k += W) {
+      const double v = Rx[p0 + k];
+      const int lab = y[Rj[p0 + k]];
+      s0 += lab == 0 ? v : 0.0;
+      s1 += lab == 1 ? v : 0.0;
+    }
+    s0 = group_sum_f64<W>(s0, sh_d);
+    s1 = group_sum_f64<W>(s1, sh_d);
+    if (lane == 0) {
+      out[row] = s0;
+      out[rows + row] = s1;
+    }
+  });
+}
+
 // ecdf(x)(x_i) * n = #{x <= x_i} from the max-ranks of the stored values among themselves (Rrank) and the row's
 // z0 = n - nnz implicit zeros, which lie below every stored value >= 0.  Stored values go to out[perm[p]] (CSC order);
 // the implicit zero's value, #{stored <= 0} + z0, to dflt[row].  Integers throughout: exact.
@@ -357,6 +383,19 @@ int launch_csr_row_stored_moment(plaidhip_ctx* ctx, const int32_t* Rp, const dou
   if (max_row_nnz > kLongRow)
     hipLaunchKernelGGL(csr_row_stored_moment_kernel<256>, dim3(std::min(rows, 2 * ctx->num_cu)), dim3(kCsrThreads), 0,
                        ctx->stream, Rp, Rx, rows, d_mean, d_out);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+int launch_csr_row_group_stored_sums(plaidhip_ctx* ctx, const int32_t* Rp, const int32_t* Rj, const double* Rx, int32_t rows,
+                                     int32_t max_row_nnz, const int32_t* d_y, double* d_out) {
+  if (rows <= 0) return PLAIDHIP_OK;
+  const int rows_per_block = kCsrThreads / 64;
+  hipLaunchKernelGGL(csr_row_group_stored_sums_kernel<64>, dim3((rows + rows_per_block - 1) / rows_per_block),
+                     dim3(kCsrThreads), 0, ctx->stream, Rp, Rj, Rx, rows, d_y, d_out);
+  if (max_row_nnz > kLongRow)
+    hipLaunchKernelGGL(csr_row_group_stored_sums_kernel<256>, dim3(std::min(rows, 2 * ctx->num_cu)), dim3(kCsrThreads), 0,
+                       ctx->stream, Rp, Rj, Rx, rows, d_y, d_out);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

@@ -245,6 +245,115 @@ int launch_fold_change(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, in
   return PLAIDHIP_OK;
 }
 
+// The block partials of row_group_sums_kernel (mean == nullptr) or of row_group_ssd_kernel (mean: [2][rows]) over the
+// score shard of a sample-sharded plaid.test (multi.cpp), with normalize_medians' last step applied on load:
+// v = (S[r, c] - med[c]) + add, shift_columns_kernel's expression and operand order (med == nullptr: v = S[r, c]).  Same
+// column blocks, the same per-row additions in ascending column order and the same [nblk][2][rows] output as the two
+// kernels above, so the seeded chain adds what the one-device entry adds after its in-place shift -- and the shifted S
+// is never written: two streaming reads of S replace the shift's read + write and the two passes after it.
+// A thread owns two adjacent rows; kWide (rows and ld even, S 16-byte aligned): one 16-byte non-temporal load per column
+// for both, otherwise two 8-byte ones.  kUn columns are loaded before the first of them is added (S is far larger than
+// the Infinity Cache: the loads of a wave must overlap).
+template <bool kSsd, bool kWide>
+__global__ void __launch_bounds__(256)
+row_group_shifted_partials_kernel(const double* __restrict__ S, int64_t ld, int32_t rows, int32_t n,
+                                  const int32_t* __restrict__ y, const double* __restrict__ med, double add,
+                                  const double* __restrict__ mean, double* __restrict__ part) {
+  typedef double f64x2_s __attribute__((ext_vector_type(2)));
+  constexpr int kUn = 8;
+  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
+  const int c0 = blockIdx.y * kColBlock;
+  const int c1 = c0 + kColBlock < n ? c0 + kColBlock : n;
+  if (r >= rows) return;
+  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
+  const bool shift = med != nullptr;
+  double m0a = 0.0, m1a = 0.0, m0b = 0.0, m1b = 0.0;
+  if (kSsd) {
+    m0a = mean[r];
+    m1a = mean[rows + r];
+    if (two) { m0b = mean[r + 1]; m1b = mean[rows + r + 1]; }
+  }
+  double s0a = 0.0, s1a = 0.0, s0b = 0.0, s1b = 0.0;
+  auto accumulate = [&](int c, double xa, double xb) {
+    const int lab = y[c];   // wave-uniform
+    double va = xa, vb = xb;
+    if (shift) {
+      const double md = med[c];
+      va = (xa - md) + add;
+      vb = (xb - md) + add;
+    }
+    if (kSsd) {
+      const double d0a = va - m0a, d1a = va - m1a, d0b = vb - m0b, d1b = vb - m1b;
+      s0a += lab == 0 ? d0a * d0a : 0.0;
+      s1a += lab == 1 ? d1a * d1a : 0.0;
+      s0b += lab == 0 ? d0b * d0b : 0.0;
+      s1b += lab == 1 ? d1b * d1b : 0.0;
+    } else {
+      s0a += lab == 0 ? va : 0.0;
+      s1a += lab == 1 ? va : 0.0;
+      s0b += lab == 0 ? vb : 0.0;
+      s1b += lab == 1 ? vb : 0.0;
+    }
+  };
+  auto load = [&](int c, double& xa, double& xb) {
+    const double* p = S + (int64_t)c * ld + r;
+    if (kWide) {
+      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(p));
+      xa = v.x;
+      xb = v.y;
+    } else {
+      xa = __builtin_nontemporal_load(p);
+      xb = two ? __builtin_nontemporal_load(p + 1) : 0.0;
+    }
+  };
+  int c = c0;
+  for (; c + kUn <= c1; c += kUn) {
+    double xa[kUn], xb[kUn];
+#pragma unroll
+    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
+#pragma unroll
+    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
+  }
+  for (; c < c1; ++c) {
+    double xa, xb;
+    load(c, xa, xb);
+    accumulate(c, xa, xb);
+  }
+  double* p = part + (int64_t)blockIdx.y * 2 * rows;
+  p[r] = s0a;
+  p[rows + r] = s1a;
+  if (two) {
+    p[r + 1] = s0b;
+    p[rows + r + 1] = s1b;
+  }
+}
+
+int launch_row_group_shifted_partials(plaidhip_ctx* ctx, const double* S, int64_t ld, int32_t rows, int32_t n,
+                                      const int32_t* d_y, const double* d_med, double add, const double* d_mean,
+                                      double* ws) {
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const dim3 grid((rows + 511) / 512, nblk);
+  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
+  if (d_mean == nullptr) {
+    if (wide)
+      hipLaunchKernelGGL((row_group_shifted_partials_kernel<false, true>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
+                         d_y, d_med, add, nullptr, ws);
+    else
+      hipLaunchKernelGGL((row_group_shifted_partials_kernel<false, false>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
+                         d_y, d_med, add, nullptr, ws);
+  } else {
+    if (wide)
+      hipLaunchKernelGGL((row_group_shifted_partials_kernel<true, true>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
+                         d_y, d_med, add, d_mean, ws);
+    else
+      hipLaunchKernelGGL((row_group_shifted_partials_kernel<true, false>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
+                         d_y, d_med, add, d_mean, ws);
+  }
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
 int64_t row_group_ws_doubles(int32_t rows, int32_t n) {
   const int64_t nblk = (n + kColBlock - 1) / kColBlock;
   return 2 * (int64_t)rows * (nblk > 0 ? nblk : 1);

@@ -8,15 +8,18 @@
 // the phases.  No RCCL: nothing but those scalars crosses between devices.  (One process per GPU over RCCL is the
 // other form, plaid_amd/sharded.py.)  The single-device entry points run the same code with one shard.
 // replaid.ucell / aucell / scse / gsva (scorer_worker) add their own couplings: the min / max behind removeLog2 = NULL and
-// the per-gene mean and sd of gsva's z transform (g values each, chained from shard to shard for dense X).
+// the per-gene mean and sd of gsva's z transform (g values each, chained from shard to shard for dense X).  plaid.test
+// (plaid_test_worker) reduces nothing but row sums over the samples: its scores stay on the devices.
 //
 // Uploads are pipelined: R hands over pageable memory, which the HIP runtime copies at ~21 GB/s; staged through
 // pinned buffers by a few feeder threads (memcpy at ~75 GB/s with four threads, tools/ubench/pcie.cpp) the DMA
 // runs at the link rate (~57 GB/s) and the kernels of a column panel start as soon as the panel has landed.
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <chrono>
@@ -286,10 +289,14 @@ struct Shared {
   // replaid.gsva, dgCMatrix: every shard's row sums of stored values, then of squared deviations, and row lengths
   std::vector<std::vector<double>> row_sum, row_ssd;
   std::vector<std::vector<int32_t>> row_len;
+  // plaid.test: the chained two-group sums ([2][rows]) of X (dense), of the score rows and of their squared deviations;
+  // shard 0's T = Gt [fc, fc^2] and F = [fc, fc^2] (leading dimension even_ld(g)); a dgCMatrix's per-shard stored-value
+  // sums go to row_sum
+  std::vector<double> chain_x, chain_s, chain_q, pt_T, pt_F;
 };
 
 struct Call {
-  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z)
+  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test
   const int32_t* Xp;
   const int32_t* Xi;
   const double* X;   // dense values or CSC @x
@@ -309,14 +316,20 @@ struct Call {
   double tau = 0.0;                 // gsva
   int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded
   int* removed_log2 = nullptr;      // scse output (may be null)
+  // method 7, plaid.test: the arguments of plaidhip_plaid_test and the group sizes of y
+  const int32_t* y = nullptr;
+  const double* gsetX = nullptr;
+  int tests = 0, metap_method = 0;
+  int64_t n0 = 0, n1 = 0;
+  double* out = nullptr;
 };
 
-// columns [lo, lo + nloc) of shard k.  Dense replaid.gsva cuts at multiples of kColBlock (kernels_stats.hip, 128 columns)
-// so that its chained row reductions add the block partials of the one-device call in the same order; everything else
-// takes plaidhip_shard_bounds.
+// columns [lo, lo + nloc) of shard k.  Dense replaid.gsva and plaid.test (dense or not: its score rows are chained too)
+// cut at multiples of kColBlock (kernels_stats.hip, 128 columns) so that their chained row reductions add the block
+// partials of the one-device call in the same order; everything else takes plaidhip_shard_bounds.
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
   int64_t lo64 = 0, hi64 = 0;
-  if (c.method == 6 && c.Xp == nullptr) {
+  if ((c.method == 6 && c.Xp == nullptr) || c.method == 7) {
     constexpr int64_t kBlock = 128;
     const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
     lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
@@ -962,6 +975,231 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   return rc;
 }
 
+// the group means of [2][rows] chained sums: reduce_blocks_kernel's scale (a product with 1 / n_k, NaN for an empty group)
+void scaled_group_means(const std::vector<double>& sums, int32_t rows, int64_t n0, int64_t n1, double* mean) {
+  const double s0 = n0 > 0 ? 1.0 / (double)n0 : std::numeric_limits<double>::quiet_NaN();
+  const double s1 = n1 > 0 ? 1.0 / (double)n1 : std::numeric_limits<double>::quiet_NaN();
+  for (int32_t i = 0; i < rows; ++i) {
+    mean[i] = sums[(size_t)i] * s0;
+    mean[(size_t)rows + i] = sums[(size_t)rows + i] * s1;
+  }
+}
+
+// one device's part of a sharded plaid.test (method 7, R/plaid.R:392-474): plaidhip_plaid_test's phases with what
+// couples the samples combined on the host in between -- everything plaid.test reduces is a row sum over the samples,
+// so only O(genes + sets) numbers cross between the shards and the scores never leave their device.
+//   logFC: dense X chains the two group sums of X from shard to shard (the one-device block order); a dgCMatrix sums
+//     each shard's stored values per group, the host adds the shards.  Shard 0 alone then takes F = [fc, fc^2] and
+//     T = Gt F, with the launches of the one-device entry.
+//   scores ("lm"): gsetX's columns uploaded, or plaid(X, G)'s sharded crossprod and medians (shard_worker), stopped
+//     before the shift: the shard keeps the raw S, its medians and mean(medx).
+//   Welch moments: the group sums of the score rows, shifted on load (launch_row_group_shifted_partials), chained; then,
+//     from the global means, the sums of squared deviations, chained.  plaidhip_plaid_test_finish runs in run_call.
+int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  int rc = PLAIDHIP_OK;
+  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
+  auto step = [&](const std::function<int()>& fn) {
+    if (!live()) return;
+    try {
+      rc = fn();
+    } catch (...) {
+      rc = on_exception();
+    }
+    if (rc != PLAIDHIP_OK) sh.abort.store(1);
+  };
+  int32_t lo = 0, nloc = 0;
+  shard_columns(c, ndev, k, &lo, &nloc);
+  const int32_t g = c.g, m = c.m, n = c.n;
+  const bool sparse = c.Xp != nullptr;
+  const bool lm = (c.tests & 4) != 0;
+  const bool scores = lm && c.gsetX == nullptr;   // plaid(X, G) computed here (R/plaid.R:424-427)
+  const int64_t ldg = even_ld(g);
+  const int64_t wide = std::max<int64_t>(g, m);
+  const size_t nl = (size_t)std::max(nloc, 1);
+  plaidhip_geneset* gs = nullptr;
+  CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dS{ctx, 4}, dsmall{ctx, 5};
+  DevBuf dy, dws, drows, drp, dRj, dRx, dF, dT;
+  uint32_t* d_flags = nullptr;
+  double *d_med = nullptr, *d_seed = nullptr, *d_run = nullptr, *d_mean = nullptr;
+  int64_t zx = 0;
+  std::vector<int32_t> ploc;
+  // host sources of asynchronous uploads: they live until the worker's last synchronisation
+  std::vector<double> x_mean, s_mean;
+
+  // ---- upload; X's group sums of this shard; plaid()'s crossprod of dense X panel by panel --------------------------------
+  step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    if (k == 0 || scores) PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    PH_TRY(dsmall.alloc(64 + nl * 8));
+    d_flags = dsmall.as<uint32_t>();
+    d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
+    PH_HIP(hipMemsetAsync(dsmall.p, 0, 64, ctx->stream));
+    PH_TRY(drows.alloc((size_t)wide * 6 * 8));   // [seed | running sums | means], [2][max(g, m)] each
+    d_seed = drows.as<double>();
+    d_run = d_seed + 2 * wide;
+    d_mean = d_run + 2 * wide;
+    if (lm) PH_TRY(dS.alloc((size_t)m * nl * 8));
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(dy.alloc((size_t)nloc * 4));
+    PH_HIP(hipMemcpyAsync(dy.p, c.y + lo, (size_t)nloc * 4, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dws.alloc((size_t)std::max(sparse ? 0 : row_group_ws_doubles(g, nloc), lm ? row_group_ws_doubles(m, nloc) : 0) * 8));
+    if (!sparse) {
+      PH_TRY(dX.alloc((size_t)ldg * nloc * 8));
+      auto on_panel = [&](int64_t c0, int64_t c1) -> int {   // (shard_worker's plaid())
+        return launch_spmm_dense_f64(ctx, gs, dX.as<double>() + c0 * ldg, ldg, (int32_t)(c1 - c0), PLAIDHIP_STAT_MEAN, 1.0,
+                                     nullptr, 0.0, dS.as<double>() + c0 * m, m, d_flags);
+      };
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ldg * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
+                              (size_t)g * 8, nloc, scores ? std::function<int(int64_t, int64_t)>(on_panel) : nullptr));
+      return launch_row_group_partials(ctx, dX.as<double>(), ldg, g, nloc, dy.as<int32_t>(), nullptr, dws.as<double>());
+    }
+    const int64_t z0 = c.Xp[lo];
+    zx = (int64_t)c.Xp[lo + nloc] - z0;
+    ploc.resize((size_t)nloc + 1);
+    for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
+    const size_t zb = (size_t)std::max<int64_t>(zx, 1);
+    PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
+    PH_TRY(dXi.alloc(zb * 4));
+    PH_TRY(dX.alloc(zb * 8));
+    PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
+    PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
+    // the shard's row view, with its column indices (they look up y), and the unscaled group sums of its stored values
+    PH_TRY(drp.alloc((size_t)(g + 2) * 4));
+    PH_TRY(dRj.alloc(zb * 4));
+    PH_TRY(dRx.alloc(zb * 8));
+    PH_TRY(launch_csc_to_csr(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), g, nloc, drp.as<int32_t>(),
+                             dRj.as<int32_t>(), dRx.as<double>(), nullptr, drp.as<int32_t>() + g + 1));
+    int32_t max_row = 0;
+    PH_HIP(hipMemcpyAsync(&max_row, drp.as<int32_t>() + g + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    PH_TRY(launch_csr_row_group_stored_sums(ctx, drp.as<int32_t>(), dRj.as<int32_t>(), dRx.as<double>(), g, max_row,
+                                            dy.as<int32_t>(), d_run));
+    std::vector<double> sums((size_t)g * 2);
+    PH_HIP(hipMemcpyAsync(sums.data(), d_run, (size_t)g * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    sh.row_sum[(size_t)k] = std::move(sums);   // (each shard writes its own slot)
+    return PLAIDHIP_OK;
+  });
+
+  // chained, ordered reductions of the [nblk][2][rows] partials in dws: in round r only shard r works, continuing shard
+  // r - 1's running sums of both groups block by block
+  auto chain = [&](std::vector<double>& run, int32_t rows) {
+    for (int r = 0; r < ndev; ++r) {
+      if (r == k)
+        step([&]() -> int {
+          if (nloc == 0) return PLAIDHIP_OK;
+          PH_HIP(hipMemcpyAsync(d_seed, run.data(), (size_t)rows * 2 * 8, hipMemcpyHostToDevice, ctx->stream));
+          PH_TRY(launch_reduce_blocks_seeded(ctx, dws.as<double>(), rows, nloc, d_seed, d_run));
+          PH_TRY(launch_reduce_blocks_seeded(ctx, dws.as<double>() + rows, rows, nloc, d_seed + rows, d_run + rows));
+          PH_HIP(hipMemcpyAsync(run.data(), d_run, (size_t)rows * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+          PH_HIP(hipStreamSynchronize(ctx->stream));
+          return PLAIDHIP_OK;
+        });
+      sh.rv.arrive_and_wait();
+    }
+  };
+
+  // ---- logFC = rowMeans(X[, y == 1]) - rowMeans(X[, y == 0]) (R/plaid.R:407-409); shard 0: Gt fc, Gt fc^2 (:478-479) -----
+  if (!sparse) chain(sh.chain_x, g);
+  else sh.rv.arrive_and_wait();   // every shard's stored-value sums are in sh.row_sum
+  step([&]() -> int {
+    if (k != 0) return PLAIDHIP_OK;
+    x_mean.resize((size_t)g * 2);
+    if (!sparse) {
+      scaled_group_means(sh.chain_x, g, c.n0, c.n1, x_mean.data());
+    } else {   // the shards added in shard order, then csr_row_moments_kernel's true division (0 / 0 = NaN, empty group)
+      for (int32_t i = 0; i < g; ++i) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int q = 0; q < ndev; ++q)
+          if (!sh.row_sum[(size_t)q].empty()) { s0 += sh.row_sum[(size_t)q][(size_t)i]; s1 += sh.row_sum[(size_t)q][(size_t)g + i]; }
+        x_mean[(size_t)i] = s0 / (double)c.n0;
+        x_mean[(size_t)g + i] = s1 / (double)c.n1;
+      }
+    }
+    PH_TRY(dF.alloc((size_t)ldg * 2 * 8));
+    PH_TRY(dT.alloc((size_t)m * 2 * 8));
+    PH_HIP(hipMemcpyAsync(d_mean, x_mean.data(), (size_t)g * 2 * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_HIP(hipMemsetAsync(dF.p, 0, (size_t)ldg * 2 * 8, ctx->stream));
+    PH_TRY(launch_fold_change(ctx, d_mean, g, ldg, dF.as<double>()));
+    PH_TRY(launch_spmm_dense_f64(ctx, gs, dF.as<double>(), ldg, 2, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(), m,
+                                 nullptr));
+    PH_HIP(hipMemcpyAsync(sh.pt_T.data(), dT.p, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(sh.pt_F.data(), dF.p, (size_t)ldg * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+
+  // ---- the scores: gsetX's columns, or plaid(X, G)'s crossprod of a dgCMatrix (dense X: done panel by panel above) ---------
+  step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nloc == 0 || !lm) return PLAIDHIP_OK;
+    if (!scores)
+      return upload_pipelined(ctx, dS.as<char>(), (size_t)m * 8, reinterpret_cast<const char*>(c.gsetX + (int64_t)lo * m),
+                              (size_t)m * 8, nloc, nullptr);
+    if (!sparse) return PLAIDHIP_OK;
+    // (after shard 0's Gt F above: another crossprod between this one and the medians would discard what it classified)
+    const int64_t nnz_choice = (int64_t)((double)c.Xp[n] / (double)n * (double)nloc);   // (as shard_worker)
+    return launch_spmm_csc_fused_f64(ctx, gs, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), nloc, zx,
+                                     PLAIDHIP_STAT_MEAN, 1.0, nullptr, 0.0, dS.as<double>(), m, d_flags, /*bounded=*/false,
+                                     nullptr, 0.0, nnz_choice);
+  });
+
+  // ---- normalize_medians (R/plaid.R:554-575) as shard_worker, up to mean(medx): the shift is applied on load below ---------
+  double add = 0.0;
+  if (scores) {
+    uint32_t fl[4] = {0, 0, 0, 0};
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(fl, d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      for (int q = 0; q < 4; ++q) sh.flags[q] |= fl[q];
+    }
+    sh.rv.arrive_and_wait();
+    const int ignore_zero = (sh.flags[1] != 0 && sh.flags[0] == 0) ? 1 : 0;   // min(x) == 0, R/plaid.R:556-557
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, nloc, ignore_zero, nullptr, d_med));
+      PH_HIP(hipMemcpyAsync(sh.med_all.data() + lo, d_med, (size_t)nloc * 8, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    sh.rv.arrive_and_wait();
+    add = live() ? mean_like_device_sum(sh.med_all.data(), n) : 0.0;   // mean(medx, na.rm = TRUE), :572
+  }
+
+  // ---- Welch moments of the score rows (Rfast::ttests(t(gsetX), ina = y + 1), :429) --------------------------------------
+  if (lm) {
+    const double* med = scores ? d_med : nullptr;
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      return launch_row_group_shifted_partials(ctx, dS.as<double>(), m, m, nloc, dy.as<int32_t>(), med, add, nullptr,
+                                               dws.as<double>());
+    });
+    chain(sh.chain_s, m);
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      s_mean.resize((size_t)m * 2);
+      scaled_group_means(sh.chain_s, m, c.n0, c.n1, s_mean.data());
+      PH_HIP(hipMemcpyAsync(d_mean, s_mean.data(), (size_t)m * 2 * 8, hipMemcpyHostToDevice, ctx->stream));
+      return launch_row_group_shifted_partials(ctx, dS.as<double>(), m, m, nloc, dy.as<int32_t>(), med, add, d_mean,
+                                               dws.as<double>());
+    });
+    chain(sh.chain_q, m);
+  }
+
+  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
+    hipStreamSynchronize(ctx->stream);
+    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
+  }
+  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
@@ -973,7 +1211,16 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.row_ssd.resize((size_t)ndev);
     sh.row_len.resize((size_t)ndev);
   }
+  if (c.method == 7) {
+    sh.chain_x.assign((size_t)c.g * 2, 0.0);
+    sh.chain_s.assign((size_t)c.m * 2, 0.0);
+    sh.chain_q.assign((size_t)c.m * 2, 0.0);
+    sh.pt_T.assign((size_t)c.m * 2, 0.0);
+    sh.pt_F.assign((size_t)even_ld(c.g) * 2, 0.0);
+    sh.row_sum.resize((size_t)ndev);
+  }
   auto worker = [&](int k) {
+    if (c.method == 7) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     return c.method <= 2 ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
   };
   int rc = PLAIDHIP_OK;
@@ -1001,6 +1248,19 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
         if (rcs[(size_t)k] != PLAIDHIP_OK) { rc = rcs[(size_t)k]; set_error("a device shard failed"); break; }
   }
   if (rc == PLAIDHIP_OK && c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = sh.removed_log2 ? 1 : 0;
+  if (rc == PLAIDHIP_OK && c.method == 7) {   // the host half of plaid.test, as plaidhip_plaid_test ends
+    const int64_t ldg = even_ld(c.g);
+    double tot1 = 0.0, tot2 = 0.0;
+    for (int32_t i = 0; i < c.g; ++i) { tot1 += sh.pt_F[(size_t)i]; tot2 += sh.pt_F[(size_t)ldg + i]; }
+    std::vector<double> SM;
+    if (c.tests & 4) {   // [group means | sums of squared deviations], [2][m] each
+      SM.resize((size_t)c.m * 4);
+      scaled_group_means(sh.chain_s, c.m, c.n0, c.n1, SM.data());
+      std::copy(sh.chain_q.begin(), sh.chain_q.end(), SM.begin() + 2 * (size_t)c.m);
+    }
+    rc = plaidhip_plaid_test_finish(c.g, c.m, c.Gp, sh.pt_T.data(), tot1, tot2, (c.tests & 4) ? SM.data() : nullptr, c.n0,
+                                    c.n1, c.tests, c.metap_method, c.out);
+  }
   return rc;
 }
 
@@ -1096,6 +1356,42 @@ int run_scorer_multi(const int* devices, int ndev, const Call& c) {
   return run_call(ctxs.data(), ndev, c);
 }
 
+Call plaid_test_call(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* y,
+                     const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests, int metap_method,
+                     double* out) {
+  Call c{7, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, nullptr};
+  c.y = y;
+  c.gsetX = gsetX;
+  c.tests = tests;
+  c.metap_method = metap_method;
+  c.out = out;
+  return c;
+}
+
+// the argument checks of plaidhip_plaid_test / plaidhip_plaid_test_csc, their messages, and the device list's, before any
+// device is touched; counts the groups of y into c.n0 / c.n1
+int check_plaid_test_call(const int* devices, int ndev, Call& c) {
+  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
+  if (devices != nullptr)
+    for (int k = 0; k < ndev; ++k)
+      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  PH_REQUIRE(c.m == 0 || c.out, "plaid_test: null out");
+  PH_REQUIRE(c.n == 0 || ((c.Xp != nullptr || c.X != nullptr) && c.y != nullptr), "plaid_test: null X / y");
+  PH_REQUIRE((c.tests & 7) != 0 && (c.tests & ~7) == 0, "plaid_test: tests is a bit mask of 1 (one), 2 (two), 4 (lm)");
+  PH_REQUIRE(c.metap_method == 0 || c.metap_method == 1, "Invalid method: %d", c.metap_method);   // R/plaid.R:533
+  c.n0 = c.n1 = 0;
+  for (int32_t j = 0; j < c.n; ++j) {
+    PH_REQUIRE(c.y[j] == 0 || c.y[j] == 1, "elements of y must be 0 or 1");                        // R/plaid.R:394
+    if (c.y[j]) ++c.n1; else ++c.n0;
+  }
+  if (c.Xp != nullptr) {
+    PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
+    PH_REQUIRE(c.Xp[c.n] == 0 || (c.Xi && c.X), "plaid_test: null Xi/Xx");
+  }
+  return PLAIDHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1144,6 +1440,30 @@ int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fai
   c.removed_log2 = removed_log2;
   PH_TRY(check_scorer_call(c));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
+  int rc = PLAIDHIP_OK;
+  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
+    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
+    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
+  }
+  if (rc == PLAIDHIP_OK) rc = run_call(ctxs.data(), nshards, c);
+  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
+  for (plaidhip_ctx* cx : ctxs)
+    if (cx) plaidhip_finalize(cx);
+  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
+  return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h): plaidhip_plaid_test_multi's engine with `nshards` contexts on ONE device.
+// fail_shard >= 0: that shard fails in its crossprod / moments phase (the call must return an error, not hang).
+int plaidhip_debug_plaid_test_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                    const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                    const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                                                    const double* gsetX, int tests, int metap_method, double* out) try {
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_plaid_test_sharded: nshards = %d", nshards);
+  Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
+  PH_TRY(check_plaid_test_call(nullptr, nshards, c));
+  if (m == 0) return PLAIDHIP_OK;
   std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
   int rc = PLAIDHIP_OK;
   for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
@@ -1234,6 +1554,17 @@ int plaidhip_gsva_multi(const int* devices, int ndev, const int32_t* Xp, const i
   c.tau = tau;
   c.rowtf = rowtf;
   return run_scorer_multi(devices, ndev, c);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_plaid_test_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                              const double* gsetX, int tests, int metap_method, double* out) try {
+  Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
+  PH_TRY(check_plaid_test_call(devices, ndev, c));
+  if (m == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_call(ctxs.data(), ndev, c);
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -656,5 +656,29 @@ def gsva_multi(X, Gp, Gi, tau=0.0, rowtf="z", devices=1) -> np.ndarray:
     return S
 
 
+def plaid_test_multi(X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0, devices=1) -> np.ndarray:
+    """plaid.test (Context.plaid_test / plaid_test_csc) with the sample columns sharded over `devices`; X dense or scipy
+    CSC.  The scores stay on the devices: only per-gene and per-set sums cross between them.  Returns sets x 6 (gsetFC,
+    p.one, p.two, p.lm, p.meta, q.meta) in G's column order; dense X gives the single-device result bit for bit."""
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.shape != (n,):
+        raise ValueError("y must have one entry per column of X")
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    sx = None
+    if gsetX is not None:
+        sx = _as_f64_fortran(gsetX)
+        if sx.shape != (m, n):
+            raise ValueError("gsetX must be sets x samples")
+    out = np.empty((m, 6), dtype=np.float64, order="F")
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_plaid_test_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(y), _np_ptr(Gp), _np_ptr(Gi), m,
+                                        _np_ptr(sx) if sx is not None else None, int(tests), int(metap_method),
+                                        _np_ptr(out)))
+    return out
+
+
 def multi_finalize():
     check(_lib.load().plaidhip_multi_finalize())

@@ -8,10 +8,10 @@
 ##   plaidhip.device     integer, the GPU ordinal the session context lives on (default 0; read when the
 ##                       context is first created)
 ##   plaidhip.devices    integer vector of GPU ordinals: with more than one, plaid() / replaid.sing() /
-##                       replaid.ssgsea() / replaid.ucell() / replaid.aucell() / replaid.scse() / replaid.gsva()
-##                       shard the sample columns over them (a host thread per device inside the library, no process
-##                       per GPU); replaid.gsva(rowtf = "ecdf") ranks all samples of a gene together and stays on the
-##                       session device.  One ordinal: that GPU is the session device; default: the session device
+##                       replaid.ssgsea() / replaid.ucell() / replaid.aucell() / replaid.scse() / replaid.gsva() /
+##                       plaid.test() shard the sample columns over them (a host thread per device inside the library,
+##                       no process per GPU); replaid.gsva(rowtf = "ecdf") ranks all samples of a gene together and
+##                       stays on the session device.  One ordinal: that GPU is the session device; default: the session device
 ##                       alone.  plaidhip.precision applies to every device of the list.
 ##   plaidhip.precision  "f64" (default: scores equal to the last bits) or "mixed" (dense crossprod stages the
 ##                       sample columns as fp32, sums fp64; ~1e-7 relative, inside the 1e-5 bar; ~1.5x faster)
@@ -313,8 +313,14 @@ plaid.test <- function(X, y, G, gsetX, tests = c("one", "two", "lm"),
   bits <- sum(c(one = 1L, two = 2L, lm = 4L)[intersect(tests, c("one", "two", "lm"))])
   .session()
   mm <- as.integer(metap.method %in% c("stouffer", "sumz"))
-  r <- if (sparse) .Call("R_plaidhip_plaid_test_csc", X@p, X@i, as.double(X@x), nrow(X), as.integer(y), pat$Gp, pat$Gi,
-                         gsetX, bits, mm, PACKAGE = "plaidhip")
+  dev <- .devices()
+  r <- if (length(dev) > 1L) {
+         ## sample shards over several GPUs: the scores stay on them, only per-gene and per-set sums are combined
+         xa <- .x_args(X)
+         .Call("R_plaidhip_plaid_test_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), as.integer(y), pat$Gp,
+               pat$Gi, gsetX, bits, mm, PACKAGE = "plaidhip")
+       } else if (sparse) .Call("R_plaidhip_plaid_test_csc", X@p, X@i, as.double(X@x), nrow(X), as.integer(y), pat$Gp,
+                                pat$Gi, gsetX, bits, mm, PACKAGE = "plaidhip")
        else .Call("R_plaidhip_plaid_test", X, as.integer(y), pat$Gp, pat$Gi, gsetX, bits, mm, PACKAGE = "plaidhip")
   keep <- c(TRUE, "one" %in% tests, "two" %in% tests, "lm" %in% tests, TRUE, TRUE)
   res <- r[, keep, drop = FALSE]

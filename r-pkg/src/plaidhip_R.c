@@ -349,6 +349,21 @@ SEXP R_plaidhip_gsva(SEXP X, SEXP Gp, SEXP Gi, SEXP tau, SEXP rowtf) {
   return S;
 }
 
+/* plaid.test() over several devices (plaidhip_plaid_test_multi): dense X (Xp, Xi NULL, Xv the matrix) or a dgCMatrix's
+ * slots; the same result as R_plaidhip_plaid_test / R_plaidhip_plaid_test_csc and the same error messages */
+SEXP R_plaidhip_plaid_test_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP y, SEXP Gp, SEXP Gi,
+                                 SEXP gsetX, SEXP tests, SEXP metap) {
+  const int m = LENGTH(Gp) - 1;
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 6));
+  int rc = plaidhip_plaid_test_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                     Rf_asInteger(g), Rf_asInteger(n), INTEGER(y), INTEGER(Gp), INTEGER(Gi), m,
+                                     Rf_isNull(gsetX) ? NULL : REAL(gsetX), Rf_asInteger(tests), Rf_asInteger(metap),
+                                     REAL(out));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(1);
+  return out;
+}
+
 /* the same two calls for a dgCMatrix: its slots, no dense X (plaidhip_plaid_test_csc / plaidhip_gsva_csc) */
 SEXP R_plaidhip_plaid_test_csc(SEXP Xp, SEXP Xi, SEXP Xx, SEXP g, SEXP y, SEXP Gp, SEXP Gi, SEXP gsetX, SEXP tests,
                                SEXP metap) {
@@ -401,6 +416,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_plaid_test", (DL_FUNC)&R_plaidhip_plaid_test, 7},
     {"R_plaidhip_gsva", (DL_FUNC)&R_plaidhip_gsva, 5},
     {"R_plaidhip_plaid_test_csc", (DL_FUNC)&R_plaidhip_plaid_test_csc, 10},
+    {"R_plaidhip_plaid_test_multi", (DL_FUNC)&R_plaidhip_plaid_test_multi, 12},
     {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
     {NULL, NULL, 0}};
 
