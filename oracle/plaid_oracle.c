@@ -39,6 +39,13 @@ static int cmp_double(const void* a, const void* b) {
   return (x > y) - (x < y);
 }
 
+/* mean of the two middle values, (a + b) / 2 rounded once: 0.5 * (a + b) unless the sum of two finite values overflows,
+ * where R's median (long-double mean on x86-64) stays finite */
+static double midpoint(double a, double b) {
+  const double s = a + b;
+  return (isinf(s) && isfinite(a) && isfinite(b)) ? 0.5 * a + 0.5 * b : 0.5 * s;
+}
+
 /* normalize_medians(x, ignore.zero), R/plaid.R:554-575.  ignore_zero: -1 = NULL (auto). */
 void oracle_normalize_medians(double* S, int32_t m, int32_t n, int ignore_zero, double* med_out) {
   const size_t tot = (size_t)m * n;
@@ -66,7 +73,7 @@ void oracle_normalize_medians(double* S, int32_t m, int32_t n, int ignore_zero, 
       md = ignore_zero ? 0.0 : NAN;            /* :566 */
     } else {
       qsort(buf, (size_t)k, sizeof(double), cmp_double);
-      md = (k & 1) ? buf[k / 2] : 0.5 * (buf[k / 2 - 1] + buf[k / 2]);
+      md = (k & 1) ? buf[k / 2] : midpoint(buf[k / 2 - 1], buf[k / 2]);
     }
     med[c] = md;
     if (md == md) { msum += md; ++mcnt; }
@@ -238,7 +245,7 @@ void oracle_normalize_medians_mt(double* S, int32_t m, int32_t n, int ignore_zer
       if (k == 0) md = ignore_zero ? 0.0 : NAN;
       else {
         qsort(buf, (size_t)k, sizeof(double), cmp_double);
-        md = (k & 1) ? buf[k / 2] : 0.5 * (buf[k / 2 - 1] + buf[k / 2]);
+        md = (k & 1) ? buf[k / 2] : midpoint(buf[k / 2 - 1], buf[k / 2]);
       }
       med[c] = md;
     }

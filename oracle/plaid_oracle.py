@@ -166,6 +166,23 @@ def chunked_crossprod(x, y, chunk=None, _log=None):
     return out
 
 
+def _nanmedian_cols(x):
+    """np.nanmedian over the columns, except that an even count's two middle values are averaged as (a + b) / 2 rounded
+    once: numpy's mean of two finite values whose sum overflows is +-Inf, R's median on x86-64 (a long-double mean) is
+    the finite midpoint"""
+    import warnings
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        med = np.nanmedian(x, axis=0)
+    for c in np.flatnonzero(np.isinf(med)):
+        v = np.sort(x[~np.isnan(x[:, c]), c])
+        if len(v) % 2 == 0:
+            a, b = v[len(v) // 2 - 1], v[len(v) // 2]
+            if np.isfinite(a) and np.isfinite(b):
+                med[c] = 0.5 * a + 0.5 * b                # exact halves, one rounding
+    return med
+
+
 def normalize_medians(x, ignore_zero=None):
     """R/plaid.R:554-575.  Returns (normalised matrix, medians)."""
     x = np.asarray(x, dtype=np.float64)
@@ -174,17 +191,10 @@ def normalize_medians(x, ignore_zero=None):
     if ignore_zero:
         zx = x.copy()
         zx[x == 0] = np.nan                               # :562-563
-        with np.errstate(all="ignore"):
-            import warnings
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                medx = np.nanmedian(zx, axis=0)           # :565
+        medx = _nanmedian_cols(zx)                        # :565
         medx[np.isnan(medx)] = 0.0                        # :566
     else:
-        import warnings
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            medx = np.nanmedian(x, axis=0)                # :569
+        medx = _nanmedian_cols(x)                         # :569
     nx = (x - medx[None, :]) + np.nanmean(medx)           # :572
     return nx, medx
 

@@ -20,6 +20,15 @@ __device__ __forceinline__ double key_to_f64(uint64_t k) {
   return __longlong_as_double((long long)u);
 }
 
+// The two middle values' mean of an even-count median, (a + b) / 2 rounded once.  That is 0.5 * (a + b) (halving is
+// exact) except where a + b overflows: two finite values of one sign beyond DBL_MAX / 2, whose halves are exact and
+// whose midpoint is finite, as R's median (a long-double mean on x86-64) returns it.  Inf and NaN inputs keep
+// 0.5 * (a + b).
+__device__ __forceinline__ double midpoint_f64(double a, double b) {
+  const double s = a + b;
+  return (__builtin_isinf(s) && __builtin_isfinite(a) && __builtin_isfinite(b)) ? 0.5 * a + 0.5 * b : 0.5 * s;
+}
+
 __device__ __forceinline__ uint32_t next_pow2(uint32_t v) {
   if (v <= 1) return 1;
   return 1u << (32 - __clz(v - 1));

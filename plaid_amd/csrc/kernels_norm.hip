@@ -83,7 +83,7 @@ col_medians_lds_kernel(const double* __restrict__ S, int64_t lds, int32_t m, int
       } else if (cnt & 1) {
         r = key_to_f64(keys[cnt >> 1]);
       } else {
-        r = 0.5 * (key_to_f64(keys[(cnt >> 1) - 1]) + key_to_f64(keys[cnt >> 1]));
+        r = midpoint_f64(key_to_f64(keys[(cnt >> 1) - 1]), key_to_f64(keys[cnt >> 1]));
       }
       med[c] = r;
     }
@@ -246,7 +246,7 @@ col_medians_bits_kernel(const double* __restrict__ S, int64_t lds, int32_t m, in
           __syncthreads();   // s_min is reused by the next column
         }
       }
-      r = (V2 == V) ? key_to_f64(V) : 0.5 * (key_to_f64(V) + key_to_f64(V2));
+      r = (V2 == V) ? key_to_f64(V) : midpoint_f64(key_to_f64(V), key_to_f64(V2));
     }
     if (tid == 0) med[c] = r;
   }
@@ -312,7 +312,7 @@ col_medians_select_kernel(const double* __restrict__ S, int64_t lds, int32_t m, 
     } else {
       const double lo = key_to_f64(radix_select_global(sc, m, ignore_zero, (cnt >> 1) - 1, hist, s_sel));
       const double hi = key_to_f64(radix_select_global(sc, m, ignore_zero, cnt >> 1, hist, s_sel));
-      r = 0.5 * (lo + hi);
+      r = midpoint_f64(lo, hi);
     }
     if (tid == 0) med[c] = r;
     __syncthreads();
@@ -453,7 +453,7 @@ col_medians_sample_kernel(const double* __restrict__ S, int64_t lds, int32_t m, 
 #endif
       if (!ok1) v1 = radix_select_global(sc, m, ignore_zero, k_lo, hist, hist + 256);   // rare
       if (!ok2) v2 = (k_hi == k_lo) ? v1 : radix_select_global(sc, m, ignore_zero, k_hi, hist, hist + 256);
-      r = (v1 == v2) ? key_to_f64(v1) : 0.5 * (key_to_f64(v1) + key_to_f64(v2));
+      r = (v1 == v2) ? key_to_f64(v1) : midpoint_f64(key_to_f64(v1), key_to_f64(v2));
     }
     if (tid == 0) med[c] = r;
     __syncthreads();
@@ -941,7 +941,7 @@ col_medians_radix_kernel(const double* __restrict__ S, int64_t lds, int32_t m, i
 #pragma unroll
         for (int w = 0; w < NW; ++w) V2 = s_mn[w] < V2 ? s_mn[w] : V2;
       }
-      r = (V2 == V) ? key_to_f64(V) : 0.5 * (key_to_f64(V) + key_to_f64(V2));
+      r = (V2 == V) ? key_to_f64(V) : midpoint_f64(key_to_f64(V), key_to_f64(V2));
     }
     if (tid == 0) med[c] = r;
     __syncthreads();   // s_mn / s_mx / s_cnt / s_key are rewritten by the next column
@@ -1197,7 +1197,7 @@ col_medians_wave_kernel(const double* __restrict__ S, int64_t lds, int32_t m, in
         }
         V2 = wave_min_u64(mn) + V + 1ull;
       }
-      r = (V2 == V) ? key_to_f64(V) : 0.5 * (key_to_f64(V) + key_to_f64(V2));
+      r = (V2 == V) ? key_to_f64(V) : midpoint_f64(key_to_f64(V), key_to_f64(V2));
     }
     if (lane == 0) med[c] = r;
     PH_MSTAMP(2)   // single-key fetch + upper middle
@@ -1743,7 +1743,7 @@ col_medians_stream_kernel(const double* __restrict__ S, int64_t lds, int32_t m, 
         }
         V2 = above;
       }
-      r = (V2 == V) ? key_to_f64(V) : 0.5 * (key_to_f64(V) + key_to_f64(V2));
+      r = (V2 == V) ? key_to_f64(V) : midpoint_f64(key_to_f64(V), key_to_f64(V2));
     }
     if (lane == 0) med[c] = r;
     PH_SSTAMP(5)   // upper-middle sweep (rare)
@@ -1912,7 +1912,7 @@ __device__ __forceinline__ void fmed_select_from(const unsigned long long* __res
   const uint64_t a1 = wave_radix_select<ITEMS>(key, (uint32_t)(k1 - below), total, kmin, kmax, s_hist, lane);
   const uint64_t a2 = (k2 == k1) ? a1 : wave_radix_select<ITEMS>(key, (uint32_t)(k2 - below), total, kmin, kmax, s_hist, lane);
   if (lane == 0) {
-    med[c] = (a1 == a2) ? key_to_f64(a1) : 0.5 * (key_to_f64(a1) + key_to_f64(a2));
+    med[c] = (a1 == a2) ? key_to_f64(a1) : midpoint_f64(key_to_f64(a1), key_to_f64(a2));
     status[c] = 1;
   }
 }
