@@ -241,6 +241,23 @@ int plaidhip_dev_colranks_csc_dense_nz_f64(plaidhip_ctx* ctx, const void* Xp, co
                                            int32_t n, int32_t max_col_nnz, int ties, int is_signed, double power,
                                            void* Rx_scratch, void* R, int64_t ldr, void* colmax);
 
+/* replaid.ssgsea.exact's operand pass (kernels_walk.hip), stream-ordered, no read-back.  For the g x n columns of X (dense,
+ * leading dimension ldx) it writes Q = rank(x, ties = "last") -- bit-identical to plaidhip_dev_colranks_dense_f64 with
+ * PLAIDHIP_TIES_LAST -- and, when alpha != 0, W = rank(x, "average")^alpha and P = W * Q (leading dimension ldq).  W is
+ * bit-identical to plaidhip_dev_colranks_dense_f64(PLAIDHIP_TIES_AVERAGE, power = alpha) wherever that call takes the
+ * bucket or partitioned ranker (columns of more than 256 genes; a clustered column the bucket ranker hands to the sorting
+ * network gets pow() there and 1/4-step roots here, a few ulp apart).  colnan: n uint32, 1 for a column holding a NaN.
+ * Two rank passes (average ranks, then min ranks of (2 r - 1) 2^26 + (g - 1 - i)); scratch: 2 ldq n doubles; g < 2^26. */
+int plaidhip_dev_ssgsea_exact_operands_f64(plaidhip_ctx* ctx, const void* X, int64_t ldx, int32_t g, int32_t n, double alpha,
+                                           void* Q, void* W, void* P, int64_t ldq, void* scratch, void* colnan);
+/* the same for a dgCMatrix (device slots; rows increasing inside each column), with the results of its dense form: the
+ * zeros are ranked, implicit zeros take their q from their row order inside the zero tie group.  nnz = Xp[n], max_col_nnz
+ * the longest column (as for plaidhip_dev_colranks_csc_f64); scratch: 3 nnz doubles.  Two rank passes over the stored
+ * values, then one dense write of Q (and W, P).                                                                        */
+int plaidhip_dev_ssgsea_exact_operands_csc_f64(plaidhip_ctx* ctx, const void* Xp, const void* Xi, const void* Xx, int32_t g,
+                                               int32_t n, int32_t max_col_nnz, int64_t nnz, double alpha, void* Q, void* W,
+                                               void* P, int64_t ldq, void* scratch, void* colnan);
+
 /* normalize_medians() (R/plaid.R:554-575) in three phases so that a sample-sharded host
  * can all-reduce between them:
  *   1. flags  : plaidhip_dev_minflags   (or the SpMM epilogue's `flags`)  -> ignore.zero
@@ -363,6 +380,21 @@ int plaidhip_ssgsea_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
                         int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                         double alpha, double* S_out);
 
+/* replaid.ssgsea.exact(X, matG, alpha, scale, norm): the original ssGSEA statistic (gao.ssgsea, single = TRUE) for any
+ * alpha, where replaid.ssgsea (R/plaid.R:233-234, 247-248) is exact at alpha = 0 only.  Per sample column with N = g genes:
+ * r = average ranks, q = rank(x, ties = "last") (order(r, decreasing = TRUE) keeps tied genes in row order), w = r^alpha;
+ * per set with k members (G's column, aligned to X's rows): A = sum w q, B = sum w, C = sum q, T = N (N + 1) / 2, and
+ * the scores, in fp64 and in exactly these operations (no other association, no contraction):
+ *     d1 = A / B;  d2 = (T - C) / (double)(N - k);  es = d1 - d2;  scale: es = es / N;  norm: es = es / (max - min)
+ * with max / min over the whole m x n result (one NaN makes every score NaN, as R's range does).  k = 0 and k = N give
+ * NaN (0 / 0).  A sample column holding a NaN scores NaN for every set at every alpha (R's NA^0 == 1 would keep
+ * gao.ssgsea finite at alpha = 0: a deliberate difference).  alpha must be finite.  At alpha = 0 (w = 1: A = C, B = k)
+ * and alpha = 1 the sums are of integers and half-integers and the scores are exact.  X dense (Xp == NULL: X_or_x are
+ * g x n doubles) or a dgCMatrix, scored as as.matrix(X) without densifying it on the host.  The result is fp64 in every
+ * precision mode.  S_out: m x n doubles.                                                                             */
+int plaidhip_ssgsea_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm, double* S_out);
+
 /* ---- several GPUs of one node from ONE host process (the R session): multi.cpp ----------------------
  * The sample columns are cut into ndev contiguous shards (plaidhip_shard_bounds); a host thread per device
  * moves its shard over its own PCIe link (pipelined through pinned staging), runs the same kernels, and the
@@ -386,6 +418,12 @@ int plaidhip_sing_csc_multi(const int* devices, int ndev, const int32_t* Xp, con
 int plaidhip_ssgsea_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                           int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
                           double* S_out);
+/* replaid.ssgsea.exact over several devices: the arguments and results of plaidhip_ssgsea_exact, bit for bit for dense X
+ * and for a dgCMatrix alike (per-column work only; norm's range is combined on the host).  The argument checks and the
+ * device list's run before any device is touched.                                                                     */
+int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                int norm, double* S_out);
 /* replaid.ucell / aucell / scse / gsva over several devices: the arguments and results of plaidhip_ucell, plaidhip_aucell,
  * plaidhip_scse and plaidhip_gsva (rowtf = 0, "z"), X dense or a dgCMatrix as above.  The argument checks run before any
  * device is touched.  What couples the shards is combined on the host: max(rX) (R/plaid.R:278, 306, 354), the min / max

@@ -246,6 +246,20 @@ def replaid_ssgsea(X, matG, alpha=0, ctx: Context | None = None):
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
+def replaid_ssgsea_exact(X, matG, alpha=0.25, scale=True, norm=False, ctx: Context | None = None):
+    """replaid.ssgsea.exact(): the original single-sample GSEA statistic (gao.ssgsea with single = TRUE) for any alpha,
+    in closed form on the device (include/plaidhip.h: plaidhip_ssgsea_exact).  G is aligned to X's rows as plaid()
+    aligns it; k counts the aligned members.  A dgCMatrix scores as as.matrix(X) would."""
+    X, matG = as_named(X), as_named(matG)
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    ctx = ctx or default_context()
+    S = ctx.ssgsea_exact(X.values, pat[0], pat[1], float(alpha), scale, norm)
+    return NamedMatrix(S, matG.colnames, X.colnames)
+
+
 def _set_sizes_unaligned(matG: NamedMatrix) -> np.ndarray:
     """Matrix::colSums(matG != 0) of the matrix as given (R/plaid.R:280 does not re-align)."""
     G = sp.csc_matrix(matG.values)

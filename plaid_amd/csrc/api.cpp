@@ -674,6 +674,40 @@ int plaidhip_dev_colranks_csc_dense_nz_f64(plaidhip_ctx* ctx, const void* Xp, co
                                           static_cast<double*>(colmax));
 } catch (...) { return plaidhip::on_exception(); }
 
+// replaid.ssgsea.exact's operand pass (kernels_walk.hip), stream-ordered
+int plaidhip_dev_ssgsea_exact_operands_f64(plaidhip_ctx* ctx, const void* X, int64_t ldx, int32_t g, int32_t n, double alpha,
+                                           void* Q, void* W, void* P, int64_t ldq, void* scratch, void* colnan) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(std::isfinite(alpha), "ssgsea_exact_operands: alpha must be finite (got %g)", alpha);
+  PH_REQUIRE(g >= 0 && n >= 0 && g < (1 << 26), "ssgsea_exact_operands: bad dims g=%d n=%d", g, n);
+  PH_REQUIRE(ldx >= g && ldq >= g, "ssgsea_exact_operands: leading dims below g");
+  PH_REQUIRE(n == 0 || colnan != nullptr, "ssgsea_exact_operands: null colnan");
+  PH_REQUIRE(g == 0 || n == 0 || (X && Q && scratch), "ssgsea_exact_operands: null X/Q/scratch");
+  PH_REQUIRE(alpha == 0.0 || g == 0 || n == 0 || (W && P), "ssgsea_exact_operands: W and P are needed when alpha != 0");
+  return launch_ssgsea_exact_operands(ctx, static_cast<const double*>(X), ldx, nullptr, nullptr, g, n, 0, 0, alpha,
+                                      static_cast<double*>(Q), static_cast<double*>(W), static_cast<double*>(P), ldq,
+                                      static_cast<double*>(scratch), static_cast<uint32_t*>(colnan));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_ssgsea_exact_operands_csc_f64(plaidhip_ctx* ctx, const void* Xp, const void* Xi, const void* Xx, int32_t g,
+                                               int32_t n, int32_t max_col_nnz, int64_t nnz, double alpha, void* Q, void* W,
+                                               void* P, int64_t ldq, void* scratch, void* colnan) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(std::isfinite(alpha), "ssgsea_exact_operands_csc: alpha must be finite (got %g)", alpha);
+  PH_REQUIRE(g >= 0 && n >= 0 && g < (1 << 26) && ldq >= g, "ssgsea_exact_operands_csc: bad dims g=%d n=%d ldq=%lld", g, n,
+             (long long)ldq);
+  PH_REQUIRE(max_col_nnz >= 0 && max_col_nnz <= g && nnz >= 0, "ssgsea_exact_operands_csc: max_col_nnz=%d nnz=%lld", max_col_nnz,
+             (long long)nnz);
+  PH_REQUIRE(n == 0 || (Xp && colnan), "ssgsea_exact_operands_csc: null Xp/colnan");
+  PH_REQUIRE(g == 0 || n == 0 || Q != nullptr, "ssgsea_exact_operands_csc: null Q");
+  PH_REQUIRE(nnz == 0 || (Xi && Xx && scratch), "ssgsea_exact_operands_csc: null Xi/Xx/scratch");
+  PH_REQUIRE(alpha == 0.0 || g == 0 || n == 0 || (W && P), "ssgsea_exact_operands_csc: W and P are needed when alpha != 0");
+  return launch_ssgsea_exact_operands(ctx, static_cast<const double*>(Xx), 0, static_cast<const int32_t*>(Xp),
+                                      static_cast<const int32_t*>(Xi), g, n, max_col_nnz, nnz, alpha, static_cast<double*>(Q),
+                                      static_cast<double*>(W), static_cast<double*>(P), ldq, static_cast<double*>(scratch),
+                                      static_cast<uint32_t*>(colnan));
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_dev_minflags(plaidhip_ctx* ctx, const void* S, int64_t count, void* flags) try {
   PH_CTX(ctx);
   PH_REQUIRE(flags != nullptr && count >= 0, "minflags: bad arguments");
@@ -933,6 +967,16 @@ int plaidhip_ssgsea_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
   // sparse branch: ranks of the non-zeros only, zeros stay 0 (R/plaid.R:600-601, 631-650); the "- 0.5" of
   // R/plaid.R:251 applies to the zeros too, which the (alpha, beta) epilogue covers
   return run_sharded(&ctx, 1, 2, Xp, Xi, Xx, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, alpha, S_out);
+} catch (...) { return plaidhip::on_exception(); }
+
+// replaid.ssgsea.exact: the one-device form of the sharded engine (multi.cpp: ssgsea_exact_worker)
+int plaidhip_ssgsea_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
+                          double* S_out) try {
+  PH_REQUIRE(ctx != nullptr, "null plaidhip_ctx");
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  PH_HIP(hipSetDevice(ctx->device));
+  return run_ssgsea_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -451,6 +451,30 @@ int launch_colranks_csc_dense_nz_f64(plaidhip_ctx* ctx, const int32_t* Xp, const
                                      int32_t n, int32_t max_col_nnz, int ties, int is_signed, double power,
                                      double* Rx_scratch, double* R, int64_t ldr, double* colmax);
 int max_sparse_rank_column();
+// whether colranks(ties = "average", power) on columns of g keys raises to a power of 1/4 steps by square roots
+// (pow_quarters: the bucket and partitioned rankers) rather than by pow() (the sorting networks); the data-dependent
+// fallback of clustered columns to the network aside
+bool colranks_uses_power_quarters(plaidhip_ctx* ctx, int32_t g);
+// kernels_walk.hip: replaid.ssgsea.exact.  Operands of g x n columns (leading dimension ldq): Q = rank(x, "last"), and
+// when alpha != 0 W = rank(x, "average")^alpha and P = W * Q; colnan[c] = 1 for a column holding a NaN.  Dense X
+// (Xp == nullptr, leading dimension ldx; scratch 2 ldq n doubles) or CSC slots (rows increasing in each column; nnz =
+// Xp[n], the longest column max_col_nnz; scratch 3 nnz doubles).  Two rank passes, stream-ordered.
+int launch_ssgsea_exact_operands(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, const int32_t* Xi,
+                                 int32_t g, int32_t n, int32_t max_col_nnz, int64_t nnz, double alpha, double* Q, double* W,
+                                 double* P, int64_t ldq, double* scratch, uint32_t* colnan);
+// S (m x n, holding C on entry) <- the pinned epilogue of A, B (nullptr: alpha = 0) and kset (device int32 set sizes);
+// part: 3 ssgsea_exact_part_blocks(m n) doubles; range_out[3] = {min, max, any NaN} of the scores
+int ssgsea_exact_part_blocks(plaidhip_ctx* ctx, int64_t count);
+int launch_ssgsea_exact_epilogue(plaidhip_ctx* ctx, const double* A, const double* B, double* S, int64_t lds, int32_t m,
+                                 int32_t n, const int32_t* kset, int64_t N, int scale, const uint32_t* colnan, double* part,
+                                 double* range_out);
+int launch_ssgsea_exact_norm(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t m, int32_t n, double range);
+// multi.cpp: replaid.ssgsea.exact on ndev contexts (one: plaidhip_ssgsea_exact); its argument checks, which touch no device
+int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                     int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
+                     double* S_out);
+int check_ssgsea_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                            const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, const double* S_out);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 int launch_col_medians(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n,

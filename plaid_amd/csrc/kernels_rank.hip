@@ -984,6 +984,13 @@ int launch_colranks_csc_dense_nz_f64(plaidhip_ctx* ctx, const int32_t* Xp, const
 }
 int max_sparse_rank_column() { return kMaxBucketKeys; }
 
+// the kernel choice of launch_colranks_dense_f64 / launch_ranks for columns of g keys: the partitioned and the bucket
+// rankers apply a power in 1/4 steps by square roots, the sorting networks by pow()
+bool colranks_uses_power_quarters(plaidhip_ctx* ctx, int32_t g) {
+  if (g > kMaxBucketKeys && (g + kPartTarget - 1) / kPartTarget <= kPartMax && ctx->opt_rank_kernel != 1) return true;
+  return g <= kMaxBucketKeys && (ctx->opt_rank_kernel >= 2 || (ctx->opt_rank_kernel == 0 && g > 256));
+}
+
 // stream-ordered: the caller states the longest column (include/plaidhip.h), nothing is read back
 int launch_colranks_csc_f64(plaidhip_ctx* ctx, const int32_t* Xp, const double* Xx, int32_t n, int32_t max_col_nnz,
                             int ties, int is_signed, double power, double* Rx, double* colmax) {

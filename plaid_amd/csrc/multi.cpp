@@ -16,6 +16,7 @@
 // runs at the link rate (~57 GB/s) and the kernels of a column panel start as soon as the panel has landed.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -293,10 +294,12 @@ struct Shared {
   // shard 0's T = Gt [fc, fc^2] and F = [fc, fc^2] (leading dimension even_ld(g)); a dgCMatrix's per-shard stored-value
   // sums go to row_sum
   std::vector<double> chain_x, chain_s, chain_q, pt_T, pt_F;
+  // replaid.ssgsea.exact with norm: a NaN among the scores of any shard (its min / max go to xmin / xmax)
+  bool es_nan = false;
 };
 
 struct Call {
-  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test
+  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test, 8 ssgsea.exact
   const int32_t* Xp;
   const int32_t* Xi;
   const double* X;   // dense values or CSC @x
@@ -316,6 +319,7 @@ struct Call {
   double tau = 0.0;                 // gsva
   int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded
   int* removed_log2 = nullptr;      // scse output (may be null)
+  int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
   // method 7, plaid.test: the arguments of plaidhip_plaid_test and the group sizes of y
   const int32_t* y = nullptr;
   const double* gsetX = nullptr;
@@ -599,11 +603,154 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 }
 
 
+// one device's part of replaid.ssgsea.exact (method 8, kernels_walk.hip): the operands of its columns, the crossprods
+// C = G'Q (the exact rank route) and, for alpha != 0, A = G'P and B = G'W (fp64), the pinned epilogue.  The only coupling
+// between the shards is the range of all scores behind norm = TRUE, combined on the host.
+int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  int rc = PLAIDHIP_OK;
+  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
+  auto step = [&](const std::function<int()>& fn) {
+    if (!live()) return;
+    try {
+      rc = fn();
+    } catch (...) {
+      rc = on_exception();
+    }
+    if (rc != PLAIDHIP_OK) sh.abort.store(1);
+  };
+  int32_t lo = 0, nloc = 0;
+  shard_columns(c, ndev, k, &lo, &nloc);
+  const int32_t g = c.g, m = c.m;
+  const bool sparse = c.Xp != nullptr;
+  const bool need_w = c.alpha != 0.0;
+  const int64_t ld = g;
+  // the scores are fp64 in every mode: the crossprods stay on the fp64 kernels whatever precision the context was given
+  const int saved_precision = ctx->precision;
+  ctx->precision = PLAIDHIP_PRECISION_F64;
+  plaidhip_geneset* gs = nullptr;
+  // the large buffers stay with the context between calls (ctx_buffer), as the other scorers' do: operands [Q | W | P |
+  // rank scratch] in one, scores [S | A | B] in another
+  CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dops{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
+  DevBuf dk, dpart;
+  HomeBuffer home;
+  double *Q = nullptr, *W = nullptr, *P = nullptr, *scratch = nullptr, *A = nullptr, *B = nullptr;
+  uint32_t* d_colnan = nullptr;
+  double* d_range = nullptr;   // {min, max, any NaN} of the shard's scores
+  std::vector<int32_t> kset((size_t)m), ploc;
+  for (int32_t j = 0; j < m; ++j) kset[(size_t)j] = c.Gp[j + 1] - c.Gp[j];   // members after the alignment
+
+  // ---- upload, operands ---------------------------------------------------------------------------------------------------
+  step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    const size_t nl = (size_t)std::max(nloc, 1);
+    PH_TRY(dsmall.alloc(64 + nl * 4));
+    d_range = dsmall.as<double>();
+    d_colnan = reinterpret_cast<uint32_t*>(dsmall.as<char>() + 64);
+    const size_t nscores = (size_t)m * nl;
+    PH_TRY(dS.alloc(nscores * 8 * (need_w ? 3 : 1)));
+    if (nloc == 0) return PLAIDHIP_OK;
+    if (need_w) {
+      A = dS.as<double>() + nscores;
+      B = A + nscores;
+    }
+    PH_TRY(dk.alloc((size_t)m * 4));
+    PH_HIP(hipMemcpyAsync(dk.p, kset.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dpart.alloc((size_t)ssgsea_exact_part_blocks(ctx, (int64_t)m * nloc) * 24));
+    const int64_t z0 = sparse ? c.Xp[lo] : 0;
+    const int64_t zx = sparse ? (int64_t)c.Xp[lo + nloc] - z0 : 0;
+    const size_t col = (size_t)ld * nloc;
+    const size_t nscratch = sparse ? 3 * (size_t)std::max<int64_t>(zx, 1) : 2 * col;
+    PH_TRY(dops.alloc((col * (need_w ? 3 : 1) + nscratch) * 8));
+    Q = dops.as<double>();
+    if (need_w) {
+      W = Q + col;
+      P = W + col;
+    }
+    scratch = Q + col * (need_w ? 3 : 1);
+    if (!sparse) {
+      PH_TRY(dX.alloc((size_t)ld * nloc * 8));
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
+                              (size_t)g * 8, nloc, nullptr));
+      PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), ld, nullptr, nullptr, g, nloc, 0, 0, c.alpha, Q, W, P, ld, scratch,
+                                          d_colnan));
+    } else {
+      ploc.resize((size_t)nloc + 1);
+      for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
+      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
+      PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
+      PH_TRY(dX.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
+      PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), dXi.as<int32_t>(), g, nloc,
+                                          host_max_col_nnz(ploc.data(), nloc), zx, c.alpha, Q, W, P, ld, scratch, d_colnan));
+    }
+    home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
+    return PLAIDHIP_OK;
+  });
+
+  // ---- crossprods, epilogue ---------------------------------------------------------------------------------------------
+  step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nloc == 0) return PLAIDHIP_OK;
+    // q holds integers in [1, N]: the rank route's u16 staging when 2 N fits, integer sums either way
+    const int xk = 2 * (int64_t)g < 65536 ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
+    PH_TRY(launch_spmm_dense_f64(ctx, gs, Q, ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dS.as<double>(), m, nullptr, xk));
+    if (need_w) {
+      PH_TRY(launch_spmm_dense_f64(ctx, gs, P, ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, A, m, nullptr));
+      PH_TRY(launch_spmm_dense_f64(ctx, gs, W, ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, B, m, nullptr));
+    }
+    return launch_ssgsea_exact_epilogue(ctx, A, B, dS.as<double>(), m, m, nloc, dk.as<int32_t>(), g, c.scale, d_colnan,
+                                        dpart.as<double>(), d_range);
+  });
+
+  // ---- norm: es / diff(range(es)) over the whole m x n result; one NaN anywhere makes every score NaN -------------------
+  if (c.normalize) {
+    double mm[3] = {INFINITY, -INFINITY, 0.0};
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_HIP(hipMemcpyAsync(mm, d_range, 24, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      return PLAIDHIP_OK;
+    });
+    {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      if (nloc > 0 && rc == PLAIDHIP_OK) {
+        sh.xmin = mm[0] < sh.xmin ? mm[0] : sh.xmin;
+        sh.xmax = mm[1] > sh.xmax ? mm[1] : sh.xmax;
+        sh.es_nan = sh.es_nan || mm[2] != 0.0;
+      }
+    }
+    sh.rv.arrive_and_wait();
+    const double range = sh.es_nan ? std::numeric_limits<double>::quiet_NaN() : sh.xmax - sh.xmin;
+    step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      return launch_ssgsea_exact_norm(ctx, dS.as<double>(), m, m, nloc, range);
+    });
+  }
+
+  // ---- the score shard goes home ----------------------------------------------------------------------------------------
+  step([&]() -> int {
+    if (nloc > 0) PH_TRY(home.copy(ctx, dS.p));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+  ctx->precision = saved_precision;
+  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
+    hipStreamSynchronize(ctx->stream);
+    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
+  }
+  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
 // one device's part of a sharded replaid.ucell / aucell / scse / gsva (methods 3 - 6).  The same phases as the context
 // entries (api.cpp: plaidhip_ucell ...), with the quantities that couple the samples combined on the host in between:
 // max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the z
 // row transform (:341-343) and the medians' flags and mean(medx) (:554-575).
 int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  if (c.method == 8) return ssgsea_exact_worker(ctx, c, ndev, k, sh);
   int rc = PLAIDHIP_OK;
   auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
   auto step = [&](const std::function<int()>& fn) {
@@ -1288,6 +1435,39 @@ int run_sharded(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* 
   return run_call(ctxs, ndev, c);
 }
 
+// replaid.ssgsea.exact's argument checks (every entry point runs them before a device is touched)
+int check_ssgsea_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                            const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, const double* S_out) {
+  PH_REQUIRE(std::isfinite(alpha), "ssgsea_exact: alpha must be finite (got %g)", alpha);
+  PH_TRY(check_host_common(Gp, g, n, m));
+  PH_REQUIRE(g < (1 << 26), "ssgsea_exact: nrow(X) = %d (at most 2^26 - 1 rows)", g);
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Gi != nullptr || Gp[m] == 0, "ssgsea_exact: null Gi");
+  PH_REQUIRE(X_or_x != nullptr || (Xp != nullptr && Xp[n] == 0), "ssgsea_exact: null X");
+  PH_REQUIRE(S_out != nullptr, "ssgsea_exact: null S_out");
+  if (Xp != nullptr) {
+    PH_TRY(check_host_csc(Xp, Xi, g, n));
+    PH_REQUIRE(Xp[n] == 0 || Xi != nullptr, "ssgsea_exact: null Xi");
+    for (int32_t c = 0; c < n; ++c)   // the expansion walks the rows of a column in order (kernels_walk.hip)
+      for (int32_t q = Xp[c] + 1; q < Xp[c + 1]; ++q)
+        PH_REQUIRE(Xi[q] > Xi[q - 1], "ssgsea_exact: row indices of column %d are not increasing (Xi[%d] = %d after %d)", c, q,
+                   Xi[q], Xi[q - 1]);
+  }
+  return PLAIDHIP_OK;
+}
+
+int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                     int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
+                     double* S_out) {
+  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
+  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  Call c{8, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, norm ? 1 : 0, alpha, S_out};
+  c.scale = scale ? 1 : 0;
+  return run_call(ctxs, ndev, c);
+}
+
 }  // namespace plaidhip
 
 // ---- multi-device entry points (include/plaidhip.h) ---------------------------------------------------------------------
@@ -1476,6 +1656,43 @@ int plaidhip_debug_plaid_test_sharded_on_one_device(int device, int nshards, int
     if (cx) plaidhip_finalize(cx);
   if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
   return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h): plaidhip_ssgsea_exact_multi's engine with `nshards` contexts on ONE device.
+// fail_shard >= 0: that shard fails in its crossprod phase (the call must return an error, not hang).
+int plaidhip_debug_ssgsea_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                      const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                      const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                                      int norm, double* S_out) try {
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_ssgsea_exact_sharded: nshards = %d", nshards);
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
+  int rc = PLAIDHIP_OK;
+  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
+    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
+    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
+  }
+  if (rc == PLAIDHIP_OK) rc = run_ssgsea_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
+  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
+  for (plaidhip_ctx* cx : ctxs)
+    if (cx) plaidhip_finalize(cx);
+  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
+  return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                int norm, double* S_out) try {
+  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
+  if (devices != nullptr)
+    for (int k = 0; k < ndev; ++k)
+      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_multi_set_precision(int mode) try {

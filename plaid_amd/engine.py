@@ -221,6 +221,20 @@ class Context:
         check(self.lib.plaidhip_dev_colranks_csc_dense_nz_f64(self.handle, Xp, Xi, Xx, int(g), int(n), int(max_col_nnz),
                                                               TIES[ties], int(signed), power, Rx_scratch, R, int(ldr), colmax))
 
+    def dev_ssgsea_exact_operands(self, X: int, ldx: int, g: int, n: int, alpha: float, Q: int, ldq: int, scratch: int,
+                                  colnan: int, W: int | None = None, P: int | None = None):
+        """replaid.ssgsea.exact's operands of dense columns: Q = last ranks, W = average ranks ^ alpha, P = W * Q (W, P
+        needed when alpha != 0), colnan[c] = 1 for a column with a NaN; scratch: 2 ldq n doubles"""
+        check(self.lib.plaidhip_dev_ssgsea_exact_operands_f64(self.handle, X, int(ldx), int(g), int(n), float(alpha), Q, W, P,
+                                                              int(ldq), scratch, colnan))
+
+    def dev_ssgsea_exact_operands_csc(self, Xp: int, Xi: int, Xx: int, g: int, n: int, max_col_nnz: int, nnz: int,
+                                      alpha: float, Q: int, ldq: int, scratch: int, colnan: int, W: int | None = None,
+                                      P: int | None = None):
+        """the same for the device slots of a dgCMatrix (dense results, zeros ranked); scratch: 3 nnz doubles"""
+        check(self.lib.plaidhip_dev_ssgsea_exact_operands_csc_f64(self.handle, Xp, Xi, Xx, int(g), int(n), int(max_col_nnz),
+                                                                  int(nnz), float(alpha), Q, W, P, int(ldq), scratch, colnan))
+
     def dev_minflags(self, S: int, count: int, flags: int):
         check(self.lib.plaidhip_dev_minflags(self.handle, S, count, flags))
 
@@ -430,6 +444,18 @@ def _scse(self, X, Gp, Gi, remove_log2=None, score_mean=False):
     return S
 
 
+def _ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False):
+    """plaidhip_ssgsea_exact: the original ssGSEA statistic (gao.ssgsea, single = TRUE) for any alpha; X dense or scipy
+    CSC (scored as its dense form), G aligned to X's rows"""
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    check(self.lib.plaidhip_ssgsea_exact(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha),
+                                         int(bool(scale)), int(bool(norm)), _np_ptr(S)))
+    return S
+
+
 def _plaid_test(self, X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
     """plaidhip_plaid_test: returns sets x 6 (gsetFC, p.one, p.two, p.lm, p.meta, q.meta), G's column order"""
     X = _as_f64_fortran(X)
@@ -532,6 +558,7 @@ Context.plaid_test_csc = _plaid_test_csc
 Context.ucell = _ucell
 Context.aucell = _aucell
 Context.scse = _scse
+Context.ssgsea_exact = _ssgsea_exact
 
 _default_ctx: Context | None = None
 
@@ -595,6 +622,19 @@ def ssgsea_multi(X, Gp, Gi, alpha=0.0, devices=1) -> np.ndarray:
     S = np.empty((m, n), dtype=np.float64, order="F")
     dp, nd, dkeep = _devices_arg(devices)
     check(lib.plaidhip_ssgsea_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), _np_ptr(S)))
+    return S
+
+
+def ssgsea_exact_multi(X, Gp, Gi, alpha=0.25, scale=True, norm=False, devices=1) -> np.ndarray:
+    """replaid.ssgsea.exact (Context.ssgsea_exact) with the sample columns sharded over `devices`"""
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_ssgsea_exact_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha),
+                                          int(bool(scale)), int(bool(norm)), _np_ptr(S)))
     return S
 
 

@@ -223,6 +223,25 @@ replaid.ssgsea <- function(X, matG, alpha = 0) {
   else { D <- as.matrix(X); storage.mode(D) <- "double"; list(NULL, NULL, D) }
 }
 
+## The original single-sample GSEA statistic (gao.ssgsea with single = TRUE) for any alpha -- replaid.ssgsea is exact at
+## alpha = 0 only (R/plaid.R:233-234, 247-248).  In closed form on the device: with average ranks r, q = rank(x,
+## ties = "last") and w = r^alpha per sample, a set with k members scores sum(w q) / sum(w) - (T - sum(q)) / (N - k),
+## T = N (N + 1) / 2, divided by N with scale and by diff(range(es)) of the whole result with norm.  Differs from
+## gao.ssgsea on purpose in one case: a sample column holding an NA scores NA for every set, at alpha = 0 too.
+replaid.ssgsea.exact <- function(X, matG, alpha = 0.25, scale = TRUE, norm = FALSE) {
+  pat <- .aligned_pattern(X, matG)
+  if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
+  .session()
+  xa <- .x_args(X)
+  dev <- .devices()
+  S <- if (length(dev) > 1L) .Call("R_plaidhip_ssgsea_exact_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X),
+                                   pat$Gp, pat$Gi, as.double(alpha), as.logical(scale), as.logical(norm), PACKAGE = "plaidhip")
+       else .Call("R_plaidhip_ssgsea_exact", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, as.double(alpha),
+                  as.logical(scale), as.logical(norm), PACKAGE = "plaidhip")
+  dimnames(S) <- list(colnames(matG), colnames(X))
+  S
+}
+
 replaid.ucell <- function(X, matG, rmax = 1500) {
   pat <- .aligned_pattern(X, matG)
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
