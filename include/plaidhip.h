@@ -258,6 +258,16 @@ int plaidhip_dev_ssgsea_exact_operands_csc_f64(plaidhip_ctx* ctx, const void* Xp
                                                int32_t n, int32_t max_col_nnz, int64_t nnz, double alpha, void* Q, void* W,
                                                void* P, int64_t ldq, void* scratch, void* colnan);
 
+/* The walk of plaidhip_ssgsea_exact_ks on operands already on the device (what plaidhip_dev_ssgsea_exact_operands*_f64
+ * wrote: Q, W with leading dimension ldq, colnan), stream-ordered, no read-back.  Gp (m + 1) / Gi (Gp[m]) are DEVICE
+ * copies of the aligned pattern (row indices in 0..g-1, distinct inside a set).  W is not read at alpha = 0 and may be
+ * NULL then.  S: m x n fp64, leading dimension lds; no norm (the caller divides).  For alpha != 0 the column's weights
+ * are first scattered into walk order, into g n doubles of the context's workspace.  g <= PLAIDHIP_GSEA_KS_MAX_GENES,
+ * else PLAIDHIP_EUNSUPPORTED with nothing launched.                                                                    */
+int plaidhip_dev_gsea_ks_f64(plaidhip_ctx* ctx, const void* Q, const void* W, int64_t ldq, const void* colnan, int32_t g,
+                             int32_t n, const void* Gp, const void* Gi, int32_t m, double alpha, int scale, void* S,
+                             int64_t lds);
+
 /* normalize_medians() (R/plaid.R:554-575) in three phases so that a sample-sharded host
  * can all-reduce between them:
  *   1. flags  : plaidhip_dev_minflags   (or the SpMM epilogue's `flags`)  -> ignore.zero
@@ -395,6 +405,27 @@ int plaidhip_ssgsea_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
 int plaidhip_ssgsea_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm, double* S_out);
 
+/* replaid.ssgsea.exact(..., single = FALSE): the running sum's value of LARGEST MAGNITUDE instead of its sum -- the classic
+ * GSEA enrichment score (gao.ssgsea's second branch, experiments/R/functions.R:568-572).  Arguments, checks, NaN rules and
+ * norm as for plaidhip_ssgsea_exact; r, q, w as there.  The walk visits the genes at pos = N + 1 - q (1 first).  For a set
+ * with k aligned members sorted by pos ascending, t = 1..k, in fp64 and in exactly these operations:
+ *     cw_t = w_1 + ... + w_t (cw_0 = 0);  B = cw_k;  miss_t = (double)(pos_t - t) / (double)(N - k)
+ *     after_t  = cw_t / B - miss_t                          (the running sum at position pos_t)
+ *     before_t = cw_{t-1} / B - miss_t   when pos_t >= 2    (the running sum at position pos_t - 1)
+ *     scale: each candidate is divided by (double)N before any comparison
+ * The running sum falls linearly between two hits, so its extremes are among these 2k candidates.  They are visited in
+ * position order (before_1, after_1, before_2, ...); the best starts at 0 and a later candidate replaces it only when its
+ * absolute value is strictly larger: step_cdf_diff[which.max(abs(step_cdf_diff))], first maximum and sign included.
+ * norm divides by max - min over the whole m x n result.  k = 0 and k = N give NaN; a sample column holding a NaN scores
+ * NaN for every set; alpha must be finite.  A candidate holds no product, so no contraction changes a bit.  At alpha = 0
+ * (cw_t = t, B = k) and alpha = 1 every candidate is exact; for other alphas cw_t and B are summed in an order that
+ * depends on k and the positions alone (never on the sharding).  One route for every k (a bitmap walk, kernels_ks.hip);
+ * its map bounds nrow(X): g > PLAIDHIP_GSEA_KS_MAX_GENES returns PLAIDHIP_EUNSUPPORTED before any device work.        */
+#define PLAIDHIP_GSEA_KS_MAX_GENES 131072
+int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                             int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
+                             double* S_out);
+
 /* ---- several GPUs of one node from ONE host process (the R session): multi.cpp ----------------------
  * The sample columns are cut into ndev contiguous shards (plaidhip_shard_bounds); a host thread per device
  * moves its shard over its own PCIe link (pipelined through pinned staging), runs the same kernels, and the
@@ -424,6 +455,11 @@ int plaidhip_ssgsea_multi(const int* devices, int ndev, const int32_t* Xp, const
 int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                                 int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
                                 int norm, double* S_out);
+/* plaidhip_ssgsea_exact_ks over several devices, bit for bit (the walk is per column; norm's range is combined on the
+ * host).  The argument checks, the bound on g among them, and the device list's run before any device is touched.     */
+int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                   int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
+                                   int scale, int norm, double* S_out);
 /* replaid.ucell / aucell / scse / gsva over several devices: the arguments and results of plaidhip_ucell, plaidhip_aucell,
  * plaidhip_scse and plaidhip_gsva (rowtf = 0, "z"), X dense or a dgCMatrix as above.  The argument checks run before any
  * device is touched.  What couples the shards is combined on the host: max(rX) (R/plaid.R:278, 306, 354), the min / max

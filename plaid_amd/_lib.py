@@ -79,6 +79,7 @@ SIGNATURES = {
     "plaidhip_dev_ssgsea_exact_operands_f64": [_vp, _vp, _i64, _i32, _i32, _f64, _vp, _vp, _vp, _i64, _vp, _vp],
     "plaidhip_dev_ssgsea_exact_operands_csc_f64": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _f64, _vp, _vp, _vp, _i64, _vp,
                                                    _vp],
+    "plaidhip_dev_gsea_ks_f64": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp, _i64],
     "plaidhip_plaid_dense": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp],
     "plaidhip_plaid_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp],
     "plaidhip_crossprod_weighted_dense": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp],
@@ -92,6 +93,7 @@ SIGNATURES = {
     "plaidhip_ssgsea_dense": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
     "plaidhip_ssgsea_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
     "plaidhip_ssgsea_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
+    "plaidhip_ssgsea_exact_ks": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_shard_bounds": [_i64, _int, _int, C.POINTER(_i64), C.POINTER(_i64)],
     "plaidhip_limit": [_int, C.POINTER(_i64)],
     "plaidhip_plaid_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp],
@@ -103,6 +105,7 @@ SIGNATURES = {
     "plaidhip_scse_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, C.POINTER(_int)],
     "plaidhip_gsva_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp],
     "plaidhip_ssgsea_exact_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
+    "plaidhip_ssgsea_exact_ks_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_plaid_test_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _int, _int, _vp],
     "plaidhip_multi_finalize": [],
     "plaidhip_multi_set_precision": [_int],

@@ -246,17 +246,18 @@ def replaid_ssgsea(X, matG, alpha=0, ctx: Context | None = None):
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
-def replaid_ssgsea_exact(X, matG, alpha=0.25, scale=True, norm=False, ctx: Context | None = None):
+def replaid_ssgsea_exact(X, matG, alpha=0.25, scale=True, norm=False, single=True, ctx: Context | None = None):
     """replaid.ssgsea.exact(): the original single-sample GSEA statistic (gao.ssgsea with single = TRUE) for any alpha,
     in closed form on the device (include/plaidhip.h: plaidhip_ssgsea_exact).  G is aligned to X's rows as plaid()
-    aligns it; k counts the aligned members.  A dgCMatrix scores as as.matrix(X) would."""
+    aligns it; k counts the aligned members.  A dgCMatrix scores as as.matrix(X) would.  single = False: the running
+    sum's value of largest magnitude (the classic GSEA enrichment score; plaidhip_ssgsea_exact_ks) instead of its sum."""
     X, matG = as_named(X), as_named(matG)
     pat = aligned_pattern(X, matG)
     if pat is None:
         _message("[plaid] ERROR. No overlapping features.")
         return None
     ctx = ctx or default_context()
-    S = ctx.ssgsea_exact(X.values, pat[0], pat[1], float(alpha), scale, norm)
+    S = ctx.ssgsea_exact(X.values, pat[0], pat[1], float(alpha), scale, norm, single)
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 

@@ -708,6 +708,28 @@ int plaidhip_dev_ssgsea_exact_operands_csc_f64(plaidhip_ctx* ctx, const void* Xp
                                       static_cast<uint32_t*>(colnan));
 } catch (...) { return plaidhip::on_exception(); }
 
+// the walk of replaid.ssgsea.exact(single = FALSE) on device operands (kernels_ks.hip), stream-ordered
+int plaidhip_dev_gsea_ks_f64(plaidhip_ctx* ctx, const void* Q, const void* W, int64_t ldq, const void* colnan, int32_t g,
+                             int32_t n, const void* Gp, const void* Gi, int32_t m, double alpha, int scale, void* S,
+                             int64_t lds) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(std::isfinite(alpha), "gsea_ks: alpha must be finite (got %g)", alpha);
+  PH_REQUIRE(g > 0 && n >= 0 && m >= 0 && ldq >= g && lds >= m, "gsea_ks: bad dims g=%d n=%d m=%d ldq=%lld lds=%lld", g, n, m,
+             (long long)ldq, (long long)lds);
+  PH_TRY(check_gsea_ks_genes(g));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Q && colnan && Gp && Gi && S, "gsea_ks: null Q/colnan/Gp/Gi/S");
+  PH_REQUIRE(alpha == 0.0 || W != nullptr, "gsea_ks: W is needed when alpha != 0");
+  double* Wpos = nullptr;
+  if (alpha != 0.0) {
+    PH_TRY(ensure_workspace(ctx, (size_t)ldq * n * 8));
+    Wpos = static_cast<double*>(ctx->ws);
+  }
+  return launch_gsea_ks(ctx, static_cast<const double*>(Q), static_cast<const double*>(W), Wpos, ldq,
+                        static_cast<const uint32_t*>(colnan), g, n, static_cast<const int32_t*>(Gp),
+                        static_cast<const int32_t*>(Gi), m, alpha, scale, static_cast<double*>(S), lds);
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_dev_minflags(plaidhip_ctx* ctx, const void* S, int64_t count, void* flags) try {
   PH_CTX(ctx);
   PH_REQUIRE(flags != nullptr && count >= 0, "minflags: bad arguments");
@@ -977,6 +999,17 @@ int plaidhip_ssgsea_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* X
   PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
   PH_HIP(hipSetDevice(ctx->device));
   return run_ssgsea_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
+} catch (...) { return plaidhip::on_exception(); }
+
+// replaid.ssgsea.exact(single = FALSE): the same engine with the walk kernel of kernels_ks.hip
+int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                             const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
+                             double* S_out) try {
+  PH_REQUIRE(ctx != nullptr, "null plaidhip_ctx");
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  PH_TRY(check_gsea_ks_genes(g));
+  PH_HIP(hipSetDevice(ctx->device));
+  return run_ssgsea_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -472,9 +472,18 @@ int launch_ssgsea_exact_norm(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t 
 // multi.cpp: replaid.ssgsea.exact on ndev contexts (one: plaidhip_ssgsea_exact); its argument checks, which touch no device
 int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                      int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
-                     double* S_out);
+                     double* S_out, int single = 1);
 int check_ssgsea_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                             const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, const double* S_out);
+int check_gsea_ks_genes(int32_t g);   // single = FALSE: PLAIDHIP_EUNSUPPORTED above PLAIDHIP_GSEA_KS_MAX_GENES rows
+// kernels_ks.hip: replaid.ssgsea.exact(single = FALSE), the walk's value of largest magnitude (include/plaidhip.h:
+// plaidhip_ssgsea_exact_ks) from the operands above; Gp / Gi on the device; Wpos: ldq n doubles of scratch when alpha != 0
+// (the weights in walk order; may alias nothing the kernel reads).  g > PLAIDHIP_GSEA_KS_MAX_GENES: PLAIDHIP_EUNSUPPORTED.
+int launch_gsea_ks(plaidhip_ctx* ctx, const double* Q, const double* W, double* Wpos, int64_t ldq, const uint32_t* colnan,
+                   int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, double* S,
+                   int64_t lds);
+// range_out[3] = {min, max, any NaN} of the m x n scores; part: 3 ssgsea_exact_part_blocks(m n) doubles
+int launch_gsea_ks_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 int launch_col_medians(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n,

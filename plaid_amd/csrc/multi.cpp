@@ -320,6 +320,7 @@ struct Call {
   int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded
   int* removed_log2 = nullptr;      // scse output (may be null)
   int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
+  int single = 1;                   // ssgsea.exact: 1 the walk's sum (closed form), 0 its value of largest magnitude (kernels_ks.hip)
   // method 7, plaid.test: the arguments of plaidhip_plaid_test and the group sizes of y
   const int32_t* y = nullptr;
   const double* gsetX = nullptr;
@@ -606,6 +607,8 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 // one device's part of replaid.ssgsea.exact (method 8, kernels_walk.hip): the operands of its columns, the crossprods
 // C = G'Q (the exact rank route) and, for alpha != 0, A = G'P and B = G'W (fp64), the pinned epilogue.  The only coupling
 // between the shards is the range of all scores behind norm = TRUE, combined on the host.
+// single = FALSE: the same operands, then the walk kernel of kernels_ks.hip in place of the crossprods and the epilogue
+// (P's columns, which it has no use for, take the weights in walk order).
 int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   int rc = PLAIDHIP_OK;
   auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
@@ -631,8 +634,9 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
   // the large buffers stay with the context between calls (ctx_buffer), as the other scorers' do: operands [Q | W | P |
   // rank scratch] in one, scores [S | A | B] in another
   CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dops{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
-  DevBuf dk, dpart;
+  DevBuf dk, dpart, dGp, dGi;
   HomeBuffer home;
+  const bool ks = c.single == 0;
   double *Q = nullptr, *W = nullptr, *P = nullptr, *scratch = nullptr, *A = nullptr, *B = nullptr;
   uint32_t* d_colnan = nullptr;
   double* d_range = nullptr;   // {min, max, any NaN} of the shard's scores
@@ -648,9 +652,16 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
     d_range = dsmall.as<double>();
     d_colnan = reinterpret_cast<uint32_t*>(dsmall.as<char>() + 64);
     const size_t nscores = (size_t)m * nl;
-    PH_TRY(dS.alloc(nscores * 8 * (need_w ? 3 : 1)));
+    PH_TRY(dS.alloc(nscores * 8 * (need_w && !ks ? 3 : 1)));
     if (nloc == 0) return PLAIDHIP_OK;
-    if (need_w) {
+    if (ks) {
+      const size_t z = (size_t)c.Gp[m];
+      PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
+      PH_TRY(dGi.alloc(std::max<size_t>(z, 1) * 4));
+      PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      if (z > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, z * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (need_w && !ks) {
       A = dS.as<double>() + nscores;
       B = A + nscores;
     }
@@ -694,6 +705,11 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
   step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
+    if (ks) {
+      PH_TRY(launch_gsea_ks(ctx, Q, W, P, ld, d_colnan, g, nloc, dGp.as<int32_t>(), dGi.as<int32_t>(), m, c.alpha, c.scale,
+                            dS.as<double>(), m));
+      return launch_gsea_ks_range(ctx, dS.as<double>(), m, m, nloc, dpart.as<double>(), d_range);
+    }
     // q holds integers in [1, N]: the rank route's u16 staging when 2 N fits, integer sums either way
     const int xk = 2 * (int64_t)g < 65536 ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
     PH_TRY(launch_spmm_dense_f64(ctx, gs, Q, ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dS.as<double>(), m, nullptr, xk));
@@ -1456,15 +1472,26 @@ int check_ssgsea_exact_args(const int32_t* Xp, const int32_t* Xi, const double* 
   return PLAIDHIP_OK;
 }
 
+// the bound of the walk kernel's bitmap (kernels_ks.hip), checked before a device is touched
+int check_gsea_ks_genes(int32_t g) {
+  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("ssgsea_exact_ks: nrow(X) = %d (at most %d rows with single = FALSE)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  return PLAIDHIP_OK;
+}
+
 int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                      int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
-                     double* S_out) {
+                     double* S_out, int single) {
   PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
   for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
   PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  if (!single) PH_TRY(check_gsea_ks_genes(g));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   Call c{8, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, norm ? 1 : 0, alpha, S_out};
   c.scale = scale ? 1 : 0;
+  c.single = single ? 1 : 0;
   return run_call(ctxs, ndev, c);
 }
 
@@ -1693,6 +1720,45 @@ int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp,
   std::vector<plaidhip_ctx*> ctxs;
   PH_TRY(multi_contexts(devices, ndev, ctxs));
   return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h): plaidhip_ssgsea_exact_ks_multi's engine with `nshards` contexts on ONE device.
+// fail_shard >= 0: that shard fails in its crossprod phase (the call must return an error, not hang).
+int plaidhip_debug_ssgsea_exact_ks_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                      const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                      const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                                      int norm, double* S_out) try {
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_ssgsea_exact_ks_sharded: nshards = %d", nshards);
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  PH_TRY(check_gsea_ks_genes(g));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
+  int rc = PLAIDHIP_OK;
+  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
+    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
+    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
+  }
+  if (rc == PLAIDHIP_OK) rc = run_ssgsea_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
+  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
+  for (plaidhip_ctx* cx : ctxs)
+    if (cx) plaidhip_finalize(cx);
+  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
+  return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                int norm, double* S_out) try {
+  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
+  if (devices != nullptr)
+    for (int k = 0; k < ndev; ++k)
+      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
+  PH_TRY(check_gsea_ks_genes(g));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_multi_set_precision(int mode) try {

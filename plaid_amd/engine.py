@@ -235,6 +235,14 @@ class Context:
         check(self.lib.plaidhip_dev_ssgsea_exact_operands_csc_f64(self.handle, Xp, Xi, Xx, int(g), int(n), int(max_col_nnz),
                                                                   int(nnz), float(alpha), Q, W, P, int(ldq), scratch, colnan))
 
+    def dev_gsea_ks(self, Q: int, ldq: int, colnan: int, g: int, n: int, Gp: int, Gi: int, m: int, alpha: float,
+                    scale: bool, S: int, lds: int, W: int | None = None):
+        """the walk of replaid.ssgsea.exact(single = FALSE) on device operands (dev_ssgsea_exact_operands' Q, W, colnan)
+        and a device copy of the aligned pattern: S (m x n) = the running sum's value of largest magnitude; W is needed
+        when alpha != 0"""
+        check(self.lib.plaidhip_dev_gsea_ks_f64(self.handle, Q, W, int(ldq), colnan, int(g), int(n), Gp, Gi, int(m),
+                                                float(alpha), int(bool(scale)), S, int(lds)))
+
     def dev_minflags(self, S: int, count: int, flags: int):
         check(self.lib.plaidhip_dev_minflags(self.handle, S, count, flags))
 
@@ -444,15 +452,17 @@ def _scse(self, X, Gp, Gi, remove_log2=None, score_mean=False):
     return S
 
 
-def _ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False):
+def _ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False, single=True):
     """plaidhip_ssgsea_exact: the original ssGSEA statistic (gao.ssgsea, single = TRUE) for any alpha; X dense or scipy
-    CSC (scored as its dense form), G aligned to X's rows"""
+    CSC (scored as its dense form), G aligned to X's rows.  single = False (plaidhip_ssgsea_exact_ks): the running sum's
+    value of largest magnitude, the classic GSEA enrichment score, instead of its sum"""
     xp, xi, xv, g, n, keep = _x_args(X)
     Gp, Gi = _as_i32(Gp), _as_i32(Gi)
     m = len(Gp) - 1
     S = np.empty((m, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_ssgsea_exact(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha),
-                                         int(bool(scale)), int(bool(norm)), _np_ptr(S)))
+    fn = self.lib.plaidhip_ssgsea_exact if single else self.lib.plaidhip_ssgsea_exact_ks
+    check(fn(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), int(bool(scale)), int(bool(norm)),
+             _np_ptr(S)))
     return S
 
 
@@ -625,16 +635,17 @@ def ssgsea_multi(X, Gp, Gi, alpha=0.0, devices=1) -> np.ndarray:
     return S
 
 
-def ssgsea_exact_multi(X, Gp, Gi, alpha=0.25, scale=True, norm=False, devices=1) -> np.ndarray:
-    """replaid.ssgsea.exact (Context.ssgsea_exact) with the sample columns sharded over `devices`"""
+def ssgsea_exact_multi(X, Gp, Gi, alpha=0.25, scale=True, norm=False, devices=1, single=True) -> np.ndarray:
+    """replaid.ssgsea.exact (Context.ssgsea_exact, either `single`) with the sample columns sharded over `devices`"""
     lib = _lib.load()
     xp, xi, xv, g, n, keep = _x_args(X)
     Gp, Gi = _as_i32(Gp), _as_i32(Gi)
     m = len(Gp) - 1
     S = np.empty((m, n), dtype=np.float64, order="F")
     dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_ssgsea_exact_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha),
-                                          int(bool(scale)), int(bool(norm)), _np_ptr(S)))
+    fn = lib.plaidhip_ssgsea_exact_multi if single else lib.plaidhip_ssgsea_exact_ks_multi
+    check(fn(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), int(bool(scale)), int(bool(norm)),
+             _np_ptr(S)))
     return S
 
 

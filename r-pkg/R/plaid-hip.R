@@ -228,15 +228,30 @@ replaid.ssgsea <- function(X, matG, alpha = 0) {
 ## ties = "last") and w = r^alpha per sample, a set with k members scores sum(w q) / sum(w) - (T - sum(q)) / (N - k),
 ## T = N (N + 1) / 2, divided by N with scale and by diff(range(es)) of the whole result with norm.  Differs from
 ## gao.ssgsea on purpose in one case: a sample column holding an NA scores NA for every set, at alpha = 0 too.
-replaid.ssgsea.exact <- function(X, matG, alpha = 0.25, scale = TRUE, norm = FALSE) {
+## single = FALSE: the running sum's value of largest magnitude instead of its sum -- the classic GSEA enrichment score,
+## step_cdf_diff[which.max(abs(step_cdf_diff))] of gao.ssgsea (first maximum, sign kept) -- from a walk kernel on the
+## device (include/plaidhip.h: plaidhip_ssgsea_exact_ks); nrow(X) at most 131,072 there.
+replaid.ssgsea.exact <- function(X, matG, alpha = 0.25, scale = TRUE, norm = FALSE, single = TRUE) {
   pat <- .aligned_pattern(X, matG)
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
   .session()
+  if (!isTRUE(as.logical(single))) return(.ssgsea_exact_ks(X, matG, pat, alpha, scale, norm))
   xa <- .x_args(X)
   dev <- .devices()
   S <- if (length(dev) > 1L) .Call("R_plaidhip_ssgsea_exact_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X),
                                    pat$Gp, pat$Gi, as.double(alpha), as.logical(scale), as.logical(norm), PACKAGE = "plaidhip")
        else .Call("R_plaidhip_ssgsea_exact", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, as.double(alpha),
+                  as.logical(scale), as.logical(norm), PACKAGE = "plaidhip")
+  dimnames(S) <- list(colnames(matG), colnames(X))
+  S
+}
+
+.ssgsea_exact_ks <- function(X, matG, pat, alpha, scale, norm) {
+  xa <- .x_args(X)
+  dev <- .devices()
+  S <- if (length(dev) > 1L) .Call("R_plaidhip_ssgsea_exact_ks_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X),
+                                   pat$Gp, pat$Gi, as.double(alpha), as.logical(scale), as.logical(norm), PACKAGE = "plaidhip")
+       else .Call("R_plaidhip_ssgsea_exact_ks", xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, as.double(alpha),
                   as.logical(scale), as.logical(norm), PACKAGE = "plaidhip")
   dimnames(S) <- list(colnames(matG), colnames(X))
   S

@@ -256,6 +256,28 @@ SEXP R_plaidhip_ssgsea_exact_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP
   return S;
 }
 
+/* replaid.ssgsea.exact(single = FALSE): the walk's value of largest magnitude */
+SEXP R_plaidhip_ssgsea_exact_ks(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP alpha, SEXP scale,
+                                SEXP norm) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_ssgsea_exact_ks(ctx(), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g), nn, INTEGER(Gp),
+                                 INTEGER(Gi), m, Rf_asReal(alpha), Rf_asLogical(scale), Rf_asLogical(norm), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
+SEXP R_plaidhip_ssgsea_exact_ks_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP alpha,
+                                      SEXP scale, SEXP norm) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_ssgsea_exact_ks_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                       Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(alpha),
+                                       Rf_asLogical(scale), Rf_asLogical(norm), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
 SEXP R_plaidhip_ucell(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP kfull, SEXP rmax) {
   const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
   SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
@@ -431,6 +453,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsva_multi", (DL_FUNC)&R_plaidhip_gsva_multi, 10},
     {"R_plaidhip_ssgsea_exact", (DL_FUNC)&R_plaidhip_ssgsea_exact, 10},
     {"R_plaidhip_ssgsea_exact_multi", (DL_FUNC)&R_plaidhip_ssgsea_exact_multi, 11},
+    {"R_plaidhip_ssgsea_exact_ks", (DL_FUNC)&R_plaidhip_ssgsea_exact_ks, 10},
+    {"R_plaidhip_ssgsea_exact_ks_multi", (DL_FUNC)&R_plaidhip_ssgsea_exact_ks_multi, 11},
     {"R_plaidhip_ucell", (DL_FUNC)&R_plaidhip_ucell, 9},
     {"R_plaidhip_aucell", (DL_FUNC)&R_plaidhip_aucell, 8},
     {"R_plaidhip_scse", (DL_FUNC)&R_plaidhip_scse, 9},
