@@ -268,6 +268,14 @@ int plaidhip_dev_gsea_ks_f64(plaidhip_ctx* ctx, const void* Q, const void* W, in
                              int32_t n, const void* Gp, const void* Gi, int32_t m, double alpha, int scale, void* S,
                              int64_t lds);
 
+/* The walk of plaidhip_gsva_exact on last ranks already on the device (Q of plaidhip_dev_ssgsea_exact_operands*_f64 with
+ * alpha = 0, applied to the row-transformed matrix v; colnan from the same call), stream-ordered, no read-back.  Gp / Gi
+ * are DEVICE copies of the aligned pattern.  S: m x n fp64, leading dimension lds.  For tau != 0 the weight table (g
+ * doubles) is built in the context's workspace first.  g <= PLAIDHIP_GSEA_KS_MAX_GENES, else PLAIDHIP_EUNSUPPORTED with
+ * nothing launched.                                                                                                    */
+int plaidhip_dev_gsva_ks_f64(plaidhip_ctx* ctx, const void* Q, int64_t ldq, const void* colnan, int32_t g, int32_t n,
+                             const void* Gp, const void* Gi, int32_t m, double tau, int max_diff, void* S, int64_t lds);
+
 /* normalize_medians() (R/plaid.R:554-575) in three phases so that a sample-sharded host
  * can all-reduce between them:
  *   1. flags  : plaidhip_dev_minflags   (or the SpMM epilogue's `flags`)  -> ignore.zero
@@ -426,6 +434,37 @@ int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t
                              int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
                              double* S_out);
 
+/* replaid.gsva.exact(X, matG, tau, rowtf, max.diff): the random-walk statistic of GSVA (Haenzelmann et al. 2013), where
+ * replaid.gsva (R/plaid.R:353-356) is a mean of transformed ranks.  rowtf: 0 "z", 1 "ecdf", 2 "none".
+ *  1. Row transform v of X: "z" and "ecdf" are replaid.gsva's own (the launches of plaidhip_gsva_multi's z transform, of
+ *     plaidhip_gsva / plaidhip_gsva_csc's ecdf; a dgCMatrix through the row view, the dense v built on the device);
+ *     "none" takes X as it is, for a caller who brings their own per-gene CDF.
+ *  2. Per sample column with N = g genes: q = rank(v, ties = "last"), the walk visits the genes at pos = N + 1 - q.  This
+ *     is order(v, decreasing = TRUE) with tied genes in row order.  No average ranks are needed.
+ *  3. Weight of the gene at pos: w = |q - N / 2|^tau (GSVA's symmetric rank score abs(seq(N, 1) - N / 2) laid along the
+ *     order), with 0^0 = 1.  N / 2 in fp64: integers for even N, half-integers for odd N.  The weight depends on the
+ *     position alone: one table of N doubles serves every column and every set of the call.
+ *  4. For a set with k aligned members sorted by pos, t = 1..k, in fp64 and in exactly these operations:
+ *         cw_t = w_1 + ... + w_t (cw_0 = 0);  B = cw_k;  miss_t = (double)(pos_t - t) / (double)(N - k)
+ *         after_t = cw_t / B - miss_t;  before_t = cw_{t-1} / B - miss_t  (only where pos_t >= 2)
+ *         mx_pos = max(0, max_t after_t);  mx_neg = min(0, min_t before_t)
+ *     The running sum rises only at a hit and ends at 0, so these hold its extremes.
+ *  5. max_diff != 0: ES = mx_pos + mx_neg.  max_diff == 0: ES = mx_pos > |mx_neg| ? mx_pos : mx_neg (GSVA's rule: equal
+ *     magnitudes return the negative one).
+ *  6. k = 0, k = N and B == 0 (tau > 0 and even N: a set made only of the gene at q = N / 2) give NaN.  A column of v
+ *     holding a NaN scores NaN for every set.  tau must be finite and >= 0, rowtf one of the three; both are refused
+ *     before any device work, as is g > PLAIDHIP_GSEA_KS_MAX_GENES (PLAIDHIP_EUNSUPPORTED).
+ *  7. At tau 0 (cw_t = t, B = k) and 1 every cw_t and B is an exact integer or half-integer sum, a candidate is two
+ *     correctly rounded divisions and a subtraction with no product in it: the bits of the same operations on the host.
+ *     For other tau, cw_t and B are summed in an order that depends on k and the positions only, never on the sharding.
+ * Deliberate differences from the GSVA package: GSVA accumulates the running sum step by step (N roundings; this form
+ * has three per candidate), its B == 0 case leaves whatever the walk held before the NaN, and abs.ranking and the kernel
+ * CDF estimate (kcdf) are not offered.  No normalize_medians (GSVA applies none).  X dense (Xp == NULL) or a dgCMatrix
+ * (rows increasing inside a column), never densified on the host: with "none" its stored values are ranked as
+ * plaidhip_ssgsea_exact ranks them.  fp64 in every precision mode.  S_out: m x n doubles.                              */
+int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                        const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff, double* S_out);
+
 /* ---- several GPUs of one node from ONE host process (the R session): multi.cpp ----------------------
  * The sample columns are cut into ndev contiguous shards (plaidhip_shard_bounds); a host thread per device
  * moves its shard over its own PCIe link (pipelined through pinned staging), runs the same kernels, and the
@@ -460,6 +499,14 @@ int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp,
 int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                                    int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
                                    int scale, int norm, double* S_out);
+/* plaidhip_gsva_exact over several devices, sharded by sample column.  "none" has no coupling between the shards; "z"
+ * chains the row moments as plaidhip_gsva_multi does (dense X: shards of whole 128-column blocks, the one-device bits;
+ * a dgCMatrix: the rows' sums of stored values are added shard by shard, which is exact whenever those sums are);
+ * "ecdf" ranks all samples of a gene together and returns PLAIDHIP_EINVAL when ndev > 1.  The walk is per column.  The
+ * argument checks and the device list's run before any device is touched.                                             */
+int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
+                              int max_diff, double* S_out);
 /* replaid.ucell / aucell / scse / gsva over several devices: the arguments and results of plaidhip_ucell, plaidhip_aucell,
  * plaidhip_scse and plaidhip_gsva (rowtf = 0, "z"), X dense or a dgCMatrix as above.  The argument checks run before any
  * device is touched.  What couples the shards is combined on the host: max(rX) (R/plaid.R:278, 306, 354), the min / max

@@ -336,6 +336,28 @@ def replaid_gsva(X, matG, tau=0, rowtf="z", ctx: Context | None = None):
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
+def replaid_gsva_exact(X, matG, tau=1, rowtf="z", max_diff=True, ctx: Context | None = None):
+    """replaid.gsva.exact(): the random-walk statistic of GSVA (Haenzelmann et al. 2013; include/plaidhip.h:
+    plaidhip_gsva_exact) where replaid.gsva is a mean of transformed ranks.  rowtf "z" / "ecdf" are replaid.gsva's row
+    transforms, "none" takes X as it is (a caller's own per-gene CDF).  The genes of a sample are walked in decreasing
+    order of the transformed value (ties in row order) with the weights |rank - N / 2| ^ tau; max_diff = True adds the
+    walk's largest positive and negative excursion, False returns the larger one (the negative one when equal).  No
+    normalize_medians; GSVA's kernel CDF estimate and abs.ranking are not offered.  tau and rowtf are checked before
+    any device is touched."""
+    from .engine import check_gsva_exact_args
+    tau, _ = check_gsva_exact_args(tau, rowtf)
+    rowtf = rowtf if isinstance(rowtf, str) else rowtf[0]
+    X, matG = as_named(X), as_named(matG)
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    ctx = ctx or default_context()
+    V = _canonical_csc(X.values) if X.is_sparse else X.values   # the CSC slots go to the device: no dense X on the host
+    S = ctx.gsva_exact(V, pat[0], pat[1], tau, rowtf, max_diff)
+    return NamedMatrix(S, matG.colnames, X.colnames)
+
+
 _TEST_BITS = {"one": 1, "two": 2, "lm": 4}
 
 

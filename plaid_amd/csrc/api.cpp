@@ -730,6 +730,29 @@ int plaidhip_dev_gsea_ks_f64(plaidhip_ctx* ctx, const void* Q, const void* W, in
                         static_cast<const int32_t*>(Gi), m, alpha, scale, static_cast<double*>(S), lds);
 } catch (...) { return plaidhip::on_exception(); }
 
+// the walk of replaid.gsva.exact on the device's last ranks (kernels_ks.hip), stream-ordered
+int plaidhip_dev_gsva_ks_f64(plaidhip_ctx* ctx, const void* Q, int64_t ldq, const void* colnan, int32_t g, int32_t n,
+                             const void* Gp, const void* Gi, int32_t m, double tau, int max_diff, void* S, int64_t lds) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(std::isfinite(tau) && tau >= 0.0, "gsva_ks: tau must be finite and >= 0 (got %g)", tau);
+  PH_REQUIRE(g > 0 && n >= 0 && m >= 0 && ldq >= g && lds >= m, "gsva_ks: bad dims g=%d n=%d m=%d ldq=%lld lds=%lld", g, n, m,
+             (long long)ldq, (long long)lds);
+  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("gsva_ks: nrow(X) = %d (at most %d rows)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Q && colnan && Gp && Gi && S, "gsva_ks: null Q/colnan/Gp/Gi/S");
+  double* T = nullptr;
+  if (tau != 0.0) {   // the weight table
+    PH_TRY(ensure_workspace(ctx, (size_t)g * 8));
+    T = static_cast<double*>(ctx->ws);
+  }
+  return launch_gsva_ks(ctx, static_cast<const double*>(Q), ldq, static_cast<const uint32_t*>(colnan), g, n,
+                        static_cast<const int32_t*>(Gp), static_cast<const int32_t*>(Gi), m, tau, max_diff, T,
+                        static_cast<double*>(S), lds);
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_dev_minflags(plaidhip_ctx* ctx, const void* S, int64_t count, void* flags) try {
   PH_CTX(ctx);
   PH_REQUIRE(flags != nullptr && count >= 0, "minflags: bad arguments");
@@ -1312,6 +1335,15 @@ int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
   for (int32_t i = 0; i < g; ++i) { tot1 += F[i]; tot2 += F[(size_t)ldg + i]; }
   return plaidhip_plaid_test_finish(g, m, Gp, T.data(), tot1, tot2, (tests & 4) ? SM.data() : nullptr, n0, n1, tests,
                                     metap_method, out);
+} catch (...) { return plaidhip::on_exception(); }
+
+// replaid.gsva.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, method 9)
+int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                        const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
+                        double* S_out) try {
+  PH_TRY(check_gsva_exact_args(1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
+  PH_CTX(ctx);
+  return run_gsva_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.gsva from the row-transformed zX (dX: g x n, leading dimension ldg) on: the scores in dS (m x n), normalised.

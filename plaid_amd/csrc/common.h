@@ -482,6 +482,16 @@ int check_gsea_ks_genes(int32_t g);   // single = FALSE: PLAIDHIP_EUNSUPPORTED a
 int launch_gsea_ks(plaidhip_ctx* ctx, const double* Q, const double* W, double* Wpos, int64_t ldq, const uint32_t* colnan,
                    int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, double* S,
                    int64_t lds);
+// kernels_ks.hip: S (m x n, leading dimension lds) <- GSVA's random-walk statistic (replaid.gsva.exact) from the last ranks
+// Q of the row-transformed columns; Gp / Gi on the device; T: g doubles of scratch for the weight table (tau != 0)
+int launch_gsva_ks(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* colnan, int32_t g, int32_t n,
+                   const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int max_diff, double* T, double* S, int64_t lds);
+// multi.cpp: replaid.gsva.exact on ndev contexts (one: plaidhip_gsva_exact); its argument checks, which touch no device
+int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                   int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
+                   double* S_out);
+int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out);
 // range_out[3] = {min, max, any NaN} of the m x n scores; part: 3 ssgsea_exact_part_blocks(m n) doubles
 int launch_gsea_ks_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out);
 // kernels_norm.hip

@@ -299,7 +299,8 @@ struct Shared {
 };
 
 struct Call {
-  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test, 8 ssgsea.exact
+  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test, 8 ssgsea.exact,
+                // 9 gsva.exact
   const int32_t* Xp;
   const int32_t* Xi;
   const double* X;   // dense values or CSC @x
@@ -317,7 +318,8 @@ struct Call {
   int remove_log2 = -1;             // scse: < 0 decided from min / max of X
   int score_mean = 0;               // scse
   double tau = 0.0;                 // gsva
-  int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded
+  int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded; gsva.exact: 0 z, 1 ecdf (one shard), 2 none
+  int max_diff = 1;                 // gsva.exact
   int* removed_log2 = nullptr;      // scse output (may be null)
   int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
   int single = 1;                   // ssgsea.exact: 1 the walk's sum (closed form), 0 its value of largest magnitude (kernels_ks.hip)
@@ -330,11 +332,11 @@ struct Call {
 };
 
 // columns [lo, lo + nloc) of shard k.  Dense replaid.gsva and plaid.test (dense or not: its score rows are chained too)
-// cut at multiples of kColBlock (kernels_stats.hip, 128 columns) so that their chained row reductions add the block
+// (and replaid.gsva.exact with its z transform) cut at multiples of kColBlock (kernels_stats.hip, 128 columns) so that their chained row reductions add the block
 // partials of the one-device call in the same order; everything else takes plaidhip_shard_bounds.
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
   int64_t lo64 = 0, hi64 = 0;
-  if ((c.method == 6 && c.Xp == nullptr) || c.method == 7) {
+  if (((c.method == 6 || (c.method == 9 && c.rowtf == 0)) && c.Xp == nullptr) || c.method == 7) {
     constexpr int64_t kBlock = 128;
     const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
     lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
@@ -784,12 +786,22 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   const bool sparse = c.Xp != nullptr;
   const int method = c.method;
   const bool ranked = method == 3 || method == 4;
+  // replaid.gsva.exact (method 9): replaid.gsva's row transform (z: the code of method 6 below; ecdf: one shard, the
+  // launches of plaidhip_gsva / plaidhip_gsva_csc; none: X as it is), then the last ranks of the columns of v and the
+  // walk of kernels_ks.hip in place of the signed ranks, the crossprod and the medians
+  const bool gx = method == 9;
+  const bool ztf = method == 6 || (gx && c.rowtf == 0);
+  const bool ecdf = gx && c.rowtf == 1;
   // leading dimension of the staged X and of the ranks: that of the context entry (dense_average_ranks, plaidhip_scse:
   // g; plaidhip_gsva: even), so that the crossprod sees the same layout
-  const int64_t ld = method == 6 ? even_ld(g) : (int64_t)g;
+  const int64_t ld = (ztf || ecdf) ? even_ld(g) : (int64_t)g;
+  const int saved_precision = ctx->precision;
+  if (gx) ctx->precision = PLAIDHIP_PRECISION_F64;   // fp64 in every mode, as replaid.ssgsea.exact
   plaidhip_geneset* gs = nullptr;
   CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dR{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
   DevBuf dscratch, dcsc, drp, drows, dy, dadd;
+  DevBuf dops, dGp, dGi, dperm, dcolnan;   // gsva.exact: [Q | rank scratch | T], the pattern, the NaN flags
+  size_t ops_t = 0;                        // where T starts in dops
   HomeBuffer home;
   uint32_t* d_flags = nullptr;
   double *d_gmax = nullptr, *d_mm = nullptr, *d_med = nullptr, *d_colmax = nullptr, *d_colsum = nullptr;
@@ -815,7 +827,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     d_colsum = d_colmax + nl;
     PH_HIP(hipMemsetAsync(dsmall.p, 0, 64, ctx->stream));
     PH_TRY(dS.alloc((size_t)m * nl * 8));
-    if (method == 6) {   // [mean | group 1 (unused) | ssd | seed | running sums], g each
+    if (ztf || ecdf) {   // [mean | group 1 (unused) | ssd | seed | running sums], g each
       PH_TRY(drows.alloc((size_t)g * 5 * 8));
       d_mean = drows.as<double>();
       d_ssd = d_mean + 2 * (size_t)g;
@@ -824,9 +836,21 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       PH_HIP(hipMemsetAsync(drows.p, 0, (size_t)g * 5 * 8, ctx->stream));
     }
     if (nloc == 0) return PLAIDHIP_OK;
+    if (gx) {
+      const size_t z = (size_t)c.Gp[m];
+      // Q, then the rank scratch (dense columns: 2 g nloc doubles; a dgCMatrix's stored values: 3 nnz), then T
+      const int64_t nz = sparse ? (int64_t)c.Xp[lo + nloc] - c.Xp[lo] : 0;
+      ops_t = (size_t)g * nloc + std::max((size_t)g * nloc * 2, (size_t)nz * 3);
+      PH_TRY(dops.alloc((ops_t + (size_t)g) * 8));
+      PH_TRY(dcolnan.alloc((size_t)nloc * 4));
+      PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
+      PH_TRY(dGi.alloc(std::max<size_t>(z, 1) * 4));
+      PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      if (z > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, z * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
     if (!sparse) {
       PH_TRY(dX.alloc((size_t)ld * nloc * 8));
-      if (method != 5) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
+      if (method != 5 && !gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
       // ucell / aucell: the ranks of a column panel follow its DMA (dense_average_ranks' kernel and arguments)
       auto on_panel = [&](int64_t c0, int64_t c1) -> int {
         return launch_colranks_dense_f64(ctx, dX.as<double>() + c0 * ld, ld, g, (int32_t)(c1 - c0), PLAIDHIP_TIES_AVERAGE, 0,
@@ -834,7 +858,14 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       };
       PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
                               (size_t)g * 8, nloc, ranked ? std::function<int(int64_t, int64_t)>(on_panel) : nullptr));
-      if (method == 6) {   // zX, step 1: the block partials of the row sums (every sample in group 0)
+      if (ecdf) {   // plaidhip_gsva's launches: genes become columns, max ranks, and back (the factor 1 / n dropped)
+        double* tmp = dops.as<double>();
+        PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), ld, g, nloc, tmp, nloc));
+        PH_TRY(launch_colranks_dense_f64(ctx, tmp, nloc, nloc, g, PLAIDHIP_TIES_MAX, 0, 1.0, dX.as<double>(), nloc, nullptr));
+        PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), nloc, nloc, g, tmp, ld));
+        PH_HIP(hipMemcpyAsync(dX.p, tmp, (size_t)ld * nloc * 8, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      if (ztf) {   // zX, step 1: the block partials of the row sums (every sample in group 0)
         PH_TRY(dy.alloc((size_t)nloc * 4));
         PH_HIP(hipMemsetAsync(dy.p, 0, (size_t)nloc * 4, ctx->stream));
         PH_TRY(dscratch.alloc((size_t)row_group_ws_doubles(g, nloc) * 8));
@@ -848,7 +879,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
       PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
       double* vals = nullptr;
-      if (method == 6) {
+      if (ztf || ecdf) {
         PH_TRY(dcsc.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
         vals = dcsc.as<double>();
       } else {
@@ -870,10 +901,24 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
           PH_TRY(launch_colranks_csc_dense_f64(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, PLAIDHIP_TIES_AVERAGE,
                                                0, 1.0, dR.as<double>(), ld, d_colmax));
         }
-      } else if (method == 6) {
+      } else if (ecdf) {
+        // plaidhip_gsva_csc's launches: #{x <= x_i} per gene from the max ranks of its stored values and its zeros
+        PH_TRY(dX.alloc((size_t)ld * nloc * 8));
+        PH_TRY(drp.alloc((size_t)(g + 2) * 4));
+        PH_TRY(dscratch.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+        PH_TRY(dperm.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
+        PH_TRY(launch_csc_to_csr(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, drp.as<int32_t>(), nullptr,
+                                 dscratch.as<double>(), dperm.as<int32_t>(), drp.as<int32_t>() + g + 1));
+        PH_HIP(hipMemcpyAsync(&max_row, drp.as<int32_t>() + g + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        PH_TRY(launch_csr_row_ecdf(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, nloc, max_row, dperm.as<int32_t>(),
+                                   dops.as<double>(), vals, drows.as<double>()));
+        PH_TRY(launch_csc_expand(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, ld, drows.as<double>(), nullptr,
+                                 nullptr, dX.as<double>()));
+      } else if (ztf) {
         // the shard's row view, and pass A of its row moments: the sums of the stored values
         PH_TRY(dX.alloc((size_t)ld * nloc * 8));
-        PH_TRY(dR.alloc((size_t)ld * nloc * 8));
+        if (!gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
         PH_TRY(drp.alloc((size_t)(g + 2) * 4));
         PH_TRY(dscratch.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
         PH_TRY(launch_csc_to_csr(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, drp.as<int32_t>(), nullptr,
@@ -926,7 +971,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   };
 
   // ---- replaid.gsva, z row transform: rowMeans and rowSds of ALL samples -----------------------------------------------
-  if (method == 6 && !sparse) {
+  if (ztf && !sparse) {
     // chained, ordered reductions: in round r only shard r works, continuing shard r - 1's running sums block by block
     auto chain = [&](std::vector<double>& run) {
       for (int r = 0; r < ndev; ++r) {
@@ -958,7 +1003,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       PH_HIP(hipStreamSynchronize(ctx->stream));
       return PLAIDHIP_OK;
     });
-  } else if (method == 6) {
+  } else if (ztf) {
     // dgCMatrix: the shards' sums of stored values added in shard order, mean = s / n; then the same for the squared
     // deviations, plus (n - nnz) mean^2 for the implicit zeros, once (csr_row_moments_kernel's expression)
     host_mean.assign((size_t)g, 0.0);
@@ -1014,8 +1059,29 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     });
   }
 
+  // ---- replaid.gsva.exact: q = rank(v, "last") of every column, then the walk ------------------------------------------------
+  if (gx)
+    step([&]() -> int {
+      if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+      if (nloc == 0) return PLAIDHIP_OK;
+      double* Q = dops.as<double>();
+      double* scratch = Q + (size_t)g * nloc;
+      double* T = Q + ops_t;
+      uint32_t* d_colnan = dcolnan.as<uint32_t>();
+      // (alpha = 0: the operand pass writes Q and the NaN flags only, no W or P)
+      if (sparse && c.rowtf == 2)   // the stored values are ranked, as replaid.ssgsea.exact ranks a dgCMatrix
+        PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), dXi.as<int32_t>(), g, nloc,
+                                            host_max_col_nnz(ploc.data(), nloc), zx, 0.0, Q, nullptr, nullptr, g, scratch,
+                                            d_colnan));
+      else
+        PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), ld, nullptr, nullptr, g, nloc, 0, 0, 0.0, Q, nullptr, nullptr, g,
+                                            scratch, d_colnan));
+      return launch_gsva_ks(ctx, Q, g, d_colnan, g, nloc, dGp.as<int32_t>(), dGi.as<int32_t>(), m, c.tau, c.max_diff, T,
+                            dS.as<double>(), m);
+    });
+
   // ---- max(rX) (ucell / aucell: R/plaid.R:278, 306; gsva: max|rX|, :354) --------------------------------------------------
-  if (method != 5) global_max(d_colmax);
+  if (method != 5 && !gx) global_max(d_colmax);
   if (ranked)
     step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
@@ -1056,7 +1122,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   }
 
   // ---- crossprod --------------------------------------------------------------------------------------------------------
-  step([&]() -> int {
+  if (!gx) step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
     if (method == 5) {
@@ -1079,7 +1145,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   });
 
   // ---- normalize_medians (R/plaid.R:554-575), as shard_worker: flags, medians, mean(medx) in the device's order -----------
-  if (method != 5) {
+  if (method != 5 && !gx) {
     uint32_t fl[4] = {0, 0, 0, 0};
     step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
@@ -1130,6 +1196,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     PH_HIP(hipStreamSynchronize(ctx->stream));
     return PLAIDHIP_OK;
   });
+  ctx->precision = saved_precision;
   if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
     hipStreamSynchronize(ctx->stream);
     return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
@@ -1367,7 +1434,7 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
   sh.med_all.assign((size_t)c.n, 0.0);
-  if (c.method == 6) {
+  if (c.method == 6 || c.method == 9) {
     sh.chain_sum.assign((size_t)c.g, 0.0);
     sh.chain_ssd.assign((size_t)c.g, 0.0);
     sh.row_sum.resize((size_t)ndev);
@@ -1492,6 +1559,35 @@ int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, con
   Call c{8, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, norm ? 1 : 0, alpha, S_out};
   c.scale = scale ? 1 : 0;
   c.single = single ? 1 : 0;
+  return run_call(ctxs, ndev, c);
+}
+
+// replaid.gsva.exact's argument checks (every entry point runs them before a device is touched)
+int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out) {
+  PH_REQUIRE(std::isfinite(tau) && tau >= 0.0, "gsva_exact: tau must be finite and >= 0 (got %g)", tau);
+  PH_REQUIRE(rowtf >= 0 && rowtf <= 2, "Error: unknown row transform %d", rowtf);                     // R/plaid.R:348
+  PH_REQUIRE(rowtf != 1 || ndev == 1, "gsva_exact_multi: rowtf = \"ecdf\" ranks all samples of a gene together and is not "
+                                      "sharded by sample; score it on one device (plaidhip_gsva_exact)");
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, 0.0, S_out));
+  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("gsva_exact: nrow(X) = %d (at most %d rows)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  return PLAIDHIP_OK;
+}
+
+int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                   int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
+                   double* S_out) {
+  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
+  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_gsva_exact_args(ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  Call c{9, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, 0, 0.0, S_out};
+  c.tau = tau;
+  c.rowtf = rowtf;
+  c.max_diff = max_diff ? 1 : 0;
   return run_call(ctxs, ndev, c);
 }
 
@@ -1759,6 +1855,43 @@ int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* 
   std::vector<plaidhip_ctx*> ctxs;
   PH_TRY(multi_contexts(devices, ndev, ctxs));
   return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h): plaidhip_gsva_exact_multi's engine with `nshards` contexts on ONE device.
+// fail_shard >= 0: that shard fails in its walk phase (the call must return an error, not hang).
+int plaidhip_debug_gsva_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                    const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                    const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
+                                                    int max_diff, double* S_out) try {
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_gsva_exact_sharded: nshards = %d", nshards);
+  PH_TRY(check_gsva_exact_args(nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
+  int rc = PLAIDHIP_OK;
+  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
+    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
+    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
+  }
+  if (rc == PLAIDHIP_OK) rc = run_gsva_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
+  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
+  for (plaidhip_ctx* cx : ctxs)
+    if (cx) plaidhip_finalize(cx);
+  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
+  return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
+                              int max_diff, double* S_out) try {
+  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
+  if (devices != nullptr)
+    for (int k = 0; k < ndev; ++k)
+      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_gsva_exact_args(ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_gsva_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_multi_set_precision(int mode) try {

@@ -243,6 +243,13 @@ class Context:
         check(self.lib.plaidhip_dev_gsea_ks_f64(self.handle, Q, W, int(ldq), colnan, int(g), int(n), Gp, Gi, int(m),
                                                 float(alpha), int(bool(scale)), S, int(lds)))
 
+    def dev_gsva_ks(self, Q: int, ldq: int, colnan: int, g: int, n: int, Gp: int, Gi: int, m: int, tau: float,
+                    max_diff: bool, S: int, lds: int):
+        """the walk of replaid.gsva.exact on the device's last ranks of the row-transformed columns
+        (dev_ssgsea_exact_operands with alpha = 0: Q, colnan) and a device copy of the aligned pattern: S (m x n)"""
+        check(self.lib.plaidhip_dev_gsva_ks_f64(self.handle, Q, int(ldq), colnan, int(g), int(n), Gp, Gi, int(m), float(tau),
+                                                int(bool(max_diff)), S, int(lds)))
+
     def dev_minflags(self, S: int, count: int, flags: int):
         check(self.lib.plaidhip_dev_minflags(self.handle, S, count, flags))
 
@@ -466,6 +473,34 @@ def _ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False, single=Tr
     return S
 
 
+GSVA_EXACT_ROWTF = {"z": 0, "ecdf": 1, "none": 2}
+
+
+def check_gsva_exact_args(tau, rowtf):
+    """the checks of plaidhip_gsva_exact that need no device: (tau, the row transform's code)"""
+    rowtf = rowtf if isinstance(rowtf, str) else rowtf[0]
+    tau = float(tau)
+    if not np.isfinite(tau) or tau < 0.0:
+        raise ValueError(f"gsva_exact: tau must be finite and >= 0 (got {tau:g})")
+    if rowtf not in GSVA_EXACT_ROWTF:
+        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
+    return tau, GSVA_EXACT_ROWTF[rowtf]
+
+
+def _gsva_exact(self, X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True):
+    """plaidhip_gsva_exact: GSVA's random-walk statistic for any tau >= 0; rowtf "z" / "ecdf" (replaid.gsva's row
+    transforms) or "none"; X dense or scipy CSC with sorted, distinct row indices (scored as its dense form), G aligned
+    to X's rows"""
+    tau, tf = check_gsva_exact_args(tau, rowtf)
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    check(self.lib.plaidhip_gsva_exact(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, tau, tf,
+                                       int(bool(max_diff)), _np_ptr(S)))
+    return S
+
+
 def _plaid_test(self, X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
     """plaidhip_plaid_test: returns sets x 6 (gsetFC, p.one, p.two, p.lm, p.meta, q.meta), G's column order"""
     X = _as_f64_fortran(X)
@@ -569,6 +604,7 @@ Context.ucell = _ucell
 Context.aucell = _aucell
 Context.scse = _scse
 Context.ssgsea_exact = _ssgsea_exact
+Context.gsva_exact = _gsva_exact
 
 _default_ctx: Context | None = None
 
@@ -646,6 +682,21 @@ def ssgsea_exact_multi(X, Gp, Gi, alpha=0.25, scale=True, norm=False, devices=1,
     fn = lib.plaidhip_ssgsea_exact_multi if single else lib.plaidhip_ssgsea_exact_ks_multi
     check(fn(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), int(bool(scale)), int(bool(norm)),
              _np_ptr(S)))
+    return S
+
+
+def gsva_exact_multi(X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True, devices=1) -> np.ndarray:
+    """replaid.gsva.exact (Context.gsva_exact) with the sample columns sharded over `devices`; "ecdf" ranks all samples
+    of a gene together and is refused over more than one device"""
+    tau, tf = check_gsva_exact_args(tau, rowtf)
+    lib = _lib.load()
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = np.empty((m, n), dtype=np.float64, order="F")
+    dp, nd, dkeep = _devices_arg(devices)
+    check(lib.plaidhip_gsva_exact_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, tau, tf, int(bool(max_diff)),
+                                        _np_ptr(S)))
     return S
 
 

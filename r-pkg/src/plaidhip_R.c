@@ -278,6 +278,27 @@ SEXP R_plaidhip_ssgsea_exact_ks_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, S
   return S;
 }
 
+/* replaid.gsva.exact: GSVA's random-walk statistic; rowtf 0 "z", 1 "ecdf", 2 "none" */
+SEXP R_plaidhip_gsva_exact(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP tau, SEXP rowtf, SEXP max_diff) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_gsva_exact(ctx(), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi),
+                            m, Rf_asReal(tau), Rf_asInteger(rowtf), Rf_asLogical(max_diff), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
+SEXP R_plaidhip_gsva_exact_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP tau,
+                                 SEXP rowtf, SEXP max_diff) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  check(plaidhip_gsva_exact_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                  Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(tau), Rf_asInteger(rowtf),
+                                  Rf_asLogical(max_diff), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
 SEXP R_plaidhip_ucell(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP kfull, SEXP rmax) {
   const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
   SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
@@ -451,6 +472,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_aucell_multi", (DL_FUNC)&R_plaidhip_aucell_multi, 9},
     {"R_plaidhip_scse_multi", (DL_FUNC)&R_plaidhip_scse_multi, 10},
     {"R_plaidhip_gsva_multi", (DL_FUNC)&R_plaidhip_gsva_multi, 10},
+    {"R_plaidhip_gsva_exact", (DL_FUNC)&R_plaidhip_gsva_exact, 10},
+    {"R_plaidhip_gsva_exact_multi", (DL_FUNC)&R_plaidhip_gsva_exact_multi, 11},
     {"R_plaidhip_ssgsea_exact", (DL_FUNC)&R_plaidhip_ssgsea_exact, 10},
     {"R_plaidhip_ssgsea_exact_multi", (DL_FUNC)&R_plaidhip_ssgsea_exact_multi, 11},
     {"R_plaidhip_ssgsea_exact_ks", (DL_FUNC)&R_plaidhip_ssgsea_exact_ks, 10},
