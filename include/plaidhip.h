@@ -435,10 +435,11 @@ int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t
                              double* S_out);
 
 /* replaid.gsva.exact(X, matG, tau, rowtf, max.diff): the random-walk statistic of GSVA (Haenzelmann et al. 2013), where
- * replaid.gsva (R/plaid.R:353-356) is a mean of transformed ranks.  rowtf: 0 "z", 1 "ecdf", 2 "none".
+ * replaid.gsva (R/plaid.R:353-356) is a mean of transformed ranks.  rowtf: 0 "z", 1 "ecdf", 2 "none", 3 "gauss".
  *  1. Row transform v of X: "z" and "ecdf" are replaid.gsva's own (the launches of plaidhip_gsva_multi's z transform, of
  *     plaidhip_gsva / plaidhip_gsva_csc's ecdf; a dgCMatrix through the row view, the dense v built on the device);
- *     "none" takes X as it is, for a caller who brings their own per-gene CDF.
+ *     "none" takes X as it is, for a caller who brings their own per-gene CDF; "gauss" is GSVA's Gaussian kernel CDF
+ *     estimate V of plaidhip_gsva_kcdf below (n >= 2, else PLAIDHIP_EINVAL before any device work), dense whatever X is.
  *  2. Per sample column with N = g genes: q = rank(v, ties = "last"), the walk visits the genes at pos = N + 1 - q.  This
  *     is order(v, decreasing = TRUE) with tied genes in row order.  No average ranks are needed.
  *  3. Weight of the gene at pos: w = |q - N / 2|^tau (GSVA's symmetric rank score abs(seq(N, 1) - N / 2) laid along the
@@ -458,12 +459,42 @@ int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t
  *     correctly rounded divisions and a subtraction with no product in it: the bits of the same operations on the host.
  *     For other tau, cw_t and B are summed in an order that depends on k and the positions only, never on the sharding.
  * Deliberate differences from the GSVA package: GSVA accumulates the running sum step by step (N roundings; this form
- * has three per candidate), its B == 0 case leaves whatever the walk held before the NaN, and abs.ranking and the kernel
- * CDF estimate (kcdf) are not offered.  No normalize_medians (GSVA applies none).  X dense (Xp == NULL) or a dgCMatrix
+ * has three per candidate), its B == 0 case leaves whatever the walk held before the NaN, abs.ranking is not offered, and
+ * of GSVA's kernel CDF estimates (kcdf) the Gaussian one is ("gauss"), the Poisson one is not.  No normalize_medians (GSVA
+ * applies none).  X dense (Xp == NULL) or a dgCMatrix
  * (rows increasing inside a column), never densified on the host: with "none" its stored values are ranked as
  * plaidhip_ssgsea_exact ranks them.  fp64 in every precision mode.  S_out: m x n doubles.                              */
 int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff, double* S_out);
+
+/* GSVA's Gaussian kernel CDF estimate (kcdf = "Gaussian": the row_d / precomputedCdf loop of its kernel_estimation.c), the
+ * row transform "gauss" of plaidhip_gsva_exact, on its own.  Per gene row i of X (g x n, n >= 2), all in fp64, every sum
+ * sequential in sample order k = 0, 1, ..., n - 1 and starting from 0.0, no product contracted into an add, every division
+ * and the square root correctly rounded:
+ *     mean = (x_0 + x_1 + ... + x_{n-1}) / (double) n
+ *     ss   = sum_k d_k * d_k,  d_k = x_k - mean                      (the product rounded, then added)
+ *     h    = sqrt(ss / (double)(n - 1)) / 4.0
+ *     c(d) : v = d / h;  v < -10 -> 0.0;  v > 10 -> 1.0;
+ *            else t = T[(int)(fabs(v) / 10.0 * 10000.0)];  v < 0 ? 1.0 - t : t
+ *     V_ij = sum_k c(x_ij - x_ik)
+ *     T[i] = Phi(10.0 * (double) i / 10000.0) = 0.5 * erfc(-t / sqrt(2.0)),  i = 0 ... 10000
+ * T is built once on the host with the C library's erfc, made non-decreasing where that erfc is not (T[i] = max(T[i],
+ * T[i - 1])), uploaded, and exported by plaidhip_gsva_kcdf_table so that a checker uses the device's own bits.
+ * A row with h == 0 (v = 0 / 0) reads T[0] = 0.5 in every term: V_ij = n / 2 exactly (GSVA indexes its table with
+ * (int) NaN there).  A row holding a NaN or an infinity has a NaN h and gives a NaN row of V (GSVA refuses such input), so
+ * every column is NaN and scores NaN under plaidhip_gsva_exact.  The kernel may find the index from |d| (1 / h) 1000 where
+ * that estimate is provably on the same side of every integer as the pinned expression, and runs the pinned operations
+ * elsewhere: the index is the pinned one always.
+ * Deliberate differences from the GSVA package: V is the sum itself, where GSVA divides by n and takes -log((1 - F) / F);
+ * both are monotone, so a sample's order of genes is the same except where their rounding merges or splits neighbours.
+ * GSVA's Poisson kernel (kcdf = "Poisson", for counts) is not offered.
+ * X dense (Xp == NULL) or a dgCMatrix, expanded on the device into the dense form (its bits by construction), never
+ * densified on the host.  n < 2: PLAIDHIP_EINVAL before any device work.  V_out: g x n doubles, column-major.            */
+#define PLAIDHIP_GSVA_KCDF_TABLE 10001
+int plaidhip_gsva_kcdf(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                       double* V_out);
+/* out[PLAIDHIP_GSVA_KCDF_TABLE] <- T.  Needs no device. */
+int plaidhip_gsva_kcdf_table(double* out);
 
 /* ---- several GPUs of one node from ONE host process (the R session): multi.cpp ----------------------
  * The sample columns are cut into ndev contiguous shards (plaidhip_shard_bounds); a host thread per device
@@ -502,8 +533,10 @@ int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* 
 /* plaidhip_gsva_exact over several devices, sharded by sample column.  "none" has no coupling between the shards; "z"
  * chains the row moments as plaidhip_gsva_multi does (dense X: shards of whole 128-column blocks, the one-device bits;
  * a dgCMatrix: the rows' sums of stored values are added shard by shard, which is exact whenever those sums are);
- * "ecdf" ranks all samples of a gene together and returns PLAIDHIP_EINVAL when ndev > 1.  The walk is per column.  The
- * argument checks and the device list's run before any device is touched.                                             */
+ * "ecdf" ranks all samples of a gene together and returns PLAIDHIP_EINVAL when ndev > 1.  "gauss" is sharded by sample
+ * too: every device receives all of X (each V_ij needs its gene's whole row) and computes V for its own columns, summing
+ * over k in the one fixed order, so every sharding gives the one-device bits.  The walk is per column.  The argument
+ * checks and the device list's run before any device is touched.                                                       */
 int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
                               int max_diff, double* S_out);

@@ -94,6 +94,8 @@ SIGNATURES = {
     "plaidhip_ssgsea_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
     "plaidhip_dev_gsva_ks_f64": [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp, _i64],
     "plaidhip_gsva_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
+    "plaidhip_gsva_kcdf": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],
+    "plaidhip_gsva_kcdf_table": [_vp],
     "plaidhip_ssgsea_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_ssgsea_exact_ks": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_shard_bounds": [_i64, _int, _int, C.POINTER(_i64), C.POINTER(_i64)],

@@ -339,10 +339,11 @@ def replaid_gsva(X, matG, tau=0, rowtf="z", ctx: Context | None = None):
 def replaid_gsva_exact(X, matG, tau=1, rowtf="z", max_diff=True, ctx: Context | None = None):
     """replaid.gsva.exact(): the random-walk statistic of GSVA (Haenzelmann et al. 2013; include/plaidhip.h:
     plaidhip_gsva_exact) where replaid.gsva is a mean of transformed ranks.  rowtf "z" / "ecdf" are replaid.gsva's row
-    transforms, "none" takes X as it is (a caller's own per-gene CDF).  The genes of a sample are walked in decreasing
+    transforms, "none" takes X as it is (a caller's own per-gene CDF), "gauss" is GSVA's own default: the Gaussian kernel
+    CDF estimate of every value among its gene's samples (Context.gsva_kcdf; at least 2 samples).  The genes of a sample are walked in decreasing
     order of the transformed value (ties in row order) with the weights |rank - N / 2| ^ tau; max_diff = True adds the
     walk's largest positive and negative excursion, False returns the larger one (the negative one when equal).  No
-    normalize_medians; GSVA's kernel CDF estimate and abs.ranking are not offered.  tau and rowtf are checked before
+    normalize_medians; GSVA's Poisson kernel and abs.ranking are not offered.  tau and rowtf are checked before
     any device is touched."""
     from .engine import check_gsva_exact_args
     tau, _ = check_gsva_exact_args(tau, rowtf)

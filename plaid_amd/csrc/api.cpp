@@ -381,6 +381,7 @@ int plaidhip_finalize(plaidhip_ctx* ctx) try {
   if (ctx->ws) hipFree(ctx->ws);
   if (ctx->rank_scratch) hipFree(ctx->rank_scratch);
   if (ctx->tie_scratch) hipFree(ctx->tie_scratch);
+  if (ctx->kcdf_table) hipFree(ctx->kcdf_table);
   if (ctx->fmed_buf) hipFree(ctx->fmed_buf);
   if (ctx->d_sel) hipFree(ctx->d_sel);
   for (int k = 0; k < plaidhip_ctx::kHostBufs; ++k)
@@ -1344,6 +1345,58 @@ int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
   PH_TRY(check_gsva_exact_args(1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
   PH_CTX(ctx);
   return run_gsva_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
+} catch (...) { return plaidhip::on_exception(); }
+
+// GSVA's Gaussian kernel CDF estimate alone (the row transform "gauss" of replaid.gsva.exact): V, g x n
+int plaidhip_gsva_kcdf(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                       double* V_out) try {
+  PH_REQUIRE(g >= 0 && n >= 0, "gsva_kcdf: bad dims g=%d n=%d", g, n);
+  PH_REQUIRE(n >= 2, "gsva_kcdf: the kernel CDF estimate needs at least 2 samples (got %d)", n);
+  PH_REQUIRE(X_or_x != nullptr || g == 0 || (Xp != nullptr && Xp[n] == 0), "null X");
+  if (Xp != nullptr) PH_TRY(check_host_csc(Xp, Xi, g, n));
+  if (g == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(V_out != nullptr, "null V_out");
+  PH_CTX(ctx);
+  DevBuf dV;
+  PH_TRY(dV.alloc((size_t)g * n * 8));
+  PH_TRY(gsva_kcdf_columns(ctx, Xp, Xi, X_or_x, g, n, 0, n, dV.as<double>()));
+  return copy_home(ctx, V_out, dV.p, (size_t)g * n * 8);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsva_kcdf_table(double* out) try {
+  PH_REQUIRE(out != nullptr, "gsva_kcdf_table: null out");
+  gsva_kcdf_table(out);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hooks (not part of include/plaidhip.h): how kcdf_sum_kernel finds its table index (0 the fast index, 1 the exact
+// operations for every term, 2 the fast index with the terms it left to the exact operations counted), and that count
+int plaidhip_debug_gsva_kcdf_set_mode(int mode) try {
+  PH_REQUIRE(mode >= 0 && mode <= 2, "debug_gsva_kcdf_set_mode: mode = %d", mode);
+  debug_gsva_kcdf_set_mode(mode);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_gsva_kcdf_width(int32_t nj) { return nj >= 1 ? debug_gsva_kcdf_width(nj) : 0; }
+
+// the bandwidths h of the rows of a dense host matrix X (g x n), as the kernel CDF estimate computes them: H_out, g doubles
+int plaidhip_debug_gsva_kcdf_bandwidths(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, double* H_out) try {
+  PH_REQUIRE(g >= 1 && n >= 2 && X != nullptr && H_out != nullptr, "debug_gsva_kcdf_bandwidths: bad arguments");
+  PH_CTX(ctx);
+  DevBuf dX, dH;
+  PH_TRY(dX.alloc((size_t)g * n * 8));
+  PH_TRY(dH.alloc((size_t)g * 8));
+  PH_TRY(upload_host(ctx, dX.p, (size_t)g * 8, X, (size_t)g * 8, n));
+  PH_TRY(launch_gsva_kcdf_bandwidths(ctx, dX.as<double>(), g, g, n, dH.as<double>()));
+  PH_HIP(hipMemcpyAsync(H_out, dH.p, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_gsva_kcdf_slow_terms(unsigned long long* out) try {
+  PH_REQUIRE(out != nullptr, "debug_gsva_kcdf_slow_terms: null out");
+  *out = debug_gsva_kcdf_slow_terms();
+  return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.gsva from the row-transformed zX (dX: g x n, leading dimension ldg) on: the scores in dS (m x n), normalised.

@@ -134,6 +134,7 @@ struct plaidhip_ctx {
   size_t tie_scratch_bytes = 0;
   void* rank_scratch = nullptr;   // value-partitioned ranking of columns beyond the LDS (kernels_rank.hip), grown on demand
   size_t rank_scratch_bytes = 0;
+  void* kcdf_table = nullptr;     // replaid.gsva.exact, rowtf "gauss": the table of Phi and a counter word (kernels_kcdf.hip), built on first use
   int debug_fail_crossprod = 0;   // test hook (plaidhip_debug_sharded_on_one_device): this context's shard fails in the crossprod phase
   // pinned staging of the pipelined host uploads (multi.cpp): kFeeders feeder threads x 2 buffers, their streams
   static constexpr int kFeeders = 4;
@@ -492,6 +493,21 @@ int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const
                    double* S_out);
 int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out);
+// kernels_kcdf.hip: GSVA's Gaussian kernel CDF estimate (include/plaidhip.h: plaidhip_gsva_kcdf).  V (g x (j1 - j0), leading
+// dimension ldv) <- the kernel sums of the test columns [j0, j1) of the dense device matrix X (g x n, leading dimension
+// ldx) over ALL n samples; H: g doubles of scratch (the bandwidths).  Stream-ordered.
+int launch_gsva_kcdf(plaidhip_ctx* ctx, const double* X, int64_t ldx, int32_t g, int32_t n, int32_t j0, int32_t j1, double* H,
+                     double* V, int64_t ldv);
+void gsva_kcdf_table(double* out);   // the PLAIDHIP_GSVA_KCDF_TABLE values of Phi the kernels read
+// H[i] <- the bandwidth h of row i alone (kcdf_row_moments_kernel, the launch launch_gsva_kcdf makes first)
+int launch_gsva_kcdf_bandwidths(plaidhip_ctx* ctx, const double* X, int64_t ldx, int32_t g, int32_t n, double* H);
+int debug_gsva_kcdf_width(int32_t nj);             // test hook: the sub-group width kcdf_sum_kernel takes for nj test columns
+void debug_gsva_kcdf_set_mode(int mode);           // test hooks: 0 fast index, 1 exact operations only, 2 fast and counting
+unsigned long long debug_gsva_kcdf_slow_terms();   // mode 2: the last launch's terms that took the exact operations
+// multi.cpp: columns [lo, lo + nloc) of V from the HOST matrix X (dense, or a dgCMatrix expanded on the device): all of X
+// goes to this device.  dV: g x nloc on the device, leading dimension g.
+int gsva_kcdf_columns(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                      int32_t lo, int32_t nloc, double* dV);
 // range_out[3] = {min, max, any NaN} of the m x n scores; part: 3 ssgsea_exact_part_blocks(m n) doubles
 int launch_gsea_ks_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out);
 // kernels_norm.hip

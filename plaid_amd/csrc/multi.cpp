@@ -318,7 +318,8 @@ struct Call {
   int remove_log2 = -1;             // scse: < 0 decided from min / max of X
   int score_mean = 0;               // scse
   double tau = 0.0;                 // gsva
-  int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded; gsva.exact: 0 z, 1 ecdf (one shard), 2 none
+  int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded; gsva.exact: 0 z, 1 ecdf (one shard), 2 none,
+                                    // 3 gauss (every shard takes all of X)
   int max_diff = 1;                 // gsva.exact
   int* removed_log2 = nullptr;      // scse output (may be null)
   int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
@@ -792,6 +793,9 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   const bool gx = method == 9;
   const bool ztf = method == 6 || (gx && c.rowtf == 0);
   const bool ecdf = gx && c.rowtf == 1;
+  // "gauss": GSVA's kernel CDF estimate (kernels_kcdf.hip).  Every V_ij needs its gene's whole row, so all of X goes to
+  // every device, which computes the columns of its own shard: dX holds V, dense, whatever X was
+  const bool gauss = gx && c.rowtf == 3;
   // leading dimension of the staged X and of the ranks: that of the context entry (dense_average_ranks, plaidhip_scse:
   // g; plaidhip_gsva: even), so that the crossprod sees the same layout
   const int64_t ld = (ztf || ecdf) ? even_ld(g) : (int64_t)g;
@@ -839,7 +843,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     if (gx) {
       const size_t z = (size_t)c.Gp[m];
       // Q, then the rank scratch (dense columns: 2 g nloc doubles; a dgCMatrix's stored values: 3 nnz), then T
-      const int64_t nz = sparse ? (int64_t)c.Xp[lo + nloc] - c.Xp[lo] : 0;
+      const int64_t nz = sparse && !gauss ? (int64_t)c.Xp[lo + nloc] - c.Xp[lo] : 0;   // ("gauss" leaves a dense V)
       ops_t = (size_t)g * nloc + std::max((size_t)g * nloc * 2, (size_t)nz * 3);
       PH_TRY(dops.alloc((ops_t + (size_t)g) * 8));
       PH_TRY(dcolnan.alloc((size_t)nloc * 4));
@@ -848,7 +852,10 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
       if (z > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, z * 4, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (!sparse) {
+    if (gauss) {
+      PH_TRY(dX.alloc((size_t)ld * nloc * 8));
+      PH_TRY(gsva_kcdf_columns(ctx, c.Xp, c.Xi, c.X, g, n, lo, nloc, dX.as<double>()));
+    } else if (!sparse) {
       PH_TRY(dX.alloc((size_t)ld * nloc * 8));
       if (method != 5 && !gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
       // ucell / aucell: the ranks of a column panel follow its DMA (dense_average_ranks' kernel and arguments)
@@ -1069,7 +1076,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       double* T = Q + ops_t;
       uint32_t* d_colnan = dcolnan.as<uint32_t>();
       // (alpha = 0: the operand pass writes Q and the NaN flags only, no W or P)
-      if (sparse && c.rowtf == 2)   // the stored values are ranked, as replaid.ssgsea.exact ranks a dgCMatrix
+      if (sparse && c.rowtf == 2)   // ("gauss" left its dense V in dX) the stored values are ranked, as replaid.ssgsea.exact ranks a dgCMatrix
         PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), dXi.as<int32_t>(), g, nloc,
                                             host_max_col_nnz(ploc.data(), nloc), zx, 0.0, Q, nullptr, nullptr, g, scratch,
                                             d_colnan));
@@ -1562,11 +1569,39 @@ int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, con
   return run_call(ctxs, ndev, c);
 }
 
+// GSVA's kernel CDF estimate of the columns [lo, lo + nloc) of the host matrix X on one device: all of X is uploaded (a
+// dgCMatrix as its slots, expanded there into the dense form), then the two kernels of kernels_kcdf.hip
+int gsva_kcdf_columns(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                      int32_t lo, int32_t nloc, double* dV) {
+  if (g <= 0 || nloc <= 0) return PLAIDHIP_OK;
+  DevBuf dfull, dp, di, dx, dh;
+  PH_TRY(dfull.alloc((size_t)g * n * 8));
+  PH_TRY(dh.alloc((size_t)g * 8));
+  if (Xp == nullptr) {
+    PH_TRY(upload_host(ctx, dfull.p, (size_t)g * 8, X_or_x, (size_t)g * 8, n));
+  } else {
+    const int64_t z = Xp[n];
+    PH_TRY(dp.alloc((size_t)(n + 1) * 4));
+    PH_TRY(di.alloc((size_t)std::max<int64_t>(z, 1) * 4));
+    PH_TRY(dx.alloc((size_t)std::max<int64_t>(z, 1) * 8));
+    PH_HIP(hipMemcpyAsync(dp.p, Xp, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(upload_host(ctx, di.p, 1, Xi, 1, z * 4));
+    PH_TRY(upload_host(ctx, dx.p, 1, X_or_x, 1, z * 8));
+    PH_HIP(hipMemsetAsync(dh.p, 0, (size_t)g * 8, ctx->stream));   // (the rows' default: a zero)
+    PH_TRY(launch_csc_expand(ctx, dp.as<int32_t>(), di.as<int32_t>(), dx.as<double>(), g, n, g, dh.as<double>(), nullptr, nullptr,
+                             dfull.as<double>()));
+  }
+  PH_TRY(launch_gsva_kcdf(ctx, dfull.as<double>(), g, g, n, lo, lo + nloc, dh.as<double>(), dV, g));
+  PH_HIP(hipStreamSynchronize(ctx->stream));   // (the buffers above are freed on return)
+  return PLAIDHIP_OK;
+}
+
 // replaid.gsva.exact's argument checks (every entry point runs them before a device is touched)
 int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out) {
   PH_REQUIRE(std::isfinite(tau) && tau >= 0.0, "gsva_exact: tau must be finite and >= 0 (got %g)", tau);
-  PH_REQUIRE(rowtf >= 0 && rowtf <= 2, "Error: unknown row transform %d", rowtf);                     // R/plaid.R:348
+  PH_REQUIRE(rowtf >= 0 && rowtf <= 3, "Error: unknown row transform %d", rowtf);                     // R/plaid.R:348
+  PH_REQUIRE(rowtf != 3 || n >= 2, "gsva_exact: rowtf = \"gauss\" needs at least 2 samples (got %d)", n);
   PH_REQUIRE(rowtf != 1 || ndev == 1, "gsva_exact_multi: rowtf = \"ecdf\" ranks all samples of a gene together and is not "
                                       "sharded by sample; score it on one device (plaidhip_gsva_exact)");
   PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, 0.0, S_out));

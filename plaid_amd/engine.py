@@ -473,7 +473,8 @@ def _ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False, single=Tr
     return S
 
 
-GSVA_EXACT_ROWTF = {"z": 0, "ecdf": 1, "none": 2}
+GSVA_EXACT_ROWTF = {"z": 0, "ecdf": 1, "none": 2, "gauss": 3}
+GSVA_KCDF_TABLE = 10001   # PLAIDHIP_GSVA_KCDF_TABLE
 
 
 def check_gsva_exact_args(tau, rowtf):
@@ -489,8 +490,8 @@ def check_gsva_exact_args(tau, rowtf):
 
 def _gsva_exact(self, X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True):
     """plaidhip_gsva_exact: GSVA's random-walk statistic for any tau >= 0; rowtf "z" / "ecdf" (replaid.gsva's row
-    transforms) or "none"; X dense or scipy CSC with sorted, distinct row indices (scored as its dense form), G aligned
-    to X's rows"""
+    transforms), "none" or "gauss" (GSVA's Gaussian kernel CDF estimate: gsva_kcdf; at least 2 samples); X dense or scipy
+    CSC with sorted, distinct row indices (scored as its dense form), G aligned to X's rows"""
     tau, tf = check_gsva_exact_args(tau, rowtf)
     xp, xi, xv, g, n, keep = _x_args(X)
     Gp, Gi = _as_i32(Gp), _as_i32(Gi)
@@ -499,6 +500,25 @@ def _gsva_exact(self, X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True):
     check(self.lib.plaidhip_gsva_exact(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, tau, tf,
                                        int(bool(max_diff)), _np_ptr(S)))
     return S
+
+
+def _gsva_kcdf(self, X):
+    """plaidhip_gsva_kcdf: V (genes x samples), GSVA's Gaussian kernel CDF estimate of every value among its gene's
+    samples (bandwidth sd / 4, the sums of include/plaidhip.h in sample order), the row transform "gauss" of gsva_exact;
+    X dense or scipy CSC (expanded on the device, the bits of its dense form); at least 2 samples"""
+    xp, xi, xv, g, n, keep = _x_args(X)
+    if n < 2:
+        raise ValueError(f"gsva_kcdf: the kernel CDF estimate needs at least 2 samples (got {n})")
+    V = np.empty((g, n), dtype=np.float64, order="F")
+    check(self.lib.plaidhip_gsva_kcdf(self.handle, xp, xi, xv, g, n, _np_ptr(V)))
+    return V
+
+
+def gsva_kcdf_table() -> np.ndarray:
+    """the 10,001 values of Phi on [0, 10] that the kernels of gsva_kcdf read (built on the host: needs no device)"""
+    T = np.empty(GSVA_KCDF_TABLE, dtype=np.float64)
+    check(_lib.load().plaidhip_gsva_kcdf_table(_np_ptr(T)))
+    return T
 
 
 def _plaid_test(self, X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
@@ -605,6 +625,8 @@ Context.aucell = _aucell
 Context.scse = _scse
 Context.ssgsea_exact = _ssgsea_exact
 Context.gsva_exact = _gsva_exact
+Context.gsva_kcdf = _gsva_kcdf
+Context.gsva_kcdf_table = staticmethod(gsva_kcdf_table)
 
 _default_ctx: Context | None = None
 
@@ -687,7 +709,8 @@ def ssgsea_exact_multi(X, Gp, Gi, alpha=0.25, scale=True, norm=False, devices=1,
 
 def gsva_exact_multi(X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True, devices=1) -> np.ndarray:
     """replaid.gsva.exact (Context.gsva_exact) with the sample columns sharded over `devices`; "ecdf" ranks all samples
-    of a gene together and is refused over more than one device"""
+    of a gene together and is refused over more than one device; "gauss" sends all of X to every device, which computes
+    the kernel CDF estimate of its own columns (the one-device bits)"""
     tau, tf = check_gsva_exact_args(tau, rowtf)
     lib = _lib.load()
     xp, xi, xv, g, n, keep = _x_args(X)

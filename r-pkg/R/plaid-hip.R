@@ -395,17 +395,21 @@ replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {
 
 ## The random-walk statistic of GSVA (Haenzelmann et al. 2013) -- replaid.gsva is the reference's approximation, a mean
 ## of transformed ranks (R/plaid.R:353-356).  include/plaidhip.h (plaidhip_gsva_exact) pins it: the row transform v of X
-## ("z" and "ecdf" as replaid.gsva's, "none": X as it is, for a caller's own per-gene CDF); per sample the genes in
+## ("z" and "ecdf" as replaid.gsva's, "none": X as it is, for a caller's own per-gene CDF, "gauss": GSVA's default, the
+## Gaussian kernel CDF estimate of every value among its gene's samples with bandwidth sd / 4, as the sum over the samples
+## without GSVA's division by n and its logit, which keep a sample's order; at least 2 samples); per sample the genes in
 ## order(v, decreasing = TRUE), ties in row order; the gene at position pos weighs abs((N + 1 - pos) - N / 2)^tau; a
 ## Kolmogorov-Smirnov walk per set whose largest positive and largest negative excursion are added (max.diff = TRUE) or
 ## the larger of which is returned (FALSE; the negative one when equal).  Sets without aligned members, with all genes,
 ## or of zero total weight score NA; a sample holding an NA scores NA for every set.  Differs from GSVA::gsva on purpose:
 ## the running sum is evaluated at the hits (three roundings per value, where GSVA's loop accumulates N), a set of zero
-## total weight is NA, and abs.ranking and the kernel CDF estimate (kcdf) are not offered.  No normalize_medians.
-## nrow(X) at most 131,072.  options(plaidhip.devices = ...) shards the samples; "ecdf" takes one device.
-replaid.gsva.exact <- function(X, matG, tau = 1, rowtf = c("z", "ecdf", "none")[1], max.diff = TRUE) {
+## total weight is NA, and abs.ranking and the Poisson kernel (kcdf = "Poisson") are not offered.  No normalize_medians.
+## nrow(X) at most 131,072.  options(plaidhip.devices = ...) shards the samples; "ecdf" takes one device, "gauss" sends all
+## of X to every device.
+replaid.gsva.exact <- function(X, matG, tau = 1, rowtf = c("z", "ecdf", "none", "gauss")[1], max.diff = TRUE) {
   rowtf <- rowtf[1]
-  if (!rowtf %in% c("z", "ecdf", "none")) stop("Error: unknown row transform", rowtf)
+  if (!rowtf %in% c("z", "ecdf", "none", "gauss")) stop("Error: unknown row transform", rowtf)
+  if (rowtf == "gauss" && ncol(X) < 2L) stop("gsva_exact: rowtf = \"gauss\" needs at least 2 samples")
   tau <- as.double(tau)
   if (length(tau) != 1L || !is.finite(tau) || tau < 0) stop("gsva_exact: tau must be finite and >= 0")
   pat <- .aligned_pattern(X, matG)
@@ -413,7 +417,7 @@ replaid.gsva.exact <- function(X, matG, tau = 1, rowtf = c("z", "ecdf", "none")[
   .session()
   if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
   xa <- .x_args(X)
-  tf <- match(rowtf, c("z", "ecdf", "none")) - 1L
+  tf <- match(rowtf, c("z", "ecdf", "none", "gauss")) - 1L
   dev <- .devices()
   S <- if (length(dev) > 1L && rowtf != "ecdf")
          .Call("R_plaidhip_gsva_exact_multi", dev, xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, tau, tf,

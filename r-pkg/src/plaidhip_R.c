@@ -278,7 +278,7 @@ SEXP R_plaidhip_ssgsea_exact_ks_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, S
   return S;
 }
 
-/* replaid.gsva.exact: GSVA's random-walk statistic; rowtf 0 "z", 1 "ecdf", 2 "none" */
+/* replaid.gsva.exact: GSVA's random-walk statistic; rowtf 0 "z", 1 "ecdf", 2 "none", 3 "gauss" */
 SEXP R_plaidhip_gsva_exact(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP tau, SEXP rowtf, SEXP max_diff) {
   const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
   SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
