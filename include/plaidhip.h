@@ -276,6 +276,14 @@ int plaidhip_dev_gsea_ks_f64(plaidhip_ctx* ctx, const void* Q, const void* W, in
 int plaidhip_dev_gsva_ks_f64(plaidhip_ctx* ctx, const void* Q, int64_t ldq, const void* colnan, int32_t g, int32_t n,
                              const void* Gp, const void* Gi, int32_t m, double tau, int max_diff, void* S, int64_t lds);
 
+/* The dispersion of plaidhip_sing_exact on ranks already on the device, stream-ordered, no read-back.  R: the min ranks of
+ * the columns (plaidhip_dev_colranks_dense_f64, ties "min"), Q: their last ranks and colnan (plaidhip_dev_ssgsea_exact_
+ * operands*_f64 with alpha = 0), both g x n fp64 with leading dimension ldq.  Gp / Gi are DEVICE copies of the aligned
+ * pattern.  S: m x n fp64, leading dimension lds.  The ranks by position (g n u32) are built in the context's workspace
+ * first.  g <= PLAIDHIP_GSEA_KS_MAX_GENES, else PLAIDHIP_EUNSUPPORTED with nothing launched.                              */
+int plaidhip_dev_sing_mad_f64(plaidhip_ctx* ctx, const void* R, const void* Q, int64_t ldq, const void* colnan, int32_t g,
+                              int32_t n, const void* Gp, const void* Gi, int32_t m, void* S, int64_t lds);
+
 /* normalize_medians() (R/plaid.R:554-575) in three phases so that a sample-sharded host
  * can all-reduce between them:
  *   1. flags  : plaidhip_dev_minflags   (or the SpMM epilogue's `flags`)  -> ignore.zero
@@ -496,6 +504,37 @@ int plaidhip_gsva_kcdf(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, 
 /* out[PLAIDHIP_GSVA_KCDF_TABLE] <- T.  Needs no device. */
 int plaidhip_gsva_kcdf_table(double* out);
 
+/* replaid.sing.exact(X, matG, matD, center, dispersion): singscore's normalised score and its dispersion, where
+ * replaid.sing (R/plaid.R:203-216) returns mean(rank) / N - 0.5, which only orders the samples as singscore does.  The
+ * formulas follow singscore's rankGenes and singscoring (simpleScore) AS RECALLED: the package's source is not in this
+ * tree, so the statistic is pinned here, operation for operation, and tested against these words.
+ * Per sample column with N = g rows (all rows of X, before the alignment with the sets, as in replaid.sing), in fp64:
+ *  1. r = rank(x, ties = "min"), integers 1..N: the ranks replaid.sing takes.  A down set is scored on d = N + 1 - r.
+ *  2. Score of a set with k aligned members of ranks s:  mean = (double)(sum s) / (double)k  (the sum an exact integer;
+ *     a down set's is k (N + 1) - sum r, formed in integers);  low = (k + 1) / 2,  high = (2 N - k + 1) / 2,  so
+ *     high - low = N - k;  score = (mean - low) / (double)(N - k),  then - 0.5 when center != 0.  Two correctly rounded
+ *     divisions and at most two subtractions; no product, nothing to contract.  k = 0 and k = N give NaN: 0 / 0, and for
+ *     k = N in a column with ties, where the min ranks sum to less than N (N + 1) / 2 and the quotient would be -Inf, NaN
+ *     by rule (high == low: the score is not defined).
+ *  3. Dispersion:  med = median(s) (R's: the mean of the two middle values for even k, an exact half-integer);
+ *     dev_i = |s_i - med|;  disp = 1.4826 * median(dev), the constant R's literal of mad().  median(dev) is an exact
+ *     multiple of 0.25 (formed in integers as 4 median(dev), then * 0.25), so the product carries the one rounding.
+ *     k = 0 gives NaN, k = N is finite.  The dispersion of a down set is that of its r (a reflection), bit for bit.
+ *  4. Column j of the down sets (Dp / Di, aligned to X's rows as Gp / Gi are, m columns) pairs with column j of the up
+ *     sets: total = up + down, one add each for score and dispersion; an empty down column makes that row NaN.
+ *     Dp == NULL: up only; total, down, total_disp and down_disp must then be NULL (PLAIDHIP_EINVAL otherwise).
+ *  5. A column of X holding a NaN gives NaN in every output.
+ * Six nullable m x n outputs; what is NULL is not computed: without a dispersion output the per-pair kernel is not
+ * launched and the launches are replaid.sing's and an epilogue.  Each column is ranked once whatever is asked for; the
+ * dispersions add one rank pass over a tie-free column built from those ranks (the last ranks).  The totals are filled on
+ * the device.  X dense (Xp == NULL) or a dgCMatrix (rows increasing inside a column), never densified on the host: its
+ * zeros are ranked as colranks ranks them for replaid.sing, the result has the dense form's bits.  fp64 and integers in
+ * every precision mode.  With a dispersion output g <= PLAIDHIP_GSEA_KS_MAX_GENES, else PLAIDHIP_EUNSUPPORTED before any
+ * device work.  Not offered: knownDirection = FALSE, other dispersion functions, stable genes, permutation p-values.    */
+int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                        const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
+                        double* total, double* up, double* down, double* total_disp, double* up_disp, double* down_disp);
+
 /* ---- several GPUs of one node from ONE host process (the R session): multi.cpp ----------------------
  * The sample columns are cut into ndev contiguous shards (plaidhip_shard_bounds); a host thread per device
  * moves its shard over its own PCIe link (pipelined through pinned staging), runs the same kernels, and the
@@ -540,6 +579,12 @@ int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* 
 int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
                               int max_diff, double* S_out);
+/* plaidhip_sing_exact over several devices, sharded by sample column.  Nothing couples the shards: every sharding returns
+ * the one-device bits.  The argument checks and the device list's run before any device is touched.                     */
+int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
+                              int32_t m, int center, double* total, double* up, double* down, double* total_disp,
+                              double* up_disp, double* down_disp);
 /* replaid.ucell / aucell / scse / gsva over several devices: the arguments and results of plaidhip_ucell, plaidhip_aucell,
  * plaidhip_scse and plaidhip_gsva (rowtf = 0, "z"), X dense or a dgCMatrix as above.  The argument checks run before any
  * device is touched.  What couples the shards is combined on the host: max(rX) (R/plaid.R:278, 306, 354), the min / max

@@ -92,6 +92,8 @@ SIGNATURES = {
     "plaidhip_sing_dense": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp],
     "plaidhip_ssgsea_dense": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
     "plaidhip_ssgsea_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
+    "plaidhip_dev_sing_mad_f64": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64],
+    "plaidhip_sing_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "plaidhip_dev_gsva_ks_f64": [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp, _i64],
     "plaidhip_gsva_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_gsva_kcdf": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],
@@ -108,6 +110,8 @@ SIGNATURES = {
     "plaidhip_aucell_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
     "plaidhip_scse_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, C.POINTER(_int)],
     "plaidhip_gsva_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp],
+    "plaidhip_sing_exact_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _int, _vp, _vp, _vp, _vp, _vp,
+                                  _vp],
     "plaidhip_gsva_exact_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_ssgsea_exact_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_ssgsea_exact_ks_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],

@@ -359,6 +359,35 @@ def replaid_gsva_exact(X, matG, tau=1, rowtf="z", max_diff=True, ctx: Context | 
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
+def replaid_sing_exact(X, matG, matD=None, center=True, dispersion=True, ctx: Context | None = None):
+    """replaid.sing.exact(): singscore's normalised score (mean rank - low) / (high - low) [- 0.5] and its dispersion, the
+    MAD of the set's ranks in the sample (include/plaidhip.h: plaidhip_sing_exact), where replaid.sing returns
+    mean(rank) / N - 0.5.  matD (optional): the down sets, column j pairing with column j of matG, with its own row
+    names.  Returns a dict of NamedMatrix: UpScore and UpDispersion; with matD also TotalScore, DownScore,
+    TotalDispersion and DownDispersion (Total = Up + Down).  dispersion = False returns the scores alone.  The arguments
+    are checked before any device is touched."""
+    from .engine import check_sing_exact_args
+    X, matG = as_named(X), as_named(matG)
+    if matD is not None:
+        matD = as_named(matD)
+        if matD.shape[1] != matG.shape[1]:
+            raise ValueError(f"sing_exact: matD has {matD.shape[1]} columns, matG {matG.shape[1]}")
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    dpat = (None, None)
+    if matD is not None:
+        dpat = aligned_pattern(X, matD)
+        if dpat is None:   # no down gene among X's rows: every down column is empty
+            dpat = (np.zeros(matD.shape[1] + 1, dtype=np.int32), np.zeros(0, dtype=np.int32))
+    check_sing_exact_args(X.shape[0], pat[0], dpat[0], dispersion)
+    ctx = ctx or default_context()
+    V = _canonical_csc(X.values) if X.is_sparse else X.values   # the CSC slots go to the device: no dense X on the host
+    out = ctx.sing_exact(V, pat[0], pat[1], dpat[0], dpat[1], center, dispersion)
+    return {name: NamedMatrix(S, matG.colnames, X.colnames) for name, S in out.items()}
+
+
 _TEST_BITS = {"one": 1, "two": 2, "lm": 4}
 
 

@@ -754,6 +754,26 @@ int plaidhip_dev_gsva_ks_f64(plaidhip_ctx* ctx, const void* Q, int64_t ldq, cons
                         static_cast<double*>(S), lds);
 } catch (...) { return plaidhip::on_exception(); }
 
+// the dispersion of replaid.sing.exact on the device's min and last ranks (kernels_sing.hip), stream-ordered
+int plaidhip_dev_sing_mad_f64(plaidhip_ctx* ctx, const void* R, const void* Q, int64_t ldq, const void* colnan, int32_t g,
+                              int32_t n, const void* Gp, const void* Gi, int32_t m, void* S, int64_t lds) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(g > 0 && n >= 0 && m >= 0 && ldq >= g && lds >= m, "sing_mad: bad dims g=%d n=%d m=%d ldq=%lld lds=%lld", g, n, m,
+             (long long)ldq, (long long)lds);
+  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("sing_mad: nrow(X) = %d (at most %d rows)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(R && Q && colnan && Gp && Gi && S, "sing_mad: null R/Q/colnan/Gp/Gi/S");
+  PH_TRY(ensure_workspace(ctx, (size_t)g * n * 4));   // the ranks by position
+  uint32_t* Rpos = static_cast<uint32_t*>(ctx->ws);
+  PH_TRY(launch_sing_rpos(ctx, static_cast<const double*>(R), static_cast<const double*>(Q), ldq,
+                          static_cast<const uint32_t*>(colnan), g, n, Rpos, g));
+  return launch_sing_mad(ctx, static_cast<const double*>(Q), ldq, Rpos, g, static_cast<const uint32_t*>(colnan), g, n,
+                         static_cast<const int32_t*>(Gp), static_cast<const int32_t*>(Gi), m, static_cast<double*>(S), lds);
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_dev_minflags(plaidhip_ctx* ctx, const void* S, int64_t count, void* flags) try {
   PH_CTX(ctx);
   PH_REQUIRE(flags != nullptr && count >= 0, "minflags: bad arguments");
@@ -1397,6 +1417,16 @@ int plaidhip_debug_gsva_kcdf_slow_terms(unsigned long long* out) try {
   PH_REQUIRE(out != nullptr, "debug_gsva_kcdf_slow_terms: null out");
   *out = debug_gsva_kcdf_slow_terms();
   return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// replaid.sing.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, method 10)
+int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                        const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
+                        double* total, double* up, double* down, double* total_disp, double* up_disp, double* down_disp) try {
+  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
+  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
+  PH_CTX(ctx);
+  return run_sing_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.gsva from the row-transformed zX (dX: g x n, leading dimension ldg) on: the scores in dS (m x n), normalised.

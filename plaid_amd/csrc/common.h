@@ -493,6 +493,33 @@ int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const
                    double* S_out);
 int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out);
+// kernels_sing.hip: replaid.sing.exact (include/plaidhip.h: plaidhip_sing_exact).  All stream-ordered.
+// colnan[c] = 1 for a column holding a NaN: dense X (Xp == nullptr, g rows, leading dimension ldx) or the stored values of
+// CSC columns (the longest max_col_nnz)
+int launch_sing_colnan(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, int32_t g, int32_t n,
+                       int32_t max_col_nnz, uint32_t* colnan);
+// Q = rank(x, "last") from the min ranks R (a rank pass over the tie-free Y = R 2^26 + (g - 1 - row)); R, Y, Q: g x n,
+// leading dimension ld; g <= 2^26
+int launch_sing_last_ranks(plaidhip_ctx* ctx, const double* R, int64_t ld, int32_t g, int32_t n, double* Y, double* Q);
+// Rpos[q - 1] = r per column (u32, leading dimension ldp), columns flagged in colnan skipped
+int launch_sing_rpos(plaidhip_ctx* ctx, const double* R, const double* Q, int64_t ld, const uint32_t* colnan, int32_t g,
+                     int32_t n, uint32_t* Rpos, int64_t ldp);
+// the pinned score epilogue in place: Cu / Cd (nullable) hold the sums of min ranks of the up / down sets, ku / kd the set
+// sizes on the device; tot (nullable, needs Cd) = up + down
+int launch_sing_score(plaidhip_ctx* ctx, double* Cu, double* Cd, double* tot, int64_t lds, int32_t m, int32_t n,
+                      const int32_t* ku, const int32_t* kd, int32_t g, int center, const uint32_t* colnan);
+int launch_sing_add(plaidhip_ctx* ctx, const double* A, const double* B, double* out, int64_t lds, int32_t m, int32_t n);
+// S (m x n, leading dimension lds) <- 1.4826 * median |s - median(s)| of every set's min ranks; Gp / Gi on the device.
+// g > PLAIDHIP_GSEA_KS_MAX_GENES: PLAIDHIP_EUNSUPPORTED.
+int launch_sing_mad(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* Rpos, int64_t ldp, const uint32_t* colnan,
+                    int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S, int64_t lds);
+// multi.cpp: replaid.sing.exact on ndev contexts (one: plaidhip_sing_exact); its argument checks, which touch no device.
+// out: total, up, down score, total, up, down dispersion, each nullable
+int run_sing_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                   int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
+                   double* const out[6]);
+int check_sing_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                          const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double* const out[6]);
 // kernels_kcdf.hip: GSVA's Gaussian kernel CDF estimate (include/plaidhip.h: plaidhip_gsva_kcdf).  V (g x (j1 - j0), leading
 // dimension ldv) <- the kernel sums of the test columns [j0, j1) of the dense device matrix X (g x n, leading dimension
 // ldx) over ALL n samples; H: g doubles of scratch (the bandwidths).  Stream-ordered.

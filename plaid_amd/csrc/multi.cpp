@@ -300,7 +300,7 @@ struct Shared {
 
 struct Call {
   int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test, 8 ssgsea.exact,
-                // 9 gsva.exact
+                // 9 gsva.exact, 10 sing.exact
   const int32_t* Xp;
   const int32_t* Xi;
   const double* X;   // dense values or CSC @x
@@ -330,6 +330,12 @@ struct Call {
   int tests = 0, metap_method = 0;
   int64_t n0 = 0, n1 = 0;
   double* out = nullptr;
+  // method 10, sing.exact: the down sets (null: none), center, and the six nullable results (total, up, down score; total,
+  // up, down dispersion)
+  const int32_t* Dp = nullptr;
+  const int32_t* Di = nullptr;
+  int center = 1;
+  double* sx_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // columns [lo, lo + nloc) of shard k.  Dense replaid.gsva and plaid.test (dense or not: its score rows are chained too)
@@ -764,12 +770,169 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
   return rc;
 }
 
+// one device's part of replaid.sing.exact (method 10, kernels_sing.hip): the min ranks of its columns as replaid.sing takes
+// them (a dgCMatrix: the dense rank matrix built on the device), the crossprods C = G'R on the exact rank route and the
+// pinned epilogue; for the dispersions the last ranks (a second rank pass over a tie-free column made from the first),
+// the ranks by position and the per-pair kernel, once per direction.  Nothing couples the shards.
+int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  int rc = PLAIDHIP_OK;
+  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
+  auto step = [&](const std::function<int()>& fn) {
+    if (!live()) return;
+    try {
+      rc = fn();
+    } catch (...) {
+      rc = on_exception();
+    }
+    if (rc != PLAIDHIP_OK) sh.abort.store(1);
+  };
+  int32_t lo = 0, nloc = 0;
+  shard_columns(c, ndev, k, &lo, &nloc);
+  const int32_t g = c.g, m = c.m;
+  const bool sparse = c.Xp != nullptr;
+  const bool down = c.Dp != nullptr;
+  const bool want_score = c.sx_out[0] || c.sx_out[1] || c.sx_out[2];
+  const bool want_disp = c.sx_out[3] || c.sx_out[4] || c.sx_out[5];
+  const int64_t ld = even_ld(g);   // replaid.sing's layout: the pair crossprod takes the ranks as it takes them there
+  const int saved_precision = ctx->precision;
+  ctx->precision = PLAIDHIP_PRECISION_F64;   // fp64 and integers in every mode, as the other exact scorers
+  plaidhip_geneset *gs_up = nullptr, *gs_dn = nullptr;
+  CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dops{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
+  DevBuf dk, dGp, dGi, dDp, dDi;
+  HomeBuffer home[6];
+  double *R = nullptr, *Y = nullptr, *Q = nullptr, *Rx = nullptr;
+  uint32_t* d_colnan = nullptr;
+  const size_t nscores = (size_t)m * (size_t)std::max(nloc, 1);
+  auto part = [&](int o) { return dS.as<double>() + (size_t)o * nscores; };   // [total | up | down] scores, then dispersions
+  std::vector<int32_t> kset((size_t)m * 2, 0), ploc;
+  for (int32_t j = 0; j < m; ++j) {   // members after the alignment
+    kset[(size_t)j] = c.Gp[j + 1] - c.Gp[j];
+    if (down) kset[(size_t)m + j] = c.Dp[j + 1] - c.Dp[j];
+  }
+
+  // ---- upload, NaN flags, min ranks; last ranks and the ranks by position --------------------------------------------------
+  step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    if (want_score) {
+      PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs_up));
+      if (down) PH_TRY(acquire_geneset(ctx, g, m, c.Dp, c.Di, &gs_dn));
+    }
+    PH_TRY(dsmall.alloc((size_t)std::max(nloc, 1) * 4));
+    d_colnan = dsmall.as<uint32_t>();
+    PH_TRY(dS.alloc(nscores * 6 * 8));
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(dk.alloc((size_t)m * 2 * 4));
+    PH_HIP(hipMemcpyAsync(dk.p, kset.data(), (size_t)m * 2 * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (want_disp) {
+      const size_t zu = (size_t)c.Gp[m], zd = down ? (size_t)c.Dp[m] : 0;
+      PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
+      PH_TRY(dGi.alloc(std::max<size_t>(zu, 1) * 4));
+      PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      if (zu > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, zu * 4, hipMemcpyHostToDevice, ctx->stream));
+      if (down) {
+        PH_TRY(dDp.alloc((size_t)(m + 1) * 4));
+        PH_TRY(dDi.alloc(std::max<size_t>(zd, 1) * 4));
+        PH_HIP(hipMemcpyAsync(dDp.p, c.Dp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (zd > 0) PH_HIP(hipMemcpyAsync(dDi.p, c.Di, zd * 4, hipMemcpyHostToDevice, ctx->stream));
+      }
+    }
+    const int64_t z0 = sparse ? c.Xp[lo] : 0;
+    const int64_t zx = sparse ? (int64_t)c.Xp[lo + nloc] - z0 : 0;
+    const size_t col = (size_t)ld * nloc;
+    // [R | Y (then the ranks by position, u32) | Q] for the dispersions, R alone without; a dgCMatrix: the ranks of its
+    // stored values behind them
+    PH_TRY(dops.alloc((col * (want_disp ? 3 : 1) + (size_t)std::max<int64_t>(zx, 1)) * 8));
+    R = dops.as<double>();
+    Y = R + col;
+    Q = Y + col;
+    Rx = R + col * (want_disp ? 3 : 1);
+    if (!sparse) {
+      PH_TRY(dX.alloc(col * 8));
+      auto on_panel = [&](int64_t c0, int64_t c1) -> int {   // the ranks of a column panel follow its DMA, as replaid.sing's
+        return launch_colranks_dense_f64(ctx, dX.as<double>() + c0 * ld, ld, g, (int32_t)(c1 - c0), PLAIDHIP_TIES_MIN, 0, 1.0,
+                                         R + c0 * ld, ld, nullptr);
+      };
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
+                              (size_t)g * 8, nloc, on_panel));
+      PH_TRY(launch_sing_colnan(ctx, dX.as<double>(), ld, nullptr, g, nloc, 0, d_colnan));
+    } else {
+      ploc.resize((size_t)nloc + 1);
+      for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
+      const int32_t max_nnz = host_max_col_nnz(ploc.data(), nloc);
+      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
+      PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
+      PH_TRY(dX.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
+      PH_TRY(launch_sing_colnan(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), g, nloc, max_nnz, d_colnan));
+      // replaid.sing ranks the zeros too (shard_worker): the dense rank matrix from the ranks of the stored values, or, for
+      // a column with more stored values than one pass ranks, densify and rank
+      if (max_nnz <= max_sparse_rank_column())
+        PH_TRY(launch_colranks_csc_dense_nz_f64(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), g, nloc, max_nnz,
+                                                PLAIDHIP_TIES_MIN, 0, 1.0, Rx, R, ld, nullptr));
+      else
+        PH_TRY(launch_colranks_csc_dense_f64(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), g, nloc,
+                                             PLAIDHIP_TIES_MIN, 0, 1.0, R, ld, nullptr));
+    }
+    if (want_disp) {
+      PH_TRY(launch_sing_last_ranks(ctx, R, ld, g, nloc, Y, Q));
+      PH_TRY(launch_sing_rpos(ctx, R, Q, ld, d_colnan, g, nloc, reinterpret_cast<uint32_t*>(Y), ld));
+    }
+    for (int o = 0; o < 6; ++o)
+      if (c.sx_out[o]) home[o].prepare(c.sx_out[o] + (int64_t)lo * m, (size_t)m * nloc * 8);
+    return PLAIDHIP_OK;
+  });
+
+  // ---- scores: crossprods on the exact rank route, the pinned epilogue; dispersions: the per-pair kernel -----------------
+  step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nloc == 0) return PLAIDHIP_OK;
+    if (want_score) {
+      // r holds integers in [1, N]: the rank route's u16 staging when 2 N fits, integer sums either way
+      const int xk = 2 * (int64_t)g < 65536 ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
+      PH_TRY(launch_spmm_dense_f64(ctx, gs_up, R, ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, part(1), m, nullptr, xk));
+      if (down)
+        PH_TRY(launch_spmm_dense_f64(ctx, gs_dn, R, ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, part(2), m, nullptr, xk));
+      PH_TRY(launch_sing_score(ctx, part(1), down ? part(2) : nullptr, down ? part(0) : nullptr, m, m, nloc, dk.as<int32_t>(),
+                               dk.as<int32_t>() + m, g, c.center, d_colnan));
+    }
+    if (want_disp) {
+      const uint32_t* Rpos = reinterpret_cast<const uint32_t*>(Y);
+      PH_TRY(launch_sing_mad(ctx, Q, ld, Rpos, ld, d_colnan, g, nloc, dGp.as<int32_t>(), dGi.as<int32_t>(), m, part(4), m));
+      if (down) {
+        // (the MAD of d = N + 1 - r is the MAD of r: a reflection)
+        PH_TRY(launch_sing_mad(ctx, Q, ld, Rpos, ld, d_colnan, g, nloc, dDp.as<int32_t>(), dDi.as<int32_t>(), m, part(5), m));
+        PH_TRY(launch_sing_add(ctx, part(4), part(5), part(3), m, m, nloc));
+      }
+    }
+    return PLAIDHIP_OK;
+  });
+
+  // ---- the requested shards go home ---------------------------------------------------------------------------------------
+  step([&]() -> int {
+    if (nloc > 0)
+      for (int o = 0; o < 6; ++o)
+        if (c.sx_out[o]) PH_TRY(home[o].copy(ctx, part(o)));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+  ctx->precision = saved_precision;
+  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
+    hipStreamSynchronize(ctx->stream);
+    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
+  }
+  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
 // one device's part of a sharded replaid.ucell / aucell / scse / gsva (methods 3 - 6).  The same phases as the context
 // entries (api.cpp: plaidhip_ucell ...), with the quantities that couple the samples combined on the host in between:
 // max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the z
 // row transform (:341-343) and the medians' flags and mean(medx) (:554-575).
 int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   if (c.method == 8) return ssgsea_exact_worker(ctx, c, ndev, k, sh);
+  if (c.method == 10) return sing_exact_worker(ctx, c, ndev, k, sh);
   int rc = PLAIDHIP_OK;
   auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
   auto step = [&](const std::function<int()>& fn) {
@@ -1626,6 +1789,41 @@ int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const
   return run_call(ctxs, ndev, c);
 }
 
+// replaid.sing.exact's argument checks (every entry point runs them before a device is touched)
+int check_sing_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                          const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double* const out[6]) {
+  const double* any = nullptr;
+  for (int o = 0; o < 6; ++o) any = any ? any : out[o];
+  PH_REQUIRE((int64_t)m * n == 0 || any != nullptr, "sing_exact: no output requested");
+  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, 0.0, any));
+  if (Dp != nullptr) {
+    PH_TRY(check_host_common(Dp, g, n, m));
+    PH_REQUIRE((int64_t)m * n == 0 || Di != nullptr || Dp[m] == 0, "sing_exact: null Di");
+  } else {
+    PH_REQUIRE(!out[0] && !out[2] && !out[3] && !out[5], "sing_exact: total and down results need the down sets");
+  }
+  if ((out[3] || out[4] || out[5]) && g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("sing_exact: nrow(X) = %d (at most %d rows with the dispersion)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  return PLAIDHIP_OK;
+}
+
+int run_sing_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                   int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
+                   double* const out[6]) {
+  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
+  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  Call c{10, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, 0, 0.0, nullptr};
+  c.Dp = Dp;
+  c.Di = Di;
+  c.center = center ? 1 : 0;
+  for (int o = 0; o < 6; ++o) c.sx_out[o] = out[o];
+  return run_call(ctxs, ndev, c);
+}
+
 }  // namespace plaidhip
 
 // ---- multi-device entry points (include/plaidhip.h) ---------------------------------------------------------------------
@@ -1927,6 +2125,47 @@ int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, c
   std::vector<plaidhip_ctx*> ctxs;
   PH_TRY(multi_contexts(devices, ndev, ctxs));
   return run_gsva_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h): plaidhip_sing_exact_multi's engine with `nshards` contexts on ONE device.
+// fail_shard >= 0: that shard fails in its crossprod phase (the call must return an error, not hang).
+int plaidhip_debug_sing_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp, const int32_t* Xi,
+                                                    const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                                                    const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m,
+                                                    int center, double* total, double* up, double* down, double* total_disp,
+                                                    double* up_disp, double* down_disp) try {
+  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_sing_exact_sharded: nshards = %d", nshards);
+  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
+  int rc = PLAIDHIP_OK;
+  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
+    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
+    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
+  }
+  if (rc == PLAIDHIP_OK) rc = run_sing_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
+  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
+  for (plaidhip_ctx* cx : ctxs)
+    if (cx) plaidhip_finalize(cx);
+  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
+  return rc;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
+                              int32_t m, int center, double* total, double* up, double* down, double* total_disp,
+                              double* up_disp, double* down_disp) try {
+  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
+  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
+  if (devices != nullptr)
+    for (int k = 0; k < ndev; ++k)
+      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_sing_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_multi_set_precision(int mode) try {

@@ -250,6 +250,12 @@ class Context:
         check(self.lib.plaidhip_dev_gsva_ks_f64(self.handle, Q, int(ldq), colnan, int(g), int(n), Gp, Gi, int(m), float(tau),
                                                 int(bool(max_diff)), S, int(lds)))
 
+    def dev_sing_mad(self, R: int, Q: int, ldq: int, colnan: int, g: int, n: int, Gp: int, Gi: int, m: int, S: int, lds: int):
+        """the dispersion of replaid.sing.exact on the device's min ranks R (dev_colranks_dense, ties "min"), last ranks Q
+        and NaN flags (dev_ssgsea_exact_operands with alpha = 0) and a device copy of the aligned pattern: S (m x n)"""
+        check(self.lib.plaidhip_dev_sing_mad_f64(self.handle, R, Q, int(ldq), colnan, int(g), int(n), Gp, Gi, int(m), S,
+                                                 int(lds)))
+
     def dev_minflags(self, S: int, count: int, flags: int):
         check(self.lib.plaidhip_dev_minflags(self.handle, S, count, flags))
 
@@ -521,6 +527,42 @@ def gsva_kcdf_table() -> np.ndarray:
     return T
 
 
+SING_EXACT_MAX_GENES = 131072   # PLAIDHIP_GSEA_KS_MAX_GENES: the dispersion kernel's bitmap
+SING_EXACT_OUTPUTS = ("TotalScore", "UpScore", "DownScore", "TotalDispersion", "UpDispersion", "DownDispersion")
+
+
+def check_sing_exact_args(g, Gp, Dp, dispersion):
+    """the checks of plaidhip_sing_exact that need no device"""
+    if Dp is not None and len(Dp) != len(Gp):
+        raise ValueError(f"sing_exact: the down sets have {len(Dp) - 1} columns, the up sets {len(Gp) - 1}")
+    if dispersion and g > SING_EXACT_MAX_GENES:
+        raise _lib.PlaidHipError(_lib.EUNSUPPORTED,
+                                 f"sing_exact: nrow(X) = {g} (at most {SING_EXACT_MAX_GENES} rows with the dispersion)")
+
+
+def _sing_exact_call(fn, head, X, Gp, Gi, Dp, Di, center, dispersion):
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    down = Dp is not None
+    if down:
+        Dp, Di = _as_i32(Dp), _as_i32(Di)
+    check_sing_exact_args(g, Gp, Dp if down else None, dispersion)
+    m = len(Gp) - 1
+    want = [down, True, down, down and dispersion, bool(dispersion), down and dispersion]
+    outs = [np.empty((m, n), dtype=np.float64, order="F") if w else None for w in want]
+    check(fn(*head, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), _np_ptr(Dp) if down else None, _np_ptr(Di) if down else None, m,
+             int(bool(center)), *[None if o is None else _np_ptr(o) for o in outs]))
+    return {name: o for name, o in zip(SING_EXACT_OUTPUTS, outs) if o is not None}
+
+
+def _sing_exact(self, X, Gp, Gi, Dp=None, Di=None, center=True, dispersion=True):
+    """plaidhip_sing_exact: singscore's normalised score and dispersion (the MAD of the set's ranks) per set and sample;
+    X dense or scipy CSC with sorted, distinct row indices (scored as its dense form), the up sets G and the down sets D
+    (optional, as many columns) aligned to X's rows.  A dict of m x n matrices: UpScore [, UpDispersion], and with down
+    sets TotalScore, DownScore [, TotalDispersion, DownDispersion].  dispersion = False launches no per-pair kernel."""
+    return _sing_exact_call(self.lib.plaidhip_sing_exact, (self.handle,), X, Gp, Gi, Dp, Di, center, dispersion)
+
+
 def _plaid_test(self, X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
     """plaidhip_plaid_test: returns sets x 6 (gsetFC, p.one, p.two, p.lm, p.meta, q.meta), G's column order"""
     X = _as_f64_fortran(X)
@@ -625,6 +667,7 @@ Context.aucell = _aucell
 Context.scse = _scse
 Context.ssgsea_exact = _ssgsea_exact
 Context.gsva_exact = _gsva_exact
+Context.sing_exact = _sing_exact
 Context.gsva_kcdf = _gsva_kcdf
 Context.gsva_kcdf_table = staticmethod(gsva_kcdf_table)
 
@@ -721,6 +764,13 @@ def gsva_exact_multi(X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True, devices=1) ->
     check(lib.plaidhip_gsva_exact_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, tau, tf, int(bool(max_diff)),
                                         _np_ptr(S)))
     return S
+
+
+def sing_exact_multi(X, Gp, Gi, Dp=None, Di=None, center=True, dispersion=True, devices=1) -> dict:
+    """replaid.sing.exact (Context.sing_exact) with the sample columns sharded over `devices`: the one-device bits"""
+    lib = _lib.load()
+    dp, nd, dkeep = _devices_arg(devices)
+    return _sing_exact_call(lib.plaidhip_sing_exact_multi, (dp, nd), X, Gp, Gi, Dp, Di, center, dispersion)
 
 
 def ucell_multi(X, Gp, Gi, k_full, rmax=1500.0, devices=1) -> np.ndarray:

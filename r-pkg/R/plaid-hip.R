@@ -427,3 +427,36 @@ replaid.gsva.exact <- function(X, matG, tau = 1, rowtf = c("z", "ecdf", "none", 
   dimnames(S) <- list(colnames(matG), colnames(X))
   S
 }
+
+## singscore's normalised score and dispersion -- replaid.sing (R/plaid.R:213-219) returns mean(rank) / N - 0.5, which
+## orders the samples as singscore does and nothing more.  The formulas follow singscore's rankGenes and singscoring AS
+## RECALLED (the package's source is not in this tree); include/plaidhip.h (plaidhip_sing_exact) pins them: per sample
+## r = rank(x, ties = "min") over ALL rows of X; for a set with k aligned members of ranks s the score is
+## (mean(s) - (k + 1) / 2) / (N - k), minus 0.5 when center; the dispersion is mad(s) = 1.4826 * median(|s - median(s)|).
+## matD (optional): the down sets, column j pairing with column j of matG, scored on N + 1 - r; Total = Up + Down.  Sets
+## without aligned members or with all N genes score NA (the dispersion of all N genes is finite); an empty down column
+## makes its Total NA; a sample holding an NA is NA everywhere.  Returns a list of sets x samples matrices: UpScore,
+## UpDispersion and, with matD, TotalScore, DownScore, TotalDispersion, DownDispersion.  dispersion = FALSE returns the
+## scores alone and runs no per-pair kernel.  With the dispersion nrow(X) is at most 131,072.  Not offered:
+## knownDirection = FALSE, other dispersion functions, stable genes, permutation p-values.
+## options(plaidhip.devices = ...) shards the samples.
+replaid.sing.exact <- function(X, matG, matD = NULL, center = TRUE, dispersion = TRUE) {
+  if (!is.null(matD) && ncol(matD) != ncol(matG)) stop("sing_exact: matD has ", ncol(matD), " columns, matG ", ncol(matG))
+  pat <- .aligned_pattern(X, matG)
+  if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
+  Dp <- integer(0); Di <- integer(0)
+  if (!is.null(matD)) {
+    dpat <- .aligned_pattern(X, matD)
+    if (is.null(dpat)) dpat <- list(Gp = integer(ncol(matD) + 1L), Gi = integer(0))
+    Dp <- dpat$Gp; Di <- dpat$Gi
+  }
+  .session()
+  if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
+  xa <- .x_args(X)
+  dev <- .devices()
+  res <- .Call("R_plaidhip_sing_exact", if (length(dev) > 1L) dev else integer(0), xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X),
+               pat$Gp, pat$Gi, Dp, Di, isTRUE(as.logical(center)), isTRUE(as.logical(dispersion)), PACKAGE = "plaidhip")
+  names(res) <- c("TotalScore", "UpScore", "DownScore", "TotalDispersion", "UpDispersion", "DownDispersion")
+  res <- res[!vapply(res, is.null, logical(1))]
+  lapply(res, function(S) { dimnames(S) <- list(colnames(matG), colnames(X)); S })
+}

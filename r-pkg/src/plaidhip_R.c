@@ -299,6 +299,37 @@ SEXP R_plaidhip_gsva_exact_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g
   return S;
 }
 
+/* replaid.sing.exact: a list of six m x n matrices (total, up, down score; total, up, down dispersion), NULL where not
+ * computed: Dp of length 0 means no down sets, dispersion FALSE no dispersions.  devices of length 0: the session's context */
+SEXP R_plaidhip_sing_exact(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP Dp, SEXP Di,
+                           SEXP center, SEXP dispersion) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  const int down = LENGTH(Dp) > 0, disp = Rf_asLogical(dispersion) != 0;
+  const int want[6] = {down, 1, down, down && disp, disp, down && disp};
+  double* out[6];
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 6));
+  for (int o = 0; o < 6; ++o) {
+    out[o] = NULL;
+    if (want[o]) {
+      SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+      SET_VECTOR_ELT(res, o, S);
+      UNPROTECT(1);
+      out[o] = REAL(S);
+    }
+  }
+  if (LENGTH(devices) > 0)
+    check(plaidhip_sing_exact_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                    Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi), down ? INTEGER(Dp) : NULL,
+                                    down ? INTEGER(Di) : NULL, m, Rf_asLogical(center), out[0], out[1], out[2], out[3], out[4],
+                                    out[5]));
+  else
+    check(plaidhip_sing_exact(ctx(), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi),
+                              down ? INTEGER(Dp) : NULL, down ? INTEGER(Di) : NULL, m, Rf_asLogical(center), out[0], out[1],
+                              out[2], out[3], out[4], out[5]));
+  UNPROTECT(1);
+  return res;
+}
+
 SEXP R_plaidhip_ucell(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP kfull, SEXP rmax) {
   const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
   SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
@@ -472,6 +503,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_aucell_multi", (DL_FUNC)&R_plaidhip_aucell_multi, 9},
     {"R_plaidhip_scse_multi", (DL_FUNC)&R_plaidhip_scse_multi, 10},
     {"R_plaidhip_gsva_multi", (DL_FUNC)&R_plaidhip_gsva_multi, 10},
+    {"R_plaidhip_sing_exact", (DL_FUNC)&R_plaidhip_sing_exact, 12},
     {"R_plaidhip_gsva_exact", (DL_FUNC)&R_plaidhip_gsva_exact, 10},
     {"R_plaidhip_gsva_exact_multi", (DL_FUNC)&R_plaidhip_gsva_exact_multi, 11},
     {"R_plaidhip_ssgsea_exact", (DL_FUNC)&R_plaidhip_ssgsea_exact, 10},
