@@ -104,10 +104,7 @@ namespace {
 
 // The host-level entry points prepare the gene-set collection themselves.  An R session calls them again and
 // again with the same matG, so the last few prepared collections stay in the context (keyed by sizes and a hash
-// of the pattern) instead of being rebuilt: preparing C2's 5,000 sets costs ~20 ms of a 76 ms call.
-struct GenesetHolder {
-  plaidhip_geneset* gs = nullptr;   // owned by the context's cache
-};
+// of the pattern) instead of being rebuilt: preparing C2's 5,000 sets costs ~20 ms of a 76 ms call (acquire_geneset).
 
 // two independent 64-bit hashes over the int32 words of the pattern (a 128-bit key; it only ever lives in this process).
 // Two ids per step and four interleaved lanes per hash: one multiply chain is latency-bound at ~1.4 ns per id (7.5 ms of
@@ -183,15 +180,6 @@ int h2d(plaidhip_ctx* ctx, void* dst, const void* src, size_t bytes) {
   return upload_host(ctx, dst, 1, src, 1, (int64_t)bytes);
 }
 
-// Dense host matrix (g x n, column-major) -> device with an EVEN leading dimension, so that both
-// columns of a pair start 16-byte aligned (the two-columns-per-pass SpMM kernel needs that).
-inline int64_t even_ld(int32_t g) { return (int64_t)g + (g & 1); }
-int h2d_cols(plaidhip_ctx* ctx, void* dst, int64_t ldd, const double* src, int32_t g, int32_t n) {
-  if ((int64_t)g * n == 0) return PLAIDHIP_OK;
-  if (ldd == g) return h2d(ctx, dst, src, (size_t)g * n * 8);
-  return upload_host(ctx, dst, (size_t)ldd * 8, src, (size_t)g * 8, n);
-}
-
 // normalize_medians on a device-resident S (R/plaid.R:554-575), fully enqueued: ignore.zero is
 // resolved on the device from the flag words, mean(medx) from the {sum, count} pair.
 int normalize_on_device(plaidhip_ctx* ctx, double* dS, int32_t m, int32_t n, int ignore_zero,
@@ -228,10 +216,6 @@ int check_host_common(const void* G_p, int32_t g, int32_t n, int32_t m) {
   return PLAIDHIP_OK;
 }
 }  // namespace plaidhip
-namespace {
-
-}  // namespace
-
 extern "C" {
 
 int plaidhip_version(void) { return PLAIDHIP_VERSION; }
@@ -1058,175 +1042,33 @@ int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t
 
 }  // extern "C"
 
-// ---- "next" rows: ucell / aucell / scse ---------------------------------------------------
-namespace {
-
-// uploads X (dense when Xp == nullptr, else CSC) and produces the dense average ranks on the device
-struct RankedInput {
-  DevBuf dX, dXp, dXi, dR, dRx, dsmall;
-  double* R = nullptr;
-  double* d_colmax = nullptr;
-  double* d_gmax = nullptr;     // device scalar max(rX)
-};
-
-int dense_average_ranks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                        int32_t g, int32_t n, RankedInput& ri) {
-  PH_TRY(ri.dR.alloc((size_t)g * n * 8));
-  PH_TRY(ri.dsmall.alloc(64 + (size_t)n * 8));
-  ri.R = ri.dR.as<double>();
-  ri.d_gmax = ri.dsmall.as<double>();
-  ri.d_colmax = reinterpret_cast<double*>(ri.dsmall.as<char>() + 64);
-  if (Xp == nullptr) {
-    PH_TRY(ri.dX.alloc((size_t)g * n * 8));
-    PH_TRY(h2d(ctx, ri.dX.p, X_or_x, (size_t)g * n * 8));
-    PH_TRY(launch_colranks_dense_f64(ctx, ri.dX.as<double>(), g, g, n, PLAIDHIP_TIES_AVERAGE, 0, 1.0, ri.R, g,
-                                     ri.d_colmax));
-  } else {
-    PH_TRY(check_host_csc(Xp, Xi, g, n));
-    const int64_t zx = Xp[n];
-    PH_TRY(ri.dXp.alloc((size_t)(n + 1) * 4));
-    PH_TRY(ri.dXi.alloc((size_t)zx * 4));
-    PH_TRY(ri.dX.alloc((size_t)zx * 8));
-    PH_TRY(h2d(ctx, ri.dXp.p, Xp, (size_t)(n + 1) * 4));
-    PH_TRY(h2d(ctx, ri.dXi.p, Xi, (size_t)zx * 4));
-    PH_TRY(h2d(ctx, ri.dX.p, X_or_x, (size_t)zx * 8));
-    // zeros tie: dense ranks from the ranks of the stored values (any nrow(X)) unless a column stores too many
-    const int32_t max_nnz = host_max_col_nnz(Xp, n);
-    if (max_nnz <= max_sparse_rank_column()) {
-      PH_TRY(ri.dRx.alloc((size_t)(zx > 0 ? zx : 1) * 8));
-      PH_TRY(launch_colranks_csc_dense_nz_f64(ctx, ri.dXp.as<int32_t>(), ri.dXi.as<int32_t>(), ri.dX.as<double>(), g, n, max_nnz,
-                                              PLAIDHIP_TIES_AVERAGE, 0, 1.0, ri.dRx.as<double>(), ri.R, g, ri.d_colmax));
-    } else {
-      PH_TRY(launch_colranks_csc_dense_f64(ctx, ri.dXp.as<int32_t>(), ri.dXi.as<int32_t>(), ri.dX.as<double>(), g, n,
-                                           PLAIDHIP_TIES_AVERAGE, 0, 1.0, ri.R, g, ri.d_colmax));
-    }
-  }
-  PH_TRY(launch_max(ctx, ri.d_colmax, n, ri.d_gmax));
-  return PLAIDHIP_OK;
-}
-
-int plaid_on_device(plaidhip_ctx* ctx, plaidhip_geneset* gs, const double* dX, int32_t g, int32_t n, int32_t m,
-                    int stat, int normalize, double* dS, DevBuf& dsmall, int x_kind = PLAIDHIP_X_ANY) {
-  PH_TRY(dsmall.alloc(64 + (size_t)n * 8));
-  uint32_t* d_flags = dsmall.as<uint32_t>();
-  double* d_red = reinterpret_cast<double*>(dsmall.as<char>() + 16);
-  double* d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
-  PH_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
-  PH_TRY(launch_spmm_dense_f64(ctx, gs, dX, g, n, stat, 1.0, nullptr, 0.0, dS, m, d_flags, x_kind));
-  if (normalize) PH_TRY(normalize_on_device(ctx, dS, m, n, PLAIDHIP_IGNORE_ZERO_AUTO, d_flags, true, d_med, d_red));
-  return PLAIDHIP_OK;
-}
-
-}  // namespace
-
+// ---- replaid.ucell / aucell / scse / gsva and plaid.test: the one-shard case of the sharded engine ------------------------
+// (multi.cpp: scorer_worker, plaid_test_worker; run_scorer / run_plaid_test check the arguments first)
 extern "C" {
 
 int plaidhip_ucell(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                    int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                    const double* k_full, double rmax, double* S_out) try {
   PH_CTX(ctx);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  PH_REQUIRE(rmax > 0, "ucell: rmax must be positive");
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(X_or_x && S_out && k_full, "ucell: null X/S_out/k_full");
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  RankedInput ri;
-  PH_TRY(dense_average_ranks(ctx, Xp, Xi, X_or_x, g, n, ri));
-  PH_TRY(launch_map(ctx, ri.R, (int64_t)g * n, 0, rmax + 1.0, ri.d_gmax));            // R/plaid.R:278
-  DevBuf dS, dsmall, dadd;
-  PH_TRY(dS.alloc((size_t)m * n * 8));
-  // pmin(max(rX) - rX, rmax + 1) of average ranks: still half-integers in [0, nrow(X)] when rmax + 1 is one
-  const double cap2 = 2.0 * (rmax + 1.0);
-  const int xk = (cap2 == std::floor(cap2) && cap2 < 65536.0) ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
-  PH_TRY(plaid_on_device(ctx, gh.gs, ri.R, g, n, m, PLAIDHIP_STAT_MEAN, 1, dS.as<double>(), dsmall, xk));   // :279
-  std::vector<double> add(m);
-  for (int32_t j = 0; j < m; ++j) add[j] = 1.0 + (k_full[j] + 1.0) / (2.0 * rmax);   // :280
-  PH_TRY(dadd.alloc((size_t)m * 8));
-  PH_TRY(h2d(ctx, dadd.p, add.data(), (size_t)m * 8));
-  PH_TRY(launch_affine(ctx, dS.as<double>(), m, m, n, -1.0 / rmax, nullptr, 1.0, dadd.as<double>(), 0.0));
-  PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  return PLAIDHIP_OK;
+  // pmin(max(rX) - rX, rmax + 1) of the average ranks, plaid(), 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:278-280)
+  return run_scorer(&ctx, 1, 3, Xp, Xi, X_or_x, g, n, Gp, Gi, m, k_full, rmax, 0.0, -1, 0, 0.0, 0, S_out, nullptr);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_aucell(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                     int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                     double auc_max_rank, double* S_out) try {
   PH_CTX(ctx);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  PH_REQUIRE(auc_max_rank > 0, "aucell: aucMaxRank must be positive");
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(X_or_x && S_out, "aucell: null X/S_out");
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  RankedInput ri;
-  PH_TRY(dense_average_ranks(ctx, Xp, Xi, X_or_x, g, n, ri));
-  PH_TRY(launch_map(ctx, ri.R, (int64_t)g * n, 1, auc_max_rank, ri.d_gmax));         // R/plaid.R:306
-  DevBuf dS, dsmall;
-  PH_TRY(dS.alloc((size_t)m * n * 8));
-  PH_TRY(plaid_on_device(ctx, gh.gs, ri.R, g, n, m, PLAIDHIP_STAT_MEAN, 1, dS.as<double>(), dsmall));   // :307
-  PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  return PLAIDHIP_OK;
+  // pmax(aucMaxRank - (max(rX) - rX), 0) of the average ranks, plaid()   (R/plaid.R:306-307)
+  return run_scorer(&ctx, 1, 4, Xp, Xi, X_or_x, g, n, Gp, Gi, m, nullptr, 0.0, auc_max_rank, -1, 0, 0.0, 0, S_out, nullptr);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_scse(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                   int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                   int remove_log2, int score_mean, double* S_out, int* removed_log2) try {
   PH_CTX(ctx);
-  if (removed_log2 != nullptr) *removed_log2 = remove_log2 > 0 ? 1 : 0;
-  PH_TRY(check_host_common(Gp, g, n, m));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(X_or_x && S_out, "scse: null X/S_out");
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  const bool sparse = Xp != nullptr;
-  if (sparse) PH_TRY(check_host_csc(Xp, Xi, g, n));
-  const int64_t nvals = sparse ? (int64_t)Xp[n] : (int64_t)g * n;
-  DevBuf dX, dXp, dXi, dS, dsmall, dcol;
-  PH_TRY(dX.alloc((size_t)nvals * 8));
-  PH_TRY(h2d(ctx, dX.p, X_or_x, (size_t)nvals * 8));
-  if (sparse) {
-    PH_TRY(dXp.alloc((size_t)(n + 1) * 4));
-    PH_TRY(dXi.alloc((size_t)nvals * 4));
-    PH_TRY(h2d(ctx, dXp.p, Xp, (size_t)(n + 1) * 4));
-    PH_TRY(h2d(ctx, dXi.p, Xi, (size_t)nvals * 4));
-  }
-  PH_TRY(dcol.alloc(64 + (size_t)n * 8));
-  double* d_mm = dcol.as<double>();
-  double* d_colsum = reinterpret_cast<double*>(dcol.as<char>() + 64);
-  if (remove_log2 < 0) {                                        // R/plaid.R:160-161: decided and applied on the device
-    PH_TRY(launch_minmax(ctx, dX.as<double>(), nvals, d_mm));
-    const bool implicit_zeros = sparse && nvals < (int64_t)g * n;   // they take part in min / max
-    PH_TRY(launch_map(ctx, dX.as<double>(), nvals, sparse ? 5 : 4, implicit_zeros ? 1.0 : 0.0, d_mm));   // :163-171
-  } else if (remove_log2) {
-    PH_TRY(launch_map(ctx, dX.as<double>(), nvals, sparse ? 3 : 2, 0.0, nullptr));                       // :163-171
-  }
-  PH_TRY(launch_col_abs_sums(ctx, dX.as<double>(), g, g, sparse ? dXp.as<int32_t>() : nullptr, n, d_colsum));
-  PH_TRY(dS.alloc((size_t)m * n * 8));
-  const int stat = score_mean ? PLAIDHIP_STAT_MEAN : PLAIDHIP_STAT_SUM;
-  if (sparse) {
-    PH_TRY(launch_spmm_csc_f64(ctx, gh.gs, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), n, nvals, stat, 1.0,
-                               nullptr, 0.0, dS.as<double>(), m, nullptr));
-  } else {
-    PH_TRY(launch_spmm_dense_f64(ctx, gh.gs, dX.as<double>(), g, n, stat, 1.0, nullptr, 0.0, dS.as<double>(), m,
-                                 nullptr));
-  }
-  // mean: sX / (colMeans|X| + 1e-8) (:176-177); sum: sX / (colSums|X| + 1e-8) * 100 (:181-182)
-  PH_TRY(launch_affine(ctx, dS.as<double>(), m, m, n, score_mean ? 1.0 : 100.0, d_colsum,
-                       score_mean ? 1.0 / (double)g : 1.0, nullptr, 0.0));
-  PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
-  double mm[2] = {0.0, 0.0};
-  if (remove_log2 < 0 && removed_log2 != nullptr)
-    PH_HIP(hipMemcpyAsync(mm, d_mm, 16, hipMemcpyDeviceToHost, ctx->stream));
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  if (remove_log2 < 0 && removed_log2 != nullptr) {   // what map_kernel decided from the same two numbers (:160-161)
-    double mn = mm[0], mx = mm[1];
-    if (sparse && nvals < (int64_t)g * n) { mn = mn < 0.0 ? mn : 0.0; mx = mx > 0.0 ? mx : 0.0; }
-    *removed_log2 = (mn == 0.0 && mx < 20.0) ? 1 : 0;
-  }
-  return PLAIDHIP_OK;
+  // removeLog2 (< 0: decided from min / max of X, R/plaid.R:160-161), sX / (colMeans|X| + 1e-8) or its sum form (:176-182)
+  return run_scorer(&ctx, 1, 5, Xp, Xi, X_or_x, g, n, Gp, Gi, m, nullptr, 0.0, 0.0, remove_log2, score_mean, 0.0, 0, S_out,
+                    removed_log2);
 } catch (...) { return plaidhip::on_exception(); }
 
 // Row-wise two-group sums / sums of squared deviations on device pointers: the pieces of plaid.test that a sample-sharded
@@ -1253,7 +1095,7 @@ int plaidhip_dev_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, i
 } catch (...) { return plaidhip::on_exception(); }
 
 // The host half of plaid.test (R/plaid.R:410-474): p-values, effect sizes, meta-p and FDR from the reduced statistics.
-// Shared by plaidhip_plaid_test and by sample-sharded callers, which all-reduce the statistics first.
+// Shared by the sharded engine (multi.cpp: run_call) and by callers over RCCL, which all-reduce the statistics first.
 int plaidhip_plaid_test_finish(int32_t g, int32_t m, const int32_t* Gp, const double* T, double tot1, double tot2,
                                const double* SM, int64_t n0, int64_t n1, int tests, int metap_method, double* out) try {
   PH_REQUIRE(g >= 0 && m >= 0 && (m == 0 || (Gp && out)), "plaid_test_finish: null Gp / out");
@@ -1303,59 +1145,7 @@ int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
                         const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
                         int metap_method, double* out) try {
   PH_CTX(ctx);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  PH_REQUIRE(m == 0 || out, "plaid_test: null out");
-  PH_REQUIRE(n == 0 || (X && y), "plaid_test: null X / y");
-  PH_REQUIRE((tests & 7) != 0 && (tests & ~7) == 0, "plaid_test: tests is a bit mask of 1 (one), 2 (two), 4 (lm)");
-  PH_REQUIRE(metap_method == 0 || metap_method == 1, "Invalid method: %d", metap_method);      // R/plaid.R:533
-  int64_t n0 = 0, n1 = 0;
-  for (int32_t c = 0; c < n; ++c) {
-    PH_REQUIRE(y[c] == 0 || y[c] == 1, "elements of y must be 0 or 1");                        // R/plaid.R:394
-    if (y[c]) ++n1; else ++n0;
-  }
-  if (m == 0) return PLAIDHIP_OK;
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  const int64_t ldg = even_ld(g);
-  DevBuf dX, dy, dmean, dF, dT, dws, dS, dsm, dsmall;
-  PH_TRY(dX.alloc((size_t)ldg * n * 8));
-  PH_TRY(dy.alloc((size_t)n * 4));
-  PH_TRY(dmean.alloc((size_t)g * 2 * 8));
-  PH_TRY(dF.alloc((size_t)ldg * 2 * 8));
-  PH_TRY(dT.alloc((size_t)m * 2 * 8));
-  const int64_t wsd = std::max(row_group_ws_doubles(g, n), row_group_ws_doubles(m, n));
-  PH_TRY(dws.alloc((size_t)wsd * 8));
-  PH_TRY(h2d_cols(ctx, dX.p, ldg, X, g, n));
-  PH_TRY(h2d(ctx, dy.p, y, (size_t)n * 4));
-  // fc = rowMeans(X[, y == 1]) - rowMeans(X[, y == 0])   (R/plaid.R:407-409); Gt fc and Gt fc^2 (:478-479)
-  PH_TRY(launch_row_group_moments(ctx, dX.as<double>(), ldg, g, n, dy.as<int32_t>(), n0, n1, dmean.as<double>(), nullptr,
-                                  dws.as<double>()));
-  PH_HIP(hipMemsetAsync(dF.p, 0, (size_t)ldg * 2 * 8, ctx->stream));
-  PH_TRY(launch_fold_change(ctx, dmean.as<double>(), g, ldg, dF.as<double>()));
-  PH_TRY(launch_spmm_dense_f64(ctx, gh.gs, dF.as<double>(), ldg, 2, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(),
-                               m, nullptr));
-  std::vector<double> T((size_t)m * 2), F((size_t)ldg * 2), SM;
-  PH_HIP(hipMemcpyAsync(T.data(), dT.p, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PH_HIP(hipMemcpyAsync(F.data(), dF.p, (size_t)ldg * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (tests & 4) {
-    // scores stay on the device: given (uploaded) or plaid(X, G) computed here (R/plaid.R:424-427)
-    PH_TRY(dS.alloc((size_t)m * n * 8));
-    if (gsetX != nullptr) {
-      PH_TRY(h2d(ctx, dS.p, gsetX, (size_t)m * n * 8));
-    } else {
-      PH_TRY(plaid_on_device(ctx, gh.gs, dX.as<double>(), (int32_t)ldg, n, m, PLAIDHIP_STAT_MEAN, 1, dS.as<double>(), dsmall));
-    }
-    PH_TRY(dsm.alloc((size_t)m * 4 * 8));
-    PH_TRY(launch_row_group_moments(ctx, dS.as<double>(), m, m, n, dy.as<int32_t>(), n0, n1, dsm.as<double>(),
-                                    dsm.as<double>() + 2 * (size_t)m, dws.as<double>()));
-    SM.resize((size_t)m * 4);
-    PH_HIP(hipMemcpyAsync(SM.data(), dsm.p, (size_t)m * 4 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  double tot1 = 0.0, tot2 = 0.0;
-  for (int32_t i = 0; i < g; ++i) { tot1 += F[i]; tot2 += F[(size_t)ldg + i]; }
-  return plaidhip_plaid_test_finish(g, m, Gp, T.data(), tot1, tot2, (tests & 4) ? SM.data() : nullptr, n0, n1, tests,
-                                    metap_method, out);
+  return run_plaid_test(&ctx, 1, nullptr, nullptr, X, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.gsva.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, method 9)
@@ -1429,220 +1219,29 @@ int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
   return run_sing_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.gsva from the row-transformed zX (dX: g x n, leading dimension ldg) on: the scores in dS (m x n), normalised.
-// dR: a second g x n buffer; dsmall: 64 + 16 n bytes.  Shared by the dense and the CSC entry.
-static int gsva_scores(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const double* dX, double* dR, int64_t ldg, int32_t g,
-                       int32_t n, int32_t m, double tau, double* dS, DevBuf& dsmall) {
-  uint32_t* d_flags = dsmall.as<uint32_t>();
-  double* d_red = reinterpret_cast<double*>(dsmall.as<char>() + 16);
-  double* d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
-  double* d_colmax = d_med + n;
-  double* d_gmax = d_red + 2;
-  // rX = colranks(zX, signed = TRUE, "average"); rX / max|rX|; sign * |rX|^(1 + tau)   (:352-358)
-  //    = sign * rank^(1+tau) / max(rank^(1+tau)): the power is fused into the rank kernel, the division into the
-  //    SpMM epilogue (alpha_div), by linearity of the mean statistic
-  PH_TRY(launch_colranks_dense_f64(ctx, dX, ldg, g, n, PLAIDHIP_TIES_AVERAGE, 1, tau > 0.0 ? 1.0 + tau : 1.0, dR, ldg,
-                                   d_colmax));
-  PH_TRY(launch_max(ctx, d_colmax, n, d_gmax));
-  PH_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
-  PH_TRY(launch_spmm_dense_f64(ctx, gs, dR, ldg, n, PLAIDHIP_STAT_MEAN, 1.0, d_gmax, 0.0, dS, m, d_flags,
-                               tau > 0.0 ? PLAIDHIP_X_ANY : PLAIDHIP_X_EXACT_F32));   // signed average ranks
-  PH_TRY(normalize_on_device(ctx, dS, m, n, PLAIDHIP_IGNORE_ZERO_AUTO, d_flags, true, d_med, d_red));   // :360 plaid()
-  return PLAIDHIP_OK;
-}
-
+// zX = (X - rowMeans(X)) / (1e-8 + rowSds(X)) ("z", R/plaid.R:341-343) or t(apply(X, 1, function(x) ecdf(x)(x))) ("ecdf",
+// :346), the signed average ranks of its columns, plaid()
 int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi,
                   int32_t m, double tau, int rowtf, double* S_out) try {
   PH_CTX(ctx);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(X && S_out, "gsva: null X/S_out");
-  PH_REQUIRE(rowtf == 0 || rowtf == 1, "Error: unknown row transform %d", rowtf);                   // R/plaid.R:348
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  const int64_t ldg = even_ld(g);
-  DevBuf dX, dR, dS, dy, dmom, dws, dsmall;
-  PH_TRY(dX.alloc((size_t)ldg * n * 8));
-  PH_TRY(dR.alloc((size_t)ldg * n * 8));
-  PH_TRY(dS.alloc((size_t)m * n * 8));
-  PH_TRY(dy.alloc((size_t)n * 4));
-  PH_TRY(dmom.alloc((size_t)g * 4 * 8));
-  PH_TRY(dws.alloc((size_t)row_group_ws_doubles(g, n) * 8));
-  PH_TRY(dsmall.alloc(64 + (size_t)n * 16));
-  PH_TRY(h2d_cols(ctx, dX.p, ldg, X, g, n));
-  PH_HIP(hipMemsetAsync(dy.p, 0, (size_t)n * 4, ctx->stream));                         // one group: every sample
-  if (rowtf == 0) {
-    // zX = (X - rowMeans(X)) / (1e-8 + rowSds(X))                                     (R/plaid.R:341-343)
-    PH_TRY(launch_row_group_moments(ctx, dX.as<double>(), ldg, g, n, dy.as<int32_t>(), n, 0, dmom.as<double>(),
-                                    dmom.as<double>() + 2 * (size_t)g, dws.as<double>()));
-    PH_TRY(launch_row_ztransform(ctx, dX.as<double>(), ldg, g, n, dmom.as<double>(), dmom.as<double>() + 2 * (size_t)g));
-  } else {
-    // zX = t(apply(X, 1, function(x) ecdf(x)(x)))  (:346): ecdf(x)(x_i) = #{x <= x_i} / n = rank(x, "max") / n per
-    // gene.  Genes become columns (transpose), the column rank kernel ranks them, and the result goes back; the
-    // factor 1/n is dropped because only the per-sample ORDER of zX is used afterwards (:352).
-    PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), ldg, g, n, dR.as<double>(), n));              // dR: n x g
-    PH_TRY(launch_colranks_dense_f64(ctx, dR.as<double>(), n, n, g, PLAIDHIP_TIES_MAX, 0, 1.0, dX.as<double>(), n, nullptr));
-    PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), n, n, g, dR.as<double>(), ldg));              // dR: g x n
-    PH_HIP(hipMemcpyAsync(dX.p, dR.p, (size_t)ldg * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  PH_TRY(gsva_scores(ctx, gh.gs, dX.as<double>(), dR.as<double>(), ldg, g, n, m, tau, dS.as<double>(), dsmall));
-  PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  return PLAIDHIP_OK;
+  return run_scorer(&ctx, 1, 6, nullptr, nullptr, X, g, n, Gp, Gi, m, nullptr, 0.0, 0.0, -1, 0, tau, rowtf, S_out, nullptr);
 } catch (...) { return plaidhip::on_exception(); }
 
-// ---- dgCMatrix input for replaid.gsva and plaid.test: the row view on the device (kernels_csr.hip) -----------------------
-
-// the CSC slots on the device (nnz = Xp[n] already validated) and their row view: Rp (g + 1 and one more int for the
-// longest row), Rx, Rj / perm when asked for.  Returns the longest row in *max_row (one 4-byte read-back).
-struct CscOnDevice {
-  DevBuf dXp, dXi, dXx, dRp, dRj, dRx, dperm;
-};
-static int upload_csc_as_rows(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
-                              bool want_rj, bool want_perm, CscOnDevice& d, int32_t* max_row) {
-  const int64_t zx = Xp[n];
-  PH_TRY(d.dXp.alloc((size_t)(n + 1) * 4));
-  PH_TRY(d.dXi.alloc((size_t)zx * 4));
-  PH_TRY(d.dXx.alloc((size_t)zx * 8));
-  PH_TRY(d.dRp.alloc((size_t)(g + 2) * 4));
-  PH_TRY(d.dRx.alloc((size_t)zx * 8));
-  if (want_rj) PH_TRY(d.dRj.alloc((size_t)zx * 4));
-  if (want_perm) PH_TRY(d.dperm.alloc((size_t)zx * 4));
-  PH_TRY(h2d(ctx, d.dXp.p, Xp, (size_t)(n + 1) * 4));
-  PH_TRY(h2d(ctx, d.dXi.p, Xi, (size_t)zx * 4));
-  PH_TRY(h2d(ctx, d.dXx.p, Xx, (size_t)zx * 8));
-  int32_t* d_maxlen = d.dRp.as<int32_t>() + g + 1;
-  PH_TRY(launch_csc_to_csr(ctx, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), g, n, d.dRp.as<int32_t>(),
-                           want_rj ? d.dRj.as<int32_t>() : nullptr, d.dRx.as<double>(),
-                           want_perm ? d.dperm.as<int32_t>() : nullptr, d_maxlen));
-  PH_HIP(hipMemcpyAsync(max_row, d_maxlen, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PH_HIP(hipStreamSynchronize(ctx->stream));   // (the rank kernels take the longest row from the host)
-  return PLAIDHIP_OK;
-}
-
+// dgCMatrix input for replaid.gsva and plaid.test: the slots go to the device as they are, where their row view
+// (kernels_csr.hip) gives the rows' moments, ecdf counts and group sums; no dense X on the host or the link
 int plaidhip_gsva_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
                       const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out) try {
   PH_CTX(ctx);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(Xp && S_out, "gsva_csc: null Xp/S_out");
-  PH_REQUIRE(rowtf == 0 || rowtf == 1, "Error: unknown row transform %d", rowtf);                   // R/plaid.R:348
-  PH_TRY(check_host_csc(Xp, Xi, g, n));
-  PH_REQUIRE(Xp[n] == 0 || (Xi && Xx), "gsva_csc: null Xi/Xx");
-  // (the ranks of the rows' stored values use a g x n buffer as scratch: a column repeating a row index could pass it)
-  PH_REQUIRE((int64_t)Xp[n] <= (int64_t)g * n, "gsva_csc: %d stored values in a %d x %d matrix (repeated row indices?)",
-             Xp[n], g, n);
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  const int64_t ldg = even_ld(g);
-  CscOnDevice d;
-  int32_t max_row = 0;
-  PH_TRY(upload_csc_as_rows(ctx, Xp, Xi, Xx, g, n, /*want_rj=*/false, /*want_perm=*/rowtf == 1, d, &max_row));
-  DevBuf dX, dR, dS, dmom, ddef, dsmall;
-  PH_TRY(dX.alloc((size_t)ldg * n * 8));
-  PH_TRY(dR.alloc((size_t)ldg * n * 8));
-  PH_TRY(dS.alloc((size_t)m * n * 8));
-  PH_TRY(dmom.alloc((size_t)g * 4 * 8));
-  PH_TRY(ddef.alloc((size_t)g * 8));
-  PH_TRY(dsmall.alloc(64 + (size_t)n * 16));
-  double* d_mean = dmom.as<double>();
-  double* d_ssd = d_mean + 2 * (size_t)g;
-  if (rowtf == 0) {
-    // zX = (X - rowMeans(X)) / (1e-8 + rowSds(X)) (R/plaid.R:341-343): the moments of each row from its stored values
-    // and its implicit zeros, then every entry of the dense zX from them (a zero's value is the row's default)
-    PH_TRY(launch_csr_row_group_moments(ctx, d.dRp.as<int32_t>(), nullptr, d.dRx.as<double>(), g, max_row, nullptr, n, 0,
-                                        d_mean, d_ssd));
-    PH_TRY(launch_row_z_defaults(ctx, d_mean, d_ssd, g, n, ddef.as<double>()));
-    PH_TRY(launch_csc_expand(ctx, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), g, n, ldg, ddef.as<double>(),
-                             d_mean, d_ssd, dX.as<double>()));
-  } else {
-    // zX = t(apply(X, 1, function(x) ecdf(x)(x))) (:346) without the factor 1/n, as the dense entry: #{x <= x_i} per
-    // gene from the max-ranks of its stored values (rank scratch: dR) and its implicit zeros; the stored entries' values
-    // go back to CSC order (into the CSC value slot, no longer needed) and are expanded with the rows' zero values
-    PH_TRY(launch_csr_row_ecdf(ctx, d.dRp.as<int32_t>(), d.dRx.as<double>(), g, n, max_row, d.dperm.as<int32_t>(),
-                               dR.as<double>(), d.dXx.as<double>(), ddef.as<double>()));
-    PH_TRY(launch_csc_expand(ctx, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), g, n, ldg, ddef.as<double>(),
-                             nullptr, nullptr, dX.as<double>()));
-  }
-  PH_TRY(gsva_scores(ctx, gh.gs, dX.as<double>(), dR.as<double>(), ldg, g, n, m, tau, dS.as<double>(), dsmall));
-  PH_TRY(copy_home(ctx, S_out, dS.p, (size_t)m * n * 8));
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  return PLAIDHIP_OK;
+  PH_REQUIRE(Xp != nullptr, "gsva_csc: null Xp");
+  return run_scorer(&ctx, 1, 6, Xp, Xi, Xx, g, n, Gp, Gi, m, nullptr, 0.0, 0.0, -1, 0, tau, rowtf, S_out, nullptr);
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_plaid_test_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
                             const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX,
                             int tests, int metap_method, double* out) try {
   PH_CTX(ctx);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  PH_REQUIRE(m == 0 || out, "plaid_test: null out");
-  PH_REQUIRE(Xp != nullptr && (n == 0 || y), "plaid_test: null X / y");
-  PH_REQUIRE((tests & 7) != 0 && (tests & ~7) == 0, "plaid_test: tests is a bit mask of 1 (one), 2 (two), 4 (lm)");
-  PH_REQUIRE(metap_method == 0 || metap_method == 1, "Invalid method: %d", metap_method);      // R/plaid.R:533
-  int64_t n0 = 0, n1 = 0;
-  for (int32_t c = 0; c < n; ++c) {
-    PH_REQUIRE(y[c] == 0 || y[c] == 1, "elements of y must be 0 or 1");                        // R/plaid.R:394
-    if (y[c]) ++n1; else ++n0;
-  }
-  PH_TRY(check_host_csc(Xp, Xi, g, n));
-  const int64_t zx = Xp[n];
-  PH_REQUIRE(zx == 0 || (Xi && Xx), "plaid_test: null Xi/Xx");
-  if (m == 0) return PLAIDHIP_OK;
-  GenesetHolder gh;
-  PH_TRY(acquire_geneset(ctx, g, m, Gp, Gi, &gh.gs));
-  const int64_t ldg = even_ld(g);
-  CscOnDevice d;
-  DevBuf dy, dmean, dF, dT, dws, dS, dsm, dsmall;
-  PH_TRY(dy.alloc((size_t)n * 4));
-  PH_TRY(h2d(ctx, dy.p, y, (size_t)n * 4));
-  int32_t max_row = 0;
-  PH_TRY(upload_csc_as_rows(ctx, Xp, Xi, Xx, g, n, /*want_rj=*/true, /*want_perm=*/false, d, &max_row));
-  PH_TRY(dmean.alloc((size_t)g * 2 * 8));
-  PH_TRY(dF.alloc((size_t)ldg * 2 * 8));
-  PH_TRY(dT.alloc((size_t)m * 2 * 8));
-  // fc = rowMeans(X[, y == 1]) - rowMeans(X[, y == 0])   (R/plaid.R:407-409) over the rows' stored values; Gt fc and
-  // Gt fc^2 (:478-479) as in the dense entry
-  PH_TRY(launch_csr_row_group_moments(ctx, d.dRp.as<int32_t>(), d.dRj.as<int32_t>(), d.dRx.as<double>(), g, max_row,
-                                      dy.as<int32_t>(), n0, n1, dmean.as<double>(), nullptr));
-  PH_HIP(hipMemsetAsync(dF.p, 0, (size_t)ldg * 2 * 8, ctx->stream));
-  PH_TRY(launch_fold_change(ctx, dmean.as<double>(), g, ldg, dF.as<double>()));
-  PH_TRY(launch_spmm_dense_f64(ctx, gh.gs, dF.as<double>(), ldg, 2, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(),
-                               m, nullptr));
-  std::vector<double> T((size_t)m * 2), F((size_t)ldg * 2), SM;
-  PH_HIP(hipMemcpyAsync(T.data(), dT.p, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PH_HIP(hipMemcpyAsync(F.data(), dF.p, (size_t)ldg * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (tests & 4) {
-    // scores stay on the device: given (uploaded) or plaid(X, G) from the CSC slots with the kernels of plaidhip_plaid_csc
-    // -- the sparse crossprod that also classifies its scores, then normalize_medians (R/plaid.R:424-427, 554-575)
-    PH_TRY(dS.alloc((size_t)m * n * 8));
-    PH_TRY(dws.alloc((size_t)row_group_ws_doubles(m, n) * 8));
-    if (gsetX != nullptr) {
-      PH_TRY(h2d(ctx, dS.p, gsetX, (size_t)m * n * 8));
-    } else if (n > 0) {
-      PH_TRY(dsmall.alloc(64 + (size_t)n * 8));
-      uint32_t* d_flags = dsmall.as<uint32_t>();
-      double* d_red = reinterpret_cast<double*>(dsmall.as<char>() + 16);
-      double* d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
-      PH_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
-      const int64_t nnz_choice = (int64_t)((double)zx / (double)n * (double)n);   // (run_sharded's choice on one shard)
-      PH_TRY(launch_spmm_csc_fused_f64(ctx, gh.gs, d.dXp.as<int32_t>(), d.dXi.as<int32_t>(), d.dXx.as<double>(), n, zx,
-                                       PLAIDHIP_STAT_MEAN, 1.0, nullptr, 0.0, dS.as<double>(), m, d_flags, /*bounded=*/false,
-                                       nullptr, 0.0, nnz_choice));
-      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, n, PLAIDHIP_IGNORE_ZERO_AUTO, d_flags, d_med));
-      PH_TRY(launch_sum(ctx, d_med, n, d_red));
-      PH_TRY(launch_shift_columns(ctx, dS.as<double>(), m, m, n, d_med, 0.0, d_red));
-    }
-    PH_TRY(dsm.alloc((size_t)m * 4 * 8));
-    PH_TRY(launch_row_group_moments(ctx, dS.as<double>(), m, m, n, dy.as<int32_t>(), n0, n1, dsm.as<double>(),
-                                    dsm.as<double>() + 2 * (size_t)m, dws.as<double>()));
-    SM.resize((size_t)m * 4);
-    PH_HIP(hipMemcpyAsync(SM.data(), dsm.p, (size_t)m * 4 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  PH_HIP(hipStreamSynchronize(ctx->stream));
-  double tot1 = 0.0, tot2 = 0.0;
-  for (int32_t i = 0; i < g; ++i) { tot1 += F[i]; tot2 += F[(size_t)ldg + i]; }
-  return plaidhip_plaid_test_finish(g, m, Gp, T.data(), tot1, tot2, (tests & 4) ? SM.data() : nullptr, n0, n1, tests,
-                                    metap_method, out);
+  PH_REQUIRE(Xp != nullptr, "plaid_test: null X / y");
+  return run_plaid_test(&ctx, 1, Xp, Xi, Xx, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -283,6 +283,16 @@ const char* last_error_cstr();
 int run_sharded(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                 int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int stat, int normalize, double alpha,
                 double* S_out);
+// the same engine for replaid.ucell / aucell / scse / gsva (method 3 ucell: k_full, rmax; 4 aucell: auc_max_rank; 5 scse:
+// remove_log2, score_mean, removed_log2; 6 gsva: tau, rowtf -- "ecdf" on one context only; what a method does not take is
+// ignored) and for plaid.test, on ndev contexts (one: plaidhip_ucell ... plaidhip_plaid_test_csc); their argument checks
+// come first and touch no device
+int run_scorer(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full, double rmax,
+               double auc_max_rank, int remove_log2, int score_mean, double tau, int rowtf, double* S_out, int* removed_log2);
+int run_plaid_test(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                   int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                   int metap_method, double* out);
 // A result's way home into the caller's pageable buffer (multi.cpp).  R hands over FRESH memory (allocMatrix -> malloc ->
 // mmap): every page faults on its first write, inside the device-to-host copy -- 4.9 GB of scores took 309 ms instead of
 // 92 (tools/ubench/d2h_fresh.cpp).  prepare() asks for transparent huge pages on the range (madvise; a hint, ignored where
@@ -324,8 +334,6 @@ int launch_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t
 int launch_row_group_moments(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n,
                              const int32_t* d_y, int64_t n0, int64_t n1, double* d_mean, double* d_ssd,
                              double* ws);
-int launch_row_ztransform(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t n, const double* d_mean,
-                          const double* d_ssd);
 // sample-sharded replaid.gsva (multi.cpp): the block partials of launch_row_group_moments over one shard, their group-0
 // reduction continued from a seed (shards chained in column order reproduce the one-shard sums bit for bit), and the z
 // transform of a shard whose moments were taken over n_total samples
@@ -357,7 +365,7 @@ int launch_csr_row_group_moments(plaidhip_ctx* ctx, const int32_t* Rp, const int
 // Rrank: Rp[rows] doubles of scratch
 int launch_csr_row_ecdf(plaidhip_ctx* ctx, const int32_t* Rp, const double* Rx, int32_t rows, int32_t n,
                         int32_t max_row_nnz, const int32_t* perm, double* Rrank, double* out, double* dflt);
-// dflt[r] = the z transform (launch_row_ztransform) of a zero in row r
+// dflt[r] = the z transform (launch_row_ztransform_shard) of a zero in row r
 int launch_row_z_defaults(plaidhip_ctx* ctx, const double* d_mean, const double* d_ssd, int32_t rows, int32_t n,
                           double* dflt);
 // dense g x n (leading dimension ld) from row defaults and the stored entries: vals as they are, or z-transformed

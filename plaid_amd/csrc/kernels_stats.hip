@@ -113,28 +113,12 @@ __device__ __forceinline__ void row_ztransform_body(double* __restrict__ A, int6
   }
 }
 
-// mom: [2][rows] group-0 means, ssd: [2][rows] group-0 sums of squared deviations (all samples in group 0)
-__global__ void __launch_bounds__(256)
-row_ztransform_kernel(double* __restrict__ A, int64_t ld, int32_t rows, int32_t n,
-                      const double* __restrict__ mean, const double* __restrict__ ssd) {
-  row_ztransform_body(A, ld, rows, n, n, mean, ssd);
-}
-
-// the same on a column shard of X: the sd divides by n_total - 1
+// mean, ssd: the group-0 means and sums of squared deviations of the rows (all samples in group 0), taken over the n_total
+// columns of X, of which A holds a shard: the sd divides by n_total - 1
 __global__ void __launch_bounds__(256)
 row_ztransform_shard_kernel(double* __restrict__ A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,
                             const double* __restrict__ mean, const double* __restrict__ ssd) {
   row_ztransform_body(A, ld, rows, ncols, n_total, mean, ssd);
-}
-
-int launch_row_ztransform(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t n, const double* d_mean,
-                          const double* d_ssd) {
-  if (rows == 0 || n == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
-  hipLaunchKernelGGL(row_ztransform_kernel, dim3((rows + 255) / 256, nblk), dim3(256), 0, ctx->stream, A, ld, rows, n,
-                     d_mean, d_ssd);
-  PH_HIP(hipGetLastError());
-  return PLAIDHIP_OK;
 }
 
 int launch_row_ztransform_shard(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,

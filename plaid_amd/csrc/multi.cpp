@@ -6,10 +6,13 @@
 // S), every device moves its shard over its own PCIe link, and the three scalars that couple the samples -- max(rX)
 // (R/plaid.R:251), min(x) == 0 (R/plaid.R:556-557) and mean(medx) (R/plaid.R:572) -- are combined on the host between
 // the phases.  No RCCL: nothing but those scalars crosses between devices.  (One process per GPU over RCCL is the
-// other form, plaid_amd/sharded.py.)  The single-device entry points run the same code with one shard.
+// other form, plaid_amd/sharded.py.)  The single-device entry points of api.cpp run the same code with one shard:
+// there is one implementation per scorer, and a context entry is its one-shard case.
 // replaid.ucell / aucell / scse / gsva (scorer_worker) add their own couplings: the min / max behind removeLog2 = NULL and
 // the per-gene mean and sd of gsva's z transform (g values each, chained from shard to shard for dense X).  plaid.test
-// (plaid_test_worker) reduces nothing but row sums over the samples: its scores stay on the devices.
+// (plaid_test_worker) reduces nothing but row sums over the samples: its scores stay on the devices.  The workers are
+// plain functions over one scaffold (Shard: the columns, `step`, the common exit) and a few shared blocks (the CSC
+// upload, the medians' coupling, the chained row reductions).
 //
 // Uploads are pipelined: R hands over pageable memory, which the HIP runtime copies at ~21 GB/s; staged through
 // pinned buffers by a few feeder threads (memcpy at ~75 GB/s with four threads, tools/ubench/pcie.cpp) the DMA
@@ -311,15 +314,15 @@ struct Call {
   int stat, normalize;
   double alpha;
   double* S_out;
-  // methods 3 - 6: the parameters of the context entries
+  // methods 3 - 6: the parameters of plaidhip_ucell / aucell / scse / gsva
   const double* k_full = nullptr;   // ucell: set sizes
   double rmax = 0.0;                // ucell
   double auc_max_rank = 0.0;        // aucell
   int remove_log2 = -1;             // scse: < 0 decided from min / max of X
   int score_mean = 0;               // scse
   double tau = 0.0;                 // gsva
-  int rowtf = 0;                    // gsva: 0 (z) only, "ecdf" is not sharded; gsva.exact: 0 z, 1 ecdf (one shard), 2 none,
-                                    // 3 gauss (every shard takes all of X)
+  int rowtf = 0;                    // gsva: 0 z, 1 ecdf (one shard); gsva.exact: 0 z, 1 ecdf (one shard), 2 none, 3 gauss
+                                    // (every shard takes all of X)
   int max_diff = 1;                 // gsva.exact
   int* removed_log2 = nullptr;      // scse output (may be null)
   int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
@@ -392,14 +395,24 @@ double mean_like_device_sum(const double* v, int64_t count) {
   return s[0] / cnt[0];
 }
 
-int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+// What every worker below runs on: shard k of ndev, its columns, its status.  Every `step` is skipped once this shard or
+// any other has failed; the rendezvous points between the steps are always reached.
+struct Shard {
+  plaidhip_ctx* ctx;
+  const Call& c;
+  int ndev, k;
+  Shared& sh;
+  int32_t lo = 0, nloc = 0;
+  int64_t zx = 0;             // a dgCMatrix: the stored values of the shard's columns
   int rc = PLAIDHIP_OK;
-#ifdef PLAIDHIP_DIAG
-  const auto t_trace0 = std::chrono::steady_clock::now();
-#endif
-  // every `step` is skipped once this shard or any other has failed; the rendezvous points are always reached
-  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
-  auto step = [&](const std::function<int()>& fn) {
+  int saved_precision = -1;   // >= 0: the context's precision, given back by finish()
+
+  Shard(plaidhip_ctx* ctx_, const Call& c_, int ndev_, int k_, Shared& sh_) : ctx(ctx_), c(c_), ndev(ndev_), k(k_), sh(sh_) {
+    shard_columns(c, ndev, k, &lo, &nloc);
+    if (c.Xp != nullptr) zx = (int64_t)c.Xp[lo + nloc] - c.Xp[lo];
+  }
+  bool live() const { return rc == PLAIDHIP_OK && sh.abort.load() == 0; }
+  template <typename Fn> void step(Fn&& fn) {
     if (!live()) return;
     try {
       rc = fn();
@@ -407,10 +420,123 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
       rc = on_exception();
     }
     if (rc != PLAIDHIP_OK) sh.abort.store(1);
-  };
-  int64_t lo64 = 0, hi64 = 0;
-  plaidhip_shard_bounds(c.n, ndev, k, &lo64, &hi64);
-  const int32_t lo = (int32_t)lo64, nloc = (int32_t)(hi64 - lo64);
+  }
+  // the exact scorers are fp64 and integers in every mode: their crossprods stay on the fp64 kernels
+  void force_f64() {
+    saved_precision = ctx->precision;
+    ctx->precision = PLAIDHIP_PRECISION_F64;
+  }
+  int finish() {
+    if (saved_precision >= 0) ctx->precision = saved_precision;
+    if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
+      hipStreamSynchronize(ctx->stream);
+      return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
+    }
+    if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+};
+
+// The CSC slots of the shard's columns go to the device: @p rebased to the shard (ploc, which the caller keeps until its
+// last synchronisation), @i and the values through the pinned ring.  *max_nnz: the shard's longest column.  dXx: a CtxBuf
+// or a DevBuf.
+template <typename Buf>
+int upload_csc_shard(const Shard& s, std::vector<int32_t>& ploc, CtxBuf& dXp, CtxBuf& dXi, Buf& dXx, int32_t* max_nnz) {
+  const Call& c = s.c;
+  const int64_t z0 = c.Xp[s.lo];
+  ploc.resize((size_t)s.nloc + 1);
+  for (int32_t j = 0; j <= s.nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[s.lo + j] - z0);
+  *max_nnz = host_max_col_nnz(ploc.data(), s.nloc);
+  const size_t zb = (size_t)std::max<int64_t>(s.zx, 1);
+  PH_TRY(dXp.alloc((size_t)(s.nloc + 1) * 4));
+  PH_TRY(dXi.alloc(zb * 4));
+  PH_TRY(dXx.alloc(zb * 8));
+  PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(s.nloc + 1) * 4, hipMemcpyHostToDevice, s.ctx->stream));
+  PH_TRY(upload_pipelined(s.ctx, dXi.template as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, s.zx * 4, nullptr));
+  return upload_pipelined(s.ctx, dXx.template as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, s.zx * 8, nullptr);
+}
+
+// the pattern of a set collection (aligned to X's rows) for the kernels that walk it
+int upload_pattern(plaidhip_ctx* ctx, const int32_t* Gp, const int32_t* Gi, int32_t m, DevBuf& dGp, DevBuf& dGi) {
+  const size_t z = (size_t)Gp[m];
+  PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
+  PH_TRY(dGi.alloc(std::max<size_t>(z, 1) * 4));
+  PH_HIP(hipMemcpyAsync(dGp.p, Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (z > 0) PH_HIP(hipMemcpyAsync(dGi.p, Gi, z * 4, hipMemcpyHostToDevice, ctx->stream));
+  return PLAIDHIP_OK;
+}
+
+// this shard's {min, max} (and "a NaN among them") into the range over all shards, in the comparisons of
+// minmax_final_kernel; a shard without columns brings {inf, -inf, false}, which change nothing
+void merge_range(Shard& s, double mn, double mx, bool any_nan = false) {
+  std::lock_guard<std::mutex> lk(s.sh.mu);
+  if (s.rc != PLAIDHIP_OK) return;
+  s.sh.xmin = mn < s.sh.xmin ? mn : s.sh.xmin;
+  s.sh.xmax = mx > s.sh.xmax ? mx : s.sh.xmax;
+  s.sh.es_nan = s.sh.es_nan || any_nan;
+}
+
+// normalize_medians (R/plaid.R:554-575) up to mean(medx), for the m x nloc scores dS whose crossprod classified them
+// (d_flags): min(x) == 0 over ALL shards decides ignore.zero (:556-557), every shard takes its columns' medians (left in
+// d_med), and mean(medx, na.rm = TRUE) (:572) is taken over ALL columns in the summation order of the device's sum kernel
+// (launch_sum) -- it does not depend on how the columns were sharded, so every sharding, one device included, normalises
+// with the same bits.  Two rendezvous.  The caller shifts the columns, or keeps the shift for later.
+double medians_and_their_mean(Shard& s, double* dS, const uint32_t* d_flags, double* d_med) {
+  const int32_t m = s.c.m, nloc = s.nloc;
+  plaidhip_ctx* ctx = s.ctx;
+  uint32_t fl[4] = {0, 0, 0, 0};
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_HIP(hipMemcpyAsync(fl, d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+  {
+    std::lock_guard<std::mutex> lk(s.sh.mu);
+    for (int q = 0; q < 4; ++q) s.sh.flags[q] |= fl[q];
+  }
+  s.sh.rv.arrive_and_wait();
+  const int ignore_zero = (s.sh.flags[1] != 0 && s.sh.flags[0] == 0) ? 1 : 0;
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(launch_col_medians_resume(ctx, dS, m, m, nloc, ignore_zero, nullptr, d_med));
+    PH_HIP(hipMemcpyAsync(s.sh.med_all.data() + s.lo, d_med, (size_t)nloc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+  s.sh.rv.arrive_and_wait();
+  return s.live() ? mean_like_device_sum(s.sh.med_all.data(), s.c.n) : 0.0;
+}
+
+// Chained, ordered reduction over the samples of the [nblk][groups][rows] block partials in ws: in round r only shard r
+// works, continuing shard r - 1's running sums (`run`, [groups][rows], on the host) block by block -- the additions of the
+// one-device call in their order.  ndev rendezvous.  d_seed, d_run: groups x rows doubles each.
+void chain_block_sums(Shard& s, std::vector<double>& run, const double* ws, int32_t rows, int groups, double* d_seed,
+                      double* d_run) {
+  plaidhip_ctx* ctx = s.ctx;
+  const size_t bytes = (size_t)rows * groups * 8;
+  for (int r = 0; r < s.ndev; ++r) {
+    if (r == s.k)
+      s.step([&]() -> int {
+        if (s.nloc == 0) return PLAIDHIP_OK;
+        PH_HIP(hipMemcpyAsync(d_seed, run.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        for (int q = 0; q < groups; ++q)
+          PH_TRY(launch_reduce_blocks_seeded(ctx, ws + (size_t)q * rows, rows, s.nloc, d_seed + (size_t)q * rows,
+                                             d_run + (size_t)q * rows));
+        PH_HIP(hipMemcpyAsync(run.data(), d_run, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        return PLAIDHIP_OK;
+      });
+    s.sh.rv.arrive_and_wait();
+  }
+}
+
+int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+#ifdef PLAIDHIP_DIAG
+  const auto t_trace0 = std::chrono::steady_clock::now();
+#endif
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m;
   const bool sparse = c.Xp != nullptr;
   const bool ranks = c.method != 0;
@@ -422,11 +548,11 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   const int64_t ldg = even_ld(g);
   uint32_t* d_flags = nullptr;
   double *d_red = nullptr, *d_med = nullptr, *d_colmax = nullptr, *d_gmax = nullptr;
-  int64_t zx = 0, z0 = 0;
+  const int64_t zx = s.zx;
   int32_t max_nnz = 0;
   std::vector<int32_t> ploc;
 
-  step([&]() -> int {
+  s.step([&]() -> int {
     PH_HIP(hipSetDevice(ctx->device));
     PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
     PH_TRACE("geneset acquired");
@@ -462,25 +588,13 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
       // threads cost the upload a quarter of its rate)
       home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
     } else {
-      z0 = c.Xp[lo];
-      zx = (int64_t)c.Xp[lo + nloc] - z0;
-      ploc.resize((size_t)nloc + 1);
-      for (int32_t j = 0; j <= nloc; ++j) {
-        ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
-        if (j > 0) max_nnz = std::max(max_nnz, ploc[(size_t)j] - ploc[(size_t)j - 1]);
-      }
-      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
-      PH_TRY(dXi.alloc((size_t)zx * 4));
-      PH_TRY(dX.alloc((size_t)zx * 8));
+      PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
       // replaid.sing ranks the zeros too (colranks' sparse branch without keep.zero, R/plaid.R:602-609: a dense rank
       // matrix): built panel by panel from the ranks of the stored values, each panel multiplied at once
       int64_t panel = ((int64_t)2 << 30) / (ldg * 8);
       panel = std::min<int64_t>(std::max<int64_t>(panel & ~(int64_t)1, 2), nloc);
       if (c.method == 1) PH_TRY(dR.alloc((size_t)(panel * ldg + zx) * 8));   // a panel of dense ranks | ranks of the stored values
       else if (ranks) PH_TRY(dR.alloc((size_t)zx * 8));
-      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
-      PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
       home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
       if (c.method == 1) {
         double* dRd = dR.as<double>();
@@ -510,7 +624,7 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   double gmax = 0.0;
   if (c.method == 2) {
     double mine = sparse ? 0.0 : -INFINITY;      // a dgCMatrix has implicit zeros
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       PH_TRY(launch_max(ctx, d_colmax, nloc, d_gmax));
       PH_HIP(hipMemcpyAsync(&mine, d_gmax, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -519,7 +633,7 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
     });
     {
       std::lock_guard<std::mutex> lk(sh.mu);
-      if (nloc > 0 && rc == PLAIDHIP_OK) {
+      if (nloc > 0 && s.rc == PLAIDHIP_OK) {
         sh.gmax = sh.gmax_set ? std::max(sh.gmax, mine) : mine;
         sh.gmax_set = true;
       }
@@ -529,7 +643,7 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   }
 
   // ---- crossprod of the rank-based callers (plaid() did it per panel) ------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
     if (c.method == 0 && !sparse) return PLAIDHIP_OK;
@@ -564,33 +678,8 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   // ---- normalize_medians (R/plaid.R:554-575): two more scalars --------------------------------------------------------
   const bool norm = c.method == 2 || (c.method == 0 && c.normalize);
   if (norm) {
-    uint32_t fl[4] = {0, 0, 0, 0};
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
-      PH_HIP(hipMemcpyAsync(fl, d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
-      PH_HIP(hipStreamSynchronize(ctx->stream));
-      PH_TRACE("crossprod done (flags)");
-      return PLAIDHIP_OK;
-    });
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      for (int q = 0; q < 4; ++q) sh.flags[q] |= fl[q];
-    }
-    sh.rv.arrive_and_wait();
-    const int ignore_zero = (sh.flags[1] != 0 && sh.flags[0] == 0) ? 1 : 0;   // min(x) == 0, R/plaid.R:556-557
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
-      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, nloc, ignore_zero, nullptr, d_med));
-      PH_HIP(hipMemcpyAsync(sh.med_all.data() + lo, d_med, (size_t)nloc * 8, hipMemcpyDeviceToHost, ctx->stream));
-      PH_HIP(hipStreamSynchronize(ctx->stream));
-      return PLAIDHIP_OK;
-    });
-    sh.rv.arrive_and_wait();
-    // mean(medx, na.rm = TRUE), R/plaid.R:572, over ALL columns in the summation order of the device's sum kernel
-    // (launch_sum): the value does not depend on how the columns were sharded, so every sharding -- one device
-    // included -- normalises with the same bits
-    const double mean_med = live() ? mean_like_device_sum(sh.med_all.data(), c.n) : 0.0;
-    step([&]() -> int {
+    const double mean_med = medians_and_their_mean(s, dS.as<double>(), d_flags, d_med);
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       return launch_shift_columns(ctx, dS.as<double>(), m, m, nloc, d_med, mean_med, nullptr);
     });
@@ -598,18 +687,13 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 
   // ---- the score shard goes home (pageable destination: the runtime's own staging runs at ~53 GB/s) ---------------------
   PH_TRACE("normalise enqueued");
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (nloc > 0) PH_TRY(home.copy(ctx, dS.p));
     PH_HIP(hipStreamSynchronize(ctx->stream));
     PH_TRACE("scores home");
     return PLAIDHIP_OK;
   });
-  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
-    hipStreamSynchronize(ctx->stream);
-    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
-  }
-  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return s.finish();
 }
 
 
@@ -619,26 +703,14 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 // single = FALSE: the same operands, then the walk kernel of kernels_ks.hip in place of the crossprods and the epilogue
 // (P's columns, which it has no use for, take the weights in walk order).
 int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
-  int rc = PLAIDHIP_OK;
-  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
-  auto step = [&](const std::function<int()>& fn) {
-    if (!live()) return;
-    try {
-      rc = fn();
-    } catch (...) {
-      rc = on_exception();
-    }
-    if (rc != PLAIDHIP_OK) sh.abort.store(1);
-  };
-  int32_t lo = 0, nloc = 0;
-  shard_columns(c, ndev, k, &lo, &nloc);
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m;
   const bool sparse = c.Xp != nullptr;
   const bool need_w = c.alpha != 0.0;
   const int64_t ld = g;
   // the scores are fp64 in every mode: the crossprods stay on the fp64 kernels whatever precision the context was given
-  const int saved_precision = ctx->precision;
-  ctx->precision = PLAIDHIP_PRECISION_F64;
+  s.force_f64();
   plaidhip_geneset* gs = nullptr;
   // the large buffers stay with the context between calls (ctx_buffer), as the other scorers' do: operands [Q | W | P |
   // rank scratch] in one, scores [S | A | B] in another
@@ -653,7 +725,7 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
   for (int32_t j = 0; j < m; ++j) kset[(size_t)j] = c.Gp[j + 1] - c.Gp[j];   // members after the alignment
 
   // ---- upload, operands ---------------------------------------------------------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     PH_HIP(hipSetDevice(ctx->device));
     PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
     const size_t nl = (size_t)std::max(nloc, 1);
@@ -663,13 +735,7 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
     const size_t nscores = (size_t)m * nl;
     PH_TRY(dS.alloc(nscores * 8 * (need_w && !ks ? 3 : 1)));
     if (nloc == 0) return PLAIDHIP_OK;
-    if (ks) {
-      const size_t z = (size_t)c.Gp[m];
-      PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
-      PH_TRY(dGi.alloc(std::max<size_t>(z, 1) * 4));
-      PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      if (z > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, z * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (ks) PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
     if (need_w && !ks) {
       A = dS.as<double>() + nscores;
       B = A + nscores;
@@ -677,8 +743,7 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
     PH_TRY(dk.alloc((size_t)m * 4));
     PH_HIP(hipMemcpyAsync(dk.p, kset.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
     PH_TRY(dpart.alloc((size_t)ssgsea_exact_part_blocks(ctx, (int64_t)m * nloc) * 24));
-    const int64_t z0 = sparse ? c.Xp[lo] : 0;
-    const int64_t zx = sparse ? (int64_t)c.Xp[lo + nloc] - z0 : 0;
+    const int64_t zx = s.zx;
     const size_t col = (size_t)ld * nloc;
     const size_t nscratch = sparse ? 3 * (size_t)std::max<int64_t>(zx, 1) : 2 * col;
     PH_TRY(dops.alloc((col * (need_w ? 3 : 1) + nscratch) * 8));
@@ -695,23 +760,17 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
       PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), ld, nullptr, nullptr, g, nloc, 0, 0, c.alpha, Q, W, P, ld, scratch,
                                           d_colnan));
     } else {
-      ploc.resize((size_t)nloc + 1);
-      for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
-      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
-      PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
-      PH_TRY(dX.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
-      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
-      PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
-      PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), dXi.as<int32_t>(), g, nloc,
-                                          host_max_col_nnz(ploc.data(), nloc), zx, c.alpha, Q, W, P, ld, scratch, d_colnan));
+      int32_t max_nnz = 0;
+      PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
+      PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), dXi.as<int32_t>(), g, nloc, max_nnz, zx,
+                                          c.alpha, Q, W, P, ld, scratch, d_colnan));
     }
     home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
     return PLAIDHIP_OK;
   });
 
   // ---- crossprods, epilogue ---------------------------------------------------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
     if (ks) {
@@ -733,41 +792,28 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
   // ---- norm: es / diff(range(es)) over the whole m x n result; one NaN anywhere makes every score NaN -------------------
   if (c.normalize) {
     double mm[3] = {INFINITY, -INFINITY, 0.0};
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       PH_HIP(hipMemcpyAsync(mm, d_range, 24, hipMemcpyDeviceToHost, ctx->stream));
       PH_HIP(hipStreamSynchronize(ctx->stream));
       return PLAIDHIP_OK;
     });
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      if (nloc > 0 && rc == PLAIDHIP_OK) {
-        sh.xmin = mm[0] < sh.xmin ? mm[0] : sh.xmin;
-        sh.xmax = mm[1] > sh.xmax ? mm[1] : sh.xmax;
-        sh.es_nan = sh.es_nan || mm[2] != 0.0;
-      }
-    }
+    merge_range(s, mm[0], mm[1], mm[2] != 0.0);
     sh.rv.arrive_and_wait();
     const double range = sh.es_nan ? std::numeric_limits<double>::quiet_NaN() : sh.xmax - sh.xmin;
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       return launch_ssgsea_exact_norm(ctx, dS.as<double>(), m, m, nloc, range);
     });
   }
 
   // ---- the score shard goes home ----------------------------------------------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (nloc > 0) PH_TRY(home.copy(ctx, dS.p));
     PH_HIP(hipStreamSynchronize(ctx->stream));
     return PLAIDHIP_OK;
   });
-  ctx->precision = saved_precision;
-  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
-    hipStreamSynchronize(ctx->stream);
-    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
-  }
-  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return s.finish();
 }
 
 // one device's part of replaid.sing.exact (method 10, kernels_sing.hip): the min ranks of its columns as replaid.sing takes
@@ -775,27 +821,15 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
 // pinned epilogue; for the dispersions the last ranks (a second rank pass over a tie-free column made from the first),
 // the ranks by position and the per-pair kernel, once per direction.  Nothing couples the shards.
 int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
-  int rc = PLAIDHIP_OK;
-  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
-  auto step = [&](const std::function<int()>& fn) {
-    if (!live()) return;
-    try {
-      rc = fn();
-    } catch (...) {
-      rc = on_exception();
-    }
-    if (rc != PLAIDHIP_OK) sh.abort.store(1);
-  };
-  int32_t lo = 0, nloc = 0;
-  shard_columns(c, ndev, k, &lo, &nloc);
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m;
   const bool sparse = c.Xp != nullptr;
   const bool down = c.Dp != nullptr;
   const bool want_score = c.sx_out[0] || c.sx_out[1] || c.sx_out[2];
   const bool want_disp = c.sx_out[3] || c.sx_out[4] || c.sx_out[5];
   const int64_t ld = even_ld(g);   // replaid.sing's layout: the pair crossprod takes the ranks as it takes them there
-  const int saved_precision = ctx->precision;
-  ctx->precision = PLAIDHIP_PRECISION_F64;   // fp64 and integers in every mode, as the other exact scorers
+  s.force_f64();
   plaidhip_geneset *gs_up = nullptr, *gs_dn = nullptr;
   CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dops{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
   DevBuf dk, dGp, dGi, dDp, dDi;
@@ -811,7 +845,7 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   }
 
   // ---- upload, NaN flags, min ranks; last ranks and the ranks by position --------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     PH_HIP(hipSetDevice(ctx->device));
     if (want_score) {
       PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs_up));
@@ -824,20 +858,10 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
     PH_TRY(dk.alloc((size_t)m * 2 * 4));
     PH_HIP(hipMemcpyAsync(dk.p, kset.data(), (size_t)m * 2 * 4, hipMemcpyHostToDevice, ctx->stream));
     if (want_disp) {
-      const size_t zu = (size_t)c.Gp[m], zd = down ? (size_t)c.Dp[m] : 0;
-      PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
-      PH_TRY(dGi.alloc(std::max<size_t>(zu, 1) * 4));
-      PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      if (zu > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, zu * 4, hipMemcpyHostToDevice, ctx->stream));
-      if (down) {
-        PH_TRY(dDp.alloc((size_t)(m + 1) * 4));
-        PH_TRY(dDi.alloc(std::max<size_t>(zd, 1) * 4));
-        PH_HIP(hipMemcpyAsync(dDp.p, c.Dp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (zd > 0) PH_HIP(hipMemcpyAsync(dDi.p, c.Di, zd * 4, hipMemcpyHostToDevice, ctx->stream));
-      }
+      PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
+      if (down) PH_TRY(upload_pattern(ctx, c.Dp, c.Di, m, dDp, dDi));
     }
-    const int64_t z0 = sparse ? c.Xp[lo] : 0;
-    const int64_t zx = sparse ? (int64_t)c.Xp[lo + nloc] - z0 : 0;
+    const int64_t zx = s.zx;
     const size_t col = (size_t)ld * nloc;
     // [R | Y (then the ranks by position, u32) | Q] for the dispersions, R alone without; a dgCMatrix: the ranks of its
     // stored values behind them
@@ -856,15 +880,8 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
                               (size_t)g * 8, nloc, on_panel));
       PH_TRY(launch_sing_colnan(ctx, dX.as<double>(), ld, nullptr, g, nloc, 0, d_colnan));
     } else {
-      ploc.resize((size_t)nloc + 1);
-      for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
-      const int32_t max_nnz = host_max_col_nnz(ploc.data(), nloc);
-      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
-      PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
-      PH_TRY(dX.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
-      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
-      PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
+      int32_t max_nnz = 0;
+      PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
       PH_TRY(launch_sing_colnan(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), g, nloc, max_nnz, d_colnan));
       // replaid.sing ranks the zeros too (shard_worker): the dense rank matrix from the ranks of the stored values, or, for
       // a column with more stored values than one pass ranks, densify and rank
@@ -885,7 +902,7 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   });
 
   // ---- scores: crossprods on the exact rank route, the pinned epilogue; dispersions: the per-pair kernel -----------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
     if (want_score) {
@@ -910,60 +927,42 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   });
 
   // ---- the requested shards go home ---------------------------------------------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (nloc > 0)
       for (int o = 0; o < 6; ++o)
         if (c.sx_out[o]) PH_TRY(home[o].copy(ctx, part(o)));
     PH_HIP(hipStreamSynchronize(ctx->stream));
     return PLAIDHIP_OK;
   });
-  ctx->precision = saved_precision;
-  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
-    hipStreamSynchronize(ctx->stream);
-    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
-  }
-  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return s.finish();
 }
 
-// one device's part of a sharded replaid.ucell / aucell / scse / gsva (methods 3 - 6).  The same phases as the context
-// entries (api.cpp: plaidhip_ucell ...), with the quantities that couple the samples combined on the host in between:
-// max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the z
-// row transform (:341-343) and the medians' flags and mean(medx) (:554-575).
+// one device's part of replaid.ucell / aucell / scse / gsva (methods 3 - 6; one shard: plaidhip_ucell ... plaidhip_gsva_csc)
+// and of replaid.gsva.exact (method 9).  The quantities that couple the samples are combined on the host between the
+// phases: max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the
+// z row transform (:341-343) and the medians' flags and mean(medx) (:554-575).
 int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   if (c.method == 8) return ssgsea_exact_worker(ctx, c, ndev, k, sh);
   if (c.method == 10) return sing_exact_worker(ctx, c, ndev, k, sh);
-  int rc = PLAIDHIP_OK;
-  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
-  auto step = [&](const std::function<int()>& fn) {
-    if (!live()) return;
-    try {
-      rc = fn();
-    } catch (...) {
-      rc = on_exception();
-    }
-    if (rc != PLAIDHIP_OK) sh.abort.store(1);
-  };
-  int32_t lo = 0, nloc = 0;
-  shard_columns(c, ndev, k, &lo, &nloc);
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m, n = c.n;
   const bool sparse = c.Xp != nullptr;
   const int method = c.method;
   const bool ranked = method == 3 || method == 4;
-  // replaid.gsva.exact (method 9): replaid.gsva's row transform (z: the code of method 6 below; ecdf: one shard, the
-  // launches of plaidhip_gsva / plaidhip_gsva_csc; none: X as it is), then the last ranks of the columns of v and the
-  // walk of kernels_ks.hip in place of the signed ranks, the crossprod and the medians
+  // replaid.gsva.exact (method 9): replaid.gsva's row transform (z, ecdf, or none: X as it is), then the last ranks of the
+  // columns of v and the walk of kernels_ks.hip in place of the signed ranks, the crossprod and the medians
   const bool gx = method == 9;
-  const bool ztf = method == 6 || (gx && c.rowtf == 0);
-  const bool ecdf = gx && c.rowtf == 1;
+  const bool ztf = (method == 6 || gx) && c.rowtf == 0;
+  // "ecdf" ranks all samples of a gene together: one shard only (the argument checks see to it)
+  const bool ecdf = (method == 6 || gx) && c.rowtf == 1;
   // "gauss": GSVA's kernel CDF estimate (kernels_kcdf.hip).  Every V_ij needs its gene's whole row, so all of X goes to
   // every device, which computes the columns of its own shard: dX holds V, dense, whatever X was
   const bool gauss = gx && c.rowtf == 3;
-  // leading dimension of the staged X and of the ranks: that of the context entry (dense_average_ranks, plaidhip_scse:
-  // g; plaidhip_gsva: even), so that the crossprod sees the same layout
+  // leading dimension of the staged X and of the ranks: g, or even where the transposes and the pair crossprod of
+  // replaid.gsva want their columns 16-byte aligned
   const int64_t ld = (ztf || ecdf) ? even_ld(g) : (int64_t)g;
-  const int saved_precision = ctx->precision;
-  if (gx) ctx->precision = PLAIDHIP_PRECISION_F64;   // fp64 in every mode, as replaid.ssgsea.exact
+  if (gx) s.force_f64();
   plaidhip_geneset* gs = nullptr;
   CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dR{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
   DevBuf dscratch, dcsc, drp, drows, dy, dadd;
@@ -973,15 +972,15 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   uint32_t* d_flags = nullptr;
   double *d_gmax = nullptr, *d_mm = nullptr, *d_med = nullptr, *d_colmax = nullptr, *d_colsum = nullptr;
   double *d_mean = nullptr, *d_ssd = nullptr, *d_seed = nullptr, *d_run = nullptr;
-  int64_t zx = 0;
-  int32_t max_row = 0;
+  const int64_t zx = s.zx;
+  int32_t max_row = 0, max_nnz = 0;
   std::vector<int32_t> ploc;
   const double n_inv = 1.0 / (double)n;   // (the scale of launch_row_group_moments' group 0)
   // host sources of asynchronous uploads: they live until the worker's last synchronisation
   std::vector<double> host_mean, host_ssd, row_nnz, add;
 
   // ---- upload; the per-shard work up to the first coupling ------------------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     PH_HIP(hipSetDevice(ctx->device));
     PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
     const size_t nl = (size_t)std::max(nloc, 1);
@@ -1004,16 +1003,12 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     }
     if (nloc == 0) return PLAIDHIP_OK;
     if (gx) {
-      const size_t z = (size_t)c.Gp[m];
       // Q, then the rank scratch (dense columns: 2 g nloc doubles; a dgCMatrix's stored values: 3 nnz), then T
-      const int64_t nz = sparse && !gauss ? (int64_t)c.Xp[lo + nloc] - c.Xp[lo] : 0;   // ("gauss" leaves a dense V)
+      const int64_t nz = gauss ? 0 : zx;   // ("gauss" leaves a dense V)
       ops_t = (size_t)g * nloc + std::max((size_t)g * nloc * 2, (size_t)nz * 3);
       PH_TRY(dops.alloc((ops_t + (size_t)g) * 8));
       PH_TRY(dcolnan.alloc((size_t)nloc * 4));
-      PH_TRY(dGp.alloc((size_t)(m + 1) * 4));
-      PH_TRY(dGi.alloc(std::max<size_t>(z, 1) * 4));
-      PH_HIP(hipMemcpyAsync(dGp.p, c.Gp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      if (z > 0) PH_HIP(hipMemcpyAsync(dGi.p, c.Gi, z * 4, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
     }
     if (gauss) {
       PH_TRY(dX.alloc((size_t)ld * nloc * 8));
@@ -1021,15 +1016,18 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     } else if (!sparse) {
       PH_TRY(dX.alloc((size_t)ld * nloc * 8));
       if (method != 5 && !gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
-      // ucell / aucell: the ranks of a column panel follow its DMA (dense_average_ranks' kernel and arguments)
+      // ucell / aucell: the average ranks of a column panel follow its DMA
       auto on_panel = [&](int64_t c0, int64_t c1) -> int {
         return launch_colranks_dense_f64(ctx, dX.as<double>() + c0 * ld, ld, g, (int32_t)(c1 - c0), PLAIDHIP_TIES_AVERAGE, 0,
                                          1.0, dR.as<double>() + c0 * ld, ld, d_colmax + c0);
       };
       PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
                               (size_t)g * 8, nloc, ranked ? std::function<int(int64_t, int64_t)>(on_panel) : nullptr));
-      if (ecdf) {   // plaidhip_gsva's launches: genes become columns, max ranks, and back (the factor 1 / n dropped)
-        double* tmp = dops.as<double>();
+      if (ecdf) {
+        // zX = t(apply(X, 1, function(x) ecdf(x)(x))) (R/plaid.R:346): ecdf(x)(x_i) = #{x <= x_i} / n = rank(x, "max") / n
+        // per gene.  Genes become columns (transpose), the column rank kernel ranks them, and the result goes back; the
+        // factor 1 / n is dropped because only the per-sample ORDER of zX is used afterwards (:352)
+        double* tmp = gx ? dops.as<double>() : dR.as<double>();
         PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), ld, g, nloc, tmp, nloc));
         PH_TRY(launch_colranks_dense_f64(ctx, tmp, nloc, nloc, g, PLAIDHIP_TIES_MAX, 0, 1.0, dX.as<double>(), nloc, nullptr));
         PH_TRY(launch_transpose_f64(ctx, dX.as<double>(), nloc, nloc, g, tmp, ld));
@@ -1042,26 +1040,14 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
         PH_TRY(launch_row_group_partials(ctx, dX.as<double>(), ld, g, nloc, dy.as<int32_t>(), nullptr, dscratch.as<double>()));
       }
     } else {
-      const int64_t z0 = c.Xp[lo];
-      zx = (int64_t)c.Xp[lo + nloc] - z0;
-      ploc.resize((size_t)nloc + 1);
-      for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
-      PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
-      PH_TRY(dXi.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
-      double* vals = nullptr;
-      if (ztf || ecdf) {
-        PH_TRY(dcsc.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
-        vals = dcsc.as<double>();
-      } else {
-        PH_TRY(dX.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
-        vals = dX.as<double>();
-      }
-      PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-      PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
-      PH_TRY(upload_pipelined(ctx, reinterpret_cast<char*>(vals), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
-      if (ranked) {   // dense average ranks, zeros tie (dense_average_ranks' sparse branch)
+      // (a row transform builds a dense zX in dX: the slots' values go beside it)
+      if (ztf || ecdf) PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dcsc, &max_nnz));
+      else PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
+      double* vals = (ztf || ecdf) ? dcsc.as<double>() : dX.as<double>();
+      if (ranked) {
+        // dense average ranks, zeros tie: from the ranks of the stored values (any nrow(X)) unless a column stores more
+        // than one pass ranks -- then it is densified and ranked
         PH_TRY(dR.alloc((size_t)ld * nloc * 8));
-        const int32_t max_nnz = host_max_col_nnz(ploc.data(), nloc);
         if (max_nnz <= max_sparse_rank_column()) {
           PH_TRY(dscratch.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
           PH_TRY(launch_colranks_csc_dense_nz_f64(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, max_nnz,
@@ -1072,8 +1058,11 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
                                                0, 1.0, dR.as<double>(), ld, d_colmax));
         }
       } else if (ecdf) {
-        // plaidhip_gsva_csc's launches: #{x <= x_i} per gene from the max ranks of its stored values and its zeros
+        // "ecdf" without the factor 1 / n, as for dense X: #{x <= x_i} per gene from the max ranks of its stored values and
+        // its implicit zeros; the stored entries' values go back to CSC order (into the CSC value slot, no longer needed)
+        // and are expanded with the rows' zero values
         PH_TRY(dX.alloc((size_t)ld * nloc * 8));
+        if (!gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));   // (zx <= g nloc: checked with the arguments)
         PH_TRY(drp.alloc((size_t)(g + 2) * 4));
         PH_TRY(dscratch.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
         PH_TRY(dperm.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
@@ -1082,7 +1071,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
         PH_HIP(hipMemcpyAsync(&max_row, drp.as<int32_t>() + g + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
         PH_HIP(hipStreamSynchronize(ctx->stream));
         PH_TRY(launch_csr_row_ecdf(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, nloc, max_row, dperm.as<int32_t>(),
-                                   dops.as<double>(), vals, drows.as<double>()));
+                                   gx ? dops.as<double>() : dR.as<double>(), vals, drows.as<double>()));
         PH_TRY(launch_csc_expand(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, g, nloc, ld, drows.as<double>(), nullptr,
                                  nullptr, dX.as<double>()));
       } else if (ztf) {
@@ -1097,14 +1086,22 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
         PH_HIP(hipMemcpyAsync(rp.data(), drp.p, (size_t)(g + 2) * 4, hipMemcpyDeviceToHost, ctx->stream));
         PH_HIP(hipStreamSynchronize(ctx->stream));
         max_row = rp[(size_t)g + 1];
-        PH_TRY(launch_csr_row_stored_moment(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, max_row, nullptr, d_run));
-        std::vector<double> sums((size_t)g);
-        std::vector<int32_t> len((size_t)g);
-        for (int32_t i = 0; i < g; ++i) len[(size_t)i] = rp[(size_t)i + 1] - rp[(size_t)i];
-        PH_HIP(hipMemcpyAsync(sums.data(), d_run, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
-        PH_HIP(hipStreamSynchronize(ctx->stream));
-        sh.row_sum[(size_t)k] = std::move(sums);   // (each shard writes its own slot)
-        sh.row_len[(size_t)k] = std::move(len);
+        // One shard: both passes in one kernel, the launch plaidhip_gsva_csc has always made.  Its division and its
+        // q + z mu^2 run on the device, where the compiler may contract them differently from the host's below: the
+        // one-device bits stay what they were.
+        if (ndev == 1) {   // (group 1's unused sums land on d_seed, which is written later)
+          PH_TRY(launch_csr_row_group_moments(ctx, drp.as<int32_t>(), nullptr, dscratch.as<double>(), g, max_row, nullptr, n, 0,
+                                              d_mean, d_ssd));
+        } else {
+          PH_TRY(launch_csr_row_stored_moment(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, max_row, nullptr, d_run));
+          std::vector<double> sums((size_t)g);
+          std::vector<int32_t> len((size_t)g);
+          for (int32_t i = 0; i < g; ++i) len[(size_t)i] = rp[(size_t)i + 1] - rp[(size_t)i];
+          PH_HIP(hipMemcpyAsync(sums.data(), d_run, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
+          PH_HIP(hipStreamSynchronize(ctx->stream));
+          sh.row_sum[(size_t)k] = std::move(sums);   // (each shard writes its own slot)
+          sh.row_len[(size_t)k] = std::move(len);
+        }
       }
     }
     // (the result's pages are made from here on, as in shard_worker)
@@ -1116,7 +1113,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   double gmax = -INFINITY;   // (the host copy of d_gmax: lives until the stream has been synchronised)
   auto global_max = [&](const double* d_vec) {
     double mine = -INFINITY;
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       PH_TRY(launch_max(ctx, d_vec, nloc, d_gmax));
       PH_HIP(hipMemcpyAsync(&mine, d_gmax, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1125,14 +1122,14 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     });
     {
       std::lock_guard<std::mutex> lk(sh.mu);
-      if (nloc > 0 && rc == PLAIDHIP_OK) {
+      if (nloc > 0 && s.rc == PLAIDHIP_OK) {
         sh.gmax = (sh.gmax_set && !(mine > sh.gmax)) ? sh.gmax : mine;
         sh.gmax_set = true;
       }
     }
     sh.rv.arrive_and_wait();
     gmax = sh.gmax_set ? sh.gmax : -INFINITY;
-    step([&]() -> int {   // every shard divides by / subtracts from the same device scalar
+    s.step([&]() -> int {   // every shard divides by / subtracts from the same device scalar
       if (nloc == 0) return PLAIDHIP_OK;
       PH_HIP(hipMemcpyAsync(d_gmax, &gmax, 8, hipMemcpyHostToDevice, ctx->stream));
       PH_HIP(hipStreamSynchronize(ctx->stream));
@@ -1142,31 +1139,16 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
 
   // ---- replaid.gsva, z row transform: rowMeans and rowSds of ALL samples -----------------------------------------------
   if (ztf && !sparse) {
-    // chained, ordered reductions: in round r only shard r works, continuing shard r - 1's running sums block by block
-    auto chain = [&](std::vector<double>& run) {
-      for (int r = 0; r < ndev; ++r) {
-        if (r == k)
-          step([&]() -> int {
-            if (nloc == 0) return PLAIDHIP_OK;
-            PH_HIP(hipMemcpyAsync(d_seed, run.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
-            PH_TRY(launch_reduce_blocks_seeded(ctx, dscratch.as<double>(), g, nloc, d_seed, d_run));
-            PH_HIP(hipMemcpyAsync(run.data(), d_run, (size_t)g * 8, hipMemcpyDeviceToHost, ctx->stream));
-            PH_HIP(hipStreamSynchronize(ctx->stream));
-            return PLAIDHIP_OK;
-          });
-        sh.rv.arrive_and_wait();
-      }
-    };
-    chain(sh.chain_sum);
-    step([&]() -> int {
+    chain_block_sums(s, sh.chain_sum, dscratch.as<double>(), g, 1, d_seed, d_run);
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       host_mean.resize((size_t)g);
       for (int32_t i = 0; i < g; ++i) host_mean[(size_t)i] = sh.chain_sum[(size_t)i] * n_inv;   // reduce_blocks_kernel's scale
       PH_HIP(hipMemcpyAsync(d_mean, host_mean.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
       return launch_row_group_partials(ctx, dX.as<double>(), ld, g, nloc, dy.as<int32_t>(), d_mean, dscratch.as<double>());
     });
-    chain(sh.chain_ssd);
-    step([&]() -> int {
+    chain_block_sums(s, sh.chain_ssd, dscratch.as<double>(), g, 1, d_seed, d_run);
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       PH_HIP(hipMemcpyAsync(d_ssd, sh.chain_ssd.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
       PH_TRY(launch_row_ztransform_shard(ctx, dX.as<double>(), ld, g, nloc, n, d_mean, d_ssd));
@@ -1180,17 +1162,17 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     host_ssd.assign((size_t)g, 0.0);
     row_nnz.assign((size_t)g, 0.0);
     sh.rv.arrive_and_wait();
-    if (live()) {
+    if (s.live()) {
       for (int32_t i = 0; i < g; ++i) {
-        double s = 0.0, z = 0.0;
+        double sum = 0.0, z = 0.0;
         for (int q = 0; q < ndev; ++q)
-          if (!sh.row_sum[(size_t)q].empty()) { s += sh.row_sum[(size_t)q][(size_t)i]; z += sh.row_len[(size_t)q][(size_t)i]; }
-        host_mean[(size_t)i] = s / (double)n;
+          if (!sh.row_sum[(size_t)q].empty()) { sum += sh.row_sum[(size_t)q][(size_t)i]; z += sh.row_len[(size_t)q][(size_t)i]; }
+        host_mean[(size_t)i] = sum / (double)n;
         row_nnz[(size_t)i] = z;
       }
     }
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
+    s.step([&]() -> int {
+      if (nloc == 0 || ndev == 1) return PLAIDHIP_OK;
       PH_HIP(hipMemcpyAsync(d_mean, host_mean.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
       PH_TRY(launch_csr_row_stored_moment(ctx, drp.as<int32_t>(), dscratch.as<double>(), g, max_row, d_mean, d_run));
       std::vector<double> q((size_t)g);
@@ -1200,18 +1182,18 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       return PLAIDHIP_OK;
     });
     sh.rv.arrive_and_wait();
-    if (live()) {
+    if (s.live()) {
       for (int32_t i = 0; i < g; ++i) {
         double q = 0.0;
-        for (int s = 0; s < ndev; ++s)
-          if (!sh.row_ssd[(size_t)s].empty()) q += sh.row_ssd[(size_t)s][(size_t)i];
+        for (int r = 0; r < ndev; ++r)
+          if (!sh.row_ssd[(size_t)r].empty()) q += sh.row_ssd[(size_t)r][(size_t)i];
         const double mu = host_mean[(size_t)i], z = (double)n - row_nnz[(size_t)i];
         host_ssd[(size_t)i] = z > 0.0 ? q + z * (mu * mu) : q;
       }
     }
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
-      PH_HIP(hipMemcpyAsync(d_ssd, host_ssd.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
+      if (ndev > 1) PH_HIP(hipMemcpyAsync(d_ssd, host_ssd.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
       double* dflt = d_seed;
       PH_TRY(launch_row_z_defaults(ctx, d_mean, d_ssd, g, n, dflt));   // (n: the sd's divisor alone)
       PH_TRY(launch_csc_expand_shard(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), dcsc.as<double>(), g, nloc, n, ld, dflt, d_mean,
@@ -1221,8 +1203,10 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     });
   }
   if (method == 6) {
-    // rX = colranks(zX, signed = TRUE, "average"), |rX|^(1 + tau) fused (gsva_scores, api.cpp)
-    step([&]() -> int {
+    // rX = colranks(zX, signed = TRUE, "average"); rX / max|rX|; sign * |rX|^(1 + tau) (R/plaid.R:352-358)
+    //    = sign * rank^(1 + tau) / max(rank^(1 + tau)): the power is fused into the rank kernel, the division into the
+    //    crossprod's epilogue (d_gmax below), by linearity of the mean statistic
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       return launch_colranks_dense_f64(ctx, dX.as<double>(), ld, g, nloc, PLAIDHIP_TIES_AVERAGE, 1,
                                        c.tau > 0.0 ? 1.0 + c.tau : 1.0, dR.as<double>(), ld, d_colmax);
@@ -1231,7 +1215,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
 
   // ---- replaid.gsva.exact: q = rank(v, "last") of every column, then the walk ------------------------------------------------
   if (gx)
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
       if (nloc == 0) return PLAIDHIP_OK;
       double* Q = dops.as<double>();
@@ -1241,8 +1225,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       // (alpha = 0: the operand pass writes Q and the NaN flags only, no W or P)
       if (sparse && c.rowtf == 2)   // ("gauss" left its dense V in dX) the stored values are ranked, as replaid.ssgsea.exact ranks a dgCMatrix
         PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), dXi.as<int32_t>(), g, nloc,
-                                            host_max_col_nnz(ploc.data(), nloc), zx, 0.0, Q, nullptr, nullptr, g, scratch,
-                                            d_colnan));
+                                            max_nnz, zx, 0.0, Q, nullptr, nullptr, g, scratch, d_colnan));
       else
         PH_TRY(launch_ssgsea_exact_operands(ctx, dX.as<double>(), ld, nullptr, nullptr, g, nloc, 0, 0, 0.0, Q, nullptr, nullptr, g,
                                             scratch, d_colnan));
@@ -1253,7 +1236,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   // ---- max(rX) (ucell / aucell: R/plaid.R:278, 306; gsva: max|rX|, :354) --------------------------------------------------
   if (method != 5 && !gx) global_max(d_colmax);
   if (ranked)
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       return method == 3 ? launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 0, c.rmax + 1.0, d_gmax)      // :278
                          : launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 1, c.auc_max_rank, d_gmax);   // :306
@@ -1263,20 +1246,14 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   bool remove_log2 = c.remove_log2 > 0;
   if (method == 5 && c.remove_log2 < 0) {
     double mm[2] = {INFINITY, -INFINITY};
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       PH_TRY(launch_minmax(ctx, dX.as<double>(), sparse ? zx : (int64_t)g * nloc, d_mm));
       PH_HIP(hipMemcpyAsync(mm, d_mm, 16, hipMemcpyDeviceToHost, ctx->stream));
       PH_HIP(hipStreamSynchronize(ctx->stream));
       return PLAIDHIP_OK;
     });
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      if (rc == PLAIDHIP_OK) {
-        sh.xmin = mm[0] < sh.xmin ? mm[0] : sh.xmin;
-        sh.xmax = mm[1] > sh.xmax ? mm[1] : sh.xmax;
-      }
-    }
+    merge_range(s, mm[0], mm[1]);
     sh.rv.arrive_and_wait();
     double mn = sh.xmin, mx = sh.xmax;
     if (sparse && (int64_t)c.Xp[n] < (int64_t)g * n) { mn = mn < 0.0 ? mn : 0.0; mx = mx > 0.0 ? mx : 0.0; }   // implicit zeros
@@ -1284,7 +1261,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   }
   if (method == 5) {
     if (k == 0) sh.removed_log2 = remove_log2;
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       if (remove_log2) PH_TRY(launch_map(ctx, dX.as<double>(), sparse ? zx : (int64_t)g * nloc, sparse ? 3 : 2, 0.0, nullptr));
       return launch_col_abs_sums(ctx, dX.as<double>(), ld, g, sparse ? dXp.as<int32_t>() : nullptr, nloc, d_colsum);
@@ -1292,13 +1269,15 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   }
 
   // ---- crossprod --------------------------------------------------------------------------------------------------------
-  if (!gx) step([&]() -> int {
+  if (!gx) s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
     if (method == 5) {
       const int stat = c.score_mean ? PLAIDHIP_STAT_MEAN : PLAIDHIP_STAT_SUM;
-      if (sparse) {   // the kernel is chosen from the density of the whole matrix, as in shard_worker
-        const int64_t nnz_choice = (int64_t)((double)c.Xp[n] / (double)n * (double)nloc);
+      if (sparse) {
+        // the kernel is chosen from the density of the whole matrix, as in shard_worker (one shard: the count itself, which
+        // x / n * n may miss by one in its last place)
+        const int64_t nnz_choice = ndev == 1 ? (int64_t)c.Xp[n] : (int64_t)((double)c.Xp[n] / (double)n * (double)nloc);
         return launch_spmm_csc_f64(ctx, gs, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), nloc, nnz_choice, stat, 1.0,
                                    nullptr, 0.0, dS.as<double>(), m, nullptr);
       }
@@ -1314,38 +1293,17 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
                                  0.0, dS.as<double>(), m, d_flags, x_kind);
   });
 
-  // ---- normalize_medians (R/plaid.R:554-575), as shard_worker: flags, medians, mean(medx) in the device's order -----------
+  // ---- normalize_medians (R/plaid.R:554-575) -------------------------------------------------------------------------------
   if (method != 5 && !gx) {
-    uint32_t fl[4] = {0, 0, 0, 0};
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
-      PH_HIP(hipMemcpyAsync(fl, d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
-      PH_HIP(hipStreamSynchronize(ctx->stream));
-      return PLAIDHIP_OK;
-    });
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      for (int q = 0; q < 4; ++q) sh.flags[q] |= fl[q];
-    }
-    sh.rv.arrive_and_wait();
-    const int ignore_zero = (sh.flags[1] != 0 && sh.flags[0] == 0) ? 1 : 0;
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
-      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, nloc, ignore_zero, nullptr, d_med));
-      PH_HIP(hipMemcpyAsync(sh.med_all.data() + lo, d_med, (size_t)nloc * 8, hipMemcpyDeviceToHost, ctx->stream));
-      PH_HIP(hipStreamSynchronize(ctx->stream));
-      return PLAIDHIP_OK;
-    });
-    sh.rv.arrive_and_wait();
-    const double mean_med = live() ? mean_like_device_sum(sh.med_all.data(), n) : 0.0;
-    step([&]() -> int {
+    const double mean_med = medians_and_their_mean(s, dS.as<double>(), d_flags, d_med);
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       return launch_shift_columns(ctx, dS.as<double>(), m, m, nloc, d_med, mean_med, nullptr);
     });
   }
 
-  // ---- the affine steps of the context entries ----------------------------------------------------------------------------
-  step([&]() -> int {
+  // ---- the affine steps of replaid.ucell and replaid.scse ------------------------------------------------------------------
+  s.step([&]() -> int {
     if (nloc == 0) return PLAIDHIP_OK;
     if (method == 3) {   // 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:280)
       add.resize((size_t)m);
@@ -1361,18 +1319,12 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   });
 
   // ---- the score shard goes home ----------------------------------------------------------------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (nloc > 0) PH_TRY(home.copy(ctx, dS.p));
     PH_HIP(hipStreamSynchronize(ctx->stream));
     return PLAIDHIP_OK;
   });
-  ctx->precision = saved_precision;
-  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
-    hipStreamSynchronize(ctx->stream);
-    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
-  }
-  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return s.finish();
 }
 
 // the group means of [2][rows] chained sums: reduce_blocks_kernel's scale (a product with 1 / n_k, NaN for an empty group)
@@ -1385,30 +1337,19 @@ void scaled_group_means(const std::vector<double>& sums, int32_t rows, int64_t n
   }
 }
 
-// one device's part of a sharded plaid.test (method 7, R/plaid.R:392-474): plaidhip_plaid_test's phases with what
+// one device's part of a sharded plaid.test (method 7, R/plaid.R:392-474; one shard: plaidhip_plaid_test / _csc), with what
 // couples the samples combined on the host in between -- everything plaid.test reduces is a row sum over the samples,
 // so only O(genes + sets) numbers cross between the shards and the scores never leave their device.
 //   logFC: dense X chains the two group sums of X from shard to shard (the one-device block order); a dgCMatrix sums
 //     each shard's stored values per group, the host adds the shards.  Shard 0 alone then takes F = [fc, fc^2] and
-//     T = Gt F, with the launches of the one-device entry.
+//     T = Gt F.
 //   scores ("lm"): gsetX's columns uploaded, or plaid(X, G)'s sharded crossprod and medians (shard_worker), stopped
 //     before the shift: the shard keeps the raw S, its medians and mean(medx).
 //   Welch moments: the group sums of the score rows, shifted on load (launch_row_group_shifted_partials), chained; then,
 //     from the global means, the sums of squared deviations, chained.  plaidhip_plaid_test_finish runs in run_call.
 int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
-  int rc = PLAIDHIP_OK;
-  auto live = [&] { return rc == PLAIDHIP_OK && sh.abort.load() == 0; };
-  auto step = [&](const std::function<int()>& fn) {
-    if (!live()) return;
-    try {
-      rc = fn();
-    } catch (...) {
-      rc = on_exception();
-    }
-    if (rc != PLAIDHIP_OK) sh.abort.store(1);
-  };
-  int32_t lo = 0, nloc = 0;
-  shard_columns(c, ndev, k, &lo, &nloc);
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m, n = c.n;
   const bool sparse = c.Xp != nullptr;
   const bool lm = (c.tests & 4) != 0;
@@ -1421,13 +1362,13 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   DevBuf dy, dws, drows, drp, dRj, dRx, dF, dT;
   uint32_t* d_flags = nullptr;
   double *d_med = nullptr, *d_seed = nullptr, *d_run = nullptr, *d_mean = nullptr;
-  int64_t zx = 0;
+  const int64_t zx = s.zx;
   std::vector<int32_t> ploc;
   // host sources of asynchronous uploads: they live until the worker's last synchronisation
   std::vector<double> x_mean, s_mean;
 
   // ---- upload; X's group sums of this shard; plaid()'s crossprod of dense X panel by panel --------------------------------
-  step([&]() -> int {
+  s.step([&]() -> int {
     PH_HIP(hipSetDevice(ctx->device));
     if (k == 0 || scores) PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
     PH_TRY(dsmall.alloc(64 + nl * 8));
@@ -1453,17 +1394,9 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
                               (size_t)g * 8, nloc, scores ? std::function<int(int64_t, int64_t)>(on_panel) : nullptr));
       return launch_row_group_partials(ctx, dX.as<double>(), ldg, g, nloc, dy.as<int32_t>(), nullptr, dws.as<double>());
     }
-    const int64_t z0 = c.Xp[lo];
-    zx = (int64_t)c.Xp[lo + nloc] - z0;
-    ploc.resize((size_t)nloc + 1);
-    for (int32_t j = 0; j <= nloc; ++j) ploc[(size_t)j] = (int32_t)(c.Xp[lo + j] - z0);
+    int32_t max_nnz = 0;
+    PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
     const size_t zb = (size_t)std::max<int64_t>(zx, 1);
-    PH_TRY(dXp.alloc((size_t)(nloc + 1) * 4));
-    PH_TRY(dXi.alloc(zb * 4));
-    PH_TRY(dX.alloc(zb * 8));
-    PH_HIP(hipMemcpyAsync(dXp.p, ploc.data(), (size_t)(nloc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    PH_TRY(upload_pipelined(ctx, dXi.as<char>(), 1, reinterpret_cast<const char*>(c.Xi + z0), 1, zx * 4, nullptr));
-    PH_TRY(upload_pipelined(ctx, dX.as<char>(), 1, reinterpret_cast<const char*>(c.X + z0), 1, zx * 8, nullptr));
     // the shard's row view, with its column indices (they look up y), and the unscaled group sums of its stored values
     PH_TRY(drp.alloc((size_t)(g + 2) * 4));
     PH_TRY(dRj.alloc(zb * 4));
@@ -1482,28 +1415,10 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
     return PLAIDHIP_OK;
   });
 
-  // chained, ordered reductions of the [nblk][2][rows] partials in dws: in round r only shard r works, continuing shard
-  // r - 1's running sums of both groups block by block
-  auto chain = [&](std::vector<double>& run, int32_t rows) {
-    for (int r = 0; r < ndev; ++r) {
-      if (r == k)
-        step([&]() -> int {
-          if (nloc == 0) return PLAIDHIP_OK;
-          PH_HIP(hipMemcpyAsync(d_seed, run.data(), (size_t)rows * 2 * 8, hipMemcpyHostToDevice, ctx->stream));
-          PH_TRY(launch_reduce_blocks_seeded(ctx, dws.as<double>(), rows, nloc, d_seed, d_run));
-          PH_TRY(launch_reduce_blocks_seeded(ctx, dws.as<double>() + rows, rows, nloc, d_seed + rows, d_run + rows));
-          PH_HIP(hipMemcpyAsync(run.data(), d_run, (size_t)rows * 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
-          PH_HIP(hipStreamSynchronize(ctx->stream));
-          return PLAIDHIP_OK;
-        });
-      sh.rv.arrive_and_wait();
-    }
-  };
-
   // ---- logFC = rowMeans(X[, y == 1]) - rowMeans(X[, y == 0]) (R/plaid.R:407-409); shard 0: Gt fc, Gt fc^2 (:478-479) -----
-  if (!sparse) chain(sh.chain_x, g);
+  if (!sparse) chain_block_sums(s, sh.chain_x, dws.as<double>(), g, 2, d_seed, d_run);
   else sh.rv.arrive_and_wait();   // every shard's stored-value sums are in sh.row_sum
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (k != 0) return PLAIDHIP_OK;
     x_mean.resize((size_t)g * 2);
     if (!sparse) {
@@ -1531,7 +1446,7 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   });
 
   // ---- the scores: gsetX's columns, or plaid(X, G)'s crossprod of a dgCMatrix (dense X: done panel by panel above) ---------
-  step([&]() -> int {
+  s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0 || !lm) return PLAIDHIP_OK;
     if (!scores)
@@ -1545,43 +1460,19 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
                                      nullptr, 0.0, nnz_choice);
   });
 
-  // ---- normalize_medians (R/plaid.R:554-575) as shard_worker, up to mean(medx): the shift is applied on load below ---------
-  double add = 0.0;
-  if (scores) {
-    uint32_t fl[4] = {0, 0, 0, 0};
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
-      PH_HIP(hipMemcpyAsync(fl, d_flags, 16, hipMemcpyDeviceToHost, ctx->stream));
-      PH_HIP(hipStreamSynchronize(ctx->stream));
-      return PLAIDHIP_OK;
-    });
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      for (int q = 0; q < 4; ++q) sh.flags[q] |= fl[q];
-    }
-    sh.rv.arrive_and_wait();
-    const int ignore_zero = (sh.flags[1] != 0 && sh.flags[0] == 0) ? 1 : 0;   // min(x) == 0, R/plaid.R:556-557
-    step([&]() -> int {
-      if (nloc == 0) return PLAIDHIP_OK;
-      PH_TRY(launch_col_medians_resume(ctx, dS.as<double>(), m, m, nloc, ignore_zero, nullptr, d_med));
-      PH_HIP(hipMemcpyAsync(sh.med_all.data() + lo, d_med, (size_t)nloc * 8, hipMemcpyDeviceToHost, ctx->stream));
-      PH_HIP(hipStreamSynchronize(ctx->stream));
-      return PLAIDHIP_OK;
-    });
-    sh.rv.arrive_and_wait();
-    add = live() ? mean_like_device_sum(sh.med_all.data(), n) : 0.0;   // mean(medx, na.rm = TRUE), :572
-  }
+  // ---- normalize_medians (R/plaid.R:554-575) up to mean(medx): the shift is applied on load below ----------------------------
+  const double add = scores ? medians_and_their_mean(s, dS.as<double>(), d_flags, d_med) : 0.0;
 
   // ---- Welch moments of the score rows (Rfast::ttests(t(gsetX), ina = y + 1), :429) --------------------------------------
   if (lm) {
     const double* med = scores ? d_med : nullptr;
-    step([&]() -> int {
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       return launch_row_group_shifted_partials(ctx, dS.as<double>(), m, m, nloc, dy.as<int32_t>(), med, add, nullptr,
                                                dws.as<double>());
     });
-    chain(sh.chain_s, m);
-    step([&]() -> int {
+    chain_block_sums(s, sh.chain_s, dws.as<double>(), m, 2, d_seed, d_run);
+    s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       s_mean.resize((size_t)m * 2);
       scaled_group_means(sh.chain_s, m, c.n0, c.n1, s_mean.data());
@@ -1589,15 +1480,16 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
       return launch_row_group_shifted_partials(ctx, dS.as<double>(), m, m, nloc, dy.as<int32_t>(), med, add, d_mean,
                                                dws.as<double>());
     });
-    chain(sh.chain_q, m);
+    chain_block_sums(s, sh.chain_q, dws.as<double>(), m, 2, d_seed, d_run);
   }
 
-  if (rc == PLAIDHIP_OK && sh.abort.load() != 0) {
-    hipStreamSynchronize(ctx->stream);
-    return PLAIDHIP_EHIP;   // another shard failed; its error text is reported
-  }
-  if (rc != PLAIDHIP_OK) hipStreamSynchronize(ctx->stream);
-  return rc;
+  return s.finish();
+}
+
+int check_contexts(plaidhip_ctx* const* ctxs, int ndev) {
+  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
+  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  return PLAIDHIP_OK;
 }
 
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
@@ -1648,7 +1540,7 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
         if (rcs[(size_t)k] != PLAIDHIP_OK) { rc = rcs[(size_t)k]; set_error("a device shard failed"); break; }
   }
   if (rc == PLAIDHIP_OK && c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = sh.removed_log2 ? 1 : 0;
-  if (rc == PLAIDHIP_OK && c.method == 7) {   // the host half of plaid.test, as plaidhip_plaid_test ends
+  if (rc == PLAIDHIP_OK && c.method == 7) {   // the host half of plaid.test (R/plaid.R:410-474)
     const int64_t ldg = even_ld(c.g);
     double tot1 = 0.0, tot2 = 0.0;
     for (int32_t i = 0; i < c.g; ++i) { tot1 += sh.pt_F[(size_t)i]; tot2 += sh.pt_F[(size_t)ldg + i]; }
@@ -1677,8 +1569,7 @@ int upload_host(plaidhip_ctx* ctx, void* dst, size_t ldd_bytes, const void* src,
 int run_sharded(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                 int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int stat, int normalize, double alpha,
                 double* S_out) {
-  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
-  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_contexts(ctxs, ndev));
   PH_TRY(check_host_common(Gp, g, n, m));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   PH_REQUIRE(X_or_x != nullptr || (Xp != nullptr && Xp[n] == 0), "null X");
@@ -1721,8 +1612,7 @@ int check_gsea_ks_genes(int32_t g) {
 int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                      int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
                      double* S_out, int single) {
-  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
-  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_contexts(ctxs, ndev));
   PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
   if (!single) PH_TRY(check_gsea_ks_genes(g));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
@@ -1778,8 +1668,7 @@ int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const 
 int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                    int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
                    double* S_out) {
-  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
-  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_contexts(ctxs, ndev));
   PH_TRY(check_gsva_exact_args(ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   Call c{9, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, 0, 0.0, S_out};
@@ -1812,8 +1701,7 @@ int check_sing_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_
 int run_sing_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                    int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
                    double* const out[6]) {
-  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
-  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
+  PH_TRY(check_contexts(ctxs, ndev));
   PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   Call c{10, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, 0, 0.0, nullptr};
@@ -1826,91 +1714,44 @@ int run_sing_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const
 
 }  // namespace plaidhip
 
-// ---- multi-device entry points (include/plaidhip.h) ---------------------------------------------------------------------
+// ---- replaid.ucell / aucell / scse / gsva and plaid.test: one set of argument checks, one way in ---------------------------
 namespace {
-
-std::mutex g_multi_mu;
-std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
-int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
-
-int multi_contexts(const int* devices, int ndev, std::vector<plaidhip_ctx*>& out) {
-  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
-  int count = 0;
-  PH_TRY(plaidhip_device_count(&count));
-  std::lock_guard<std::mutex> lk(g_multi_mu);
-  if ((int)g_multi_ctx.size() < count) g_multi_ctx.resize((size_t)count, nullptr);
-  out.clear();
-  for (int k = 0; k < ndev; ++k) {
-    const int d = devices ? devices[k] : k;
-    PH_REQUIRE(d >= 0 && d < count, "multi: device %d out of range [0, %d)", d, count);
-    for (int q = 0; q < k; ++q) PH_REQUIRE((devices ? devices[q] : q) != d, "multi: device %d listed twice", d);
-    if (g_multi_ctx[(size_t)d] == nullptr) PH_TRY(plaidhip_init(d, nullptr, &g_multi_ctx[(size_t)d]));
-    g_multi_ctx[(size_t)d]->precision = g_multi_precision;
-    out.push_back(g_multi_ctx[(size_t)d]);
-  }
-  return PLAIDHIP_OK;
-}
-
-// the argument checks of the context entries (api.cpp: plaidhip_ucell ...), before any device is touched
-int check_scorer_call(const Call& c) {
-  if (c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = c.remove_log2 > 0 ? 1 : 0;
-  PH_REQUIRE(c.method >= 3 && c.method <= 6, "sharded scorer: bad method %d", c.method);
-  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
-  if (c.method == 3) PH_REQUIRE(c.rmax > 0, "ucell_multi: rmax must be positive");
-  if (c.method == 4) PH_REQUIRE(c.auc_max_rank > 0, "aucell_multi: aucMaxRank must be positive");
-  if (c.method == 6) {
-    PH_REQUIRE(c.rowtf == 0 || c.rowtf == 1, "Error: unknown row transform %d", c.rowtf);              // R/plaid.R:348
-    PH_REQUIRE(c.rowtf == 0, "gsva_multi: rowtf = \"ecdf\" ranks all samples of a gene together and is not sharded by "
-                             "sample; score it on one device (plaidhip_gsva / plaidhip_gsva_csc)");
-  }
-  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "null X");
-  PH_REQUIRE(c.S_out != nullptr, "null S_out");
-  if (c.method == 3) PH_REQUIRE(c.k_full != nullptr, "ucell_multi: null k_full");
-  if (c.Xp != nullptr) {
-    PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
-    PH_REQUIRE(c.Xp[c.n] == 0 || c.Xi != nullptr, "null Xi");
-    // (as plaidhip_gsva_csc: the row view's buffers hold at most g x n values)
-    if (c.method == 6)
-      PH_REQUIRE((int64_t)c.Xp[c.n] <= (int64_t)c.g * c.n, "gsva_multi: %d stored values in a %d x %d matrix (repeated row "
-                 "indices?)", c.Xp[c.n], c.g, c.n);
-  }
-  return PLAIDHIP_OK;
-}
 
 Call scorer_call(int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                  const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) {
   return Call{method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, S_out};
 }
 
-// checks, then the contexts of `devices`, then the sharded call
-int run_scorer_multi(const int* devices, int ndev, const Call& c) {
-  PH_TRY(check_scorer_call(c));
+// the argument checks of methods 3 - 6, before any device is touched.  multi: a plaidhip_*_multi entry, which refuses
+// rowtf = "ecdf" whatever the device count; the others take it on one shard
+int check_scorer_call(const Call& c, int ndev, bool multi) {
+  if (c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = c.remove_log2 > 0 ? 1 : 0;
+  PH_REQUIRE(c.method >= 3 && c.method <= 6, "scorer: bad method %d", c.method);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  if (c.method == 3) PH_REQUIRE(c.rmax > 0, "ucell: rmax must be positive");
+  if (c.method == 4) PH_REQUIRE(c.auc_max_rank > 0, "aucell: aucMaxRank must be positive");
+  if (c.method == 6) {
+    PH_REQUIRE(c.rowtf == 0 || c.rowtf == 1, "Error: unknown row transform %d", c.rowtf);              // R/plaid.R:348
+    PH_REQUIRE(c.rowtf == 0 || (!multi && ndev == 1), "gsva: rowtf = \"ecdf\" ranks all samples of a gene together and is "
+               "not sharded by sample; score it on one device (plaidhip_gsva / plaidhip_gsva_csc)");
+  }
   if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_call(ctxs.data(), ndev, c);
+  PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "null X");
+  PH_REQUIRE(c.S_out != nullptr, "null S_out");
+  if (c.method == 3) PH_REQUIRE(c.k_full != nullptr, "ucell: null k_full");
+  if (c.Xp != nullptr) {
+    PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
+    PH_REQUIRE(c.Xp[c.n] == 0 || c.Xi != nullptr, "null Xi");
+    // (the ranks of the rows' stored values use a g x n buffer as scratch: a column repeating a row index could pass it)
+    if (c.method == 6)
+      PH_REQUIRE((int64_t)c.Xp[c.n] <= (int64_t)c.g * c.n, "gsva: %d stored values in a %d x %d matrix (repeated row "
+                 "indices?)", c.Xp[c.n], c.g, c.n);
+  }
+  return PLAIDHIP_OK;
 }
 
-Call plaid_test_call(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* y,
-                     const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests, int metap_method,
-                     double* out) {
-  Call c{7, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, nullptr};
-  c.y = y;
-  c.gsetX = gsetX;
-  c.tests = tests;
-  c.metap_method = metap_method;
-  c.out = out;
-  return c;
-}
-
-// the argument checks of plaidhip_plaid_test / plaidhip_plaid_test_csc, their messages, and the device list's, before any
-// device is touched; counts the groups of y into c.n0 / c.n1
-int check_plaid_test_call(const int* devices, int ndev, Call& c) {
-  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
-  if (devices != nullptr)
-    for (int k = 0; k < ndev; ++k)
-      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+// plaid.test's argument checks and their messages, before any device is touched; counts the groups of y into c.n0 / c.n1
+int check_plaid_test_call(Call& c) {
   PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
   PH_REQUIRE(c.m == 0 || c.out, "plaid_test: null out");
   PH_REQUIRE(c.n == 0 || ((c.Xp != nullptr || c.X != nullptr) && c.y != nullptr), "plaid_test: null X / y");
@@ -1928,43 +1769,25 @@ int check_plaid_test_call(const int* devices, int ndev, Call& c) {
   return PLAIDHIP_OK;
 }
 
+Call plaid_test_call(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* y,
+                     const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests, int metap_method,
+                     double* out) {
+  Call c{7, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, nullptr};
+  c.y = y;
+  c.gsetX = gsetX;
+  c.tests = tests;
+  c.metap_method = metap_method;
+  c.out = out;
+  return c;
+}
+
 }  // namespace
 
-extern "C" {
+namespace plaidhip {
 
-// Test hook (not part of include/plaidhip.h): the multi-device engine with `nshards` contexts on ONE device -- worker
-// threads, rendezvous, cross-shard scalars and the failure path are what a 1-GPU box can exercise of plaidhip_*_multi.
-// method 0 plaid, 1 sing, 2 ssgsea; fail_shard >= 0: that shard fails in its crossprod phase (the call must return an
-// error, not hang).
-int plaidhip_debug_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
-                                         const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
-                                         const int32_t* Gi, int32_t m, int stat, int normalize, double alpha, double* S_out) try {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_sharded: nshards = %d", nshards);
-  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
-    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
-    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
-  }
-  if (rc == PLAIDHIP_OK)
-    rc = run_sharded(ctxs.data(), nshards, method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, stat, normalize, alpha, S_out);
-  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* c : ctxs)
-    if (c) plaidhip_finalize(c);
-  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
-  return rc;
-} catch (...) { return plaidhip::on_exception(); }
-
-// Test hook (not part of include/plaidhip.h): plaidhip_{ucell,aucell,scse,gsva}_multi's engine with `nshards` contexts on
-// ONE device.  method 3 ucell (k_full, rmax), 4 aucell (auc_max_rank), 5 scse (remove_log2, score_mean, removed_log2),
-// 6 gsva (tau, rowtf); the parameters a method does not take are ignored.  fail_shard >= 0: that shard fails in its
-// crossprod phase.
-int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
-                                                const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                                                const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full,
-                                                double rmax, double auc_max_rank, int remove_log2, int score_mean, double tau,
-                                                int rowtf, double* S_out, int* removed_log2) try {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_scorer_sharded: nshards = %d", nshards);
+int run_scorer(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full, double rmax,
+               double auc_max_rank, int remove_log2, int score_mean, double tau, int rowtf, double* S_out, int* removed_log2) {
   Call c = scorer_call(method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
   c.k_full = k_full;
   c.rmax = rmax;
@@ -1974,76 +1797,134 @@ int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fai
   c.tau = tau;
   c.rowtf = rowtf;
   c.removed_log2 = removed_log2;
-  PH_TRY(check_scorer_call(c));
+  PH_TRY(check_contexts(ctxs, ndev));
+  PH_TRY(check_scorer_call(c, ndev, /*multi=*/false));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  return run_call(ctxs, ndev, c);
+}
+
+int run_plaid_test(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                   int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                   int metap_method, double* out) {
+  Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
+  PH_TRY(check_contexts(ctxs, ndev));
+  PH_TRY(check_plaid_test_call(c));
+  if (m == 0) return PLAIDHIP_OK;
+  return run_call(ctxs, ndev, c);
+}
+
+}  // namespace plaidhip
+
+// ---- multi-device entry points (include/plaidhip.h) ---------------------------------------------------------------------
+namespace {
+
+std::mutex g_multi_mu;
+std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
+int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
+
+// the device list's own checks, which touch no device (multi_contexts repeats them against the device count)
+int check_devices(const int* devices, int ndev) {
+  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
+  if (devices != nullptr)
+    for (int k = 0; k < ndev; ++k)
+      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  return PLAIDHIP_OK;
+}
+
+int multi_contexts(const int* devices, int ndev, std::vector<plaidhip_ctx*>& out) {
+  PH_TRY(check_devices(devices, ndev));
+  int count = 0;
+  PH_TRY(plaidhip_device_count(&count));
+  std::lock_guard<std::mutex> lk(g_multi_mu);
+  if ((int)g_multi_ctx.size() < count) g_multi_ctx.resize((size_t)count, nullptr);
+  out.clear();
+  for (int k = 0; k < ndev; ++k) {
+    const int d = devices ? devices[k] : k;
+    PH_REQUIRE(d >= 0 && d < count, "multi: device %d out of range [0, %d)", d, count);
+    if (g_multi_ctx[(size_t)d] == nullptr) PH_TRY(plaidhip_init(d, nullptr, &g_multi_ctx[(size_t)d]));
+    g_multi_ctx[(size_t)d]->precision = g_multi_precision;
+    out.push_back(g_multi_ctx[(size_t)d]);
+  }
+  return PLAIDHIP_OK;
+}
+
+// checks, then the contexts of `devices`, then the sharded call
+int run_scorer_multi(const int* devices, int ndev, const Call& c) {
+  PH_TRY(check_scorer_call(c, ndev, /*multi=*/true));
+  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  std::vector<plaidhip_ctx*> ctxs;
+  PH_TRY(multi_contexts(devices, ndev, ctxs));
+  return run_call(ctxs.data(), ndev, c);
+}
+
+// The test hooks' engine: `nshards` contexts on ONE device -- worker threads, rendezvous, cross-shard scalars and the
+// failure path are what a 1-GPU box can exercise of plaidhip_*_multi.  fail_shard >= 0: that shard fails in its crossprod
+// phase (the call must return an error, not hang).  The error text of `call` outlives the contexts' release.
+int sharded_on_one_device(int device, int nshards, int fail_shard, const std::function<int(plaidhip_ctx* const*)>& call) {
+  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_sharded: nshards = %d", nshards);
   std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
   int rc = PLAIDHIP_OK;
   for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
     rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
     if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
   }
-  if (rc == PLAIDHIP_OK) rc = run_call(ctxs.data(), nshards, c);
+  if (rc == PLAIDHIP_OK) rc = call(ctxs.data());
   const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* cx : ctxs)
-    if (cx) plaidhip_finalize(cx);
+  for (plaidhip_ctx* c : ctxs)
+    if (c) plaidhip_finalize(c);
   if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Test hooks (not part of include/plaidhip.h): the engine behind the plaidhip_*_multi entry of the same name, through
+// sharded_on_one_device.  plaid / sing / ssgsea: method 0 plaid, 1 sing, 2 ssgsea.
+int plaidhip_debug_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
+                                         const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                                         const int32_t* Gi, int32_t m, int stat, int normalize, double alpha, double* S_out) try {
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_sharded(ctxs, nshards, method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, stat, normalize, alpha, S_out);
+  });
 } catch (...) { return plaidhip::on_exception(); }
 
-// Test hook (not part of include/plaidhip.h): plaidhip_plaid_test_multi's engine with `nshards` contexts on ONE device.
-// fail_shard >= 0: that shard fails in its crossprod / moments phase (the call must return an error, not hang).
+// method 3 ucell (k_full, rmax), 4 aucell (auc_max_rank), 5 scse (remove_log2, score_mean, removed_log2), 6 gsva (tau,
+// rowtf); the parameters a method does not take are ignored
+int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
+                                                const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full,
+                                                double rmax, double auc_max_rank, int remove_log2, int score_mean, double tau,
+                                                int rowtf, double* S_out, int* removed_log2) try {
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_scorer(ctxs, nshards, method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, k_full, rmax, auc_max_rank, remove_log2,
+                      score_mean, tau, rowtf, S_out, removed_log2);
+  });
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_debug_plaid_test_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
                                                     const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                                                     const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
                                                     const double* gsetX, int tests, int metap_method, double* out) try {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_plaid_test_sharded: nshards = %d", nshards);
-  Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
-  PH_TRY(check_plaid_test_call(nullptr, nshards, c));
-  if (m == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
-    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
-    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
-  }
-  if (rc == PLAIDHIP_OK) rc = run_call(ctxs.data(), nshards, c);
-  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* cx : ctxs)
-    if (cx) plaidhip_finalize(cx);
-  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
-  return rc;
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_plaid_test(ctxs, nshards, Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
+  });
 } catch (...) { return plaidhip::on_exception(); }
 
-// Test hook (not part of include/plaidhip.h): plaidhip_ssgsea_exact_multi's engine with `nshards` contexts on ONE device.
-// fail_shard >= 0: that shard fails in its crossprod phase (the call must return an error, not hang).
 int plaidhip_debug_ssgsea_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
                                                       const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                                                       const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
                                                       int norm, double* S_out) try {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_ssgsea_exact_sharded: nshards = %d", nshards);
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
-    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
-    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
-  }
-  if (rc == PLAIDHIP_OK) rc = run_ssgsea_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
-  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* cx : ctxs)
-    if (cx) plaidhip_finalize(cx);
-  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
-  return rc;
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_ssgsea_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
+  });
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                                 int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
                                 int norm, double* S_out) try {
-  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
-  if (devices != nullptr)
-    for (int k = 0; k < ndev; ++k)
-      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_devices(devices, ndev));
   PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   std::vector<plaidhip_ctx*> ctxs;
@@ -2051,37 +1932,19 @@ int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp,
   return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
 } catch (...) { return plaidhip::on_exception(); }
 
-// Test hook (not part of include/plaidhip.h): plaidhip_ssgsea_exact_ks_multi's engine with `nshards` contexts on ONE device.
-// fail_shard >= 0: that shard fails in its crossprod phase (the call must return an error, not hang).
 int plaidhip_debug_ssgsea_exact_ks_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
                                                       const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                                                       const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
                                                       int norm, double* S_out) try {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_ssgsea_exact_ks_sharded: nshards = %d", nshards);
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  PH_TRY(check_gsea_ks_genes(g));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
-    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
-    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
-  }
-  if (rc == PLAIDHIP_OK) rc = run_ssgsea_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
-  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* cx : ctxs)
-    if (cx) plaidhip_finalize(cx);
-  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
-  return rc;
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_ssgsea_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
+  });
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                                 int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
                                 int norm, double* S_out) try {
-  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
-  if (devices != nullptr)
-    for (int k = 0; k < ndev; ++k)
-      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_devices(devices, ndev));
   PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
   PH_TRY(check_gsea_ks_genes(g));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
@@ -2090,36 +1953,19 @@ int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* 
   return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
 } catch (...) { return plaidhip::on_exception(); }
 
-// Test hook (not part of include/plaidhip.h): plaidhip_gsva_exact_multi's engine with `nshards` contexts on ONE device.
-// fail_shard >= 0: that shard fails in its walk phase (the call must return an error, not hang).
 int plaidhip_debug_gsva_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
                                                     const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                                                     const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
                                                     int max_diff, double* S_out) try {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_gsva_exact_sharded: nshards = %d", nshards);
-  PH_TRY(check_gsva_exact_args(nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
-    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
-    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
-  }
-  if (rc == PLAIDHIP_OK) rc = run_gsva_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
-  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* cx : ctxs)
-    if (cx) plaidhip_finalize(cx);
-  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
-  return rc;
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_gsva_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
+  });
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
                               int max_diff, double* S_out) try {
-  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
-  if (devices != nullptr)
-    for (int k = 0; k < ndev; ++k)
-      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_devices(devices, ndev));
   PH_TRY(check_gsva_exact_args(ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   std::vector<plaidhip_ctx*> ctxs;
@@ -2127,29 +1973,15 @@ int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, c
   return run_gsva_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
 } catch (...) { return plaidhip::on_exception(); }
 
-// Test hook (not part of include/plaidhip.h): plaidhip_sing_exact_multi's engine with `nshards` contexts on ONE device.
-// fail_shard >= 0: that shard fails in its crossprod phase (the call must return an error, not hang).
 int plaidhip_debug_sing_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp, const int32_t* Xi,
                                                     const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
                                                     const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m,
                                                     int center, double* total, double* up, double* down, double* total_disp,
                                                     double* up_disp, double* down_disp) try {
   double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_sing_exact_sharded: nshards = %d", nshards);
-  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
-  int rc = PLAIDHIP_OK;
-  for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
-    rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
-    if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
-  }
-  if (rc == PLAIDHIP_OK) rc = run_sing_exact(ctxs.data(), nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
-  const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* cx : ctxs)
-    if (cx) plaidhip_finalize(cx);
-  if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
-  return rc;
+  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
+    return run_sing_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
+  });
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
@@ -2157,10 +1989,7 @@ int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, c
                               int32_t m, int center, double* total, double* up, double* down, double* total_disp,
                               double* up_disp, double* down_disp) try {
   double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
-  PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
-  if (devices != nullptr)
-    for (int k = 0; k < ndev; ++k)
-      for (int q = 0; q < k; ++q) PH_REQUIRE(devices[q] != devices[k], "multi: device %d listed twice", devices[k]);
+  PH_TRY(check_devices(devices, ndev));
   PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
   std::vector<plaidhip_ctx*> ctxs;
@@ -2250,7 +2079,8 @@ int plaidhip_plaid_test_multi(const int* devices, int ndev, const int32_t* Xp, c
                               int32_t g, int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
                               const double* gsetX, int tests, int metap_method, double* out) try {
   Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
-  PH_TRY(check_plaid_test_call(devices, ndev, c));
+  PH_TRY(check_devices(devices, ndev));
+  PH_TRY(check_plaid_test_call(c));
   if (m == 0) return PLAIDHIP_OK;
   std::vector<plaidhip_ctx*> ctxs;
   PH_TRY(multi_contexts(devices, ndev, ctxs));

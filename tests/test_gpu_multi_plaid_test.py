@@ -1,10 +1,11 @@
 """plaid.test over several devices (plaidhip_plaid_test_multi, multi.cpp).
 
 A 1-GPU box reaches the multi-device engine with ndev >= 2 through a test hook that runs it with `nshards` contexts on
-device 0.  Dense X must equal the single-device context entry bit for bit, NaNs included, for every sharding, every
-`tests` mask, both meta-p methods and with gsetX given or computed (the shards are cut at 128-column blocks and every
-sum over the samples is chained from shard to shard in the one-device order).  A dgCMatrix adds its sums in another
-order: it must agree with plaidhip_plaid_test_csc and with the oracle within the suite's plaid.test tolerances.
+device 0.  plaidhip_plaid_test / plaidhip_plaid_test_csc are the same engine with one shard, so the comparisons below
+say: every sharding equals the one-shard run.  Dense X bit for bit, NaNs included, for every `tests` mask, both meta-p
+methods and with gsetX given or computed (the shards are cut at 128-column blocks and every sum over the samples is
+chained from shard to shard in the one-shard order).  A dgCMatrix adds its shards' sums in shard order: it must agree
+with the one-shard run and with the oracle within the suite's plaid.test tolerances.
 """
 import os
 

@@ -1,9 +1,10 @@
 """replaid.ucell / aucell / scse / gsva over several devices (plaidhip_*_multi, multi.cpp).
 
 A 1-GPU box reaches the multi-device engine with ndev >= 2 through a test hook that runs it with `nshards` contexts on
-device 0.  Dense X must equal the single-device context entry bit for bit for every sharding (the gsva row moments are
-chained across the shards in the one-device order); a dgCMatrix must agree with it and with the oracle within the
-suite's tolerance, and `removed_log2` must be the context entry's.
+device 0.  The context entries (plaidhip_ucell ... plaidhip_gsva_csc) are the same engine with one shard, so the
+comparisons below say: every sharding equals the one-shard run.  Dense X bit for bit (the gsva row moments are chained
+across the shards in the one-shard order); a dgCMatrix must agree with the one-shard run and with the oracle within the
+suite's tolerance, and `removed_log2` must be the one-shard run's.
 """
 import ctypes as C
 import os

@@ -3,14 +3,15 @@
 References and bounds: tests/helpers/exact_stats.py (group_moments, sum_bound, mean_bound, ssd_bound, welch_interval).
   a. the dense device entries dev_row_group_sums / dev_row_group_ssd at the kernels' seams (256 rows per workgroup, 128
      columns per partial, ld > rows, one row, one column), with sentinels around every buffer
-  b. the Welch route of the context entry: gsetFC = m1 - m0 at the means' bound, p.lm by the interval check, the
-     degenerate cases pinned exactly
+  b. the Welch route of the context entry (the sharded engine with one shard): gsetFC = m1 - m0 at the means' bound, p.lm
+     by the interval check, the degenerate cases pinned exactly
   c. the gene fold changes through one-gene sets (tests = 1: gsetFC[j] = fc_j / (1 + 1e-8)), dense and dgCMatrix,
      including a row longer than kLongRow (the 256-thread CSR row path) and two identical rows with identical bits
   d. p.one and p.two from the device crossprod (tests = 3) by the interval check; no set may be "not separable"
      (tests/test_exact_stats_ref.py asserts that from the reference alone, for the same seeds and shapes)
   e. the sharded engine at odd numbers of sets -- the first cases that run row_group_shifted_partials_kernel<*, false> and
-     its lone last row: bit-identical to the one-device entry, and within the exact bounds when gsetX is given
+     its lone last row: every sharding bit-identical to the one-shard run (the context entry), and within the exact bounds
+     when gsetX is given
 In (a) the device entry returns SUMS (reduce_blocks_kernel with scale 1); the means are formed by the test as
 sums * fl(1 / n_k), the expression plaid_amd/sharded.py uses on these entries, and fed back to dev_row_group_ssd.  The
 kernel's own scale0 / scale1 path (the c = 3 of mean_bound) runs in (b), (c) and (e), through plaid_test's gsetFC.
