@@ -9,7 +9,7 @@
 #include <limits>
 #include <vector>
 
-#include "common.h"
+#include "call.h"
 
 namespace plaidhip {
 
@@ -810,20 +810,18 @@ int plaidhip_dev_shift_columns_cast_f32(plaidhip_ctx* ctx, const void* S, int64_
 int plaidhip_plaid_dense(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n,
                          const int32_t* Gp, const int32_t* Gi, int32_t m, int stat, int normalize,
                          double* S_out) try {
-  PH_CTX(ctx);
   PH_REQUIRE(stat == PLAIDHIP_STAT_MEAN || stat == PLAIDHIP_STAT_SUM, "plaid_dense: bad stat %d", stat);
   PH_REQUIRE(n == 0 || (X && S_out), "plaid_dense: null X/S_out");
   // one shard on this context: pipelined upload, crossprod per column panel, normalize_medians, download (multi.cpp)
-  return run_sharded(&ctx, 1, 0, nullptr, nullptr, X, g, n, Gp, Gi, m, stat, normalize, 0.0, S_out);
+  return dispatch(on_context(ctx), plaid_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, stat, normalize, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_plaid_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx,
                        int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                        int stat, int normalize, double* S_out) try {
-  PH_CTX(ctx);
   PH_REQUIRE(stat == PLAIDHIP_STAT_MEAN || stat == PLAIDHIP_STAT_SUM, "plaid_csc: bad stat %d", stat);
   PH_REQUIRE(Xp != nullptr && (n == 0 || S_out), "plaid_csc: null Xp/S_out");
-  return run_sharded(&ctx, 1, 0, Xp, Xi, Xx, g, n, Gp, Gi, m, stat, normalize, 0.0, S_out);
+  return dispatch(on_context(ctx), plaid_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, stat, normalize, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 // chunked_crossprod with a general sparse x: upload the slots, one launch, download (host pointers)
@@ -984,9 +982,7 @@ int plaidhip_colranks_csc_dense(plaidhip_ctx* ctx, const int32_t* Xp, const int3
 
 int plaidhip_sing_dense(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) try {
-  PH_CTX(ctx);
-  // rX = colranks(X, ties.method="min") / nrow(X) - 0.5 ; plaid(rX, normalize=FALSE)  (R/plaid.R:215-217)
-  return run_sharded(&ctx, 1, 1, nullptr, nullptr, X, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 0, 0.0, S_out);
+  return dispatch(on_context(ctx), sing_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.sing for a dgCMatrix X: colranks(X, ties.method = "min") ranks the zeros too (sparse branch without keep.zero,
@@ -996,79 +992,61 @@ int plaidhip_sing_dense(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
 // the PCIe link sees a dense X.
 int plaidhip_sing_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
                       const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) try {
-  PH_CTX(ctx);
   PH_REQUIRE(Xp != nullptr, "sing_csc: null Xp");
-  return run_sharded(&ctx, 1, 1, Xp, Xi, Xx, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 0, 0.0, S_out);
+  return dispatch(on_context(ctx), sing_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_ssgsea_dense(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
                           double* S_out) try {
-  PH_CTX(ctx);
-  // rX = colranks(X, ties="average")^(1+alpha) ; rX/max(rX) - 0.5 ; plaid(mean, normalize=TRUE)  (R/plaid.R:245-253)
-  return run_sharded(&ctx, 1, 2, nullptr, nullptr, X, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, alpha, S_out);
+  return dispatch(on_context(ctx), ssgsea_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, alpha, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_ssgsea_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx,
                         int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                         double alpha, double* S_out) try {
-  PH_CTX(ctx);
   PH_REQUIRE(Xp != nullptr, "ssgsea_csc: null Xp");
   // sparse branch: ranks of the non-zeros only, zeros stay 0 (R/plaid.R:600-601, 631-650); the "- 0.5" of
   // R/plaid.R:251 applies to the zeros too, which the (alpha, beta) epilogue covers
-  return run_sharded(&ctx, 1, 2, Xp, Xi, Xx, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, alpha, S_out);
+  return dispatch(on_context(ctx), ssgsea_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, alpha, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.ssgsea.exact: the one-device form of the sharded engine (multi.cpp: ssgsea_exact_worker)
 int plaidhip_ssgsea_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
                           double* S_out) try {
-  PH_REQUIRE(ctx != nullptr, "null plaidhip_ctx");
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  PH_HIP(hipSetDevice(ctx->device));
-  return run_ssgsea_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
+  return dispatch(on_context(ctx), ssgsea_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, scale, norm, S_out, 1));
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.ssgsea.exact(single = FALSE): the same engine with the walk kernel of kernels_ks.hip
 int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                              const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
                              double* S_out) try {
-  PH_REQUIRE(ctx != nullptr, "null plaidhip_ctx");
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  PH_TRY(check_gsea_ks_genes(g));
-  PH_HIP(hipSetDevice(ctx->device));
-  return run_ssgsea_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
+  return dispatch(on_context(ctx), ssgsea_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, scale, norm, S_out, 0));
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"
 
 // ---- replaid.ucell / aucell / scse / gsva and plaid.test: the one-shard case of the sharded engine ------------------------
-// (multi.cpp: scorer_worker, plaid_test_worker; run_scorer / run_plaid_test check the arguments first)
+// (multi.cpp: scorer_worker, plaid_test_worker; dispatch checks the arguments first)
 extern "C" {
 
 int plaidhip_ucell(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                    int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                    const double* k_full, double rmax, double* S_out) try {
-  PH_CTX(ctx);
-  // pmin(max(rX) - rX, rmax + 1) of the average ranks, plaid(), 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:278-280)
-  return run_scorer(&ctx, 1, 3, Xp, Xi, X_or_x, g, n, Gp, Gi, m, k_full, rmax, 0.0, -1, 0, 0.0, 0, S_out, nullptr);
+  return dispatch(on_context(ctx), ucell_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, k_full, rmax, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_aucell(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                     int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                     double auc_max_rank, double* S_out) try {
-  PH_CTX(ctx);
-  // pmax(aucMaxRank - (max(rX) - rX), 0) of the average ranks, plaid()   (R/plaid.R:306-307)
-  return run_scorer(&ctx, 1, 4, Xp, Xi, X_or_x, g, n, Gp, Gi, m, nullptr, 0.0, auc_max_rank, -1, 0, 0.0, 0, S_out, nullptr);
+  return dispatch(on_context(ctx), aucell_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, auc_max_rank, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_scse(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                   int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                   int remove_log2, int score_mean, double* S_out, int* removed_log2) try {
-  PH_CTX(ctx);
-  // removeLog2 (< 0: decided from min / max of X, R/plaid.R:160-161), sX / (colMeans|X| + 1e-8) or its sum form (:176-182)
-  return run_scorer(&ctx, 1, 5, Xp, Xi, X_or_x, g, n, Gp, Gi, m, nullptr, 0.0, 0.0, remove_log2, score_mean, 0.0, 0, S_out,
-                    removed_log2);
+  return dispatch(on_context(ctx), scse_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, remove_log2, score_mean, S_out, removed_log2));
 } catch (...) { return plaidhip::on_exception(); }
 
 // Row-wise two-group sums / sums of squared deviations on device pointers: the pieces of plaid.test that a sample-sharded
@@ -1144,17 +1122,14 @@ int plaidhip_plaid_test_finish(int32_t g, int32_t m, const int32_t* Gp, const do
 int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* y,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
                         int metap_method, double* out) try {
-  PH_CTX(ctx);
-  return run_plaid_test(&ctx, 1, nullptr, nullptr, X, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
+  return dispatch(on_context(ctx), plaid_test_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.gsva.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, method 9)
+// replaid.gsva.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, kGsvaExact)
 int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
                         double* S_out) try {
-  PH_TRY(check_gsva_exact_args(1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
-  PH_CTX(ctx);
-  return run_gsva_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
+  return dispatch(on_context(ctx), gsva_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tau, rowtf, max_diff, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 // GSVA's Gaussian kernel CDF estimate alone (the row transform "gauss" of replaid.gsva.exact): V, g x n
@@ -1209,39 +1184,32 @@ int plaidhip_debug_gsva_kcdf_slow_terms(unsigned long long* out) try {
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.sing.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, method 10)
+// replaid.sing.exact: the one-device form of the sharded engine (multi.cpp: sing_exact_worker)
 int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                         const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
                         double* total, double* up, double* down, double* total_disp, double* up_disp, double* down_disp) try {
-  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
-  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
-  PH_CTX(ctx);
-  return run_sing_exact(&ctx, 1, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
+  return dispatch(on_context(ctx), sing_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, center, total, up, down, total_disp, up_disp,
+                                                   down_disp));
 } catch (...) { return plaidhip::on_exception(); }
 
-// zX = (X - rowMeans(X)) / (1e-8 + rowSds(X)) ("z", R/plaid.R:341-343) or t(apply(X, 1, function(x) ecdf(x)(x))) ("ecdf",
-// :346), the signed average ranks of its columns, plaid()
 int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi,
                   int32_t m, double tau, int rowtf, double* S_out) try {
-  PH_CTX(ctx);
-  return run_scorer(&ctx, 1, 6, nullptr, nullptr, X, g, n, Gp, Gi, m, nullptr, 0.0, 0.0, -1, 0, tau, rowtf, S_out, nullptr);
+  return dispatch(on_context(ctx), gsva_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, tau, rowtf, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 // dgCMatrix input for replaid.gsva and plaid.test: the slots go to the device as they are, where their row view
 // (kernels_csr.hip) gives the rows' moments, ecdf counts and group sums; no dense X on the host or the link
 int plaidhip_gsva_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
                       const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out) try {
-  PH_CTX(ctx);
   PH_REQUIRE(Xp != nullptr, "gsva_csc: null Xp");
-  return run_scorer(&ctx, 1, 6, Xp, Xi, Xx, g, n, Gp, Gi, m, nullptr, 0.0, 0.0, -1, 0, tau, rowtf, S_out, nullptr);
+  return dispatch(on_context(ctx), gsva_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, tau, rowtf, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_plaid_test_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
                             const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX,
                             int tests, int metap_method, double* out) try {
-  PH_CTX(ctx);
   PH_REQUIRE(Xp != nullptr, "plaid_test: null X / y");
-  return run_plaid_test(&ctx, 1, Xp, Xi, Xx, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
+  return dispatch(on_context(ctx), plaid_test_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

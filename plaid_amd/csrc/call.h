@@ -1,0 +1,196 @@
+// One host-level scorer call: what it computes (Call), where it runs (Target), and the one way in (dispatch, multi.cpp).
+// Host only: api.cpp and multi.cpp.
+#pragma once
+
+#include "common.h"
+
+namespace plaidhip {
+
+// the ordinals are what the test hooks plaidhip_debug_sharded_on_one_device / _scorer_sharded_on_one_device take
+enum Method : int {
+  kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
+  kGsvaExact = 9, kSingExact = 10
+};
+inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
+inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
+
+// the matrix and the aligned set collection every scorer takes: X dense (Xp == nullptr) or the slots of a dgCMatrix
+struct Operands {
+  const int32_t* Xp;
+  const int32_t* Xi;
+  const double* X;   // dense values or CSC @x
+  int32_t g, n;
+  const int32_t* Gp;
+  const int32_t* Gi;
+  int32_t m;
+};
+
+struct Call : Operands {
+  int method = kPlaid;
+  int stat = PLAIDHIP_STAT_MEAN, normalize = 1;
+  double alpha = 0.0;
+  double* S_out = nullptr;
+  const double* k_full = nullptr;   // ucell: set sizes
+  double rmax = 0.0;                // ucell
+  double auc_max_rank = 0.0;        // aucell
+  int remove_log2 = -1;             // scse: < 0 decided from min / max of X
+  int score_mean = 0;               // scse
+  double tau = 0.0;                 // gsva
+  int rowtf = 0;                    // gsva: 0 z, 1 ecdf (one shard); gsva.exact: 0 z, 1 ecdf (one shard), 2 none, 3 gauss
+                                    // (every shard takes all of X)
+  int max_diff = 1;                 // gsva.exact
+  int* removed_log2 = nullptr;      // scse output (may be null)
+  int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
+  int single = 1;                   // ssgsea.exact: 1 the walk's sum (closed form), 0 its value of largest magnitude (kernels_ks.hip)
+  // plaid.test: the arguments of plaidhip_plaid_test and the group sizes of y (counted by check_call)
+  const int32_t* y = nullptr;
+  const double* gsetX = nullptr;
+  int tests = 0, metap_method = 0;
+  int64_t n0 = 0, n1 = 0;
+  double* out = nullptr;
+  // sing.exact: the down sets (null: none), center, and the six nullable results (total, up, down score; total, up, down
+  // dispersion)
+  const int32_t* Dp = nullptr;
+  const int32_t* Di = nullptr;
+  int center = 1;
+  double* sx_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
+// ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
+inline Call make_call(int method, const Operands& x, double* S_out) {
+  Call c;
+  static_cast<Operands&>(c) = x;
+  c.method = method;
+  c.S_out = S_out;
+  return c;
+}
+// plaid / sing / ssgsea by ordinal: the hook's form, and its alone
+inline Call rank_sum_call(int method, const Operands& x, int stat, int normalize, double alpha, double* S_out) {
+  Call c = make_call(method, x, S_out);
+  c.stat = stat;
+  c.normalize = normalize;
+  c.alpha = alpha;
+  return c;
+}
+inline Call plaid_call(const Operands& x, int stat, int normalize, double* S_out) {
+  Call c = make_call(kPlaid, x, S_out);
+  c.stat = stat;
+  c.normalize = normalize;
+  return c;
+}
+// rX = colranks(X, ties.method="min") / nrow(X) - 0.5 ; plaid(rX, normalize=FALSE)  (R/plaid.R:215-217)
+inline Call sing_call(const Operands& x, double* S_out) {
+  Call c = make_call(kSing, x, S_out);
+  c.normalize = 0;
+  return c;
+}
+// rX = colranks(X, ties="average")^(1+alpha) ; rX/max(rX) - 0.5 ; plaid(mean, normalize=TRUE)  (R/plaid.R:245-253)
+inline Call ssgsea_call(const Operands& x, double alpha, double* S_out) {
+  Call c = make_call(kSsgsea, x, S_out);
+  c.alpha = alpha;
+  return c;
+}
+// ucell / aucell / scse / gsva by ordinal: the hook's form, and its alone; the parameters a method does not take are ignored
+inline Call scorer_call(int method, const Operands& x, const double* k_full, double rmax, double auc_max_rank, int remove_log2,
+                        int score_mean, double tau, int rowtf, double* S_out, int* removed_log2) {
+  Call c = make_call(method, x, S_out);
+  c.k_full = k_full;
+  c.rmax = rmax;
+  c.auc_max_rank = auc_max_rank;
+  c.remove_log2 = remove_log2;
+  c.score_mean = score_mean;
+  c.tau = tau;
+  c.rowtf = rowtf;
+  c.removed_log2 = removed_log2;
+  return c;
+}
+// pmin(max(rX) - rX, rmax + 1) of the average ranks, plaid(), 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:278-280)
+inline Call ucell_call(const Operands& x, const double* k_full, double rmax, double* S_out) {
+  Call c = make_call(kUcell, x, S_out);
+  c.k_full = k_full;
+  c.rmax = rmax;
+  return c;
+}
+// pmax(aucMaxRank - (max(rX) - rX), 0) of the average ranks, plaid()   (R/plaid.R:306-307)
+inline Call aucell_call(const Operands& x, double auc_max_rank, double* S_out) {
+  Call c = make_call(kAucell, x, S_out);
+  c.auc_max_rank = auc_max_rank;
+  return c;
+}
+// removeLog2 (< 0: decided from min / max of X, R/plaid.R:160-161), sX / (colMeans|X| + 1e-8) or its sum form (:176-182)
+inline Call scse_call(const Operands& x, int remove_log2, int score_mean, double* S_out, int* removed_log2) {
+  Call c = make_call(kScse, x, S_out);
+  c.remove_log2 = remove_log2;
+  c.score_mean = score_mean;
+  c.removed_log2 = removed_log2;
+  return c;
+}
+// zX = (X - rowMeans(X)) / (1e-8 + rowSds(X)) ("z", R/plaid.R:341-343) or t(apply(X, 1, function(x) ecdf(x)(x))) ("ecdf",
+// :346), the signed average ranks of its columns, plaid()
+inline Call gsva_call(const Operands& x, double tau, int rowtf, double* S_out) {
+  Call c = make_call(kGsva, x, S_out);
+  c.tau = tau;
+  c.rowtf = rowtf;
+  return c;
+}
+inline Call plaid_test_call(const Operands& x, const int32_t* y, const double* gsetX, int tests, int metap_method, double* out) {
+  Call c = make_call(kPlaidTest, x, nullptr);
+  c.y = y;
+  c.gsetX = gsetX;
+  c.tests = tests;
+  c.metap_method = metap_method;
+  c.out = out;
+  return c;
+}
+inline Call ssgsea_exact_call(const Operands& x, double alpha, int scale, int norm, double* S_out, int single) {
+  Call c = make_call(kSsgseaExact, x, S_out);
+  c.stat = PLAIDHIP_STAT_SUM;
+  c.normalize = norm ? 1 : 0;
+  c.alpha = alpha;
+  c.scale = scale ? 1 : 0;
+  c.single = single ? 1 : 0;
+  return c;
+}
+inline Call gsva_exact_call(const Operands& x, double tau, int rowtf, int max_diff, double* S_out) {
+  Call c = make_call(kGsvaExact, x, S_out);
+  c.stat = PLAIDHIP_STAT_SUM;
+  c.normalize = 0;
+  c.tau = tau;
+  c.rowtf = rowtf;
+  c.max_diff = max_diff ? 1 : 0;
+  return c;
+}
+inline Call sing_exact_call(const Operands& x, const int32_t* Dp, const int32_t* Di, int center, double* total, double* up,
+                            double* down, double* total_disp, double* up_disp, double* down_disp) {
+  Call c = make_call(kSingExact, x, nullptr);
+  c.stat = PLAIDHIP_STAT_SUM;
+  c.normalize = 0;
+  c.Dp = Dp;
+  c.Di = Di;
+  c.center = center ? 1 : 0;
+  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
+  for (int o = 0; o < 6; ++o) c.sx_out[o] = out[o];
+  return c;
+}
+
+// ---- where a call runs -------------------------------------------------------------------------------------------------
+struct Target {
+  enum Kind { kContext, kDevices, kHook } kind;
+  plaidhip_ctx* ctx;            // kContext: the caller's context (one shard)
+  const int* devices;           // kDevices: plaidhip_*_multi's list (null: the first ndev devices)
+  int device, ndev, fail_shard; // kHook: ndev contexts on `device`, shard fail_shard (>= 0) fails in its crossprod phase
+};
+inline Target on_context(plaidhip_ctx* ctx) { return Target{Target::kContext, ctx, nullptr, 0, 1, -1}; }
+inline Target on_devices(const int* devices, int ndev) { return Target{Target::kDevices, nullptr, devices, 0, ndev, -1}; }
+inline Target on_hook(int device, int nshards, int fail_shard) {
+  return Target{Target::kHook, nullptr, nullptr, device, nshards, fail_shard};
+}
+
+// The one way in (multi.cpp): the device list's (or the hook's) own checks, check_call, a null context, the empty result,
+// the contexts, run_call.  Nothing before the contexts touches a device.
+int dispatch(const Target& t, Call c);
+// the argument checks of every method, which touch no device.  multi: a plaidhip_*_multi entry, which refuses replaid.gsva's
+// rowtf = "ecdf" whatever the device count; the others take it on one shard.  Counts plaid.test's groups into c.n0 / c.n1.
+int check_call(Call& c, int ndev, bool multi);
+
+}  // namespace plaidhip

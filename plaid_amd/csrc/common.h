@@ -278,21 +278,6 @@ int acquire_geneset(plaidhip_ctx* ctx, int32_t g, int32_t m, const int32_t* Gp, 
 int check_host_csc(const int32_t* Xp, const int32_t* Xi, int32_t g, int32_t n);
 int check_host_common(const void* G_p, int32_t g, int32_t n, int32_t m);
 const char* last_error_cstr();
-// the sample-sharded host pipeline behind plaid / replaid.sing / replaid.ssgsea (multi.cpp): ndev contexts, one per
-// device; X dense (Xp == nullptr) or CSC; method 0 plaid, 1 sing, 2 ssgsea
-int run_sharded(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int stat, int normalize, double alpha,
-                double* S_out);
-// the same engine for replaid.ucell / aucell / scse / gsva (method 3 ucell: k_full, rmax; 4 aucell: auc_max_rank; 5 scse:
-// remove_log2, score_mean, removed_log2; 6 gsva: tau, rowtf -- "ecdf" on one context only; what a method does not take is
-// ignored) and for plaid.test, on ndev contexts (one: plaidhip_ucell ... plaidhip_plaid_test_csc); their argument checks
-// come first and touch no device
-int run_scorer(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full, double rmax,
-               double auc_max_rank, int remove_log2, int score_mean, double tau, int rowtf, double* S_out, int* removed_log2);
-int run_plaid_test(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                   int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
-                   int metap_method, double* out);
 // A result's way home into the caller's pageable buffer (multi.cpp).  R hands over FRESH memory (allocMatrix -> malloc ->
 // mmap): every page faults on its first write, inside the device-to-host copy -- 4.9 GB of scores took 309 ms instead of
 // 92 (tools/ubench/d2h_fresh.cpp).  prepare() asks for transparent huge pages on the range (madvise; a hint, ignored where
@@ -478,12 +463,7 @@ int launch_ssgsea_exact_epilogue(plaidhip_ctx* ctx, const double* A, const doubl
                                  int32_t n, const int32_t* kset, int64_t N, int scale, const uint32_t* colnan, double* part,
                                  double* range_out);
 int launch_ssgsea_exact_norm(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t m, int32_t n, double range);
-// multi.cpp: replaid.ssgsea.exact on ndev contexts (one: plaidhip_ssgsea_exact); its argument checks, which touch no device
-int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                     int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
-                     double* S_out, int single = 1);
-int check_ssgsea_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                            const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, const double* S_out);
+// multi.cpp: the walk kernel's row bound, which touches no device
 int check_gsea_ks_genes(int32_t g);   // single = FALSE: PLAIDHIP_EUNSUPPORTED above PLAIDHIP_GSEA_KS_MAX_GENES rows
 // kernels_ks.hip: replaid.ssgsea.exact(single = FALSE), the walk's value of largest magnitude (include/plaidhip.h:
 // plaidhip_ssgsea_exact_ks) from the operands above; Gp / Gi on the device; Wpos: ldq n doubles of scratch when alpha != 0
@@ -495,12 +475,6 @@ int launch_gsea_ks(plaidhip_ctx* ctx, const double* Q, const double* W, double* 
 // Q of the row-transformed columns; Gp / Gi on the device; T: g doubles of scratch for the weight table (tau != 0)
 int launch_gsva_ks(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* colnan, int32_t g, int32_t n,
                    const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int max_diff, double* T, double* S, int64_t lds);
-// multi.cpp: replaid.gsva.exact on ndev contexts (one: plaidhip_gsva_exact); its argument checks, which touch no device
-int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                   int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
-                   double* S_out);
-int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                          const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out);
 // kernels_sing.hip: replaid.sing.exact (include/plaidhip.h: plaidhip_sing_exact).  All stream-ordered.
 // colnan[c] = 1 for a column holding a NaN: dense X (Xp == nullptr, g rows, leading dimension ldx) or the stored values of
 // CSC columns (the longest max_col_nnz)
@@ -521,13 +495,6 @@ int launch_sing_add(plaidhip_ctx* ctx, const double* A, const double* B, double*
 // g > PLAIDHIP_GSEA_KS_MAX_GENES: PLAIDHIP_EUNSUPPORTED.
 int launch_sing_mad(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* Rpos, int64_t ldp, const uint32_t* colnan,
                     int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S, int64_t lds);
-// multi.cpp: replaid.sing.exact on ndev contexts (one: plaidhip_sing_exact); its argument checks, which touch no device.
-// out: total, up, down score, total, up, down dispersion, each nullable
-int run_sing_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                   int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
-                   double* const out[6]);
-int check_sing_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
-                          const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double* const out[6]);
 // kernels_kcdf.hip: GSVA's Gaussian kernel CDF estimate (include/plaidhip.h: plaidhip_gsva_kcdf).  V (g x (j1 - j0), leading
 // dimension ldv) <- the kernel sums of the test columns [j0, j1) of the dense device matrix X (g x n, leading dimension
 // ldx) over ALL n samples; H: g doubles of scratch (the bandwidths).  Stream-ordered.

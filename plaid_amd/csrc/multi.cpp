@@ -32,7 +32,7 @@
 
 #include <sys/mman.h>
 
-#include "common.h"
+#include "call.h"
 
 using namespace plaidhip;
 
@@ -301,52 +301,12 @@ struct Shared {
   bool es_nan = false;
 };
 
-struct Call {
-  int method;   // 0 plaid, 1 sing, 2 ssgsea, 3 ucell, 4 aucell, 5 scse, 6 gsva (rowtf z), 7 plaid.test, 8 ssgsea.exact,
-                // 9 gsva.exact, 10 sing.exact
-  const int32_t* Xp;
-  const int32_t* Xi;
-  const double* X;   // dense values or CSC @x
-  int32_t g, n;
-  const int32_t* Gp;
-  const int32_t* Gi;
-  int32_t m;
-  int stat, normalize;
-  double alpha;
-  double* S_out;
-  // methods 3 - 6: the parameters of plaidhip_ucell / aucell / scse / gsva
-  const double* k_full = nullptr;   // ucell: set sizes
-  double rmax = 0.0;                // ucell
-  double auc_max_rank = 0.0;        // aucell
-  int remove_log2 = -1;             // scse: < 0 decided from min / max of X
-  int score_mean = 0;               // scse
-  double tau = 0.0;                 // gsva
-  int rowtf = 0;                    // gsva: 0 z, 1 ecdf (one shard); gsva.exact: 0 z, 1 ecdf (one shard), 2 none, 3 gauss
-                                    // (every shard takes all of X)
-  int max_diff = 1;                 // gsva.exact
-  int* removed_log2 = nullptr;      // scse output (may be null)
-  int scale = 1;                    // ssgsea.exact (its norm is `normalize`)
-  int single = 1;                   // ssgsea.exact: 1 the walk's sum (closed form), 0 its value of largest magnitude (kernels_ks.hip)
-  // method 7, plaid.test: the arguments of plaidhip_plaid_test and the group sizes of y
-  const int32_t* y = nullptr;
-  const double* gsetX = nullptr;
-  int tests = 0, metap_method = 0;
-  int64_t n0 = 0, n1 = 0;
-  double* out = nullptr;
-  // method 10, sing.exact: the down sets (null: none), center, and the six nullable results (total, up, down score; total,
-  // up, down dispersion)
-  const int32_t* Dp = nullptr;
-  const int32_t* Di = nullptr;
-  int center = 1;
-  double* sx_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-};
-
 // columns [lo, lo + nloc) of shard k.  Dense replaid.gsva and plaid.test (dense or not: its score rows are chained too)
 // (and replaid.gsva.exact with its z transform) cut at multiples of kColBlock (kernels_stats.hip, 128 columns) so that their chained row reductions add the block
 // partials of the one-device call in the same order; everything else takes plaidhip_shard_bounds.
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
   int64_t lo64 = 0, hi64 = 0;
-  if (((c.method == 6 || (c.method == 9 && c.rowtf == 0)) && c.Xp == nullptr) || c.method == 7) {
+  if (((c.method == kGsva || (c.method == kGsvaExact && c.rowtf == 0)) && c.Xp == nullptr) || c.method == kPlaidTest) {
     constexpr int64_t kBlock = 128;
     const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
     lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
@@ -539,7 +499,7 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m;
   const bool sparse = c.Xp != nullptr;
-  const bool ranks = c.method != 0;
+  const bool ranks = c.method != kPlaid;
   plaidhip_geneset* gs = nullptr;
   CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dR{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
   // the caller's S is usually fresh, untouched memory (R: allocMatrix): its pages are made while the upload and the
@@ -574,11 +534,11 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
       auto on_panel = [&](int64_t c0, int64_t c1) -> int {
         const int32_t nc = (int32_t)(c1 - c0);
         const double* xp = dX.as<double>() + c0 * ldg;
-        if (c.method == 0)
+        if (c.method == kPlaid)
           return launch_spmm_dense_f64(ctx, gs, xp, ldg, nc, c.stat, 1.0, nullptr, 0.0, dS.as<double>() + c0 * m, m, d_flags);
-        return launch_colranks_dense_f64(ctx, xp, ldg, g, nc, c.method == 1 ? PLAIDHIP_TIES_MIN : PLAIDHIP_TIES_AVERAGE, 0,
-                                         c.method == 2 ? 1.0 + c.alpha : 1.0, dR.as<double>() + c0 * ldg, ldg,
-                                         c.method == 2 ? d_colmax + c0 : nullptr);
+        return launch_colranks_dense_f64(ctx, xp, ldg, g, nc, c.method == kSing ? PLAIDHIP_TIES_MIN : PLAIDHIP_TIES_AVERAGE, 0,
+                                         c.method == kSsgsea ? 1.0 + c.alpha : 1.0, dR.as<double>() + c0 * ldg, ldg,
+                                         c.method == kSsgsea ? d_colmax + c0 : nullptr);
       };
       PH_TRACE("buffers ready");
       PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ldg * 8, reinterpret_cast<const char*>(Xh), (size_t)g * 8, nloc,
@@ -593,10 +553,10 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
       // matrix): built panel by panel from the ranks of the stored values, each panel multiplied at once
       int64_t panel = ((int64_t)2 << 30) / (ldg * 8);
       panel = std::min<int64_t>(std::max<int64_t>(panel & ~(int64_t)1, 2), nloc);
-      if (c.method == 1) PH_TRY(dR.alloc((size_t)(panel * ldg + zx) * 8));   // a panel of dense ranks | ranks of the stored values
+      if (c.method == kSing) PH_TRY(dR.alloc((size_t)(panel * ldg + zx) * 8));   // a panel of dense ranks | ranks of the stored values
       else if (ranks) PH_TRY(dR.alloc((size_t)zx * 8));
       home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
-      if (c.method == 1) {
+      if (c.method == kSing) {
         double* dRd = dR.as<double>();
         double* dRx = dRd + panel * ldg;
         const bool by_stored = max_nnz <= max_sparse_rank_column();
@@ -614,15 +574,15 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
         }
       } else if (ranks)   // sparse_colranks: the stored values among themselves (R/plaid.R:600-601, 631-650)
         PH_TRY(launch_colranks_csc_f64(ctx, dXp.as<int32_t>(), dX.as<double>(), nloc, max_nnz,
-                                       c.method == 1 ? PLAIDHIP_TIES_MIN : PLAIDHIP_TIES_AVERAGE, 0,
-                                       c.method == 2 ? 1.0 + c.alpha : 1.0, dR.as<double>(), c.method == 2 ? d_colmax : nullptr));
+                                       c.method == kSing ? PLAIDHIP_TIES_MIN : PLAIDHIP_TIES_AVERAGE, 0,
+                                       c.method == kSsgsea ? 1.0 + c.alpha : 1.0, dR.as<double>(), c.method == kSsgsea ? d_colmax : nullptr));
     }
     return PLAIDHIP_OK;
   });
 
   // ---- max(rX) over every shard (replaid.ssgsea, R/plaid.R:251) ----------------------------------------------------
   double gmax = 0.0;
-  if (c.method == 2) {
+  if (c.method == kSsgsea) {
     double mine = sparse ? 0.0 : -INFINITY;      // a dgCMatrix has implicit zeros
     s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
@@ -646,12 +606,12 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
-    if (c.method == 0 && !sparse) return PLAIDHIP_OK;
-    if (c.method == 1 && sparse) return PLAIDHIP_OK;   // done panel by panel above
+    if (c.method == kPlaid && !sparse) return PLAIDHIP_OK;
+    if (c.method == kSing && sparse) return PLAIDHIP_OK;   // done panel by panel above
     double a = 1.0, b = 0.0;
     int stat = c.stat;
-    if (c.method == 1) { a = 1.0 / (double)g; b = -0.5; stat = PLAIDHIP_STAT_MEAN; }       // R/plaid.R:216
-    if (c.method == 2) { a = 1.0 / gmax; b = -0.5; stat = PLAIDHIP_STAT_MEAN; }            // R/plaid.R:251
+    if (c.method == kSing) { a = 1.0 / (double)g; b = -0.5; stat = PLAIDHIP_STAT_MEAN; }       // R/plaid.R:216
+    if (c.method == kSsgsea) { a = 1.0 / gmax; b = -0.5; stat = PLAIDHIP_STAT_MEAN; }            // R/plaid.R:251
     const double* vals = ranks ? dR.as<double>() : dX.as<double>();
     if (sparse) {
       // scatter or gather is chosen from the density of the WHOLE matrix, not of the shard: every sharding of the same
@@ -661,22 +621,22 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
       const int64_t nnz_choice = (int64_t)((double)c.Xp[c.n] / (double)c.n * (double)nloc);
       // replaid.ssgsea: the values are rank weights in [0, max(rX)] (the scatter kernel may sum them in fixed point)
       // (normalised results: the crossprod also classifies its scores for the medians below, launch_col_medians_resume)
-      const bool will_norm = c.method == 2 || (c.method == 0 && c.normalize);
+      const bool will_norm = c.method == kSsgsea || (c.method == kPlaid && c.normalize);
       if (will_norm)
         return launch_spmm_csc_fused_f64(ctx, gs, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, nloc, zx, stat, a, nullptr, b,
-                                         dS.as<double>(), m, d_flags, /*bounded=*/c.method == 2, nullptr, gmax, nnz_choice);
+                                         dS.as<double>(), m, d_flags, /*bounded=*/c.method == kSsgsea, nullptr, gmax, nnz_choice);
       return launch_spmm_csc_f64(ctx, gs, dXp.as<int32_t>(), dXi.as<int32_t>(), vals, nloc, nnz_choice, stat, a, nullptr, b,
-                                 dS.as<double>(), m, d_flags, /*bounded=*/c.method == 2, nullptr, gmax);
+                                 dS.as<double>(), m, d_flags, /*bounded=*/c.method == kSsgsea, nullptr, gmax);
     }
-    const int x_kind = (c.method == 1 || (c.method == 2 && c.alpha == 0.0)) ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
+    const int x_kind = (c.method == kSing || (c.method == kSsgsea && c.alpha == 0.0)) ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
     // (normalised results on the fp64 pair kernel: the crossprod also classifies its scores for the medians below)
-    if (c.method == 2 || (c.method == 0 && c.normalize))
+    if (c.method == kSsgsea || (c.method == kPlaid && c.normalize))
       return launch_spmm_dense_fused_f64(ctx, gs, vals, ldg, nloc, stat, a, nullptr, b, dS.as<double>(), m, d_flags, x_kind);
     return launch_spmm_dense_f64(ctx, gs, vals, ldg, nloc, stat, a, nullptr, b, dS.as<double>(), m, d_flags, x_kind);
   });
 
   // ---- normalize_medians (R/plaid.R:554-575): two more scalars --------------------------------------------------------
-  const bool norm = c.method == 2 || (c.method == 0 && c.normalize);
+  const bool norm = c.method == kSsgsea || (c.method == kPlaid && c.normalize);
   if (norm) {
     const double mean_med = medians_and_their_mean(s, dS.as<double>(), d_flags, d_med);
     s.step([&]() -> int {
@@ -697,7 +657,7 @@ int shard_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 }
 
 
-// one device's part of replaid.ssgsea.exact (method 8, kernels_walk.hip): the operands of its columns, the crossprods
+// one device's part of replaid.ssgsea.exact (kSsgseaExact, kernels_walk.hip): the operands of its columns, the crossprods
 // C = G'Q (the exact rank route) and, for alpha != 0, A = G'P and B = G'W (fp64), the pinned epilogue.  The only coupling
 // between the shards is the range of all scores behind norm = TRUE, combined on the host.
 // single = FALSE: the same operands, then the walk kernel of kernels_ks.hip in place of the crossprods and the epilogue
@@ -816,7 +776,7 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
   return s.finish();
 }
 
-// one device's part of replaid.sing.exact (method 10, kernels_sing.hip): the min ranks of its columns as replaid.sing takes
+// one device's part of replaid.sing.exact (kSingExact, kernels_sing.hip): the min ranks of its columns as replaid.sing takes
 // them (a dgCMatrix: the dense rank matrix built on the device), the crossprods C = G'R on the exact rank route and the
 // pinned epilogue; for the dispersions the last ranks (a second rank pass over a tie-free column made from the first),
 // the ranks by position and the per-pair kernel, once per direction.  Nothing couples the shards.
@@ -937,25 +897,25 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   return s.finish();
 }
 
-// one device's part of replaid.ucell / aucell / scse / gsva (methods 3 - 6; one shard: plaidhip_ucell ... plaidhip_gsva_csc)
-// and of replaid.gsva.exact (method 9).  The quantities that couple the samples are combined on the host between the
+// one device's part of replaid.ucell / aucell / scse / gsva (kUcell ... kGsva; one shard: plaidhip_ucell ... plaidhip_gsva_csc)
+// and of replaid.gsva.exact (kGsvaExact).  The quantities that couple the samples are combined on the host between the
 // phases: max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the
 // z row transform (:341-343) and the medians' flags and mean(medx) (:554-575).
 int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
-  if (c.method == 8) return ssgsea_exact_worker(ctx, c, ndev, k, sh);
-  if (c.method == 10) return sing_exact_worker(ctx, c, ndev, k, sh);
+  if (c.method == kSsgseaExact) return ssgsea_exact_worker(ctx, c, ndev, k, sh);
+  if (c.method == kSingExact) return sing_exact_worker(ctx, c, ndev, k, sh);
   Shard s(ctx, c, ndev, k, sh);
   const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m, n = c.n;
   const bool sparse = c.Xp != nullptr;
   const int method = c.method;
-  const bool ranked = method == 3 || method == 4;
-  // replaid.gsva.exact (method 9): replaid.gsva's row transform (z, ecdf, or none: X as it is), then the last ranks of the
+  const bool ranked = method == kUcell || method == kAucell;
+  // replaid.gsva.exact (kGsvaExact): replaid.gsva's row transform (z, ecdf, or none: X as it is), then the last ranks of the
   // columns of v and the walk of kernels_ks.hip in place of the signed ranks, the crossprod and the medians
-  const bool gx = method == 9;
-  const bool ztf = (method == 6 || gx) && c.rowtf == 0;
+  const bool gx = method == kGsvaExact;
+  const bool ztf = (method == kGsva || gx) && c.rowtf == 0;
   // "ecdf" ranks all samples of a gene together: one shard only (the argument checks see to it)
-  const bool ecdf = (method == 6 || gx) && c.rowtf == 1;
+  const bool ecdf = (method == kGsva || gx) && c.rowtf == 1;
   // "gauss": GSVA's kernel CDF estimate (kernels_kcdf.hip).  Every V_ij needs its gene's whole row, so all of X goes to
   // every device, which computes the columns of its own shard: dX holds V, dense, whatever X was
   const bool gauss = gx && c.rowtf == 3;
@@ -1015,7 +975,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       PH_TRY(gsva_kcdf_columns(ctx, c.Xp, c.Xi, c.X, g, n, lo, nloc, dX.as<double>()));
     } else if (!sparse) {
       PH_TRY(dX.alloc((size_t)ld * nloc * 8));
-      if (method != 5 && !gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
+      if (method != kScse && !gx) PH_TRY(dR.alloc((size_t)ld * nloc * 8));
       // ucell / aucell: the average ranks of a column panel follow its DMA
       auto on_panel = [&](int64_t c0, int64_t c1) -> int {
         return launch_colranks_dense_f64(ctx, dX.as<double>() + c0 * ld, ld, g, (int32_t)(c1 - c0), PLAIDHIP_TIES_AVERAGE, 0,
@@ -1202,7 +1162,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       return PLAIDHIP_OK;
     });
   }
-  if (method == 6) {
+  if (method == kGsva) {
     // rX = colranks(zX, signed = TRUE, "average"); rX / max|rX|; sign * |rX|^(1 + tau) (R/plaid.R:352-358)
     //    = sign * rank^(1 + tau) / max(rank^(1 + tau)): the power is fused into the rank kernel, the division into the
     //    crossprod's epilogue (d_gmax below), by linearity of the mean statistic
@@ -1234,17 +1194,17 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     });
 
   // ---- max(rX) (ucell / aucell: R/plaid.R:278, 306; gsva: max|rX|, :354) --------------------------------------------------
-  if (method != 5 && !gx) global_max(d_colmax);
+  if (method != kScse && !gx) global_max(d_colmax);
   if (ranked)
     s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
-      return method == 3 ? launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 0, c.rmax + 1.0, d_gmax)      // :278
+      return method == kUcell ? launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 0, c.rmax + 1.0, d_gmax)      // :278
                          : launch_map(ctx, dR.as<double>(), (int64_t)g * nloc, 1, c.auc_max_rank, d_gmax);   // :306
     });
 
   // ---- replaid.scse: removeLog2 = NULL decided once, from min / max of the whole matrix (R/plaid.R:160-161) -------------
   bool remove_log2 = c.remove_log2 > 0;
-  if (method == 5 && c.remove_log2 < 0) {
+  if (method == kScse && c.remove_log2 < 0) {
     double mm[2] = {INFINITY, -INFINITY};
     s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
@@ -1259,7 +1219,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     if (sparse && (int64_t)c.Xp[n] < (int64_t)g * n) { mn = mn < 0.0 ? mn : 0.0; mx = mx > 0.0 ? mx : 0.0; }   // implicit zeros
     remove_log2 = mn == 0.0 && mx < 20.0;
   }
-  if (method == 5) {
+  if (method == kScse) {
     if (k == 0) sh.removed_log2 = remove_log2;
     s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
@@ -1272,7 +1232,7 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   if (!gx) s.step([&]() -> int {
     if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
     if (nloc == 0) return PLAIDHIP_OK;
-    if (method == 5) {
+    if (method == kScse) {
       const int stat = c.score_mean ? PLAIDHIP_STAT_MEAN : PLAIDHIP_STAT_SUM;
       if (sparse) {
         // the kernel is chosen from the density of the whole matrix, as in shard_worker (one shard: the count itself, which
@@ -1284,17 +1244,17 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
       return launch_spmm_dense_f64(ctx, gs, dX.as<double>(), ld, nloc, stat, 1.0, nullptr, 0.0, dS.as<double>(), m, nullptr);
     }
     int x_kind = PLAIDHIP_X_ANY;
-    if (method == 3) {   // pmin(max(rX) - rX, rmax + 1) of average ranks: half-integers when rmax + 1 is one
+    if (method == kUcell) {   // pmin(max(rX) - rX, rmax + 1) of average ranks: half-integers when rmax + 1 is one
       const double cap2 = 2.0 * (c.rmax + 1.0);
       x_kind = (cap2 == std::floor(cap2) && cap2 < 65536.0) ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
     }
-    if (method == 6) x_kind = c.tau > 0.0 ? PLAIDHIP_X_ANY : PLAIDHIP_X_EXACT_F32;   // signed average ranks
-    return launch_spmm_dense_f64(ctx, gs, dR.as<double>(), ld, nloc, PLAIDHIP_STAT_MEAN, 1.0, method == 6 ? d_gmax : nullptr,
+    if (method == kGsva) x_kind = c.tau > 0.0 ? PLAIDHIP_X_ANY : PLAIDHIP_X_EXACT_F32;   // signed average ranks
+    return launch_spmm_dense_f64(ctx, gs, dR.as<double>(), ld, nloc, PLAIDHIP_STAT_MEAN, 1.0, method == kGsva ? d_gmax : nullptr,
                                  0.0, dS.as<double>(), m, d_flags, x_kind);
   });
 
   // ---- normalize_medians (R/plaid.R:554-575) -------------------------------------------------------------------------------
-  if (method != 5 && !gx) {
+  if (method != kScse && !gx) {
     const double mean_med = medians_and_their_mean(s, dS.as<double>(), d_flags, d_med);
     s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
@@ -1305,14 +1265,14 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   // ---- the affine steps of replaid.ucell and replaid.scse ------------------------------------------------------------------
   s.step([&]() -> int {
     if (nloc == 0) return PLAIDHIP_OK;
-    if (method == 3) {   // 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:280)
+    if (method == kUcell) {   // 1 - S / rmax + (k + 1) / (2 rmax)   (R/plaid.R:280)
       add.resize((size_t)m);
       for (int32_t j = 0; j < m; ++j) add[(size_t)j] = 1.0 + (c.k_full[j] + 1.0) / (2.0 * c.rmax);
       PH_TRY(dadd.alloc((size_t)m * 8));
       PH_HIP(hipMemcpyAsync(dadd.p, add.data(), (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
       return launch_affine(ctx, dS.as<double>(), m, m, nloc, -1.0 / c.rmax, nullptr, 1.0, dadd.as<double>(), 0.0);
     }
-    if (method == 5)   // mean: sX / (colMeans|X| + 1e-8) (:176-177); sum: sX / (colSums|X| + 1e-8) * 100 (:181-182)
+    if (method == kScse)   // mean: sX / (colMeans|X| + 1e-8) (:176-177); sum: sX / (colSums|X| + 1e-8) * 100 (:181-182)
       return launch_affine(ctx, dS.as<double>(), m, m, nloc, c.score_mean ? 1.0 : 100.0, d_colsum,
                            c.score_mean ? 1.0 / (double)g : 1.0, nullptr, 0.0);
     return PLAIDHIP_OK;
@@ -1337,7 +1297,7 @@ void scaled_group_means(const std::vector<double>& sums, int32_t rows, int64_t n
   }
 }
 
-// one device's part of a sharded plaid.test (method 7, R/plaid.R:392-474; one shard: plaidhip_plaid_test / _csc), with what
+// one device's part of a sharded plaid.test (kPlaidTest, R/plaid.R:392-474; one shard: plaidhip_plaid_test / _csc), with what
 // couples the samples combined on the host in between -- everything plaid.test reduces is a row sum over the samples,
 // so only O(genes + sets) numbers cross between the shards and the scores never leave their device.
 //   logFC: dense X chains the two group sums of X from shard to shard (the one-device block order); a dgCMatrix sums
@@ -1486,24 +1446,18 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   return s.finish();
 }
 
-int check_contexts(plaidhip_ctx* const* ctxs, int ndev) {
-  PH_REQUIRE(ndev >= 1 && ctxs != nullptr, "sharded call: no device");
-  for (int k = 0; k < ndev; ++k) PH_REQUIRE(ctxs[k] != nullptr, "sharded call: null context %d", k);
-  return PLAIDHIP_OK;
-}
-
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
   sh.med_all.assign((size_t)c.n, 0.0);
-  if (c.method == 6 || c.method == 9) {
+  if (c.method == kGsva || c.method == kGsvaExact) {
     sh.chain_sum.assign((size_t)c.g, 0.0);
     sh.chain_ssd.assign((size_t)c.g, 0.0);
     sh.row_sum.resize((size_t)ndev);
     sh.row_ssd.resize((size_t)ndev);
     sh.row_len.resize((size_t)ndev);
   }
-  if (c.method == 7) {
+  if (c.method == kPlaidTest) {
     sh.chain_x.assign((size_t)c.g * 2, 0.0);
     sh.chain_s.assign((size_t)c.m * 2, 0.0);
     sh.chain_q.assign((size_t)c.m * 2, 0.0);
@@ -1512,8 +1466,8 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.row_sum.resize((size_t)ndev);
   }
   auto worker = [&](int k) {
-    if (c.method == 7) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
-    return c.method <= 2 ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
+    return is_rank_sum(c.method) ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
   };
   int rc = PLAIDHIP_OK;
   if (ndev == 1) {
@@ -1539,8 +1493,8 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
       for (int k = 0; k < ndev; ++k)
         if (rcs[(size_t)k] != PLAIDHIP_OK) { rc = rcs[(size_t)k]; set_error("a device shard failed"); break; }
   }
-  if (rc == PLAIDHIP_OK && c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = sh.removed_log2 ? 1 : 0;
-  if (rc == PLAIDHIP_OK && c.method == 7) {   // the host half of plaid.test (R/plaid.R:410-474)
+  if (rc == PLAIDHIP_OK && c.method == kScse && c.removed_log2 != nullptr) *c.removed_log2 = sh.removed_log2 ? 1 : 0;
+  if (rc == PLAIDHIP_OK && c.method == kPlaidTest) {   // the host half of plaid.test (R/plaid.R:410-474)
     const int64_t ldg = even_ld(c.g);
     double tot1 = 0.0, tot2 = 0.0;
     for (int32_t i = 0; i < c.g; ++i) { tot1 += sh.pt_F[(size_t)i]; tot2 += sh.pt_F[(size_t)ldg + i]; }
@@ -1564,62 +1518,6 @@ namespace plaidhip {
 // hipMemcpy from pageable memory runs at ~21 GB/s, the ring at the link rate)
 int upload_host(plaidhip_ctx* ctx, void* dst, size_t ldd_bytes, const void* src, size_t row_bytes, int64_t cols) {
   return upload_pipelined(ctx, static_cast<char*>(dst), ldd_bytes, static_cast<const char*>(src), row_bytes, cols, nullptr);
-}
-
-int run_sharded(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int stat, int normalize, double alpha,
-                double* S_out) {
-  PH_TRY(check_contexts(ctxs, ndev));
-  PH_TRY(check_host_common(Gp, g, n, m));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(X_or_x != nullptr || (Xp != nullptr && Xp[n] == 0), "null X");
-  PH_REQUIRE(S_out != nullptr, "null S_out");
-  if (Xp != nullptr) PH_TRY(check_host_csc(Xp, Xi, g, n));
-  Call c{method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, stat, normalize, alpha, S_out};
-  return run_call(ctxs, ndev, c);
-}
-
-// replaid.ssgsea.exact's argument checks (every entry point runs them before a device is touched)
-int check_ssgsea_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                            const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, const double* S_out) {
-  PH_REQUIRE(std::isfinite(alpha), "ssgsea_exact: alpha must be finite (got %g)", alpha);
-  PH_TRY(check_host_common(Gp, g, n, m));
-  PH_REQUIRE(g < (1 << 26), "ssgsea_exact: nrow(X) = %d (at most 2^26 - 1 rows)", g);
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(Gi != nullptr || Gp[m] == 0, "ssgsea_exact: null Gi");
-  PH_REQUIRE(X_or_x != nullptr || (Xp != nullptr && Xp[n] == 0), "ssgsea_exact: null X");
-  PH_REQUIRE(S_out != nullptr, "ssgsea_exact: null S_out");
-  if (Xp != nullptr) {
-    PH_TRY(check_host_csc(Xp, Xi, g, n));
-    PH_REQUIRE(Xp[n] == 0 || Xi != nullptr, "ssgsea_exact: null Xi");
-    for (int32_t c = 0; c < n; ++c)   // the expansion walks the rows of a column in order (kernels_walk.hip)
-      for (int32_t q = Xp[c] + 1; q < Xp[c + 1]; ++q)
-        PH_REQUIRE(Xi[q] > Xi[q - 1], "ssgsea_exact: row indices of column %d are not increasing (Xi[%d] = %d after %d)", c, q,
-                   Xi[q], Xi[q - 1]);
-  }
-  return PLAIDHIP_OK;
-}
-
-// the bound of the walk kernel's bitmap (kernels_ks.hip), checked before a device is touched
-int check_gsea_ks_genes(int32_t g) {
-  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("ssgsea_exact_ks: nrow(X) = %d (at most %d rows with single = FALSE)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
-  return PLAIDHIP_OK;
-}
-
-int run_ssgsea_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                     int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
-                     double* S_out, int single) {
-  PH_TRY(check_contexts(ctxs, ndev));
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  if (!single) PH_TRY(check_gsea_ks_genes(g));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  Call c{8, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, norm ? 1 : 0, alpha, S_out};
-  c.scale = scale ? 1 : 0;
-  c.single = single ? 1 : 0;
-  return run_call(ctxs, ndev, c);
 }
 
 // GSVA's kernel CDF estimate of the columns [lo, lo + nloc) of the host matrix X on one device: all of X is uploaded (a
@@ -1649,88 +1547,94 @@ int gsva_kcdf_columns(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, c
   return PLAIDHIP_OK;
 }
 
-// replaid.gsva.exact's argument checks (every entry point runs them before a device is touched)
-int check_gsva_exact_args(int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                          const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, const double* S_out) {
-  PH_REQUIRE(std::isfinite(tau) && tau >= 0.0, "gsva_exact: tau must be finite and >= 0 (got %g)", tau);
-  PH_REQUIRE(rowtf >= 0 && rowtf <= 3, "Error: unknown row transform %d", rowtf);                     // R/plaid.R:348
-  PH_REQUIRE(rowtf != 3 || n >= 2, "gsva_exact: rowtf = \"gauss\" needs at least 2 samples (got %d)", n);
-  PH_REQUIRE(rowtf != 1 || ndev == 1, "gsva_exact_multi: rowtf = \"ecdf\" ranks all samples of a gene together and is not "
-                                      "sharded by sample; score it on one device (plaidhip_gsva_exact)");
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, 0.0, S_out));
+// the bound of the walk kernel's bitmap (kernels_ks.hip), checked before a device is touched
+int check_gsea_ks_genes(int32_t g) {
   if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("gsva_exact: nrow(X) = %d (at most %d rows)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    set_error("ssgsea_exact_ks: nrow(X) = %d (at most %d rows with single = FALSE)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
     return PLAIDHIP_EUNSUPPORTED;
   }
   return PLAIDHIP_OK;
-}
-
-int run_gsva_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                   int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
-                   double* S_out) {
-  PH_TRY(check_contexts(ctxs, ndev));
-  PH_TRY(check_gsva_exact_args(ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  Call c{9, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, 0, 0.0, S_out};
-  c.tau = tau;
-  c.rowtf = rowtf;
-  c.max_diff = max_diff ? 1 : 0;
-  return run_call(ctxs, ndev, c);
-}
-
-// replaid.sing.exact's argument checks (every entry point runs them before a device is touched)
-int check_sing_exact_args(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
-                          const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double* const out[6]) {
-  const double* any = nullptr;
-  for (int o = 0; o < 6; ++o) any = any ? any : out[o];
-  PH_REQUIRE((int64_t)m * n == 0 || any != nullptr, "sing_exact: no output requested");
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, 0.0, any));
-  if (Dp != nullptr) {
-    PH_TRY(check_host_common(Dp, g, n, m));
-    PH_REQUIRE((int64_t)m * n == 0 || Di != nullptr || Dp[m] == 0, "sing_exact: null Di");
-  } else {
-    PH_REQUIRE(!out[0] && !out[2] && !out[3] && !out[5], "sing_exact: total and down results need the down sets");
-  }
-  if ((out[3] || out[4] || out[5]) && g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("sing_exact: nrow(X) = %d (at most %d rows with the dispersion)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
-  return PLAIDHIP_OK;
-}
-
-int run_sing_exact(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                   int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
-                   double* const out[6]) {
-  PH_TRY(check_contexts(ctxs, ndev));
-  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  Call c{10, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_SUM, 0, 0.0, nullptr};
-  c.Dp = Dp;
-  c.Di = Di;
-  c.center = center ? 1 : 0;
-  for (int o = 0; o < 6; ++o) c.sx_out[o] = out[o];
-  return run_call(ctxs, ndev, c);
 }
 
 }  // namespace plaidhip
 
-// ---- replaid.ucell / aucell / scse / gsva and plaid.test: one set of argument checks, one way in ---------------------------
+// ---- the argument checks of every method: check_call.  None touches a device. -----------------------------------------------
 namespace {
 
-Call scorer_call(int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                 const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) {
-  return Call{method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, S_out};
+// plaid / sing / ssgsea
+int check_rank_sum_call(const Call& c) {
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "null X");
+  PH_REQUIRE(c.S_out != nullptr, "null S_out");
+  if (c.Xp != nullptr) PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
+  return PLAIDHIP_OK;
 }
 
-// the argument checks of methods 3 - 6, before any device is touched.  multi: a plaidhip_*_multi entry, which refuses
-// rowtf = "ecdf" whatever the device count; the others take it on one shard
-int check_scorer_call(const Call& c, int ndev, bool multi) {
-  if (c.method == 5 && c.removed_log2 != nullptr) *c.removed_log2 = c.remove_log2 > 0 ? 1 : 0;
-  PH_REQUIRE(c.method >= 3 && c.method <= 6, "scorer: bad method %d", c.method);
+// replaid.ssgsea.exact; replaid.gsva.exact and replaid.sing.exact (alpha 0) run it inside theirs.  S_out: the result, or
+// any one of sing.exact's
+int check_ssgsea_exact_call(const Call& c, const double* S_out) {
+  PH_REQUIRE(std::isfinite(c.alpha), "ssgsea_exact: alpha must be finite (got %g)", c.alpha);
   PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
-  if (c.method == 3) PH_REQUIRE(c.rmax > 0, "ucell: rmax must be positive");
-  if (c.method == 4) PH_REQUIRE(c.auc_max_rank > 0, "aucell: aucMaxRank must be positive");
-  if (c.method == 6) {
+  PH_REQUIRE(c.g < (1 << 26), "ssgsea_exact: nrow(X) = %d (at most 2^26 - 1 rows)", c.g);
+  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "ssgsea_exact: null Gi");
+  PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "ssgsea_exact: null X");
+  PH_REQUIRE(S_out != nullptr, "ssgsea_exact: null S_out");
+  if (c.Xp != nullptr) {
+    const int32_t* Xp = c.Xp;
+    const int32_t* Xi = c.Xi;
+    PH_TRY(check_host_csc(Xp, Xi, c.g, c.n));
+    PH_REQUIRE(Xp[c.n] == 0 || Xi != nullptr, "ssgsea_exact: null Xi");
+    for (int32_t j = 0; j < c.n; ++j)   // the expansion walks the rows of a column in order (kernels_walk.hip)
+      for (int32_t q = Xp[j] + 1; q < Xp[j + 1]; ++q)
+        PH_REQUIRE(Xi[q] > Xi[q - 1], "ssgsea_exact: row indices of column %d are not increasing (Xi[%d] = %d after %d)", j, q,
+                   Xi[q], Xi[q - 1]);
+  }
+  return PLAIDHIP_OK;
+}
+
+int check_gsva_exact_call(const Call& c, int ndev) {
+  PH_REQUIRE(std::isfinite(c.tau) && c.tau >= 0.0, "gsva_exact: tau must be finite and >= 0 (got %g)", c.tau);
+  PH_REQUIRE(c.rowtf >= 0 && c.rowtf <= 3, "Error: unknown row transform %d", c.rowtf);                     // R/plaid.R:348
+  PH_REQUIRE(c.rowtf != 3 || c.n >= 2, "gsva_exact: rowtf = \"gauss\" needs at least 2 samples (got %d)", c.n);
+  PH_REQUIRE(c.rowtf != 1 || ndev == 1, "gsva_exact_multi: rowtf = \"ecdf\" ranks all samples of a gene together and is not "
+                                        "sharded by sample; score it on one device (plaidhip_gsva_exact)");
+  PH_TRY(check_ssgsea_exact_call(c, c.S_out));
+  if (c.g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("gsva_exact: nrow(X) = %d (at most %d rows)", c.g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  return PLAIDHIP_OK;
+}
+
+int check_sing_exact_call(const Call& c) {
+  double* const* out = c.sx_out;
+  const double* any = nullptr;
+  for (int o = 0; o < 6; ++o) any = any ? any : out[o];
+  PH_REQUIRE((int64_t)c.m * c.n == 0 || any != nullptr, "sing_exact: no output requested");
+  PH_TRY(check_ssgsea_exact_call(c, any));
+  if (c.Dp != nullptr) {
+    PH_TRY(check_host_common(c.Dp, c.g, c.n, c.m));
+    PH_REQUIRE((int64_t)c.m * c.n == 0 || c.Di != nullptr || c.Dp[c.m] == 0, "sing_exact: null Di");
+  } else {
+    PH_REQUIRE(!out[0] && !out[2] && !out[3] && !out[5], "sing_exact: total and down results need the down sets");
+  }
+  if ((out[3] || out[4] || out[5]) && c.g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("sing_exact: nrow(X) = %d (at most %d rows with the dispersion)", c.g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  return PLAIDHIP_OK;
+}
+
+// replaid.ucell / aucell / scse / gsva
+int check_scorer_call(const Call& c, int ndev, bool multi) {
+  if (c.method == kScse && c.removed_log2 != nullptr) *c.removed_log2 = c.remove_log2 > 0 ? 1 : 0;
+  PH_REQUIRE(is_scorer(c.method), "scorer: bad method %d", c.method);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  if (c.method == kUcell) PH_REQUIRE(c.rmax > 0, "ucell: rmax must be positive");
+  if (c.method == kAucell) PH_REQUIRE(c.auc_max_rank > 0, "aucell: aucMaxRank must be positive");
+  if (c.method == kGsva) {
     PH_REQUIRE(c.rowtf == 0 || c.rowtf == 1, "Error: unknown row transform %d", c.rowtf);              // R/plaid.R:348
     PH_REQUIRE(c.rowtf == 0 || (!multi && ndev == 1), "gsva: rowtf = \"ecdf\" ranks all samples of a gene together and is "
                "not sharded by sample; score it on one device (plaidhip_gsva / plaidhip_gsva_csc)");
@@ -1738,19 +1642,19 @@ int check_scorer_call(const Call& c, int ndev, bool multi) {
   if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
   PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "null X");
   PH_REQUIRE(c.S_out != nullptr, "null S_out");
-  if (c.method == 3) PH_REQUIRE(c.k_full != nullptr, "ucell: null k_full");
+  if (c.method == kUcell) PH_REQUIRE(c.k_full != nullptr, "ucell: null k_full");
   if (c.Xp != nullptr) {
     PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
     PH_REQUIRE(c.Xp[c.n] == 0 || c.Xi != nullptr, "null Xi");
     // (the ranks of the rows' stored values use a g x n buffer as scratch: a column repeating a row index could pass it)
-    if (c.method == 6)
+    if (c.method == kGsva)
       PH_REQUIRE((int64_t)c.Xp[c.n] <= (int64_t)c.g * c.n, "gsva: %d stored values in a %d x %d matrix (repeated row "
                  "indices?)", c.Xp[c.n], c.g, c.n);
   }
   return PLAIDHIP_OK;
 }
 
-// plaid.test's argument checks and their messages, before any device is touched; counts the groups of y into c.n0 / c.n1
+// plaid.test, and their messages; counts the groups of y into c.n0 / c.n1
 int check_plaid_test_call(Call& c) {
   PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
   PH_REQUIRE(c.m == 0 || c.out, "plaid_test: null out");
@@ -1769,60 +1673,11 @@ int check_plaid_test_call(Call& c) {
   return PLAIDHIP_OK;
 }
 
-Call plaid_test_call(const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* y,
-                     const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests, int metap_method,
-                     double* out) {
-  Call c{7, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, 0.0, nullptr};
-  c.y = y;
-  c.gsetX = gsetX;
-  c.tests = tests;
-  c.metap_method = metap_method;
-  c.out = out;
-  return c;
-}
-
-}  // namespace
-
-namespace plaidhip {
-
-int run_scorer(plaidhip_ctx* const* ctxs, int ndev, int method, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full, double rmax,
-               double auc_max_rank, int remove_log2, int score_mean, double tau, int rowtf, double* S_out, int* removed_log2) {
-  Call c = scorer_call(method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
-  c.k_full = k_full;
-  c.rmax = rmax;
-  c.auc_max_rank = auc_max_rank;
-  c.remove_log2 = remove_log2;
-  c.score_mean = score_mean;
-  c.tau = tau;
-  c.rowtf = rowtf;
-  c.removed_log2 = removed_log2;
-  PH_TRY(check_contexts(ctxs, ndev));
-  PH_TRY(check_scorer_call(c, ndev, /*multi=*/false));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  return run_call(ctxs, ndev, c);
-}
-
-int run_plaid_test(plaidhip_ctx* const* ctxs, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
-                   int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
-                   int metap_method, double* out) {
-  Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
-  PH_TRY(check_contexts(ctxs, ndev));
-  PH_TRY(check_plaid_test_call(c));
-  if (m == 0) return PLAIDHIP_OK;
-  return run_call(ctxs, ndev, c);
-}
-
-}  // namespace plaidhip
-
-// ---- multi-device entry points (include/plaidhip.h) ---------------------------------------------------------------------
-namespace {
-
 std::mutex g_multi_mu;
 std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
 int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
 
-// the device list's own checks, which touch no device (multi_contexts repeats them against the device count)
+// the device list's own checks, which touch no device
 int check_devices(const int* devices, int ndev) {
   PH_REQUIRE(ndev >= 1 && ndev <= 64, "multi: ndev = %d", ndev);
   if (devices != nullptr)
@@ -1832,7 +1687,6 @@ int check_devices(const int* devices, int ndev) {
 }
 
 int multi_contexts(const int* devices, int ndev, std::vector<plaidhip_ctx*>& out) {
-  PH_TRY(check_devices(devices, ndev));
   int count = 0;
   PH_TRY(plaidhip_device_count(&count));
   std::lock_guard<std::mutex> lk(g_multi_mu);
@@ -1848,154 +1702,61 @@ int multi_contexts(const int* devices, int ndev, std::vector<plaidhip_ctx*>& out
   return PLAIDHIP_OK;
 }
 
-// checks, then the contexts of `devices`, then the sharded call
-int run_scorer_multi(const int* devices, int ndev, const Call& c) {
-  PH_TRY(check_scorer_call(c, ndev, /*multi=*/true));
-  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_call(ctxs.data(), ndev, c);
-}
-
 // The test hooks' engine: `nshards` contexts on ONE device -- worker threads, rendezvous, cross-shard scalars and the
 // failure path are what a 1-GPU box can exercise of plaidhip_*_multi.  fail_shard >= 0: that shard fails in its crossprod
-// phase (the call must return an error, not hang).  The error text of `call` outlives the contexts' release.
-int sharded_on_one_device(int device, int nshards, int fail_shard, const std::function<int(plaidhip_ctx* const*)>& call) {
-  PH_REQUIRE(nshards >= 1 && nshards <= 64, "debug_sharded: nshards = %d", nshards);
+// phase (the call must return an error, not hang).  The error text of the call outlives the contexts' release.
+int run_on_one_device(int device, int nshards, int fail_shard, const Call& c) {
   std::vector<plaidhip_ctx*> ctxs((size_t)nshards, nullptr);
   int rc = PLAIDHIP_OK;
   for (int k = 0; k < nshards && rc == PLAIDHIP_OK; ++k) {
     rc = plaidhip_init(device, nullptr, &ctxs[(size_t)k]);
     if (rc == PLAIDHIP_OK && k == fail_shard) ctxs[(size_t)k]->debug_fail_crossprod = 1;
   }
-  if (rc == PLAIDHIP_OK) rc = call(ctxs.data());
+  if (rc == PLAIDHIP_OK) rc = run_call(ctxs.data(), nshards, c);
   const std::string err = rc != PLAIDHIP_OK ? std::string(last_error_cstr()) : std::string();
-  for (plaidhip_ctx* c : ctxs)
-    if (c) plaidhip_finalize(c);
+  for (plaidhip_ctx* x : ctxs)
+    if (x) plaidhip_finalize(x);
   if (rc != PLAIDHIP_OK) set_error("%s", err.c_str());
   return rc;
 }
 
 }  // namespace
 
+namespace plaidhip {
+
+int check_call(Call& c, int ndev, bool multi) {
+  if (is_rank_sum(c.method)) return check_rank_sum_call(c);
+  switch (c.method) {
+    case kPlaidTest: return check_plaid_test_call(c);
+    case kSsgseaExact:
+      PH_TRY(check_ssgsea_exact_call(c, c.S_out));
+      return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
+    case kGsvaExact: return check_gsva_exact_call(c, ndev);
+    case kSingExact: return check_sing_exact_call(c);
+    default: return check_scorer_call(c, ndev, multi);   // (which refuses what is no method at all)
+  }
+}
+
+int dispatch(const Target& t, Call c) {
+  // (the shard count first: check_call reads it.  A null context after the arguments: tests reach the checks without one)
+  if (t.kind == Target::kDevices) PH_TRY(check_devices(t.devices, t.ndev));
+  if (t.kind == Target::kHook) PH_REQUIRE(t.ndev >= 1 && t.ndev <= 64, "debug_sharded: nshards = %d", t.ndev);
+  PH_TRY(check_call(c, t.ndev, t.kind == Target::kDevices));
+  if (t.kind == Target::kContext) PH_REQUIRE(t.ctx != nullptr, "null plaidhip_ctx");
+  if (c.method == kPlaidTest ? c.m == 0 : (int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  if (t.kind == Target::kHook) return run_on_one_device(t.device, t.ndev, t.fail_shard, c);
+  std::vector<plaidhip_ctx*> ctxs(1, t.ctx);
+  if (t.kind == Target::kContext)
+    PH_HIP(hipSetDevice(t.ctx->device));
+  else
+    PH_TRY(multi_contexts(t.devices, t.ndev, ctxs));
+  return run_call(ctxs.data(), t.ndev, c);
+}
+
+}  // namespace plaidhip
+
+// ---- multi-device entry points (include/plaidhip.h) and the test hooks: build the Call, dispatch ------------------------------
 extern "C" {
-
-// Test hooks (not part of include/plaidhip.h): the engine behind the plaidhip_*_multi entry of the same name, through
-// sharded_on_one_device.  plaid / sing / ssgsea: method 0 plaid, 1 sing, 2 ssgsea.
-int plaidhip_debug_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
-                                         const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
-                                         const int32_t* Gi, int32_t m, int stat, int normalize, double alpha, double* S_out) try {
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_sharded(ctxs, nshards, method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, stat, normalize, alpha, S_out);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-// method 3 ucell (k_full, rmax), 4 aucell (auc_max_rank), 5 scse (remove_log2, score_mean, removed_log2), 6 gsva (tau,
-// rowtf); the parameters a method does not take are ignored
-int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
-                                                const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                                                const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full,
-                                                double rmax, double auc_max_rank, int remove_log2, int score_mean, double tau,
-                                                int rowtf, double* S_out, int* removed_log2) try {
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_scorer(ctxs, nshards, method, Xp, Xi, X_or_x, g, n, Gp, Gi, m, k_full, rmax, auc_max_rank, remove_log2,
-                      score_mean, tau, rowtf, S_out, removed_log2);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_debug_plaid_test_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
-                                                    const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                                                    const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
-                                                    const double* gsetX, int tests, int metap_method, double* out) try {
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_plaid_test(ctxs, nshards, Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_debug_ssgsea_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
-                                                      const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                                                      const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
-                                                      int norm, double* S_out) try {
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_ssgsea_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
-                                int norm, double* S_out) try {
-  PH_TRY(check_devices(devices, ndev));
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out);
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_debug_ssgsea_exact_ks_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
-                                                      const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                                                      const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
-                                                      int norm, double* S_out) try {
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_ssgsea_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
-                                int norm, double* S_out) try {
-  PH_TRY(check_devices(devices, ndev));
-  PH_TRY(check_ssgsea_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, S_out));
-  PH_TRY(check_gsea_ks_genes(g));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_ssgsea_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, alpha, scale, norm, S_out, 0);
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_debug_gsva_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
-                                                    const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
-                                                    const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
-                                                    int max_diff, double* S_out) try {
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_gsva_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
-                              int max_diff, double* S_out) try {
-  PH_TRY(check_devices(devices, ndev));
-  PH_TRY(check_gsva_exact_args(ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, S_out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_gsva_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, m, tau, rowtf, max_diff, S_out);
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_debug_sing_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp, const int32_t* Xi,
-                                                    const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
-                                                    const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m,
-                                                    int center, double* total, double* up, double* down, double* total_disp,
-                                                    double* up_disp, double* down_disp) try {
-  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
-  return sharded_on_one_device(device, nshards, fail_shard, [&](plaidhip_ctx* const* ctxs) {
-    return run_sing_exact(ctxs, nshards, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
-  });
-} catch (...) { return plaidhip::on_exception(); }
-
-int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
-                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
-                              int32_t m, int center, double* total, double* up, double* down, double* total_disp,
-                              double* up_disp, double* down_disp) try {
-  double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
-  PH_TRY(check_devices(devices, ndev));
-  PH_TRY(check_sing_exact_args(Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, out));
-  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_sing_exact(ctxs.data(), ndev, Xp, Xi, X_or_x, g, n, Gp, Gi, Dp, Di, m, center, out);
-} catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_multi_set_precision(int mode) try {
   PH_REQUIRE(mode == PLAIDHIP_PRECISION_F64 || mode == PLAIDHIP_PRECISION_MIXED, "multi_set_precision: bad mode %d", mode);
@@ -2011,80 +1772,146 @@ int plaidhip_multi_finalize(void) try {
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
+// Each plaidhip_*_multi entry; then the test hooks (not part of include/plaidhip.h): the same calls on `nshards` contexts of
+// one device (run_on_one_device), so a hook's signature is its entry's with (device, nshards, fail_shard) for (devices,
+// ndev).  Two hooks serve several entries by Method ordinal: plaid / sing / ssgsea (0 - 2) and ucell / aucell / scse /
+// gsva (3 - 6; the parameters a method does not take are ignored).
+
 int plaidhip_plaid_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                          int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int stat, int normalize, double* S_out) try {
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
   PH_REQUIRE(stat == PLAIDHIP_STAT_MEAN || stat == PLAIDHIP_STAT_SUM, "plaid_multi: bad stat %d", stat);
-  return run_sharded(ctxs.data(), ndev, 0, Xp, Xi, X_or_x, g, n, Gp, Gi, m, stat, normalize, 0.0, S_out);
+  return dispatch(on_devices(devices, ndev), plaid_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, stat, normalize, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_sing_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const int32_t* Gp,
                         const int32_t* Gi, int32_t m, double* S_out) try {
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_sharded(ctxs.data(), ndev, 1, nullptr, nullptr, X, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 0, 0.0, S_out);
+  return dispatch(on_devices(devices, ndev), sing_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_sing_csc_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g,
                             int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) try {
   PH_REQUIRE(Xp != nullptr, "sing_csc_multi: null Xp");
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_sharded(ctxs.data(), ndev, 1, Xp, Xi, Xx, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 0, 0.0, S_out);
+  return dispatch(on_devices(devices, ndev), sing_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_ssgsea_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                           int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, double* S_out) try {
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_sharded(ctxs.data(), ndev, 2, Xp, Xi, X_or_x, g, n, Gp, Gi, m, PLAIDHIP_STAT_MEAN, 1, alpha, S_out);
+  return dispatch(on_devices(devices, ndev), ssgsea_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_ucell_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                          int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full, double rmax,
                          double* S_out) try {
-  Call c = scorer_call(3, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
-  c.k_full = k_full;
-  c.rmax = rmax;
-  return run_scorer_multi(devices, ndev, c);
+  return dispatch(on_devices(devices, ndev), ucell_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, k_full, rmax, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_aucell_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                           int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank, double* S_out) try {
-  Call c = scorer_call(4, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
-  c.auc_max_rank = auc_max_rank;
-  return run_scorer_multi(devices, ndev, c);
+  return dispatch(on_devices(devices, ndev), aucell_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, auc_max_rank, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_scse_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                         int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, int remove_log2, int score_mean,
                         double* S_out, int* removed_log2) try {
-  Call c = scorer_call(5, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
-  c.remove_log2 = remove_log2;
-  c.score_mean = score_mean;
-  c.removed_log2 = removed_log2;
-  return run_scorer_multi(devices, ndev, c);
+  return dispatch(on_devices(devices, ndev),
+                  scse_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, remove_log2, score_mean, S_out, removed_log2));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_gsva_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
                         int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, double* S_out) try {
-  Call c = scorer_call(6, Xp, Xi, X_or_x, g, n, Gp, Gi, m, S_out);
-  c.tau = tau;
-  c.rowtf = rowtf;
-  return run_scorer_multi(devices, ndev, c);
+  return dispatch(on_devices(devices, ndev), gsva_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tau, rowtf, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_plaid_test_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                               int32_t g, int32_t n, const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
                               const double* gsetX, int tests, int metap_method, double* out) try {
-  Call c = plaid_test_call(Xp, Xi, X_or_x, g, n, y, Gp, Gi, m, gsetX, tests, metap_method, out);
-  PH_TRY(check_devices(devices, ndev));
-  PH_TRY(check_plaid_test_call(c));
-  if (m == 0) return PLAIDHIP_OK;
-  std::vector<plaidhip_ctx*> ctxs;
-  PH_TRY(multi_contexts(devices, ndev, ctxs));
-  return run_call(ctxs.data(), ndev, c);
+  return dispatch(on_devices(devices, ndev),
+                  plaid_test_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                int norm, double* S_out) try {
+  return dispatch(on_devices(devices, ndev), ssgsea_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, scale, norm, S_out, 1));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_ssgsea_exact_ks_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                   int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
+                                   int scale, int norm, double* S_out) try {
+  return dispatch(on_devices(devices, ndev), ssgsea_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, scale, norm, S_out, 0));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsva_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
+                              int max_diff, double* S_out) try {
+  return dispatch(on_devices(devices, ndev), gsva_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tau, rowtf, max_diff, S_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                              int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
+                              int32_t m, int center, double* total, double* up, double* down, double* total_disp,
+                              double* up_disp, double* down_disp) try {
+  return dispatch(on_devices(devices, ndev), sing_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, center, total, up, down,
+                                                             total_disp, up_disp, down_disp));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
+                                         const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                                         const int32_t* Gi, int32_t m, int stat, int normalize, double alpha, double* S_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  rank_sum_call(method, {Xp, Xi, X_or_x, g, n, Gp, Gi, m}, stat, normalize, alpha, S_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_scorer_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
+                                                const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                const int32_t* Gp, const int32_t* Gi, int32_t m, const double* k_full,
+                                                double rmax, double auc_max_rank, int remove_log2, int score_mean, double tau,
+                                                int rowtf, double* S_out, int* removed_log2) try {
+  PH_REQUIRE(is_scorer(method), "scorer: bad method %d", method);   // (the ordinal picks the checks: none but these four)
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  scorer_call(method, {Xp, Xi, X_or_x, g, n, Gp, Gi, m}, k_full, rmax, auc_max_rank, remove_log2, score_mean, tau,
+                              rowtf, S_out, removed_log2));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_plaid_test_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                    const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                    const int32_t* y, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                                                    const double* gsetX, int tests, int metap_method, double* out) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  plaid_test_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_ssgsea_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                      const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                      const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
+                                                      int norm, double* S_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  ssgsea_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, scale, norm, S_out, 1));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_ssgsea_exact_ks_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                         const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                         const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha,
+                                                         int scale, int norm, double* S_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  ssgsea_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, alpha, scale, norm, S_out, 0));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_gsva_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                    const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                    const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf,
+                                                    int max_diff, double* S_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  gsva_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tau, rowtf, max_diff, S_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_sing_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp, const int32_t* Xi,
+                                                    const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                                                    const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m,
+                                                    int center, double* total, double* up, double* down, double* total_disp,
+                                                    double* up_disp, double* down_disp) try {
+  return dispatch(on_hook(device, nshards, fail_shard), sing_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, center, total,
+                                                                         up, down, total_disp, up_disp, down_disp));
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -68,6 +68,131 @@ class Geneset:
             pass
 
 
+def _x_args(X):
+    """(Xp, Xi, values, g, n, keepalive) for a dense ndarray or a scipy CSC matrix."""
+    if not isinstance(X, np.ndarray):
+        import scipy.sparse as sp
+        if sp.issparse(X):
+            X = sp.csc_matrix(X)
+            return _slots(X.indptr, X.indices, X.data, X.shape[0])
+    Xd = _as_f64_fortran(X)
+    return None, None, _np_ptr(Xd), Xd.shape[0], Xd.shape[1], (Xd,)
+
+
+def _slots(Xp, Xi, Xx, g):
+    """_x_args of the slots of a g x n CSC matrix"""
+    Xp, Xi = _as_i32(Xp), _as_i32(Xi)
+    Xx = np.ascontiguousarray(Xx, dtype=np.float64)
+    return _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), len(Xp) - 1, (Xp, Xi, Xx)
+
+
+def _result(out, m, n):
+    """the caller's own result buffer (any byte offset; Fortran order like an R matrix) or a fresh one"""
+    if out is None:
+        return np.empty((m, n), dtype=np.float64, order="F")
+    if out.shape != (m, n) or out.dtype != np.float64 or not out.flags.f_contiguous or not out.flags.writeable:
+        raise ValueError(f"out: a writeable Fortran-ordered float64 array of shape {(m, n)}")
+    return out
+
+
+def _score(fn, head, X, Gp, Gi, *tail, pre=(), post=(), dense=False, out=None, cols=None):
+    """The one marshaller of the host-level scorers: fn(*head, X, g, n, *pre, Gp, Gi, m, *tail, result, *post).  head: (handle,) of
+    a context entry, (devices pointer, ndev) of a plaidhip_*_multi entry, (device, nshards, fail_shard) of a test hook; X: a
+    dense array, a scipy CSC matrix or _slots(); dense: the entry takes no Xp / Xi.  The result is m x n, or m x cols."""
+    xp, xi, xv, g, n, keep = X if isinstance(X, tuple) else _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    S = _result(out, m, n if cols is None else cols)
+    x = (xv, g, n) if dense else (xp, xi, xv, g, n)
+    check(fn(*head, *x, *pre, _np_ptr(Gp), _np_ptr(Gi), m, *tail, _np_ptr(S), *post))
+    return S
+
+
+def _rowtf(rowtf) -> int:
+    if rowtf not in ("z", "ecdf"):
+        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
+    return 0 if rowtf == "z" else 1
+
+
+def _remove_log2(remove_log2) -> int:
+    return -1 if remove_log2 is None else int(bool(remove_log2))
+
+
+def _plaid_test(fn, head, X, y, Gp, Gi, gsetX, tests, metap_method, dense=False, out=None):
+    """plaid.test through _score: sets x 6 (gsetFC, p.one, p.two, p.lm, p.meta, q.meta), G's column order"""
+    X = X if isinstance(X, tuple) else _x_args(X)
+    n, m = X[4], len(Gp) - 1
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.shape != (n,):
+        raise ValueError("y must have one entry per column of X")
+    sx = None
+    if gsetX is not None:
+        sx = _as_f64_fortran(gsetX)
+        if sx.shape != (m, n):
+            raise ValueError("gsetX must be sets x samples")
+    return _score(fn, head, X, Gp, Gi, None if sx is None else _np_ptr(sx), int(tests), int(metap_method), pre=(_np_ptr(y),),
+                  dense=dense, out=out, cols=6)
+
+
+GSVA_EXACT_ROWTF = {"z": 0, "ecdf": 1, "none": 2, "gauss": 3}
+GSVA_KCDF_TABLE = 10001   # PLAIDHIP_GSVA_KCDF_TABLE
+
+
+def check_gsva_exact_args(tau, rowtf):
+    """the checks of plaidhip_gsva_exact that need no device: (tau, the row transform's code)"""
+    rowtf = rowtf if isinstance(rowtf, str) else rowtf[0]
+    tau = float(tau)
+    if not np.isfinite(tau) or tau < 0.0:
+        raise ValueError(f"gsva_exact: tau must be finite and >= 0 (got {tau:g})")
+    if rowtf not in GSVA_EXACT_ROWTF:
+        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
+    return tau, GSVA_EXACT_ROWTF[rowtf]
+
+
+def _scse(fn, head, X, Gp, Gi, remove_log2, score_mean):
+    """(S, whether the 2 ** x transform ran): the automatic decision is taken on the device (R/plaid.R:160-161)"""
+    removed = C.c_int(0)
+    S = _score(fn, head, X, Gp, Gi, _remove_log2(remove_log2), int(bool(score_mean)), post=(C.byref(removed),))
+    return S, bool(removed.value)
+
+
+def gsva_kcdf_table() -> np.ndarray:
+    """the 10,001 values of Phi on [0, 10] that the kernels of gsva_kcdf read (built on the host: needs no device)"""
+    T = np.empty(GSVA_KCDF_TABLE, dtype=np.float64)
+    check(_lib.load().plaidhip_gsva_kcdf_table(_np_ptr(T)))
+    return T
+
+
+SING_EXACT_MAX_GENES = 131072   # PLAIDHIP_GSEA_KS_MAX_GENES: the dispersion kernel's bitmap
+SING_EXACT_OUTPUTS = ("TotalScore", "UpScore", "DownScore", "TotalDispersion", "UpDispersion", "DownDispersion")
+
+
+def check_sing_exact_args(g, Gp, Dp, dispersion):
+    """the checks of plaidhip_sing_exact that need no device"""
+    if Dp is not None and len(Dp) != len(Gp):
+        raise ValueError(f"sing_exact: the down sets have {len(Dp) - 1} columns, the up sets {len(Gp) - 1}")
+    if dispersion and g > SING_EXACT_MAX_GENES:
+        raise _lib.PlaidHipError(_lib.EUNSUPPORTED,
+                                 f"sing_exact: nrow(X) = {g} (at most {SING_EXACT_MAX_GENES} rows with the dispersion)")
+
+
+def _sing_exact_call(fn, head, X, Gp, Gi, Dp, Di, center, dispersion, fill=None):
+    """fill: what the results hold before the call (the tests' sentinel); None leaves them uninitialised"""
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    down = Dp is not None
+    if down:
+        Dp, Di = _as_i32(Dp), _as_i32(Di)
+    check_sing_exact_args(g, Gp, Dp if down else None, dispersion)
+    m = len(Gp) - 1
+    want = [down, True, down, down and dispersion, bool(dispersion), down and dispersion]
+    outs = [(np.empty if fill is None else np.full)((m, n), *(() if fill is None else (fill,)), dtype=np.float64, order="F")
+            if w else None for w in want]
+    check(fn(*head, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), _np_ptr(Dp) if down else None, _np_ptr(Di) if down else None, m,
+             int(bool(center)), *[None if o is None else _np_ptr(o) for o in outs]))
+    return {name: o for name, o in zip(SING_EXACT_OUTPUTS, outs) if o is not None}
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -290,36 +415,16 @@ class Context:
         check(self.lib.plaidhip_dev_row_group_ssd(self.handle, A, ld, rows, n, y, mean, ssd))
 
     # ---- host-level (numpy in, numpy out; the library stages through HBM) -------------
-    @staticmethod
-    def _result(out, m, n):
-        """the caller's own result buffer (any byte offset; Fortran order like an R matrix) or a fresh one"""
-        if out is None:
-            return np.empty((m, n), dtype=np.float64, order="F")
-        if out.shape != (m, n) or out.dtype != np.float64 or not out.flags.f_contiguous or not out.flags.writeable:
-            raise ValueError(f"out: a writeable Fortran-ordered float64 array of shape {(m, n)}")
-        return out
+    _result = staticmethod(_result)
+
+    def _host(self, name, X, Gp, Gi, *tail, **kw):
+        return _score(getattr(self.lib, "plaidhip_" + name), (self.handle,), X, Gp, Gi, *tail, **kw)
 
     def plaid_dense(self, X, Gp, Gi, stat="mean", normalize=True, out=None) -> np.ndarray:
-        X = _as_f64_fortran(X)
-        g, n = X.shape
-        Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-        m = len(Gp) - 1
-        S = self._result(out, m, n)
-        check(self.lib.plaidhip_plaid_dense(self.handle, _np_ptr(X), g, n, _np_ptr(Gp), _np_ptr(Gi), m,
-                                            STAT[stat], int(bool(normalize)), _np_ptr(S)))
-        return S
+        return self._host("plaid_dense", _as_f64_fortran(X), Gp, Gi, STAT[stat], int(bool(normalize)), dense=True, out=out)
 
     def plaid_csc(self, Xp, Xi, Xx, g: int, Gp, Gi, stat="mean", normalize=True, out=None) -> np.ndarray:
-        Xp, Xi = _as_i32(Xp), _as_i32(Xi)
-        Xx = np.ascontiguousarray(Xx, dtype=np.float64)
-        n = len(Xp) - 1
-        Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-        m = len(Gp) - 1
-        S = self._result(out, m, n)
-        check(self.lib.plaidhip_plaid_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n,
-                                          _np_ptr(Gp), _np_ptr(Gi), m, STAT[stat], int(bool(normalize)),
-                                          _np_ptr(S)))
-        return S
+        return self._host("plaid_csc", _slots(Xp, Xi, Xx, g), Gp, Gi, STAT[stat], int(bool(normalize)), out=out)
 
     def crossprod_weighted(self, Wp, Wi, Wx, g: int, Y=None, Yp=None, Yi=None, Yx=None) -> np.ndarray:
         """chunked_crossprod's t(x) %*% y for a sparse x with arbitrary stored values (R/plaid.R:100-123); y dense
@@ -340,18 +445,6 @@ class Context:
         S = np.empty((m, n), dtype=np.float64, order="F")
         check(self.lib.plaidhip_crossprod_weighted_csc(self.handle, _np_ptr(Wp), _np_ptr(Wi), _np_ptr(Wx), int(g), m,
                                                        _np_ptr(Yp), _np_ptr(Yi), _np_ptr(Yx), n, _np_ptr(S)))
-        return S
-
-    def sing_csc(self, Xp, Xi, Xx, g: int, Gp, Gi) -> np.ndarray:
-        """replaid.sing for a dgCMatrix X (zeros are ranked, R/plaid.R:215-217 with colranks' sparse branch :602-609)"""
-        Xp, Xi = _as_i32(Xp), _as_i32(Xi)
-        Xx = np.ascontiguousarray(Xx, dtype=np.float64)
-        n = len(Xp) - 1
-        Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-        m = len(Gp) - 1
-        S = np.empty((m, n), dtype=np.float64, order="F")
-        check(self.lib.plaidhip_sing_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n, _np_ptr(Gp),
-                                         _np_ptr(Gi), m, _np_ptr(S)))
         return S
 
     def normalize_medians(self, S, ignore_zero=None):
@@ -389,199 +482,80 @@ class Context:
         return R
 
     def sing_dense(self, X, Gp, Gi) -> np.ndarray:
-        X = _as_f64_fortran(X)
-        g, n = X.shape
-        Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-        m = len(Gp) - 1
-        S = np.empty((m, n), dtype=np.float64, order="F")
-        check(self.lib.plaidhip_sing_dense(self.handle, _np_ptr(X), g, n, _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(S)))
-        return S
+        return self._host("sing_dense", _as_f64_fortran(X), Gp, Gi, dense=True)
+
+    def sing_csc(self, Xp, Xi, Xx, g: int, Gp, Gi) -> np.ndarray:
+        """replaid.sing for a dgCMatrix X (zeros are ranked, R/plaid.R:215-217 with colranks' sparse branch :602-609)"""
+        return self._host("sing_csc", _slots(Xp, Xi, Xx, g), Gp, Gi)
 
     def ssgsea_dense(self, X, Gp, Gi, alpha=0.0) -> np.ndarray:
-        X = _as_f64_fortran(X)
-        g, n = X.shape
-        Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-        m = len(Gp) - 1
-        S = np.empty((m, n), dtype=np.float64, order="F")
-        check(self.lib.plaidhip_ssgsea_dense(self.handle, _np_ptr(X), g, n, _np_ptr(Gp), _np_ptr(Gi), m,
-                                             float(alpha), _np_ptr(S)))
-        return S
+        return self._host("ssgsea_dense", _as_f64_fortran(X), Gp, Gi, float(alpha), dense=True)
 
     def ssgsea_csc(self, Xp, Xi, Xx, g: int, Gp, Gi, alpha=0.0) -> np.ndarray:
-        Xp, Xi = _as_i32(Xp), _as_i32(Xi)
-        Xx = np.ascontiguousarray(Xx, dtype=np.float64)
-        n = len(Xp) - 1
-        Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-        m = len(Gp) - 1
-        S = np.empty((m, n), dtype=np.float64, order="F")
-        check(self.lib.plaidhip_ssgsea_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n,
-                                           _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), _np_ptr(S)))
+        return self._host("ssgsea_csc", _slots(Xp, Xi, Xx, g), Gp, Gi, float(alpha))
+
+    def ucell(self, X, Gp, Gi, k_full, rmax=1500.0):
+        kf = np.ascontiguousarray(k_full, dtype=np.float64)
+        return self._host("ucell", X, Gp, Gi, _np_ptr(kf), float(rmax))
+
+    def aucell(self, X, Gp, Gi, auc_max_rank):
+        return self._host("aucell", X, Gp, Gi, float(auc_max_rank))
+
+    def scse(self, X, Gp, Gi, remove_log2=None, score_mean=False):
+        S, self.last_scse_removed_log2 = _scse(self.lib.plaidhip_scse, (self.handle,), X, Gp, Gi, remove_log2, score_mean)
         return S
 
+    def ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False, single=True):
+        """plaidhip_ssgsea_exact: the original ssGSEA statistic (gao.ssgsea, single = TRUE) for any alpha; X dense or scipy
+        CSC (scored as its dense form), G aligned to X's rows.  single = False (plaidhip_ssgsea_exact_ks): the running sum's
+        value of largest magnitude, the classic GSEA enrichment score, instead of its sum"""
+        return self._host("ssgsea_exact" if single else "ssgsea_exact_ks", X, Gp, Gi, float(alpha), int(bool(scale)),
+                           int(bool(norm)))
 
-def _x_args(X):
-    """(Xp, Xi, values, g, n, keepalive) for a dense ndarray or a scipy CSC matrix."""
-    import scipy.sparse as sp
-    if sp.issparse(X):
-        X = sp.csc_matrix(X)
-        Xp, Xi = _as_i32(X.indptr), _as_i32(X.indices)
-        Xx = np.ascontiguousarray(X.data, dtype=np.float64)
-        return _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), X.shape[0], X.shape[1], (Xp, Xi, Xx)
-    Xd = _as_f64_fortran(X)
-    return None, None, _np_ptr(Xd), Xd.shape[0], Xd.shape[1], (Xd,)
+    def gsva_exact(self, X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True):
+        """plaidhip_gsva_exact: GSVA's random-walk statistic for any tau >= 0; rowtf "z" / "ecdf" (replaid.gsva's row
+        transforms), "none" or "gauss" (GSVA's Gaussian kernel CDF estimate: gsva_kcdf; at least 2 samples); X dense or scipy
+        CSC with sorted, distinct row indices (scored as its dense form), G aligned to X's rows"""
+        return self._host("gsva_exact", X, Gp, Gi, *check_gsva_exact_args(tau, rowtf), int(bool(max_diff)))
 
+    def gsva_kcdf(self, X):
+        """plaidhip_gsva_kcdf: V (genes x samples), GSVA's Gaussian kernel CDF estimate of every value among its gene's
+        samples (bandwidth sd / 4, the sums of include/plaidhip.h in sample order), the row transform "gauss" of gsva_exact;
+        X dense or scipy CSC (expanded on the device, the bits of its dense form); at least 2 samples"""
+        xp, xi, xv, g, n, keep = _x_args(X)
+        if n < 2:
+            raise ValueError(f"gsva_kcdf: the kernel CDF estimate needs at least 2 samples (got {n})")
+        V = np.empty((g, n), dtype=np.float64, order="F")
+        check(self.lib.plaidhip_gsva_kcdf(self.handle, xp, xi, xv, g, n, _np_ptr(V)))
+        return V
 
-def _ucell(self, X, Gp, Gi, k_full, rmax=1500.0):
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    kf = np.ascontiguousarray(k_full, dtype=np.float64)
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_ucell(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(kf),
-                                  float(rmax), _np_ptr(S)))
-    return S
+    @staticmethod
+    def gsva_kcdf_table() -> np.ndarray:
+        return gsva_kcdf_table()
 
+    def sing_exact(self, X, Gp, Gi, Dp=None, Di=None, center=True, dispersion=True):
+        """plaidhip_sing_exact: singscore's normalised score and dispersion (the MAD of the set's ranks) per set and sample;
+        X dense or scipy CSC with sorted, distinct row indices (scored as its dense form), the up sets G and the down sets D
+        (optional, as many columns) aligned to X's rows.  A dict of m x n matrices: UpScore [, UpDispersion], and with down
+        sets TotalScore, DownScore [, TotalDispersion, DownDispersion].  dispersion = False launches no per-pair kernel."""
+        return _sing_exact_call(self.lib.plaidhip_sing_exact, (self.handle,), X, Gp, Gi, Dp, Di, center, dispersion)
 
-def _aucell(self, X, Gp, Gi, auc_max_rank):
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_aucell(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m,
-                                   float(auc_max_rank), _np_ptr(S)))
-    return S
+    def gsva(self, X, Gp, Gi, tau=0.0, rowtf="z"):
+        return self._host("gsva", _as_f64_fortran(X), Gp, Gi, float(tau), _rowtf(rowtf), dense=True)
 
+    def gsva_csc(self, Xp, Xi, Xx, g, Gp, Gi, tau=0.0, rowtf="z"):
+        """plaidhip_gsva_csc: replaid.gsva on the slots of a g x n CSC matrix (no dense X on the host)"""
+        return self._host("gsva_csc", _slots(Xp, Xi, Xx, g), Gp, Gi, float(tau), _rowtf(rowtf))
 
-def _scse(self, X, Gp, Gi, remove_log2=None, score_mean=False):
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    rl = -1 if remove_log2 is None else int(bool(remove_log2))
-    removed = C.c_int(0)
-    check(self.lib.plaidhip_scse(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, rl,
-                                 int(bool(score_mean)), _np_ptr(S), C.byref(removed)))
-    self.last_scse_removed_log2 = bool(removed.value)   # the automatic decision is taken on the device (R/plaid.R:160-161)
-    return S
+    def plaid_test(self, X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
+        """plaidhip_plaid_test: returns sets x 6 (gsetFC, p.one, p.two, p.lm, p.meta, q.meta), G's column order"""
+        return _plaid_test(self.lib.plaidhip_plaid_test, (self.handle,), _as_f64_fortran(X), y, Gp, Gi, gsetX, tests,
+                           metap_method, dense=True)
 
-
-def _ssgsea_exact(self, X, Gp, Gi, alpha=0.25, scale=True, norm=False, single=True):
-    """plaidhip_ssgsea_exact: the original ssGSEA statistic (gao.ssgsea, single = TRUE) for any alpha; X dense or scipy
-    CSC (scored as its dense form), G aligned to X's rows.  single = False (plaidhip_ssgsea_exact_ks): the running sum's
-    value of largest magnitude, the classic GSEA enrichment score, instead of its sum"""
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    fn = self.lib.plaidhip_ssgsea_exact if single else self.lib.plaidhip_ssgsea_exact_ks
-    check(fn(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), int(bool(scale)), int(bool(norm)),
-             _np_ptr(S)))
-    return S
-
-
-GSVA_EXACT_ROWTF = {"z": 0, "ecdf": 1, "none": 2, "gauss": 3}
-GSVA_KCDF_TABLE = 10001   # PLAIDHIP_GSVA_KCDF_TABLE
-
-
-def check_gsva_exact_args(tau, rowtf):
-    """the checks of plaidhip_gsva_exact that need no device: (tau, the row transform's code)"""
-    rowtf = rowtf if isinstance(rowtf, str) else rowtf[0]
-    tau = float(tau)
-    if not np.isfinite(tau) or tau < 0.0:
-        raise ValueError(f"gsva_exact: tau must be finite and >= 0 (got {tau:g})")
-    if rowtf not in GSVA_EXACT_ROWTF:
-        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
-    return tau, GSVA_EXACT_ROWTF[rowtf]
-
-
-def _gsva_exact(self, X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True):
-    """plaidhip_gsva_exact: GSVA's random-walk statistic for any tau >= 0; rowtf "z" / "ecdf" (replaid.gsva's row
-    transforms), "none" or "gauss" (GSVA's Gaussian kernel CDF estimate: gsva_kcdf; at least 2 samples); X dense or scipy
-    CSC with sorted, distinct row indices (scored as its dense form), G aligned to X's rows"""
-    tau, tf = check_gsva_exact_args(tau, rowtf)
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_gsva_exact(self.handle, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, tau, tf,
-                                       int(bool(max_diff)), _np_ptr(S)))
-    return S
-
-
-def _gsva_kcdf(self, X):
-    """plaidhip_gsva_kcdf: V (genes x samples), GSVA's Gaussian kernel CDF estimate of every value among its gene's
-    samples (bandwidth sd / 4, the sums of include/plaidhip.h in sample order), the row transform "gauss" of gsva_exact;
-    X dense or scipy CSC (expanded on the device, the bits of its dense form); at least 2 samples"""
-    xp, xi, xv, g, n, keep = _x_args(X)
-    if n < 2:
-        raise ValueError(f"gsva_kcdf: the kernel CDF estimate needs at least 2 samples (got {n})")
-    V = np.empty((g, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_gsva_kcdf(self.handle, xp, xi, xv, g, n, _np_ptr(V)))
-    return V
-
-
-def gsva_kcdf_table() -> np.ndarray:
-    """the 10,001 values of Phi on [0, 10] that the kernels of gsva_kcdf read (built on the host: needs no device)"""
-    T = np.empty(GSVA_KCDF_TABLE, dtype=np.float64)
-    check(_lib.load().plaidhip_gsva_kcdf_table(_np_ptr(T)))
-    return T
-
-
-SING_EXACT_MAX_GENES = 131072   # PLAIDHIP_GSEA_KS_MAX_GENES: the dispersion kernel's bitmap
-SING_EXACT_OUTPUTS = ("TotalScore", "UpScore", "DownScore", "TotalDispersion", "UpDispersion", "DownDispersion")
-
-
-def check_sing_exact_args(g, Gp, Dp, dispersion):
-    """the checks of plaidhip_sing_exact that need no device"""
-    if Dp is not None and len(Dp) != len(Gp):
-        raise ValueError(f"sing_exact: the down sets have {len(Dp) - 1} columns, the up sets {len(Gp) - 1}")
-    if dispersion and g > SING_EXACT_MAX_GENES:
-        raise _lib.PlaidHipError(_lib.EUNSUPPORTED,
-                                 f"sing_exact: nrow(X) = {g} (at most {SING_EXACT_MAX_GENES} rows with the dispersion)")
-
-
-def _sing_exact_call(fn, head, X, Gp, Gi, Dp, Di, center, dispersion):
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    down = Dp is not None
-    if down:
-        Dp, Di = _as_i32(Dp), _as_i32(Di)
-    check_sing_exact_args(g, Gp, Dp if down else None, dispersion)
-    m = len(Gp) - 1
-    want = [down, True, down, down and dispersion, bool(dispersion), down and dispersion]
-    outs = [np.empty((m, n), dtype=np.float64, order="F") if w else None for w in want]
-    check(fn(*head, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), _np_ptr(Dp) if down else None, _np_ptr(Di) if down else None, m,
-             int(bool(center)), *[None if o is None else _np_ptr(o) for o in outs]))
-    return {name: o for name, o in zip(SING_EXACT_OUTPUTS, outs) if o is not None}
-
-
-def _sing_exact(self, X, Gp, Gi, Dp=None, Di=None, center=True, dispersion=True):
-    """plaidhip_sing_exact: singscore's normalised score and dispersion (the MAD of the set's ranks) per set and sample;
-    X dense or scipy CSC with sorted, distinct row indices (scored as its dense form), the up sets G and the down sets D
-    (optional, as many columns) aligned to X's rows.  A dict of m x n matrices: UpScore [, UpDispersion], and with down
-    sets TotalScore, DownScore [, TotalDispersion, DownDispersion].  dispersion = False launches no per-pair kernel."""
-    return _sing_exact_call(self.lib.plaidhip_sing_exact, (self.handle,), X, Gp, Gi, Dp, Di, center, dispersion)
-
-
-def _plaid_test(self, X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
-    """plaidhip_plaid_test: returns sets x 6 (gsetFC, p.one, p.two, p.lm, p.meta, q.meta), G's column order"""
-    X = _as_f64_fortran(X)
-    g, n = X.shape
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    if y.shape != (n,):
-        raise ValueError("y must have one entry per column of X")
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    sx = None
-    if gsetX is not None:
-        sx = _as_f64_fortran(gsetX)
-        if sx.shape != (m, n):
-            raise ValueError("gsetX must be sets x samples")
-    out = np.empty((m, 6), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_plaid_test(self.handle, _np_ptr(X), g, n, _np_ptr(y), _np_ptr(Gp), _np_ptr(Gi), m,
-                                       _np_ptr(sx) if sx is not None else None, int(tests), int(metap_method),
-                                       _np_ptr(out)))
-    return out
+    def plaid_test_csc(self, Xp, Xi, Xx, g, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
+        """plaidhip_plaid_test_csc: Context.plaid_test on the slots of a g x n CSC matrix"""
+        return _plaid_test(self.lib.plaidhip_plaid_test_csc, (self.handle,), _slots(Xp, Xi, Xx, g), y, Gp, Gi, gsetX, tests,
+                           metap_method)
 
 
 def plaid_test_finish(g, Gp, T, tot1, tot2, SM, n0, n1, tests=7, metap_method=0, lib=None):
@@ -606,71 +580,6 @@ def plaid_test_finish(g, Gp, T, tot1, tot2, SM, n0, n1, tests=7, metap_method=0,
     return out
 
 
-def _gsva(self, X, Gp, Gi, tau=0.0, rowtf="z"):
-    if rowtf not in ("z", "ecdf"):
-        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
-    X = _as_f64_fortran(X)
-    g, n = X.shape
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_gsva(self.handle, _np_ptr(X), g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(tau),
-                                 0 if rowtf == "z" else 1, _np_ptr(S)))
-    return S
-
-
-def _csc_args(Xp, Xi, Xx):
-    Xp, Xi = _as_i32(Xp), _as_i32(Xi)
-    Xx = np.ascontiguousarray(Xx, dtype=np.float64)
-    return Xp, Xi, Xx, len(Xp) - 1
-
-
-def _gsva_csc(self, Xp, Xi, Xx, g, Gp, Gi, tau=0.0, rowtf="z"):
-    """plaidhip_gsva_csc: replaid.gsva on the slots of a g x n CSC matrix (no dense X on the host)"""
-    if rowtf not in ("z", "ecdf"):
-        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
-    Xp, Xi, Xx, n = _csc_args(Xp, Xi, Xx)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_gsva_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n, _np_ptr(Gp),
-                                     _np_ptr(Gi), m, float(tau), 0 if rowtf == "z" else 1, _np_ptr(S)))
-    return S
-
-
-def _plaid_test_csc(self, Xp, Xi, Xx, g, y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
-    """plaidhip_plaid_test_csc: Context.plaid_test on the slots of a g x n CSC matrix"""
-    Xp, Xi, Xx, n = _csc_args(Xp, Xi, Xx)
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    if y.shape != (n,):
-        raise ValueError("y must have one entry per column of X")
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    sx = None
-    if gsetX is not None:
-        sx = _as_f64_fortran(gsetX)
-        if sx.shape != (m, n):
-            raise ValueError("gsetX must be sets x samples")
-    out = np.empty((m, 6), dtype=np.float64, order="F")
-    check(self.lib.plaidhip_plaid_test_csc(self.handle, _np_ptr(Xp), _np_ptr(Xi), _np_ptr(Xx), int(g), n, _np_ptr(y),
-                                           _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(sx) if sx is not None else None,
-                                           int(tests), int(metap_method), _np_ptr(out)))
-    return out
-
-
-Context.gsva = _gsva
-Context.gsva_csc = _gsva_csc
-Context.plaid_test = _plaid_test
-Context.plaid_test_csc = _plaid_test_csc
-Context.ucell = _ucell
-Context.aucell = _aucell
-Context.scse = _scse
-Context.ssgsea_exact = _ssgsea_exact
-Context.gsva_exact = _gsva_exact
-Context.sing_exact = _sing_exact
-Context.gsva_kcdf = _gsva_kcdf
-Context.gsva_kcdf_table = staticmethod(gsva_kcdf_table)
-
 _default_ctx: Context | None = None
 
 
@@ -691,168 +600,78 @@ def shard_bounds(n: int, ndev: int, k: int):
     return lo.value, hi.value
 
 
-def _devices_arg(devices):
+def _multi(name, devices):
+    """(plaidhip_<name>_multi, its head): devices an int (devices 0 .. n-1) or a list of ordinals"""
     if devices is None:
         raise ValueError("devices: a list of device ordinals or an int (the first ndev devices)")
+    fn = getattr(_lib.load(), f"plaidhip_{name}_multi")
     if isinstance(devices, int):
-        return None, int(devices), None
+        return fn, (None, int(devices))
     d = np.ascontiguousarray(devices, dtype=np.int32)
-    return _np_ptr(d), len(d), d
+    return fn, (d.ctypes.data_as(C.c_void_p), len(d))   # (the pointer object keeps d alive)
 
 
 def plaid_multi(X, Gp, Gi, stat="mean", normalize=True, devices=1) -> np.ndarray:
     """plaid() with the sample columns sharded over `devices` (an int: devices 0 .. n-1, or a list of ordinals)"""
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_plaid_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, STAT[stat], int(bool(normalize)),
-                                   _np_ptr(S)))
-    return S
+    return _score(*_multi("plaid", devices), X, Gp, Gi, STAT[stat], int(bool(normalize)))
 
 
 def sing_multi(X, Gp, Gi, devices=1) -> np.ndarray:
-    lib = _lib.load()
-    X = _as_f64_fortran(X)
-    g, n = X.shape
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_sing_multi(dp, nd, _np_ptr(X), g, n, _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(S)))
-    return S
+    return _score(*_multi("sing", devices), _as_f64_fortran(X), Gp, Gi, dense=True)
 
 
 def ssgsea_multi(X, Gp, Gi, alpha=0.0, devices=1) -> np.ndarray:
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_ssgsea_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), _np_ptr(S)))
-    return S
+    return _score(*_multi("ssgsea", devices), X, Gp, Gi, float(alpha))
 
 
 def ssgsea_exact_multi(X, Gp, Gi, alpha=0.25, scale=True, norm=False, devices=1, single=True) -> np.ndarray:
     """replaid.ssgsea.exact (Context.ssgsea_exact, either `single`) with the sample columns sharded over `devices`"""
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    fn = lib.plaidhip_ssgsea_exact_multi if single else lib.plaidhip_ssgsea_exact_ks_multi
-    check(fn(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(alpha), int(bool(scale)), int(bool(norm)),
-             _np_ptr(S)))
-    return S
+    return _score(*_multi("ssgsea_exact" if single else "ssgsea_exact_ks", devices), X, Gp, Gi, float(alpha), int(bool(scale)),
+                  int(bool(norm)))
 
 
 def gsva_exact_multi(X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True, devices=1) -> np.ndarray:
     """replaid.gsva.exact (Context.gsva_exact) with the sample columns sharded over `devices`; "ecdf" ranks all samples
     of a gene together and is refused over more than one device; "gauss" sends all of X to every device, which computes
     the kernel CDF estimate of its own columns (the one-device bits)"""
-    tau, tf = check_gsva_exact_args(tau, rowtf)
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_gsva_exact_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, tau, tf, int(bool(max_diff)),
-                                        _np_ptr(S)))
-    return S
+    args = check_gsva_exact_args(tau, rowtf)
+    return _score(*_multi("gsva_exact", devices), X, Gp, Gi, *args, int(bool(max_diff)))
 
 
 def sing_exact_multi(X, Gp, Gi, Dp=None, Di=None, center=True, dispersion=True, devices=1) -> dict:
     """replaid.sing.exact (Context.sing_exact) with the sample columns sharded over `devices`: the one-device bits"""
-    lib = _lib.load()
-    dp, nd, dkeep = _devices_arg(devices)
-    return _sing_exact_call(lib.plaidhip_sing_exact_multi, (dp, nd), X, Gp, Gi, Dp, Di, center, dispersion)
+    return _sing_exact_call(*_multi("sing_exact", devices), X, Gp, Gi, Dp, Di, center, dispersion)
 
 
 def ucell_multi(X, Gp, Gi, k_full, rmax=1500.0, devices=1) -> np.ndarray:
     """replaid.ucell (Context.ucell) with the sample columns sharded over `devices`"""
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
     kf = np.ascontiguousarray(k_full, dtype=np.float64)
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_ucell_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(kf), float(rmax),
-                                   _np_ptr(S)))
-    return S
+    return _score(*_multi("ucell", devices), X, Gp, Gi, _np_ptr(kf), float(rmax))
 
 
 def aucell_multi(X, Gp, Gi, auc_max_rank, devices=1) -> np.ndarray:
     """replaid.aucell (Context.aucell) with the sample columns sharded over `devices`"""
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_aucell_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(auc_max_rank), _np_ptr(S)))
-    return S
+    return _score(*_multi("aucell", devices), X, Gp, Gi, float(auc_max_rank))
 
 
 def scse_multi(X, Gp, Gi, remove_log2=None, score_mean=False, devices=1):
     """replaid.scse (Context.scse) with the sample columns sharded over `devices`: (S, removed_log2), the second
     telling whether the 2 ** x transform ran (removeLog2 = NULL is decided once, for the whole matrix)"""
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    rl = -1 if remove_log2 is None else int(bool(remove_log2))
-    removed = C.c_int(0)
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_scse_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, rl, int(bool(score_mean)),
-                                  _np_ptr(S), C.byref(removed)))
-    return S, bool(removed.value)
+    return _scse(*_multi("scse", devices), X, Gp, Gi, remove_log2, score_mean)
 
 
 def gsva_multi(X, Gp, Gi, tau=0.0, rowtf="z", devices=1) -> np.ndarray:
     """replaid.gsva (Context.gsva / gsva_csc) with the sample columns sharded over `devices`; rowtf "z" only -- "ecdf"
     ranks all samples of a gene together and is refused (score it on one device)"""
-    if rowtf not in ("z", "ecdf"):
-        raise ValueError("Error: unknown row transform" + str(rowtf))          # R/plaid.R:348
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    S = np.empty((m, n), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_gsva_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), m, float(tau),
-                                  0 if rowtf == "z" else 1, _np_ptr(S)))
-    return S
+    tf = _rowtf(rowtf)
+    return _score(*_multi("gsva", devices), X, Gp, Gi, float(tau), tf)
 
 
 def plaid_test_multi(X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0, devices=1) -> np.ndarray:
     """plaid.test (Context.plaid_test / plaid_test_csc) with the sample columns sharded over `devices`; X dense or scipy
     CSC.  The scores stay on the devices: only per-gene and per-set sums cross between them.  Returns sets x 6 (gsetFC,
     p.one, p.two, p.lm, p.meta, q.meta) in G's column order; dense X gives the single-device result bit for bit."""
-    lib = _lib.load()
-    xp, xi, xv, g, n, keep = _x_args(X)
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    if y.shape != (n,):
-        raise ValueError("y must have one entry per column of X")
-    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
-    m = len(Gp) - 1
-    sx = None
-    if gsetX is not None:
-        sx = _as_f64_fortran(gsetX)
-        if sx.shape != (m, n):
-            raise ValueError("gsetX must be sets x samples")
-    out = np.empty((m, 6), dtype=np.float64, order="F")
-    dp, nd, dkeep = _devices_arg(devices)
-    check(lib.plaidhip_plaid_test_multi(dp, nd, xp, xi, xv, g, n, _np_ptr(y), _np_ptr(Gp), _np_ptr(Gi), m,
-                                        _np_ptr(sx) if sx is not None else None, int(tests), int(metap_method),
-                                        _np_ptr(out)))
-    return out
+    return _plaid_test(*_multi("plaid_test", devices), X, y, Gp, Gi, gsetX, tests, metap_method)
 
 
 def multi_finalize():

@@ -8,7 +8,6 @@ the 64 lanes of a wavefront, the 64 bits of a map word and the 4,096 positions o
 each of them and one above.  A dgCMatrix must score as its dense form; sharding, the mixed precision mode and the Python
 alignment must not change a bit.
 """
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import scipy.sparse as sp
 
 from tests.helpers import exact_ref as er
 from tests.helpers import gsea_ks_walk as kw
+from tests.helpers import sharded_hooks
 from tests.test_gpu_ssgsea_exact import SHAPES, _sets, _sparse, _tied
 
 pytestmark = pytest.mark.gpu
@@ -137,31 +137,8 @@ def test_dgcmatrix_scores_equal_the_dense_form(hip_ctx, density):
 
 
 # ------------------------------------------------------------------------------------------------- 5. sharding, modes
-def _hook():
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_ssgsea_exact_ks_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int, C.c_int,
-                   vp]
-    return fn
-
-
 def _run_hook(nshards, X, Gp, Gi, alpha, norm, fail=-1):
-    fn = _hook()
-    g, n = X.shape
-    m = len(Gp) - 1
-    S = np.full((m, n), np.nan, order="F")
-    if sp.issparse(X):
-        X = sp.csc_matrix(X)
-        p_ = np.ascontiguousarray(X.indptr, dtype=np.int32)
-        i_ = np.ascontiguousarray(X.indices, dtype=np.int32)
-        x_ = np.ascontiguousarray(X.data, dtype=np.float64)
-        xp, xi, xv = p_.ctypes.data, i_.ctypes.data, x_.ctypes.data
-    else:
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        xp, xi, xv = None, None, Xf.ctypes.data
-    rc = fn(0, nshards, fail, xp, xi, xv, g, n, Gp.ctypes.data, Gi.ctypes.data, m, float(alpha), 1, int(norm), S.ctypes.data)
-    return rc, S
+    return sharded_hooks.score("ssgsea_exact_ks", nshards, X, Gp, Gi, float(alpha), 1, int(norm), fail=fail)
 
 
 @pytest.mark.parametrize("kind", ["dense", "csc"])

@@ -17,6 +17,7 @@ import scipy.sparse as sp
 from tests.helpers import exact_ref as er
 from tests.helpers import gsva_kcdf as gk
 from tests.helpers import gsva_walk as gw
+from tests.helpers import sharded_hooks
 from tests.test_gpu_ssgsea_exact import _sets
 
 pytestmark = pytest.mark.gpu
@@ -240,25 +241,7 @@ def test_dgcmatrix_scores_as_its_dense_form(hip_ctx, density):
 # ------------------------------------------------------------------------------------------------- 3. sharding, modes
 def _run_hook(nshards, X, Gp, Gi, tau, max_diff):
     """plaidhip_gsva_exact_multi's engine with nshards contexts on one device (the library's debug hook), rowtf = 3"""
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_gsva_exact_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int, C.c_int,
-                   vp]
-    g, n = X.shape
-    m = len(Gp) - 1
-    S = np.full((m, n), np.nan, order="F")
-    if sp.issparse(X):
-        X = sp.csc_matrix(X)
-        p_ = np.ascontiguousarray(X.indptr, dtype=np.int32)
-        i_ = np.ascontiguousarray(X.indices, dtype=np.int32)
-        x_ = np.ascontiguousarray(X.data, dtype=np.float64)
-        xp, xi, xv = p_.ctypes.data, i_.ctypes.data, x_.ctypes.data
-    else:
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        xp, xi, xv = None, None, Xf.ctypes.data
-    rc = fn(0, nshards, -1, xp, xi, xv, g, n, Gp.ctypes.data, Gi.ctypes.data, m, float(tau), 3, int(max_diff), S.ctypes.data)
-    return rc, S
+    return sharded_hooks.score("gsva_exact", nshards, X, Gp, Gi, float(tau), 3, int(max_diff))
 
 
 @pytest.mark.parametrize("kind", ["dense", "csc"])

@@ -6,12 +6,13 @@ comparisons below say: every sharding equals the one-shard run.  Dense X bit for
 across the shards in the one-shard order); a dgCMatrix must agree with the one-shard run and with the oracle within the
 suite's tolerance, and `removed_log2` must be the one-shard run's.
 """
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 import scipy.sparse as sp
+
+from tests.helpers import sharded_hooks
 
 pytestmark = pytest.mark.gpu
 
@@ -32,38 +33,7 @@ def _oracle():
     return plaid_oracle
 
 
-def _hook():
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_scorer_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_double,
-                   C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.POINTER(C.c_int)]
-    return fn
-
-
-def run(nshards, method, X, Gp, Gi, fail=-1, k_full=None, rmax=1500.0, auc_max_rank=1.0, remove_log2=None,
-        score_mean=False, tau=0.0, rowtf=0):
-    """(status, S, removed_log2) of the sharded engine with nshards contexts on device 0; X dense or scipy CSC"""
-    fn = _hook()
-    g, n = X.shape
-    m = len(Gp) - 1
-    S = np.full((m, n), np.nan, order="F")
-    Gp, Gi = np.ascontiguousarray(Gp, dtype=np.int32), np.ascontiguousarray(Gi, dtype=np.int32)
-    kf = np.ascontiguousarray(k_full if k_full is not None else np.zeros(m), dtype=np.float64)
-    removed = C.c_int(-7)
-    rl = -1 if remove_log2 is None else int(bool(remove_log2))
-    if sp.issparse(X):
-        X = sp.csc_matrix(X)
-        p_ = np.ascontiguousarray(X.indptr, dtype=np.int32)
-        i_ = np.ascontiguousarray(X.indices, dtype=np.int32)
-        x_ = np.ascontiguousarray(X.data, dtype=np.float64)
-        xp, xi, xv = p_.ctypes.data, i_.ctypes.data, x_.ctypes.data
-    else:
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        xp, xi, xv = None, None, Xf.ctypes.data
-    rc = fn(0, nshards, fail, method, xp, xi, xv, g, n, Gp.ctypes.data, Gi.ctypes.data, m, kf.ctypes.data, float(rmax),
-            float(auc_max_rank), rl, int(bool(score_mean)), float(tau), int(rowtf), S.ctypes.data, C.byref(removed))
-    return rc, S, removed.value
+run = sharded_hooks.scorer
 
 
 def _ctx_args(X):

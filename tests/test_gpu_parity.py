@@ -1335,31 +1335,15 @@ def test_multi_device_engine_with_several_shards_on_one_gpu(hip_ctx, nshards):
     flags / {sum, count} reductions, shards of unequal size, empty shards (n < nshards), and a shard that fails (the call
     returns an error instead of hanging).  Dense input must equal the one-context result bit for bit; CSC input takes
     the same kernel for every sharding (chosen from the global density) and is compared with the oracle tolerance."""
-    import ctypes as C
     import plaid_amd
     from plaid_amd import synth as sy
     from plaid_amd._lib import load
+    from tests.helpers import sharded_hooks
     lib = load()
-    fn = lib.plaidhip_debug_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int, C.c_int,
-                   C.c_double, vp]
 
     def run(method, X, Gp, Gi, stat=0, normalize=1, alpha=0.0, fail=-1, Xcsc=None):
-        g = X.shape[0] if Xcsc is None else Xcsc.shape[0]
-        n = X.shape[1] if Xcsc is None else Xcsc.shape[1]
-        m = len(Gp) - 1
-        S = np.full((m, n), np.nan, order="F")
-        if Xcsc is None:
-            Xf = np.asfortranarray(X)
-            rc = fn(0, nshards, fail, method, None, None, Xf.ctypes.data, g, n, Gp.ctypes.data, Gi.ctypes.data, m, stat,
-                    normalize, alpha, S.ctypes.data)
-        else:
-            p_, i_, x_ = (np.ascontiguousarray(Xcsc.indptr, dtype=np.int32), np.ascontiguousarray(Xcsc.indices, dtype=np.int32),
-                          np.ascontiguousarray(Xcsc.data, dtype=np.float64))
-            rc = fn(0, nshards, fail, method, p_.ctypes.data, i_.ctypes.data, x_.ctypes.data, g, n, Gp.ctypes.data,
-                    Gi.ctypes.data, m, stat, normalize, alpha, S.ctypes.data)
-        return rc, S
+        return sharded_hooks.score("", nshards, X if Xcsc is None else Xcsc, Gp, Gi, stat, normalize, alpha, fail=fail,
+                                   method=method)
 
     g, m = 9000, 150
     Gp, Gi = sy.geneset_csc(g, m, kmax=300)

@@ -167,30 +167,17 @@ def test_normalize_medians_of_61k_scores_with_many_ties(hip_ctx):
 def test_multi_shard_engine_on_the_reference_shaped_collection(hip_ctx, nshards):
     """plaidhip_*_multi's engine (thread per shard) with the 61,459-set collection: dense plaid / sing / ssgsea equal the
     one-context results bit for bit, the sparse route meets the oracle"""
-    import ctypes as C
     from plaid_amd import synth as sy
     from plaid_amd._lib import load
-    lib = load()
-    fn = lib.plaidhip_debug_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int, C.c_int,
-                   C.c_double, vp]
+    from tests.helpers import sharded_hooks
     g, m = 12010, 61459
     Gp, Gi, G, rn = _collection(g, m)
     n = 2 * nshards + 1
     X = sy.dense_columns(g, 0, n, tied=True)
 
     def run(method, Xf=None, Xs=None, alpha=0.0):
-        S = np.full((m, n), np.nan, order="F")
-        if Xs is None:
-            rc = fn(0, nshards, -1, method, None, None, Xf.ctypes.data, g, n, Gp.ctypes.data, Gi.ctypes.data, m, 0, 1, alpha,
-                    S.ctypes.data)
-        else:
-            p_, i_, x_ = (np.ascontiguousarray(Xs.indptr, dtype=np.int32), np.ascontiguousarray(Xs.indices, dtype=np.int32),
-                          np.ascontiguousarray(Xs.data, dtype=np.float64))
-            rc = fn(0, nshards, -1, method, p_.ctypes.data, i_.ctypes.data, x_.ctypes.data, g, n, Gp.ctypes.data, Gi.ctypes.data,
-                    m, 0, 1, alpha, S.ctypes.data)
-        assert rc == 0, lib.plaidhip_last_error_string()
+        rc, S = sharded_hooks.score("", nshards, Xf if Xs is None else Xs, Gp, Gi, 0, 1, alpha, method=method)
+        assert rc == 0, load().plaidhip_last_error_string()
         return S
 
     Xf = np.asfortranarray(X)

@@ -7,7 +7,6 @@ kernel has ONE route for every set size; its seams are the 64 lanes of a wavefro
 4,096 positions of a run of 64 words.  A dgCMatrix scores as its dense form; sharding, the mixed precision mode and the
 Python alignment must not change a bit.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -16,6 +15,7 @@ import scipy.sparse as sp
 
 from tests.helpers import exact_ref as er
 from tests.helpers import sing_mad as sm
+from tests.helpers import sharded_hooks
 from tests.test_gpu_ssgsea_exact import SHAPES, _sets, _sparse, _tied
 from tests.test_sing_exact_ref import pbmc_case
 
@@ -162,31 +162,8 @@ def test_dgcmatrix_equals_the_dense_form(hip_ctx, density):
 
 
 # --------------------------------------------------------------------------------------------------- 5. sharding, modes
-def _hook():
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_sing_exact_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int] + [vp] * 6
-    return fn
-
-
 def _run_hook(nshards, X, Gp, Gi, Dp, Di, center=True, fail=-1):
-    fn = _hook()
-    g, n = X.shape
-    m = len(Gp) - 1
-    outs = [np.full((m, n), -7.0, order="F") for _ in range(6)]
-    if sp.issparse(X):
-        X = sp.csc_matrix(X)
-        p_ = np.ascontiguousarray(X.indptr, dtype=np.int32)
-        i_ = np.ascontiguousarray(X.indices, dtype=np.int32)
-        x_ = np.ascontiguousarray(X.data, dtype=np.float64)
-        xp, xi, xv = p_.ctypes.data, i_.ctypes.data, x_.ctypes.data
-    else:
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        xp, xi, xv = None, None, Xf.ctypes.data
-    rc = fn(0, nshards, fail, xp, xi, xv, g, n, Gp.ctypes.data, Gi.ctypes.data, Dp.ctypes.data, Di.ctypes.data, m, int(center),
-            *[o.ctypes.data for o in outs])
-    return rc, dict(zip(sm.NAMES, outs))
+    return sharded_hooks.sing_exact(nshards, X, Gp, Gi, Dp, Di, center, fail=fail)
 
 
 @pytest.mark.parametrize("kind", ["dense", "csc"])

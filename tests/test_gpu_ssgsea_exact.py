@@ -5,7 +5,6 @@ the pinned epilogue evaluated in numpy bit for bit.  Other alphas: within a boun
 reproduce colranks(ties = "last") and colranks(ties = "average", power = alpha) bit for bit; a dgCMatrix must score as its
 dense form; the sharded engine, the mixed precision mode and the Python alignment must not change a bit.
 """
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import scipy.sparse as sp
 
 from tests.helpers import exact_ref as er
 from tests.helpers import ssgsea_walk as sw
+from tests.helpers import sharded_hooks
 
 pytestmark = pytest.mark.gpu
 
@@ -214,31 +214,8 @@ def test_norm_divides_by_the_range_and_nan_spreads(hip_ctx):
 
 
 # ------------------------------------------------------------------------------------------------- sharding
-def _hook():
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_ssgsea_exact_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int, C.c_int,
-                   vp]
-    return fn
-
-
 def _run_hook(nshards, X, Gp, Gi, alpha, norm, fail=-1):
-    fn = _hook()
-    g, n = X.shape
-    m = len(Gp) - 1
-    S = np.full((m, n), np.nan, order="F")
-    if sp.issparse(X):
-        X = sp.csc_matrix(X)
-        p_ = np.ascontiguousarray(X.indptr, dtype=np.int32)
-        i_ = np.ascontiguousarray(X.indices, dtype=np.int32)
-        x_ = np.ascontiguousarray(X.data, dtype=np.float64)
-        xp, xi, xv = p_.ctypes.data, i_.ctypes.data, x_.ctypes.data
-    else:
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        xp, xi, xv = None, None, Xf.ctypes.data
-    rc = fn(0, nshards, fail, xp, xi, xv, g, n, Gp.ctypes.data, Gi.ctypes.data, m, float(alpha), 1, int(norm), S.ctypes.data)
-    return rc, S
+    return sharded_hooks.score("ssgsea_exact", nshards, X, Gp, Gi, float(alpha), 1, int(norm), fail=fail)
 
 
 @pytest.mark.parametrize("kind", ["dense", "csc"])

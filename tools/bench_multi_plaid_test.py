@@ -8,7 +8,6 @@ one: bit equality, or the largest relative difference.  With more than one GPU a
     python3 tools/bench_multi_plaid_test.py [--reps 3] [--shapes dense,csc]
     python3 tools/bench_multi_plaid_test.py --profile multi|single   (shape 1 alone, for a rocprofv3 --kernel-trace run)"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -34,22 +33,10 @@ def _median_ms(fn, reps):
 
 
 def _hook(X, y, Gp, Gi, nshards, out):
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_plaid_test_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int, C.c_int,
-                   vp]
-    g, n = X.shape
-    m = len(Gp) - 1
-    if sp.issparse(X):
-        xp, xi, xv = X.indptr.ctypes.data, X.indices.ctypes.data, X.data.ctypes.data
-    else:
-        xp, xi, xv = None, None, X.ctypes.data
+    from tests.helpers import sharded_hooks
 
     def call():
-        rc = fn(0, nshards, -1, xp, xi, xv, g, n, y.ctypes.data, Gp.ctypes.data, Gi.ctypes.data, m, None, TESTS, 0,
-                out.ctypes.data)
-        assert rc == 0
+        assert sharded_hooks.plaid_test(nshards, X, y, Gp, Gi, tests=TESTS, out=out)[0] == 0
         return out
     return call
 

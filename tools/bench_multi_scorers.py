@@ -4,7 +4,6 @@ through the N-shards-on-one-device test hook (5 shards against 1: the same call,
 Median wall milliseconds of --reps calls after one warm-up call each; prints one JSON line.
     python3 tools/bench_multi_scorers.py [--genes 20000 --cells 10000 --sets 5000 --density 0.05 --reps 3]"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -28,20 +27,12 @@ def _median_ms(fn, reps):
 
 
 def _hook_gsva(X, Gp, Gi, nshards):
-    from plaid_amd._lib import load
-    fn = load().plaidhip_debug_scorer_sharded_on_one_device
-    vp = C.c_void_p
-    fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_double,
-                   C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.POINTER(C.c_int)]
-    g, n = X.shape
+    from tests.helpers import sharded_hooks
     m = len(Gp) - 1
-    S = np.empty((m, n), order="F")
-    removed = C.c_int(0)
+    S, kf = np.empty((m, X.shape[1]), order="F"), np.zeros(m)   # (allocated once: the timed call touches no fresh page)
 
     def call():
-        rc = fn(0, nshards, -1, 6, None, None, X.ctypes.data, g, n, Gp.ctypes.data, Gi.ctypes.data, m, None, 0.0, 0.0, -1, 0,
-                0.0, 0, S.ctypes.data, C.byref(removed))
-        assert rc == 0
+        assert sharded_hooks.scorer(nshards, sharded_hooks.GSVA, X, Gp, Gi, k_full=kf, out=S)[0] == 0
     return call
 
 
