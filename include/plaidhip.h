@@ -535,6 +535,70 @@ int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
                         const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
                         double* total, double* up, double* down, double* total_disp, double* up_disp, double* down_disp);
 
+/* replaid.ucell.exact and replaid.aucell.exact: the statistics of UCell (ScoreSignatures_UCell) and of AUCell
+ * (AUCell_calcAUC) on truncated ranks, where replaid.ucell is "near exact" (max(rX) - rX for the descending rank, plaid()'s
+ * median normalisation and its 1e-8) and replaid.aucell a ramp with a factor of 1.08.  The formulas follow the two packages
+ * AS RECALLED: their sources are not in this tree, so the statistics are pinned here, operation for operation, and tested
+ * against these words.
+ * Common to both, per sample column: N = g rows; all rows of X are ranked before the alignment with the sets, as in
+ * replaid.ucell.  X dense (Xp == NULL) or a dgCMatrix (rows increasing inside a column) whose implicit zeros are ranked; it
+ * is never expanded, on the host or on the device: no g x n buffer of any type is allocated for it, device memory is
+ * O(nnz + n T + m n).  A column holding a NaN gives NaN in all of its outputs.  k: the aligned members of a set.  fp64 and
+ * integers in every precision mode.
+ *
+ * plaidhip_ucell_exact, T = max_rank, an integer in 1..N:
+ *  1. d = rank(-x, ties = "average") = N + 1 - colranks(x, "average"): half-integers.
+ *  2. UCell's truncation, which is not pmin: c = (d <= T) ? d : T + 1.  Weight u = T + 1 - c: a half-integer >= 0, zero for
+ *     every gene with d > T.  A tie group is weighted as a whole or not at all: the group at the boundary, with `a` strictly
+ *     larger values and `c` members, has the average rank a + (c + 1) / 2 and is weighted exactly when that is <= T.
+ *  3. K = k_full[j] when impute != 0 (UCell's missing_genes = "impute": absent members count with rank T + 1; k_full[j] an
+ *     integer >= k), else K = k.  In integers: S2 = 2 sum u over the aligned members;
+ *     U2 = 2 K (T + 1) - S2 - K (K + 1);  auc = 1.0 - (double)U2 / (double)(2 K T): one correctly rounded division and one
+ *     subtraction, no product of doubles.  auc < 0 gives 0.0.  K = 0 gives NaN.
+ *     2 N T >= 2^53 (or 2 K (T + 1) + K (K + 1) >= 2^53 for an imputed K): PLAIDHIP_EUNSUPPORTED before any device work.
+ *  4. Down sets (Dp / Di, aligned to X's rows, m columns; their imputed sizes in k_full_down): column j pairs with column j
+ *     of the up sets.  down = the same statistic on the down members;  total = up - w_neg * down: one multiplication and one
+ *     subtraction, never contracted.  total < 0 gives 0.0.  An empty down column makes total NaN.  w_neg finite and >= 0.
+ *     Three nullable m x n outputs; what is NULL is not computed.  Dp == NULL with total or down non-NULL: PLAIDHIP_EINVAL.
+ *     impute != 0 with k_full == NULL (or, beside down sets, k_full_down == NULL): PLAIDHIP_EINVAL.
+ *
+ * plaidhip_aucell_exact, A = auc_max_rank, an integer in 1..N:
+ *  1. AUCell breaks ties at random; here they are broken by row order, so that the result is a function of its input:
+ *     pos = N + 1 - rank(x, ties = "last"), distinct integers, the earlier row of a tie taking the smaller pos.
+ *  2. area = sum (A - pos) over the members with pos < A (strict, as AUCell's x < aucThreshold);  kk = min(k, A - 1);
+ *     maxAUC = kk A - kk (kk + 1) / 2, both exact integers;  score = (double)area / (double)maxAUC: one division.
+ *     k = 0 or A = 1 gives 0 / 0 = NaN.  2 N A >= 2^53: PLAIDHIP_EUNSUPPORTED before any device work.
+ *  3. No normalize_medians.  Not offered: random ties, and AUCell's older normalisation (A k).                            */
+int plaidhip_ucell_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                         const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double max_rank,
+                         double w_neg, int impute, const double* k_full, const double* k_full_down, double* total, double* up,
+                         double* down);
+int plaidhip_aucell_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank, double* S_out);
+
+/* The truncated-rank stage of the two on device operands, stream-ordered, no read-back: per column the compressed list
+ * (row, weight) of the entries whose weight is not zero, rows ascending, as CSC slots Wp (n + 1), Wi, Wx (doubles) that
+ * plaidhip_dev_spmm_csc_f64 takes (stat = sum gives S2 / 2, or the area).  mode PLAIDHIP_TRUNC_UCELL: weights u;
+ * PLAIDHIP_TRUNC_AUCELL: A - pos for the first A - 1 positions.  T in 1..g, g < 2^26.  A count pass, an exclusive scan on
+ * the device and a fill pass place the columns; `capacity` (entries of Wi / Wx) must cover what the columns can take:
+ * n min(g, 2 T - 1) (UCell) or n min(g, T - 1) (AUCell), and for _csc nnz (UCell) or n min(g, T - 1) (AUCell); else
+ * PLAIDHIP_EINVAL.  colnan: n words, 1 for a column holding a NaN (which gets no entries); counts: n words of scratch.
+ * Dense: X g x n (leading dimension ldx), R_scratch g x n doubles.
+ * _csc: the slots of a g x n matrix, rows increasing inside a column, Xp[0] = 0, nnz = Xp[n], max_col_nnz the longest
+ * column; scratch 2 nnz doubles.  All zeros, stored and implicit, form one tie group.  UCell: where that group is weighted
+ * it is not enumerated: u0[c] (n doubles) receives its weight and every stored non-zero entry the weight u - u0 (any
+ * sign; entries whose shifted weight is zero are left out), so that sum u over a set = sum of its entries + k u0[c].
+ * AUCell: u0 is zeroed, and the first zero rows in row order, implicit ones included, fill the positions the positive
+ * values leave below A.                                                                                              */
+#define PLAIDHIP_TRUNC_UCELL 0
+#define PLAIDHIP_TRUNC_AUCELL 1
+int plaidhip_dev_truncated_ranks_f64(plaidhip_ctx* ctx, const void* X, int64_t ldx, int32_t g, int32_t n, int mode, int64_t T,
+                                     void* R_scratch, void* colnan, void* counts, void* Wp, void* Wi, void* Wx,
+                                     int64_t capacity);
+int plaidhip_dev_truncated_ranks_csc_f64(plaidhip_ctx* ctx, const void* Xp, const void* Xi, const void* Xx, int32_t g, int32_t n,
+                                         int32_t max_col_nnz, int64_t nnz, int mode, int64_t T, void* scratch, void* colnan,
+                                         void* counts, void* u0, void* Wp, void* Wi, void* Wx, int64_t capacity);
+
 /* ---- several GPUs of one node from ONE host process (the R session): multi.cpp ----------------------
  * The sample columns are cut into ndev contiguous shards (plaidhip_shard_bounds); a host thread per device
  * moves its shard over its own PCIe link (pipelined through pinned staging), runs the same kernels, and the
@@ -585,6 +649,17 @@ int plaidhip_sing_exact_multi(const int* devices, int ndev, const int32_t* Xp, c
                               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
                               int32_t m, int center, double* total, double* up, double* down, double* total_disp,
                               double* up_disp, double* down_disp);
+/* plaidhip_ucell_exact and plaidhip_aucell_exact over several devices, sharded by sample column.  Nothing couples the
+ * shards and every sum is exact: every sharding returns the one-device bits, dense and dgCMatrix.  Memory per shard (nloc =
+ * its columns): dense X g x nloc and its ranks panel by panel; a dgCMatrix its slots, 2 nnz doubles and the compressed
+ * weights.  The argument checks and the device list's run before any device is touched.                               */
+int plaidhip_ucell_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
+                               int32_t m, double max_rank, double w_neg, int impute, const double* k_full,
+                               const double* k_full_down, double* total, double* up, double* down);
+int plaidhip_aucell_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank,
+                                double* S_out);
 /* replaid.ucell / aucell / scse / gsva over several devices: the arguments and results of plaidhip_ucell, plaidhip_aucell,
  * plaidhip_scse and plaidhip_gsva (rowtf = 0, "z"), X dense or a dgCMatrix as above.  The argument checks run before any
  * device is touched.  What couples the shards is combined on the host: max(rX) (R/plaid.R:278, 306, 354), the min / max

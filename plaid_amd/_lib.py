@@ -94,6 +94,14 @@ SIGNATURES = {
     "plaidhip_ssgsea_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
     "plaidhip_dev_sing_mad_f64": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i64],
     "plaidhip_sing_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_ucell_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _int, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_aucell_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
+    "plaidhip_ucell_exact_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _int, _vp, _vp, _vp,
+                                   _vp, _vp],
+    "plaidhip_aucell_exact_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp],
+    "plaidhip_dev_truncated_ranks_f64": [_vp, _vp, _i64, _i32, _i32, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64],
+    "plaidhip_dev_truncated_ranks_csc_f64": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _i64],
     "plaidhip_dev_gsva_ks_f64": [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _vp, _i64],
     "plaidhip_gsva_exact": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _int, _int, _vp],
     "plaidhip_gsva_kcdf": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],

@@ -388,6 +388,63 @@ def replaid_sing_exact(X, matG, matD=None, center=True, dispersion=True, ctx: Co
     return {name: NamedMatrix(S, matG.colnames, X.colnames) for name, S in out.items()}
 
 
+def replaid_ucell_exact(X, matG, matD=None, maxRank=1500, w_neg=1, k_full=None, impute=False, ctx: Context | None = None):
+    """replaid.ucell.exact(): UCell's statistic (include/plaidhip.h: plaidhip_ucell_exact) where replaid.ucell is near exact:
+    the descending average ranks truncated by UCell's rule (d <= maxRank ? d : maxRank + 1), the Mann-Whitney form in
+    integers closed by one division, no median normalisation.  matD (optional): the down sets, column j pairing with column
+    j of matG; TotalScore = UpScore - w_neg * DownScore, clamped at 0.  impute = True is UCell's missing_genes = "impute":
+    the members of a set that X lacks count with rank maxRank + 1 (k_full = colSums(matG != 0) of the un-aligned matrix; a k_full of the caller's overrides it for the up sets).
+    A sparse X is never expanded.  Returns a dict of NamedMatrix: UpScore, and with matD also TotalScore and DownScore.
+    The arguments are checked before any device is touched."""
+    from .engine import check_truncated_rank
+    X, matG = as_named(X), as_named(matG)
+    if matD is not None:
+        matD = as_named(matD)
+        if matD.shape[1] != matG.shape[1]:
+            raise ValueError(f"ucell_exact: matD has {matD.shape[1]} columns, matG {matG.shape[1]}")
+    w_neg = float(w_neg)
+    if not np.isfinite(w_neg) or w_neg < 0.0:
+        raise ValueError(f"ucell_exact: w_neg must be finite and >= 0 (got {w_neg:g})")
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    T = check_truncated_rank("ucell_exact", "maxRank", X.shape[0], maxRank)
+    dpat = (None, None)
+    if matD is not None:
+        dpat = aligned_pattern(X, matD)
+        if dpat is None:   # no down gene among X's rows: every down column is empty
+            dpat = (np.zeros(matD.shape[1] + 1, dtype=np.int32), np.zeros(0, dtype=np.int32))
+    impute = bool(impute) or k_full is not None
+    kf = (np.asarray(k_full, dtype=np.float64) if k_full is not None else _set_sizes_unaligned(matG)) if impute else None
+    kd = _set_sizes_unaligned(matD) if impute and matD is not None else None
+    ctx = ctx or default_context()
+    V = _canonical_csc(X.values) if X.is_sparse else X.values   # the CSC slots go to the device: no dense X anywhere
+    out = ctx.ucell_exact(V, pat[0], pat[1], dpat[0], dpat[1], T, w_neg, kf, kd)
+    return {name: NamedMatrix(S, matG.colnames, X.colnames) for name, S in out.items()}
+
+
+def replaid_aucell_exact(X, matG, aucMaxRank=None, ctx: Context | None = None):
+    """replaid.aucell.exact(): AUCell's AUC (include/plaidhip.h: plaidhip_aucell_exact) where replaid.aucell is a ramp with a
+    factor of 1.08: the area under the recovery curve over the first aucMaxRank - 1 positions, divided by the largest area
+    a set of its size can reach.  aucMaxRank defaults to ceiling(0.05 * nrow(X)).  Ties are broken by row order (AUCell
+    breaks them at random); no median normalisation.  A sparse X is never expanded.  The arguments are checked before any
+    device is touched."""
+    from .engine import check_truncated_rank
+    X, matG = as_named(X), as_named(matG)
+    if aucMaxRank is None:
+        aucMaxRank = int(np.ceil(0.05 * X.shape[0]))
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    A = check_truncated_rank("aucell_exact", "aucMaxRank", X.shape[0], aucMaxRank)
+    ctx = ctx or default_context()
+    V = _canonical_csc(X.values) if X.is_sparse else X.values
+    S = ctx.aucell_exact(V, pat[0], pat[1], A)
+    return NamedMatrix(S, matG.colnames, X.colnames)
+
+
 _TEST_BITS = {"one": 1, "two": 2, "lm": 4}
 
 

@@ -1192,6 +1192,65 @@ int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
                                                    down_disp));
 } catch (...) { return plaidhip::on_exception(); }
 
+// replaid.ucell.exact / replaid.aucell.exact: the one-device forms of the sharded engine (multi.cpp: truncated_exact_worker)
+int plaidhip_ucell_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                         const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double max_rank,
+                         double w_neg, int impute, const double* k_full, const double* k_full_down, double* total, double* up,
+                         double* down) try {
+  PH_REQUIRE(!impute || k_full != nullptr || m == 0, "ucell_exact: impute needs k_full");
+  return dispatch(on_context(ctx), ucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, max_rank, w_neg,
+                                                    impute ? k_full : nullptr, impute ? k_full_down : nullptr, total, up, down));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_aucell_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank, double* S_out) try {
+  return dispatch(on_context(ctx), aucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, auc_max_rank, S_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the truncated-rank stage on device operands (kernels_trunc.hip), stream-ordered
+static int check_truncated_dev(const char* who, int32_t g, int32_t n, int mode, int64_t T) {
+  PH_REQUIRE(g > 0 && n >= 0 && g < (1 << 26), "%s: bad dims g=%d n=%d (at most 2^26 - 1 rows)", who, g, n);
+  PH_REQUIRE(mode == PLAIDHIP_TRUNC_UCELL || mode == PLAIDHIP_TRUNC_AUCELL, "%s: bad mode %d", who, mode);
+  PH_REQUIRE(T >= 1 && T <= g, "%s: T = %lld outside 1..%d", who, (long long)T, g);
+  return PLAIDHIP_OK;
+}
+
+int plaidhip_dev_truncated_ranks_f64(plaidhip_ctx* ctx, const void* X, int64_t ldx, int32_t g, int32_t n, int mode, int64_t T,
+                                     void* R_scratch, void* colnan, void* counts, void* Wp, void* Wi, void* Wx,
+                                     int64_t capacity) try {
+  PH_CTX(ctx);
+  PH_TRY(check_truncated_dev("truncated_ranks", g, n, mode, T));
+  PH_REQUIRE(ldx >= g, "truncated_ranks: ldx = %lld < g", (long long)ldx);
+  if (n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(X && R_scratch && colnan && counts && Wp && Wi && Wx, "truncated_ranks: null X/R_scratch/colnan/counts/Wp/Wi/Wx");
+  const int64_t need = truncated_bound(mode, T, g, g, false) * n;
+  PH_REQUIRE(capacity >= need && need < ((int64_t)1 << 31), "truncated_ranks: capacity %lld, the columns may take %lld entries",
+             (long long)capacity, (long long)need);
+  return truncated_ranks_stage(ctx, mode, T, static_cast<const double*>(X), ldx, nullptr, nullptr, g, n, 0, 0,
+                               static_cast<double*>(R_scratch), static_cast<uint32_t*>(colnan), static_cast<int32_t*>(counts),
+                               static_cast<int32_t*>(Wp), static_cast<int32_t*>(Wi), static_cast<double*>(Wx), capacity, nullptr);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_truncated_ranks_csc_f64(plaidhip_ctx* ctx, const void* Xp, const void* Xi, const void* Xx, int32_t g, int32_t n,
+                                         int32_t max_col_nnz, int64_t nnz, int mode, int64_t T, void* scratch, void* colnan,
+                                         void* counts, void* u0, void* Wp, void* Wi, void* Wx, int64_t capacity) try {
+  PH_CTX(ctx);
+  PH_TRY(check_truncated_dev("truncated_ranks_csc", g, n, mode, T));
+  PH_REQUIRE(max_col_nnz >= 0 && max_col_nnz <= g && nnz >= 0, "truncated_ranks_csc: max_col_nnz = %d, nnz = %lld", max_col_nnz,
+             (long long)nnz);
+  if (n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Xp && (nnz == 0 || (Xi && Xx)) && scratch && colnan && counts && u0 && Wp && Wi && Wx,
+             "truncated_ranks_csc: null Xp/Xi/Xx/scratch/colnan/counts/u0/Wp/Wi/Wx");
+  const int64_t need = mode == PLAIDHIP_TRUNC_UCELL ? nnz : truncated_bound(mode, T, g, 0, true) * n;
+  PH_REQUIRE(capacity >= need && need < ((int64_t)1 << 31), "truncated_ranks_csc: capacity %lld, the columns may take %lld entries",
+             (long long)capacity, (long long)need);
+  if (mode == PLAIDHIP_TRUNC_AUCELL) PH_HIP(hipMemsetAsync(u0, 0, (size_t)n * 8, ctx->stream));
+  return truncated_ranks_stage(ctx, mode, T, static_cast<const double*>(Xx), 0, static_cast<const int32_t*>(Xp),
+                               static_cast<const int32_t*>(Xi), g, n, max_col_nnz, nnz, static_cast<double*>(scratch),
+                               static_cast<uint32_t*>(colnan), static_cast<int32_t*>(counts), static_cast<int32_t*>(Wp),
+                               static_cast<int32_t*>(Wi), static_cast<double*>(Wx), capacity, static_cast<double*>(u0));
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_gsva(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi,
                   int32_t m, double tau, int rowtf, double* S_out) try {
   return dispatch(on_context(ctx), gsva_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, tau, rowtf, S_out));

@@ -9,7 +9,7 @@ namespace plaidhip {
 // the ordinals are what the test hooks plaidhip_debug_sharded_on_one_device / _scorer_sharded_on_one_device take
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
-  kGsvaExact = 9, kSingExact = 10
+  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -54,6 +54,11 @@ struct Call : Operands {
   const int32_t* Di = nullptr;
   int center = 1;
   double* sx_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // ucell.exact: maxRank (aucell.exact: aucMaxRank), w_neg, the down sets (Dp / Di), the imputed set sizes (k_full for the up
+  // sets, k_full_down; null: the aligned sizes) and the nullable results sx_out[0..2] (total, up, down); aucell.exact: S_out
+  double max_rank = 0.0;
+  double w_neg = 1.0;
+  const double* k_full_down = nullptr;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -170,6 +175,30 @@ inline Call sing_exact_call(const Operands& x, const int32_t* Dp, const int32_t*
   c.center = center ? 1 : 0;
   double* const out[6] = {total, up, down, total_disp, up_disp, down_disp};
   for (int o = 0; o < 6; ++o) c.sx_out[o] = out[o];
+  return c;
+}
+// maxRank = T; K = k_full (null: the aligned size); total = up - w_neg * down (include/plaidhip.h: plaidhip_ucell_exact)
+inline Call ucell_exact_call(const Operands& x, const int32_t* Dp, const int32_t* Di, double max_rank, double w_neg,
+                             const double* k_full, const double* k_full_down, double* total, double* up, double* down) {
+  Call c = make_call(kUcellExact, x, nullptr);
+  c.stat = PLAIDHIP_STAT_SUM;
+  c.normalize = 0;
+  c.Dp = Dp;
+  c.Di = Di;
+  c.max_rank = max_rank;
+  c.w_neg = w_neg;
+  c.k_full = k_full;
+  c.k_full_down = k_full_down;
+  c.sx_out[0] = total;
+  c.sx_out[1] = up;
+  c.sx_out[2] = down;
+  return c;
+}
+inline Call aucell_exact_call(const Operands& x, double auc_max_rank, double* S_out) {
+  Call c = make_call(kAucellExact, x, S_out);
+  c.stat = PLAIDHIP_STAT_SUM;
+  c.normalize = 0;
+  c.max_rank = auc_max_rank;
   return c;
 }
 

@@ -495,6 +495,34 @@ int launch_sing_add(plaidhip_ctx* ctx, const double* A, const double* B, double*
 // g > PLAIDHIP_GSEA_KS_MAX_GENES: PLAIDHIP_EUNSUPPORTED.
 int launch_sing_mad(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* Rpos, int64_t ldp, const uint32_t* colnan,
                     int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S, int64_t lds);
+// kernels_trunc.hip: replaid.ucell.exact / replaid.aucell.exact (include/plaidhip.h: plaidhip_ucell_exact).  All stream-ordered.
+// mode: PLAIDHIP_TRUNC_UCELL / _AUCELL; T: maxRank or aucMaxRank.  The most entries a column of g rows (a CSC column of len
+// stored values) can get: what sizes the slots
+int64_t truncated_bound(int mode, int64_t T, int64_t g, int64_t len, bool sparse);
+// Y = the tie-free column whose min ranks are rank(x, "last") of the stored values of CSC columns, from their min ranks
+int launch_truncated_last_prep(plaidhip_ctx* ctx, const int32_t* Xp, const double* Rmin, int32_t n, int32_t max_col_nnz,
+                               double* Y);
+// count, scan, fill: the compressed columns (Wp n + 1, Wi, Wx; rows ascending) of the non-zero weights from the ranks R --
+// dense (Xp == nullptr: rank(x, "average") or, AUCell, rank(x, "last") of all g rows, leading dimension ldr) or of the stored
+// values of CSC columns among themselves (rows increasing in each column).  cnt: n words of scratch; cap: the entries of
+// Wi / Wx, behind which nothing is written.  u0 (CSC, UCell; n
+// doubles): the zeros' weight, which the entries' weights are shifted by.
+int launch_truncated_compact(plaidhip_ctx* ctx, int mode, int64_t T, const double* R, int64_t ldr, const int32_t* Xp,
+                             const int32_t* Xi, const double* Xx, int32_t g, int32_t n, const uint32_t* colnan, int32_t* cnt,
+                             int32_t* Wp, int32_t* Wi, double* Wx, int64_t cap, double* u0);
+// the pinned epilogues in place: Cu / Cd (nullable) hold the weight sums of the up / down sets, ku / kd the aligned set sizes
+// and Ku / Kd (nullable: k) the imputed ones; tot (nullable, needs Cu and Cd) = up - w_neg * down
+int launch_ucell_exact(plaidhip_ctx* ctx, double* Cu, double* Cd, double* tot, int64_t lds, int32_t m, int32_t n,
+                       const int32_t* ku, const int32_t* kd, const double* Ku, const double* Kd, const double* u0, int64_t T,
+                       double w_neg, const uint32_t* colnan);
+int launch_aucell_exact(plaidhip_ctx* ctx, double* C, int64_t lds, int32_t m, int32_t n, const int32_t* kset, int64_t A,
+                        const uint32_t* colnan);
+// the whole stage on device operands (what plaidhip_dev_truncated_ranks_f64 / _csc_f64 and the workers run): the
+// NaN flags, the rank passes and launch_truncated_compact.  Dense: X g x n (ldx), R g x n doubles of scratch (ld g).  CSC:
+// scratch 2 nnz doubles.
+int truncated_ranks_stage(plaidhip_ctx* ctx, int mode, int64_t T, const double* X, int64_t ldx, const int32_t* Xp,
+                          const int32_t* Xi, int32_t g, int32_t n, int32_t max_col_nnz, int64_t nnz, double* scratch,
+                          uint32_t* colnan, int32_t* cnt, int32_t* Wp, int32_t* Wi, double* Wx, int64_t cap, double* u0);
 // kernels_kcdf.hip: GSVA's Gaussian kernel CDF estimate (include/plaidhip.h: plaidhip_gsva_kcdf).  V (g x (j1 - j0), leading
 // dimension ldv) <- the kernel sums of the test columns [j0, j1) of the dense device matrix X (g x n, leading dimension
 // ldx) over ALL n samples; H: g doubles of scratch (the bandwidths).  Stream-ordered.

@@ -897,6 +897,147 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   return s.finish();
 }
 
+// one device's part of replaid.ucell.exact / replaid.aucell.exact (kUcellExact, kAucellExact; kernels_trunc.hip): the
+// truncated-rank stage turns the shard's columns into compressed columns of rank weights, panel by panel (a panel's slots
+// stay below 2^27 entries and are sized by what its own columns can take), the sparse crossprod multiplies each panel with the prepared sets, and the pinned epilogue
+// closes.  A dgCMatrix is never expanded: O(nnz + columns x T) on the device.  Nothing couples the shards, nothing is read
+// back before the results.
+int truncated_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
+  const int32_t g = c.g, m = c.m;
+  const bool sparse = c.Xp != nullptr;
+  const bool ucell = c.method == kUcellExact;
+  const int mode = ucell ? PLAIDHIP_TRUNC_UCELL : PLAIDHIP_TRUNC_AUCELL;
+  const int64_t T = (int64_t)c.max_rank;
+  double* const outs[3] = {ucell ? c.sx_out[0] : nullptr, ucell ? c.sx_out[1] : c.S_out, ucell ? c.sx_out[2] : nullptr};
+  const bool up = outs[0] || outs[1], down = outs[0] || outs[2];
+  s.force_f64();
+  plaidhip_geneset *gs_up = nullptr, *gs_dn = nullptr;
+  CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dops{ctx, 3}, dS{ctx, 4}, dsmall{ctx, 5};
+  DevBuf dk, dK, dWi, dWx;
+  HomeBuffer home[3];
+  const size_t nl = (size_t)std::max(nloc, 1);
+  const size_t nscores = (size_t)m * nl;
+  auto part = [&](int o) { return dS.as<double>() + (size_t)o * nscores; };   // [total | up | down]
+  std::vector<int32_t> kset((size_t)m * 2, 0), ploc;
+  std::vector<double> kfull;
+  for (int32_t j = 0; j < m; ++j) {   // members after the alignment
+    kset[(size_t)j] = c.Gp[j + 1] - c.Gp[j];
+    if (c.Dp != nullptr) kset[(size_t)m + j] = c.Dp[j + 1] - c.Dp[j];
+  }
+  if (c.k_full != nullptr) {
+    kfull.assign((size_t)m * 2, 0.0);
+    for (int32_t j = 0; j < m; ++j) {
+      kfull[(size_t)j] = c.k_full[j];
+      if (c.k_full_down != nullptr) kfull[(size_t)m + j] = c.k_full_down[j];
+    }
+  }
+  double* d_u0 = nullptr;
+  uint32_t* d_colnan = nullptr;
+  int32_t *d_cnt = nullptr, *d_Wp = nullptr;
+  int32_t max_nnz = 0;
+  std::vector<int64_t> pcol{0}, pent;   // the panels' first columns, and the most entries each can take (its slots)
+  int64_t wcap = 1, pmax = 1;            // the largest panel's entries and columns
+
+  // ---- upload -----------------------------------------------------------------------------------------------------------------
+  s.step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    if (up) PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs_up));
+    if (down) PH_TRY(acquire_geneset(ctx, g, m, c.Dp, c.Di, &gs_dn));
+    // [u0 | NaN flags | counts | slot pointers]
+    PH_TRY(dsmall.alloc(nl * 8 + nl * 4 + nl * 4 + (nl + 1) * 4));
+    d_u0 = dsmall.as<double>();
+    d_colnan = reinterpret_cast<uint32_t*>(d_u0 + nl);
+    d_cnt = reinterpret_cast<int32_t*>(d_colnan + nl);
+    d_Wp = d_cnt + nl;
+    PH_TRY(dS.alloc(nscores * 3 * 8));
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(dk.alloc((size_t)m * 2 * 4));
+    PH_HIP(hipMemcpyAsync(dk.p, kset.data(), (size_t)m * 2 * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!kfull.empty()) {
+      PH_TRY(dK.alloc((size_t)m * 2 * 8));
+      PH_HIP(hipMemcpyAsync(dK.p, kfull.data(), (size_t)m * 2 * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (!sparse) {
+      PH_TRY(dX.alloc((size_t)g * nloc * 8));
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)g * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
+                              (size_t)g * 8, nloc, nullptr));
+    } else {
+      PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
+    }
+    // panels of columns whose slots stay below 2^27 entries, sized by what their own columns can take: a dgCMatrix in
+    // UCell mode by its stored values (the sum over a panel is its nnz), everything else by the rank bound
+    {
+      int64_t sum = 0;
+      for (int32_t j = 0; j < nloc; ++j) {
+        const int64_t b = truncated_bound(mode, T, g, sparse ? ploc[(size_t)j + 1] - ploc[(size_t)j] : 0, sparse);
+        if (sum + b > ((int64_t)1 << 27) && j > pcol.back()) {
+          pent.push_back(sum);
+          pcol.push_back(j);
+          sum = 0;
+        }
+        sum += b;
+      }
+      pent.push_back(sum);
+      pcol.push_back(nloc);
+      for (size_t q = 0; q < pent.size(); ++q) {
+        wcap = std::max(wcap, pent[q]);
+        pmax = std::max(pmax, pcol[q + 1] - pcol[q]);
+      }
+    }
+    // the ranks: a panel of dense columns, or of the stored values of the whole shard (and, for "last", the tie-free copy)
+    PH_TRY(dops.alloc((sparse ? (size_t)std::max<int64_t>(s.zx, 1) * 2 : (size_t)g * (size_t)pmax) * 8));
+    PH_TRY(dWi.alloc((size_t)wcap * 4));
+    PH_TRY(dWx.alloc((size_t)wcap * 8));
+    for (int o = 0; o < 3; ++o)
+      if (outs[o]) home[o].prepare(outs[o] + (int64_t)lo * m, (size_t)m * nloc * 8);
+    return PLAIDHIP_OK;
+  });
+
+  // ---- per panel: the truncated ranks as compressed columns, their crossprods; then the pinned epilogue ----------------------
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nloc == 0) return PLAIDHIP_OK;
+    for (size_t q = 0; q + 1 < pcol.size(); ++q) {
+      const int64_t c0 = pcol[q];
+      const int32_t nc = (int32_t)(pcol[q + 1] - c0);
+      if (!sparse)
+        PH_TRY(truncated_ranks_stage(ctx, mode, T, dX.as<double>() + c0 * g, g, nullptr, nullptr, g, nc, 0, 0, dops.as<double>(),
+                                     d_colnan + c0, d_cnt, d_Wp, dWi.as<int32_t>(), dWx.as<double>(), wcap, nullptr));
+      else   // (absolute offsets into the shard's @i / @x, and into the rank scratch)
+        PH_TRY(truncated_ranks_stage(ctx, mode, T, dX.as<double>(), 0, dXp.as<int32_t>() + c0, dXi.as<int32_t>(), g, nc, max_nnz,
+                                     s.zx, dops.as<double>(), d_colnan + c0, d_cnt, d_Wp, dWi.as<int32_t>(), dWx.as<double>(),
+                                     wcap, d_u0 + c0));
+      // The weights are half-integers (UCell; the shifted ones of any sign) or integers: every sum is exact on the fixed-point
+      // and on the fp64 accumulators alike (a negative weight sends the scatter kernel to fp64, decided on the device), and on
+      // the gather kernel; an estimate of the entries picks between scatter and gather
+      const int64_t est = std::min<int64_t>(pent[q], (int64_t)nc * T);
+      if (up)
+        PH_TRY(launch_spmm_csc_f64(ctx, gs_up, d_Wp, dWi.as<int32_t>(), dWx.as<double>(), nc, est, PLAIDHIP_STAT_SUM, 1.0, nullptr,
+                                   0.0, part(1) + c0 * m, m, nullptr));
+      if (down)
+        PH_TRY(launch_spmm_csc_f64(ctx, gs_dn, d_Wp, dWi.as<int32_t>(), dWx.as<double>(), nc, est, PLAIDHIP_STAT_SUM, 1.0, nullptr,
+                                   0.0, part(2) + c0 * m, m, nullptr));
+    }
+    if (!ucell) return launch_aucell_exact(ctx, part(1), m, m, nloc, dk.as<int32_t>(), T, d_colnan);
+    const double* K = kfull.empty() ? nullptr : dK.as<double>();
+    return launch_ucell_exact(ctx, up ? part(1) : nullptr, down ? part(2) : nullptr, outs[0] ? part(0) : nullptr, m, m, nloc,
+                              dk.as<int32_t>(), dk.as<int32_t>() + m, K, (K && c.k_full_down) ? K + m : nullptr,
+                              sparse ? d_u0 : nullptr, T, c.w_neg, d_colnan);
+  });
+
+  // ---- the requested shards go home ---------------------------------------------------------------------------------------
+  s.step([&]() -> int {
+    if (nloc > 0)
+      for (int o = 0; o < 3; ++o)
+        if (outs[o]) PH_TRY(home[o].copy(ctx, part(o)));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+  return s.finish();
+}
+
 // one device's part of replaid.ucell / aucell / scse / gsva (kUcell ... kGsva; one shard: plaidhip_ucell ... plaidhip_gsva_csc)
 // and of replaid.gsva.exact (kGsvaExact).  The quantities that couple the samples are combined on the host between the
 // phases: max(rX) (R/plaid.R:278, 306), the min / max behind removeLog2 = NULL (:160-161), the per-gene mean and sd of the
@@ -904,6 +1045,7 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
 int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   if (c.method == kSsgseaExact) return ssgsea_exact_worker(ctx, c, ndev, k, sh);
   if (c.method == kSingExact) return sing_exact_worker(ctx, c, ndev, k, sh);
+  if (c.method == kUcellExact || c.method == kAucellExact) return truncated_exact_worker(ctx, c, ndev, k, sh);
   Shard s(ctx, c, ndev, k, sh);
   const int32_t lo = s.lo, nloc = s.nloc;
   const int32_t g = c.g, m = c.m, n = c.n;
@@ -1627,6 +1769,51 @@ int check_sing_exact_call(const Call& c) {
   return PLAIDHIP_OK;
 }
 
+// replaid.ucell.exact / replaid.aucell.exact.  The order is part of the contract: the rank bound and the 2^53 bound of the
+// integer epilogue come before anything reads X.
+int check_truncated_exact_call(const Call& c) {
+  const bool ucell = c.method == kUcellExact;
+  const char* who = ucell ? "ucell_exact" : "aucell_exact";
+  const char* what = ucell ? "maxRank" : "aucMaxRank";
+  const double* any = ucell ? nullptr : c.S_out;
+  if (ucell) {
+    for (int o = 0; o < 3; ++o) any = any ? any : c.sx_out[o];
+    PH_REQUIRE(std::isfinite(c.w_neg) && c.w_neg >= 0.0, "ucell_exact: w_neg must be finite and >= 0 (got %g)", c.w_neg);
+  }
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  if (ucell && c.Dp != nullptr) PH_TRY(check_host_common(c.Dp, c.g, c.n, c.m));
+  if (ucell && c.Dp == nullptr)
+    PH_REQUIRE(!c.sx_out[0] && !c.sx_out[2], "ucell_exact: total and down results need the down sets");
+  if ((int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.max_rank >= 1.0 && c.max_rank <= (double)c.g && c.max_rank == std::floor(c.max_rank),
+             "%s: %s must be an integer in 1..nrow(X) = %d (got %g)", who, what, c.g, c.max_rank);
+  if (2.0 * (double)c.g * c.max_rank >= 0x1p53) {
+    set_error("%s: 2 nrow(X) %s = 2 x %d x %.0f does not stay below 2^53", who, what, c.g, c.max_rank);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  PH_REQUIRE(any != nullptr, "%s: no output requested", who);
+  PH_TRY(check_ssgsea_exact_call(c, any));
+  if (ucell && c.Dp != nullptr) PH_REQUIRE(c.Di != nullptr || c.Dp[c.m] == 0, "ucell_exact: null Di");
+  if (ucell && c.k_full != nullptr) {
+    PH_REQUIRE(c.Dp == nullptr || c.k_full_down != nullptr, "ucell_exact: impute needs k_full_down beside the down sets");
+    for (int pass = 0; pass < (c.Dp != nullptr ? 2 : 1); ++pass) {
+      const double* K = pass ? c.k_full_down : c.k_full;
+      const int32_t* P = pass ? c.Dp : c.Gp;
+      for (int32_t j = 0; j < c.m; ++j) {
+        PH_REQUIRE(std::isfinite(K[j]) && K[j] == std::floor(K[j]) && K[j] >= (double)(P[j + 1] - P[j]),
+                   "ucell_exact: k_full%s[%d] = %g is no integer >= the %d aligned members", pass ? "_down" : "", j, K[j],
+                   P[j + 1] - P[j]);
+        if (2.0 * K[j] * (c.max_rank + 1.0) + K[j] * (K[j] + 1.0) >= 0x1p53) {
+          set_error("ucell_exact: k_full%s[%d] = %g with maxRank = %.0f does not stay below 2^53", pass ? "_down" : "", j, K[j],
+                    c.max_rank);
+          return PLAIDHIP_EUNSUPPORTED;
+        }
+      }
+    }
+  }
+  return PLAIDHIP_OK;
+}
+
 // replaid.ucell / aucell / scse / gsva
 int check_scorer_call(const Call& c, int ndev, bool multi) {
   if (c.method == kScse && c.removed_log2 != nullptr) *c.removed_log2 = c.remove_log2 > 0 ? 1 : 0;
@@ -1733,6 +1920,8 @@ int check_call(Call& c, int ndev, bool multi) {
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
     case kGsvaExact: return check_gsva_exact_call(c, ndev);
     case kSingExact: return check_sing_exact_call(c);
+    case kUcellExact:
+    case kAucellExact: return check_truncated_exact_call(c);
     default: return check_scorer_call(c, ndev, multi);   // (which refuses what is no method at all)
   }
 }
@@ -1912,6 +2101,41 @@ int plaidhip_debug_sing_exact_sharded_on_one_device(int device, int nshards, int
                                                     double* up_disp, double* down_disp) try {
   return dispatch(on_hook(device, nshards, fail_shard), sing_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, center, total,
                                                                          up, down, total_disp, up_disp, down_disp));
+} catch (...) { return plaidhip::on_exception(); }
+
+// impute != 0: K = k_full (k_full_down for the down sets), which must be given; impute == 0: they are not read
+int plaidhip_ucell_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                               int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
+                               int32_t m, double max_rank, double w_neg, int impute, const double* k_full,
+                               const double* k_full_down, double* total, double* up, double* down) try {
+  PH_REQUIRE(!impute || k_full != nullptr || m == 0, "ucell_exact: impute needs k_full");
+  return dispatch(on_devices(devices, ndev),
+                  ucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, max_rank, w_neg, impute ? k_full : nullptr,
+                                   impute ? k_full_down : nullptr, total, up, down));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_aucell_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
+                                int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank,
+                                double* S_out) try {
+  return dispatch(on_devices(devices, ndev), aucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, auc_max_rank, S_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_ucell_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                     const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                     const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di,
+                                                     int32_t m, double max_rank, double w_neg, int impute, const double* k_full,
+                                                     const double* k_full_down, double* total, double* up, double* down) try {
+  PH_REQUIRE(!impute || k_full != nullptr || m == 0, "ucell_exact: impute needs k_full");
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  ucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Dp, Di, max_rank, w_neg, impute ? k_full : nullptr,
+                                   impute ? k_full_down : nullptr, total, up, down));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_aucell_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                      const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                      const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank,
+                                                      double* S_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard), aucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, auc_max_rank, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -193,6 +193,46 @@ def _sing_exact_call(fn, head, X, Gp, Gi, Dp, Di, center, dispersion, fill=None)
     return {name: o for name, o in zip(SING_EXACT_OUTPUTS, outs) if o is not None}
 
 
+UCELL_EXACT_OUTPUTS = ("TotalScore", "UpScore", "DownScore")
+TRUNC_MODE = {"ucell": 0, "aucell": 1}   # PLAIDHIP_TRUNC_*
+
+
+def check_truncated_rank(who, what, g, rank):
+    """maxRank / aucMaxRank as plaidhip_ucell_exact / plaidhip_aucell_exact check it, which needs no device"""
+    r = float(rank)
+    if not (1.0 <= r <= float(g)) or r != np.floor(r):
+        raise ValueError(f"{who}: {what} must be an integer in 1..nrow(X) = {g} (got {r:g})")
+    if 2.0 * float(g) * r >= 2.0 ** 53:
+        raise _lib.PlaidHipError(_lib.EUNSUPPORTED, f"{who}: 2 nrow(X) {what} = 2 x {g} x {r:.0f} does not stay below 2^53")
+    return r
+
+
+def _ucell_exact_call(fn, head, X, Gp, Gi, Dp, Di, max_rank, w_neg, k_full, k_full_down, fill=None):
+    """fill: what the results hold before the call (the tests' sentinel); None leaves them uninitialised"""
+    xp, xi, xv, g, n, keep = _x_args(X)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    down = Dp is not None
+    if down:
+        Dp, Di = _as_i32(Dp), _as_i32(Di)
+        if len(Dp) != len(Gp):
+            raise ValueError(f"ucell_exact: the down sets have {len(Dp) - 1} columns, the up sets {len(Gp) - 1}")
+    w_neg = float(w_neg)
+    if not np.isfinite(w_neg) or w_neg < 0.0:
+        raise ValueError(f"ucell_exact: w_neg must be finite and >= 0 (got {w_neg:g})")
+    m = len(Gp) - 1
+    impute = k_full is not None
+    kf = np.ascontiguousarray(k_full, dtype=np.float64) if impute else None
+    kd = np.ascontiguousarray(k_full_down, dtype=np.float64) if impute and k_full_down is not None else None
+    if impute and (kf.shape != (m,) or (kd is not None and kd.shape != (m,))):
+        raise ValueError("ucell_exact: k_full must have one entry per set")
+    outs = [(np.empty if fill is None else np.full)((m, n), *(() if fill is None else (fill,)), dtype=np.float64, order="F")
+            if w else None for w in (down, True, down)]
+    check(fn(*head, xp, xi, xv, g, n, _np_ptr(Gp), _np_ptr(Gi), _np_ptr(Dp) if down else None, _np_ptr(Di) if down else None, m,
+             float(max_rank), w_neg, int(impute), None if kf is None else _np_ptr(kf), None if kd is None else _np_ptr(kd),
+             *[None if o is None else _np_ptr(o) for o in outs]))
+    return {name: o for name, o in zip(UCELL_EXACT_OUTPUTS, outs) if o is not None}
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -540,6 +580,29 @@ class Context:
         sets TotalScore, DownScore [, TotalDispersion, DownDispersion].  dispersion = False launches no per-pair kernel."""
         return _sing_exact_call(self.lib.plaidhip_sing_exact, (self.handle,), X, Gp, Gi, Dp, Di, center, dispersion)
 
+    def ucell_exact(self, X, Gp, Gi, Dp=None, Di=None, max_rank=1500, w_neg=1.0, k_full=None, k_full_down=None):
+        """plaidhip_ucell_exact: UCell's statistic on truncated ranks; X dense or scipy CSC with sorted, distinct row indices
+        (never expanded), the up sets G and the down sets D (optional, as many columns) aligned to X's rows.  k_full (and
+        k_full_down): the set sizes before the alignment (UCell's missing_genes = "impute"); None: the aligned sizes.  A
+        dict of m x n matrices: UpScore, and with down sets TotalScore (up - w_neg * down, clamped at 0) and DownScore."""
+        return _ucell_exact_call(self.lib.plaidhip_ucell_exact, (self.handle,), X, Gp, Gi, Dp, Di, max_rank, w_neg, k_full,
+                                 k_full_down)
+
+    def aucell_exact(self, X, Gp, Gi, auc_max_rank):
+        """plaidhip_aucell_exact: AUCell's AUC on truncated ranks, ties broken by row order; X dense or scipy CSC with sorted,
+        distinct row indices (never expanded), G aligned to X's rows"""
+        return self._host("aucell_exact", X, Gp, Gi, float(auc_max_rank))
+
+    def dev_truncated_ranks(self, X: int, ldx: int, g: int, n: int, mode, T: int, R_scratch: int, colnan: int, counts: int,
+                            Wp: int, Wi: int, Wx: int, capacity: int):
+        check(self.lib.plaidhip_dev_truncated_ranks_f64(self.handle, X, ldx, g, n, TRUNC_MODE[mode], int(T), R_scratch, colnan,
+                                                        counts, Wp, Wi, Wx, int(capacity)))
+
+    def dev_truncated_ranks_csc(self, Xp: int, Xi: int, Xx: int, g: int, n: int, max_col_nnz: int, nnz: int, mode, T: int,
+                                scratch: int, colnan: int, counts: int, u0: int, Wp: int, Wi: int, Wx: int, capacity: int):
+        check(self.lib.plaidhip_dev_truncated_ranks_csc_f64(self.handle, Xp, Xi, Xx, g, n, max_col_nnz, nnz, TRUNC_MODE[mode],
+                                                            int(T), scratch, colnan, counts, u0, Wp, Wi, Wx, int(capacity)))
+
     def gsva(self, X, Gp, Gi, tau=0.0, rowtf="z"):
         return self._host("gsva", _as_f64_fortran(X), Gp, Gi, float(tau), _rowtf(rowtf), dense=True)
 
@@ -641,6 +704,16 @@ def gsva_exact_multi(X, Gp, Gi, tau=1.0, rowtf="z", max_diff=True, devices=1) ->
 def sing_exact_multi(X, Gp, Gi, Dp=None, Di=None, center=True, dispersion=True, devices=1) -> dict:
     """replaid.sing.exact (Context.sing_exact) with the sample columns sharded over `devices`: the one-device bits"""
     return _sing_exact_call(*_multi("sing_exact", devices), X, Gp, Gi, Dp, Di, center, dispersion)
+
+
+def ucell_exact_multi(X, Gp, Gi, Dp=None, Di=None, max_rank=1500, w_neg=1.0, k_full=None, k_full_down=None, devices=1) -> dict:
+    """replaid.ucell.exact (Context.ucell_exact) with the sample columns sharded over `devices`: the one-device bits"""
+    return _ucell_exact_call(*_multi("ucell_exact", devices), X, Gp, Gi, Dp, Di, max_rank, w_neg, k_full, k_full_down)
+
+
+def aucell_exact_multi(X, Gp, Gi, auc_max_rank, devices=1) -> np.ndarray:
+    """replaid.aucell.exact (Context.aucell_exact) with the sample columns sharded over `devices`: the one-device bits"""
+    return _score(*_multi("aucell_exact", devices), X, Gp, Gi, float(auc_max_rank))
 
 
 def ucell_multi(X, Gp, Gi, k_full, rmax=1500.0, devices=1) -> np.ndarray:

@@ -286,6 +286,71 @@ replaid.aucell <- function(X, matG, aucMaxRank = ceiling(0.05 * nrow(X))) {
   S
 }
 
+## UCell's statistic on truncated ranks -- replaid.ucell (R/plaid.R:276-282) is "near exact": max(rX) - rX for the descending
+## rank, plaid()'s median normalisation and its 1e-8.  The formulas follow UCell AS RECALLED (the package's source is not in
+## this tree); include/plaidhip.h (plaidhip_ucell_exact) pins them: per sample d = rank(-x, ties = "average") over ALL rows
+## of X, truncated by UCell's rule c = (d <= maxRank) ? d : maxRank + 1 (not pmin: a tie group is kept as a whole or not at
+## all); for a set of K members 1 - U / (K maxRank) with U = sum(c) - K (K + 1) / 2, formed in integers and closed by one
+## division.  K is the number of aligned members, or with impute = TRUE colSums(matG != 0) of the un-aligned matrix (UCell's
+## missing_genes = "impute": absent members count with rank maxRank + 1); k_full overrides it for the up sets.  matD
+## (optional): the down sets, column j pairing with column j of matG; TotalScore = UpScore - w_neg * DownScore, below 0
+## gives 0.  Sets without members score NA; an empty down column makes its TotalScore NA; a sample holding an NA is NA
+## everywhere.  No normalize_medians.  A dgCMatrix is never expanded, on the host or on the device.  Returns a list of sets x
+## samples matrices: UpScore and, with matD, TotalScore and DownScore.  options(plaidhip.devices = ...) shards the samples.
+replaid.ucell.exact <- function(X, matG, matD = NULL, maxRank = 1500, w_neg = 1, k_full = NULL, impute = FALSE) {
+  if (!is.null(matD) && ncol(matD) != ncol(matG)) stop("ucell_exact: matD has ", ncol(matD), " columns, matG ", ncol(matG))
+  maxRank <- as.double(maxRank); w_neg <- as.double(w_neg)
+  if (length(maxRank) != 1L || is.na(maxRank) || maxRank != floor(maxRank) || maxRank < 1 || maxRank > nrow(X))
+    stop("ucell_exact: maxRank must be an integer in 1..nrow(X)")
+  if (length(w_neg) != 1L || !is.finite(w_neg) || w_neg < 0) stop("ucell_exact: w_neg must be finite and >= 0")
+  pat <- .aligned_pattern(X, matG)
+  if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
+  Dp <- integer(0); Di <- integer(0)
+  if (!is.null(matD)) {
+    dpat <- .aligned_pattern(X, matD)
+    if (is.null(dpat)) dpat <- list(Gp = integer(ncol(matD) + 1L), Gi = integer(0))
+    Dp <- dpat$Gp; Di <- dpat$Gi
+  }
+  kf <- double(0); kd <- double(0)
+  if (!is.null(k_full) || isTRUE(impute)) {
+    kf <- if (!is.null(k_full)) as.double(k_full) else as.double(Matrix::colSums(matG != 0))
+    if (length(kf) != ncol(matG)) stop("ucell_exact: k_full must have one entry per set")
+    if (!is.null(matD)) kd <- as.double(Matrix::colSums(matD != 0))
+  }
+  .session()
+  if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
+  xa <- .x_args(X)
+  dev <- .devices()
+  res <- .Call("R_plaidhip_ucell_exact", if (length(dev) > 1L) dev else integer(0), xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X),
+               pat$Gp, pat$Gi, Dp, Di, maxRank, w_neg, kf, kd, PACKAGE = "plaidhip")
+  names(res) <- c("TotalScore", "UpScore", "DownScore")
+  res <- res[!vapply(res, is.null, logical(1))]
+  lapply(res, function(S) { dimnames(S) <- list(colnames(matG), colnames(X)); S })
+}
+
+## AUCell's AUC on truncated ranks -- replaid.aucell (R/plaid.R:304-309) is a ramp with a factor of 1.08.  The formulas
+## follow AUCell AS RECALLED; include/plaidhip.h (plaidhip_aucell_exact) pins them: per sample the positions
+## pos = N + 1 - rank(x, ties = "last") over ALL rows of X (AUCell breaks ties at random; here the earlier row comes first, so
+## that the result is a function of its input); area = sum(aucMaxRank - pos) over the members with pos < aucMaxRank,
+## divided by the largest area min(k, aucMaxRank - 1) members can reach.  Sets without aligned members score NA, as does
+## aucMaxRank = 1.  No normalize_medians; random ties and AUCell's older normalisation (aucMaxRank * k) are not offered.  A
+## dgCMatrix is never expanded.  options(plaidhip.devices = ...) shards the samples.
+replaid.aucell.exact <- function(X, matG, aucMaxRank = ceiling(0.05 * nrow(X))) {
+  aucMaxRank <- as.double(aucMaxRank)
+  if (length(aucMaxRank) != 1L || is.na(aucMaxRank) || aucMaxRank != floor(aucMaxRank) || aucMaxRank < 1 ||
+      aucMaxRank > nrow(X)) stop("aucell_exact: aucMaxRank must be an integer in 1..nrow(X)")
+  pat <- .aligned_pattern(X, matG)
+  if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
+  .session()
+  if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
+  xa <- .x_args(X)
+  dev <- .devices()
+  S <- .Call("R_plaidhip_aucell_exact", if (length(dev) > 1L) dev else integer(0), xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X),
+             pat$Gp, pat$Gi, aucMaxRank, PACKAGE = "plaidhip")
+  dimnames(S) <- list(colnames(matG), colnames(X))
+  S
+}
+
 replaid.scse <- function(X, matG, removeLog2 = NULL, scoreMean = FALSE) {
   pat <- .aligned_pattern(X, matG)
   if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }

@@ -330,6 +330,52 @@ SEXP R_plaidhip_sing_exact(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP
   return res;
 }
 
+/* replaid.ucell.exact: a list of three m x n matrices (total, up, down), NULL where not computed: Dp of length 0 means no
+ * down sets, kfull of length 0 no imputation.  devices of length 0: the session's context */
+SEXP R_plaidhip_ucell_exact(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP Dp, SEXP Di,
+                            SEXP max_rank, SEXP w_neg, SEXP kfull, SEXP kfull_down) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  const int down = LENGTH(Dp) > 0, impute = LENGTH(kfull) > 0;
+  const int want[3] = {down, 1, down};
+  double* out[3];
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+  for (int o = 0; o < 3; ++o) {
+    out[o] = NULL;
+    if (want[o]) {
+      SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+      SET_VECTOR_ELT(res, o, S);
+      UNPROTECT(1);
+      out[o] = REAL(S);
+    }
+  }
+  const double* kf = impute ? REAL(kfull) : NULL;
+  const double* kd = impute && LENGTH(kfull_down) > 0 ? REAL(kfull_down) : NULL;
+  if (LENGTH(devices) > 0)
+    check(plaidhip_ucell_exact_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                     Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi), down ? INTEGER(Dp) : NULL,
+                                     down ? INTEGER(Di) : NULL, m, Rf_asReal(max_rank), Rf_asReal(w_neg), impute, kf, kd, out[0],
+                                     out[1], out[2]));
+  else
+    check(plaidhip_ucell_exact(ctx(), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi),
+                               down ? INTEGER(Dp) : NULL, down ? INTEGER(Di) : NULL, m, Rf_asReal(max_rank), Rf_asReal(w_neg),
+                               impute, kf, kd, out[0], out[1], out[2]));
+  UNPROTECT(1);
+  return res;
+}
+
+SEXP R_plaidhip_aucell_exact(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP auc_max_rank) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  if (LENGTH(devices) > 0)
+    check(plaidhip_aucell_exact_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                      Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(auc_max_rank), REAL(S)));
+  else
+    check(plaidhip_aucell_exact(ctx(), int_or_null(Xp), int_or_null(Xi), REAL(Xv), Rf_asInteger(g), nn, INTEGER(Gp), INTEGER(Gi),
+                                m, Rf_asReal(auc_max_rank), REAL(S)));
+  UNPROTECT(1);
+  return S;
+}
+
 SEXP R_plaidhip_ucell(SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP kfull, SEXP rmax) {
   const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n);
   SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
@@ -504,6 +550,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_scse_multi", (DL_FUNC)&R_plaidhip_scse_multi, 10},
     {"R_plaidhip_gsva_multi", (DL_FUNC)&R_plaidhip_gsva_multi, 10},
     {"R_plaidhip_sing_exact", (DL_FUNC)&R_plaidhip_sing_exact, 12},
+    {"R_plaidhip_ucell_exact", (DL_FUNC)&R_plaidhip_ucell_exact, 14},
+    {"R_plaidhip_aucell_exact", (DL_FUNC)&R_plaidhip_aucell_exact, 9},
     {"R_plaidhip_gsva_exact", (DL_FUNC)&R_plaidhip_gsva_exact, 10},
     {"R_plaidhip_gsva_exact_multi", (DL_FUNC)&R_plaidhip_gsva_exact_multi, 11},
     {"R_plaidhip_ssgsea_exact", (DL_FUNC)&R_plaidhip_ssgsea_exact, 10},
