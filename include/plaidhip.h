@@ -795,6 +795,51 @@ int plaidhip_dev_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, i
 int plaidhip_plaid_test_finish(int32_t g, int32_t m, const int32_t* Gp, const double* T, double tot1, double tot2,
                                const double* SM, int64_t n0, int64_t n1, int tests, int metap_method, double* out);
 
+/* plaid.test.contrasts(X, Y, G, gsetX, tests, metap.method): plaid.test for every column of a contrast matrix in one pass
+ * over the scores.  Y: n x C, int32, column-major, 0 / 1 per sample and -1 for NA: the sample takes no part in that
+ * contrast.  Anything else is PLAIDHIP_EINVAL with a message naming the contrast and the sample (both counted from 1),
+ * before any device is touched.  With sel_j = which(!is.na(Y[, j])), contrast j is the reference's
+ *     plaid.test(X[, sel_j], Y[sel_j, j], G, gsetX = S_all[, sel_j], tests, metap.method)         (R/plaid.R:392-474)
+ * where S_all is the gsetX given or, gsetX == NULL, plaid(X, G) over ALL samples (:424-427): the scores are computed and
+ * normalised once (the constant mean(medx) cancels in the Welch test and in gsetFC).  A contrast without NA is therefore
+ * plaidhip_plaid_test(X, Y[, j], ...) and has its bits, NaNs included; empty groups, groups of one and constant rows
+ * behave as documented there.  A NaN or Inf in an excluded sample's column of X (given gsetX) or of gsetX does not reach
+ * that contrast: an excluded column is added as +0.0.
+ * out: m x 6 x C doubles, contrast j at out + j * 6 * m with plaidhip_plaid_test's six columns in G's order.  C == 0 or
+ * m == 0: nothing is written.  tests / metap_method: as plaidhip_plaid_test.
+ * How: the row moments are taken for PLAIDHIP_CONTRAST_TILE contrasts per read of the matrix (kernels_contrasts.hip), so
+ * dense X is read ceil(C / tile) times for the logFC and the scores 2 ceil(C / tile) times for the Welch moments, not C
+ * and 2 C times, and plaid(X, G) runs once.  Gt [fc_j, fc_j^2] is the dense crossprod of plaidhip_plaid_test, called per
+ * contrast with its two columns; a dgCMatrix is uploaded and transposed once, its stored-value group sums run once per
+ * contrast.  The host tail is plaidhip_plaid_test_finish per contrast with that contrast's group sizes.
+ * Device memory: X (or its slots and row view) and, with "lm", the scores S once; the block partials
+ * 2 * C * rows * ceil(n / 128) doubles for rows = g (dense X) and rows = m ("lm"), one buffer for both;
+ * O(C * (g + m)) besides.
+ *   plaidhip_plaid_test_contrasts: dense X.  plaidhip_plaid_test_contrasts_csc: the slots of a dgCMatrix.
+ *   plaidhip_plaid_test_contrasts_multi: the sample columns sharded over devices exactly as plaidhip_plaid_test_multi
+ *     (X dense with Xp == NULL, or the slots), the chained sums carried as [C][2][rows]; for dense X every sharding has the
+ *     bits of the one-device call.  This is the single-process form; a process per GPU combines the two _dev_ entries
+ *     below as plaid_amd/sharded.py does for plaid.test.
+ *   plaidhip_dev_row_contrast_sums / _ssd: plaidhip_dev_row_group_sums / _ssd for C label columns at once.  Device
+ *     pointers, stream-ordered.  Y: n x C int32 column-major (0, 1, anything else: excluded); sums, mean, ssd:
+ *     [C][2][rows].  A contrast without an excluded sample has the bits of the one-label entries.                        */
+#define PLAIDHIP_CONTRAST_TILE 8
+int plaidhip_plaid_test_contrasts(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Y, int32_t C,
+                                  const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                                  int metap_method, double* out);
+int plaidhip_plaid_test_contrasts_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g,
+                                      int32_t n, const int32_t* Y, int32_t C, const int32_t* Gp, const int32_t* Gi,
+                                      int32_t m, const double* gsetX, int tests, int metap_method, double* out);
+int plaidhip_plaid_test_contrasts_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi,
+                                        const double* X_or_x, int32_t g, int32_t n, const int32_t* Y, int32_t C,
+                                        const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                                        int metap_method, double* out);
+int plaidhip_dev_row_contrast_sums(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n,
+                                   const int32_t* Y, int32_t C, double* sums);
+int plaidhip_dev_row_contrast_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n,
+                                  const int32_t* Y, int32_t C, const double* mean, double* ssd);
+int plaidhip_contrast_tile(void);   /* PLAIDHIP_CONTRAST_TILE of the built library */
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

@@ -448,15 +448,10 @@ def replaid_aucell_exact(X, matG, aucMaxRank=None, ctx: Context | None = None):
 _TEST_BITS = {"one": 1, "two": 2, "lm": 4}
 
 
-def plaid_test(X, y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fisher", sort_by="p.meta",
-               ctx: Context | None = None):
-    """plaid.test(), R/plaid.R:392-474: one-/two-sample t-tests of the logFC inside each set plus a Welch test
-    of the single-sample scores between the two groups, combined by Fisher or Stouffer, BH-adjusted.
-    The statistics are reduced on the device; with gsetX=None the scores plaid(X, G) never leave it.
-    Returns a NamedMatrix (sets x [gsetFC, p.<test>..., p.meta, q.meta]) ordered by `sort_by` (:469-471)."""
-    y = np.asarray(y)
-    if not np.all(np.isin(np.unique(y), (0, 1))):
-        raise ValueError("elements of y must be 0 or 1")                      # :394
+def _plaid_test_operands(X, G, gsetX, tests, metap_method):
+    """What plaid_test and plaid_test_contrasts share before the device: G from a gmt, the tests' bit mask, the meta-p
+    code, the rows of X and G aligned by name (:403-405), gsetX's rows in G's column order.
+    Returns (Xs, Gp, Gi, sx, bits, mm, tests, the set names)."""
     if isinstance(G, (GmtList, dict)) or (isinstance(G, tuple) and len(G) == 2):
         _message("[plaid.test] converting gmt to sparse matrix...")           # :396-397
         G = gmt2mat(G)
@@ -506,11 +501,11 @@ def plaid_test(X, y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fi
             sx = np.asarray(gx.values)[[pos[nm] for nm in G.colnames], :]
         else:
             sx = np.asarray(gx.values)
-    ctx = ctx or default_context()
-    if sp.issparse(Xs):
-        out = ctx.plaid_test_csc(Xs.indptr, Xs.indices, Xs.data, Xs.shape[0], y.astype(np.int32), Gp, Gi, sx, bits, mm)
-    else:
-        out = ctx.plaid_test(Xs, y.astype(np.int32), Gp, Gi, sx, bits, mm)
+    return Xs, Gp, Gi, sx, bits, mm, tests, list(G.colnames)
+
+
+def _plaid_test_table(out, tests, rn, sort_by):
+    """sets x 6 of the library -> the NamedMatrix plaid.test returns: the columns asked for, ordered by `sort_by` (:469-471)"""
     cols, names = [0], ["gsetFC"]
     for t, c in (("one", 1), ("two", 2), ("lm", 3)):
         if t in tests:
@@ -519,9 +514,53 @@ def plaid_test(X, y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fi
     cols += [4, 5]
     names += ["p.meta", "q.meta"]
     res = out[:, cols]
-    rn = list(G.colnames)
+    rn = list(rn)
     if sort_by in names:
         o = np.argsort(res[:, names.index(sort_by)], kind="stable")       # order()
         res = res[o, :]
         rn = [rn[k] for k in o]
     return NamedMatrix(res, rn, names)
+
+
+def plaid_test(X, y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fisher", sort_by="p.meta",
+               ctx: Context | None = None):
+    """plaid.test(), R/plaid.R:392-474: one-/two-sample t-tests of the logFC inside each set plus a Welch test
+    of the single-sample scores between the two groups, combined by Fisher or Stouffer, BH-adjusted.
+    The statistics are reduced on the device; with gsetX=None the scores plaid(X, G) never leave it.
+    Returns a NamedMatrix (sets x [gsetFC, p.<test>..., p.meta, q.meta]) ordered by `sort_by` (:469-471)."""
+    y = np.asarray(y)
+    if not np.all(np.isin(np.unique(y), (0, 1))):
+        raise ValueError("elements of y must be 0 or 1")                      # :394
+    Xs, Gp, Gi, sx, bits, mm, tests, rn = _plaid_test_operands(X, G, gsetX, tests, metap_method)
+    ctx = ctx or default_context()
+    if sp.issparse(Xs):
+        out = ctx.plaid_test_csc(Xs.indptr, Xs.indices, Xs.data, Xs.shape[0], y.astype(np.int32), Gp, Gi, sx, bits, mm)
+    else:
+        out = ctx.plaid_test(Xs, y.astype(np.int32), Gp, Gi, sx, bits, mm)
+    return _plaid_test_table(out, tests, rn, sort_by)
+
+
+def plaid_test_contrasts(X, Y, G, gsetX=None, tests=("one", "two", "lm"), metap_method="fisher", sort_by="p.meta",
+                         ctx: Context | None = None):
+    """plaid.test.contrasts(): plaid.test for every column of the contrast matrix Y (samples x contrasts; 0, 1, and NaN or
+    -1 for a sample that takes no part in the contrast) in one pass over the scores.  Contrast j is
+    plaid.test(X[, sel], Y[sel, j], G, gsetX = S_all[, sel]) with sel the samples of the contrast and S_all the gsetX given,
+    or plaid(X, G) over all samples, computed once.  Y: a NamedMatrix (its column names name the contrasts) or an array
+    (contrasts "1", "2", ...).  Returns a dict in Y's column order: contrast name -> the NamedMatrix plaid_test returns."""
+    from .engine import contrast_labels
+    Yn = Y if isinstance(Y, NamedMatrix) else None
+    Yv = np.asarray(Yn.values if Yn is not None else Y)
+    if Yv.ndim == 1:
+        Yv = Yv[:, None]
+    ncon = Yv.shape[1] if Yv.ndim == 2 else 0
+    names = list(Yn.colnames) if Yn is not None and Yn.colnames is not None else [str(j + 1) for j in range(ncon)]
+    Xs, Gp, Gi, sx, bits, mm, tests, rn = _plaid_test_operands(X, G, gsetX, tests, metap_method)
+    lab = contrast_labels(Yv, Xs.shape[1])
+    if not np.all(np.isin(lab, (0, 1, -1))):
+        raise ValueError("elements of Y must be 0, 1 or NA")
+    ctx = ctx or default_context()
+    if sp.issparse(Xs):
+        out = ctx.plaid_test_contrasts_csc(Xs.indptr, Xs.indices, Xs.data, Xs.shape[0], lab, Gp, Gi, sx, bits, mm)
+    else:
+        out = ctx.plaid_test_contrasts(Xs, lab, Gp, Gi, sx, bits, mm)
+    return {nm: _plaid_test_table(out[:, :, j], tests, rn, sort_by) for j, nm in enumerate(names)}

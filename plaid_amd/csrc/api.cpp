@@ -1072,6 +1072,36 @@ int plaidhip_dev_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, i
   return launch_row_group_ssd(ctx, A, ld, rows, n, y, mean, ssd, static_cast<double*>(ctx->ws));
 } catch (...) { return plaidhip::on_exception(); }
 
+// the two entries above for C label columns at once (kernels_contrasts.hip); Y: n x C, sums / mean / ssd: [C][2][rows].  The
+// label masks and the block partials live in the context's workspace.
+static int dev_row_contrast_moment(plaidhip_ctx* ctx, const char* what, const double* A, int64_t ld, int32_t rows, int32_t n,
+                                   const int32_t* Y, int32_t C, const double* mean, bool need_mean, double* out) {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ld >= rows && C >= 0 && C <= 65535, "%s: bad shape rows=%d n=%d ld=%lld C=%d", what, rows,
+             n, (long long)ld, C);
+  if (rows == 0 || C == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(out && (!need_mean || mean) && (n == 0 || (A && Y)), "%s: null argument", what);
+  const size_t part = (size_t)row_contrast_ws_doubles(rows, n, C) * 8;
+  PH_TRY(ensure_workspace(ctx, part + (size_t)contrast_mask_bytes(n, C)));
+  double* ws = static_cast<double*>(ctx->ws);
+  void* masks = static_cast<char*>(ctx->ws) + part;
+  PH_TRY(launch_contrast_masks(ctx, Y, n, n, C, masks));
+  PH_TRY(launch_row_contrast_partials(ctx, A, ld, rows, n, masks, C, nullptr, 0.0, mean, ws));
+  return launch_reduce_blocks_flat(ctx, ws, (int64_t)C * 2 * rows, n, nullptr, out);
+}
+
+int plaidhip_dev_row_contrast_sums(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int32_t* Y,
+                                   int32_t C, double* sums) try {
+  return dev_row_contrast_moment(ctx, "row_contrast_sums", A, ld, rows, n, Y, C, nullptr, false, sums);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_row_contrast_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int32_t* Y,
+                                  int32_t C, const double* mean, double* ssd) try {
+  return dev_row_contrast_moment(ctx, "row_contrast_ssd", A, ld, rows, n, Y, C, mean, true, ssd);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_contrast_tile(void) { return PLAIDHIP_CONTRAST_TILE; }
+
 // The host half of plaid.test (R/plaid.R:410-474): p-values, effect sizes, meta-p and FDR from the reduced statistics.
 // Shared by the sharded engine (multi.cpp: run_call) and by callers over RCCL, which all-reduce the statistics first.
 int plaidhip_plaid_test_finish(int32_t g, int32_t m, const int32_t* Gp, const double* T, double tot1, double tot2,
@@ -1123,6 +1153,21 @@ int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
                         const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
                         int metap_method, double* out) try {
   return dispatch(on_context(ctx), plaid_test_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.test.contrasts: the one-shard case of plaid_test_contrasts_worker (multi.cpp)
+int plaidhip_plaid_test_contrasts(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Y, int32_t C,
+                                  const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                                  int metap_method, double* out) try {
+  return dispatch(on_context(ctx),
+                  plaid_test_contrasts_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, Y, C, gsetX, tests, metap_method, out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_plaid_test_contrasts_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g,
+                                      int32_t n, const int32_t* Y, int32_t C, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                                      const double* gsetX, int tests, int metap_method, double* out) try {
+  PH_REQUIRE(Xp != nullptr, "plaid_test_contrasts: null X");
+  return dispatch(on_context(ctx), plaid_test_contrasts_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, Y, C, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
 // replaid.gsva.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, kGsvaExact)

@@ -2,6 +2,8 @@
 // Host only: api.cpp and multi.cpp.
 #pragma once
 
+#include <vector>
+
 #include "common.h"
 
 namespace plaidhip {
@@ -9,7 +11,7 @@ namespace plaidhip {
 // the ordinals are what the test hooks plaidhip_debug_sharded_on_one_device / _scorer_sharded_on_one_device take
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
-  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12
+  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -48,6 +50,10 @@ struct Call : Operands {
   int tests = 0, metap_method = 0;
   int64_t n0 = 0, n1 = 0;
   double* out = nullptr;
+  // plaid.test.contrasts: y is Y (n x C, column-major, -1: the sample takes no part), out m x 6 x C; the group sizes of
+  // every contrast (counted by check_call)
+  int32_t ncontrast = 0;
+  std::vector<int64_t> cn0, cn1;
   // sing.exact: the down sets (null: none), center, and the six nullable results (total, up, down score; total, up, down
   // dispersion)
   const int32_t* Dp = nullptr;
@@ -141,6 +147,18 @@ inline Call gsva_call(const Operands& x, double tau, int rowtf, double* S_out) {
 inline Call plaid_test_call(const Operands& x, const int32_t* y, const double* gsetX, int tests, int metap_method, double* out) {
   Call c = make_call(kPlaidTest, x, nullptr);
   c.y = y;
+  c.gsetX = gsetX;
+  c.tests = tests;
+  c.metap_method = metap_method;
+  c.out = out;
+  return c;
+}
+// plaid.test(X[, sel_j], Y[sel_j, j], G, gsetX = S_all[, sel_j]) for every column j of Y, sel_j = which(!is.na(Y[, j]))
+inline Call plaid_test_contrasts_call(const Operands& x, const int32_t* Y, int32_t C, const double* gsetX, int tests,
+                                      int metap_method, double* out) {
+  Call c = make_call(kPlaidTestContrasts, x, nullptr);
+  c.y = Y;
+  c.ncontrast = C;
   c.gsetX = gsetX;
   c.tests = tests;
   c.metap_method = metap_method;

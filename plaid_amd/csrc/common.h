@@ -337,6 +337,19 @@ int launch_transpose_f64(plaidhip_ctx* ctx, const double* A, int64_t lda, int32_
                          int64_t ldb);
 int launch_fold_change(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, int64_t ld2, double* d_F);
 int64_t row_group_ws_doubles(int32_t rows, int32_t n);
+// kernels_contrasts.hip (plaid.test.contrasts): the same moments for C label columns per read of the matrix.  d_Y: n x C
+// labels (0, 1, else excluded), leading dimension ldy; d_masks: contrast_mask_bytes(n, C) bytes, filled by
+// launch_contrast_masks; ws: row_contrast_ws_doubles(rows, n, C) doubles of block partials [nblk][C][2][rows]; d_mean (null:
+// sums; else sums of squared deviations from it), d_seed, d_out: [C][2][rows]
+int64_t row_contrast_ws_doubles(int32_t rows, int32_t n, int32_t C);
+int64_t contrast_mask_bytes(int32_t n, int32_t C);
+int launch_contrast_masks(plaidhip_ctx* ctx, const int32_t* d_Y, int64_t ldy, int32_t n, int32_t C, void* d_masks);
+int launch_row_contrast_partials(plaidhip_ctx* ctx, const double* S, int64_t ld, int32_t rows, int32_t n,
+                                 const void* d_masks, int32_t C, const double* d_med, double add, const double* d_mean,
+                                 double* ws);
+int launch_reduce_blocks_flat(plaidhip_ctx* ctx, const double* ws, int64_t len, int32_t n, const double* d_seed,
+                              double* d_out);
+int launch_fold_change_contrasts(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, int32_t C, int64_t ld2, double* d_F);
 // kernels_csr.hip: the row view of a CSC matrix (replaid.gsva / plaid.test on a dgCMatrix).  All pointers are device
 // pointers.  Transpose: Rp g + 1, Rx / Rj / perm Xp[n] entries each (Rj, perm optional), within a row ascending column
 // order; *d_maxlen = the longest row.  Uses the context workspace.

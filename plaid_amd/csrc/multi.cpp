@@ -306,7 +306,8 @@ struct Shared {
 // partials of the one-device call in the same order; everything else takes plaidhip_shard_bounds.
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
   int64_t lo64 = 0, hi64 = 0;
-  if (((c.method == kGsva || (c.method == kGsvaExact && c.rowtf == 0)) && c.Xp == nullptr) || c.method == kPlaidTest) {
+  if (((c.method == kGsva || (c.method == kGsvaExact && c.rowtf == 0)) && c.Xp == nullptr) || c.method == kPlaidTest ||
+      c.method == kPlaidTestContrasts) {
     constexpr int64_t kBlock = 128;
     const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
     lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
@@ -1588,6 +1589,192 @@ int plaid_test_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
   return s.finish();
 }
 
+// chain_block_sums for the [nblk][C][2][rows] partials of launch_row_contrast_partials: every contrast and group at once
+// (launch_reduce_blocks_flat); run, d_seed, d_run: [C][2][rows].  ndev rendezvous.
+void chain_contrast_sums(Shard& s, std::vector<double>& run, const double* ws, int32_t rows, int32_t C, double* d_seed,
+                         double* d_run) {
+  plaidhip_ctx* ctx = s.ctx;
+  const int64_t len = (int64_t)C * 2 * rows;
+  for (int r = 0; r < s.ndev; ++r) {
+    if (r == s.k)
+      s.step([&]() -> int {
+        if (s.nloc == 0) return PLAIDHIP_OK;
+        PH_HIP(hipMemcpyAsync(d_seed, run.data(), (size_t)len * 8, hipMemcpyHostToDevice, ctx->stream));
+        PH_TRY(launch_reduce_blocks_flat(ctx, ws, len, s.nloc, d_seed, d_run));
+        PH_HIP(hipMemcpyAsync(run.data(), d_run, (size_t)len * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        return PLAIDHIP_OK;
+      });
+    s.sh.rv.arrive_and_wait();
+  }
+}
+
+// scaled_group_means for every contrast of [C][2][rows] chained sums, each with its own group sizes
+void scaled_contrast_means(const Call& c, const std::vector<double>& sums, int32_t rows, double* mean) {
+  for (int32_t j = 0; j < c.ncontrast; ++j) {
+    const int64_t n0 = c.cn0[(size_t)j], n1 = c.cn1[(size_t)j];
+    const double s0 = n0 > 0 ? 1.0 / (double)n0 : std::numeric_limits<double>::quiet_NaN();
+    const double s1 = n1 > 0 ? 1.0 / (double)n1 : std::numeric_limits<double>::quiet_NaN();
+    const size_t o = (size_t)j * 2 * rows;
+    for (int32_t i = 0; i < rows; ++i) {
+      mean[o + i] = sums[o + i] * s0;
+      mean[o + rows + i] = sums[o + rows + i] * s1;
+    }
+  }
+}
+
+// one device's part of plaid.test.contrasts (kPlaidTestContrasts; include/plaidhip.h: plaidhip_plaid_test_contrasts):
+// plaid_test_worker with C label columns.  The same phases and rendezvous; what was [2][rows] is [C][2][rows], the row
+// moments come from kernels_contrasts.hip (every read of X and of S shared by a tile of contrasts), plaid(X, G) and the
+// medians run once, and shard 0 takes Gt [fc_j, fc_j^2] per contrast with the crossprod call of plaid_test_worker.  A
+// contrast adds what plaid_test_worker adds for its label column, in its order.
+int plaid_test_contrasts_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc;
+  const int32_t g = c.g, m = c.m, n = c.n, C = c.ncontrast;
+  const bool sparse = c.Xp != nullptr;
+  const bool lm = (c.tests & 4) != 0;
+  const bool scores = lm && c.gsetX == nullptr;   // plaid(X, G) computed here (R/plaid.R:424-427), once
+  const int64_t ldg = even_ld(g);
+  const int64_t wide = std::max<int64_t>(g, m);
+  const size_t nl = (size_t)std::max(nloc, 1);
+  plaidhip_geneset* gs = nullptr;
+  CtxBuf dX{ctx, 0}, dXp{ctx, 1}, dXi{ctx, 2}, dS{ctx, 4}, dsmall{ctx, 5};
+  DevBuf dY, dmask, dws, drows, drp, dRj, dRx, dF, dT;
+  uint32_t* d_flags = nullptr;
+  double *d_med = nullptr, *d_seed = nullptr, *d_run = nullptr, *d_mean = nullptr;
+  const int64_t zx = s.zx;
+  std::vector<int32_t> ploc;
+  // host sources of asynchronous uploads: they live until the worker's last synchronisation
+  std::vector<double> x_mean, s_mean;
+
+  // ---- upload; the labels and their masks; X's group sums of this shard; plaid()'s crossprod of dense X ---------------------
+  s.step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    if (k == 0 || scores) PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    PH_TRY(dsmall.alloc(64 + nl * 8));
+    d_flags = dsmall.as<uint32_t>();
+    d_med = reinterpret_cast<double*>(dsmall.as<char>() + 64);
+    PH_HIP(hipMemsetAsync(dsmall.p, 0, 64, ctx->stream));
+    PH_TRY(drows.alloc((size_t)wide * 6 * C * 8));   // [seed | running sums | means], [C][2][max(g, m)] each
+    d_seed = drows.as<double>();
+    d_run = d_seed + 2 * wide * C;
+    d_mean = d_run + 2 * wide * C;
+    if (lm) PH_TRY(dS.alloc((size_t)m * nl * 8));
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(dY.alloc((size_t)nloc * C * 4));   // the shard's rows of Y, nloc x C
+    for (int32_t j = 0; j < C; ++j)
+      PH_HIP(hipMemcpyAsync(dY.as<int32_t>() + (size_t)j * nloc, c.y + (size_t)j * n + lo, (size_t)nloc * 4,
+                            hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dmask.alloc((size_t)contrast_mask_bytes(nloc, C)));
+    PH_TRY(launch_contrast_masks(ctx, dY.as<int32_t>(), nloc, nloc, C, dmask.p));
+    PH_TRY(dws.alloc((size_t)std::max<int64_t>(
+        {sparse ? 0 : row_contrast_ws_doubles(g, nloc, C), lm ? row_contrast_ws_doubles(m, nloc, C) : 0, 1}) * 8));
+    if (!sparse) {
+      PH_TRY(dX.alloc((size_t)ldg * nloc * 8));
+      auto on_panel = [&](int64_t c0, int64_t c1) -> int {   // (shard_worker's plaid())
+        return launch_spmm_dense_f64(ctx, gs, dX.as<double>() + c0 * ldg, ldg, (int32_t)(c1 - c0), PLAIDHIP_STAT_MEAN, 1.0,
+                                     nullptr, 0.0, dS.as<double>() + c0 * m, m, d_flags);
+      };
+      PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ldg * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
+                              (size_t)g * 8, nloc, scores ? std::function<int(int64_t, int64_t)>(on_panel) : nullptr));
+      return launch_row_contrast_partials(ctx, dX.as<double>(), ldg, g, nloc, dmask.p, C, nullptr, 0.0, nullptr,
+                                          dws.as<double>());
+    }
+    int32_t max_nnz = 0;
+    PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
+    const size_t zb = (size_t)std::max<int64_t>(zx, 1);
+    // the shard's row view, built once; the unscaled group sums of its stored values, per contrast
+    PH_TRY(drp.alloc((size_t)(g + 2) * 4));
+    PH_TRY(dRj.alloc(zb * 4));
+    PH_TRY(dRx.alloc(zb * 8));
+    PH_TRY(launch_csc_to_csr(ctx, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), g, nloc, drp.as<int32_t>(),
+                             dRj.as<int32_t>(), dRx.as<double>(), nullptr, drp.as<int32_t>() + g + 1));
+    int32_t max_row = 0;
+    PH_HIP(hipMemcpyAsync(&max_row, drp.as<int32_t>() + g + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    for (int32_t j = 0; j < C; ++j)
+      PH_TRY(launch_csr_row_group_stored_sums(ctx, drp.as<int32_t>(), dRj.as<int32_t>(), dRx.as<double>(), g, max_row,
+                                              dY.as<int32_t>() + (size_t)j * nloc, d_run + (size_t)j * 2 * g));
+    std::vector<double> sums((size_t)g * 2 * C);
+    PH_HIP(hipMemcpyAsync(sums.data(), d_run, sums.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    sh.row_sum[(size_t)k] = std::move(sums);   // (each shard writes its own slot)
+    return PLAIDHIP_OK;
+  });
+
+  // ---- logFC_j (R/plaid.R:407-409 on the contrast's samples); shard 0: Gt fc_j, Gt fc_j^2 (:478-479) ------------------------
+  if (!sparse) chain_contrast_sums(s, sh.chain_x, dws.as<double>(), g, C, d_seed, d_run);
+  else sh.rv.arrive_and_wait();   // every shard's stored-value sums are in sh.row_sum
+  s.step([&]() -> int {
+    if (k != 0) return PLAIDHIP_OK;
+    x_mean.resize((size_t)g * 2 * C);
+    if (!sparse) {
+      scaled_contrast_means(c, sh.chain_x, g, x_mean.data());
+    } else {   // the shards added in shard order, then csr_row_moments_kernel's true division (0 / 0 = NaN, empty group)
+      for (int32_t j = 0; j < C; ++j) {
+        const size_t o = (size_t)j * 2 * g;
+        for (int32_t i = 0; i < g; ++i) {
+          double s0 = 0.0, s1 = 0.0;
+          for (int q = 0; q < ndev; ++q)
+            if (!sh.row_sum[(size_t)q].empty()) { s0 += sh.row_sum[(size_t)q][o + i]; s1 += sh.row_sum[(size_t)q][o + g + i]; }
+          x_mean[o + i] = s0 / (double)c.cn0[(size_t)j];
+          x_mean[o + g + i] = s1 / (double)c.cn1[(size_t)j];
+        }
+      }
+    }
+    PH_TRY(dF.alloc((size_t)ldg * 2 * C * 8));
+    PH_TRY(dT.alloc((size_t)m * 2 * C * 8));
+    PH_HIP(hipMemcpyAsync(d_mean, x_mean.data(), x_mean.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_HIP(hipMemsetAsync(dF.p, 0, (size_t)ldg * 2 * C * 8, ctx->stream));
+    PH_TRY(launch_fold_change_contrasts(ctx, d_mean, g, C, ldg, dF.as<double>()));
+    for (int32_t j = 0; j < C; ++j)   // two columns per call: the crossprod call of plaid_test_worker, so its bits
+      PH_TRY(launch_spmm_dense_f64(ctx, gs, dF.as<double>() + (size_t)j * 2 * ldg, ldg, 2, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0,
+                                   dT.as<double>() + (size_t)j * 2 * m, m, nullptr));
+    PH_HIP(hipMemcpyAsync(sh.pt_T.data(), dT.p, (size_t)m * 2 * C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(sh.pt_F.data(), dF.p, (size_t)ldg * 2 * C * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  });
+
+  // ---- the scores, once: gsetX's columns, or plaid(X, G)'s crossprod of a dgCMatrix (dense X: done panel by panel above) ----
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nloc == 0 || !lm) return PLAIDHIP_OK;
+    if (!scores)
+      return upload_pipelined(ctx, dS.as<char>(), (size_t)m * 8, reinterpret_cast<const char*>(c.gsetX + (int64_t)lo * m),
+                              (size_t)m * 8, nloc, nullptr);
+    if (!sparse) return PLAIDHIP_OK;
+    const int64_t nnz_choice = (int64_t)((double)c.Xp[n] / (double)n * (double)nloc);   // (as shard_worker)
+    return launch_spmm_csc_fused_f64(ctx, gs, dXp.as<int32_t>(), dXi.as<int32_t>(), dX.as<double>(), nloc, zx,
+                                     PLAIDHIP_STAT_MEAN, 1.0, nullptr, 0.0, dS.as<double>(), m, d_flags, /*bounded=*/false,
+                                     nullptr, 0.0, nnz_choice);
+  });
+
+  // ---- normalize_medians (R/plaid.R:554-575) over ALL samples, up to mean(medx): the shift is applied on load below ---------
+  const double add = scores ? medians_and_their_mean(s, dS.as<double>(), d_flags, d_med) : 0.0;
+
+  // ---- Welch moments of the score rows, every contrast per read of S (Rfast::ttests(t(gsetX), ina = y + 1), :429) -----------
+  if (lm) {
+    const double* med = scores ? d_med : nullptr;
+    s.step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      return launch_row_contrast_partials(ctx, dS.as<double>(), m, m, nloc, dmask.p, C, med, add, nullptr, dws.as<double>());
+    });
+    chain_contrast_sums(s, sh.chain_s, dws.as<double>(), m, C, d_seed, d_run);
+    s.step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      s_mean.resize((size_t)m * 2 * C);
+      scaled_contrast_means(c, sh.chain_s, m, s_mean.data());
+      PH_HIP(hipMemcpyAsync(d_mean, s_mean.data(), s_mean.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+      return launch_row_contrast_partials(ctx, dS.as<double>(), m, m, nloc, dmask.p, C, med, add, d_mean, dws.as<double>());
+    });
+    chain_contrast_sums(s, sh.chain_q, dws.as<double>(), m, C, d_seed, d_run);
+  }
+
+  return s.finish();
+}
+
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
@@ -1607,8 +1794,18 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.pt_F.assign((size_t)even_ld(c.g) * 2, 0.0);
     sh.row_sum.resize((size_t)ndev);
   }
+  if (c.method == kPlaidTestContrasts) {   // plaid.test's, [C] of each
+    const size_t C = (size_t)c.ncontrast;
+    sh.chain_x.assign((size_t)c.g * 2 * C, 0.0);
+    sh.chain_s.assign((size_t)c.m * 2 * C, 0.0);
+    sh.chain_q.assign((size_t)c.m * 2 * C, 0.0);
+    sh.pt_T.assign((size_t)c.m * 2 * C, 0.0);
+    sh.pt_F.assign((size_t)even_ld(c.g) * 2 * C, 0.0);
+    sh.row_sum.resize((size_t)ndev);
+  }
   auto worker = [&](int k) {
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
     return is_rank_sum(c.method) ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
   };
   int rc = PLAIDHIP_OK;
@@ -1648,6 +1845,28 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     }
     rc = plaidhip_plaid_test_finish(c.g, c.m, c.Gp, sh.pt_T.data(), tot1, tot2, (c.tests & 4) ? SM.data() : nullptr, c.n0,
                                     c.n1, c.tests, c.metap_method, c.out);
+  }
+  if (rc == PLAIDHIP_OK && c.method == kPlaidTestContrasts) {   // the same host half, once per contrast with its group sizes
+    const int64_t ldg = even_ld(c.g);
+    const size_t m = (size_t)c.m;
+    std::vector<double> SM, means;
+    if (c.tests & 4) {
+      SM.resize(m * 4);
+      means.resize(m * 2 * (size_t)c.ncontrast);
+      scaled_contrast_means(c, sh.chain_s, c.m, means.data());
+    }
+    for (int32_t j = 0; j < c.ncontrast && rc == PLAIDHIP_OK; ++j) {
+      const double* F = sh.pt_F.data() + (size_t)j * 2 * ldg;
+      double tot1 = 0.0, tot2 = 0.0;
+      for (int32_t i = 0; i < c.g; ++i) { tot1 += F[(size_t)i]; tot2 += F[(size_t)ldg + i]; }
+      if (c.tests & 4) {
+        std::copy(means.begin() + (size_t)j * 2 * m, means.begin() + (size_t)(j + 1) * 2 * m, SM.begin());
+        std::copy(sh.chain_q.begin() + (size_t)j * 2 * m, sh.chain_q.begin() + (size_t)(j + 1) * 2 * m, SM.begin() + 2 * m);
+      }
+      rc = plaidhip_plaid_test_finish(c.g, c.m, c.Gp, sh.pt_T.data() + (size_t)j * 2 * m, tot1, tot2,
+                                      (c.tests & 4) ? SM.data() : nullptr, c.cn0[(size_t)j], c.cn1[(size_t)j], c.tests,
+                                      c.metap_method, c.out + (size_t)j * 6 * m);
+    }
   }
   return rc;
 }
@@ -1860,6 +2079,32 @@ int check_plaid_test_call(Call& c) {
   return PLAIDHIP_OK;
 }
 
+// plaid.test.contrasts: plaid.test's checks with Y (n x C; 0, 1, -1 = NA) for y; counts every contrast's groups
+int check_plaid_test_contrasts_call(Call& c) {
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  PH_REQUIRE(c.ncontrast >= 0 && c.ncontrast <= 65535, "plaid_test_contrasts: C = %d (0 <= C <= 65535)", c.ncontrast);
+  PH_REQUIRE(c.m == 0 || c.ncontrast == 0 || c.out, "plaid_test_contrasts: null out");
+  PH_REQUIRE(c.n == 0 || c.Xp != nullptr || c.X != nullptr, "plaid_test_contrasts: null X");
+  PH_REQUIRE(c.n == 0 || c.ncontrast == 0 || c.y != nullptr, "plaid_test_contrasts: null Y");
+  PH_REQUIRE((c.tests & 7) != 0 && (c.tests & ~7) == 0, "plaid_test: tests is a bit mask of 1 (one), 2 (two), 4 (lm)");
+  PH_REQUIRE(c.metap_method == 0 || c.metap_method == 1, "Invalid method: %d", c.metap_method);   // R/plaid.R:533
+  c.cn0.assign((size_t)c.ncontrast, 0);
+  c.cn1.assign((size_t)c.ncontrast, 0);
+  for (int32_t j = 0; j < c.ncontrast; ++j)
+    for (int32_t i = 0; i < c.n; ++i) {
+      const int32_t lab = c.y[(size_t)j * c.n + i];
+      PH_REQUIRE(lab == 0 || lab == 1 || lab == -1, "elements of Y must be 0, 1 or NA (-1): contrast %d, sample %d is %d",
+                 j + 1, i + 1, lab);
+      if (lab == 1) ++c.cn1[(size_t)j];
+      else if (lab == 0) ++c.cn0[(size_t)j];
+    }
+  if (c.Xp != nullptr) {
+    PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
+    PH_REQUIRE(c.Xp[c.n] == 0 || (c.Xi && c.X), "plaid_test_contrasts: null Xi/Xx");
+  }
+  return PLAIDHIP_OK;
+}
+
 std::mutex g_multi_mu;
 std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
 int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
@@ -1915,6 +2160,7 @@ int check_call(Call& c, int ndev, bool multi) {
   if (is_rank_sum(c.method)) return check_rank_sum_call(c);
   switch (c.method) {
     case kPlaidTest: return check_plaid_test_call(c);
+    case kPlaidTestContrasts: return check_plaid_test_contrasts_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -1932,7 +2178,11 @@ int dispatch(const Target& t, Call c) {
   if (t.kind == Target::kHook) PH_REQUIRE(t.ndev >= 1 && t.ndev <= 64, "debug_sharded: nshards = %d", t.ndev);
   PH_TRY(check_call(c, t.ndev, t.kind == Target::kDevices));
   if (t.kind == Target::kContext) PH_REQUIRE(t.ctx != nullptr, "null plaidhip_ctx");
-  if (c.method == kPlaidTest ? c.m == 0 : (int64_t)c.m * c.n == 0) return PLAIDHIP_OK;
+  if (c.method == kPlaidTestContrasts) {
+    if (c.m == 0 || c.ncontrast == 0) return PLAIDHIP_OK;
+  } else if (c.method == kPlaidTest ? c.m == 0 : (int64_t)c.m * c.n == 0) {
+    return PLAIDHIP_OK;
+  }
   if (t.kind == Target::kHook) return run_on_one_device(t.device, t.ndev, t.fail_shard, c);
   std::vector<plaidhip_ctx*> ctxs(1, t.ctx);
   if (t.kind == Target::kContext)
@@ -2018,6 +2268,14 @@ int plaidhip_plaid_test_multi(const int* devices, int ndev, const int32_t* Xp, c
                   plaid_test_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
+int plaidhip_plaid_test_contrasts_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi,
+                                        const double* X_or_x, int32_t g, int32_t n, const int32_t* Y, int32_t C,
+                                        const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                                        int metap_method, double* out) try {
+  return dispatch(on_devices(devices, ndev),
+                  plaid_test_contrasts_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Y, C, gsetX, tests, metap_method, out));
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_ssgsea_exact_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
                                 int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale,
                                 int norm, double* S_out) try {
@@ -2068,6 +2326,15 @@ int plaidhip_debug_plaid_test_sharded_on_one_device(int device, int nshards, int
                                                     const double* gsetX, int tests, int metap_method, double* out) try {
   return dispatch(on_hook(device, nshards, fail_shard),
                   plaid_test_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_plaid_test_contrasts_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,
+                                                              const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
+                                                              const int32_t* Y, int32_t C, const int32_t* Gp,
+                                                              const int32_t* Gi, int32_t m, const double* gsetX, int tests,
+                                                              int metap_method, double* out) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  plaid_test_contrasts_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, Y, C, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_ssgsea_exact_sharded_on_one_device(int device, int nshards, int fail_shard, const int32_t* Xp,

@@ -134,6 +134,52 @@ def _plaid_test(fn, head, X, y, Gp, Gi, gsetX, tests, metap_method, dense=False,
                   dense=dense, out=out, cols=6)
 
 
+def contrast_labels(Y, n):
+    """Y of plaid.test.contrasts as the C ABI takes it: n x C int32, Fortran order, -1 for NA.  Y: integers (0, 1, -1) or
+    floats (0, 1, NaN or -1); one column may come as a vector.  Other values are kept (rounded towards zero, an out-of-range
+    or fractional one as 2) for the library's own check to name."""
+    Y = np.asarray(Y)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.ndim != 2 or Y.shape[0] != n:
+        raise ValueError("Y must have one row per column of X")
+    if Y.dtype.kind == "f":
+        with np.errstate(invalid="ignore"):
+            bad = ~np.isnan(Y) & ~np.isin(Y, (0.0, 1.0, -1.0))
+            Y = np.where(np.isnan(Y), -1.0, np.where(bad, 2.0, Y))
+    elif Y.dtype.kind not in "iub":
+        raise ValueError("Y must be numeric: 0, 1, and NaN or -1 for a sample that takes no part")
+    else:
+        Y = np.where((Y < -1) | (Y > 1), 2, Y)
+    return np.asfortranarray(Y, dtype=np.int32)
+
+
+def contrast_tile() -> int:
+    """PLAIDHIP_CONTRAST_TILE: the contrasts that share one read of the matrix (needs no device)"""
+    return int(_lib.load().plaidhip_contrast_tile())
+
+
+def _plaid_test_contrasts(fn, head, X, Y, Gp, Gi, gsetX, tests, metap_method, dense=False, out=None):
+    """plaid.test.contrasts through _score: sets x 6 x C, [:, :, j] what _plaid_test returns for contrast j"""
+    X = X if isinstance(X, tuple) else _x_args(X)
+    n, m = X[4], len(Gp) - 1
+    Y = contrast_labels(Y, n)
+    ncon = Y.shape[1]
+    sx = None
+    if gsetX is not None:
+        sx = _as_f64_fortran(gsetX)
+        if sx.shape != (m, n):
+            raise ValueError("gsetX must be sets x samples")
+    if out is None:
+        out = np.empty((m, 6, ncon), dtype=np.float64, order="F")
+    elif out.shape != (m, 6, ncon) or out.dtype != np.float64 or not out.flags.f_contiguous or not out.flags.writeable:
+        raise ValueError(f"out: a writeable Fortran-ordered float64 array of shape {(m, 6, ncon)}")
+    flat = out.reshape((m, 6 * ncon), order="F")   # (a view: contrast j's six columns are columns 6 j .. 6 j + 5)
+    _score(fn, head, X, Gp, Gi, None if sx is None else _np_ptr(sx), int(tests), int(metap_method), pre=(_np_ptr(Y), ncon),
+           dense=dense, out=flat, cols=6 * ncon)
+    return out
+
+
 GSVA_EXACT_ROWTF = {"z": 0, "ecdf": 1, "none": 2, "gauss": 3}
 GSVA_KCDF_TABLE = 10001   # PLAIDHIP_GSVA_KCDF_TABLE
 
@@ -450,6 +496,14 @@ class Context:
         """per-row sums over the columns with y == 0 / y == 1 -> sums[2][rows] (plaid.test, R/plaid.R:407-408, 431)"""
         check(self.lib.plaidhip_dev_row_group_sums(self.handle, A, ld, rows, n, y, sums))
 
+    def dev_row_contrast_sums(self, A: int, ld: int, rows: int, n: int, Y: int, C: int, sums: int):
+        """dev_row_group_sums for the C label columns of Y (n x C int32, column-major) at once; sums: [C][2][rows]"""
+        check(self.lib.plaidhip_dev_row_contrast_sums(self.handle, A, ld, rows, n, Y, C, sums))
+
+    def dev_row_contrast_ssd(self, A: int, ld: int, rows: int, n: int, Y: int, C: int, mean: int, ssd: int):
+        """dev_row_group_ssd for C label columns at once; mean, ssd: [C][2][rows]"""
+        check(self.lib.plaidhip_dev_row_contrast_ssd(self.handle, A, ld, rows, n, Y, C, mean, ssd))
+
     def dev_row_group_ssd(self, A: int, ld: int, rows: int, n: int, y: int, mean: int, ssd: int):
         """per-row sums of squared deviations from the given group means -> ssd[2][rows] (R/plaid.R:429)"""
         check(self.lib.plaidhip_dev_row_group_ssd(self.handle, A, ld, rows, n, y, mean, ssd))
@@ -620,6 +674,17 @@ class Context:
         return _plaid_test(self.lib.plaidhip_plaid_test_csc, (self.handle,), _slots(Xp, Xi, Xx, g), y, Gp, Gi, gsetX, tests,
                            metap_method)
 
+    def plaid_test_contrasts(self, X, Y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
+        """plaidhip_plaid_test_contrasts: Y n x C (0, 1, NaN or -1: the sample takes no part).  Returns sets x 6 x C,
+        [:, :, j] = plaid_test on the samples of contrast j, with the scores of all samples"""
+        return _plaid_test_contrasts(self.lib.plaidhip_plaid_test_contrasts, (self.handle,), _as_f64_fortran(X), Y, Gp, Gi,
+                                     gsetX, tests, metap_method, dense=True)
+
+    def plaid_test_contrasts_csc(self, Xp, Xi, Xx, g, Y, Gp, Gi, gsetX=None, tests=7, metap_method=0):
+        """plaidhip_plaid_test_contrasts_csc: Context.plaid_test_contrasts on the slots of a g x n CSC matrix"""
+        return _plaid_test_contrasts(self.lib.plaidhip_plaid_test_contrasts_csc, (self.handle,), _slots(Xp, Xi, Xx, g), Y, Gp,
+                                     Gi, gsetX, tests, metap_method)
+
 
 def plaid_test_finish(g, Gp, T, tot1, tot2, SM, n0, n1, tests=7, metap_method=0, lib=None):
     """plaidhip_plaid_test_finish (host only): the p-values, effect sizes, meta-p and FDR of plaid.test from the reduced
@@ -745,6 +810,12 @@ def plaid_test_multi(X, y, Gp, Gi, gsetX=None, tests=7, metap_method=0, devices=
     CSC.  The scores stay on the devices: only per-gene and per-set sums cross between them.  Returns sets x 6 (gsetFC,
     p.one, p.two, p.lm, p.meta, q.meta) in G's column order; dense X gives the single-device result bit for bit."""
     return _plaid_test(*_multi("plaid_test", devices), X, y, Gp, Gi, gsetX, tests, metap_method)
+
+
+def plaid_test_contrasts_multi(X, Y, Gp, Gi, gsetX=None, tests=7, metap_method=0, devices=1) -> np.ndarray:
+    """plaid.test.contrasts (Context.plaid_test_contrasts / _csc) with the sample columns sharded over `devices`, as
+    plaid_test_multi; sets x 6 x C, dense X the single-device result bit for bit"""
+    return _plaid_test_contrasts(*_multi("plaid_test_contrasts", devices), X, Y, Gp, Gi, gsetX, tests, metap_method)
 
 
 def multi_finalize():

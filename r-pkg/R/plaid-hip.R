@@ -429,6 +429,52 @@ plaid.test <- function(X, y, G, gsetX, tests = c("one", "two", "lm"),
 }
 
 
+## plaid.test.contrasts(): plaid.test() for every column of a contrast matrix Y (samples x contrasts; 0, 1, NA = the sample
+## takes no part) in ONE call.  Contrast j is plaid.test(X[, sel], Y[sel, j], G, gsetX = S[, sel]) with sel <- !is.na(Y[, j])
+## and S the gsetX given or plaid(X, G) over all samples, computed once; every pass over the scores is shared by the
+## contrasts.  Returns a named list (the columns of Y) of plaid.test() results.
+plaid.test.contrasts <- function(X, Y, G, gsetX = NULL, tests = c("one", "two", "lm"),
+                                 metap.method = "fisher", sort.by = "p.meta") {
+  Y <- as.matrix(Y)
+  if (nrow(Y) != ncol(X)) stop("Y must have one row per column of X")
+  if (!all(unique(as.vector(Y)) %in% c(0, 1, NA))) stop("elements of Y must be 0, 1 or NA")
+  if (is.list(G)) {
+    message("[plaid.test] converting gmt to sparse matrix...")
+    G <- gmt2mat(G)
+  }
+  if (!metap.method %in% c("fisher", "sumlog", "stouffer", "sumz")) stop("Invalid method: ", metap.method)
+  gg <- intersect(rownames(G), rownames(X))
+  sparse <- inherits(X, "CsparseMatrix")
+  if (sparse) {
+    X <- methods::as(X[gg, , drop = FALSE], "generalMatrix")
+  } else {
+    X <- as.matrix(X[gg, , drop = FALSE]); storage.mode(X) <- "double"
+  }
+  G <- G[gg, , drop = FALSE]
+  pat <- .aligned_pattern(X, G)
+  if (!is.null(gsetX)) { gsetX <- as.matrix(gsetX[colnames(G), , drop = FALSE]); storage.mode(gsetX) <- "double" }
+  bits <- sum(c(one = 1L, two = 2L, lm = 4L)[intersect(tests, c("one", "two", "lm"))])
+  .session()
+  mm <- as.integer(metap.method %in% c("stouffer", "sumz"))
+  Yi <- matrix(as.integer(Y), nrow(Y), ncol(Y))
+  Yi[is.na(Yi)] <- -1L
+  xa <- .x_args(X)
+  r <- .Call("R_plaidhip_plaid_test_contrasts", .devices(), xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), Yi, pat$Gp, pat$Gi,
+             gsetX, bits, mm, PACKAGE = "plaidhip")
+  dim(r) <- c(nrow(r), 6L, ncol(Y))
+  keep <- c(TRUE, "one" %in% tests, "two" %in% tests, "lm" %in% tests, TRUE, TRUE)
+  cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
+  out <- lapply(seq_len(ncol(Y)), function(j) {
+    res <- matrix(r[, keep, j], nrow = dim(r)[1])
+    dimnames(res) <- list(colnames(G), c("gsetFC", "p.one", "p.two", "p.lm", "p.meta", "q.meta")[keep])
+    if (sort.by %in% colnames(res)) res <- res[order(res[, sort.by]), , drop = FALSE]
+    res
+  })
+  names(out) <- cn
+  out
+}
+
+
 ## replaid.gsva(), R/plaid.R:338-363: the row transform ("z" or "ecdf"), the signed ranks, the power and
 ## plaid() run on the device in one call.
 replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {

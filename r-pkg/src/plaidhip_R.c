@@ -504,6 +504,31 @@ SEXP R_plaidhip_plaid_test_multi(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g
   return out;
 }
 
+/* plaid.test.contrasts(): an m x 6C matrix, columns 6 j + 1 .. 6 j + 6 the matrix of R_plaidhip_plaid_test for contrast j
+ * (the caller gives it dim m x 6 x C).  Y: n x C
+ * integers, -1 for NA.  Dense X (Xp, Xi NULL, Xv the matrix) or a dgCMatrix's slots; several devices: the _multi entry */
+SEXP R_plaidhip_plaid_test_contrasts(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Y, SEXP Gp, SEXP Gi,
+                                     SEXP gsetX, SEXP tests, SEXP metap) {
+  const int m = LENGTH(Gp) - 1, C = Rf_ncols(Y);
+  const double* gx = Rf_isNull(gsetX) ? NULL : REAL(gsetX);
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 6 * C));
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_plaid_test_contrasts_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv),
+                                             Rf_asInteger(g), Rf_asInteger(n), INTEGER(Y), C, INTEGER(Gp), INTEGER(Gi), m, gx,
+                                             Rf_asInteger(tests), Rf_asInteger(metap), REAL(out));
+  else if (!Rf_isNull(Xp))
+    rc = plaidhip_plaid_test_contrasts_csc(ctx(), INTEGER(Xp), INTEGER(Xi), REAL(Xv), Rf_asInteger(g), Rf_asInteger(n),
+                                           INTEGER(Y), C, INTEGER(Gp), INTEGER(Gi), m, gx, Rf_asInteger(tests),
+                                           Rf_asInteger(metap), REAL(out));
+  else
+    rc = plaidhip_plaid_test_contrasts(ctx(), REAL(Xv), Rf_asInteger(g), Rf_asInteger(n), INTEGER(Y), C, INTEGER(Gp),
+                                       INTEGER(Gi), m, gx, Rf_asInteger(tests), Rf_asInteger(metap), REAL(out));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(1);
+  return out;
+}
+
 /* the same two calls for a dgCMatrix: its slots, no dense X (plaidhip_plaid_test_csc / plaidhip_gsva_csc) */
 SEXP R_plaidhip_plaid_test_csc(SEXP Xp, SEXP Xi, SEXP Xx, SEXP g, SEXP y, SEXP Gp, SEXP Gi, SEXP gsetX, SEXP tests,
                                SEXP metap) {
@@ -566,6 +591,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsva", (DL_FUNC)&R_plaidhip_gsva, 5},
     {"R_plaidhip_plaid_test_csc", (DL_FUNC)&R_plaidhip_plaid_test_csc, 10},
     {"R_plaidhip_plaid_test_multi", (DL_FUNC)&R_plaidhip_plaid_test_multi, 12},
+    {"R_plaidhip_plaid_test_contrasts", (DL_FUNC)&R_plaidhip_plaid_test_contrasts, 12},
     {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
     {NULL, NULL, 0}};
 
