@@ -840,6 +840,60 @@ int plaidhip_dev_row_contrast_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld
                                   const int32_t* Y, int32_t C, const double* mean, double* ssd);
 int plaidhip_contrast_tile(void);   /* PLAIDHIP_CONTRAST_TILE of the built library */
 
+/* plaid.gsea(stats, G, nperm, gseaParam): preranked GSEA with a permutation null -- ES, NES, pval and padj of every set for
+ * every ranked list (a logFC vector, or one per contrast).  The form is fgsea's fgseaSimple with scoreType = "std" AS
+ * RECALLED: the package's source is not in this tree, so the statistic is pinned here, operation for operation, and tested
+ * against these words.
+ * Operands, per ranked list (a column of stat, g x c, column-major, beside weight, g x c, all finite and >= 0):
+ *     N = g genes.  The walk order is order(-stat), stable: tied genes go in row order.
+ *     pos_obs[i] in 0..N-1 is gene i's place in that order (the second rank pass of plaidhip_sing_exact gives it).
+ *     Wpos[pos_obs[i]] = weight[i].  The wrappers pass weight = |stat|^gseaParam, computed on the host: the device never
+ *     calls pow.
+ * A placement is an int32 vector pos[0..N) that is a permutation of 0..N-1.  The observed placement is pos_obs; null
+ * placement b is column b of P (g x B) and is the same for every set and every list.
+ * A set with k members has 1-based positions p_1 < ... < p_k, taken from pos[i] + 1 over its members i.  Then, in fp64:
+ *     w_t = Wpos[p_t - 1];  cw_t = w_1 + ... + w_t;  B = cw_k
+ *     if B == 0:  w_t = 1 for all t   (cw_t = t, B = k: the unweighted walk, as fgsea's calcGseaStat does for NR == 0)
+ *     miss_t = (double)(p_t - t) / (double)(N - k)
+ *     after_t = cw_t / B - miss_t;   before_t = cw_{t-1} / B - miss_t      (t = 1..k, cw_0 = 0)
+ *     maxP = max_t after_t;  minP = min_t before_t
+ *     ES = maxP > -minP ? maxP : (maxP < -minP ? minP : 0.0)
+ * k = 0 or k = N gives NaN in every output column of that set, except `size`.  A list holding a NaN or an infinity in stat
+ * gives NaN for that list.  A negative, NaN or infinite weight is an argument error before any device work.
+ * Per (set, list), over the null scores es_b, b = 0..B-1 (B = nperm):
+ *     nGeEs = #{es_b >= ES}   nLeEs = #{es_b <= ES}   nGeZero = #{es_b >= 0}   nLeZero = #{es_b <= 0}
+ *     sumPos = sum max(es_b, 0)    sumNeg = sum min(es_b, 0)
+ *     NES  = ES > 0 ? ES / (sumPos / nGeZero) : ES / fabs(sumNeg / nLeZero)
+ *     pval = min((1 + nLeEs) / (1 + nLeZero), (1 + nGeEs) / (1 + nGeZero))
+ *     nMoreExtreme = ES > 0 ? nGeEs : nLeEs
+ * The two sums are taken in blocks of PLAIDHIP_GSEA_PERM_BLOCK consecutive permutations: inside a block sequentially in b
+ * from 0.0, the block sums then sequentially in block order from 0.0.  No product is contracted anywhere; the divisions
+ * follow IEEE, so a zero mean gives +-Inf or NaN as the form says.  Where every weight is an integer below 2^20 (or 1)
+ * every cw_t is exact and all of this has the bits of the same operations on the host; for other weights cw_t and B are
+ * summed in an order that depends on the positions alone, never on the sharding.
+ * padj is Benjamini-Hochberg over the sets of one list that have a non-NaN pval (the host routine behind q.meta).
+ * Permutations: perm != NULL is int32, g x nperm, every column checked on the device to be a permutation of 0..g-1 before
+ * it is walked (PLAIDHIP_EINVAL otherwise).  The columns are checked slab by slab as they are uploaded, so a bad column may
+ * be found after earlier slabs were walked: on any error out and null_out are unspecified.  perm == NULL generates the placements from seed: for gene i and permutation b,
+ * Philox4x32-10 with counter (i, b, 0, 0) and key (seed & 0xffffffff, seed >> 32) gives words o0..o3;
+ * r = ((uint64)o0 << 4) | (o1 >> 28) (36 bits);  y = (double)(r 2^17 + i), exact and free of ties because g <= 131,072;
+ * P[., b] = (ascending min rank of y within column b) - 1.  The placement of (i, b) depends on nothing else: it is the same
+ * under every sharding.  plaidhip_gsea_permutations returns these placements themselves (P_out: g x nperm int32).
+ * out: m x 12 x c, column-major: ES, NES, pval, padj, nMoreExtreme, size, nGeEs, nLeEs, nGeZero, nLeZero, sumPos, sumNeg.
+ * null_out (nullable): the m x nperm x c null scores.  Argument errors, in this order: nperm < 1, c < 1,
+ * g > PLAIDHIP_GSEA_KS_MAX_GENES (PLAIDHIP_EUNSUPPORTED), a bad weight, then (on the device) a bad perm column.
+ * plaidhip_gsea_multi shares the permutation blocks out over the devices in whole blocks; every device holds stat, weight
+ * and G; the block partials are chained in block order and reduced once: every sharding returns the one-device bits.
+ * Not offered: scoreType "pos" / "neg", fgsea's multilevel p-values (the smallest pval is 1 / (nperm + 1)), leading edges. */
+#define PLAIDHIP_GSEA_PERM_BLOCK 64
+int plaidhip_gsea(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
+                  const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out,
+                  double* null_out);
+int plaidhip_gsea_multi(const int* devices, int ndev, const double* stat, const double* weight, int32_t g, int32_t c,
+                        const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
+                        double* out, double* null_out);
+int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out);
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

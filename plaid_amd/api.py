@@ -564,3 +564,60 @@ def plaid_test_contrasts(X, Y, G, gsetX=None, tests=("one", "two", "lm"), metap_
     else:
         out = ctx.plaid_test_contrasts(Xs, lab, Gp, Gi, sx, bits, mm)
     return {nm: _plaid_test_table(out[:, :, j], tests, rn, sort_by) for j, nm in enumerate(names)}
+
+
+_GSEA_NAMES = ["ES", "NES", "pval", "padj", "nMoreExtreme", "size"]
+
+
+def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=1, perm=None, sort_by="pval",
+               ctx: Context | None = None):
+    """plaid.gsea(): preranked GSEA (fgsea's fgseaSimple, scoreType "std", as pinned in include/plaidhip.h) of a named
+    vector of statistics, or of every column of a genes x contrasts NamedMatrix, against the sets of G (a gmt or a
+    membership matrix), with a permutation null of `nperm` placements generated on the device from `seed` (or the caller's
+    `perm`, genes x permutations int32 over the aligned genes).  Genes are aligned by name as plaid.test aligns them; the
+    weights |stat|^gseaParam are formed here, on the host.  Sets with fewer than minSize or more than maxSize (default: the
+    aligned genes - 1) aligned members are dropped.  Returns one NamedMatrix (sets x [ES, NES, pval, padj, nMoreExtreme,
+    size]) ordered by `sort_by` when stats is a named vector (a dict or a pandas Series, gene -> statistic); for a
+    NamedMatrix, of one column or of many, a dict, column name -> NamedMatrix, in the columns' order.  The default seed is
+    plaid.gsea's in the R package, so the same call gives the same table in both."""
+    if isinstance(stats, dict):
+        stats = NamedMatrix(np.array(list(stats.values()), dtype=np.float64), list(stats.keys()), ["stat"])
+        single = True
+    else:
+        single = not isinstance(stats, NamedMatrix) and np.ndim(stats) == 1
+        try:
+            import pandas as pd
+            if isinstance(stats, pd.Series):
+                stats, single = NamedMatrix(stats.to_numpy(dtype=np.float64), list(stats.index), ["stat"]), True
+        except ImportError:  # pragma: no cover
+            pass
+    if isinstance(G, (GmtList, dict)) or (isinstance(G, tuple) and len(G) == 2):
+        _message("[plaid.gsea] converting gmt to sparse matrix...")
+        G = gmt2mat(G)
+    stats = as_named(stats)
+    if sp.issparse(stats.values):
+        raise ValueError("plaid.gsea: stats must be dense")
+    gp = float(gseaParam)
+    if not np.isfinite(gp) or gp < 0.0:
+        raise ValueError(f"plaid.gsea: gseaParam must be finite and >= 0 (got {gp:g})")
+    Xs, Gp, Gi, _, _, _, _, rn = _plaid_test_operands(stats, G, None, "one", "fisher")
+    N = Xs.shape[0]
+    sizes = np.diff(Gp)
+    hi = N - 1 if maxSize is None else int(maxSize)
+    keep = np.flatnonzero((sizes >= int(minSize)) & (sizes <= hi))
+    Gi = np.concatenate([Gi[Gp[j]:Gp[j + 1]] for j in keep]).astype(np.int32) if len(keep) else np.zeros(0, np.int32)
+    Gp = np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int32)
+    rn = [rn[j] for j in keep]
+    with np.errstate(invalid="ignore"):
+        W = np.ones_like(Xs) if gp == 0.0 else (np.abs(Xs) if gp == 1.0 else np.abs(Xs) ** gp)
+    W = np.where(np.isfinite(W), W, 0.0)   # (a list with a NaN or an infinity is NaN by the statistic's own rule)
+    ctx = ctx or default_context()
+    out = ctx.gsea(Xs, W, Gp, Gi, perm=perm, nperm=nperm, seed=seed)
+    res = {}
+    for l, nm in enumerate(stats.colnames):
+        tab, names = out[:, :6, l], list(rn)
+        if sort_by in _GSEA_NAMES:
+            o = np.argsort(tab[:, _GSEA_NAMES.index(sort_by)], kind="stable")       # order(): NaN last
+            tab, names = tab[o, :], [names[k] for k in o]
+        res[nm] = NamedMatrix(tab, names, _GSEA_NAMES)
+    return res[stats.colnames[0]] if single and len(res) == 1 else res

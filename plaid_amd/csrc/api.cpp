@@ -1177,6 +1177,36 @@ int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
   return dispatch(on_context(ctx), gsva_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tau, rowtf, max_diff, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.gsea: the one-device form of the sharded engine (multi.cpp: gsea_worker, kGsea)
+int plaidhip_gsea(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
+                  const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out,
+                  double* null_out) try {
+  return dispatch(on_context(ctx), gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them
+int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out) try {
+  PH_REQUIRE(g >= 1 && nperm >= 1, "gsea_permutations: bad dims g=%d nperm=%d", g, nperm);
+  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("gsea_permutations: %d genes (at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  PH_REQUIRE(P_out != nullptr, "gsea_permutations: null P_out");
+  PH_CTX(ctx);
+  const int32_t slab = std::min(nperm, gsea_slab_perms(g));
+  DevBuf dY, dR, dP;
+  PH_TRY(dY.alloc((size_t)g * slab * 8));
+  PH_TRY(dR.alloc((size_t)g * slab * 8));
+  PH_TRY(dP.alloc((size_t)g * slab * 4));
+  for (int64_t b0 = 0; b0 < nperm; b0 += slab) {
+    const int32_t nb = (int32_t)std::min<int64_t>(slab, nperm - b0);
+    PH_TRY(launch_gsea_placements(ctx, g, b0, nb, seed, dY.as<double>(), dR.as<double>(), dP.as<int32_t>()));
+    PH_HIP(hipMemcpyAsync(P_out + b0 * g, dP.p, (size_t)g * nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
 // GSVA's Gaussian kernel CDF estimate alone (the row transform "gauss" of replaid.gsva.exact): V, g x n
 int plaidhip_gsva_kcdf(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                        double* V_out) try {

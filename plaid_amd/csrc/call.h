@@ -11,7 +11,7 @@ namespace plaidhip {
 // the ordinals are what the test hooks plaidhip_debug_sharded_on_one_device / _scorer_sharded_on_one_device take
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
-  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13
+  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -65,6 +65,16 @@ struct Call : Operands {
   double max_rank = 0.0;
   double w_neg = 1.0;
   const double* k_full_down = nullptr;
+  // plaid.gsea: X is stat (g x n, n = the ranked lists, dense), out m x 12 x n; the weights beside stat, the caller's
+  // placements (null: generated from seed), the permutations, the nullable m x nperm x n null scores; whether any weight
+  // differs from 1 and which lists hold a NaN or an infinity (both found by check_call)
+  const double* weight = nullptr;
+  const int32_t* perm = nullptr;
+  int32_t nperm = 0;
+  uint64_t seed = 0;
+  double* null_out = nullptr;
+  int gsea_weighted = 0;
+  std::vector<uint32_t> listnan;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -218,6 +228,18 @@ inline Call aucell_exact_call(const Operands& x, double auc_max_rank, double* S_
   c.normalize = 0;
   c.max_rank = auc_max_rank;
   return c;
+}
+// fgseaSimple(scoreType = "std") as pinned in include/plaidhip.h: plaidhip_gsea
+inline Call gsea_call(const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
+                      int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out, double* null_out) {
+  Call k = make_call(kGsea, {nullptr, nullptr, stat, g, c, Gp, Gi, m}, nullptr);
+  k.weight = weight;
+  k.perm = perm;
+  k.nperm = nperm;
+  k.seed = seed;
+  k.out = out;
+  k.null_out = null_out;
+  return k;
 }
 
 // ---- where a call runs -------------------------------------------------------------------------------------------------

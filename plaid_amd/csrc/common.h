@@ -553,6 +553,33 @@ int gsva_kcdf_columns(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, c
                       int32_t lo, int32_t nloc, double* dV);
 // range_out[3] = {min, max, any NaN} of the m x n scores; part: 3 ssgsea_exact_part_blocks(m n) doubles
 int launch_gsea_ks_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out);
+// kernels_gsea.hip: plaid.gsea (include/plaidhip.h: plaidhip_gsea).  All stream-ordered, all pointers device pointers.
+// pos_obs (c x g int32) and Wpos (c x g) of every list from its last ranks Q and weights W (leading dimension ld; the
+// outputs are packed, leading dimension g); a list flagged in listnan is skipped
+int launch_gsea_operands(plaidhip_ctx* ctx, const double* Q, const double* W, int64_t ld, const uint32_t* listnan, int32_t g,
+                         int32_t c, int32_t* pos_obs, double* Wpos);
+// P (g x nb int32) <- the generated placements of the permutations b0 .. b0 + nb - 1; Y, R: g x nb doubles of scratch
+int launch_gsea_placements(plaidhip_ctx* ctx, int32_t g, int64_t b0, int32_t nb, uint64_t seed, double* Y, double* R,
+                           int32_t* P);
+// the permutations one slab of the null holds: Y, R (fp64) and P (int32) of a slab stay within 256 MB, whole blocks of
+// PLAIDHIP_GSEA_PERM_BLOCK, at least one (gsea_worker and plaidhip_gsea_permutations walk the same slabs)
+inline int32_t gsea_slab_perms(int32_t g) {
+  const int64_t fit = ((int64_t)256 << 20) / (20 * (int64_t)(g > 1 ? g : 1)) / PLAIDHIP_GSEA_PERM_BLOCK * PLAIDHIP_GSEA_PERM_BLOCK;
+  return (int32_t)(fit > PLAIDHIP_GSEA_PERM_BLOCK ? fit : PLAIDHIP_GSEA_PERM_BLOCK);
+}
+// bad[0] |= 1 and bad[1] = max(bad[1], col0 + column + 1) for every column of P (g x nb) that is no permutation of 0..g-1
+int launch_gsea_check_perm(plaidhip_ctx* ctx, const int32_t* P, int32_t g, int32_t nb, int32_t col0, uint32_t* bad);
+// ES (c x m) <- the observed scores; weighted == 0: every weight is 1 (Wpos is not read)
+int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, const int32_t* pos_obs, const double* Wpos, const uint32_t* listnan,
+                    int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* ES);
+// the null walks of the nbs placements in P (whole blocks of 64 but the call's last): their block partials into
+// part[blk_at0 ..][c][6][m], the scores into null_out ([c][nbs][m]) when it is not null
+int launch_gsea_null(plaidhip_ctx* ctx, int weighted, const int32_t* P, int32_t nbs, const double* Wpos, const uint32_t* listnan,
+                     const double* ES, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* part,
+                     int64_t blk_at0, double* null_out);
+// out (m x 12 x c; padj left NaN) from all nblk blocks of partials, added in block order
+int launch_gsea_null_reduce(plaidhip_ctx* ctx, const double* part, int32_t nblk, const double* ES, const int32_t* Gp, int32_t m,
+                            int32_t c, double* out);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 int launch_col_medians(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n,

@@ -299,6 +299,8 @@ struct Shared {
   std::vector<double> chain_x, chain_s, chain_q, pt_T, pt_F;
   // replaid.ssgsea.exact with norm: a NaN among the scores of any shard (its min / max go to xmin / xmax)
   bool es_nan = false;
+  // plaid.gsea: the block partials [nblk][c][6][m] of all permutation blocks, each shard writing its own blocks
+  std::vector<double> gsea_part;
 };
 
 // columns [lo, lo + nloc) of shard k.  Dense replaid.gsva and plaid.test (dense or not: its score rows are chained too)
@@ -1775,6 +1777,123 @@ int plaid_test_contrasts_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int 
   return s.finish();
 }
 
+// one device's part of plaid.gsea (kGsea, kernels_gsea.hip).  Every shard holds stat, weight and G and forms the observed
+// placements and scores itself (the same bits everywhere); the permutation blocks are shared out in whole blocks
+// (plaidhip_shard_bounds over the blocks) and walked slab by slab; the block partials meet on the host in block order and
+// shard 0 reduces them once, so every sharding has the one-shard bits.  One rendezvous.
+int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t g = c.g, nl = c.n, m = c.m, B = c.nperm;
+  const int32_t nblk = (B + PLAIDHIP_GSEA_PERM_BLOCK - 1) / PLAIDHIP_GSEA_PERM_BLOCK;
+  int64_t blo = 0, bhi = 0;
+  plaidhip_shard_bounds(nblk, ndev, k, &blo, &bhi);
+  const int64_t p_lo = blo * PLAIDHIP_GSEA_PERM_BLOCK, p_hi = std::min<int64_t>(B, bhi * PLAIDHIP_GSEA_PERM_BLOCK);
+  const size_t col = (size_t)g * nl, blk_doubles = (size_t)nl * 6 * m;
+  DevBuf dstat, dw, dR, dY, dQ, dWpos, dpos, dnan, dGp, dGi, dES, dpart, dslabY, dslabR, dP, dbad, dnull, dout, dall;
+  const int32_t slab = gsea_slab_perms(g);
+
+  // ---- upload, the observed placements and scores -------------------------------------------------------------------------
+  s.step([&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    PH_TRY(dstat.alloc(col * 8));
+    PH_TRY(dw.alloc(col * 8));
+    PH_TRY(dR.alloc(col * 8));
+    PH_TRY(dY.alloc(col * 8));
+    PH_TRY(dQ.alloc(col * 8));
+    PH_TRY(dWpos.alloc(col * 8));
+    PH_TRY(dpos.alloc(col * 4));
+    PH_TRY(dnan.alloc((size_t)nl * 4));
+    PH_TRY(dES.alloc((size_t)m * nl * 8));
+    PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
+    PH_TRY(upload_pipelined(ctx, dstat.as<char>(), (size_t)g * 8, reinterpret_cast<const char*>(c.X), (size_t)g * 8, nl, nullptr));
+    PH_TRY(upload_pipelined(ctx, dw.as<char>(), (size_t)g * 8, reinterpret_cast<const char*>(c.weight), (size_t)g * 8, nl,
+                            nullptr));
+    PH_HIP(hipMemcpyAsync(dnan.p, c.listnan.data(), (size_t)nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    PH_HIP(hipMemsetAsync(dWpos.p, 0, col * 8, ctx->stream));
+    PH_HIP(hipMemsetAsync(dpos.p, 0, col * 4, ctx->stream));
+    PH_TRY(launch_colranks_dense_f64(ctx, dstat.as<double>(), g, g, nl, PLAIDHIP_TIES_MIN, 0, 1.0, dR.as<double>(), g, nullptr));
+    PH_TRY(launch_sing_last_ranks(ctx, dR.as<double>(), g, g, nl, dY.as<double>(), dQ.as<double>()));
+    PH_TRY(launch_gsea_operands(ctx, dQ.as<double>(), dw.as<double>(), g, dnan.as<uint32_t>(), g, nl, dpos.as<int32_t>(),
+                                dWpos.as<double>()));
+    return launch_gsea_obs(ctx, c.gsea_weighted, dpos.as<int32_t>(), dWpos.as<double>(), dnan.as<uint32_t>(), g, nl,
+                           dGp.as<int32_t>(), dGi.as<int32_t>(), m, dES.as<double>());
+  });
+
+  // ---- this shard's blocks of the null, slab by slab ------------------------------------------------------------------------
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (p_hi <= p_lo) return PLAIDHIP_OK;
+    const int32_t smax = (int32_t)std::min<int64_t>(slab, p_hi - p_lo);
+    PH_TRY(dpart.alloc((size_t)(bhi - blo) * blk_doubles * 8));
+    PH_TRY(dP.alloc((size_t)g * smax * 4));
+    PH_TRY(dbad.alloc(8));
+    PH_HIP(hipMemsetAsync(dbad.p, 0, 8, ctx->stream));
+    if (c.perm == nullptr) {
+      PH_TRY(dslabY.alloc((size_t)g * smax * 8));
+      PH_TRY(dslabR.alloc((size_t)g * smax * 8));
+    }
+    if (c.null_out != nullptr) PH_TRY(dnull.alloc((size_t)m * smax * nl * 8));
+    for (int64_t b0 = p_lo; b0 < p_hi; b0 += slab) {
+      const int32_t nbs = (int32_t)std::min<int64_t>(slab, p_hi - b0);
+      if (c.perm == nullptr) {
+        PH_TRY(launch_gsea_placements(ctx, g, b0, nbs, c.seed, dslabY.as<double>(), dslabR.as<double>(), dP.as<int32_t>()));
+      } else {
+        PH_TRY(upload_pipelined(ctx, dP.as<char>(), (size_t)g * 4, reinterpret_cast<const char*>(c.perm + b0 * g), (size_t)g * 4,
+                                nbs, nullptr));
+        PH_TRY(launch_gsea_check_perm(ctx, dP.as<int32_t>(), g, nbs, (int32_t)b0, dbad.as<uint32_t>()));
+        uint32_t bad[2] = {0u, 0u};
+        PH_HIP(hipMemcpyAsync(bad, dbad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        PH_REQUIRE(bad[0] == 0u, "gsea: column %u of perm is no permutation of 0..%d", bad[1] - 1u, g - 1);
+      }
+      PH_TRY(launch_gsea_null(ctx, c.gsea_weighted, dP.as<int32_t>(), nbs, dWpos.as<double>(), dnan.as<uint32_t>(),
+                              dES.as<double>(), g, nl, dGp.as<int32_t>(), dGi.as<int32_t>(), m, dpart.as<double>(),
+                              (b0 - p_lo) / PLAIDHIP_GSEA_PERM_BLOCK, c.null_out != nullptr ? dnull.as<double>() : nullptr));
+      if (c.null_out != nullptr)
+        for (int32_t l = 0; l < nl; ++l)
+          PH_HIP(hipMemcpyAsync(c.null_out + ((int64_t)l * B + b0) * m, dnull.as<double>() + (size_t)l * nbs * m,
+                                (size_t)nbs * m * 8, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));   // (the slab's buffers are the next slab's)
+    }
+    if (ndev > 1) {
+      PH_HIP(hipMemcpyAsync(sh.gsea_part.data() + (size_t)blo * blk_doubles, dpart.p, (size_t)(bhi - blo) * blk_doubles * 8,
+                            hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PLAIDHIP_OK;
+  });
+  sh.rv.arrive_and_wait();
+
+  // ---- shard 0: the blocks in order, NES and pval; padj on the host ---------------------------------------------------------
+  if (k == 0)
+    s.step([&]() -> int {
+      const double* part = dpart.as<double>();
+      if (ndev > 1) {
+        PH_TRY(dall.alloc((size_t)nblk * blk_doubles * 8));
+        PH_HIP(hipMemcpyAsync(dall.p, sh.gsea_part.data(), (size_t)nblk * blk_doubles * 8, hipMemcpyHostToDevice, ctx->stream));
+        part = dall.as<double>();
+      }
+      PH_TRY(dout.alloc((size_t)m * 12 * nl * 8));
+      PH_TRY(launch_gsea_null_reduce(ctx, part, nblk, dES.as<double>(), dGp.as<int32_t>(), m, nl, dout.as<double>()));
+      PH_HIP(hipMemcpyAsync(c.out, dout.p, (size_t)m * 12 * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
+      PH_HIP(hipStreamSynchronize(ctx->stream));
+      std::vector<double> p, q;
+      std::vector<int32_t> at;
+      for (int32_t l = 0; l < nl; ++l) {   // Benjamini-Hochberg over the sets of the list that have a p-value
+        double* o = c.out + (size_t)l * 12 * m;
+        p.clear();
+        at.clear();
+        for (int32_t j = 0; j < m; ++j)
+          if (o[2 * (size_t)m + j] == o[2 * (size_t)m + j]) { p.push_back(o[2 * (size_t)m + j]); at.push_back(j); }
+        q.resize(p.size());
+        if (!p.empty()) p_adjust_fdr(p.data(), (int64_t)p.size(), q.data());
+        for (size_t e = 0; e < p.size(); ++e) o[3 * (size_t)m + at[e]] = q[e];
+      }
+      return PLAIDHIP_OK;
+    });
+  return s.finish();
+}
+
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
@@ -1803,7 +1922,10 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.pt_F.assign((size_t)even_ld(c.g) * 2 * C, 0.0);
     sh.row_sum.resize((size_t)ndev);
   }
+  if (c.method == kGsea && ndev > 1)
+    sh.gsea_part.assign((size_t)((c.nperm + PLAIDHIP_GSEA_PERM_BLOCK - 1) / PLAIDHIP_GSEA_PERM_BLOCK) * c.n * 6 * c.m, 0.0);
   auto worker = [&](int k) {
+    if (c.method == kGsea) return gsea_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
     return is_rank_sum(c.method) ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
@@ -2105,6 +2227,33 @@ int check_plaid_test_contrasts_call(Call& c) {
   return PLAIDHIP_OK;
 }
 
+// plaid.gsea; the order is part of the contract (include/plaidhip.h).  Finds whether any weight differs from 1 and the lists
+// that hold a NaN or an infinity
+int check_gsea_call(Call& c) {
+  PH_REQUIRE(c.nperm >= 1, "gsea: nperm = %d (at least 1)", c.nperm);
+  PH_REQUIRE(c.n >= 1, "gsea: %d ranked lists (at least 1)", c.n);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  if (c.g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("gsea: %d genes (at most %d)", c.g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  PH_REQUIRE(c.X != nullptr && c.weight != nullptr, "gsea: null stat / weight");
+  c.gsea_weighted = 0;
+  for (int64_t e = 0; e < (int64_t)c.g * c.n; ++e) {
+    const double w = c.weight[e];
+    PH_REQUIRE(std::isfinite(w) && w >= 0.0, "gsea: weight[%lld] = %g (weights are finite and >= 0)", (long long)e, w);
+    if (w != 1.0) c.gsea_weighted = 1;
+  }
+  c.listnan.assign((size_t)c.n, 0u);
+  for (int32_t l = 0; l < c.n; ++l)
+    for (int32_t i = 0; i < c.g; ++i)
+      if (!std::isfinite(c.X[(int64_t)l * c.g + i])) { c.listnan[(size_t)l] = 1u; break; }
+  if (c.m == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "gsea: null Gi");
+  PH_REQUIRE(c.out != nullptr, "gsea: null out");
+  return PLAIDHIP_OK;
+}
+
 std::mutex g_multi_mu;
 std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
 int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
@@ -2161,6 +2310,7 @@ int check_call(Call& c, int ndev, bool multi) {
   switch (c.method) {
     case kPlaidTest: return check_plaid_test_call(c);
     case kPlaidTestContrasts: return check_plaid_test_contrasts_call(c);
+    case kGsea: return check_gsea_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -2403,6 +2553,19 @@ int plaidhip_debug_aucell_exact_sharded_on_one_device(int device, int nshards, i
                                                       const int32_t* Gp, const int32_t* Gi, int32_t m, double auc_max_rank,
                                                       double* S_out) try {
   return dispatch(on_hook(device, nshards, fail_shard), aucell_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, auc_max_rank, S_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsea_multi(const int* devices, int ndev, const double* stat, const double* weight, int32_t g, int32_t c,
+                        const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
+                        double* out, double* null_out) try {
+  return dispatch(on_devices(devices, ndev), gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_gsea_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat, const double* weight,
+                                              int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                                              const int32_t* perm, int32_t nperm, uint64_t seed, double* out,
+                                              double* null_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard), gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 }  // extern "C"

@@ -279,6 +279,54 @@ def _ucell_exact_call(fn, head, X, Gp, Gi, Dp, Di, max_rank, w_neg, k_full, k_fu
     return {name: o for name, o in zip(UCELL_EXACT_OUTPUTS, outs) if o is not None}
 
 
+GSEA_KS_MAX_GENES = 131072   # PLAIDHIP_GSEA_KS_MAX_GENES
+GSEA_COLUMNS = ("ES", "NES", "pval", "padj", "nMoreExtreme", "size", "nGeEs", "nLeEs", "nGeZero", "nLeZero", "sumPos", "sumNeg")
+
+
+def check_gsea_args(stat, weight, perm, nperm):
+    """the checks of plaidhip_gsea that need no device, in its order: (stat, weight, perm or None, nperm) as the ABI takes
+    them.  stat / weight: g genes x c lists (a vector is one list); perm: g x nperm int32 placements or None."""
+    stat = _as_f64_fortran(stat)
+    if stat.ndim == 1:
+        stat = np.asfortranarray(stat.reshape(-1, 1))
+    weight = _as_f64_fortran(weight)
+    if weight.ndim == 1:
+        weight = np.asfortranarray(weight.reshape(-1, 1))
+    if stat.ndim != 2 or weight.shape != stat.shape:
+        raise ValueError("gsea: stat and weight must be genes x lists of one shape")
+    if perm is not None:
+        perm = np.asfortranarray(perm, dtype=np.int32)
+        if perm.ndim != 2 or perm.shape[0] != stat.shape[0]:
+            raise ValueError("gsea: perm must be genes x permutations")
+        nperm = perm.shape[1]
+    nperm = int(nperm)
+    if nperm < 1:
+        raise ValueError(f"gsea: nperm = {nperm} (at least 1)")
+    if stat.shape[1] < 1:
+        raise ValueError("gsea: 0 ranked lists (at least 1)")
+    if stat.shape[0] > GSEA_KS_MAX_GENES:
+        raise _lib.PlaidHipError(_lib.EUNSUPPORTED, f"gsea: {stat.shape[0]} genes (at most {GSEA_KS_MAX_GENES})")
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.isfinite(weight) & (weight >= 0.0))
+    if bad.any():
+        raise ValueError(f"gsea: weight[{int(np.flatnonzero(bad.ravel(order='F'))[0])}] is not finite and >= 0")
+    return stat, weight, perm, nperm
+
+
+def _gsea(fn, head, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False):
+    """plaidhip_gsea / _multi / the hook: sets x 12 x lists (GSEA_COLUMNS), and the sets x nperm x lists null scores with
+    null = True"""
+    stat, weight, perm, nperm = check_gsea_args(stat, weight, perm, nperm)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    g, c = stat.shape
+    m = len(Gp) - 1
+    out = np.full((m, 12, c), np.nan, dtype=np.float64, order="F")
+    nul = np.full((m, nperm, c), np.nan, dtype=np.float64, order="F") if null else None
+    check(fn(*head, _np_ptr(stat), _np_ptr(weight), g, c, _np_ptr(Gp), _np_ptr(Gi), m, None if perm is None else _np_ptr(perm),
+             nperm, int(seed) & (2**64 - 1), _np_ptr(out), None if nul is None else _np_ptr(nul)))
+    return (out, nul) if null else out
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -647,6 +695,18 @@ class Context:
         distinct row indices (never expanded), G aligned to X's rows"""
         return self._host("aucell_exact", X, Gp, Gi, float(auc_max_rank))
 
+    def gsea(self, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False):
+        """plaidhip_gsea: preranked GSEA of the columns of stat (genes x lists) with their weights; perm: genes x nperm
+        int32 placements, or None for the placements generated from `seed`.  Returns sets x 12 x lists (GSEA_COLUMNS); with
+        null = True also the sets x nperm x lists null scores."""
+        return _gsea(self.lib.plaidhip_gsea, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null)
+
+    def gsea_permutations(self, g: int, nperm: int, seed=1) -> np.ndarray:
+        """plaidhip_gsea_permutations: the genes x nperm int32 placements plaidhip_gsea generates from `seed`"""
+        P = np.empty((int(g), int(nperm)), dtype=np.int32, order="F")
+        check(self.lib.plaidhip_gsea_permutations(self.handle, int(g), int(nperm), int(seed) & (2**64 - 1), _np_ptr(P)))
+        return P
+
     def dev_truncated_ranks(self, X: int, ldx: int, g: int, n: int, mode, T: int, R_scratch: int, colnan: int, counts: int,
                             Wp: int, Wi: int, Wx: int, capacity: int):
         check(self.lib.plaidhip_dev_truncated_ranks_f64(self.handle, X, ldx, g, n, TRUNC_MODE[mode], int(T), R_scratch, colnan,
@@ -816,6 +876,11 @@ def plaid_test_contrasts_multi(X, Y, Gp, Gi, gsetX=None, tests=7, metap_method=0
     """plaid.test.contrasts (Context.plaid_test_contrasts / _csc) with the sample columns sharded over `devices`, as
     plaid_test_multi; sets x 6 x C, dense X the single-device result bit for bit"""
     return _plaid_test_contrasts(*_multi("plaid_test_contrasts", devices), X, Y, Gp, Gi, gsetX, tests, metap_method)
+
+
+def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, devices=1):
+    """plaid.gsea (Context.gsea) with the permutation blocks shared out over `devices`: the one-device bits"""
+    return _gsea(*_multi("gsea", devices), stat, weight, Gp, Gi, perm, nperm, seed, null)
 
 
 def multi_finalize():

@@ -475,6 +475,51 @@ plaid.test.contrasts <- function(X, Y, G, gsetX = NULL, tests = c("one", "two", 
 }
 
 
+## plaid.gsea(): preranked GSEA with a permutation null on the device -- what fgsea::fgsea(gmt, fc) gives the enrichment
+## experiments (experiments/compare-enrichment/enrichment-methods.R:28): ES, NES, pval, padj for a named vector of
+## statistics, or for every column of a genes x contrasts matrix.  include/plaidhip.h (plaidhip_gsea) pins the statistic
+## (fgseaSimple, scoreType = "std"); the weights abs(stats)^gseaParam are formed here.  perm: NULL (nperm placements
+## generated from seed) or a genes x nperm integer matrix whose columns are permutations of seq_len(genes) over the aligned
+## genes.  Returns a matrix (a vector of statistics) or a named list of matrices, rows ordered by sort.by.
+plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSize = NULL, seed = 1, perm = NULL,
+                       sort.by = "pval") {
+  single <- is.null(dim(stats))
+  if (single) stats <- matrix(stats, ncol = 1, dimnames = list(names(stats), "stat"))
+  stats <- as.matrix(stats); storage.mode(stats) <- "double"
+  if (is.list(G)) {
+    message("[plaid.gsea] converting gmt to sparse matrix...")
+    G <- gmt2mat(G)
+  }
+  if (length(gseaParam) != 1L || !is.finite(gseaParam) || gseaParam < 0) stop("plaid.gsea: gseaParam must be finite and >= 0")
+  gg <- intersect(rownames(G), rownames(stats))
+  stats <- stats[gg, , drop = FALSE]
+  G <- G[gg, , drop = FALSE]
+  size <- Matrix::colSums(G != 0)
+  if (is.null(maxSize)) maxSize <- length(gg) - 1L
+  G <- G[, size >= minSize & size <= maxSize, drop = FALSE]
+  pat <- .aligned_pattern(stats, G)
+  W <- abs(stats)^gseaParam
+  W[!is.finite(W)] <- 0
+  if (!is.null(perm)) {
+    perm <- as.matrix(perm)
+    if (nrow(perm) != nrow(stats)) stop("plaid.gsea: perm must have one row per aligned gene")
+    perm <- matrix(as.integer(perm) - 1L, nrow(perm), ncol(perm))
+  }
+  .session()
+  r <- .Call("R_plaidhip_gsea", .devices(), stats, W, pat$Gp, pat$Gi, perm, as.integer(nperm), as.numeric(seed %% 2^32),
+             as.numeric((seed %/% 2^32) %% 2^32), PACKAGE = "plaidhip")
+  dim(r) <- c(nrow(r), 12L, ncol(stats))
+  cols <- c("ES", "NES", "pval", "padj", "nMoreExtreme", "size")
+  out <- lapply(seq_len(ncol(stats)), function(l) {
+    res <- matrix(r[, 1:6, l], nrow = dim(r)[1], dimnames = list(colnames(G), cols))
+    if (sort.by %in% cols) res <- res[order(res[, sort.by]), , drop = FALSE]
+    res
+  })
+  names(out) <- colnames(stats)
+  if (single) out[[1]] else out
+}
+
+
 ## replaid.gsva(), R/plaid.R:338-363: the row transform ("z" or "ecdf"), the signed ranks, the power and
 ## plaid() run on the device in one call.
 replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {

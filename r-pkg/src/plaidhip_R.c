@@ -552,6 +552,27 @@ SEXP R_plaidhip_gsva_csc(SEXP Xp, SEXP Xi, SEXP Xx, SEXP g, SEXP Gp, SEXP Gi, SE
   return S;
 }
 
+/* plaid.gsea(): an m x 12c matrix, columns 12 l + 1 .. 12 l + 12 the columns of plaidhip_gsea for list l (the caller gives
+ * it dim m x 12 x c).  stat, weight: g x c doubles; perm: NULL (the placements generated from seed, two 32-bit halves in a
+ * double each) or a g x nperm integer matrix of 0-based placements; several devices: the _multi entry */
+SEXP R_plaidhip_gsea(SEXP devices, SEXP stat, SEXP weight, SEXP Gp, SEXP Gi, SEXP perm, SEXP nperm, SEXP seed_lo,
+                     SEXP seed_hi) {
+  const int g = Rf_nrows(stat), c = Rf_ncols(stat), m = LENGTH(Gp) - 1;
+  const int B = Rf_isNull(perm) ? Rf_asInteger(nperm) : Rf_ncols(perm);
+  const uint64_t seed = ((uint64_t)(uint32_t)Rf_asReal(seed_hi) << 32) | (uint64_t)(uint32_t)Rf_asReal(seed_lo);
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 12 * c));
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_gsea_multi(INTEGER(devices), LENGTH(devices), REAL(stat), REAL(weight), g, c, INTEGER(Gp), INTEGER(Gi), m,
+                             int_or_null(perm), B, seed, REAL(out), NULL);
+  else
+    rc = plaidhip_gsea(ctx(), REAL(stat), REAL(weight), g, c, INTEGER(Gp), INTEGER(Gi), m, int_or_null(perm), B, seed,
+                       REAL(out), NULL);
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(1);
+  return out;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -593,6 +614,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_plaid_test_multi", (DL_FUNC)&R_plaidhip_plaid_test_multi, 12},
     {"R_plaidhip_plaid_test_contrasts", (DL_FUNC)&R_plaidhip_plaid_test_contrasts, 12},
     {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
+    {"R_plaidhip_gsea", (DL_FUNC)&R_plaidhip_gsea, 9},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {

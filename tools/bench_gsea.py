@@ -1,0 +1,136 @@
+"""plaid.gsea (Context.gsea) at the enrichment experiments' shape, one MI355X: 20,000 genes, 5,000 sets of synth's size
+distribution, 1,000 permutations, 1 and 8 ranked lists, unweighted (weight 1) and weighted (|N(0, 1)|).  The yardstick is
+the walk kernel replaid.ssgsea.exact(single = FALSE) already has: gsea_ks_kernel at 20,000 genes x 1,000 columns x the same
+sets, alpha 0 beside the unweighted cases and 0.25 beside the weighted ones -- the same number of (set, walk) pairs as one
+list of the null.  Each case runs in a fresh process, one warm-up call first.
+
+    python3 tools/bench_gsea.py [--reps 3] [--cases c1_unweighted,...]      host call times, one JSON line
+    python3 tools/bench_gsea.py --profile DIR [--cases ...]                 the kernel times as well, one JSON line
+    python3 tools/bench_gsea.py --case c8_weighted --reps 1                 one case in this process: what the profiler wraps
+
+--profile runs every case a second time, in a run of its own, as
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR/CASE -- python3 tools/bench_gsea.py --case CASE --reps 1
+reads the case's kernel (gsea_null_kernel, or gsea_ks_kernel for the yardstick) from the *kernel_stats.csv of that run and
+reports kernel_ms, the kernel's time per host call (all of its launches, over the warm-up and the one timed call), and
+pairs_per_s = sets x permutations x lists over that time.  The stats files stay in DIR."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+GENES, SETS, PERMS = 20000, 5000, 1000
+CASES = {
+    "c1_unweighted": dict(lists=1, weighted=False),
+    "c8_unweighted": dict(lists=8, weighted=False),
+    "c1_weighted": dict(lists=1, weighted=True),
+    "c8_weighted": dict(lists=8, weighted=True),
+    "ks_alpha0": dict(ks=True, alpha=0.0),          # the yardstick: gsea_ks_kernel, 1,000 columns
+    "ks_alpha025": dict(ks=True, alpha=0.25),
+}
+
+
+def _median_ms(fn, reps):
+    fn()                                   # warm-up: code objects, buffers, the result's pages
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def run_case(name, reps, genes=GENES, sets=SETS, perms=PERMS):
+    import plaid_amd
+    from plaid_amd import synth
+    p = CASES[name]
+    Gp, Gi = synth.geneset_csc(genes, sets)
+    rng = np.random.default_rng(17)
+    ctx = plaid_amd.Context(0)
+    try:
+        if p.get("ks"):
+            X = synth.dense_columns(genes, 0, perms)
+            ms = _median_ms(lambda: ctx.ssgsea_exact(X, Gp, Gi, p["alpha"], True, False, single=False), reps)
+            pairs = sets * perms
+        else:
+            stat = rng.normal(size=(genes, p["lists"]))
+            w = np.abs(rng.normal(size=stat.shape)) if p["weighted"] else np.ones_like(stat)
+            ms = _median_ms(lambda: ctx.gsea(stat, w, Gp, Gi, nperm=perms, seed=1), reps)
+            pairs = sets * perms * p["lists"]
+    finally:
+        ctx.close()
+    return {"case": name, **p, "genes": genes, "sets": sets, "perms": perms, "reps": reps, "host_ms": round(ms, 2), "pairs": pairs,
+            "host_pairs_per_s": round(pairs / (ms * 1e-3), 1)}
+
+
+def _kernel_of(name):
+    return "gsea_ks_kernel" if CASES[name].get("ks") else "gsea_null_kernel"
+
+
+def profile_case(name, outdir, genes, sets, perms, limit_s):
+    """the case under rocprofv3 --kernel-trace --stats in a process of its own; its kernel's row of the stats file"""
+    import csv
+    import glob
+    d = os.path.join(outdir, name)
+    os.makedirs(d, exist_ok=True)
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
+           "--case", name, "--reps", "1", "--genes", str(genes), "--sets", str(sets), "--perms", str(perms)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit_s)
+    if r.returncode != 0:
+        return {"error": (r.stderr or r.stdout)[-500:], "returncode": r.returncode}
+    files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
+    if not files:
+        return {"error": f"no *kernel_stats.csv under {d}", "returncode": 0}
+    calls = total_ns = 0
+    with open(files[0], newline="") as fh:
+        for row in csv.DictReader(fh):
+            if _kernel_of(name) in row["Name"]:
+                calls += int(row["Calls"])
+                total_ns += int(row["TotalDurationNs"])
+    if calls == 0:
+        return {"error": f"{_kernel_of(name)} is not in {files[0]}", "returncode": 0}
+    host_calls = 2                                    # the warm-up and --reps 1
+    ms = total_ns * 1e-6 / host_calls
+    pairs = sets * perms * CASES[name].get("lists", 1)
+    return {"kernel": _kernel_of(name), "kernel_launches": calls, "kernel_ms": round(ms, 3), "pairs_per_s": round(pairs / (ms * 1e-3), 1),
+            "stats_file": os.path.relpath(files[0], outdir)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--case", default=None, help="run one case in this process and print its JSON")
+    ap.add_argument("--genes", type=int, default=GENES)
+    ap.add_argument("--sets", type=int, default=SETS)
+    ap.add_argument("--perms", type=int, default=PERMS)
+    ap.add_argument("--profile", default=None, metavar="DIR", help="also run every case under rocprofv3, stats files into DIR")
+    ap.add_argument("--limit", type=int, default=300, help="seconds a profiled case may take")
+    a = ap.parse_args()
+    if a.case is not None:
+        print(json.dumps(run_case(a.case, a.reps, a.genes, a.sets, a.perms)))
+        return
+    out = []
+    for name in a.cases.split(","):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name, "--reps", str(a.reps), "--genes", str(a.genes),
+                            "--sets", str(a.sets), "--perms", str(a.perms)], capture_output=True, text=True, timeout=a.limit)
+        if r.returncode != 0:
+            out.append({"case": name, "error": (r.stderr or r.stdout)[-500:], "returncode": r.returncode})
+            break                          # a failed case ends the run: nothing more is started on the device
+        out.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        if a.profile is not None:
+            k = profile_case(name, a.profile, a.genes, a.sets, a.perms, a.limit)
+            out[-1].update(k)
+            if "error" in k:
+                break
+    print(json.dumps({"tool": "bench_gsea", "cases": out}))
+
+
+if __name__ == "__main__":
+    main()
