@@ -884,14 +884,49 @@ int plaidhip_contrast_tile(void);   /* PLAIDHIP_CONTRAST_TILE of the built libra
  * g > PLAIDHIP_GSEA_KS_MAX_GENES (PLAIDHIP_EUNSUPPORTED), a bad weight, then (on the device) a bad perm column.
  * plaidhip_gsea_multi shares the permutation blocks out over the devices in whole blocks; every device holds stat, weight
  * and G; the block partials are chained in block order and reduced once: every sharding returns the one-device bits.
- * Not offered: scoreType "pos" / "neg", fgsea's multilevel p-values (the smallest pval is 1 / (nperm + 1)), leading edges. */
+ * Score types (plaidhip_gsea_scored; fgsea's scoreType, AS RECALLED like the rest): PLAIDHIP_GSEA_STD is everything above,
+ * unchanged.  With maxP and minP as defined above, for the observed score and for every null score alike:
+ *                     std (above)                                           pos                        neg
+ *     ES              maxP > -minP ? maxP : (maxP < -minP ? minP : 0.0)     maxP                       minP
+ *     NES             ES > 0 ? ES/(sumPos/nGeZero)                          ES/(sumPos/nGeZero)        ES/fabs(sumNeg/nLeZero)
+ *                            : ES/fabs(sumNeg/nLeZero)
+ *     pval            min((1+nLeEs)/(1+nLeZero), (1+nGeEs)/(1+nGeZero))     (1+nGeEs)/(1+nGeZero)      (1+nLeEs)/(1+nLeZero)
+ *     nMoreExtreme    ES > 0 ? nGeEs : nLeEs                                nGeEs                      nLeEs
+ * The six partials, their block order and the IEEE division rule are the same for all three types, and so are the NaN rules
+ * (k = 0, k = N, a list with a NaN or an infinity).
+ * Leading edge of (set j, list l), defined on the observed placement.  Let t_top be the smallest t with after_t == maxP
+ * and t_bot the smallest t with before_t == minP: fp64 equality on the values the walk itself forms, the first occurrence
+ * as R's which.max / which.min give it.
+ *     top branch:     the members t = 1 .. t_top in walk order (decreasing stat); length t_top
+ *     bottom branch:  the members t = k .. t_bot, from the end of the list backwards; length k - t_bot + 1
+ *     std takes the top branch if maxP > -minP, the bottom branch if maxP < -minP, and is empty (length 0) if they tie;
+ *     pos always takes the top branch and neg always the bottom branch, also where ES is 0.
+ *     A NaN pair (k = 0, k = N, a NaN list) has length 0.
+ * le_len is m x c int32 and le_idx is nnz x c int32, nnz = Gp[m]: the edge of (j, l) is le_idx[l nnz + Gp[j] + 0 .. len-1],
+ * len = le_len[l m + j], row indices into stat (the numbering of Gi) in the order above; the rest of the set's segment is
+ * -1.  An edge never exceeds k, so a set's own segment of G always holds it.  le_len and le_idx are passed both or neither.
+ * plaidhip_gsea / plaidhip_gsea_multi are plaidhip_gsea_scored / _multi with PLAIDHIP_GSEA_STD and no edge buffers.  The
+ * argument errors of plaidhip_gsea_scored, in this order: score_type outside 0..2, exactly one of le_len / le_idx null,
+ * then those above.  Under plaidhip_gsea_scored_multi the edges are formed once, on the first device, after the reduction;
+ * every sharding returns the one-device bits of out, null_out, le_len and le_idx.
+ * Not offered: fgsea's multilevel p-values (the smallest pval is 1 / (nperm + 1)). */
 #define PLAIDHIP_GSEA_PERM_BLOCK 64
+#define PLAIDHIP_GSEA_STD 0
+#define PLAIDHIP_GSEA_POS 1
+#define PLAIDHIP_GSEA_NEG 2
 int plaidhip_gsea(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
                   const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out,
                   double* null_out);
 int plaidhip_gsea_multi(const int* devices, int ndev, const double* stat, const double* weight, int32_t g, int32_t c,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
                         double* out, double* null_out);
+int plaidhip_gsea_scored(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
+                         const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, int score_type,
+                         double* out, double* null_out, int32_t* le_len, int32_t* le_idx);
+int plaidhip_gsea_scored_multi(const int* devices, int ndev, const double* stat, const double* weight, int32_t g, int32_t c,
+                               const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm,
+                               uint64_t seed, int score_type, double* out, double* null_out, int32_t* le_len,
+                               int32_t* le_idx);
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out);
 
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------

@@ -143,6 +143,9 @@ SIGNATURES = {
     "plaidhip_contrast_tile": [],
     "plaidhip_gsea": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _vp, _vp],
     "plaidhip_gsea_multi": [_vp, _int, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _vp, _vp],
+    "plaidhip_gsea_scored": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _int, _vp, _vp, _vp, _vp],
+    "plaidhip_gsea_scored_multi": [_vp, _int, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _int, _vp, _vp, _vp,
+                                   _vp],
     "plaidhip_gsea_permutations": [_vp, _i32, _i32, C.c_uint64, _vp],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],
     # host-only GMT text path (gmt.cpp)

@@ -569,9 +569,12 @@ def plaid_test_contrasts(X, Y, G, gsetX=None, tests=("one", "two", "lm"), metap_
 _GSEA_NAMES = ["ES", "NES", "pval", "padj", "nMoreExtreme", "size"]
 
 
+_GSEA_SCORE_TYPES = ("std", "pos", "neg")
+
+
 def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=1, perm=None, sort_by="pval",
-               ctx: Context | None = None):
-    """plaid.gsea(): preranked GSEA (fgsea's fgseaSimple, scoreType "std", as pinned in include/plaidhip.h) of a named
+               ctx: Context | None = None, scoreType="std", leadingEdge=False):
+    """plaid.gsea(): preranked GSEA (fgsea's fgseaSimple as pinned in include/plaidhip.h) of a named
     vector of statistics, or of every column of a genes x contrasts NamedMatrix, against the sets of G (a gmt or a
     membership matrix), with a permutation null of `nperm` placements generated on the device from `seed` (or the caller's
     `perm`, genes x permutations int32 over the aligned genes).  Genes are aligned by name as plaid.test aligns them; the
@@ -579,7 +582,12 @@ def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=
     aligned genes - 1) aligned members are dropped.  Returns one NamedMatrix (sets x [ES, NES, pval, padj, nMoreExtreme,
     size]) ordered by `sort_by` when stats is a named vector (a dict or a pandas Series, gene -> statistic); for a
     NamedMatrix, of one column or of many, a dict, column name -> NamedMatrix, in the columns' order.  The default seed is
-    plaid.gsea's in the R package, so the same call gives the same table in both."""
+    plaid.gsea's in the R package, so the same call gives the same table in both.
+    scoreType "pos" / "neg" scores one side of the walk (for a statistic of one sign, such as |logFC|, F or -log p).
+    leadingEdge = True returns (table, edges) wherever a table is returned: edges is a list, one entry per table row in
+    the table's order, of the gene names that drive the set's score, in walk order."""
+    if scoreType not in _GSEA_SCORE_TYPES:
+        raise ValueError(f"plaid.gsea: scoreType must be one of {list(_GSEA_SCORE_TYPES)} (got {scoreType!r})")
     if isinstance(stats, dict):
         stats = NamedMatrix(np.array(list(stats.values()), dtype=np.float64), list(stats.keys()), ["stat"])
         single = True
@@ -612,12 +620,19 @@ def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=
         W = np.ones_like(Xs) if gp == 0.0 else (np.abs(Xs) if gp == 1.0 else np.abs(Xs) ** gp)
     W = np.where(np.isfinite(W), W, 0.0)   # (a list with a NaN or an infinity is NaN by the statistic's own rule)
     ctx = ctx or default_context()
-    out = ctx.gsea(Xs, W, Gp, Gi, perm=perm, nperm=nperm, seed=seed)
+    out = ctx.gsea(Xs, W, Gp, Gi, perm=perm, nperm=nperm, seed=seed, score_type=scoreType, leading_edge=bool(leadingEdge))
+    if leadingEdge:
+        out, le_len, le_idx = out
+        posx = _first_pos(stats.rownames)
+        genes = [nm for nm in dict.fromkeys(as_named(G).rownames) if nm in posx]     # the aligned rows, as Gi numbers them
     res = {}
     for l, nm in enumerate(stats.colnames):
         tab, names = out[:, :6, l], list(rn)
+        o = np.arange(len(names))
         if sort_by in _GSEA_NAMES:
             o = np.argsort(tab[:, _GSEA_NAMES.index(sort_by)], kind="stable")       # order(): NaN last
             tab, names = tab[o, :], [names[k] for k in o]
         res[nm] = NamedMatrix(tab, names, _GSEA_NAMES)
+        if leadingEdge:
+            res[nm] = (res[nm], [[genes[r] for r in le_idx[Gp[j]:Gp[j] + le_len[j, l], l]] for j in o])
     return res[stats.colnames[0]] if single and len(res) == 1 else res

@@ -1184,6 +1184,14 @@ int plaidhip_gsea(plaidhip_ctx* ctx, const double* stat, const double* weight, i
   return dispatch(on_context(ctx), gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out));
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.gsea with a score type and, when asked for, the leading edges: the same Call
+int plaidhip_gsea_scored(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
+                         const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, int score_type,
+                         double* out, double* null_out, int32_t* le_len, int32_t* le_idx) try {
+  return dispatch(on_context(ctx),
+                  gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
 // the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out) try {
   PH_REQUIRE(g >= 1 && nperm >= 1, "gsea_permutations: bad dims g=%d nperm=%d", g, nperm);

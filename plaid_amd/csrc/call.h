@@ -73,6 +73,9 @@ struct Call : Operands {
   int32_t nperm = 0;
   uint64_t seed = 0;
   double* null_out = nullptr;
+  int score_type = PLAIDHIP_GSEA_STD;   // the choice between the walk's extremes
+  int32_t* le_len = nullptr;            // the leading edges (both null: none): m x n lengths,
+  int32_t* le_idx = nullptr;            // Gp[m] x n rows of stat, a set's edge in its own segment of G
   int gsea_weighted = 0;
   std::vector<uint32_t> listnan;
 };
@@ -229,9 +232,10 @@ inline Call aucell_exact_call(const Operands& x, double auc_max_rank, double* S_
   c.max_rank = auc_max_rank;
   return c;
 }
-// fgseaSimple(scoreType = "std") as pinned in include/plaidhip.h: plaidhip_gsea
+// fgseaSimple as pinned in include/plaidhip.h: plaidhip_gsea (std, no edges) and plaidhip_gsea_scored
 inline Call gsea_call(const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
-                      int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out, double* null_out) {
+                      int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out, double* null_out,
+                      int score_type = PLAIDHIP_GSEA_STD, int32_t* le_len = nullptr, int32_t* le_idx = nullptr) {
   Call k = make_call(kGsea, {nullptr, nullptr, stat, g, c, Gp, Gi, m}, nullptr);
   k.weight = weight;
   k.perm = perm;
@@ -239,6 +243,9 @@ inline Call gsea_call(const double* stat, const double* weight, int32_t g, int32
   k.seed = seed;
   k.out = out;
   k.null_out = null_out;
+  k.score_type = score_type;
+  k.le_len = le_len;
+  k.le_idx = le_idx;
   return k;
 }
 

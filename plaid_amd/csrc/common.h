@@ -569,17 +569,23 @@ inline int32_t gsea_slab_perms(int32_t g) {
 }
 // bad[0] |= 1 and bad[1] = max(bad[1], col0 + column + 1) for every column of P (g x nb) that is no permutation of 0..g-1
 int launch_gsea_check_perm(plaidhip_ctx* ctx, const int32_t* P, int32_t g, int32_t nb, int32_t col0, uint32_t* bad);
-// ES (c x m) <- the observed scores; weighted == 0: every weight is 1 (Wpos is not read)
-int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, const int32_t* pos_obs, const double* Wpos, const uint32_t* listnan,
-                    int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* ES);
+// ES (c x m) <- the observed scores; weighted == 0: every weight is 1 (Wpos is not read); score_type: PLAIDHIP_GSEA_STD /
+// _POS / _NEG, here and below
+int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* pos_obs, const double* Wpos,
+                    const uint32_t* listnan, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* ES);
+// the leading edges on the observed placements: le_len (c x m), le_idx (c x Gp[m]; the segment of (j, l) at l Gp[m] + Gp[j],
+// -1 past the edge)
+int launch_gsea_edges(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* pos_obs, const double* Wpos,
+                      const uint32_t* listnan, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                      int32_t* le_len, int32_t* le_idx);
 // the null walks of the nbs placements in P (whole blocks of 64 but the call's last): their block partials into
 // part[blk_at0 ..][c][6][m], the scores into null_out ([c][nbs][m]) when it is not null
-int launch_gsea_null(plaidhip_ctx* ctx, int weighted, const int32_t* P, int32_t nbs, const double* Wpos, const uint32_t* listnan,
-                     const double* ES, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* part,
-                     int64_t blk_at0, double* null_out);
+int launch_gsea_null(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* P, int32_t nbs, const double* Wpos,
+                     const uint32_t* listnan, const double* ES, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
+                     int32_t m, double* part, int64_t blk_at0, double* null_out);
 // out (m x 12 x c; padj left NaN) from all nblk blocks of partials, added in block order
 int launch_gsea_null_reduce(plaidhip_ctx* ctx, const double* part, int32_t nblk, const double* ES, const int32_t* Gp, int32_t m,
-                            int32_t c, double* out);
+                            int32_t c, int score_type, double* out);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 int launch_col_medians(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n,

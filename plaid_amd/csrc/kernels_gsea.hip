@@ -13,6 +13,10 @@
 // The 64 null scores stay in LDS; one thread per list then forms the block's six partials against the observed score,
 // sequentially in b.  gsea_null_reduce_kernel adds the blocks in order.
 //
+// The score type (std / pos / neg: which of the walk's two extremes is the score) is a template parameter of the walk and
+// of the two kernels above, and an argument of the reduction.  gsea_edge_kernel walks the observed placement once more with
+// the place of each extreme kept, and writes the leading edges.
+//
 // This file is compiled with fp contraction off (the pragma below): every product, quotient and difference of the pinned
 // form is its own IEEE operation.
 #include <algorithm>
@@ -142,14 +146,27 @@ __device__ __forceinline__ double gn_total_weight(const unsigned long long* bm, 
   return B;
 }
 
-// ES of the set whose bits are in the map: max(after), min(before) over the members, the pinned choice between them
-template <bool WEIGHTED>
+// where the walk met its extremes (the leading edge): t_top the smallest t with after_t == maxP, t_bot the smallest t with
+// before_t == minP (both 1-based), and the members the map holds
+struct GnExtremes {
+  double maxP, minP;
+  uint32_t t_top, t_bot, members;
+};
+
+// ES of the set whose bits are in the map: max(after), min(before) over the members, the choice between them that the score
+// type ST pins (PLAIDHIP_GSEA_STD / _POS / _NEG; launch-uniform, a template parameter so that an instantiation carries the
+// extreme it needs and no other).  EDGE: the walk also carries the t of each extreme -- (value, t) pairs, the smaller t on
+// equal values -- leaves every word's exclusive member count in `prefix` (LDS, beside the map) and returns the extremes in
+// *ex.  The values are formed by the same operations either way, so maxP / minP of an EDGE walk have the bits behind ES.
+template <bool WEIGHTED, int ST, bool EDGE = false>
 __device__ __forceinline__ double gn_walk(unsigned long long* bm, int32_t nw64, const double* __restrict__ wp, double B,
-                                          int32_t N, int32_t k, bool clear, int lane) {
+                                          int32_t N, int32_t k, bool clear, int lane, uint32_t* prefix = nullptr,
+                                          GnExtremes* ex = nullptr) {
   const double dmiss = (double)(N - k);
   uint32_t tbase = 0u;     // members in the words already walked
   double cwbase = 0.0;     // their weight
   double mxp = -INFINITY, mnp = INFINITY;
+  uint32_t tmx = 0xffffffffu, tmn = 0xffffffffu;   // (EDGE) a lane's t only grows, so a strict update keeps its first
   for (int32_t w0 = 0; w0 < nw64; w0 += 64) {
     unsigned long long word = bm[w0 + lane];
     if (__ballot(word != 0ull) == 0ull) continue;
@@ -158,6 +175,7 @@ __device__ __forceinline__ double gn_walk(unsigned long long* bm, int32_t nw64, 
     const uint32_t incl = wave_incl_scan_u32(cnt);
     uint32_t t = tbase + incl - cnt;
     tbase += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if constexpr (EDGE) prefix[w0 + lane] = t;
     const int32_t pos0 = (w0 + lane) * 64;   // position - 1 of the word's bit 0
     double cw = 0.0;
     if (WEIGHTED) {
@@ -181,31 +199,68 @@ __device__ __forceinline__ double gn_walk(unsigned long long* bm, int32_t nw64, 
       const double miss = (double)(pos - (int32_t)t) / dmiss;
       const double before = cwprev / B - miss;
       const double after = cwt / B - miss;
-      mnp = before < mnp ? before : mnp;
-      mxp = after > mxp ? after : mxp;
+      if constexpr (EDGE) {
+        if (before < mnp) { mnp = before; tmn = t; }
+        if (after > mxp) { mxp = after; tmx = t; }
+      } else {
+        mnp = before < mnp ? before : mnp;
+        mxp = after > mxp ? after : mxp;
+      }
     }
   }
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double a = __shfl_xor(mxp, o), b = __shfl_xor(mnp, o);
-    mxp = a > mxp ? a : mxp;
-    mnp = b < mnp ? b : mnp;
+  if constexpr (EDGE) {
+    // lanes own different words and the outer loop different chunks of 64 words, so equal values can sit in any two
+    // lanes: the tie is settled here, by t, and every lane ends with the same pair
+    for (int o = 32; o >= 1; o >>= 1) {
+      const double a = __shfl_xor(mxp, o), b = __shfl_xor(mnp, o);
+      const uint32_t ta = (uint32_t)__shfl_xor((int)tmx, o), tb = (uint32_t)__shfl_xor((int)tmn, o);
+      if (a > mxp || (a == mxp && ta < tmx)) { mxp = a; tmx = ta; }
+      if (b < mnp || (b == mnp && tb < tmn)) { mnp = b; tmn = tb; }
+    }
+    ex->maxP = mxp;
+    ex->minP = mnp;
+    ex->t_top = tmx;
+    ex->t_bot = tmn;
+    ex->members = tbase;
+  } else {
+    for (int o = 32; o >= 1; o >>= 1) {   // (an extreme the score type does not read is dropped by the compiler)
+      const double a = __shfl_xor(mxp, o), b = __shfl_xor(mnp, o);
+      mxp = a > mxp ? a : mxp;
+      mnp = b < mnp ? b : mnp;
+    }
   }
+  if (ST == PLAIDHIP_GSEA_POS) return mxp;
+  if (ST == PLAIDHIP_GSEA_NEG) return mnp;
   return mxp > -mnp ? mxp : (mxp < -mnp ? mnp : 0.0);
 }
 
 // the score of the set in the map under one list's weights; B == 0: the unweighted walk
-template <bool WEIGHTED>
+template <bool WEIGHTED, int ST>
 __device__ __forceinline__ double gn_score(unsigned long long* bm, int32_t nw64, const double* __restrict__ wp, int32_t N,
                                            int32_t k, bool clear, int lane) {
   if (WEIGHTED) {
     const double B = gn_total_weight(bm, nw64, wp, lane);
-    if (B != 0.0) return gn_walk<true>(bm, nw64, wp, B, N, k, clear, lane);
+    if (B != 0.0) return gn_walk<true, ST>(bm, nw64, wp, B, N, k, clear, lane);
   }
-  return gn_walk<false>(bm, nw64, wp, (double)k, N, k, clear, lane);
+  return gn_walk<false, ST>(bm, nw64, wp, (double)k, N, k, clear, lane);
+}
+
+// the same choice of walk with the extremes' places kept (the map stays set)
+template <bool WEIGHTED>
+__device__ __forceinline__ void gn_extremes(unsigned long long* bm, int32_t nw64, const double* __restrict__ wp, int32_t N,
+                                            int32_t k, int lane, uint32_t* prefix, GnExtremes* ex) {
+  if (WEIGHTED) {
+    const double B = gn_total_weight(bm, nw64, wp, lane);
+    if (B != 0.0) {
+      gn_walk<true, PLAIDHIP_GSEA_STD, true>(bm, nw64, wp, B, N, k, false, lane, prefix, ex);
+      return;
+    }
+  }
+  gn_walk<false, PLAIDHIP_GSEA_STD, true>(bm, nw64, wp, (double)k, N, k, false, lane, prefix, ex);
 }
 
 // ES[l m + j] of every (set j, list l): one wavefront per pair, the placement pos_obs of the list
-template <bool WEIGHTED>
+template <bool WEIGHTED, int ST>
 __global__ void __launch_bounds__(64 * kGnWaves)
 gsea_obs_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__ Wpos, const uint32_t* __restrict__ listnan,
                 int32_t N, int32_t c, const int32_t* __restrict__ Gp, const int32_t* __restrict__ Gi, int32_t m,
@@ -226,8 +281,75 @@ gsea_obs_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__ 
     }
     gn_set_bits(reinterpret_cast<uint32_t*>(bm), pos_obs + (int64_t)l * N, Gi, p0, k, N, lane);
     gn_wave_sync();
-    const double es = gn_score<WEIGHTED>(bm, nw64, Wpos + (int64_t)l * N, N, k, true, lane);
+    const double es = gn_score<WEIGHTED, ST>(bm, nw64, Wpos + (int64_t)l * N, N, k, true, lane);
     if (lane == 0) ES[e] = es;
+    gn_wave_sync();   // the cleared words before the next pair's bits
+  }
+}
+
+// The leading edge of every (set j, list l) on the observed placement: one wavefront per pair, the map of gsea_obs_kernel
+// and, beside it in LDS, 4 bytes per word for the words' exclusive member counts.  The walk keeps where maxP and minP were
+// first met; the score type picks the branch (std: by the sign rule of ES, none on a tie).  Then every member finds its own
+// walk index t from its position p -- prefix[p >> 6] + the word's bits below p -- and, if it is in the edge, writes its row
+// to slot t - 1 (top branch: walk order) or members - t (bottom branch: from the end of the list backwards).  Each slot of
+// the set's segment is written by exactly one lane: the edge's by its member, the rest (-1) by the fill.
+// le_len: [c][m]; le_idx: [c][nnz], nnz = Gp[m], the segment of (j, l) at l nnz + Gp[j].
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(64 * kGnWaves)
+gsea_edge_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__ Wpos, const uint32_t* __restrict__ listnan,
+                 int32_t N, int32_t c, const int32_t* __restrict__ Gp, const int32_t* __restrict__ Gi, int32_t m,
+                 int score_type, int32_t* __restrict__ le_len, int32_t* __restrict__ le_idx, int32_t nw64) {
+  extern __shared__ unsigned long long gn_map[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long* bm = gn_map + (size_t)wave * nw64;
+  uint32_t* prefix = reinterpret_cast<uint32_t*>(gn_map + (size_t)kGnWaves * nw64) + (size_t)wave * nw64;
+  for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
+  gn_wave_sync();
+  const int32_t nnz = Gp[m];
+  const int64_t pairs = (int64_t)m * c;
+  for (int64_t e = (int64_t)blockIdx.x * kGnWaves + wave; e < pairs; e += (int64_t)gridDim.x * kGnWaves) {
+    const int32_t l = (int32_t)(e / m), j = (int32_t)(e - (int64_t)l * m);
+    const int32_t p0 = Gp[j], k = Gp[j + 1] - p0;
+    if (k <= 0 || p0 < 0 || k > nnz - p0) {   // no segment to write (the second and third: a pattern that is none)
+      if (lane == 0) le_len[e] = 0;
+      continue;
+    }
+    int32_t* seg = le_idx + (int64_t)l * nnz + p0;
+    if (k >= N || listnan[l] != 0u) {
+      for (int32_t i = lane; i < k; i += 64) seg[i] = -1;
+      if (lane == 0) le_len[e] = 0;
+      continue;
+    }
+    const int32_t* pos = pos_obs + (int64_t)l * N;
+    gn_set_bits(reinterpret_cast<uint32_t*>(bm), pos, Gi, p0, k, N, lane);
+    gn_wave_sync();
+    GnExtremes ex;
+    gn_extremes<WEIGHTED>(bm, nw64, Wpos + (int64_t)l * N, N, k, lane, prefix, &ex);
+    gn_wave_sync();   // the words' counts before other lanes read them
+    const bool top = score_type == PLAIDHIP_GSEA_POS || (score_type == PLAIDHIP_GSEA_STD && ex.maxP > -ex.minP);
+    const bool bot = score_type == PLAIDHIP_GSEA_NEG || (score_type == PLAIDHIP_GSEA_STD && ex.maxP < -ex.minP);
+    const uint32_t kk = ex.members;   // k for a set of distinct rows in range; never more
+    uint32_t len = top ? ex.t_top : (bot ? kk - ex.t_bot + 1u : 0u);
+    if (kk == 0u || kk > (uint32_t)k || len > kk) len = 0u;
+    if (len != 0u) {
+      for (int32_t i = lane; i < k; i += 64) {
+        const int32_t row = Gi[p0 + i];
+        if ((uint32_t)row >= (uint32_t)N) continue;
+        const int32_t p = pos[row];
+        if ((uint32_t)p >= (uint32_t)N) continue;
+        const unsigned long long word = bm[p >> 6];
+        const uint32_t t = prefix[p >> 6] + (uint32_t)__popcll(word & ((1ull << (p & 63)) - 1ull)) + 1u;
+        if (top) {
+          if (t <= ex.t_top) seg[t - 1u] = row;
+        } else if (t >= ex.t_bot && t <= kk) {
+          seg[kk - t] = row;
+        }
+      }
+    }
+    for (int32_t i = (int32_t)len + lane; i < k; i += 64) seg[i] = -1;
+    if (lane == 0) le_len[e] = (int32_t)len;
+    gn_wave_sync();   // every lane has read the map
+    for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
     gn_wave_sync();   // the cleared words before the next pair's bits
   }
 }
@@ -235,7 +357,7 @@ gsea_obs_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__ 
 // P: g x nbs placements of this launch (the permutations bglob0 .. bglob0 + nbs - 1 of Btot; bglob0 a multiple of 64).
 // part: [block][c][6][m] from block blk_at0 of the buffer on; null_out (nullable): [c][nbs][m], this launch's columns.
 // Tasks are ordered set-first inside a block of permutations, so the workgroups in flight share its 64 columns of P in L2.
-template <bool WEIGHTED>
+template <bool WEIGHTED, int ST>
 __global__ void __launch_bounds__(64 * kGnWaves)
 gsea_null_kernel(const int32_t* __restrict__ P, int32_t nbs, const double* __restrict__ Wpos,
                  const uint32_t* __restrict__ listnan, const double* __restrict__ ES, int32_t N, int32_t c,
@@ -273,7 +395,7 @@ gsea_null_kernel(const int32_t* __restrict__ P, int32_t nbs, const double* __res
         const bool last = li == nwalk - 1;
         double es = nan;
         if (valid && (!WEIGHTED || listnan[l] == 0u)) {
-          es = gn_score<WEIGHTED>(bm, nw64, WEIGHTED ? Wpos + (int64_t)l * N : nullptr, N, k, last, lane);
+          es = gn_score<WEIGHTED, ST>(bm, nw64, WEIGHTED ? Wpos + (int64_t)l * N : nullptr, N, k, last, lane);
         } else if (valid && last) {
           for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
         }
@@ -321,7 +443,7 @@ gsea_null_kernel(const int32_t* __restrict__ P, int32_t nbs, const double* __res
 // the blocks in order; NES, pval, nMoreExtreme.  out: m x 12 x c (column 3, padj, is the host's)
 __global__ void __launch_bounds__(256)
 gsea_null_reduce_kernel(const double* __restrict__ part, int32_t nblk, const double* __restrict__ ES,
-                        const int32_t* __restrict__ Gp, int32_t m, int32_t c, double* __restrict__ out) {
+                        const int32_t* __restrict__ Gp, int32_t m, int32_t c, int score_type, double* __restrict__ out) {
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int64_t pairs = (int64_t)m * c;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < pairs; e += (int64_t)gridDim.x * blockDim.x) {
@@ -340,13 +462,15 @@ gsea_null_reduce_kernel(const double* __restrict__ part, int32_t nblk, const dou
       continue;
     }
     const double n_ge = acc[0], n_le = acc[1], n_ge0 = acc[2], n_le0 = acc[3], sum_pos = acc[4], sum_neg = acc[5];
-    const double nes = es > 0.0 ? es / (sum_pos / n_ge0) : es / fabs(sum_neg / n_le0);
+    // std: the side of ES; pos: the upper side; neg: the lower side
+    const bool upper = score_type == PLAIDHIP_GSEA_POS || (score_type == PLAIDHIP_GSEA_STD && es > 0.0);
+    const double nes = upper ? es / (sum_pos / n_ge0) : es / fabs(sum_neg / n_le0);
     const double pl = (1.0 + n_le) / (1.0 + n_le0), pg = (1.0 + n_ge) / (1.0 + n_ge0);
     o[0] = es;
     o[(int64_t)m] = nes;
-    o[2 * (int64_t)m] = pl < pg ? pl : pg;
+    o[2 * (int64_t)m] = score_type == PLAIDHIP_GSEA_POS ? pg : (score_type == PLAIDHIP_GSEA_NEG ? pl : (pl < pg ? pl : pg));
     o[3 * (int64_t)m] = nan;
-    o[4 * (int64_t)m] = es > 0.0 ? n_ge : n_le;
+    o[4 * (int64_t)m] = upper ? n_ge : n_le;
     o[5 * (int64_t)m] = size;
     for (int q = 0; q < 6; ++q) o[(int64_t)(6 + q) * m] = acc[q];
   }
@@ -393,8 +517,8 @@ int launch_gsea_check_perm(plaidhip_ctx* ctx, const int32_t* P, int32_t g, int32
   return PLAIDHIP_OK;
 }
 
-int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, const int32_t* pos_obs, const double* Wpos, const uint32_t* listnan,
-                    int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* ES) {
+int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* pos_obs, const double* Wpos,
+                    const uint32_t* listnan, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* ES) {
   if ((int64_t)m * c == 0) return PLAIDHIP_OK;
   if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
     set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
@@ -404,19 +528,51 @@ int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, const int32_t* pos_obs, con
   const size_t shmem = (size_t)kGnWaves * nw64 * 8;   // at most 64 KB
   const int64_t pairs = (int64_t)m * c;
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pairs + kGnWaves - 1) / kGnWaves, (int64_t)ctx->num_cu * 16));
-  if (weighted)
-    hipLaunchKernelGGL(gsea_obs_kernel<true>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
-                       Gp, Gi, m, ES, nw64);
-  else
-    hipLaunchKernelGGL(gsea_obs_kernel<false>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
-                       Gp, Gi, m, ES, nw64);
+#define PH_GSEA_OBS(W, ST)                                                                                                     \
+  hipLaunchKernelGGL((gsea_obs_kernel<W, ST>), dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, \
+                     c, Gp, Gi, m, ES, nw64)
+  if (weighted) {
+    if (score_type == PLAIDHIP_GSEA_POS) PH_GSEA_OBS(true, PLAIDHIP_GSEA_POS);
+    else if (score_type == PLAIDHIP_GSEA_NEG) PH_GSEA_OBS(true, PLAIDHIP_GSEA_NEG);
+    else PH_GSEA_OBS(true, PLAIDHIP_GSEA_STD);
+  } else {
+    if (score_type == PLAIDHIP_GSEA_POS) PH_GSEA_OBS(false, PLAIDHIP_GSEA_POS);
+    else if (score_type == PLAIDHIP_GSEA_NEG) PH_GSEA_OBS(false, PLAIDHIP_GSEA_NEG);
+    else PH_GSEA_OBS(false, PLAIDHIP_GSEA_STD);
+  }
+#undef PH_GSEA_OBS
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
 
-int launch_gsea_null(plaidhip_ctx* ctx, int weighted, const int32_t* P, int32_t nbs, const double* Wpos, const uint32_t* listnan,
-                     const double* ES, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* part,
-                     int64_t blk_at0, double* null_out) {
+int launch_gsea_edges(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* pos_obs, const double* Wpos,
+                      const uint32_t* listnan, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                      int32_t* le_len, int32_t* le_idx) {
+  if ((int64_t)m * c == 0) return PLAIDHIP_OK;
+  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
+    set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  const int32_t nw64 = gn_map_words(g);
+  const size_t shmem = (size_t)kGnWaves * nw64 * 12;   // the maps and the words' counts: at most 96 KB
+  const int64_t pairs = (int64_t)m * c;
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pairs + kGnWaves - 1) / kGnWaves, (int64_t)ctx->num_cu * 16));
+  if (weighted) {
+    PH_FULL_LDS(ctx, gsea_edge_kernel<true>);
+    hipLaunchKernelGGL(gsea_edge_kernel<true>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
+                       Gp, Gi, m, score_type, le_len, le_idx, nw64);
+  } else {
+    PH_FULL_LDS(ctx, gsea_edge_kernel<false>);
+    hipLaunchKernelGGL(gsea_edge_kernel<false>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
+                       Gp, Gi, m, score_type, le_len, le_idx, nw64);
+  }
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+int launch_gsea_null(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* P, int32_t nbs, const double* Wpos,
+                     const uint32_t* listnan, const double* ES, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
+                     int32_t m, double* part, int64_t blk_at0, double* null_out) {
   if ((int64_t)m * c == 0 || nbs == 0) return PLAIDHIP_OK;
   if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
     set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
@@ -427,25 +583,32 @@ int launch_gsea_null(plaidhip_ctx* ctx, int weighted, const int32_t* P, int32_t 
   const int32_t ntile = weighted ? (c + kGnListTile - 1) / kGnListTile : 1;
   const int64_t tasks = (int64_t)m * ntile * ((nbs + kGnBlock - 1) / kGnBlock);
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tasks, (int64_t)ctx->num_cu * 16));
+#define PH_GSEA_NULL(W, ST)                                                                                                   \
+  do {                                                                                                                        \
+    PH_FULL_LDS(ctx, (gsea_null_kernel<W, ST>));                                                                              \
+    hipLaunchKernelGGL((gsea_null_kernel<W, ST>), dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, P, nbs, Wpos, listnan, \
+                       ES, g, c, Gp, Gi, m, part, blk_at0, null_out, nw64);                                                   \
+  } while (0)
   if (weighted) {
-    PH_FULL_LDS(ctx, gsea_null_kernel<true>);
-    hipLaunchKernelGGL(gsea_null_kernel<true>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, P, nbs, Wpos, listnan, ES, g,
-                       c, Gp, Gi, m, part, blk_at0, null_out, nw64);
+    if (score_type == PLAIDHIP_GSEA_POS) PH_GSEA_NULL(true, PLAIDHIP_GSEA_POS);
+    else if (score_type == PLAIDHIP_GSEA_NEG) PH_GSEA_NULL(true, PLAIDHIP_GSEA_NEG);
+    else PH_GSEA_NULL(true, PLAIDHIP_GSEA_STD);
   } else {
-    PH_FULL_LDS(ctx, gsea_null_kernel<false>);
-    hipLaunchKernelGGL(gsea_null_kernel<false>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, P, nbs, Wpos, listnan, ES, g,
-                       c, Gp, Gi, m, part, blk_at0, null_out, nw64);
+    if (score_type == PLAIDHIP_GSEA_POS) PH_GSEA_NULL(false, PLAIDHIP_GSEA_POS);
+    else if (score_type == PLAIDHIP_GSEA_NEG) PH_GSEA_NULL(false, PLAIDHIP_GSEA_NEG);
+    else PH_GSEA_NULL(false, PLAIDHIP_GSEA_STD);
   }
+#undef PH_GSEA_NULL
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
 
 int launch_gsea_null_reduce(plaidhip_ctx* ctx, const double* part, int32_t nblk, const double* ES, const int32_t* Gp, int32_t m,
-                            int32_t c, double* out) {
+                            int32_t c, int score_type, double* out) {
   const int64_t pairs = (int64_t)m * c;
   if (pairs == 0) return PLAIDHIP_OK;
   hipLaunchKernelGGL(gsea_null_reduce_kernel, dim3((unsigned)std::min<int64_t>((pairs + 255) / 256, 65536)), dim3(256), 0,
-                     ctx->stream, part, nblk, ES, Gp, m, c, out);
+                     ctx->stream, part, nblk, ES, Gp, m, c, score_type, out);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

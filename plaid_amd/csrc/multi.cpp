@@ -1789,7 +1789,7 @@ int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   plaidhip_shard_bounds(nblk, ndev, k, &blo, &bhi);
   const int64_t p_lo = blo * PLAIDHIP_GSEA_PERM_BLOCK, p_hi = std::min<int64_t>(B, bhi * PLAIDHIP_GSEA_PERM_BLOCK);
   const size_t col = (size_t)g * nl, blk_doubles = (size_t)nl * 6 * m;
-  DevBuf dstat, dw, dR, dY, dQ, dWpos, dpos, dnan, dGp, dGi, dES, dpart, dslabY, dslabR, dP, dbad, dnull, dout, dall;
+  DevBuf dstat, dw, dR, dY, dQ, dWpos, dpos, dnan, dGp, dGi, dES, dpart, dslabY, dslabR, dP, dbad, dnull, dout, dall, dlen, didx;
   const int32_t slab = gsea_slab_perms(g);
 
   // ---- upload, the observed placements and scores -------------------------------------------------------------------------
@@ -1815,7 +1815,7 @@ int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
     PH_TRY(launch_sing_last_ranks(ctx, dR.as<double>(), g, g, nl, dY.as<double>(), dQ.as<double>()));
     PH_TRY(launch_gsea_operands(ctx, dQ.as<double>(), dw.as<double>(), g, dnan.as<uint32_t>(), g, nl, dpos.as<int32_t>(),
                                 dWpos.as<double>()));
-    return launch_gsea_obs(ctx, c.gsea_weighted, dpos.as<int32_t>(), dWpos.as<double>(), dnan.as<uint32_t>(), g, nl,
+    return launch_gsea_obs(ctx, c.gsea_weighted, c.score_type, dpos.as<int32_t>(), dWpos.as<double>(), dnan.as<uint32_t>(), g, nl,
                            dGp.as<int32_t>(), dGi.as<int32_t>(), m, dES.as<double>());
   });
 
@@ -1846,7 +1846,7 @@ int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
         PH_HIP(hipStreamSynchronize(ctx->stream));
         PH_REQUIRE(bad[0] == 0u, "gsea: column %u of perm is no permutation of 0..%d", bad[1] - 1u, g - 1);
       }
-      PH_TRY(launch_gsea_null(ctx, c.gsea_weighted, dP.as<int32_t>(), nbs, dWpos.as<double>(), dnan.as<uint32_t>(),
+      PH_TRY(launch_gsea_null(ctx, c.gsea_weighted, c.score_type, dP.as<int32_t>(), nbs, dWpos.as<double>(), dnan.as<uint32_t>(),
                               dES.as<double>(), g, nl, dGp.as<int32_t>(), dGi.as<int32_t>(), m, dpart.as<double>(),
                               (b0 - p_lo) / PLAIDHIP_GSEA_PERM_BLOCK, c.null_out != nullptr ? dnull.as<double>() : nullptr));
       if (c.null_out != nullptr)
@@ -1874,8 +1874,18 @@ int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
         part = dall.as<double>();
       }
       PH_TRY(dout.alloc((size_t)m * 12 * nl * 8));
-      PH_TRY(launch_gsea_null_reduce(ctx, part, nblk, dES.as<double>(), dGp.as<int32_t>(), m, nl, dout.as<double>()));
+      PH_TRY(launch_gsea_null_reduce(ctx, part, nblk, dES.as<double>(), dGp.as<int32_t>(), m, nl, c.score_type,
+                                     dout.as<double>()));
       PH_HIP(hipMemcpyAsync(c.out, dout.p, (size_t)m * 12 * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (c.le_len != nullptr) {   // the leading edges, once, on the observed placements this shard already holds
+        const size_t nnz = (size_t)c.Gp[m];
+        PH_TRY(dlen.alloc((size_t)m * nl * 4));
+        PH_TRY(didx.alloc(nnz * nl * 4));
+        PH_TRY(launch_gsea_edges(ctx, c.gsea_weighted, c.score_type, dpos.as<int32_t>(), dWpos.as<double>(), dnan.as<uint32_t>(),
+                                 g, nl, dGp.as<int32_t>(), dGi.as<int32_t>(), m, dlen.as<int32_t>(), didx.as<int32_t>()));
+        PH_HIP(hipMemcpyAsync(c.le_len, dlen.p, (size_t)m * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (nnz != 0) PH_HIP(hipMemcpyAsync(c.le_idx, didx.p, nnz * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+      }
       PH_HIP(hipStreamSynchronize(ctx->stream));
       std::vector<double> p, q;
       std::vector<int32_t> at;
@@ -2230,6 +2240,9 @@ int check_plaid_test_contrasts_call(Call& c) {
 // plaid.gsea; the order is part of the contract (include/plaidhip.h).  Finds whether any weight differs from 1 and the lists
 // that hold a NaN or an infinity
 int check_gsea_call(Call& c) {
+  PH_REQUIRE(c.score_type >= PLAIDHIP_GSEA_STD && c.score_type <= PLAIDHIP_GSEA_NEG, "gsea: score_type = %d (0 std, 1 pos, 2 neg)",
+             c.score_type);
+  PH_REQUIRE((c.le_len == nullptr) == (c.le_idx == nullptr), "gsea: le_len and le_idx are passed both or neither");
   PH_REQUIRE(c.nperm >= 1, "gsea: nperm = %d (at least 1)", c.nperm);
   PH_REQUIRE(c.n >= 1, "gsea: %d ranked lists (at least 1)", c.n);
   PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
@@ -2559,6 +2572,23 @@ int plaidhip_gsea_multi(const int* devices, int ndev, const double* stat, const 
                         const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
                         double* out, double* null_out) try {
   return dispatch(on_devices(devices, ndev), gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsea_scored_multi(const int* devices, int ndev, const double* stat, const double* weight, int32_t g, int32_t c,
+                               const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm,
+                               uint64_t seed, int score_type, double* out, double* null_out, int32_t* le_len,
+                               int32_t* le_idx) try {
+  return dispatch(on_devices(devices, ndev),
+                  gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_gsea_scored_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat,
+                                                     const double* weight, int32_t g, int32_t c, const int32_t* Gp,
+                                                     const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm,
+                                                     uint64_t seed, int score_type, double* out, double* null_out,
+                                                     int32_t* le_len, int32_t* le_idx) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_gsea_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat, const double* weight,

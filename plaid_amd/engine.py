@@ -313,18 +313,40 @@ def check_gsea_args(stat, weight, perm, nperm):
     return stat, weight, perm, nperm
 
 
-def _gsea(fn, head, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False):
+GSEA_SCORE_TYPES = {"std": 0, "pos": 1, "neg": 2}   # PLAIDHIP_GSEA_STD / _POS / _NEG
+
+
+def gsea_score_type(score_type):
+    """the ABI's ordinal of a score type name (an ordinal passes through, so a test reaches the library's own check)"""
+    if isinstance(score_type, str):
+        if score_type not in GSEA_SCORE_TYPES:
+            raise ValueError(f"gsea: score_type must be one of {sorted(GSEA_SCORE_TYPES)} (got {score_type!r})")
+        return GSEA_SCORE_TYPES[score_type]
+    return int(score_type)
+
+
+def _gsea(fn, head, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, score_type=None, leading_edge=False):
     """plaidhip_gsea / _multi / the hook: sets x 12 x lists (GSEA_COLUMNS), and the sets x nperm x lists null scores with
-    null = True"""
+    null = True.  score_type not None: `fn` is plaidhip_gsea_scored / _multi / its hook; with leading_edge the result ends
+    with le_len (sets x lists int32) and le_idx (Gp[-1] x lists int32, -1 past a set's edge)"""
     stat, weight, perm, nperm = check_gsea_args(stat, weight, perm, nperm)
     Gp, Gi = _as_i32(Gp), _as_i32(Gi)
     g, c = stat.shape
     m = len(Gp) - 1
     out = np.full((m, 12, c), np.nan, dtype=np.float64, order="F")
     nul = np.full((m, nperm, c), np.nan, dtype=np.float64, order="F") if null else None
+    tail = ()
+    res = (out, nul) if null else (out,)
+    if score_type is not None:
+        le_len = np.full((m, c), -7, dtype=np.int32, order="F") if leading_edge else None
+        le_idx = np.full((int(Gp[-1]), c), -7, dtype=np.int32, order="F") if leading_edge else None
+        tail = (None if le_len is None else _np_ptr(le_len), None if le_idx is None else _np_ptr(le_idx))
+        if leading_edge:
+            res += (le_len, le_idx)
     check(fn(*head, _np_ptr(stat), _np_ptr(weight), g, c, _np_ptr(Gp), _np_ptr(Gi), m, None if perm is None else _np_ptr(perm),
-             nperm, int(seed) & (2**64 - 1), _np_ptr(out), None if nul is None else _np_ptr(nul)))
-    return (out, nul) if null else out
+             nperm, int(seed) & (2**64 - 1), *(() if score_type is None else (gsea_score_type(score_type),)), _np_ptr(out),
+             None if nul is None else _np_ptr(nul), *tail))
+    return res if len(res) > 1 else out
 
 
 class Context:
@@ -695,11 +717,16 @@ class Context:
         distinct row indices (never expanded), G aligned to X's rows"""
         return self._host("aucell_exact", X, Gp, Gi, float(auc_max_rank))
 
-    def gsea(self, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False):
+    def gsea(self, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, score_type="std", leading_edge=False):
         """plaidhip_gsea: preranked GSEA of the columns of stat (genes x lists) with their weights; perm: genes x nperm
         int32 placements, or None for the placements generated from `seed`.  Returns sets x 12 x lists (GSEA_COLUMNS); with
-        null = True also the sets x nperm x lists null scores."""
-        return _gsea(self.lib.plaidhip_gsea, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null)
+        null = True also the sets x nperm x lists null scores.  score_type "pos" / "neg" (plaidhip_gsea_scored) scores one
+        side of the walk; leading_edge = True appends le_len (sets x lists int32) and le_idx (Gp[-1] x lists int32: the edge
+        of set j in list l is le_idx[Gp[j]:Gp[j] + le_len[j, l], l], rows of stat, -1 behind it)."""
+        if gsea_score_type(score_type) == 0 and not leading_edge:
+            return _gsea(self.lib.plaidhip_gsea, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null)
+        return _gsea(self.lib.plaidhip_gsea_scored, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type,
+                     leading_edge)
 
     def gsea_permutations(self, g: int, nperm: int, seed=1) -> np.ndarray:
         """plaidhip_gsea_permutations: the genes x nperm int32 placements plaidhip_gsea generates from `seed`"""
@@ -878,9 +905,11 @@ def plaid_test_contrasts_multi(X, Y, Gp, Gi, gsetX=None, tests=7, metap_method=0
     return _plaid_test_contrasts(*_multi("plaid_test_contrasts", devices), X, Y, Gp, Gi, gsetX, tests, metap_method)
 
 
-def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, devices=1):
+def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, devices=1, score_type="std", leading_edge=False):
     """plaid.gsea (Context.gsea) with the permutation blocks shared out over `devices`: the one-device bits"""
-    return _gsea(*_multi("gsea", devices), stat, weight, Gp, Gi, perm, nperm, seed, null)
+    if gsea_score_type(score_type) == 0 and not leading_edge:
+        return _gsea(*_multi("gsea", devices), stat, weight, Gp, Gi, perm, nperm, seed, null)
+    return _gsea(*_multi("gsea_scored", devices), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type, leading_edge)
 
 
 def multi_finalize():

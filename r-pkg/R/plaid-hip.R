@@ -478,11 +478,15 @@ plaid.test.contrasts <- function(X, Y, G, gsetX = NULL, tests = c("one", "two", 
 ## plaid.gsea(): preranked GSEA with a permutation null on the device -- what fgsea::fgsea(gmt, fc) gives the enrichment
 ## experiments (experiments/compare-enrichment/enrichment-methods.R:28): ES, NES, pval, padj for a named vector of
 ## statistics, or for every column of a genes x contrasts matrix.  include/plaidhip.h (plaidhip_gsea) pins the statistic
-## (fgseaSimple, scoreType = "std"); the weights abs(stats)^gseaParam are formed here.  perm: NULL (nperm placements
+## (fgseaSimple); the weights abs(stats)^gseaParam are formed here.  perm: NULL (nperm placements
 ## generated from seed) or a genes x nperm integer matrix whose columns are permutations of seq_len(genes) over the aligned
 ## genes.  Returns a matrix (a vector of statistics) or a named list of matrices, rows ordered by sort.by.
+## scoreType "pos" / "neg" scores one side of the walk (a statistic of one sign: |logFC|, F, -log p).  leadingEdge = TRUE
+## returns, wherever a matrix is returned, list(table = <that matrix>, leadingEdge = <named list, one character vector of
+## gene names per table row in the table's order: the genes that drive the set's score, in walk order>).
 plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSize = NULL, seed = 1, perm = NULL,
-                       sort.by = "pval") {
+                       sort.by = "pval", scoreType = c("std", "pos", "neg"), leadingEdge = FALSE) {
+  scoreType <- match.arg(scoreType)
   single <- is.null(dim(stats))
   if (single) stats <- matrix(stats, ncol = 1, dimnames = list(names(stats), "stat"))
   stats <- as.matrix(stats); storage.mode(stats) <- "double"
@@ -506,14 +510,28 @@ plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSi
     perm <- matrix(as.integer(perm) - 1L, nrow(perm), ncol(perm))
   }
   .session()
-  r <- .Call("R_plaidhip_gsea", .devices(), stats, W, pat$Gp, pat$Gi, perm, as.integer(nperm), as.numeric(seed %% 2^32),
-             as.numeric((seed %/% 2^32) %% 2^32), PACKAGE = "plaidhip")
+  edges <- isTRUE(as.logical(leadingEdge))
+  le <- NULL
+  if (scoreType == "std" && !edges) {
+    r <- .Call("R_plaidhip_gsea", .devices(), stats, W, pat$Gp, pat$Gi, perm, as.integer(nperm), as.numeric(seed %% 2^32),
+               as.numeric((seed %/% 2^32) %% 2^32), PACKAGE = "plaidhip")
+  } else {
+    le <- .Call("R_plaidhip_gsea_scored", .devices(), stats, W, pat$Gp, pat$Gi, perm, as.integer(nperm),
+                as.numeric(seed %% 2^32), as.numeric((seed %/% 2^32) %% 2^32), match(scoreType, c("std", "pos", "neg")) - 1L,
+                edges, PACKAGE = "plaidhip")
+    r <- le[[1]]
+  }
   dim(r) <- c(nrow(r), 12L, ncol(stats))
   cols <- c("ES", "NES", "pval", "padj", "nMoreExtreme", "size")
   out <- lapply(seq_len(ncol(stats)), function(l) {
     res <- matrix(r[, 1:6, l], nrow = dim(r)[1], dimnames = list(colnames(G), cols))
-    if (sort.by %in% cols) res <- res[order(res[, sort.by]), , drop = FALSE]
-    res
+    o <- if (sort.by %in% cols) order(res[, sort.by]) else seq_len(nrow(res))
+    res <- res[o, , drop = FALSE]
+    if (!edges) return(res)
+    ## the edge of set j in list l: le_idx[Gp[j] + seq_len(le_len[j, l]), l], 0-based rows of the aligned genes
+    led <- lapply(o, function(j) rownames(stats)[le[[3]][pat$Gp[j] + seq_len(le[[2]][j, l]), l] + 1L])
+    names(led) <- rownames(res)
+    list(table = res, leadingEdge = led)
   })
   names(out) <- colnames(stats)
   if (single) out[[1]] else out

@@ -573,6 +573,40 @@ SEXP R_plaidhip_gsea(SEXP devices, SEXP stat, SEXP weight, SEXP Gp, SEXP Gi, SEX
   return out;
 }
 
+/* plaid.gsea(scoreType =, leadingEdge =): list(out, le_len, le_idx) of plaidhip_gsea_scored -- out as R_plaidhip_gsea
+ * returns it; le_len (m x c integer) and le_idx (Gp[m] x c integer, 0-based rows of stat, -1 behind a set's edge), or NULL
+ * for both when no edges are asked for */
+SEXP R_plaidhip_gsea_scored(SEXP devices, SEXP stat, SEXP weight, SEXP Gp, SEXP Gi, SEXP perm, SEXP nperm, SEXP seed_lo,
+                            SEXP seed_hi, SEXP score_type, SEXP edges) {
+  const int g = Rf_nrows(stat), c = Rf_ncols(stat), m = LENGTH(Gp) - 1;
+  const int B = Rf_isNull(perm) ? Rf_asInteger(nperm) : Rf_ncols(perm);
+  const uint64_t seed = ((uint64_t)(uint32_t)Rf_asReal(seed_hi) << 32) | (uint64_t)(uint32_t)Rf_asReal(seed_lo);
+  const int want = Rf_asLogical(edges) == 1, st = Rf_asInteger(score_type);
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 12 * c));
+  SET_VECTOR_ELT(res, 0, out);
+  int32_t *le_len = NULL, *le_idx = NULL;
+  if (want) {
+    SEXP len = PROTECT(Rf_allocMatrix(INTSXP, m, c));
+    SEXP idx = PROTECT(Rf_allocMatrix(INTSXP, INTEGER(Gp)[m], c));
+    SET_VECTOR_ELT(res, 1, len);
+    SET_VECTOR_ELT(res, 2, idx);
+    le_len = INTEGER(len);
+    le_idx = INTEGER(idx);
+    UNPROTECT(2);
+  }
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_gsea_scored_multi(INTEGER(devices), LENGTH(devices), REAL(stat), REAL(weight), g, c, INTEGER(Gp), INTEGER(Gi),
+                                    m, int_or_null(perm), B, seed, st, REAL(out), NULL, le_len, le_idx);
+  else
+    rc = plaidhip_gsea_scored(ctx(), REAL(stat), REAL(weight), g, c, INTEGER(Gp), INTEGER(Gi), m, int_or_null(perm), B, seed, st,
+                              REAL(out), NULL, le_len, le_idx);
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(2);
+  return res;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -615,6 +649,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_plaid_test_contrasts", (DL_FUNC)&R_plaidhip_plaid_test_contrasts, 12},
     {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
     {"R_plaidhip_gsea", (DL_FUNC)&R_plaidhip_gsea, 9},
+    {"R_plaidhip_gsea_scored", (DL_FUNC)&R_plaidhip_gsea_scored, 11},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {

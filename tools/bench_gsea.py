@@ -2,7 +2,10 @@
 distribution, 1,000 permutations, 1 and 8 ranked lists, unweighted (weight 1) and weighted (|N(0, 1)|).  The yardstick is
 the walk kernel replaid.ssgsea.exact(single = FALSE) already has: gsea_ks_kernel at 20,000 genes x 1,000 columns x the same
 sets, alpha 0 beside the unweighted cases and 0.25 beside the weighted ones -- the same number of (set, walk) pairs as one
-list of the null.  Each case runs in a fresh process, one warm-up call first.
+list of the null.  Each case runs in a fresh process, one warm-up call first.  --score-type pos / neg runs the plaid.gsea
+cases through plaidhip_gsea_scored; the cases of EDGE_CASES (named in --cases; not among the defaults) ask for the
+leading edges as well, and under --profile report gsea_edge_kernel beside gsea_obs_kernel from the same run: both take one
+walk per (set, list) pair, and the edge adds the emit.
 
     python3 tools/bench_gsea.py [--reps 3] [--cases c1_unweighted,...]      host call times, one JSON line
     python3 tools/bench_gsea.py --profile DIR [--cases ...]                 the kernel times as well, one JSON line
@@ -34,6 +37,11 @@ CASES = {
     "ks_alpha0": dict(ks=True, alpha=0.0),          # the yardstick: gsea_ks_kernel, 1,000 columns
     "ks_alpha025": dict(ks=True, alpha=0.25),
 }
+EDGE_CASES = {
+    "c8_unweighted_edges": dict(lists=8, weighted=False, edges=True),
+    "c8_weighted_edges": dict(lists=8, weighted=True, edges=True),
+}
+ALL_CASES = {**CASES, **EDGE_CASES}
 
 
 def _median_ms(fn, reps):
@@ -46,10 +54,10 @@ def _median_ms(fn, reps):
     return float(np.median(ts))
 
 
-def run_case(name, reps, genes=GENES, sets=SETS, perms=PERMS):
+def run_case(name, reps, genes=GENES, sets=SETS, perms=PERMS, score_type="std"):
     import plaid_amd
     from plaid_amd import synth
-    p = CASES[name]
+    p = ALL_CASES[name]
     Gp, Gi = synth.geneset_csc(genes, sets)
     rng = np.random.default_rng(17)
     ctx = plaid_amd.Context(0)
@@ -61,26 +69,30 @@ def run_case(name, reps, genes=GENES, sets=SETS, perms=PERMS):
         else:
             stat = rng.normal(size=(genes, p["lists"]))
             w = np.abs(rng.normal(size=stat.shape)) if p["weighted"] else np.ones_like(stat)
-            ms = _median_ms(lambda: ctx.gsea(stat, w, Gp, Gi, nperm=perms, seed=1), reps)
+            kw = {} if score_type == "std" and not p.get("edges") else dict(score_type=score_type, leading_edge=bool(p.get("edges")))
+            ms = _median_ms(lambda: ctx.gsea(stat, w, Gp, Gi, nperm=perms, seed=1, **kw), reps)
             pairs = sets * perms * p["lists"]
     finally:
         ctx.close()
+    if not p.get("ks"):
+        p = {**p, "score_type": score_type}
     return {"case": name, **p, "genes": genes, "sets": sets, "perms": perms, "reps": reps, "host_ms": round(ms, 2), "pairs": pairs,
             "host_pairs_per_s": round(pairs / (ms * 1e-3), 1)}
 
 
 def _kernel_of(name):
-    return "gsea_ks_kernel" if CASES[name].get("ks") else "gsea_null_kernel"
+    return "gsea_ks_kernel" if ALL_CASES[name].get("ks") else "gsea_null_kernel"
 
 
-def profile_case(name, outdir, genes, sets, perms, limit_s):
+def profile_case(name, outdir, genes, sets, perms, limit_s, score_type="std"):
     """the case under rocprofv3 --kernel-trace --stats in a process of its own; its kernel's row of the stats file"""
     import csv
     import glob
     d = os.path.join(outdir, name)
     os.makedirs(d, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-           "--case", name, "--reps", "1", "--genes", str(genes), "--sets", str(sets), "--perms", str(perms)]
+           "--case", name, "--reps", "1", "--genes", str(genes), "--sets", str(sets), "--perms", str(perms), "--score-type",
+           score_type]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit_s)
     if r.returncode != 0:
         return {"error": (r.stderr or r.stdout)[-500:], "returncode": r.returncode}
@@ -88,18 +100,25 @@ def profile_case(name, outdir, genes, sets, perms, limit_s):
     if not files:
         return {"error": f"no *kernel_stats.csv under {d}", "returncode": 0}
     calls = total_ns = 0
+    beside = {"gsea_obs_kernel": 0, "gsea_edge_kernel": 0} if ALL_CASES[name].get("edges") else {}
     with open(files[0], newline="") as fh:
         for row in csv.DictReader(fh):
             if _kernel_of(name) in row["Name"]:
                 calls += int(row["Calls"])
                 total_ns += int(row["TotalDurationNs"])
+            for k in beside:
+                if k in row["Name"]:
+                    beside[k] += int(row["TotalDurationNs"])
     if calls == 0:
         return {"error": f"{_kernel_of(name)} is not in {files[0]}", "returncode": 0}
     host_calls = 2                                    # the warm-up and --reps 1
     ms = total_ns * 1e-6 / host_calls
-    pairs = sets * perms * CASES[name].get("lists", 1)
-    return {"kernel": _kernel_of(name), "kernel_launches": calls, "kernel_ms": round(ms, 3), "pairs_per_s": round(pairs / (ms * 1e-3), 1),
-            "stats_file": os.path.relpath(files[0], outdir)}
+    pairs = sets * perms * ALL_CASES[name].get("lists", 1)
+    res = {"kernel": _kernel_of(name), "kernel_launches": calls, "kernel_ms": round(ms, 3), "pairs_per_s": round(pairs / (ms * 1e-3), 1),
+           "stats_file": os.path.relpath(files[0], outdir)}
+    for k, ns in beside.items():          # per host call, like kernel_ms: one walk per (set, list) pair each
+        res[k + "_ms"] = round(ns * 1e-6 / host_calls, 3)
+    return res
 
 
 def main():
@@ -110,22 +129,24 @@ def main():
     ap.add_argument("--genes", type=int, default=GENES)
     ap.add_argument("--sets", type=int, default=SETS)
     ap.add_argument("--perms", type=int, default=PERMS)
+    ap.add_argument("--score-type", default="std", choices=["std", "pos", "neg"], help="scoreType of the plaid.gsea cases")
     ap.add_argument("--profile", default=None, metavar="DIR", help="also run every case under rocprofv3, stats files into DIR")
     ap.add_argument("--limit", type=int, default=300, help="seconds a profiled case may take")
     a = ap.parse_args()
     if a.case is not None:
-        print(json.dumps(run_case(a.case, a.reps, a.genes, a.sets, a.perms)))
+        print(json.dumps(run_case(a.case, a.reps, a.genes, a.sets, a.perms, a.score_type)))
         return
     out = []
     for name in a.cases.split(","):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name, "--reps", str(a.reps), "--genes", str(a.genes),
-                            "--sets", str(a.sets), "--perms", str(a.perms)], capture_output=True, text=True, timeout=a.limit)
+                            "--sets", str(a.sets), "--perms", str(a.perms), "--score-type", a.score_type], capture_output=True,
+                           text=True, timeout=a.limit)
         if r.returncode != 0:
             out.append({"case": name, "error": (r.stderr or r.stdout)[-500:], "returncode": r.returncode})
             break                          # a failed case ends the run: nothing more is started on the device
         out.append(json.loads(r.stdout.strip().splitlines()[-1]))
         if a.profile is not None:
-            k = profile_case(name, a.profile, a.genes, a.sets, a.perms, a.limit)
+            k = profile_case(name, a.profile, a.genes, a.sets, a.perms, a.limit, a.score_type)
             out[-1].update(k)
             if "error" in k:
                 break
