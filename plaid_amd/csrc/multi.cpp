@@ -1080,7 +1080,6 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   const int64_t zx = s.zx;
   int32_t max_row = 0, max_nnz = 0;
   std::vector<int32_t> ploc;
-  const double n_inv = 1.0 / (double)n;   // (the scale of launch_row_group_moments' group 0)
   // host sources of asynchronous uploads: they live until the worker's last synchronisation
   std::vector<double> host_mean, host_ssd, row_nnz, add;
 
@@ -1248,7 +1247,9 @@ int scorer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
     s.step([&]() -> int {
       if (nloc == 0) return PLAIDHIP_OK;
       host_mean.resize((size_t)g);
-      for (int32_t i = 0; i < g; ++i) host_mean[(size_t)i] = sh.chain_sum[(size_t)i] * n_inv;   // reduce_blocks_kernel's scale
+      // A true division, as rowMeans and the dgCMatrix branch below divide: sum * fl(1 / n) misses the mean of a constant
+      // gene for some n (1.25 at n = 105), whose z then is -2e-8 instead of 0 and whose signed rank -1 instead of 0
+      for (int32_t i = 0; i < g; ++i) host_mean[(size_t)i] = sh.chain_sum[(size_t)i] / (double)n;
       PH_HIP(hipMemcpyAsync(d_mean, host_mean.data(), (size_t)g * 8, hipMemcpyHostToDevice, ctx->stream));
       return launch_row_group_partials(ctx, dX.as<double>(), ld, g, nloc, dy.as<int32_t>(), d_mean, dscratch.as<double>());
     });

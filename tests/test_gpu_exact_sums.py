@@ -12,6 +12,7 @@ import pytest
 import scipy.sparse as sp
 
 from tests.helpers import exact_ref as er
+from tests.helpers.gsva_ref import _long_sums, _normalized_ref, _w
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +34,6 @@ def _data(kind, g, n, seed):
     if kind == "well":
         return rng.gamma(2.0, 1.0, size=(g, n)) + 0.25
     return np.where(rng.random((g, n)) < 0.5, 1e6, -1e6) + rng.normal(size=(g, n))
-
-
-def _w(Gp):
-    return 1.0 / (1e-8 + np.diff(Gp).astype(np.float64))
 
 
 def _check_mean_and_sum(got_mean, got_sum, Gp, Gi, X, what):
@@ -337,23 +334,6 @@ def test_replaid_sing_within_the_fp64_bound_of_exact_rank_sums(hip_ctx, sparse):
 
 
 # ---------------------------------------------------------------- normalised rank routes: replaid.ssgsea and replaid.ucell
-def _normalized_ref(T, E):
-    """normalize_medians(T) (ignore.zero FALSE) in long double, and a bound on |device - reference| for a device whose raw
-    scores S lie within E of T elementwise.  A column median is 1-Lipschitz in the max norm, so |med(S) - med(T)| <=
-    max_col E; the midpoints round once on either side (2 u |med|); mean(med) adds its own sum and division roundings
-    ((n + 2) u mean|med|); then fl(fl(S - med) + add) rounds twice and the reference once"""
-    u = er.U
-    n = T.shape[1]
-    med = er.col_medians(T, False)
-    Mc = E.max(axis=0) + 2.0 * u * np.abs(med)
-    ld = np.longdouble
-    add = np.mean(med.astype(ld))
-    N = ((T.astype(ld) - med.astype(ld)[None, :]) + add).astype(np.float64)
-    A = Mc.mean() + (n + 2) * u * np.abs(med).mean()
-    B = E + Mc[None, :] + A + u * (np.abs(T) + np.abs(med)[None, :]) + 2.0 * u * np.abs(N) + u * abs(float(add))
-    return N, B
-
-
 def _rank_case(sparse, seed):
     from plaid_amd import synth as sy
     g, n, m = 12001, 9, 400
@@ -364,15 +344,6 @@ def _rank_case(sparse, seed):
     else:
         X = sy.dense_columns(g, 0, n, tied=True)
     return g, Gp, Gi, X
-
-
-def _long_sums(Gp, Gi, W):
-    """exact set sums of long-double terms: the fp64 head and tail of each term summed apart"""
-    hi = W.astype(np.float64)
-    lo = (W - hi.astype(np.longdouble)).astype(np.float64)
-    s_hi, mag, k = er.set_sums(Gp, Gi, hi)
-    s_lo, _, _ = er.set_sums(Gp, Gi, lo)
-    return s_hi.astype(np.longdouble) + s_lo.astype(np.longdouble), mag, k
 
 
 @pytest.mark.parametrize("sparse", [False, True])
