@@ -462,6 +462,27 @@ int max_sparse_rank_column();
 // (pow_quarters: the bucket and partitioned rankers) rather than by pow() (the sorting networks); the data-dependent
 // fallback of clustered columns to the network aside
 bool colranks_uses_power_quarters(plaidhip_ctx* ctx, int32_t g);
+// ---- what the exact scorers share (the walk itself: bitmap_walk.h; the device loops: exact_common.h) ----------------------
+// columns of a dense matrix (Xp == nullptr) or the stored values of CSC columns
+struct RankCols {
+  const int32_t* Xp;
+  int32_t g, n;            // dense: rows; CSC: the longest column (what sizes the grid).  n columns
+  int64_t ldx, ldr, lds;   // dense: leading dimensions of the input, of the ranks and of the scratch columns
+};
+inline RankCols dense_cols(int32_t g, int32_t n, int64_t ld) { return RankCols{nullptr, g, n, ld, ld, ld}; }
+inline RankCols csc_cols(const int32_t* Xp, int32_t max_col_nnz, int32_t n) { return RankCols{Xp, max_col_nnz, n, 0, 0, 0}; }
+// kernels_rank.hip: Q = rank(x, "last") from the min or average ranks R (a min-rank pass over the tie-free
+// Y = (2 R - 1) 2^26 + (cnt - 1 - item)); R, Y, Q laid out as `cols` (dense: leading dimension ld); Q may be R; columns of
+// fewer than 2^26 values.  Stream-ordered.
+int launch_last_ranks(plaidhip_ctx* ctx, const RankCols& cols, const double* R, double* Y, double* Q);
+// kernels_rank.hip: colnan[c] = 1 for a column holding a NaN: dense X (Xp == nullptr, g rows, leading dimension ldx) or the
+// stored values of CSC columns (the longest max_col_nnz)
+int launch_colnan(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, int32_t g, int32_t n,
+                  int32_t max_col_nnz, uint32_t* colnan);
+// kernels_walk.hip: range_out[3] = {min, max, any NaN} of the m x n scores; part: 3 score_part_blocks(m n) doubles.
+// score_part_blocks: the workgroups of the element-wise kernels over m x n scores
+int score_part_blocks(plaidhip_ctx* ctx, int64_t count);
+int launch_score_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out);
 // kernels_walk.hip: replaid.ssgsea.exact.  Operands of g x n columns (leading dimension ldq): Q = rank(x, "last"), and
 // when alpha != 0 W = rank(x, "average")^alpha and P = W * Q; colnan[c] = 1 for a column holding a NaN.  Dense X
 // (Xp == nullptr, leading dimension ldx; scratch 2 ldq n doubles) or CSC slots (rows increasing in each column; nnz =
@@ -470,8 +491,7 @@ int launch_ssgsea_exact_operands(plaidhip_ctx* ctx, const double* X, int64_t ldx
                                  int32_t g, int32_t n, int32_t max_col_nnz, int64_t nnz, double alpha, double* Q, double* W,
                                  double* P, int64_t ldq, double* scratch, uint32_t* colnan);
 // S (m x n, holding C on entry) <- the pinned epilogue of A, B (nullptr: alpha = 0) and kset (device int32 set sizes);
-// part: 3 ssgsea_exact_part_blocks(m n) doubles; range_out[3] = {min, max, any NaN} of the scores
-int ssgsea_exact_part_blocks(plaidhip_ctx* ctx, int64_t count);
+// part: 3 score_part_blocks(m n) doubles; range_out[3] = {min, max, any NaN} of the scores
 int launch_ssgsea_exact_epilogue(plaidhip_ctx* ctx, const double* A, const double* B, double* S, int64_t lds, int32_t m,
                                  int32_t n, const int32_t* kset, int64_t N, int scale, const uint32_t* colnan, double* part,
                                  double* range_out);
@@ -489,13 +509,6 @@ int launch_gsea_ks(plaidhip_ctx* ctx, const double* Q, const double* W, double* 
 int launch_gsva_ks(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* colnan, int32_t g, int32_t n,
                    const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int max_diff, double* T, double* S, int64_t lds);
 // kernels_sing.hip: replaid.sing.exact (include/plaidhip.h: plaidhip_sing_exact).  All stream-ordered.
-// colnan[c] = 1 for a column holding a NaN: dense X (Xp == nullptr, g rows, leading dimension ldx) or the stored values of
-// CSC columns (the longest max_col_nnz)
-int launch_sing_colnan(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, int32_t g, int32_t n,
-                       int32_t max_col_nnz, uint32_t* colnan);
-// Q = rank(x, "last") from the min ranks R (a rank pass over the tie-free Y = R 2^26 + (g - 1 - row)); R, Y, Q: g x n,
-// leading dimension ld; g <= 2^26
-int launch_sing_last_ranks(plaidhip_ctx* ctx, const double* R, int64_t ld, int32_t g, int32_t n, double* Y, double* Q);
 // Rpos[q - 1] = r per column (u32, leading dimension ldp), columns flagged in colnan skipped
 int launch_sing_rpos(plaidhip_ctx* ctx, const double* R, const double* Q, int64_t ld, const uint32_t* colnan, int32_t g,
                      int32_t n, uint32_t* Rpos, int64_t ldp);
@@ -512,9 +525,6 @@ int launch_sing_mad(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint3
 // mode: PLAIDHIP_TRUNC_UCELL / _AUCELL; T: maxRank or aucMaxRank.  The most entries a column of g rows (a CSC column of len
 // stored values) can get: what sizes the slots
 int64_t truncated_bound(int mode, int64_t T, int64_t g, int64_t len, bool sparse);
-// Y = the tie-free column whose min ranks are rank(x, "last") of the stored values of CSC columns, from their min ranks
-int launch_truncated_last_prep(plaidhip_ctx* ctx, const int32_t* Xp, const double* Rmin, int32_t n, int32_t max_col_nnz,
-                               double* Y);
 // count, scan, fill: the compressed columns (Wp n + 1, Wi, Wx; rows ascending) of the non-zero weights from the ranks R --
 // dense (Xp == nullptr: rank(x, "average") or, AUCell, rank(x, "last") of all g rows, leading dimension ldr) or of the stored
 // values of CSC columns among themselves (rows increasing in each column).  cnt: n words of scratch; cap: the entries of
@@ -551,8 +561,6 @@ unsigned long long debug_gsva_kcdf_slow_terms();   // mode 2: the last launch's 
 // goes to this device.  dV: g x nloc on the device, leading dimension g.
 int gsva_kcdf_columns(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                       int32_t lo, int32_t nloc, double* dV);
-// range_out[3] = {min, max, any NaN} of the m x n scores; part: 3 ssgsea_exact_part_blocks(m n) doubles
-int launch_gsea_ks_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out);
 // kernels_gsea.hip: plaid.gsea (include/plaidhip.h: plaidhip_gsea).  All stream-ordered, all pointers device pointers.
 // pos_obs (c x g int32) and Wpos (c x g) of every list from its last ranks Q and weights W (leading dimension ld; the
 // outputs are packed, leading dimension g); a list flagged in listnan is skipped

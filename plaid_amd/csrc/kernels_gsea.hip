@@ -1,7 +1,7 @@
 // plaid.gsea: preranked GSEA with a permutation null (include/plaidhip.h: plaidhip_gsea).
 //
 // The observed enrichment score of a (set, list) pair and the B null scores of the set are the same walk: the bitmap walk
-// of kernels_ks.hip over a PLACEMENT, an int32 permutation pos[0..N) of 0..N-1 that says where each gene stands in the
+// of bitmap_walk.h over a PLACEMENT, an int32 permutation pos[0..N) of 0..N-1 that says where each gene stands in the
 // walk.  The observed placement of a list is its order by decreasing stat (gsea_operand_kernel, from the last ranks); null
 // placement b is column b of P and serves every set and every list.  The weight of a hit depends on the walk position
 // alone: Wpos[pos] per list, scattered once.  So the null walks read 4-byte placements and one Wpos per list where
@@ -21,8 +21,7 @@
 // form is its own IEEE operation.
 #include <algorithm>
 
-#include "common.h"
-#include "rank_bucket.h"
+#include "bitmap_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -34,12 +33,6 @@ constexpr int kGnWaves = 4;        // wavefronts per workgroup, one permutation 
 constexpr int kGnBlock = 64;       // permutations per block of partials (PLAIDHIP_GSEA_PERM_BLOCK)
 constexpr int kGnListTile = 8;     // lists that share one setting of a permutation's bits
 static_assert(kGnBlock == PLAIDHIP_GSEA_PERM_BLOCK, "the block of the pinned summation order");
-
-__device__ __forceinline__ void gn_wave_sync() {   // LDS written by the wavefront's lanes is read by its other lanes
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- Philox4x32-10 (Salmon et al., SC'11): counter (i, b, 0, 0), key (seed lo, seed hi) ------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -118,32 +111,11 @@ gsea_operand_kernel(const double* __restrict__ Q, const double* __restrict__ W, 
   }
 }
 
-// ---- the walk (one wavefront) ------------------------------------------------------------------------------------------------
+// ---- the walk (one wavefront; bitmap_walk.h) ----------------------------------------------------------------------------------
 // bit pos[i] of the map for every member i of the set
-__device__ __forceinline__ void gn_set_bits(uint32_t* bm32, const int32_t* __restrict__ pos, const int32_t* __restrict__ Gi,
+__device__ __forceinline__ void gn_set_bits(unsigned long long* bm, const int32_t* __restrict__ pos, const int32_t* __restrict__ Gi,
                                             int32_t p0, int32_t k, int32_t N, int lane) {
-  for (int32_t i = lane; i < k; i += 64) {
-    const int32_t row = Gi[p0 + i];
-    if ((uint32_t)row >= (uint32_t)N) continue;
-    const int32_t b = pos[row];
-    if ((uint32_t)b < (uint32_t)N) atomicOr(&bm32[b >> 5], 1u << (b & 31));
-  }
-}
-
-// B = the weight of the set's members, by a pass over the map that adds the words' weights as the walk adds them to its base
-__device__ __forceinline__ double gn_total_weight(const unsigned long long* bm, int32_t nw64, const double* __restrict__ wp,
-                                                  int lane) {
-  double B = 0.0;
-  for (int32_t w0 = 0; w0 < nw64; w0 += 64) {
-    const unsigned long long word = bm[w0 + lane];
-    if (__ballot(word != 0ull) == 0ull) continue;
-    const int32_t pos0 = (w0 + lane) * 64;
-    double s = 0.0;
-    for (unsigned long long wd = word; wd != 0ull; wd &= wd - 1ull) s += wp[pos0 + (__ffsll((long long)wd) - 1)];
-    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
-    B += __shfl(s, 63);
-  }
-  return B;
+  walk_set_bits(bm, Gi, p0, k, N, lane, [&](int32_t row) { return pos[row]; });
 }
 
 // where the walk met its extremes (the leading edge): t_top the smallest t with after_t == maxP, t_bot the smallest t with
@@ -163,51 +135,22 @@ __device__ __forceinline__ double gn_walk(unsigned long long* bm, int32_t nw64, 
                                           int32_t N, int32_t k, bool clear, int lane, uint32_t* prefix = nullptr,
                                           GnExtremes* ex = nullptr) {
   const double dmiss = (double)(N - k);
-  uint32_t tbase = 0u;     // members in the words already walked
-  double cwbase = 0.0;     // their weight
-  double mxp = -INFINITY, mnp = INFINITY;
+  double mxp = -INFINITY, mnp = INFINITY;   // no pos >= 2 rule: before_1 = 0 takes part
   uint32_t tmx = 0xffffffffu, tmn = 0xffffffffu;   // (EDGE) a lane's t only grows, so a strict update keeps its first
-  for (int32_t w0 = 0; w0 < nw64; w0 += 64) {
-    unsigned long long word = bm[w0 + lane];
-    if (__ballot(word != 0ull) == 0ull) continue;
-    if (clear) bm[w0 + lane] = 0ull;
-    const uint32_t cnt = (uint32_t)__popcll(word);
-    const uint32_t incl = wave_incl_scan_u32(cnt);
-    uint32_t t = tbase + incl - cnt;
-    tbase += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if constexpr (EDGE) prefix[w0 + lane] = t;
-    const int32_t pos0 = (w0 + lane) * 64;   // position - 1 of the word's bit 0
-    double cw = 0.0;
-    if (WEIGHTED) {
-      double s = 0.0;
-      for (unsigned long long wd = word; wd != 0ull; wd &= wd - 1ull) s += wp[pos0 + (__ffsll((long long)wd) - 1)];
-      double inc = s;   // inclusive prefix sum over the lanes
-      for (int o = 1; o < 64; o <<= 1) {
-        const double up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-      }
-      const double excl = __shfl_up(inc, 1);
-      cw = cwbase + (lane == 0 ? 0.0 : excl);
-      cwbase += __shfl(inc, 63);
+  if constexpr (EDGE) __builtin_assume(prefix != nullptr);
+  const uint32_t members = walk_scan<WEIGHTED>(bm, nw64, wp, clear, lane, EDGE ? prefix : nullptr,
+                                               [&](int32_t pos, uint32_t t, double cwprev, double cwt) {
+    const double miss = (double)(pos - (int32_t)t) / dmiss;
+    const double before = cwprev / B - miss;
+    const double after = cwt / B - miss;
+    if constexpr (EDGE) {
+      if (before < mnp) { mnp = before; tmn = t; }
+      if (after > mxp) { mxp = after; tmx = t; }
+    } else {
+      mnp = before < mnp ? before : mnp;
+      mxp = after > mxp ? after : mxp;
     }
-    for (; word != 0ull; word &= word - 1ull) {
-      const int32_t pos = pos0 + __ffsll((long long)word);   // p_t
-      const double cwprev = WEIGHTED ? cw : (double)t;
-      t += 1u;
-      if (WEIGHTED) cw += wp[pos - 1];
-      const double cwt = WEIGHTED ? cw : (double)t;
-      const double miss = (double)(pos - (int32_t)t) / dmiss;
-      const double before = cwprev / B - miss;
-      const double after = cwt / B - miss;
-      if constexpr (EDGE) {
-        if (before < mnp) { mnp = before; tmn = t; }
-        if (after > mxp) { mxp = after; tmx = t; }
-      } else {
-        mnp = before < mnp ? before : mnp;
-        mxp = after > mxp ? after : mxp;
-      }
-    }
-  }
+  });
   if constexpr (EDGE) {
     // lanes own different words and the outer loop different chunks of 64 words, so equal values can sit in any two
     // lanes: the tie is settled here, by t, and every lane ends with the same pair
@@ -221,7 +164,7 @@ __device__ __forceinline__ double gn_walk(unsigned long long* bm, int32_t nw64, 
     ex->minP = mnp;
     ex->t_top = tmx;
     ex->t_bot = tmn;
-    ex->members = tbase;
+    ex->members = members;
   } else {
     for (int o = 32; o >= 1; o >>= 1) {   // (an extreme the score type does not read is dropped by the compiler)
       const double a = __shfl_xor(mxp, o), b = __shfl_xor(mnp, o);
@@ -239,7 +182,7 @@ template <bool WEIGHTED, int ST>
 __device__ __forceinline__ double gn_score(unsigned long long* bm, int32_t nw64, const double* __restrict__ wp, int32_t N,
                                            int32_t k, bool clear, int lane) {
   if (WEIGHTED) {
-    const double B = gn_total_weight(bm, nw64, wp, lane);
+    const double B = walk_total_weight(bm, nw64, wp, lane);
     if (B != 0.0) return gn_walk<true, ST>(bm, nw64, wp, B, N, k, clear, lane);
   }
   return gn_walk<false, ST>(bm, nw64, wp, (double)k, N, k, clear, lane);
@@ -250,7 +193,7 @@ template <bool WEIGHTED>
 __device__ __forceinline__ void gn_extremes(unsigned long long* bm, int32_t nw64, const double* __restrict__ wp, int32_t N,
                                             int32_t k, int lane, uint32_t* prefix, GnExtremes* ex) {
   if (WEIGHTED) {
-    const double B = gn_total_weight(bm, nw64, wp, lane);
+    const double B = walk_total_weight(bm, nw64, wp, lane);
     if (B != 0.0) {
       gn_walk<true, PLAIDHIP_GSEA_STD, true>(bm, nw64, wp, B, N, k, false, lane, prefix, ex);
       return;
@@ -268,8 +211,8 @@ gsea_obs_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__ 
   extern __shared__ unsigned long long gn_map[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long* bm = gn_map + (size_t)wave * nw64;
-  for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
-  gn_wave_sync();
+  walk_zero_map(bm, nw64, lane);
+  walk_wave_sync();
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int64_t pairs = (int64_t)m * c;
   for (int64_t e = (int64_t)blockIdx.x * kGnWaves + wave; e < pairs; e += (int64_t)gridDim.x * kGnWaves) {
@@ -279,11 +222,11 @@ gsea_obs_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__ 
       if (lane == 0) ES[e] = nan;
       continue;
     }
-    gn_set_bits(reinterpret_cast<uint32_t*>(bm), pos_obs + (int64_t)l * N, Gi, p0, k, N, lane);
-    gn_wave_sync();
+    gn_set_bits(bm, pos_obs + (int64_t)l * N, Gi, p0, k, N, lane);
+    walk_wave_sync();
     const double es = gn_score<WEIGHTED, ST>(bm, nw64, Wpos + (int64_t)l * N, N, k, true, lane);
     if (lane == 0) ES[e] = es;
-    gn_wave_sync();   // the cleared words before the next pair's bits
+    walk_wave_sync();   // the cleared words before the next pair's bits
   }
 }
 
@@ -303,8 +246,8 @@ gsea_edge_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long* bm = gn_map + (size_t)wave * nw64;
   uint32_t* prefix = reinterpret_cast<uint32_t*>(gn_map + (size_t)kGnWaves * nw64) + (size_t)wave * nw64;
-  for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
-  gn_wave_sync();
+  walk_zero_map(bm, nw64, lane);
+  walk_wave_sync();
   const int32_t nnz = Gp[m];
   const int64_t pairs = (int64_t)m * c;
   for (int64_t e = (int64_t)blockIdx.x * kGnWaves + wave; e < pairs; e += (int64_t)gridDim.x * kGnWaves) {
@@ -321,11 +264,11 @@ gsea_edge_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__
       continue;
     }
     const int32_t* pos = pos_obs + (int64_t)l * N;
-    gn_set_bits(reinterpret_cast<uint32_t*>(bm), pos, Gi, p0, k, N, lane);
-    gn_wave_sync();
+    gn_set_bits(bm, pos, Gi, p0, k, N, lane);
+    walk_wave_sync();
     GnExtremes ex;
     gn_extremes<WEIGHTED>(bm, nw64, Wpos + (int64_t)l * N, N, k, lane, prefix, &ex);
-    gn_wave_sync();   // the words' counts before other lanes read them
+    walk_wave_sync();   // the words' counts before other lanes read them
     const bool top = score_type == PLAIDHIP_GSEA_POS || (score_type == PLAIDHIP_GSEA_STD && ex.maxP > -ex.minP);
     const bool bot = score_type == PLAIDHIP_GSEA_NEG || (score_type == PLAIDHIP_GSEA_STD && ex.maxP < -ex.minP);
     const uint32_t kk = ex.members;   // k for a set of distinct rows in range; never more
@@ -348,9 +291,9 @@ gsea_edge_kernel(const int32_t* __restrict__ pos_obs, const double* __restrict__
     }
     for (int32_t i = (int32_t)len + lane; i < k; i += 64) seg[i] = -1;
     if (lane == 0) le_len[e] = (int32_t)len;
-    gn_wave_sync();   // every lane has read the map
-    for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
-    gn_wave_sync();   // the cleared words before the next pair's bits
+    walk_wave_sync();   // every lane has read the map
+    walk_zero_map(bm, nw64, lane);
+    walk_wave_sync();   // the cleared words before the next pair's bits
   }
 }
 
@@ -367,8 +310,8 @@ gsea_null_kernel(const int32_t* __restrict__ P, int32_t nbs, const double* __res
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long* bm = gn_map + (size_t)wave * nw64;
   double* s_es = reinterpret_cast<double*>(gn_map + (size_t)kGnWaves * nw64);   // [list of the tile][64]
-  for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
-  gn_wave_sync();
+  walk_zero_map(bm, nw64, lane);
+  walk_wave_sync();
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int32_t ntile = WEIGHTED ? (c + kGnListTile - 1) / kGnListTile : 1;
   const int32_t nblk = (nbs + kGnBlock - 1) / kGnBlock;
@@ -387,8 +330,8 @@ gsea_null_kernel(const int32_t* __restrict__ P, int32_t nbs, const double* __res
     for (int32_t pi = wave; pi < nb; pi += kGnWaves) {   // (pi is uniform in the wavefront)
       const int32_t col = blk * kGnBlock + pi;
       if (valid) {
-        gn_set_bits(reinterpret_cast<uint32_t*>(bm), P + (int64_t)col * N, Gi, p0, k, N, lane);
-        gn_wave_sync();
+        gn_set_bits(bm, P + (int64_t)col * N, Gi, p0, k, N, lane);
+        walk_wave_sync();
       }
       for (int32_t li = 0; li < nwalk; ++li) {
         const int32_t l = l0 + li;
@@ -397,11 +340,11 @@ gsea_null_kernel(const int32_t* __restrict__ P, int32_t nbs, const double* __res
         if (valid && (!WEIGHTED || listnan[l] == 0u)) {
           es = gn_score<WEIGHTED, ST>(bm, nw64, WEIGHTED ? Wpos + (int64_t)l * N : nullptr, N, k, last, lane);
         } else if (valid && last) {
-          for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
+          walk_zero_map(bm, nw64, lane);
         }
         if (lane == 0) s_es[li * kGnBlock + pi] = es;
       }
-      gn_wave_sync();   // the cleared words before the next permutation's bits
+      walk_wave_sync();   // the cleared words before the next permutation's bits
     }
     __syncthreads();
     // ---- the block's six partials of every list, sequentially in b; the null scores themselves when asked for -----------
@@ -476,7 +419,12 @@ gsea_null_reduce_kernel(const double* __restrict__ part, int32_t nblk, const dou
   }
 }
 
-inline int32_t gn_map_words(int32_t g) { return (int32_t)((((int64_t)g + 63) / 64 + 63) / 64 * 64); }
+constexpr const char* kGnTooManyGenes = "gsea: %d genes (the walk's bitmap takes at most %d)";
+
+// one wavefront per (set, list) pair
+WalkLaunch gn_pair_launch(plaidhip_ctx* ctx, int32_t g, int64_t pairs, int extra) {
+  return walk_launch((pairs + kGnWaves - 1) / kGnWaves, (int64_t)ctx->num_cu * 16, kGnWaves, g, extra);
+}
 
 }  // namespace
 
@@ -507,10 +455,7 @@ int launch_gsea_placements(plaidhip_ctx* ctx, int32_t g, int64_t b0, int32_t nb,
 
 int launch_gsea_check_perm(plaidhip_ctx* ctx, const int32_t* P, int32_t g, int32_t nb, int32_t col0, uint32_t* bad) {
   if (g == 0 || nb == 0) return PLAIDHIP_OK;
-  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
+  if (const int rc = check_walk_genes(kGnTooManyGenes, g)) return rc;
   hipLaunchKernelGGL(gsea_check_perm_kernel, dim3((unsigned)std::min(nb, ctx->num_cu * 8)), dim3(256), 0, ctx->stream, P, g, nb,
                      col0, bad);
   PH_HIP(hipGetLastError());
@@ -520,17 +465,11 @@ int launch_gsea_check_perm(plaidhip_ctx* ctx, const int32_t* P, int32_t g, int32
 int launch_gsea_obs(plaidhip_ctx* ctx, int weighted, int score_type, const int32_t* pos_obs, const double* Wpos,
                     const uint32_t* listnan, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* ES) {
   if ((int64_t)m * c == 0) return PLAIDHIP_OK;
-  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
-  const int32_t nw64 = gn_map_words(g);
-  const size_t shmem = (size_t)kGnWaves * nw64 * 8;   // at most 64 KB
-  const int64_t pairs = (int64_t)m * c;
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pairs + kGnWaves - 1) / kGnWaves, (int64_t)ctx->num_cu * 16));
+  if (const int rc = check_walk_genes(kGnTooManyGenes, g)) return rc;
+  const WalkLaunch wl = gn_pair_launch(ctx, g, (int64_t)m * c, 0);
 #define PH_GSEA_OBS(W, ST)                                                                                                     \
-  hipLaunchKernelGGL((gsea_obs_kernel<W, ST>), dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, \
-                     c, Gp, Gi, m, ES, nw64)
+  hipLaunchKernelGGL((gsea_obs_kernel<W, ST>), dim3(wl.blocks), dim3(64 * kGnWaves), wl.shmem, ctx->stream, pos_obs, Wpos, listnan, g, \
+                     c, Gp, Gi, m, ES, wl.nw64)
   if (weighted) {
     if (score_type == PLAIDHIP_GSEA_POS) PH_GSEA_OBS(true, PLAIDHIP_GSEA_POS);
     else if (score_type == PLAIDHIP_GSEA_NEG) PH_GSEA_OBS(true, PLAIDHIP_GSEA_NEG);
@@ -549,22 +488,16 @@ int launch_gsea_edges(plaidhip_ctx* ctx, int weighted, int score_type, const int
                       const uint32_t* listnan, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
                       int32_t* le_len, int32_t* le_idx) {
   if ((int64_t)m * c == 0) return PLAIDHIP_OK;
-  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
-  const int32_t nw64 = gn_map_words(g);
-  const size_t shmem = (size_t)kGnWaves * nw64 * 12;   // the maps and the words' counts: at most 96 KB
-  const int64_t pairs = (int64_t)m * c;
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pairs + kGnWaves - 1) / kGnWaves, (int64_t)ctx->num_cu * 16));
+  if (const int rc = check_walk_genes(kGnTooManyGenes, g)) return rc;
+  const WalkLaunch wl = gn_pair_launch(ctx, g, (int64_t)m * c, 4);   // the maps and the words' counts: at most 96 KB
   if (weighted) {
     PH_FULL_LDS(ctx, gsea_edge_kernel<true>);
-    hipLaunchKernelGGL(gsea_edge_kernel<true>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
-                       Gp, Gi, m, score_type, le_len, le_idx, nw64);
+    hipLaunchKernelGGL(gsea_edge_kernel<true>, dim3(wl.blocks), dim3(64 * kGnWaves), wl.shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
+                       Gp, Gi, m, score_type, le_len, le_idx, wl.nw64);
   } else {
     PH_FULL_LDS(ctx, gsea_edge_kernel<false>);
-    hipLaunchKernelGGL(gsea_edge_kernel<false>, dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
-                       Gp, Gi, m, score_type, le_len, le_idx, nw64);
+    hipLaunchKernelGGL(gsea_edge_kernel<false>, dim3(wl.blocks), dim3(64 * kGnWaves), wl.shmem, ctx->stream, pos_obs, Wpos, listnan, g, c,
+                       Gp, Gi, m, score_type, le_len, le_idx, wl.nw64);
   }
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
@@ -574,20 +507,16 @@ int launch_gsea_null(plaidhip_ctx* ctx, int weighted, int score_type, const int3
                      const uint32_t* listnan, const double* ES, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
                      int32_t m, double* part, int64_t blk_at0, double* null_out) {
   if ((int64_t)m * c == 0 || nbs == 0) return PLAIDHIP_OK;
-  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("gsea: %d genes (the walk's bitmap takes at most %d)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
-  const int32_t nw64 = gn_map_words(g);
-  const size_t shmem = (size_t)kGnWaves * nw64 * 8 + (size_t)kGnListTile * kGnBlock * 8;   // at most 68 KB
+  if (const int rc = check_walk_genes(kGnTooManyGenes, g)) return rc;
   const int32_t ntile = weighted ? (c + kGnListTile - 1) / kGnListTile : 1;
   const int64_t tasks = (int64_t)m * ntile * ((nbs + kGnBlock - 1) / kGnBlock);
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tasks, (int64_t)ctx->num_cu * 16));
+  const WalkLaunch wl = walk_launch(tasks, (int64_t)ctx->num_cu * 16, kGnWaves, g);
+  const size_t shmem = wl.shmem + (size_t)kGnListTile * kGnBlock * 8;   // the maps and a tile's null scores: at most 68 KB
 #define PH_GSEA_NULL(W, ST)                                                                                                   \
   do {                                                                                                                        \
     PH_FULL_LDS(ctx, (gsea_null_kernel<W, ST>));                                                                              \
-    hipLaunchKernelGGL((gsea_null_kernel<W, ST>), dim3(blocks), dim3(64 * kGnWaves), shmem, ctx->stream, P, nbs, Wpos, listnan, \
-                       ES, g, c, Gp, Gi, m, part, blk_at0, null_out, nw64);                                                   \
+    hipLaunchKernelGGL((gsea_null_kernel<W, ST>), dim3(wl.blocks), dim3(64 * kGnWaves), shmem, ctx->stream, P, nbs, Wpos, listnan, \
+                       ES, g, c, Gp, Gi, m, part, blk_at0, null_out, wl.nw64);                                                   \
   } while (0)
   if (weighted) {
     if (score_type == PLAIDHIP_GSEA_POS) PH_GSEA_NULL(true, PLAIDHIP_GSEA_POS);

@@ -13,6 +13,7 @@
 // (R: NA stays NA) and do not disturb the ranks of the others.
 #include "common.h"
 #include "device_sort.h"
+#include "exact_common.h"
 #include "rank_bucket.h"
 
 namespace plaidhip {
@@ -763,72 +764,53 @@ static int launch_colranks_partitioned(plaidhip_ctx* ctx, const double* X, int64
 // y is exact in a double (lb, i < 2^26).  NaN inputs stay NaN through every pass.  Signed: the ranks of |x|, signed at the
 // end.  These methods are off the hot path (plaid's own callers use "average" and "min" only): 2 - 3 passes of the fast
 // kernels plus element-wise kernels, any column length the rank kernels take.
-constexpr double kTieShift = 67108864.0;   // 2^26
-
-struct TieCols {   // columns of a dense matrix (Xp == nullptr) or the stored values of CSC columns
-  const int32_t* Xp;
-  int32_t g, n;
-  int64_t ldx, ldr, lds;   // leading dimensions of X, R and of the scratch columns
-};
-
-template <typename F>
-__device__ __forceinline__ void tie_for_each(const TieCols& t, F f) {
-  for (int c = blockIdx.y; c < t.n; c += gridDim.y) {
-    int64_t xb, rb, sb;
-    int32_t cnt;
-    if (t.Xp != nullptr) { xb = rb = sb = t.Xp[c]; cnt = t.Xp[c + 1] - t.Xp[c]; }
-    else { xb = (int64_t)c * t.ldx; rb = (int64_t)c * t.ldr; sb = (int64_t)c * t.lds; cnt = t.g; }
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) f(xb + i, rb + i, sb, i, cnt);
-  }
-}
-
 // A = lb (NaN for a NaN input), B = the tie-free column y.  R holds sign * min rank of |x| (signed) or the min rank.
 __global__ void __launch_bounds__(256)
-tie_prep_kernel(TieCols t, const double* __restrict__ X, const double* __restrict__ R, int is_signed, int last,
+tie_prep_kernel(RankCols t, const double* __restrict__ X, const double* __restrict__ R, int is_signed, int last,
                 double* __restrict__ A, double* __restrict__ B) {
-  tie_for_each(t, [&](int64_t xi, int64_t ri, int64_t sb, int32_t i, int32_t cnt) {
-    const double x = X[xi], r = R[ri];
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double x = X[it.x], r = R[it.r];
     // signed ranks are 0 at x == 0, whose |x| is the smallest value of the column: lb = 0
     const double lb = (r != r) ? r : ((is_signed && x == 0.0) ? 0.0 : fabs(r) - 1.0);
-    A[sb + i] = lb;
-    B[sb + i] = lb * kTieShift + (double)(last ? cnt - 1 - i : i);
+    A[it.s] = lb;
+    B[it.s] = lb * kTieFreeShift + (double)(last ? it.cnt - 1 - it.i : it.i);
   });
 }
 
 // first / last: R holds the min rank of y = the wanted rank of |x| (or x); signed: put the sign on
 __global__ void __launch_bounds__(256)
-tie_sign_kernel(TieCols t, const double* __restrict__ X, double* __restrict__ R) {
-  tie_for_each(t, [&](int64_t xi, int64_t ri, int64_t, int32_t, int32_t) {
-    const double x = X[xi], r = R[ri];
-    R[ri] = (x == 0.0) ? 0.0 : ((x < 0.0) ? -r : r);   // (NaN: neither branch, r is NaN already)
+tie_sign_kernel(RankCols t, const double* __restrict__ X, double* __restrict__ R) {
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double x = X[it.x], r = R[it.r];
+    R[it.r] = (x == 0.0) ? 0.0 : ((x < 0.0) ? -r : r);   // (NaN: neither branch, r is NaN already)
   });
 }
 
 // dense, step 1: R holds first ranks, A the lower bounds: B = lb at the leaders, NaN elsewhere
 __global__ void __launch_bounds__(256)
-tie_leader_kernel(TieCols t, const double* __restrict__ R, const double* __restrict__ A, double* __restrict__ B) {
-  tie_for_each(t, [&](int64_t, int64_t ri, int64_t sb, int32_t i, int32_t) {
-    const double lb = A[sb + i];
-    B[sb + i] = (R[ri] == lb + 1.0) ? lb : __longlong_as_double(0x7ff8000000000000ll);
+tie_leader_kernel(RankCols t, const double* __restrict__ R, const double* __restrict__ A, double* __restrict__ B) {
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double lb = A[it.s];
+    B[it.s] = (R[it.r] == lb + 1.0) ? lb : __longlong_as_double(0x7ff8000000000000ll);
   });
 }
 // step 2: R holds the dense rank at the leaders (NaN elsewhere): leave it at slot lb of the scratch column
 __global__ void __launch_bounds__(256)
-tie_scatter_kernel(TieCols t, const double* __restrict__ R, const double* __restrict__ A, double* __restrict__ B) {
-  tie_for_each(t, [&](int64_t, int64_t ri, int64_t sb, int32_t i, int32_t) {
-    const double d = R[ri];
-    if (d == d) B[sb + (int64_t)A[sb + i]] = d;
+tie_scatter_kernel(RankCols t, const double* __restrict__ R, const double* __restrict__ A, double* __restrict__ B) {
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double d = R[it.r];
+    if (d == d) B[it.s - it.i + (int64_t)A[it.s]] = d;
   });
 }
 // step 3: every member reads its group's slot
 __global__ void __launch_bounds__(256)
-tie_gather_kernel(TieCols t, const double* __restrict__ X, const double* __restrict__ A, const double* __restrict__ B,
+tie_gather_kernel(RankCols t, const double* __restrict__ X, const double* __restrict__ A, const double* __restrict__ B,
                   int is_signed, double* __restrict__ R) {
-  tie_for_each(t, [&](int64_t xi, int64_t ri, int64_t sb, int32_t i, int32_t) {
-    const double lb = A[sb + i], x = X[xi];
-    double r = (lb != lb) ? lb : B[sb + (int64_t)lb];
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double lb = A[it.s], x = X[it.x];
+    double r = (lb != lb) ? lb : B[it.s - it.i + (int64_t)lb];
     if (is_signed) r = (x == 0.0) ? 0.0 : ((x < 0.0) ? -r : r);
-    R[ri] = r;
+    R[it.r] = r;
   });
 }
 
@@ -853,8 +835,8 @@ static int launch_colranks_composed(plaidhip_ctx* ctx, const double* X, int64_t 
     if (Xp != nullptr) return launch_colranks_csc_f64(ctx, Xp, V, n, max_len, PLAIDHIP_TIES_MIN, sgn, 1.0, Out, nullptr);
     return launch_colranks_dense_f64(ctx, V, ldv, g, n, PLAIDHIP_TIES_MIN, sgn, 1.0, Out, ldo, nullptr);
   };
-  TieCols t{Xp, g, n, ldx, ldr, lds};
-  const dim3 grid((unsigned)std::min<int64_t>(((int64_t)max_len + 255) / 256, 64), (unsigned)std::min(n, 16384));
+  const RankCols t{Xp, g, n, ldx, ldr, lds};
+  const dim3 grid = rank_cols_grid(t);
   int rc = ranks_min(X, ldx, is_signed, R, ldr);                                  // lb + 1 (with the sign when signed)
   if (rc != PLAIDHIP_OK) return rc;
   hipLaunchKernelGGL(tie_prep_kernel, grid, dim3(256), 0, ctx->stream, t, X, R, is_signed, ties == PLAIDHIP_TIES_LAST ? 1 : 0, A, B);
@@ -869,6 +851,45 @@ static int launch_colranks_composed(plaidhip_ctx* ctx, const double* X, int64_t 
     hipLaunchKernelGGL(tie_scatter_kernel, grid, dim3(256), 0, ctx->stream, t, R, A, B);
     hipLaunchKernelGGL(tie_gather_kernel, grid, dim3(256), 0, ctx->stream, t, X, A, B, is_signed, R);
   }
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+// ---- rank(x, "last") from ranks that are already there, and the NaN flags of columns (the exact scorers) ------------------
+// the tie-free column y = (2 r - 1) * 2^26 + (cnt - 1 - i) from min or average ranks r: the tie groups keep their order
+// (2 r - 1 is an integer that grows with r either way) and a group's rows come last-first, so the min ranks of y are the
+// last ranks.  A NaN stays NaN; exact for cnt < 2^26, with or without contraction.
+__global__ void __launch_bounds__(256)
+last_prep_kernel(RankCols t, const double* __restrict__ R, double* __restrict__ Y) {
+  for_each_rank_item(t, [&](const RankItem& it) {
+    Y[it.r] = (2.0 * R[it.r] - 1.0) * kTieFreeShift + (double)(it.cnt - 1 - it.i);
+  });
+}
+
+// colnan[c] = 1 for a column holding a NaN
+__global__ void __launch_bounds__(256)
+colnan_kernel(RankCols t, const double* __restrict__ X, uint32_t* __restrict__ colnan) {
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double v = X[it.x];
+    if (v != v) colnan[it.c] = 1u;
+  });
+}
+
+int launch_last_ranks(plaidhip_ctx* ctx, const RankCols& cols, const double* R, double* Y, double* Q) {
+  if (cols.n == 0 || cols.g == 0) return PLAIDHIP_OK;
+  hipLaunchKernelGGL(last_prep_kernel, rank_cols_grid(cols), dim3(256), 0, ctx->stream, cols, R, Y);
+  PH_HIP(hipGetLastError());
+  if (cols.Xp != nullptr) return launch_colranks_csc_f64(ctx, cols.Xp, Y, cols.n, cols.g, PLAIDHIP_TIES_MIN, 0, 1.0, Q, nullptr);
+  return launch_colranks_dense_f64(ctx, Y, cols.ldr, cols.g, cols.n, PLAIDHIP_TIES_MIN, 0, 1.0, Q, cols.ldr, nullptr);
+}
+
+int launch_colnan(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, int32_t g, int32_t n,
+                  int32_t max_col_nnz, uint32_t* colnan) {
+  if (n == 0) return PLAIDHIP_OK;
+  PH_HIP(hipMemsetAsync(colnan, 0, (size_t)n * 4, ctx->stream));
+  const RankCols t = Xp != nullptr ? csc_cols(Xp, max_col_nnz, n) : dense_cols(g, n, ldx);
+  if (t.g <= 0) return PLAIDHIP_OK;
+  hipLaunchKernelGGL(colnan_kernel, rank_cols_grid(t), dim3(256), 0, ctx->stream, t, X, colnan);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

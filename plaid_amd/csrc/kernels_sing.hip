@@ -6,7 +6,7 @@
 //
 // The dispersion is a median of absolute deviations from a median per (set, column) pair: not a crossprod and not a walk
 // extremum.  sing_mad_kernel takes the workgroup, tile and task order of kernels_ks.hip: ONE wavefront per pair sets the
-// members' bits in an N-bit map in LDS, for every set size 0..N, without a sort.
+// members' bits in an N-bit map in LDS (bitmap_walk.h), for every set size 0..N, without a sort.
 //   * Min ranks tie, so the map is set over the tie-free last ranks q (bit q - 1); the order by q is an order by r.  Rpos,
 //     built once per column and shared by all sets, gives r by position: Rpos[q - 1] = r (u32).
 //   * One pass over the map leaves the number of members in each run of 64 words (a lane per run: at most 32 runs at
@@ -22,8 +22,8 @@
 // Cost per pair: k atomics, 2 N / 64 LDS words, about 2 log2(k) + 6 dependent gathers from Rpos.
 #include <algorithm>
 
-#include "common.h"
-#include "rank_bucket.h"
+#include "bitmap_walk.h"
+#include "exact_common.h"
 
 namespace plaidhip {
 
@@ -31,40 +31,6 @@ namespace {
 
 constexpr int kMadWaves = 4;       // wavefronts per workgroup, one (set, column) pair each at a time
 constexpr int kMadColTile = 16;    // sample columns a workgroup takes for one set before it moves to the next set
-constexpr double kSingShift = 67108864.0;   // 2^26: (r, i) -> one exact double for r <= g, i < g <= 2^17
-
-__device__ __forceinline__ void mad_wave_sync() {   // LDS written by the wavefront's lanes is read by its other lanes
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// colnan[c] = 1 for a column holding a NaN: the g rows of a dense column (Xp == nullptr) or the stored values of a CSC one
-__global__ void __launch_bounds__(256)
-sing_colnan_kernel(const double* __restrict__ X, int64_t ldx, const int32_t* __restrict__ Xp, int32_t g, int32_t n,
-                   uint32_t* __restrict__ colnan) {
-  for (int c = blockIdx.y; c < n; c += gridDim.y) {
-    const int64_t b = Xp != nullptr ? (int64_t)Xp[c] : (int64_t)c * ldx;
-    const int32_t cnt = Xp != nullptr ? Xp[c + 1] - Xp[c] : g;
-    bool bad = false;
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) {
-      const double v = X[b + i];
-      bad = bad || v != v;
-    }
-    if (bad) colnan[c] = 1u;
-  }
-}
-
-// the tie-free column whose min ranks are the last ranks: y = r * 2^26 + (g - 1 - i), exact (r <= g <= 2^17), with or
-// without contraction; the rows of a tie group come last-first
-__global__ void __launch_bounds__(256)
-sing_prep_kernel(const double* __restrict__ R, int64_t ld, int32_t g, int32_t n, double* __restrict__ Y) {
-  for (int c = blockIdx.y; c < n; c += gridDim.y) {
-    const int64_t b = (int64_t)c * ld;
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < g; i += gridDim.x * blockDim.x)
-      Y[b + i] = R[b + i] * kSingShift + (double)(g - 1 - i);
-  }
-}
 
 // Rpos[q - 1] = r of every row of a column (u32, leading dimension ldp).  A column holding a NaN is skipped (its q are
 // no permutation; sing_mad_kernel never reads its Rpos); a q outside 1..g is never followed.
@@ -89,10 +55,7 @@ sing_score_kernel(double* __restrict__ Cu, double* __restrict__ Cd, double* __re
                   const int32_t* __restrict__ ku, const int32_t* __restrict__ kd, int64_t N, int center,
                   const uint32_t* __restrict__ colnan) {
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  const int64_t total = (int64_t)m * n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = e / m, j = e - c * m;
-    const int64_t at = c * lds + j;
+  for_each_score(m, n, lds, [&](int64_t c, int64_t j, int64_t at) {
     const bool bad = colnan[c] != 0u;
     double up, dn = 0.0;
     {
@@ -116,18 +79,14 @@ sing_score_kernel(double* __restrict__ Cu, double* __restrict__ Cd, double* __re
       Cd[at] = dn;
       if (tot != nullptr) tot[at] = up + dn;
     }
-  }
+  });
 }
 
 // out = a + b over m x n (the total dispersion), one add
 __global__ void __launch_bounds__(256)
 sing_add_kernel(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ out, int64_t lds, int32_t m,
                 int32_t n) {
-  const int64_t total = (int64_t)m * n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = e / m, j = e - c * m;
-    out[c * lds + j] = A[c * lds + j] + B[c * lds + j];
-  }
+  for_each_score(m, n, lds, [&](int64_t, int64_t, int64_t at) { out[at] = A[at] + B[at]; });
 }
 
 // position (bit index in the map) of the t-th member, t in 0..k-1, uniform in the wavefront.  runincl: the lane's inclusive
@@ -160,9 +119,8 @@ sing_mad_kernel(const double* __restrict__ Q, int64_t ldq, const uint32_t* __res
   extern __shared__ unsigned long long mad_map[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long* bm = mad_map + (size_t)wave * nw64;
-  uint32_t* bm32 = reinterpret_cast<uint32_t*>(bm);
-  for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
-  mad_wave_sync();
+  walk_zero_map(bm, nw64, lane);
+  walk_wave_sync();
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int nruns = nw64 / 64;
   const int64_t tiles = ((int64_t)n + kMadColTile - 1) / kMadColTile;
@@ -180,13 +138,8 @@ sing_mad_kernel(const double* __restrict__ Q, int64_t ldq, const uint32_t* __res
       }
       // ---- the members' bits ------------------------------------------------------------------------------------------------
       const double* qc = Q + (int64_t)c * ldq;
-      for (int32_t i = lane; i < kk; i += 64) {
-        const int32_t row = Gi[p0 + i];
-        if ((uint32_t)row >= (uint32_t)N) continue;
-        const int32_t b = (int32_t)qc[row] - 1;
-        if ((uint32_t)b < (uint32_t)N) atomicOr(&bm32[b >> 5], 1u << (b & 31));
-      }
-      mad_wave_sync();
+      walk_set_bits(bm, Gi, p0, kk, N, lane, [&](int32_t row) { return (int32_t)qc[row] - 1; });
+      walk_wave_sync();
       // ---- members per run of 64 words: lane `run` keeps the run's count --------------------------------------------------
       uint32_t runcnt = 0u;
       for (int run = 0; run < nruns; ++run) {
@@ -239,45 +192,18 @@ sing_mad_kernel(const double* __restrict__ Q, int64_t ldq, const uint32_t* __res
       }
       if (lane == 0) *out = 1.4826 * ((double)md4 * 0.25);
       // ---- the map back to zero -----------------------------------------------------------------------------------------------
-      for (int32_t i = lane; i < nw64; i += 64) bm[i] = 0ull;
-      mad_wave_sync();
+      walk_zero_map(bm, nw64, lane);
+      walk_wave_sync();
     }
   }
 }
 
-dim3 sing_grid(int32_t g, int32_t n) {
-  return dim3((unsigned)std::min<int64_t>(((int64_t)g + 255) / 256, 64), (unsigned)std::min(n, 16384));
-}
-
-int sing_blocks(plaidhip_ctx* ctx, int64_t count) {
-  const int64_t b = (count + 255) / 256, cap = (int64_t)ctx->num_cu * 4;
-  return (int)std::max<int64_t>(1, std::min(b, cap));
-}
-
 }  // namespace
-
-int launch_sing_colnan(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, int32_t g, int32_t n,
-                       int32_t max_col_nnz, uint32_t* colnan) {
-  if (n == 0) return PLAIDHIP_OK;
-  PH_HIP(hipMemsetAsync(colnan, 0, (size_t)n * 4, ctx->stream));
-  const int32_t len = Xp != nullptr ? max_col_nnz : g;
-  if (len <= 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(sing_colnan_kernel, sing_grid(len, n), dim3(256), 0, ctx->stream, X, ldx, Xp, g, n, colnan);
-  PH_HIP(hipGetLastError());
-  return PLAIDHIP_OK;
-}
-
-int launch_sing_last_ranks(plaidhip_ctx* ctx, const double* R, int64_t ld, int32_t g, int32_t n, double* Y, double* Q) {
-  if (n == 0 || g == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(sing_prep_kernel, sing_grid(g, n), dim3(256), 0, ctx->stream, R, ld, g, n, Y);
-  PH_HIP(hipGetLastError());
-  return launch_colranks_dense_f64(ctx, Y, ld, g, n, PLAIDHIP_TIES_MIN, 0, 1.0, Q, ld, nullptr);
-}
 
 int launch_sing_rpos(plaidhip_ctx* ctx, const double* R, const double* Q, int64_t ld, const uint32_t* colnan, int32_t g,
                      int32_t n, uint32_t* Rpos, int64_t ldp) {
   if (n == 0 || g == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(sing_rpos_kernel, sing_grid(g, n), dim3(256), 0, ctx->stream, R, Q, ld, colnan, g, n, Rpos, ldp);
+  hipLaunchKernelGGL(sing_rpos_kernel, rank_cols_grid(dense_cols(g, n, ld)), dim3(256), 0, ctx->stream, R, Q, ld, colnan, g, n, Rpos, ldp);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
@@ -285,7 +211,7 @@ int launch_sing_rpos(plaidhip_ctx* ctx, const double* R, const double* Q, int64_
 int launch_sing_score(plaidhip_ctx* ctx, double* Cu, double* Cd, double* tot, int64_t lds, int32_t m, int32_t n,
                       const int32_t* ku, const int32_t* kd, int32_t g, int center, const uint32_t* colnan) {
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(sing_score_kernel, dim3(sing_blocks(ctx, (int64_t)m * n)), dim3(256), 0, ctx->stream, Cu, Cd, tot, lds, m, n,
+  hipLaunchKernelGGL(sing_score_kernel, dim3(score_part_blocks(ctx, (int64_t)m * n)), dim3(256), 0, ctx->stream, Cu, Cd, tot, lds, m, n,
                      ku, kd, (int64_t)g, center, colnan);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
@@ -293,7 +219,7 @@ int launch_sing_score(plaidhip_ctx* ctx, double* Cu, double* Cd, double* tot, in
 
 int launch_sing_add(plaidhip_ctx* ctx, const double* A, const double* B, double* out, int64_t lds, int32_t m, int32_t n) {
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(sing_add_kernel, dim3(sing_blocks(ctx, (int64_t)m * n)), dim3(256), 0, ctx->stream, A, B, out, lds, m, n);
+  hipLaunchKernelGGL(sing_add_kernel, dim3(score_part_blocks(ctx, (int64_t)m * n)), dim3(256), 0, ctx->stream, A, B, out, lds, m, n);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
@@ -301,16 +227,10 @@ int launch_sing_add(plaidhip_ctx* ctx, const double* A, const double* B, double*
 int launch_sing_mad(plaidhip_ctx* ctx, const double* Q, int64_t ldq, const uint32_t* Rpos, int64_t ldp, const uint32_t* colnan,
                     int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S, int64_t lds) {
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  if (g > PLAIDHIP_GSEA_KS_MAX_GENES) {
-    set_error("sing_mad: nrow(X) = %d (the bitmap takes at most %d genes)", g, PLAIDHIP_GSEA_KS_MAX_GENES);
-    return PLAIDHIP_EUNSUPPORTED;
-  }
-  const int32_t nw64 = (int32_t)((((int64_t)g + 63) / 64 + 63) / 64 * 64);
-  const size_t shmem = (size_t)kMadWaves * nw64 * 8;   // at most 64 KB at PLAIDHIP_GSEA_KS_MAX_GENES
-  const int64_t tasks = (((int64_t)n + kMadColTile - 1) / kMadColTile) * m;
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tasks, (int64_t)ctx->num_cu * 32));
-  hipLaunchKernelGGL(sing_mad_kernel, dim3(blocks), dim3(64 * kMadWaves), shmem, ctx->stream, Q, ldq, Rpos, ldp, colnan, g, n, Gp,
-                     Gi, m, S, lds, nw64);
+  if (const int rc = check_walk_genes("sing_mad: nrow(X) = %d (the bitmap takes at most %d genes)", g)) return rc;
+  const WalkLaunch wl = walk_launch((((int64_t)n + kMadColTile - 1) / kMadColTile) * m, (int64_t)ctx->num_cu * 32, kMadWaves, g);
+  hipLaunchKernelGGL(sing_mad_kernel, dim3(wl.blocks), dim3(64 * kMadWaves), wl.shmem, ctx->stream, Q, ldq, Rpos, ldp, colnan, g, n, Gp,
+                     Gi, m, S, lds, wl.nw64);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

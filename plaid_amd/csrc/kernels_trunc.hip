@@ -31,13 +31,13 @@
 #include <algorithm>
 
 #include "common.h"
+#include "exact_common.h"
 
 namespace plaidhip {
 
 namespace {
 
 constexpr int kTruncBlock = 256;
-constexpr double kTruncShift = 67108864.0;   // 2^26
 
 // exclusive scan of one count per thread over the workgroup (NW wavefronts); *total: the sum.  s_w: NW words of LDS, free
 // to reuse when the call returns on every thread (two barriers inside).
@@ -266,18 +266,6 @@ trunc_scan_kernel(const int32_t* __restrict__ cnt, int32_t n, int32_t* __restric
   if (threadIdx.x == 0) ptr[n] = (int32_t)carry;
 }
 
-// the tie-free column whose min ranks are rank(x, "last") of the stored values of CSC columns: y = (min rank - 1) 2^26 +
-// (len - 1 - i), exact for len < 2^26
-__global__ void __launch_bounds__(256)
-trunc_last_prep_kernel(const int32_t* __restrict__ Xp, const double* __restrict__ Rmin, int32_t n, double* __restrict__ Y) {
-  for (int c = blockIdx.y; c < n; c += gridDim.y) {
-    const int64_t b = Xp[c];
-    const int32_t len = Xp[c + 1] - Xp[c];
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x)
-      Y[b + i] = (Rmin[b + i] - 1.0) * kTruncShift + (double)(len - 1 - i);
-  }
-}
-
 // ---- the pinned epilogues (include/plaidhip.h) -------------------------------------------------------------------------
 // UCell.  C holds sum (u - u0) over the aligned members (a half-integer, exact); S2 = 2 C + 2 k u0 in integers.
 __device__ __forceinline__ double ucell_exact_one(double C, double u0, int64_t k, int64_t K, int64_t T, bool bad) {
@@ -294,10 +282,7 @@ ucell_exact_kernel(double* __restrict__ Cu, double* __restrict__ Cd, double* __r
                    const int32_t* __restrict__ ku, const int32_t* __restrict__ kd, const double* __restrict__ Ku,
                    const double* __restrict__ Kd, const double* __restrict__ u0, int64_t T, double w_neg,
                    const uint32_t* __restrict__ colnan) {
-  const int64_t total = (int64_t)m * n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = e / m, j = e - c * m;
-    const int64_t at = c * lds + j;
+  for_each_score(m, n, lds, [&](int64_t c, int64_t j, int64_t at) {
     const bool bad = colnan[c] != 0u;
     const double z0 = u0 != nullptr ? u0[c] : 0.0;
     double up = 0.0;
@@ -316,7 +301,7 @@ ucell_exact_kernel(double* __restrict__ Cu, double* __restrict__ Cd, double* __r
         tot[at] = t < 0.0 ? 0.0 : t;   // (a NaN stays)
       }
     }
-  }
+  });
 }
 
 // AUCell.  C holds the area sum (A - pos), an exact integer.
@@ -324,10 +309,7 @@ __global__ void __launch_bounds__(256)
 aucell_exact_kernel(double* __restrict__ C, int64_t lds, int32_t m, int32_t n, const int32_t* __restrict__ kset, int64_t A,
                     const uint32_t* __restrict__ colnan) {
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  const int64_t total = (int64_t)m * n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = e / m, j = e - c * m;
-    const int64_t at = c * lds + j;
+  for_each_score(m, n, lds, [&](int64_t c, int64_t j, int64_t at) {
     const int64_t k = kset[j];
     const int64_t kk = k < A - 1 ? k : A - 1;
     const int64_t max_auc = kk * A - kk * (kk + 1) / 2;
@@ -335,7 +317,7 @@ aucell_exact_kernel(double* __restrict__ C, int64_t lds, int32_t m, int32_t n, c
     double s = (double)area / (double)max_auc;   // (k = 0 or A = 1: 0 / 0)
     if (colnan[c] != 0u) s = nan;
     C[at] = s;
-  }
+  });
 }
 
 }  // namespace
@@ -345,15 +327,6 @@ int64_t truncated_bound(int mode, int64_t T, int64_t g, int64_t len, bool sparse
   if (mode == 1) return std::min<int64_t>(g, T - 1);
   if (sparse) return len;                       // the shifted weights: every stored non-zero value may carry one
   return std::min<int64_t>(g, 2 * T - 1);       // the boundary tie group, whose average is <= T, ends at 2 T - 1 at most
-}
-
-int launch_truncated_last_prep(plaidhip_ctx* ctx, const int32_t* Xp, const double* Rmin, int32_t n, int32_t max_col_nnz,
-                               double* Y) {
-  if (n == 0 || max_col_nnz == 0) return PLAIDHIP_OK;
-  const dim3 grid((unsigned)std::min<int64_t>(((int64_t)max_col_nnz + 255) / 256, 64), (unsigned)std::min(n, 16384));
-  hipLaunchKernelGGL(trunc_last_prep_kernel, grid, dim3(256), 0, ctx->stream, Xp, Rmin, n, Y);
-  PH_HIP(hipGetLastError());
-  return PLAIDHIP_OK;
 }
 
 int launch_truncated_compact(plaidhip_ctx* ctx, int mode, int64_t T, const double* R, int64_t ldr, const int32_t* Xp,
@@ -420,7 +393,7 @@ int truncated_ranks_stage(plaidhip_ctx* ctx, int mode, int64_t T, const double* 
                           const int32_t* Xi, int32_t g, int32_t n, int32_t max_col_nnz, int64_t nnz, double* scratch,
                           uint32_t* colnan, int32_t* cnt, int32_t* Wp, int32_t* Wi, double* Wx, int64_t cap, double* u0) {
   if (n == 0 || g == 0) return PLAIDHIP_OK;
-  int rc = launch_sing_colnan(ctx, X, ldx, Xp, g, n, max_col_nnz, colnan);
+  int rc = launch_colnan(ctx, X, ldx, Xp, g, n, max_col_nnz, colnan);
   if (rc != PLAIDHIP_OK) return rc;
   double* R = scratch;
   if (Xp == nullptr) {
@@ -435,8 +408,7 @@ int truncated_ranks_stage(plaidhip_ctx* ctx, int mode, int64_t T, const double* 
   } else {   // rank(x, "last") of the stored values: two min-rank passes, stream-ordered (the size of Y is the caller's nnz)
     double* Y = scratch + std::max<int64_t>(nnz, 1);
     rc = launch_colranks_csc_f64(ctx, Xp, X, n, max_col_nnz, PLAIDHIP_TIES_MIN, 0, 1.0, R, nullptr);
-    if (rc == PLAIDHIP_OK) rc = launch_truncated_last_prep(ctx, Xp, R, n, max_col_nnz, Y);
-    if (rc == PLAIDHIP_OK) rc = launch_colranks_csc_f64(ctx, Xp, Y, n, max_col_nnz, PLAIDHIP_TIES_MIN, 0, 1.0, R, nullptr);
+    if (rc == PLAIDHIP_OK) rc = launch_last_ranks(ctx, csc_cols(Xp, max_col_nnz, n), R, Y, R);
   }
   if (rc != PLAIDHIP_OK) return rc;
   return launch_truncated_compact(ctx, mode, T, R, 0, Xp, Xi, X, g, n, colnan, cnt, Wp, Wi, Wx, cap, u0);

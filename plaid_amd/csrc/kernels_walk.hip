@@ -9,8 +9,7 @@
 // Operands with TWO rank passes (the rank kernels of colranks(), the only ranking code):
 //   1. R = average ranks (power 1: half-integers, exact);
 //   2. Q = min ranks of the tie-free column y_i = (2 R_i - 1) * 2^26 + (cnt - 1 - i): the tie groups keep their order
-//      and a group's rows come last-first, so these are the "last" ranks (kernels_rank.hip, launch_colranks_composed,
-//      builds ties.method = "last" the same way from min ranks);
+//      and a group's rows come last-first, so these are the "last" ranks (kernels_rank.hip: launch_last_ranks);
 //   3. element-wise: w = R^alpha with the exponent routine the rank kernel of that column length applies (pow_quarters
 //      when 4 alpha is an integer in 1..16 and the bucket / partitioned ranker takes the column, pow otherwise), P = w q.
 // A dgCMatrix is ranked on its stored values only (both passes over nnz) and expanded into dense operand columns: the
@@ -20,56 +19,28 @@
 
 #include "common.h"
 #include "device_sort.h"
+#include "exact_common.h"
 #include "rank_bucket.h"
 
 namespace plaidhip {
 
 namespace {
 
-constexpr double kWalkShift = 67108864.0;   // 2^26: (2 r - 1, i) -> one exact double for r <= cnt, i < cnt < 2^26
-
-struct WalkCols {   // columns of a dense matrix (Xp == nullptr) or the stored values of CSC columns
-  const int32_t* Xp;
-  int32_t g, n;
-  int64_t ld;       // dense: leading dimension of L / Q / the scratch columns
-};
-
-template <typename F>
-__device__ __forceinline__ void walk_for_each(const WalkCols& t, F f) {
-  for (int c = blockIdx.y; c < t.n; c += gridDim.y) {
-    int64_t b;
-    int32_t cnt;
-    if (t.Xp != nullptr) { b = t.Xp[c]; cnt = t.Xp[c + 1] - t.Xp[c]; }
-    else { b = (int64_t)c * t.ld; cnt = t.g; }
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) f(c, b, i, cnt);
-  }
-}
-
 __device__ __forceinline__ double walk_pow(double r, double power, int pow_q4) {
   return power == 1.0 ? r : (pow_q4 > 0 ? pow_quarters(r, pow_q4) : PH_POW(r, power));
 }
 
-// y = (2 r - 1) * 2^26 + (cnt - 1 - i) from the average ranks R (NaN stays NaN); exact for cnt < 2^26, with or without
-// contraction
-__global__ void __launch_bounds__(256)
-walk_prep_kernel(WalkCols t, const double* __restrict__ R, double* __restrict__ Y) {
-  walk_for_each(t, [&](int, int64_t b, int32_t i, int32_t cnt) {
-    const double r = R[b + i];
-    Y[b + i] = (2.0 * r - 1.0) * kWalkShift + (double)(cnt - 1 - i);
-  });
-}
-
 // dense columns: w = r^alpha and P = w q (need_w), the NaN flag of the column
 __global__ void __launch_bounds__(256)
-walk_finish_dense_kernel(WalkCols t, const double* __restrict__ R, const double* __restrict__ Q, int need_w, double power,
+walk_finish_dense_kernel(RankCols t, const double* __restrict__ R, const double* __restrict__ Q, int need_w, double power,
                          int pow_q4, double* __restrict__ W, double* __restrict__ P, uint32_t* __restrict__ colnan) {
-  walk_for_each(t, [&](int c, int64_t b, int32_t i, int32_t) {
-    const double r = R[b + i];
-    if (r != r) colnan[c] = 1u;
+  for_each_rank_item(t, [&](const RankItem& it) {
+    const double r = R[it.r];
+    if (r != r) colnan[it.c] = 1u;
     if (need_w) {
       const double w = r == r ? walk_pow(r, power, pow_q4) : r;
-      W[b + i] = w;
-      P[b + i] = w * Q[b + i];
+      W[it.r] = w;
+      P[it.r] = w * Q[it.r];
     }
   });
 }
@@ -150,17 +121,10 @@ __global__ void __launch_bounds__(256)
 walk_epilogue_kernel(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ S, int64_t lds,
                      int32_t m, int32_t n, const int32_t* __restrict__ kset, int64_t N, int scale,
                      const uint32_t* __restrict__ colnan, double* __restrict__ part) {
-  __shared__ double s_mn[4], s_mx[4];
-  __shared__ uint32_t s_nan;
   const double T = (double)(N * (N + 1) / 2);
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  if (threadIdx.x == 0) s_nan = 0u;
-  double mn = INFINITY, mx = -INFINITY;
-  uint32_t anynan = 0u;
-  const int64_t total = (int64_t)m * n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = e / m, j = e - c * m;
-    const int64_t at = c * lds + j;
+  double mn = INFINITY, mx = -INFINITY, nf = 0.0;
+  for_each_score(m, n, lds, [&](int64_t c, int64_t j, int64_t at) {
     const int32_t k = kset[j];
     const double cv = S[at];
     const double av = A != nullptr ? A[at] : cv;
@@ -171,30 +135,23 @@ walk_epilogue_kernel(const double* __restrict__ A, const double* __restrict__ B,
     if (scale) es = es / (double)N;
     if (colnan[c]) es = nan;
     S[at] = es;
-    if (es != es) anynan = 1u;
-    else { mn = es < mn ? es : mn; mx = es > mx ? es : mx; }
-  }
-  __syncthreads();
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
-    mn = a < mn ? a : mn;
-    mx = b > mx ? b : mx;
-  }
-  if (anynan) atomicOr(&s_nan, 1u);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { s_mn[wave] = mn; s_mx[wave] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) { mn = s_mn[w] < mn ? s_mn[w] : mn; mx = s_mx[w] > mx ? s_mx[w] : mx; }
-    part[3 * (int64_t)blockIdx.x] = mn;
-    part[3 * (int64_t)blockIdx.x + 1] = mx;
-    part[3 * (int64_t)blockIdx.x + 2] = s_nan ? 1.0 : 0.0;
-  }
+    score_range_take(es, mn, mx, nf);
+  });
+  score_range_block(mn, mx, nf, part);
+}
+
+// block partials {min, max, any NaN} of m x n scores (launch_score_range: the scores of single = FALSE, which no epilogue
+// kernel passes over)
+__global__ void __launch_bounds__(256)
+gsea_ks_range_kernel(const double* __restrict__ S, int64_t lds, int32_t m, int32_t n, double* __restrict__ part) {
+  double mn = INFINITY, mx = -INFINITY, nf = 0.0;
+  for_each_score(m, n, lds, [&](int64_t, int64_t, int64_t at) { score_range_take(S[at], mn, mx, nf); });
+  score_range_block(mn, mx, nf, part);
 }
 
 // {min, max, any NaN} over the block partials (min / max select: any order gives the same values)
 __global__ void __launch_bounds__(64)
-walk_range_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
+gsea_ks_range_final_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
   double mn = INFINITY, mx = -INFINITY, nf = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 64) {
     mn = part[3 * b] < mn ? part[3 * b] : mn;
@@ -212,15 +169,7 @@ walk_range_kernel(const double* __restrict__ part, int nblocks, double* __restri
 
 __global__ void __launch_bounds__(256)
 walk_norm_kernel(double* __restrict__ S, int64_t lds, int32_t m, int32_t n, double range) {
-  const int64_t total = (int64_t)m * n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = e / m, j = e - c * m;
-    S[c * lds + j] = S[c * lds + j] / range;
-  }
-}
-
-dim3 walk_grid(int32_t max_len, int32_t n) {
-  return dim3((unsigned)std::min<int64_t>(((int64_t)max_len + 255) / 256, 64), (unsigned)std::min(n, 16384));
+  for_each_score(m, n, lds, [&](int64_t, int64_t, int64_t at) { S[at] = S[at] / range; });
 }
 
 // the exponent routine of colranks(ties = "average", power = alpha) for columns of g keys
@@ -230,14 +179,21 @@ int walk_pow_q4(plaidhip_ctx* ctx, int32_t g, double power) {
   return colranks_uses_power_quarters(ctx, g) ? pq : 0;
 }
 
-int part_blocks(plaidhip_ctx* ctx, int64_t count) {
+}  // namespace
+
+int score_part_blocks(plaidhip_ctx* ctx, int64_t count) {
   const int64_t b = (count + 255) / 256, cap = (int64_t)ctx->num_cu * 4;
   return (int)std::max<int64_t>(1, std::min(b, cap));
 }
 
-}  // namespace
-
-int ssgsea_exact_part_blocks(plaidhip_ctx* ctx, int64_t count) { return part_blocks(ctx, count); }
+int launch_score_range(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n, double* part, double* range_out) {
+  if ((int64_t)m * n == 0) return PLAIDHIP_OK;
+  const int blocks = score_part_blocks(ctx, (int64_t)m * n);
+  hipLaunchKernelGGL(gsea_ks_range_kernel, dim3(blocks), dim3(256), 0, ctx->stream, S, lds, m, n, part);
+  hipLaunchKernelGGL(gsea_ks_range_final_kernel, dim3(1), dim3(64), 0, ctx->stream, part, blocks, range_out);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
 
 int launch_ssgsea_exact_operands(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t* Xp, const int32_t* Xi,
                                  int32_t g, int32_t n, int32_t max_col_nnz, int64_t nnz, double alpha, double* Q, double* W,
@@ -251,14 +207,13 @@ int launch_ssgsea_exact_operands(plaidhip_ctx* ctx, const double* X, int64_t ldx
   if (Xp == nullptr) {
     double* R = scratch;
     double* Y = scratch + ldq * (int64_t)n;
-    const WalkCols t{nullptr, g, n, ldq};
-    const dim3 grid = walk_grid(g, n);
+    const RankCols t = dense_cols(g, n, ldq);
     rc = launch_colranks_dense_f64(ctx, X, ldx, g, n, PLAIDHIP_TIES_AVERAGE, 0, 1.0, R, ldq, nullptr);      // pass 1
     if (rc != PLAIDHIP_OK) return rc;
-    hipLaunchKernelGGL(walk_prep_kernel, grid, dim3(256), 0, ctx->stream, t, R, Y);
-    rc = launch_colranks_dense_f64(ctx, Y, ldq, g, n, PLAIDHIP_TIES_MIN, 0, 1.0, Q, ldq, nullptr);          // pass 2
+    rc = launch_last_ranks(ctx, t, R, Y, Q);                                                                 // pass 2
     if (rc != PLAIDHIP_OK) return rc;
-    hipLaunchKernelGGL(walk_finish_dense_kernel, grid, dim3(256), 0, ctx->stream, t, R, Q, need_w, alpha, pow_q4, W, P, colnan);
+    hipLaunchKernelGGL(walk_finish_dense_kernel, rank_cols_grid(t), dim3(256), 0, ctx->stream, t, R, Q, need_w, alpha, pow_q4, W, P,
+                       colnan);
     PH_HIP(hipGetLastError());
     return PLAIDHIP_OK;
   }
@@ -267,12 +222,9 @@ int launch_ssgsea_exact_operands(plaidhip_ctx* ctx, const double* X, int64_t ldx
   double* Yx = scratch + nnz;
   double* Qx = scratch + 2 * nnz;
   if (max_col_nnz > 0) {
-    const WalkCols t{Xp, max_col_nnz, n, 0};
-    const dim3 grid = walk_grid(max_col_nnz, n);
     rc = launch_colranks_csc_f64(ctx, Xp, X, n, max_col_nnz, PLAIDHIP_TIES_AVERAGE, 0, 1.0, Rx, nullptr);      // pass 1
     if (rc != PLAIDHIP_OK) return rc;
-    hipLaunchKernelGGL(walk_prep_kernel, grid, dim3(256), 0, ctx->stream, t, Rx, Yx);
-    rc = launch_colranks_csc_f64(ctx, Xp, Yx, n, max_col_nnz, PLAIDHIP_TIES_MIN, 0, 1.0, Qx, nullptr);         // pass 2
+    rc = launch_last_ranks(ctx, csc_cols(Xp, max_col_nnz, n), Rx, Yx, Qx);                                     // pass 2
     if (rc != PLAIDHIP_OK) return rc;
   }
   const int cap = ctx->num_cu * 16;
@@ -287,17 +239,17 @@ int launch_ssgsea_exact_epilogue(plaidhip_ctx* ctx, const double* A, const doubl
                                  int32_t n, const int32_t* kset, int64_t N, int scale, const uint32_t* colnan, double* part,
                                  double* range_out) {
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  const int blocks = part_blocks(ctx, (int64_t)m * n);
+  const int blocks = score_part_blocks(ctx, (int64_t)m * n);
   hipLaunchKernelGGL(walk_epilogue_kernel, dim3(blocks), dim3(256), 0, ctx->stream, A, B, S, lds, m, n, kset, N, scale, colnan,
                      part);
-  hipLaunchKernelGGL(walk_range_kernel, dim3(1), dim3(64), 0, ctx->stream, part, blocks, range_out);
+  hipLaunchKernelGGL(gsea_ks_range_final_kernel, dim3(1), dim3(64), 0, ctx->stream, part, blocks, range_out);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
 
 int launch_ssgsea_exact_norm(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t m, int32_t n, double range) {
   if ((int64_t)m * n == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(walk_norm_kernel, dim3(part_blocks(ctx, (int64_t)m * n)), dim3(256), 0, ctx->stream, S, lds, m, n, range);
+  hipLaunchKernelGGL(walk_norm_kernel, dim3(score_part_blocks(ctx, (int64_t)m * n)), dim3(256), 0, ctx->stream, S, lds, m, n, range);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

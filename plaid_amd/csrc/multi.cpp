@@ -705,7 +705,7 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
     }
     PH_TRY(dk.alloc((size_t)m * 4));
     PH_HIP(hipMemcpyAsync(dk.p, kset.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
-    PH_TRY(dpart.alloc((size_t)ssgsea_exact_part_blocks(ctx, (int64_t)m * nloc) * 24));
+    PH_TRY(dpart.alloc((size_t)score_part_blocks(ctx, (int64_t)m * nloc) * 24));
     const int64_t zx = s.zx;
     const size_t col = (size_t)ld * nloc;
     const size_t nscratch = sparse ? 3 * (size_t)std::max<int64_t>(zx, 1) : 2 * col;
@@ -739,7 +739,7 @@ int ssgsea_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Share
     if (ks) {
       PH_TRY(launch_gsea_ks(ctx, Q, W, P, ld, d_colnan, g, nloc, dGp.as<int32_t>(), dGi.as<int32_t>(), m, c.alpha, c.scale,
                             dS.as<double>(), m));
-      return launch_gsea_ks_range(ctx, dS.as<double>(), m, m, nloc, dpart.as<double>(), d_range);
+      return launch_score_range(ctx, dS.as<double>(), m, m, nloc, dpart.as<double>(), d_range);
     }
     // q holds integers in [1, N]: the rank route's u16 staging when 2 N fits, integer sums either way
     const int xk = 2 * (int64_t)g < 65536 ? PLAIDHIP_X_RANKS : PLAIDHIP_X_ANY;
@@ -841,11 +841,11 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
       };
       PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * g),
                               (size_t)g * 8, nloc, on_panel));
-      PH_TRY(launch_sing_colnan(ctx, dX.as<double>(), ld, nullptr, g, nloc, 0, d_colnan));
+      PH_TRY(launch_colnan(ctx, dX.as<double>(), ld, nullptr, g, nloc, 0, d_colnan));
     } else {
       int32_t max_nnz = 0;
       PH_TRY(upload_csc_shard(s, ploc, dXp, dXi, dX, &max_nnz));
-      PH_TRY(launch_sing_colnan(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), g, nloc, max_nnz, d_colnan));
+      PH_TRY(launch_colnan(ctx, dX.as<double>(), 0, dXp.as<int32_t>(), g, nloc, max_nnz, d_colnan));
       // replaid.sing ranks the zeros too (shard_worker): the dense rank matrix from the ranks of the stored values, or, for
       // a column with more stored values than one pass ranks, densify and rank
       if (max_nnz <= max_sparse_rank_column())
@@ -856,7 +856,7 @@ int sing_exact_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared&
                                              PLAIDHIP_TIES_MIN, 0, 1.0, R, ld, nullptr));
     }
     if (want_disp) {
-      PH_TRY(launch_sing_last_ranks(ctx, R, ld, g, nloc, Y, Q));
+      PH_TRY(launch_last_ranks(ctx, dense_cols(g, nloc, ld), R, Y, Q));
       PH_TRY(launch_sing_rpos(ctx, R, Q, ld, d_colnan, g, nloc, reinterpret_cast<uint32_t*>(Y), ld));
     }
     for (int o = 0; o < 6; ++o)
@@ -1813,7 +1813,7 @@ int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
     PH_HIP(hipMemsetAsync(dWpos.p, 0, col * 8, ctx->stream));
     PH_HIP(hipMemsetAsync(dpos.p, 0, col * 4, ctx->stream));
     PH_TRY(launch_colranks_dense_f64(ctx, dstat.as<double>(), g, g, nl, PLAIDHIP_TIES_MIN, 0, 1.0, dR.as<double>(), g, nullptr));
-    PH_TRY(launch_sing_last_ranks(ctx, dR.as<double>(), g, g, nl, dY.as<double>(), dQ.as<double>()));
+    PH_TRY(launch_last_ranks(ctx, dense_cols(g, nl, g), dR.as<double>(), dY.as<double>(), dQ.as<double>()));
     PH_TRY(launch_gsea_operands(ctx, dQ.as<double>(), dw.as<double>(), g, dnan.as<uint32_t>(), g, nl, dpos.as<int32_t>(),
                                 dWpos.as<double>()));
     return launch_gsea_obs(ctx, c.gsea_weighted, c.score_type, dpos.as<int32_t>(), dWpos.as<double>(), dnan.as<uint32_t>(), g, nl,
