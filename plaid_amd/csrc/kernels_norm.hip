@@ -14,6 +14,18 @@
 #include <type_traits>
 #include "device_sort.h"
 
+// A/B knobs for `make variant DEFS=...` (tools/ab_norm.sh); the product carries no run-time switch.
+//   PLAIDHIP_SHIFT_CACHED_BYTES: shift_columns_kernel stores plainly and walks from the last column down while S is no
+//     larger than this many bytes (0: never, the behaviour before); see launch_shift_columns.
+//   PLAIDHIP_MED_PAIR_LOADS: col_medians_wave_kernel reads the rows that every column of its class has with 16-byte loads
+//     where the column is aligned.
+#ifndef PLAIDHIP_SHIFT_CACHED_BYTES
+#define PLAIDHIP_SHIFT_CACHED_BYTES (4ll * 256 * 1024 * 1024)
+#endif
+#ifndef PLAIDHIP_MED_PAIR_LOADS
+#define PLAIDHIP_MED_PAIR_LOADS 1
+#endif
+
 namespace plaidhip {
 
 __global__ void __launch_bounds__(256)
@@ -500,15 +512,20 @@ max_kernel(const double* __restrict__ v, int64_t count, double* out) {
 }
 
 // (x - med[col]) + mean(med): one streaming read + write of S.  16-byte accesses, four of them in flight per thread
-// before the first is used, non-temporal both ways (S does not fit any cache and is not read again by this kernel).
+// before the first is used, loads non-temporal.  CACHED = false: non-temporal stores, columns in ascending order (S fits
+// no cache).  CACHED = true, for an S of the order of the Infinity Cache: plain stores, which find the line where the load
+// left it, and columns from the last to the first, so that the pass ends on the columns the next crossprod writes first
+// (DESIGN.md 4.3 has the measurements and where the size bound comes from).
+template <bool CACHED>
 __global__ void __launch_bounds__(256)
 shift_columns_kernel(double* __restrict__ S, int64_t lds, int32_t m, int32_t n,
                      const double* __restrict__ med, double add, const double* __restrict__ red) {
   typedef double f64x2_s __attribute__((ext_vector_type(2)));
   constexpr int UN = 4;   // (measured with 2 / 4 / 8: 4 is the best or within 3 % of it at m = 5,000 and 50,000, aligned or not)
   if (red != nullptr) add = red[0] / red[1];   // mean(medx, na.rm=TRUE) from {sum, count}
-  // grid.y walks columns, grid.x * block walks the rows of a column
-  for (int c = blockIdx.y; c < n; c += gridDim.y) {
+  // grid.y walks columns (CACHED: from the last one down), grid.x * block walks the rows of a column
+  for (int cy = blockIdx.y; cy < n; cy += gridDim.y) {
+    const int c = CACHED ? n - 1 - cy : cy;
     double* sc = S + (int64_t)c * lds;
     const double md = med[c];
     const int head = (int)((reinterpret_cast<uintptr_t>(sc) >> 3) & 1u);   // first element not 16-byte aligned
@@ -532,7 +549,8 @@ shift_columns_kernel(double* __restrict__ S, int64_t lds, int32_t m, int32_t n,
           f64x2_s r;
           r.x = (v[u].x - md) + add;
           r.y = (v[u].y - md) + add;
-          __builtin_nontemporal_store(r, p + i);
+          if constexpr (CACHED) p[i] = r;
+          else __builtin_nontemporal_store(r, p + i);
         }
       }
     }
@@ -1062,14 +1080,30 @@ col_medians_wave_kernel(const double* __restrict__ S, int64_t lds, int32_t m, in
     // plain loads, no mask.  Only the last 16 rows can reach past the column's end: clamped address, masked below.
     constexpr int FULL = ITEMS - 16;
     const double* __restrict__ scl = sc + lane_o;
+    // A 16-byte aligned column reads those FULL rows two values per lane: 8-byte loads run at 0.54-0.70 of the rate of
+    // 16-byte ones on this part, and this read is half of the kernel's time.  Which lane and register hold which value
+    // does not matter to the selection.  A column that starts on an odd multiple of 8 bytes keeps the 8-byte loads.
+#if PLAIDHIP_MED_PAIR_LOADS
+    const bool pairs = FULL > 0 && __builtin_amdgcn_readfirstlane((int)(reinterpret_cast<uintptr_t>(sc) & 15u)) == 0;
+#else
+    constexpr bool pairs = false;
+#endif
+    if (pairs) {
+      const f64x2_t* __restrict__ sp = reinterpret_cast<const f64x2_t*>(sc) + lane_o;
 #pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      if (j < FULL) {
-        raw[j] = __builtin_nontemporal_load(scl + j * 64);
-      } else {
-        const int i = lane_o + j * 64;
-        raw[j] = __builtin_nontemporal_load(sc + (i < m ? i : m - 1));
+      for (int jj = 0; jj < FULL / 2; ++jj) {
+        const f64x2_t v2 = __builtin_nontemporal_load(sp + jj * 64);
+        raw[2 * jj] = v2.x;
+        raw[2 * jj + 1] = v2.y;
       }
+    } else {
+#pragma unroll
+      for (int j = 0; j < FULL; ++j) raw[j] = __builtin_nontemporal_load(scl + j * 64);
+    }
+#pragma unroll
+    for (int j = FULL; j < ITEMS; ++j) {
+      const int i = lane_o + j * 64;
+      raw[j] = __builtin_nontemporal_load(sc + (i < m ? i : m - 1));
     }
     // (the bound is re-read through an opaque copy: the lane masks of the address clamps above must not be kept in
     //  scalar registers until the values arrive)
@@ -2019,6 +2053,8 @@ int launch_col_medians(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t 
   // wave-per-column register-resident selection up to 6,144 values (measured against the workgroup-per-column radix
   // kernel on 10k columns, one box: 1,000 sets 0.023 vs 0.048 ms, 3,000: 0.058 vs 0.096, 5,000: 0.106 vs 0.179, 6,000:
   // 0.123 vs 0.202); the workgroup kernel stays selectable in the tools/ build as a cross-check
+  // (with the 16-byte loads of the unmasked rows, same columns, another box, before -> after: 1,000 sets 0.0197 -> 0.0197 ms,
+  // 3,000: 0.0513 -> 0.0520, 6,000: 0.1160 -> 0.1153 -- no class moves alone; at 5,000 they are worth 2.5 us after a cached shift)
   const bool want_wave = (force && force[0] == 'w') || (!force && m <= 6144);
   if (want_wave && m <= 6144) {
     // (the kernel reads its first ITEMS - 16 rows of 64 values without a bound: the class follows from m, here and only here)
@@ -2145,7 +2181,14 @@ int launch_shift_columns(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t m, i
   if (const char* e = getenv("PLAIDHIP_SHIFT_BY")) by = n < atoi(e) ? n : atoi(e);   // (rows = min(n, value))
 #endif
   if (bx > bx_cap) bx = bx_cap;
-  hipLaunchKernelGGL(shift_columns_kernel, dim3(bx, by), dim3(256), 0, ctx->stream, S, lds, m, n, med, add, red);
+  // plain stores and the descending walk while S is at most four times the 256 MiB Infinity Cache: what they gain is a
+  // cache effect (measured at 400 MB); beyond, at most a quarter of S can be on the die when the pass or its successor
+  // comes by, and the non-temporal ascending form measured at 3-40 GB stays as it was
+  const bool cached = (int64_t)n * lds * 8 <= (int64_t)(PLAIDHIP_SHIFT_CACHED_BYTES);
+  if (cached)
+    hipLaunchKernelGGL(shift_columns_kernel<true>, dim3(bx, by), dim3(256), 0, ctx->stream, S, lds, m, n, med, add, red);
+  else
+    hipLaunchKernelGGL(shift_columns_kernel<false>, dim3(bx, by), dim3(256), 0, ctx->stream, S, lds, m, n, med, add, red);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
