@@ -596,11 +596,12 @@ int launch_gsea_null_reduce(plaidhip_ctx* ctx, const double* part, int32_t nblk,
                             int32_t c, int score_type, double* out);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
+// kernels_medians.hip
 int launch_col_medians(plaidhip_ctx* ctx, const double* S, int64_t lds, int32_t m, int32_t n,
                        int ignore_zero, const uint32_t* flags, double* med,
                        // non-null (streaming kernel, m > 6,144 only): columns with status[c] != 0 already have their median
                        const int32_t* status = nullptr);
-// medians selected inside the sparse crossprod launch (kernels_norm.hip / kernels_spmm.hip: MED)
+// medians selected inside the sparse crossprod launch (kernels_medians.hip / kernels_spmm.hip: MED)
 int launch_colmean_predict(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t n, const double* u,
                            double alpha, const double* alpha_div, double beta_kappa, double* pred);
 int launch_median_calibrate(plaidhip_ctx* ctx, const double* medK, const double* pred, int32_t K, const uint32_t* flagsK,
@@ -608,6 +609,7 @@ int launch_median_calibrate(plaidhip_ctx* ctx, const double* medK, const double*
 int launch_median_select(plaidhip_ctx* ctx, const unsigned long long* cand, const uint32_t* cnt, int32_t n, int32_t nslice,
                          int32_t capc, int32_t m, const double* cal, int ignore_zero, const uint32_t* flags, double* med,
                          int32_t* status);
+// kernels_norm.hip
 int launch_sum(plaidhip_ctx* ctx, const double* v, int64_t count, double* out);
 int launch_max(plaidhip_ctx* ctx, const double* v, int64_t count, double* out);
 int launch_shift_columns(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t m, int32_t n,

@@ -831,7 +831,7 @@ extern "C" int plaidhip_geneset_create(plaidhip_ctx* ctx, int32_t g, int32_t m, 
       // the MEAN score of a sample column without the crossprod: mean_j S[j, c] = alpha * sum_i x[i, c] u[i] + beta * kappa
       // with u[i] = (1 / m) sum_{j containing i} weight_j and kappa = (1 / m) sum_j size_j weight_j (per statistic, like
       // kw above).  The scatter launch that selects the column medians on the fly brackets them around this mean
-      // (kernels_norm.hip: colmean_predict_kernel).
+      // (kernels_medians.hip: colmean_predict_kernel).
       std::vector<double> uv((size_t)2 * g, 0.0);
       sp.kappa[0] = sp.kappa[1] = 0.0;
       for (int32_t j = 0; j < m; ++j) {

@@ -86,7 +86,7 @@ def _keys(v):
 
 
 def _bracket(col, iz):
-    """restatement of the sampled start of col_medians_stream_kernel (kernels_norm.hip): None when the sample is not used,
+    """restatement of the sampled start of col_medians_stream_kernel (kernels_medians.hip): None when the sample is not used,
     else (hit, keys inside [qa, qb], ccap)"""
     m = len(col)
     K = 16 if m > 32768 else 8

@@ -285,7 +285,7 @@ def test_sparse_colranks_ragged(hip_ctx):
 
 
 def test_medians_large_m_select_path(hip_ctx):
-    """m above the LDS sort limit takes the radix-select kernel"""
+    """m above 6,144 takes the streaming kernel (col_medians_stream_kernel), here with its sampled start"""
     rng = np.random.default_rng(11)
     S = rng.normal(size=(25000, 6))
     S[rng.random(S.shape) < 0.1] = 0.0
@@ -412,8 +412,8 @@ def test_c2_full_size_properties(hip_ctx):
 
 @pytest.mark.parametrize("m", [1, 2, 3, 64, 65, 1024, 1025, 2048, 2049, 3072, 3073, 4096, 4097, 5000, 5120, 5121, 6144, 6145, 16384, 20000, 33000, 50000, 65536, 65537, 70000])
 def test_medians_every_kernel_size_class(hip_ctx, m):
-    """column lengths across the register-resident classes (<=2048/6144/16384/32768/65536), the
-    radix-select fallback beyond, heavy ties, both parities of the valid count"""
+    """column lengths across the six classes of 1,024 values of the wave kernel (up to 6,144) and the streaming kernel
+    beyond (512 sample values, 1,024 from 32,769 sets), heavy ties, both parities of the valid count"""
     rng = np.random.default_rng(m)
     n = 5
     S = np.round(rng.normal(size=(m, n)), 2)            # many ties

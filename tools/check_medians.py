@@ -1,6 +1,8 @@
-"""Runs the column-median kernel the library selects (or the one PLAIDHIP_MEDIAN_KERNEL forces in the tools/ build) on
-seeded matrices of several shapes and saves the medians, so that two kernels can be compared bit for bit:
-    python3 tools/check_medians.py --out a.npz;  PLAIDHIP_MEDIAN_KERNEL=wave PLAIDHIP_LIB=... python3 tools/check_medians.py --out b.npz --against a.npz"""
+"""Runs the column medians of the library that PLAIDHIP_LIB names (default: the product build) on seeded matrices of
+several shapes -- every class of the wave kernel, and the streaming kernel at both sample sizes -- and saves them, so that
+two builds can be compared bit for bit:
+    PLAIDHIP_LIB=/path/to/other/libplaidhip.so python3 tools/check_medians.py --out a.npz
+    python3 tools/check_medians.py --out b.npz --against a.npz"""
 import argparse
 import os
 import sys
@@ -21,7 +23,8 @@ def main():
     ctx = plaid_amd.Context(0)
     res = {}
     for m, n in ((5000, 3000), (4999, 257), (1, 5), (2, 9), (63, 100), (64, 100), (65, 100), (1024, 513), (1025, 300), (2048, 300),
-                 (3000, 300), (4096, 300), (4097, 300), (5120, 300), (5121, 300), (6144, 300)):
+                 (3000, 300), (4096, 300), (4097, 300), (5120, 300), (5121, 300), (6144, 300),
+                 (6145, 300), (8192, 257), (20000, 64), (40000, 16), (70000, 8)):      # the streaming kernel
         gen = torch.Generator(device=dev)
         gen.manual_seed(m * 131 + n)
         S = torch.randn((n, m), dtype=torch.float64, device=dev, generator=gen) * 3 + 1
