@@ -929,6 +929,65 @@ int plaidhip_gsea_scored_multi(const int* devices, int ndev, const double* stat,
                                int32_t* le_idx);
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out);
 
+/* plaid.fisher(sig, G): over-representation analysis -- Fisher's exact (hypergeometric) test of every list of significant
+ * genes against every set, in three directions.  The form is fgsea::fora / fisher.test(alternative = "greater") AS
+ * RECALLED: their source is not in this tree, so the statistic is pinned here, operation for operation, and tested against
+ * these words and against exact rational arithmetic.
+ * Operands: sig is g x c int8, column-major; sig[i, l] is -1 (gene i significant down in list l), 0 (not significant) or
+ * +1 (significant up).  Any other value is PLAIDHIP_EINVAL, found on the host before any device work.  The universe is the
+ * g rows: N = g.  The sets are Gp / Gi as everywhere else (rows of sig, 0-based).
+ * Per list l:  nUp = #{i : sig[i, l] = +1},  nDn = #{i : sig[i, l] = -1}.  Per set j with k = Gp[j + 1] - Gp[j] members:
+ * ovUp = #{members with sig = +1}, ovDn = #{members with sig = -1}.  All are exact integer counts.  Three directions:
+ *     up:    K = nUp         x = ovUp
+ *     down:  K = nDn         x = ovDn
+ *     any:   K = nUp + nDn   x = ovUp + ovDn
+ * Upper tail p = P(X >= x), X ~ Hypergeometric(N, K, k) (k draws from N genes of which K are marked), all in fp64, the
+ * integers in 64 bits:
+ *     lo = max(0, k + K - N);  hi = min(k, K)
+ *     if x <= lo: p = 1.0;  if x > hi: p = 0.0;  otherwise
+ *     t0 = clamp(floor((k + 1)(K + 1) / (N + 2)), lo, hi)                         (the mode: every other term is <= its own)
+ *     u = 1.0;  total = 1.0;  upper = (t0 >= x) ? 1.0 : 0.0
+ *     upwards, for t = t0 .. hi - 1 in order:
+ *         u = (u * ((double)(K - t) * (double)(k - t))) / ((double)(t + 1) * (double)(N - K - k + t + 1))
+ *         total += u;  upper += u if t + 1 >= x
+ *     downwards, restart u = 1.0, for t = t0 .. lo + 1 descending:
+ *         u = (u * ((double)t * (double)(N - K - k + t))) / ((double)(K - t + 1) * (double)(k - t + 1))
+ *         total += u;  upper += u if t - 1 >= x
+ *     p = upper / total
+ * The integer products are exact (g <= PLAIDHIP_FISHER_MAX_GENES = 2^26, else PLAIDHIP_EUNSUPPORTED), so a step is one
+ * rounded multiply and one rounded divide, and the additions run in exactly that order.  No product is contracted, and
+ * there is no pow, lgamma or exp.  A term that underflows becomes 0 and stays 0 (adding it changes nothing, so a walk may
+ * stop there).  Where the true p is at least 2^-900 the result lies within (4 n + 2) 2^-53 of it, relatively, n = hi - lo + 1
+ * (DESIGN.md section 19 derives this); a true p below about 2^-900 may come back as any value in [0, 2^-890], including 0.
+ * Odds ratio (the sample one, not fisher.test's conditional MLE): a = x, b = k - x, c' = K - x, d = N - k - K + x,
+ *     OR = ((double)a * (double)d) / ((double)b * (double)c')          IEEE: x / 0 = Inf, 0 / 0 = NaN
+ * NaN rule, as plaid.gsea's: k = 0 or k = N gives NaN in every column of that set except size, ovUp and ovDn.  K = 0 is not
+ * special: x = 0, so p = 1.
+ * padj is Benjamini-Hochberg per list and direction over the sets with a non-NaN p (the host routine behind plaid.gsea's
+ * padj and q.meta).
+ * out: m x 12 x c, column-major: size, ovUp, ovDn, pUp, pDn, pAny, padjUp, padjDn, padjAny, orUp, orDn, orAny.
+ * tot_out: 2 x c doubles: nUp, nDn of every list.
+ * ov_len (m x c int32) and ov_idx (nnz x c int32, nnz = Gp[m]) are passed both or neither, laid out as plaid.gsea's le_len /
+ * le_idx: the overlap of (j, l) is ov_idx[l nnz + Gp[j] + 0 .. len-1], len = ov_len[l m + j] = ovUp + ovDn: the rows of set j
+ * with sig != 0 in list l, in the set's own member order (the order of Gi); the rest of the set's segment is -1.
+ * Argument errors, in this order: c < 1; bad dims or a null Gp; null sig or tot_out (or out, with m > 0); exactly one of
+ * ov_len / ov_idx null; g > PLAIDHIP_FISHER_MAX_GENES (PLAIDHIP_EUNSUPPORTED); Gp not starting at 0 or decreasing, a null
+ * Gi, or a Gi row outside 0..g-1; a bad sig value.  All are found on the host before any device is touched.  m = 0 returns
+ * PLAIDHIP_OK with nothing written, as the other entries do.
+ * plaidhip_fisher_multi shares the lists out over the devices (plaidhip_shard_bounds over c); a device takes the columns of
+ * sig of its lists and all of G.  A list's results depend on that list alone and its counts are integers, so every
+ * sharding, including ndev > c, returns the one-device bits of out, tot_out, ov_len and ov_idx.
+ * plaidhip_hyper_tail is the tail above, the same inline function, on the host: no device is touched.  0 <= K, k <= N
+ * (else PLAIDHIP_EINVAL), N <= PLAIDHIP_FISHER_MAX_GENES (else PLAIDHIP_EUNSUPPORTED), any x.  It applies no NaN rule.
+ * Not offered: two-sided p-values and the conditional-MLE odds ratio. */
+#define PLAIDHIP_FISHER_MAX_GENES (1 << 26)
+#define PLAIDHIP_FISHER_LIST_TILE 8
+int plaidhip_fisher(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                    double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx);
+int plaidhip_fisher_multi(const int* devices, int ndev, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp,
+                          const int32_t* Gi, int32_t m, double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx);
+int plaidhip_hyper_tail(int64_t N, int64_t K, int64_t k, int64_t x, double* p);
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

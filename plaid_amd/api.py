@@ -636,3 +636,94 @@ def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=
         if leadingEdge:
             res[nm] = (res[nm], [[genes[r] for r in le_idx[Gp[j]:Gp[j] + le_len[j, l], l]] for j in o])
     return res[stats.colnames[0]] if single and len(res) == 1 else res
+
+
+_FISHER_NAMES = ["size", "ovUp", "ovDn", "pUp", "pDn", "pAny", "padjUp", "padjDn", "padjAny", "orUp", "orDn", "orAny"]
+
+
+def plaid_sig(logFC, pvalue, lfc=0.2, pcut=0.05):
+    """plaid.sig(): the lists plaid.fisher takes, from gene-level results: +1 where logFC > lfc and pvalue < pcut, -1 where
+    logFC < -lfc and pvalue < pcut, 0 elsewhere; a NaN in either input gives 0.  (The rule of the reference's comparison
+    of enrichment methods.)  logFC and pvalue have one shape (a vector, a dict / Series, or genes x contrasts); a
+    NamedMatrix, dict or Series comes back as a NamedMatrix with the same names, anything else as an int8 array.  Runs
+    on the host."""
+    names = None
+    if isinstance(logFC, dict):
+        names = (list(logFC.keys()), ["sig"])
+        pvalue = [pvalue[k] for k in logFC] if isinstance(pvalue, dict) else pvalue
+        logFC = list(logFC.values())
+    elif isinstance(logFC, NamedMatrix):
+        names = (logFC.rownames, logFC.colnames)
+        logFC = logFC.values
+    elif hasattr(logFC, "index") and hasattr(logFC, "to_numpy"):     # a pandas Series / DataFrame
+        names = (list(logFC.index), list(getattr(logFC, "columns", ["sig"])))
+        logFC = logFC.to_numpy(dtype=np.float64)
+    if isinstance(pvalue, NamedMatrix):
+        pvalue = pvalue.values
+    elif hasattr(pvalue, "to_numpy"):
+        pvalue = pvalue.to_numpy(dtype=np.float64)
+    fc, pv = np.asarray(logFC, dtype=np.float64), np.asarray(pvalue, dtype=np.float64)
+    if fc.shape != pv.shape:
+        raise ValueError(f"plaid.sig: logFC {fc.shape} and pvalue {pv.shape} must have one shape")
+    with np.errstate(invalid="ignore"):   # (a comparison with NaN is False: 0)
+        hit = pv < float(pcut)
+        s = (hit & (fc > float(lfc))).astype(np.int8) - (hit & (fc < -float(lfc))).astype(np.int8)
+    if names is None:
+        return s
+    return NamedMatrix(s.reshape(len(names[0]), -1), names[0], names[1])
+
+
+def plaid_fisher(sig, G, minSize=1, maxSize=None, sort_by="pAny", overlap=False, ctx: Context | None = None):
+    """plaid.fisher(): over-representation analysis (Fisher's exact / hypergeometric test, upper tail, as pinned in
+    include/plaidhip.h) of a named vector of -1 / 0 / +1 (gene significant down / not / up; plaid_sig makes one), or of
+    every column of a genes x contrasts NamedMatrix, against the sets of G (a gmt or a membership matrix).  Genes are
+    aligned by name as plaid.gsea aligns them, and the universe is the aligned rows.  Sets with fewer than minSize or more
+    than maxSize (default: the aligned genes - 1) aligned members are dropped.  Returns one NamedMatrix (sets x [size, ovUp,
+    ovDn, pUp, pDn, pAny, padjUp, padjDn, padjAny, orUp, orDn, orAny]) ordered by `sort_by` (stable, NaN last) when sig is a
+    named vector (a dict or a pandas Series); for a NamedMatrix, of one column or of many, a dict, column name ->
+    NamedMatrix, in the columns' order.  overlap = True returns (table, genes) wherever a table is returned: genes is a
+    list, one entry per table row in the table's order, of (gene name, sign) for the set's members that are in the list, in
+    the set's member order."""
+    if isinstance(sig, dict):
+        sig = NamedMatrix(np.array(list(sig.values()), dtype=np.float64), list(sig.keys()), ["sig"])
+        single = True
+    else:
+        single = not isinstance(sig, NamedMatrix) and np.ndim(sig) == 1
+        try:
+            import pandas as pd
+            if isinstance(sig, pd.Series):
+                sig, single = NamedMatrix(sig.to_numpy(dtype=np.float64), list(sig.index), ["sig"]), True
+        except ImportError:  # pragma: no cover
+            pass
+    if isinstance(G, (GmtList, dict)) or (isinstance(G, tuple) and len(G) == 2):
+        _message("[plaid.fisher] converting gmt to sparse matrix...")
+        G = gmt2mat(G)
+    sig = as_named(sig)
+    if sp.issparse(sig.values):
+        raise ValueError("plaid.fisher: sig must be dense")
+    Xs, Gp, Gi, _, _, _, _, rn = _plaid_test_operands(sig, G, None, "one", "fisher")
+    N = Xs.shape[0]
+    sizes = np.diff(Gp)
+    hi = N - 1 if maxSize is None else int(maxSize)
+    keep = np.flatnonzero((sizes >= int(minSize)) & (sizes <= hi))
+    Gi = np.concatenate([Gi[Gp[j]:Gp[j + 1]] for j in keep]).astype(np.int32) if len(keep) else np.zeros(0, np.int32)
+    Gp = np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int32)
+    rn = [rn[j] for j in keep]
+    ctx = ctx or default_context()
+    res_dev = ctx.fisher(Xs, Gp, Gi, overlap=bool(overlap))
+    out = res_dev[0]
+    if overlap:
+        ov_len, ov_idx = res_dev[2], res_dev[3]
+        posx = _first_pos(sig.rownames)
+        genes = [nm for nm in dict.fromkeys(as_named(G).rownames) if nm in posx]     # the aligned rows, as Gi numbers them
+    res = {}
+    for l, nm in enumerate(sig.colnames):
+        tab, names = out[:, :, l], list(rn)
+        o = np.arange(len(names))
+        if sort_by in _FISHER_NAMES:
+            o = np.argsort(tab[:, _FISHER_NAMES.index(sort_by)], kind="stable")       # order(): NaN last
+            tab, names = tab[o, :], [names[k] for k in o]
+        res[nm] = NamedMatrix(tab, names, _FISHER_NAMES)
+        if overlap:
+            res[nm] = (res[nm], [[(genes[r], int(Xs[r, l])) for r in ov_idx[Gp[j]:Gp[j] + ov_len[j, l], l]] for j in o])
+    return res[sig.colnames[0]] if single and len(res) == 1 else res

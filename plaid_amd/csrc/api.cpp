@@ -1192,6 +1192,12 @@ int plaidhip_gsea_scored(plaidhip_ctx* ctx, const double* stat, const double* we
                   gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.fisher: the one-device form of the sharded engine (multi.cpp: fisher_worker, kFisher)
+int plaidhip_fisher(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                    double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx) try {
+  return dispatch(on_context(ctx), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
 // the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out) try {
   PH_REQUIRE(g >= 1 && nperm >= 1, "gsea_permutations: bad dims g=%d nperm=%d", g, nperm);

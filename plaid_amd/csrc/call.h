@@ -11,7 +11,7 @@ namespace plaidhip {
 // the ordinals are what the test hooks plaidhip_debug_sharded_on_one_device / _scorer_sharded_on_one_device take
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
-  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14
+  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -78,6 +78,10 @@ struct Call : Operands {
   int32_t* le_idx = nullptr;            // Gp[m] x n rows of stat, a set's edge in its own segment of G
   int gsea_weighted = 0;
   std::vector<uint32_t> listnan;
+  // plaid.fisher: sig (g x n int8, n = the lists; X stays null), out m x 12 x n, the 2 x n list totals, and the overlap
+  // lists in le_len / le_idx (both null: none)
+  const int8_t* sig = nullptr;
+  double* tot_out = nullptr;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -246,6 +250,17 @@ inline Call gsea_call(const double* stat, const double* weight, int32_t g, int32
   k.score_type = score_type;
   k.le_len = le_len;
   k.le_idx = le_idx;
+  return k;
+}
+// over-representation tests as pinned in include/plaidhip.h: plaidhip_fisher
+inline Call fisher_call(const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* out,
+                        double* tot_out, int32_t* ov_len, int32_t* ov_idx) {
+  Call k = make_call(kFisher, {nullptr, nullptr, nullptr, g, c, Gp, Gi, m}, nullptr);
+  k.sig = sig;
+  k.out = out;
+  k.tot_out = tot_out;
+  k.le_len = ov_len;
+  k.le_idx = ov_idx;
   return k;
 }
 

@@ -594,6 +594,19 @@ int launch_gsea_null(plaidhip_ctx* ctx, int weighted, int score_type, const int3
 // out (m x 12 x c; padj left NaN) from all nblk blocks of partials, added in block order
 int launch_gsea_null_reduce(plaidhip_ctx* ctx, const double* part, int32_t nblk, const double* ES, const int32_t* Gp, int32_t m,
                             int32_t c, int score_type, double* out);
+// kernels_fisher.hip: plaid.fisher (include/plaidhip.h: plaidhip_fisher).  All stream-ordered, all pointers device pointers.
+// masks ([ceil(c / PLAIDHIP_FISHER_LIST_TILE)][g] u16: bit t up, bit 8 + t down in list tile * 8 + t) and tot ([c][2] int32:
+// nUp, nDn; zeroed here) of the lists in sig (g x c int8, packed)
+int launch_fisher_pack(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, uint16_t* masks, int32_t* tot);
+// ov ([c][2][m] int32: ovUp, ovDn) of every (list, set) from the masks; every Gi is in 0..g-1 (checked on the host)
+int launch_fisher_count(plaidhip_ctx* ctx, const uint16_t* masks, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
+                        int32_t m, int32_t* ov);
+// out (m x 12 x c; the three padj columns left NaN) from the counts: hyper_tail.h's tail and odds ratio
+int launch_fisher_tail(plaidhip_ctx* ctx, const int32_t* tot, const int32_t* ov, const int32_t* Gp, int32_t g, int32_t c,
+                       int32_t m, double* out);
+// the overlap lists: len (c x m), idx (c x Gp[m]; the segment of (j, l) at l Gp[m] + Gp[j], -1 past the overlap)
+int launch_fisher_overlap(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
+                          int32_t m, int32_t* len, int32_t* idx);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 // kernels_medians.hip

@@ -1905,6 +1905,78 @@ int gsea_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   return s.finish();
 }
 
+constexpr int kFisherBhThreads = 8;            // host threads of one shard's Benjamini-Hochberg columns, at most
+constexpr int64_t kFisherBhWork = 1 << 16;     // p-values per thread below which another thread is not worth its start
+// one device's part of plaid.fisher (kFisher, kernels_fisher.hip).  The lists are shared out (plaidhip_shard_bounds over c):
+// a shard takes the columns of sig of its lists and all of G, and a list's results depend on that list alone, so every
+// sharding has the one-shard bits.  Benjamini-Hochberg of the shard's own lists runs on the host, on the shard's thread and,
+// for many lists, on a few more (every column is the same routine whichever thread runs it).  No rendezvous.
+int fisher_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t g = c.g, m = c.m, l0 = s.lo, nl = s.nloc;
+  const size_t nnz = (size_t)c.Gp[m];
+  DevBuf dsig, dmask, dtot, dov, dGp, dGi, dout, dlen, didx;
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nl <= 0) return PLAIDHIP_OK;
+    PH_HIP(hipSetDevice(ctx->device));
+    const int32_t ntile = (nl + PLAIDHIP_FISHER_LIST_TILE - 1) / PLAIDHIP_FISHER_LIST_TILE;
+    PH_TRY(dsig.alloc((size_t)g * nl));
+    PH_TRY(dmask.alloc((size_t)g * ntile * 2));
+    PH_TRY(dtot.alloc((size_t)nl * 2 * 4));
+    PH_TRY(dov.alloc((size_t)nl * 2 * m * 4));
+    PH_TRY(dout.alloc((size_t)m * 12 * nl * 8));
+    PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
+    PH_TRY(upload_pipelined(ctx, dsig.as<char>(), (size_t)g, reinterpret_cast<const char*>(c.sig + (size_t)l0 * g), (size_t)g, nl,
+                            nullptr));
+    PH_TRY(launch_fisher_pack(ctx, dsig.as<int8_t>(), g, nl, dmask.as<uint16_t>(), dtot.as<int32_t>()));
+    PH_TRY(launch_fisher_count(ctx, dmask.as<uint16_t>(), g, nl, dGp.as<int32_t>(), dGi.as<int32_t>(), m, dov.as<int32_t>()));
+    PH_TRY(launch_fisher_tail(ctx, dtot.as<int32_t>(), dov.as<int32_t>(), dGp.as<int32_t>(), g, nl, m, dout.as<double>()));
+    double* out = c.out + (size_t)l0 * 12 * m;
+    std::vector<int32_t> tot((size_t)nl * 2);
+    PH_HIP(hipMemcpyAsync(out, dout.p, (size_t)m * 12 * nl * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(tot.data(), dtot.p, (size_t)nl * 2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c.le_len != nullptr) {
+      PH_TRY(dlen.alloc((size_t)m * nl * 4));
+      PH_TRY(didx.alloc(std::max<size_t>(nnz * nl, 1) * 4));
+      PH_TRY(launch_fisher_overlap(ctx, dsig.as<int8_t>(), g, nl, dGp.as<int32_t>(), dGi.as<int32_t>(), m, dlen.as<int32_t>(),
+                                   didx.as<int32_t>()));
+      PH_HIP(hipMemcpyAsync(c.le_len + (size_t)l0 * m, dlen.p, (size_t)m * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (nnz != 0)
+        PH_HIP(hipMemcpyAsync(c.le_idx + (size_t)l0 * nnz, didx.p, nnz * nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    for (int32_t l = 0; l < nl; ++l) {
+      c.tot_out[2 * (size_t)(l0 + l)] = (double)tot[2 * (size_t)l];
+      c.tot_out[2 * (size_t)(l0 + l) + 1] = (double)tot[2 * (size_t)l + 1];
+    }
+    // Benjamini-Hochberg per (list, direction) over the sets that have a p-value: 3 nl independent sorts of m values, which
+    // outweigh the kernels from a few lists on -- dealt to host threads when there is enough of them
+    const int64_t ncol = 3 * (int64_t)nl;
+    auto adjust = [&](int64_t q0, int64_t step) {
+      for (int64_t q = q0; q < ncol; q += step) {
+        double* o = out + (size_t)(q / 3) * 12 * m;
+        p_adjust_fdr(o + (size_t)(3 + q % 3) * m, m, o + (size_t)(6 + q % 3) * m);
+      }
+    };
+    const int64_t nth = std::min<int64_t>({(int64_t)kFisherBhThreads, ncol * m / kFisherBhWork, ncol});
+    if (nth <= 1) {
+      adjust(0, 1);
+    } else {
+      std::vector<std::thread> th;
+      std::atomic<int> failed{0};
+      for (int64_t t = 0; t < nth; ++t)
+        th.emplace_back([&, t] {
+          try { adjust(t, nth); } catch (...) { failed.store(1); }
+        });
+      for (auto& t : th) t.join();
+      if (failed.load() != 0) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+    }
+    return PLAIDHIP_OK;
+  });
+  return s.finish();
+}
+
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
@@ -1937,6 +2009,7 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.gsea_part.assign((size_t)((c.nperm + PLAIDHIP_GSEA_PERM_BLOCK - 1) / PLAIDHIP_GSEA_PERM_BLOCK) * c.n * 6 * c.m, 0.0);
   auto worker = [&](int k) {
     if (c.method == kGsea) return gsea_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kFisher) return fisher_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
     return is_rank_sum(c.method) ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
@@ -2268,6 +2341,28 @@ int check_gsea_call(Call& c) {
   return PLAIDHIP_OK;
 }
 
+// plaid.fisher; the order is part of the contract (include/plaidhip.h)
+int check_fisher_call(const Call& c) {
+  PH_REQUIRE(c.n >= 1, "fisher: %d lists (at least 1)", c.n);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  PH_REQUIRE(c.sig != nullptr && c.tot_out != nullptr && (c.out != nullptr || c.m == 0), "fisher: null sig / out / tot_out");
+  PH_REQUIRE((c.le_len == nullptr) == (c.le_idx == nullptr), "fisher: ov_len and ov_idx are passed both or neither");
+  if (c.g > PLAIDHIP_FISHER_MAX_GENES) {
+    set_error("fisher: %d genes (at most %d)", c.g, PLAIDHIP_FISHER_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  PH_REQUIRE(c.Gp[0] == 0, "fisher: Gp[0] = %d (a column pointer starts at 0)", c.Gp[0]);
+  for (int32_t j = 0; j < c.m; ++j)
+    PH_REQUIRE(c.Gp[j + 1] >= c.Gp[j], "fisher: Gp[%d] = %d after %d (a column pointer does not decrease)", j + 1, c.Gp[j + 1],
+               c.Gp[j]);
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "fisher: null Gi");
+  for (int32_t e = 0; e < c.Gp[c.m]; ++e)
+    PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "fisher: Gi[%d] = %d (rows are 0..%d)", e, c.Gi[e], c.g - 1);
+  for (int64_t e = 0; e < (int64_t)c.g * c.n; ++e)
+    PH_REQUIRE(c.sig[e] >= -1 && c.sig[e] <= 1, "fisher: sig[%lld] = %d (-1 down, 0, +1 up)", (long long)e, (int)c.sig[e]);
+  return PLAIDHIP_OK;
+}
+
 std::mutex g_multi_mu;
 std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
 int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
@@ -2325,6 +2420,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kPlaidTest: return check_plaid_test_call(c);
     case kPlaidTestContrasts: return check_plaid_test_contrasts_call(c);
     case kGsea: return check_gsea_call(c);
+    case kFisher: return check_fisher_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -2590,6 +2686,17 @@ int plaidhip_debug_gsea_scored_sharded_on_one_device(int device, int nshards, in
                                                      int32_t* le_len, int32_t* le_idx) try {
   return dispatch(on_hook(device, nshards, fail_shard),
                   gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_fisher_multi(const int* devices, int ndev, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp,
+                          const int32_t* Gi, int32_t m, double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx) try {
+  return dispatch(on_devices(devices, ndev), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fail_shard, const int8_t* sig, int32_t g, int32_t c,
+                                                const int32_t* Gp, const int32_t* Gi, int32_t m, double* out, double* tot_out,
+                                                int32_t* ov_len, int32_t* ov_idx) try {
+  return dispatch(on_hook(device, nshards, fail_shard), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_gsea_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat, const double* weight,

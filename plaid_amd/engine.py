@@ -349,6 +349,55 @@ def _gsea(fn, head, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=Fa
     return res if len(res) > 1 else out
 
 
+FISHER_MAX_GENES = 1 << 26   # PLAIDHIP_FISHER_MAX_GENES
+FISHER_COLUMNS = ("size", "ovUp", "ovDn", "pUp", "pDn", "pAny", "padjUp", "padjDn", "padjAny", "orUp", "orDn", "orAny")
+
+
+def check_fisher_args(sig):
+    """the checks of plaidhip_fisher on sig that need no device, in its order: sig as the ABI takes it, g genes x c lists
+    int8 of -1 / 0 / +1 (a vector is one list).  Values that are no integers in -1..1 (NaN among them) are refused here:
+    an int8 cannot hold them."""
+    a = np.asarray(sig)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.ndim != 2:
+        raise ValueError("fisher: sig must be genes x lists")
+    if a.shape[1] < 1:
+        raise ValueError("fisher: 0 lists (at least 1)")
+    if a.shape[0] > FISHER_MAX_GENES:
+        raise _lib.PlaidHipError(_lib.EUNSUPPORTED, f"fisher: {a.shape[0]} genes (at most {FISHER_MAX_GENES})")
+    if a.dtype != np.int8:
+        bad = ~np.isin(a, (-1, 0, 1))
+        if bad.any():
+            e = int(np.flatnonzero(bad.ravel(order="F"))[0])
+            raise ValueError(f"fisher: sig[{e}] = {a.ravel(order='F')[e]} (-1 down, 0, +1 up)")
+    return np.asfortranarray(a, dtype=np.int8)
+
+
+def _fisher(fn, head, sig, Gp, Gi, overlap=False):
+    """plaidhip_fisher / _multi / the hook: (out, tot) -- sets x 12 x lists (FISHER_COLUMNS) and the 2 x lists totals (nUp,
+    nDn) -- and with overlap also ov_len (sets x lists int32) and ov_idx (Gp[-1] x lists int32, -1 past a set's overlap)"""
+    sig = check_fisher_args(sig)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    g, c = sig.shape
+    m = len(Gp) - 1
+    out = np.full((m, 12, c), np.nan, dtype=np.float64, order="F")
+    tot = np.full((2, c), np.nan, dtype=np.float64, order="F")
+    ov_len = np.full((m, c), -7, dtype=np.int32, order="F") if overlap else None
+    ov_idx = np.full((int(Gp[-1]), c), -7, dtype=np.int32, order="F") if overlap else None
+    check(fn(*head, _np_ptr(sig), g, c, _np_ptr(Gp), _np_ptr(Gi), m, _np_ptr(out), _np_ptr(tot),
+             None if ov_len is None else _np_ptr(ov_len), None if ov_idx is None else _np_ptr(ov_idx)))
+    return (out, tot, ov_len, ov_idx) if overlap else (out, tot)
+
+
+def hyper_tail(N, K, k, x) -> float:
+    """plaidhip_hyper_tail: P(X >= x), X ~ Hypergeometric(N, K, k), by the form pinned in include/plaidhip.h, on the host
+    (no device is touched)"""
+    p = C.c_double(np.nan)
+    check(_lib.load().plaidhip_hyper_tail(int(N), int(K), int(k), int(x), C.byref(p)))
+    return p.value
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -728,6 +777,12 @@ class Context:
         return _gsea(self.lib.plaidhip_gsea_scored, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type,
                      leading_edge)
 
+    def fisher(self, sig, Gp, Gi, overlap=False):
+        """plaidhip_fisher: over-representation tests of the columns of sig (genes x lists of -1 / 0 / +1) against the sets:
+        (out, tot) -- sets x 12 x lists (FISHER_COLUMNS) and the 2 x lists totals nUp, nDn; with overlap also (ov_len, ov_idx),
+        the rows of every set with sig != 0, in the set's member order"""
+        return _fisher(self.lib.plaidhip_fisher, (self.handle,), sig, Gp, Gi, overlap)
+
     def gsea_permutations(self, g: int, nperm: int, seed=1) -> np.ndarray:
         """plaidhip_gsea_permutations: the genes x nperm int32 placements plaidhip_gsea generates from `seed`"""
         P = np.empty((int(g), int(nperm)), dtype=np.int32, order="F")
@@ -910,6 +965,11 @@ def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, 
     if gsea_score_type(score_type) == 0 and not leading_edge:
         return _gsea(*_multi("gsea", devices), stat, weight, Gp, Gi, perm, nperm, seed, null)
     return _gsea(*_multi("gsea_scored", devices), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type, leading_edge)
+
+
+def fisher_multi(sig, Gp, Gi, overlap=False, devices=1):
+    """plaid.fisher (Context.fisher) with the lists shared out over `devices`: the one-device bits"""
+    return _fisher(*_multi("fisher", devices), sig, Gp, Gi, overlap)
 
 
 def multi_finalize():

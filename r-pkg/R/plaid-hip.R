@@ -538,6 +538,72 @@ plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSi
 }
 
 
+## plaid.sig(): the lists plaid.fisher() takes, from gene-level results, by the rule of the enrichment experiments
+## (experiments/compare-enrichment/enrichment-methods.R:22-23): +1 where logFC > lfc & pvalue < pcut, -1 where
+## logFC < -lfc & pvalue < pcut, 0 elsewhere (an NA in either input gives 0).  logFC and pvalue: vectors or matrices of
+## one shape; the names of logFC are kept.  Runs on the host.
+plaid.sig <- function(logFC, pvalue, lfc = 0.2, pcut = 0.05) {
+  if (!identical(dim(logFC), dim(pvalue)) || length(logFC) != length(pvalue)) stop("plaid.sig: logFC and pvalue must have one shape")
+  hit <- !is.na(pvalue) & !is.na(logFC) & pvalue < pcut
+  s <- logFC
+  s[] <- 0L
+  s[hit & logFC > lfc] <- 1L
+  s[hit & logFC < -lfc] <- -1L
+  storage.mode(s) <- "integer"
+  s
+}
+
+
+## plaid.fisher(): over-representation analysis on the device -- what gset.fisher2(sig.up, sig.dn, gmt) gives the enrichment
+## experiments (experiments/compare-enrichment/enrichment-methods.R:29): Fisher's exact (hypergeometric, upper tail) test of
+## the genes significant up, down and either way against every set, for a named vector of -1 / 0 / 1 (plaid.sig makes one)
+## or for every column of a genes x contrasts matrix.  include/plaidhip.h (plaidhip_fisher) pins the statistic.  Genes are
+## aligned by name as plaid.gsea aligns them; the universe is the aligned rows.  Returns a matrix (a vector) or a named list
+## of matrices: sets x (size, ovUp, ovDn, pUp, pDn, pAny, padjUp, padjDn, padjAny, orUp, orDn, orAny), rows ordered by
+## sort.by (NA last).  overlap = TRUE returns, wherever a matrix is returned, list(table = <that matrix>, overlap = <named
+## list, one named integer vector per table row in the table's order: the sign of every member of the set that is in the
+## list, named by gene, in the set's member order>).
+plaid.fisher <- function(sig, G, minSize = 1, maxSize = NULL, sort.by = "pAny", overlap = FALSE) {
+  single <- is.null(dim(sig))
+  if (single) sig <- matrix(sig, ncol = 1, dimnames = list(names(sig), "sig"))
+  sig <- as.matrix(sig)
+  if (anyNA(sig) || !all(sig %in% c(-1, 0, 1))) stop("plaid.fisher: sig must hold -1, 0 or 1")
+  storage.mode(sig) <- "integer"
+  if (is.list(G)) {
+    message("[plaid.fisher] converting gmt to sparse matrix...")
+    G <- gmt2mat(G)
+  }
+  gg <- intersect(rownames(G), rownames(sig))
+  sig <- sig[gg, , drop = FALSE]
+  G <- G[gg, , drop = FALSE]
+  size <- Matrix::colSums(G != 0)
+  if (is.null(maxSize)) maxSize <- length(gg) - 1L
+  G <- G[, size >= minSize & size <= maxSize, drop = FALSE]
+  pat <- .aligned_pattern(sig, G)
+  .session()
+  want <- isTRUE(as.logical(overlap))
+  r <- .Call("R_plaidhip_fisher", .devices(), sig, pat$Gp, pat$Gi, want, PACKAGE = "plaidhip")
+  tab <- r[[1]]
+  dim(tab) <- c(nrow(tab), 12L, ncol(sig))
+  cols <- c("size", "ovUp", "ovDn", "pUp", "pDn", "pAny", "padjUp", "padjDn", "padjAny", "orUp", "orDn", "orAny")
+  out <- lapply(seq_len(ncol(sig)), function(l) {
+    res <- matrix(tab[, , l], nrow = dim(tab)[1], dimnames = list(colnames(G), cols))
+    o <- if (sort.by %in% cols) order(res[, sort.by]) else seq_len(nrow(res))
+    res <- res[o, , drop = FALSE]
+    if (!want) return(res)
+    ## the overlap of set j in list l: ov_idx[Gp[j] + seq_len(ov_len[j, l]), l], 0-based rows of the aligned genes
+    ov <- lapply(o, function(j) {
+      rows <- r[[4]][pat$Gp[j] + seq_len(r[[3]][j, l]), l] + 1L
+      stats::setNames(sig[rows, l], rownames(sig)[rows])
+    })
+    names(ov) <- rownames(res)
+    list(table = res, overlap = ov)
+  })
+  names(out) <- colnames(sig)
+  if (single) out[[1]] else out
+}
+
+
 ## replaid.gsva(), R/plaid.R:338-363: the row transform ("z" or "ecdf"), the signed ranks, the power and
 ## plaid() run on the device in one call.
 replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {

@@ -607,6 +607,47 @@ SEXP R_plaidhip_gsea_scored(SEXP devices, SEXP stat, SEXP weight, SEXP Gp, SEXP 
   return res;
 }
 
+/* plaid.fisher(): list(out, tot, ov_len, ov_idx) of plaidhip_fisher -- out an m x 12c matrix (columns 12 l + 1 .. 12 l + 12
+ * the columns of list l; the caller gives it dim m x 12 x c), tot 2 x c (nUp, nDn); ov_len (m x c integer) and ov_idx
+ * (Gp[m] x c integer, 0-based rows of sig, -1 behind a set's overlap), or NULL for both when no overlap lists are asked for.
+ * sig: a g x c integer matrix of -1 / 0 / 1 (R has no 8-bit integer: it is narrowed here; NA is refused); several
+ * devices: the _multi entry */
+SEXP R_plaidhip_fisher(SEXP devices, SEXP sig, SEXP Gp, SEXP Gi, SEXP overlap) {
+  const int g = Rf_nrows(sig), c = Rf_ncols(sig), m = LENGTH(Gp) - 1;
+  const int want = Rf_asLogical(overlap) == 1;
+  const size_t count = (size_t)g * (size_t)c;
+  int8_t* s8 = (int8_t*)R_alloc(count > 0 ? count : 1, 1);
+  const int* s = INTEGER(sig);
+  for (size_t e = 0; e < count; ++e) {
+    if (s[e] < -1 || s[e] > 1) Rf_error("plaid.fisher: sig holds a value that is not -1, 0 or 1 (or NA)");
+    s8[e] = (int8_t)s[e];
+  }
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 12 * c));
+  SEXP tot = PROTECT(Rf_allocMatrix(REALSXP, 2, c));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, tot);
+  int32_t *ov_len = NULL, *ov_idx = NULL;
+  if (want) {
+    SEXP len = PROTECT(Rf_allocMatrix(INTSXP, m, c));
+    SEXP idx = PROTECT(Rf_allocMatrix(INTSXP, INTEGER(Gp)[m], c));
+    SET_VECTOR_ELT(res, 2, len);
+    SET_VECTOR_ELT(res, 3, idx);
+    ov_len = INTEGER(len);
+    ov_idx = INTEGER(idx);
+    UNPROTECT(2);
+  }
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_fisher_multi(INTEGER(devices), LENGTH(devices), s8, g, c, INTEGER(Gp), INTEGER(Gi), m, REAL(out), REAL(tot),
+                               ov_len, ov_idx);
+  else
+    rc = plaidhip_fisher(ctx(), s8, g, c, INTEGER(Gp), INTEGER(Gi), m, REAL(out), REAL(tot), ov_len, ov_idx);
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(3);
+  return res;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -650,6 +691,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
     {"R_plaidhip_gsea", (DL_FUNC)&R_plaidhip_gsea, 9},
     {"R_plaidhip_gsea_scored", (DL_FUNC)&R_plaidhip_gsea_scored, 11},
+    {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {
