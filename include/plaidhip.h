@@ -95,7 +95,11 @@ int plaidhip_set_stream(plaidhip_ctx* ctx, void* stream);
 enum plaidhip_option {
   PLAIDHIP_OPT_SPMM_DENSE_KERNEL = 1,  /* 0 auto (default) | 1 one-column kernel | 2 pair kernel wherever it applies |
                                           3 dense 0/1 G x bf16x3 split of X on MFMA (BASELINE config 4's "GEMM" form:
-                                          ~145x the flops of the SpMM, ~1e-7 relative; measured beside it, never default) */
+                                          ~145x the flops of the SpMM, ~1e-7 relative; measured beside it, never default) |
+                                          4 as 0, but the pair kernel always in its 1,024-thread form with the slice
+                                          partial sums in a scratch, also where the collection qualifies for the
+                                          768-thread form that keeps them in registers (more than 10,224 genes and at most
+                                          6,144 sets): the same scores bit for bit; tests and A/B runs compare the two  */
   PLAIDHIP_OPT_SPMM_SPARSE_KERNEL = 2, /* 0 auto: by nnz(X) (default) | 1 scatter | 2 gather                        */
   PLAIDHIP_OPT_NT_STORE = 3,           /* -1 auto (default) | 0 plain stores of S | 1 streaming stores              */
   PLAIDHIP_OPT_RANKS_F32 = 4,          /* staging of RANK inputs in the crossprod, all three exact and bit-identical:

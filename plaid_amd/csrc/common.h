@@ -25,6 +25,11 @@ constexpr int kMaxLdsKeys = kLdsBytes / 8;               // 20480
 // pair kernel: 16-byte entries (two sample columns), 16 zero entries behind them
 constexpr int kPadSlotsPair = 16;
 constexpr int kMaxLdsGenesPair = kLdsBytes / 16 - kPadSlotsPair;   // 10224
+// pair plans of more than one gene slice whose tiles can be dealt to 12 wavefronts, at most 8 each (<= 6,144 sets): the
+// pair kernel runs them at 768 threads (3 wavefronts per SIMD: 168 vector registers each) and keeps a lane's partial sums of
+// the slices before in registers, one pair per tile
+constexpr int kPairRegWaves = 12;
+constexpr int kPairRegPartials = 8;
 constexpr int kMaxPairSlices = 8;
 // scatter kernel (sparse X): fp64 accumulators of one chunk of gene sets in LDS
 constexpr int kScatterTrash = 64;                      // accumulators behind a chunk that padded id slots add into
@@ -99,7 +104,7 @@ struct plaidhip_ctx {
   std::vector<cached_geneset> gs_cache;
   int precision = 0;   // PLAIDHIP_PRECISION_*: 0 fp64 throughout (default), 1 fp32 operand staging in the dense SpMM
   // plaidhip_set_option (include/plaidhip.h: enum plaidhip_option)
-  int opt_dense_kernel = 0;    // 0 auto | 1 one-column | 2 pair wherever it applies | 3 dense bf16x3 GEMM on MFMA
+  int opt_dense_kernel = 0;    // 0 auto | 1 one-column | 2 pair wherever it applies | 3 dense bf16x3 GEMM on MFMA | 4 auto, pair kernel in its scratch form
   int opt_sparse_kernel = 0;   // 0 auto | 1 scatter | 2 gather
   int opt_nt_store = -1;       // -1 auto | 0 | 1
   int opt_ranks_f32 = 2;       // rank inputs: 0 fp64 kernels | 1 fp32 staging | 2 u16 staging, integer sums (all exact)
@@ -188,12 +193,14 @@ struct plaidhip_pair_slice_dev {
   int32_t g0, gs;
 };
 struct plaidhip_pair_plan {
-  int32_t waves = 0;
+  int32_t waves = 0;                           // wavefronts that have tiles (the arrays are laid out for 16 either way)
+  bool regp = false;                           // built for kPairRegWaves wavefronts x <= kPairRegPartials tiles (see above)
   int32_t ktiles = 0;                          // wave-stream tiles (all waves)
   int64_t chunks = 0;
   std::vector<plaidhip_pair_slice> slices;
   plaidhip_pair_slice_dev* d_slices = nullptr;
   // partial sums between gene slices: [workgroup][wave-stream tile + 1][lane] x {A, B}
+  // (a regp plan has none until PLAIDHIP_OPT_SPMM_DENSE_KERNEL = 4 pins the scratch form: alloc_pair_partial)
   double* d_partial = nullptr;
   int32_t partial_wgs = 0;
   int32_t* d_wave_tile_off = nullptr;
@@ -390,6 +397,7 @@ double combine_p(const double* p, int np, int method);
 void p_adjust_fdr(const double* p, int64_t m, double* q);
 
 // kernels_spmm.hip
+int alloc_pair_partial(plaidhip_ctx* ctx, plaidhip_geneset* gs);   // geneset.cpp: the pair plan's slice-partial scratch, once
 int launch_spmm_dense_f64(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const double* X,
                           int64_t ldx, int32_t n, int stat, double alpha, const double* alpha_div,
                           double beta, double* S, int64_t lds, uint32_t* flags,

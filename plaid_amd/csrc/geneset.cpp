@@ -217,7 +217,8 @@ struct HostPlan {
 // waves reach the end-of-column barrier together.  PLAIDHIP_WAVE_WEIGHTS="a,b,c,d" overrides (tools/ build).
 void wave_weights(int waves, std::vector<double>& wt, const double* share16) {
   double age[4] = {1.0, 1.0, 1.0, 1.0};
-  if (waves == 16) { age[0] = share16[0]; age[1] = share16[1]; age[2] = share16[2]; age[3] = share16[3]; }
+  // (12: the register-partial pair plan, three wavefronts per SIMD -- its caller passes three shares)
+  if (waves == 16 || waves == kPairRegWaves) { age[0] = share16[0]; age[1] = share16[1]; age[2] = share16[2]; age[3] = waves == 16 ? share16[3] : 1.0; }
 #ifdef PLAIDHIP_DIAG
   if (const char* e = getenv("PLAIDHIP_WAVE_WEIGHTS")) {
     double a, b, c, d;
@@ -230,9 +231,10 @@ void wave_weights(int waves, std::vector<double>& wt, const double* share16) {
   for (int w = 0; w < waves; ++w) wt[w] = age[std::min(3, w / 4)];
 }
 
-// longest-processing-time assignment of tiles (cost[t]) to wavefronts with capacity weights
+// longest-processing-time assignment of tiles (cost[t]) to wavefronts with capacity weights; no wavefront gets more than
+// `cap` tiles (the caller sees to tiles <= waves * cap)
 void assign_tiles(const std::vector<int64_t>& cost, int waves, std::vector<std::vector<int32_t>>& mine,
-                  const double* share16) {
+                  const double* share16, int32_t cap = INT32_MAX) {
   const int32_t tiles = (int32_t)cost.size();
   std::vector<double> wt;
   wave_weights(waves, wt, share16);
@@ -245,6 +247,7 @@ void assign_tiles(const std::vector<int64_t>& cost, int waves, std::vector<std::
     int best = 0;
     double bv = 1e300;
     for (int w = 0; w < waves; ++w) {
+      if ((int64_t)mine[w].size() >= cap) continue;
       const double v = (load[w] + (double)cost[t]) / wt[w];
       if (v < bv) { bv = v; best = w; }
     }
@@ -413,12 +416,24 @@ struct PairPlanHost {
   std::vector<int32_t> meta_j;           // [k][lane], shared
   std::vector<double> meta_w, meta_k;
   int64_t chunks = 0;
+  bool regp = false;                     // dealt to kPairRegWaves wavefronts, at most kPairRegPartials tiles each
+  int live_waves = 0;
 };
 
 // Tiles (lane <-> set) and the tile -> wavefront assignment are the SAME in every gene slice, so a
 // lane meets the same set again in the next slice and its partial sum can round-trip through S
 // privately (no cross-wave hand-off).
-void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi, int waves, PairPlanHost& pp) {
+// A plan of more than one slice whose tiles fit kPairRegWaves wavefronts x kPairRegPartials is dealt to those alone
+// (`waves` stays the length of the per-wavefront arrays: the wavefronts behind have empty streams), and the kernel keeps
+// the partial sums in registers instead (pair_plan_regp; `allow_regp` false: the tools' probe of the 16-wavefront form).
+bool pair_plan_regp(int32_t g, int32_t m) {
+  return g > kMaxLdsGenesPair && (m + 63) / 64 <= kPairRegWaves * kPairRegPartials;
+}
+
+void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi, int waves, PairPlanHost& pp,
+                     bool allow_regp = true) {
+  const bool regp = allow_regp && waves >= kPairRegWaves && pair_plan_regp(g, m);
+  const int live = regp ? kPairRegWaves : waves;   // wavefronts that get tiles
   const int32_t nsl = (g + kMaxLdsGenesPair - 1) / kMaxLdsGenesPair;
   int32_t width = (g + nsl - 1) / nsl;
   width = (width + 1) & ~1;
@@ -473,7 +488,19 @@ void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
     t = std::min(1.0, std::max(0.0, t));
     for (int q = 0; q < 4; ++q) share[q] = lo[q] + t * (hi[q] - lo[q]);
   }
-  assign_tiles(tot, waves, mine, share);
+  if (regp) {
+    // three wavefronts per SIMD: with these shares the three age classes spend the same time in the gather loop (in-kernel
+    // stamps per wavefront at C2, tools/bench_spmm.py --ablate 4: 1.50 / 1.50 / 1.48 M cycles; with {1.30, 1.00, 0.70} the
+    // youngest class ran 9 % longer than the oldest, with equal shares the launch took 4 % longer;
+    // profiles/pair_regp_stamps.txt).  The cap takes what the oldest class cannot hold (8 tiles where its share asks for 8.8).
+    static const double s12[3] = {1.34, 1.00, 0.66};
+    assign_tiles(tot, live, mine, s12, kPairRegPartials);
+    mine.resize(waves);
+  } else {
+    assign_tiles(tot, waves, mine, share);
+  }
+  pp.regp = regp;
+  pp.live_waves = live;
   pp.wave_tile_off.assign(waves + 1, 0);
   std::vector<int32_t> ktile;   // wave-stream order -> tile
   for (int w = 0; w < waves; ++w) {
@@ -542,6 +569,19 @@ int upload(plaidhip_ctx* ctx, const std::vector<T>& h, T** d) {
 }  // namespace
 
 namespace plaidhip {
+// the scratch of the partial sums between gene slices: [workgroup][wave-stream tile + 1][lane] x {A, B}
+int alloc_pair_partial(plaidhip_ctx* ctx, plaidhip_geneset* gs) {
+  if (gs->pair.d_partial != nullptr) return PLAIDHIP_OK;
+  gs->pair.partial_wgs = ctx->num_cu;
+  const size_t bytes = (size_t)gs->pair.partial_wgs * (gs->pair.ktiles + 1) * 64 * 2 * sizeof(double);
+  if (hipMalloc(reinterpret_cast<void**>(&gs->pair.d_partial), bytes) != hipSuccess) {
+    gs->pair.d_partial = nullptr;
+    set_error("hipMalloc(%zu) for the slice partial sums failed", bytes);
+    return PLAIDHIP_ENOMEM;
+  }
+  return PLAIDHIP_OK;
+}
+
 int spmm_block_for_genes(int32_t g) {
 #ifdef PLAIDHIP_DIAG
   static const char* e = getenv("PLAIDHIP_SPMM_BLOCK");   // tuning knob (tools/ build)
@@ -636,8 +676,9 @@ extern "C" int plaidhip_geneset_create(plaidhip_ctx* ctx, int32_t g, int32_t m, 
     // pair plan (two sample columns per LDS entry) for the dense-X kernel
     PairPlanHost pp;
     std::vector<plaidhip_pair_slice_dev> hd;
-    gs->pair.waves = 16;
-    build_pair_plan(g, m, Gp, Gi, gs->pair.waves, pp);
+    build_pair_plan(g, m, Gp, Gi, 16, pp);
+    gs->pair.waves = pp.live_waves;
+    gs->pair.regp = pp.regp;
     TSW("pair plan built");
     gs->pair.chunks = pp.chunks;
     if ((rc = upload(ctx, pp.wave_tile_off, &gs->pair.d_wave_tile_off)) != PLAIDHIP_OK) goto fail;
@@ -657,16 +698,9 @@ extern "C" int plaidhip_geneset_create(plaidhip_ctx* ctx, int32_t g, int32_t m, 
     for (const plaidhip_pair_slice& d : gs->pair.slices)
       hd.push_back(plaidhip_pair_slice_dev{d.d_tile_idx, d.d_wave_chunk_off, d.d_wtile_end, d.g0, d.gs});
     if ((rc = upload(ctx, hd, &gs->pair.d_slices)) != PLAIDHIP_OK) goto fail;
-    gs->pair.ktiles = pp.wave_tile_off[gs->pair.waves];
-    if (gs->pair.slices.size() > 1) {
-      gs->pair.partial_wgs = ctx->num_cu;
-      const size_t bytes = (size_t)gs->pair.partial_wgs * (gs->pair.ktiles + 1) * 64 * 2 * sizeof(double);
-      if (hipMalloc(reinterpret_cast<void**>(&gs->pair.d_partial), bytes) != hipSuccess) {
-        set_error("hipMalloc(%zu) for the slice partial sums failed", bytes);
-        rc = PLAIDHIP_ENOMEM;
-        goto fail;
-      }
-    }
+    gs->pair.ktiles = pp.wave_tile_off[16];
+    // (a register-partial plan needs no scratch; launch_colpair allocates one if the scratch form is pinned)
+    if (gs->pair.slices.size() > 1 && !gs->pair.regp && (rc = alloc_pair_partial(ctx, gs)) != PLAIDHIP_OK) goto fail;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = PLAIDHIP_EHIP; goto fail; }
   }
   TSW("pair plan uploaded");
@@ -904,7 +938,8 @@ extern "C" int plaidhip_geneset_info(const plaidhip_geneset* gs, int64_t info[8]
 // Diagnostic / test hook (not part of include/plaidhip.h): builds the pair plan on the host only
 // and checks it.  out[0]=slices out[1]=chunks (all slices) out[2]=memberships found in the plan
 // out[3]=conflicts (two lanes of one ds_read_b128 lane group on the same 16-byte slot in one
-// step) out[4]=memberships scheduled for the wrong set / twice / out of slice.
+// step) out[4]=memberships scheduled for the wrong set / twice / out of slice.  out[5..7]: the register-partial form
+// (eligible, most tiles on one wavefront, wavefronts with tiles).
 extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
                                               int32_t waves, int64_t out[8]) try {
   PairPlanHost pp;
@@ -944,6 +979,11 @@ extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_
   out[2] = found;
   out[3] = conflicts;
   out[4] = wrong;
+  int64_t most = 0;
+  for (int w = 0; w < waves; ++w) most = std::max<int64_t>(most, pp.wave_tile_off[w + 1] - pp.wave_tile_off[w]);
+  out[5] = pp.regp ? 1 : 0;     // dealt to kPairRegWaves wavefronts for the register-partial form of the kernel
+  out[6] = most;                // tiles of the wavefront with the most (regp: <= kPairRegPartials)
+  out[7] = pp.live_waves;       // wavefronts that may have tiles
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 

@@ -407,6 +407,9 @@ spmm_colgather_f64(SpmmArgs a) {
 // one launch; partial sums rest in a private [workgroup][tile][lane] scratch (L2-resident) between
 // slices, the epilogue runs in the last slice.  The host schedule (geneset.cpp, plan_tile_b128)
 // is conflict-free for the four 16-lane groups a ds_read_b128 is served in.
+// BLOCK = 768, REGP: the form for plans of more than one slice and at most 12 x 8 tiles (common.h, kPairRegWaves): a lane keeps
+// the partial sums of its wavefront's tiles in registers across the slices of a pair -- no scratch, no store or load at the
+// tile ends; the same tiles, the same sums, the same bits.
 struct SpmmPairArgs {
   const double* X;
   int64_t ldx;
@@ -466,11 +469,14 @@ __device__ __forceinline__ f64x2 lds_pair_at(uint32_t byte_off) {
 // bracket sits around the column's MEAN score, which the workgroup computes from the X it stages: sum_i x[i, c] u[i].
 // PNT: the partial sums of the slice before are read with non-temporal loads (a compile-time form: hipcc merges the two
 // arms of a run-time choice into ONE plain load).
-template <bool STAMP, int ABL = 0, bool CSC_X = false, bool MED = false, bool PNT = false>
-__global__ void __launch_bounds__(1024)
+template <bool STAMP, int ABL = 0, bool CSC_X = false, bool MED = false, bool PNT = false, int BLOCK = 1024, bool REGP = false>
+__global__ void __launch_bounds__(BLOCK)
 spmm_colpair_f64(SpmmPairArgs a) {
-  constexpr int BLOCK = 1024;
+  constexpr int NI = (kMaxLdsGenesPair / 2 + BLOCK - 1) / BLOCK;   // 16-byte loads per lane and column that cover a slice
+  static_assert(NI <= 7, "prefetch registers");
   static_assert(!(MED && CSC_X), "the classifying epilogue is built for dense X");
+  static_assert(!MED || (BLOCK == 1024 && !REGP), "the classifying epilogue sums 16 wavefronts and meets no register-partial plan");
+  static_assert(!REGP || !PNT, "no scratch to read in the register-partial form");
   if (spec_guard(a.spec, a.spec_gen, a.flags)) return;
   if constexpr (CSC_X) {
     if (a.sparse_cells != 0 && ((int64_t)a.Xp[a.n] - a.Xp[0]) * 8 < a.sparse_cells) return;
@@ -495,17 +501,17 @@ spmm_colpair_f64(SpmmPairArgs a) {
   const int tk_begin = ((cptr_i32)a.wave_tile_off)[wave];
   const int ns = a.nslices;
   const bool is_mean = a.stat == PLAIDHIP_STAT_MEAN;
-  f64x2 p0, p1, p2, p3, p4, p5, p6, p7, p8, p9;   // next slice: p0..p4 column A, p5..p9 column B
-  p0 = p1 = p2 = p3 = p4 = p5 = p6 = p7 = p8 = p9 = f64x2{0.0, 0.0};
+  f64x2 pa0, pa1, pa2, pa3, pa4, pa5, pa6, pb0, pb1, pb2, pb3, pb4, pb5, pb6;   // next slice: pa column A, pb column B (NI of each)
+  pa0 = pa1 = pa2 = pa3 = pa4 = pa5 = pa6 = pb0 = pb1 = pb2 = pb3 = pb4 = pb5 = pb6 = f64x2{0.0, 0.0};
 
 #define PLAIDHIP_PF_ONE(k, reg, base)                                                              \
-  if ((k + 1) * BLOCK <= g2_) {                                                                     \
+  if constexpr (k < NI) { if ((k + 1) * BLOCK <= g2_) {                                                                   \
     reg = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(base + (size_t)k * BLOCK * 16 + lane_off16)); \
   } else { /* dead during the gather loop: never carries an old value across it */                  \
     reg = f64x2{0.0, 0.0};                                                                          \
     if (k * BLOCK < g2_ && tid + k * BLOCK < g2_)                                                   \
       reg = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(base + (size_t)k * BLOCK * 16 + lane_off16)); \
-  }
+  } }
 #define PLAIDHIP_PREFETCH(pp_, si_)                                                                 \
   do {                                                                                              \
     uint32_t lane_off16 = (uint32_t)tid * 16u;                                                      \
@@ -516,13 +522,15 @@ spmm_colpair_f64(SpmmPairArgs a) {
     const int cb_ = (ca_ + 1 < a.n) ? ca_ + 1 : ca_;                                                \
     const char* xa_ = reinterpret_cast<const char*>(a.X + (int64_t)ca_ * a.ldx + g0_);              \
     const char* xb_ = reinterpret_cast<const char*>(a.X + (int64_t)cb_ * a.ldx + g0_);              \
-    PLAIDHIP_PF_ONE(0, p0, xa_) PLAIDHIP_PF_ONE(1, p1, xa_) PLAIDHIP_PF_ONE(2, p2, xa_)             \
-    PLAIDHIP_PF_ONE(3, p3, xa_) PLAIDHIP_PF_ONE(4, p4, xa_)                                         \
-    PLAIDHIP_PF_ONE(0, p5, xb_) PLAIDHIP_PF_ONE(1, p6, xb_) PLAIDHIP_PF_ONE(2, p7, xb_)             \
-    PLAIDHIP_PF_ONE(3, p8, xb_) PLAIDHIP_PF_ONE(4, p9, xb_)                                         \
+    PLAIDHIP_PF_ONE(0, pa0, xa_) PLAIDHIP_PF_ONE(1, pa1, xa_) PLAIDHIP_PF_ONE(2, pa2, xa_)          \
+    PLAIDHIP_PF_ONE(3, pa3, xa_) PLAIDHIP_PF_ONE(4, pa4, xa_) PLAIDHIP_PF_ONE(5, pa5, xa_)          \
+    PLAIDHIP_PF_ONE(6, pa6, xa_)                                                                    \
+    PLAIDHIP_PF_ONE(0, pb0, xb_) PLAIDHIP_PF_ONE(1, pb1, xb_) PLAIDHIP_PF_ONE(2, pb2, xb_)          \
+    PLAIDHIP_PF_ONE(3, pb3, xb_) PLAIDHIP_PF_ONE(4, pb4, xb_) PLAIDHIP_PF_ONE(5, pb5, xb_)          \
+    PLAIDHIP_PF_ONE(6, pb6, xb_)                                                                    \
   } while (0)
 #define PLAIDHIP_ST_ONE(k, ra, rb)                      \
-  if (k * BLOCK < g2) {                                  \
+  if constexpr (k < NI) if (k * BLOCK < g2) {            \
     const int i_ = tid_o + k * BLOCK;                    \
     if (i_ < g2) {                                       \
       ent[2 * i_] = f64x2{ra.x, rb.x};                   \
@@ -532,7 +540,26 @@ spmm_colpair_f64(SpmmPairArgs a) {
 
   int p = blockIdx.x;
   if (!CSC_X && p < a.npairs) PLAIDHIP_PREFETCH(p, 0);
-  const char* part = reinterpret_cast<const char*>(a.partial + (size_t)blockIdx.x * (size_t)(a.ktiles + 1) * 64);  // uniform
+  // partial sums of the slices before: REGP -- up to kPairRegPartials tiles per wavefront, one register pair per lane and tile,
+  // alive across the slices of a pair (slot = tile ordinal within the wavefront's stream); otherwise the workgroup's scratch
+  const char* part = nullptr;
+  if constexpr (!REGP) part = reinterpret_cast<const char*>(a.partial + (size_t)blockIdx.x * (size_t)(a.ktiles + 1) * 64);  // uniform
+  f64x2 r0, r1, r2, r3, r4, r5, r6, r7;
+  r0 = r1 = r2 = r3 = r4 = r5 = r6 = r7 = f64x2{0.0, 0.0};
+  static_assert(kPairRegPartials == 8, "register slots r0..r7");
+// wave-uniform slot choice (s_ is a scalar): once per tile and slice
+#define PLAIDHIP_RSLOT_PUT(s_, v_)                                                     \
+  switch (s_) {                                                                        \
+    case 0: r0 = (v_); break; case 1: r1 = (v_); break; case 2: r2 = (v_); break;      \
+    case 3: r3 = (v_); break; case 4: r4 = (v_); break; case 5: r5 = (v_); break;      \
+    case 6: r6 = (v_); break; default: r7 = (v_); break;                               \
+  }
+#define PLAIDHIP_RSLOT_GET(s_, o_)                                                     \
+  switch (s_) {                                                                        \
+    case 0: o_ = r0; break; case 1: o_ = r1; break; case 2: o_ = r2; break;            \
+    case 3: o_ = r3; break; case 4: o_ = r4; break; case 5: o_ = r5; break;            \
+    case 6: o_ = r6; break; default: o_ = r7; break;                                   \
+  }
 
   // MED: wave-uniform state of the pair being written (scalar registers)
   double med_dotA = 0.0, med_dotB = 0.0;                      // this thread's share of sum_i x[i, c] u[i]
@@ -565,19 +592,19 @@ spmm_colpair_f64(SpmmPairArgs a) {
       int tid_o = tid;
       asm volatile("" : "+v"(tid_o));
       if constexpr (MED) {
-        // this slice's share of the column means: the prefetched X of the slice is in p0..p9 (zero past the slice's end), u
+        // this slice's share of the column means: the prefetched X of the slice is in pa0.. / pb0.. (zero past the slice's end), u
         // comes from L2 (160 KB per statistic); unconditional loads at clamped indices: one round trip for all five
         const char* ub_ = reinterpret_cast<const char*>(a.med_u + sl->g0);
         const int last2_ = g2 > 0 ? g2 - 1 : 0;
 #define PLAIDHIP_DOT_ONE(k, ra, rb)                                                                    \
-  if (k * BLOCK < g2) {                                                                                 \
+  if constexpr (k < NI) if (k * BLOCK < g2) {                                                                              \
     const int i_ = tid_o + k * BLOCK;                                                                   \
     const f64x2 u_ = *reinterpret_cast<const f64x2*>(ub_ + (size_t)(i_ < last2_ ? i_ : last2_) * 16);  \
     med_dotA += ra.x * u_.x + ra.y * u_.y;                                                              \
     med_dotB += rb.x * u_.x + rb.y * u_.y;                                                              \
   }
-        PLAIDHIP_DOT_ONE(0, p0, p5) PLAIDHIP_DOT_ONE(1, p1, p6) PLAIDHIP_DOT_ONE(2, p2, p7)
-        PLAIDHIP_DOT_ONE(3, p3, p8) PLAIDHIP_DOT_ONE(4, p4, p9)
+        PLAIDHIP_DOT_ONE(0, pa0, pb0) PLAIDHIP_DOT_ONE(1, pa1, pb1) PLAIDHIP_DOT_ONE(2, pa2, pb2)
+        PLAIDHIP_DOT_ONE(3, pa3, pb3) PLAIDHIP_DOT_ONE(4, pa4, pb4)
 #undef PLAIDHIP_DOT_ONE
         if ((gs_ & 1) && tid == 0) {
           const int64_t gl = (int64_t)sl->g0 + gs_ - 1;
@@ -613,8 +640,9 @@ spmm_colpair_f64(SpmmPairArgs a) {
       }
       if constexpr (!CSC_X) {
         // ---- stage the slice of both columns, interleaved ---------------------------------
-        PLAIDHIP_ST_ONE(0, p0, p5) PLAIDHIP_ST_ONE(1, p1, p6) PLAIDHIP_ST_ONE(2, p2, p7)
-        PLAIDHIP_ST_ONE(3, p3, p8) PLAIDHIP_ST_ONE(4, p4, p9)
+        PLAIDHIP_ST_ONE(0, pa0, pb0) PLAIDHIP_ST_ONE(1, pa1, pb1) PLAIDHIP_ST_ONE(2, pa2, pb2)
+        PLAIDHIP_ST_ONE(3, pa3, pb3) PLAIDHIP_ST_ONE(4, pa4, pb4) PLAIDHIP_ST_ONE(5, pa5, pb5)
+        PLAIDHIP_ST_ONE(6, pa6, pb6)
         if ((gs_ & 1) && tid == 0) {
           const int64_t gl = (int64_t)sl->g0 + gs_ - 1;
           ent[gs_ - 1] = f64x2{a.X[(int64_t)cA * a.ldx + gl], a.X[(int64_t)cB * a.ldx + gl]};
@@ -731,7 +759,9 @@ spmm_colpair_f64(SpmmPairArgs a) {
     const double sumA = ((a0 + a1) + (a2 + a3)) + old.x;                                       \
     const double sumB = ((b0 + b1) + (b2 + b3)) + old.y;                                       \
     if (!last) {                                                                               \
-      if (PH_PAIR_PSTORE) {                                                                    \
+      if constexpr (REGP) {                                                                    \
+        PLAIDHIP_RSLOT_PUT(k - tk_begin, (f64x2{sumA, sumB}))                                  \
+      } else if (PH_PAIR_PSTORE) {                                                                 \
         f64x2* dst_ = reinterpret_cast<f64x2*>(const_cast<char*>(part) + (int64_t)PH_PAIR_PSLOT(k) * 1024 + ioff);  \
         if (PH_PAIR_PST_NT) __builtin_nontemporal_store(f64x2{sumA, sumB}, dst_);              \
         else if (PH_PAIR_PST_SC1) {                                                            \
@@ -758,7 +788,9 @@ spmm_colpair_f64(SpmmPairArgs a) {
       mw = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.meta_w) + (int64_t)k * 512 + moff8);   \
       mk = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.meta_k) + (int64_t)k * 512 + moff8);   \
     }                                                                                          \
-    if (!first && PH_PAIR_PLOAD) {                                                             \
+    if constexpr (REGP) {                                                                      \
+      if (!first) { PLAIDHIP_RSLOT_GET(k - tk_begin, old) }                                    \
+    } else if (!first && PH_PAIR_PLOAD) {                                                      \
       const f64x2* src_ = reinterpret_cast<const f64x2*>(part + (int64_t)PH_PAIR_PSLOT(k) * 1024 + ioff);  \
       if (PH_PAIR_PLD_SC1) {                                                                   \
         old.x = __hip_atomic_load(reinterpret_cast<const double*>(src_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      \
@@ -788,7 +820,9 @@ spmm_colpair_f64(SpmmPairArgs a) {
           mk = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.meta_k) + (int64_t)k * 512 + moff8);
         }
         f64x2 old = f64x2{0.0, 0.0};
-        if (!first && PH_PAIR_PLOAD) {
+        if constexpr (REGP) {
+          if (!first) old = r0;
+        } else if (!first && PH_PAIR_PLOAD) {
           const f64x2* src_ = reinterpret_cast<const f64x2*>(part + (int64_t)PH_PAIR_PSLOT(k) * 1024 + ioff);
           old = (PH_PAIR_PLD_NT || PNT) ? __builtin_nontemporal_load(src_) : *src_;
         }
@@ -851,7 +885,7 @@ spmm_colpair_f64(SpmmPairArgs a) {
       if (want_pf) {
         PLAIDHIP_PREFETCH(np, nsi);
       } else {  // (tells the register allocator the old values are not needed across the gather loop)
-        p0 = p1 = p2 = p3 = p4 = p5 = p6 = p7 = p8 = p9 = f64x2{0.0, 0.0};
+        pa0 = pa1 = pa2 = pa3 = pa4 = pa5 = pa6 = pb0 = pb1 = pb2 = pb3 = pb4 = pb5 = pb6 = f64x2{0.0, 0.0};
       }
       if constexpr (STAMP) ts2 = __builtin_amdgcn_s_memtime();
       __syncthreads();  // the slice is overwritten by the next iteration
@@ -883,6 +917,8 @@ spmm_colpair_f64(SpmmPairArgs a) {
 #undef PLAIDHIP_PREFETCH
 #undef PLAIDHIP_PF_ONE
 #undef PLAIDHIP_ST_ONE
+#undef PLAIDHIP_RSLOT_PUT
+#undef PLAIDHIP_RSLOT_GET
 }
 
 
@@ -2171,7 +2207,8 @@ static int nt_store_mode(const plaidhip_ctx* ctx, const plaidhip_geneset* gs) {
 }
 
 // which dense-X kernel (plaidhip_set_option(PLAIDHIP_OPT_SPMM_DENSE_KERNEL)): 0 one-column, 1 default (pair where
-// it applies), 2 pair wherever possible
+// it applies), 2 pair wherever possible.  (Option value 4 chooses like the default and only pins the form of the pair kernel:
+// launch_colpair.)
 static int pair_kernel_mode(const plaidhip_ctx* ctx) {
   return ctx->opt_dense_kernel == 1 ? 0 : (ctx->opt_dense_kernel == 2 ? 2 : 1);
 }
@@ -2196,6 +2233,18 @@ static int launch_colpair(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const d
   int32_t gmax = 0;
   for (const plaidhip_pair_slice& sl : pl.slices) gmax = sl.gs > gmax ? sl.gs : gmax;
   const size_t smem = (size_t)(gmax + kPadSlotsPair) * 16;
+  // A plan built for kPairRegWaves wavefronts with at most kPairRegPartials tiles each (geneset.cpp) runs at 768 threads with
+  // the partial sums of the slices in registers: no scratch, no store and no load at the tile ends.  Option value 4 pins
+  // the 1,024-thread scratch form on the same plan (its last four wavefronts then have no tiles): same tiles, same sums.
+  const bool regp = pl.regp && ctx->opt_dense_kernel != 4 && (g_ablate == 0 || g_ablate == 4);
+  if (regp && med != nullptr) {
+    set_error("pair kernel: the classifying epilogue met a register-partial plan (%d sets)", gs->m);
+    return PLAIDHIP_EINVAL;
+  }
+  if (!regp && pl.slices.size() > 1 && pl.d_partial == nullptr) {
+    const int rc = alloc_pair_partial(ctx, const_cast<plaidhip_geneset*>(gs));   // (an eligible plan has none until it is pinned)
+    if (rc != PLAIDHIP_OK) return rc;
+  }
   PH_FULL_LDS(ctx, (&spmm_colpair_f64<false>));
   SpmmPairArgs a{};
   a.X = X;
@@ -2233,9 +2282,26 @@ static int launch_colpair(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const d
   if (per_cu > 2) per_cu = 2;
   if (per_cu < 1) per_cu = 1;
   int grid = ctx->num_cu * per_cu;
-  if (a.nslices > 1 && grid > pl.partial_wgs) grid = pl.partial_wgs;
+  if (!regp && a.nslices > 1 && grid > pl.partial_wgs) grid = pl.partial_wgs;
   if (grid > a.npairs) grid = a.npairs;
-  if (med != nullptr) {   // dense X, medians selected on the fly
+  if (regp) {
+    a.partial = nullptr;
+    if (Xp != nullptr) {   // sparse X
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, true>), dim3(grid),
+                         dim3(kPairRegWaves * 64), smem, ctx->stream, a);
+    }
+#ifdef PLAIDHIP_DIAG
+#define PH_DIAG_SECTION 15
+#include "kernels_spmm_diag.inc"
+#undef PH_DIAG_SECTION
+#endif
+    else {
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, true>), dim3(grid),
+                         dim3(kPairRegWaves * 64), smem, ctx->stream, a);
+    }
+  } else if (med != nullptr) {   // dense X, medians selected on the fly
     a.med_u = med->u;
     a.med_beta_kappa = med->beta_kappa;
     a.med_cal = med->cal;

@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--ablate", type=int, default=0, help="diagnostic SpMM variant 1..7 (wrong results by design; needs PLAIDHIP_LIB=<the make diag library>)")
     ap.add_argument("--fused", action="store_true", help="c3 / c4: medians selected inside the crossprod launch (dev_spmm_csc_fused / dev_spmm_dense_fused + dev_col_medians_resume)")
     ap.add_argument("--stamps", action="store_true", help="in-kernel phase stamps of the scatter kernel (diag library)")
-    ap.add_argument("--dense-kernel", default="auto", choices=["auto", "single", "pair", "mfma"])
+    ap.add_argument("--dense-kernel", default="auto", choices=["auto", "single", "pair", "mfma", "pair_scratch"])
     ap.add_argument("--sparse-kernel", default="auto", choices=["auto", "scatter", "gather"])
     ap.add_argument("--nt-store", default="auto", choices=["auto", "off", "on"], help="non-temporal stores of the scores")
     ap.add_argument("--scatter-fixed", default="on", choices=["on", "off"], help="c3: u64 fixed-point accumulators in the scatter kernel")
@@ -243,6 +243,8 @@ def main():
                   f"({100*d[:,2].mean()/tot:.0f}%)  passes per column (last launch) {d[:,3].sum() / n:.2f}")
     if a.ablate == 4 or a.ablate in (2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16):
         waves = info["waves"]
+        if g > 10224 and (m + 63) // 64 <= 96 and a.dense_kernel != "pair_scratch" and a.ablate == 4:
+            waves = 12   # the 768-thread register-partial form of the pair kernel (stamps are laid out per launched wavefront)
         nwg = min(n, 256)
         d = dbg.cpu().numpy()[: nwg * waves * 4].reshape(nwg, waves, 4).astype(float)
         tot = d[:, :, 3].mean()
@@ -251,6 +253,7 @@ def main():
               f"end-barrier wait {d[:,:,2].mean():.0f} ({100*d[:,:,2].mean()/tot:.1f}%) total {tot:.0f}")
         print("  per-wave gather cycles, WG 0:", d[0, :, 1].astype(int).tolist())
         print("  per-wave wait   cycles, WG 0:", d[0, :, 2].astype(int).tolist())
+        print("  per-wave gather cycles, mean over WGs:", d[:, :, 1].mean(axis=0).astype(int).tolist())
     if a.kernel == "spmm":
         z = int(Gp[-1])
         b = g * n * 8 + 4 * z + 4 * (m + 1) + m * n * 8

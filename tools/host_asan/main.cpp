@@ -48,7 +48,8 @@ static void plans() {
   const Case cases[] = {{37, 3, 1, 30, true},      {1000, 70, 1, 200, false},  {10224, 130, 5, 300, true},
                         {10226, 129, 5, 300, false}, {20000, 700, 15, 500, true}, {20448, 65, 1, 2000, false},
                         {20449, 64, 15, 500, true}, {45000, 300, 15, 500, false}, {1, 5, 1, 1, true},
-                        {20000, 5000, 15, 500, true}, {20000, 50000, 15, 500, true}};
+                        {20000, 5000, 15, 500, true}, {20000, 50000, 15, 500, true}, {10225, 6144, 15, 40, true},
+                        {30001, 6145, 15, 40, false}};
   plaidhip_ctx ctx;
   for (const Case& c : cases) {
     std::vector<int32_t> Gp, Gi;
@@ -57,6 +58,9 @@ static void plans() {
     REQUIRE(plaidhip_debug_pair_plan_check(c.g, c.m, Gp.data(), Gi.data(), 16, out) == PLAIDHIP_OK);
     REQUIRE(out[2] == (int64_t)Gi.size());   // every membership scheduled exactly once
     REQUIRE(out[4] == 0);                    // none for the wrong set, twice, or outside its slice
+    // more than one slice and at most 12 x 8 tiles: dealt to 12 wavefronts, no more than 8 tiles each (register partials)
+    REQUIRE(out[5] == ((c.g > plaidhip::kMaxLdsGenesPair && (c.m + 63) / 64 <= plaidhip::kPairRegWaves * plaidhip::kPairRegPartials) ? 1 : 0));
+    if (out[5]) REQUIRE(out[6] <= plaidhip::kPairRegPartials && out[7] == plaidhip::kPairRegWaves);
     plaidhip_geneset* gs = nullptr;
     REQUIRE(plaidhip_geneset_create(&ctx, c.g, c.m, Gp.data(), Gi.data(), &gs) == PLAIDHIP_OK);
     int64_t info[8];

@@ -1,7 +1,8 @@
 // Host-only probe of the gene-set planners (geneset.cpp) on a collection read from a file: how long
 // plaidhip_geneset_create takes, how many bytes it uploads, the slot efficiency (real / padded index slots) of the
 // one-column and pair plans, and the pair plan's self-check (every membership scheduled exactly once, in its slice, for
-// its set; bank conflicts beyond the deliberate two-way ones).  Built with g++ against the host stand-ins of the HIP
+// its set; bank conflicts beyond the deliberate two-way ones; whether the plan is the 12-wavefront register-partial form
+// and the most tiles one wavefront got).  Built with g++ against the host stand-ins of the HIP
 // runtime (tools/host_asan/hip_stubs.cpp) by `make -C plaid_amd/csrc plan-probe`; tests/test_host_logic.py runs it on a
 // collection with the shape of the reference's benchmark (61,459 sets, Zipf gene popularity, an all-genes set).
 // File: int32 g, int32 m, int32 Gp[m + 1], int32 Gi[Gp[m]] (little endian).  Prints one JSON object.
@@ -51,9 +52,9 @@ int main(int argc, char** argv) {
          ", \"pair_slices\": %" PRId64 ", \"pair_found\": %" PRId64 ", \"pair_conflicts\": %" PRId64 ", \"pair_wrong\": %" PRId64
          ", \"scatter_chunks\": %" PRId64 ", \"scatter_segments\": %" PRId64 ", \"scatter_found\": %" PRId64
          ", \"scatter_wrong\": %" PRId64 ", \"scatter_instructions\": %" PRId64 ", \"scatter_collisions\": %" PRId64
-         ", \"check_s\": %.3f}\n",
+         ", \"pair_regp\": %" PRId64 ", \"pair_most_tiles\": %" PRId64 ", \"pair_waves\": %" PRId64 ", \"check_s\": %.3f}\n",
          g, m, info[2], sec, live, info[3], info[7], info[5], pc[0], pc[2], pc[3], pc[4], sc[0], sc[1], sc[2], sc[3], sc[4],
-         sc[5], sec_check);
+         sc[5], pc[5], pc[6], pc[7], sec_check);
   plaidhip_geneset_destroy(gs);
   return 0;
 }
