@@ -992,6 +992,87 @@ int plaidhip_fisher_multi(const int* devices, int ndev, const int8_t* sig, int32
                           const int32_t* Gi, int32_t m, double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx);
 int plaidhip_hyper_tail(int64_t N, int64_t K, int64_t k, int64_t x, double* p);
 
+/* plaid.limma(A, design, contrasts): limma's moderated t-test -- lmFit + eBayes + topTable -- of every row of A (the
+ * single-sample scores of the sets, or the expression of the genes) for one or several designs.  The form is limma's AS
+ * RECALLED: its source is not in this tree, so the statistic is pinned here and tested against these words in 50-digit
+ * arithmetic and against an independent least-squares restatement.
+ * Operands: A rows x n doubles, column-major, one row per set or gene.  nfit designs D_f, each n x p column-major, D_f at
+ * design + f * n * p; p is the same for every fit, 1 <= p <= PLAIDHIP_LIMMA_MAX_COEF.  use: n x nfit int8, column-major,
+ * 0 = the sample takes no part in fit f (NULL: every sample in every fit).  K: the contrasts, p x q column-major, shared
+ * by the fits (NULL: the p unit vectors, and q must be p).  For fit f, sel are its used samples and n_f their number.
+ * 1. The design, on the host in fp64.  Householder QR without pivoting of the rows sel of D_f, column k reflected by
+ *    x - alpha e_1 with alpha = -sign(x_1) ||x||_2 (sign(0) = +1), R_kk = alpha: Q_f (n x p, thin, the rows of excluded
+ *    samples zero) and R_f (p x p, upper).  Column k is rank-deficient when |R_kk| <= 1e-7 ||D_f[sel, k]||_2.
+ *    For contrast j: v_j = R_f^-T K_j by forward substitution, u_j = sqrt(sum_k v_jk^2) in ascending k (limma's
+ *    stdev.unscaled), and logFC = v_j' E = sum_k v_jk E_k by fma in ascending k from 0.0, on the host: no coefficient
+ *    vector is formed.
+ * 2. Per row, on the device (kernels_lmfit.hip), x_c = A[r, c], all in fp64 with no contracted product but the fma written:
+ *      E_k = sum over c of (c in sel ? fma(x_c, Q_f[c, k], .) : unchanged)
+ *      M   = the same with the weight 1.0 / (double)n_f for Q_f[c, k]                         (AveExpr)
+ *      r_c = fma(-Q_f[c, p-1], E_{p-1}, ... fma(-Q_f[c, 0], E_0, x_c))                        (ascending k, from x_c)
+ *      RSS = sum over c of (c in sel ? r_c * r_c : 0.0), from the reduced E of ALL samples; never sum x^2 - sum E^2
+ *      s2  = RSS / (n_f - p)
+ *    Every sum runs over the columns of a block of 128 in ascending order from 0.0, and the blocks are added in ascending
+ *    order.  The select form matters: an excluded sample may hold NaN or Inf, and it does not reach a fit that left it out.
+ * 3. eBayes per fit, on the host (squeezeVar / fitFDist; no trend, not robust), d = n_f - p:
+ *      rows with a finite s2 are "ok", n_ok their number; the other rows get NaN in every column and take no part;
+ *      x = max(s2, 1e-5 m), m = median(s2) over the ok rows (the mean of the middle two for an even count), m = 1 if it is 0;
+ *      e = log x - digamma(d / 2) + log(d / 2);   ebar = mean(e);   v = sum (e - ebar)^2 / (n_ok - 1) - trigamma(d / 2);
+ *      v > 0:  df.prior = 2 y with trigamma(y) = v,  s2.prior = exp(ebar + digamma(y) - log y);
+ *      else:   df.prior = +Inf,  s2.prior = mean(x);
+ *      n_ok < 2: df.prior = 0, s2.prior = NaN, and the test is the ordinary t;
+ *      s2.post = (d s2 + d0 s0^2) / (d + d0), s0^2 when d0 is infinite, s2 when d0 is 0;   df.total = min(d + d0, n_ok d);
+ *      t = logFC / (u_j sqrt(s2.post));   P.Value = 2 pt(-|t|, df.total) (the tail of plaid.test, a real df);
+ *      adj.P.Val = Benjamini-Hochberg over the rows of each (fit, contrast), NaN rows apart.
+ *    digamma and trigamma: the recurrence up to an argument >= 10, then the asymptotic series.  The root of trigamma(y) = v
+ *    is pinned as a property (to a relative 1e-12 in y or better for 1e-6 <= v <= 1e7), not as an iteration; outside that
+ *    range limma's own closed forms stand: y = 1 / sqrt(v) for v > 1e7 and y = 1 / v for v < 1e-6.
+ * out: rows x 6 x q x nfit doubles, column-major: logFC, AveExpr, t, P.Value, adj.P.Val, sigma2 (the unmoderated s2), in
+ * the row order of A; contrast j of fit f at out + (f * q + j) * 6 * rows.
+ * hyper: nfit x 4 doubles, row-major per fit: df.residual, df.prior, s2.prior, n_ok.
+ * rows == 0, nfit == 0 or q == 0: PLAIDHIP_OK with nothing written.
+ * Argument errors, in this order, all PLAIDHIP_EINVAL and all found on the host before any device is touched: bad dims
+ * (rows, n, nfit, q < 0, nfit > PLAIDHIP_LIMMA_MAX_FITS, n > PLAIDHIP_LIMMA_MAX_SAMPLES); p outside 1..PLAIDHIP_LIMMA_MAX_COEF; K == NULL with q != p; a null design; a null A, out or
+ * hyper where something is to be written; a non-finite entry of K; then fit by fit: a non-finite entry of a used row of
+ * D_f, n_f - p < 1, a rank-deficient column -- with a message naming the fit and the column (or sample), counted from 1.
+ * A non-finite entry of an unused row of D_f is accepted.
+ * How: the W = nfit (p + 1) weight columns of all fits (p columns of Q_f, then use / n_f) lie side by side and are cut into
+ * tiles of PLAIDHIP_LIMMA_TILE; a thread owns two adjacent rows and keeps a tile's accumulators in registers, so A is read
+ * ceil(W / tile) times for the effects and nfit times for the RSS.
+ * plaidhip_limma_multi shards the SAMPLES over the devices at multiples of 128 columns.  The effects are handed from shard
+ * to shard as [W][rows], then every shard takes the RSS of its columns from the full effects and hands it on as
+ * [nfit][rows]; every sharding, with more shards than samples too, has the bits of the one-device call.
+ *   plaidhip_dev_row_design_effects / _rss: the two passes on device pointers, stream-ordered.  A: rows x n, leading
+ *     dimension ld.  Q: n x p x nfit doubles (Q_f column-major at Q + f n p), use: n x nfit int8 or NULL, invn: nfit doubles,
+ *     1 / n_f.  E: [W][rows], fit f's p effects then its M at rows f (p + 1) ...  rss: [nfit][rows].  seed (NULL: zeros):
+ *     the sums of the shards before this one, of the result's shape.  _rss takes the E of ALL shards, as
+ *     plaidhip_dev_row_contrast_ssd takes the means of all shards.  The partials live in the context's workspace.
+ *   plaidhip_limma_design (host only): step 1 for one design: Q (n x p), R (p x p column-major), v (p x q), u (q), *nf;
+ *     each may be NULL.  `fit` is the number its messages name.
+ *   plaidhip_limma_finish (host only): step 3 and the output from E ([W][rows]), rss ([nfit][rows]), nf (nfit), v
+ *     (p x q x nfit) and u (q x nfit).  Tails and Benjamini-Hochberg are dealt to at most 8 host threads.
+ * Not offered: trend = TRUE and robust = TRUE; array or observation weights; the B-statistic and the F-statistic; per-row
+ * missing values (a NaN in a used sample makes the row NaN: limma would refit that row on the rest); a dgCMatrix input;
+ * fusing a scorer with the test so that the scores never leave the device. */
+#define PLAIDHIP_LIMMA_MAX_COEF 32
+#define PLAIDHIP_LIMMA_TILE 8
+#define PLAIDHIP_LIMMA_MAX_FITS 15000         /* nfit (p + 1) / tile and nfit are launch grid extents, at most 65,535 each */
+#define PLAIDHIP_LIMMA_MAX_SAMPLES 8388480    /* 65,535 column blocks of 128: a launch grid extent as well */
+int plaidhip_limma(plaidhip_ctx* ctx, const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit,
+                   const int8_t* use, const double* K, int32_t q, double* out, double* hyper);
+int plaidhip_limma_multi(const int* devices, int ndev, const double* A, int32_t rows, int32_t n, const double* design,
+                         int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double* out, double* hyper);
+int plaidhip_dev_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                                    const int8_t* use, const double* invn, int32_t p, int32_t nfit, const double* seed,
+                                    double* E);
+int plaidhip_dev_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                                const int8_t* use, int32_t p, int32_t nfit, const double* E, const double* seed, double* rss);
+int plaidhip_limma_design(const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q, int32_t fit,
+                          double* Q, double* R, double* v, double* u, int64_t* nf);
+int plaidhip_limma_finish(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
+                          const int64_t* nf, const double* v, const double* u, double* out, double* hyper);
+int plaidhip_limma_tile(void);   /* PLAIDHIP_LIMMA_TILE of the built library */
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

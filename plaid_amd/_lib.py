@@ -150,6 +150,13 @@ SIGNATURES = {
     "plaidhip_fisher": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_fisher_multi": [_vp, _int, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_hyper_tail": [_i64, _i64, _i64, _i64, _vp],
+    "plaidhip_limma": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "plaidhip_limma_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "plaidhip_dev_row_design_effects": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "plaidhip_dev_row_design_rss": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "plaidhip_limma_design": [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_limma_finish": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_limma_tile": [],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],
     # host-only GMT text path (gmt.cpp)
     "plaidhip_gmt_read": [C.c_char_p, _int, _i64, C.POINTER(_vp)],

@@ -727,3 +727,89 @@ def plaid_fisher(sig, G, minSize=1, maxSize=None, sort_by="pAny", overlap=False,
         if overlap:
             res[nm] = (res[nm], [[(genes[r], int(Xs[r, l])) for r in ov_idx[Gp[j]:Gp[j] + ov_len[j, l], l]] for j in o])
     return res[sig.colnames[0]] if single and len(res) == 1 else res
+
+
+_LIMMA_NAMES = ["logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2"]
+_LIMMA_HYPER = ["df.residual", "df.prior", "s2.prior", "n.ok"]
+_LIMMA_SORT = {"none": None, "P.Value": (3, 1), "P": (3, 1), "p": (3, 1), "t": (2, -1), "logFC": (0, -1), "AveExpr": (1, -1)}
+
+
+def _limma_table(tab, rn, sort_by):
+    """rows x 6 of the library -> the NamedMatrix plaid.limma returns: topTable's order for `sort_by` -- "none" (the rows of
+    S), "P.Value" / "P" / "p" (increasing), "t" and "logFC" (decreasing magnitude), "AveExpr" (decreasing); stable, NaN last"""
+    if sort_by not in _LIMMA_SORT:
+        raise ValueError(f"plaid.limma: sort_by must be one of {sorted(_LIMMA_SORT)}")
+    rn = list(rn)
+    if _LIMMA_SORT[sort_by] is not None:
+        col, sign = _LIMMA_SORT[sort_by]
+        key = tab[:, col] if sign > 0 else -np.abs(tab[:, col]) if col != 1 else -tab[:, col]
+        o = np.argsort(key, kind="stable")
+        tab, rn = tab[o, :], [rn[k] for k in o]
+    return NamedMatrix(tab, rn, _LIMMA_NAMES)
+
+
+def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Context | None = None):
+    """plaid.limma(): limma's moderated t-test (lmFit + eBayes + topTable, as pinned in include/plaidhip.h) of every row of S
+    -- a NamedMatrix of single-sample scores (sets x samples) or of expression (genes x samples) -- for one design (samples
+    x coefficients; a NamedMatrix names the coefficients).  contrasts: coefficients x contrasts (a NamedMatrix names them),
+    None: every coefficient.  use: one entry per sample, False / 0 / NaN leaves it out of the fit (a NaN or Inf it holds in
+    S does not reach the fit).  Returns (tables, hyper): tables is a dict, contrast name -> NamedMatrix (rows x [logFC,
+    AveExpr, t, P.Value, adj.P.Val, sigma2]) ordered by `sort_by`; hyper a dict of df.residual, df.prior, s2.prior and n.ok.
+    The logFC and P.Value columns are what plaid_sig and plaid_gsea take.  Not offered: trend, robust, weights, the B- and
+    F-statistics, per-row missing values (a NaN in a used sample makes the row NaN), a sparse S."""
+    S = as_named(S)
+    if S.is_sparse:
+        raise ValueError("plaid.limma: S must be dense")
+    Dn = design if isinstance(design, NamedMatrix) else None
+    Dv = np.asarray(Dn.values if Dn is not None else design, dtype=np.float64)
+    if Dv.ndim != 2:
+        raise ValueError("plaid.limma: design must be samples x coefficients")
+    coef = list(Dn.colnames) if Dn is not None else [f"coef{k + 1}" for k in range(Dv.shape[1])]
+    if contrasts is None:
+        Kv, names = None, coef
+    else:
+        Kn = contrasts if isinstance(contrasts, NamedMatrix) else None
+        Kv = np.asarray(Kn.values if Kn is not None else contrasts, dtype=np.float64)
+        Kv = Kv[:, None] if Kv.ndim == 1 else Kv
+        names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
+    _limma_table(np.zeros((0, 6)), [], sort_by)   # (an unknown sort_by is refused before the device)
+    ctx = ctx or default_context()
+    out, hyper = ctx.limma(S.values, Dv, use, Kv)
+    tables = {nm: _limma_table(out[:, :, j, 0], S.rownames, sort_by) for j, nm in enumerate(names)}
+    return tables, dict(zip(_LIMMA_HYPER, (float(x) for x in hyper[0])))
+
+
+def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = None):
+    """plaid.limma.contrasts(): the reference's gx.limma(S, y, B, method = 1) for every column of the contrast matrix Y
+    (samples x contrasts; 0, 1, and NaN or -1 for a sample that takes no part) in one call: contrast j fits the design
+    [1, Y[, j], B] on the samples with a label and tests the coefficient of Y[, j].  B: batch covariates, samples x
+    covariates, or None.  S is uploaded once and read ceil(C (p + 1) / 8) times for the effects, p = 2 + ncol(B).  Y: a
+    NamedMatrix (its column names name the contrasts) or an array (contrasts "1", "2", ...).  Returns (tables, hyper):
+    contrast name -> the NamedMatrix plaid_limma returns, and contrast name -> its hyper-parameters."""
+    from .engine import contrast_labels
+    S = as_named(S)
+    if S.is_sparse:
+        raise ValueError("plaid.limma: S must be dense")
+    n = S.shape[1]
+    Yn = Y if isinstance(Y, NamedMatrix) else None
+    lab = contrast_labels(Yn.values if Yn is not None else Y, n)
+    if not np.all(np.isin(lab, (0, 1, -1))):
+        raise ValueError("elements of Y must be 0, 1 or NA")
+    ncon = lab.shape[1]
+    names = list(Yn.colnames) if Yn is not None and Yn.colnames is not None else [str(j + 1) for j in range(ncon)]
+    Bv = np.zeros((n, 0)) if B is None else np.asarray(B.values if isinstance(B, NamedMatrix) else B, dtype=np.float64)
+    Bv = Bv[:, None] if Bv.ndim == 1 else Bv
+    if Bv.ndim != 2 or Bv.shape[0] != n:
+        raise ValueError("B must have one row per column of S")
+    p = 2 + Bv.shape[1]
+    D = np.empty((n, p, ncon), order="F")
+    D[:, 0, :] = 1.0
+    D[:, 1, :] = np.where(lab == 1, 1.0, 0.0)
+    D[:, 2:, :] = Bv[:, :, None]
+    K = np.zeros((p, 1))
+    K[1, 0] = 1.0
+    _limma_table(np.zeros((0, 6)), [], sort_by)
+    ctx = ctx or default_context()
+    out, hyper = ctx.limma(S.values, D, lab != -1, K)
+    tables = {nm: _limma_table(out[:, :, 0, j], S.rownames, sort_by) for j, nm in enumerate(names)}
+    return tables, {nm: dict(zip(_LIMMA_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}

@@ -1198,6 +1198,51 @@ int plaidhip_fisher(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, 
   return dispatch(on_context(ctx), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.limma: the one-device form of the sharded engine (multi.cpp: limma_worker, kLimma)
+int plaidhip_limma(plaidhip_ctx* ctx, const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit,
+                   const int8_t* use, const double* K, int32_t q, double* out, double* hyper) try {
+  return dispatch(on_context(ctx), limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the two device passes of plaid.limma on device pointers (kernels_lmfit.hip).  The workspace holds the block partials, then
+// the masks, then (effects only) the tile weights.
+static int dev_row_design_pass(plaidhip_ctx* ctx, const char* what, const double* A, int64_t ld, int32_t rows, int32_t n,
+                               const double* Q, const int8_t* use, const double* invn, int32_t p, int32_t nfit, const double* E,
+                               bool rss, const double* seed, double* out) {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ld >= rows && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS,
+             "%s: bad shape rows=%d n=%d ld=%lld nfit=%d (nfit <= %d)", what, rows, n, (long long)ld, nfit, PLAIDHIP_LIMMA_MAX_FITS);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "%s: p = %d coefficients (1 <= p <= %d)", what, p, PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(n <= PLAIDHIP_LIMMA_MAX_SAMPLES, "%s: %d samples (at most %d)", what, n, PLAIDHIP_LIMMA_MAX_SAMPLES);
+  if (rows == 0 || nfit == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(out && (!rss || E) && (n == 0 || (A && Q && (rss || invn))), "%s: null argument", what);
+  const int64_t W = (int64_t)nfit * (p + 1), cols = rss ? nfit : W;
+  const size_t part = ((size_t)row_design_ws_doubles(rows, n, cols) * 8 + 15) / 16 * 16;
+  const size_t mb = (size_t)lmfit_mask_bytes(n, W);
+  PH_TRY(ensure_workspace(ctx, part + mb + (rss ? 0 : (size_t)lmfit_weight_bytes(n, W))));
+  double* ws = static_cast<double*>(ctx->ws);
+  void* masks = static_cast<char*>(ctx->ws) + part;
+  double* wt = rss ? nullptr : reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + part + mb);   // (the RSS pass reads no weight)
+  PH_TRY(launch_lmfit_masks(ctx, Q, use, invn, n, p, nfit, masks, wt));
+  if (rss) PH_TRY(launch_row_design_rss(ctx, A, ld, rows, n, Q, masks, p, nfit, E, ws));
+  else PH_TRY(launch_row_design_effects(ctx, A, ld, rows, n, masks, wt, (int32_t)W, ws));
+  return launch_reduce_blocks_flat(ctx, ws, cols * rows, n, seed, out);
+}
+
+int plaidhip_dev_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                                    const int8_t* use, const double* invn, int32_t p, int32_t nfit, const double* seed,
+                                    double* E) try {
+  return dev_row_design_pass(ctx, "row_design_effects", A, ld, rows, n, Q, use, invn, p, nfit, nullptr, false, seed, E);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                                const int8_t* use, int32_t p, int32_t nfit, const double* E, const double* seed,
+                                double* rss) try {
+  return dev_row_design_pass(ctx, "row_design_rss", A, ld, rows, n, Q, use, nullptr, p, nfit, E, true, seed, rss);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_tile(void) { return PLAIDHIP_LIMMA_TILE; }
+
 // the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out) try {
   PH_REQUIRE(g >= 1 && nperm >= 1, "gsea_permutations: bad dims g=%d nperm=%d", g, nperm);

@@ -11,7 +11,8 @@ namespace plaidhip {
 // the ordinals are what the test hooks plaidhip_debug_sharded_on_one_device / _scorer_sharded_on_one_device take
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
-  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15
+  kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
+  kLimma = 16
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -82,6 +83,16 @@ struct Call : Operands {
   // lists in le_len / le_idx (both null: none)
   const int8_t* sig = nullptr;
   double* tot_out = nullptr;
+  // plaid.limma: X is A (g rows x n samples; no sets: Gp stays null, m = 0), the nfit designs (n x p each), use (n x nfit,
+  // null: all), K (p x q, null: the unit vectors), out g x 6 x q x nfit and hyper nfit x 4; what check_call makes of the
+  // designs: Q (n x p x nfit), 1 / n_f, n_f, v (p x q x nfit) and u (q x nfit)
+  const double* design = nullptr;
+  const int8_t* use = nullptr;
+  const double* K = nullptr;
+  int32_t ncoef = 0, nfit = 0, nq = 0;
+  double* hyper = nullptr;
+  std::vector<double> lm_Q, lm_invn, lm_v, lm_u;
+  std::vector<int64_t> lm_nf;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -261,6 +272,21 @@ inline Call fisher_call(const int8_t* sig, int32_t g, int32_t c, const int32_t* 
   k.tot_out = tot_out;
   k.le_len = ov_len;
   k.le_idx = ov_idx;
+  return k;
+}
+
+// lmFit + eBayes + topTable as pinned in include/plaidhip.h: plaidhip_limma
+inline Call limma_call(const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                       const double* K, int32_t q, double* out, double* hyper) {
+  Call k = make_call(kLimma, {nullptr, nullptr, A, rows, n, nullptr, nullptr, 0}, nullptr);
+  k.design = design;
+  k.ncoef = p;
+  k.nfit = nfit;
+  k.use = use;
+  k.K = K;
+  k.nq = q;
+  k.out = out;
+  k.hyper = hyper;
   return k;
 }
 

@@ -357,6 +357,24 @@ int launch_row_contrast_partials(plaidhip_ctx* ctx, const double* S, int64_t ld,
 int launch_reduce_blocks_flat(plaidhip_ctx* ctx, const double* ws, int64_t len, int32_t n, const double* d_seed,
                               double* d_out);
 int launch_fold_change_contrasts(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, int32_t C, int64_t ld2, double* d_F);
+// kernels_lmfit.hip (plaid.limma): the weighted row sums of W = nfit (p + 1) weight columns (fit f: p columns of Q_f, then
+// use / n_f) per read of the matrix in tiles of PLAIDHIP_LIMMA_TILE, and the residual sums of squares at the reduced effects.
+// d_Q: n x p x nfit, d_use: n x nfit int8 or null, d_invn: nfit; d_masks / d_wt: lmfit_mask_bytes / lmfit_weight_bytes bytes,
+// filled by launch_lmfit_masks; ws: row_design_ws_doubles(rows, n, W or nfit) doubles of block partials [nblk][cols][rows],
+// reduced by launch_reduce_blocks_flat; d_E: [W][rows]
+int64_t lmfit_tiles(int64_t W);
+int64_t row_design_ws_doubles(int32_t rows, int32_t n, int64_t cols);
+int64_t lmfit_mask_bytes(int32_t n, int64_t W);
+int64_t lmfit_weight_bytes(int32_t n, int64_t W);
+int launch_lmfit_masks(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_use, const double* d_invn, int32_t n, int32_t p,
+                       int32_t nfit, void* d_masks, double* d_wt);
+int launch_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const void* d_masks,
+                              const double* d_wt, int32_t W, double* ws);
+int launch_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
+                          const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws);
+// stats.cpp: one design of plaid.limma (include/plaidhip.h: plaidhip_limma_design); what: the entry its messages name
+int limma_design(const char* what, const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q,
+                 int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf);
 // kernels_csr.hip: the row view of a CSC matrix (replaid.gsva / plaid.test on a dgCMatrix).  All pointers are device
 // pointers.  Transpose: Rp g + 1, Rx / Rj / perm Xp[n] entries each (Rj, perm optional), within a row ascending column
 // order; *d_maxlen = the longest row.  Uses the context workspace.

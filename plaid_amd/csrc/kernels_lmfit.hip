@@ -1,0 +1,260 @@
+// plaid.limma: the per-row linear-model fit of include/plaidhip.h (plaidhip_limma), two passes over a rows x n matrix.
+//
+// kernels_contrasts.hip generalised from 0 / 1 labels to real weights.  A fit f is the thin Q_f of its design (n x p, made on
+// the host) and its used samples; what a row needs of it are the effects E_k = sum_c x_c Q_f[c, k], the mean M (one more
+// weight column, use / n_f) and then the residual sum of squares at the reduced effects.  The W = nfit (p + 1) weight
+// columns of all fits lie side by side (fit f: columns f (p + 1) + 0 .. p - 1 are Q_f's, column f (p + 1) + p is the mean's)
+// and are cut into tiles of kTile; the weights of a column of A and the bits "this sample is used by the fit that owns tile
+// column t" are the same for every row -- wavefront-uniform, read through scalar loads.  A thread owns two adjacent rows,
+// walks a block of kColBlock columns in ascending order and keeps the tile's accumulators in registers, so A is read
+// ceil(W / kTile) times for the effects and nfit times for the residuals.  As in kernels_contrasts.hip:
+//     acc = in ? fma(x, w, acc) : acc          per column of the block, ascending (RSS: acc += in ? r * r : 0.0)
+//     part[block][column][row]
+//     blocks added in ascending order, from an optional seed (reduce_blocks_flat_kernel)
+// The select form matters: an excluded column leaves the accumulator alone whatever it holds (NaN, Inf).  The file is
+// compiled with -ffp-contract=off (and says so below): the only fused operations are the fma written out.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace plaidhip {
+
+constexpr int kLmColBlock = 128;   // kernels_contrasts.hip's column block (launch_reduce_blocks_flat counts in it)
+constexpr int kLmTile = PLAIDHIP_LIMMA_TILE;
+
+// masks[tile][c]: bit t = sample c is used by the fit of column tile * kTile + t (an 8-bit mask, kept in a 32-bit word so
+// that it is one scalar load); wt[tile][c][t]: that column's weight for the sample -- Q_f[c, k], 1 / n_f for the mean's
+// column, 0.0 for an excluded sample and past column W.  Q: n x p x nfit, use: n x nfit or null, invn: nfit.  wt == nullptr:
+// the masks alone (the RSS pass reads no weight), and Q and invn are not read.
+__global__ void __launch_bounds__(256)
+lmfit_masks_kernel(const double* __restrict__ Q, const int8_t* __restrict__ use, const double* __restrict__ invn, int32_t n,
+                   int32_t p, int32_t nfit, uint32_t* __restrict__ masks, double* __restrict__ wt) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int tile = blockIdx.y;
+  if (c >= n) return;
+  const int64_t W = (int64_t)nfit * (p + 1);
+  uint32_t bits = 0;
+  double* w = wt != nullptr ? wt + ((int64_t)tile * n + c) * kLmTile : nullptr;
+  for (int t = 0; t < kLmTile; ++t) {
+    const int64_t j = (int64_t)tile * kLmTile + t;
+    double v = 0.0;
+    if (j < W) {
+      const int64_t f = j / (p + 1);
+      const int k = (int)(j % (p + 1));
+      if (use == nullptr || use[f * n + c] != 0) {
+        bits |= 1u << t;
+        if (w != nullptr) v = k < p ? Q[(f * p + k) * n + c] : invn[f];
+      }
+    }
+    if (w != nullptr) w[t] = v;
+  }
+  masks[(int64_t)tile * n + c] = bits;
+}
+
+// The block partials part[nblk][W][rows] of the W weighted row sums, tile blockIdx.z.  The load scheme is
+// row_contrast_partials_kernel's: kWide (rows and ld even, A 16-byte aligned) one 16-byte non-temporal load per column for
+// both rows, otherwise two 8-byte ones; kUn columns are loaded before the first of them is used.
+template <bool kWide>
+__global__ void __launch_bounds__(256)
+row_design_effects_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const uint32_t* __restrict__ masks,
+                          const double* __restrict__ wt, int32_t W, double* __restrict__ part) {
+  typedef double f64x2_s __attribute__((ext_vector_type(2)));
+  constexpr int T = kLmTile;
+  constexpr int kUn = 8;
+  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
+  const int c0 = blockIdx.y * kLmColBlock;
+  const int c1 = c0 + kLmColBlock < n ? c0 + kLmColBlock : n;
+  const int j0 = blockIdx.z * T;                      // the tile's first column
+  const int nt = W - j0 < T ? W - j0 : T;             // its live columns (the others' bits are 0, nothing is written)
+  const uint32_t* __restrict__ mk = masks + (int64_t)blockIdx.z * n;
+  const double* __restrict__ wk = wt + (int64_t)blockIdx.z * n * T;
+  if (r >= rows) return;
+  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
+  double a[T], b[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) a[t] = b[t] = 0.0;
+  auto accumulate = [&](int c, double xa, double xb) {
+    const uint32_t k = mk[c];                         // wave-uniform, as the weights
+    const double* __restrict__ w = wk + (int64_t)c * T;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const bool in = ((k >> t) & 1u) != 0;
+      const double wc = w[t];
+      a[t] = in ? __builtin_fma(xa, wc, a[t]) : a[t];
+      b[t] = in ? __builtin_fma(xb, wc, b[t]) : b[t];
+    }
+  };
+  auto load = [&](int c, double& xa, double& xb) {
+    const double* q = A + (int64_t)c * ld + r;
+    if (kWide) {
+      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
+      xa = v.x;
+      xb = v.y;
+    } else {
+      xa = __builtin_nontemporal_load(q);
+      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
+    }
+  };
+  int c = c0;
+  for (; c + kUn <= c1; c += kUn) {
+    double xa[kUn], xb[kUn];
+#pragma unroll
+    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
+#pragma unroll
+    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
+  }
+  for (; c < c1; ++c) {
+    double xa, xb;
+    load(c, xa, xb);
+    accumulate(c, xa, xb);
+  }
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    if (t >= nt) break;
+    double* o = part + ((int64_t)blockIdx.y * W + (j0 + t)) * rows;
+    o[r] = a[t];
+    if (two) o[r + 1] = b[t];
+  }
+}
+
+// The block partials part[nblk][nfit][rows] of the residual sums of squares of fit blockIdx.z at the reduced effects E
+// ([W][rows]): r = x - sum_k Q[c, k] E_k as p chained fma in ascending k, starting from x; the sum takes in ? r * r : 0.0.
+// A thread keeps its two rows' p effects in registers (kP: p rounded up to 4, 8, 16 or 32; DESIGN.md section 20 has the
+// resource report that chose registers over an LDS tile).  Q's entries of a column are wave-uniform.
+template <int kP, bool kWide>
+__global__ void __launch_bounds__(256)
+row_design_rss_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const double* __restrict__ Q,
+                      const uint32_t* __restrict__ masks, int32_t p, int32_t nfit, const double* __restrict__ E,
+                      double* __restrict__ part) {
+  typedef double f64x2_s __attribute__((ext_vector_type(2)));
+  constexpr int kUn = 8;
+  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
+  const int c0 = blockIdx.y * kLmColBlock;
+  const int c1 = c0 + kLmColBlock < n ? c0 + kLmColBlock : n;
+  const int f = blockIdx.z;
+  const int64_t jm = (int64_t)f * (p + 1) + p;        // the fit's mean column: its bit says "used by fit f"
+  const uint32_t* __restrict__ mk = masks + (jm / kLmTile) * n;
+  const int bit = (int)(jm % kLmTile);
+  const double* __restrict__ Qf = Q + (int64_t)f * p * n;
+  if (r >= rows) return;
+  const bool two = r + 1 < rows;
+  double ea[kP], eb[kP];
+#pragma unroll
+  for (int k = 0; k < kP; ++k) {
+    ea[k] = eb[k] = 0.0;
+    if (k < p) {
+      const double* e = E + ((int64_t)f * (p + 1) + k) * rows;
+      ea[k] = e[r];
+      if (two) eb[k] = e[r + 1];
+    }
+  }
+  double sa = 0.0, sb = 0.0;
+  auto accumulate = [&](int c, double xa, double xb) {
+    const bool in = ((mk[c] >> bit) & 1u) != 0;
+    double ra = xa, rb = xb;
+#pragma unroll
+    for (int k = 0; k < kP; ++k) {
+      if (k >= p) break;
+      const double nq = -Qf[(int64_t)k * n + c];
+      ra = __builtin_fma(nq, ea[k], ra);
+      rb = __builtin_fma(nq, eb[k], rb);
+    }
+    const double qa = ra * ra, qb = rb * rb;
+    sa += in ? qa : 0.0;
+    sb += in ? qb : 0.0;
+  };
+  auto load = [&](int c, double& xa, double& xb) {
+    const double* q = A + (int64_t)c * ld + r;
+    if (kWide) {
+      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
+      xa = v.x;
+      xb = v.y;
+    } else {
+      xa = __builtin_nontemporal_load(q);
+      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
+    }
+  };
+  int c = c0;
+  for (; c + kUn <= c1; c += kUn) {
+    double xa[kUn], xb[kUn];
+#pragma unroll
+    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
+#pragma unroll
+    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
+  }
+  for (; c < c1; ++c) {
+    double xa, xb;
+    load(c, xa, xb);
+    accumulate(c, xa, xb);
+  }
+  double* o = part + ((int64_t)blockIdx.y * nfit + f) * rows;
+  o[r] = sa;
+  if (two) o[r + 1] = sb;
+}
+
+int64_t lmfit_tiles(int64_t W) { return (W + kLmTile - 1) / kLmTile; }
+
+// doubles of the block partials [nblk][cols][rows]
+int64_t row_design_ws_doubles(int32_t rows, int32_t n, int64_t cols) {
+  const int64_t nblk = (n + kLmColBlock - 1) / kLmColBlock;
+  return (int64_t)rows * cols * (nblk > 0 ? nblk : 1);
+}
+
+// bytes of the masks of n columns and W weight columns, and of their weights (a multiple of 16 each)
+int64_t lmfit_mask_bytes(int32_t n, int64_t W) { return (lmfit_tiles(W) * (int64_t)(n > 0 ? n : 1) * 4 + 15) / 16 * 16; }
+int64_t lmfit_weight_bytes(int32_t n, int64_t W) { return lmfit_tiles(W) * (int64_t)(n > 0 ? n : 1) * kLmTile * 8; }
+
+int launch_lmfit_masks(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_use, const double* d_invn, int32_t n, int32_t p,
+                       int32_t nfit, void* d_masks, double* d_wt) {
+  if (n == 0 || nfit == 0) return PLAIDHIP_OK;
+  const int64_t W = (int64_t)nfit * (p + 1);
+  hipLaunchKernelGGL(lmfit_masks_kernel, dim3((n + 255) / 256, (unsigned)lmfit_tiles(W)), dim3(256), 0, ctx->stream, d_Q, d_use,
+                     d_invn, n, p, nfit, static_cast<uint32_t*>(d_masks), d_wt);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+// ws: row_design_ws_doubles(rows, n, W) doubles, [nblk][W][rows]; d_masks / d_wt: launch_lmfit_masks of the same n and W
+int launch_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const void* d_masks,
+                              const double* d_wt, int32_t W, double* ws) {
+  if (rows == 0 || n == 0 || W == 0) return PLAIDHIP_OK;
+  const int nblk = (n + kLmColBlock - 1) / kLmColBlock;
+  const dim3 grid((rows + 511) / 512, nblk, (unsigned)lmfit_tiles(W));
+  const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
+  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
+  if (wide)
+    hipLaunchKernelGGL((row_design_effects_kernel<true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+  else
+    hipLaunchKernelGGL((row_design_effects_kernel<false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+template <int kP>
+static void launch_rss_p(plaidhip_ctx* ctx, bool wide, dim3 grid, const double* A, int64_t ld, int32_t rows, int32_t n,
+                         const double* d_Q, const uint32_t* mk, int32_t p, int32_t nfit, const double* d_E, double* ws) {
+  if (wide)
+    hipLaunchKernelGGL((row_design_rss_kernel<kP, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
+                       ws);
+  else
+    hipLaunchKernelGGL((row_design_rss_kernel<kP, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
+                       ws);
+}
+
+// ws: row_design_ws_doubles(rows, n, nfit) doubles, [nblk][nfit][rows]; d_E: [nfit (p + 1)][rows], the effects of all samples
+int launch_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
+                          const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws) {
+  if (rows == 0 || n == 0 || nfit == 0) return PLAIDHIP_OK;
+  const int nblk = (n + kLmColBlock - 1) / kLmColBlock;
+  const dim3 grid((rows + 511) / 512, nblk, nfit);
+  const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
+  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
+  if (p <= 4) launch_rss_p<4>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  else if (p <= 8) launch_rss_p<8>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  else if (p <= 16) launch_rss_p<16>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  else launch_rss_p<32>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+}  // namespace plaidhip

@@ -296,6 +296,7 @@ struct Shared {
   // plaid.test: the chained two-group sums ([2][rows]) of X (dense), of the score rows and of their squared deviations;
   // shard 0's T = Gt [fc, fc^2] and F = [fc, fc^2] (leading dimension even_ld(g)); a dgCMatrix's per-shard stored-value
   // sums go to row_sum
+  // plaid.limma: chain_x is the chained effects [W][rows], chain_q the chained residual sums of squares [nfit][rows]
   std::vector<double> chain_x, chain_s, chain_q, pt_T, pt_F;
   // replaid.ssgsea.exact with norm: a NaN among the scores of any shard (its min / max go to xmin / xmax)
   bool es_nan = false;
@@ -309,7 +310,7 @@ struct Shared {
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
   int64_t lo64 = 0, hi64 = 0;
   if (((c.method == kGsva || (c.method == kGsvaExact && c.rowtf == 0)) && c.Xp == nullptr) || c.method == kPlaidTest ||
-      c.method == kPlaidTestContrasts) {
+      c.method == kPlaidTestContrasts || c.method == kLimma) {
     constexpr int64_t kBlock = 128;
     const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
     lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
@@ -1977,6 +1978,87 @@ int fisher_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   return s.finish();
 }
 
+// chain_contrast_sums for any [nblk][len] partials of the shard's columns (launch_reduce_blocks_flat): shard r adds its blocks,
+// in order, to what the shards before it left in `run`; d_seed, d_run: len doubles each.  ndev rendezvous.
+void chain_flat_sums(Shard& s, std::vector<double>& run, const double* ws, int64_t len, double* d_seed, double* d_run) {
+  plaidhip_ctx* ctx = s.ctx;
+  for (int r = 0; r < s.ndev; ++r) {
+    if (r == s.k)
+      s.step([&]() -> int {
+        if (s.nloc == 0) return PLAIDHIP_OK;
+        PH_HIP(hipMemcpyAsync(d_seed, run.data(), (size_t)len * 8, hipMemcpyHostToDevice, ctx->stream));
+        PH_TRY(launch_reduce_blocks_flat(ctx, ws, len, s.nloc, d_seed, d_run));
+        PH_HIP(hipMemcpyAsync(run.data(), d_run, (size_t)len * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        return PLAIDHIP_OK;
+      });
+    s.sh.rv.arrive_and_wait();
+  }
+}
+
+// one device's part of plaid.limma (kLimma, kernels_lmfit.hip; include/plaidhip.h: plaidhip_limma).  The SAMPLES are shared
+// out at multiples of 128 columns, as for plaid.test.contrasts: a shard takes its columns of A and its rows of every Q_f and
+// of use.  Round one chains the effects and means [W][rows] from shard to shard; after it every shard holds the effects of
+// all samples and takes the residual sums of squares of its own columns, which round two chains as [nfit][rows].  The block
+// partials are added in the order of the one-device call, so every sharding has its bits.  2 ndev rendezvous.
+int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc, rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit;
+  const int64_t W = (int64_t)nfit * (p + 1), ld = even_ld(rows);
+  CtxBuf dA{ctx, 0};
+  DevBuf dQ, duse, dinvn, dmask, dwt, dws, drows;
+  double *d_seed = nullptr, *d_run = nullptr, *d_E = nullptr;
+  // host sources of asynchronous uploads: they live until the worker's last synchronisation
+  std::vector<double> qloc;
+  std::vector<int8_t> uloc;
+
+  // ---- upload; the shard's rows of Q and use, their masks and tile weights; the effects' block partials ----------------------
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    PH_HIP(hipSetDevice(ctx->device));
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(drows.alloc((size_t)W * rows * 3 * 8));   // [seed | running sums | the effects of all samples], [W][rows] each
+    d_seed = drows.as<double>();
+    d_run = d_seed + W * rows;
+    d_E = d_run + W * rows;
+    qloc.resize((size_t)nloc * p * nfit);
+    for (int64_t col = 0; col < (int64_t)p * nfit; ++col)
+      std::copy(c.lm_Q.begin() + col * n + lo, c.lm_Q.begin() + col * n + lo + nloc, qloc.begin() + col * nloc);
+    PH_TRY(dQ.alloc(qloc.size() * 8));
+    PH_HIP(hipMemcpyAsync(dQ.p, qloc.data(), qloc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (c.use != nullptr) {
+      uloc.resize((size_t)nloc * nfit);
+      for (int32_t f = 0; f < nfit; ++f)
+        std::copy(c.use + (size_t)f * n + lo, c.use + (size_t)f * n + lo + nloc, uloc.begin() + (size_t)f * nloc);
+      PH_TRY(duse.alloc(uloc.size()));
+      PH_HIP(hipMemcpyAsync(duse.p, uloc.data(), uloc.size(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    PH_TRY(dinvn.alloc((size_t)nfit * 8));
+    PH_HIP(hipMemcpyAsync(dinvn.p, c.lm_invn.data(), (size_t)nfit * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dmask.alloc((size_t)lmfit_mask_bytes(nloc, W)));
+    PH_TRY(dwt.alloc((size_t)lmfit_weight_bytes(nloc, W)));
+    PH_TRY(launch_lmfit_masks(ctx, dQ.as<double>(), c.use != nullptr ? duse.as<int8_t>() : nullptr, dinvn.as<double>(), nloc, p,
+                              nfit, dmask.p, dwt.as<double>()));
+    PH_TRY(dws.alloc((size_t)row_design_ws_doubles(rows, nloc, W) * 8));   // (W >= nfit: the RSS partials fit too)
+    PH_TRY(dA.alloc((size_t)ld * nloc * 8));
+    PH_TRY(upload_pipelined(ctx, dA.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * rows),
+                            (size_t)rows * 8, nloc, nullptr));
+    return launch_row_design_effects(ctx, dA.as<double>(), ld, rows, nloc, dmask.p, dwt.as<double>(), (int32_t)W,
+                                     dws.as<double>());
+  });
+  chain_flat_sums(s, sh.chain_x, dws.as<double>(), W * rows, d_seed, d_run);
+
+  // ---- the residual sums of squares of the shard's columns at the effects of ALL samples -------------------------------------
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_HIP(hipMemcpyAsync(d_E, sh.chain_x.data(), (size_t)W * rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    return launch_row_design_rss(ctx, dA.as<double>(), ld, rows, nloc, dQ.as<double>(), dmask.p, p, nfit, d_E,
+                                 dws.as<double>());
+  });
+  chain_flat_sums(s, sh.chain_q, dws.as<double>(), (int64_t)nfit * rows, d_seed, d_run);
+  return s.finish();
+}
+
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
 int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   Shared sh(ndev);
@@ -2005,11 +2087,16 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.pt_F.assign((size_t)even_ld(c.g) * 2 * C, 0.0);
     sh.row_sum.resize((size_t)ndev);
   }
+  if (c.method == kLimma) {
+    sh.chain_x.assign((size_t)c.nfit * (c.ncoef + 1) * c.g, 0.0);
+    sh.chain_q.assign((size_t)c.nfit * c.g, 0.0);
+  }
   if (c.method == kGsea && ndev > 1)
     sh.gsea_part.assign((size_t)((c.nperm + PLAIDHIP_GSEA_PERM_BLOCK - 1) / PLAIDHIP_GSEA_PERM_BLOCK) * c.n * 6 * c.m, 0.0);
   auto worker = [&](int k) {
     if (c.method == kGsea) return gsea_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kFisher) return fisher_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kLimma) return limma_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
     return is_rank_sum(c.method) ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
@@ -2052,6 +2139,9 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     rc = plaidhip_plaid_test_finish(c.g, c.m, c.Gp, sh.pt_T.data(), tot1, tot2, (c.tests & 4) ? SM.data() : nullptr, c.n0,
                                     c.n1, c.tests, c.metap_method, c.out);
   }
+  if (rc == PLAIDHIP_OK && c.method == kLimma)   // eBayes and the tables, on the host from the chained sums
+    rc = plaidhip_limma_finish(c.g, c.ncoef, c.nfit, c.nq, sh.chain_x.data(), sh.chain_q.data(), c.lm_nf.data(), c.lm_v.data(),
+                               c.lm_u.data(), c.out, c.hyper);
   if (rc == PLAIDHIP_OK && c.method == kPlaidTestContrasts) {   // the same host half, once per contrast with its group sizes
     const int64_t ldg = even_ld(c.g);
     const size_t m = (size_t)c.m;
@@ -2363,6 +2453,35 @@ int check_fisher_call(const Call& c) {
   return PLAIDHIP_OK;
 }
 
+// plaid.limma; the order is part of the contract (include/plaidhip.h).  Makes every fit's Q, v, u and n_f: the designs are
+// decomposed here, on the host, so that a design that cannot be fitted is refused before any device is touched
+int check_limma_call(Call& c) {
+  const int32_t rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, q = c.nq;
+  PH_REQUIRE(rows >= 0 && n >= 0 && n <= PLAIDHIP_LIMMA_MAX_SAMPLES && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS && q >= 0,
+             "limma: bad dims rows=%d n=%d nfit=%d q=%d (n <= %d, nfit <= %d)", rows, n, nfit, q, PLAIDHIP_LIMMA_MAX_SAMPLES,
+             PLAIDHIP_LIMMA_MAX_FITS);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "limma: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(c.K != nullptr || q == p, "limma: q = %d without K (the p = %d unit vectors)", q, p);
+  PH_REQUIRE(c.design != nullptr || nfit == 0, "limma: null design");
+  PH_REQUIRE(rows == 0 || nfit == 0 || q == 0 || (c.X != nullptr && c.out != nullptr && c.hyper != nullptr),
+             "limma: null A / out / hyper");
+  if (c.K != nullptr)
+    for (int64_t e = 0; e < (int64_t)p * q; ++e)
+      PH_REQUIRE(std::isfinite(c.K[e]), "limma: K[%lld] = %g (the contrasts are finite)", (long long)e, c.K[e]);
+  c.lm_Q.assign((size_t)n * p * nfit, 0.0);
+  c.lm_v.assign((size_t)p * q * nfit, 0.0);
+  c.lm_u.assign((size_t)q * nfit, 0.0);
+  c.lm_nf.assign((size_t)nfit, 0);
+  c.lm_invn.assign((size_t)nfit, 0.0);
+  for (int32_t f = 0; f < nfit; ++f) {
+    PH_TRY(limma_design("limma", c.design + (size_t)f * n * p, n, p, c.use != nullptr ? c.use + (size_t)f * n : nullptr, c.K, q,
+                        f + 1, c.lm_Q.data() + (size_t)f * n * p, nullptr, c.lm_v.data() + (size_t)f * p * q,
+                        c.lm_u.data() + (size_t)f * q, &c.lm_nf[(size_t)f]));
+    c.lm_invn[(size_t)f] = 1.0 / (double)c.lm_nf[(size_t)f];
+  }
+  return PLAIDHIP_OK;
+}
+
 std::mutex g_multi_mu;
 std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
 int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
@@ -2421,6 +2540,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kPlaidTestContrasts: return check_plaid_test_contrasts_call(c);
     case kGsea: return check_gsea_call(c);
     case kFisher: return check_fisher_call(c);
+    case kLimma: return check_limma_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -2440,6 +2560,8 @@ int dispatch(const Target& t, Call c) {
   if (t.kind == Target::kContext) PH_REQUIRE(t.ctx != nullptr, "null plaidhip_ctx");
   if (c.method == kPlaidTestContrasts) {
     if (c.m == 0 || c.ncontrast == 0) return PLAIDHIP_OK;
+  } else if (c.method == kLimma) {
+    if (c.g == 0 || c.nfit == 0 || c.nq == 0) return PLAIDHIP_OK;
   } else if (c.method == kPlaidTest ? c.m == 0 : (int64_t)c.m * c.n == 0) {
     return PLAIDHIP_OK;
   }
@@ -2691,6 +2813,18 @@ int plaidhip_debug_gsea_scored_sharded_on_one_device(int device, int nshards, in
 int plaidhip_fisher_multi(const int* devices, int ndev, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp,
                           const int32_t* Gi, int32_t m, double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx) try {
   return dispatch(on_devices(devices, ndev), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_multi(const int* devices, int ndev, const double* A, int32_t rows, int32_t n, const double* design,
+                         int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double* out,
+                         double* hyper) try {
+  return dispatch(on_devices(devices, ndev), limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_limma_sharded_on_one_device(int device, int nshards, int fail_shard, const double* A, int32_t rows, int32_t n,
+                                               const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K,
+                                               int32_t q, double* out, double* hyper) try {
+  return dispatch(on_hook(device, nshards, fail_shard), limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fail_shard, const int8_t* sig, int32_t g, int32_t c,

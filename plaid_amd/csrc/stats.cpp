@@ -5,9 +5,11 @@
 //   pchisq(x, 2k, lower=FALSE)  = exp(-x/2) * sum_{i<k} (x/2)^i / i!
 //   qnorm / pnorm upper tails   = Wichura's AS241 (PPND16) / erfc
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <limits>
 #include <numeric>
+#include <thread>
 #include <vector>
 
 #include "common.h"
@@ -251,7 +253,269 @@ double combine_p(const double* p, int np, int method) {
   return pnorm_upper(zz / std::sqrt((double)np));
 }
 
+
+// ---- plaid.limma (include/plaidhip.h: plaidhip_limma): the design on the host, the empirical-Bayes tail --------------------
+
+namespace {
+
+// digamma, trigamma and tetragamma in plain fp64: the recurrence up to an argument >= 10, then the asymptotic series
+double lm_digamma(double x) {
+  double s = 0.0;
+  while (x < 10.0) { s -= 1.0 / x; x += 1.0; }
+  const double i2 = 1.0 / (x * x);
+  const double tail = i2 * (1.0 / 12.0 - i2 * (1.0 / 120.0 - i2 * (1.0 / 252.0 - i2 * (1.0 / 240.0 - i2 * (1.0 / 132.0 -
+                      i2 * (691.0 / 32760.0 - i2 * (1.0 / 12.0)))))));
+  return s + (std::log(x) - 0.5 / x - tail);
+}
+
+double lm_trigamma(double x) {
+  double s = 0.0;
+  while (x < 10.0) { s += 1.0 / (x * x); x += 1.0; }
+  const double i1 = 1.0 / x, i2 = i1 * i1;
+  const double tail = i1 * i2 * (1.0 / 6.0 - i2 * (1.0 / 30.0 - i2 * (1.0 / 42.0 - i2 * (1.0 / 30.0 - i2 * (5.0 / 66.0 -
+                      i2 * (691.0 / 2730.0 - i2 * (7.0 / 6.0)))))));
+  return s + (i1 + 0.5 * i2 + tail);
+}
+
+double lm_tetragamma(double x) {   // (only steers the Newton steps below: the root does not depend on its last bits)
+  double s = 0.0;
+  while (x < 10.0) { s -= 2.0 / (x * x * x); x += 1.0; }
+  const double i1 = 1.0 / x, i2 = i1 * i1;
+  return s - i2 * (1.0 + i1 + i2 * (0.5 - i2 * (1.0 / 6.0 - i2 * (1.0 / 6.0 - i2 * (3.0 / 10.0 - i2 * (5.0 / 6.0))))));
+}
+
+// y with trigamma(y) = v, v > 0: limma's closed forms at the two ends, else Newton on 1 / trigamma from 0.5 + 1 / v (the
+// function is convex there, so the steps rise monotonically to the root); stopped when a step is below 1e-14 y
+double lm_trigamma_inverse(double v) {
+  if (v > 1e7) return 1.0 / std::sqrt(v);
+  if (v < 1e-6) return 1.0 / v;
+  double y = 0.5 + 1.0 / v;
+  for (int it = 0; it < 60; ++it) {
+    const double tri = lm_trigamma(y);
+    const double dif = tri * (1.0 - tri / v) / lm_tetragamma(y);
+    y += dif;
+    if (!(std::fabs(dif) > 1e-14 * y)) break;
+  }
+  return y;
+}
+
+constexpr int kLimmaThreads = 8;              // host threads of the tails and of the Benjamini-Hochberg columns, at most
+constexpr int64_t kLimmaWork = 1 << 15;       // rows per thread below which another thread is not worth its start
+
+// fn(t, nth) on nth threads (t = 0 .. nth - 1); false: a thread could not be started or ran out of memory
+template <typename Fn>
+bool lm_threads(int64_t nth, Fn&& fn) {
+  if (nth <= 1) { fn((int64_t)0, (int64_t)1); return true; }
+  std::vector<std::thread> th;
+  std::atomic<int> failed{0};
+  try {
+    for (int64_t t = 0; t < nth; ++t)
+      th.emplace_back([&, t] {
+        try { fn(t, nth); } catch (...) { failed.store(1); }
+      });
+  } catch (...) { failed.store(1); }
+  for (auto& t : th) t.join();
+  return failed.load() == 0;
+}
+
+}  // namespace
+
+int limma_design(const char* what, const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q,
+                 int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf_out) {
+  std::vector<int32_t> sel;
+  for (int32_t c = 0; c < n; ++c)
+    if (use == nullptr || use[c] != 0) sel.push_back(c);
+  const int64_t nf = (int64_t)sel.size();
+  for (int64_t i = 0; i < nf; ++i)
+    for (int32_t k = 0; k < p; ++k)
+      PH_REQUIRE(std::isfinite(D[(int64_t)k * n + sel[(size_t)i]]), "%s: the design of fit %d is not finite at sample %d, column %d",
+                 what, fit, sel[(size_t)i] + 1, k + 1);
+  PH_REQUIRE(nf - p >= 1, "%s: fit %d has %lld samples for %d coefficients (at least %d: no residual degree of freedom)", what,
+             fit, (long long)nf, p, p + 1);
+  std::vector<double> a((size_t)nf * p), v0((size_t)p), vn((size_t)p), Rm((size_t)p * p, 0.0);
+  for (int32_t k = 0; k < p; ++k)
+    for (int64_t i = 0; i < nf; ++i) a[(size_t)(k * nf + i)] = D[(int64_t)k * n + sel[(size_t)i]];
+  for (int32_t k = 0; k < p; ++k) {
+    double* x = a.data() + (size_t)k * nf;
+    double col2 = 0.0, sub2 = 0.0;
+    for (int64_t i = 0; i < nf; ++i) col2 += D[(int64_t)k * n + sel[(size_t)i]] * D[(int64_t)k * n + sel[(size_t)i]];
+    for (int64_t i = k; i < nf; ++i) sub2 += x[i] * x[i];
+    const double alpha = x[k] >= 0.0 ? -std::sqrt(sub2) : std::sqrt(sub2);
+    PH_REQUIRE(std::fabs(alpha) > 1e-7 * std::sqrt(col2),
+               "%s: column %d of the design of fit %d is rank-deficient (|R_kk| = %g, the column's norm %g)", what, k + 1, fit,
+               std::fabs(alpha), std::sqrt(col2));
+    // the reflector's vector x - alpha e_1 stays in x[k ..], its first entry in v0 and its squared norm in vn
+    v0[(size_t)k] = x[k] - alpha;
+    double n2 = v0[(size_t)k] * v0[(size_t)k];
+    for (int64_t i = k + 1; i < nf; ++i) n2 += x[i] * x[i];
+    vn[(size_t)k] = n2;
+    for (int32_t j = k + 1; j < p; ++j) {
+      double* y = a.data() + (size_t)j * nf;
+      double dot = v0[(size_t)k] * y[k];
+      for (int64_t i = k + 1; i < nf; ++i) dot += x[i] * y[i];
+      const double s = 2.0 * dot / n2;
+      y[k] -= s * v0[(size_t)k];
+      for (int64_t i = k + 1; i < nf; ++i) y[i] -= s * x[i];
+    }
+    Rm[(size_t)k * p + k] = alpha;
+    for (int32_t j = k + 1; j < p; ++j) Rm[(size_t)j * p + k] = a[(size_t)j * nf + k];
+  }
+  if (Q != nullptr) {   // the thin Q: the reflectors applied to the first p columns of the identity, last reflector first
+    std::vector<double> qs((size_t)nf * p, 0.0);
+    for (int32_t j = 0; j < p; ++j) qs[(size_t)j * nf + j] = 1.0;
+    for (int32_t k = p - 1; k >= 0; --k) {
+      const double* x = a.data() + (size_t)k * nf;
+      for (int32_t j = k; j < p; ++j) {
+        double* y = qs.data() + (size_t)j * nf;
+        double dot = v0[(size_t)k] * y[k];
+        for (int64_t i = k + 1; i < nf; ++i) dot += x[i] * y[i];
+        const double s = 2.0 * dot / vn[(size_t)k];
+        y[k] -= s * v0[(size_t)k];
+        for (int64_t i = k + 1; i < nf; ++i) y[i] -= s * x[i];
+      }
+    }
+    std::fill(Q, Q + (size_t)n * p, 0.0);
+    for (int32_t k = 0; k < p; ++k)
+      for (int64_t i = 0; i < nf; ++i) Q[(int64_t)k * n + sel[(size_t)i]] = qs[(size_t)k * nf + i];
+  }
+  if (R != nullptr) std::copy(Rm.begin(), Rm.end(), R);
+  if (nf_out != nullptr) *nf_out = nf;
+  std::vector<double> vj((size_t)p);
+  for (int32_t j = 0; j < q && (v != nullptr || u != nullptr); ++j) {   // R' v_j = K_j, forward; u_j = |v_j|
+    double s2 = 0.0;
+    for (int32_t i = 0; i < p; ++i) {
+      double acc = K != nullptr ? K[(size_t)j * p + i] : (i == j ? 1.0 : 0.0);
+      for (int32_t l = 0; l < i; ++l) acc -= Rm[(size_t)i * p + l] * vj[(size_t)l];
+      vj[(size_t)i] = acc / Rm[(size_t)i * p + i];
+      s2 += vj[(size_t)i] * vj[(size_t)i];
+    }
+    if (v != nullptr) std::copy(vj.begin(), vj.end(), v + (size_t)j * p);
+    if (u != nullptr) u[j] = std::sqrt(s2);
+  }
+  return PLAIDHIP_OK;
+}
+
 }  // namespace plaidhip
+
+extern "C" {
+
+int plaidhip_limma_design(const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q, int32_t fit,
+                          double* Q, double* R, double* v, double* u, int64_t* nf) try {
+  using namespace plaidhip;
+  PH_REQUIRE(n >= 0 && q >= 0, "limma_design: bad dims n=%d q=%d", n, q);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "limma_design: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(K != nullptr || q == p, "limma_design: q = %d without K (the p = %d unit vectors)", q, p);
+  PH_REQUIRE(D != nullptr || n == 0, "limma_design: null design");
+  if (K != nullptr)
+    for (int64_t e = 0; e < (int64_t)p * q; ++e)
+      PH_REQUIRE(std::isfinite(K[e]), "limma_design: K[%lld] = %g (the contrasts are finite)", (long long)e, K[e]);
+  return limma_design("limma_design", D, n, p, use, K, q, fit, Q, R, v, u, nf);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_finish(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
+                          const int64_t* nf, const double* v, const double* u, double* out, double* hyper) try {
+  using namespace plaidhip;
+  PH_REQUIRE(rows >= 0 && nfit >= 0 && q >= 0, "limma_finish: bad dims rows=%d nfit=%d q=%d", rows, nfit, q);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "limma_finish: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  if (rows == 0 || nfit == 0 || q == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(E && rss && nf && v && u && out && hyper, "limma_finish: null argument");
+  for (int32_t f = 0; f < nfit; ++f)
+    PH_REQUIRE(nf[f] - p >= 1, "limma_finish: fit %d has %lld samples for %d coefficients", f + 1, (long long)nf[f], p);
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const size_t R = (size_t)rows;
+  // per fit: s2, the prior, s2.post and df.total
+  std::vector<double> s2(R * nfit), post(R * nfit), dft((size_t)nfit), xs;
+  for (int32_t f = 0; f < nfit; ++f) {
+    const double d = (double)(nf[f] - p);
+    double* s = s2.data() + R * f;
+    xs.clear();
+    for (size_t r = 0; r < R; ++r) {
+      s[r] = rss[R * f + r] / d;
+      if (std::isfinite(s[r])) xs.push_back(s[r]);
+    }
+    const int64_t nok = (int64_t)xs.size();
+    double d0 = 0.0, s0 = nan;
+    if (nok >= 2) {
+      const size_t h = (size_t)nok / 2;
+      std::nth_element(xs.begin(), xs.begin() + h, xs.end());
+      double med = xs[h];
+      if (nok % 2 == 0) med = (*std::max_element(xs.begin(), xs.begin() + h) + med) / 2.0;
+      if (med == 0.0) med = 1.0;
+      const double floor_x = 1e-5 * med, shift = -lm_digamma(0.5 * d) + std::log(0.5 * d);
+      double esum = 0.0, xsum = 0.0;
+      std::vector<double> e;
+      e.reserve((size_t)nok);
+      for (size_t r = 0; r < R; ++r) {   // (in row order: the sums below are pinned as ascending)
+        if (!std::isfinite(s[r])) continue;
+        const double x = std::max(s[r], floor_x);
+        e.push_back(std::log(x) + shift);
+        esum += e.back();
+        xsum += x;
+      }
+      const double ebar = esum / (double)nok;
+      double ss = 0.0;
+      for (double ei : e) ss += (ei - ebar) * (ei - ebar);
+      const double var = ss / (double)(nok - 1) - lm_trigamma(0.5 * d);
+      if (var > 0.0) {
+        const double y = lm_trigamma_inverse(var);
+        d0 = 2.0 * y;
+        s0 = std::exp(ebar + lm_digamma(y) - std::log(y));
+      } else {
+        d0 = inf;
+        s0 = xsum / (double)nok;
+      }
+    }
+    hyper[4 * (size_t)f] = d;
+    hyper[4 * (size_t)f + 1] = d0;
+    hyper[4 * (size_t)f + 2] = s0;
+    hyper[4 * (size_t)f + 3] = (double)nok;
+    dft[(size_t)f] = std::isinf(d0) ? (double)nok * d : std::min(d + d0, (double)nok * d);
+    double* po = post.data() + R * f;
+    for (size_t r = 0; r < R; ++r)
+      po[r] = !std::isfinite(s[r]) ? nan : std::isinf(d0) ? s0 : d0 == 0.0 ? s[r] : (d * s[r] + d0 * s0) / (d + d0);
+  }
+  // logFC, AveExpr, t, P.Value and sigma2 of every (fit, contrast, row): row chunks dealt to the threads
+  const int64_t ncol = (int64_t)nfit * q, items = ncol * rows;
+  const int32_t W1 = p + 1;
+  auto tails = [&](int64_t t, int64_t nth) {
+    const int64_t lo = items * t / nth, hi = items * (t + 1) / nth;
+    for (int64_t e = lo; e < hi; ++e) {
+      const int64_t col = e / rows;
+      const size_t r = (size_t)(e % rows);
+      const int32_t f = (int32_t)(col / q), j = (int32_t)(col % q);
+      double* o = out + (size_t)col * 6 * R;
+      const double sr = s2[R * f + r];
+      if (!std::isfinite(sr)) {
+        for (int c = 0; c < 6; ++c) o[(size_t)c * R + r] = nan;
+        continue;
+      }
+      const double* vj = v + ((size_t)f * q + j) * p;
+      double fc = 0.0;
+      for (int32_t k = 0; k < p; ++k) fc = std::fma(vj[k], E[((size_t)f * W1 + k) * R + r], fc);
+      const double tt = fc / (u[(size_t)f * q + j] * std::sqrt(post[R * f + r]));
+      o[r] = fc;
+      o[R + r] = E[((size_t)f * W1 + p) * R + r];
+      o[2 * R + r] = tt;
+      o[3 * R + r] = t_two_sided_p(tt, dft[(size_t)f]);
+      o[5 * R + r] = sr;
+    }
+  };
+  const int64_t nth = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, items / kLimmaWork}));
+  if (!lm_threads(nth, tails)) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+  auto adjust = [&](int64_t t, int64_t nt) {
+    for (int64_t col = t; col < ncol; col += nt) {
+      double* o = out + (size_t)col * 6 * R;
+      p_adjust_fdr(o + 3 * R, rows, o + 4 * R);
+    }
+  };
+  const int64_t nbh = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, items / kLimmaWork, ncol}));
+  if (!lm_threads(nbh, adjust)) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+}  // extern "C"
 
 // Test hook (not part of include/plaidhip.h): the distribution functions above, so that the CPU-side
 // tests can check them against scipy without a device.  kind 0: 2*pt(|x|, a, lower=FALSE);

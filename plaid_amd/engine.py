@@ -398,6 +398,104 @@ def hyper_tail(N, K, k, x) -> float:
     return p.value
 
 
+LIMMA_MAX_COEF = 32   # PLAIDHIP_LIMMA_MAX_COEF
+LIMMA_COLUMNS = ("logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2")
+LIMMA_HYPER = ("df.residual", "df.prior", "s2.prior", "n.ok")
+
+
+def limma_tile() -> int:
+    """PLAIDHIP_LIMMA_TILE: the weight columns that share one read of the matrix (needs no device)"""
+    return int(_lib.load().plaidhip_limma_tile())
+
+
+def limma_operands(n, design, use=None, contrasts=None):
+    """design, use and contrasts as the C ABI takes them: (D n x p x nfit float64, use n x nfit int8 or None, K p x q float64
+    or None, q), all Fortran-ordered.  design: n x p (one fit) or n x p x nfit; use: n or n x nfit, anything that is zero,
+    False or NaN leaves the sample out; contrasts: p or p x q."""
+    D = np.asarray(design, dtype=np.float64)
+    if D.ndim == 2:
+        D = D[:, :, None]
+    if D.ndim != 3 or D.shape[0] != n:
+        raise ValueError("design must be samples x coefficients (x fits), one row per column of the matrix")
+    D = np.asfortranarray(D)
+    p, nfit = D.shape[1], D.shape[2]
+    U = None
+    if use is not None:
+        U = np.asarray(use)
+        if U.ndim == 1:
+            U = U[:, None]
+        if U.shape != (n, nfit):
+            raise ValueError("use must be samples x fits")
+        if U.dtype.kind == "f":
+            U = ~np.isnan(U) & (U != 0)
+        U = np.asfortranarray(U != 0, dtype=np.int8)
+    K = None
+    if contrasts is not None:
+        K = np.asarray(contrasts, dtype=np.float64)
+        if K.ndim == 1:
+            K = K[:, None]
+        if K.ndim != 2 or K.shape[0] != p:
+            raise ValueError("contrasts must be coefficients x contrasts")
+        K = np.asfortranarray(K)
+    return D, U, K, (p if K is None else K.shape[1])
+
+
+def _limma(fn, head, A, design, use=None, contrasts=None, out=None, hyper=None):
+    """plaidhip_limma / _multi / the hook: (out, hyper) -- rows x 6 x q x nfit (LIMMA_COLUMNS) and nfit x 4 (LIMMA_HYPER)"""
+    A = _as_f64_fortran(A)
+    if A.ndim != 2:
+        raise ValueError("limma: the matrix must be rows x samples")
+    rows, n = A.shape
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    out = np.full((rows, 6, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 4), np.nan, dtype=np.float64) if hyper is None else hyper
+    check(fn(*head, _np_ptr(A), rows, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+             q, _np_ptr(out), _np_ptr(hyper)))
+    return out, hyper
+
+
+def limma_design(design, use=None, contrasts=None, fit=1) -> dict:
+    """plaidhip_limma_design on the host (no device is touched): the thin Q (n x p, zero rows for the samples left out) and R
+    of the Householder QR of one design's used rows, v = R^-T K (p x q), u = |v_j| (limma's stdev.unscaled) and n_f"""
+    D0 = np.asarray(design, dtype=np.float64)
+    if D0.ndim != 2:
+        raise ValueError("limma_design: one design, samples x coefficients")
+    D, U, K, q = limma_operands(D0.shape[0], D0, use, contrasts)
+    n, p = D.shape[0], D.shape[1]
+    Q = np.full((n, p), np.nan, order="F")
+    R = np.full((p, p), np.nan, order="F")
+    v = np.full((p, q), np.nan, order="F")
+    u = np.full(q, np.nan)
+    nf = C.c_int64(-1)
+    check(_lib.load().plaidhip_limma_design(_np_ptr(D), n, p, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+                                            q, int(fit), _np_ptr(Q), _np_ptr(R), _np_ptr(v), _np_ptr(u),
+                                            C.cast(C.byref(nf), C.c_void_p)))
+    return {"Q": Q, "R": R, "v": v, "u": u, "nf": int(nf.value)}
+
+
+def limma_finish(E, rss, nf, v, u):
+    """plaidhip_limma_finish on the host (no device is touched): E (nfit (p + 1)) x rows -- per fit its p effects, then the
+    means --, rss nfit x rows, nf the samples of every fit, v p x q x nfit, u q x nfit -> (out rows x 6 x q x nfit, hyper
+    nfit x 4)"""
+    v = np.asarray(v, dtype=np.float64)
+    v = v[:, :, None] if v.ndim == 2 else v
+    p, q, nfit = v.shape
+    E = np.ascontiguousarray(np.asarray(E, dtype=np.float64).reshape(nfit * (p + 1), -1))
+    rows = E.shape[1]
+    rss = np.ascontiguousarray(np.asarray(rss, dtype=np.float64).reshape(nfit, rows))
+    nf = np.ascontiguousarray(np.atleast_1d(nf), dtype=np.int64)
+    u = np.asfortranarray(np.asarray(u, dtype=np.float64).reshape((q, nfit), order="F"))
+    v = np.asfortranarray(v)
+    if nf.shape != (nfit,):
+        raise ValueError("limma_finish: nf has one entry per fit")
+    out = np.full((rows, 6, q, nfit), np.nan, dtype=np.float64, order="F")
+    hyper = np.full((nfit, 4), np.nan, dtype=np.float64)
+    check(_lib.load().plaidhip_limma_finish(rows, p, nfit, q, _np_ptr(E), _np_ptr(rss), _np_ptr(nf), _np_ptr(v), _np_ptr(u),
+                                            _np_ptr(out), _np_ptr(hyper)))
+    return out, hyper
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -777,6 +875,20 @@ class Context:
         return _gsea(self.lib.plaidhip_gsea_scored, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type,
                      leading_edge)
 
+    def limma(self, A, design, use=None, contrasts=None):
+        """plaidhip_limma: moderated t-tests of the rows of A (rows x samples) for the designs (samples x p, or x p x nfit),
+        the samples `use` leaves out (samples x nfit, None: none) and the contrasts (p x q, None: every coefficient):
+        (out rows x 6 x q x nfit in LIMMA_COLUMNS, hyper nfit x 4 in LIMMA_HYPER)"""
+        return _limma(self.lib.plaidhip_limma, (self.handle,), A, design, use, contrasts)
+
+    def dev_row_design_effects(self, A: int, ld: int, rows: int, n: int, Q: int, use, invn: int, p: int, nfit: int, seed, E: int):
+        """plaidhip_dev_row_design_effects on device pointers: E [nfit (p + 1)][rows]; use and seed may be None"""
+        check(self.lib.plaidhip_dev_row_design_effects(self.handle, A, ld, rows, n, Q, use, invn, p, nfit, seed, E))
+
+    def dev_row_design_rss(self, A: int, ld: int, rows: int, n: int, Q: int, use, p: int, nfit: int, E: int, seed, rss: int):
+        """plaidhip_dev_row_design_rss on device pointers: rss [nfit][rows] at the effects E of all samples"""
+        check(self.lib.plaidhip_dev_row_design_rss(self.handle, A, ld, rows, n, Q, use, p, nfit, E, seed, rss))
+
     def fisher(self, sig, Gp, Gi, overlap=False):
         """plaidhip_fisher: over-representation tests of the columns of sig (genes x lists of -1 / 0 / +1) against the sets:
         (out, tot) -- sets x 12 x lists (FISHER_COLUMNS) and the 2 x lists totals nUp, nDn; with overlap also (ov_len, ov_idx),
@@ -970,6 +1082,11 @@ def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, 
 def fisher_multi(sig, Gp, Gi, overlap=False, devices=1):
     """plaid.fisher (Context.fisher) with the lists shared out over `devices`: the one-device bits"""
     return _fisher(*_multi("fisher", devices), sig, Gp, Gi, overlap)
+
+
+def limma_multi(A, design, use=None, contrasts=None, devices=1):
+    """plaid.limma (Context.limma) with the sample columns sharded over `devices`: the one-device bits"""
+    return _limma(*_multi("limma", devices), A, design, use, contrasts)
 
 
 def multi_finalize():

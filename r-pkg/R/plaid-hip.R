@@ -604,6 +604,89 @@ plaid.fisher <- function(sig, G, minSize = 1, maxSize = NULL, sort.by = "pAny", 
 }
 
 
+## the tables of plaid.limma() / plaid.limma.contrasts() from the library's rows x 6 block: topTable's order for sort.by --
+## "none" (the rows of S), "P.Value" / "P" / "p" (increasing), "t" and "logFC" (decreasing magnitude), "AveExpr" (decreasing)
+.limma_sorts <- c("none", "P.Value", "P", "p", "t", "logFC", "AveExpr")
+
+.limma_table <- function(tab, rn, sort.by) {
+  cols <- c("logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2")
+  res <- matrix(tab, nrow = length(rn), ncol = 6L, dimnames = list(rn, cols))
+  key <- switch(sort.by, none = NULL, P.Value = , P = , p = res[, "P.Value"], t = -abs(res[, "t"]),
+                logFC = -abs(res[, "logFC"]), AveExpr = -res[, "AveExpr"],
+                stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", ")))
+  if (!is.null(key)) res <- res[order(key), , drop = FALSE]
+  res
+}
+
+.limma_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok"))
+
+
+## plaid.limma(): limma's moderated t-test (lmFit + eBayes + topTable, as pinned in include/plaidhip.h: plaidhip_limma) of
+## every row of S -- single-sample scores (sets x samples) or expression (genes x samples) -- for one design (samples x
+## coefficients).  contrasts: coefficients x contrasts, NULL: every coefficient.  use: one entry per sample, FALSE / 0 / NA
+## leaves it out of the fit.  Returns list(tables = <named list, one matrix per contrast: rows x (logFC, AveExpr, t, P.Value,
+## adj.P.Val, sigma2), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok)).  logFC and P.Value are what
+## plaid.sig() and plaid.gsea() take.  Not offered: trend, robust, weights, the B- and F-statistics, per-row missing values
+## (an NA in a used sample makes the row NA), a sparse S.
+plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none") {
+  S <- as.matrix(S); storage.mode(S) <- "double"
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(S)) stop("design must have one row per column of S")
+  cn <- if (is.null(colnames(design))) paste0("coef", seq_len(ncol(design))) else colnames(design)
+  if (!is.null(contrasts)) {
+    contrasts <- as.matrix(contrasts); storage.mode(contrasts) <- "double"
+    if (nrow(contrasts) != ncol(design)) stop("contrasts must have one row per coefficient")
+    cn <- if (is.null(colnames(contrasts))) as.character(seq_len(ncol(contrasts))) else colnames(contrasts)
+  }
+  if (!is.null(use)) {
+    if (length(use) != ncol(S)) stop("use must have one entry per column of S")
+    use <- matrix(as.integer(!is.na(use) & use != 0), ncol = 1)
+  }
+  rn <- if (is.null(rownames(S))) paste0("row", seq_len(nrow(S))) else rownames(S)
+  if (length(sort.by) != 1L || !sort.by %in% .limma_sorts) stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", "))
+  .session()
+  r <- .Call("R_plaidhip_limma", .devices(), S, design, 1L, use, contrasts, PACKAGE = "plaidhip")
+  out <- r[[1]]
+  dim(out) <- c(nrow(S), 6L, length(cn))
+  tables <- lapply(seq_along(cn), function(j) .limma_table(out[, , j], rn, sort.by))
+  names(tables) <- cn
+  list(tables = tables, hyper = .limma_hyper(r[[2]][, 1]))
+}
+
+
+## plaid.limma.contrasts(): gx.limma(S, y, B, method = 1) (experiments/R/functions.R:294-444) for every column of a contrast
+## matrix Y (samples x contrasts; 0, 1, NA = the sample takes no part) in ONE call: contrast j fits [1, Y[, j], B] on the
+## samples with a label and tests the coefficient of Y[, j].  B: batch covariates (samples x covariates) or NULL.  S is
+## uploaded once and read ceiling(ncol(Y) * (p + 1) / 8) times for the effects.  Returns list(tables = <named list (the
+## columns of Y) of plaid.limma() tables>, hyper = <named list of their hyper-parameters>).
+plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none") {
+  S <- as.matrix(S); storage.mode(S) <- "double"
+  Y <- as.matrix(Y)
+  if (nrow(Y) != ncol(S)) stop("Y must have one row per column of S")
+  if (!all(unique(as.vector(Y)) %in% c(0, 1, NA))) stop("elements of Y must be 0, 1 or NA")
+  if (!is.null(B)) {
+    B <- as.matrix(B); storage.mode(B) <- "double"
+    if (nrow(B) != ncol(S)) stop("B must have one row per column of S")
+  }
+  D <- do.call(cbind, lapply(seq_len(ncol(Y)), function(j) cbind(1, ifelse(is.na(Y[, j]), 0, Y[, j]), B)))
+  storage.mode(D) <- "double"
+  p <- 2L + (if (is.null(B)) 0L else ncol(B))
+  K <- matrix(0, p, 1); K[2, 1] <- 1
+  use <- matrix(as.integer(!is.na(Y)), nrow(Y), ncol(Y))
+  cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
+  rn <- if (is.null(rownames(S))) paste0("row", seq_len(nrow(S))) else rownames(S)
+  if (length(sort.by) != 1L || !sort.by %in% .limma_sorts) stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", "))
+  .session()
+  r <- .Call("R_plaidhip_limma", .devices(), S, D, ncol(Y), use, K, PACKAGE = "plaidhip")
+  out <- r[[1]]
+  dim(out) <- c(nrow(S), 6L, ncol(Y))
+  tables <- lapply(seq_len(ncol(Y)), function(j) .limma_table(out[, , j], rn, sort.by))
+  hyper <- lapply(seq_len(ncol(Y)), function(j) .limma_hyper(r[[2]][, j]))
+  names(tables) <- names(hyper) <- cn
+  list(tables = tables, hyper = hyper)
+}
+
+
 ## replaid.gsva(), R/plaid.R:338-363: the row transform ("z" or "ecdf"), the signed ranks, the power and
 ## plaid() run on the device in one call.
 replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {

@@ -648,6 +648,42 @@ SEXP R_plaidhip_fisher(SEXP devices, SEXP sig, SEXP Gp, SEXP Gi, SEXP overlap) {
   return res;
 }
 
+/* plaid.limma(): list(out, hyper) of plaidhip_limma -- out a rows x (6 q nfit) matrix (the caller gives it dim rows x 6 x q x
+ * nfit), hyper 4 x nfit (df.residual, df.prior, s2.prior, n.ok down a column).  A: rows x n doubles; design: n x (p nfit)
+ * doubles, the fits' designs side by side; use: NULL or an n x nfit integer matrix (0 or NA: the sample takes no part; R has
+ * no 8-bit integer: it is narrowed here); K: NULL (every coefficient) or p x q doubles; several devices: the _multi entry */
+SEXP R_plaidhip_limma(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use, SEXP K) {
+  const int rows = Rf_nrows(A), n = Rf_ncols(A), nfit = Rf_asInteger(nfit_);
+  if (nfit < 1 || Rf_nrows(design) != n || Rf_ncols(design) % nfit != 0)
+    Rf_error("plaid.limma: design must have one row per sample and the same number of columns for every fit");
+  const int p = Rf_ncols(design) / nfit;
+  const int q = Rf_isNull(K) ? p : Rf_ncols(K);
+  if (!Rf_isNull(K) && Rf_nrows(K) != p) Rf_error("plaid.limma: contrasts must have one row per coefficient");
+  int8_t* u8 = NULL;
+  if (!Rf_isNull(use)) {
+    if (Rf_nrows(use) != n || Rf_ncols(use) != nfit) Rf_error("plaid.limma: use must be samples x fits");
+    const size_t count = (size_t)n * (size_t)nfit;
+    const int* u = INTEGER(use);
+    u8 = (int8_t*)R_alloc(count > 0 ? count : 1, 1);
+    for (size_t e = 0; e < count; ++e) u8[e] = (int8_t)(u[e] != 0 && u[e] != NA_INTEGER);
+  }
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, rows, 6 * q * nfit));
+  SEXP hyper = PROTECT(Rf_allocMatrix(REALSXP, 4, nfit));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, hyper);
+  const double* Kp = Rf_isNull(K) ? NULL : REAL(K);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_limma_multi(INTEGER(devices), LENGTH(devices), REAL(A), rows, n, REAL(design), p, nfit, u8, Kp, q, REAL(out),
+                              REAL(hyper));
+  else
+    rc = plaidhip_limma(ctx(), REAL(A), rows, n, REAL(design), p, nfit, u8, Kp, q, REAL(out), REAL(hyper));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(3);
+  return res;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -692,6 +728,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsea", (DL_FUNC)&R_plaidhip_gsea, 9},
     {"R_plaidhip_gsea_scored", (DL_FUNC)&R_plaidhip_gsea_scored, 11},
     {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
+    {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {

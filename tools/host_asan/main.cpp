@@ -1,6 +1,6 @@
 // Sanitizer run of the library's host code (ASan / UBSan on the CPU build): the index planners
 // of geneset.cpp (tile schedules, edge colouring, pair slices, scatter segments -- 840 lines of index arithmetic),
-// the GMT parser and gmt2mat of gmt.cpp, and the p-value tails of stats.cpp.  Built and run by
+// the GMT parser and gmt2mat of gmt.cpp, and the p-value tails and plaid.limma's host half of stats.cpp.  Built and run by
 // `make -C plaid_amd/csrc host-asan`; any sanitizer report aborts with a non-zero status.
 #include <algorithm>
 #include <cinttypes>
@@ -166,6 +166,55 @@ static void tails() {
   printf("  stats: 2000 random moment sets through the t / chi^2 / normal tails, combine_p and BH\n");
 }
 
+// plaid.limma's host half: designs that fit and designs that are refused through plaidhip_limma_design, and
+// plaidhip_limma_finish on both sides of its thread threshold, with rows that are not ok
+static void limma() {
+  std::mt19937_64 rng(7);
+  std::normal_distribution<double> N(0.0, 1.0);
+  for (int p : {1, 2, 3, 32}) {
+    const int n = p + 1 + (int)(rng() % 9), q = p;
+    std::vector<double> D((size_t)n * p), Q((size_t)n * p), R((size_t)p * p), v((size_t)p * q), u((size_t)q);
+    std::vector<int8_t> use((size_t)n + 3, 1);
+    for (auto& x : D) x = N(rng);
+    for (int c = 0; c < n; ++c) D[(size_t)c] = 1.0;
+    int64_t nf = 0;
+    REQUIRE(plaidhip_limma_design(D.data(), n, p, nullptr, nullptr, q, 1, Q.data(), R.data(), v.data(), u.data(), &nf) == PLAIDHIP_OK);
+    REQUIRE(nf == n);
+    for (int j = 0; j < q; ++j) REQUIRE(u[(size_t)j] > 0.0);
+    // three more samples that take no part and hold NaN; nothing but u asked for
+    std::vector<double> D2((size_t)(n + 3) * p, NAN);
+    for (int k = 0; k < p; ++k)
+      for (int c = 0; c < n; ++c) D2[(size_t)k * (n + 3) + c + (c >= 2 ? 3 : 0)] = D[(size_t)k * n + c];
+    use[2] = use[3] = use[4] = 0;
+    std::vector<double> u2((size_t)q);
+    REQUIRE(plaidhip_limma_design(D2.data(), n + 3, p, use.data(), nullptr, q, 2, nullptr, nullptr, nullptr, u2.data(), &nf) == PLAIDHIP_OK);
+    REQUIRE(nf == n);
+    for (int j = 0; j < q; ++j) REQUIRE(std::fabs(u2[(size_t)j] - u[(size_t)j]) <= 1e-12 * u[(size_t)j]);
+    if (p >= 2) {   // a duplicated column, n_f = p
+      for (int c = 0; c < n; ++c) D[(size_t)(p - 1) * n + c] = D[(size_t)c];
+      REQUIRE(plaidhip_limma_design(D.data(), n, p, nullptr, nullptr, q, 1, Q.data(), nullptr, nullptr, nullptr, nullptr) == PLAIDHIP_EINVAL);
+      REQUIRE(plaidhip_limma_design(D.data(), p, p, nullptr, nullptr, q, 1, nullptr, nullptr, nullptr, nullptr, nullptr) == PLAIDHIP_EINVAL);
+    }
+  }
+  for (int rows : {1, 3, 500, 70001}) {
+    const int p = 2, nfit = 2, q = 2;
+    std::vector<double> E((size_t)nfit * (p + 1) * rows), rss((size_t)nfit * rows), v((size_t)p * q * nfit), u((size_t)q * nfit, 0.5);
+    std::vector<double> out((size_t)rows * 6 * q * nfit), hyper((size_t)nfit * 4);
+    for (auto& x : E) x = N(rng);
+    for (auto& x : v) x = N(rng);
+    for (auto& x : rss) { const double z = N(rng); x = z * z; }
+    if (rows >= 3) { rss[1] = NAN; rss[(size_t)rows + 2] = INFINITY; rss[0] = 0.0; }
+    const int64_t nf[2] = {9, 3};
+    REQUIRE(plaidhip_limma_finish(rows, p, nfit, q, E.data(), rss.data(), nf, v.data(), u.data(), out.data(), hyper.data()) == PLAIDHIP_OK);
+    for (size_t e = 0; e < (size_t)rows; ++e) {
+      const double pv = out[3 * (size_t)rows + e];
+      REQUIRE(std::isnan(pv) || (pv >= 0.0 && pv <= 1.0));
+    }
+    REQUIRE(hyper[3] == (double)(rows >= 3 ? rows - 1 : rows));
+  }
+  printf("  limma: designs of 1, 2, 3 and 32 coefficients, refused ones, and the finish step up to 70,001 rows on host threads\n");
+}
+
 int main() {
   printf("[host-asan] planners\n");
   plans();
@@ -173,6 +222,8 @@ int main() {
   gmt();
   printf("[host-asan] p-value tails\n");
   tails();
+  printf("[host-asan] plaid.limma's design and finish\n");
+  limma();
   printf("[host-asan] ok\n");
   return 0;
 }
