@@ -250,7 +250,8 @@ int plaidhip_dev_colranks_csc_dense_nz_f64(plaidhip_ctx* ctx, const void* Xp, co
  * PLAIDHIP_TIES_LAST -- and, when alpha != 0, W = rank(x, "average")^alpha and P = W * Q (leading dimension ldq).  W is
  * bit-identical to plaidhip_dev_colranks_dense_f64(PLAIDHIP_TIES_AVERAGE, power = alpha) wherever that call takes the
  * bucket or partitioned ranker (columns of more than 256 genes; a clustered column the bucket ranker hands to the sorting
- * network gets pow() there and 1/4-step roots here, a few ulp apart).  colnan: n uint32, 1 for a column holding a NaN.
+ * network gets pow() there and 1/4-step roots here: each within its allowance of the exact power -- 3 u = 3 * 2^-53
+ * relative for pow(), 0 to 5.5 u for the roots by the count in rank_bucket.h -- so at most 8.5 u apart).  colnan: n uint32, 1 for a column holding a NaN.
  * Two rank passes (average ranks, then min ranks of (2 r - 1) 2^26 + (g - 1 - i)); scratch: 2 ldq n doubles; g < 2^26. */
 int plaidhip_dev_ssgsea_exact_operands_f64(plaidhip_ctx* ctx, const void* X, int64_t ldx, int32_t g, int32_t n, double alpha,
                                            void* Q, void* W, void* P, int64_t ldq, void* scratch, void* colnan);

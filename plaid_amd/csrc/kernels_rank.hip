@@ -325,6 +325,36 @@ static int launch_network(plaidhip_ctx* ctx, const double* Xv, int64_t ldx, int3
   return PLAIDHIP_OK;
 }
 
+// Signed ranks with a generic power: the bucket ranker's pow() loop writes 0 for a zero and skips its power, so a column
+// with no other valid entry is left with the start value of its maximum (-inf; 0 for the stored values of a CSC column).
+// Every other route -- the bucket ranker's quarter path, the sorting networks, the partitioned ranker -- takes the maximum
+// before the sign and the zero mask: such a column's maximum is the common weight of its tied zeros, ((g + 1) / 2)^power for
+// the average rank of g zeros.  This pass gives the bucket ranker's columns that value: one wavefront per column reads
+// colmax[c] and only counts the zeros of a column that is still at the start value (lb = 0, ub = their number).
+__global__ void __launch_bounds__(256)
+colmax_zero_group_kernel(const double* __restrict__ Xv, int64_t ldx, int32_t g_dense, const int32_t* __restrict__ Xp,
+                         int32_t n, int ties, double power, int densified, double* __restrict__ colmax) {
+  const int lane = threadIdx.x & 63;
+  for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < n; c += gridDim.x * 4) {   // (c is uniform in the wavefront)
+    const double start = (Xp != nullptr && !densified) ? 0.0 : -INFINITY;
+    if (colmax[c] != start) continue;
+    const double* xc = Xp != nullptr ? Xv + Xp[c] : Xv + (int64_t)c * ldx;
+    const int32_t cnt = Xp != nullptr ? Xp[c + 1] - Xp[c] : g_dense;
+    uint32_t zeros = 0, others = 0;
+    for (int32_t i = lane; i < cnt; i += 64) {
+      const double v = xc[i];
+      zeros += (v == 0.0) ? 1u : 0u;
+      others += (v == 0.0) ? 0u : 1u;                         // (NaN: no rank, no part in the maximum)
+    }
+    zeros = wave_incl_scan_u32(zeros);
+    others = wave_incl_scan_u32(others);
+    if (lane == 63) {
+      const uint32_t nz = densified ? (uint32_t)g_dense - others : zeros;      // (the implicit zeros of a densified column)
+      if (nz != 0u) colmax[c] = PH_POW(rank_from_bounds(0u, nz, ties), power);
+    }
+  }
+}
+
 template <int BLOCK, int KPT>
 static int launch_bucket(plaidhip_ctx* ctx, const RankBucketArgs& a, int32_t max_len, int grid) {
   using L = RankBucketLayout<BLOCK, KPT>;
@@ -430,8 +460,16 @@ static int launch_ranks(plaidhip_ctx* ctx, const double* Xv, int64_t ldx, int32_
   if (rc != PLAIDHIP_OK) return rc;
   // columns the bucket kernel gave up on (clustered values): a small persistent grid reads the device-side list
   const int fb_grid = grid_cap < ctx->num_cu ? grid_cap : ctx->num_cu;
-  return launch_network(ctx, Xv, ldx, g_dense, Xp, n, max_len, ties, is_signed, power, R, ldr, colmax, Xi_dense,
-                        dscratch, fb_grid, ws_off, fb_list, fb_count);
+  rc = launch_network(ctx, Xv, ldx, g_dense, Xp, n, max_len, ties, is_signed, power, R, ldr, colmax, Xi_dense,
+                      dscratch, fb_grid, ws_off, fb_list, fb_count);
+  if (rc != PLAIDHIP_OK) return rc;
+  if (colmax != nullptr && is_signed && a.pow_q4 == 0 && power != 1.0) {
+    const int cap = ctx->num_cu * 8, blocks = (n + 3) / 4;
+    hipLaunchKernelGGL(colmax_zero_group_kernel, dim3(blocks < cap ? blocks : cap), dim3(256), 0, ctx->stream, Xv, ldx, g_dense,
+                       Xp, n, ties, power, Xi_dense != nullptr ? 1 : 0, colmax);
+    PH_HIP(hipGetLastError());
+  }
+  return PLAIDHIP_OK;
 }
 
 // ---- dense columns beyond the LDS: rank by value partition --------------------------------------------------------------

@@ -89,7 +89,9 @@ __device__ __forceinline__ double ph_max_f64(double a, double b) {
 // simplified Newton iteration z += z (r - z^4) / (4 r) with 1 / (4 r) taken from the first estimate (its 2^-22 error only
 // scales the correction: 2^-22 -> 2^-44 -> 2^-66): 12 fp64 instructions against ~30 for sqrt(sqrt(r)) -- the rank kernel is
 // bound by its vector instructions (5.2k per wavefront and column, profiles/r06p_pmc_c4_summary.txt), and ssGSEA's
-// alpha = 0.25 spent a fifth of them on the two correctly rounded square roots.  Within 1 ulp of sqrt(sqrt(r)).
+// alpha = 0.25 spent a fifth of them on the two correctly rounded square roots.  Within 1 ulp of sqrt(sqrt(r)) and within
+// rho = 2 u (u = 2^-53, relative) of the exact r^(1/4): both asserted for every half-integer rank up to 196,608, on every
+// kernel that calls this, by tests/test_gpu_rank_weights.py (the measured maxima are in DESIGN.md 6.1).
 __device__ __forceinline__ double root4_pos(double r) {
   const double y = __builtin_amdgcn_rsq(r);          // ~ r^-1/2
   double z = __builtin_amdgcn_rsq(y);                // ~ r^1/4
@@ -103,7 +105,13 @@ __device__ __forceinline__ double root4_pos(double r) {
   return z;
 }
 
-// r^(q/4) for r > 0 by (correctly rounded) square roots and multiplications: a few ulp, ~6x cheaper than pow()
+// r^(q/4) for r > 0 by (correctly rounded) square roots and multiplications, ~6x cheaper than pow().  The error against the
+// exact power, counted from the operations below for a rank r (a half-integer of at most 19 significant bits: r, r^2 and
+// 1.0 * x are exact; one u = 2^-53 per inexact product or root; an error halves through a root), rho = root4_pos's 2 u:
+//     q      1    2  3    4  5        6  7    8  9        10  11   12  13       14  15   16
+//     <= u   rho  1  3.5  0  rho + 1  2  4.5  0  rho + 1  2   4.5  1   rho + 2  3   5.5  1
+// (3.90 and 3.96 u are reached at q = 7, 11 and 15: above the 3 u of pow()).  tests/helpers/pow_ref.py restates the
+// sequence in numpy; tests/test_gpu_rank_weights.py holds every route to its bits and to these counts over every rank.
 __device__ __forceinline__ double pow_quarters(double r, int q) {
   double res = 1.0, base = r;
   for (int e = q >> 2; e; e >>= 1) {

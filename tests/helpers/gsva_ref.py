@@ -20,12 +20,14 @@ import scipy.sparse as sp
 import scipy.stats as st
 
 from tests.helpers import exact_ref as er
+from tests.helpers.pow_ref import pow_allowance_u
 
 ld = np.longdouble
 assert np.finfo(ld).eps == 2.0 ** -63, "the references need x87 extended precision (long double with a 64-bit significand)"
 U = er.U
-POW_ULPS = 3.0          # the project's allowance for one device weight r^p, p != 1 (pow_quarters / pow()): 3 u
-EXP2_ULPS = 3.0         # the allowance for one device 2^x (map_kernel ops 2, 3): starts at the same 3 u
+# (one device weight r^p, p != 1: pow_ref.pow_allowance_u(p) u -- counted from pow_quarters' code or pow()'s 3 u, and held
+# on the device over every rank by tests/test_gpu_rank_weights.py)
+EXP2_ULPS = 3.0         # the allowance for one device 2^x (map_kernel ops 2, 3): 3 u
 
 
 # ------------------------------------------------------------------ shared with test_gpu_exact_sums.py
@@ -203,8 +205,9 @@ def gsva_raw_ref(X, Gp, Gi, tau, rowtf):
     the device's raw score, mag = w sum |weight| / max.  The device (multi.cpp, scorer_worker) sums its own weights
     (k - 1 roundings) and applies fl(1 / max) * (sum * w): 3 roundings; the reference rounds T once; one spare: c = 5 for
     tau = 0, where weights and max are half-integers, exact on both sides.  tau > 0: every device weight is within
-    POW_ULPS u of r^(1 + tau) (pow_quarters for 1.5, pow() for 1.3), which carries to the sum and to the max: c = 5 + 6.
-    The row transform adds nothing: under separated() it changes no rank."""
+    a = pow_allowance_u(1 + tau) u of r^(1 + tau) (3 u for 1.5 and 1.3 on whichever route a column takes, 4.5 u for
+    pow_quarters' 1.75), which carries to the sum and to the max: c = 5 + 2 a.  The row transform adds nothing: under
+    separated() it changes no rank."""
     sign, R = gsva_signed_ranks(X, rowtf)
     power = ld(np.float64(1.0) + np.float64(tau)) if tau > 0 else ld(1.0)     # the device's fp64 exponent
     W = sign.astype(ld) * np.power(R.astype(ld), power)
@@ -212,7 +215,7 @@ def gsva_raw_ref(X, Gp, Gi, tau, rowtf):
     P, mag, k = _long_sums(Gp, Gi, W)
     w = _w(Gp)[:, None]
     T = (w.astype(ld) * (P / wmax)).astype(np.float64)
-    c = 5.0 + (2.0 * POW_ULPS if tau > 0 else 0.0)
+    c = 5.0 + (2.0 * pow_allowance_u(np.float64(1.0) + np.float64(tau)) if tau > 0 else 0.0)
     E = (k + c) * U * (w * mag / float(wmax))
     return T, E, float(wmax)
 

@@ -13,6 +13,7 @@ import scipy.sparse as sp
 
 from tests.helpers import exact_ref as er
 from tests.helpers.gsva_ref import _long_sums, _normalized_ref, _w
+from tests.helpers.pow_ref import pow_allowance_u
 
 pytestmark = pytest.mark.gpu
 
@@ -346,17 +347,17 @@ def _rank_case(sparse, seed):
     return g, Gp, Gi, X
 
 
-@pytest.mark.parametrize("sparse", [False, True])
-@pytest.mark.parametrize("alpha", [0.0, 0.25])
-def test_replaid_ssgsea_within_the_bound_of_exact_rank_sums(hip_ctx, sparse, alpha):
+def _ssgsea_within_the_bound(hip_ctx, sparse, alpha):
     """replaid.ssgsea in the default staging: mean over the set of (r^(1 + alpha) / max(r^(1 + alpha)) - 0.5), then
     normalize_medians (R/plaid.R:245-253).  Reference: the oracle's average ranks (sparse: zeros stay 0), their powers in
     long double, exact sums P, T = w (P / max - 0.5 k) in long double.
 
     The device sums its weights and applies alpha * (sum * w) + beta * (k * w) with alpha = fl(1 / max), beta = -0.5.
-    Relative to mag = w (P / max + 0.5 k), c counts: the device's r^1.25 (<= 3 u per weight, and so on the sum and on its
-    max: 3 + 3), fl(1 / max) 1, sum * w 1, alpha * (...) 1, k * w 1, the final add 1, the reference's sum P and T 2: c = 12
-    for alpha = 0.25; alpha = 0 has exact weights and max: c = 6.  The sum itself: (k - 1) roundings in fp64 -- or, where
+    Relative to mag = w (P / max + 0.5 k), c counts: the device's r^(1 + alpha) (a = pow_ref.pow_allowance_u(1 + alpha) u
+    per weight, and so on the sum and on its max: 2 a; a = 3 for 1.25 -- root4_pos' 2 u and one product --, 4.5 for 1.75:
+    two square roots and three products), fl(1 / max) 1, sum * w 1, alpha * (...) 1, k * w 1, the final add 1, the
+    reference's sum P and T 2: c = 6 + 2 a = 12 for alpha = 0.25 and 15 for alpha = 0.75; alpha = 0 has exact weights
+    and max: c = 6.  The sum itself: (k - 1) roundings in fp64 -- or, where
     the scatter kernel's predicate (restated on the host) allows fixed point for these bounded weights, 2^-40 of P, the
     grid's guarantee (then the k term is replaced).  The medians step adds the bound of _normalized_ref"""
     from oracle import plaid_oracle as po
@@ -372,7 +373,8 @@ def test_replaid_ssgsea_within_the_bound_of_exact_rank_sums(hip_ctx, sparse, alp
     T = (w.astype(ld) * (P / wmax - ld(0.5) * kk.astype(ld))).astype(np.float64)
     Pf = P.astype(np.float64)
     mag = w * (Pf / float(wmax) + 0.5 * kk)
-    c = 12 if alpha else 6
+    c = 6 + 2 * pow_allowance_u(np.float64(1.0) + np.float64(alpha))      # (an exponent of 1: no allowance)
+    assert c == {0.0: 6, 0.25: 12, 0.75: 15}[alpha]
     E = (k + c) * er.U * mag
     if sparse:
         Wx = np.concatenate([W.astype(np.float64)[X.indices[X.indptr[j]:X.indptr[j + 1]], j] for j in range(X.shape[1])])
@@ -383,6 +385,18 @@ def test_replaid_ssgsea_within_the_bound_of_exact_rank_sums(hip_ctx, sparse, alp
     assert abs(T.min()) > 10 * E.max()                         # ignore.zero auto resolves as on the device (min(S) != 0)
     er.assert_within(got, N, B, f"ssgsea alpha={alpha} sparse={sparse}")
     assert B.max() < 1e-11 * np.abs(N).max()                   # (the bound stays far below the 1e-5 bar)
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+@pytest.mark.parametrize("alpha", [0.0, 0.25])
+def test_replaid_ssgsea_within_the_bound_of_exact_rank_sums(hip_ctx, sparse, alpha):
+    _ssgsea_within_the_bound(hip_ctx, sparse, alpha)
+
+
+def test_replaid_ssgsea_alpha_075_within_the_bound_of_its_larger_allowance(hip_ctx):
+    """alpha = 0.75: the exponent 1.75 is pow_quarters' q = 7, whose weights exceed 3 u (3.90 u over the domain, by IEEE
+    operations alone): held at the c = 15 that its derived 4.5 u gives"""
+    _ssgsea_within_the_bound(hip_ctx, False, 0.75)
 
 
 @pytest.mark.parametrize("sparse", [False, True])

@@ -63,6 +63,20 @@ def test_gsva_dense_z_within_the_bound(hip_ctx, name, tau):
     _declared_rows(S, Gp, ties)
 
 
+def test_gsva_dense_z_tau_075_within_the_bound_of_its_larger_allowance(hip_ctx):
+    """tau = 0.75: the exponent 1.75 is pow_quarters' q = 7, whose weights exceed 3 u by IEEE operations alone (3.90 u over
+    every rank, tests/test_pow_ref.py): held at the c = 5 + 2 * 4.5 that pow_ref.pow_allowance_u(1.75) gives, at the
+    12,289-row size class"""
+    from tests.helpers.pow_ref import pow_allowance_u
+    assert pow_allowance_u(1.75) == 4.5
+    name, tau = "g12289", 0.75
+    assert _ambiguous("dense", name) == 0
+    X, Gp, Gi, ties = gc.dense_case(name)
+    S = hip_ctx.gsva(X, Gp, Gi, tau, "z")
+    _within(S, "dense", name, tau, "z", "dense z")
+    _declared_rows(S, Gp, ties)
+
+
 @pytest.mark.parametrize("tau", gc.TAUS)
 @pytest.mark.parametrize("name", list(gc.CSC))
 def test_gsva_csc_z_within_the_bound_and_so_is_the_dense_entry(hip_ctx, name, tau):
