@@ -82,8 +82,17 @@ int plaidhip_finalize(plaidhip_ctx* ctx);
 int plaidhip_synchronize(plaidhip_ctx* ctx);
 /* Precision of the dense crossprod.  PLAIDHIP_PRECISION_F64 (default): fp64 storage and accumulation,
  * scores agree with the reference to ~1e-15.  PLAIDHIP_PRECISION_MIXED (opt-in): the sample columns are
- * staged as fp32 (2^-24 relative rounding of the inputs, ~6e-8 on the scores, inside the 1e-5 bar),
- * sums stay fp64; applies to dense X with 8,192 < genes <= 20,448, everything else keeps fp64.        */
+ * staged as fp32 (2^-24 relative rounding of the inputs, ~6e-8 on the scores, inside the 1e-5 bar).
+ * The sums are NOT fp64 throughout: the eight values a lane gathers per chunk are added as two four-term
+ * fp32 partial sums, (v0 + v1) + (v2 + v3), and only those partials are accumulated in fp64.  For a set
+ * of k genes with mag = sum |x| every raw sum is within
+ *   3 * 2^-24 * (1 + 2^-22) * mag  +  (k + c) * 2^-53 * mag  +  k * 2^-149
+ * of the exact sum (cast 2^-24, four-term fp32 sum 2 * 2^-24, the fp64 accumulation and the c roundings
+ * of the epilogue, values below the fp32 normal range); tests/helpers/compact_ref.py derives it and
+ * tests/test_gpu_compact_staging.py holds the kernel to it, cancelling data included.  The cast is the
+ * IEEE one: NaN and +-Inf propagate to exactly the scores of their sets (flag words as in fp64), a
+ * finite |x| >= 2^128 (1e39) becomes +-Inf in its sets, and |x| <= 2^-150 (1e-46) contributes 0.
+ * Applies to dense X with 8,192 < genes <= 20,448, everything else keeps fp64.                        */
 enum { PLAIDHIP_PRECISION_F64 = 0, PLAIDHIP_PRECISION_MIXED = 1 };
 int plaidhip_set_precision(plaidhip_ctx* ctx, int mode);
 /* Enqueue on `stream` (a hipStream_t) from now on; NULL means the device's null stream, e.g. the
@@ -163,9 +172,9 @@ int plaidhip_dev_spmm_dense_f64(plaidhip_ctx* ctx, const plaidhip_geneset* gs, c
  * is staged as u16 (four sample columns per 8-byte LDS entry) and summed in integers: exact, order-independent and
  * bit-identical to plaidhip_dev_spmm_dense_f64 on the same input, at a quarter of its LDS bytes per score.  The launch is
  * speculative: a value that is not such a rank (NaN -- matrixStats::colRanks keeps NA --, +-Inf, a negative value, a double
- * >= 32,768) is seen while staging, and the fp64 kernel enqueued right behind it on the same stream then recomputes the
- * scores (it returns at once otherwise), so the result is plaidhip_dev_spmm_dense_f64's for ANY input, NaN propagation
- * included.  Shapes the u16 kernel does not take (nrow(X) <= 8,192 or > 20,448) run the general kernels.             */
+ * >= 32,768, a value that is not a multiple of 1/2) is seen while staging, in whichever column of whichever pass, and the
+ * fp64 kernel enqueued right behind it on the same stream then recomputes the scores (it returns at once otherwise), so
+ * the result is plaidhip_dev_spmm_dense_f64's for ANY input, NaN propagation included.  Shapes the u16 kernel does not take (nrow(X) <= 8,192 or > 20,448) run the general kernels.             */
 int plaidhip_dev_spmm_ranks_f64(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const void* R,
                                 int64_t ldr, int32_t n, int stat, double alpha, const void* alpha_div,
                                 double beta, void* S, int64_t lds, void* flags);

@@ -175,6 +175,11 @@ SIGNATURES = {
     "plaidhip_gmtmat_destroy": [_vp],
 }
 
+# test hooks the library exports without declaring them in include/plaidhip.h (kept out of SIGNATURES, which mirrors it)
+DEBUG_SIGNATURES = {
+    "plaidhip_debug_spec_fell_back": [_vp, C.POINTER(_int)],
+}
+
 # return types other than the int status code
 RESTYPES = {
     "plaidhip_last_error_string": C.c_char_p,
@@ -212,6 +217,10 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = RESTYPES.get(name, _int)
+    for name, argtypes in DEBUG_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = _int
     _lib = lib
     return lib
 

@@ -460,6 +460,22 @@ int plaidhip_dev_spmm_ranks_f64(plaidhip_ctx* ctx, const plaidhip_geneset* gs, c
                                static_cast<uint32_t*>(flags), PLAIDHIP_X_RANKS);
 } catch (...) { return plaidhip::on_exception(); }
 
+// Test hook (not part of include/plaidhip.h), read-only: did the last speculative launch of this context (the u16 quad
+// kernel of plaidhip_dev_spmm_ranks_f64 and of the rank-valued scorers) meet a value that is not a rank, so that the fp64
+// kernel enqueued behind it recomputed the scores?  *out = 1 if so, 0 if the u16 scores stand (or no speculative launch
+// has run).  Waits for the context's stream, then compares the generation word the kernel leaves with the host's.
+int plaidhip_debug_spec_fell_back(plaidhip_ctx* ctx, int* out) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(out != nullptr, "debug_spec_fell_back: null out");
+  *out = 0;
+  if (ctx->d_spec == nullptr || ctx->spec_gen == 0u) return PLAIDHIP_OK;
+  uint32_t seen = 0;
+  PH_HIP(hipMemcpyAsync(&seen, ctx->d_spec, sizeof(seen), hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  *out = seen == ctx->spec_gen ? 1 : 0;
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_dev_spmm_csc_f64(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const void* Xp,
                               const void* Xi, const void* Xx, int32_t n, int64_t nnz, int stat, double alpha,
                               const void* alpha_div, double beta, void* S, int64_t lds, void* flags) try {

@@ -1644,9 +1644,12 @@ int launch_spmm_scatter_csc_f64(plaidhip_ctx* ctx, const plaidhip_geneset* gs, c
 // whole 20k-gene pair fits the LDS (no gene slices, no partial sums) and one ds_read_b64 serves two
 // scores -- a quarter of the LDS bytes per score of the fp64 one-column kernel.  The eight values a
 // lane gathers per chunk are summed with packed fp32 adds (four terms per partial sum) and the
-// chunk's partials are added to fp64 accumulators, so the only precision given up is the rounding of
-// the inputs to fp32 (2^-24 relative per value, ~6e-8 on the scores; the fp64 kernels stay the
-// default and the parity reference).  Same host schedule as the one-column kernel (32-lane halves
+// chunk's partials are added to fp64 accumulators, so the precision given up is the rounding of
+// the inputs to fp32 (2^-24 relative per value) and the two roundings of a four-term fp32 partial sum
+// (2 * 2^-24 of its terms): within 3 * 2^-24 * (1 + 2^-22) * sum |x| + the fp64 bound of the exact sum
+// (tests/helpers/compact_ref.py::mixed_bound, held in tests/test_gpu_compact_staging.py), ~6e-8 on
+// well-conditioned scores; the fp64 kernels stay the default and the parity reference.  Rank inputs
+// ((half-)integers <= 32,767.5) lose nothing: cast and partials are exact.  Same host schedule as the one-column kernel (32-lane halves
 // of ds_read_b64 against 32 bank pairs), same per-wave tile streams and epilogue.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

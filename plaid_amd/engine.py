@@ -543,7 +543,8 @@ class Context:
 
     def set_precision(self, mode: str):
         """"f64" (default): fp64 throughout.  "mixed": the dense crossprod stages the sample columns as fp32
-        (inputs rounded to 2^-24 relative, sums fp64) -- about 2x the SpMM rate, scores within ~1e-7."""
+        (inputs rounded to 2^-24 relative, four-term fp32 partial sums accumulated in fp64: 3 * 2^-24 of sum |x| plus the
+        fp64 bound, include/plaidhip.h) -- about 2x the SpMM rate, scores within ~1e-7."""
         check(self.lib.plaidhip_set_precision(self.handle, {"f64": 0, "mixed": 1}[mode]))
 
     def geneset(self, g: int, Gp, Gi) -> Geneset:
@@ -570,6 +571,13 @@ class Context:
         sums -- bit-identical to dev_spmm_dense on the same input"""
         check(self.lib.plaidhip_dev_spmm_ranks_f64(self.handle, gs.handle, R, ldr, n, STAT[stat], alpha,
                                                    alpha_div, beta, S, lds, flags))
+
+    def debug_spec_fell_back(self) -> bool:
+        """test hook (plaidhip_debug_spec_fell_back, read-only; waits for the stream): True when the last speculative
+        u16 launch of this context met a value that is not a rank and the fp64 kernel behind it recomputed the scores"""
+        out = C.c_int(0)
+        check(self.lib.plaidhip_debug_spec_fell_back(self.handle, C.byref(out)))
+        return bool(out.value)
 
     def dev_spmm_csc(self, gs: Geneset, Xp: int, Xi: int, Xx: int, n: int, S: int, lds: int,
                      stat="mean", alpha=1.0, beta=0.0, flags: int | None = None,
