@@ -1002,6 +1002,63 @@ int plaidhip_fisher_multi(const int* devices, int ndev, const int8_t* sig, int32
                           const int32_t* Gi, int32_t m, double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx);
 int plaidhip_hyper_tail(int64_t N, int64_t K, int64_t k, int64_t x, double* p);
 
+/* plaid.rankcor(stat, G): the Pearson correlation of a per-gene statistic, or of its ranks, with the 0/1 membership column
+ * of every set -- the reference's gset.rankcor(fc, matG, compute.p = TRUE[, use.rank = FALSE]) (experiments/R/functions.R:
+ * 183-237), one list (contrast, or sample) per column, with per-list missing values.
+ * Operands: stat is g x c doubles, column-major; a NaN means "gene i takes no part in list l" (R's NA, na.last = "keep").
+ * Per list: V = the rows that are not NaN, n = |V|.  Per set j: k = the number of its members (rows of Gi) in V.
+ * RANK MODE (use_rank = 1).  r_i = the rank of stat[i] among V, ascending, +-Inf ordinary values, -0 == +0; ties is
+ * PLAIDHIP_TIES_AVERAGE, _MIN or _MAX (the dense rank kernel's values, NaN kept).  The reference ranks with ties.method =
+ * "random", which is no function of the input: the callers' default here is "average"; lists without ties are the same
+ * under every method.  z_i = 2 r_i is an integer in 2 .. 2 n, and everything before the epilogue is exact integers:
+ *     A = sum of z_i over the members in V;  T1 = sum of z_i over V;  T2 = sum of z_i^2 over V        (T2 <= 2^53)
+ *     num = n A - k T1                               (|num| < 2^53: int64)
+ *     P   = k (n - k) (n T2 - T1^2)                  (< 2^102: unsigned 128-bit)
+ *     Q   = P - num^2                                (>= 0 by Cauchy-Schwarz; 128-bit)
+ * The epilogue runs on the host in fp64; a 128-bit integer becomes a double by ONE rounding to nearest, ties to even:
+ *     P == 0 (k = 0, k = n, an all-tied list, n <= 1): rho = t = p = NaN
+ *     Q == 0: rho = +-1.0 (the sign of num), t = +-Inf, p = 0.0;  otherwise
+ *     rho = (double)num / sqrt((double)P)
+ *     tsq = ((double)(n - 2) * (double)(num^2)) / (double)Q;   t = copysign(sqrt(tsq), num);   p = 2.0 * pnorm_upper(|t|)
+ *     n <= 2: t = p = NaN, whatever Q is.
+ * pnorm_upper(x) = 0.5 * erfc(x / sqrt(2.0)), the routine behind every normal tail of this library.  rho lies within
+ * 3 * 2^-53 of the exact value, relatively, and t within 4 * 2^-53 (DESIGN.md section 21 derives 2.5 and 3).
+ * VALUE MODE (use_rank = 0).  A list whose V holds an infinity, or whose values over V are all equal (max == min), gives NaN
+ * in rho, t, p and q.  mu = (the sum of stat over V) / (double)n, d_i = stat[i] - mu (one rounding each), and
+ *     A = sum of d_i over the members in V;  T1 = sum of d_i over V;  T2 = sum of d_i * d_i over V
+ *     num = A - ((double)k * T1) / (double)n
+ *     den = sqrt((((double)k * (double)(n - k)) / (double)n) * (T2 - (T1 * T1) / (double)n))
+ *     rho = num / den            (den == 0 or not finite, k = 0, k = n: NaN)
+ *     w   = (1.0 - rho) * (1.0 + rho);   w <= 0: t = copysign(Inf, rho), p = 0.0;   otherwise
+ *     t   = rho * sqrt((double)(n - 2) / w);   p = 2.0 * pnorm_upper(|t|);   n <= 2: t = p = NaN
+ * This is the correlation for ANY shift mu (the centred two-pass form; never sum x^2 - n mu^2).  No product is contracted.
+ * The order of every fp64 sum is fixed by the launch geometry alone, never by the sharding or the number of lists:
+ *   over V (the sum for mu, then T1 and T2): thread h of 256 adds rows h, h + 256, ... in ascending order from 0.0 (a row
+ *   outside V is skipped), and the 256 partials are added pairwise, partial[h] += partial[h + s] for s = 128, 64, ..., 1;
+ *   over a set: lane h of 64 adds the members in V at positions h, h + 64, ... of the set's segment of Gi in ascending order
+ *   from 0.0, and the lanes are added by the butterfly v += (v of lane h xor s) for s = 32, 16, 8, 4, 2, 1.
+ * q.value is Benjamini-Hochberg per list over the sets with a non-NaN p (the host routine behind every padj here).
+ * out: m x 5 x c doubles, column-major: size (k), rho, t, p.value, q.value.  tot_out: c doubles, n of every list.
+ * Argument errors, in this order, all found on the host before any device is touched: c < 1; bad dims or a null Gp; null
+ * stat or tot_out (or out, with m > 0); use_rank not 0 / 1 or ties not one of the three; g > PLAIDHIP_RANKCOR_MAX_GENES
+ * (PLAIDHIP_EUNSUPPORTED); Gp not starting at 0 or decreasing, a set of more than g members, a null Gi, or a Gi row outside
+ * 0..g-1.  m = 0 returns PLAIDHIP_OK with nothing written.
+ * plaidhip_rankcor_multi shares the lists out over the devices (plaidhip_shard_bounds over c); a device takes its columns of
+ * stat and all of G.  A list's results depend on that list alone, so every sharding, ndev > c included, returns the
+ * one-device bits of out and tot_out.
+ * plaidhip_rankcor_finish (host only, no device): the rank-mode epilogue and Benjamini-Hochberg on integer operands: n, T1,
+ * T2: c each; k, A: m x c, list-major (set j of list l at l m + j); out as above.  Operands outside the ranges above
+ * (n < 0, k outside 0..n, n > PLAIDHIP_RANKCOR_MAX_GENES, T1 < 0, T2 < 0, P < num^2) are PLAIDHIP_EINVAL.
+ * Not offered: a dgCMatrix stat; ties = "random"; the reference's cor_sparse_matrix for a non-binary gset. */
+#define PLAIDHIP_RANKCOR_MAX_GENES 131072
+#define PLAIDHIP_RANKCOR_LIST_TILE 8
+int plaidhip_rankcor(plaidhip_ctx* ctx, const double* stat, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                     int use_rank, int ties, double* out, double* tot_out);
+int plaidhip_rankcor_multi(const int* devices, int ndev, const double* stat, int32_t g, int32_t c, const int32_t* Gp,
+                           const int32_t* Gi, int32_t m, int use_rank, int ties, double* out, double* tot_out);
+int plaidhip_rankcor_finish(int32_t m, int32_t c, const int64_t* n, const int64_t* T1, const int64_t* T2, const int64_t* k,
+                            const int64_t* A, double* out);
+
 /* plaid.limma(A, design, contrasts): limma's moderated t-test -- lmFit + eBayes + topTable -- of every row of A (the
  * single-sample scores of the sets, or the expression of the genes) for one or several designs.  The form is limma's AS
  * RECALLED: its source is not in this tree, so the statistic is pinned here and tested against these words in 50-digit

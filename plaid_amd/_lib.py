@@ -150,6 +150,9 @@ SIGNATURES = {
     "plaidhip_fisher": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_fisher_multi": [_vp, _int, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_hyper_tail": [_i64, _i64, _i64, _i64, _vp],
+    "plaidhip_rankcor": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, _vp],
+    "plaidhip_rankcor_multi": [_vp, _int, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, _vp],
+    "plaidhip_rankcor_finish": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "plaidhip_limma": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "plaidhip_limma_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "plaidhip_dev_row_design_effects": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],

@@ -729,6 +729,63 @@ def plaid_fisher(sig, G, minSize=1, maxSize=None, sort_by="pAny", overlap=False,
     return res[sig.colnames[0]] if single and len(res) == 1 else res
 
 
+_RANKCOR_NAMES = ["size", "rho", "t", "p.value", "q.value"]
+
+
+def plaid_rankcor(stat, G, use_rank=True, compute_p=True, ties="average", minSize=1, maxSize=None, sort_by="p.value",
+                  ctx: Context | None = None):
+    """plaid.rankcor(): the reference's gset.rankcor(fc, matG, compute.p = TRUE) -- the Pearson correlation of the ranks of a
+    per-gene statistic (use_rank = False: of the statistic itself) with the 0/1 membership of every set of G (a gmt or a
+    membership matrix), as pinned in include/plaidhip.h -- for a named vector (a dict or a pandas Series, gene ->
+    statistic) or every column of a genes x lists NamedMatrix (contrasts, or samples).  A NaN leaves the gene out of that
+    list alone: the ranks, the universe and the sets' sizes are taken over the list's own genes.  Genes are aligned by name
+    as plaid.gsea aligns them.  ties: "average" (default), "min" or "max"; the reference's "random" is no function of the
+    input and is not offered (lists without ties are the same under all of them).  Sets with fewer than minSize or more than
+    maxSize (default: the aligned genes - 1) aligned members are dropped.  Returns one NamedMatrix (sets x [size, rho, t,
+    p.value, q.value]; [size, rho] with compute_p = False) ordered by `sort_by` (stable, NaN last; |rho| decreasing for
+    "rho") when stat is a named vector; for a NamedMatrix, of one column or of many, a dict, column name -> NamedMatrix, in
+    the columns' order.  p.value is the normal tail of the t-transform of rho, q.value Benjamini-Hochberg per list."""
+    from .engine import rankcor_ties
+    rankcor_ties(ties)   # (an unknown method is refused before anything else)
+    if isinstance(stat, dict):
+        stat = NamedMatrix(np.array(list(stat.values()), dtype=np.float64), list(stat.keys()), ["stat"])
+        single = True
+    else:
+        single = not isinstance(stat, NamedMatrix) and np.ndim(stat) == 1
+        try:
+            import pandas as pd
+            if isinstance(stat, pd.Series):
+                stat, single = NamedMatrix(stat.to_numpy(dtype=np.float64), list(stat.index), ["stat"]), True
+        except ImportError:  # pragma: no cover
+            pass
+    if isinstance(G, (GmtList, dict)) or (isinstance(G, tuple) and len(G) == 2):
+        _message("[plaid.rankcor] converting gmt to sparse matrix...")
+        G = gmt2mat(G)
+    stat = as_named(stat)
+    if sp.issparse(stat.values):
+        raise ValueError("plaid.rankcor: stat must be dense")
+    Xs, Gp, Gi, _, _, _, _, rn = _plaid_test_operands(stat, G, None, "one", "fisher")
+    N = Xs.shape[0]
+    sizes = np.diff(Gp)
+    hi = N - 1 if maxSize is None else int(maxSize)
+    keep = np.flatnonzero((sizes >= int(minSize)) & (sizes <= hi))
+    Gi = np.concatenate([Gi[Gp[j]:Gp[j + 1]] for j in keep]).astype(np.int32) if len(keep) else np.zeros(0, np.int32)
+    Gp = np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int32)
+    rn = [rn[j] for j in keep]
+    ctx = ctx or default_context()
+    out, _ = ctx.rankcor(Xs, Gp, Gi, use_rank=use_rank, ties=ties)
+    cols = _RANKCOR_NAMES if compute_p else _RANKCOR_NAMES[:2]
+    res = {}
+    for l, nm in enumerate(stat.colnames):
+        tab, names = out[:, :len(cols), l], list(rn)
+        if sort_by in cols:
+            key = tab[:, cols.index(sort_by)]
+            o = np.argsort(-np.abs(key) if sort_by == "rho" else key, kind="stable")       # order(): NaN last
+            tab, names = tab[o, :], [names[k] for k in o]
+        res[nm] = NamedMatrix(tab, names, list(cols))
+    return res[stat.colnames[0]] if single and len(res) == 1 else res
+
+
 _LIMMA_NAMES = ["logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2"]
 _LIMMA_HYPER = ["df.residual", "df.prior", "s2.prior", "n.ok"]
 _LIMMA_SORT = {"none": None, "P.Value": (3, 1), "P": (3, 1), "p": (3, 1), "t": (2, -1), "logFC": (0, -1), "AveExpr": (1, -1)}

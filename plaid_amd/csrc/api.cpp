@@ -1208,6 +1208,12 @@ int plaidhip_gsea_scored(plaidhip_ctx* ctx, const double* stat, const double* we
                   gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.rankcor: the one-device form of the sharded engine (multi.cpp: rankcor_worker, kRankcor)
+int plaidhip_rankcor(plaidhip_ctx* ctx, const double* stat, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                     int use_rank, int ties, double* out, double* tot_out) try {
+  return dispatch(on_context(ctx), rankcor_call(stat, g, c, Gp, Gi, m, use_rank, ties, out, tot_out));
+} catch (...) { return plaidhip::on_exception(); }
+
 // plaid.fisher: the one-device form of the sharded engine (multi.cpp: fisher_worker, kFisher)
 int plaidhip_fisher(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
                     double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx) try {

@@ -12,7 +12,7 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16
+  kLimma = 16, kRankcor = 17
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -83,6 +83,9 @@ struct Call : Operands {
   // lists in le_len / le_idx (both null: none)
   const int8_t* sig = nullptr;
   double* tot_out = nullptr;
+  // plaid.rankcor: X is stat (g x n, n = the lists, dense; NaN: the gene takes no part in the list), out m x 5 x n, tot_out
+  // the n universe sizes; ranks (with their ties) or values
+  int use_rank = 1, ties = PLAIDHIP_TIES_AVERAGE;
   // plaid.limma: X is A (g rows x n samples; no sets: Gp stays null, m = 0), the nfit designs (n x p each), use (n x nfit,
   // null: all), K (p x q, null: the unit vectors), out g x 6 x q x nfit and hyper nfit x 4; what check_call makes of the
   // designs: Q (n x p x nfit), 1 / n_f, n_f, v (p x q x nfit) and u (q x nfit)
@@ -272,6 +275,17 @@ inline Call fisher_call(const int8_t* sig, int32_t g, int32_t c, const int32_t* 
   k.tot_out = tot_out;
   k.le_len = ov_len;
   k.le_idx = ov_idx;
+  return k;
+}
+
+// correlation of statistics or ranks with every set as pinned in include/plaidhip.h: plaidhip_rankcor
+inline Call rankcor_call(const double* stat, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, int use_rank,
+                         int ties, double* out, double* tot_out) {
+  Call k = make_call(kRankcor, {nullptr, nullptr, stat, g, c, Gp, Gi, m}, nullptr);
+  k.use_rank = use_rank;
+  k.ties = ties;
+  k.out = out;
+  k.tot_out = tot_out;
   return k;
 }
 

@@ -633,6 +633,22 @@ int launch_fisher_tail(plaidhip_ctx* ctx, const int32_t* tot, const int32_t* ov,
 // the overlap lists: len (c x m), idx (c x Gp[m]; the segment of (j, l) at l Gp[m] + Gp[j], -1 past the overlap)
 int launch_fisher_overlap(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi,
                           int32_t m, int32_t* len, int32_t* idx);
+// kernels_rankcor.hip: plaid.rankcor (include/plaidhip.h: plaidhip_rankcor).  All stream-ordered, all pointers device pointers.
+// value mode: D (g x c, leading dimension g) <- stat - mu with NaN kept, vs ([c][4]) <- {n, T1, T2, flag (1: the list holds
+// an infinity, 2: its values are all equal)}
+int launch_rankcor_center(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t c, double* D, double* vs);
+// tiles ([ceil(c / PLAIDHIP_RANKCOR_LIST_TILE)][g][8]: uint32 z = 2 rank, or doubles; 0 outside V) from R (g x c, leading
+// dimension g: the ranks or the centred values, NaN outside V).  use_rank: sums ([c][3] u64 = n, T1, T2; zeroed here), vmask
+// unused; else vmask ([ntile][g] bytes, bit t: in V of list tile * 8 + t), sums unused
+int launch_rankcor_pack(plaidhip_ctx* ctx, int use_rank, const double* R, int32_t g, int32_t c, void* tiles, uint8_t* vmask,
+                        unsigned long long* sums);
+// kout ([c][m] int32: the members in V) and Aout ([c][m] int64 or double: their sum) of every (list, set); every Gi is in
+// 0..g-1 and no set has more than g members (checked on the host)
+int launch_rankcor_gather(plaidhip_ctx* ctx, int use_rank, const void* tiles, const uint8_t* vmask, int32_t g, int32_t c,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, int32_t* kout, void* Aout);
+// stats.cpp: the pinned epilogues of one (list, set), host only: o[0 .. 2] <- rho, t, p
+void rankcor_rank_epilogue(int64_t n, int64_t T1, int64_t T2, int64_t k, int64_t A, double* o);
+void rankcor_value_epilogue(int64_t n, double T1, double T2, int flag, int64_t k, double A, double* o);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 // kernels_medians.hip

@@ -1978,6 +1978,90 @@ int fisher_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
   return s.finish();
 }
 
+constexpr int kRankcorThreads = 8;            // host threads of one shard's epilogues and Benjamini-Hochberg columns, at most
+constexpr int64_t kRankcorWork = 1 << 16;     // (list, set) pairs per thread below which another thread is not worth its start
+// one device's part of plaid.rankcor (kRankcor, kernels_rankcor.hip).  The lists are shared out (plaidhip_shard_bounds over
+// c): a shard takes its columns of stat and all of G.  A list's ranks, sums and gathers depend on that list alone (the
+// integer ones are exact, the fp64 ones run in an order the launch geometry fixes per list and per set), so every sharding
+// has the one-shard bits.  The epilogue and Benjamini-Hochberg of the shard's lists run on the host.  No rendezvous.
+int rankcor_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t g = c.g, m = c.m, l0 = s.lo, nl = s.nloc;
+  DevBuf dX, dR, dtile, dmask, dsum, dk, dA, dGp, dGi;
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (nl <= 0) return PLAIDHIP_OK;
+    PH_HIP(hipSetDevice(ctx->device));
+    const int use_rank = c.use_rank;
+    const int32_t ntile = (nl + PLAIDHIP_RANKCOR_LIST_TILE - 1) / PLAIDHIP_RANKCOR_LIST_TILE;
+    const size_t cell = use_rank ? 4 : 8;
+    PH_TRY(dX.alloc((size_t)g * nl * 8));
+    PH_TRY(dR.alloc((size_t)g * nl * 8));
+    PH_TRY(dtile.alloc((size_t)ntile * g * PLAIDHIP_RANKCOR_LIST_TILE * cell));
+    if (!use_rank) PH_TRY(dmask.alloc((size_t)ntile * g));
+    PH_TRY(dsum.alloc((size_t)nl * 4 * 8));   // ranks: [nl][3] u64; values: [nl][4] doubles
+    PH_TRY(dk.alloc((size_t)nl * m * 4));
+    PH_TRY(dA.alloc((size_t)nl * m * 8));
+    PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
+    PH_TRY(upload_pipelined(ctx, dX.as<char>(), (size_t)g * 8, reinterpret_cast<const char*>(c.X + (size_t)l0 * g), (size_t)g * 8,
+                            nl, nullptr));
+    if (use_rank)
+      PH_TRY(launch_colranks_dense_f64(ctx, dX.as<double>(), g, g, nl, c.ties, 0, 1.0, dR.as<double>(), g, nullptr));
+    else
+      PH_TRY(launch_rankcor_center(ctx, dX.as<double>(), g, nl, dR.as<double>(), dsum.as<double>()));
+    PH_TRY(launch_rankcor_pack(ctx, use_rank, dR.as<double>(), g, nl, dtile.p, dmask.as<uint8_t>(),
+                               dsum.as<unsigned long long>()));
+    PH_TRY(launch_rankcor_gather(ctx, use_rank, dtile.p, dmask.as<uint8_t>(), g, nl, dGp.as<int32_t>(), dGi.as<int32_t>(), m,
+                                 dk.as<int32_t>(), dA.p));
+    std::vector<int32_t> hk((size_t)nl * m);
+    std::vector<int64_t> hA((size_t)nl * m), hsum((size_t)nl * 4);   // (hA, hsum: int64 or the bits of doubles)
+    PH_HIP(hipMemcpyAsync(hk.data(), dk.p, hk.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(hA.data(), dA.p, hA.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(hsum.data(), dsum.p, (size_t)nl * (use_rank ? 3 : 4) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    auto as_double = [](int64_t bits) { double d; std::memcpy(&d, &bits, 8); return d; };
+    // the epilogue and Benjamini-Hochberg of every list: nl independent columns of m tails and one sort of m values, which
+    // outweigh the kernels from a few lists on -- dealt to host threads when there is enough of them (a list is the same
+    // routine whichever thread runs it)
+    auto finish_lists = [&](int64_t q0, int64_t step) {
+      for (int64_t l = q0; l < nl; l += step) {
+        double* o = c.out + (size_t)(l0 + l) * 5 * m;
+        const int64_t n = use_rank ? hsum[3 * (size_t)l] : (int64_t)as_double(hsum[4 * (size_t)l]);
+        c.tot_out[(size_t)(l0 + l)] = (double)n;
+        for (int32_t j = 0; j < m; ++j) {
+          const size_t e = (size_t)l * m + j;
+          double r[3];
+          if (use_rank)
+            rankcor_rank_epilogue(n, hsum[3 * (size_t)l + 1], hsum[3 * (size_t)l + 2], hk[e], hA[e], r);
+          else
+            rankcor_value_epilogue(n, as_double(hsum[4 * (size_t)l + 1]), as_double(hsum[4 * (size_t)l + 2]),
+                                   (int)as_double(hsum[4 * (size_t)l + 3]), hk[e], as_double(hA[e]), r);
+          o[j] = (double)hk[e];
+          o[(size_t)m + j] = r[0];
+          o[2 * (size_t)m + j] = r[1];
+          o[3 * (size_t)m + j] = r[2];
+        }
+        p_adjust_fdr(o + 3 * (size_t)m, m, o + 4 * (size_t)m);
+      }
+    };
+    const int64_t nth = std::min<int64_t>({(int64_t)kRankcorThreads, (int64_t)nl * m / kRankcorWork, (int64_t)nl});
+    if (nth <= 1) {
+      finish_lists(0, 1);
+    } else {
+      std::vector<std::thread> th;
+      std::atomic<int> failed{0};
+      for (int64_t t = 0; t < nth; ++t)
+        th.emplace_back([&, t] {
+          try { finish_lists(t, nth); } catch (...) { failed.store(1); }
+        });
+      for (auto& t : th) t.join();
+      if (failed.load() != 0) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+    }
+    return PLAIDHIP_OK;
+  });
+  return s.finish();
+}
+
 // chain_contrast_sums for any [nblk][len] partials of the shard's columns (launch_reduce_blocks_flat): shard r adds its blocks,
 // in order, to what the shards before it left in `run`; d_seed, d_run: len doubles each.  ndev rendezvous.
 void chain_flat_sums(Shard& s, std::vector<double>& run, const double* ws, int64_t len, double* d_seed, double* d_run) {
@@ -2096,6 +2180,7 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   auto worker = [&](int k) {
     if (c.method == kGsea) return gsea_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kFisher) return fisher_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kRankcor) return rankcor_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kLimma) return limma_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
@@ -2453,6 +2538,31 @@ int check_fisher_call(const Call& c) {
   return PLAIDHIP_OK;
 }
 
+// plaid.rankcor; the order is part of the contract (include/plaidhip.h)
+int check_rankcor_call(const Call& c) {
+  PH_REQUIRE(c.n >= 1, "rankcor: %d lists (at least 1)", c.n);
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  PH_REQUIRE(c.X != nullptr && c.tot_out != nullptr && (c.out != nullptr || c.m == 0), "rankcor: null stat / out / tot_out");
+  PH_REQUIRE(c.use_rank == 0 || c.use_rank == 1, "rankcor: use_rank = %d (0 values, 1 ranks)", c.use_rank);
+  PH_REQUIRE(c.ties == PLAIDHIP_TIES_AVERAGE || c.ties == PLAIDHIP_TIES_MIN || c.ties == PLAIDHIP_TIES_MAX,
+             "rankcor: ties = %d (0 average, 1 min, 2 max)", c.ties);
+  if (c.g > PLAIDHIP_RANKCOR_MAX_GENES) {
+    set_error("rankcor: %d genes (at most %d)", c.g, PLAIDHIP_RANKCOR_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
+  PH_REQUIRE(c.Gp[0] == 0, "rankcor: Gp[0] = %d (a column pointer starts at 0)", c.Gp[0]);
+  for (int32_t j = 0; j < c.m; ++j) {
+    PH_REQUIRE(c.Gp[j + 1] >= c.Gp[j], "rankcor: Gp[%d] = %d after %d (a column pointer does not decrease)", j + 1, c.Gp[j + 1],
+               c.Gp[j]);
+    PH_REQUIRE(c.Gp[j + 1] - c.Gp[j] <= c.g, "rankcor: set %d has %d members (at most the %d genes)", j + 1,
+               c.Gp[j + 1] - c.Gp[j], c.g);
+  }
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "rankcor: null Gi");
+  for (int32_t e = 0; e < c.Gp[c.m]; ++e)
+    PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "rankcor: Gi[%d] = %d (rows are 0..%d)", e, c.Gi[e], c.g - 1);
+  return PLAIDHIP_OK;
+}
+
 // plaid.limma; the order is part of the contract (include/plaidhip.h).  Makes every fit's Q, v, u and n_f: the designs are
 // decomposed here, on the host, so that a design that cannot be fitted is refused before any device is touched
 int check_limma_call(Call& c) {
@@ -2540,6 +2650,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kPlaidTestContrasts: return check_plaid_test_contrasts_call(c);
     case kGsea: return check_gsea_call(c);
     case kFisher: return check_fisher_call(c);
+    case kRankcor: return check_rankcor_call(c);
     case kLimma: return check_limma_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
@@ -2831,6 +2942,17 @@ int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fai
                                                 const int32_t* Gp, const int32_t* Gi, int32_t m, double* out, double* tot_out,
                                                 int32_t* ov_len, int32_t* ov_idx) try {
   return dispatch(on_hook(device, nshards, fail_shard), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_rankcor_multi(const int* devices, int ndev, const double* stat, int32_t g, int32_t c, const int32_t* Gp,
+                           const int32_t* Gi, int32_t m, int use_rank, int ties, double* out, double* tot_out) try {
+  return dispatch(on_devices(devices, ndev), rankcor_call(stat, g, c, Gp, Gi, m, use_rank, ties, out, tot_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_rankcor_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat, int32_t g,
+                                                 int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, int use_rank,
+                                                 int ties, double* out, double* tot_out) try {
+  return dispatch(on_hook(device, nshards, fail_shard), rankcor_call(stat, g, c, Gp, Gi, m, use_rank, ties, out, tot_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_gsea_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat, const double* weight,

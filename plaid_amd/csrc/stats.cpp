@@ -395,9 +395,111 @@ int limma_design(const char* what, const double* D, int32_t n, int32_t p, const 
   return PLAIDHIP_OK;
 }
 
+// ---- plaid.rankcor: the pinned epilogues (include/plaidhip.h: plaidhip_rankcor) -------------------------
+namespace {
+
+typedef unsigned __int128 u128;
+
+// an unsigned 128-bit integer to the nearest double, ties to even, in one rounding: the top 64 bits with the bits below
+// them folded into the last one (far below the 53 that are kept), converted by the hardware and scaled by a power of two
+double u128_to_double(u128 v) {
+  const uint64_t hi = (uint64_t)(v >> 64), lo = (uint64_t)v;
+  if (hi == 0) return (double)lo;
+  const int shift = 64 - __builtin_clzll(hi);   // 1 .. 64: the bits above 64
+  uint64_t top = (uint64_t)(v >> shift);
+  if ((v & ((((u128)1) << shift) - 1)) != 0) top |= 1ull;
+  return std::ldexp((double)top, shift);
+}
+
+}  // namespace
+
+void rankcor_rank_epilogue(int64_t n, int64_t T1, int64_t T2, int64_t k, int64_t A, double* o) {
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  o[0] = o[1] = o[2] = nan;
+  if (n <= 1 || k <= 0 || k >= n) return;
+  const int64_t num = n * A - k * T1;
+  const u128 D = (u128)(uint64_t)n * (u128)(uint64_t)T2 - (u128)(uint64_t)T1 * (u128)(uint64_t)T1;
+  const u128 P = (u128)((uint64_t)k * (uint64_t)(n - k)) * D;
+  if (P == 0) return;
+  const uint64_t an = (uint64_t)(num < 0 ? -num : num);
+  const u128 num2 = (u128)an * (u128)an;
+  const u128 Q = P - num2;
+  if (Q == 0) {
+    o[0] = num < 0 ? -1.0 : 1.0;
+    if (n > 2) { o[1] = num < 0 ? -inf : inf; o[2] = 0.0; }
+    return;
+  }
+  o[0] = (double)num / std::sqrt(u128_to_double(P));
+  if (n <= 2) return;
+  const double tsq = ((double)(n - 2) * u128_to_double(num2)) / u128_to_double(Q);
+  const double t = std::copysign(std::sqrt(tsq), (double)num);
+  o[1] = t;
+  o[2] = 2.0 * pnorm_upper(std::fabs(t));
+}
+
+void rankcor_value_epilogue(int64_t n, double T1, double T2, int flag, int64_t k, double A, double* o) {
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  o[0] = o[1] = o[2] = nan;
+  if (flag != 0 || n <= 1 || k <= 0 || k >= n) return;
+  const double nd = (double)n, kd = (double)k;
+  const double num = A - (kd * T1) / nd;
+  const double den = std::sqrt(((kd * (double)(n - k)) / nd) * (T2 - (T1 * T1) / nd));
+  if (!(den > 0.0) || !std::isfinite(den)) return;
+  const double rho = num / den;
+  o[0] = rho;
+  if (n <= 2 || rho != rho) return;
+  const double w = (1.0 - rho) * (1.0 + rho);
+  if (w <= 0.0) {
+    o[1] = std::copysign(inf, rho);
+    o[2] = 0.0;
+    return;
+  }
+  const double t = rho * std::sqrt((double)(n - 2) / w);
+  o[1] = t;
+  o[2] = 2.0 * pnorm_upper(std::fabs(t));
+}
+
 }  // namespace plaidhip
 
 extern "C" {
+
+int plaidhip_rankcor_finish(int32_t m, int32_t c, const int64_t* n, const int64_t* T1, const int64_t* T2, const int64_t* k,
+                            const int64_t* A, double* out) try {
+  using namespace plaidhip;
+  PH_REQUIRE(m >= 0 && c >= 0, "rankcor_finish: bad dims m=%d c=%d", m, c);
+  if (m == 0 || c == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(n && T1 && T2 && k && A && out, "rankcor_finish: null argument");
+  for (int32_t l = 0; l < c; ++l) {
+    PH_REQUIRE(n[l] >= 0 && n[l] <= PLAIDHIP_RANKCOR_MAX_GENES && T1[l] >= 0 && T2[l] >= 0 &&
+                   T1[l] <= 2 * n[l] * n[l] && T2[l] <= 4 * n[l] * n[l] * n[l],
+               "rankcor_finish: list %d: n = %lld, T1 = %lld, T2 = %lld", l + 1, (long long)n[l], (long long)T1[l],
+               (long long)T2[l]);
+    PH_REQUIRE((unsigned __int128)n[l] * (unsigned __int128)T2[l] >= (unsigned __int128)T1[l] * (unsigned __int128)T1[l],
+               "rankcor_finish: list %d: n T2 < T1^2", l + 1);
+    for (int32_t j = 0; j < m; ++j) {
+      const int64_t kk = k[(size_t)l * m + j], a = A[(size_t)l * m + j];
+      PH_REQUIRE(kk >= 0 && kk <= n[l] && a >= 0 && a <= T1[l], "rankcor_finish: list %d, set %d: k = %lld, A = %lld", l + 1, j + 1,
+                 (long long)kk, (long long)a);
+      const unsigned __int128 D = (unsigned __int128)n[l] * (unsigned __int128)T2[l] - (unsigned __int128)T1[l] * (unsigned __int128)T1[l];
+      const int64_t num = n[l] * a - kk * T1[l];
+      const unsigned __int128 an = (unsigned __int128)(num < 0 ? -num : num);
+      PH_REQUIRE((unsigned __int128)(kk * (n[l] - kk)) * D >= an * an, "rankcor_finish: list %d, set %d: P < num^2", l + 1, j + 1);
+    }
+  }
+  for (int32_t l = 0; l < c; ++l) {
+    double* o = out + (size_t)l * 5 * m;
+    for (int32_t j = 0; j < m; ++j) {
+      double r[3];
+      rankcor_rank_epilogue(n[l], T1[l], T2[l], k[(size_t)l * m + j], A[(size_t)l * m + j], r);
+      o[j] = (double)k[(size_t)l * m + j];
+      o[(size_t)m + j] = r[0];
+      o[2 * (size_t)m + j] = r[1];
+      o[3 * (size_t)m + j] = r[2];
+    }
+    p_adjust_fdr(o + 3 * (size_t)m, m, o + 4 * (size_t)m);
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_limma_design(const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q, int32_t fit,
                           double* Q, double* R, double* v, double* u, int64_t* nf) try {

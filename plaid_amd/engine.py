@@ -398,6 +398,62 @@ def hyper_tail(N, K, k, x) -> float:
     return p.value
 
 
+RANKCOR_MAX_GENES = 131072   # PLAIDHIP_RANKCOR_MAX_GENES
+RANKCOR_COLUMNS = ("size", "rho", "t", "p.value", "q.value")
+RANKCOR_TIES = {"average": 0, "min": 1, "max": 2}   # PLAIDHIP_TIES_AVERAGE / _MIN / _MAX
+
+
+def rankcor_ties(ties):
+    """the ABI's ordinal of a ties method name (an ordinal passes through, so a test reaches the library's own check);
+    "random", the reference's method, is no function of the input and is refused"""
+    if isinstance(ties, str):
+        if ties not in RANKCOR_TIES:
+            raise ValueError(f"rankcor: ties must be one of {sorted(RANKCOR_TIES)} (got {ties!r})")
+        return RANKCOR_TIES[ties]
+    return int(ties)
+
+
+def check_rankcor_args(stat, use_rank=True, ties="average"):
+    """the checks of plaidhip_rankcor that need no device, in its order: (stat, use_rank, ties) as the ABI takes them.
+    stat: g genes x c lists of float64 (a vector is one list); NaN: the gene takes no part in that list"""
+    a = _as_f64_fortran(stat)
+    if a.ndim == 1:
+        a = np.asfortranarray(a.reshape(-1, 1))
+    if a.ndim != 2:
+        raise ValueError("rankcor: stat must be genes x lists")
+    if a.shape[1] < 1:
+        raise ValueError("rankcor: 0 lists (at least 1)")
+    t = rankcor_ties(ties)
+    if a.shape[0] > RANKCOR_MAX_GENES:
+        raise _lib.PlaidHipError(_lib.EUNSUPPORTED, f"rankcor: {a.shape[0]} genes (at most {RANKCOR_MAX_GENES})")
+    return a, int(bool(use_rank)), t
+
+
+def _rankcor(fn, head, stat, Gp, Gi, use_rank=True, ties="average"):
+    """plaidhip_rankcor / _multi / the hook: (out, tot) -- sets x 5 x lists (RANKCOR_COLUMNS) and the lists' universe sizes"""
+    stat, use_rank, ties = check_rankcor_args(stat, use_rank, ties)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    g, c = stat.shape
+    m = len(Gp) - 1
+    out = np.full((m, 5, c), np.nan, dtype=np.float64, order="F")
+    tot = np.full(c, np.nan, dtype=np.float64)
+    check(fn(*head, _np_ptr(stat), g, c, _np_ptr(Gp), _np_ptr(Gi), m, use_rank, ties, _np_ptr(out), _np_ptr(tot)))
+    return out, tot
+
+
+def rankcor_finish(n, T1, T2, k, A) -> np.ndarray:
+    """plaidhip_rankcor_finish: the rank-mode epilogue and Benjamini-Hochberg on integer operands, on the host (no device is
+    touched).  n, T1, T2: one per list; k, A: sets x lists.  Returns sets x 5 x lists (RANKCOR_COLUMNS)"""
+    n, T1, T2 = (np.ascontiguousarray(np.atleast_1d(v), dtype=np.int64) for v in (n, T1, T2))
+    k, A = (np.asfortranarray(np.asarray(v, dtype=np.int64).reshape(-1, len(n))) for v in (k, A))
+    m, c = k.shape
+    if not (T1.shape == T2.shape == n.shape and A.shape == k.shape):
+        raise ValueError("rankcor_finish: n, T1, T2 have one entry per list; k and A are sets x lists")
+    out = np.full((m, 5, c), np.nan, dtype=np.float64, order="F")
+    check(_lib.load().plaidhip_rankcor_finish(m, c, _np_ptr(n), _np_ptr(T1), _np_ptr(T2), _np_ptr(k), _np_ptr(A), _np_ptr(out)))
+    return out
+
+
 LIMMA_MAX_COEF = 32   # PLAIDHIP_LIMMA_MAX_COEF
 LIMMA_COLUMNS = ("logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2")
 LIMMA_HYPER = ("df.residual", "df.prior", "s2.prior", "n.ok")
@@ -903,6 +959,12 @@ class Context:
         the rows of every set with sig != 0, in the set's member order"""
         return _fisher(self.lib.plaidhip_fisher, (self.handle,), sig, Gp, Gi, overlap)
 
+    def rankcor(self, stat, Gp, Gi, use_rank=True, ties="average"):
+        """plaidhip_rankcor: the correlation of the columns of stat (genes x lists; NaN: the gene takes no part in the list),
+        or of their ranks, with every set's membership: (out, tot) -- sets x 5 x lists (RANKCOR_COLUMNS) and the lists'
+        universe sizes n"""
+        return _rankcor(self.lib.plaidhip_rankcor, (self.handle,), stat, Gp, Gi, use_rank, ties)
+
     def gsea_permutations(self, g: int, nperm: int, seed=1) -> np.ndarray:
         """plaidhip_gsea_permutations: the genes x nperm int32 placements plaidhip_gsea generates from `seed`"""
         P = np.empty((int(g), int(nperm)), dtype=np.int32, order="F")
@@ -1090,6 +1152,11 @@ def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, 
 def fisher_multi(sig, Gp, Gi, overlap=False, devices=1):
     """plaid.fisher (Context.fisher) with the lists shared out over `devices`: the one-device bits"""
     return _fisher(*_multi("fisher", devices), sig, Gp, Gi, overlap)
+
+
+def rankcor_multi(stat, Gp, Gi, use_rank=True, ties="average", devices=1):
+    """plaid.rankcor (Context.rankcor) with the lists shared out over `devices`: the one-device bits"""
+    return _rankcor(*_multi("rankcor", devices), stat, Gp, Gi, use_rank, ties)
 
 
 def limma_multi(A, design, use=None, contrasts=None, devices=1):

@@ -604,6 +604,51 @@ plaid.fisher <- function(sig, G, minSize = 1, maxSize = NULL, sort.by = "pAny", 
 }
 
 
+## plaid.rankcor(): the reference's gset.rankcor(fc, matG, compute.p = TRUE) (experiments/R/functions.R:183-237) on the device
+## -- the "rankcor" and (use.rank = FALSE) "cor" families of the enrichment experiments
+## (experiments/compare-enrichment/enrichment-methods.R:36-37) and the first two single-sample scorers of run.methods: the
+## Pearson correlation of the ranks of a per-gene statistic, or of the statistic itself, with the 0/1 membership of every
+## set, for a named vector or every column of a genes x lists matrix (contrasts, or samples).  An NA leaves the gene out of
+## that list alone (ranks with na.last = "keep"; the universe and the set sizes are the list's own).
+## include/plaidhip.h (plaidhip_rankcor) pins the statistic.  ties: "average" (default), "min" or "max"; the reference's
+## ties.method = "random" is no function of the input and is not offered (lists without ties are the same under all of
+## them).  Genes are aligned by name as plaid.gsea aligns them.  Returns a matrix (a vector) or a named list of matrices:
+## sets x (size, rho, t, p.value, q.value) -- (size, rho) with compute.p = FALSE -- rows ordered by sort.by (NA last;
+## decreasing |rho| for "rho").
+plaid.rankcor <- function(stat, G, use.rank = TRUE, compute.p = TRUE, ties = c("average", "min", "max"), minSize = 1,
+                          maxSize = NULL, sort.by = "p.value") {
+  ties <- match.arg(ties)
+  single <- is.null(dim(stat))
+  if (single) stat <- matrix(stat, ncol = 1, dimnames = list(names(stat), "stat"))
+  stat <- as.matrix(stat); storage.mode(stat) <- "double"
+  if (is.list(G)) {
+    message("[plaid.rankcor] converting gmt to sparse matrix...")
+    G <- gmt2mat(G)
+  }
+  gg <- intersect(rownames(G), rownames(stat))
+  stat <- stat[gg, , drop = FALSE]
+  G <- G[gg, , drop = FALSE]
+  size <- Matrix::colSums(G != 0)
+  if (is.null(maxSize)) maxSize <- length(gg) - 1L
+  G <- G[, size >= minSize & size <= maxSize, drop = FALSE]
+  pat <- .aligned_pattern(stat, G)
+  .session()
+  r <- .Call("R_plaidhip_rankcor", .devices(), stat, pat$Gp, pat$Gi, isTRUE(as.logical(use.rank)),
+             match(ties, c("average", "min", "max")) - 1L, PACKAGE = "plaidhip")
+  tab <- r[[1]]
+  dim(tab) <- c(nrow(tab), 5L, ncol(stat))
+  cols <- c("size", "rho", "t", "p.value", "q.value")
+  if (!isTRUE(as.logical(compute.p))) cols <- cols[1:2]
+  out <- lapply(seq_len(ncol(stat)), function(l) {
+    res <- matrix(tab[, seq_along(cols), l], nrow = dim(tab)[1], dimnames = list(colnames(G), cols))
+    o <- if (sort.by %in% cols) order(if (sort.by == "rho") -abs(res[, "rho"]) else res[, sort.by]) else seq_len(nrow(res))
+    res[o, , drop = FALSE]
+  })
+  names(out) <- colnames(stat)
+  if (single) out[[1]] else out
+}
+
+
 ## the tables of plaid.limma() / plaid.limma.contrasts() from the library's rows x 6 block: topTable's order for sort.by --
 ## "none" (the rows of S), "P.Value" / "P" / "p" (increasing), "t" and "logFC" (decreasing magnitude), "AveExpr" (decreasing)
 .limma_sorts <- c("none", "P.Value", "P", "p", "t", "logFC", "AveExpr")

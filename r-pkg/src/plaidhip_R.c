@@ -684,6 +684,28 @@ SEXP R_plaidhip_limma(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use, S
   return res;
 }
 
+/* plaid.rankcor(): list(out, tot) of plaidhip_rankcor -- out an m x 5c matrix (columns 5 l + 1 .. 5 l + 5 the columns of list
+ * l; the caller gives it dim m x 5 x c), tot the c universe sizes.  stat: a g x c double matrix, NA / NaN: the gene takes no
+ * part in that list; ties: 0 average, 1 min, 2 max; several devices: the _multi entry */
+SEXP R_plaidhip_rankcor(SEXP devices, SEXP stat, SEXP Gp, SEXP Gi, SEXP use_rank, SEXP ties) {
+  const int g = Rf_nrows(stat), c = Rf_ncols(stat), m = LENGTH(Gp) - 1;
+  const int ur = Rf_asLogical(use_rank) == 1, tm = Rf_asInteger(ties);
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 5 * c));
+  SEXP tot = PROTECT(Rf_allocVector(REALSXP, c));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, tot);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_rankcor_multi(INTEGER(devices), LENGTH(devices), REAL(stat), g, c, INTEGER(Gp), INTEGER(Gi), m, ur, tm,
+                                REAL(out), REAL(tot));
+  else
+    rc = plaidhip_rankcor(ctx(), REAL(stat), g, c, INTEGER(Gp), INTEGER(Gi), m, ur, tm, REAL(out), REAL(tot));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(3);
+  return res;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -729,6 +751,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsea_scored", (DL_FUNC)&R_plaidhip_gsea_scored, 11},
     {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
     {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
+    {"R_plaidhip_rankcor", (DL_FUNC)&R_plaidhip_rankcor, 6},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {

@@ -215,6 +215,32 @@ static void limma() {
   printf("  limma: designs of 1, 2, 3 and 32 coefficients, refused ones, and the finish step up to 70,001 rows on host threads\n");
 }
 
+// plaid.rankcor's host half: plaidhip_rankcor_finish on tie-free lists at the integer limits (n = 131,072: 128-bit products),
+// on the degenerate tables and on operands it must refuse
+static void rankcor() {
+  for (int64_t n : {2, 3, 10, 1000, 131072}) {
+    const int32_t m = 6;
+    // z = 2, 4, ..., 2n: T1 = n (n + 1), T2 = 2 n (n + 1) (2n + 1) / 3; a set of the k highest ranks has A = k (2n - k + 1)
+    const int64_t T1 = n * (n + 1), T2 = 2 * n * (n + 1) * (2 * n + 1) / 3;
+    const int64_t ks[m] = {0, 1, n / 2, n - 1, n, 1};
+    std::vector<int64_t> k(ks, ks + m), A((size_t)m);
+    for (int j = 0; j < m; ++j) A[(size_t)j] = k[(size_t)j] * (2 * n - k[(size_t)j] + 1);
+    A[5] = 2;   // the lowest rank alone
+    std::vector<double> out((size_t)m * 5, -7.0);
+    REQUIRE(plaidhip_rankcor_finish(m, 1, &n, &T1, &T2, k.data(), A.data(), out.data()) == PLAIDHIP_OK);
+    for (int j = 0; j < m; ++j) {
+      const double rho = out[(size_t)m + j], pv = out[3 * (size_t)m + j];
+      REQUIRE(out[(size_t)j] == (double)k[(size_t)j]);
+      REQUIRE((k[(size_t)j] == 0 || k[(size_t)j] == n) ? std::isnan(rho) : (rho >= -1.0 && rho <= 1.0));
+      REQUIRE(std::isnan(pv) || (pv >= 0.0 && pv <= 1.0));
+    }
+    REQUIRE(n < 3 || (out[(size_t)m + 1] > 0.0 && out[(size_t)m + 5] < 0.0));
+    const int64_t bad = n + 1;
+    REQUIRE(plaidhip_rankcor_finish(1, 1, &n, &T1, &T2, &bad, A.data(), out.data()) == PLAIDHIP_EINVAL);
+  }
+  printf("  rankcor: the finish step at n = 2 .. 131,072, k = 0 .. n, and refused operands\n");
+}
+
 int main() {
   printf("[host-asan] planners\n");
   plans();
@@ -224,6 +250,8 @@ int main() {
   tails();
   printf("[host-asan] plaid.limma's design and finish\n");
   limma();
+  printf("[host-asan] plaid.rankcor's finish\n");
+  rankcor();
   printf("[host-asan] ok\n");
   return 0;
 }
