@@ -1059,6 +1059,74 @@ int plaidhip_rankcor_multi(const int* devices, int ndev, const double* stat, int
 int plaidhip_rankcor_finish(int32_t m, int32_t c, const int64_t* n, const int64_t* T1, const int64_t* T2, const int64_t* k,
                             const int64_t* A, double* out);
 
+/* replaid.zscore(X, G) and replaid.plage(X, G): the other two methods of GSVA::gsva(), the reference's
+ * gset.gsva(X, geneSets, method = "zscore" | "plage") (experiments/R/functions.R:148-160); DESIGN.md section 22.
+ * Operands: X is g x n doubles, column-major, or the slots of a dgCMatrix (sorted, distinct row indices), which is expanded
+ * on the device and scored as its dense form: the same bits.  G is aligned to X's rows (Gp, Gi).  n >= 2.
+ * STANDARDIZATION, per gene row over all n samples, fp64, GSVA's scale() (no 1e-8, unlike replaid.gsva):
+ *     mean = (sum of x) / (double)n;   ss = sum of (x - mean)^2;   sd = sqrt(ss / (double)(n - 1));   z = (x - mean) / sd
+ * Both sums run over the samples 0, 1, ..., n - 1 in that order from 0.0, one addition each (the order of
+ * kcdf_row_moments_kernel, kernels_kcdf.hip); d = x - mean and d * d are rounded before they are added.
+ *   sd == 0: a constant gene.  It is left out of every set, as GSVA's filter does: a set's effective size k counts its other
+ *   members (a member listed twice counts twice).
+ *   sd not finite (the row holds a NaN or an infinity, or its sum of squares overflows): the row stays a member, and every
+ *   score of every set that contains it is NaN.  Other sets are untouched.
+ * ZSCORE (Lee et al. 2008).  S[s, j] = (sum of z_ij over the kept members of s) / sqrt((double)k_s); the sum is the crossprod
+ * of plaidhip_plaid_dense with stat = sum on Z (a constant row holds 0.0 there), the division and the square root are
+ * correctly rounded.  k_s == 0 gives NaN.  size_out (nullable): the m effective sizes.
+ * PLAGE (Tomfohr et al. 2005).  Z_s is the k x n block of the set's kept rows in G's own order, C = Z_s Z_s' (k x k; n - 1
+ * times the genes' correlation matrix), u the unit eigenvector of C's largest eigenvalue lambda, and the score
+ *     v_j = (sum over i of u_i z_ij) / sqrt(lambda)                 (svd(Z_s)$v[, 1] up to sign)
+ * summed over the kept members in G's order from 0.0, each product rounded before it is added.  k == 0 gives a NaN row;
+ * k == 1 gives u = (1), lambda = C_00 and v = z / sqrt(lambda).
+ *   C.  C_ab = the sum over the samples 0, 1, ..., n - 1, in that order from 0.0, of the products z_aj z_bj, each ROUNDED
+ *   before it is added (no fused operation; the rows are padded with zeros to a multiple of 16 samples, which adds exact
+ *   zeros).  The order depends on nothing but n.  C_ab is computed once for a <= b and mirrored, so C is symmetric bit for
+ *   bit, and two rows whose products cancel term by term (the orthogonal pair [1,-1,1,-1], [1,1,-1,-1]) give an exact 0.
+ *   (The fp64 matrix instruction v_mfma_f64_16x16x4_f64 adds unrounded products and leaves a rounding residue there (1.9e-18 of
+ *   lambda on that pair): the kernel built on it stays behind a test hook)
+ *   Start.  u = the column of C with the largest squared 2-norm (sum over j = 0..k-1 in order of C_ji^2; the lowest index
+ *   at a tie), divided by the square root of that sum.  (Never the all-ones vector: for k = 2 it is always an eigenvector,
+ *   and for a negatively correlated pair the wrong one.)
+ *   Step t = 1, 2, ...: y = C u (y_i = sum over j = 0..k-1 in order of C_ij u_j), lambda = u'y, r = ||y - lambda u||_2.
+ *   Stop when r <= tol * lambda (converged = 1) or when t == maxit (converged = 0: the last iterate is returned);
+ *   otherwise u = y / ||y||_2.  The returned u is the one lambda and r were computed for.
+ *   The sums over i (u'y, the norms, and those of the orientation and the trace) run in one fixed tree: thread h of 256
+ *   adds its elements h, h + 256, ... in ascending order from 0.0, then partial[h] += partial[h + w] for w = 128, 64, ..., 1.
+ *   No product is contracted into an add anywhere.
+ *   Orientation, part of the definition: s = sum of u_i, a = sum of |u_i|.  If |s| > 2^-20 a, u is oriented so that s > 0
+ *   (the score rises when the set's genes rise on average).  Otherwise the first kept member in G's order with
+ *   |u_i| >= max|u| / 2 is made positive (member 0 of a negatively correlated pair).
+ *   info_out (nullable): m x 6 doubles, column-major: size (the effective k), lambda, explained = lambda / trace(C) (the
+ *   trace summed from the computed diagonal), iterations (the steps taken), residual = r / lambda, converged.  A set with
+ *   k == 0 or with a flagged member reports its size, NaN in lambda, explained and residual, and 0 in the other two.
+ *   load_out (nullable): Gp[m] doubles, u in the set's own segment of G (the layout of plaidhip_gsea_scored's le_idx); the
+ *   entry of a dropped constant member is 0.0, the kept members of a NaN set hold NaN.
+ * tol (the callers' default 2^-40) and maxit (1000) are arguments, as in any eigensolver.
+ * Argument errors, in this order, all found on the host before any device is touched: bad dims or a null Gp; n < 2;
+ * (plage) tol not > 0 (a NaN included), maxit < 1; Gp not starting at 0 or decreasing; (plage) a set of more than
+ * PLAIDHIP_PLAGE_MAX_SET members; with m > 0: a null X, S_out or Gi, a malformed dgCMatrix, a Gi row outside 0..g-1.
+ * m = 0 returns PLAIDHIP_OK with nothing written.
+ * The _multi forms send all of X to every device, as rowtf = "gauss" does: every device standardizes and (plage) forms C
+ * and u of every set -- redundant by design, the same code in the same order, hence the same bits -- and then scores its
+ * own sample columns (plaidhip_shard_bounds over n).  Every sharding, ndev > n included, returns the one-device bits.
+ * Not offered: sets shared out over devices; sets above the cap; GSVA's Poisson kernel. */
+#define PLAIDHIP_PLAGE_MAX_SET 4096
+int plaidhip_plage(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                   double tol, int32_t maxit, double* S_out, double* info_out, double* load_out);
+int plaidhip_plage_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                       const int32_t* Gp, const int32_t* Gi, int32_t m, double tol, int32_t maxit, double* S_out, double* info_out,
+                       double* load_out);
+int plaidhip_plage_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                         int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tol, int32_t maxit, double* S_out,
+                         double* info_out, double* load_out);
+int plaidhip_zscore(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                    double* S_out, double* size_out);
+int plaidhip_zscore_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                        const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out, double* size_out);
+int plaidhip_zscore_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                          int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out, double* size_out);
+
 /* plaid.limma(A, design, contrasts): limma's moderated t-test -- lmFit + eBayes + topTable -- of every row of A (the
  * single-sample scores of the sets, or the expression of the genes) for one or several designs.  The form is limma's AS
  * RECALLED: its source is not in this tree, so the statistic is pinned here and tested against these words in 50-digit

@@ -153,6 +153,12 @@ SIGNATURES = {
     "plaidhip_rankcor": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, _vp],
     "plaidhip_rankcor_multi": [_vp, _int, _vp, _i32, _i32, _vp, _vp, _i32, _int, _int, _vp, _vp],
     "plaidhip_rankcor_finish": [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_plage": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp],
+    "plaidhip_plage_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp],
+    "plaidhip_plage_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp],
+    "plaidhip_zscore": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "plaidhip_zscore_csc": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "plaidhip_zscore_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "plaidhip_limma": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "plaidhip_limma_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "plaidhip_dev_row_design_effects": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],

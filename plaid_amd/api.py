@@ -359,6 +359,70 @@ def replaid_gsva_exact(X, matG, tau=1, rowtf="z", max_diff=True, ctx: Context | 
     return NamedMatrix(S, matG.colnames, X.colnames)
 
 
+def _sized_pattern(X, matG, minSize, maxSize):
+    """the aligned pattern of the sets with minSize <= aligned members <= maxSize (None: no upper limit), and their names"""
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    Gp, Gi = np.asarray(pat[0]), np.asarray(pat[1])
+    sizes = np.diff(Gp)
+    keep = np.flatnonzero((sizes >= int(minSize)) & (sizes <= (sizes.max(initial=0) if maxSize is None else int(maxSize))))
+    Gi = np.concatenate([Gi[Gp[j]:Gp[j + 1]] for j in keep]).astype(np.int32) if len(keep) else np.zeros(0, np.int32)
+    Gp = np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int32)
+    return Gp, Gi, [matG.colnames[j] for j in keep]
+
+
+def replaid_plage(X, matG, minSize=1, maxSize=None, tol=2.0 ** -40, maxit=1000, loadings=False, ctx: Context | None = None):
+    """replaid.plage(): GSVA's method = "plage" (Tomfohr et al. 2005) -- per set the first right singular vector of the
+    standardized expression block of its genes, the set's "activity" across the samples -- as pinned in include/plaidhip.h
+    (plaidhip_plage).  Genes are standardized over all samples (GSVA's scale()); constant genes are left out of every set;
+    a gene holding NaN or Inf makes the scores of its sets NaN.  The sign, arbitrary in LAPACK and so in GSVA, is pinned:
+    the score rises when the set's genes rise on average.  X dense or sparse (scored as its dense form).  Sets with fewer
+    than minSize or more than maxSize aligned members are dropped; maxSize above the cap of 4096 members is a ValueError, and
+    so is a kept set above it.  tol, maxit: the stop test and the step cap of the power iteration.  Returns (scores, info):
+    sets x samples, and sets x [size, lambda, explained, iterations, residual, converged]; with loadings = True also a
+    dict, set -> (gene names, loadings) over the set's aligned members (0 for a dropped constant gene)."""
+    from .engine import PLAGE_COLUMNS, PLAGE_MAX_SET
+    if maxSize is not None and int(maxSize) > PLAGE_MAX_SET:
+        raise ValueError(f"replaid.plage: maxSize = {int(maxSize)} (at most {PLAGE_MAX_SET} members)")
+    if not (float(tol) > 0.0):
+        raise ValueError(f"replaid.plage: tol = {tol} (a positive number)")
+    if int(maxit) < 1:
+        raise ValueError(f"replaid.plage: maxit = {maxit} (at least 1)")
+    X, matG = as_named(X), as_named(matG)
+    pat = _sized_pattern(X, matG, minSize, maxSize)
+    if pat is None:
+        return None
+    Gp, Gi, names = pat
+    if len(Gp) > 1 and int(np.diff(Gp).max()) > PLAGE_MAX_SET:
+        raise ValueError(f"replaid.plage: a set of {int(np.diff(Gp).max())} members (at most {PLAGE_MAX_SET}; set maxSize)")
+    ctx = ctx or default_context()
+    V = _canonical_csc(X.values) if X.is_sparse else X.values
+    res = ctx.plage(V, Gp, Gi, tol, maxit, loadings)
+    out = (NamedMatrix(res[0], names, X.colnames), NamedMatrix(res[1], names, list(PLAGE_COLUMNS)))
+    if not loadings:
+        return out
+    load = {nm: ([X.rownames[i] for i in Gi[Gp[j]:Gp[j + 1]]], res[2][Gp[j]:Gp[j + 1]].copy()) for j, nm in enumerate(names)}
+    return out + (load,)
+
+
+def replaid_zscore(X, matG, ctx: Context | None = None):
+    """replaid.zscore(): GSVA's method = "zscore" (Lee et al. 2008) -- the sum of a set's standardized genes over the
+    square root of their number -- as pinned in include/plaidhip.h (plaidhip_zscore).  Genes are standardized over all
+    samples (GSVA's scale()); constant genes are left out of every set; a set without a kept gene scores NaN, and so does
+    every set holding a gene with NaN or Inf.  X dense or sparse (scored as its dense form).  Returns sets x samples."""
+    X, matG = as_named(X), as_named(matG)
+    pat = aligned_pattern(X, matG)
+    if pat is None:
+        _message("[plaid] ERROR. No overlapping features.")
+        return None
+    ctx = ctx or default_context()
+    V = _canonical_csc(X.values) if X.is_sparse else X.values
+    S, _ = ctx.zscore(V, pat[0], pat[1])
+    return NamedMatrix(S, matG.colnames, X.colnames)
+
+
 def replaid_sing_exact(X, matG, matD=None, center=True, dispersion=True, ctx: Context | None = None):
     """replaid.sing.exact(): singscore's normalised score (mean rank - low) / (high - low) [- 0.5] and its dispersion, the
     MAD of the set's ranks in the sample (include/plaidhip.h: plaidhip_sing_exact), where replaid.sing returns

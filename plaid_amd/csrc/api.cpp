@@ -1214,6 +1214,30 @@ int plaidhip_rankcor(plaidhip_ctx* ctx, const double* stat, int32_t g, int32_t c
   return dispatch(on_context(ctx), rankcor_call(stat, g, c, Gp, Gi, m, use_rank, ties, out, tot_out));
 } catch (...) { return plaidhip::on_exception(); }
 
+// replaid.plage / replaid.zscore: the one-device forms of the sharded engine (multi.cpp: plage_worker, kPlage / kZscore)
+int plaidhip_plage(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                   double tol, int32_t maxit, double* S_out, double* info_out, double* load_out) try {
+  return dispatch(on_context(ctx), plage_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, tol, maxit, S_out, info_out, load_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_plage_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                       const int32_t* Gp, const int32_t* Gi, int32_t m, double tol, int32_t maxit, double* S_out, double* info_out,
+                       double* load_out) try {
+  PH_REQUIRE(Xp != nullptr, "plage_csc: null Xp");
+  return dispatch(on_context(ctx), plage_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, tol, maxit, S_out, info_out, load_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_zscore(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                    double* S_out, double* size_out) try {
+  return dispatch(on_context(ctx), zscore_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, S_out, size_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_zscore_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
+                        const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out, double* size_out) try {
+  PH_REQUIRE(Xp != nullptr, "zscore_csc: null Xp");
+  return dispatch(on_context(ctx), zscore_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, S_out, size_out));
+} catch (...) { return plaidhip::on_exception(); }
+
 // plaid.fisher: the one-device form of the sharded engine (multi.cpp: fisher_worker, kFisher)
 int plaidhip_fisher(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
                     double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx) try {

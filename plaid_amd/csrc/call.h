@@ -12,7 +12,7 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16, kRankcor = 17
+  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -86,6 +86,11 @@ struct Call : Operands {
   // plaid.rankcor: X is stat (g x n, n = the lists, dense; NaN: the gene takes no part in the list), out m x 5 x n, tot_out
   // the n universe sizes; ranks (with their ties) or values
   int use_rank = 1, ties = PLAIDHIP_TIES_AVERAGE;
+  // replaid.plage: the stop test and the step cap of the power iteration, out m x 6 (the per-set statistics, nullable),
+  // load_out Gp[m] loadings (nullable); replaid.zscore: out the m effective sizes (nullable)
+  double tol = 0.0;
+  int32_t maxit = 0;
+  double* load_out = nullptr;
   // plaid.limma: X is A (g rows x n samples; no sets: Gp stays null, m = 0), the nfit designs (n x p each), use (n x nfit,
   // null: all), K (p x q, null: the unit vectors), out g x 6 x q x nfit and hyper nfit x 4; what check_call makes of the
   // designs: Q (n x p x nfit), 1 / n_f, n_f, v (p x q x nfit) and u (q x nfit)
@@ -286,6 +291,23 @@ inline Call rankcor_call(const double* stat, int32_t g, int32_t c, const int32_t
   k.ties = ties;
   k.out = out;
   k.tot_out = tot_out;
+  return k;
+}
+
+// GSVA's "plage" and "zscore" as pinned in include/plaidhip.h: plaidhip_plage, plaidhip_zscore
+inline Call plage_call(const Operands& x, double tol, int32_t maxit, double* S_out, double* info_out, double* load_out) {
+  Call k = make_call(kPlage, x, S_out);
+  k.tol = tol;
+  k.maxit = maxit;
+  k.out = info_out;
+  k.load_out = load_out;
+  return k;
+}
+inline Call zscore_call(const Operands& x, double* S_out, double* size_out) {
+  Call k = make_call(kZscore, x, S_out);
+  k.stat = PLAIDHIP_STAT_SUM;
+  k.normalize = 0;
+  k.out = size_out;
   return k;
 }
 

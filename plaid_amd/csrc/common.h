@@ -649,6 +649,35 @@ int launch_rankcor_gather(plaidhip_ctx* ctx, int use_rank, const void* tiles, co
 // stats.cpp: the pinned epilogues of one (list, set), host only: o[0 .. 2] <- rho, t, p
 void rankcor_rank_epilogue(int64_t n, int64_t T1, int64_t T2, int64_t k, int64_t A, double* o);
 void rankcor_value_epilogue(int64_t n, double T1, double T2, int flag, int64_t k, double A, double* o);
+// kernels_plage.hip: replaid.zscore and replaid.plage (include/plaidhip.h: plaidhip_zscore, plaidhip_plage).  All stream-ordered,
+// all pointers device pointers unless said otherwise.  mean, sd: g doubles; flag: g int32 (0 kept, 1 constant, 2 sd not
+// finite)
+int launch_plage_moments(plaidhip_ctx* ctx, const double* X, int64_t ldx, int32_t g, int32_t n, double* mean, double* sd,
+                         int32_t* flag);
+// Z (g x nj, leading dimension ldz) of the columns [j0, j0 + nj) of X: 0.0 in a constant row, NaN in a flagged one
+int launch_plage_standardize_columns(plaidhip_ctx* ctx, const double* X, int64_t ldx, int32_t g, int32_t j0, int32_t nj,
+                                     const double* mean, const double* sd, const int32_t* flag, double* Z, int64_t ldz);
+// Zg (g rows of ldz = plage_row_ld(n) doubles: a gene's n samples, then zeros) of all of X
+int64_t plage_row_ld(int32_t n);
+void debug_plage_set_gram(int mode);   // test hook: 0 the product's Gram kernel (rounded products), 1 the MFMA form
+int launch_plage_standardize_rows(plaidhip_ctx* ctx, const double* X, int64_t ldx, int32_t g, int32_t n, const double* mean,
+                                  const double* sd, const int32_t* flag, double* Zg, int64_t ldz);
+// per set: Ci / Cpos (Gp[m] int32 each: the kept members' rows and their positions in the set's segment, G's order), keff
+// and nanflag (m int32 each); every Gi is in 0..g-1 (checked on the host)
+int launch_plage_compact(plaidhip_ctx* ctx, const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* flag, int32_t* Ci,
+                         int32_t* Cpos, int32_t* keff, int32_t* nanflag);
+// the Gram matrices and the power iteration of every set: U (Gp[m] doubles: the oriented unit vector over the kept members),
+// stats (m x 6, column-major), L (Gp[m] doubles or null: the loadings by member position).  hGp: the host's Gp.  Synchronizes.
+int launch_plage_sets(plaidhip_ctx* ctx, const double* Zg, int64_t ldz, const int32_t* hGp, const int32_t* Gp, const int32_t* Ci,
+                      const int32_t* Cpos, const int32_t* keff, const int32_t* nanflag, int32_t m, double tol, int32_t maxit,
+                      double* U, double* stats, double* L);
+// S (m x nj, leading dimension lds) <- the scores of the samples [j0, j0 + nj)
+int launch_plage_project(plaidhip_ctx* ctx, const double* Zg, int64_t ldz, const int32_t* Gp, const int32_t* Ci,
+                         const int32_t* keff, const int32_t* nanflag, const double* U, const double* stats, int32_t m, int32_t j0,
+                         int32_t nj, double* S, int64_t lds);
+// S (m x n sums of z over every set) <- S / sqrt(k); NaN for k = 0 and for a set with a flagged member
+int launch_zscore_epilogue(plaidhip_ctx* ctx, double* S, int64_t lds, int32_t m, int32_t n, const int32_t* keff,
+                           const int32_t* nanflag);
 // kernels_norm.hip
 int launch_minflags(plaidhip_ctx* ctx, const double* S, int64_t count, uint32_t* flags);
 // kernels_medians.hip

@@ -2062,6 +2062,112 @@ int rankcor_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh
   return s.finish();
 }
 
+// one device's part of replaid.plage and replaid.zscore (kPlage, kZscore; kernels_plage.hip).  A gene's moments need all its
+// samples and a set's eigenvector all of its rows, so every shard takes all of X (a dgCMatrix as its slots, expanded on the
+// device into the dense form, as rowtf = "gauss" does), standardizes, and -- for plage -- forms C and u of EVERY set: the
+// same code in the same order on every device, hence the same bits.  The shard then projects (plage) or sums (zscore: the
+// crossprod with stat = sum on Z, then the epilogue) its own sample columns.  Shard 0 brings home what does not depend on
+// the columns: the per-set statistics and the loadings, or the effective sizes.  No rendezvous.
+int plage_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t g = c.g, n = c.n, m = c.m, lo = s.lo, nloc = s.nloc;
+  const bool plage = c.method == kPlage;
+  const bool writer = k == 0;
+  const bool idle = nloc <= 0 && !writer;
+  const size_t z = (size_t)std::max<int32_t>(c.Gp[m], 1);
+  const int64_t ldz = plage ? plage_row_ld(n) : (int64_t)g;
+  s.force_f64();   // (zscore's crossprod stays on the fp64 kernels whatever precision the context was given)
+  plaidhip_geneset* gs = nullptr;
+  DevBuf dfull, dp, di, dx, ddflt, dmom, dflag, dGp, dGi, dCi, dCpos, dkf, dZ, dU, dstats, dL, dS;
+  HomeBuffer home;
+  std::vector<int32_t> hk;
+
+  // ---- all of X, the moments, the kept members, Z --------------------------------------------------------------------------
+  s.step([&]() -> int {
+    if (idle) return PLAIDHIP_OK;
+    PH_HIP(hipSetDevice(ctx->device));
+    PH_TRY(dfull.alloc((size_t)g * n * 8));
+    if (c.Xp == nullptr) {
+      PH_TRY(upload_host(ctx, dfull.p, (size_t)g * 8, c.X, (size_t)g * 8, n));
+    } else {
+      const int64_t zx = c.Xp[n];
+      PH_TRY(dp.alloc((size_t)(n + 1) * 4));
+      PH_TRY(di.alloc((size_t)std::max<int64_t>(zx, 1) * 4));
+      PH_TRY(dx.alloc((size_t)std::max<int64_t>(zx, 1) * 8));
+      PH_TRY(ddflt.alloc((size_t)g * 8));
+      PH_HIP(hipMemcpyAsync(dp.p, c.Xp, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(upload_host(ctx, di.p, 1, c.Xi, 1, zx * 4));
+      PH_TRY(upload_host(ctx, dx.p, 1, c.X, 1, zx * 8));
+      PH_HIP(hipMemsetAsync(ddflt.p, 0, (size_t)g * 8, ctx->stream));   // (the rows' default: a zero)
+      PH_TRY(launch_csc_expand(ctx, dp.as<int32_t>(), di.as<int32_t>(), dx.as<double>(), g, n, g, ddflt.as<double>(), nullptr,
+                               nullptr, dfull.as<double>()));
+    }
+    PH_TRY(dmom.alloc((size_t)g * 2 * 8));
+    PH_TRY(dflag.alloc((size_t)g * 4));
+    double* d_mean = dmom.as<double>();
+    double* d_sd = d_mean + g;
+    PH_TRY(launch_plage_moments(ctx, dfull.as<double>(), g, g, n, d_mean, d_sd, dflag.as<int32_t>()));
+    PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
+    PH_TRY(dCi.alloc(z * 4));
+    PH_TRY(dCpos.alloc(z * 4));
+    PH_TRY(dkf.alloc((size_t)m * 2 * 4));   // [keff | nanflag]
+    PH_TRY(launch_plage_compact(ctx, dGp.as<int32_t>(), dGi.as<int32_t>(), m, dflag.as<int32_t>(), dCi.as<int32_t>(),
+                                dCpos.as<int32_t>(), dkf.as<int32_t>(), dkf.as<int32_t>() + m));
+    PH_TRY(dS.alloc((size_t)m * std::max(nloc, 1) * 8));
+    if (plage) {
+      PH_TRY(dZ.alloc((size_t)g * ldz * 8));
+      PH_TRY(launch_plage_standardize_rows(ctx, dfull.as<double>(), g, g, n, d_mean, d_sd, dflag.as<int32_t>(), dZ.as<double>(),
+                                           ldz));
+    } else if (nloc > 0) {
+      PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+      PH_TRY(dZ.alloc((size_t)g * nloc * 8));
+      PH_TRY(launch_plage_standardize_columns(ctx, dfull.as<double>(), g, g, lo, nloc, d_mean, d_sd, dflag.as<int32_t>(),
+                                              dZ.as<double>(), ldz));
+    }
+    if (nloc > 0) home.prepare(c.S_out + (int64_t)lo * m, (size_t)m * nloc * 8);
+    return PLAIDHIP_OK;
+  });
+
+  // ---- plage: C, u and the projection; zscore: the crossprod and its epilogue -----------------------------------------------
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    if (idle) return PLAIDHIP_OK;
+    const int32_t* d_keff = dkf.as<int32_t>();
+    const int32_t* d_nan = d_keff + m;
+    if (plage) {
+      PH_TRY(dU.alloc(z * 8));
+      PH_TRY(dstats.alloc((size_t)m * 6 * 8));
+      if (writer && c.load_out != nullptr) PH_TRY(dL.alloc(z * 8));
+      PH_TRY(launch_plage_sets(ctx, dZ.as<double>(), ldz, c.Gp, dGp.as<int32_t>(), dCi.as<int32_t>(), dCpos.as<int32_t>(), d_keff,
+                               d_nan, m, c.tol, c.maxit, dU.as<double>(), dstats.as<double>(), dL.as<double>()));
+      return launch_plage_project(ctx, dZ.as<double>(), ldz, dGp.as<int32_t>(), dCi.as<int32_t>(), d_keff, d_nan, dU.as<double>(),
+                                  dstats.as<double>(), m, lo, nloc, dS.as<double>(), m);
+    }
+    if (nloc <= 0) return PLAIDHIP_OK;
+    PH_TRY(launch_spmm_dense_f64(ctx, gs, dZ.as<double>(), ldz, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dS.as<double>(), m,
+                                 nullptr));
+    return launch_zscore_epilogue(ctx, dS.as<double>(), m, m, nloc, d_keff, d_nan);
+  });
+
+  // ---- the score shard goes home; shard 0 brings the per-set results ----------------------------------------------------------
+  s.step([&]() -> int {
+    if (idle) return PLAIDHIP_OK;
+    if (nloc > 0) PH_TRY(home.copy(ctx, dS.p));
+    if (writer && plage && c.out != nullptr)
+      PH_HIP(hipMemcpyAsync(c.out, dstats.p, (size_t)m * 6 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (writer && plage && c.load_out != nullptr && c.Gp[m] > 0)
+      PH_HIP(hipMemcpyAsync(c.load_out, dL.p, (size_t)c.Gp[m] * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (writer && !plage && c.out != nullptr) {
+      hk.resize((size_t)m);
+      PH_HIP(hipMemcpyAsync(hk.data(), dkf.p, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t j = 0; j < hk.size(); ++j) c.out[j] = (double)hk[j];
+    return PLAIDHIP_OK;
+  });
+  return s.finish();
+}
+
 // chain_contrast_sums for any [nblk][len] partials of the shard's columns (launch_reduce_blocks_flat): shard r adds its blocks,
 // in order, to what the shards before it left in `run`; d_seed, d_run: len doubles each.  ndev rendezvous.
 void chain_flat_sums(Shard& s, std::vector<double>& run, const double* ws, int64_t len, double* d_seed, double* d_run) {
@@ -2181,6 +2287,7 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     if (c.method == kGsea) return gsea_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kFisher) return fisher_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kRankcor) return rankcor_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kPlage || c.method == kZscore) return plage_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kLimma) return limma_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
@@ -2563,6 +2670,40 @@ int check_rankcor_call(const Call& c) {
   return PLAIDHIP_OK;
 }
 
+// replaid.plage and replaid.zscore; the order is part of the contract (include/plaidhip.h)
+int check_plage_call(const Call& c) {
+  const bool plage = c.method == kPlage;
+  const char* who = plage ? "plage" : "zscore";
+  PH_TRY(check_host_common(c.Gp, c.g, c.n, c.m));
+  PH_REQUIRE(c.n >= 2, "%s: %d samples (at least 2)", who, c.n);
+  if (plage) {
+    PH_REQUIRE(c.tol > 0.0, "plage: tol = %g (a positive number)", c.tol);   // (a NaN is refused here too)
+    PH_REQUIRE(c.maxit >= 1, "plage: maxit = %d (at least 1)", c.maxit);
+  }
+  PH_REQUIRE(c.Gp[0] == 0, "%s: Gp[0] = %d (a column pointer starts at 0)", who, c.Gp[0]);
+  for (int32_t j = 0; j < c.m; ++j) {
+    PH_REQUIRE(c.Gp[j + 1] >= c.Gp[j], "%s: Gp[%d] = %d after %d (a column pointer does not decrease)", who, j + 1, c.Gp[j + 1],
+               c.Gp[j]);
+    PH_REQUIRE(!plage || c.Gp[j + 1] - c.Gp[j] <= PLAIDHIP_PLAGE_MAX_SET, "plage: set %d has %d members (at most %d)", j + 1,
+               c.Gp[j + 1] - c.Gp[j], PLAIDHIP_PLAGE_MAX_SET);
+  }
+  if (c.m == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.X != nullptr || (c.Xp != nullptr && c.Xp[c.n] == 0), "%s: null X", who);
+  PH_REQUIRE(c.S_out != nullptr, "%s: null S_out", who);
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "%s: null Gi", who);
+  if (c.Xp != nullptr) {
+    PH_TRY(check_host_csc(c.Xp, c.Xi, c.g, c.n));
+    PH_REQUIRE(c.Xp[c.n] == 0 || c.Xi != nullptr, "%s: null Xi", who);
+    for (int32_t j = 0; j < c.n; ++j)   // (the expansion takes a column's rows as sorted and distinct)
+      for (int32_t q = c.Xp[j] + 1; q < c.Xp[j + 1]; ++q)
+        PH_REQUIRE(c.Xi[q] > c.Xi[q - 1], "%s: row indices of column %d are not increasing (Xi[%d] = %d after %d)", who, j, q,
+                   c.Xi[q], c.Xi[q - 1]);
+  }
+  for (int32_t e = 0; e < c.Gp[c.m]; ++e)
+    PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "%s: Gi[%d] = %d (rows are 0..%d)", who, e, c.Gi[e], c.g - 1);
+  return PLAIDHIP_OK;
+}
+
 // plaid.limma; the order is part of the contract (include/plaidhip.h).  Makes every fit's Q, v, u and n_f: the designs are
 // decomposed here, on the host, so that a design that cannot be fitted is refused before any device is touched
 int check_limma_call(Call& c) {
@@ -2651,6 +2792,8 @@ int check_call(Call& c, int ndev, bool multi) {
     case kGsea: return check_gsea_call(c);
     case kFisher: return check_fisher_call(c);
     case kRankcor: return check_rankcor_call(c);
+    case kPlage:
+    case kZscore: return check_plage_call(c);
     case kLimma: return check_limma_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
@@ -2953,6 +3096,35 @@ int plaidhip_debug_rankcor_sharded_on_one_device(int device, int nshards, int fa
                                                  int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, int use_rank,
                                                  int ties, double* out, double* tot_out) try {
   return dispatch(on_hook(device, nshards, fail_shard), rankcor_call(stat, g, c, Gp, Gi, m, use_rank, ties, out, tot_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_plage_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                         int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double tol, int32_t maxit, double* S_out,
+                         double* info_out, double* load_out) try {
+  return dispatch(on_devices(devices, ndev), plage_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tol, maxit, S_out, info_out, load_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_zscore_multi(const int* devices, int ndev, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g,
+                          int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out, double* size_out) try {
+  return dispatch(on_devices(devices, ndev), zscore_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, S_out, size_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+// which Gram kernel replaid.plage launches: 0 the product's (rounded products), 1 the MFMA form
+int plaidhip_debug_plage_gram(int mode) try {
+  PH_REQUIRE(mode == 0 || mode == 1, "debug_plage_gram: mode = %d", mode);
+  plaidhip::debug_plage_set_gram(mode);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// method: kPlage (18) or kZscore (19), which takes no tol / maxit / load_out and the sizes in info_out
+int plaidhip_debug_plage_sharded_on_one_device(int device, int nshards, int fail_shard, int method, const int32_t* Xp,
+                                               const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n, const int32_t* Gp,
+                                               const int32_t* Gi, int32_t m, double tol, int32_t maxit, double* S_out,
+                                               double* info_out, double* load_out) try {
+  PH_REQUIRE(method == kPlage || method == kZscore, "debug_plage_sharded: method = %d", method);
+  const Operands x{Xp, Xi, X_or_x, g, n, Gp, Gi, m};
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  method == kPlage ? plage_call(x, tol, maxit, S_out, info_out, load_out) : zscore_call(x, S_out, info_out));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_gsea_sharded_on_one_device(int device, int nshards, int fail_shard, const double* stat, const double* weight,

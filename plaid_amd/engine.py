@@ -454,6 +454,39 @@ def rankcor_finish(n, T1, T2, k, A) -> np.ndarray:
     return out
 
 
+PLAGE_MAX_SET = 4096   # PLAIDHIP_PLAGE_MAX_SET
+PLAGE_COLUMNS = ("size", "lambda", "explained", "iterations", "residual", "converged")
+PLAGE_TOL = 2.0 ** -40
+
+
+def _plage(fn, head, X, Gp, Gi, tol=PLAGE_TOL, maxit=1000, loadings=False, csc=None):
+    """plaidhip_plage / _csc / _multi / the hook: (S, info[, loadings]) -- sets x samples, sets x 6 (PLAGE_COLUMNS) and the
+    Gp[m] loadings in the sets' own segments of G.  csc: the entry takes the slots (True), a dense X alone (False), or
+    either (None: the _multi form)"""
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    info = np.full((m, 6), np.nan, dtype=np.float64, order="F")
+    L = np.full(int(Gp[-1]), np.nan, dtype=np.float64) if loadings else None
+    S = _score(fn, head, X, Gp, Gi, float(tol), int(maxit), post=(_np_ptr(info), None if L is None else _np_ptr(L)),
+               dense=csc is False)
+    return (S, info, L) if loadings else (S, info)
+
+
+def _zscore(fn, head, X, Gp, Gi, csc=None):
+    """plaidhip_zscore / _csc / _multi / the hook: (S, size) -- sets x samples and the sets' effective sizes"""
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    size = np.full(len(Gp) - 1, np.nan, dtype=np.float64)
+    S = _score(fn, head, X, Gp, Gi, post=(_np_ptr(size),), dense=csc is False)
+    return S, size
+
+
+def _is_sparse(X):
+    """whether _x_args would hand the entry the slots of a CSC matrix (a scipy sparse matrix, or _slots())"""
+    if isinstance(X, tuple):
+        return X[0] is not None
+    return not isinstance(X, np.ndarray) and hasattr(X, "tocsc")
+
+
 LIMMA_MAX_COEF = 32   # PLAIDHIP_LIMMA_MAX_COEF
 LIMMA_COLUMNS = ("logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2")
 LIMMA_HYPER = ("df.residual", "df.prior", "s2.prior", "n.ok")
@@ -965,6 +998,20 @@ class Context:
         universe sizes n"""
         return _rankcor(self.lib.plaidhip_rankcor, (self.handle,), stat, Gp, Gi, use_rank, ties)
 
+    def plage(self, X, Gp, Gi, tol=PLAGE_TOL, maxit=1000, loadings=False):
+        """plaidhip_plage / plaidhip_plage_csc: PLAGE (the first right singular vector of every set's standardized block,
+        oriented as include/plaidhip.h pins it); X dense or scipy CSC.  (S, info[, loadings]): sets x samples, sets x 6
+        (PLAGE_COLUMNS), and the Gp[m] loadings"""
+        sparse = _is_sparse(X)
+        fn = self.lib.plaidhip_plage_csc if sparse else self.lib.plaidhip_plage
+        return _plage(fn, (self.handle,), X, Gp, Gi, tol, maxit, loadings, csc=sparse)
+
+    def zscore(self, X, Gp, Gi):
+        """plaidhip_zscore / plaidhip_zscore_csc: the combined z-score of every set; X dense or scipy CSC.  (S, size)"""
+        sparse = _is_sparse(X)
+        fn = self.lib.plaidhip_zscore_csc if sparse else self.lib.plaidhip_zscore
+        return _zscore(fn, (self.handle,), X, Gp, Gi, csc=sparse)
+
     def gsea_permutations(self, g: int, nperm: int, seed=1) -> np.ndarray:
         """plaidhip_gsea_permutations: the genes x nperm int32 placements plaidhip_gsea generates from `seed`"""
         P = np.empty((int(g), int(nperm)), dtype=np.int32, order="F")
@@ -1157,6 +1204,17 @@ def fisher_multi(sig, Gp, Gi, overlap=False, devices=1):
 def rankcor_multi(stat, Gp, Gi, use_rank=True, ties="average", devices=1):
     """plaid.rankcor (Context.rankcor) with the lists shared out over `devices`: the one-device bits"""
     return _rankcor(*_multi("rankcor", devices), stat, Gp, Gi, use_rank, ties)
+
+
+def plage_multi(X, Gp, Gi, tol=PLAGE_TOL, maxit=1000, loadings=False, devices=1):
+    """replaid.plage (Context.plage) with the sample columns shared out over `devices`; every device takes all of X and
+    forms every set's eigenvector: the one-device bits"""
+    return _plage(*_multi("plage", devices), X, Gp, Gi, tol, maxit, loadings)
+
+
+def zscore_multi(X, Gp, Gi, devices=1):
+    """replaid.zscore (Context.zscore) with the sample columns shared out over `devices`: the one-device bits"""
+    return _zscore(*_multi("zscore", devices), X, Gp, Gi)
 
 
 def limma_multi(A, design, use=None, contrasts=None, devices=1):

@@ -796,6 +796,68 @@ replaid.gsva.exact <- function(X, matG, tau = 1, rowtf = c("z", "ecdf", "none", 
   S
 }
 
+## GSVA's method = "plage" (Tomfohr et al. 2005), the third of the four methods of the reference's gset.gsva
+## (experiments/R/functions.R:148-160): per set the first right singular vector of the standardized expression block of its
+## genes -- svd(Z_s)$v[, 1], the set's "activity" across the samples.  include/plaidhip.h (plaidhip_plage) pins it: genes
+## standardized over all samples as scale() does (no 1e-8), constant genes left out of every set, a gene holding NA / Inf
+## making its sets NA; the eigenvector by power iteration from the largest column of Z_s Z_s' (tol, maxit: its stop test and
+## step cap).  The sign, arbitrary in LAPACK and so in GSVA, is pinned: the score rises when the set's genes rise on average
+## (a balanced pair: its first gene is positive).  Sets with fewer than minSize or more than maxSize aligned members are
+## dropped; sets above 4,096 members are not offered.  Returns the sets x samples scores with attribute "info": sets x (size,
+## lambda, explained, iterations, residual, converged); loadings = TRUE adds attribute "loadings", a named list of the sets'
+## loadings over their aligned genes (0 for a dropped constant gene).  options(plaidhip.devices = ...) shards the samples;
+## every device takes all of X.
+replaid.plage <- function(X, matG, minSize = 1, maxSize = NULL, tol = 2^-40, maxit = 1000L, loadings = FALSE) {
+  if (!is.null(maxSize) && maxSize > 4096L) stop("replaid.plage: maxSize = ", maxSize, " (at most 4096 members)")
+  tol <- as.double(tol)
+  if (length(tol) != 1L || is.na(tol) || tol <= 0) stop("replaid.plage: tol = ", tol, " (a positive number)")
+  maxit <- as.integer(maxit)
+  if (length(maxit) != 1L || is.na(maxit) || maxit < 1L) stop("replaid.plage: maxit = ", maxit, " (at least 1)")
+  if (ncol(X) < 2L) stop("plage: ", ncol(X), " samples (at least 2)")
+  gg <- intersect(rownames(matG), rownames(X))
+  if (length(gg) == 0L) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
+  size <- Matrix::colSums(matG[gg, , drop = FALSE] != 0)
+  keep <- size >= minSize & (if (is.null(maxSize)) TRUE else size <= maxSize)
+  if (any(size[keep] > 4096L)) stop("replaid.plage: a set of ", max(size[keep]), " members (at most 4096; set maxSize)")
+  matG <- matG[, keep, drop = FALSE]
+  pat <- .aligned_pattern(X, matG)
+  .session()
+  if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
+  xa <- .x_args(X)
+  r <- .Call("R_plaidhip_plage", .devices(), xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, tol, maxit,
+             isTRUE(as.logical(loadings)), PACKAGE = "plaidhip")
+  S <- r[[1]]
+  dimnames(S) <- list(colnames(matG), colnames(X))
+  info <- r[[2]]
+  dimnames(info) <- list(colnames(matG), c("size", "lambda", "explained", "iterations", "residual", "converged"))
+  attr(S, "info") <- info
+  if (isTRUE(as.logical(loadings))) {
+    L <- lapply(seq_len(ncol(matG)), function(j) {
+      seg <- seq_len(pat$Gp[j + 1L] - pat$Gp[j]) + pat$Gp[j]
+      stats::setNames(r[[3]][seg], rownames(X)[pat$Gi[seg] + 1L])
+    })
+    names(L) <- colnames(matG)
+    attr(S, "loadings") <- L
+  }
+  S
+}
+
+## GSVA's method = "zscore" (Lee et al. 2008), the fourth: the sum of a set's standardized genes over the square root of
+## their number.  include/plaidhip.h (plaidhip_zscore) pins it: the standardization of replaid.plage; a set without a kept
+## gene scores NA, and so does every set holding a gene with NA / Inf.  Returns sets x samples.
+## options(plaidhip.devices = ...) shards the samples; every device takes all of X.
+replaid.zscore <- function(X, matG) {
+  if (ncol(X) < 2L) stop("zscore: ", ncol(X), " samples (at least 2)")
+  pat <- .aligned_pattern(X, matG)
+  if (is.null(pat)) { message("[plaid] ERROR. No overlapping features."); return(NULL) }
+  .session()
+  if (methods::is(X, "sparseMatrix")) X <- methods::as(X, "generalMatrix")
+  xa <- .x_args(X)
+  S <- .Call("R_plaidhip_zscore", .devices(), xa[[1]], xa[[2]], xa[[3]], nrow(X), ncol(X), pat$Gp, pat$Gi, PACKAGE = "plaidhip")
+  dimnames(S) <- list(colnames(matG), colnames(X))
+  S
+}
+
 ## singscore's normalised score and dispersion -- replaid.sing (R/plaid.R:213-219) returns mean(rank) / N - 0.5, which
 ## orders the samples as singscore does and nothing more.  The formulas follow singscore's rankGenes and singscoring AS
 ## RECALLED (the package's source is not in this tree); include/plaidhip.h (plaidhip_sing_exact) pins them: per sample

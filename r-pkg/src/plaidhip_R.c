@@ -706,6 +706,52 @@ SEXP R_plaidhip_rankcor(SEXP devices, SEXP stat, SEXP Gp, SEXP Gi, SEXP use_rank
   return res;
 }
 
+/* replaid.plage(): list(S, info, loadings) of plaidhip_plage -- S m x n, info m x 6 (size, lambda, explained, iterations,
+ * residual, converged), loadings Gp[m] doubles in the sets' own segments of G (NULL unless asked).  Xp / Xi NULL: a dense
+ * X.  One device: plaidhip_plage or plaidhip_plage_csc on the session's context; several: the _multi entry */
+SEXP R_plaidhip_plage(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi, SEXP tol, SEXP maxit,
+                      SEXP loadings) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n), gg = Rf_asInteger(g), want = Rf_asLogical(loadings) == 1;
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  SEXP info = PROTECT(Rf_allocMatrix(REALSXP, m, 6));
+  SEXP load = PROTECT(want ? Rf_allocVector(REALSXP, INTEGER(Gp)[m]) : R_NilValue);
+  SET_VECTOR_ELT(res, 0, S);
+  SET_VECTOR_ELT(res, 1, info);
+  SET_VECTOR_ELT(res, 2, load);
+  double* L = want ? REAL(load) : NULL;
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_plage_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv), gg, nn, INTEGER(Gp),
+                              INTEGER(Gi), m, Rf_asReal(tol), Rf_asInteger(maxit), REAL(S), REAL(info), L);
+  else if (int_or_null(Xp) != NULL)
+    rc = plaidhip_plage_csc(ctx(), INTEGER(Xp), int_or_null(Xi), REAL(Xv), gg, nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(tol),
+                            Rf_asInteger(maxit), REAL(S), REAL(info), L);
+  else
+    rc = plaidhip_plage(ctx(), REAL(Xv), gg, nn, INTEGER(Gp), INTEGER(Gi), m, Rf_asReal(tol), Rf_asInteger(maxit), REAL(S),
+                        REAL(info), L);
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(4);
+  return res;
+}
+
+/* replaid.zscore(): the m x n scores of plaidhip_zscore; the dispatch of R_plaidhip_plage */
+SEXP R_plaidhip_zscore(SEXP devices, SEXP Xp, SEXP Xi, SEXP Xv, SEXP g, SEXP n, SEXP Gp, SEXP Gi) {
+  const int m = LENGTH(Gp) - 1, nn = Rf_asInteger(n), gg = Rf_asInteger(g);
+  SEXP S = PROTECT(Rf_allocMatrix(REALSXP, m, nn));
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_zscore_multi(INTEGER(devices), LENGTH(devices), int_or_null(Xp), int_or_null(Xi), REAL(Xv), gg, nn, INTEGER(Gp),
+                               INTEGER(Gi), m, REAL(S), NULL);
+  else if (int_or_null(Xp) != NULL)
+    rc = plaidhip_zscore_csc(ctx(), INTEGER(Xp), int_or_null(Xi), REAL(Xv), gg, nn, INTEGER(Gp), INTEGER(Gi), m, REAL(S), NULL);
+  else
+    rc = plaidhip_zscore(ctx(), REAL(Xv), gg, nn, INTEGER(Gp), INTEGER(Gi), m, REAL(S), NULL);
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(1);
+  return S;
+}
+
 static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_session", (DL_FUNC)&R_plaidhip_session, 2},
     {"R_plaidhip_plaid_dense", (DL_FUNC)&R_plaidhip_plaid_dense, 5},
@@ -752,6 +798,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
     {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
     {"R_plaidhip_rankcor", (DL_FUNC)&R_plaidhip_rankcor, 6},
+    {"R_plaidhip_plage", (DL_FUNC)&R_plaidhip_plage, 11},
+    {"R_plaidhip_zscore", (DL_FUNC)&R_plaidhip_zscore, 8},
     {NULL, NULL, 0}};
 
 void R_init_plaidhip(DllInfo* dll) {
