@@ -104,7 +104,23 @@ int plaidhip_set_stream(plaidhip_ctx* ctx, void* stream);
 enum plaidhip_option {
   PLAIDHIP_OPT_SPMM_DENSE_KERNEL = 1,  /* 0 auto (default) | 1 one-column kernel | 2 pair kernel wherever it applies |
                                           3 dense 0/1 G x bf16x3 split of X on MFMA (BASELINE config 4's "GEMM" form:
-                                          ~145x the flops of the SpMM, ~1e-7 relative; measured beside it, never default) |
+                                          ~145x the flops of the SpMM; measured beside it, never default).  NOT fp64 sums:
+                                          each value is split into three bf16 terms (24 significant bits) and summed in
+                                          fp32 on the matrix cores.  For a set of k nonzero terms with mag = sum |x| every
+                                          raw sum is within
+                                            3 k 2^-23 mag  +  (k + c) 2^-53 mag  +  3 k 2^-126
+                                          of the exact sum (3 k fp32 additions of one ulp each, the split's 2^-24 inside
+                                          them; the c fp64 roundings of the epilogue; fp32 / bf16 subnormals, which may be
+                                          flushed); tests/helpers/mfma_ref.py derives it, tests/test_gpu_mfma.py holds the
+                                          kernels to it.  Range: the fp32 sums overflow to +-Inf where a partial sum
+                                          passes 3.4e38, so sum |x| over a set has to stay below 2^127.  NaN and +-Inf
+                                          reach exactly the scores of the sets that hold their gene, as on the fp64
+                                          kernels (flag words included; +Inf and -Inf in one set give NaN): they, and a
+                                          finite |x| >= (2 - 2^-8) 2^127 = 3.39e38 whose bf16 head would be Inf, never
+                                          enter the matrix core but are added to their sets' scores in fp64 by a kernel
+                                          enqueued behind it -- such a finite value counts as the fp64 number it is, not
+                                          as Inf.  No host synchronisation is added: the call stays capturable.
+                                          Every dense scorer entry of the context takes this route while it is set |
                                           4 as 0, but the pair kernel always in its 1,024-thread form with the slice
                                           partial sums in a scratch, also where the collection qualifies for the
                                           768-thread form that keeps them in registers (more than 10,224 genes and at most

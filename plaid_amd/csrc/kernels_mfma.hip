@@ -6,9 +6,27 @@
 // config 4 names, parity-checked against the SpMM route, so that its rate can be put beside the SpMM time
 // (bench.py c4 block): it loses by the factor the arithmetic says.
 //
-//   * W (fp64) is split into three bf16 terms, W = hi + mid + lo (24 significant bits, ~6e-8 relative: inside the
-//     1e-5 bar); three MFMA products accumulate into the same fp32 tile.  Sums of <= 500 products of magnitude <= 1
-//     keep ~1e-7 relative in fp32.
+//   * W (fp64) is split into three bf16 terms, W = hi + mid + lo (24 significant bits: |W - hi - mid - lo| <= 2^-24 |W|);
+//     three MFMA products accumulate into the same fp32 tile.  CONTRACT (include/plaidhip.h, DESIGN.md section 4.4;
+//     tests/helpers/mfma_ref.py derives it, tests/test_gpu_mfma.py holds the kernels to it): for a set of k nonzero terms
+//     with mag = sum |x| every raw sum is within
+//         3 k 2^-23 mag  +  (k + c) 2^-53 mag  +  3 k 2^-126
+//     of the exact sum (3 k fp32 additions of one ulp each, the split's 2^-24 inside them; the c fp64 roundings of the
+//     epilogue; fp32 / bf16 subnormals).  The fp32 tile overflows where a partial sum passes 3.4e38: sum |x| over a set
+//     has to stay below 2^127.
+//   * What the split cannot carry never enters the bf16 operand: NaN, +-Inf and a finite x whose bf16 head rounds to
+//     Inf (|x| >= (2 - 2^-8) 2^127 = 3.39e38; "unsplittable").  G is DENSE 0/1 here, so 0 * NaN = 0 * Inf = NaN inside
+//     the matrix core would reach EVERY set of the sample, not only the sets that hold the gene, and hi = Inf makes
+//     mid = Inf - Inf = NaN.  split3_bf16_kernel stages such a value as 0 and marks its sample (one word per sample and
+//     one for the panel, in the workspace behind the planes); mfma_fixup_kernel, enqueued behind the MFMA kernel, returns
+//     at once on an unmarked panel and otherwise adds the staged-out values of a marked sample in fp64, in gene order, to
+//     exactly the scores of the sets that hold their genes, one thread per (set, sample): NaN, +Inf, -Inf and
+//     Inf - Inf = NaN land where the fp64 route puts them, a finite unsplittable value is added as the fp64 value it is.
+//     The MFMA kernel publishes into three private flag words behind the marks; the fix-up passes them on to the
+//     caller's words on an unmarked panel and otherwise takes the flags from the final scores of the whole panel (a
+//     staged-out value scores 0 in a singleton: has_zero would be wrong).  The MFMA kernel itself is untouched by all
+//     this.  No list, hence no capacity: a marked sample's column of X is read again, 256 genes at a time.  No host
+//     synchronisation: the call stays capturable.
 //   * tile (round 5): 256 samples x 256 sets per 512-thread workgroup, one per CU; eight wavefronts in 2 x 4, each
 //     128 samples x 64 sets = 4 x 2 MFMA tiles of v_mfma_f32_32x32x16_bf16 (128 accumulator registers).  Samples are
 //     the MFMA rows and sets the columns, so that a lane of the accumulator tile is a set: 32 lanes store 32
@@ -35,17 +53,30 @@ constexpr int kMfmaRowB = 80;    // bytes per LDS row: 32 bf16 + 16 bytes of pad
 constexpr int kMfmaGkPad = 64;   // the gene dimension of the bf16 operands is padded to a multiple of this
 constexpr int kMfmaStageB = 4 * kMfmaTile * kMfmaRowB;   // W hi / mid / lo, G: 81,920 bytes per stage
 
-// X (fp64, column-major genes x samples: a sample's genes are contiguous) -> three bf16 matrices [rows_pad][gk]
+// the bf16 head of x, and whether x survives the split: not NaN, +-Inf, or a finite value whose head rounds to Inf
+__device__ __forceinline__ bool mfma_splittable(double x, __bf16* hi) {
+  *hi = (__bf16)(float)x;
+  return fabsf((float)*hi) <= 3.40282346638528859812e38f;   // (false for NaN)
+}
+
+// X (fp64, column-major genes x samples: a sample's genes are contiguous) -> three bf16 matrices [rows_pad][gk];
+// spec[c] = 1 for a sample with an unsplittable value (staged as 0), spec[rows_pad] = 1 if there is any (zeroed before)
 __global__ void __launch_bounds__(256)
 split3_bf16_kernel(const double* __restrict__ X, int64_t ldx, int32_t g, int32_t gk, int32_t ncols, int32_t rows_pad,
-                   __bf16* __restrict__ W3) {
+                   __bf16* __restrict__ W3, uint32_t* __restrict__ spec) {
   const int64_t plane = (int64_t)rows_pad * gk;
   for (int c = blockIdx.y; c < rows_pad; c += gridDim.y) {
     const double* xc = X + (int64_t)c * ldx;
     __bf16* w = W3 + (int64_t)c * gk;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < gk; i += gridDim.x * blockDim.x) {
       double x = (c < ncols && i < g) ? xc[i] : 0.0;
-      const __bf16 hi = (__bf16)(float)x;
+      __bf16 hi;
+      if (!mfma_splittable(x, &hi)) {   // (only a value read from X: the padding is 0)
+        x = 0.0;
+        hi = (__bf16)0.0f;
+        spec[c] = 1u;
+        spec[rows_pad] = 1u;
+      }
       x -= (double)(float)hi;
       const __bf16 mid = (__bf16)(float)x;
       x -= (double)(float)mid;
@@ -219,6 +250,80 @@ crossprod_mfma_bf16x3_kernel(MfmaArgs a) {
   publish_flags_mfma(f, a.flags);
 }
 
+// The values split3_bf16_kernel staged out, added in fp64 behind the MFMA kernel (file header).  Workgroup (bx, c): sets
+// 256 bx ... of sample c, samples grid-strided; 256 genes of the sample's column at a time are tested again, the
+// unsplittable ones compacted into LDS IN GENE ORDER (wavefront ballots: no atomics, a fixed order of additions), and
+// every thread adds those its set holds (the dense G is the membership test).  Thread (set, sample) alone writes its score.
+// spec: [0, rows_pad) the marks, [rows_pad] any mark, [rows_pad + 1, rows_pad + 4) the MFMA kernel's flag words.
+__global__ void __launch_bounds__(256)
+mfma_fixup_kernel(const double* __restrict__ X, int64_t ldx, int32_t g, int32_t gk, int32_t ncols, int32_t rows_pad,
+                  int32_t m, const __bf16* __restrict__ Gd, const double* __restrict__ w, int32_t stat, double alpha,
+                  const double* __restrict__ alpha_div, double* __restrict__ S, int64_t lds,
+                  const uint32_t* __restrict__ spec, uint32_t* flags) {
+  if (spec[rows_pad] == 0u) {   // (the whole grid: nothing was staged out, the MFMA kernel's flag words stand)
+    if (flags != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3 && spec[rows_pad + 1 + threadIdx.x] != 0u &&
+        __hip_atomic_load(&flags[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+      __hip_atomic_store(&flags[threadIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+  __shared__ double s_val[256];
+  __shared__ int32_t s_gene[256];
+  __shared__ int32_t s_cnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int j = blockIdx.x * 256 + tid;
+  const double al = (alpha_div != nullptr) ? alpha / *alpha_div : alpha;
+  const double wj = (j < m && stat == PLAIDHIP_STAT_MEAN) ? w[j] : 1.0;
+  uint32_t f = 0;
+  for (int c = blockIdx.y; c < ncols; c += gridDim.y) {
+    const double* xc = X + (int64_t)c * ldx;
+    double sp = 0.0;
+    bool hit = false;
+    const int gc = (spec[c] != 0u) ? g : 0;   // (uniform over the workgroup; an unmarked sample only gives its flags)
+    for (int i0 = 0; i0 < gc; i0 += 256) {
+      const int i = i0 + tid;
+      const double x = (i < gc) ? xc[i] : 0.0;
+      __bf16 hi;
+      const bool out = !mfma_splittable(x, &hi);
+      const unsigned long long mask = __ballot(out);
+      if (lane == 0) s_cnt[wv] = __popcll(mask);
+      __syncthreads();
+      int base = 0, total = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int cq = s_cnt[q];
+        base += (q < wv) ? cq : 0;
+        total += cq;
+      }
+      if (out) {
+        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+        s_gene[pos] = i;
+        s_val[pos] = x;
+      }
+      __syncthreads();
+      if (j < m) {
+        const __bf16* grow = Gd + (int64_t)j * gk;
+        for (int e = 0; e < total; ++e)
+          if ((float)grow[s_gene[e]] != 0.0f) {
+            sp += s_val[e];
+            hit = true;
+          }
+      }
+      __syncthreads();   // (the next 256 genes overwrite the list)
+    }
+    if (j < m) {
+      double v = S[(int64_t)c * lds + j];
+      if (hit) {
+        v += al * (sp * wj);
+        S[(int64_t)c * lds + j] = v;
+      }
+      f |= (v < 0.0) ? PLAIDHIP_FLAG_HAS_NEG : 0u;
+      f |= (v == 0.0) ? PLAIDHIP_FLAG_HAS_ZERO : 0u;
+      f |= (v != v) ? PLAIDHIP_FLAG_HAS_NAN : 0u;
+    }
+  }
+  publish_flags_mfma(f, flags);
+}
+
 // dense 0/1 membership, sets x genes, bf16, built on first use from the pattern kept with the gene-set collection
 static int ensure_dense_g(plaidhip_ctx* ctx, plaidhip_geneset* gs) {
   // the lazily built matrix is the one mutable part of a prepared collection: built into local pointers, published
@@ -260,14 +365,18 @@ int launch_spmm_mfma_f64(plaidhip_ctx* ctx, plaidhip_geneset* gs, const double* 
   // sample panels of at most 8,192 columns: the split operand costs 6 bytes per value
   const int32_t panel = 8192;
   const int32_t prow = ((n < panel ? n : panel) + kMfmaTile - 1) / kMfmaTile * kMfmaTile;
-  rc = ensure_workspace(ctx, (size_t)3 * prow * gk * 2);
+  const size_t planes_b = (size_t)3 * prow * gk * 2;   // (a multiple of 98,304)
+  rc = ensure_workspace(ctx, planes_b + (size_t)(prow + 4) * 4);
   if (rc != PLAIDHIP_OK) return rc;
   __bf16* W3 = reinterpret_cast<__bf16*>(ctx->ws);
+  // marks of the staged-out values: one per sample, one for the panel; then the MFMA kernel's three flag words
+  uint32_t* spec = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(ctx->ws) + planes_b);
   for (int32_t c0 = 0; c0 < n; c0 += panel) {
     const int32_t nc = (n - c0) < panel ? (n - c0) : panel;
     const int32_t rows_pad = (nc + kMfmaTile - 1) / kMfmaTile * kMfmaTile;
+    PH_HIP(hipMemsetAsync(spec, 0, (size_t)(rows_pad + 4) * 4, ctx->stream));
     hipLaunchKernelGGL(split3_bf16_kernel, dim3((gk + 255) / 256, rows_pad < 4096 ? rows_pad : 4096), dim3(256), 0, ctx->stream,
-                       X + (int64_t)c0 * ldx, ldx, gs->g, gk, nc, rows_pad, W3);
+                       X + (int64_t)c0 * ldx, ldx, gs->g, gk, nc, rows_pad, W3, spec);
     MfmaArgs a{};
     a.W3 = W3;
     a.Gd = reinterpret_cast<const __bf16*>(gs->d_dense_g);
@@ -283,10 +392,14 @@ int launch_spmm_mfma_f64(plaidhip_ctx* ctx, plaidhip_geneset* gs, const double* 
     a.alpha_div = alpha_div;
     a.S = S + (int64_t)c0 * lds;
     a.lds = lds;
-    a.flags = flags;
+    a.flags = (flags != nullptr) ? spec + rows_pad + 1 : nullptr;   // (private words: mfma_fixup_kernel publishes)
     const int mt = (gs->m + kMfmaTile - 1) / kMfmaTile;
     PH_FULL_LDS(ctx, (&crossprod_mfma_bf16x3_kernel));
     hipLaunchKernelGGL(crossprod_mfma_bf16x3_kernel, dim3(mt, rows_pad / kMfmaTile), dim3(512), 2 * kMfmaStageB, ctx->stream, a);
+    // the staged-out values, in fp64, to the sets that hold them: returns at once on a panel without any
+    hipLaunchKernelGGL(mfma_fixup_kernel, dim3((gs->m + 255) / 256, nc < 64 ? nc : 64), dim3(256), 0, ctx->stream,
+                       X + (int64_t)c0 * ldx, ldx, gs->g, gk, nc, rows_pad, gs->m, a.Gd, a.w, stat, alpha, alpha_div,
+                       a.S, lds, spec, flags);
   }
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
