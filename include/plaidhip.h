@@ -939,7 +939,8 @@ int plaidhip_contrast_tile(void);   /* PLAIDHIP_CONTRAST_TILE of the built libra
  * argument errors of plaidhip_gsea_scored, in this order: score_type outside 0..2, exactly one of le_len / le_idx null,
  * then those above.  Under plaidhip_gsea_scored_multi the edges are formed once, on the first device, after the reduction;
  * every sharding returns the one-device bits of out, null_out, le_len and le_idx.
- * Not offered: fgsea's multilevel p-values (the smallest pval is 1 / (nperm + 1)). */
+ * Not offered: fgsea's multilevel p-values by these entries themselves (their smallest pval is 1 / (nperm + 1));
+ * plaidhip_gsea_multilevel, below, adds them. */
 #define PLAIDHIP_GSEA_PERM_BLOCK 64
 #define PLAIDHIP_GSEA_STD 0
 #define PLAIDHIP_GSEA_POS 1
@@ -958,6 +959,76 @@ int plaidhip_gsea_scored_multi(const int* devices, int ndev, const double* stat,
                                uint64_t seed, int score_type, double* out, double* null_out, int32_t* le_len,
                                int32_t* le_idx);
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out);
+
+/* plaid.gsea(multilevel = TRUE): p-values below 1 / (nperm + 1) by adaptive multilevel splitting with a one-gene Metropolis
+ * move (the method of fgsea's multilevel routine, Korotkevich et al.).  fgsea's source is not in this tree: the estimator is
+ * pinned here, operation for operation, and tested against these words and against exhaustive enumeration (DESIGN.md
+ * section 23).  It has fgsea's reading -- pval, log2err -- not fgsea's bits.
+ * Level function.  A RULER belongs to one (list l, side, set size k).  Positive side: ES > 0 under std, or pos; negative
+ * side: ES < 0 under std, or neg.  A state is a k-subset S of the positions 0..N-1 of list l's observed placement; its
+ * score h(S) is formed by the operations above over the list's Wpos (the B == 0 rule included):
+ *     pos: maxP(S)     neg: -minP(S)     std, positive side: ES(S)     std, negative side: -ES(S)
+ * The target of a set is gamma = |ES|.  A std set with ES == 0, or a NaN pair, has no ruler (its ml_out row is NaN).
+ * Random numbers: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (x, i, k, tag), i the sample slot and
+ * tag = 0x80000000 | (l << 1) | side, l < 2^30: the high bit keeps the stream apart from the placements' counters
+ * (i, b, 0, 0).  An integer in 0..R-1 from a word o is ((uint64)o * R) >> 32; a value's probability differs from 1 / R by
+ * at most 2^-32, a relative bias of at most R / 2^32 (2^-15 at R = 131,072).
+ * Initial states.  The sample size n is odd, 3 <= n <= PLAIDHIP_GSEA_ML_MAX_SAMPLE.  Draw d = 0, 1, ... of slot i is word
+ * (d & 3) of the counter with x = 0x80000000 | (d >> 2), mapped to 0..N-1.  T0 = the first min(k, N - k) distinct values
+ * of that sequence; S_i = T0 if 2 k <= N, otherwise its complement.
+ * Stage l = 0, 1, ..., with P_0 = 1.0:
+ *     1. m_l = the (n + 1) / 2-th smallest of h_0..h_{n-1};  2. s_l = #{h_i > m_l} (strictly: the levels rise strictly)
+ *     3. the stage's n scores are recorded
+ *     4. the ruler ends REACHED if m_l >= gamma_max, the largest target of its sets;  5. otherwise STALLED if s_l == 0
+ *     6. otherwise P_{l+1} = P_l * ((double)s_l / (double)n), and it ends at the FLOOR if P_{l+1} < eps or
+ *        l + 1 == PLAIDHIP_GSEA_ML_MAX_STAGES
+ *     7. otherwise the j-th slot (in slot order) with h_i <= m_l takes a copy of the (j mod s_l)-th survivor in slot order
+ *     8. every slot, survivors too, makes T = sweeps * k proposals (sweeps in 1..32).  Proposal `step` of slot i reads
+ *        words o0, o1 of the counter with x = l * T + step (below 2^31):  a = (o0 * k) >> 32,  b = (o1 * N) >> 32.
+ *        p_a = the a-th member of S_i in ascending position (0-based).  If bit b is set (b == p_a included) nothing moves;
+ *        otherwise S' = S_i - {p_a} + {b} is taken iff h(S') > m_l.
+ * Read-off of a set with target gamma: l* = the first stage with m_l >= gamma, or the last stage if there is none;
+ * c = #{h_i of stage l* >= gamma}, c' = max(c, 1);
+ *     qhat = P_{l*} * ((double)c' / (double)n)
+ *     status = PLAIDHIP_GSEA_ML_ESTIMATED if a stage with m_l >= gamma existed, otherwise the ruler's end, _FLOOR or
+ *              _STALLED, and qhat is then an upper bound
+ *     log2err = sqrt(sum_{j < l*} (n - s_j) / ((double)n * s_j) + (n - c') / ((double)n * c')) / ln 2, the terms added
+ *               in the order of j from 0.0, the last term last; formed on the host
+ * A set's row depends on its own gamma, k, list, side and the seed, never on the sets that share its ruler.
+ * The table: the permutation pass of plaidhip_gsea_scored runs unchanged (out, null_out, the edges), then
+ *     denom = (1 + nGeZero) / (1 + nperm) on the positive side, (1 + nLeZero) / (1 + nperm) on the negative side
+ *     pvalML = min(1, qhat / denom)
+ *     pval (reported) = the permutation one where nMoreExtreme >= ml_min or the pair has no ruler, pvalML otherwise
+ *     padj = Benjamini-Hochberg over the reported pval
+ * ml_min = 0 returns plaidhip_gsea_scored's twelve columns bit for bit.
+ * ml_out: m x 6 x c: pvalML, log2err, l*, status, qhat, denom.
+ * plaidhip_gsea_ruler runs ONE ruler (one list: stat and weight are g long; k; the list's number l for the counter; side)
+ * to the caller's gamma and returns its trace: *nstages, *end_status (PLAIDHIP_GSEA_ML_ESTIMATED for REACHED, _FLOOR,
+ * _STALLED), m_out and s_out (PLAIDHIP_GSEA_ML_MAX_STAGES each) and h_out (MAX_STAGES x n, stage-major), filled for the
+ * stages run.  It is to the chains what plaidhip_gsea_permutations is to the null.
+ * Argument errors, in this order and before any device work: sample_size even or outside 3..PLAIDHIP_GSEA_ML_MAX_SAMPLE,
+ * sweeps outside 1..32, eps not in [0, 1), ml_min < 0, c >= 2^30, a null ml_out, then plaidhip_gsea_scored's.
+ * plaidhip_gsea_ruler: those of the first three, then side outside 0..1 (or against a pos / neg score type), l outside
+ * 0..2^30-1, k outside 1..g-1, gamma NaN, then score_type, g and the weights as above.
+ * plaidhip_gsea_multilevel_multi shares the rulers out as whole rulers (plaidhip_shard_bounds over the ruler list, which is
+ * sorted by list, side and k); the read-off meets on the first device's thread: every sharding returns the one-device bits. */
+#define PLAIDHIP_GSEA_ML_MAX_STAGES 256
+#define PLAIDHIP_GSEA_ML_MAX_SAMPLE 1023
+#define PLAIDHIP_GSEA_ML_ESTIMATED 0
+#define PLAIDHIP_GSEA_ML_FLOOR 1
+#define PLAIDHIP_GSEA_ML_STALLED 2
+int plaidhip_gsea_multilevel(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c,
+                             const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
+                             int score_type, int32_t sample_size, int32_t sweeps, double eps, int32_t ml_min, double* out,
+                             double* null_out, int32_t* le_len, int32_t* le_idx, double* ml_out);
+int plaidhip_gsea_multilevel_multi(const int* devices, int ndev, const double* stat, const double* weight, int32_t g, int32_t c,
+                                   const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm,
+                                   uint64_t seed, int score_type, int32_t sample_size, int32_t sweeps, double eps,
+                                   int32_t ml_min, double* out, double* null_out, int32_t* le_len, int32_t* le_idx,
+                                   double* ml_out);
+int plaidhip_gsea_ruler(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t k, int32_t l, int side,
+                        int score_type, double gamma, uint64_t seed, int32_t sample_size, int32_t sweeps, double eps,
+                        int32_t* nstages, int32_t* end_status, double* m_out, int32_t* s_out, double* h_out);
 
 /* plaid.fisher(sig, G): over-representation analysis -- Fisher's exact (hypergeometric) test of every list of significant
  * genes against every set, in three directions.  The form is fgsea::fora / fisher.test(alternative = "greater") AS

@@ -8,7 +8,7 @@ from ._lib import PlaidHipError, device_count
 from .api import (aligned_pattern, chunked_crossprod, colranks, normalize_medians, plaid, plaid_fisher, plaid_gsea, plaid_limma, plaid_limma_contrasts, plaid_rankcor, plaid_sig, plaid_test, plaid_test_contrasts, replaid_gsva,
                   replaid_gsva_exact, replaid_plage, replaid_zscore, replaid_aucell, replaid_scse, replaid_sing, replaid_sing_exact, replaid_ssgsea, replaid_ssgsea_exact, replaid_ucell,
                   replaid_ucell_exact, replaid_aucell_exact, sparse_colranks)
-from .engine import (Context, Geneset, aucell_multi, default_context, fisher_multi, gsea_multi, limma_multi, gsva_exact_multi, gsva_kcdf_table, gsva_multi, multi_finalize, plaid_multi,
+from .engine import (Context, Geneset, aucell_multi, default_context, fisher_multi, gsea_multi, gsea_multilevel_multi, limma_multi, gsva_exact_multi, gsva_kcdf_table, gsva_multi, multi_finalize, plaid_multi,
                      plaid_test_contrasts_multi, plaid_test_multi, plage_multi, zscore_multi, rankcor_multi, scse_multi, shard_bounds, sing_exact_multi, sing_multi, ssgsea_exact_multi, ssgsea_multi,
                      ucell_multi, ucell_exact_multi, aucell_exact_multi)
 from .gmt import GmtList, gmt2mat, mat2gmt, read_gmt, write_gmt
@@ -22,7 +22,7 @@ __all__ = [
     "plaid_test", "replaid_gsva", "plaid_multi", "sing_multi", "ssgsea_multi", "ssgsea_exact_multi", "ucell_multi",
     "aucell_multi", "scse_multi", "gsva_multi", "replaid_gsva_exact", "gsva_exact_multi", "replaid_sing_exact", "sing_exact_multi", "gsva_kcdf_table",
     "plaid_test_multi", "shard_bounds", "multi_finalize", "replaid_ucell_exact", "replaid_aucell_exact", "ucell_exact_multi",
-    "aucell_exact_multi", "plaid_test_contrasts", "plaid_test_contrasts_multi", "plaid_gsea", "gsea_multi",
+    "aucell_exact_multi", "plaid_test_contrasts", "plaid_test_contrasts_multi", "plaid_gsea", "gsea_multi", "gsea_multilevel_multi",
     "plaid_fisher", "plaid_sig", "fisher_multi", "plaid_limma", "plaid_limma_contrasts", "limma_multi",
     "plaid_rankcor", "rankcor_multi", "replaid_plage", "replaid_zscore", "plage_multi", "zscore_multi",
 ]

@@ -147,6 +147,12 @@ SIGNATURES = {
     "plaidhip_gsea_scored_multi": [_vp, _int, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _int, _vp, _vp, _vp,
                                    _vp],
     "plaidhip_gsea_permutations": [_vp, _i32, _i32, C.c_uint64, _vp],
+    "plaidhip_gsea_multilevel": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _int, _i32, _i32, _f64, _i32, _vp,
+                                 _vp, _vp, _vp, _vp],
+    "plaidhip_gsea_multilevel_multi": [_vp, _int, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, C.c_uint64, _int, _i32, _i32,
+                                       _f64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_gsea_ruler": [_vp, _vp, _vp, _i32, _i32, _i32, _int, _int, _f64, C.c_uint64, _i32, _i32, _f64, _vp, _vp, _vp, _vp,
+                            _vp],
     "plaidhip_fisher": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_fisher_multi": [_vp, _int, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_hyper_tail": [_i64, _i64, _i64, _i64, _vp],

@@ -637,7 +637,8 @@ _GSEA_SCORE_TYPES = ("std", "pos", "neg")
 
 
 def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=1, perm=None, sort_by="pval",
-               ctx: Context | None = None, scoreType="std", leadingEdge=False):
+               ctx: Context | None = None, scoreType="std", leadingEdge=False, multilevel=False, sampleSize=101, eps=1e-50,
+               sweeps=4, mlMin=10):
     """plaid.gsea(): preranked GSEA (fgsea's fgseaSimple as pinned in include/plaidhip.h) of a named
     vector of statistics, or of every column of a genes x contrasts NamedMatrix, against the sets of G (a gmt or a
     membership matrix), with a permutation null of `nperm` placements generated on the device from `seed` (or the caller's
@@ -649,7 +650,11 @@ def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=
     plaid.gsea's in the R package, so the same call gives the same table in both.
     scoreType "pos" / "neg" scores one side of the walk (for a statistic of one sign, such as |logFC|, F or -log p).
     leadingEdge = True returns (table, edges) wherever a table is returned: edges is a list, one entry per table row in
-    the table's order, of the gene names that drive the set's score, in walk order."""
+    the table's order, of the gene names that drive the set's score, in walk order.
+    multilevel = True (fgsea's multilevel reading, as pinned in include/plaidhip.h: plaidhip_gsea_multilevel) replaces the
+    pval of every set that fewer than mlMin permutations matched by an adaptive multilevel splitting estimate from
+    sampleSize chains (odd), `sweeps` * size proposals a stage, down to about eps; padj is over the reported pval, and the
+    table gains a log2err column (the expected error of log2 pval; NaN where the permutation pval stands)."""
     if scoreType not in _GSEA_SCORE_TYPES:
         raise ValueError(f"plaid.gsea: scoreType must be one of {list(_GSEA_SCORE_TYPES)} (got {scoreType!r})")
     if isinstance(stats, dict):
@@ -684,19 +689,31 @@ def plaid_gsea(stats, G, nperm=1000, gseaParam=1, minSize=1, maxSize=None, seed=
         W = np.ones_like(Xs) if gp == 0.0 else (np.abs(Xs) if gp == 1.0 else np.abs(Xs) ** gp)
     W = np.where(np.isfinite(W), W, 0.0)   # (a list with a NaN or an infinity is NaN by the statistic's own rule)
     ctx = ctx or default_context()
-    out = ctx.gsea(Xs, W, Gp, Gi, perm=perm, nperm=nperm, seed=seed, score_type=scoreType, leading_edge=bool(leadingEdge))
+    cols = _GSEA_NAMES
+    if multilevel:
+        res = ctx.gsea_multilevel(Xs, W, Gp, Gi, perm=perm, nperm=nperm, seed=seed, score_type=scoreType,
+                                  leading_edge=bool(leadingEdge), sample_size=sampleSize, sweeps=sweeps, eps=eps, ml_min=mlMin)
+        out, ml = res[0], res[1]
+        used = out[:, 4, :] < int(mlMin)                      # where pvalML is the reported pval
+        out = np.concatenate([out[:, :6, :], np.where(used, ml[:, 1, :], np.nan)[:, None, :]], axis=1)
+        cols = _GSEA_NAMES + ["log2err"]
+        if leadingEdge:
+            le_len, le_idx = res[2], res[3]
+    else:
+        out = ctx.gsea(Xs, W, Gp, Gi, perm=perm, nperm=nperm, seed=seed, score_type=scoreType, leading_edge=bool(leadingEdge))
+        if leadingEdge:
+            out, le_len, le_idx = out
     if leadingEdge:
-        out, le_len, le_idx = out
         posx = _first_pos(stats.rownames)
         genes = [nm for nm in dict.fromkeys(as_named(G).rownames) if nm in posx]     # the aligned rows, as Gi numbers them
     res = {}
     for l, nm in enumerate(stats.colnames):
-        tab, names = out[:, :6, l], list(rn)
+        tab, names = out[:, :len(cols), l], list(rn)
         o = np.arange(len(names))
-        if sort_by in _GSEA_NAMES:
-            o = np.argsort(tab[:, _GSEA_NAMES.index(sort_by)], kind="stable")       # order(): NaN last
+        if sort_by in cols:
+            o = np.argsort(tab[:, cols.index(sort_by)], kind="stable")       # order(): NaN last
             tab, names = tab[o, :], [names[k] for k in o]
-        res[nm] = NamedMatrix(tab, names, _GSEA_NAMES)
+        res[nm] = NamedMatrix(tab, names, list(cols))
         if leadingEdge:
             res[nm] = (res[nm], [[genes[r] for r in le_idx[Gp[j]:Gp[j] + le_len[j, l], l]] for j in o])
     return res[stats.colnames[0]] if single and len(res) == 1 else res

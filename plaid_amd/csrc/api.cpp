@@ -1208,6 +1208,23 @@ int plaidhip_gsea_scored(plaidhip_ctx* ctx, const double* stat, const double* we
                   gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.gsea with multilevel p-values, and one ruler's trace: the same engine (multi.cpp: gsea_worker / gsea_ruler_worker,
+// kGseaMultilevel)
+int plaidhip_gsea_multilevel(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c,
+                             const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
+                             int score_type, int32_t sample_size, int32_t sweeps, double eps, int32_t ml_min, double* out,
+                             double* null_out, int32_t* le_len, int32_t* le_idx, double* ml_out) try {
+  return dispatch(on_context(ctx), gsea_multilevel_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, score_type, sample_size,
+                                                        sweeps, eps, ml_min, out, null_out, le_len, le_idx, ml_out));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_gsea_ruler(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t k, int32_t l, int side,
+                        int score_type, double gamma, uint64_t seed, int32_t sample_size, int32_t sweeps, double eps,
+                        int32_t* nstages, int32_t* end_status, double* m_out, int32_t* s_out, double* h_out) try {
+  return dispatch(on_context(ctx), gsea_ruler_call(stat, weight, g, k, l, side, score_type, gamma, seed, sample_size, sweeps, eps,
+                                                   nstages, end_status, m_out, s_out, h_out));
+} catch (...) { return plaidhip::on_exception(); }
+
 // plaid.rankcor: the one-device form of the sharded engine (multi.cpp: rankcor_worker, kRankcor)
 int plaidhip_rankcor(plaidhip_ctx* ctx, const double* stat, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
                      int use_rank, int ties, double* out, double* tot_out) try {

@@ -12,7 +12,7 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19
+  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -79,6 +79,20 @@ struct Call : Operands {
   int32_t* le_idx = nullptr;            // Gp[m] x n rows of stat, a set's edge in its own segment of G
   int gsea_weighted = 0;
   std::vector<uint32_t> listnan;
+  // plaid.gsea's multilevel p-values (kGseaMultilevel): plaid.gsea's fields and the sample size, the sweeps, eps, ml_min and
+  // ml_out (m x 6 x n).  ml_ruler: ONE ruler instead (plaidhip_gsea_ruler) -- X / weight are one list, no sets; its size,
+  // list number, side and target, and where its trace goes
+  int32_t ml_sample = 0, ml_sweeps = 0, ml_min = 0;
+  double ml_eps = 0.0;
+  double* ml_out = nullptr;
+  int ml_ruler = 0;
+  int32_t ml_k = 0, ml_l = 0, ml_side = 0;
+  double ml_gamma = 0.0;
+  int32_t* ml_nstages = nullptr;
+  int32_t* ml_end = nullptr;
+  double* ml_m = nullptr;
+  int32_t* ml_s = nullptr;
+  double* ml_h = nullptr;
   // plaid.fisher: sig (g x n int8, n = the lists; X stays null), out m x 12 x n, the 2 x n list totals, and the overlap
   // lists in le_len / le_idx (both null: none)
   const int8_t* sig = nullptr;
@@ -270,6 +284,43 @@ inline Call gsea_call(const double* stat, const double* weight, int32_t g, int32
   k.le_len = le_len;
   k.le_idx = le_idx;
   return k;
+}
+// plaid.gsea with multilevel p-values as pinned in include/plaidhip.h: plaidhip_gsea_multilevel; one ruler's trace:
+// plaidhip_gsea_ruler
+inline Call gsea_multilevel_call(const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
+                                 const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, int score_type,
+                                 int32_t sample_size, int32_t sweeps, double eps, int32_t ml_min, double* out, double* null_out,
+                                 int32_t* le_len, int32_t* le_idx, double* ml_out) {
+  Call k = gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx);
+  k.method = kGseaMultilevel;
+  k.ml_sample = sample_size;
+  k.ml_sweeps = sweeps;
+  k.ml_eps = eps;
+  k.ml_min = ml_min;
+  k.ml_out = ml_out;
+  return k;
+}
+inline Call gsea_ruler_call(const double* stat, const double* weight, int32_t g, int32_t k, int32_t l, int side, int score_type,
+                            double gamma, uint64_t seed, int32_t sample_size, int32_t sweeps, double eps, int32_t* nstages,
+                            int32_t* end_status, double* m_out, int32_t* s_out, double* h_out) {
+  Call c = make_call(kGseaMultilevel, {nullptr, nullptr, stat, g, 1, nullptr, nullptr, 0}, nullptr);
+  c.weight = weight;
+  c.seed = seed;
+  c.score_type = score_type;
+  c.ml_sample = sample_size;
+  c.ml_sweeps = sweeps;
+  c.ml_eps = eps;
+  c.ml_ruler = 1;
+  c.ml_k = k;
+  c.ml_l = l;
+  c.ml_side = side;
+  c.ml_gamma = gamma;
+  c.ml_nstages = nstages;
+  c.ml_end = end_status;
+  c.ml_m = m_out;
+  c.ml_s = s_out;
+  c.ml_h = h_out;
+  return c;
 }
 // over-representation tests as pinned in include/plaidhip.h: plaidhip_fisher
 inline Call fisher_call(const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m, double* out,

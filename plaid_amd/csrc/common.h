@@ -620,6 +620,38 @@ int launch_gsea_null(plaidhip_ctx* ctx, int weighted, int score_type, const int3
 // out (m x 12 x c; padj left NaN) from all nblk blocks of partials, added in block order
 int launch_gsea_null_reduce(plaidhip_ctx* ctx, const double* part, int32_t nblk, const double* ES, const int32_t* Gp, int32_t m,
                             int32_t c, int score_type, double* out);
+// kernels_gsea_ml.hip: plaid.gsea's multilevel p-values (include/plaidhip.h: plaidhip_gsea_multilevel).  All stream-ordered,
+// all pointers device pointers.  A ruler: one (list, side, set size) and the sets [set0, set0 + nset) of the per-set arrays.
+struct GseaMlRuler {
+  int32_t l;        // the list's Wpos on this device
+  int32_t tag;      // the list's number in the Philox counter
+  int32_t side;     // 0 positive, 1 negative
+  int32_t k;
+  int32_t set0, nset;
+  double gmax;      // the largest target of its sets
+};
+struct GseaMlState {
+  int32_t stage;    // stages recorded so far
+  int32_t ended;
+  int32_t status;   // when ended: PLAIDHIP_GSEA_ML_ESTIMATED (the level reached gmax) / _FLOOR / _STALLED
+  int32_t pad;
+  double level;     // m of the last stage recorded
+  double P;         // P of the next stage (of the last one once ended)
+};
+inline int32_t gsea_ml_map_words(int32_t g) { return (g + 63) / 64; }   // words of one slot's map in global memory
+// maps ([nr][n][gsea_ml_map_words(g)]) and H ([nr][n]) <- the initial states and their scores
+int launch_gsea_ml_init(plaidhip_ctx* ctx, int weighted, int score_type, const GseaMlRuler* rulers, int32_t nr, int32_t n,
+                        int32_t g, const double* Wpos, uint64_t seed, unsigned long long* maps, double* H);
+// one stage of every unfinished ruler: level, count, trace (s_trace, m_trace: [nr][PLAIDHIP_GSEA_ML_MAX_STAGES]; h_trace
+// nullable: [nr][MAX_STAGES][n]), read-off (gamma in; lstar, -1 before; cnt; est), end test, survivor copies; *unfinished +=
+// the rulers that go on
+int launch_gsea_ml_stage(plaidhip_ctx* ctx, const GseaMlRuler* rulers, GseaMlState* state, int32_t nr, int32_t n, int32_t g,
+                         double eps, unsigned long long* maps, double* H, int32_t* s_trace, double* m_trace, double* h_trace,
+                         const double* gamma, int32_t* lstar, int32_t* cnt, int32_t* est, uint32_t* unfinished);
+// sweeps * k proposals of every slot of every unfinished ruler against the level of the stage just recorded
+int launch_gsea_ml_mutate(plaidhip_ctx* ctx, int weighted, int score_type, const GseaMlRuler* rulers, const GseaMlState* state,
+                          int32_t nr, int32_t n, int32_t g, const double* Wpos, uint64_t seed, int32_t sweeps,
+                          unsigned long long* maps, double* H);
 // kernels_fisher.hip: plaid.fisher (include/plaidhip.h: plaidhip_fisher).  All stream-ordered, all pointers device pointers.
 // masks ([ceil(c / PLAIDHIP_FISHER_LIST_TILE)][g] u16: bit t up, bit 8 + t down in list tile * 8 + t) and tot ([c][2] int32:
 // nUp, nDn; zeroed here) of the lists in sig (g x c int8, packed)

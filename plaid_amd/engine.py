@@ -349,6 +349,48 @@ def _gsea(fn, head, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=Fa
     return res if len(res) > 1 else out
 
 
+GSEA_ML_MAX_STAGES = 256     # PLAIDHIP_GSEA_ML_MAX_STAGES
+GSEA_ML_MAX_SAMPLE = 1023    # PLAIDHIP_GSEA_ML_MAX_SAMPLE
+GSEA_ML_COLUMNS = ("pvalML", "log2err", "stage", "status", "qhat", "denom")
+GSEA_ML_STATUS = ("estimated", "floor", "stalled")   # PLAIDHIP_GSEA_ML_ESTIMATED / _FLOOR / _STALLED
+
+
+def check_gsea_ml_args(who, sample_size, sweeps, eps):
+    """the checks of the chains' own parameters, in the library's order"""
+    sample_size, sweeps, eps = int(sample_size), int(sweeps), float(eps)
+    if not (3 <= sample_size <= GSEA_ML_MAX_SAMPLE and sample_size % 2 == 1):
+        raise ValueError(f"{who}: sample_size = {sample_size} (odd, 3..{GSEA_ML_MAX_SAMPLE})")
+    if not 1 <= sweeps <= 32:
+        raise ValueError(f"{who}: sweeps = {sweeps} (1..32)")
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"{who}: eps = {eps:g} (0 <= eps < 1)")
+    return sample_size, sweeps, eps
+
+
+def _gsea_multilevel(fn, head, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, score_type="std",
+                     leading_edge=False, sample_size=101, sweeps=4, eps=1e-50, ml_min=10):
+    """plaidhip_gsea_multilevel / _multi / the hook: (out, ml[, null][, le_len, le_idx]) -- out as _gsea's with the reported
+    pval and padj, ml sets x 6 x lists (GSEA_ML_COLUMNS; NaN for a pair without a ruler)"""
+    sample_size, sweeps, eps = check_gsea_ml_args("gsea_multilevel", sample_size, sweeps, eps)
+    ml_min = int(ml_min)
+    if ml_min < 0:
+        raise ValueError(f"gsea_multilevel: ml_min = {ml_min} (at least 0)")
+    stat, weight, perm, nperm = check_gsea_args(stat, weight, perm, nperm)
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    g, c = stat.shape
+    m = len(Gp) - 1
+    out = np.full((m, 12, c), np.nan, dtype=np.float64, order="F")
+    ml = np.full((m, 6, c), np.nan, dtype=np.float64, order="F")
+    nul = np.full((m, nperm, c), np.nan, dtype=np.float64, order="F") if null else None
+    le_len = np.full((m, c), -7, dtype=np.int32, order="F") if leading_edge else None
+    le_idx = np.full((int(Gp[-1]), c), -7, dtype=np.int32, order="F") if leading_edge else None
+    check(fn(*head, _np_ptr(stat), _np_ptr(weight), g, c, _np_ptr(Gp), _np_ptr(Gi), m, None if perm is None else _np_ptr(perm),
+             nperm, int(seed) & (2**64 - 1), gsea_score_type(score_type), sample_size, sweeps, eps, ml_min, _np_ptr(out),
+             None if nul is None else _np_ptr(nul), None if le_len is None else _np_ptr(le_len),
+             None if le_idx is None else _np_ptr(le_idx), _np_ptr(ml)))
+    return (out, ml) + ((nul,) if null else ()) + ((le_len, le_idx) if leading_edge else ())
+
+
 FISHER_MAX_GENES = 1 << 26   # PLAIDHIP_FISHER_MAX_GENES
 FISHER_COLUMNS = ("size", "ovUp", "ovDn", "pUp", "pDn", "pAny", "padjUp", "padjDn", "padjAny", "orUp", "orDn", "orAny")
 
@@ -972,6 +1014,32 @@ class Context:
         return _gsea(self.lib.plaidhip_gsea_scored, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type,
                      leading_edge)
 
+    def gsea_multilevel(self, stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, score_type="std",
+                        leading_edge=False, sample_size=101, sweeps=4, eps=1e-50, ml_min=10):
+        """plaidhip_gsea_multilevel: Context.gsea with multilevel p-values where fewer than ml_min permutations were as
+        extreme: (out, ml[, null][, le_len, le_idx]) -- out sets x 12 x lists with the reported pval and padj, ml sets x 6 x
+        lists (GSEA_ML_COLUMNS: pvalML, log2err, the read-off stage, the status as an index of GSEA_ML_STATUS, qhat, denom)"""
+        return _gsea_multilevel(self.lib.plaidhip_gsea_multilevel, (self.handle,), stat, weight, Gp, Gi, perm, nperm, seed, null,
+                                score_type, leading_edge, sample_size, sweeps, eps, ml_min)
+
+    def gsea_ruler(self, stat, weight, k, l=0, side=0, score_type="std", gamma=2.0, seed=1, sample_size=101, sweeps=4, eps=1e-50):
+        """plaidhip_gsea_ruler: one ruler of one list (stat, weight: genes), set size k, list number l and side (0 positive,
+        1 negative), run to the target gamma: {"stages", "status", "m", "s", "h"} -- the levels, the counts above them and the
+        stages x sample_size scores of the stages it ran"""
+        sample_size, sweeps, eps = check_gsea_ml_args("gsea_ruler", sample_size, sweeps, eps)
+        stat, weight = np.ascontiguousarray(stat, dtype=np.float64).ravel(), np.ascontiguousarray(weight, dtype=np.float64).ravel()
+        if stat.shape != weight.shape:
+            raise ValueError("gsea_ruler: stat and weight must be one list of one length")
+        S = GSEA_ML_MAX_STAGES
+        nst, end = C.c_int32(0), C.c_int32(0)
+        m_out, s_out = np.zeros(S, dtype=np.float64), np.zeros(S, dtype=np.int32)
+        h_out = np.zeros((S, sample_size), dtype=np.float64)
+        check(self.lib.plaidhip_gsea_ruler(self.handle, _np_ptr(stat), _np_ptr(weight), len(stat), int(k), int(l), int(side),
+                                           gsea_score_type(score_type), float(gamma), int(seed) & (2**64 - 1), sample_size, sweeps,
+                                           eps, C.byref(nst), C.byref(end), _np_ptr(m_out), _np_ptr(s_out), _np_ptr(h_out)))
+        ns = nst.value
+        return {"stages": ns, "status": end.value, "m": m_out[:ns].copy(), "s": s_out[:ns].copy(), "h": h_out[:ns].copy()}
+
     def limma(self, A, design, use=None, contrasts=None):
         """plaidhip_limma: moderated t-tests of the rows of A (rows x samples) for the designs (samples x p, or x p x nfit),
         the samples `use` leaves out (samples x nfit, None: none) and the contrasts (p x q, None: every coefficient):
@@ -1194,6 +1262,14 @@ def gsea_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, 
     if gsea_score_type(score_type) == 0 and not leading_edge:
         return _gsea(*_multi("gsea", devices), stat, weight, Gp, Gi, perm, nperm, seed, null)
     return _gsea(*_multi("gsea_scored", devices), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type, leading_edge)
+
+
+def gsea_multilevel_multi(stat, weight, Gp, Gi, perm=None, nperm=1000, seed=1, null=False, devices=1, score_type="std",
+                          leading_edge=False, sample_size=101, sweeps=4, eps=1e-50, ml_min=10):
+    """plaid.gsea with multilevel p-values (Context.gsea_multilevel), the permutation blocks and the rulers shared out over
+    `devices`: the one-device bits"""
+    return _gsea_multilevel(*_multi("gsea_multilevel", devices), stat, weight, Gp, Gi, perm, nperm, seed, null, score_type,
+                            leading_edge, sample_size, sweeps, eps, ml_min)
 
 
 def fisher_multi(sig, Gp, Gi, overlap=False, devices=1):

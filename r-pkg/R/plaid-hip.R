@@ -484,8 +484,13 @@ plaid.test.contrasts <- function(X, Y, G, gsetX = NULL, tests = c("one", "two", 
 ## scoreType "pos" / "neg" scores one side of the walk (a statistic of one sign: |logFC|, F, -log p).  leadingEdge = TRUE
 ## returns, wherever a matrix is returned, list(table = <that matrix>, leadingEdge = <named list, one character vector of
 ## gene names per table row in the table's order: the genes that drive the set's score, in walk order>).
+## multilevel = TRUE (fgsea's multilevel reading, as pinned in include/plaidhip.h: plaidhip_gsea_multilevel) replaces the pval
+## of every set that fewer than mlMin permutations matched by an adaptive multilevel splitting estimate from sampleSize
+## chains (odd), sweeps * size proposals a stage, down to about eps; padj is over the reported pval and the table gains a
+## log2err column (NA where the permutation pval stands).
 plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSize = NULL, seed = 1, perm = NULL,
-                       sort.by = "pval", scoreType = c("std", "pos", "neg"), leadingEdge = FALSE) {
+                       sort.by = "pval", scoreType = c("std", "pos", "neg"), leadingEdge = FALSE, multilevel = FALSE,
+                       sampleSize = 101, eps = 1e-50, sweeps = 4, mlMin = 10) {
   scoreType <- match.arg(scoreType)
   single <- is.null(dim(stats))
   if (single) stats <- matrix(stats, ncol = 1, dimnames = list(names(stats), "stat"))
@@ -512,7 +517,15 @@ plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSi
   .session()
   edges <- isTRUE(as.logical(leadingEdge))
   le <- NULL
-  if (scoreType == "std" && !edges) {
+  ml <- NULL
+  if (isTRUE(as.logical(multilevel))) {
+    le <- .Call("R_plaidhip_gsea_multilevel", .devices(), stats, W, pat$Gp, pat$Gi, perm, as.integer(nperm),
+                as.numeric(seed %% 2^32), as.numeric((seed %/% 2^32) %% 2^32), match(scoreType, c("std", "pos", "neg")) - 1L,
+                edges, as.numeric(c(sampleSize, sweeps, eps, mlMin)), PACKAGE = "plaidhip")
+    r <- le[[1]]
+    ml <- le[[4]]
+    dim(ml) <- c(nrow(ml), 6L, ncol(stats))
+  } else if (scoreType == "std" && !edges) {
     r <- .Call("R_plaidhip_gsea", .devices(), stats, W, pat$Gp, pat$Gi, perm, as.integer(nperm), as.numeric(seed %% 2^32),
                as.numeric((seed %/% 2^32) %% 2^32), PACKAGE = "plaidhip")
   } else {
@@ -525,6 +538,7 @@ plaid.gsea <- function(stats, G, nperm = 1000, gseaParam = 1, minSize = 1, maxSi
   cols <- c("ES", "NES", "pval", "padj", "nMoreExtreme", "size")
   out <- lapply(seq_len(ncol(stats)), function(l) {
     res <- matrix(r[, 1:6, l], nrow = dim(r)[1], dimnames = list(colnames(G), cols))
+    if (!is.null(ml)) res <- cbind(res, log2err = ifelse(!is.na(r[, 5, l]) & r[, 5, l] < mlMin, ml[, 2, l], NA_real_))
     o <- if (sort.by %in% cols) order(res[, sort.by]) else seq_len(nrow(res))
     res <- res[o, , drop = FALSE]
     if (!edges) return(res)

@@ -607,6 +607,46 @@ SEXP R_plaidhip_gsea_scored(SEXP devices, SEXP stat, SEXP weight, SEXP Gp, SEXP 
   return res;
 }
 
+/* plaid.gsea(multilevel = TRUE): list(out, le_len, le_idx, ml) of plaidhip_gsea_multilevel -- the first three as
+ * R_plaidhip_gsea_scored returns them (out with the reported pval and padj), ml an m x 6c matrix (columns 6 l + 1 .. 6 l + 6:
+ * pvalML, log2err, stage, status, qhat, denom of list l).  ml_par: c(sampleSize, sweeps, eps, mlMin) */
+SEXP R_plaidhip_gsea_multilevel(SEXP devices, SEXP stat, SEXP weight, SEXP Gp, SEXP Gi, SEXP perm, SEXP nperm, SEXP seed_lo,
+                                SEXP seed_hi, SEXP score_type, SEXP edges, SEXP ml_par) {
+  const int g = Rf_nrows(stat), c = Rf_ncols(stat), m = LENGTH(Gp) - 1;
+  const int B = Rf_isNull(perm) ? Rf_asInteger(nperm) : Rf_ncols(perm);
+  const uint64_t seed = ((uint64_t)(uint32_t)Rf_asReal(seed_hi) << 32) | (uint64_t)(uint32_t)Rf_asReal(seed_lo);
+  const int want = Rf_asLogical(edges) == 1, st = Rf_asInteger(score_type);
+  if (LENGTH(ml_par) != 4) Rf_error("plaid.gsea: ml_par must be c(sampleSize, sweeps, eps, mlMin)");
+  const double* par = REAL(ml_par);
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 12 * c));
+  SEXP ml = PROTECT(Rf_allocMatrix(REALSXP, m, 6 * c));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 3, ml);
+  int32_t *le_len = NULL, *le_idx = NULL;
+  if (want) {
+    SEXP len = PROTECT(Rf_allocMatrix(INTSXP, m, c));
+    SEXP idx = PROTECT(Rf_allocMatrix(INTSXP, INTEGER(Gp)[m], c));
+    SET_VECTOR_ELT(res, 1, len);
+    SET_VECTOR_ELT(res, 2, idx);
+    le_len = INTEGER(len);
+    le_idx = INTEGER(idx);
+    UNPROTECT(2);
+  }
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_gsea_multilevel_multi(INTEGER(devices), LENGTH(devices), REAL(stat), REAL(weight), g, c, INTEGER(Gp),
+                                        INTEGER(Gi), m, int_or_null(perm), B, seed, st, (int32_t)par[0], (int32_t)par[1], par[2],
+                                        (int32_t)par[3], REAL(out), NULL, le_len, le_idx, REAL(ml));
+  else
+    rc = plaidhip_gsea_multilevel(ctx(), REAL(stat), REAL(weight), g, c, INTEGER(Gp), INTEGER(Gi), m, int_or_null(perm), B, seed,
+                                  st, (int32_t)par[0], (int32_t)par[1], par[2], (int32_t)par[3], REAL(out), NULL, le_len, le_idx,
+                                  REAL(ml));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(3);
+  return res;
+}
+
 /* plaid.fisher(): list(out, tot, ov_len, ov_idx) of plaidhip_fisher -- out an m x 12c matrix (columns 12 l + 1 .. 12 l + 12
  * the columns of list l; the caller gives it dim m x 12 x c), tot 2 x c (nUp, nDn); ov_len (m x c integer) and ov_idx
  * (Gp[m] x c integer, 0-based rows of sig, -1 behind a set's overlap), or NULL for both when no overlap lists are asked for.
@@ -795,6 +835,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsva_csc", (DL_FUNC)&R_plaidhip_gsva_csc, 8},
     {"R_plaidhip_gsea", (DL_FUNC)&R_plaidhip_gsea, 9},
     {"R_plaidhip_gsea_scored", (DL_FUNC)&R_plaidhip_gsea_scored, 11},
+    {"R_plaidhip_gsea_multilevel", (DL_FUNC)&R_plaidhip_gsea_multilevel, 12},
     {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
     {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
     {"R_plaidhip_rankcor", (DL_FUNC)&R_plaidhip_rankcor, 6},
