@@ -1273,10 +1273,59 @@ int plaidhip_zscore_multi(const int* devices, int ndev, const int32_t* Xp, const
  *     each may be NULL.  `fit` is the number its messages name.
  *   plaidhip_limma_finish (host only): step 3 and the output from E ([W][rows]), rss ([nfit][rows]), nf (nfit), v
  *     (p x q x nfit) and u (q x nfit).  Tails and Benjamini-Hochberg are dealt to at most 8 host threads.
- * Not offered: trend = TRUE and robust = TRUE; array or observation weights; the B-statistic and the F-statistic; per-row
- * missing values (a NaN in a used sample makes the row NaN: limma would refit that row on the rest); a dgCMatrix input;
- * fusing a scorer with the test so that the scores never leave the device. */
+ * Not offered: trend = TRUE and robust = TRUE; array or observation weights; the B-statistic and the F-statistic; a
+ * dgCMatrix input; fusing a scorer with the test so that the scores never leave the device.  In plaidhip_limma a NaN in a
+ * used sample makes the row NaN; plaidhip_limma_na (below) refits such a row on the samples it has.
+ *
+ * plaidhip_limma_na / _na_multi: na = "fit", limma's handling of per-row missing values (lmFit refits a row with NA on the
+ * samples it has) and gx.limma's max.na.  The operands of plaidhip_limma plus max_na, and dfres.  DESIGN.md section 24.
+ * - Missing is NaN only (R's NA / NaN).  Inf is a value: a used Inf makes the row NaN, as above.
+ * - max_na: a row whose share of NaN over ALL n columns, (double)count / (double)n, exceeds max_na is not fitted in any fit:
+ *   NaN in every column, no part in eBayes (rowMeans(is.na(X)) <= max.na).  max_na = 0 refuses every row with a NaN.
+ * - For fit f and row r: mis = the samples of sel that are NaN in the row, obs = sel \ mis.  E' and M' are step 2's sums
+ *   with the select "c in sel and x_c == x_c", in the same order; a row without NaN in sel has the bits of plaidhip_limma,
+ *   skips the solve (gamma = E exactly) and has the fit's u_j.
+ * - An incomplete row: with q_c = row c of Q_f, for every pair (k, l <= k)
+ *     s = sum over mis in ascending c of fma(q_ck, q_cl, .) from 0.0 -- one chain --,   H_kl = (k == l ? 1.0 : 0.0) - s.
+ *   H = L L' by Cholesky without pivoting, row by row: L_kl = (H_kl - sum_{m<l} L_km L_lm) / L_ll, the pivot d_k = H_kk -
+ *   sum_{m<k} L_km^2, L_kk = sqrt(d_k), every sum a chain of fma(-a, b, .) in ascending m from H_kl.  L y = E' forward and
+ *   L' gamma = y backward, the sums likewise in ascending m (from E'_k, from y_k), then one division.  For contrast j:
+ *   w = L^-1 v_j forward, u_j = sqrt(sum_k fma(w_k, w_k, .)) ascending from 0.0 (stdev.unscaled of the row), and logFC =
+ *   sum_k v_jk gamma_k as in step 1.  AveExpr = (M' * (double)n_f) / (double)|obs|.  RSS is step 2's chain at gamma instead
+ *   of E with the extended select; s2 = RSS / d_r, d_r = |obs| - p.  The chain's step, the factorisation with the
+ *   substitutions, u_j and the mean are inline functions of csrc/lmfit_na.h, one copy for the device and for
+ *   plaidhip_limma_na_solve (a GPU test holds the device to that entry bit for bit).  The chain runs over the row's own missing samples, so the result does not
+ *   depend on the launch geometry or on the sharding.
+ * - Estimability is a rule: row r is not estimable in fit f when a pivot d_k <= 1e-10 (or is NaN) or |obs| - p < 1.  Then it
+ *   is NaN in that fit and not ok.  A pivot is 1 minus the leverage the missing samples hold on direction k, so 1e-10 would
+ *   be a 1e10-fold variance inflation; rounding leaves about (|mis| + p) 2^-52 in a pivot that is exactly 0.  limma would
+ *   still report the estimable coefficients of such a row (NA for the others); this does not.
+ * - eBayes with unequal df: limma's classic moment estimator fitFDist with a vector df1 (newer limma releases fit unequal
+ *   df by another route).  Over the ok rows (finite s2) of the fit, d_r as above:
+ *     e_r = log x_r - digamma(d_r / 2) + log(d_r / 2);   v = sum (e - ebar)^2 / (n_ok - 1) - mean_r trigamma(d_r / 2)
+ *     s2.post_r = (d_r s2_r + d0 s0^2) / (d_r + d0);   df.total_r = min(d_r + d0, df.pooled),  df.pooled = sum_r d_r
+ *   with sums in ascending row order.  Where all ok rows share one d the mean of trigamma is trigamma(d / 2) itself and
+ *   df.pooled is n_ok d: step 3 as it stands above, to the bit.
+ * - dfres: rows x nfit doubles, column-major: d_r of every ok (row, fit), NaN for the others.  hyper: nfit x 5 row-major:
+ *   the four of plaidhip_limma (df.residual = n_f - p, the complete rows') and df.pooled.
+ * - p <= PLAIDHIP_LIMMA_NA_MAX_COEF: the lower triangle of H is held by the lanes of one wavefront.  gx.limma's designs are
+ *   intercept + group + a few batch columns.
+ * - Argument errors: those of plaidhip_limma in their order, with, after "p outside 1..PLAIDHIP_LIMMA_MAX_COEF": p >
+ *   PLAIDHIP_LIMMA_NA_MAX_COEF, then max_na outside [0, 1] or NaN; and a null dfres after "a null A, out or hyper".
+ * - How: a count pass (a thread per row and block of 128 columns: coalesced, and with the host's prefix sums over (row,
+ *   block) a row's NaN columns come out ascending with no atomic; counts first, then the columns into space sized from the
+ *   total) and per (fit, row) counts inside sel; the incomplete pairs form a work list; Gram and solve with one wavefront
+ *   per pair (lane = one entry of the triangle, the sample's row of Q_f through LDS once), writing gamma where the RSS pass
+ *   reads E.  _na_multi: sample shards at multiples of 128 columns; counts add, the lists concatenate in shard order, and
+ *   one device runs the work list on the concatenated lists: every sharding, with more shards than samples too, has the
+ *   one-device bits.  A failing shard reports and nothing is written.
+ *   plaidhip_limma_na_solve (host only): one incomplete row.  qmis: nmis x p row-major, the rows q_c of its missing samples
+ *     in ascending c; Ep: E' (p); nobs = |obs|; v: p x q.  Writes gamma (p), u (q), *ok and the pivots d_k (p, may be
+ *     NULL; NaN past the pivot that broke the rule).
+ *   plaidhip_limma_finish_na (host only): plaidhip_limma_finish with drow ([nfit][rows]: d_r, NaN for a row that is not
+ *     fitted) and urow ([nfit q][rows]) in place of u, and hyper nfit x 5. */
 #define PLAIDHIP_LIMMA_MAX_COEF 32
+#define PLAIDHIP_LIMMA_NA_MAX_COEF 10         /* 10 * 11 / 2 = 55 entries of the triangle <= the 64 lanes of a wavefront */
 #define PLAIDHIP_LIMMA_TILE 8
 #define PLAIDHIP_LIMMA_MAX_FITS 15000         /* nfit (p + 1) / tile and nfit are launch grid extents, at most 65,535 each */
 #define PLAIDHIP_LIMMA_MAX_SAMPLES 8388480    /* 65,535 column blocks of 128: a launch grid extent as well */
@@ -1294,6 +1343,16 @@ int plaidhip_limma_design(const double* D, int32_t n, int32_t p, const int8_t* u
 int plaidhip_limma_finish(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
                           const int64_t* nf, const double* v, const double* u, double* out, double* hyper);
 int plaidhip_limma_tile(void);   /* PLAIDHIP_LIMMA_TILE of the built library */
+int plaidhip_limma_na(plaidhip_ctx* ctx, const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit,
+                      const int8_t* use, const double* K, int32_t q, double max_na, double* out, double* hyper, double* dfres);
+int plaidhip_limma_na_multi(const int* devices, int ndev, const double* A, int32_t rows, int32_t n, const double* design,
+                            int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na, double* out,
+                            double* hyper, double* dfres);
+int plaidhip_limma_na_solve(int32_t p, int32_t nmis, const double* qmis, const double* Ep, int64_t nobs, const double* v,
+                            int32_t q, double* gamma, double* u, double* pivots, int32_t* ok);
+int plaidhip_limma_finish_na(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
+                             const int64_t* nf, const double* v, const double* drow, const double* urow, double* out,
+                             double* hyper);
 
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set

@@ -869,6 +869,7 @@ def plaid_rankcor(stat, G, use_rank=True, compute_p=True, ties="average", minSiz
 
 _LIMMA_NAMES = ["logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2"]
 _LIMMA_HYPER = ["df.residual", "df.prior", "s2.prior", "n.ok"]
+_LIMMA_HYPER_NA = _LIMMA_HYPER + ["df.pooled"]
 _LIMMA_SORT = {"none": None, "P.Value": (3, 1), "P": (3, 1), "p": (3, 1), "t": (2, -1), "logFC": (0, -1), "AveExpr": (1, -1)}
 
 
@@ -883,18 +884,33 @@ def _limma_table(tab, rn, sort_by):
         key = tab[:, col] if sign > 0 else -np.abs(tab[:, col]) if col != 1 else -tab[:, col]
         o = np.argsort(key, kind="stable")
         tab, rn = tab[o, :], [rn[k] for k in o]
-    return NamedMatrix(tab, rn, _LIMMA_NAMES)
+    return NamedMatrix(tab, rn, _LIMMA_NAMES + ["df.residual"][:tab.shape[1] - 6])
 
 
-def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Context | None = None):
+def _limma_run(ctx, A, design, use, contrasts, na, max_na):
+    """(out rows x 6 or 7 x q x nfit, hyper, its names): under na = "fit" the rows' df.residual is the seventh column"""
+    if na == "propagate":
+        out, hyper = ctx.limma(A, design, use, contrasts)
+        return out, hyper, _LIMMA_HYPER
+    out, hyper, dfres = ctx.limma(A, design, use, contrasts, na=na, max_na=max_na)
+    dfr = np.broadcast_to(dfres[:, None, None, :], (out.shape[0], 1, out.shape[2], out.shape[3]))
+    dfr = np.where(np.isnan(out[:, 5:6, :, :]), np.nan, dfr)
+    return np.concatenate([out, dfr], axis=1), hyper, _LIMMA_HYPER_NA
+
+
+def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Context | None = None, na="propagate", max_na=0.2):
     """plaid.limma(): limma's moderated t-test (lmFit + eBayes + topTable, as pinned in include/plaidhip.h) of every row of S
     -- a NamedMatrix of single-sample scores (sets x samples) or of expression (genes x samples) -- for one design (samples
     x coefficients; a NamedMatrix names the coefficients).  contrasts: coefficients x contrasts (a NamedMatrix names them),
     None: every coefficient.  use: one entry per sample, False / 0 / NaN leaves it out of the fit (a NaN or Inf it holds in
     S does not reach the fit).  Returns (tables, hyper): tables is a dict, contrast name -> NamedMatrix (rows x [logFC,
     AveExpr, t, P.Value, adj.P.Val, sigma2]) ordered by `sort_by`; hyper a dict of df.residual, df.prior, s2.prior and n.ok.
-    The logFC and P.Value columns are what plaid_sig and plaid_gsea take.  Not offered: trend, robust, weights, the B- and
-    F-statistics, per-row missing values (a NaN in a used sample makes the row NaN), a sparse S."""
+    The logFC and P.Value columns are what plaid_sig and plaid_gsea take.
+    na: "propagate" (a NaN in a used sample makes the row NaN) or "fit": limma's own handling -- a row with at most the
+    share max_na of NaN over all samples (gx.limma's max.na) is refitted on the samples it has, with its own df.residual
+    and stdev.unscaled, and eBayes takes the unequal df; a row above max_na, or one that is not estimable on what it has,
+    is NaN.  The tables then have a seventh column df.residual and hyper has df.pooled; at most 10 coefficients.
+    Not offered: trend, robust, weights, the B- and F-statistics, a sparse S."""
     S = as_named(S)
     if S.is_sparse:
         raise ValueError("plaid.limma: S must be dense")
@@ -912,18 +928,19 @@ def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Contex
         names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
     _limma_table(np.zeros((0, 6)), [], sort_by)   # (an unknown sort_by is refused before the device)
     ctx = ctx or default_context()
-    out, hyper = ctx.limma(S.values, Dv, use, Kv)
+    out, hyper, hnames = _limma_run(ctx, S.values, Dv, use, Kv, na, max_na)
     tables = {nm: _limma_table(out[:, :, j, 0], S.rownames, sort_by) for j, nm in enumerate(names)}
-    return tables, dict(zip(_LIMMA_HYPER, (float(x) for x in hyper[0])))
+    return tables, dict(zip(hnames, (float(x) for x in hyper[0])))
 
 
-def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = None):
+def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = None, na="propagate", max_na=0.2):
     """plaid.limma.contrasts(): the reference's gx.limma(S, y, B, method = 1) for every column of the contrast matrix Y
     (samples x contrasts; 0, 1, and NaN or -1 for a sample that takes no part) in one call: contrast j fits the design
     [1, Y[, j], B] on the samples with a label and tests the coefficient of Y[, j].  B: batch covariates, samples x
     covariates, or None.  S is uploaded once and read ceil(C (p + 1) / 8) times for the effects, p = 2 + ncol(B).  Y: a
     NamedMatrix (its column names name the contrasts) or an array (contrasts "1", "2", ...).  Returns (tables, hyper):
-    contrast name -> the NamedMatrix plaid_limma returns, and contrast name -> its hyper-parameters."""
+    contrast name -> the NamedMatrix plaid_limma returns, and contrast name -> its hyper-parameters.  na, max_na: as
+    plaid_limma; with na = "fit" and max_na = 0.2 this is gx.limma(S, y, B, max.na = 0.2) on a matrix with missing values."""
     from .engine import contrast_labels
     S = as_named(S)
     if S.is_sparse:
@@ -948,6 +965,6 @@ def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = No
     K[1, 0] = 1.0
     _limma_table(np.zeros((0, 6)), [], sort_by)
     ctx = ctx or default_context()
-    out, hyper = ctx.limma(S.values, D, lab != -1, K)
+    out, hyper, hnames = _limma_run(ctx, S.values, D, lab != -1, K, na, max_na)
     tables = {nm: _limma_table(out[:, :, 0, j], S.rownames, sort_by) for j, nm in enumerate(names)}
-    return tables, {nm: dict(zip(_LIMMA_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
+    return tables, {nm: dict(zip(hnames, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}

@@ -1267,6 +1267,12 @@ int plaidhip_limma(plaidhip_ctx* ctx, const double* A, int32_t rows, int32_t n, 
   return dispatch(on_context(ctx), limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper));
 } catch (...) { return plaidhip::on_exception(); }
 
+int plaidhip_limma_na(plaidhip_ctx* ctx, const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit,
+                      const int8_t* use, const double* K, int32_t q, double max_na, double* out, double* hyper,
+                      double* dfres) try {
+  return dispatch(on_context(ctx), limma_na_call(A, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
+} catch (...) { return plaidhip::on_exception(); }
+
 // the two device passes of plaid.limma on device pointers (kernels_lmfit.hip).  The workspace holds the block partials, then
 // the masks, then (effects only) the tile weights.
 static int dev_row_design_pass(plaidhip_ctx* ctx, const char* what, const double* A, int64_t ld, int32_t rows, int32_t n,

@@ -115,6 +115,11 @@ struct Call : Operands {
   double* hyper = nullptr;
   std::vector<double> lm_Q, lm_invn, lm_v, lm_u;
   std::vector<int64_t> lm_nf;
+  // plaid.limma with na = "fit" (plaidhip_limma_na): rows with at most max_na of their n values NaN are refitted on the
+  // samples they have; dfres g x nfit, hyper nfit x 5
+  int na_fit = 0;
+  double max_na = 0.0;
+  double* dfres = nullptr;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -374,6 +379,17 @@ inline Call limma_call(const double* A, int32_t rows, int32_t n, const double* d
   k.nq = q;
   k.out = out;
   k.hyper = hyper;
+  return k;
+}
+
+// plaid.limma with na = "fit" as pinned in include/plaidhip.h: plaidhip_limma_na
+inline Call limma_na_call(const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit,
+                          const int8_t* use, const double* K, int32_t q, double max_na, double* out, double* hyper,
+                          double* dfres) {
+  Call k = limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper);
+  k.na_fit = 1;
+  k.max_na = max_na;
+  k.dfres = dfres;
   return k;
 }
 

@@ -369,9 +369,27 @@ int64_t lmfit_weight_bytes(int32_t n, int64_t W);
 int launch_lmfit_masks(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_use, const double* d_invn, int32_t n, int32_t p,
                        int32_t nfit, void* d_masks, double* d_wt);
 int launch_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const void* d_masks,
-                              const double* d_wt, int32_t W, double* ws);
+                              const double* d_wt, int32_t W, double* ws, bool na = false);
 int launch_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
-                          const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws);
+                          const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws, bool na = false);
+// na = "fit" (plaidhip_limma_na): `na` above extends the select by x == x.  The count pass: cnt[b][r] = the NaN of row r in
+// column block b of 128 (d_off null; nblk x rows), then d_list[d_off[b][r] ..] = their columns (d_off: the exclusive prefix
+// sums of cnt, row by row and block by block within a row, so a row's columns lie together and ascend).
+// launch_lmfit_nan_pairs: the NaN of every (fit, row) inside the fit's used samples from the rows' lists (d_off: rows + 1
+// row offsets), cnt [nfit][rows].  launch_lmfit_na_solve: Gram and solve over a work list of npairs (row, fit) pairs
+// (lmfit_na.h): d_E [W][rows] changed in place, d_u npairs x q, d_ok npairs.  p <= PLAIDHIP_LIMMA_NA_MAX_COEF.
+int launch_lmfit_nan_rows(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int64_t* d_off,
+                          int32_t* d_cnt, int32_t* d_list);
+int launch_lmfit_nan_pairs(plaidhip_ctx* ctx, const int64_t* d_off, const int32_t* d_list, const int8_t* d_use, int32_t rows,
+                           int32_t n, int32_t nfit, int32_t* d_cnt);
+int launch_lmfit_na_solve(plaidhip_ctx* ctx, int64_t npairs, const int32_t* d_pairs, const int64_t* d_off, const int32_t* d_list,
+                          const double* d_Q, const int8_t* d_use, int32_t n, int32_t p, int32_t q, const double* d_v,
+                          const int32_t* d_nobs, const double* d_nf, int32_t rows, double* d_E, double* d_u, int32_t* d_ok);
+// stats.cpp: eBayes and the tables of plaid.limma.  drow ([nfit][rows], NaN: the row is not fitted) and urow ([nfit q][rows])
+// null: every row of fit f has nf[f] - p and u[f q + j] (plaidhip_limma_finish); hyper has hcols (4 or 5) values per fit
+int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
+                      const int64_t* nf, const double* v, const double* u, const double* drow, const double* urow, double* out,
+                      double* hyper, int hcols);
 // stats.cpp: one design of plaid.limma (include/plaidhip.h: plaidhip_limma_design); what: the entry its messages name
 int limma_design(const char* what, const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q,
                  int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf);

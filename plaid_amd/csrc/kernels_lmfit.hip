@@ -14,6 +14,7 @@
 // The select form matters: an excluded column leaves the accumulator alone whatever it holds (NaN, Inf).  The file is
 // compiled with -ffp-contract=off (and says so below): the only fused operations are the fma written out.
 #include "common.h"
+#include "lmfit_na.h"
 
 #pragma clang fp contract(off)
 
@@ -54,7 +55,8 @@ lmfit_masks_kernel(const double* __restrict__ Q, const int8_t* __restrict__ use,
 // The block partials part[nblk][W][rows] of the W weighted row sums, tile blockIdx.z.  The load scheme is
 // row_contrast_partials_kernel's: kWide (rows and ld even, A 16-byte aligned) one 16-byte non-temporal load per column for
 // both rows, otherwise two 8-byte ones; kUn columns are loaded before the first of them is used.
-template <bool kWide>
+// kNa (na = "fit"): a NaN takes no part either -- the select is "c in sel and x_c == x_c", per row.
+template <bool kWide, bool kNa>
 __global__ void __launch_bounds__(256)
 row_design_effects_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const uint32_t* __restrict__ masks,
                           const double* __restrict__ wt, int32_t W, double* __restrict__ part) {
@@ -80,8 +82,9 @@ row_design_effects_kernel(const double* __restrict__ A, int64_t ld, int32_t rows
     for (int t = 0; t < T; ++t) {
       const bool in = ((k >> t) & 1u) != 0;
       const double wc = w[t];
-      a[t] = in ? __builtin_fma(xa, wc, a[t]) : a[t];
-      b[t] = in ? __builtin_fma(xb, wc, b[t]) : b[t];
+      const bool ia = kNa ? (in && xa == xa) : in, ib = kNa ? (in && xb == xb) : in;
+      a[t] = ia ? __builtin_fma(xa, wc, a[t]) : a[t];
+      b[t] = ib ? __builtin_fma(xb, wc, b[t]) : b[t];
     }
   };
   auto load = [&](int c, double& xa, double& xb) {
@@ -121,7 +124,8 @@ row_design_effects_kernel(const double* __restrict__ A, int64_t ld, int32_t rows
 // ([W][rows]): r = x - sum_k Q[c, k] E_k as p chained fma in ascending k, starting from x; the sum takes in ? r * r : 0.0.
 // A thread keeps its two rows' p effects in registers (kP: p rounded up to 4, 8, 16 or 32; DESIGN.md section 20 has the
 // resource report that chose registers over an LDS tile).  Q's entries of a column are wave-uniform.
-template <int kP, bool kWide>
+// kNa: the select extended by x_c == x_c, as in the effects.
+template <int kP, bool kWide, bool kNa>
 __global__ void __launch_bounds__(256)
 row_design_rss_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const double* __restrict__ Q,
                       const uint32_t* __restrict__ masks, int32_t p, int32_t nfit, const double* __restrict__ E,
@@ -160,8 +164,8 @@ row_design_rss_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, in
       rb = __builtin_fma(nq, eb[k], rb);
     }
     const double qa = ra * ra, qb = rb * rb;
-    sa += in ? qa : 0.0;
-    sb += in ? qb : 0.0;
+    sa += (kNa ? (in && xa == xa) : in) ? qa : 0.0;
+    sb += (kNa ? (in && xb == xb) : in) ? qb : 0.0;
   };
   auto load = [&](int c, double& xa, double& xb) {
     const double* q = A + (int64_t)c * ld + r;
@@ -192,6 +196,128 @@ row_design_rss_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, in
   if (two) o[r + 1] = sb;
 }
 
+// ---- na = "fit" (include/plaidhip.h: plaidhip_limma_na) ---------------------------------------------------
+constexpr int kNaP = PLAIDHIP_LIMMA_NA_MAX_COEF;
+static_assert(kNaP >= 8 && kNaP * (kNaP + 1) / 2 <= 64, "the lower triangle of H is one wavefront's lanes");
+
+// The count pass.  A thread owns one row and one block of 128 columns (blockIdx.y), so a column's loads are coalesced, the
+// grid fills the device as the effects kernel's does, and a row's NaN come out in ascending column order with no atomic:
+// within a block the thread walks ascending, and the blocks of a row are laid out one after the other by the prefix sums.
+// off == nullptr: cnt[b][r] = the NaN of row r in block b.  Otherwise the second sweep: list[off[b][r] ..] = their column
+// indices (off: the exclusive prefix sums of cnt taken row by row, block by block within a row).
+__global__ void __launch_bounds__(256)
+lmfit_nan_rows_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const int64_t* __restrict__ off,
+                      int32_t* __restrict__ cnt, int32_t* __restrict__ list) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  const int c0 = blockIdx.y * kLmColBlock;
+  const int c1 = c0 + kLmColBlock < n ? c0 + kLmColBlock : n;
+  if (r >= rows) return;
+  const int64_t slot = (int64_t)blockIdx.y * rows + r;
+  int32_t k = 0;
+  int32_t* o = off != nullptr ? list + off[slot] : nullptr;
+  for (int c = c0; c < c1; ++c) {
+    const double x = __builtin_nontemporal_load(A + (int64_t)c * ld + r);
+    if (x != x) {
+      if (o != nullptr) o[k] = c;
+      ++k;
+    }
+  }
+  if (off == nullptr) cnt[slot] = k;
+}
+
+// cnt[f][r] = the NaN of row r inside the used samples of fit f = blockIdx.y, from the row's list (use: n x nfit or null)
+__global__ void __launch_bounds__(256)
+lmfit_nan_pairs_kernel(const int64_t* __restrict__ off, const int32_t* __restrict__ list, const int8_t* __restrict__ use,
+                       int32_t rows, int32_t n, int32_t* __restrict__ cnt) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  const int f = blockIdx.y;
+  if (r >= rows) return;
+  int32_t k = 0;
+  for (int64_t i = off[r]; i < off[r + 1]; ++i) k += use == nullptr || use[(int64_t)f * n + list[i]] != 0 ? 1 : 0;
+  cnt[(int64_t)f * rows + r] = k;
+}
+
+// Gram and solve: one wavefront per incomplete (row, fit) pair of the work list (pairs[2 i], pairs[2 i + 1]).  Lane t < p (p +
+// 1) / 2 owns the entry (k, l <= k) of H and runs its chain over the pair's missing samples -- the row's list, ascending,
+// without the samples the fit left out (a wave-uniform test); the sample's row of Q_f goes through LDS once for all lanes.
+// Then the shared solve (lmfit_na.h) on lane 0, and the contrasts' u_j dealt to the lanes.  E ([W][rows]) holds E' and M'
+// of the pair on entry, gamma and the mean over the observed samples on return; a pair that is not estimable gets NaN.
+// LDS: 120 doubles and a flag, 968 bytes.
+__global__ void __launch_bounds__(64)
+lmfit_na_solve_kernel(const int32_t* __restrict__ pairs, const int64_t* __restrict__ off, const int32_t* __restrict__ list,
+                      const double* __restrict__ Q, const int8_t* __restrict__ use, int32_t n, int32_t p, int32_t q,
+                      const double* __restrict__ v, const int32_t* __restrict__ nobs, const double* __restrict__ nf,
+                      int32_t rows, double* __restrict__ E, double* __restrict__ upair, int32_t* __restrict__ okpair) {
+  __shared__ double qrow[kNaP];
+  __shared__ double H[kNaP * kNaP];
+  __shared__ double gam[kNaP];
+  __shared__ int ok;
+  const int lane = threadIdx.x;
+  const int r = pairs[2 * (int64_t)blockIdx.x], f = pairs[2 * (int64_t)blockIdx.x + 1];
+  const double* __restrict__ Qf = Q + (int64_t)f * p * n;
+  const int8_t* __restrict__ uf = use != nullptr ? use + (int64_t)f * n : nullptr;
+  int k = 0, l = lane;   // lane -> (k, l): row k of the triangle starts at k (k + 1) / 2
+  while (l > k) { l -= k + 1; ++k; }
+  const bool mine = k < p;
+  double s = 0.0;
+  for (int64_t i = off[r]; i < off[r + 1]; ++i) {
+    const int c = list[i];
+    if (uf != nullptr && uf[c] == 0) continue;
+    __syncthreads();
+    if (lane < p) qrow[lane] = Qf[(int64_t)lane * n + c];
+    __syncthreads();
+    if (mine) s = lmfit_na_gram_step(qrow[k], qrow[l], s);
+  }
+  if (mine) H[k * kNaP + l] = (k == l ? 1.0 : 0.0) - s;
+  double* e = E + (int64_t)f * (p + 1) * rows + r;
+  __syncthreads();
+  if (lane == 0) {
+    double ep[kNaP];
+    for (int t = 0; t < p; ++t) ep[t] = e[(int64_t)t * rows];
+    ok = lmfit_na_factor_solve(p, H, kNaP, ep, gam) ? 1 : 0;
+    const double nan = __builtin_nan("");
+    for (int t = 0; t < p; ++t) e[(int64_t)t * rows] = ok ? gam[t] : nan;
+    e[(int64_t)p * rows] = ok ? lmfit_na_mean(e[(int64_t)p * rows], nf[f], (double)nobs[blockIdx.x]) : nan;
+    okpair[blockIdx.x] = ok;
+  }
+  __syncthreads();
+  for (int j = lane; j < q; j += 64) {
+    double w[kNaP];
+    upair[(int64_t)blockIdx.x * q + j] =
+        ok ? lmfit_na_unscaled(p, H, kNaP, v + ((int64_t)f * q + j) * p, w) : __builtin_nan("");
+  }
+}
+
+int launch_lmfit_nan_rows(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int64_t* d_off,
+                          int32_t* d_cnt, int32_t* d_list) {
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  hipLaunchKernelGGL(lmfit_nan_rows_kernel, dim3((rows + 255) / 256, (n + kLmColBlock - 1) / kLmColBlock), dim3(256), 0,
+                     ctx->stream, A, ld, rows, n, d_off, d_cnt, d_list);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+int launch_lmfit_nan_pairs(plaidhip_ctx* ctx, const int64_t* d_off, const int32_t* d_list, const int8_t* d_use, int32_t rows,
+                           int32_t n, int32_t nfit, int32_t* d_cnt) {
+  if (rows == 0 || nfit == 0) return PLAIDHIP_OK;
+  hipLaunchKernelGGL(lmfit_nan_pairs_kernel, dim3((rows + 255) / 256, nfit), dim3(256), 0, ctx->stream, d_off, d_list, d_use,
+                     rows, n, d_cnt);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
+// npairs work items; d_E: [nfit (p + 1)][rows], changed in place; d_u: npairs x q; d_ok: npairs
+int launch_lmfit_na_solve(plaidhip_ctx* ctx, int64_t npairs, const int32_t* d_pairs, const int64_t* d_off, const int32_t* d_list,
+                          const double* d_Q, const int8_t* d_use, int32_t n, int32_t p, int32_t q, const double* d_v,
+                          const int32_t* d_nobs, const double* d_nf, int32_t rows, double* d_E, double* d_u, int32_t* d_ok) {
+  if (npairs == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(p >= 1 && p <= kNaP && npairs <= 2147483647, "limma_na: p = %d, %lld pairs", p, (long long)npairs);
+  hipLaunchKernelGGL(lmfit_na_solve_kernel, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, d_pairs, d_off, d_list, d_Q, d_use,
+                     n, p, q, d_v, d_nobs, d_nf, rows, d_E, d_u, d_ok);
+  PH_HIP(hipGetLastError());
+  return PLAIDHIP_OK;
+}
+
 int64_t lmfit_tiles(int64_t W) { return (W + kLmTile - 1) / kLmTile; }
 
 // doubles of the block partials [nblk][cols][rows]
@@ -216,43 +342,51 @@ int launch_lmfit_masks(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_use
 
 // ws: row_design_ws_doubles(rows, n, W) doubles, [nblk][W][rows]; d_masks / d_wt: launch_lmfit_masks of the same n and W
 int launch_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const void* d_masks,
-                              const double* d_wt, int32_t W, double* ws) {
+                              const double* d_wt, int32_t W, double* ws, bool na) {
   if (rows == 0 || n == 0 || W == 0) return PLAIDHIP_OK;
   const int nblk = (n + kLmColBlock - 1) / kLmColBlock;
   const dim3 grid((rows + 511) / 512, nblk, (unsigned)lmfit_tiles(W));
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
   const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
-  if (wide)
-    hipLaunchKernelGGL((row_design_effects_kernel<true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+  if (wide && na)
+    hipLaunchKernelGGL((row_design_effects_kernel<true, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+  else if (wide)
+    hipLaunchKernelGGL((row_design_effects_kernel<true, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+  else if (na)
+    hipLaunchKernelGGL((row_design_effects_kernel<false, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
   else
-    hipLaunchKernelGGL((row_design_effects_kernel<false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+    hipLaunchKernelGGL((row_design_effects_kernel<false, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
 
-template <int kP>
+template <int kP, bool kNa>
 static void launch_rss_p(plaidhip_ctx* ctx, bool wide, dim3 grid, const double* A, int64_t ld, int32_t rows, int32_t n,
                          const double* d_Q, const uint32_t* mk, int32_t p, int32_t nfit, const double* d_E, double* ws) {
   if (wide)
-    hipLaunchKernelGGL((row_design_rss_kernel<kP, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
+    hipLaunchKernelGGL((row_design_rss_kernel<kP, true, kNa>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
                        ws);
   else
-    hipLaunchKernelGGL((row_design_rss_kernel<kP, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
+    hipLaunchKernelGGL((row_design_rss_kernel<kP, false, kNa>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
                        ws);
 }
 
 // ws: row_design_ws_doubles(rows, n, nfit) doubles, [nblk][nfit][rows]; d_E: [nfit (p + 1)][rows], the effects of all samples
 int launch_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
-                          const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws) {
+                          const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws, bool na) {
   if (rows == 0 || n == 0 || nfit == 0) return PLAIDHIP_OK;
   const int nblk = (n + kLmColBlock - 1) / kLmColBlock;
   const dim3 grid((rows + 511) / 512, nblk, nfit);
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
   const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
-  if (p <= 4) launch_rss_p<4>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-  else if (p <= 8) launch_rss_p<8>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-  else if (p <= 16) launch_rss_p<16>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-  else launch_rss_p<32>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  if (na) {
+    if (p <= 4) launch_rss_p<4, true>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+    else if (p <= 8) launch_rss_p<8, true>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+    else launch_rss_p<16, true>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);   // (p <= NA_MAX_COEF)
+  } else if (p <= 4) launch_rss_p<4, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  else if (p <= 8) launch_rss_p<8, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  else if (p <= 16) launch_rss_p<16, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  else launch_rss_p<32, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

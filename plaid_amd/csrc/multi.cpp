@@ -298,6 +298,12 @@ struct Shared {
   // sums go to row_sum
   // plaid.limma: chain_x is the chained effects [W][rows], chain_q the chained residual sums of squares [nfit][rows]
   std::vector<double> chain_x, chain_s, chain_q, pt_T, pt_F;
+  // plaid.limma with na = "fit": every shard's NaN per row and their (global) columns, row after row; the NaN of every
+  // (fit, row) inside the fit's used samples, added over the shards; then, from shard 0, df.residual [nfit][rows] (NaN: not
+  // fitted) and u [nfit q][rows]
+  std::vector<std::vector<int32_t>> na_cnt, na_list;
+  std::vector<int32_t> na_pair;
+  std::vector<double> na_d, na_u;
   // replaid.ssgsea.exact with norm: a NaN among the scores of any shard (its min / max go to xmin / xmax)
   bool es_nan = false;
   // plaid.gsea: the block partials [nblk][c][6][m] of all permutation blocks, each shard writing its own blocks
@@ -2422,11 +2428,93 @@ void chain_flat_sums(Shard& s, std::vector<double>& run, const double* ws, int64
   }
 }
 
+// plaid.limma with na = "fit", after the effects are chained: shard 0 merges the shards' NaN lists in shard order (a row's
+// columns ascending), decides which rows are fitted (max_na) and which (row, fit) pairs are incomplete, and runs Gram and
+// solve (kernels_lmfit.hip) over those: the pair's effects in sh.chain_x become gamma, its mean the mean over the observed
+// samples, and sh.na_d / sh.na_u take every row's df.residual (NaN: not fitted) and u_j.  A pair's chain runs over the row's
+// own missing samples in ascending order whatever the sharding, so every sharding has the one-device bits.
+int limma_na_refit(plaidhip_ctx* ctx, const Call& c, int ndev, Shared& sh, double* d_E) {
+  const int32_t rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, q = c.nq;
+  const size_t R = (size_t)rows;
+  const int64_t W = (int64_t)nfit * (p + 1);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int64_t> off(R + 1, 0);
+  for (size_t r = 0; r < R; ++r) {
+    int64_t tot = 0;
+    for (int k = 0; k < ndev; ++k) tot += sh.na_cnt[(size_t)k].empty() ? 0 : sh.na_cnt[(size_t)k][r];
+    off[r + 1] = off[r] + tot;
+  }
+  std::vector<int32_t> list((size_t)off[R]);
+  std::vector<size_t> pos((size_t)ndev, 0);
+  for (size_t r = 0; r < R; ++r) {
+    int64_t w = off[r];
+    for (int k = 0; k < ndev; ++k) {
+      const int32_t ck = sh.na_cnt[(size_t)k].empty() ? 0 : sh.na_cnt[(size_t)k][r];
+      std::copy(sh.na_list[(size_t)k].begin() + pos[(size_t)k], sh.na_list[(size_t)k].begin() + pos[(size_t)k] + ck,
+                list.begin() + w);
+      pos[(size_t)k] += (size_t)ck;
+      w += ck;
+    }
+  }
+  sh.na_d.assign(R * nfit, nan);
+  sh.na_u.assign(R * nfit * q, nan);
+  std::vector<int32_t> pairs, nobs;
+  for (int32_t f = 0; f < nfit; ++f)
+    for (size_t r = 0; r < R; ++r) {
+      const bool fitted = (double)(off[r + 1] - off[r]) / (double)n <= c.max_na;   // rowMeans(is.na(X)) <= max.na
+      const int64_t mis = sh.na_pair[R * f + r], d = c.lm_nf[(size_t)f] - mis - p;
+      if (fitted && d >= 1) sh.na_d[R * f + r] = (double)d;
+      for (int32_t j = 0; j < q; ++j) sh.na_u[((size_t)f * q + j) * R + r] = c.lm_u[(size_t)f * q + j];
+      if (mis > 0 && fitted && d >= 1) {
+        pairs.push_back((int32_t)r);
+        pairs.push_back(f);
+        nobs.push_back((int32_t)(c.lm_nf[(size_t)f] - mis));
+      }
+    }
+  const size_t np = nobs.size();
+  if (np == 0) return PLAIDHIP_OK;
+  std::vector<double> nfd((size_t)nfit), upair(np * q);
+  std::vector<int32_t> okp(np);
+  for (int32_t f = 0; f < nfit; ++f) nfd[(size_t)f] = (double)c.lm_nf[(size_t)f];
+  DevBuf dpairs, doff, dlist, dQ, duse, dv, dnobs, dnf, du, dok;
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
+    PH_TRY(b.alloc(bytes));
+    PH_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return PLAIDHIP_OK;
+  };
+  PH_TRY(up(dpairs, pairs.data(), pairs.size() * 4));
+  PH_TRY(up(doff, off.data(), off.size() * 8));
+  PH_TRY(up(dlist, list.data(), list.size() * 4));
+  PH_TRY(up(dQ, c.lm_Q.data(), c.lm_Q.size() * 8));
+  if (c.use != nullptr) PH_TRY(up(duse, c.use, (size_t)n * nfit));
+  PH_TRY(up(dv, c.lm_v.data(), c.lm_v.size() * 8));
+  PH_TRY(up(dnobs, nobs.data(), np * 4));
+  PH_TRY(up(dnf, nfd.data(), nfd.size() * 8));
+  PH_TRY(du.alloc(np * q * 8));
+  PH_TRY(dok.alloc(np * 4));
+  PH_HIP(hipMemcpyAsync(d_E, sh.chain_x.data(), (size_t)W * R * 8, hipMemcpyHostToDevice, ctx->stream));
+  PH_TRY(launch_lmfit_na_solve(ctx, (int64_t)np, dpairs.as<int32_t>(), doff.as<int64_t>(), dlist.as<int32_t>(), dQ.as<double>(),
+                               c.use != nullptr ? duse.as<int8_t>() : nullptr, n, p, q, dv.as<double>(), dnobs.as<int32_t>(),
+                               dnf.as<double>(), rows, d_E, du.as<double>(), dok.as<int32_t>()));
+  PH_HIP(hipMemcpyAsync(sh.chain_x.data(), d_E, (size_t)W * R * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipMemcpyAsync(upair.data(), du.p, np * q * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipMemcpyAsync(okp.data(), dok.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < np; ++i) {
+    const size_t r = (size_t)pairs[2 * i], f = (size_t)pairs[2 * i + 1];
+    if (!okp[i]) sh.na_d[R * f + r] = nan;
+    for (int32_t j = 0; j < q; ++j) sh.na_u[(f * q + j) * R + r] = upair[i * q + j];
+  }
+  return PLAIDHIP_OK;
+}
+
 // one device's part of plaid.limma (kLimma, kernels_lmfit.hip; include/plaidhip.h: plaidhip_limma).  The SAMPLES are shared
 // out at multiples of 128 columns, as for plaid.test.contrasts: a shard takes its columns of A and its rows of every Q_f and
 // of use.  Round one chains the effects and means [W][rows] from shard to shard; after it every shard holds the effects of
 // all samples and takes the residual sums of squares of its own columns, which round two chains as [nfit][rows].  The block
 // partials are added in the order of the one-device call, so every sharding has its bits.  2 ndev rendezvous.
+// na = "fit" (c.na_fit): both passes take the select "used and not NaN"; round one also lists the NaN of the shard's columns
+// (the count pass), and between the rounds shard 0 refits the incomplete (row, fit) pairs (limma_na_refit): one more rendezvous.
 int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
   Shard s(ctx, c, ndev, k, sh);
   const int32_t lo = s.lo, nloc = s.nloc, rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit;
@@ -2469,17 +2557,64 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
     PH_TRY(dA.alloc((size_t)ld * nloc * 8));
     PH_TRY(upload_pipelined(ctx, dA.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * rows),
                             (size_t)rows * 8, nloc, nullptr));
-    return launch_row_design_effects(ctx, dA.as<double>(), ld, rows, nloc, dmask.p, dwt.as<double>(), (int32_t)W,
-                                     dws.as<double>());
+    PH_TRY(launch_row_design_effects(ctx, dA.as<double>(), ld, rows, nloc, dmask.p, dwt.as<double>(), (int32_t)W,
+                                     dws.as<double>(), c.na_fit != 0));
+    if (!c.na_fit) return PLAIDHIP_OK;
+    // the count pass: the NaN of every (column block, row) of the shard, their columns in ascending order (a second sweep,
+    // once the space is known), and the NaN of every (fit, row) inside the fit's used samples
+    std::vector<int32_t>& cnt = sh.na_cnt[(size_t)k];
+    std::vector<int32_t>& list = sh.na_list[(size_t)k];
+    const size_t R = (size_t)rows, nblk = ((size_t)nloc + 127) / 128;
+    std::vector<int32_t> bcnt(nblk * R);                   // [block][row]
+    DevBuf dcnt, doff, drow, dlist, dpc;
+    PH_TRY(dcnt.alloc(bcnt.size() * 4));
+    PH_TRY(launch_lmfit_nan_rows(ctx, dA.as<double>(), ld, rows, nloc, nullptr, dcnt.as<int32_t>(), nullptr));
+    PH_HIP(hipMemcpyAsync(bcnt.data(), dcnt.p, bcnt.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    cnt.assign(R, 0);
+    std::vector<int64_t> off(nblk * R), rowoff(R + 1, 0);   // where (block, row) writes; where a row's list starts
+    int64_t run = 0;
+    for (size_t r = 0; r < R; ++r) {
+      for (size_t b = 0; b < nblk; ++b) {
+        off[b * R + r] = run;
+        run += bcnt[b * R + r];
+      }
+      cnt[r] = (int32_t)(run - rowoff[r]);
+      rowoff[r + 1] = run;
+    }
+    const size_t total = (size_t)run;
+    if (total == 0) return PLAIDHIP_OK;
+    std::vector<int32_t> pc((size_t)nfit * rows);
+    list.resize(total);
+    PH_TRY(doff.alloc(off.size() * 8));
+    PH_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(drow.alloc(rowoff.size() * 8));
+    PH_HIP(hipMemcpyAsync(drow.p, rowoff.data(), rowoff.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dlist.alloc(total * 4));
+    PH_TRY(dpc.alloc(pc.size() * 4));
+    PH_TRY(launch_lmfit_nan_rows(ctx, dA.as<double>(), ld, rows, nloc, doff.as<int64_t>(), nullptr, dlist.as<int32_t>()));
+    PH_TRY(launch_lmfit_nan_pairs(ctx, drow.as<int64_t>(), dlist.as<int32_t>(), c.use != nullptr ? duse.as<int8_t>() : nullptr,
+                                  rows, nloc, nfit, dpc.as<int32_t>()));
+    PH_HIP(hipMemcpyAsync(list.data(), dlist.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(pc.data(), dpc.p, pc.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    for (int32_t& col : list) col += lo;
+    std::lock_guard<std::mutex> lk(sh.mu);
+    for (size_t i = 0; i < pc.size(); ++i) sh.na_pair[i] += pc[i];
+    return PLAIDHIP_OK;
   });
   chain_flat_sums(s, sh.chain_x, dws.as<double>(), W * rows, d_seed, d_run);
+  if (c.na_fit) {   // (every shard's lists are complete: chain_flat_sums has met ndev times since)
+    if (k == 0) s.step([&]() -> int { return limma_na_refit(ctx, c, ndev, sh, d_E); });
+    sh.rv.arrive_and_wait();
+  }
 
   // ---- the residual sums of squares of the shard's columns at the effects of ALL samples -------------------------------------
   s.step([&]() -> int {
     if (nloc == 0) return PLAIDHIP_OK;
     PH_HIP(hipMemcpyAsync(d_E, sh.chain_x.data(), (size_t)W * rows * 8, hipMemcpyHostToDevice, ctx->stream));
     return launch_row_design_rss(ctx, dA.as<double>(), ld, rows, nloc, dQ.as<double>(), dmask.p, p, nfit, d_E,
-                                 dws.as<double>());
+                                 dws.as<double>(), c.na_fit != 0);
   });
   chain_flat_sums(s, sh.chain_q, dws.as<double>(), (int64_t)nfit * rows, d_seed, d_run);
   return s.finish();
@@ -2516,6 +2651,11 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   if (c.method == kLimma) {
     sh.chain_x.assign((size_t)c.nfit * (c.ncoef + 1) * c.g, 0.0);
     sh.chain_q.assign((size_t)c.nfit * c.g, 0.0);
+    if (c.na_fit) {
+      sh.na_cnt.resize((size_t)ndev);
+      sh.na_list.resize((size_t)ndev);
+      sh.na_pair.assign((size_t)c.nfit * c.g, 0);
+    }
   }
   if (c.method == kGseaMultilevel && !c.ml_ruler)
     sh.gsea_ml.assign((size_t)c.m * c.n * 4, std::numeric_limits<double>::quiet_NaN());
@@ -2570,7 +2710,18 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     rc = plaidhip_plaid_test_finish(c.g, c.m, c.Gp, sh.pt_T.data(), tot1, tot2, (c.tests & 4) ? SM.data() : nullptr, c.n0,
                                     c.n1, c.tests, c.metap_method, c.out);
   }
-  if (rc == PLAIDHIP_OK && c.method == kLimma)   // eBayes and the tables, on the host from the chained sums
+  if (rc == PLAIDHIP_OK && c.method == kLimma && c.na_fit) {
+    rc = plaidhip_limma_finish_na(c.g, c.ncoef, c.nfit, c.nq, sh.chain_x.data(), sh.chain_q.data(), c.lm_nf.data(),
+                                  c.lm_v.data(), sh.na_d.data(), sh.na_u.data(), c.out, c.hyper);
+    if (rc == PLAIDHIP_OK) {   // df.residual of the rows that came out of the fit; NaN for the others
+      const size_t R = (size_t)c.g;
+      for (int32_t f = 0; f < c.nfit; ++f) {
+        const double* sigma2 = c.out + ((size_t)f * c.nq * 6 + 5) * R;   // (of the fit's first contrast: NaN = not ok)
+        for (size_t r = 0; r < R; ++r)
+          c.dfres[R * f + r] = std::isnan(sigma2[r]) ? std::numeric_limits<double>::quiet_NaN() : sh.na_d[R * f + r];
+      }
+    }
+  } else if (rc == PLAIDHIP_OK && c.method == kLimma)   // eBayes and the tables, on the host from the chained sums
     rc = plaidhip_limma_finish(c.g, c.ncoef, c.nfit, c.nq, sh.chain_x.data(), sh.chain_q.data(), c.lm_nf.data(), c.lm_v.data(),
                                c.lm_u.data(), c.out, c.hyper);
   if (rc == PLAIDHIP_OK && c.method == kPlaidTestContrasts) {   // the same host half, once per contrast with its group sizes
@@ -2994,10 +3145,16 @@ int check_limma_call(Call& c) {
              "limma: bad dims rows=%d n=%d nfit=%d q=%d (n <= %d, nfit <= %d)", rows, n, nfit, q, PLAIDHIP_LIMMA_MAX_SAMPLES,
              PLAIDHIP_LIMMA_MAX_FITS);
   PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "limma: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
+  if (c.na_fit) {
+    PH_REQUIRE(p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "limma: p = %d coefficients with na = \"fit\" (p <= %d)", p,
+               PLAIDHIP_LIMMA_NA_MAX_COEF);
+    PH_REQUIRE(c.max_na >= 0.0 && c.max_na <= 1.0, "limma: max_na = %g (a share, 0 <= max_na <= 1)", c.max_na);
+  }
   PH_REQUIRE(c.K != nullptr || q == p, "limma: q = %d without K (the p = %d unit vectors)", q, p);
   PH_REQUIRE(c.design != nullptr || nfit == 0, "limma: null design");
   PH_REQUIRE(rows == 0 || nfit == 0 || q == 0 || (c.X != nullptr && c.out != nullptr && c.hyper != nullptr),
              "limma: null A / out / hyper");
+  PH_REQUIRE(!c.na_fit || rows == 0 || nfit == 0 || q == 0 || c.dfres != nullptr, "limma: null dfres");
   if (c.K != nullptr)
     for (int64_t e = 0; e < (int64_t)p * q; ++e)
       PH_REQUIRE(std::isfinite(c.K[e]), "limma: K[%lld] = %g (the contrasts are finite)", (long long)e, c.K[e]);
@@ -3385,6 +3542,20 @@ int plaidhip_debug_limma_sharded_on_one_device(int device, int nshards, int fail
                                                const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K,
                                                int32_t q, double* out, double* hyper) try {
   return dispatch(on_hook(device, nshards, fail_shard), limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_na_multi(const int* devices, int ndev, const double* A, int32_t rows, int32_t n, const double* design,
+                            int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na, double* out,
+                            double* hyper, double* dfres) try {
+  return dispatch(on_devices(devices, ndev), limma_na_call(A, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_limma_na_sharded_on_one_device(int device, int nshards, int fail_shard, const double* A, int32_t rows,
+                                                  int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                                                  const double* K, int32_t q, double max_na, double* out, double* hyper,
+                                                  double* dfres) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  limma_na_call(A, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fail_shard, const int8_t* sig, int32_t g, int32_t c,

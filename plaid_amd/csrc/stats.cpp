@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "lmfit_na.h"
 
 namespace plaidhip {
 
@@ -395,6 +396,133 @@ int limma_design(const char* what, const double* D, int32_t n, int32_t p, const 
   return PLAIDHIP_OK;
 }
 
+// Step 3 of plaid.limma and its tables.  drow == nullptr is plaidhip_limma_finish: every row of fit f has d = n_f - p and
+// the fit's u_j.  Otherwise (plaidhip_limma_finish_na) row r of fit f has d_r = drow[f][r] (NaN: not fitted) and its own
+// u_j, and squeezeVar's moments take a vector df1; where all ok rows share one d the operations are those of the first form.
+int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
+                      const int64_t* nf, const double* v, const double* u, const double* drow, const double* urow, double* out,
+                      double* hyper, int hcols) {
+  PH_REQUIRE(rows >= 0 && nfit >= 0 && q >= 0, "%s: bad dims rows=%d nfit=%d q=%d", what, rows, nfit, q);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "%s: p = %d coefficients (1 <= p <= %d)", what, p, PLAIDHIP_LIMMA_MAX_COEF);
+  if (rows == 0 || nfit == 0 || q == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(E && rss && nf && v && u && out && hyper, "%s: null argument", what);
+  for (int32_t f = 0; f < nfit; ++f)
+    PH_REQUIRE(nf[f] - p >= 1, "%s: fit %d has %lld samples for %d coefficients", what, f + 1, (long long)nf[f], p);
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const size_t R = (size_t)rows;
+  // per fit: s2, the prior, s2.post and df.total
+  std::vector<double> s2(R * nfit), post(R * nfit), d0s((size_t)nfit), pooled((size_t)nfit), xs;
+  for (int32_t f = 0; f < nfit; ++f) {
+    const double dfit = (double)(nf[f] - p);
+    const double* dr = drow != nullptr ? drow + R * f : nullptr;
+    double* s = s2.data() + R * f;
+    xs.clear();
+    double d = dfit, dsum = 0.0;   // d: the ok rows' residual df where they share one
+    bool alleq = true;
+    for (size_t r = 0; r < R; ++r) {
+      const double di = dr != nullptr ? dr[r] : dfit;
+      s[r] = rss[R * f + r] / di;
+      if (!std::isfinite(s[r])) continue;
+      if (dr != nullptr) {
+        if (xs.empty()) d = di;
+        else if (di != d) alleq = false;
+        dsum += di;
+      }
+      xs.push_back(s[r]);
+    }
+    const int64_t nok = (int64_t)xs.size();
+    const double pool = alleq ? (double)nok * d : dsum;   // df.pooled
+    double d0 = 0.0, s0 = nan;
+    if (nok >= 2) {
+      const size_t h = (size_t)nok / 2;
+      std::nth_element(xs.begin(), xs.begin() + h, xs.end());
+      double med = xs[h];
+      if (nok % 2 == 0) med = (*std::max_element(xs.begin(), xs.begin() + h) + med) / 2.0;
+      if (med == 0.0) med = 1.0;
+      const double floor_x = 1e-5 * med, shift = -lm_digamma(0.5 * d) + std::log(0.5 * d);
+      double esum = 0.0, xsum = 0.0, trisum = 0.0;
+      std::vector<double> e;
+      e.reserve((size_t)nok);
+      for (size_t r = 0; r < R; ++r) {   // (in row order: the sums below are pinned as ascending)
+        if (!std::isfinite(s[r])) continue;
+        const double x = std::max(s[r], floor_x);
+        if (alleq) {
+          e.push_back(std::log(x) + shift);
+        } else {
+          e.push_back(std::log(x) + (-lm_digamma(0.5 * dr[r]) + std::log(0.5 * dr[r])));
+          trisum += lm_trigamma(0.5 * dr[r]);
+        }
+        esum += e.back();
+        xsum += x;
+      }
+      const double ebar = esum / (double)nok;
+      double ss = 0.0;
+      for (double ei : e) ss += (ei - ebar) * (ei - ebar);
+      const double var = ss / (double)(nok - 1) - (alleq ? lm_trigamma(0.5 * d) : trisum / (double)nok);
+      if (var > 0.0) {
+        const double y = lm_trigamma_inverse(var);
+        d0 = 2.0 * y;
+        s0 = std::exp(ebar + lm_digamma(y) - std::log(y));
+      } else {
+        d0 = inf;
+        s0 = xsum / (double)nok;
+      }
+    }
+    hyper[(size_t)hcols * f] = dfit;
+    hyper[(size_t)hcols * f + 1] = d0;
+    hyper[(size_t)hcols * f + 2] = s0;
+    hyper[(size_t)hcols * f + 3] = (double)nok;
+    if (hcols > 4) hyper[(size_t)hcols * f + 4] = pool;
+    d0s[(size_t)f] = d0;
+    pooled[(size_t)f] = pool;
+    double* po = post.data() + R * f;
+    for (size_t r = 0; r < R; ++r) {
+      const double di = dr != nullptr ? dr[r] : dfit;
+      po[r] = !std::isfinite(s[r]) ? nan : std::isinf(d0) ? s0 : d0 == 0.0 ? s[r] : (di * s[r] + d0 * s0) / (di + d0);
+    }
+  }
+  // logFC, AveExpr, t, P.Value and sigma2 of every (fit, contrast, row): row chunks dealt to the threads
+  const int64_t ncol = (int64_t)nfit * q, items = ncol * rows;
+  const int32_t W1 = p + 1;
+  auto tails = [&](int64_t t, int64_t nth) {
+    const int64_t lo = items * t / nth, hi = items * (t + 1) / nth;
+    for (int64_t e = lo; e < hi; ++e) {
+      const int64_t col = e / rows;
+      const size_t r = (size_t)(e % rows);
+      const int32_t f = (int32_t)(col / q), j = (int32_t)(col % q);
+      double* o = out + (size_t)col * 6 * R;
+      const double sr = s2[R * f + r];
+      if (!std::isfinite(sr)) {
+        for (int c = 0; c < 6; ++c) o[(size_t)c * R + r] = nan;
+        continue;
+      }
+      const double* vj = v + ((size_t)f * q + j) * p;
+      double fc = 0.0;
+      for (int32_t k = 0; k < p; ++k) fc = std::fma(vj[k], E[((size_t)f * W1 + k) * R + r], fc);
+      const double uj = urow != nullptr ? urow[(size_t)col * R + r] : u[(size_t)f * q + j];
+      const double di = drow != nullptr ? drow[R * f + r] : (double)(nf[f] - p);
+      const double d0 = d0s[(size_t)f], pool = pooled[(size_t)f];
+      const double tt = fc / (uj * std::sqrt(post[R * f + r]));
+      o[r] = fc;
+      o[R + r] = E[((size_t)f * W1 + p) * R + r];
+      o[2 * R + r] = tt;
+      o[3 * R + r] = t_two_sided_p(tt, std::isinf(d0) ? pool : std::min(di + d0, pool));
+      o[5 * R + r] = sr;
+    }
+  };
+  const int64_t nth = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, items / kLimmaWork}));
+  if (!lm_threads(nth, tails)) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+  auto adjust = [&](int64_t t, int64_t nt) {
+    for (int64_t col = t; col < ncol; col += nt) {
+      double* o = out + (size_t)col * 6 * R;
+      p_adjust_fdr(o + 3 * R, rows, o + 4 * R);
+    }
+  };
+  const int64_t nbh = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, items / kLimmaWork, ncol}));
+  if (!lm_threads(nbh, adjust)) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+  return PLAIDHIP_OK;
+}
+
 // ---- plaid.rankcor: the pinned epilogues (include/plaidhip.h: plaidhip_rankcor) -------------------------
 namespace {
 
@@ -517,103 +645,36 @@ int plaidhip_limma_design(const double* D, int32_t n, int32_t p, const int8_t* u
 
 int plaidhip_limma_finish(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
                           const int64_t* nf, const double* v, const double* u, double* out, double* hyper) try {
+  return plaidhip::limma_finish_rows("limma_finish", rows, p, nfit, q, E, rss, nf, v, u, nullptr, nullptr, out, hyper, 4);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_finish_na(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
+                             const int64_t* nf, const double* v, const double* drow, const double* urow, double* out,
+                             double* hyper) try {
   using namespace plaidhip;
-  PH_REQUIRE(rows >= 0 && nfit >= 0 && q >= 0, "limma_finish: bad dims rows=%d nfit=%d q=%d", rows, nfit, q);
-  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "limma_finish: p = %d coefficients (1 <= p <= %d)", p,
-             PLAIDHIP_LIMMA_MAX_COEF);
-  if (rows == 0 || nfit == 0 || q == 0) return PLAIDHIP_OK;
-  PH_REQUIRE(E && rss && nf && v && u && out && hyper, "limma_finish: null argument");
-  for (int32_t f = 0; f < nfit; ++f)
-    PH_REQUIRE(nf[f] - p >= 1, "limma_finish: fit %d has %lld samples for %d coefficients", f + 1, (long long)nf[f], p);
-  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
-  const size_t R = (size_t)rows;
-  // per fit: s2, the prior, s2.post and df.total
-  std::vector<double> s2(R * nfit), post(R * nfit), dft((size_t)nfit), xs;
-  for (int32_t f = 0; f < nfit; ++f) {
-    const double d = (double)(nf[f] - p);
-    double* s = s2.data() + R * f;
-    xs.clear();
-    for (size_t r = 0; r < R; ++r) {
-      s[r] = rss[R * f + r] / d;
-      if (std::isfinite(s[r])) xs.push_back(s[r]);
-    }
-    const int64_t nok = (int64_t)xs.size();
-    double d0 = 0.0, s0 = nan;
-    if (nok >= 2) {
-      const size_t h = (size_t)nok / 2;
-      std::nth_element(xs.begin(), xs.begin() + h, xs.end());
-      double med = xs[h];
-      if (nok % 2 == 0) med = (*std::max_element(xs.begin(), xs.begin() + h) + med) / 2.0;
-      if (med == 0.0) med = 1.0;
-      const double floor_x = 1e-5 * med, shift = -lm_digamma(0.5 * d) + std::log(0.5 * d);
-      double esum = 0.0, xsum = 0.0;
-      std::vector<double> e;
-      e.reserve((size_t)nok);
-      for (size_t r = 0; r < R; ++r) {   // (in row order: the sums below are pinned as ascending)
-        if (!std::isfinite(s[r])) continue;
-        const double x = std::max(s[r], floor_x);
-        e.push_back(std::log(x) + shift);
-        esum += e.back();
-        xsum += x;
-      }
-      const double ebar = esum / (double)nok;
-      double ss = 0.0;
-      for (double ei : e) ss += (ei - ebar) * (ei - ebar);
-      const double var = ss / (double)(nok - 1) - lm_trigamma(0.5 * d);
-      if (var > 0.0) {
-        const double y = lm_trigamma_inverse(var);
-        d0 = 2.0 * y;
-        s0 = std::exp(ebar + lm_digamma(y) - std::log(y));
-      } else {
-        d0 = inf;
-        s0 = xsum / (double)nok;
-      }
-    }
-    hyper[4 * (size_t)f] = d;
-    hyper[4 * (size_t)f + 1] = d0;
-    hyper[4 * (size_t)f + 2] = s0;
-    hyper[4 * (size_t)f + 3] = (double)nok;
-    dft[(size_t)f] = std::isinf(d0) ? (double)nok * d : std::min(d + d0, (double)nok * d);
-    double* po = post.data() + R * f;
-    for (size_t r = 0; r < R; ++r)
-      po[r] = !std::isfinite(s[r]) ? nan : std::isinf(d0) ? s0 : d0 == 0.0 ? s[r] : (d * s[r] + d0 * s0) / (d + d0);
-  }
-  // logFC, AveExpr, t, P.Value and sigma2 of every (fit, contrast, row): row chunks dealt to the threads
-  const int64_t ncol = (int64_t)nfit * q, items = ncol * rows;
-  const int32_t W1 = p + 1;
-  auto tails = [&](int64_t t, int64_t nth) {
-    const int64_t lo = items * t / nth, hi = items * (t + 1) / nth;
-    for (int64_t e = lo; e < hi; ++e) {
-      const int64_t col = e / rows;
-      const size_t r = (size_t)(e % rows);
-      const int32_t f = (int32_t)(col / q), j = (int32_t)(col % q);
-      double* o = out + (size_t)col * 6 * R;
-      const double sr = s2[R * f + r];
-      if (!std::isfinite(sr)) {
-        for (int c = 0; c < 6; ++c) o[(size_t)c * R + r] = nan;
-        continue;
-      }
-      const double* vj = v + ((size_t)f * q + j) * p;
-      double fc = 0.0;
-      for (int32_t k = 0; k < p; ++k) fc = std::fma(vj[k], E[((size_t)f * W1 + k) * R + r], fc);
-      const double tt = fc / (u[(size_t)f * q + j] * std::sqrt(post[R * f + r]));
-      o[r] = fc;
-      o[R + r] = E[((size_t)f * W1 + p) * R + r];
-      o[2 * R + r] = tt;
-      o[3 * R + r] = t_two_sided_p(tt, dft[(size_t)f]);
-      o[5 * R + r] = sr;
-    }
-  };
-  const int64_t nth = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, items / kLimmaWork}));
-  if (!lm_threads(nth, tails)) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
-  auto adjust = [&](int64_t t, int64_t nt) {
-    for (int64_t col = t; col < ncol; col += nt) {
-      double* o = out + (size_t)col * 6 * R;
-      p_adjust_fdr(o + 3 * R, rows, o + 4 * R);
-    }
-  };
-  const int64_t nbh = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, items / kLimmaWork, ncol}));
-  if (!lm_threads(nbh, adjust)) { set_error("out of host memory"); return PLAIDHIP_ENOMEM; }
+  PH_REQUIRE(rows == 0 || nfit == 0 || q == 0 || (drow != nullptr && urow != nullptr), "limma_finish_na: null argument");
+  return limma_finish_rows("limma_finish_na", rows, p, nfit, q, E, rss, nf, v, urow, drow, urow, out, hyper, 5);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_na_solve(int32_t p, int32_t nmis, const double* qmis, const double* Ep, int64_t nobs, const double* v,
+                            int32_t q, double* gamma, double* u, double* pivots, int32_t* ok) try {
+  using namespace plaidhip;
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "limma_na_solve: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_NA_MAX_COEF);
+  PH_REQUIRE(nmis >= 0 && q >= 0, "limma_na_solve: bad dims nmis=%d q=%d", nmis, q);
+  PH_REQUIRE((qmis || nmis == 0) && Ep && (v || q == 0) && gamma && (u || q == 0) && ok, "limma_na_solve: null argument");
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  constexpr int P = PLAIDHIP_LIMMA_NA_MAX_COEF;
+  double H[P * P], w[P];
+  for (int k = 0; k < p; ++k)
+    for (int l = 0; l <= k; ++l) H[k * P + l] = (k == l ? 1.0 : 0.0) - lmfit_na_gram_chain(qmis + k, qmis + l, p, nmis);
+  double piv[P];
+  for (int k = 0; k < p; ++k) piv[k] = nan;
+  *ok = lmfit_na_factor_solve(p, H, P, Ep, gamma, piv) && nobs - p >= 1 ? 1 : 0;
+  if (!*ok)
+    for (int k = 0; k < p; ++k) gamma[k] = nan;
+  if (pivots != nullptr) std::copy(piv, piv + p, pivots);
+  for (int32_t j = 0; j < q; ++j) u[j] = *ok ? lmfit_na_unscaled(p, H, P, v + (size_t)j * p, w) : nan;
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 

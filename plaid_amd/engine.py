@@ -532,6 +532,9 @@ def _is_sparse(X):
 LIMMA_MAX_COEF = 32   # PLAIDHIP_LIMMA_MAX_COEF
 LIMMA_COLUMNS = ("logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2")
 LIMMA_HYPER = ("df.residual", "df.prior", "s2.prior", "n.ok")
+LIMMA_NA_MAX_COEF = 10   # PLAIDHIP_LIMMA_NA_MAX_COEF
+LIMMA_HYPER_NA = LIMMA_HYPER + ("df.pooled",)
+LIMMA_NA = ("propagate", "fit")
 
 
 def limma_tile() -> int:
@@ -583,6 +586,70 @@ def _limma(fn, head, A, design, use=None, contrasts=None, out=None, hyper=None):
     hyper = np.full((nfit, 4), np.nan, dtype=np.float64) if hyper is None else hyper
     check(fn(*head, _np_ptr(A), rows, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
              q, _np_ptr(out), _np_ptr(hyper)))
+    return out, hyper
+
+
+def _limma_na(fn, head, A, design, use=None, contrasts=None, max_na=0.2, out=None, hyper=None, dfres=None):
+    """plaidhip_limma_na / _multi / the hook (na = "fit"): (out, hyper, dfres) -- rows x 6 x q x nfit, nfit x 5
+    (LIMMA_HYPER_NA) and rows x nfit, the df.residual of every fitted (row, fit), NaN for the others"""
+    A = _as_f64_fortran(A)
+    if A.ndim != 2:
+        raise ValueError("limma: the matrix must be rows x samples")
+    rows, n = A.shape
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    out = np.full((rows, 6, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 5), np.nan, dtype=np.float64) if hyper is None else hyper
+    dfres = np.full((rows, nfit), np.nan, dtype=np.float64, order="F") if dfres is None else dfres
+    check(fn(*head, _np_ptr(A), rows, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+             q, float(max_na), _np_ptr(out), _np_ptr(hyper), _np_ptr(dfres)))
+    return out, hyper, dfres
+
+
+def _limma_any(fn, fn_na, head, A, design, use, contrasts, na, max_na):
+    if na not in LIMMA_NA:
+        raise ValueError(f"limma: na must be one of {LIMMA_NA}")
+    if na == "fit":
+        return _limma_na(fn_na, head, A, design, use, contrasts, max_na)
+    return _limma(fn, head, A, design, use, contrasts)
+
+
+def limma_na_solve(qmis, Ep, nobs, v) -> dict:
+    """plaidhip_limma_na_solve on the host (no device is touched): the refit of one incomplete row.  qmis: nmis x p, the rows
+    of Q_f of its missing samples in ascending order; Ep: E' (p); nobs: its observed samples; v: p x q -> gamma (p), u (q),
+    the Cholesky pivots (p) and ok"""
+    qmis = np.ascontiguousarray(np.asarray(qmis, dtype=np.float64))
+    Ep = np.ascontiguousarray(np.asarray(Ep, dtype=np.float64))
+    p = Ep.shape[0]
+    qmis = qmis.reshape(-1, p)
+    v = np.asfortranarray(np.asarray(v, dtype=np.float64).reshape(p, -1))
+    q = v.shape[1]
+    gamma, u, piv = np.full(p, -7.0), np.full(q, -7.0), np.full(p, -7.0)
+    ok = C.c_int32(-7)
+    check(_lib.load().plaidhip_limma_na_solve(p, qmis.shape[0], _np_ptr(qmis), _np_ptr(Ep), int(nobs), _np_ptr(v), q,
+                                              _np_ptr(gamma), _np_ptr(u), _np_ptr(piv), C.cast(C.byref(ok), C.c_void_p)))
+    return {"gamma": gamma, "u": u, "pivots": piv, "ok": bool(ok.value)}
+
+
+def limma_finish_na(E, rss, nf, v, drow, urow):
+    """plaidhip_limma_finish_na on the host: limma_finish with the rows' own df.residual drow (nfit x rows, NaN: not fitted)
+    and u (nfit q x rows) -> (out rows x 6 x q x nfit, hyper nfit x 5)"""
+    v = np.asarray(v, dtype=np.float64)
+    v = v[:, :, None] if v.ndim == 2 else v
+    p, q, nfit = v.shape
+    E = np.ascontiguousarray(np.asarray(E, dtype=np.float64).reshape(nfit * (p + 1), -1))
+    rows = E.shape[1]
+    rss = np.ascontiguousarray(np.asarray(rss, dtype=np.float64).reshape(nfit, rows))
+    drow = np.ascontiguousarray(np.asarray(drow, dtype=np.float64).reshape(nfit, rows))
+    urow = np.ascontiguousarray(np.asarray(urow, dtype=np.float64).reshape(nfit * q, rows))
+    nf = np.ascontiguousarray(np.atleast_1d(nf), dtype=np.int64)
+    v = np.asfortranarray(v)
+    if nf.shape != (nfit,):
+        raise ValueError("limma_finish_na: nf has one entry per fit")
+    out = np.full((rows, 6, q, nfit), np.nan, dtype=np.float64, order="F")
+    hyper = np.full((nfit, 5), np.nan, dtype=np.float64)
+    check(_lib.load().plaidhip_limma_finish_na(rows, p, nfit, q, _np_ptr(E), _np_ptr(rss), _np_ptr(nf), _np_ptr(v), _np_ptr(drow),
+                                               _np_ptr(urow), _np_ptr(out), _np_ptr(hyper)))
     return out, hyper
 
 
@@ -1040,11 +1107,15 @@ class Context:
         ns = nst.value
         return {"stages": ns, "status": end.value, "m": m_out[:ns].copy(), "s": s_out[:ns].copy(), "h": h_out[:ns].copy()}
 
-    def limma(self, A, design, use=None, contrasts=None):
+    def limma(self, A, design, use=None, contrasts=None, na="propagate", max_na=0.2):
         """plaidhip_limma: moderated t-tests of the rows of A (rows x samples) for the designs (samples x p, or x p x nfit),
         the samples `use` leaves out (samples x nfit, None: none) and the contrasts (p x q, None: every coefficient):
-        (out rows x 6 x q x nfit in LIMMA_COLUMNS, hyper nfit x 4 in LIMMA_HYPER)"""
-        return _limma(self.lib.plaidhip_limma, (self.handle,), A, design, use, contrasts)
+        (out rows x 6 x q x nfit in LIMMA_COLUMNS, hyper nfit x 4 in LIMMA_HYPER).  na = "fit" (plaidhip_limma_na): rows with at
+        most the share max_na of NaN are refitted on the samples they have, and the result is (out, hyper nfit x 5 in
+        LIMMA_HYPER_NA, dfres rows x nfit: the df.residual of every fitted row, NaN for the others); at most
+        LIMMA_NA_MAX_COEF coefficients"""
+        return _limma_any(self.lib.plaidhip_limma, self.lib.plaidhip_limma_na, (self.handle,), A, design, use, contrasts, na,
+                          max_na)
 
     def dev_row_design_effects(self, A: int, ld: int, rows: int, n: int, Q: int, use, invn: int, p: int, nfit: int, seed, E: int):
         """plaidhip_dev_row_design_effects on device pointers: E [nfit (p + 1)][rows]; use and seed may be None"""
@@ -1293,9 +1364,11 @@ def zscore_multi(X, Gp, Gi, devices=1):
     return _zscore(*_multi("zscore", devices), X, Gp, Gi)
 
 
-def limma_multi(A, design, use=None, contrasts=None, devices=1):
-    """plaid.limma (Context.limma) with the sample columns sharded over `devices`: the one-device bits"""
-    return _limma(*_multi("limma", devices), A, design, use, contrasts)
+def limma_multi(A, design, use=None, contrasts=None, devices=1, na="propagate", max_na=0.2):
+    """plaid.limma (Context.limma) with the sample columns sharded over `devices`: the one-device bits.  Returns (out, hyper),
+    or with na = "fit" (out, hyper nfit x 5, dfres rows x nfit) as Context.limma does"""
+    fn, head = _multi("limma", devices)
+    return _limma_any(fn, _multi("limma_na", devices)[0], head, A, design, use, contrasts, na, max_na)
 
 
 def multi_finalize():

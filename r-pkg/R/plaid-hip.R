@@ -667,9 +667,13 @@ plaid.rankcor <- function(stat, G, use.rank = TRUE, compute.p = TRUE, ties = c("
 ## "none" (the rows of S), "P.Value" / "P" / "p" (increasing), "t" and "logFC" (decreasing magnitude), "AveExpr" (decreasing)
 .limma_sorts <- c("none", "P.Value", "P", "p", "t", "logFC", "AveExpr")
 
-.limma_table <- function(tab, rn, sort.by) {
+.limma_table <- function(tab, rn, sort.by, dfr = NULL) {
   cols <- c("logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "sigma2")
   res <- matrix(tab, nrow = length(rn), ncol = 6L, dimnames = list(rn, cols))
+  if (!is.null(dfr)) {   # na = "fit": the rows' own df.residual, NA where the row is NA
+    dfr[is.na(res[, "sigma2"])] <- NA_real_
+    res <- cbind(res, df.residual = dfr)
+  }
   key <- switch(sort.by, none = NULL, P.Value = , P = , p = res[, "P.Value"], t = -abs(res[, "t"]),
                 logFC = -abs(res[, "logFC"]), AveExpr = -res[, "AveExpr"],
                 stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", ")))
@@ -677,7 +681,23 @@ plaid.rankcor <- function(stat, G, use.rank = TRUE, compute.p = TRUE, ties = c("
   res
 }
 
-.limma_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok"))
+.limma_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok", "df.pooled")[seq_along(h)])
+
+## the library call behind both: na = "propagate" is plaidhip_limma; na = "fit" is plaidhip_limma_na, whose tables get the
+## rows' own df.residual as a seventh column (NA where the row is NA)
+.limma_call <- function(S, D, nfit, use, K, na, max.na, ncon, rn, sort.by) {
+  if (na == "propagate") {
+    r <- .Call("R_plaidhip_limma", .devices(), S, D, nfit, use, K, PACKAGE = "plaidhip")
+  } else {
+    if (length(max.na) != 1L || is.na(max.na) || max.na < 0 || max.na > 1) stop("plaid.limma: max.na must be a share in [0, 1]")
+    r <- .Call("R_plaidhip_limma_na", .devices(), S, D, nfit, use, K, as.double(max.na), PACKAGE = "plaidhip")
+  }
+  out <- r[[1]]
+  dim(out) <- c(nrow(S), 6L, ncon)
+  tables <- lapply(seq_len(ncon), function(j)
+    .limma_table(out[, , j], rn, sort.by, if (na == "fit") r[[3]][, if (nfit == 1L) 1L else j] else NULL))
+  list(tables = tables, hyper = r[[2]])
+}
 
 
 ## plaid.limma(): limma's moderated t-test (lmFit + eBayes + topTable, as pinned in include/plaidhip.h: plaidhip_limma) of
@@ -685,9 +705,13 @@ plaid.rankcor <- function(stat, G, use.rank = TRUE, compute.p = TRUE, ties = c("
 ## coefficients).  contrasts: coefficients x contrasts, NULL: every coefficient.  use: one entry per sample, FALSE / 0 / NA
 ## leaves it out of the fit.  Returns list(tables = <named list, one matrix per contrast: rows x (logFC, AveExpr, t, P.Value,
 ## adj.P.Val, sigma2), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok)).  logFC and P.Value are what
-## plaid.sig() and plaid.gsea() take.  Not offered: trend, robust, weights, the B- and F-statistics, per-row missing values
-## (an NA in a used sample makes the row NA), a sparse S.
-plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none") {
+## plaid.sig() and plaid.gsea() take.  na = "propagate": an NA in a used sample makes the row NA.  na = "fit": limma's own
+## handling -- a row with at most the share max.na of NA over all samples (gx.limma's max.na) is refitted on the samples it
+## has, with its own df.residual (a seventh column of the tables) and stdev.unscaled, and eBayes takes the unequal df
+## (hyper gains df.pooled); a row above max.na, or not estimable on what it has, is NA; at most 10 coefficients.
+## Not offered: trend, robust, weights, the B- and F-statistics, a sparse S.
+plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none", na = c("propagate", "fit"), max.na = 0.2) {
+  na <- match.arg(na)
   S <- as.matrix(S); storage.mode(S) <- "double"
   design <- as.matrix(design); storage.mode(design) <- "double"
   if (nrow(design) != ncol(S)) stop("design must have one row per column of S")
@@ -704,12 +728,10 @@ plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none
   rn <- if (is.null(rownames(S))) paste0("row", seq_len(nrow(S))) else rownames(S)
   if (length(sort.by) != 1L || !sort.by %in% .limma_sorts) stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", "))
   .session()
-  r <- .Call("R_plaidhip_limma", .devices(), S, design, 1L, use, contrasts, PACKAGE = "plaidhip")
-  out <- r[[1]]
-  dim(out) <- c(nrow(S), 6L, length(cn))
-  tables <- lapply(seq_along(cn), function(j) .limma_table(out[, , j], rn, sort.by))
+  r <- .limma_call(S, design, 1L, use, contrasts, na, max.na, length(cn), rn, sort.by)
+  tables <- r$tables
   names(tables) <- cn
-  list(tables = tables, hyper = .limma_hyper(r[[2]][, 1]))
+  list(tables = tables, hyper = .limma_hyper(r$hyper[, 1]))
 }
 
 
@@ -717,8 +739,10 @@ plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none
 ## matrix Y (samples x contrasts; 0, 1, NA = the sample takes no part) in ONE call: contrast j fits [1, Y[, j], B] on the
 ## samples with a label and tests the coefficient of Y[, j].  B: batch covariates (samples x covariates) or NULL.  S is
 ## uploaded once and read ceiling(ncol(Y) * (p + 1) / 8) times for the effects.  Returns list(tables = <named list (the
-## columns of Y) of plaid.limma() tables>, hyper = <named list of their hyper-parameters>).
-plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none") {
+## columns of Y) of plaid.limma() tables>, hyper = <named list of their hyper-parameters>).  na, max.na: as plaid.limma();
+## na = "fit" with max.na = 0.2 is gx.limma(S, y, B, max.na = 0.20) on a matrix with missing values.
+plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none", na = c("propagate", "fit"), max.na = 0.2) {
+  na <- match.arg(na)
   S <- as.matrix(S); storage.mode(S) <- "double"
   Y <- as.matrix(Y)
   if (nrow(Y) != ncol(S)) stop("Y must have one row per column of S")
@@ -736,11 +760,9 @@ plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none") {
   rn <- if (is.null(rownames(S))) paste0("row", seq_len(nrow(S))) else rownames(S)
   if (length(sort.by) != 1L || !sort.by %in% .limma_sorts) stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", "))
   .session()
-  r <- .Call("R_plaidhip_limma", .devices(), S, D, ncol(Y), use, K, PACKAGE = "plaidhip")
-  out <- r[[1]]
-  dim(out) <- c(nrow(S), 6L, ncol(Y))
-  tables <- lapply(seq_len(ncol(Y)), function(j) .limma_table(out[, , j], rn, sort.by))
-  hyper <- lapply(seq_len(ncol(Y)), function(j) .limma_hyper(r[[2]][, j]))
+  r <- .limma_call(S, D, ncol(Y), use, K, na, max.na, ncol(Y), rn, sort.by)
+  tables <- r$tables
+  hyper <- lapply(seq_len(ncol(Y)), function(j) .limma_hyper(r$hyper[, j]))
   names(tables) <- names(hyper) <- cn
   list(tables = tables, hyper = hyper)
 }

@@ -724,6 +724,44 @@ SEXP R_plaidhip_limma(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use, S
   return res;
 }
 
+/* plaid.limma(na = "fit"): list(out, hyper, dfres) of plaidhip_limma_na -- R_plaidhip_limma's operands and max_na; hyper 5 x
+ * nfit (df.pooled last), dfres rows x nfit (the df.residual of every fitted row, NaN for the others) */
+SEXP R_plaidhip_limma_na(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use, SEXP K, SEXP max_na_) {
+  const int rows = Rf_nrows(A), n = Rf_ncols(A), nfit = Rf_asInteger(nfit_);
+  const double max_na = Rf_asReal(max_na_);
+  if (nfit < 1 || Rf_nrows(design) != n || Rf_ncols(design) % nfit != 0)
+    Rf_error("plaid.limma: design must have one row per sample and the same number of columns for every fit");
+  const int p = Rf_ncols(design) / nfit;
+  const int q = Rf_isNull(K) ? p : Rf_ncols(K);
+  if (!Rf_isNull(K) && Rf_nrows(K) != p) Rf_error("plaid.limma: contrasts must have one row per coefficient");
+  int8_t* u8 = NULL;
+  if (!Rf_isNull(use)) {
+    if (Rf_nrows(use) != n || Rf_ncols(use) != nfit) Rf_error("plaid.limma: use must be samples x fits");
+    const size_t count = (size_t)n * (size_t)nfit;
+    const int* u = INTEGER(use);
+    u8 = (int8_t*)R_alloc(count > 0 ? count : 1, 1);
+    for (size_t e = 0; e < count; ++e) u8[e] = (int8_t)(u[e] != 0 && u[e] != NA_INTEGER);
+  }
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, rows, 6 * q * nfit));
+  SEXP hyper = PROTECT(Rf_allocMatrix(REALSXP, 5, nfit));
+  SEXP dfres = PROTECT(Rf_allocMatrix(REALSXP, rows, nfit));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, hyper);
+  SET_VECTOR_ELT(res, 2, dfres);
+  const double* Kp = Rf_isNull(K) ? NULL : REAL(K);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_limma_na_multi(INTEGER(devices), LENGTH(devices), REAL(A), rows, n, REAL(design), p, nfit, u8, Kp, q, max_na,
+                                 REAL(out), REAL(hyper), REAL(dfres));
+  else
+    rc = plaidhip_limma_na(ctx(), REAL(A), rows, n, REAL(design), p, nfit, u8, Kp, q, max_na, REAL(out), REAL(hyper),
+                           REAL(dfres));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(4);
+  return res;
+}
+
 /* plaid.rankcor(): list(out, tot) of plaidhip_rankcor -- out an m x 5c matrix (columns 5 l + 1 .. 5 l + 5 the columns of list
  * l; the caller gives it dim m x 5 x c), tot the c universe sizes.  stat: a g x c double matrix, NA / NaN: the gene takes no
  * part in that list; ties: 0 average, 1 min, 2 max; several devices: the _multi entry */
@@ -838,6 +876,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_gsea_multilevel", (DL_FUNC)&R_plaidhip_gsea_multilevel, 12},
     {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
     {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
+    {"R_plaidhip_limma_na", (DL_FUNC)&R_plaidhip_limma_na, 7},
     {"R_plaidhip_rankcor", (DL_FUNC)&R_plaidhip_rankcor, 6},
     {"R_plaidhip_plage", (DL_FUNC)&R_plaidhip_plage, 11},
     {"R_plaidhip_zscore", (DL_FUNC)&R_plaidhip_zscore, 8},

@@ -211,8 +211,38 @@ static void limma() {
       REQUIRE(std::isnan(pv) || (pv >= 0.0 && pv <= 1.0));
     }
     REQUIRE(hyper[3] == (double)(rows >= 3 ? rows - 1 : rows));
+    // na = "fit": the rows' own df.residual (three values, NaN for a row that is not fitted) and u
+    std::vector<double> drow((size_t)nfit * rows), urow((size_t)nfit * q * rows, 0.5), hyper5((size_t)nfit * 5);
+    for (size_t e = 0; e < drow.size(); ++e) drow[e] = (double)(1 + e % 3);
+    if (rows >= 3) drow[2] = NAN;
+    REQUIRE(plaidhip_limma_finish_na(rows, p, nfit, q, E.data(), rss.data(), nf, v.data(), drow.data(), urow.data(), out.data(),
+                                     hyper5.data()) == PLAIDHIP_OK);
+    REQUIRE(hyper5[3] == (double)(rows >= 3 ? rows - 2 : rows));
+    REQUIRE(rows < 3 || std::isnan(out[2]));
   }
-  printf("  limma: designs of 1, 2, 3 and 32 coefficients, refused ones, and the finish step up to 70,001 rows on host threads\n");
+  // one incomplete row through the shared solve (csrc/lmfit_na.h) at every p: the rows of an orthonormal Q that are missing
+  for (int p = 1; p <= PLAIDHIP_LIMMA_NA_MAX_COEF; ++p) {
+    const int n = 24, q = 2;
+    std::vector<double> D((size_t)n * p), Q((size_t)n * p), R((size_t)p * p), v((size_t)p * q), u((size_t)q), K((size_t)p * q);
+    for (auto& x : D) x = N(rng);
+    for (auto& x : K) x = N(rng);
+    int64_t nf = 0;
+    REQUIRE(plaidhip_limma_design(D.data(), n, p, nullptr, K.data(), q, 1, Q.data(), R.data(), v.data(), u.data(), &nf) == PLAIDHIP_OK);
+    for (int nmis : {0, 1, 5, n - p}) {   // (n - p missing: no residual degree of freedom)
+      std::vector<double> qmis((size_t)(nmis > 0 ? nmis : 1) * p), Ep((size_t)p), gamma((size_t)p), uu((size_t)q), piv((size_t)p);
+      for (int i = 0; i < nmis; ++i)
+        for (int k = 0; k < p; ++k) qmis[(size_t)i * p + k] = Q[(size_t)k * n + i];
+      for (auto& x : Ep) x = N(rng);
+      int32_t ok = -1;
+      REQUIRE(plaidhip_limma_na_solve(p, nmis, qmis.data(), Ep.data(), n - nmis, v.data(), q, gamma.data(), uu.data(), piv.data(),
+                                      &ok) == PLAIDHIP_OK);
+      REQUIRE(ok == (nmis < n - p ? 1 : 0));
+      if (ok) for (int j = 0; j < q; ++j) REQUIRE(uu[(size_t)j] >= u[(size_t)j] * (1.0 - 1e-12));   // missing samples never shrink it
+      if (nmis == 0) for (int k = 0; k < p; ++k) REQUIRE(gamma[(size_t)k] == Ep[(size_t)k]);
+    }
+  }
+  printf("  limma: designs of 1, 2, 3 and 32 coefficients, refused ones, the finish step up to 70,001 rows on host threads, with\n"
+         "         per-row df, and the refit of an incomplete row at 1 .. %d coefficients\n", PLAIDHIP_LIMMA_NA_MAX_COEF);
 }
 
 // plaid.rankcor's host half: plaidhip_rankcor_finish on tie-free lists at the integer limits (n = 131,072: 128-bit products),
