@@ -1354,6 +1354,84 @@ int plaidhip_limma_finish_na(int32_t rows, int32_t p, int32_t nfit, int32_t q, c
                              const int64_t* nf, const double* v, const double* drow, const double* urow, double* out,
                              double* hyper);
 
+/* plaid.camera(X, design, G, contrasts): limma's competitive gene-set test camera (Wu & Smyth 2012) for every set, contrast
+ * and design -- the one common set test that corrects a set's p-value for the correlation between its genes.  The form is
+ * limma's camera.default AS RECALLED: its source is not in this tree, so the statistic is pinned here and tested against
+ * these words restated literally (a complete QR of the design, U = Q2'x / sigma) in 50-digit arithmetic.
+ * Operands: X is g x n doubles, column-major, one row per gene; the designs D_f, use and the contrasts K are those of
+ * plaidhip_limma; G is aligned to X's rows (Gp, Gi; a member listed twice counts twice).  d = n_f - p.
+ * 1. The fit: steps 1 to 3 of plaidhip_limma, unchanged.  For (fit f, contrast j) the gene statistic is plaid.limma's t,
+ *    t_g = logFC / (u_j sqrt(s2.post)) (camera's unscaledt / sqrt(var.post)).  A gene that is not ok in fit f (s2 not
+ *    finite) leaves that fit's universe, as a NaN does in plaid.rankcor: G_f is the number of ok genes, the size m of a set
+ *    counts its ok members only.  df.camera = min(d + df.prior, G_f - 2) -- not plaid.limma's df.total.
+ * 2. Standardised residuals, per fit, on the device (kernels_camera.hip): r_gc is step 2's chain of plaidhip_limma from the
+ *    reduced effects of ALL samples, fma(-Q_f[c, k], E_k, .) in ascending k from x_c, and
+ *      z_gc = r_gc / sqrt(max(s2_g, 1e-8))  for a used sample and an ok gene,  0.0 otherwise,    s2_g = RSS_g / d:
+ *    one square root per gene and one division per element, both correctly rounded; no reciprocal is formed.  The chain's
+ *    step, the gene's divisor and the select are inline functions of csrc/camera.h, one copy for the device and for
+ *    plaidhip_camera_residual_row (a GPU test holds the device to that entry bit for bit).
+ * 3. The variance inflation factor of a set with m > 1.  limma forms U = Q2'x / sigma (g x d, Q2 an orthonormal basis of
+ *    the residual space) and takes m * mean(colMeans(U[set, ])^2).  Every residual lies in the span of Q2, so that value is
+ *      vif = || sum over the set's members of z_g ||^2 / (m d),
+ *    the norm taken in sample space over the n samples: no n x n matrix and no second QR.  T = G'Z (m x n) is the dense
+ *    crossprod of plaidhip_plaid_dense (stat = sum, fp64) applied to Z.  The squares t * t of a row of T, each rounded, are
+ *    added over the columns of a block of 128 in ascending order from 0.0, and the blocks are added in ascending order: the
+ *    order of the RSS pass.  correlation = (vif - 1) / (m - 1).  m = 1: vif = 1, correlation = NaN.  m = 0: both NaN.
+ *    allow_neg_cor = 0 (limma's default) uses max(vif, 1) in the test; the reported VIF and correlation stay as estimated.
+ * 4. A fixed correlation, inter_gene_cor = rho inside (-1, 1) (limma's current default is 0.01; NaN asks for step 3):
+ *    vif = 1 + (m - 1) rho as it stands (no max), correlation = rho, for every set with m >= 1.  Steps 2 and 3 are skipped
+ *    entirely: no Z is formed.
+ * 5. The test of (fit, contrast, set), plaidhip_camera_finish: fp64 on the host, sums over the genes in ascending order
+ *    from 0.0.  Over the ok genes' t: mean = sum / G; var = sum of (t - mean)^2 / (G - 1) (two passes).  m2 = G - m,
+ *      delta  = (G / m2) * (sumt / m - mean)                    sumt: the member sum of t
+ *      pooled = ((G - 1) var - ((delta delta) m m2) / G) / (G - 2)
+ *      T_set  = delta / sqrt(pooled * (vif / m + 1 / m2))
+ *      Down = pt(T_set, df.camera), Up the upper tail, from h = pt(-|T_set|, df.camera) (the tail of plaid.test, a real
+ *      df) and 1 - h;  PValue = 2 min(Down, Up);  Direction = Up if Up < Down, else Down (the callers' column);
+ *      FDR = Benjamini-Hochberg over the sets of each (fit, contrast), NaN rows apart.
+ *    t, Down, Up, PValue and FDR are NaN when m = 0, m2 = 0, G < 3, pooled <= 0 or pooled * (vif / m + 1 / m2) <= 0 (a
+ *    negative fixed rho on a large set); NGenes, Correlation and VIF are reported as in steps 3 and 4 all the same.
+ *    The member sums of t and the counts m come from ONE crossprod of the membership with [the t columns | the ok
+ *    indicators] (a gene that is not ok holds 0.0 in both); the counts are sums of 0 / 1 in fp64: exact.
+ * out: m x 8 x q x nfit doubles, column-major: NGenes, Correlation, VIF, t, Down, Up, PValue, FDR; contrast j of fit f at
+ * out + (f * q + j) * 8 * m.  hyper: nfit x 6 doubles, row-major per fit: plaid.limma's four (df.residual, df.prior,
+ * s2.prior, n_ok), then G_f and df.camera.  g == 0, nfit == 0, q == 0 or m == 0: PLAIDHIP_OK with nothing written.
+ * Argument errors, all PLAIDHIP_EINVAL and all found on the host before any device is touched: m < 0; those of
+ * plaidhip_limma in their order (named "camera:"); then a null Gp, Gp not starting at 0 or decreasing, a set of more than g
+ * members, a null Gi, a Gi row outside 0..g-1; then inter_gene_cor outside (-1, 1) unless it is NaN.
+ * How: Z is materialised and the crossprod reused -- gathering the members' rows of X set by set would read X about twelve
+ * times over at 5,000 sets of 50.  One fit's Z (g x n_shard) and T live in the context's buffers at a time.
+ * plaidhip_camera_multi shards the SAMPLES at multiples of 128 columns as plaidhip_limma_multi does; after its two rounds a
+ * third hands the sums of T^2 from shard to shard as [nfit][m].  T's columns do not depend on the sharding, the partial
+ * sums are those of the one-device call: every sharding, with more shards than samples too, has the one-device bits.
+ *   plaidhip_dev_camera_residuals: step 2 on device pointers, stream-ordered.  A: rows x n, leading dimension ld; Q, use as
+ *     in plaidhip_dev_row_design_rss; E [nfit (p + 1)][rows] and rss [nfit][rows] of ALL samples; `fit` counted from 0;
+ *     d = n_f - p; Z: rows x n, leading dimension ldz.  The masks live in the context's workspace.
+ *   plaidhip_dev_camera_sumsq: out[s] = seed[s] (NULL: 0.0) + the block sums of T[s, c]^2 in ascending order; T: m x n,
+ *     leading dimension ldt.  A thread owns one set and one block of 128 columns; the partials live in the workspace.
+ *   plaidhip_camera_residual_row (host only): step 2 for one gene: x (n), Q (n x p column-major, Q_f), use (n, or NULL),
+ *     E (p), the gene's rss and d; z (n).
+ *   plaidhip_camera_finish (host only): step 5.  t: g x q x nfit; ok: g x nfit int8; sumt: m x q x nfit; cnt: m x nfit;
+ *     ss: m x nfit, the sums of T^2 (NULL: the fixed inter_gene_cor); dfres, dfprior: nfit; gdf: nfit x 2 (G_f, df.camera).
+ * Not offered: use.ranks = TRUE (the rank-sum form); trend.var; array or observation weights; a dgCMatrix X; na = "fit"
+ * rows (limma's camera refuses NA; here such a gene leaves the universe); fry / roast. */
+int plaidhip_camera(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                    const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                    double inter_gene_cor, int allow_neg_cor, double* out, double* hyper);
+int plaidhip_camera_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const double* design, int32_t p,
+                          int32_t nfit, const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi,
+                          int32_t m, double inter_gene_cor, int allow_neg_cor, double* out, double* hyper);
+int plaidhip_dev_camera_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                                  const int8_t* use, int32_t p, int32_t nfit, int32_t fit, const double* E, const double* rss,
+                                  double d, double* Z, int64_t ldz);
+int plaidhip_dev_camera_sumsq(plaidhip_ctx* ctx, const double* T, int64_t ldt, int32_t m, int32_t n, const double* seed,
+                              double* out);
+int plaidhip_camera_residual_row(int32_t n, int32_t p, const double* x, const double* Q, const int8_t* use, const double* E,
+                                 double rss, double d, double* z);
+int plaidhip_camera_finish(int32_t g, int32_t m, int32_t nfit, int32_t q, const double* t, const int8_t* ok, const double* sumt,
+                           const double* cnt, const double* ss, const double* dfres, const double* dfprior,
+                           double inter_gene_cor, int allow_neg_cor, double* out, double* gdf);
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

@@ -176,6 +176,12 @@ SIGNATURES = {
     "plaidhip_limma_na_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _vp],
     "plaidhip_limma_na_solve": [_i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "plaidhip_limma_finish_na": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_camera": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _f64, _int, _vp, _vp],
+    "plaidhip_camera_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _f64, _int, _vp, _vp],
+    "plaidhip_dev_camera_residuals": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f64, _vp, _i64],
+    "plaidhip_dev_camera_sumsq": [_vp, _vp, _i64, _i32, _i32, _vp, _vp],
+    "plaidhip_camera_residual_row": [_i32, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _vp],
+    "plaidhip_camera_finish": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _int, _vp, _vp],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],
     # host-only GMT text path (gmt.cpp)
     "plaidhip_gmt_read": [C.c_char_p, _int, _i64, C.POINTER(_vp)],

@@ -968,3 +968,143 @@ def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = No
     out, hyper, hnames = _limma_run(ctx, S.values, D, lab != -1, K, na, max_na)
     tables = {nm: _limma_table(out[:, :, 0, j], S.rownames, sort_by) for j, nm in enumerate(names)}
     return tables, {nm: dict(zip(hnames, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
+
+
+_CAMERA_NAMES = ["NGenes", "Correlation", "VIF", "t", "Direction", "PValue", "FDR"]
+_CAMERA_SORT = {"none": None, "PValue": 5, "P": 5, "p": 5, "FDR": 6, "t": 3, "Correlation": 1, "VIF": 2, "NGenes": 0}
+
+
+def _camera_table(tab, rn, sort_by):
+    """sets x 8 of the library -> the NamedMatrix plaid.camera returns: Direction is +1 (Up) where Up < Down, else -1 (Down),
+    NaN on a NaN row; ordered by `sort_by` -- "none", "PValue" / "P" / "p" and "FDR" (increasing), "t", "Correlation", "VIF"
+    (decreasing magnitude), "NGenes" (decreasing); stable, NaN last"""
+    if sort_by not in _CAMERA_SORT:
+        raise ValueError(f"plaid.camera: sort_by must be one of {sorted(_CAMERA_SORT)}")
+    down, up = tab[:, 4], tab[:, 5]
+    direction = np.where(np.isnan(up) | np.isnan(down), np.nan, np.where(up < down, 1.0, -1.0))
+    tab = np.column_stack([tab[:, 0:4], direction, tab[:, 6:8]])
+    rn = list(rn)
+    col = _CAMERA_SORT[sort_by]
+    if col is not None:
+        key = tab[:, col] if col in (5, 6) else -tab[:, col] if col == 0 else -np.abs(tab[:, col])
+        o = np.argsort(key, kind="stable")
+        tab, rn = tab[o, :], [rn[k] for k in o]
+    return NamedMatrix(tab, rn, _CAMERA_NAMES)
+
+
+def _camera_sets(who, X, G, minSize, maxSize):
+    """X (genes x samples, a NamedMatrix) and G (a gmt or a membership matrix): every row of X stays -- camera's universe is
+    all the genes, also those in no set -- and the members of G are mapped to the rows of X by name (a name X does not have
+    is dropped; the first of a repeated name counts).  Sets outside minSize .. maxSize (default: the genes - 1) mapped members
+    are dropped: (Xs, Gp, Gi, names)"""
+    if isinstance(G, (GmtList, dict)) or (isinstance(G, tuple) and len(G) == 2):
+        _message(f"[{who}] converting gmt to sparse matrix...")
+        G = gmt2mat(G)
+    X, G = as_named(X), as_named(G)
+    if X.is_sparse:
+        raise ValueError(f"{who}: X must be dense")
+    posx = _first_pos(X.rownames)
+    seen, grow, xrow = set(), [], []
+    for k, nm in enumerate(G.rownames):
+        if nm in seen:
+            continue
+        seen.add(nm)
+        r = posx.get(nm)
+        if r is not None:
+            grow.append(k)
+            xrow.append(r)
+    Gs = sp.csc_matrix(G.values)[grow, :].tocsc()
+    xrow = np.asarray(xrow, dtype=np.int32)
+    sets = [np.sort(xrow[Gs.indices[Gs.indptr[j]:Gs.indptr[j + 1]][Gs.data[Gs.indptr[j]:Gs.indptr[j + 1]] != 0]])
+            for j in range(Gs.shape[1])]
+    hi = X.shape[0] - 1 if maxSize is None else int(maxSize)
+    keep = [j for j, s_ in enumerate(sets) if int(minSize) <= len(s_) <= hi]
+    Gi = np.concatenate([sets[j] for j in keep]).astype(np.int32) if keep else np.zeros(0, np.int32)
+    Gp = np.concatenate([[0], np.cumsum([len(sets[j]) for j in keep])]).astype(np.int32)
+    return np.asfortranarray(np.asarray(X.values), dtype=np.float64), Gp, Gi, [G.colnames[j] for j in keep]
+
+
+def plaid_camera(X, design, G, contrasts=None, use=None, inter_gene_cor=0.01, allow_neg_cor=False, minSize=1, maxSize=None,
+                 sort_by="PValue", ctx: Context | None = None):
+    """plaid.camera(): limma's competitive gene-set test camera (Wu & Smyth 2012, as pinned in include/plaidhip.h) of every set
+    of G (a gmt or a membership matrix) on the expression X (a genes x samples NamedMatrix) for one design (samples x
+    coefficients; a NamedMatrix names the coefficients).  contrasts, use: as plaid_limma.  The gene statistic is
+    plaid_limma's moderated t; a set's two-sample t against the other genes is corrected by the variance inflation factor
+    1 + (m - 1) rho.  inter_gene_cor: the fixed rho (limma's default 0.01), or None to estimate every set's VIF from the
+    residuals of its genes (allow_neg_cor = False then uses max(VIF, 1) in the test; the reported VIF and Correlation stay
+    as estimated).  The universe is every row of X, also the genes in no set; the members of G are found in X by name.  A
+    gene with a NaN or Inf in a used sample leaves the universe.  Sets with fewer than minSize or more than maxSize
+    (default: the genes - 1) members in X are dropped.  Returns (tables, hyper): tables is a dict, contrast name -> NamedMatrix (sets x [NGenes, Correlation, VIF, t,
+    Direction (+1 Up, -1 Down), PValue, FDR]) ordered by `sort_by` (default "PValue"; stable, NaN last); hyper a dict of
+    plaid_limma's four values, n.genes and df.camera.
+    Not offered: use.ranks, trend.var, weights, a sparse X, na = "fit", fry / roast."""
+    Xs, Gp, Gi, rn = _camera_sets("plaid.camera", X, G, minSize, maxSize)
+    Dn = design if isinstance(design, NamedMatrix) else None
+    Dv = np.asarray(Dn.values if Dn is not None else design, dtype=np.float64)
+    if Dv.ndim != 2:
+        raise ValueError("plaid.camera: design must be samples x coefficients")
+    coef = list(Dn.colnames) if Dn is not None else [f"coef{k + 1}" for k in range(Dv.shape[1])]
+    if contrasts is None:
+        Kv, names = None, coef
+    else:
+        Kn = contrasts if isinstance(contrasts, NamedMatrix) else None
+        Kv = np.asarray(Kn.values if Kn is not None else contrasts, dtype=np.float64)
+        Kv = Kv[:, None] if Kv.ndim == 1 else Kv
+        names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
+    _camera_table(np.zeros((0, 8)), [], sort_by)   # (an unknown sort_by and a correlation outside (-1, 1): before the device)
+    from .engine import CAMERA_HYPER, check_camera_cor
+    check_camera_cor(inter_gene_cor)
+    ctx = ctx or default_context()
+    out, hyper = ctx.camera(Xs, Dv, Gp, Gi, use, Kv, inter_gene_cor, allow_neg_cor)
+    tables = {nm: _camera_table(out[:, :, j, 0], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, dict(zip(CAMERA_HYPER, (float(x) for x in hyper[0])))
+
+
+def plaid_camera_contrasts(X, Y, G, B=None, inter_gene_cor=0.01, allow_neg_cor=False, minSize=1, maxSize=None,
+                           sort_by="PValue", ctx: Context | None = None):
+    """plaid.camera.contrasts(): plaid_camera for every column of the contrast matrix Y (samples x contrasts; 0, 1, and NaN or
+    -1 for a sample that takes no part) in one call, with the designs of plaid_limma_contrasts: contrast j fits [1, Y[, j], B]
+    on the samples with a label and tests the sets on the moderated t of the coefficient of Y[, j].  X is uploaded once.
+    Returns (tables, hyper): contrast name -> the NamedMatrix plaid_camera returns, and contrast name -> its
+    hyper-parameters.  Contrast j has the bits of plaid_camera on that contrast's design and samples."""
+    from .engine import CAMERA_HYPER, check_camera_cor, contrast_labels
+    check_camera_cor(inter_gene_cor)
+    Xs, Gp, Gi, rn = _camera_sets("plaid.camera", X, G, minSize, maxSize)
+    n = Xs.shape[1]
+    Yn = Y if isinstance(Y, NamedMatrix) else None
+    lab = contrast_labels(Yn.values if Yn is not None else Y, n)
+    if not np.all(np.isin(lab, (0, 1, -1))):
+        raise ValueError("elements of Y must be 0, 1 or NA")
+    ncon = lab.shape[1]
+    names = list(Yn.colnames) if Yn is not None and Yn.colnames is not None else [str(j + 1) for j in range(ncon)]
+    Bv = np.zeros((n, 0)) if B is None else np.asarray(B.values if isinstance(B, NamedMatrix) else B, dtype=np.float64)
+    Bv = Bv[:, None] if Bv.ndim == 1 else Bv
+    if Bv.ndim != 2 or Bv.shape[0] != n:
+        raise ValueError("B must have one row per column of X")
+    p = 2 + Bv.shape[1]
+    D = np.empty((n, p, ncon), order="F")
+    D[:, 0, :] = 1.0
+    D[:, 1, :] = np.where(lab == 1, 1.0, 0.0)
+    D[:, 2:, :] = Bv[:, :, None]
+    K = np.zeros((p, 1))
+    K[1, 0] = 1.0
+    _camera_table(np.zeros((0, 8)), [], sort_by)
+    ctx = ctx or default_context()
+    out, hyper = ctx.camera(Xs, D, Gp, Gi, lab != -1, K, inter_gene_cor, allow_neg_cor)
+    tables = {nm: _camera_table(out[:, :, 0, j], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, {nm: dict(zip(CAMERA_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
+
+
+def plaid_intergenecor(X, design, G, use=None, minSize=1, maxSize=None, ctx: Context | None = None):
+    """plaid.intergenecor(): limma's interGeneCorrelation(X[set, ], design) for every set of G at once -- the variance
+    inflation factor of the set's mean, estimated from the residuals of its genes, and the mean pairwise correlation
+    (VIF - 1) / (m - 1) it stands for.  Returns a NamedMatrix, sets x [NGenes, Correlation, VIF], in G's order."""
+    Xs, Gp, Gi, rn = _camera_sets("plaid.intergenecor", X, G, minSize, maxSize)
+    Dv = np.asarray(design.values if isinstance(design, NamedMatrix) else design, dtype=np.float64)
+    if Dv.ndim != 2:
+        raise ValueError("plaid.intergenecor: design must be samples x coefficients")
+    K = np.zeros((Dv.shape[1], 1))
+    K[0, 0] = 1.0   # (any contrast: the VIF does not depend on it)
+    ctx = ctx or default_context()
+    out, _ = ctx.camera(Xs, Dv, Gp, Gi, use, K, None, True)
+    return NamedMatrix(np.ascontiguousarray(out[:, 0:3, 0, 0]), rn, _CAMERA_NAMES[:3])

@@ -1312,6 +1312,49 @@ int plaidhip_dev_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, 
 
 int plaidhip_limma_tile(void) { return PLAIDHIP_LIMMA_TILE; }
 
+// plaid.camera: the one-device form of the sharded engine (multi.cpp: limma_worker with kCamera, camera_tail)
+int plaidhip_camera(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                    const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                    double inter_gene_cor, int allow_neg_cor, double* out, double* hyper) try {
+  return dispatch(on_context(ctx),
+                  camera_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, inter_gene_cor, allow_neg_cor, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the two device passes of plaid.camera on device pointers (kernels_camera.hip).  The workspace holds the masks of the
+// residual pass, or the block partials of the sums of squares.
+int plaidhip_dev_camera_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                                  const int8_t* use, int32_t p, int32_t nfit, int32_t fit, const double* E, const double* rss,
+                                  double d, double* Z, int64_t ldz) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ld >= rows && ldz >= rows && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS,
+             "camera_residuals: bad shape rows=%d n=%d ld=%lld ldz=%lld nfit=%d (nfit <= %d)", rows, n, (long long)ld,
+             (long long)ldz, nfit, PLAIDHIP_LIMMA_MAX_FITS);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "camera_residuals: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(n <= PLAIDHIP_LIMMA_MAX_SAMPLES, "camera_residuals: %d samples (at most %d)", n, PLAIDHIP_LIMMA_MAX_SAMPLES);
+  PH_REQUIRE(fit >= 0 && fit < nfit, "camera_residuals: fit %d of %d", fit, nfit);
+  PH_REQUIRE(d >= 1.0, "camera_residuals: d = %g residual degrees of freedom (at least 1)", d);
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(A && Q && E && rss && Z, "camera_residuals: null argument");
+  const int64_t W = (int64_t)nfit * (p + 1);
+  PH_TRY(ensure_workspace(ctx, (size_t)lmfit_mask_bytes(n, W)));
+  PH_TRY(launch_lmfit_masks(ctx, Q, use, nullptr, n, p, nfit, ctx->ws, nullptr));
+  return launch_camera_residuals(ctx, A, ld, rows, n, Q, ctx->ws, p, fit, E, rss, d, Z, ldz);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_camera_sumsq(plaidhip_ctx* ctx, const double* T, int64_t ldt, int32_t m, int32_t n, const double* seed,
+                              double* out) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(m >= 0 && n >= 0 && ldt >= m && n <= PLAIDHIP_LIMMA_MAX_SAMPLES, "camera_sumsq: bad shape m=%d n=%d ldt=%lld (n <= %d)",
+             m, n, (long long)ldt, PLAIDHIP_LIMMA_MAX_SAMPLES);
+  if (m == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(out && (n == 0 || T), "camera_sumsq: null argument");
+  PH_TRY(ensure_workspace(ctx, (size_t)camera_sumsq_ws_doubles(n, m) * 8));
+  double* ws = static_cast<double*>(ctx->ws);
+  PH_TRY(launch_camera_sumsq(ctx, T, ldt, m, n, ws, m));
+  return launch_reduce_blocks_flat(ctx, ws, m, n, seed, out);
+} catch (...) { return plaidhip::on_exception(); }
+
 // the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out) try {
   PH_REQUIRE(g >= 1 && nperm >= 1, "gsea_permutations: bad dims g=%d nperm=%d", g, nperm);

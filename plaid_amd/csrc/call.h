@@ -12,7 +12,7 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20
+  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -120,6 +120,10 @@ struct Call : Operands {
   int na_fit = 0;
   double max_na = 0.0;
   double* dfres = nullptr;
+  // plaid.camera (kCamera): plaid.limma's operands (X genes x n, designs, use, K) and the sets; the fixed inter-gene
+  // correlation (NaN: estimated from the residuals), allow.neg.cor; out m x 8 x q x nfit, hyper nfit x 6
+  double inter_gene_cor = 0.0;
+  int allow_neg_cor = 0;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -390,6 +394,20 @@ inline Call limma_na_call(const double* A, int32_t rows, int32_t n, const double
   k.na_fit = 1;
   k.max_na = max_na;
   k.dfres = dfres;
+  return k;
+}
+
+// limma's competitive set test as pinned in include/plaidhip.h: plaidhip_camera
+inline Call camera_call(const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                        const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m, double inter_gene_cor,
+                        int allow_neg_cor, double* out, double* hyper) {
+  Call k = limma_call(X, g, n, design, p, nfit, use, K, q, out, hyper);
+  k.method = kCamera;
+  k.Gp = Gp;
+  k.Gi = Gi;
+  k.m = m;
+  k.inter_gene_cor = inter_gene_cor;
+  k.allow_neg_cor = allow_neg_cor ? 1 : 0;
   return k;
 }
 

@@ -385,6 +385,15 @@ int launch_lmfit_nan_pairs(plaidhip_ctx* ctx, const int64_t* d_off, const int32_
 int launch_lmfit_na_solve(plaidhip_ctx* ctx, int64_t npairs, const int32_t* d_pairs, const int64_t* d_off, const int32_t* d_list,
                           const double* d_Q, const int8_t* d_use, int32_t n, int32_t p, int32_t q, const double* d_v,
                           const int32_t* d_nobs, const double* d_nf, int32_t rows, double* d_E, double* d_u, int32_t* d_ok);
+// kernels_camera.hip (plaid.camera): Z (rows x n, leading dimension ldz) of fit f -- the residual chain of
+// launch_row_design_rss with a store, scaled by the gene's sqrt(max(rss / d, 1e-8)) (camera.h) -- from d_E [W][rows] and
+// d_rss [nfit][rows] of ALL samples; and the block partials part[block][set] (`stride` doubles from block to block) of the
+// sums over the columns of T[set, c]^2 (T: m x n, leading dimension ldt), reduced by launch_reduce_blocks_flat
+int launch_camera_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
+                            const void* d_masks, int32_t p, int32_t f, const double* d_E, const double* d_rss, double d, double* Z,
+                            int64_t ldz);
+int64_t camera_sumsq_ws_doubles(int32_t n, int64_t len);
+int launch_camera_sumsq(plaidhip_ctx* ctx, const double* T, int64_t ldt, int32_t m, int32_t n, double* part, int64_t stride);
 // stats.cpp: eBayes and the tables of plaid.limma.  drow ([nfit][rows], NaN: the row is not fitted) and urow ([nfit q][rows])
 // null: every row of fit f has nf[f] - p and u[f q + j] (plaidhip_limma_finish); hyper has hcols (4 or 5) values per fit
 int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,

@@ -304,6 +304,8 @@ struct Shared {
   std::vector<std::vector<int32_t>> na_cnt, na_list;
   std::vector<int32_t> na_pair;
   std::vector<double> na_d, na_u;
+  // plaid.camera: the chained sums over the samples of T^2, [nfit][m] (T = G'Z of every fit)
+  std::vector<double> cam_ss;
   // replaid.ssgsea.exact with norm: a NaN among the scores of any shard (its min / max go to xmin / xmax)
   bool es_nan = false;
   // plaid.gsea: the block partials [nblk][c][6][m] of all permutation blocks, each shard writing its own blocks
@@ -319,7 +321,7 @@ struct Shared {
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc) {
   int64_t lo64 = 0, hi64 = 0;
   if (((c.method == kGsva || (c.method == kGsvaExact && c.rowtf == 0)) && c.Xp == nullptr) || c.method == kPlaidTest ||
-      c.method == kPlaidTestContrasts || c.method == kLimma) {
+      c.method == kPlaidTestContrasts || c.method == kLimma || c.method == kCamera) {
     constexpr int64_t kBlock = 128;
     const int64_t per = kBlock * (((c.n + kBlock - 1) / kBlock + ndev - 1) / ndev);
     lo64 = std::min<int64_t>(c.n, (int64_t)k * per);
@@ -2519,6 +2521,7 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   Shard s(ctx, c, ndev, k, sh);
   const int32_t lo = s.lo, nloc = s.nloc, rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit;
   const int64_t W = (int64_t)nfit * (p + 1), ld = even_ld(rows);
+  if (c.method == kCamera) s.force_f64();   // (T = G'Z stays on the fp64 kernels whatever precision the context was given)
   CtxBuf dA{ctx, 0};
   DevBuf dQ, duse, dinvn, dmask, dwt, dws, drows;
   double *d_seed = nullptr, *d_run = nullptr, *d_E = nullptr;
@@ -2617,7 +2620,97 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
                                  dws.as<double>(), c.na_fit != 0);
   });
   chain_flat_sums(s, sh.chain_q, dws.as<double>(), (int64_t)nfit * rows, d_seed, d_run);
+  if (c.method != kCamera || !std::isnan(c.inter_gene_cor)) return s.finish();
+
+  // ---- plaid.camera, the estimated correlation: fit by fit, Z of the shard's columns from the effects and the residual sums of
+  // squares of ALL samples (every shard has met ndev times since the last of them was added), T = G'Z by the dense crossprod,
+  // and the block partials of the sums of T^2, [nblk][nfit][m]; round three chains them as [nfit][m].  One fit's Z and T are
+  // alive at a time. ----------------------------------------------------------------------------------------------------------
+  const int32_t m = c.m;
+  CtxBuf dZ{ctx, 3}, dT{ctx, 4}, dsq{ctx, 5};   // (they live in the context between calls, as A does)
+  double *d_part = nullptr, *d_chain = nullptr;   // dsq: [the block partials | the chain's seed | its running sums]
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    plaidhip_geneset* gs = nullptr;
+    PH_TRY(acquire_geneset(ctx, rows, m, c.Gp, c.Gi, &gs));
+    double* d_rss = d_seed;   // (the chains above are done with it; W >= nfit)
+    PH_HIP(hipMemcpyAsync(d_rss, sh.chain_q.data(), (size_t)nfit * rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dZ.alloc((size_t)ld * nloc * 8));
+    PH_TRY(dT.alloc((size_t)m * nloc * 8));
+    const size_t npart = (size_t)camera_sumsq_ws_doubles(nloc, (int64_t)nfit * m);
+    PH_TRY(dsq.alloc((npart + (size_t)nfit * m * 2) * 8));
+    d_part = dsq.as<double>();
+    d_chain = d_part + npart;
+    for (int32_t f = 0; f < nfit; ++f) {
+      PH_TRY(launch_camera_residuals(ctx, dA.as<double>(), ld, rows, nloc, dQ.as<double>(), dmask.p, p, f, d_E, d_rss,
+                                     (double)(c.lm_nf[(size_t)f] - p), dZ.as<double>(), ld));
+      PH_TRY(launch_spmm_dense_f64(ctx, gs, dZ.as<double>(), ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(), m,
+                                   nullptr));
+      PH_TRY(launch_camera_sumsq(ctx, dT.as<double>(), m, m, nloc, d_part + (size_t)f * m, (int64_t)nfit * m));
+    }
+    return PLAIDHIP_OK;
+  });
+  chain_flat_sums(s, sh.cam_ss, d_part, (int64_t)nfit * m, d_chain, d_chain + (size_t)nfit * m);
   return s.finish();
+}
+
+// plaid.camera after the workers: eBayes and the gene statistics on the host (plaidhip_limma_finish), the member sums of t
+// and the counts of ok members from ONE crossprod of the membership with [the t columns | the ok indicators] on the first
+// context (a gene that is not ok holds 0.0 in both), then the pinned test (plaidhip_camera_finish).
+int camera_tail(plaidhip_ctx* ctx, const Call& c, Shared& sh) {
+  const int32_t g = c.g, m = c.m, nfit = c.nfit, q = c.nq, p = c.ncoef;
+  const size_t R = (size_t)g, ncol = (size_t)nfit * q;
+  std::vector<double> tab(R * 6 * ncol), hyp((size_t)nfit * 4);
+  PH_TRY(plaidhip_limma_finish(g, p, nfit, q, sh.chain_x.data(), sh.chain_q.data(), c.lm_nf.data(), c.lm_v.data(), c.lm_u.data(),
+                               tab.data(), hyp.data()));
+  std::vector<double> B(R * (ncol + nfit)), t(R * ncol), S((size_t)m * (ncol + nfit)), dres((size_t)nfit), dprior((size_t)nfit);
+  std::vector<int8_t> ok(R * nfit);
+  for (int32_t f = 0; f < nfit; ++f) {
+    const double* sigma2 = tab.data() + ((size_t)f * q * 6 + 5) * R;   // (of the fit's first contrast: NaN = not ok)
+    for (size_t r = 0; r < R; ++r) {
+      ok[R * f + r] = std::isnan(sigma2[r]) ? 0 : 1;
+      B[(ncol + f) * R + r] = ok[R * f + r] ? 1.0 : 0.0;
+    }
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      const double* tj = tab.data() + (col * 6 + 2) * R;
+      for (size_t r = 0; r < R; ++r) {
+        t[col * R + r] = tj[r];
+        B[col * R + r] = ok[R * f + r] ? tj[r] : 0.0;
+      }
+    }
+    dres[(size_t)f] = hyp[4 * (size_t)f];
+    dprior[(size_t)f] = hyp[4 * (size_t)f + 1];
+  }
+  const int saved = ctx->precision;
+  ctx->precision = PLAIDHIP_PRECISION_F64;
+  int rc = [&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    plaidhip_geneset* gs = nullptr;
+    PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    DevBuf dB, dS;
+    PH_TRY(dB.alloc(B.size() * 8));
+    PH_TRY(dS.alloc(S.size() * 8));
+    PH_TRY(upload_host(ctx, dB.p, R * 8, B.data(), R * 8, (int64_t)(ncol + nfit)));
+    PH_TRY(launch_spmm_dense_f64(ctx, gs, dB.as<double>(), g, (int32_t)(ncol + nfit), PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0,
+                                 dS.as<double>(), m, nullptr));
+    PH_HIP(hipMemcpyAsync(S.data(), dS.p, S.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  }();
+  ctx->precision = saved;
+  if (rc != PLAIDHIP_OK) return rc;
+  const bool estimate = std::isnan(c.inter_gene_cor);
+  std::vector<double> gdf((size_t)nfit * 2);
+  PH_TRY(plaidhip_camera_finish(g, m, nfit, q, t.data(), ok.data(), S.data(), S.data() + (size_t)m * ncol,
+                                estimate ? sh.cam_ss.data() : nullptr, dres.data(), dprior.data(), c.inter_gene_cor,
+                                c.allow_neg_cor, c.out, gdf.data()));
+  for (int32_t f = 0; f < nfit; ++f) {
+    for (int h = 0; h < 4; ++h) c.hyper[6 * (size_t)f + h] = hyp[4 * (size_t)f + h];
+    c.hyper[6 * (size_t)f + 4] = gdf[2 * (size_t)f];
+    c.hyper[6 * (size_t)f + 5] = gdf[2 * (size_t)f + 1];
+  }
+  return PLAIDHIP_OK;
 }
 
 // every shard on a thread of its own (one shard: the calling thread); the first failure's text is reported
@@ -2648,7 +2741,8 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     sh.pt_F.assign((size_t)even_ld(c.g) * 2 * C, 0.0);
     sh.row_sum.resize((size_t)ndev);
   }
-  if (c.method == kLimma) {
+  if (c.method == kCamera) sh.cam_ss.assign((size_t)c.nfit * c.m, 0.0);
+  if (c.method == kLimma || c.method == kCamera) {
     sh.chain_x.assign((size_t)c.nfit * (c.ncoef + 1) * c.g, 0.0);
     sh.chain_q.assign((size_t)c.nfit * c.g, 0.0);
     if (c.na_fit) {
@@ -2667,7 +2761,7 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
     if (c.method == kFisher) return fisher_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kRankcor) return rankcor_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlage || c.method == kZscore) return plage_worker(ctxs[k], c, ndev, k, sh);
-    if (c.method == kLimma) return limma_worker(ctxs[k], c, ndev, k, sh);
+    if (c.method == kLimma || c.method == kCamera) return limma_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTest) return plaid_test_worker(ctxs[k], c, ndev, k, sh);
     if (c.method == kPlaidTestContrasts) return plaid_test_contrasts_worker(ctxs[k], c, ndev, k, sh);
     return is_rank_sum(c.method) ? shard_worker(ctxs[k], c, ndev, k, sh) : scorer_worker(ctxs[k], c, ndev, k, sh);
@@ -2724,6 +2818,7 @@ int run_call(plaidhip_ctx* const* ctxs, int ndev, const Call& c) {
   } else if (rc == PLAIDHIP_OK && c.method == kLimma)   // eBayes and the tables, on the host from the chained sums
     rc = plaidhip_limma_finish(c.g, c.ncoef, c.nfit, c.nq, sh.chain_x.data(), sh.chain_q.data(), c.lm_nf.data(), c.lm_v.data(),
                                c.lm_u.data(), c.out, c.hyper);
+  if (rc == PLAIDHIP_OK && c.method == kCamera) rc = camera_tail(ctxs[0], c, sh);
   if (rc == PLAIDHIP_OK && c.method == kPlaidTestContrasts) {   // the same host half, once per contrast with its group sizes
     const int64_t ldg = even_ld(c.g);
     const size_t m = (size_t)c.m;
@@ -3140,31 +3235,33 @@ int check_plage_call(const Call& c) {
 // plaid.limma; the order is part of the contract (include/plaidhip.h).  Makes every fit's Q, v, u and n_f: the designs are
 // decomposed here, on the host, so that a design that cannot be fitted is refused before any device is touched
 int check_limma_call(Call& c) {
+  const char* who = c.method == kCamera ? "camera" : "limma";
+  const bool sets = c.method != kCamera || c.m != 0;   // (plaid.camera without sets writes nothing)
   const int32_t rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, q = c.nq;
   PH_REQUIRE(rows >= 0 && n >= 0 && n <= PLAIDHIP_LIMMA_MAX_SAMPLES && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS && q >= 0,
-             "limma: bad dims rows=%d n=%d nfit=%d q=%d (n <= %d, nfit <= %d)", rows, n, nfit, q, PLAIDHIP_LIMMA_MAX_SAMPLES,
+             "%s: bad dims rows=%d n=%d nfit=%d q=%d (n <= %d, nfit <= %d)", who, rows, n, nfit, q, PLAIDHIP_LIMMA_MAX_SAMPLES,
              PLAIDHIP_LIMMA_MAX_FITS);
-  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "limma: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "%s: p = %d coefficients (1 <= p <= %d)", who, p, PLAIDHIP_LIMMA_MAX_COEF);
   if (c.na_fit) {
-    PH_REQUIRE(p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "limma: p = %d coefficients with na = \"fit\" (p <= %d)", p,
+    PH_REQUIRE(p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "%s: p = %d coefficients with na = \"fit\" (p <= %d)", who, p,
                PLAIDHIP_LIMMA_NA_MAX_COEF);
-    PH_REQUIRE(c.max_na >= 0.0 && c.max_na <= 1.0, "limma: max_na = %g (a share, 0 <= max_na <= 1)", c.max_na);
+    PH_REQUIRE(c.max_na >= 0.0 && c.max_na <= 1.0, "%s: max_na = %g (a share, 0 <= max_na <= 1)", who, c.max_na);
   }
-  PH_REQUIRE(c.K != nullptr || q == p, "limma: q = %d without K (the p = %d unit vectors)", q, p);
-  PH_REQUIRE(c.design != nullptr || nfit == 0, "limma: null design");
-  PH_REQUIRE(rows == 0 || nfit == 0 || q == 0 || (c.X != nullptr && c.out != nullptr && c.hyper != nullptr),
-             "limma: null A / out / hyper");
-  PH_REQUIRE(!c.na_fit || rows == 0 || nfit == 0 || q == 0 || c.dfres != nullptr, "limma: null dfres");
+  PH_REQUIRE(c.K != nullptr || q == p, "%s: q = %d without K (the p = %d unit vectors)", who, q, p);
+  PH_REQUIRE(c.design != nullptr || nfit == 0, "%s: null design", who);
+  PH_REQUIRE(rows == 0 || nfit == 0 || q == 0 || !sets || (c.X != nullptr && c.out != nullptr && c.hyper != nullptr),
+             "%s: null A / out / hyper", who);
+  PH_REQUIRE(!c.na_fit || rows == 0 || nfit == 0 || q == 0 || c.dfres != nullptr, "%s: null dfres", who);
   if (c.K != nullptr)
     for (int64_t e = 0; e < (int64_t)p * q; ++e)
-      PH_REQUIRE(std::isfinite(c.K[e]), "limma: K[%lld] = %g (the contrasts are finite)", (long long)e, c.K[e]);
+      PH_REQUIRE(std::isfinite(c.K[e]), "%s: K[%lld] = %g (the contrasts are finite)", who, (long long)e, c.K[e]);
   c.lm_Q.assign((size_t)n * p * nfit, 0.0);
   c.lm_v.assign((size_t)p * q * nfit, 0.0);
   c.lm_u.assign((size_t)q * nfit, 0.0);
   c.lm_nf.assign((size_t)nfit, 0);
   c.lm_invn.assign((size_t)nfit, 0.0);
   for (int32_t f = 0; f < nfit; ++f) {
-    PH_TRY(limma_design("limma", c.design + (size_t)f * n * p, n, p, c.use != nullptr ? c.use + (size_t)f * n : nullptr, c.K, q,
+    PH_TRY(limma_design(who, c.design + (size_t)f * n * p, n, p, c.use != nullptr ? c.use + (size_t)f * n : nullptr, c.K, q,
                         f + 1, c.lm_Q.data() + (size_t)f * n * p, nullptr, c.lm_v.data() + (size_t)f * p * q,
                         c.lm_u.data() + (size_t)f * q, &c.lm_nf[(size_t)f]));
     c.lm_invn[(size_t)f] = 1.0 / (double)c.lm_nf[(size_t)f];
@@ -3172,8 +3269,29 @@ int check_limma_call(Call& c) {
   return PLAIDHIP_OK;
 }
 
+// plaid.camera; the order is part of the contract (include/plaidhip.h): plaid.limma's checks in their order (the designs are
+// decomposed there), then the membership's as plaid.rankcor makes them, then the fixed correlation
+int check_camera_call(Call& c) {
+  PH_REQUIRE(c.m >= 0, "camera: bad dims m=%d", c.m);
+  PH_TRY(check_limma_call(c));
+  PH_REQUIRE(c.Gp != nullptr, "camera: null Gp");
+  PH_REQUIRE(c.Gp[0] == 0, "camera: Gp[0] = %d (a column pointer starts at 0)", c.Gp[0]);
+  for (int32_t j = 0; j < c.m; ++j) {
+    PH_REQUIRE(c.Gp[j + 1] >= c.Gp[j], "camera: Gp[%d] = %d after %d (a column pointer does not decrease)", j + 1, c.Gp[j + 1],
+               c.Gp[j]);
+    PH_REQUIRE(c.Gp[j + 1] - c.Gp[j] <= c.g, "camera: set %d has %d members (at most the %d genes)", j + 1,
+               c.Gp[j + 1] - c.Gp[j], c.g);
+  }
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "camera: null Gi");
+  for (int32_t e = 0; e < c.Gp[c.m]; ++e)
+    PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "camera: Gi[%d] = %d (rows are 0..%d)", e, c.Gi[e], c.g - 1);
+  PH_REQUIRE(std::isnan(c.inter_gene_cor) || (c.inter_gene_cor > -1.0 && c.inter_gene_cor < 1.0),
+             "camera: inter_gene_cor = %g (a correlation inside (-1, 1), or NaN to estimate it)", c.inter_gene_cor);
+  return PLAIDHIP_OK;
+}
+
 std::mutex g_multi_mu;
-std::vector<plaidhip_ctx*> g_multi_ctx;   // one lazily created context per device, owned by the library
+std::vector<plaidhip_ctx*> g_multi_ctx;  // one lazily created context per device, owned by the library
 int g_multi_precision = PLAIDHIP_PRECISION_F64;   // plaidhip_multi_set_precision: applies to these contexts
 
 // the device list's own checks, which touch no device
@@ -3235,6 +3353,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kPlage:
     case kZscore: return check_plage_call(c);
     case kLimma: return check_limma_call(c);
+    case kCamera: return check_camera_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -3258,6 +3377,8 @@ int dispatch(const Target& t, Call c) {
     if (c.m == 0 || c.ncontrast == 0) return PLAIDHIP_OK;
   } else if (c.method == kLimma) {
     if (c.g == 0 || c.nfit == 0 || c.nq == 0) return PLAIDHIP_OK;
+  } else if (c.method == kCamera) {
+    if (c.g == 0 || c.nfit == 0 || c.nq == 0 || c.m == 0) return PLAIDHIP_OK;
   } else if (c.method == kPlaidTest ? c.m == 0 : (int64_t)c.m * c.n == 0) {
     return PLAIDHIP_OK;
   }
@@ -3556,6 +3677,21 @@ int plaidhip_debug_limma_na_sharded_on_one_device(int device, int nshards, int f
                                                   double* dfres) try {
   return dispatch(on_hook(device, nshards, fail_shard),
                   limma_na_call(A, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_camera_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const double* design, int32_t p,
+                          int32_t nfit, const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi,
+                          int32_t m, double inter_gene_cor, int allow_neg_cor, double* out, double* hyper) try {
+  return dispatch(on_devices(devices, ndev),
+                  camera_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, inter_gene_cor, allow_neg_cor, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_camera_sharded_on_one_device(int device, int nshards, int fail_shard, const double* X, int32_t g, int32_t n,
+                                                const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                                                const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                                                double inter_gene_cor, int allow_neg_cor, double* out, double* hyper) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  camera_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, inter_gene_cor, allow_neg_cor, out, hyper));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fail_shard, const int8_t* sig, int32_t g, int32_t c,

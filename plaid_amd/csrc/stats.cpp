@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "camera.h"
 #include "common.h"
 #include "lmfit_na.h"
 
@@ -675,6 +676,109 @@ int plaidhip_limma_na_solve(int32_t p, int32_t nmis, const double* qmis, const d
     for (int k = 0; k < p; ++k) gamma[k] = nan;
   if (pivots != nullptr) std::copy(piv, piv + p, pivots);
   for (int32_t j = 0; j < q; ++j) u[j] = *ok ? lmfit_na_unscaled(p, H, P, v + (size_t)j * p, w) : nan;
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.camera, step 2 for one gene (include/plaidhip.h): the functions the device runs (camera.h)
+int plaidhip_camera_residual_row(int32_t n, int32_t p, const double* x, const double* Q, const int8_t* use, const double* E,
+                                 double rss, double d, double* z) try {
+  using namespace plaidhip;
+  PH_REQUIRE(n >= 0, "camera_residual_row: bad dims n=%d", n);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "camera_residual_row: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(d >= 1.0, "camera_residual_row: d = %g residual degrees of freedom (at least 1)", d);
+  if (n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(x && Q && E && z, "camera_residual_row: null argument");
+  const double scale = camera_gene_scale(rss, d);
+  for (int32_t c = 0; c < n; ++c) {
+    double r = x[c];
+    for (int32_t k = 0; k < p; ++k) r = camera_chain_step(Q[(size_t)k * n + c], E[k], r);
+    z[c] = camera_standardise(r, scale, use == nullptr || use[c] != 0);
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.camera, step 5 (include/plaidhip.h): the test of every (fit, contrast, set), fp64, every sum over the genes in
+// ascending order
+int plaidhip_camera_finish(int32_t g, int32_t m, int32_t nfit, int32_t q, const double* t, const int8_t* ok, const double* sumt,
+                           const double* cnt, const double* ss, const double* dfres, const double* dfprior,
+                           double inter_gene_cor, int allow_neg_cor, double* out, double* gdf) try {
+  using namespace plaidhip;
+  PH_REQUIRE(g >= 0 && m >= 0 && nfit >= 0 && q >= 0, "camera_finish: bad dims g=%d m=%d nfit=%d q=%d", g, m, nfit, q);
+  if (nfit == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(dfres && dfprior && gdf, "camera_finish: null argument");
+  PH_REQUIRE(g == 0 || ok, "camera_finish: null argument");
+  PH_REQUIRE(m == 0 || q == 0 || ((g == 0 || t) && sumt && cnt && out), "camera_finish: null argument");
+  PH_REQUIRE(ss != nullptr || (inter_gene_cor > -1.0 && inter_gene_cor < 1.0),
+             "camera_finish: inter_gene_cor = %g without sums of squares (a correlation inside (-1, 1))", inter_gene_cor);
+  for (int32_t f = 0; f < nfit; ++f)
+    PH_REQUIRE(dfres[f] >= 1.0 && dfprior[f] >= 0.0, "camera_finish: fit %d: df.residual = %g, df.prior = %g", f + 1, dfres[f],
+               dfprior[f]);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const size_t R = (size_t)g, M = (size_t)m;
+  for (int32_t f = 0; f < nfit; ++f) {
+    const int8_t* okf = ok + R * f;
+    int64_t Gn = 0;
+    for (size_t r = 0; r < R; ++r) Gn += okf[r] != 0 ? 1 : 0;
+    const double G = (double)Gn, d = dfres[f];
+    const double dfc = std::min(d + dfprior[f], G - 2.0);   // df.camera
+    gdf[2 * (size_t)f] = G;
+    gdf[2 * (size_t)f + 1] = dfc;
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      const double* tj = t + col * R;
+      double* o = out + col * 8 * M;
+      double sum = 0.0;
+      for (size_t r = 0; r < R; ++r)
+        if (okf[r] != 0) sum += tj[r];
+      const double mean = sum / G;
+      double dev = 0.0;
+      for (size_t r = 0; r < R; ++r)
+        if (okf[r] != 0) {
+          const double e = tj[r] - mean;
+          dev += e * e;
+        }
+      const double var = dev / (G - 1.0);
+      for (size_t s = 0; s < M; ++s) {
+        const double mm = cnt[M * f + s];
+        double vif = nan, cor = nan;
+        if (ss != nullptr) {
+          if (mm > 1.0) {
+            vif = ss[M * f + s] / (mm * d);
+            cor = (vif - 1.0) / (mm - 1.0);
+          } else if (mm == 1.0) {
+            vif = 1.0;
+          }
+        } else if (mm >= 1.0) {
+          vif = 1.0 + (mm - 1.0) * inter_gene_cor;
+          cor = inter_gene_cor;
+        }
+        o[s] = mm;
+        o[M + s] = cor;
+        o[2 * M + s] = vif;
+        double T = nan, down = nan, up = nan, pv = nan;
+        const double m2 = G - mm;
+        if (mm >= 1.0 && m2 >= 1.0 && Gn >= 3) {
+          const double used = ss != nullptr && !allow_neg_cor ? std::max(vif, 1.0) : vif;
+          const double delta = (G / m2) * (sumt[col * M + s] / mm - mean);
+          const double pooled = ((G - 1.0) * var - ((delta * delta) * mm * m2) / G) / (G - 2.0);
+          const double scale2 = pooled * (used / mm + 1.0 / m2);
+          if (pooled > 0.0 && scale2 > 0.0) {
+            T = delta / std::sqrt(scale2);
+            const double half = 0.5 * t_two_sided_p(T, dfc);   // pt(-|T|, df.camera)
+            down = T < 0.0 ? half : 1.0 - half;
+            up = T < 0.0 ? 1.0 - half : half;
+            pv = 2.0 * std::min(down, up);
+          }
+        }
+        o[3 * M + s] = T;
+        o[4 * M + s] = down;
+        o[5 * M + s] = up;
+        o[6 * M + s] = pv;
+      }
+      p_adjust_fdr(o + 6 * M, m, o + 7 * M);
+    }
+  }
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 

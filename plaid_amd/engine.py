@@ -694,6 +694,74 @@ def limma_finish(E, rss, nf, v, u):
     return out, hyper
 
 
+CAMERA_COLUMNS = ("NGenes", "Correlation", "VIF", "t", "Down", "Up", "PValue", "FDR")
+CAMERA_HYPER = LIMMA_HYPER + ("n.genes", "df.camera")
+
+
+def check_camera_cor(inter_gene_cor):
+    """inter_gene_cor as the C ABI takes it: a correlation inside (-1, 1), or None / NaN to estimate it from the residuals"""
+    rho = np.nan if inter_gene_cor is None else float(inter_gene_cor)
+    if not (np.isnan(rho) or -1.0 < rho < 1.0):
+        raise ValueError(f"camera: inter_gene_cor = {rho:g} (a correlation inside (-1, 1), or None to estimate it)")
+    return rho
+
+
+def _camera(fn, head, X, design, Gp, Gi, use=None, contrasts=None, inter_gene_cor=0.01, allow_neg_cor=False, out=None,
+            hyper=None):
+    """plaidhip_camera / _multi / the hook: (out, hyper) -- sets x 8 x q x nfit (CAMERA_COLUMNS) and nfit x 6 (CAMERA_HYPER)"""
+    X = _as_f64_fortran(X)
+    if X.ndim != 2:
+        raise ValueError("camera: the matrix must be genes x samples")
+    g, n = X.shape
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    out = np.full((m, 8, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 6), np.nan, dtype=np.float64) if hyper is None else hyper
+    check(fn(*head, _np_ptr(X), g, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+             q, _np_ptr(Gp), _np_ptr(Gi), m, check_camera_cor(inter_gene_cor), int(bool(allow_neg_cor)), _np_ptr(out),
+             _np_ptr(hyper)))
+    return out, hyper
+
+
+def camera_residual_row(x, Q, use, E, rss, d) -> np.ndarray:
+    """plaidhip_camera_residual_row on the host (no device is touched): the standardised residuals of one gene.  x: n; Q: n x p,
+    the fit's thin Q; use: n or None; E: the gene's p effects; rss and d = n_f - p"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(len(x), -1))
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    U = None if use is None else np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int8)
+    z = np.full(len(x), -7.0)
+    check(_lib.load().plaidhip_camera_residual_row(len(x), Q.shape[1], _np_ptr(x), _np_ptr(Q), None if U is None else _np_ptr(U),
+                                                   _np_ptr(E), float(rss), float(d), _np_ptr(z)))
+    return z
+
+
+def camera_finish(t, ok, sumt, cnt, ss, dfres, dfprior, inter_gene_cor=None, allow_neg_cor=False):
+    """plaidhip_camera_finish on the host (no device is touched): t genes x q x nfit, ok genes x nfit, sumt sets x q x nfit,
+    cnt sets x nfit, ss sets x nfit (None: the fixed inter_gene_cor), dfres / dfprior per fit -> (out sets x 8 x q x nfit,
+    gdf nfit x 2: the universe's size and df.camera)"""
+    t = np.asarray(t, dtype=np.float64)
+    t = np.asfortranarray(t[:, :, None] if t.ndim == 2 else t)
+    g, q, nfit = t.shape
+    ok = np.asfortranarray(np.asarray(ok).reshape((g, nfit), order="F") != 0, dtype=np.int8)
+    cnt = np.asfortranarray(np.asarray(cnt, dtype=np.float64).reshape((-1, nfit), order="F"))
+    m = cnt.shape[0]
+    sumt = np.asfortranarray(np.asarray(sumt, dtype=np.float64).reshape((m, q, nfit), order="F"))
+    ss = None if ss is None else np.asfortranarray(np.asarray(ss, dtype=np.float64).reshape((m, nfit), order="F"))
+    dfres, dfprior = (np.ascontiguousarray(np.atleast_1d(v), dtype=np.float64) for v in (dfres, dfprior))
+    if dfres.shape != (nfit,) or dfprior.shape != (nfit,):
+        raise ValueError("camera_finish: dfres and dfprior have one entry per fit")
+    out = np.full((m, 8, q, nfit), -7.0, order="F")
+    gdf = np.full((nfit, 2), -7.0)
+    rho = np.nan if inter_gene_cor is None else float(inter_gene_cor)
+    check(_lib.load().plaidhip_camera_finish(g, m, nfit, q, _np_ptr(t), _np_ptr(ok), _np_ptr(sumt), _np_ptr(cnt),
+                                             None if ss is None else _np_ptr(ss), _np_ptr(dfres), _np_ptr(dfprior), rho,
+                                             int(bool(allow_neg_cor)), _np_ptr(out), _np_ptr(gdf)))
+    return out, gdf
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -1125,6 +1193,24 @@ class Context:
         """plaidhip_dev_row_design_rss on device pointers: rss [nfit][rows] at the effects E of all samples"""
         check(self.lib.plaidhip_dev_row_design_rss(self.handle, A, ld, rows, n, Q, use, p, nfit, E, seed, rss))
 
+    def camera(self, X, design, Gp, Gi, use=None, contrasts=None, inter_gene_cor=0.01, allow_neg_cor=False):
+        """plaidhip_camera: limma's competitive set test of the sets (Gp, Gi, aligned to the rows of X) for the gene statistics
+        plaid.limma gives on X (genes x samples) with the designs, `use` and contrasts of Context.limma.  inter_gene_cor: the
+        fixed correlation (limma's default 0.01), or None to estimate every set's variance inflation factor from the
+        residuals.  (out sets x 8 x q x nfit in CAMERA_COLUMNS, hyper nfit x 6 in CAMERA_HYPER)"""
+        return _camera(self.lib.plaidhip_camera, (self.handle,), X, design, Gp, Gi, use, contrasts, inter_gene_cor, allow_neg_cor)
+
+    def dev_camera_residuals(self, A: int, ld: int, rows: int, n: int, Q: int, use, p: int, nfit: int, fit: int, E: int, rss: int,
+                             d: float, Z: int, ldz: int):
+        """plaidhip_dev_camera_residuals on device pointers: Z (rows x n, leading dimension ldz) of fit `fit` (from 0) at the
+        effects E and the residual sums of squares rss of all samples; use may be None"""
+        check(self.lib.plaidhip_dev_camera_residuals(self.handle, A, ld, rows, n, Q, use, p, nfit, fit, E, rss, float(d), Z, ldz))
+
+    def dev_camera_sumsq(self, T: int, ldt: int, m: int, n: int, seed, out: int):
+        """plaidhip_dev_camera_sumsq on device pointers: out[s] = seed[s] + the sums over the columns of T[s, c]^2 in the
+        pinned block order; seed may be None"""
+        check(self.lib.plaidhip_dev_camera_sumsq(self.handle, T, ldt, m, n, seed, out))
+
     def fisher(self, sig, Gp, Gi, overlap=False):
         """plaidhip_fisher: over-representation tests of the columns of sig (genes x lists of -1 / 0 / +1) against the sets:
         (out, tot) -- sets x 12 x lists (FISHER_COLUMNS) and the 2 x lists totals nUp, nDn; with overlap also (ov_len, ov_idx),
@@ -1362,6 +1448,11 @@ def plage_multi(X, Gp, Gi, tol=PLAGE_TOL, maxit=1000, loadings=False, devices=1)
 def zscore_multi(X, Gp, Gi, devices=1):
     """replaid.zscore (Context.zscore) with the sample columns shared out over `devices`: the one-device bits"""
     return _zscore(*_multi("zscore", devices), X, Gp, Gi)
+
+
+def camera_multi(X, design, Gp, Gi, use=None, contrasts=None, inter_gene_cor=0.01, allow_neg_cor=False, devices=1):
+    """plaid.camera (Context.camera) with the sample columns sharded over `devices`: the one-device bits"""
+    return _camera(*_multi("camera", devices), X, design, Gp, Gi, use, contrasts, inter_gene_cor, allow_neg_cor)
 
 
 def limma_multi(A, design, use=None, contrasts=None, devices=1, na="propagate", max_na=0.2):

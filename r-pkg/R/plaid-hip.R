@@ -768,6 +768,140 @@ plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none", na = c("prop
 }
 
 
+## the tables of plaid.camera() / plaid.camera.contrasts() from the library's sets x 8 block (NGenes, Correlation, VIF, t,
+## Down, Up, PValue, FDR): Direction is "Up" where Up < Down, else "Down" (limma's column), NA on an NA row; ordered by
+## sort.by -- "none", "PValue" / "P" / "p" and "FDR" (increasing), "t", "Correlation", "VIF" (decreasing magnitude),
+## "NGenes" (decreasing); NA last
+.camera_sorts <- c("none", "PValue", "P", "p", "FDR", "t", "Correlation", "VIF", "NGenes")
+
+.camera_table <- function(tab, rn, sort.by) {
+  tab <- matrix(tab, nrow = length(rn), ncol = 8L)
+  res <- data.frame(NGenes = tab[, 1], Correlation = tab[, 2], VIF = tab[, 3], t = tab[, 4],
+                    Direction = ifelse(is.na(tab[, 5]) | is.na(tab[, 6]), NA_character_, ifelse(tab[, 6] < tab[, 5], "Up", "Down")),
+                    PValue = tab[, 7], FDR = tab[, 8], row.names = rn, stringsAsFactors = FALSE)
+  key <- switch(sort.by, none = NULL, PValue = , P = , p = res$PValue, FDR = res$FDR, t = -abs(res$t),
+                Correlation = -abs(res$Correlation), VIF = -abs(res$VIF), NGenes = -res$NGenes,
+                stop("plaid.camera: sort.by must be one of ", paste(.camera_sorts, collapse = ", ")))
+  if (!is.null(key)) res <- res[order(key), , drop = FALSE]
+  res
+}
+
+.camera_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok", "n.genes", "df.camera"))
+
+## X as a double matrix with row names, and the sets of G (a gmt list or a genes x sets membership matrix) as the pattern
+## (Gp, Gi) over the rows of X: every row of X stays -- camera's universe is all the genes, also those in no set -- and a
+## member X does not have is dropped.  Sets outside minSize .. maxSize (default: the genes - 1) members in X are dropped.
+.camera_sets <- function(X, G, minSize, maxSize) {
+  if (inherits(X, "sparseMatrix")) stop("plaid.camera: X must be dense")
+  X <- as.matrix(X); storage.mode(X) <- "double"
+  if (is.null(rownames(X))) stop("plaid.camera: X needs row names")
+  if (is.list(G)) {
+    message("[plaid.camera] converting gmt to sparse matrix...")
+    G <- gmt2mat(G)
+  }
+  G <- methods::as(methods::as(methods::as(G, "dMatrix"), "generalMatrix"), "CsparseMatrix")
+  rows <- match(rownames(G), rownames(X))
+  rows[duplicated(rownames(G))] <- NA_integer_
+  sets <- lapply(seq_len(ncol(G)), function(j) {
+    k <- seq.int(G@p[j] + 1L, length.out = G@p[j + 1L] - G@p[j])
+    r <- rows[G@i[k] + 1L][G@x[k] != 0]
+    sort(r[!is.na(r)]) - 1L
+  })
+  size <- lengths(sets)
+  if (is.null(maxSize)) maxSize <- nrow(X) - 1L
+  keep <- which(size >= minSize & size <= maxSize)
+  list(X = X, Gp = as.integer(c(0L, cumsum(size[keep]))), Gi = as.integer(unlist(sets[keep])), names = colnames(G)[keep])
+}
+
+.camera_call <- function(cs, D, nfit, use, K, inter.gene.cor, allow.neg.cor, ncon, sort.by) {
+  rho <- if (is.null(inter.gene.cor) || is.na(inter.gene.cor)) NA_real_ else as.double(inter.gene.cor)
+  if (!is.na(rho) && (rho <= -1 || rho >= 1)) stop("plaid.camera: inter.gene.cor must lie inside (-1, 1), or be NA to estimate it")
+  if (length(sort.by) != 1L || !sort.by %in% .camera_sorts) stop("plaid.camera: sort.by must be one of ", paste(.camera_sorts, collapse = ", "))
+  .session()
+  r <- .Call("R_plaidhip_camera", .devices(), cs$X, D, nfit, use, K, cs$Gp, cs$Gi, rho, isTRUE(as.logical(allow.neg.cor)),
+             PACKAGE = "plaidhip")
+  out <- r[[1]]
+  dim(out) <- c(length(cs$names), 8L, ncon)
+  list(tables = lapply(seq_len(ncon), function(j) .camera_table(out[, , j], cs$names, sort.by)), hyper = r[[2]], raw = out)
+}
+
+
+## plaid.camera(): limma's competitive gene-set test camera (Wu & Smyth 2012, as pinned in include/plaidhip.h:
+## plaidhip_camera) of every set of G on the expression X (genes x samples) for one design (samples x coefficients).
+## contrasts, use: as plaid.limma().  The gene statistic is plaid.limma()'s moderated t; a set's two-sample t against the
+## other genes is corrected by the variance inflation factor 1 + (m - 1) rho.  inter.gene.cor: the fixed rho (limma's default
+## 0.01), or NA / NULL to estimate every set's VIF from the residuals of its genes (allow.neg.cor = FALSE then uses max(VIF, 1)
+## in the test; the reported VIF and Correlation stay as estimated).  A gene with an NA in a used sample leaves the universe.
+## Returns list(tables = <named list, one data frame per contrast: sets x (NGenes, Correlation, VIF, t, Direction, PValue,
+## FDR), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok, n.genes, df.camera)).
+## Not offered: use.ranks, trend.var, weights, a sparse X, na = "fit", fry / roast.
+plaid.camera <- function(X, design, G, contrasts = NULL, use = NULL, inter.gene.cor = 0.01, allow.neg.cor = FALSE, minSize = 1,
+                         maxSize = NULL, sort.by = "PValue") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(cs$X)) stop("design must have one row per column of X")
+  cn <- if (is.null(colnames(design))) paste0("coef", seq_len(ncol(design))) else colnames(design)
+  if (!is.null(contrasts)) {
+    contrasts <- as.matrix(contrasts); storage.mode(contrasts) <- "double"
+    if (nrow(contrasts) != ncol(design)) stop("contrasts must have one row per coefficient")
+    cn <- if (is.null(colnames(contrasts))) as.character(seq_len(ncol(contrasts))) else colnames(contrasts)
+  }
+  if (!is.null(use)) {
+    if (length(use) != ncol(cs$X)) stop("use must have one entry per column of X")
+    use <- matrix(as.integer(!is.na(use) & use != 0), ncol = 1)
+  }
+  r <- .camera_call(cs, design, 1L, use, contrasts, inter.gene.cor, allow.neg.cor, length(cn), sort.by)
+  tables <- r$tables
+  names(tables) <- cn
+  list(tables = tables, hyper = .camera_hyper(r$hyper[, 1]))
+}
+
+
+## plaid.camera.contrasts(): plaid.camera() for every column of a contrast matrix Y (samples x contrasts; 0, 1, NA = the
+## sample takes no part) in ONE call, with the designs of plaid.limma.contrasts(): contrast j fits [1, Y[, j], B] on the
+## samples with a label and tests the sets on the moderated t of the coefficient of Y[, j].  X is uploaded once.  Returns
+## list(tables = <named list (the columns of Y) of plaid.camera() tables>, hyper = <named list of their hyper-parameters>).
+plaid.camera.contrasts <- function(X, Y, G, B = NULL, inter.gene.cor = 0.01, allow.neg.cor = FALSE, minSize = 1, maxSize = NULL,
+                                   sort.by = "PValue") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  Y <- as.matrix(Y)
+  if (nrow(Y) != ncol(cs$X)) stop("Y must have one row per column of X")
+  if (!all(unique(as.vector(Y)) %in% c(0, 1, NA))) stop("elements of Y must be 0, 1 or NA")
+  if (!is.null(B)) {
+    B <- as.matrix(B); storage.mode(B) <- "double"
+    if (nrow(B) != ncol(cs$X)) stop("B must have one row per column of X")
+  }
+  D <- do.call(cbind, lapply(seq_len(ncol(Y)), function(j) cbind(1, ifelse(is.na(Y[, j]), 0, Y[, j]), B)))
+  storage.mode(D) <- "double"
+  p <- 2L + (if (is.null(B)) 0L else ncol(B))
+  K <- matrix(0, p, 1); K[2, 1] <- 1
+  use <- matrix(as.integer(!is.na(Y)), nrow(Y), ncol(Y))
+  cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
+  r <- .camera_call(cs, D, ncol(Y), use, K, inter.gene.cor, allow.neg.cor, ncol(Y), sort.by)
+  tables <- r$tables
+  hyper <- lapply(seq_len(ncol(Y)), function(j) .camera_hyper(r$hyper[, j]))
+  names(tables) <- names(hyper) <- cn
+  list(tables = tables, hyper = hyper)
+}
+
+
+## plaid.intergenecor(): limma's interGeneCorrelation(X[set, ], design) for every set of G at once: the variance inflation
+## factor of the set's mean, estimated from the residuals of its genes, and the mean pairwise correlation (VIF - 1) / (m - 1).
+## Returns a matrix, sets x (NGenes, Correlation, VIF), in G's order.
+plaid.intergenecor <- function(X, design, G, use = NULL, minSize = 1, maxSize = NULL) {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(cs$X)) stop("design must have one row per column of X")
+  if (!is.null(use)) {
+    if (length(use) != ncol(cs$X)) stop("use must have one entry per column of X")
+    use <- matrix(as.integer(!is.na(use) & use != 0), ncol = 1)
+  }
+  K <- matrix(0, ncol(design), 1); K[1, 1] <- 1   # (any contrast: the VIF does not depend on it)
+  r <- .camera_call(cs, design, 1L, use, K, NA_real_, TRUE, 1L, "none")
+  matrix(r$raw[, 1:3, 1], nrow = length(cs$names), dimnames = list(cs$names, c("NGenes", "Correlation", "VIF")))
+}
+
+
 ## replaid.gsva(), R/plaid.R:338-363: the row transform ("z" or "ecdf"), the signed ranks, the power and
 ## plaid() run on the device in one call.
 replaid.gsva <- function(X, matG, tau = 0, rowtf = c("z", "ecdf")[1]) {

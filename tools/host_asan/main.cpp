@@ -271,6 +271,63 @@ static void rankcor() {
   printf("  rankcor: the finish step at n = 2 .. 131,072, k = 0 .. n, and refused operands\n");
 }
 
+// plaid.camera's host half: plaidhip_camera_residual_row with samples left out and genes that are not ok, and
+// plaidhip_camera_finish with estimated and fixed correlations over sets of 0 .. G ok members and universes of 0 .. 3 genes
+static void camera() {
+  std::mt19937_64 rng(11);
+  std::normal_distribution<double> N(0.0, 1.0);
+  for (int p : {1, 4, 32}) {
+    const int n = p + 5;
+    std::vector<double> x((size_t)n), Q((size_t)n * p), E((size_t)p), z((size_t)n, -7.0);
+    std::vector<int8_t> use((size_t)n, 1);
+    use[1] = 0;
+    for (auto& v : x) v = N(rng);
+    for (auto& v : Q) v = N(rng);
+    for (auto& v : E) v = N(rng);
+    x[1] = NAN;
+    REQUIRE(plaidhip_camera_residual_row(n, p, x.data(), Q.data(), use.data(), E.data(), 2.5, 4.0, z.data()) == PLAIDHIP_OK);
+    REQUIRE(z[1] == 0.0);
+    for (int c = 0; c < n; ++c) REQUIRE(std::isfinite(z[(size_t)c]));
+    REQUIRE(plaidhip_camera_residual_row(n, p, x.data(), Q.data(), nullptr, E.data(), NAN, 4.0, z.data()) == PLAIDHIP_OK);
+    for (int c = 0; c < n; ++c) REQUIRE(z[(size_t)c] == 0.0);
+    REQUIRE(plaidhip_camera_residual_row(n, p, x.data(), Q.data(), nullptr, E.data(), 0.0, 4.0, z.data()) == PLAIDHIP_OK);   // the floor
+    REQUIRE(std::isnan(z[1]) && std::isfinite(z[0]));
+  }
+  for (int g : {0, 1, 2, 3, 400}) {
+    const int m = 5, nfit = 2, q = 2;
+    std::vector<double> t((size_t)g * q * nfit), sumt((size_t)m * q * nfit), cnt((size_t)m * nfit), ss((size_t)m * nfit);
+    std::vector<int8_t> ok((size_t)g * nfit, 1);
+    for (auto& v : t) v = N(rng);
+    if (g >= 3) { ok[1] = 0; t[1] = NAN; }
+    const int G0 = g >= 3 ? g - 1 : g;
+    const int sizes[m] = {0, 1, G0 / 2, G0 > 0 ? G0 - 1 : 0, G0};
+    for (int f = 0; f < nfit; ++f)
+      for (int s = 0; s < m; ++s) {
+        cnt[(size_t)f * m + s] = (double)std::min(sizes[s], f == 0 ? G0 : g);
+        ss[(size_t)f * m + s] = std::fabs(N(rng)) * 10.0 * (sizes[s] + 1);
+        for (int j = 0; j < q; ++j) sumt[((size_t)f * q + j) * m + s] = N(rng) * sizes[s];
+      }
+    const double dres[2] = {6.0, 1.0}, dprior[2] = {3.5, INFINITY};
+    std::vector<double> out((size_t)m * 8 * q * nfit, -7.0), gdf((size_t)nfit * 2, -7.0);
+    for (int mode = 0; mode < 3; ++mode) {
+      REQUIRE(plaidhip_camera_finish(g, m, nfit, q, t.data(), ok.data(), sumt.data(), cnt.data(), mode == 2 ? nullptr : ss.data(), dres,
+                                     dprior, mode == 2 ? -0.05 : NAN, mode == 1, out.data(), gdf.data()) == PLAIDHIP_OK);
+      REQUIRE(gdf[0] == (double)G0 && gdf[2] == (double)g);
+      for (size_t col = 0; col < (size_t)q * nfit; ++col)
+        for (int s = 0; s < m; ++s) {
+          const double* o = out.data() + col * 8 * m;
+          const double pv = o[6 * m + s], fdr = o[7 * m + s];
+          REQUIRE(o[s] == cnt[(col / q) * m + s]);
+          REQUIRE(std::isnan(pv) ? std::isnan(fdr) : (pv >= 0.0 && pv <= 1.0 && fdr >= pv - 1e-15 && fdr <= 1.0));
+          REQUIRE(g >= 3 || std::isnan(pv));
+        }
+    }
+    REQUIRE(plaidhip_camera_finish(g, m, nfit, q, t.data(), ok.data(), sumt.data(), cnt.data(), nullptr, dres, dprior, 1.0, 0, out.data(),
+                                   gdf.data()) == PLAIDHIP_EINVAL);
+  }
+  printf("  camera: the residual row at 1, 4 and 32 coefficients, the finish step over universes of 0 .. 400 genes, refused operands\n");
+}
+
 int main() {
   printf("[host-asan] planners\n");
   plans();
@@ -282,6 +339,8 @@ int main() {
   limma();
   printf("[host-asan] plaid.rankcor's finish\n");
   rankcor();
+  printf("[host-asan] plaid.camera's residual row and finish\n");
+  camera();
   printf("[host-asan] ok\n");
   return 0;
 }
