@@ -175,7 +175,7 @@ int acquire_geneset(plaidhip_ctx* ctx, int32_t g, int32_t m, const int32_t* Gp, 
 }  // namespace plaidhip
 namespace {
 
-// (pageable memory: through the pinned staging ring once it is worth it, multi.cpp)
+// (pageable memory: through the pinned staging ring once it is worth it, shard.cpp)
 int h2d(plaidhip_ctx* ctx, void* dst, const void* src, size_t bytes) {
   return upload_host(ctx, dst, 1, src, 1, (int64_t)bytes);
 }
@@ -828,7 +828,7 @@ int plaidhip_plaid_dense(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t 
                          double* S_out) try {
   PH_REQUIRE(stat == PLAIDHIP_STAT_MEAN || stat == PLAIDHIP_STAT_SUM, "plaid_dense: bad stat %d", stat);
   PH_REQUIRE(n == 0 || (X && S_out), "plaid_dense: null X/S_out");
-  // one shard on this context: pipelined upload, crossprod per column panel, normalize_medians, download (multi.cpp)
+  // one shard on this context: pipelined upload, crossprod per column panel, normalize_medians, download (shard_rank_sum.cpp)
   return dispatch(on_context(ctx), plaid_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, stat, normalize, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
@@ -1004,7 +1004,7 @@ int plaidhip_sing_dense(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
 // replaid.sing for a dgCMatrix X: colranks(X, ties.method = "min") ranks the zeros too (sparse branch without keep.zero,
 // R/plaid.R:602-609), / nrow(X) - 0.5, plaid(normalize = FALSE) (:215-217).  The reference densifies X to rank it; here
 // the CSC slots go to the device as they are, the dense min-ranks are built per panel of columns from the ranks of the
-// stored values (zeros tie), and the rank crossprod runs on each panel (multi.cpp: shard_worker): neither the host nor
+// stored values (zeros tie), and the rank crossprod runs on each panel (shard_rank_sum.cpp: shard_worker): neither the host nor
 // the PCIe link sees a dense X.
 int plaidhip_sing_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g, int32_t n,
                       const int32_t* Gp, const int32_t* Gi, int32_t m, double* S_out) try {
@@ -1027,7 +1027,7 @@ int plaidhip_ssgsea_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
   return dispatch(on_context(ctx), ssgsea_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, alpha, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.ssgsea.exact: the one-device form of the sharded engine (multi.cpp: ssgsea_exact_worker)
+// replaid.ssgsea.exact: the one-device form of the sharded engine (shard_exact.cpp: ssgsea_exact_worker)
 int plaidhip_ssgsea_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                           const int32_t* Gp, const int32_t* Gi, int32_t m, double alpha, int scale, int norm,
                           double* S_out) try {
@@ -1044,7 +1044,7 @@ int plaidhip_ssgsea_exact_ks(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t
 }  // extern "C"
 
 // ---- replaid.ucell / aucell / scse / gsva and plaid.test: the one-shard case of the sharded engine ------------------------
-// (multi.cpp: scorer_worker, plaid_test_worker; dispatch checks the arguments first)
+// (shard_scorer.cpp: scorer_worker, shard_plaid_test.cpp: plaid_test_worker; dispatch checks the arguments first)
 extern "C" {
 
 int plaidhip_ucell(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x,
@@ -1119,7 +1119,7 @@ int plaidhip_dev_row_contrast_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld
 int plaidhip_contrast_tile(void) { return PLAIDHIP_CONTRAST_TILE; }
 
 // The host half of plaid.test (R/plaid.R:410-474): p-values, effect sizes, meta-p and FDR from the reduced statistics.
-// Shared by the sharded engine (multi.cpp: run_call) and by callers over RCCL, which all-reduce the statistics first.
+// Shared by the sharded engine (shard_plaid_test.cpp: plaid_test_tail) and by callers over RCCL, which all-reduce the statistics first.
 int plaidhip_plaid_test_finish(int32_t g, int32_t m, const int32_t* Gp, const double* T, double tot1, double tot2,
                                const double* SM, int64_t n0, int64_t n1, int tests, int metap_method, double* out) try {
   PH_REQUIRE(g >= 0 && m >= 0 && (m == 0 || (Gp && out)), "plaid_test_finish: null Gp / out");
@@ -1171,7 +1171,7 @@ int plaidhip_plaid_test(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n
   return dispatch(on_context(ctx), plaid_test_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, y, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// plaid.test.contrasts: the one-shard case of plaid_test_contrasts_worker (multi.cpp)
+// plaid.test.contrasts: the one-shard case of plaid_test_worker with C label columns (shard_plaid_test.cpp)
 int plaidhip_plaid_test_contrasts(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Y, int32_t C,
                                   const int32_t* Gp, const int32_t* Gi, int32_t m, const double* gsetX, int tests,
                                   int metap_method, double* out) try {
@@ -1186,14 +1186,14 @@ int plaidhip_plaid_test_contrasts_csc(plaidhip_ctx* ctx, const int32_t* Xp, cons
   return dispatch(on_context(ctx), plaid_test_contrasts_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, Y, C, gsetX, tests, metap_method, out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.gsva.exact: the one-device form of the sharded engine (multi.cpp: scorer_worker, kGsvaExact)
+// replaid.gsva.exact: the one-device form of the sharded engine (shard_scorer.cpp: scorer_worker, kGsvaExact)
 int plaidhip_gsva_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                         const int32_t* Gp, const int32_t* Gi, int32_t m, double tau, int rowtf, int max_diff,
                         double* S_out) try {
   return dispatch(on_context(ctx), gsva_exact_call({Xp, Xi, X_or_x, g, n, Gp, Gi, m}, tau, rowtf, max_diff, S_out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// plaid.gsea: the one-device form of the sharded engine (multi.cpp: gsea_worker, kGsea)
+// plaid.gsea: the one-device form of the sharded engine (shard_gsea.cpp: gsea_worker, kGsea)
 int plaidhip_gsea(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c, const int32_t* Gp,
                   const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed, double* out,
                   double* null_out) try {
@@ -1208,7 +1208,7 @@ int plaidhip_gsea_scored(plaidhip_ctx* ctx, const double* stat, const double* we
                   gsea_call(stat, weight, g, c, Gp, Gi, m, perm, nperm, seed, out, null_out, score_type, le_len, le_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
-// plaid.gsea with multilevel p-values, and one ruler's trace: the same engine (multi.cpp: gsea_worker / gsea_ruler_worker,
+// plaid.gsea with multilevel p-values, and one ruler's trace: the same engine (shard_gsea.cpp: gsea_worker / gsea_ruler_worker,
 // kGseaMultilevel)
 int plaidhip_gsea_multilevel(plaidhip_ctx* ctx, const double* stat, const double* weight, int32_t g, int32_t c,
                              const int32_t* Gp, const int32_t* Gi, int32_t m, const int32_t* perm, int32_t nperm, uint64_t seed,
@@ -1225,13 +1225,13 @@ int plaidhip_gsea_ruler(plaidhip_ctx* ctx, const double* stat, const double* wei
                                                    nstages, end_status, m_out, s_out, h_out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// plaid.rankcor: the one-device form of the sharded engine (multi.cpp: rankcor_worker, kRankcor)
+// plaid.rankcor: the one-device form of the sharded engine (shard_lists.cpp: rankcor_worker, kRankcor)
 int plaidhip_rankcor(plaidhip_ctx* ctx, const double* stat, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
                      int use_rank, int ties, double* out, double* tot_out) try {
   return dispatch(on_context(ctx), rankcor_call(stat, g, c, Gp, Gi, m, use_rank, ties, out, tot_out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.plage / replaid.zscore: the one-device forms of the sharded engine (multi.cpp: plage_worker, kPlage / kZscore)
+// replaid.plage / replaid.zscore: the one-device forms of the sharded engine (shard_lists.cpp: plage_worker, kPlage / kZscore)
 int plaidhip_plage(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const int32_t* Gp, const int32_t* Gi, int32_t m,
                    double tol, int32_t maxit, double* S_out, double* info_out, double* load_out) try {
   return dispatch(on_context(ctx), plage_call({nullptr, nullptr, X, g, n, Gp, Gi, m}, tol, maxit, S_out, info_out, load_out));
@@ -1255,13 +1255,13 @@ int plaidhip_zscore_csc(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
   return dispatch(on_context(ctx), zscore_call({Xp, Xi, Xx, g, n, Gp, Gi, m}, S_out, size_out));
 } catch (...) { return plaidhip::on_exception(); }
 
-// plaid.fisher: the one-device form of the sharded engine (multi.cpp: fisher_worker, kFisher)
+// plaid.fisher: the one-device form of the sharded engine (shard_lists.cpp: fisher_worker, kFisher)
 int plaidhip_fisher(plaidhip_ctx* ctx, const int8_t* sig, int32_t g, int32_t c, const int32_t* Gp, const int32_t* Gi, int32_t m,
                     double* out, double* tot_out, int32_t* ov_len, int32_t* ov_idx) try {
   return dispatch(on_context(ctx), fisher_call(sig, g, c, Gp, Gi, m, out, tot_out, ov_len, ov_idx));
 } catch (...) { return plaidhip::on_exception(); }
 
-// plaid.limma: the one-device form of the sharded engine (multi.cpp: limma_worker, kLimma)
+// plaid.limma: the one-device form of the sharded engine (shard_limma.cpp: limma_worker, kLimma)
 int plaidhip_limma(plaidhip_ctx* ctx, const double* A, int32_t rows, int32_t n, const double* design, int32_t p, int32_t nfit,
                    const int8_t* use, const double* K, int32_t q, double* out, double* hyper) try {
   return dispatch(on_context(ctx), limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper));
@@ -1312,7 +1312,7 @@ int plaidhip_dev_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, 
 
 int plaidhip_limma_tile(void) { return PLAIDHIP_LIMMA_TILE; }
 
-// plaid.camera: the one-device form of the sharded engine (multi.cpp: limma_worker with kCamera, camera_tail)
+// plaid.camera: the one-device form of the sharded engine (shard_limma.cpp: limma_worker with kCamera, camera_tail)
 int plaidhip_camera(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
                     const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
                     double inter_gene_cor, int allow_neg_cor, double* out, double* hyper) try {
@@ -1430,7 +1430,7 @@ int plaidhip_debug_gsva_kcdf_slow_terms(unsigned long long* out) try {
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.sing.exact: the one-device form of the sharded engine (multi.cpp: sing_exact_worker)
+// replaid.sing.exact: the one-device form of the sharded engine (shard_exact.cpp: sing_exact_worker)
 int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                         const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, int center,
                         double* total, double* up, double* down, double* total_disp, double* up_disp, double* down_disp) try {
@@ -1438,7 +1438,7 @@ int plaidhip_sing_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi,
                                                    down_disp));
 } catch (...) { return plaidhip::on_exception(); }
 
-// replaid.ucell.exact / replaid.aucell.exact: the one-device forms of the sharded engine (multi.cpp: truncated_exact_worker)
+// replaid.ucell.exact / replaid.aucell.exact: the one-device forms of the sharded engine (shard_exact.cpp: truncated_exact_worker)
 int plaidhip_ucell_exact(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* X_or_x, int32_t g, int32_t n,
                          const int32_t* Gp, const int32_t* Gi, const int32_t* Dp, const int32_t* Di, int32_t m, double max_rank,
                          double w_neg, int impute, const double* k_full, const double* k_full_down, double* total, double* up,

@@ -1,5 +1,5 @@
 // One host-level scorer call: what it computes (Call), where it runs (Target), and the one way in (dispatch, multi.cpp).
-// Host only: api.cpp and multi.cpp.
+// Host only: api.cpp, multi.cpp and the sharded engine (shard.h, shard.cpp, shard_*.cpp).
 #pragma once
 
 #include <vector>
@@ -14,7 +14,7 @@ enum Method : int {
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
   kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21
 };
-inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker
+inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker's three
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
 
 // the matrix and the aligned set collection every scorer takes: X dense (Xp == nullptr) or the slots of a dgCMatrix
@@ -425,7 +425,7 @@ inline Target on_hook(int device, int nshards, int fail_shard) {
 }
 
 // The one way in (multi.cpp): the device list's (or the hook's) own checks, check_call, a null context, the empty result,
-// the contexts, run_call.  Nothing before the contexts touches a device.
+// the contexts, run_call (shard.cpp).  Nothing before the contexts touches a device.
 int dispatch(const Target& t, Call c);
 // the argument checks of every method, which touch no device.  multi: a plaidhip_*_multi entry, which refuses replaid.gsva's
 // rowtf = "ecdf" whatever the device count; the others take it on one shard.  Counts plaid.test's groups into c.n0 / c.n1.

@@ -1,0 +1,322 @@
+// plaid.limma and plaid.camera on the sharded engine (shard.cpp).
+#include "shard.h"
+
+namespace plaidhip {
+
+namespace {
+
+// plaid.limma with na = "fit", after the effects are chained: shard 0 merges the shards' NaN lists in shard order (a row's
+// columns ascending), decides which rows are fitted (max_na) and which (row, fit) pairs are incomplete, and runs Gram and
+// solve (kernels_lmfit.hip) over those: the pair's effects in sh.limma.effects become gamma, its mean the mean over the
+// observed samples, and sh.limma.na_d / na_u take every row's df.residual (NaN: not fitted) and u_j.  A pair's chain runs
+// over the row's own missing samples in ascending order whatever the sharding, so every sharding has the one-device bits.
+int limma_na_refit(plaidhip_ctx* ctx, const Call& c, int ndev, Shared& sh, double* d_E) {
+  const int32_t rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, q = c.nq;
+  const size_t R = (size_t)rows;
+  const int64_t W = (int64_t)nfit * (p + 1);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int64_t> off(R + 1, 0);
+  for (size_t r = 0; r < R; ++r) {
+    int64_t tot = 0;
+    for (int k = 0; k < ndev; ++k) tot += sh.limma.na_cnt[(size_t)k].empty() ? 0 : sh.limma.na_cnt[(size_t)k][r];
+    off[r + 1] = off[r] + tot;
+  }
+  std::vector<int32_t> list((size_t)off[R]);
+  std::vector<size_t> pos((size_t)ndev, 0);
+  for (size_t r = 0; r < R; ++r) {
+    int64_t w = off[r];
+    for (int k = 0; k < ndev; ++k) {
+      const int32_t ck = sh.limma.na_cnt[(size_t)k].empty() ? 0 : sh.limma.na_cnt[(size_t)k][r];
+      std::copy(sh.limma.na_list[(size_t)k].begin() + pos[(size_t)k], sh.limma.na_list[(size_t)k].begin() + pos[(size_t)k] + ck,
+                list.begin() + w);
+      pos[(size_t)k] += (size_t)ck;
+      w += ck;
+    }
+  }
+  sh.limma.na_d.assign(R * nfit, nan);
+  sh.limma.na_u.assign(R * nfit * q, nan);
+  std::vector<int32_t> pairs, nobs;
+  for (int32_t f = 0; f < nfit; ++f)
+    for (size_t r = 0; r < R; ++r) {
+      const bool fitted = (double)(off[r + 1] - off[r]) / (double)n <= c.max_na;   // rowMeans(is.na(X)) <= max.na
+      const int64_t mis = sh.limma.na_pair[R * f + r], d = c.lm_nf[(size_t)f] - mis - p;
+      if (fitted && d >= 1) sh.limma.na_d[R * f + r] = (double)d;
+      for (int32_t j = 0; j < q; ++j) sh.limma.na_u[((size_t)f * q + j) * R + r] = c.lm_u[(size_t)f * q + j];
+      if (mis > 0 && fitted && d >= 1) {
+        pairs.push_back((int32_t)r);
+        pairs.push_back(f);
+        nobs.push_back((int32_t)(c.lm_nf[(size_t)f] - mis));
+      }
+    }
+  const size_t np = nobs.size();
+  if (np == 0) return PLAIDHIP_OK;
+  std::vector<double> nfd((size_t)nfit), upair(np * q);
+  std::vector<int32_t> okp(np);
+  for (int32_t f = 0; f < nfit; ++f) nfd[(size_t)f] = (double)c.lm_nf[(size_t)f];
+  DevBuf dpairs, doff, dlist, dQ, duse, dv, dnobs, dnf, du, dok;
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
+    PH_TRY(b.alloc(bytes));
+    PH_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return PLAIDHIP_OK;
+  };
+  PH_TRY(up(dpairs, pairs.data(), pairs.size() * 4));
+  PH_TRY(up(doff, off.data(), off.size() * 8));
+  PH_TRY(up(dlist, list.data(), list.size() * 4));
+  PH_TRY(up(dQ, c.lm_Q.data(), c.lm_Q.size() * 8));
+  if (c.use != nullptr) PH_TRY(up(duse, c.use, (size_t)n * nfit));
+  PH_TRY(up(dv, c.lm_v.data(), c.lm_v.size() * 8));
+  PH_TRY(up(dnobs, nobs.data(), np * 4));
+  PH_TRY(up(dnf, nfd.data(), nfd.size() * 8));
+  PH_TRY(du.alloc(np * q * 8));
+  PH_TRY(dok.alloc(np * 4));
+  PH_HIP(hipMemcpyAsync(d_E, sh.limma.effects.data(), (size_t)W * R * 8, hipMemcpyHostToDevice, ctx->stream));
+  PH_TRY(launch_lmfit_na_solve(ctx, (int64_t)np, dpairs.as<int32_t>(), doff.as<int64_t>(), dlist.as<int32_t>(), dQ.as<double>(),
+                               c.use != nullptr ? duse.as<int8_t>() : nullptr, n, p, q, dv.as<double>(), dnobs.as<int32_t>(),
+                               dnf.as<double>(), rows, d_E, du.as<double>(), dok.as<int32_t>()));
+  PH_HIP(hipMemcpyAsync(sh.limma.effects.data(), d_E, (size_t)W * R * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipMemcpyAsync(upair.data(), du.p, np * q * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipMemcpyAsync(okp.data(), dok.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < np; ++i) {
+    const size_t r = (size_t)pairs[2 * i], f = (size_t)pairs[2 * i + 1];
+    if (!okp[i]) sh.limma.na_d[R * f + r] = nan;
+    for (int32_t j = 0; j < q; ++j) sh.limma.na_u[(f * q + j) * R + r] = upair[i * q + j];
+  }
+  return PLAIDHIP_OK;
+}
+
+}  // namespace
+
+// one device's part of plaid.limma (kLimma, kernels_lmfit.hip; include/plaidhip.h: plaidhip_limma).  The SAMPLES are shared
+// out at multiples of 128 columns, as for plaid.test.contrasts: a shard takes its columns of A and its rows of every Q_f and
+// of use.  Round one chains the effects and means [W][rows] from shard to shard; after it every shard holds the effects of
+// all samples and takes the residual sums of squares of its own columns, which round two chains as [nfit][rows].  The block
+// partials are added in the order of the one-device call, so every sharding has its bits.  2 ndev rendezvous.
+// na = "fit" (c.na_fit): both passes take the select "used and not NaN"; round one also lists the NaN of the shard's columns
+// (the count pass), and between the rounds shard 0 refits the incomplete (row, fit) pairs (limma_na_refit): one more rendezvous.
+int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t lo = s.lo, nloc = s.nloc, rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit;
+  const int64_t W = (int64_t)nfit * (p + 1), ld = even_ld(rows);
+  if (c.method == kCamera) s.force_f64();   // (T = G'Z stays on the fp64 kernels whatever precision the context was given)
+  CtxBuf dA{ctx, 0};
+  DevBuf dQ, duse, dinvn, dmask, dwt, dws, drows;
+  double *d_seed = nullptr, *d_run = nullptr, *d_E = nullptr;
+  // host sources of asynchronous uploads: they live until the worker's last synchronisation
+  std::vector<double> qloc;
+  std::vector<int8_t> uloc;
+
+  // ---- upload; the shard's rows of Q and use, their masks and tile weights; the effects' block partials ----------------------
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    PH_HIP(hipSetDevice(ctx->device));
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(drows.alloc((size_t)W * rows * 3 * 8));   // [seed | running sums | the effects of all samples], [W][rows] each
+    d_seed = drows.as<double>();
+    d_run = d_seed + W * rows;
+    d_E = d_run + W * rows;
+    qloc.resize((size_t)nloc * p * nfit);
+    for (int64_t col = 0; col < (int64_t)p * nfit; ++col)
+      std::copy(c.lm_Q.begin() + col * n + lo, c.lm_Q.begin() + col * n + lo + nloc, qloc.begin() + col * nloc);
+    PH_TRY(dQ.alloc(qloc.size() * 8));
+    PH_HIP(hipMemcpyAsync(dQ.p, qloc.data(), qloc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (c.use != nullptr) {
+      uloc.resize((size_t)nloc * nfit);
+      for (int32_t f = 0; f < nfit; ++f)
+        std::copy(c.use + (size_t)f * n + lo, c.use + (size_t)f * n + lo + nloc, uloc.begin() + (size_t)f * nloc);
+      PH_TRY(duse.alloc(uloc.size()));
+      PH_HIP(hipMemcpyAsync(duse.p, uloc.data(), uloc.size(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    PH_TRY(dinvn.alloc((size_t)nfit * 8));
+    PH_HIP(hipMemcpyAsync(dinvn.p, c.lm_invn.data(), (size_t)nfit * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dmask.alloc((size_t)lmfit_mask_bytes(nloc, W)));
+    PH_TRY(dwt.alloc((size_t)lmfit_weight_bytes(nloc, W)));
+    PH_TRY(launch_lmfit_masks(ctx, dQ.as<double>(), c.use != nullptr ? duse.as<int8_t>() : nullptr, dinvn.as<double>(), nloc, p,
+                              nfit, dmask.p, dwt.as<double>()));
+    PH_TRY(dws.alloc((size_t)row_design_ws_doubles(rows, nloc, W) * 8));   // (W >= nfit: the RSS partials fit too)
+    PH_TRY(dA.alloc((size_t)ld * nloc * 8));
+    PH_TRY(upload_pipelined(ctx, dA.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X + (int64_t)lo * rows),
+                            (size_t)rows * 8, nloc, nullptr));
+    PH_TRY(launch_row_design_effects(ctx, dA.as<double>(), ld, rows, nloc, dmask.p, dwt.as<double>(), (int32_t)W,
+                                     dws.as<double>(), c.na_fit != 0));
+    if (!c.na_fit) return PLAIDHIP_OK;
+    // the count pass: the NaN of every (column block, row) of the shard, their columns in ascending order (a second sweep,
+    // once the space is known), and the NaN of every (fit, row) inside the fit's used samples
+    std::vector<int32_t>& cnt = sh.limma.na_cnt[(size_t)k];
+    std::vector<int32_t>& list = sh.limma.na_list[(size_t)k];
+    const size_t R = (size_t)rows, nblk = ((size_t)nloc + 127) / 128;
+    std::vector<int32_t> bcnt(nblk * R);                   // [block][row]
+    DevBuf dcnt, doff, drow, dlist, dpc;
+    PH_TRY(dcnt.alloc(bcnt.size() * 4));
+    PH_TRY(launch_lmfit_nan_rows(ctx, dA.as<double>(), ld, rows, nloc, nullptr, dcnt.as<int32_t>(), nullptr));
+    PH_HIP(hipMemcpyAsync(bcnt.data(), dcnt.p, bcnt.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    cnt.assign(R, 0);
+    std::vector<int64_t> off(nblk * R), rowoff(R + 1, 0);   // where (block, row) writes; where a row's list starts
+    int64_t run = 0;
+    for (size_t r = 0; r < R; ++r) {
+      for (size_t b = 0; b < nblk; ++b) {
+        off[b * R + r] = run;
+        run += bcnt[b * R + r];
+      }
+      cnt[r] = (int32_t)(run - rowoff[r]);
+      rowoff[r + 1] = run;
+    }
+    const size_t total = (size_t)run;
+    if (total == 0) return PLAIDHIP_OK;
+    std::vector<int32_t> pc((size_t)nfit * rows);
+    list.resize(total);
+    PH_TRY(doff.alloc(off.size() * 8));
+    PH_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(drow.alloc(rowoff.size() * 8));
+    PH_HIP(hipMemcpyAsync(drow.p, rowoff.data(), rowoff.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dlist.alloc(total * 4));
+    PH_TRY(dpc.alloc(pc.size() * 4));
+    PH_TRY(launch_lmfit_nan_rows(ctx, dA.as<double>(), ld, rows, nloc, doff.as<int64_t>(), nullptr, dlist.as<int32_t>()));
+    PH_TRY(launch_lmfit_nan_pairs(ctx, drow.as<int64_t>(), dlist.as<int32_t>(), c.use != nullptr ? duse.as<int8_t>() : nullptr,
+                                  rows, nloc, nfit, dpc.as<int32_t>()));
+    PH_HIP(hipMemcpyAsync(list.data(), dlist.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(pc.data(), dpc.p, pc.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    for (int32_t& col : list) col += lo;
+    std::lock_guard<std::mutex> lk(sh.mu);
+    for (size_t i = 0; i < pc.size(); ++i) sh.limma.na_pair[i] += pc[i];
+    return PLAIDHIP_OK;
+  });
+  chain_flat_sums(s, sh.limma.effects, dws.as<double>(), W * rows, d_seed, d_run);
+  if (c.na_fit) {   // (every shard's lists are complete: chain_flat_sums has met ndev times since)
+    if (k == 0) s.step([&]() -> int { return limma_na_refit(ctx, c, ndev, sh, d_E); });
+    sh.rv.arrive_and_wait();
+  }
+
+  // ---- the residual sums of squares of the shard's columns at the effects of ALL samples -------------------------------------
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_HIP(hipMemcpyAsync(d_E, sh.limma.effects.data(), (size_t)W * rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    return launch_row_design_rss(ctx, dA.as<double>(), ld, rows, nloc, dQ.as<double>(), dmask.p, p, nfit, d_E,
+                                 dws.as<double>(), c.na_fit != 0);
+  });
+  chain_flat_sums(s, sh.limma.rss, dws.as<double>(), (int64_t)nfit * rows, d_seed, d_run);
+  if (c.method != kCamera || !std::isnan(c.inter_gene_cor)) return s.finish();
+
+  // ---- plaid.camera, the estimated correlation: fit by fit, Z of the shard's columns from the effects and the residual sums of
+  // squares of ALL samples (every shard has met ndev times since the last of them was added), T = G'Z by the dense crossprod,
+  // and the block partials of the sums of T^2, [nblk][nfit][m]; round three chains them as [nfit][m].  One fit's Z and T are
+  // alive at a time. ----------------------------------------------------------------------------------------------------------
+  const int32_t m = c.m;
+  CtxBuf dZ{ctx, 3}, dT{ctx, 4}, dsq{ctx, 5};   // (they live in the context between calls, as A does)
+  double *d_part = nullptr, *d_chain = nullptr;   // dsq: [the block partials | the chain's seed | its running sums]
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    plaidhip_geneset* gs = nullptr;
+    PH_TRY(acquire_geneset(ctx, rows, m, c.Gp, c.Gi, &gs));
+    double* d_rss = d_seed;   // (the chains above are done with it; W >= nfit)
+    PH_HIP(hipMemcpyAsync(d_rss, sh.limma.rss.data(), (size_t)nfit * rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dZ.alloc((size_t)ld * nloc * 8));
+    PH_TRY(dT.alloc((size_t)m * nloc * 8));
+    const size_t npart = (size_t)camera_sumsq_ws_doubles(nloc, (int64_t)nfit * m);
+    PH_TRY(dsq.alloc((npart + (size_t)nfit * m * 2) * 8));
+    d_part = dsq.as<double>();
+    d_chain = d_part + npart;
+    for (int32_t f = 0; f < nfit; ++f) {
+      PH_TRY(launch_camera_residuals(ctx, dA.as<double>(), ld, rows, nloc, dQ.as<double>(), dmask.p, p, f, d_E, d_rss,
+                                     (double)(c.lm_nf[(size_t)f] - p), dZ.as<double>(), ld));
+      PH_TRY(launch_spmm_dense_f64(ctx, gs, dZ.as<double>(), ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(), m,
+                                   nullptr));
+      PH_TRY(launch_camera_sumsq(ctx, dT.as<double>(), m, m, nloc, d_part + (size_t)f * m, (int64_t)nfit * m));
+    }
+    return PLAIDHIP_OK;
+  });
+  chain_flat_sums(s, sh.camera.ss, d_part, (int64_t)nfit * m, d_chain, d_chain + (size_t)nfit * m);
+  return s.finish();
+}
+
+bool limma_empty(const Call& c) { return c.g == 0 || c.nfit == 0 || c.nq == 0 || (c.method == kCamera && c.m == 0); }
+
+void limma_prepare(Shared& sh, const Call& c, int ndev) {
+  if (c.method == kCamera) sh.camera.ss.assign((size_t)c.nfit * c.m, 0.0);
+  sh.limma.effects.assign((size_t)c.nfit * (c.ncoef + 1) * c.g, 0.0);
+  sh.limma.rss.assign((size_t)c.nfit * c.g, 0.0);
+  if (c.na_fit) {
+    sh.limma.na_cnt.resize((size_t)ndev);
+    sh.limma.na_list.resize((size_t)ndev);
+    sh.limma.na_pair.assign((size_t)c.nfit * c.g, 0);
+  }
+}
+
+// plaid.limma after the workers: eBayes and the tables, on the host from the chained sums
+int limma_tail(plaidhip_ctx*, const Call& c, Shared& sh) {
+  if (!c.na_fit)
+    return plaidhip_limma_finish(c.g, c.ncoef, c.nfit, c.nq, sh.limma.effects.data(), sh.limma.rss.data(), c.lm_nf.data(),
+                                 c.lm_v.data(), c.lm_u.data(), c.out, c.hyper);
+  PH_TRY(plaidhip_limma_finish_na(c.g, c.ncoef, c.nfit, c.nq, sh.limma.effects.data(), sh.limma.rss.data(), c.lm_nf.data(),
+                                  c.lm_v.data(), sh.limma.na_d.data(), sh.limma.na_u.data(), c.out, c.hyper));
+  const size_t R = (size_t)c.g;   // df.residual of the rows that came out of the fit; NaN for the others
+  for (int32_t f = 0; f < c.nfit; ++f) {
+    const double* sigma2 = c.out + ((size_t)f * c.nq * 6 + 5) * R;   // (of the fit's first contrast: NaN = not ok)
+    for (size_t r = 0; r < R; ++r)
+      c.dfres[R * f + r] = std::isnan(sigma2[r]) ? std::numeric_limits<double>::quiet_NaN() : sh.limma.na_d[R * f + r];
+  }
+  return PLAIDHIP_OK;
+}
+
+// plaid.camera after the workers: eBayes and the gene statistics on the host (plaidhip_limma_finish), the member sums of t
+// and the counts of ok members from ONE crossprod of the membership with [the t columns | the ok indicators] on the first
+// context (a gene that is not ok holds 0.0 in both), then the pinned test (plaidhip_camera_finish).
+int camera_tail(plaidhip_ctx* ctx, const Call& c, Shared& sh) {
+  const int32_t g = c.g, m = c.m, nfit = c.nfit, q = c.nq, p = c.ncoef;
+  const size_t R = (size_t)g, ncol = (size_t)nfit * q;
+  std::vector<double> tab(R * 6 * ncol), hyp((size_t)nfit * 4);
+  PH_TRY(plaidhip_limma_finish(g, p, nfit, q, sh.limma.effects.data(), sh.limma.rss.data(), c.lm_nf.data(), c.lm_v.data(),
+                               c.lm_u.data(), tab.data(), hyp.data()));
+  std::vector<double> B(R * (ncol + nfit)), t(R * ncol), S((size_t)m * (ncol + nfit)), dres((size_t)nfit), dprior((size_t)nfit);
+  std::vector<int8_t> ok(R * nfit);
+  for (int32_t f = 0; f < nfit; ++f) {
+    const double* sigma2 = tab.data() + ((size_t)f * q * 6 + 5) * R;   // (of the fit's first contrast: NaN = not ok)
+    for (size_t r = 0; r < R; ++r) {
+      ok[R * f + r] = std::isnan(sigma2[r]) ? 0 : 1;
+      B[(ncol + f) * R + r] = ok[R * f + r] ? 1.0 : 0.0;
+    }
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      const double* tj = tab.data() + (col * 6 + 2) * R;
+      for (size_t r = 0; r < R; ++r) {
+        t[col * R + r] = tj[r];
+        B[col * R + r] = ok[R * f + r] ? tj[r] : 0.0;
+      }
+    }
+    dres[(size_t)f] = hyp[4 * (size_t)f];
+    dprior[(size_t)f] = hyp[4 * (size_t)f + 1];
+  }
+  const int saved = ctx->precision;
+  ctx->precision = PLAIDHIP_PRECISION_F64;
+  int rc = [&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    plaidhip_geneset* gs = nullptr;
+    PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    DevBuf dB, dS;
+    PH_TRY(dB.alloc(B.size() * 8));
+    PH_TRY(dS.alloc(S.size() * 8));
+    PH_TRY(upload_host(ctx, dB.p, R * 8, B.data(), R * 8, (int64_t)(ncol + nfit)));
+    PH_TRY(launch_spmm_dense_f64(ctx, gs, dB.as<double>(), g, (int32_t)(ncol + nfit), PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0,
+                                 dS.as<double>(), m, nullptr));
+    PH_HIP(hipMemcpyAsync(S.data(), dS.p, S.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PLAIDHIP_OK;
+  }();
+  ctx->precision = saved;
+  if (rc != PLAIDHIP_OK) return rc;
+  const bool estimate = std::isnan(c.inter_gene_cor);
+  std::vector<double> gdf((size_t)nfit * 2);
+  PH_TRY(plaidhip_camera_finish(g, m, nfit, q, t.data(), ok.data(), S.data(), S.data() + (size_t)m * ncol,
+                                estimate ? sh.camera.ss.data() : nullptr, dres.data(), dprior.data(), c.inter_gene_cor,
+                                c.allow_neg_cor, c.out, gdf.data()));
+  for (int32_t f = 0; f < nfit; ++f) {
+    for (int h = 0; h < 4; ++h) c.hyper[6 * (size_t)f + h] = hyp[4 * (size_t)f + h];
+    c.hyper[6 * (size_t)f + 4] = gdf[2 * (size_t)f];
+    c.hyper[6 * (size_t)f + 5] = gdf[2 * (size_t)f + 1];
+  }
+  return PLAIDHIP_OK;
+}
+
+}  // namespace plaidhip

@@ -202,7 +202,7 @@ def gsva_signed_ranks(X, rowtf):
 def gsva_raw_ref(X, Gp, Gi, tau, rowtf):
     """(T, E, wmax): replaid.gsva before normalize_medians, T = w (P / max) with P the exact set sums of the weights
     sign r^(1 + tau) (long double) and max the largest |weight| of the whole matrix, and the bound E = (k + c) u mag on
-    the device's raw score, mag = w sum |weight| / max.  The device (multi.cpp, scorer_worker) sums its own weights
+    the device's raw score, mag = w sum |weight| / max.  The device (shard_scorer.cpp, scorer_worker) sums its own weights
     (k - 1 roundings) and applies fl(1 / max) * (sum * w): 3 roundings; the reference rounds T once; one spare: c = 5 for
     tau = 0, where weights and max are half-integers, exact on both sides.  tau > 0: every device weight is within
     a = pow_allowance_u(1 + tau) u of r^(1 + tau) (3 u for 1.5 and 1.3 on whichever route a column takes, 4.5 u for

@@ -1,4 +1,4 @@
-"""plaid.camera on the device (kernels_camera.hip, multi.cpp: limma_worker with kCamera) -- `pytest -m gpu`.
+"""plaid.camera on the device (kernels_camera.hip, shard_limma.cpp: limma_worker with kCamera) -- `pytest -m gpu`.
 
 Integer-valued X in -8 .. 8.  What is checked, and against what:
   1. Z of plaidhip_dev_camera_residuals is equal bit for bit to plaidhip_camera_residual_row (the same inline functions, on

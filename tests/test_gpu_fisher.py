@@ -169,7 +169,7 @@ def test_fisher_multi_on_the_first_device(hip_ctx):
 
 def test_many_lists_and_sets_adjust_on_several_host_threads(hip_ctx):
     """3,000 sets x 40 lists: 360,000 p-values, enough for the Benjamini-Hochberg columns to be dealt to several host
-    threads (multi.cpp: kFisherBhWork).  padj against the restatement applied to the call's own p columns, the counts
+    threads (shard_lists.cpp: kFisherBhWork).  padj against the restatement applied to the call's own p columns, the counts
     against a sparse product, and two shards against one."""
     import scipy.sparse as sp
     N, m, c = 300, 3000, 40

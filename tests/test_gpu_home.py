@@ -1,4 +1,4 @@
-"""The score matrix's way home through the host entry points (plaid_amd/csrc/multi.cpp, HomeBuffer): results of more than
+"""The score matrix's way home through the host entry points (plaid_amd/csrc/shard.cpp, HomeBuffer): results of more than
 16 MB return in 64 MB chunks behind threads that make the caller's pages.  The bytes must not depend on it: fresh and
 reused destinations, destinations at odd byte offsets, sizes just around the chunk boundaries, every host entry.
 `pytest -m gpu`."""

@@ -480,7 +480,8 @@ def test_a_cpp_exception_becomes_an_error_code():
     # and the sources: no int entry point without the handler
     import re
     csrc = os.path.join(ROOT, "plaid_amd", "csrc")
-    for name in ("api.cpp", "multi.cpp", "geneset.cpp", "gmt.cpp"):
+    for name in ("api.cpp", "multi.cpp", "shard.cpp", "shard_rank_sum.cpp", "shard_scorer.cpp", "shard_exact.cpp",
+                 "shard_plaid_test.cpp", "shard_gsea.cpp", "shard_lists.cpp", "shard_limma.cpp", "geneset.cpp", "gmt.cpp"):
         text = open(os.path.join(csrc, name)).read()
         for m_ in re.finditer(r'^(?:extern "C" )?int (plaidhip_\w+)\([^;{]*\)\s*(try\s*)?\{', text, flags=re.M):
             body_one_line = text[m_.end():text.index("\n", m_.end())].strip().endswith("}")
