@@ -1432,6 +1432,105 @@ int plaidhip_camera_finish(int32_t g, int32_t m, int32_t nfit, int32_t q, const 
                            const double* cnt, const double* ss, const double* dfres, const double* dfprior,
                            double inter_gene_cor, int allow_neg_cor, double* out, double* gdf);
 
+/* plaid.fry(X, design, G, contrasts): limma's SELF-CONTAINED rotation gene-set test in closed form -- fry, the limit of
+ * roast for infinitely many rotations (Wu et al. 2010; Giner & Smyth) -- for every set, contrast and design.  camera asks
+ * whether a set moves more than the other genes; fry asks whether the set is differential at all.  It draws no random
+ * number: the result is a pure function of the input.  The form is limma's fry.default / .fryEffects AS RECALLED: the source
+ * is not in this tree, so the statistic is pinned here and tested against these words restated at 50 digits (DESIGN.md
+ * section 26).  Operands as plaidhip_camera.  For fit f: d = n_f - p >= 1, contrast j has plaid.limma's v_j and u_j.
+ * 1. The fit and the divisors: steps 1 to 3 of plaidhip_limma, unchanged.  s2_g = RSS_g / d; s2.post_g is eBayes' posterior
+ *    variance with the prior (df.prior, s2.prior) of plaidhip_limma_finish, bit for bit (one function makes both).  The
+ *    divisor c_g is sqrt(s2.post_g) for standardize = 0 ("posterior.sd", the default), sqrt(s2_g) for 1 ("residual.sd") and
+ *    1.0 for 2 ("none"); "p2" is not offered.  A gene that is not ok in the fit (s2 not finite: a NaN or Inf in a used
+ *    sample), or whose divisor is 0 or not finite, leaves the fit's universe -- a stated deviation: limma would divide by
+ *    it.  Sets count their members inside the universe only: m.
+ * 2. The standardised effects of gene g are the row F_g = [ e_gj | rho_g ] of length d + 1:
+ *      e_gj  = logFC_gj / (u_j c_g)                       with the posterior sd exactly plaid.limma's moderated t
+ *      z_gc  = r_gc / c_g for a used sample, else 0.0     r_gc: camera's chain, fma(-Q_f[c, k], E_k, .) ascending k from x_c
+ *      rho_g = Q2' z_g                                    Q2: the n_f - p other columns of the full Householder Q of step 1
+ *    (the reflectors applied, last first, to the identity's columns p .. n_f - 1, scattered to the used samples).  z comes
+ *    from kernels_fry.hip's residual pass: camera's with c_g read instead of derived; the chain step and the select are
+ *    inline functions of csrc/camera.h and csrc/fry.h, one copy for the device and for plaidhip_fry_residual_row.  rho is
+ *    d more weight columns of plaid.limma's effects pass run over Z: rho_gk = sum over c of fma(z_gc, Q2[c, k], .) over the
+ *    columns of a block of 128 ascending from 0.0, the blocks added ascending.  |sum_g rho_g| = |sum_g z_g| (Q2 is an
+ *    isometry on the residual space).
+ * 3. Directional, for every n:  T = G'Z by the dense crossprod, the sums of T^2 as in step 3 of plaidhip_camera, and
+ *      t = (sum_g e_gj / m) / sqrt(|sum_g z_g|^2 / ((m m) d)),    PValue = 2 pt(-|t|, d)  -- the df is d, not d + df.prior.
+ *    Direction is Down (-1) if t < 0, else Up (+1); NaN where t is NaN.  m = 0: NaN.  IEEE decides 0 / 0 and x / 0.
+ * 4. Mixed, for fits with d + 1 <= PLAIDHIP_FRY_MIXED_MAX.  M_j = F_S' F_S ((d + 1) x (d + 1)) over the set's members,
+ *    D = min(m, d + 1), lambda_1 >= ... >= lambda_D its D largest eigenvalues (limma's svd(EffectsSet)$d^2):
+ *      SA = tr M_j,  SA2 = |M_j|_F^2,   den = lambda_1 - lambda_D
+ *      Fobs = (sum_g e_gj^2 - lambda_D) / den
+ *      bm = 1 / D,   bv = (D - 1) / (D D) / (D / 2 + 1)
+ *      Fm = (SA bm - lambda_D) / den
+ *      Fv = (bv SA2 - bv / (D - 1) (SA SA - SA2)) / (den den)
+ *      ab = Fm (1 - Fm) / Fv - 1,   alpha = ab Fm,   beta = ab - alpha
+ *      PValue.Mixed = pbeta(Fobs, alpha, beta, lower.tail = FALSE)
+ *    m = 1: PValue.Mixed = PValue.  alpha or beta not finite or not positive (lambda_1 = lambda_D among them): NaN.
+ *    On the device, on the first context: fry_gram_kernel (a workgroup per set) makes C = sum_g rho_g rho_g', and per
+ *    contrast b_j = sum_g e_gj rho_g and a_j = sum_g e_gj^2 -- every entry one accumulator from 0.0 over the members in the
+ *    order of Gi, the product rounded, then added -- and
+ *      tr M_j = a_j + sum_i C_ii,    |M_j|_F^2 = (a_j a_j + 2 sum_i b_ji^2) + sum_i (sum_k C_ik^2),
+ *    every sum ascending from 0.0 with rounded squares.  fry_eigen_kernel (a workgroup per (set, contrast)) holds
+ *    M_j = [a_j, b_j'; b_j, C] in LDS and runs cyclic two-sided Jacobi in the round-robin tournament order, until the
+ *    off-diagonal mass is at most 2^-53 |M_j|_F or 30 sweeps; lambda_D is picked BY INDEX from the sorted diagonal (for
+ *    m < d + 1 the eigenvalues past m are rounding noise about 0 and are never picked).  The eigenvalues are pinned as a
+ *    property -- within max(4 x LAPACK's own deviation, D 2^-53) lambda_1 of the exact spectrum of M_j -- not as bits.
+ *    A fit above the cap has NaN in PValue.Mixed and FDR.Mixed and 0 in its hyper flag; its other columns are complete.
+ * 5. FDR, FDR.Mixed: Benjamini-Hochberg over the sets of each (fit, contrast), NaN rows apart (plaidhip_fry_finish).
+ * out: m x 7 x q x nfit doubles, column-major: NGenes, Direction, t, PValue, FDR, PValue.Mixed, FDR.Mixed; contrast j of
+ * fit f at out + (f * q + j) * 7 * m.  hyper: nfit x 7 doubles, row-major per fit: plaid.limma's four (df.residual,
+ * df.prior, s2.prior, n_ok), the universe's size, d + 1, and 1.0 / 0.0: the mixed test was offered.
+ * g == 0, nfit == 0, q == 0 or m == 0: PLAIDHIP_OK with nothing written.
+ * Argument errors, all PLAIDHIP_EINVAL and all found on the host before any device is touched: m < 0; those of
+ * plaidhip_limma in their order (named "fry:"); the membership's as plaidhip_camera makes them; then standardize outside
+ * 0..2; then q > PLAIDHIP_FRY_MAX_CONTRASTS.
+ * plaidhip_fry_multi shards the SAMPLES at multiples of 128 columns: after plaid.limma's two rounds shard 0 makes the
+ * divisors from the RSS of ALL samples, a third round chains the sums of T^2 and, fit by fit under the cap, a round
+ * chains rho as [d + 1][g] (the last column, a mean, is not used).  Every partial sum is that of the one-device call, and
+ * the Gram and eigen stages run once, after the chains: every sharding has the one-device bits.
+ *   plaidhip_dev_fry_residuals: step 2's z on device pointers; plaidhip_dev_camera_residuals with cg ([nfit][rows]) in place
+ *     of rss and d.
+ *   plaidhip_dev_fry_residual_effects: rho [d + 1][rows] = seed (NULL: 0.0) + the block sums of Z Q2 (row d, the effects
+ *     pass's mean column with weight 0.0, is not used); Z: rows x n, leading dimension ldz; Q2: n x d column-major; use: n
+ *     or NULL; d <= PLAIDHIP_FRY_MIXED_MAX - 1.  Synchronises the stream before it returns.
+ *   plaidhip_dev_fry_gram: rho: rows x d ROW-major, e: rows x q row-major (both 0.0 outside the universe), Gp / Gi device
+ *     pointers; C: m x d x d, b: m x q x d, a, tr, fro: m x q.
+ *   plaidhip_dev_fry_eigen: nprob matrices M (dim x dim each, symmetric), Dk (nprob int32, from 1): lam1, lamD, sweeps,
+ *     converged per problem.
+ *   plaidhip_fry_q2, _fry_divisors, _fry_residual_row, _fry_finish (host only): Q2 of one design (n x (n_f - p)); step 1's
+ *     c_g [nfit][rows] (NaN: outside the universe) from rss [nfit][rows]; step 2's z for one gene; steps 3 to 5 from
+ *     dres (nfit), cnt (m x nfit), sume (m x q x nfit), ss (m x nfit) and, mixed (nfit int8, may be NULL) saying where,
+ *     sume2, lam1, lamD, trM, froM (m x q x nfit each).
+ * Not offered: roast and mroast (random rotations); gene weights; array or observation weights; trend.var; robust; a
+ * dgCMatrix X; na = "fit" rows; standardize = "p2". */
+#define PLAIDHIP_FRY_MIXED_MAX 128            /* d + 1 effects: M in LDS with an odd row stride is 129 KiB of the CU's 160 */
+#define PLAIDHIP_FRY_MAX_CONTRASTS 32
+int plaidhip_fry(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                 const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                 int standardize, double* out, double* hyper);
+int plaidhip_fry_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const double* design, int32_t p,
+                       int32_t nfit, const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi,
+                       int32_t m, int standardize, double* out, double* hyper);
+int plaidhip_dev_fry_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                               const int8_t* use, int32_t p, int32_t nfit, int32_t fit, const double* E, const double* cg,
+                               double* Z, int64_t ldz);
+int plaidhip_dev_fry_residual_effects(plaidhip_ctx* ctx, const double* Z, int64_t ldz, int32_t rows, int32_t n,
+                                      const double* Q2, const int8_t* use, int32_t d, const double* seed, double* rho);
+int plaidhip_dev_fry_gram(plaidhip_ctx* ctx, const double* rho, const double* e, int32_t rows, int32_t d, int32_t q,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double* C, double* b, double* a, double* tr,
+                          double* fro);
+int plaidhip_dev_fry_eigen(plaidhip_ctx* ctx, const double* M, int32_t dim, int64_t nprob, const int32_t* Dk, double* lam1,
+                           double* lamD, int32_t* sweeps, int32_t* converged);
+int plaidhip_fry_q2(const double* D, int32_t n, int32_t p, const int8_t* use, int32_t fit, double* Q2, int64_t* nf);
+int plaidhip_fry_divisors(int32_t rows, int32_t p, int32_t nfit, const double* rss, const int64_t* nf, int standardize,
+                          double* cg);
+int plaidhip_fry_residual_row(int32_t n, int32_t p, const double* x, const double* Q, const int8_t* use, const double* E,
+                              double c, double* z);
+int plaidhip_fry_finish(int32_t m, int32_t nfit, int32_t q, const double* dres, const double* cnt, const double* sume,
+                        const double* ss, const double* sume2, const double* lam1, const double* lamD, const double* trM,
+                        const double* froM, const int8_t* mixed, double* out);
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

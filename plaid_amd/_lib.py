@@ -182,6 +182,16 @@ SIGNATURES = {
     "plaidhip_dev_camera_sumsq": [_vp, _vp, _i64, _i32, _i32, _vp, _vp],
     "plaidhip_camera_residual_row": [_i32, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _vp],
     "plaidhip_camera_finish": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _int, _vp, _vp],
+    "plaidhip_fry": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _int, _vp, _vp],
+    "plaidhip_fry_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _int, _vp, _vp],
+    "plaidhip_dev_fry_residuals": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64],
+    "plaidhip_dev_fry_residual_effects": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "plaidhip_dev_fry_gram": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_dev_fry_eigen": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_fry_q2": [_vp, _i32, _i32, _vp, _i32, _vp, _vp],
+    "plaidhip_fry_divisors": [_i32, _i32, _i32, _vp, _vp, _int, _vp],
+    "plaidhip_fry_residual_row": [_i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp],
+    "plaidhip_fry_finish": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],
     # host-only GMT text path (gmt.cpp)
     "plaidhip_gmt_read": [C.c_char_p, _int, _i64, C.POINTER(_vp)],

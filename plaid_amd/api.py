@@ -1095,6 +1095,92 @@ def plaid_camera_contrasts(X, Y, G, B=None, inter_gene_cor=0.01, allow_neg_cor=F
     return tables, {nm: dict(zip(CAMERA_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
 
 
+_FRY_NAMES = ["NGenes", "Direction", "t", "PValue", "FDR", "PValue.Mixed", "FDR.Mixed"]
+_FRY_SORT = {"none": None, "directional": 3, "mixed": 5}
+
+
+def _fry_table(tab, rn, sort_by):
+    """sets x 7 of the library -> the NamedMatrix plaid.fry returns (Direction +1 Up, -1 Down), ordered by `sort_by`:
+    "directional" (PValue increasing), "mixed" (PValue.Mixed increasing) or "none"; stable, NaN last"""
+    if sort_by not in _FRY_SORT:
+        raise ValueError(f"plaid.fry: sort_by must be one of {sorted(_FRY_SORT)}")
+    rn = list(rn)
+    col = _FRY_SORT[sort_by]
+    if col is not None:
+        o = np.argsort(tab[:, col], kind="stable")
+        tab, rn = tab[o, :], [rn[k] for k in o]
+    return NamedMatrix(np.ascontiguousarray(tab), rn, _FRY_NAMES)
+
+
+def plaid_fry(X, design, G, contrasts=None, use=None, standardize="posterior.sd", minSize=1, maxSize=None,
+              sort_by="directional", ctx: Context | None = None):
+    """plaid.fry(): limma's self-contained rotation gene-set test in closed form (fry: roast with infinitely many rotations,
+    as pinned in include/plaidhip.h) of every set of G on the expression X for one design; the operands are plaid_camera's.
+    camera asks whether a set moves more than the other genes, fry whether the set is differential at all; it draws no
+    random number.  standardize: "posterior.sd" (the default: the effects are plaid_limma's moderated t), "residual.sd" or
+    "none".  A gene with a NaN or Inf in a used sample, or with a divisor that is 0, leaves the universe.  The directional
+    test is complete for any number of samples; the mixed test (a set whose genes move in both directions) is offered for
+    fits with df.residual + 1 <= 128 effects, and NaN above that (hyper["mixed"] = 0).  Returns (tables, hyper): contrast
+    name -> NamedMatrix (sets x [NGenes, Direction (+1 Up, -1 Down), t, PValue, FDR, PValue.Mixed, FDR.Mixed]) ordered by
+    `sort_by` ("directional", "mixed" or "none"; stable, NaN last), and plaid_limma's four values, n.genes, n.effects
+    (df.residual + 1) and mixed.
+    Not offered: roast / mroast, gene or array weights, trend.var, robust, a sparse X, na = "fit", standardize = "p2"."""
+    from .engine import FRY_HYPER, check_fry_standardize
+    check_fry_standardize(standardize)
+    _fry_table(np.zeros((0, 7)), [], sort_by)   # (an unknown sort_by: before the device)
+    Xs, Gp, Gi, rn = _camera_sets("plaid.fry", X, G, minSize, maxSize)
+    Dn = design if isinstance(design, NamedMatrix) else None
+    Dv = np.asarray(Dn.values if Dn is not None else design, dtype=np.float64)
+    if Dv.ndim != 2:
+        raise ValueError("plaid.fry: design must be samples x coefficients")
+    coef = list(Dn.colnames) if Dn is not None else [f"coef{k + 1}" for k in range(Dv.shape[1])]
+    if contrasts is None:
+        Kv, names = None, coef
+    else:
+        Kn = contrasts if isinstance(contrasts, NamedMatrix) else None
+        Kv = np.asarray(Kn.values if Kn is not None else contrasts, dtype=np.float64)
+        Kv = Kv[:, None] if Kv.ndim == 1 else Kv
+        names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
+    ctx = ctx or default_context()
+    out, hyper = ctx.fry(Xs, Dv, Gp, Gi, use, Kv, standardize)
+    tables = {nm: _fry_table(out[:, :, j, 0], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, dict(zip(FRY_HYPER, (float(x) for x in hyper[0])))
+
+
+def plaid_fry_contrasts(X, Y, G, B=None, standardize="posterior.sd", minSize=1, maxSize=None, sort_by="directional",
+                        ctx: Context | None = None):
+    """plaid.fry.contrasts(): plaid_fry for every column of the contrast matrix Y in one call, with the designs of
+    plaid_limma_contrasts: contrast j fits [1, Y[, j], B] on the samples with a label and tests the sets on the coefficient
+    of Y[, j].  X is uploaded once.  Returns (tables, hyper) keyed by contrast name; contrast j has the bits of plaid_fry on
+    that contrast's design and samples."""
+    from .engine import FRY_HYPER, check_fry_standardize, contrast_labels
+    check_fry_standardize(standardize)
+    _fry_table(np.zeros((0, 7)), [], sort_by)
+    Xs, Gp, Gi, rn = _camera_sets("plaid.fry", X, G, minSize, maxSize)
+    n = Xs.shape[1]
+    Yn = Y if isinstance(Y, NamedMatrix) else None
+    lab = contrast_labels(Yn.values if Yn is not None else Y, n)
+    if not np.all(np.isin(lab, (0, 1, -1))):
+        raise ValueError("elements of Y must be 0, 1 or NA")
+    ncon = lab.shape[1]
+    names = list(Yn.colnames) if Yn is not None and Yn.colnames is not None else [str(j + 1) for j in range(ncon)]
+    Bv = np.zeros((n, 0)) if B is None else np.asarray(B.values if isinstance(B, NamedMatrix) else B, dtype=np.float64)
+    Bv = Bv[:, None] if Bv.ndim == 1 else Bv
+    if Bv.ndim != 2 or Bv.shape[0] != n:
+        raise ValueError("B must have one row per column of X")
+    p = 2 + Bv.shape[1]
+    D = np.empty((n, p, ncon), order="F")
+    D[:, 0, :] = 1.0
+    D[:, 1, :] = np.where(lab == 1, 1.0, 0.0)
+    D[:, 2:, :] = Bv[:, :, None]
+    K = np.zeros((p, 1))
+    K[1, 0] = 1.0
+    ctx = ctx or default_context()
+    out, hyper = ctx.fry(Xs, D, Gp, Gi, lab != -1, K, standardize)
+    tables = {nm: _fry_table(out[:, :, 0, j], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, {nm: dict(zip(FRY_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
+
+
 def plaid_intergenecor(X, design, G, use=None, minSize=1, maxSize=None, ctx: Context | None = None):
     """plaid.intergenecor(): limma's interGeneCorrelation(X[set, ], design) for every set of G at once -- the variance
     inflation factor of the set's mean, estimated from the residuals of its genes, and the mean pairwise correlation

@@ -1355,6 +1355,86 @@ int plaidhip_dev_camera_sumsq(plaidhip_ctx* ctx, const double* T, int64_t ldt, i
   return launch_reduce_blocks_flat(ctx, ws, m, n, seed, out);
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.fry: the one-device form of the sharded engine (shard_limma.cpp: limma_worker with kFry, fry_tail)
+int plaidhip_fry(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                 const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                 int standardize, double* out, double* hyper) try {
+  return dispatch(on_context(ctx), fry_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, standardize, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the device passes of plaid.fry on device pointers (kernels_fry.hip; the residual effects are kernels_lmfit.hip's effects
+// pass with Q2 for Q).  The workspace holds the masks of the residual pass; the block partials, masks and tile weights of
+// the effects pass.
+int plaidhip_dev_fry_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* Q,
+                               const int8_t* use, int32_t p, int32_t nfit, int32_t fit, const double* E, const double* cg,
+                               double* Z, int64_t ldz) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ld >= rows && ldz >= rows && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS,
+             "fry_residuals: bad shape rows=%d n=%d ld=%lld ldz=%lld nfit=%d (nfit <= %d)", rows, n, (long long)ld,
+             (long long)ldz, nfit, PLAIDHIP_LIMMA_MAX_FITS);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "fry_residuals: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(n <= PLAIDHIP_LIMMA_MAX_SAMPLES, "fry_residuals: %d samples (at most %d)", n, PLAIDHIP_LIMMA_MAX_SAMPLES);
+  PH_REQUIRE(fit >= 0 && fit < nfit, "fry_residuals: fit %d of %d", fit, nfit);
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(A && Q && E && cg && Z, "fry_residuals: null argument");
+  const int64_t W = (int64_t)nfit * (p + 1);
+  PH_TRY(ensure_workspace(ctx, (size_t)lmfit_mask_bytes(n, W)));
+  PH_TRY(launch_lmfit_masks(ctx, Q, use, nullptr, n, p, nfit, ctx->ws, nullptr));
+  return launch_fry_residuals(ctx, A, ld, rows, n, Q, ctx->ws, p, fit, E, cg, Z, ldz);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_fry_residual_effects(plaidhip_ctx* ctx, const double* Z, int64_t ldz, int32_t rows, int32_t n,
+                                      const double* Q2, const int8_t* use, int32_t d, const double* seed, double* rho) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ldz >= rows && n <= PLAIDHIP_LIMMA_MAX_SAMPLES,
+             "fry_residual_effects: bad shape rows=%d n=%d ldz=%lld (n <= %d)", rows, n, (long long)ldz,
+             PLAIDHIP_LIMMA_MAX_SAMPLES);
+  PH_REQUIRE(d >= 1 && d + 1 <= PLAIDHIP_FRY_MIXED_MAX, "fry_residual_effects: d = %d residual effects (1 <= d <= %d)", d,
+             PLAIDHIP_FRY_MIXED_MAX - 1);
+  if (rows == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(rho && (n == 0 || (Z && Q2)), "fry_residual_effects: null argument");
+  const int64_t W = d + 1;   // (the effects pass's mean column: weight 0.0 here)
+  const size_t part = ((size_t)row_design_ws_doubles(rows, n, W) * 8 + 15) / 16 * 16;
+  const size_t mb = (size_t)lmfit_mask_bytes(n, W);
+  PH_TRY(ensure_workspace(ctx, part + mb + (size_t)lmfit_weight_bytes(n, W)));
+  DevBuf dzero;
+  PH_TRY(dzero.alloc(8));
+  PH_HIP(hipMemsetAsync(dzero.p, 0, 8, ctx->stream));
+  double* ws = static_cast<double*>(ctx->ws);
+  void* masks = static_cast<char*>(ctx->ws) + part;
+  double* wt = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + part + mb);
+  PH_TRY(launch_lmfit_masks(ctx, Q2, use, dzero.as<double>(), n, d, 1, masks, wt));
+  PH_TRY(launch_row_design_effects(ctx, Z, ldz, rows, n, masks, wt, (int32_t)W, ws));
+  PH_TRY(launch_reduce_blocks_flat(ctx, ws, W * rows, n, seed, rho));
+  PH_HIP(hipStreamSynchronize(ctx->stream));   // (dzero is released on return)
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_fry_gram(plaidhip_ctx* ctx, const double* rho, const double* e, int32_t rows, int32_t d, int32_t q,
+                          const int32_t* Gp, const int32_t* Gi, int32_t m, double* C, double* b, double* a, double* tr,
+                          double* fro) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && m >= 0, "fry_gram: bad dims rows=%d m=%d", rows, m);
+  PH_REQUIRE(d >= 1 && d + 1 <= PLAIDHIP_FRY_MIXED_MAX, "fry_gram: d = %d residual effects (1 <= d <= %d)", d,
+             PLAIDHIP_FRY_MIXED_MAX - 1);
+  PH_REQUIRE(q >= 1 && q <= PLAIDHIP_FRY_MAX_CONTRASTS, "fry_gram: q = %d contrasts (1 <= q <= %d)", q,
+             PLAIDHIP_FRY_MAX_CONTRASTS);
+  if (m == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(rho && e && Gp && Gi && C && b && a && tr && fro, "fry_gram: null argument");
+  return launch_fry_gram(ctx, rho, e, d, q, Gp, Gi, 0, m, C, b, a, tr, fro);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_fry_eigen(plaidhip_ctx* ctx, const double* M, int32_t dim, int64_t nprob, const int32_t* Dk, double* lam1,
+                           double* lamD, int32_t* sweeps, int32_t* converged) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(dim >= 1 && dim <= PLAIDHIP_FRY_MIXED_MAX, "fry_eigen: dim = %d (1 <= dim <= %d)", dim, PLAIDHIP_FRY_MIXED_MAX);
+  PH_REQUIRE(nprob >= 0 && nprob <= 0x7fffffff, "fry_eigen: %lld problems", (long long)nprob);
+  if (nprob == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(M && Dk && lam1 && lamD && sweeps && converged, "fry_eigen: null argument");
+  return launch_fry_eigen(ctx, M, nullptr, nullptr, nullptr, dim, 1, nprob, Dk, lam1, lamD, sweeps, converged);
+} catch (...) { return plaidhip::on_exception(); }
+
 // the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them
 int plaidhip_gsea_permutations(plaidhip_ctx* ctx, int32_t g, int32_t nperm, uint64_t seed, int32_t* P_out) try {
   PH_REQUIRE(g >= 1 && nperm >= 1, "gsea_permutations: bad dims g=%d nperm=%d", g, nperm);

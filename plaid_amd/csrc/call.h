@@ -12,7 +12,7 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21
+  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21, kFry = 22
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker's three
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -124,6 +124,11 @@ struct Call : Operands {
   // correlation (NaN: estimated from the residuals), allow.neg.cor; out m x 8 x q x nfit, hyper nfit x 6
   double inter_gene_cor = 0.0;
   int allow_neg_cor = 0;
+  // plaid.fry (kFry): plaid.camera's operands; standardize (PLAIDHIP_FRY_STANDARDIZE_*, fry.h); out m x 7 x q x nfit, hyper
+  // nfit x 7; what check_call adds to plaid.limma's: Q2 of every fit under the cap (n x (n_f - p) at lm_Q2_off[f], -1: above)
+  int standardize = 0;
+  std::vector<double> lm_Q2;
+  std::vector<int64_t> lm_Q2_off;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -408,6 +413,19 @@ inline Call camera_call(const double* X, int32_t g, int32_t n, const double* des
   k.m = m;
   k.inter_gene_cor = inter_gene_cor;
   k.allow_neg_cor = allow_neg_cor ? 1 : 0;
+  return k;
+}
+
+// limma's self-contained set test in closed form as pinned in include/plaidhip.h: plaidhip_fry
+inline Call fry_call(const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                     const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m, int standardize, double* out,
+                     double* hyper) {
+  Call k = limma_call(X, g, n, design, p, nfit, use, K, q, out, hyper);
+  k.method = kFry;
+  k.Gp = Gp;
+  k.Gi = Gi;
+  k.m = m;
+  k.standardize = standardize;
   return k;
 }
 

@@ -394,6 +394,16 @@ int launch_camera_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int3
                             int64_t ldz);
 int64_t camera_sumsq_ws_doubles(int32_t n, int64_t len);
 int launch_camera_sumsq(plaidhip_ctx* ctx, const double* T, int64_t ldt, int32_t m, int32_t n, double* part, int64_t stride);
+// kernels_fry.hip (plaid.fry): camera's residual pass with the divisors d_cg [nfit][rows] read, not derived; the Gram matrix
+// of the residual effects of sets s0 .. s0 + ns - 1 with its borders; the two eigenvalues of every M
+int launch_fry_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
+                         const void* d_masks, int32_t p, int32_t f, const double* d_E, const double* d_cg, double* Z,
+                         int64_t ldz);
+int launch_fry_gram(plaidhip_ctx* ctx, const double* d_rho, const double* d_e, int32_t d, int32_t q, const int32_t* d_Gp,
+                    const int32_t* d_Gi, int32_t s0, int32_t ns, double* d_C, double* d_b, double* d_a, double* d_tr, double* d_fro);
+int launch_fry_eigen(plaidhip_ctx* ctx, const double* d_M, const double* d_C, const double* d_b, const double* d_a, int32_t dim,
+                     int32_t q, int64_t nprob, const int32_t* d_Dk, double* d_lam1, double* d_lamD, int32_t* d_sweeps,
+                     int32_t* d_conv);
 // stats.cpp: eBayes and the tables of plaid.limma.  drow ([nfit][rows], NaN: the row is not fitted) and urow ([nfit q][rows])
 // null: every row of fit f has nf[f] - p and u[f q + j] (plaidhip_limma_finish); hyper has hcols (4 or 5) values per fit
 int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
@@ -401,7 +411,15 @@ int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, i
                       double* hyper, int hcols);
 // stats.cpp: one design of plaid.limma (include/plaidhip.h: plaidhip_limma_design); what: the entry its messages name
 int limma_design(const char* what, const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q,
-                 int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf);
+                 int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf, double* Q2 = nullptr);
+// stats.cpp: squeezeVar of one fit, shared by plaid.limma's tables and plaid.fry's divisors
+struct LimmaPrior { double d0, s0, pool; int64_t nok; };
+LimmaPrior limma_squeeze_fit(size_t R, double dfit, const double* dr, const double* rssf, double* s, double* po);
+// stats.cpp (plaid.fry): the divisors c_g [nfit][rows] (NaN: the gene is outside the fit's universe); standardize as in
+// include/plaidhip.h
+void fry_divisors(int32_t rows, int32_t p, int32_t nfit, const double* rss, const int64_t* nf, int standardize, double* cg);
+double t_two_sided_p(double t, double df);
+double beta_upper(double x, double a, double b);
 // kernels_csr.hip: the row view of a CSC matrix (replaid.gsva / plaid.test on a dgCMatrix).  All pointers are device
 // pointers.  Transpose: Rp g + 1, Rx / Rj / perm Xp[n] entries each (Rj, perm optional), within a row ascending column
 // order; *d_maxlen = the longest row.  Uses the context workspace.

@@ -371,8 +371,8 @@ int check_plage_call(const Call& c) {
 // plaid.limma; the order is part of the contract (include/plaidhip.h).  Makes every fit's Q, v, u and n_f: the designs are
 // decomposed here, on the host, so that a design that cannot be fitted is refused before any device is touched
 int check_limma_call(Call& c) {
-  const char* who = c.method == kCamera ? "camera" : "limma";
-  const bool sets = c.method != kCamera || c.m != 0;   // (plaid.camera without sets writes nothing)
+  const char* who = c.method == kCamera ? "camera" : c.method == kFry ? "fry" : "limma";
+  const bool sets = (c.method != kCamera && c.method != kFry) || c.m != 0;   // (plaid.camera without sets writes nothing)
   const int32_t rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, q = c.nq;
   PH_REQUIRE(rows >= 0 && n >= 0 && n <= PLAIDHIP_LIMMA_MAX_SAMPLES && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS && q >= 0,
              "%s: bad dims rows=%d n=%d nfit=%d q=%d (n <= %d, nfit <= %d)", who, rows, n, nfit, q, PLAIDHIP_LIMMA_MAX_SAMPLES,
@@ -396,10 +396,26 @@ int check_limma_call(Call& c) {
   c.lm_u.assign((size_t)q * nfit, 0.0);
   c.lm_nf.assign((size_t)nfit, 0);
   c.lm_invn.assign((size_t)nfit, 0.0);
+  // plaid.fry: the same decomposition also gives Q2 (n x d at lm_Q2_off[f]) of every fit with 1 <= d and d + 1 effects
+  // under the cap; d is known from the count of used samples
+  c.lm_Q2_off.assign((size_t)nfit, -1);
+  if (c.method == kFry && rows != 0 && q != 0 && c.m > 0) {
+    size_t total = 0;
+    for (int32_t f = 0; f < nfit; ++f) {
+      int64_t nf = n;
+      if (c.use != nullptr) nf = std::count_if(c.use + (size_t)f * n, c.use + (size_t)(f + 1) * n, [](int8_t u) { return u != 0; });
+      const int64_t d = nf - p;
+      if (d < 1 || d + 1 > PLAIDHIP_FRY_MIXED_MAX) continue;
+      c.lm_Q2_off[(size_t)f] = (int64_t)total;
+      total += (size_t)n * (size_t)d;
+    }
+    c.lm_Q2.assign(total, 0.0);
+  }
   for (int32_t f = 0; f < nfit; ++f) {
     PH_TRY(limma_design(who, c.design + (size_t)f * n * p, n, p, c.use != nullptr ? c.use + (size_t)f * n : nullptr, c.K, q,
                         f + 1, c.lm_Q.data() + (size_t)f * n * p, nullptr, c.lm_v.data() + (size_t)f * p * q,
-                        c.lm_u.data() + (size_t)f * q, &c.lm_nf[(size_t)f]));
+                        c.lm_u.data() + (size_t)f * q, &c.lm_nf[(size_t)f],
+                        c.lm_Q2_off[(size_t)f] >= 0 ? c.lm_Q2.data() + c.lm_Q2_off[(size_t)f] : nullptr));
     c.lm_invn[(size_t)f] = 1.0 / (double)c.lm_nf[(size_t)f];
   }
   return PLAIDHIP_OK;
@@ -408,21 +424,34 @@ int check_limma_call(Call& c) {
 // plaid.camera; the order is part of the contract (include/plaidhip.h): plaid.limma's checks in their order (the designs are
 // decomposed there), then the membership's as plaid.rankcor makes them, then the fixed correlation
 int check_camera_call(Call& c) {
-  PH_REQUIRE(c.m >= 0, "camera: bad dims m=%d", c.m);
+  const char* who = c.method == kFry ? "fry" : "camera";
+  PH_REQUIRE(c.m >= 0, "%s: bad dims m=%d", who, c.m);
   PH_TRY(check_limma_call(c));
-  PH_REQUIRE(c.Gp != nullptr, "camera: null Gp");
-  PH_REQUIRE(c.Gp[0] == 0, "camera: Gp[0] = %d (a column pointer starts at 0)", c.Gp[0]);
+  PH_REQUIRE(c.Gp != nullptr, "%s: null Gp", who);
+  PH_REQUIRE(c.Gp[0] == 0, "%s: Gp[0] = %d (a column pointer starts at 0)", who, c.Gp[0]);
   for (int32_t j = 0; j < c.m; ++j) {
-    PH_REQUIRE(c.Gp[j + 1] >= c.Gp[j], "camera: Gp[%d] = %d after %d (a column pointer does not decrease)", j + 1, c.Gp[j + 1],
-               c.Gp[j]);
-    PH_REQUIRE(c.Gp[j + 1] - c.Gp[j] <= c.g, "camera: set %d has %d members (at most the %d genes)", j + 1,
+    PH_REQUIRE(c.Gp[j + 1] >= c.Gp[j], "%s: Gp[%d] = %d after %d (a column pointer does not decrease)", who, j + 1,
+               c.Gp[j + 1], c.Gp[j]);
+    PH_REQUIRE(c.Gp[j + 1] - c.Gp[j] <= c.g, "%s: set %d has %d members (at most the %d genes)", who, j + 1,
                c.Gp[j + 1] - c.Gp[j], c.g);
   }
-  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "camera: null Gi");
+  PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "%s: null Gi", who);
   for (int32_t e = 0; e < c.Gp[c.m]; ++e)
-    PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "camera: Gi[%d] = %d (rows are 0..%d)", e, c.Gi[e], c.g - 1);
+    PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "%s: Gi[%d] = %d (rows are 0..%d)", who, e, c.Gi[e], c.g - 1);
+  if (c.method == kFry) return PLAIDHIP_OK;
   PH_REQUIRE(std::isnan(c.inter_gene_cor) || (c.inter_gene_cor > -1.0 && c.inter_gene_cor < 1.0),
              "camera: inter_gene_cor = %g (a correlation inside (-1, 1), or NaN to estimate it)", c.inter_gene_cor);
+  return PLAIDHIP_OK;
+}
+
+// plaid.fry; the order is part of the contract (include/plaidhip.h): plaid.camera's checks of the fit and of the membership,
+// then standardize and the number of contrasts.  Q2 of every fit under the cap comes out of plaid.limma's one decomposition
+// (check_limma_call)
+int check_fry_call(Call& c) {
+  PH_TRY(check_camera_call(c));
+  PH_REQUIRE(c.standardize >= 0 && c.standardize <= 2, "fry: standardize = %d (0 posterior.sd, 1 residual.sd, 2 none)",
+             c.standardize);
+  PH_REQUIRE(c.nq <= PLAIDHIP_FRY_MAX_CONTRASTS, "fry: q = %d contrasts (at most %d)", c.nq, PLAIDHIP_FRY_MAX_CONTRASTS);
   return PLAIDHIP_OK;
 }
 
@@ -490,6 +519,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kZscore: return check_plage_call(c);
     case kLimma: return check_limma_call(c);
     case kCamera: return check_camera_call(c);
+    case kFry: return check_fry_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -818,6 +848,20 @@ int plaidhip_debug_camera_sharded_on_one_device(int device, int nshards, int fai
                                                 double inter_gene_cor, int allow_neg_cor, double* out, double* hyper) try {
   return dispatch(on_hook(device, nshards, fail_shard),
                   camera_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, inter_gene_cor, allow_neg_cor, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_fry_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const double* design, int32_t p,
+                       int32_t nfit, const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi,
+                       int32_t m, int standardize, double* out, double* hyper) try {
+  return dispatch(on_devices(devices, ndev), fry_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, standardize, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_fry_sharded_on_one_device(int device, int nshards, int fail_shard, const double* X, int32_t g, int32_t n,
+                                             const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K,
+                                             int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m, int standardize,
+                                             double* out, double* hyper) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  fry_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, standardize, out, hyper));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fail_shard, const int8_t* sig, int32_t g, int32_t c,

@@ -390,6 +390,7 @@ Route route(const Call& c) {
     case kPlage: case kZscore: return {false, no_scores, nullptr, plage_worker, nullptr};
     case kLimma: return {true, limma_empty, limma_prepare, limma_worker, limma_tail};
     case kCamera: return {true, limma_empty, limma_prepare, limma_worker, camera_tail};
+    case kFry: return {true, limma_empty, limma_prepare, limma_worker, fry_tail};
   }
   return {false, no_scores, nullptr, nullptr, nullptr};   // (no method at all: check_call has refused it)
 }

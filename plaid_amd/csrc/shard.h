@@ -101,6 +101,12 @@ struct Shared {
   } limma;
   // plaid.camera: the chained sums over the samples of T^2, [nfit][m] (T = G'Z of every fit)
   struct Camera { std::vector<double> ss; } camera;
+  // plaid.fry: the divisors [nfit][rows] (shard 0 makes them after the RSS chain); the chained residual effects of every
+  // fit under the cap, [d + 1][rows] each (camera.ss takes the sums of T^2)
+  struct Fry {
+    std::vector<double> cg;
+    std::vector<std::vector<double>> rho;
+  } fry;
   // plaid.gsea: the block partials [nblk][c][6][m] of all permutation blocks, each shard writing its own blocks; multilevel:
   // (qhat, log2err, stage, status) of every (list, set), NaN without a ruler, each shard writing the sets of its own rulers
   struct Gsea { std::vector<double> part, ml; } gsea;
@@ -225,6 +231,7 @@ bool limma_empty(const Call& c);
 void limma_prepare(Shared& sh, const Call& c, int ndev);
 int limma_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 int camera_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
+int fry_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 
 // ---- what the engine knows about a method on the run side (shard.cpp) --------------------------------------------------------
 struct Route {

@@ -85,6 +85,82 @@ int limma_na_refit(plaidhip_ctx* ctx, const Call& c, int ndev, Shared& sh, doubl
   return PLAIDHIP_OK;
 }
 
+// plaid.fry after plaid.limma's two rounds (include/plaidhip.h: plaidhip_fry).  Shard 0 makes the divisors c_g from the
+// residual sums of squares of ALL samples (the prior needs every gene's).  Then, fit by fit: Z' of the shard's columns
+// (kernels_fry.hip), T = G'Z' and the block partials of the sums of T^2, as the estimated-VIF branch of plaid.camera below;
+// and for a fit under the cap the residual effects rho = Q2'z' as d (+ 1, the pass's mean column) more weight columns of the
+// effects pass run over Z', chained as [d + 1][rows].  A last round chains the sums of T^2 as [nfit][m].
+int fry_rounds(Shard& s, CtxBuf& dA, int64_t ld, DevBuf& dQ, DevBuf& duse, DevBuf& dmask, double* d_E) {
+  plaidhip_ctx* ctx = s.ctx;
+  const Call& c = s.c;
+  Shared& sh = s.sh;
+  const int32_t lo = s.lo, nloc = s.nloc, rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, m = c.m;
+  if (s.k == 0)
+    s.step([&]() -> int {
+      fry_divisors(rows, p, nfit, sh.limma.rss.data(), c.lm_nf.data(), c.standardize, sh.fry.cg.data());
+      return PLAIDHIP_OK;
+    });
+  sh.rv.arrive_and_wait();
+  int64_t dmax = 0;   // the widest fit under the cap
+  for (int32_t f = 0; f < nfit; ++f)
+    if (c.lm_Q2_off[(size_t)f] >= 0) dmax = std::max<int64_t>(dmax, c.lm_nf[(size_t)f] - p);
+  const int64_t Wmax = dmax > 0 ? dmax + 1 : 0;
+  CtxBuf dZ{ctx, 3}, dT{ctx, 4}, dsq{ctx, 5};
+  DevBuf dcg, dq2, dzero, dmask2, dwt2, dws2, dchain2;
+  double *d_part = nullptr, *d_chain = nullptr;
+  std::vector<double> q2loc;
+  plaidhip_geneset* gs = nullptr;
+  s.step([&]() -> int {
+    if (nloc == 0) return PLAIDHIP_OK;
+    PH_TRY(acquire_geneset(ctx, rows, m, c.Gp, c.Gi, &gs));
+    PH_TRY(dcg.alloc((size_t)nfit * rows * 8));
+    PH_HIP(hipMemcpyAsync(dcg.p, sh.fry.cg.data(), (size_t)nfit * rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dZ.alloc((size_t)ld * nloc * 8));
+    PH_TRY(dT.alloc((size_t)m * nloc * 8));
+    const size_t npart = (size_t)camera_sumsq_ws_doubles(nloc, (int64_t)nfit * m);
+    PH_TRY(dsq.alloc((npart + (size_t)nfit * m * 2) * 8));
+    d_part = dsq.as<double>();
+    d_chain = d_part + npart;
+    if (Wmax > 0) {
+      PH_TRY(dq2.alloc((size_t)nloc * dmax * 8));
+      PH_TRY(dzero.alloc(8));
+      PH_HIP(hipMemsetAsync(dzero.p, 0, 8, ctx->stream));   // (the weight of the effects pass's mean column: not used)
+      PH_TRY(dmask2.alloc((size_t)lmfit_mask_bytes(nloc, Wmax)));
+      PH_TRY(dwt2.alloc((size_t)lmfit_weight_bytes(nloc, Wmax)));
+      PH_TRY(dws2.alloc((size_t)row_design_ws_doubles(rows, nloc, Wmax) * 8));
+      PH_TRY(dchain2.alloc((size_t)Wmax * rows * 2 * 8));
+    }
+    return PLAIDHIP_OK;
+  });
+  for (int32_t f = 0; f < nfit; ++f) {
+    const int64_t off2 = c.lm_Q2_off[(size_t)f], d = c.lm_nf[(size_t)f] - p, W = d + 1;
+    s.step([&]() -> int {
+      if (nloc == 0) return PLAIDHIP_OK;
+      PH_TRY(launch_fry_residuals(ctx, dA.as<double>(), ld, rows, nloc, dQ.as<double>(), dmask.p, p, f, d_E, dcg.as<double>(),
+                                  dZ.as<double>(), ld));
+      PH_TRY(launch_spmm_dense_f64(ctx, gs, dZ.as<double>(), ld, nloc, PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0, dT.as<double>(), m,
+                                   nullptr));
+      PH_TRY(launch_camera_sumsq(ctx, dT.as<double>(), m, m, nloc, d_part + (size_t)f * m, (int64_t)nfit * m));
+      if (off2 < 0) return PLAIDHIP_OK;
+      PH_HIP(hipStreamSynchronize(ctx->stream));   // (q2loc below is the source of the previous fit's upload)
+      q2loc.resize((size_t)nloc * d);
+      for (int64_t col = 0; col < d; ++col)
+        std::copy(c.lm_Q2.begin() + off2 + col * n + lo, c.lm_Q2.begin() + off2 + col * n + lo + nloc,
+                  q2loc.begin() + col * nloc);
+      PH_HIP(hipMemcpyAsync(dq2.p, q2loc.data(), q2loc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+      PH_TRY(launch_lmfit_masks(ctx, dq2.as<double>(), c.use != nullptr ? duse.as<int8_t>() + (size_t)f * nloc : nullptr,
+                                dzero.as<double>(), nloc, (int32_t)d, 1, dmask2.p, dwt2.as<double>()));
+      return launch_row_design_effects(ctx, dZ.as<double>(), ld, rows, nloc, dmask2.p, dwt2.as<double>(), (int32_t)W,
+                                       dws2.as<double>());
+    });
+    if (off2 >= 0)
+      chain_flat_sums(s, sh.fry.rho[(size_t)f], dws2.as<double>(), W * rows, dchain2.as<double>(),
+                      dchain2.as<double>() + (size_t)W * rows);
+  }
+  chain_flat_sums(s, sh.camera.ss, d_part, (int64_t)nfit * m, d_chain, d_chain + (size_t)nfit * m);
+  return s.finish();
+}
+
 }  // namespace
 
 // one device's part of plaid.limma (kLimma, kernels_lmfit.hip; include/plaidhip.h: plaidhip_limma).  The SAMPLES are shared
@@ -98,7 +174,7 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   Shard s(ctx, c, ndev, k, sh);
   const int32_t lo = s.lo, nloc = s.nloc, rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit;
   const int64_t W = (int64_t)nfit * (p + 1), ld = even_ld(rows);
-  if (c.method == kCamera) s.force_f64();   // (T = G'Z stays on the fp64 kernels whatever precision the context was given)
+  if (c.method == kCamera || c.method == kFry) s.force_f64();   // (T = G'Z stays on the fp64 kernels whatever precision the context was given)
   CtxBuf dA{ctx, 0};
   DevBuf dQ, duse, dinvn, dmask, dwt, dws, drows;
   double *d_seed = nullptr, *d_run = nullptr, *d_E = nullptr;
@@ -197,6 +273,7 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
                                  dws.as<double>(), c.na_fit != 0);
   });
   chain_flat_sums(s, sh.limma.rss, dws.as<double>(), (int64_t)nfit * rows, d_seed, d_run);
+  if (c.method == kFry) return fry_rounds(s, dA, ld, dQ, duse, dmask, d_E);
   if (c.method != kCamera || !std::isnan(c.inter_gene_cor)) return s.finish();
 
   // ---- plaid.camera, the estimated correlation: fit by fit, Z of the shard's columns from the effects and the residual sums of
@@ -231,10 +308,18 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
   return s.finish();
 }
 
-bool limma_empty(const Call& c) { return c.g == 0 || c.nfit == 0 || c.nq == 0 || (c.method == kCamera && c.m == 0); }
+bool limma_empty(const Call& c) {
+  return c.g == 0 || c.nfit == 0 || c.nq == 0 || ((c.method == kCamera || c.method == kFry) && c.m == 0);
+}
 
 void limma_prepare(Shared& sh, const Call& c, int ndev) {
-  if (c.method == kCamera) sh.camera.ss.assign((size_t)c.nfit * c.m, 0.0);
+  if (c.method == kCamera || c.method == kFry) sh.camera.ss.assign((size_t)c.nfit * c.m, 0.0);
+  if (c.method == kFry) {
+    sh.fry.cg.assign((size_t)c.nfit * c.g, 0.0);
+    sh.fry.rho.assign((size_t)c.nfit, std::vector<double>());
+    for (int32_t f = 0; f < c.nfit; ++f)
+      if (c.lm_Q2_off[(size_t)f] >= 0) sh.fry.rho[(size_t)f].assign((size_t)(c.lm_nf[(size_t)f] - c.ncoef + 1) * c.g, 0.0);
+  }
   sh.limma.effects.assign((size_t)c.nfit * (c.ncoef + 1) * c.g, 0.0);
   sh.limma.rss.assign((size_t)c.nfit * c.g, 0.0);
   if (c.na_fit) {
@@ -315,6 +400,154 @@ int camera_tail(plaidhip_ctx* ctx, const Call& c, Shared& sh) {
     for (int h = 0; h < 4; ++h) c.hyper[6 * (size_t)f + h] = hyp[4 * (size_t)f + h];
     c.hyper[6 * (size_t)f + 4] = gdf[2 * (size_t)f];
     c.hyper[6 * (size_t)f + 5] = gdf[2 * (size_t)f + 1];
+  }
+  return PLAIDHIP_OK;
+}
+
+// plaid.fry after the workers (include/plaidhip.h: plaidhip_fry).  eBayes and the gene statistics on the host
+// (plaidhip_limma_finish), e_gj = logFC / (u_j c_g), the member sums of e and the counts from ONE crossprod as in
+// camera_tail; for every fit under the cap the Gram matrices and their two eigenvalues on the first context, sets in
+// chunks of at most 256 MiB of C; then the pinned tests (plaidhip_fry_finish).  Everything here is made from the chained
+// sums, so every sharding has the one-device bits.
+int fry_tail(plaidhip_ctx* ctx, const Call& c, Shared& sh) {
+  const int32_t g = c.g, m = c.m, nfit = c.nfit, q = c.nq, p = c.ncoef;
+  const size_t R = (size_t)g, M = (size_t)m, ncol = (size_t)nfit * q;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> tab(R * 6 * ncol), hyp((size_t)nfit * 4);
+  PH_TRY(plaidhip_limma_finish(g, p, nfit, q, sh.limma.effects.data(), sh.limma.rss.data(), c.lm_nf.data(), c.lm_v.data(),
+                               c.lm_u.data(), tab.data(), hyp.data()));
+  std::vector<double> B(R * (ncol + nfit)), S(M * (ncol + nfit)), dres((size_t)nfit), uni((size_t)nfit, 0.0);
+  std::vector<int8_t> mixed((size_t)nfit, 0);
+  bool any_mixed = false;
+  for (int32_t f = 0; f < nfit; ++f) {
+    const double* cg = sh.fry.cg.data() + R * f;
+    for (size_t r = 0; r < R; ++r) {
+      const bool in = cg[r] == cg[r];
+      B[(ncol + f) * R + r] = in ? 1.0 : 0.0;
+      uni[(size_t)f] += in ? 1.0 : 0.0;
+    }
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      const double* fc = tab.data() + col * 6 * R;
+      const double uj = c.lm_u[col];
+      for (size_t r = 0; r < R; ++r) B[col * R + r] = cg[r] == cg[r] ? fc[r] / (uj * cg[r]) : 0.0;
+    }
+    dres[(size_t)f] = hyp[4 * (size_t)f];
+    mixed[(size_t)f] = c.lm_Q2_off[(size_t)f] >= 0 ? 1 : 0;
+    any_mixed = any_mixed || mixed[(size_t)f] != 0;
+  }
+  std::vector<double> sume2, lam1, lamD, trM, froM;
+  if (any_mixed) {
+    sume2.assign(M * ncol, nan);
+    lam1.assign(M * ncol, nan);
+    lamD.assign(M * ncol, nan);
+    trM.assign(M * ncol, nan);
+    froM.assign(M * ncol, nan);
+  }
+  const int saved = ctx->precision;
+  ctx->precision = PLAIDHIP_PRECISION_F64;
+  int rc = [&]() -> int {
+    PH_HIP(hipSetDevice(ctx->device));
+    plaidhip_geneset* gs = nullptr;
+    PH_TRY(acquire_geneset(ctx, g, m, c.Gp, c.Gi, &gs));
+    DevBuf dB, dS;
+    PH_TRY(dB.alloc(B.size() * 8));
+    PH_TRY(dS.alloc(S.size() * 8));
+    PH_TRY(upload_host(ctx, dB.p, R * 8, B.data(), R * 8, (int64_t)(ncol + nfit)));
+    PH_TRY(launch_spmm_dense_f64(ctx, gs, dB.as<double>(), g, (int32_t)(ncol + nfit), PLAIDHIP_STAT_SUM, 1.0, nullptr, 0.0,
+                                 dS.as<double>(), m, nullptr));
+    PH_HIP(hipMemcpyAsync(S.data(), dS.p, S.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    if (!any_mixed) return PLAIDHIP_OK;
+    DevBuf dGp, dGi, drho, de, dC, db, da, dtr, dfro, dDk, dl1, dlD, dsw, dcv;
+    PH_TRY(upload_pattern(ctx, c.Gp, c.Gi, m, dGp, dGi));
+    std::vector<double> rhoT, eT, ha, htr, hfro, hl1, hlD;
+    std::vector<int32_t> Dk, hcv;
+    // the device buffers once, sized for the largest need of any fit under the cap (a set chunk holds at most 256 MiB of C)
+    auto chunk_of = [&](int32_t d) {
+      return (int32_t)std::max<int64_t>(1, std::min<int64_t>(m, ((int64_t)256 << 20) / ((int64_t)d * d * 8)));
+    };
+    size_t max_rho = 0, max_C = 0, max_b = 0, max_nq = 0;
+    for (int32_t f = 0; f < nfit; ++f) {
+      if (!mixed[(size_t)f]) continue;
+      const int32_t d = (int32_t)(c.lm_nf[(size_t)f] - p);
+      const size_t ch = (size_t)chunk_of(d);
+      max_rho = std::max(max_rho, R * (size_t)d);
+      max_C = std::max(max_C, ch * (size_t)d * d);
+      max_b = std::max(max_b, ch * q * (size_t)d);
+      max_nq = std::max(max_nq, ch * q);
+    }
+    PH_TRY(drho.alloc(max_rho * 8));
+    PH_TRY(de.alloc(R * q * 8));
+    PH_TRY(dC.alloc(max_C * 8));
+    PH_TRY(db.alloc(max_b * 8));
+    PH_TRY(da.alloc(max_nq * 8));
+    PH_TRY(dtr.alloc(max_nq * 8));
+    PH_TRY(dfro.alloc(max_nq * 8));
+    PH_TRY(dDk.alloc(max_nq * 4));
+    PH_TRY(dl1.alloc(max_nq * 8));
+    PH_TRY(dlD.alloc(max_nq * 8));
+    PH_TRY(dsw.alloc(max_nq * 4));
+    PH_TRY(dcv.alloc(max_nq * 4));
+    for (int32_t f = 0; f < nfit; ++f) {
+      if (!mixed[(size_t)f]) continue;
+      const int32_t d = (int32_t)(c.lm_nf[(size_t)f] - p);
+      const double* rho = sh.fry.rho[(size_t)f].data();   // [d + 1][rows]; gene-major for the gather
+      rhoT.resize(R * d);
+      eT.resize(R * q);
+      for (int32_t k = 0; k < d; ++k)
+        for (size_t r = 0; r < R; ++r) rhoT[r * d + k] = rho[(size_t)k * R + r];
+      for (int32_t j = 0; j < q; ++j)
+        for (size_t r = 0; r < R; ++r) eT[r * q + j] = B[((size_t)f * q + j) * R + r];
+      const int32_t chunk = chunk_of(d);
+      const size_t nq = (size_t)chunk * q;
+      PH_TRY(upload_host(ctx, drho.p, 1, rhoT.data(), 1, (int64_t)rhoT.size() * 8));
+      PH_TRY(upload_host(ctx, de.p, 1, eT.data(), 1, (int64_t)eT.size() * 8));
+      ha.resize(nq); htr.resize(nq); hfro.resize(nq); hl1.resize(nq); hlD.resize(nq); Dk.resize(nq); hcv.resize(nq);
+      for (int32_t s0 = 0; s0 < m; s0 += chunk) {
+        const int32_t ns = std::min(chunk, m - s0);
+        const size_t np = (size_t)ns * q;
+        for (int32_t s = 0; s < ns; ++s) {
+          const double mm = S[(ncol + f) * M + s0 + s];
+          for (int32_t j = 0; j < q; ++j) Dk[(size_t)s * q + j] = (int32_t)std::max(1.0, std::min(mm, (double)d + 1.0));
+        }
+        PH_HIP(hipMemcpyAsync(dDk.p, Dk.data(), np * 4, hipMemcpyHostToDevice, ctx->stream));
+        PH_TRY(launch_fry_gram(ctx, drho.as<double>(), de.as<double>(), d, q, dGp.as<int32_t>(), dGi.as<int32_t>(), s0, ns,
+                               dC.as<double>(), db.as<double>(), da.as<double>(), dtr.as<double>(), dfro.as<double>()));
+        PH_TRY(launch_fry_eigen(ctx, nullptr, dC.as<double>(), db.as<double>(), da.as<double>(), d + 1, q, (int64_t)np,
+                                dDk.as<int32_t>(), dl1.as<double>(), dlD.as<double>(), dsw.as<int32_t>(), dcv.as<int32_t>()));
+        PH_HIP(hipMemcpyAsync(ha.data(), da.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipMemcpyAsync(htr.data(), dtr.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipMemcpyAsync(hfro.data(), dfro.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipMemcpyAsync(hl1.data(), dl1.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipMemcpyAsync(hlD.data(), dlD.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipMemcpyAsync(hcv.data(), dcv.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));
+        for (int32_t s = 0; s < ns; ++s)
+          for (int32_t j = 0; j < q; ++j) {
+            const size_t src = (size_t)s * q + j, dst = ((size_t)f * q + j) * M + s0 + s;
+            const bool okc = hcv[src] != 0;   // (a problem that did not converge has no eigenvalues: NaN in the mixed columns)
+            sume2[dst] = ha[src];
+            trM[dst] = htr[src];
+            froM[dst] = hfro[src];
+            lam1[dst] = okc ? hl1[src] : nan;
+            lamD[dst] = okc ? hlD[src] : nan;
+          }
+      }
+    }
+    return PLAIDHIP_OK;
+  }();
+  ctx->precision = saved;
+  if (rc != PLAIDHIP_OK) return rc;
+  PH_TRY(plaidhip_fry_finish(m, nfit, q, dres.data(), S.data() + M * ncol, S.data(), sh.camera.ss.data(),
+                             any_mixed ? sume2.data() : nullptr, any_mixed ? lam1.data() : nullptr,
+                             any_mixed ? lamD.data() : nullptr, any_mixed ? trM.data() : nullptr,
+                             any_mixed ? froM.data() : nullptr, any_mixed ? mixed.data() : nullptr, c.out));
+  for (int32_t f = 0; f < nfit; ++f) {
+    for (int h = 0; h < 4; ++h) c.hyper[7 * (size_t)f + h] = hyp[4 * (size_t)f + h];
+    c.hyper[7 * (size_t)f + 4] = uni[(size_t)f];
+    c.hyper[7 * (size_t)f + 5] = dres[(size_t)f] + 1.0;
+    c.hyper[7 * (size_t)f + 6] = mixed[(size_t)f] ? 1.0 : 0.0;
   }
   return PLAIDHIP_OK;
 }

@@ -14,6 +14,7 @@
 
 #include "camera.h"
 #include "common.h"
+#include "fry.h"
 #include "lmfit_na.h"
 
 namespace plaidhip {
@@ -117,6 +118,12 @@ double t_two_sided_p(double t, double df) {
   const double t2 = t * t;
   // I_x(df/2, 1/2) at x = df / (df + t^2): small p <=> small x, which betai evaluates directly (no 1 - ...)
   return betai(0.5 * df, 0.5, df / (df + t2), t2 / (df + t2));
+}
+
+// pbeta(x, a, b, lower.tail = FALSE) = I_{1 - x}(b, a): betai takes both arguments, so neither tail forms 1 - (1 - ...)
+double beta_upper(double x, double a, double b) {
+  if (std::isnan(x) || !(a > 0.0) || !(b > 0.0)) return std::numeric_limits<double>::quiet_NaN();
+  return betai(b, a, 1.0 - x, x);
 }
 
 // pchisq(x, 2k, lower.tail = FALSE), k a positive integer
@@ -323,7 +330,7 @@ bool lm_threads(int64_t nth, Fn&& fn) {
 }  // namespace
 
 int limma_design(const char* what, const double* D, int32_t n, int32_t p, const int8_t* use, const double* K, int32_t q,
-                 int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf_out) {
+                 int32_t fit, double* Q, double* R, double* v, double* u, int64_t* nf_out, double* Q2) {
   std::vector<int32_t> sel;
   for (int32_t c = 0; c < n; ++c)
     if (use == nullptr || use[c] != 0) sel.push_back(c);
@@ -380,6 +387,24 @@ int limma_design(const char* what, const double* D, int32_t n, int32_t p, const 
     for (int32_t k = 0; k < p; ++k)
       for (int64_t i = 0; i < nf; ++i) Q[(int64_t)k * n + sel[(size_t)i]] = qs[(size_t)k * nf + i];
   }
+  if (Q2 != nullptr) {   // the other n_f - p columns of the full Q (plaid.fry): every reflector, last first, on e_p .. e_{n_f - 1}
+    const int64_t d = nf - p;
+    std::vector<double> y((size_t)nf);
+    std::fill(Q2, Q2 + (size_t)n * d, 0.0);
+    for (int64_t j = 0; j < d; ++j) {
+      std::fill(y.begin(), y.end(), 0.0);
+      y[(size_t)(p + j)] = 1.0;
+      for (int32_t k = p - 1; k >= 0; --k) {
+        const double* x = a.data() + (size_t)k * nf;
+        double dot = v0[(size_t)k] * y[(size_t)k];
+        for (int64_t i = k + 1; i < nf; ++i) dot += x[i] * y[(size_t)i];
+        const double s = 2.0 * dot / vn[(size_t)k];
+        y[(size_t)k] -= s * v0[(size_t)k];
+        for (int64_t i = k + 1; i < nf; ++i) y[(size_t)i] -= s * x[i];
+      }
+      for (int64_t i = 0; i < nf; ++i) Q2[j * n + sel[(size_t)i]] = y[(size_t)i];
+    }
+  }
   if (R != nullptr) std::copy(Rm.begin(), Rm.end(), R);
   if (nf_out != nullptr) *nf_out = nf;
   std::vector<double> vj((size_t)p);
@@ -397,6 +422,86 @@ int limma_design(const char* what, const double* D, int32_t n, int32_t p, const 
   return PLAIDHIP_OK;
 }
 
+// squeezeVar of one fit (step 3 of plaid.limma), for plaid.limma's tables and for plaid.fry's divisors: s[r] = rss[r] / d_r,
+// the prior (d0, s0^2) from the ok rows, po[r] = s2.post (NaN for a row that is not ok).  dr == nullptr: every row has d = dfit.
+LimmaPrior limma_squeeze_fit(size_t R, double dfit, const double* dr, const double* rssf, double* s, double* po) {
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  std::vector<double> xs;
+  double d = dfit, dsum = 0.0;   // d: the ok rows' residual df where they share one
+  bool alleq = true;
+  for (size_t r = 0; r < R; ++r) {
+    const double di = dr != nullptr ? dr[r] : dfit;
+    s[r] = rssf[r] / di;
+    if (!std::isfinite(s[r])) continue;
+    if (dr != nullptr) {
+      if (xs.empty()) d = di;
+      else if (di != d) alleq = false;
+      dsum += di;
+    }
+    xs.push_back(s[r]);
+  }
+  const int64_t nok = (int64_t)xs.size();
+  const double pool = alleq ? (double)nok * d : dsum;   // df.pooled
+  double d0 = 0.0, s0 = nan;
+  if (nok >= 2) {
+    const size_t h = (size_t)nok / 2;
+    std::nth_element(xs.begin(), xs.begin() + h, xs.end());
+    double med = xs[h];
+    if (nok % 2 == 0) med = (*std::max_element(xs.begin(), xs.begin() + h) + med) / 2.0;
+    if (med == 0.0) med = 1.0;
+    const double floor_x = 1e-5 * med, shift = -lm_digamma(0.5 * d) + std::log(0.5 * d);
+    double esum = 0.0, xsum = 0.0, trisum = 0.0;
+    std::vector<double> e;
+    e.reserve((size_t)nok);
+    for (size_t r = 0; r < R; ++r) {   // (in row order: the sums below are pinned as ascending)
+      if (!std::isfinite(s[r])) continue;
+      const double x = std::max(s[r], floor_x);
+      if (alleq) {
+        e.push_back(std::log(x) + shift);
+      } else {
+        e.push_back(std::log(x) + (-lm_digamma(0.5 * dr[r]) + std::log(0.5 * dr[r])));
+        trisum += lm_trigamma(0.5 * dr[r]);
+      }
+      esum += e.back();
+      xsum += x;
+    }
+    const double ebar = esum / (double)nok;
+    double ss = 0.0;
+    for (double ei : e) ss += (ei - ebar) * (ei - ebar);
+    const double var = ss / (double)(nok - 1) - (alleq ? lm_trigamma(0.5 * d) : trisum / (double)nok);
+    if (var > 0.0) {
+      const double y = lm_trigamma_inverse(var);
+      d0 = 2.0 * y;
+      s0 = std::exp(ebar + lm_digamma(y) - std::log(y));
+    } else {
+      d0 = inf;
+      s0 = xsum / (double)nok;
+    }
+  }
+  for (size_t r = 0; r < R; ++r) {
+    const double di = dr != nullptr ? dr[r] : dfit;
+    po[r] = !std::isfinite(s[r]) ? nan : std::isinf(d0) ? s0 : d0 == 0.0 ? s[r] : (di * s[r] + d0 * s0) / (di + d0);
+  }
+  return LimmaPrior{d0, s0, pool, nok};
+}
+
+// plaid.fry's divisors (include/plaidhip.h: plaidhip_fry, step 1): c_g = sqrt(s2.post), sqrt(s2) or 1.0 of an ok gene; a
+// divisor that is 0 or not finite, and every gene that is not ok, becomes NaN: the gene is outside the fit's universe
+void fry_divisors(int32_t rows, int32_t p, int32_t nfit, const double* rss, const int64_t* nf, int standardize, double* cg) {
+  const size_t R = (size_t)rows;
+  std::vector<double> s(R), po(R);
+  for (int32_t f = 0; f < nfit; ++f) {
+    limma_squeeze_fit(R, (double)(nf[f] - p), nullptr, rss + R * f, s.data(), po.data());
+    for (size_t r = 0; r < R; ++r) {
+      double c = std::numeric_limits<double>::quiet_NaN();
+      if (std::isfinite(s[r]))
+        c = standardize == PLAIDHIP_FRY_STANDARDIZE_POSTERIOR ? std::sqrt(po[r])
+            : standardize == PLAIDHIP_FRY_STANDARDIZE_RESIDUAL ? std::sqrt(s[r]) : 1.0;
+      cg[R * f + r] = fry_in_universe(c) ? c : std::numeric_limits<double>::quiet_NaN();
+    }
+  }
+}
+
 // Step 3 of plaid.limma and its tables.  drow == nullptr is plaidhip_limma_finish: every row of fit f has d = n_f - p and
 // the fit's u_j.  Otherwise (plaidhip_limma_finish_na) row r of fit f has d_r = drow[f][r] (NaN: not fitted) and its own
 // u_j, and squeezeVar's moments take a vector df1; where all ok rows share one d the operations are those of the first form.
@@ -409,78 +514,21 @@ int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, i
   PH_REQUIRE(E && rss && nf && v && u && out && hyper, "%s: null argument", what);
   for (int32_t f = 0; f < nfit; ++f)
     PH_REQUIRE(nf[f] - p >= 1, "%s: fit %d has %lld samples for %d coefficients", what, f + 1, (long long)nf[f], p);
-  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
   const size_t R = (size_t)rows;
   // per fit: s2, the prior, s2.post and df.total
-  std::vector<double> s2(R * nfit), post(R * nfit), d0s((size_t)nfit), pooled((size_t)nfit), xs;
+  std::vector<double> s2(R * nfit), post(R * nfit), d0s((size_t)nfit), pooled((size_t)nfit);
   for (int32_t f = 0; f < nfit; ++f) {
     const double dfit = (double)(nf[f] - p);
-    const double* dr = drow != nullptr ? drow + R * f : nullptr;
-    double* s = s2.data() + R * f;
-    xs.clear();
-    double d = dfit, dsum = 0.0;   // d: the ok rows' residual df where they share one
-    bool alleq = true;
-    for (size_t r = 0; r < R; ++r) {
-      const double di = dr != nullptr ? dr[r] : dfit;
-      s[r] = rss[R * f + r] / di;
-      if (!std::isfinite(s[r])) continue;
-      if (dr != nullptr) {
-        if (xs.empty()) d = di;
-        else if (di != d) alleq = false;
-        dsum += di;
-      }
-      xs.push_back(s[r]);
-    }
-    const int64_t nok = (int64_t)xs.size();
-    const double pool = alleq ? (double)nok * d : dsum;   // df.pooled
-    double d0 = 0.0, s0 = nan;
-    if (nok >= 2) {
-      const size_t h = (size_t)nok / 2;
-      std::nth_element(xs.begin(), xs.begin() + h, xs.end());
-      double med = xs[h];
-      if (nok % 2 == 0) med = (*std::max_element(xs.begin(), xs.begin() + h) + med) / 2.0;
-      if (med == 0.0) med = 1.0;
-      const double floor_x = 1e-5 * med, shift = -lm_digamma(0.5 * d) + std::log(0.5 * d);
-      double esum = 0.0, xsum = 0.0, trisum = 0.0;
-      std::vector<double> e;
-      e.reserve((size_t)nok);
-      for (size_t r = 0; r < R; ++r) {   // (in row order: the sums below are pinned as ascending)
-        if (!std::isfinite(s[r])) continue;
-        const double x = std::max(s[r], floor_x);
-        if (alleq) {
-          e.push_back(std::log(x) + shift);
-        } else {
-          e.push_back(std::log(x) + (-lm_digamma(0.5 * dr[r]) + std::log(0.5 * dr[r])));
-          trisum += lm_trigamma(0.5 * dr[r]);
-        }
-        esum += e.back();
-        xsum += x;
-      }
-      const double ebar = esum / (double)nok;
-      double ss = 0.0;
-      for (double ei : e) ss += (ei - ebar) * (ei - ebar);
-      const double var = ss / (double)(nok - 1) - (alleq ? lm_trigamma(0.5 * d) : trisum / (double)nok);
-      if (var > 0.0) {
-        const double y = lm_trigamma_inverse(var);
-        d0 = 2.0 * y;
-        s0 = std::exp(ebar + lm_digamma(y) - std::log(y));
-      } else {
-        d0 = inf;
-        s0 = xsum / (double)nok;
-      }
-    }
+    const LimmaPrior pr = limma_squeeze_fit(R, dfit, drow != nullptr ? drow + R * f : nullptr, rss + R * f, s2.data() + R * f,
+                                            post.data() + R * f);
     hyper[(size_t)hcols * f] = dfit;
-    hyper[(size_t)hcols * f + 1] = d0;
-    hyper[(size_t)hcols * f + 2] = s0;
-    hyper[(size_t)hcols * f + 3] = (double)nok;
-    if (hcols > 4) hyper[(size_t)hcols * f + 4] = pool;
-    d0s[(size_t)f] = d0;
-    pooled[(size_t)f] = pool;
-    double* po = post.data() + R * f;
-    for (size_t r = 0; r < R; ++r) {
-      const double di = dr != nullptr ? dr[r] : dfit;
-      po[r] = !std::isfinite(s[r]) ? nan : std::isinf(d0) ? s0 : d0 == 0.0 ? s[r] : (di * s[r] + d0 * s0) / (di + d0);
-    }
+    hyper[(size_t)hcols * f + 1] = pr.d0;
+    hyper[(size_t)hcols * f + 2] = pr.s0;
+    hyper[(size_t)hcols * f + 3] = (double)pr.nok;
+    if (hcols > 4) hyper[(size_t)hcols * f + 4] = pr.pool;
+    d0s[(size_t)f] = pr.d0;
+    pooled[(size_t)f] = pr.pool;
   }
   // logFC, AveExpr, t, P.Value and sigma2 of every (fit, contrast, row): row chunks dealt to the threads
   const int64_t ncol = (int64_t)nfit * q, items = ncol * rows;
@@ -782,7 +830,108 @@ int plaidhip_camera_finish(int32_t g, int32_t m, int32_t nfit, int32_t q, const 
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.fry, step 2 for one gene (include/plaidhip.h): the functions the device runs (camera.h, fry.h)
+int plaidhip_fry_residual_row(int32_t n, int32_t p, const double* x, const double* Q, const int8_t* use, const double* E,
+                              double c, double* z) try {
+  using namespace plaidhip;
+  PH_REQUIRE(n >= 0, "fry_residual_row: bad dims n=%d", n);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "fry_residual_row: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  if (n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(x && Q && E && z, "fry_residual_row: null argument");
+  for (int32_t s = 0; s < n; ++s) {
+    double r = x[s];
+    for (int32_t k = 0; k < p; ++k) r = camera_chain_step(Q[(size_t)k * n + s], E[k], r);
+    z[s] = fry_standardise(r, c, use == nullptr || use[s] != 0);
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.fry (include/plaidhip.h): Q2 of one design, n x (n_f - p) column-major, the rows of unused samples zero
+int plaidhip_fry_q2(const double* D, int32_t n, int32_t p, const int8_t* use, int32_t fit, double* Q2, int64_t* nf) try {
+  using namespace plaidhip;
+  PH_REQUIRE(n >= 0, "fry_q2: bad dims n=%d", n);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "fry_q2: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(D != nullptr || n == 0, "fry_q2: null design");
+  PH_REQUIRE(Q2 != nullptr, "fry_q2: null Q2");
+  return limma_design("fry_q2", D, n, p, use, nullptr, 0, fit, nullptr, nullptr, nullptr, nullptr, nf, Q2);
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.fry, step 1 (include/plaidhip.h): the divisors of every (fit, gene) from the residual sums of squares of ALL samples
+int plaidhip_fry_divisors(int32_t rows, int32_t p, int32_t nfit, const double* rss, const int64_t* nf, int standardize,
+                          double* cg) try {
+  using namespace plaidhip;
+  PH_REQUIRE(rows >= 0 && nfit >= 0, "fry_divisors: bad dims rows=%d nfit=%d", rows, nfit);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "fry_divisors: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(standardize >= 0 && standardize <= 2, "fry_divisors: standardize = %d (0 posterior.sd, 1 residual.sd, 2 none)",
+             standardize);
+  if (rows == 0 || nfit == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(rss && nf && cg, "fry_divisors: null argument");
+  for (int32_t f = 0; f < nfit; ++f)
+    PH_REQUIRE(nf[f] - p >= 1, "fry_divisors: fit %d has %lld samples for %d coefficients", f + 1, (long long)nf[f], p);
+  fry_divisors(rows, p, nfit, rss, nf, standardize, cg);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.fry, step 5 (include/plaidhip.h): the tests of every (fit, contrast, set), fp64
+int plaidhip_fry_finish(int32_t m, int32_t nfit, int32_t q, const double* dres, const double* cnt, const double* sume,
+                        const double* ss, const double* sume2, const double* lam1, const double* lamD, const double* trM,
+                        const double* froM, const int8_t* mixed, double* out) try {
+  using namespace plaidhip;
+  PH_REQUIRE(m >= 0 && nfit >= 0 && q >= 0, "fry_finish: bad dims m=%d nfit=%d q=%d", m, nfit, q);
+  if (m == 0 || nfit == 0 || q == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(dres && cnt && sume && ss && out, "fry_finish: null argument");
+  const bool any_mixed = mixed != nullptr;
+  PH_REQUIRE(!any_mixed || (sume2 && lam1 && lamD && trM && froM), "fry_finish: null argument of the mixed test");
+  for (int32_t f = 0; f < nfit; ++f) PH_REQUIRE(dres[f] >= 1.0, "fry_finish: fit %d: df.residual = %g", f + 1, dres[f]);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const size_t M = (size_t)m;
+  for (int32_t f = 0; f < nfit; ++f) {
+    const double d = dres[f];
+    const bool mix = any_mixed && mixed[f] != 0;
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      double* o = out + col * 7 * M;
+      for (size_t s = 0; s < M; ++s) {
+        const double mm = cnt[M * f + s];
+        double dir = nan, t = nan, pv = nan, pm = nan;
+        if (mm >= 1.0) {
+          const double mean = sume[col * M + s] / mm;
+          t = mean / std::sqrt(ss[M * f + s] / ((mm * mm) * d));
+          pv = t_two_sided_p(t, d);
+          if (t == t) dir = t < 0.0 ? -1.0 : 1.0;
+          if (mix && mm == 1.0) {
+            pm = pv;
+          } else if (mix) {
+            const double D = std::min(mm, d + 1.0), l1 = lam1[col * M + s], lD = lamD[col * M + s];
+            const double A = trM[col * M + s], A2 = froM[col * M + s], den = l1 - lD;
+            const double Fobs = (sume2[col * M + s] - lD) / den;
+            const double bm = 1.0 / D, bv = (D - 1.0) / (D * D) / (D / 2.0 + 1.0);
+            const double Fm = (A * bm - lD) / den;
+            const double Fv = (bv * A2 - bv / (D - 1.0) * (A * A - A2)) / (den * den);
+            const double ab = Fm * (1.0 - Fm) / Fv - 1.0, alpha = ab * Fm, beta = ab - alpha;
+            if (std::isfinite(alpha) && std::isfinite(beta) && alpha > 0.0 && beta > 0.0 && Fobs == Fobs)
+              pm = beta_upper(Fobs, alpha, beta);
+          }
+        }
+        o[s] = mm;
+        o[M + s] = dir;
+        o[2 * M + s] = t;
+        o[3 * M + s] = pv;
+        o[5 * M + s] = pm;
+      }
+      p_adjust_fdr(o + 3 * M, m, o + 4 * M);
+      p_adjust_fdr(o + 5 * M, m, o + 6 * M);
+    }
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
 }  // extern "C"
+
+// Test hook (not part of include/plaidhip.h): pbeta(x, a, b, lower.tail = FALSE) as plaid.fry's mixed test takes it
+extern "C" double plaidhip_debug_beta_upper(double x, double a, double b) { return plaidhip::beta_upper(x, a, b); }
 
 // Test hook (not part of include/plaidhip.h): the distribution functions above, so that the CPU-side
 // tests can check them against scipy without a device.  kind 0: 2*pt(|x|, a, lower=FALSE);

@@ -762,6 +762,103 @@ def camera_finish(t, ok, sumt, cnt, ss, dfres, dfprior, inter_gene_cor=None, all
     return out, gdf
 
 
+FRY_COLUMNS = ("NGenes", "Direction", "t", "PValue", "FDR", "PValue.Mixed", "FDR.Mixed")
+FRY_HYPER = LIMMA_HYPER + ("n.genes", "n.effects", "mixed")
+FRY_STANDARDIZE = {"posterior.sd": 0, "residual.sd": 1, "none": 2}
+FRY_MIXED_MAX = 128
+
+
+def check_fry_standardize(standardize):
+    """standardize as the C ABI takes it"""
+    if standardize not in FRY_STANDARDIZE:
+        raise ValueError(f"fry: standardize must be one of {sorted(FRY_STANDARDIZE)} (\"p2\" is not offered)")
+    return FRY_STANDARDIZE[standardize]
+
+
+def _fry(fn, head, X, design, Gp, Gi, use=None, contrasts=None, standardize="posterior.sd", out=None, hyper=None):
+    """plaidhip_fry / _multi / the hook: (out, hyper) -- sets x 7 x q x nfit (FRY_COLUMNS) and nfit x 7 (FRY_HYPER)"""
+    X = _as_f64_fortran(X)
+    if X.ndim != 2:
+        raise ValueError("fry: the matrix must be genes x samples")
+    g, n = X.shape
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    out = np.full((m, 7, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 7), np.nan, dtype=np.float64) if hyper is None else hyper
+    check(fn(*head, _np_ptr(X), g, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+             q, _np_ptr(Gp), _np_ptr(Gi), m, check_fry_standardize(standardize), _np_ptr(out), _np_ptr(hyper)))
+    return out, hyper
+
+
+def fry_q2(design, use=None, fit=1) -> np.ndarray:
+    """plaidhip_fry_q2 on the host (no device is touched): the n x (n_f - p) other columns of the full Householder Q of one
+    design, the rows of the samples left out zero"""
+    D0 = np.asarray(design, dtype=np.float64)
+    if D0.ndim != 2:
+        raise ValueError("fry_q2: one design, samples x coefficients")
+    D, U, _, _ = limma_operands(D0.shape[0], D0, use, None)
+    n, p = D.shape[0], D.shape[1]
+    nf = n if U is None else int(U.sum())
+    Q2 = np.full((n, max(nf - p, 0)), np.nan, order="F")
+    got = C.c_int64(-1)
+    check(_lib.load().plaidhip_fry_q2(_np_ptr(D), n, p, None if U is None else _np_ptr(U), int(fit), _np_ptr(Q2),
+                                      C.cast(C.byref(got), C.c_void_p)))
+    return Q2
+
+
+def fry_divisors(rss, nf, p, standardize="posterior.sd") -> np.ndarray:
+    """plaidhip_fry_divisors on the host: rss nfit x rows, nf per fit -> c_g nfit x rows (NaN: outside the universe)"""
+    rss = np.ascontiguousarray(np.atleast_2d(np.asarray(rss, dtype=np.float64)))
+    nfit, rows = rss.shape
+    nf = np.ascontiguousarray(np.atleast_1d(nf), dtype=np.int64)
+    if nf.shape != (nfit,):
+        raise ValueError("fry_divisors: nf has one entry per fit")
+    cg = np.full((nfit, rows), -7.0)
+    check(_lib.load().plaidhip_fry_divisors(rows, int(p), nfit, _np_ptr(rss), _np_ptr(nf), check_fry_standardize(standardize),
+                                            _np_ptr(cg)))
+    return cg
+
+
+def fry_residual_row(x, Q, use, E, c) -> np.ndarray:
+    """plaidhip_fry_residual_row on the host: the standardised residuals of one gene at the divisor c"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64).reshape(len(x), -1))
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    U = None if use is None else np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int8)
+    z = np.full(len(x), -7.0)
+    check(_lib.load().plaidhip_fry_residual_row(len(x), Q.shape[1], _np_ptr(x), _np_ptr(Q), None if U is None else _np_ptr(U),
+                                                _np_ptr(E), float(c), _np_ptr(z)))
+    return z
+
+
+def fry_finish(dres, cnt, sume, ss, sume2=None, lam1=None, lamD=None, trM=None, froM=None, mixed=None):
+    """plaidhip_fry_finish on the host: dres per fit, cnt and ss sets x nfit, sume (and the mixed test's sume2, lam1, lamD,
+    trM, froM) sets x q x nfit, mixed per fit or None -> out sets x 7 x q x nfit"""
+    sume = np.asarray(sume, dtype=np.float64)
+    sume = np.asfortranarray(sume[:, :, None] if sume.ndim == 2 else sume)
+    m, q, nfit = sume.shape
+    f2 = lambda v: np.asfortranarray(np.asarray(v, dtype=np.float64).reshape((m, nfit), order="F"))
+    f3 = lambda v: np.asfortranarray(np.asarray(v, dtype=np.float64).reshape((m, q, nfit), order="F"))
+    cnt, ss = f2(cnt), f2(ss)
+    dres = np.ascontiguousarray(np.atleast_1d(dres), dtype=np.float64)
+    extra = [None] * 5 if mixed is None else [f3(v) for v in (sume2, lam1, lamD, trM, froM)]
+    mx = None if mixed is None else np.ascontiguousarray(np.atleast_1d(mixed), dtype=np.int8)
+    out = np.full((m, 7, q, nfit), -7.0, order="F")
+    check(_lib.load().plaidhip_fry_finish(m, nfit, q, _np_ptr(dres), _np_ptr(cnt), _np_ptr(sume), _np_ptr(ss),
+                                          *[None if v is None else _np_ptr(v) for v in extra],
+                                          None if mx is None else _np_ptr(mx), _np_ptr(out)))
+    return out
+
+
+def beta_upper(x, a, b) -> float:
+    """pbeta(x, a, b, lower.tail = FALSE) as plaid.fry's mixed test takes it (a test hook of the library)"""
+    f = _lib.load().plaidhip_debug_beta_upper
+    f.argtypes, f.restype = [C.c_double] * 3, C.c_double
+    return float(f(float(x), float(a), float(b)))
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -1200,6 +1297,29 @@ class Context:
         residuals.  (out sets x 8 x q x nfit in CAMERA_COLUMNS, hyper nfit x 6 in CAMERA_HYPER)"""
         return _camera(self.lib.plaidhip_camera, (self.handle,), X, design, Gp, Gi, use, contrasts, inter_gene_cor, allow_neg_cor)
 
+    def fry(self, X, design, Gp, Gi, use=None, contrasts=None, standardize="posterior.sd"):
+        """plaidhip_fry: limma's self-contained set test fry of the sets (Gp, Gi, aligned to the rows of X), as
+        Context.camera takes its operands.  Returns (out, hyper): sets x 7 x q x nfit (FRY_COLUMNS) and nfit x 7 (FRY_HYPER)."""
+        return _fry(self.lib.plaidhip_fry, (self.handle,), X, design, Gp, Gi, use, contrasts, standardize)
+
+    def dev_fry_residuals(self, A: int, ld: int, rows: int, n: int, Q: int, use, p: int, nfit: int, fit: int, E: int, cg: int,
+                          Z: int, ldz: int):
+        """plaidhip_dev_fry_residuals on device pointers: dev_camera_residuals with the divisors cg ([nfit][rows])"""
+        check(self.lib.plaidhip_dev_fry_residuals(self.handle, A, ld, rows, n, Q, use, p, nfit, fit, E, cg, Z, ldz))
+
+    def dev_fry_residual_effects(self, Z: int, ldz: int, rows: int, n: int, Q2: int, use, d: int, seed, rho: int):
+        """plaidhip_dev_fry_residual_effects on device pointers: rho ([d + 1][rows], the last row unused) = seed + Z Q2"""
+        check(self.lib.plaidhip_dev_fry_residual_effects(self.handle, Z, ldz, rows, n, Q2, use, d, seed, rho))
+
+    def dev_fry_gram(self, rho: int, e: int, rows: int, d: int, q: int, Gp: int, Gi: int, m: int, Cm: int, b: int, a: int,
+                     tr: int, fro: int):
+        """plaidhip_dev_fry_gram on device pointers: C (m x d x d), b (m x q x d), a, tr, fro (m x q) of every set"""
+        check(self.lib.plaidhip_dev_fry_gram(self.handle, rho, e, rows, d, q, Gp, Gi, m, Cm, b, a, tr, fro))
+
+    def dev_fry_eigen(self, M: int, dim: int, nprob: int, Dk: int, lam1: int, lamD: int, sweeps: int, conv: int):
+        """plaidhip_dev_fry_eigen on device pointers: the largest and the Dk-th largest eigenvalue of nprob matrices"""
+        check(self.lib.plaidhip_dev_fry_eigen(self.handle, M, dim, nprob, Dk, lam1, lamD, sweeps, conv))
+
     def dev_camera_residuals(self, A: int, ld: int, rows: int, n: int, Q: int, use, p: int, nfit: int, fit: int, E: int, rss: int,
                              d: float, Z: int, ldz: int):
         """plaidhip_dev_camera_residuals on device pointers: Z (rows x n, leading dimension ldz) of fit `fit` (from 0) at the
@@ -1448,6 +1568,11 @@ def plage_multi(X, Gp, Gi, tol=PLAGE_TOL, maxit=1000, loadings=False, devices=1)
 def zscore_multi(X, Gp, Gi, devices=1):
     """replaid.zscore (Context.zscore) with the sample columns shared out over `devices`: the one-device bits"""
     return _zscore(*_multi("zscore", devices), X, Gp, Gi)
+
+
+def fry_multi(X, design, Gp, Gi, use=None, contrasts=None, standardize="posterior.sd", devices=1):
+    """plaid.fry (Context.fry) with the sample columns sharded over `devices`: the one-device bits"""
+    return _fry(*_multi("fry", devices), X, design, Gp, Gi, use, contrasts, standardize)
 
 
 def camera_multi(X, design, Gp, Gi, use=None, contrasts=None, inter_gene_cor=0.01, allow_neg_cor=False, devices=1):

@@ -885,6 +885,94 @@ plaid.camera.contrasts <- function(X, Y, G, B = NULL, inter.gene.cor = 0.01, all
 }
 
 
+## the tables of plaid.fry() / plaid.fry.contrasts() from the library's sets x 7 block (NGenes, Direction, t, PValue, FDR,
+## PValue.Mixed, FDR.Mixed): Direction is "Up" for +1 and "Down" for -1; ordered by sort.by -- "directional" (PValue),
+## "mixed" (PValue.Mixed), "none"; NA last
+.fry_sorts <- c("directional", "mixed", "none")
+.fry_standardize <- c("posterior.sd", "residual.sd", "none")
+
+.fry_table <- function(tab, rn, sort.by) {
+  tab <- matrix(tab, nrow = length(rn), ncol = 7L)
+  res <- data.frame(NGenes = tab[, 1], Direction = ifelse(is.na(tab[, 2]), NA_character_, ifelse(tab[, 2] > 0, "Up", "Down")),
+                    t = tab[, 3], PValue = tab[, 4], FDR = tab[, 5], PValue.Mixed = tab[, 6], FDR.Mixed = tab[, 7],
+                    row.names = rn, stringsAsFactors = FALSE)
+  key <- switch(sort.by, none = NULL, directional = res$PValue, mixed = res$PValue.Mixed)
+  if (!is.null(key)) res <- res[order(key), , drop = FALSE]
+  res
+}
+
+.fry_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok", "n.genes", "n.effects", "mixed"))
+
+.fry_call <- function(cs, D, nfit, use, K, standardize, ncon, sort.by) {
+  if (length(standardize) != 1L || !standardize %in% .fry_standardize)
+    stop("plaid.fry: standardize must be one of ", paste(.fry_standardize, collapse = ", "), " (\"p2\" is not offered)")
+  if (length(sort.by) != 1L || !sort.by %in% .fry_sorts) stop("plaid.fry: sort.by must be one of ", paste(.fry_sorts, collapse = ", "))
+  .session()
+  r <- .Call("R_plaidhip_fry", .devices(), cs$X, D, nfit, use, K, cs$Gp, cs$Gi, match(standardize, .fry_standardize) - 1L,
+             PACKAGE = "plaidhip")
+  out <- r[[1]]
+  dim(out) <- c(length(cs$names), 7L, ncon)
+  list(tables = lapply(seq_len(ncon), function(j) .fry_table(out[, , j], cs$names, sort.by)), hyper = r[[2]])
+}
+
+
+## plaid.fry(): limma's self-contained rotation gene-set test in closed form (fry: roast with infinitely many rotations, as
+## pinned in include/plaidhip.h: plaidhip_fry) of every set of G on the expression X (genes x samples) for one design.  The
+## operands are plaid.camera()'s.  camera asks whether a set moves more than the other genes, fry whether the set is
+## differential at all; no random number is drawn.  standardize: "posterior.sd" (the default: the effects are plaid.limma()'s
+## moderated t), "residual.sd" or "none".  The directional test is complete for any number of samples; the mixed test is
+## offered for fits with df.residual + 1 <= 128 effects and NA above that (hyper$mixed = 0).
+## Returns list(tables = <named list, one data frame per contrast: sets x (NGenes, Direction, t, PValue, FDR, PValue.Mixed,
+## FDR.Mixed), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok, n.genes, n.effects, mixed)).
+## Not offered: roast / mroast, gene or array weights, trend.var, robust, a sparse X, na = "fit", standardize = "p2".
+plaid.fry <- function(X, design, G, contrasts = NULL, use = NULL, standardize = "posterior.sd", minSize = 1, maxSize = NULL,
+                      sort.by = "directional") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(cs$X)) stop("design must have one row per column of X")
+  cn <- if (is.null(colnames(design))) paste0("coef", seq_len(ncol(design))) else colnames(design)
+  if (!is.null(contrasts)) {
+    contrasts <- as.matrix(contrasts); storage.mode(contrasts) <- "double"
+    if (nrow(contrasts) != ncol(design)) stop("contrasts must have one row per coefficient")
+    cn <- if (is.null(colnames(contrasts))) as.character(seq_len(ncol(contrasts))) else colnames(contrasts)
+  }
+  if (!is.null(use)) {
+    if (length(use) != ncol(cs$X)) stop("use must have one entry per column of X")
+    use <- matrix(as.integer(!is.na(use) & use != 0), ncol = 1)
+  }
+  r <- .fry_call(cs, design, 1L, use, contrasts, standardize, length(cn), sort.by)
+  tables <- r$tables
+  names(tables) <- cn
+  list(tables = tables, hyper = .fry_hyper(r$hyper[, 1]))
+}
+
+
+## plaid.fry.contrasts(): plaid.fry() for every column of a contrast matrix Y (samples x contrasts; 0, 1, NA = the sample
+## takes no part) in ONE call, with the designs of plaid.limma.contrasts().  X is uploaded once.
+plaid.fry.contrasts <- function(X, Y, G, B = NULL, standardize = "posterior.sd", minSize = 1, maxSize = NULL,
+                                sort.by = "directional") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  Y <- as.matrix(Y)
+  if (nrow(Y) != ncol(cs$X)) stop("Y must have one row per column of X")
+  if (!all(unique(as.vector(Y)) %in% c(0, 1, NA))) stop("elements of Y must be 0, 1 or NA")
+  if (!is.null(B)) {
+    B <- as.matrix(B); storage.mode(B) <- "double"
+    if (nrow(B) != ncol(cs$X)) stop("B must have one row per column of X")
+  }
+  D <- do.call(cbind, lapply(seq_len(ncol(Y)), function(j) cbind(1, ifelse(is.na(Y[, j]), 0, Y[, j]), B)))
+  storage.mode(D) <- "double"
+  p <- 2L + (if (is.null(B)) 0L else ncol(B))
+  K <- matrix(0, p, 1); K[2, 1] <- 1
+  use <- matrix(as.integer(!is.na(Y)), nrow(Y), ncol(Y))
+  cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
+  r <- .fry_call(cs, D, ncol(Y), use, K, standardize, ncol(Y), sort.by)
+  tables <- r$tables
+  hyper <- lapply(seq_len(ncol(Y)), function(j) .fry_hyper(r$hyper[, j]))
+  names(tables) <- names(hyper) <- cn
+  list(tables = tables, hyper = hyper)
+}
+
+
 ## plaid.intergenecor(): limma's interGeneCorrelation(X[set, ], design) for every set of G at once: the variance inflation
 ## factor of the set's mean, estimated from the residuals of its genes, and the mean pairwise correlation (VIF - 1) / (m - 1).
 ## Returns a matrix, sets x (NGenes, Correlation, VIF), in G's order.

@@ -765,6 +765,44 @@ SEXP R_plaidhip_camera(SEXP devices, SEXP X, SEXP design, SEXP nfit_, SEXP use, 
   return res;
 }
 
+/* plaid.fry(): list(out, hyper) of plaidhip_fry -- out an m x (7 q nfit) matrix (the caller gives it dim m x 7 x q x nfit:
+ * NGenes, Direction, t, PValue, FDR, PValue.Mixed, FDR.Mixed), hyper 7 x nfit (plaid.limma's four, n.genes, n.effects, mixed
+ * down a column).  X, design, use, K, Gp, Gi: as R_plaidhip_camera; standardize: 0 posterior.sd, 1 residual.sd, 2 none */
+SEXP R_plaidhip_fry(SEXP devices, SEXP X, SEXP design, SEXP nfit_, SEXP use, SEXP K, SEXP Gp, SEXP Gi, SEXP standardize_) {
+  const int g = Rf_nrows(X), n = Rf_ncols(X), nfit = Rf_asInteger(nfit_), m = LENGTH(Gp) - 1;
+  if (nfit < 1 || Rf_nrows(design) != n || Rf_ncols(design) % nfit != 0)
+    Rf_error("plaid.fry: design must have one row per sample and the same number of columns for every fit");
+  if (m < 0) Rf_error("plaid.fry: an empty column pointer");
+  const int p = Rf_ncols(design) / nfit;
+  const int q = Rf_isNull(K) ? p : Rf_ncols(K);
+  if (!Rf_isNull(K) && Rf_nrows(K) != p) Rf_error("plaid.fry: contrasts must have one row per coefficient");
+  int8_t* u8 = NULL;
+  if (!Rf_isNull(use)) {
+    if (Rf_nrows(use) != n || Rf_ncols(use) != nfit) Rf_error("plaid.fry: use must be samples x fits");
+    const size_t count = (size_t)n * (size_t)nfit;
+    const int* u = INTEGER(use);
+    u8 = (int8_t*)R_alloc(count > 0 ? count : 1, 1);
+    for (size_t e = 0; e < count; ++e) u8[e] = (int8_t)(u[e] != 0 && u[e] != NA_INTEGER);
+  }
+  const int standardize = Rf_asInteger(standardize_);
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 7 * q * nfit));
+  SEXP hyper = PROTECT(Rf_allocMatrix(REALSXP, 7, nfit));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, hyper);
+  const double* Kp = Rf_isNull(K) ? NULL : REAL(K);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_fry_multi(INTEGER(devices), LENGTH(devices), REAL(X), g, n, REAL(design), p, nfit, u8, Kp, q, INTEGER(Gp),
+                            INTEGER(Gi), m, standardize, REAL(out), REAL(hyper));
+  else
+    rc = plaidhip_fry(ctx(), REAL(X), g, n, REAL(design), p, nfit, u8, Kp, q, INTEGER(Gp), INTEGER(Gi), m, standardize,
+                      REAL(out), REAL(hyper));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(3);
+  return res;
+}
+
 /* plaid.limma(na = "fit"): list(out, hyper, dfres) of plaidhip_limma_na -- R_plaidhip_limma's operands and max_na; hyper 5 x
  * nfit (df.pooled last), dfres rows x nfit (the df.residual of every fitted row, NaN for the others) */
 SEXP R_plaidhip_limma_na(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use, SEXP K, SEXP max_na_) {
@@ -919,6 +957,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
     {"R_plaidhip_limma_na", (DL_FUNC)&R_plaidhip_limma_na, 7},
     {"R_plaidhip_camera", (DL_FUNC)&R_plaidhip_camera, 10},
+    {"R_plaidhip_fry", (DL_FUNC)&R_plaidhip_fry, 9},
     {"R_plaidhip_rankcor", (DL_FUNC)&R_plaidhip_rankcor, 6},
     {"R_plaidhip_plage", (DL_FUNC)&R_plaidhip_plage, 11},
     {"R_plaidhip_zscore", (DL_FUNC)&R_plaidhip_zscore, 8},
