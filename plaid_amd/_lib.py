@@ -213,6 +213,7 @@ SIGNATURES = {
 # test hooks the library exports without declaring them in include/plaidhip.h (kept out of SIGNATURES, which mirrors it)
 DEBUG_SIGNATURES = {
     "plaidhip_debug_spec_fell_back": [_vp, C.POINTER(_int)],
+    "plaidhip_debug_rank_fallbacks": [_vp, C.POINTER(_i32)],
 }
 
 # return types other than the int status code

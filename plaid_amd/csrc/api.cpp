@@ -36,6 +36,7 @@ int ensure_workspace(plaidhip_ctx* ctx, size_t bytes) {
     PH_HIP(hipFree(ctx->ws));
     ctx->ws = nullptr;
     ctx->ws_bytes = 0;
+    ctx->rank_fb_count[0] = nullptr;   // (the bucket ranker's hand-over counter lived there)
   }
   bytes = (bytes + 4095) & ~(size_t)4095;
   PH_HIP(hipMalloc(&ctx->ws, bytes));
@@ -473,6 +474,26 @@ int plaidhip_debug_spec_fell_back(plaidhip_ctx* ctx, int* out) try {
   PH_HIP(hipMemcpyAsync(&seen, ctx->d_spec, sizeof(seen), hipMemcpyDeviceToHost, ctx->stream));
   PH_HIP(hipStreamSynchronize(ctx->stream));
   *out = seen == ctx->spec_gen ? 1 : 0;
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// Test hook (not part of include/plaidhip.h), read-only: how many columns did the last rank launch of this context hand to
+// the sorting network?  out[0]: the bucket ranker (launch_ranks: columns with a mixed fine bucket of more than 256 keys),
+// out[1]: the value-partitioned ranker (launch_colranks_partitioned: columns with an open interval of more than 20,352
+// keys); -1 where that launcher has not run with a hand-over list (the sorting network ranked everything, nothing was
+// ranked, or the buffer that held the word has been released since).  Waits for the context's stream and reads the device
+// words the launch left; meant to be called directly after the launch (other kernels reuse the workspace the first word
+// lives in).  A partitioned launch ranks its segments with launch_ranks, but its own sorting-network pass reuses that
+// workspace: out[0] is -1 after it.
+int plaidhip_debug_rank_fallbacks(plaidhip_ctx* ctx, int32_t* out) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(out != nullptr, "debug_rank_fallbacks: null out");
+  for (int k = 0; k < 2; ++k) {
+    out[k] = -1;
+    if (ctx->rank_fb_count[k] != nullptr)
+      PH_HIP(hipMemcpyAsync(&out[k], ctx->rank_fb_count[k], sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PH_HIP(hipStreamSynchronize(ctx->stream));
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 

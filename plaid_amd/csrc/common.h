@@ -139,6 +139,10 @@ struct plaidhip_ctx {
   size_t tie_scratch_bytes = 0;
   void* rank_scratch = nullptr;   // value-partitioned ranking of columns beyond the LDS (kernels_rank.hip), grown on demand
   size_t rank_scratch_bytes = 0;
+  // test hook (plaidhip_debug_rank_fallbacks): the device words that count the columns the last launch handed to the sorting
+  // network: [0] launch_ranks (the bucket ranker; lives in ws), [1] launch_colranks_partitioned (lives in rank_scratch);
+  // nullptr: that launcher has not run with a hand-over list, or its buffer has been released since
+  const int32_t* rank_fb_count[2] = {nullptr, nullptr};
   void* kcdf_table = nullptr;     // replaid.gsva.exact, rowtf "gauss": the table of Phi and a counter word (kernels_kcdf.hip), built on first use
   int debug_fail_crossprod = 0;   // test hook (plaidhip_debug_sharded_on_one_device): this context's shard fails in the crossprod phase
   // pinned staging of the pipelined host uploads (multi.cpp): kFeeders feeder threads x 2 buffers, their streams

@@ -313,7 +313,8 @@ static int launch_network(plaidhip_ctx* ctx, const double* Xv, int64_t ldx, int3
                        g_dense, Xp, n, ties, is_signed, power, R, ldr, colmax, (uint64_t*)nullptr,
                        key_slots, Xi_dense, dscratch, col_list, col_count);
   } else {
-    // large columns: keys live in a global scratch slice per workgroup (L2-resident)
+    // large columns: keys live in a global scratch slice per workgroup (L2-resident).  This branch has its OWN grid,
+    // min(n, 2 CU) -- the callers size the key scratch for it -- and ignores grid_cap, also when it walks a hand-over list
     const int grid = n < 2 * ctx->num_cu ? n : 2 * ctx->num_cu;
     const int64_t stride = ((int64_t)max_len + 1) & ~1ll;
     hipLaunchKernelGGL(colranks_f64_kernel<true>, dim3(grid), dim3(1024), scratch, ctx->stream, Xv,
@@ -379,6 +380,12 @@ static int launch_bucket(plaidhip_ctx* ctx, const RankBucketArgs& a, int32_t max
 // longest column the bucket kernel takes: 8 bytes per key + its scratch must fit the CU's LDS
 constexpr int kMaxBucketKeys = (kLdsBytes - kRankMisc) / 8;   // 20,352
 
+// plaidhip_debug_rank_fallbacks reads the hand-over counters of the LAST rank launch: every entry point of this file
+// (launch_colranks_dense_f64 / _csc_f64 / _csc_dense_f64 / _csc_dense_nz_f64) forgets both words first; launch_ranks and
+// launch_colranks_partitioned then note where theirs lies.  The buffers' owners forget the word they free (ensure_workspace,
+// the growth of rank_scratch).
+static void forget_rank_fallbacks(plaidhip_ctx* ctx) { ctx->rank_fb_count[0] = ctx->rank_fb_count[1] = nullptr; }
+
 static int launch_ranks(plaidhip_ctx* ctx, const double* Xv, int64_t ldx, int32_t g_dense,
                         const int32_t* Xp, int32_t n, int32_t max_len, int ties, int is_signed,
                         double power, double* R, int64_t ldr, double* colmax,
@@ -423,6 +430,7 @@ static int launch_ranks(plaidhip_ctx* ctx, const double* Xv, int64_t ldx, int32_
   int32_t* fb_count = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ctx->ws) + fb_off);
   int32_t* fb_list = fb_count + 4;
   PH_HIP(hipMemsetAsync(fb_count, 0, 16, ctx->stream));
+  ctx->rank_fb_count[0] = fb_count;
   RankBucketArgs a{};
   a.Xv = Xv;
   a.ldx = ldx;
@@ -742,6 +750,7 @@ static int launch_colranks_partitioned(plaidhip_ctx* ctx, const double* X, int64
   const size_t need = 2 * a8 + a4 + am + asp + aco + afb;
   if (ctx->rank_scratch_bytes < need) {
     PH_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->rank_fb_count[1] = nullptr;
     if (ctx->rank_scratch) PH_HIP(hipFree(ctx->rank_scratch));
     ctx->rank_scratch = nullptr;
     ctx->rank_scratch_bytes = 0;
@@ -758,6 +767,7 @@ static int launch_colranks_partitioned(plaidhip_ctx* ctx, const double* X, int64
   int32_t* fb_count = reinterpret_cast<int32_t*>(base + 2 * a8 + a4 + am + asp + aco);
   int32_t* fb_list = fb_count + 4;
   PH_HIP(hipMemsetAsync(fb_count, 0, 16, ctx->stream));
+  ctx->rank_fb_count[1] = fb_count;
   for (int64_t c0 = 0; c0 < n; c0 += panel) {
     const int32_t nc = (int32_t)((n - c0) < panel ? (n - c0) : panel);
     const double* Xc = Xp != nullptr ? X : X + c0 * ldx;        // (CSC: the pointers are absolute offsets into @x and R)
@@ -780,8 +790,11 @@ static int launch_colranks_partitioned(plaidhip_ctx* ctx, const double* X, int64
   }
   // columns with an over-full open interval (heavy clusters the sample did not isolate): the sorting network on a global
   // scratch, as before; a persistent grid reads the device-side list
+  // (fb_grid holds for 20,352 < g <= kMaxLdsGenes, where launch_network walks the list with its LDS kernel; beyond, its
+  // global-key branch takes min(n, 2 CU) workgroups whatever it is given -- the key scratch below is sized for that)
   const int fb_grid = n < ctx->num_cu ? n : ctx->num_cu;
   const int64_t stride = ((int64_t)g + 1) & ~1ll;
+  ctx->rank_fb_count[0] = nullptr;   // (the segments' counter lies where the key scratch of the launch below begins)
   const int rcw = ensure_workspace(ctx, (size_t)(n < 2 * ctx->num_cu ? n : 2 * ctx->num_cu) * (size_t)stride * 8);
   if (rcw != PLAIDHIP_OK) return rcw;
   return launch_network(ctx, X, ldx, Xp != nullptr ? 0 : g, Xp, n, g, ties, is_signed, power, R, ldr, colmax, nullptr, nullptr,
@@ -935,6 +948,7 @@ int launch_colnan(plaidhip_ctx* ctx, const double* X, int64_t ldx, const int32_t
 int launch_colranks_dense_f64(plaidhip_ctx* ctx, const double* X, int64_t ldx, int32_t g, int32_t n,
                               int ties, int is_signed, double power, double* R, int64_t ldr,
                               double* colmax) {
+  forget_rank_fallbacks(ctx);
   if (ties >= PLAIDHIP_TIES_FIRST)   // "first" / "last" / "dense": composed from min-rank passes (power 1, no column maximum)
     return launch_colranks_composed(ctx, X, ldx, g, nullptr, n, g, 0, ties, is_signed, R, ldr);
   // columns beyond the bucket ranker's LDS: cut by value into segments it takes (above), unless the context pins a kernel
@@ -946,6 +960,7 @@ int launch_colranks_dense_f64(plaidhip_ctx* ctx, const double* X, int64_t ldx, i
 int launch_colranks_csc_dense_f64(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx,
                                   int32_t g, int32_t n, int ties, int is_signed, double power, double* R,
                                   int64_t ldr, double* colmax) {
+  forget_rank_fallbacks(ctx);
   return launch_ranks(ctx, Xx, 0, g, Xp, n, g, ties, is_signed, power, R, ldr, colmax, Xi);
 }
 
@@ -1030,6 +1045,7 @@ expand_sparse_ranks_kernel(const int32_t* __restrict__ Xp, const int32_t* __rest
 int launch_colranks_csc_dense_nz_f64(plaidhip_ctx* ctx, const int32_t* Xp, const int32_t* Xi, const double* Xx, int32_t g,
                                      int32_t n, int32_t max_col_nnz, int ties, int is_signed, double power,
                                      double* Rx_scratch, double* R, int64_t ldr, double* colmax) {
+  forget_rank_fallbacks(ctx);
   if (n == 0 || g == 0) return PLAIDHIP_OK;
   const int rc = launch_ranks(ctx, Xx, 0, 0, Xp, n, max_col_nnz, ties, is_signed, 1.0, Rx_scratch, 0, nullptr);
   if (rc != PLAIDHIP_OK) return rc;
@@ -1053,6 +1069,7 @@ bool colranks_uses_power_quarters(plaidhip_ctx* ctx, int32_t g) {
 // stream-ordered: the caller states the longest column (include/plaidhip.h), nothing is read back
 int launch_colranks_csc_f64(plaidhip_ctx* ctx, const int32_t* Xp, const double* Xx, int32_t n, int32_t max_col_nnz,
                             int ties, int is_signed, double power, double* Rx, double* colmax) {
+  forget_rank_fallbacks(ctx);
   if (ties >= PLAIDHIP_TIES_FIRST && n > 0) {   // "first" / "last": composed; needs nnz(X) on the host (one read-back)
     int32_t ends[1] = {0};
     int32_t first[1] = {0};

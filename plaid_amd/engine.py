@@ -1013,6 +1013,20 @@ class Context:
         check(self.lib.plaidhip_dev_colranks_csc_f64(self.handle, Xp, Xx, n, int(max_col_nnz), TIES[ties], int(signed),
                                                      power, Rx, colmax))
 
+    def dev_colranks_csc_dense(self, Xp: int, Xi: int, Xx: int, g: int, n: int, R: int, ldr: int, ties="average",
+                               signed=False, power=1.0, colmax: int | None = None):
+        """dense ranks of CSC columns (zeros ranked) by densify-and-rank: columns with any number of stored values"""
+        check(self.lib.plaidhip_dev_colranks_csc_dense_f64(self.handle, Xp, Xi, Xx, int(g), int(n), TIES[ties], int(signed),
+                                                           power, R, int(ldr), colmax))
+
+    def debug_rank_fallbacks(self):
+        """test hook (plaidhip_debug_rank_fallbacks, read-only; waits for the stream): the number of columns the last rank
+        launch of this context handed to the sorting network -- (by the bucket ranker, by the value-partitioned ranker);
+        -1 where that launcher did not run with a hand-over list"""
+        out = (C.c_int32 * 2)()
+        check(self.lib.plaidhip_debug_rank_fallbacks(self.handle, out))
+        return int(out[0]), int(out[1])
+
     def dev_colranks_csc_dense_nz(self, Xp: int, Xi: int, Xx: int, g: int, n: int, max_col_nnz: int, Rx_scratch: int, R: int,
                                   ldr: int, ties="average", signed=False, power=1.0, colmax: int | None = None):
         """dense ranks of CSC columns (zeros ranked) from the ranks of the stored values: any nrow(X); Rx_scratch: Xp[n]
