@@ -1531,6 +1531,104 @@ int plaidhip_fry_finish(int32_t m, int32_t nfit, int32_t q, const double* dres, 
                         const double* ss, const double* sume2, const double* lam1, const double* lamD, const double* trM,
                         const double* froM, const int8_t* mixed, double* out);
 
+/* plaid.roast(X, design, G, contrasts): limma's rotation gene-set test with SAMPLED rotations (Wu et al. 2010) -- the test
+ * that plaid.fry is the closed-form limit of -- for every set, contrast and design.  What it adds to plaid.fry: a mixed test
+ * for any number of samples, and the set statistics mean50 (limma's default for roast), floormean and msq beside mean.  The
+ * form is limma's roast / mroast AS RECALLED, pinned here: the source is not in this tree, so the tests hold the code to these
+ * words restated at 50 digits.  Operands as plaidhip_fry.  For fit f: d = n_f - p >= 1; contrast j
+ * has plaid.limma's logFC_gj, u_j (stdev.unscaled), the gene's RSS_g, and the prior (df0, s0^2) of plaidhip_limma_finish.
+ * limma rotates a gene's effects [beta | rho] (rho = Q2' r, the d residual effects) by random unit vectors R of length
+ * d + 1.  Here the rotation is taken in SAMPLE space: rho . R2 = r . w with w = Q2 R2, and a Gaussian R2 gives w the law of
+ * (I - Q1 Q1') nu for a Gaussian n_f-vector nu; |[beta | rho]|^2 = beta^2 + RSS.  Neither rho, Q2 nor an n x n matrix is
+ * ever made, so there is no cap on the samples.
+ * 1. Universe: a gene that is not ok in the fit (s2 not finite: a NaN or Inf in a used sample) leaves it.  Sets count their
+ *    members inside the universe only: m.
+ * 2. Rotations k = 0 .. nrot - 1 of fit f (counted from 0), shared by every set and contrast of the fit (as romer shares
+ *    them; mroast draws fresh ones per set -- a stated deviation).  Index i = 0 is nu_0, i = c + 1 the used sample c:
+ *      (x0, x1, x2, x3) = Philox4x32-10(counter = (i, k, f, 0x726f6173), key = (seed mod 2^32, seed / 2^32))
+ *      u1 = (((x0 2^32 + x1) >> 11) + 1) 2^-53,   u2 = ((x2 2^32 + x3) >> 11) 2^-53
+ *      nu_i = sqrt(-2 log(u1)) cos(2 pi u2)                       (Box-Muller, the cosine branch)
+ *      a_k = sum_c Q1[c, k] nu_c ascending c from 0.0;  wt_c = nu_c - (sum_k Q1[c, k] a_k ascending k from 0.0)
+ *      s = sqrt(nu_0^2 + sum_c wt_c^2 ascending),   r0 = nu_0 / s,   w_c = wt_c / s;   0.0 on the samples the fit leaves out.
+ *    The sum under the root is kept in double-double -- every square split exactly by an fma, the terms added by two-sum,
+ *    fp64 operations only -- and s is sqrt(hi) corrected once by (hi - s s + lo) / (2 s): the rounded root of the sum, the
+ *    same bits on every IEEE host.
+ *    Q1 is plaid.limma's thin Q of the design.  A draw is a function of (seed, f, k, i) alone.  They are made on the host
+ *    (plaidhip_roast_rotations); W is (n + 1) x nrot row-major: W[0][k] = r0, W[c + 1][k] = w_c.  Every entry also takes the
+ *    caller's own W (rotations != NULL: nfit matrices), as they are.
+ * 3. The rotated moderated statistic of gene g under rotation k, beta = logFC_gj / u_j (roast.h, one copy for all):
+ *      B = beta r0 rounded, then fma(r_gc, w_c, .) over ALL samples c ascending (r_gc: plaid.fry's residual chain with a
+ *          divisor of 1.0; 0.0 on a sample left out)
+ *      s2r = (beta beta + RSS_g - B B) / d, and 0.0 unless that is > 0
+ *      post = (df0 s0^2 + d s2r) / (df0 + d);   df0 infinite: s0^2;   df0 = 0 (fewer than two ok genes): s2r
+ *      t = B / sqrt(post)                         IEEE decides x / 0
+ *    The OBSERVED column is plaid.limma's moderated t itself, bit for bit -- not a rotation with r0 = 1.
+ * 4. z-score on nu = min(df0 + d, 10,000) degrees of freedom (the winsorised df; also what makes an infinite df0 finite).
+ *    zscore = 0 ("hill", the default), Hill's (1970) form: A = nu - 1/2, C = 48 A A, y = A log1p(t t / nu),
+ *      z = sign(t) sqrt(y) (1 + ((y + 3) + (((-0.4 y - 3.3) y - 24) y - 85.5) / ((0.8 y y + 100) + C)) / C)
+ *    every operation rounded on its own in this order.  zscore = 1 ("none"): z = t.  limma's exact qnorm(pt()) is not
+ *    offered (an incomplete beta per element).  A gene outside the universe has beta = NaN and so z = NaN; no set reads it.
+ * 5. The set statistic, four sides (down, up, upordown, mixed) over the m members' z; upordown = up if up > down, else
+ *    down.  set_statistic 0 "mean": up = S / m, down = -S / m with S = sum z, mixed = sum |z| / m.  1 "floormean":
+ *    down = sum max(-z, 0) / m, up = sum max(z, 0) / m, mixed = sum max(|z|, sqrt(q)) / m with q = qchisq(0.5, 1), sqrt(q) =
+ *    0.67448975019608171.  2 "msq": down = sum over z < 0 of z z / m, up = sum over z > 0 of z z / m, mixed = sum z z / m.
+ *    3 "mean50" (the default): h = floor(m / 2) + 1; up is the mean of the h largest z, down of the h largest -z, mixed of
+ *    the h largest |z|, pinned without a sort: the keys are z + 0.0, (-z) + 0.0, |z| (no -0.0 among them), tau the h-th
+ *    largest key, and the side is ((sum of the keys > tau in the set's own order) + (h - #{> tau}) tau) / h.  A NaN among a
+ *    set's z makes its three mean50 sides NaN.  Every sum is ONE accumulator from 0.0 over the members in the order of
+ *    Gi (the squares rounded first), so the sides are reproducible bit for bit from the z.  mean50 holds a set's z in LDS:
+ *    a set with more than PLAIDHIP_ROAST_MEAN50_MAX members in the universe has NaN p-values under mean50 and raises the
+ *    hyper flag; the other three statistics take any m.
+ * 6. b = #{k : stat_k >= stat_obs} per side (exact integers), p = (b + 1) / (nrot + 1).  PropDown, PropUp: the shares of the
+ *    members with observed z < -sqrt(2), z > sqrt(2).  Direction is Up (+1) where p_up < p_down, else Down (-1).  PValue is
+ *    the upordown side, PValue.Mixed the mixed side.  FDR, FDR.Mixed: Benjamini-Hochberg over the sets of each (fit,
+ *    contrast); with midp (the default) taken on p - 0.5 / (nrot + 1) and then raised to at least p.  m = 0: NaN but NGenes.
+ * out: m x 8 x q x nfit doubles, column-major: NGenes, PropDown, PropUp, Direction, PValue, FDR, PValue.Mixed, FDR.Mixed;
+ * contrast j of fit f at out + (f * q + j) * 8 * m.  hyper: nfit x 7 doubles: plaid.limma's four (df.residual, df.prior,
+ * s2.prior, n_ok), the universe's size, nrot, and 1.0 where a set was above the mean50 cap (else 0.0).
+ * g == 0, nfit == 0, q == 0 or m == 0: PLAIDHIP_OK with nothing written.
+ * Argument errors, all PLAIDHIP_EINVAL and all found on the host before any device is touched: those of plaidhip_fry in
+ * their order without its standardize (named "roast:"); then set_statistic outside 0..3; zscore outside 0..1; nrot < 1;
+ * nrot > PLAIDHIP_ROAST_MAX_ROTATIONS.
+ * On the device (kernels_roast.hip): roast_rotate_kernel fuses steps 3 and 4 and writes z as [tile of 64 rotations][g][64],
+ * in chunks of whole tiles of at most PLAIDHIP_ROAST_Z_BYTES; roast_stat_kernel / roast_mean50_kernel make step 5 with a
+ * lane per rotation and add b with integer atomics; the observed statistics come from the same kernels on a one-column z.
+ * plaidhip_roast_multi shards the ROTATIONS in whole tiles of 64: device k of ndev takes tiles [T k / ndev, T (k + 1) / ndev)
+ * of the T = ceil(nrot / 64).  Every device takes all of X and runs plaid.limma's two cheap passes itself, in the operations
+ * and the order of the one-device call, so all hold the same effects, RSS and observed statistics; a z is made whole on one
+ * device by one chain, and the int32 counts are added on the host: every sharding has the one-device bits.  The set sizes,
+ * PropDown / PropUp and hyper come from the first device.  A device without a tile (ndev > T) does nothing.
+ *   plaidhip_dev_roast_rotate: steps 3 and 4 on device pointers.  Rz: the raw residuals [n][ldz]; beta, rss: rows each; W:
+ *     (n + 1) x ldw row-major with ldw a multiple of 16 that is >= nrot; chunk: rotations per launch (a multiple of 64; 0:
+ *     all at once); Z: ceil(nrot / 64) x rows x 64 doubles, the padding of the last tile not written.
+ *   plaidhip_dev_roast_stats: step 5 on device pointers from that Z.  Gp, Gi: the pattern of the members INSIDE the
+ *     universe; stat: m x nrot x 4 (or NULL); obs: m x 4 and cnt: m x 4 int32, raised by b (both or neither).
+ *   plaidhip_roast_rotations (host only): step 2 for one design and fit number `fit` (from 0): W, (n + 1) x nrot.
+ *   plaidhip_roast_finish (host only): step 6 from cnt (int32, 4 x m x q x nfit), msize (m x nfit), ndown and nup (m x q x
+ *     nfit: the members beyond -+sqrt(2)).
+ * Not offered: per-set rotations (mroast's), romer, gene or array weights, trend.var, robust, a dgCMatrix X, na = "fit"
+ * rows, the exact z-score. */
+#define PLAIDHIP_ROAST_MEAN50_MAX 16384        /* members: one rotation of z at an odd stride and 3 KiB beside it is 131 KiB of the CU's 160 */
+#define PLAIDHIP_ROAST_MAX_ROTATIONS 1048576
+#define PLAIDHIP_ROAST_Z_BYTES ((int64_t)256 << 20)
+int plaidhip_roast(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                   const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                   int set_statistic, int zscore, int32_t nrot, uint64_t seed, int midp, const double* rotations, double* out,
+                   double* hyper);
+int plaidhip_roast_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const double* design, int32_t p,
+                         int32_t nfit, const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi,
+                         int32_t m, int set_statistic, int zscore, int32_t nrot, uint64_t seed, int midp,
+                         const double* rotations, double* out, double* hyper);
+int plaidhip_dev_roast_rotate(plaidhip_ctx* ctx, const double* Rz, int64_t ldz, int32_t rows, int32_t n, const double* beta,
+                              const double* rss, const double* W, int64_t ldw, int32_t nrot, double d, double df0, double s02,
+                              int zscore, int32_t chunk, double* Z);
+int plaidhip_dev_roast_stats(plaidhip_ctx* ctx, const double* Z, int32_t rows, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                             int set_statistic, int32_t nrot, double* stat, const double* obs, int32_t* cnt);
+int plaidhip_roast_rotations(const double* design, int32_t n, int32_t p, const int8_t* use, int32_t fit, int32_t nrot,
+                             uint64_t seed, double* W);
+int plaidhip_roast_finish(int32_t m, int32_t nfit, int32_t q, int32_t nrot, int set_statistic, int midp, const int32_t* cnt,
+                          const double* msize, const double* ndown, const double* nup, double* out);
+
 /* ---- GMT text -> 0/1 membership matrix on the host (no device involved) --------------------------
  * Replaces read.gmt() R/gmt-utils.R:99-125 and gmt2mat() R/gmt-utils.R:19-66 (50.9 s for a 50k-set
  * collection in R, experiments/benchmark/benchmark-plaid.R:42).  Objects are owned by the library

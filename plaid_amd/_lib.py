@@ -192,6 +192,14 @@ SIGNATURES = {
     "plaidhip_fry_divisors": [_i32, _i32, _i32, _vp, _vp, _int, _vp],
     "plaidhip_fry_residual_row": [_i32, _i32, _vp, _vp, _vp, _vp, _f64, _vp],
     "plaidhip_fry_finish": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_roast": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _int, _int, _i32, C.c_uint64, _int, _vp,
+                       _vp, _vp],
+    "plaidhip_roast_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _int, _int, _i32,
+                             C.c_uint64, _int, _vp, _vp, _vp],
+    "plaidhip_dev_roast_rotate": [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f64, _int, _i32, _vp],
+    "plaidhip_dev_roast_stats": [_vp, _vp, _i32, _vp, _vp, _i32, _int, _i32, _vp, _vp, _vp],
+    "plaidhip_roast_rotations": [_vp, _i32, _i32, _vp, _i32, _i32, C.c_uint64, _vp],
+    "plaidhip_roast_finish": [_i32, _i32, _i32, _i32, _int, _int, _vp, _vp, _vp, _vp, _vp],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],
     # host-only GMT text path (gmt.cpp)
     "plaidhip_gmt_read": [C.c_char_p, _int, _i64, C.POINTER(_vp)],

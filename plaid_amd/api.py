@@ -1181,6 +1181,93 @@ def plaid_fry_contrasts(X, Y, G, B=None, standardize="posterior.sd", minSize=1, 
     return tables, {nm: dict(zip(FRY_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
 
 
+_ROAST_NAMES = ["NGenes", "PropDown", "PropUp", "Direction", "PValue", "FDR", "PValue.Mixed", "FDR.Mixed"]
+_ROAST_SORT = {"none": None, "directional": 4, "mixed": 6}
+
+
+def _roast_table(tab, rn, sort_by):
+    """sets x 8 of the library -> the NamedMatrix plaid.roast returns (Direction +1 Up, -1 Down), ordered by `sort_by`:
+    "directional" (PValue increasing), "mixed" (PValue.Mixed increasing) or "none"; stable, NaN last"""
+    rn = list(rn)
+    col = _ROAST_SORT[sort_by]
+    if col is not None:
+        o = np.argsort(tab[:, col], kind="stable")
+        tab, rn = tab[o, :], [rn[k] for k in o]
+    return NamedMatrix(np.ascontiguousarray(tab), rn, _ROAST_NAMES)
+
+
+def plaid_roast(X, design, G, contrasts=None, use=None, set_statistic="mean50", nrot=1999, seed=1, zscore="hill", midp=True,
+                rotations=None, minSize=1, maxSize=None, sort_by="directional", ctx: Context | None = None):
+    """plaid.roast(): limma's rotation gene-set test with sampled rotations (roast / mroast as pinned in
+    include/plaidhip.h) of every set of G on the expression X for one design; the operands are plaid_fry's.  What it adds
+    to plaid_fry: a mixed test for any number of samples, and the set statistics "mean50" (the default), "floormean" and
+    "msq" beside "mean".  The rotations are drawn in sample space from `seed` (Philox4x32-10) and shared by every set and
+    contrast -- or given: rotations, (samples + 1) x nrot with row 0 = r0.  zscore: "hill" (the default) or "none".  p =
+    (b + 1) / (nrot + 1); midp takes the FDR on p - 0.5 / (nrot + 1).  A gene with a NaN or Inf in a used sample leaves the
+    universe; under "mean50" a set with more than 16,384 members there has NaN p-values (hyper["mean50.capped"] = 1).
+    Returns (tables, hyper): contrast name -> NamedMatrix (sets x [NGenes, PropDown, PropUp, Direction (+1 Up, -1 Down),
+    PValue, FDR, PValue.Mixed, FDR.Mixed]) ordered by `sort_by` ("directional", "mixed" or "none"; stable, NaN last), and
+    plaid_limma's four values, n.genes, nrot and mean50.capped.
+    Not offered: per-set rotations, romer, gene or array weights, trend.var, robust, a sparse X, na = "fit"."""
+    from .engine import ROAST_HYPER, check_roast_options
+    check_roast_options(set_statistic, zscore)
+    if sort_by not in _ROAST_SORT:   # (before the device)
+        raise ValueError(f"plaid.roast: sort_by must be one of {sorted(_ROAST_SORT)}")
+    Xs, Gp, Gi, rn = _camera_sets("plaid.roast", X, G, minSize, maxSize)
+    Dn = design if isinstance(design, NamedMatrix) else None
+    Dv = np.asarray(Dn.values if Dn is not None else design, dtype=np.float64)
+    if Dv.ndim != 2:
+        raise ValueError("plaid.roast: design must be samples x coefficients")
+    coef = list(Dn.colnames) if Dn is not None else [f"coef{k + 1}" for k in range(Dv.shape[1])]
+    if contrasts is None:
+        Kv, names = None, coef
+    else:
+        Kn = contrasts if isinstance(contrasts, NamedMatrix) else None
+        Kv = np.asarray(Kn.values if Kn is not None else contrasts, dtype=np.float64)
+        Kv = Kv[:, None] if Kv.ndim == 1 else Kv
+        names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
+    ctx = ctx or default_context()
+    out, hyper = ctx.roast(Xs, Dv, Gp, Gi, use, Kv, set_statistic, nrot, seed, zscore, midp, rotations)
+    tables = {nm: _roast_table(out[:, :, j, 0], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, dict(zip(ROAST_HYPER, (float(x) for x in hyper[0])))
+
+
+def plaid_roast_contrasts(X, Y, G, B=None, set_statistic="mean50", nrot=1999, seed=1, zscore="hill", midp=True, rotations=None,
+                          minSize=1, maxSize=None, sort_by="directional", ctx: Context | None = None):
+    """plaid.roast.contrasts(): plaid_roast for every column of the contrast matrix Y in one call, with the designs of
+    plaid_limma_contrasts: contrast j fits [1, Y[, j], B] on the samples with a label and tests the sets on the coefficient
+    of Y[, j].  X is uploaded once.  Contrast j is fit number j: its generated rotations are those of (seed, j), so its
+    table has the bits of plaid_roast on that contrast's design and samples only for j = 0 -- or for any j where
+    `rotations` ((samples + 1) x nrot x contrasts) are given.  Returns (tables, hyper) keyed by contrast name."""
+    from .engine import ROAST_HYPER, check_roast_options, contrast_labels
+    check_roast_options(set_statistic, zscore)
+    if sort_by not in _ROAST_SORT:
+        raise ValueError(f"plaid.roast: sort_by must be one of {sorted(_ROAST_SORT)}")
+    Xs, Gp, Gi, rn = _camera_sets("plaid.roast", X, G, minSize, maxSize)
+    n = Xs.shape[1]
+    Yn = Y if isinstance(Y, NamedMatrix) else None
+    lab = contrast_labels(Yn.values if Yn is not None else Y, n)
+    if not np.all(np.isin(lab, (0, 1, -1))):
+        raise ValueError("elements of Y must be 0, 1 or NA")
+    ncon = lab.shape[1]
+    names = list(Yn.colnames) if Yn is not None and Yn.colnames is not None else [str(j + 1) for j in range(ncon)]
+    Bv = np.zeros((n, 0)) if B is None else np.asarray(B.values if isinstance(B, NamedMatrix) else B, dtype=np.float64)
+    Bv = Bv[:, None] if Bv.ndim == 1 else Bv
+    if Bv.ndim != 2 or Bv.shape[0] != n:
+        raise ValueError("B must have one row per column of X")
+    p = 2 + Bv.shape[1]
+    D = np.empty((n, p, ncon), order="F")
+    D[:, 0, :] = 1.0
+    D[:, 1, :] = np.where(lab == 1, 1.0, 0.0)
+    D[:, 2:, :] = Bv[:, :, None]
+    K = np.zeros((p, 1))
+    K[1, 0] = 1.0
+    ctx = ctx or default_context()
+    out, hyper = ctx.roast(Xs, D, Gp, Gi, lab != -1, K, set_statistic, nrot, seed, zscore, midp, rotations)
+    tables = {nm: _roast_table(out[:, :, 0, j], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, {nm: dict(zip(ROAST_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
+
+
 def plaid_intergenecor(X, design, G, use=None, minSize=1, maxSize=None, ctx: Context | None = None):
     """plaid.intergenecor(): limma's interGeneCorrelation(X[set, ], design) for every set of G at once -- the variance
     inflation factor of the set's mean, estimated from the residuals of its genes, and the mean pairwise correlation

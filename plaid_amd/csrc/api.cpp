@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "call.h"
+#include "roast.h"
 
 namespace plaidhip {
 
@@ -1454,6 +1455,72 @@ int plaidhip_dev_fry_eigen(plaidhip_ctx* ctx, const double* M, int32_t dim, int6
   if (nprob == 0) return PLAIDHIP_OK;
   PH_REQUIRE(M && Dk && lam1 && lamD && sweeps && converged, "fry_eigen: null argument");
   return launch_fry_eigen(ctx, M, nullptr, nullptr, nullptr, dim, 1, nprob, Dk, lam1, lamD, sweeps, converged);
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.roast: the one-device form of the sharded engine (shard_limma.cpp: limma_worker with kRoast, roast_tail)
+int plaidhip_roast(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                   const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                   int set_statistic, int zscore, int32_t nrot, uint64_t seed, int midp, const double* rotations, double* out,
+                   double* hyper) try {
+  return dispatch(on_context(ctx), roast_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic, zscore, nrot, seed,
+                                              midp, rotations, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the device passes of plaid.roast on device pointers (kernels_roast.hip)
+int plaidhip_dev_roast_rotate(plaidhip_ctx* ctx, const double* Rz, int64_t ldz, int32_t rows, int32_t n, const double* beta,
+                              const double* rss, const double* W, int64_t ldw, int32_t nrot, double d, double df0, double s02,
+                              int zscore, int32_t chunk, double* Z) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ldz >= rows && n <= PLAIDHIP_LIMMA_MAX_SAMPLES,
+             "roast_rotate: bad shape rows=%d n=%d ldz=%lld (n <= %d)", rows, n, (long long)ldz, PLAIDHIP_LIMMA_MAX_SAMPLES);
+  PH_REQUIRE(nrot >= 1 && nrot <= PLAIDHIP_ROAST_MAX_ROTATIONS, "roast_rotate: nrot = %d (1 <= nrot <= %d)", nrot,
+             PLAIDHIP_ROAST_MAX_ROTATIONS);
+  PH_REQUIRE(ldw % 16 == 0 && ldw >= nrot, "roast_rotate: ldw = %lld (a multiple of 16, at least nrot = %d)", (long long)ldw, nrot);
+  PH_REQUIRE(chunk >= 0 && chunk % 64 == 0, "roast_rotate: chunk = %d rotations (a multiple of 64, or 0: all)", chunk);
+  PH_REQUIRE(zscore >= 0 && zscore <= 1, "roast_rotate: zscore = %d (0 hill, 1 none)", zscore);
+  PH_REQUIRE(d >= 1.0, "roast_rotate: df.residual = %g", d);
+  if (rows == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(beta && rss && W && Z && (n == 0 || Rz), "roast_rotate: null argument");
+  const RoastFit rf = roast_fit(d, df0, s02);
+  const int32_t step = chunk == 0 ? (nrot + 63) / 64 * 64 : chunk;
+  for (int32_t k0 = 0; k0 < nrot; k0 += step)
+    PH_TRY(launch_roast_rotate(ctx, Rz, ldz, rows, n, beta, rss, W, ldw, k0, std::min(nrot, k0 + step), rf, zscore,
+                               Z + (size_t)(k0 / 64) * rows * 64));
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_roast_stats(plaidhip_ctx* ctx, const double* Z, int32_t rows, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                             int set_statistic, int32_t nrot, double* stat, const double* obs, int32_t* cnt) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && m >= 0, "roast_stats: bad dims rows=%d m=%d", rows, m);
+  PH_REQUIRE(set_statistic >= 0 && set_statistic <= 3, "roast_stats: set_statistic = %d (0 mean, 1 floormean, 2 msq, 3 mean50)",
+             set_statistic);
+  PH_REQUIRE(nrot >= 1 && nrot <= PLAIDHIP_ROAST_MAX_ROTATIONS, "roast_stats: nrot = %d (1 <= nrot <= %d)", nrot,
+             PLAIDHIP_ROAST_MAX_ROTATIONS);
+  PH_REQUIRE((obs == nullptr) == (cnt == nullptr), "roast_stats: obs and cnt go together");
+  if (m == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Z && Gp && Gi && (stat || cnt), "roast_stats: null argument");
+  int32_t cls_cnt[3] = {0, 0, 0};
+  DevBuf dsel;
+  std::vector<int32_t> gp, sel;
+  if (set_statistic == PLAIDHIP_ROAST_STAT_MEAN50) {   // the size classes need the set sizes on the host
+    gp.resize((size_t)m + 1);
+    sel.resize((size_t)m);
+    PH_HIP(hipMemcpyAsync(gp.data(), Gp, ((size_t)m + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    size_t at = 0;
+    for (int cls = 0; cls < 3; ++cls)
+      for (int32_t s = 0; s < m; ++s)
+        if (roast_mean50_class(gp[(size_t)s + 1] - gp[(size_t)s]) == cls) {
+          sel[at++] = s;
+          ++cls_cnt[cls];
+        }
+    PH_TRY(dsel.alloc((size_t)m * 4));
+    PH_HIP(hipMemcpyAsync(dsel.p, sel.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  PH_TRY(launch_roast_stats(ctx, Z, rows, Gp, Gi, m, set_statistic, 0, nrot, nrot, dsel.as<int32_t>(), cls_cnt, stat, obs, cnt));
+  PH_HIP(hipStreamSynchronize(ctx->stream));   // (dsel is released on return)
+  return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
 // the generated placements of plaid.gsea themselves, slab by slab as gsea_worker generates them

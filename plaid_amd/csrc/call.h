@@ -12,7 +12,7 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21, kFry = 22
+  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21, kFry = 22, kRoast = 23
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker's three
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -129,6 +129,12 @@ struct Call : Operands {
   int standardize = 0;
   std::vector<double> lm_Q2;
   std::vector<int64_t> lm_Q2_off;
+  // plaid.roast (kRoast): plaid.camera's operands; the set statistic and z-score (roast.h), nrot, seed, midp, the caller's
+  // rotations (nfit x (n + 1) x nrot, or null: generated); out m x 8 x q x nfit, hyper nfit x 7
+  int set_statistic = 0, zscore = 0, midp = 1;
+  int32_t nrot = 0;
+  uint64_t roast_seed = 0;
+  const double* rotations = nullptr;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -426,6 +432,24 @@ inline Call fry_call(const double* X, int32_t g, int32_t n, const double* design
   k.Gi = Gi;
   k.m = m;
   k.standardize = standardize;
+  return k;
+}
+
+// limma's rotation set test with sampled rotations as pinned in include/plaidhip.h: plaidhip_roast
+inline Call roast_call(const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                       const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m, int set_statistic,
+                       int zscore, int32_t nrot, uint64_t seed, int midp, const double* rotations, double* out, double* hyper) {
+  Call k = limma_call(X, g, n, design, p, nfit, use, K, q, out, hyper);
+  k.method = kRoast;
+  k.Gp = Gp;
+  k.Gi = Gi;
+  k.m = m;
+  k.set_statistic = set_statistic;
+  k.zscore = zscore;
+  k.nrot = nrot;
+  k.roast_seed = seed;
+  k.midp = midp;
+  k.rotations = rotations;
   return k;
 }
 

@@ -408,6 +408,20 @@ int launch_fry_gram(plaidhip_ctx* ctx, const double* d_rho, const double* d_e, i
 int launch_fry_eigen(plaidhip_ctx* ctx, const double* d_M, const double* d_C, const double* d_b, const double* d_a, int32_t dim,
                      int32_t q, int64_t nprob, const int32_t* d_Dk, double* d_lam1, double* d_lamD, int32_t* d_sweeps,
                      int32_t* d_conv);
+// kernels_roast.hip (plaid.roast): z of rotations k0 .. k1 - 1 (k0 a multiple of 64) as [tile from k0 / 64][rows][64]; the
+// observed one-column tile; the four sides of every (set, rotation) and / or the counts against d_obs (mean50: d_sel and
+// class_cnt[3] from roast.h's size classes)
+struct RoastFit;
+int launch_roast_rotate(plaidhip_ctx* ctx, const double* Rz, int64_t ldz, int32_t rows, int32_t n, const double* d_beta,
+                        const double* d_rss, const double* d_W, int64_t ldw, int32_t k0, int32_t k1, RoastFit fit, int zscore,
+                        double* Z);
+int launch_roast_observed(plaidhip_ctx* ctx, const double* d_t, int32_t rows, double nu, int zscore, double* Z);
+int launch_roast_stats(plaidhip_ctx* ctx, const double* Z, int32_t rows, const int32_t* d_Gp, const int32_t* d_Gi, int32_t m,
+                       int set_statistic, int32_t k0, int32_t k1, int32_t nrot, const int32_t* d_sel, const int32_t* class_cnt,
+                       double* d_stat, const double* d_obs, int32_t* d_cnt);
+// stats.cpp (plaid.roast): W ((n + 1) x nrot row-major) of one fit from its thin Q
+void roast_rotations(const double* Q, int32_t n, int32_t p, const int8_t* use, int32_t fit, int32_t nrot, uint64_t seed,
+                     double* W);
 // stats.cpp: eBayes and the tables of plaid.limma.  drow ([nfit][rows], NaN: the row is not fitted) and urow ([nfit q][rows])
 // null: every row of fit f has nf[f] - p and u[f q + j] (plaidhip_limma_finish); hyper has hcols (4 or 5) values per fit
 int limma_finish_rows(const char* what, int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,

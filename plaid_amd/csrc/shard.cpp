@@ -391,6 +391,7 @@ Route route(const Call& c) {
     case kLimma: return {true, limma_empty, limma_prepare, limma_worker, limma_tail};
     case kCamera: return {true, limma_empty, limma_prepare, limma_worker, camera_tail};
     case kFry: return {true, limma_empty, limma_prepare, limma_worker, fry_tail};
+    case kRoast: return {false, limma_empty, roast_prepare, roast_worker, roast_tail};
   }
   return {false, no_scores, nullptr, nullptr, nullptr};   // (no method at all: check_call has refused it)
 }

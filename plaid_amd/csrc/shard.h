@@ -107,6 +107,13 @@ struct Shared {
     std::vector<double> cg;
     std::vector<std::vector<double>> rho;
   } fry;
+  // plaid.roast: the generated rotations of every fit ((n + 1) x nrot; empty: the caller's), the counts added over the shards
+  // ([nfit q][m][4]), and from shard 0 the set sizes, the members beyond -+sqrt(2) and the hyperparameters
+  struct Roast {
+    std::vector<std::vector<double>> W;
+    std::vector<int32_t> cnt;
+    std::vector<double> msize, ndown, nup, hyper;
+  } roast;
   // plaid.gsea: the block partials [nblk][c][6][m] of all permutation blocks, each shard writing its own blocks; multilevel:
   // (qhat, log2err, stage, status) of every (list, set), NaN without a ruler, each shard writing the sets of its own rulers
   struct Gsea { std::vector<double> part, ml; } gsea;
@@ -232,6 +239,9 @@ void limma_prepare(Shared& sh, const Call& c, int ndev);
 int limma_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 int camera_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 int fry_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
+int roast_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);
+void roast_prepare(Shared& sh, const Call& c, int ndev);
+int roast_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 
 // ---- what the engine knows about a method on the run side (shard.cpp) --------------------------------------------------------
 struct Route {

@@ -1,5 +1,6 @@
 // plaid.limma and plaid.camera on the sharded engine (shard.cpp).
 #include "shard.h"
+#include "roast.h"
 
 namespace plaidhip {
 
@@ -309,7 +310,7 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 }
 
 bool limma_empty(const Call& c) {
-  return c.g == 0 || c.nfit == 0 || c.nq == 0 || ((c.method == kCamera || c.method == kFry) && c.m == 0);
+  return c.g == 0 || c.nfit == 0 || c.nq == 0 || ((c.method == kCamera || c.method == kFry || c.method == kRoast) && c.m == 0);
 }
 
 void limma_prepare(Shared& sh, const Call& c, int ndev) {
@@ -549,6 +550,193 @@ int fry_tail(plaidhip_ctx* ctx, const Call& c, Shared& sh) {
     c.hyper[7 * (size_t)f + 5] = dres[(size_t)f] + 1.0;
     c.hyper[7 * (size_t)f + 6] = mixed[(size_t)f] ? 1.0 : 0.0;
   }
+  return PLAIDHIP_OK;
+}
+
+// plaid.roast (include/plaidhip.h: plaidhip_roast).  The ROTATIONS are dealt to the shards in whole tiles of 64: shard k
+// takes tiles [ntile k / ndev, ntile (k + 1) / ndev).  Every shard takes all of X and runs plaid.limma's two passes itself,
+// with the operations and the order of the one-device call (a 0.0 seed, then the block partials ascending), so every shard
+// holds the same effects, RSS, tables and observed statistics; no rendezvous.  Then, fit by fit: the raw residuals of all
+// samples (kernels_fry.hip's pass with a divisor of 1.0) and, per contrast, the observed statistics, z of the shard's
+// rotations in chunks of whole tiles and the counts against the observed statistics (kernels_roast.hip).  A z is made whole
+// on one device by one chain, and the counts are integers added under the lock: every sharding has the one-device bits.
+// Shard 0 also leaves the hyperparameters, the set sizes and the members beyond -+sqrt(2) for roast_tail.
+int roast_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) {
+  Shard s(ctx, c, ndev, k, sh);
+  const int32_t g = c.g, m = c.m, nfit = c.nfit, q = c.nq, p = c.ncoef, n = c.n, nrot = c.nrot;
+  const size_t R = (size_t)g, M = (size_t)m, ncol = (size_t)nfit * q;
+  const int64_t ld = even_ld(g), W1 = (int64_t)nfit * (p + 1);
+  const int64_t ntile = ((int64_t)nrot + 63) / 64, ldw = ((int64_t)nrot + 15) / 16 * 16;
+  const int64_t t_lo = ntile * k / ndev, t_hi = ntile * (k + 1) / ndev;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  s.step([&]() -> int {
+    if (ctx->debug_fail_crossprod) { set_error("injected failure in the crossprod phase (test hook)"); return PLAIDHIP_EHIP; }
+    PH_HIP(hipSetDevice(ctx->device));
+    if (t_hi == t_lo && k != 0) return PLAIDHIP_OK;   // (no tile: nothing to add; shard 0 still makes what the tail reads)
+    // ---- plaid.limma's two passes over all samples, as the one-device call makes them ----
+    CtxBuf dA{ctx, 0}, dR{ctx, 3}, dZ{ctx, 4};
+    DevBuf dQ, duse, dinvn, dmask, dwt, dws, drows;
+    PH_TRY(drows.alloc((size_t)W1 * R * 3 * 8));   // [a 0.0 seed | the effects | the RSS]
+    double *d_seed = drows.as<double>(), *d_E = d_seed + W1 * R, *d_rss = d_E + W1 * R;
+    PH_HIP(hipMemsetAsync(d_seed, 0, (size_t)W1 * R * 8, ctx->stream));
+    PH_TRY(dQ.alloc(c.lm_Q.size() * 8));
+    PH_HIP(hipMemcpyAsync(dQ.p, c.lm_Q.data(), c.lm_Q.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (c.use != nullptr) {
+      PH_TRY(duse.alloc((size_t)n * nfit));
+      PH_HIP(hipMemcpyAsync(duse.p, c.use, (size_t)n * nfit, hipMemcpyHostToDevice, ctx->stream));
+    }
+    PH_TRY(dinvn.alloc((size_t)nfit * 8));
+    PH_HIP(hipMemcpyAsync(dinvn.p, c.lm_invn.data(), (size_t)nfit * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dmask.alloc((size_t)lmfit_mask_bytes(n, W1)));
+    PH_TRY(dwt.alloc((size_t)lmfit_weight_bytes(n, W1)));
+    PH_TRY(launch_lmfit_masks(ctx, dQ.as<double>(), c.use != nullptr ? duse.as<int8_t>() : nullptr, dinvn.as<double>(), n, p, nfit,
+                              dmask.p, dwt.as<double>()));
+    PH_TRY(dws.alloc((size_t)row_design_ws_doubles(g, n, W1) * 8));
+    PH_TRY(dA.alloc((size_t)ld * n * 8));
+    PH_TRY(upload_pipelined(ctx, dA.as<char>(), (size_t)ld * 8, reinterpret_cast<const char*>(c.X), R * 8, n, nullptr));
+    PH_TRY(launch_row_design_effects(ctx, dA.as<double>(), ld, g, n, dmask.p, dwt.as<double>(), (int32_t)W1, dws.as<double>()));
+    PH_TRY(launch_reduce_blocks_flat(ctx, dws.as<double>(), W1 * g, n, d_seed, d_E));
+    PH_TRY(launch_row_design_rss(ctx, dA.as<double>(), ld, g, n, dQ.as<double>(), dmask.p, p, nfit, d_E, dws.as<double>()));
+    PH_TRY(launch_reduce_blocks_flat(ctx, dws.as<double>(), (int64_t)nfit * g, n, d_seed, d_rss));
+    std::vector<double> E((size_t)W1 * R), rss((size_t)nfit * R), tab(R * 6 * ncol), hyp((size_t)nfit * 4);
+    PH_HIP(hipMemcpyAsync(E.data(), d_E, E.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipMemcpyAsync(rss.data(), d_rss, rss.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    PH_TRY(plaidhip_limma_finish(g, p, nfit, q, E.data(), rss.data(), c.lm_nf.data(), c.lm_v.data(), c.lm_u.data(), tab.data(),
+                                 hyp.data()));
+    // ---- the universe of every fit, and the pattern of the members inside it ----
+    std::vector<double> cg(R * nfit);
+    std::vector<std::vector<int32_t>> Gpf((size_t)nfit), Gif((size_t)nfit);
+    for (int32_t f = 0; f < nfit; ++f) {
+      const double* sigma2 = tab.data() + ((size_t)f * q * 6 + 5) * R;   // (of the fit's first contrast: NaN = not ok)
+      double uni = 0.0, capped = 0.0;
+      for (size_t r = 0; r < R; ++r) {
+        cg[R * f + r] = std::isnan(sigma2[r]) ? nan : 1.0;
+        uni += std::isnan(sigma2[r]) ? 0.0 : 1.0;
+      }
+      std::vector<int32_t>& gp = Gpf[(size_t)f];
+      std::vector<int32_t>& gi = Gif[(size_t)f];
+      gp.assign(M + 1, 0);
+      for (int32_t st = 0; st < m; ++st) {
+        for (int32_t e = c.Gp[st]; e < c.Gp[st + 1]; ++e)
+          if (!std::isnan(sigma2[c.Gi[e]])) gi.push_back(c.Gi[e]);
+        gp[(size_t)st + 1] = (int32_t)gi.size();
+        const int32_t ms = gp[(size_t)st + 1] - gp[(size_t)st];
+        if (k == 0) sh.roast.msize[M * f + st] = (double)ms;
+        if (c.set_statistic == PLAIDHIP_ROAST_STAT_MEAN50 && ms > PLAIDHIP_ROAST_MEAN50_MAX) capped = 1.0;
+      }
+      if (k == 0) {
+        for (int h = 0; h < 4; ++h) sh.roast.hyper[7 * (size_t)f + h] = hyp[4 * (size_t)f + h];
+        sh.roast.hyper[7 * (size_t)f + 4] = uni;
+        sh.roast.hyper[7 * (size_t)f + 5] = (double)nrot;
+        sh.roast.hyper[7 * (size_t)f + 6] = capped;
+      }
+    }
+    // ---- the shard's tiles ----
+    const int64_t mine = std::max<int64_t>(t_hi - t_lo, 1);
+    const int64_t ctile = std::max<int64_t>(1, std::min<int64_t>(mine, PLAIDHIP_ROAST_Z_BYTES / ((int64_t)R * 64 * 8)));
+    DevBuf dcg, dW, dGp, dGi, dsel, dbeta, dt, dZo, dobs, dcnt;
+    PH_TRY(dR.alloc((size_t)ld * n * 8));
+    PH_TRY(dZ.alloc((size_t)ctile * R * 64 * 8));
+    PH_TRY(dcg.alloc(cg.size() * 8));
+    PH_HIP(hipMemcpyAsync(dcg.p, cg.data(), cg.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    PH_TRY(dW.alloc((size_t)(n + 1) * ldw * 8));
+    PH_HIP(hipMemsetAsync(dW.p, 0, (size_t)(n + 1) * ldw * 8, ctx->stream));
+    PH_TRY(dGp.alloc((M + 1) * 4));
+    PH_TRY(dGi.alloc(std::max<size_t>((size_t)c.Gp[m], 1) * 4));
+    PH_TRY(dsel.alloc(M * 4));
+    PH_TRY(dbeta.alloc(R * 8));
+    PH_TRY(dt.alloc(R * 8));
+    PH_TRY(dZo.alloc(R * 64 * 8));
+    PH_TRY(dobs.alloc(M * 4 * 8));
+    PH_TRY(dcnt.alloc(M * 4 * 4));
+    std::vector<double> beta(R), zobs(R);
+    std::vector<int32_t> sel(M), hcnt(M * 4);
+    for (int32_t f = 0; f < nfit; ++f) {
+      const std::vector<int32_t>& gp = Gpf[(size_t)f];
+      const std::vector<int32_t>& gi = Gif[(size_t)f];
+      PH_TRY(launch_fry_residuals(ctx, dA.as<double>(), ld, g, n, dQ.as<double>(), dmask.p, p, f, d_E, dcg.as<double>(),
+                                  dR.as<double>(), ld));
+      const double* Wh = c.rotations != nullptr ? c.rotations + (size_t)f * (n + 1) * nrot : sh.roast.W[(size_t)f].data();
+      PH_HIP(hipMemcpy2DAsync(dW.p, (size_t)ldw * 8, Wh, (size_t)nrot * 8, (size_t)nrot * 8, (size_t)n + 1, hipMemcpyHostToDevice,
+                              ctx->stream));
+      PH_HIP(hipMemcpyAsync(dGp.p, gp.data(), (M + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+      if (!gi.empty()) PH_HIP(hipMemcpyAsync(dGi.p, gi.data(), gi.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+      int32_t cls_cnt[3] = {0, 0, 0};
+      if (c.set_statistic == PLAIDHIP_ROAST_STAT_MEAN50) {   // the sets, class after class
+        size_t at = 0;
+        for (int cls = 0; cls < 3; ++cls)
+          for (int32_t st = 0; st < m; ++st)
+            if (roast_mean50_class(gp[(size_t)st + 1] - gp[(size_t)st]) == cls) {
+              sel[at++] = st;
+              ++cls_cnt[cls];
+            }
+        PH_HIP(hipMemcpyAsync(dsel.p, sel.data(), M * 4, hipMemcpyHostToDevice, ctx->stream));
+      }
+      const RoastFit rf = roast_fit(hyp[4 * (size_t)f], hyp[4 * (size_t)f + 1], hyp[4 * (size_t)f + 2]);
+      for (int32_t j = 0; j < q; ++j) {
+        const size_t col = (size_t)f * q + j;
+        const double* fc = tab.data() + col * 6 * R;
+        const double uj = c.lm_u[col];
+        for (size_t r = 0; r < R; ++r) beta[r] = cg[R * f + r] == 1.0 ? fc[r] / uj : nan;
+        PH_HIP(hipMemcpyAsync(dbeta.p, beta.data(), R * 8, hipMemcpyHostToDevice, ctx->stream));
+        PH_HIP(hipMemcpyAsync(dt.p, fc + 2 * R, R * 8, hipMemcpyHostToDevice, ctx->stream));
+        PH_TRY(launch_roast_observed(ctx, dt.as<double>(), g, rf.nu, c.zscore, dZo.as<double>()));
+        PH_TRY(launch_roast_stats(ctx, dZo.as<double>(), g, dGp.as<int32_t>(), dGi.as<int32_t>(), m, c.set_statistic, 0, 1, 1,
+                                  dsel.as<int32_t>(), cls_cnt, dobs.as<double>(), nullptr, nullptr));
+        PH_HIP(hipMemsetAsync(dcnt.p, 0, M * 4 * 4, ctx->stream));
+        for (int64_t t0 = t_lo; t0 < t_hi; t0 += ctile) {
+          const int32_t k0 = (int32_t)(t0 * 64), k1 = (int32_t)std::min<int64_t>(nrot, std::min(t0 + ctile, t_hi) * 64);
+          PH_TRY(launch_roast_rotate(ctx, dR.as<double>(), ld, g, n, dbeta.as<double>(), d_rss + R * f, dW.as<double>(), ldw, k0,
+                                     k1, rf, c.zscore, dZ.as<double>()));
+          PH_TRY(launch_roast_stats(ctx, dZ.as<double>(), g, dGp.as<int32_t>(), dGi.as<int32_t>(), m, c.set_statistic, k0, k1, nrot,
+                                    dsel.as<int32_t>(), cls_cnt, nullptr, dobs.as<double>(), dcnt.as<int32_t>()));
+        }
+        if (k == 0) PH_HIP(hipMemcpy2DAsync(zobs.data(), 8, dZo.p, 64 * 8, 8, R, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipMemcpyAsync(hcnt.data(), dcnt.p, M * 4 * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PH_HIP(hipStreamSynchronize(ctx->stream));   // (beta and the lists above are the sources of this contrast's uploads)
+        {
+          std::lock_guard<std::mutex> lk(sh.mu);
+          int32_t* tot = sh.roast.cnt.data() + col * 4 * M;
+          for (size_t e = 0; e < 4 * M; ++e) tot[e] += hcnt[e];
+        }
+        if (k != 0) continue;
+        const double cut = std::sqrt(2.0);
+        for (size_t st = 0; st < M; ++st)
+          for (int32_t e = gp[st]; e < gp[st + 1]; ++e) {
+            const double z = zobs[(size_t)gi[(size_t)e]];
+            sh.roast.ndown[col * M + st] += z < -cut ? 1.0 : 0.0;
+            sh.roast.nup[col * M + st] += z > cut ? 1.0 : 0.0;
+          }
+      }
+    }
+    return PLAIDHIP_OK;
+  });
+  return s.finish();
+}
+
+// sizes plaid.roast's part of Shared; the generated rotations of every fit are made here, once, before the workers
+void roast_prepare(Shared& sh, const Call& c, int) {
+  const size_t M = (size_t)c.m, ncol = (size_t)c.nfit * c.nq;
+  sh.roast.cnt.assign(4 * M * ncol, 0);
+  sh.roast.ndown.assign(M * ncol, 0.0);
+  sh.roast.nup.assign(M * ncol, 0.0);
+  sh.roast.msize.assign(M * c.nfit, 0.0);
+  sh.roast.hyper.assign((size_t)c.nfit * 7, 0.0);
+  sh.roast.W.assign((size_t)c.nfit, std::vector<double>());
+  if (c.rotations != nullptr) return;
+  for (int32_t f = 0; f < c.nfit; ++f) {
+    sh.roast.W[(size_t)f].resize((size_t)(c.n + 1) * c.nrot);
+    roast_rotations(c.lm_Q.data() + (size_t)f * c.n * c.ncoef, c.n, c.ncoef, c.use != nullptr ? c.use + (size_t)f * c.n : nullptr, f,
+                    c.nrot, c.roast_seed, sh.roast.W[(size_t)f].data());
+  }
+}
+
+// plaid.roast after the workers: the tables from the summed counts (plaidhip_roast_finish), on the host
+int roast_tail(plaidhip_ctx*, const Call& c, Shared& sh) {
+  PH_TRY(plaidhip_roast_finish(c.m, c.nfit, c.nq, c.nrot, c.set_statistic, c.midp, sh.roast.cnt.data(), sh.roast.msize.data(),
+                               sh.roast.ndown.data(), sh.roast.nup.data(), c.out));
+  std::copy(sh.roast.hyper.begin(), sh.roast.hyper.end(), c.hyper);
   return PLAIDHIP_OK;
 }
 

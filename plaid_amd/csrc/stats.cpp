@@ -16,6 +16,7 @@
 #include "common.h"
 #include "fry.h"
 #include "lmfit_na.h"
+#include "roast.h"
 
 namespace plaidhip {
 
@@ -502,6 +503,84 @@ void fry_divisors(int32_t rows, int32_t p, int32_t nfit, const double* rss, cons
   }
 }
 
+// Philox4x32-10 (Salmon et al. 2011): one block of four words from a counter and a key
+static void philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+  for (int round = 0; round < 10; ++round) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// A sum of squares in double-double, fp64 operations only (the same bits on every IEEE host): a square is split exactly
+// into its rounded product and the fma's remainder, the sum runs through Knuth's two-sum; root() is sqrt(hi) corrected once
+// by (hi - s0 s0 + lo) / (2 s0), the residual taken with an fma.
+struct DoubleSum {
+  double hi = 0.0, lo = 0.0;
+  void add_square(double x) {
+#pragma clang fp contract(off)
+    const double pr = x * x, pe = std::fma(x, x, -pr);
+    const double s = hi + pr, bb = s - hi;
+    const double err = (hi - (s - bb)) + (pr - bb);
+    hi = s;
+    lo += err + pe;
+  }
+  double root() const {
+#pragma clang fp contract(off)
+    const double s0 = std::sqrt(hi);
+    if (!(s0 > 0.0)) return s0;
+    const double res = std::fma(-s0, s0, hi) + lo;
+    return s0 + res / (2.0 * s0);
+  }
+};
+
+// plaid.roast's standard normal of (seed, fit, rotation k, index i) (include/plaidhip.h: plaidhip_roast, step 2)
+static double roast_normal(uint64_t seed, int32_t fit, int32_t k, int32_t i) {
+  const uint32_t ctr[4] = {(uint32_t)i, (uint32_t)k, (uint32_t)fit, 0x726f6173u};
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  uint32_t x[4];
+  philox4x32_10(ctr, key, x);
+  const double u1 = (double)(((((uint64_t)x[0] << 32) | x[1]) >> 11) + 1) * 0x1p-53;
+  const double u2 = (double)((((uint64_t)x[2] << 32) | x[3]) >> 11) * 0x1p-53;
+  return std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586476925286766559 * u2);
+}
+
+// plaid.roast, step 2: W ((n + 1) x nrot row-major) of one fit from its thin Q (n x p column-major, 0.0 on the samples left
+// out); rotations dealt to the threads, each a function of (seed, fit, k) alone
+void roast_rotations(const double* Q, int32_t n, int32_t p, const int8_t* use, int32_t fit, int32_t nrot, uint64_t seed,
+                     double* W) {
+  auto work = [&](int64_t t, int64_t nth) {
+    std::vector<double> nu((size_t)n), a((size_t)p);
+    for (int64_t k = nrot * t / nth; k < nrot * (t + 1) / nth; ++k) {
+      const double nu0 = roast_normal(seed, fit, (int32_t)k, 0);
+      for (int32_t c = 0; c < n; ++c) nu[(size_t)c] = use == nullptr || use[c] != 0 ? roast_normal(seed, fit, (int32_t)k, c + 1) : 0.0;
+      for (int32_t j = 0; j < p; ++j) {
+        double acc = 0.0;
+        for (int32_t c = 0; c < n; ++c) acc += Q[(size_t)j * n + c] * nu[(size_t)c];
+        a[(size_t)j] = acc;
+      }
+      DoubleSum ss;   // (double-double: s is the rounded root of the exact sum but for a part in 2^100)
+      ss.add_square(nu0);
+      for (int32_t c = 0; c < n; ++c) {
+        if (use != nullptr && use[c] == 0) continue;
+        double proj = 0.0;
+        for (int32_t j = 0; j < p; ++j) proj += Q[(size_t)j * n + c] * a[(size_t)j];
+        nu[(size_t)c] -= proj;
+        ss.add_square(nu[(size_t)c]);
+      }
+      const double s = ss.root();
+      W[k] = nu0 / s;
+      for (int32_t c = 0; c < n; ++c) W[(size_t)(c + 1) * nrot + k] = use == nullptr || use[c] != 0 ? nu[(size_t)c] / s : 0.0;
+    }
+  };
+  const int64_t nth = std::max<int64_t>(1, std::min<int64_t>({(int64_t)kLimmaThreads, (int64_t)nrot * n * p / kLimmaWork}));
+  if (!lm_threads(nth, work)) work(0, 1);   // (no thread to be had: on the calling one)
+}
+
 // Step 3 of plaid.limma and its tables.  drow == nullptr is plaidhip_limma_finish: every row of fit f has d = n_f - p and
 // the fit's u_j.  Otherwise (plaidhip_limma_finish_na) row r of fit f has d_r = drow[f][r] (NaN: not fitted) and its own
 // u_j, and squeezeVar's moments take a vector df1; where all ok rows share one d the operations are those of the first form.
@@ -928,7 +1007,76 @@ int plaidhip_fry_finish(int32_t m, int32_t nfit, int32_t q, const double* dres, 
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.roast, step 2 (include/plaidhip.h): the rotations of one design in sample space, W (n + 1) x nrot row-major
+int plaidhip_roast_rotations(const double* design, int32_t n, int32_t p, const int8_t* use, int32_t fit, int32_t nrot,
+                             uint64_t seed, double* W) try {
+  using namespace plaidhip;
+  PH_REQUIRE(n >= 0 && fit >= 0, "roast_rotations: bad dims n=%d fit=%d", n, fit);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "roast_rotations: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(nrot >= 1 && nrot <= PLAIDHIP_ROAST_MAX_ROTATIONS, "roast_rotations: nrot = %d (1 <= nrot <= %d)", nrot,
+             PLAIDHIP_ROAST_MAX_ROTATIONS);
+  PH_REQUIRE(design != nullptr || n == 0, "roast_rotations: null design");
+  PH_REQUIRE(W != nullptr, "roast_rotations: null W");
+  std::vector<double> Q((size_t)n * p);
+  const int rc = limma_design("roast_rotations", design, n, p, use, nullptr, 0, fit + 1, Q.data(), nullptr, nullptr, nullptr, nullptr);
+  if (rc != PLAIDHIP_OK) return rc;
+  roast_rotations(Q.data(), n, p, use, fit, nrot, seed, W);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.roast, step 6 (include/plaidhip.h): the tables of every (fit, contrast) from the exact counts
+int plaidhip_roast_finish(int32_t m, int32_t nfit, int32_t q, int32_t nrot, int set_statistic, int midp, const int32_t* cnt,
+                          const double* msize, const double* ndown, const double* nup, double* out) try {
+  using namespace plaidhip;
+  PH_REQUIRE(m >= 0 && nfit >= 0 && q >= 0, "roast_finish: bad dims m=%d nfit=%d q=%d", m, nfit, q);
+  PH_REQUIRE(set_statistic >= 0 && set_statistic <= 3, "roast_finish: set_statistic = %d (0 mean, 1 floormean, 2 msq, 3 mean50)",
+             set_statistic);
+  PH_REQUIRE(nrot >= 1, "roast_finish: nrot = %d (at least 1)", nrot);
+  if (m == 0 || nfit == 0 || q == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(cnt && msize && ndown && nup && out, "roast_finish: null argument");
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const size_t M = (size_t)m;
+  const double den = (double)nrot + 1.0, half = 0.5 / den;
+  std::vector<double> pm(M), fm(M);
+  for (int32_t f = 0; f < nfit; ++f)
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      double* o = out + col * 8 * M;
+      const int32_t* b = cnt + col * 4 * M;
+      for (size_t s = 0; s < M; ++s) {
+        const double mm = msize[M * f + s];
+        const bool has = mm >= 1.0 && !(set_statistic == PLAIDHIP_ROAST_STAT_MEAN50 && mm > (double)PLAIDHIP_ROAST_MEAN50_MAX);
+        const double pd = ((double)b[4 * s] + 1.0) / den, pu = ((double)b[4 * s + 1] + 1.0) / den;
+        o[s] = mm;
+        o[M + s] = mm >= 1.0 ? ndown[col * M + s] / mm : nan;
+        o[2 * M + s] = mm >= 1.0 ? nup[col * M + s] / mm : nan;
+        o[3 * M + s] = !has ? nan : pu < pd ? 1.0 : -1.0;
+        o[4 * M + s] = has ? ((double)b[4 * s + 2] + 1.0) / den : nan;
+        o[6 * M + s] = has ? ((double)b[4 * s + 3] + 1.0) / den : nan;
+      }
+      for (int c = 4; c <= 6; c += 2) {   // FDR of PValue, then of PValue.Mixed
+        if (!midp) {
+          p_adjust_fdr(o + (size_t)c * M, m, o + (size_t)(c + 1) * M);
+          continue;
+        }
+        for (size_t s = 0; s < M; ++s) pm[s] = o[(size_t)c * M + s] - half;
+        p_adjust_fdr(pm.data(), m, fm.data());
+        for (size_t s = 0; s < M; ++s) {
+          const double pv = o[(size_t)c * M + s];
+          o[(size_t)(c + 1) * M + s] = pv != pv ? nan : fm[s] > pv ? fm[s] : pv;
+        }
+      }
+    }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
 }  // extern "C"
+
+// Test hook (not part of include/plaidhip.h): plaid.roast's standard normals of (seed, fit, rotation k), indices i0 .. i0 + count - 1
+extern "C" void plaidhip_debug_roast_normals(uint64_t seed, int32_t fit, int32_t k, int32_t i0, int32_t count, double* out) {
+  for (int32_t i = 0; i < count; ++i) out[i] = plaidhip::roast_normal(seed, fit, k, i0 + i);
+}
 
 // Test hook (not part of include/plaidhip.h): pbeta(x, a, b, lower.tail = FALSE) as plaid.fry's mixed test takes it
 extern "C" double plaidhip_debug_beta_upper(double x, double a, double b) { return plaidhip::beta_upper(x, a, b); }

@@ -859,6 +859,81 @@ def beta_upper(x, a, b) -> float:
     return float(f(float(x), float(a), float(b)))
 
 
+ROAST_COLUMNS = ("NGenes", "PropDown", "PropUp", "Direction", "PValue", "FDR", "PValue.Mixed", "FDR.Mixed")
+ROAST_HYPER = LIMMA_HYPER + ("n.genes", "nrot", "mean50.capped")
+ROAST_STATISTIC = {"mean": 0, "floormean": 1, "msq": 2, "mean50": 3}
+ROAST_ZSCORE = {"hill": 0, "none": 1}
+ROAST_MEAN50_MAX = 16384
+
+
+def check_roast_options(set_statistic, zscore):
+    """(set_statistic, zscore) as the C ABI takes them"""
+    if set_statistic not in ROAST_STATISTIC:
+        raise ValueError(f"roast: set_statistic must be one of {sorted(ROAST_STATISTIC)}")
+    if zscore not in ROAST_ZSCORE:
+        raise ValueError(f"roast: zscore must be one of {sorted(ROAST_ZSCORE)} (the exact qnorm(pt()) is not offered)")
+    return ROAST_STATISTIC[set_statistic], ROAST_ZSCORE[zscore]
+
+
+def _roast(fn, head, X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean50", nrot=1999, seed=1, zscore="hill",
+           midp=True, rotations=None, out=None, hyper=None):
+    """plaidhip_roast / _multi / the hook: (out, hyper) -- sets x 8 x q x nfit (ROAST_COLUMNS) and nfit x 7 (ROAST_HYPER).
+    rotations: None (generated from `seed`) or (n + 1) x nrot (x nfit), row 0 = r0"""
+    X = _as_f64_fortran(X)
+    if X.ndim != 2:
+        raise ValueError("roast: the matrix must be genes x samples")
+    g, n = X.shape
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    stat, zs = check_roast_options(set_statistic, zscore)
+    Wr = None
+    if rotations is not None:
+        Wr = np.asarray(rotations, dtype=np.float64)
+        Wr = Wr[:, :, None] if Wr.ndim == 2 else Wr
+        if Wr.ndim != 3 or Wr.shape[0] != n + 1 or Wr.shape[2] != nfit:
+            raise ValueError("roast: rotations must be (samples + 1) x nrot (x fits)")
+        nrot = Wr.shape[1]
+        Wr = np.ascontiguousarray(Wr.transpose(2, 0, 1))   # [fit][n + 1][nrot]
+    out = np.full((m, 8, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 7), np.nan, dtype=np.float64) if hyper is None else hyper
+    check(fn(*head, _np_ptr(X), g, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+             q, _np_ptr(Gp), _np_ptr(Gi), m, stat, zs, int(nrot), int(seed), int(bool(midp)), None if Wr is None else _np_ptr(Wr),
+             _np_ptr(out), _np_ptr(hyper)))
+    return out, hyper
+
+
+def roast_rotations(design, use=None, fit=0, nrot=1999, seed=1) -> np.ndarray:
+    """plaidhip_roast_rotations on the host (no device is touched): W, (n + 1) x nrot, of one design and fit number `fit`
+    (from 0): row 0 is r0, row c + 1 the weight of sample c (0.0 where the fit leaves it out)"""
+    D0 = np.asarray(design, dtype=np.float64)
+    if D0.ndim != 2:
+        raise ValueError("roast_rotations: one design, samples x coefficients")
+    D, U, _, _ = limma_operands(D0.shape[0], D0, use, None)
+    n, p = D.shape[0], D.shape[1]
+    W = np.full((n + 1, max(int(nrot), 0)), np.nan)
+    check(_lib.load().plaidhip_roast_rotations(_np_ptr(D), n, p, None if U is None else _np_ptr(U), int(fit), int(nrot), int(seed),
+                                               _np_ptr(W)))
+    return W
+
+
+def roast_finish(cnt, msize, ndown, nup, nrot, set_statistic="mean50", midp=True):
+    """plaidhip_roast_finish on the host: cnt sets x 4 (x q x nfit) integer counts (down, up, upordown, mixed), msize sets
+    (x nfit), ndown and nup sets (x q x nfit) -> out sets x 8 x q x nfit"""
+    cnt = np.asarray(cnt)
+    cnt = cnt[:, :, None, None] if cnt.ndim == 2 else cnt
+    m, _, q, nfit = cnt.shape
+    cn = np.ascontiguousarray(cnt.transpose(3, 2, 0, 1), dtype=np.int32)   # [fit][contrast][set][4]
+    f2 = lambda v: np.asfortranarray(np.asarray(v, dtype=np.float64).reshape((m, nfit), order="F"))
+    f3 = lambda v: np.asfortranarray(np.asarray(v, dtype=np.float64).reshape((m, q, nfit), order="F"))
+    ms, nd, nu = f2(msize), f3(ndown), f3(nup)
+    out = np.full((m, 8, q, nfit), -7.0, order="F")
+    check(_lib.load().plaidhip_roast_finish(m, nfit, q, int(nrot), ROAST_STATISTIC[set_statistic], int(bool(midp)), _np_ptr(cn),
+                                            _np_ptr(ms), _np_ptr(nd), _np_ptr(nu), _np_ptr(out)))
+    return out
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -1316,6 +1391,23 @@ class Context:
         Context.camera takes its operands.  Returns (out, hyper): sets x 7 x q x nfit (FRY_COLUMNS) and nfit x 7 (FRY_HYPER)."""
         return _fry(self.lib.plaidhip_fry, (self.handle,), X, design, Gp, Gi, use, contrasts, standardize)
 
+    def roast(self, X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean50", nrot=1999, seed=1, zscore="hill",
+              midp=True, rotations=None):
+        """plaidhip_roast: limma's rotation set test with sampled rotations of the sets (Gp, Gi, aligned to the rows of X), as
+        Context.fry takes its operands.  Returns (out, hyper): sets x 8 x q x nfit (ROAST_COLUMNS), nfit x 7 (ROAST_HYPER)."""
+        return _roast(self.lib.plaidhip_roast, (self.handle,), X, design, Gp, Gi, use, contrasts, set_statistic, nrot, seed,
+                      zscore, midp, rotations)
+
+    def dev_roast_rotate(self, Rz: int, ldz: int, rows: int, n: int, beta: int, rss: int, W: int, ldw: int, nrot: int, d: float,
+                         df0: float, s02: float, zscore: int, chunk: int, Z: int):
+        """plaidhip_dev_roast_rotate on device pointers: z of every (gene, rotation) as [tile of 64][rows][64]"""
+        check(self.lib.plaidhip_dev_roast_rotate(self.handle, Rz, ldz, rows, n, beta, rss, W, ldw, nrot, d, df0, s02, zscore,
+                                                 chunk, Z))
+
+    def dev_roast_stats(self, Z: int, rows: int, Gp: int, Gi: int, m: int, set_statistic: int, nrot: int, stat, obs, cnt):
+        """plaidhip_dev_roast_stats on device pointers: the four sides (m x nrot x 4) and / or the counts against obs"""
+        check(self.lib.plaidhip_dev_roast_stats(self.handle, Z, rows, Gp, Gi, m, set_statistic, nrot, stat, obs, cnt))
+
     def dev_fry_residuals(self, A: int, ld: int, rows: int, n: int, Q: int, use, p: int, nfit: int, fit: int, E: int, cg: int,
                           Z: int, ldz: int):
         """plaidhip_dev_fry_residuals on device pointers: dev_camera_residuals with the divisors cg ([nfit][rows])"""
@@ -1587,6 +1679,13 @@ def zscore_multi(X, Gp, Gi, devices=1):
 def fry_multi(X, design, Gp, Gi, use=None, contrasts=None, standardize="posterior.sd", devices=1):
     """plaid.fry (Context.fry) with the sample columns sharded over `devices`: the one-device bits"""
     return _fry(*_multi("fry", devices), X, design, Gp, Gi, use, contrasts, standardize)
+
+
+def roast_multi(X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean50", nrot=1999, seed=1, zscore="hill", midp=True,
+                rotations=None, devices=1):
+    """plaid.roast (Context.roast) with the fit's sample columns sharded over `devices`: the one-device bits"""
+    return _roast(*_multi("roast", devices), X, design, Gp, Gi, use, contrasts, set_statistic, nrot, seed, zscore, midp,
+                  rotations)
 
 
 def camera_multi(X, design, Gp, Gi, use=None, contrasts=None, inter_gene_cor=0.01, allow_neg_cor=False, devices=1):

@@ -973,6 +973,109 @@ plaid.fry.contrasts <- function(X, Y, G, B = NULL, standardize = "posterior.sd",
 }
 
 
+.roast_statistics <- c("mean", "floormean", "msq", "mean50")
+.roast_zscores <- c("hill", "none")
+.roast_sorts <- c("directional", "mixed", "none")
+
+.roast_table <- function(tab, rn, sort.by) {
+  tab <- matrix(tab, nrow = length(rn), ncol = 8L)
+  res <- data.frame(NGenes = tab[, 1], PropDown = tab[, 2], PropUp = tab[, 3],
+                    Direction = ifelse(is.na(tab[, 4]), NA_character_, ifelse(tab[, 4] > 0, "Up", "Down")),
+                    PValue = tab[, 5], FDR = tab[, 6], PValue.Mixed = tab[, 7], FDR.Mixed = tab[, 8],
+                    row.names = rn, stringsAsFactors = FALSE)
+  key <- switch(sort.by, none = NULL, directional = res$PValue, mixed = res$PValue.Mixed)
+  if (!is.null(key)) res <- res[order(key), , drop = FALSE]
+  res
+}
+
+.roast_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok", "n.genes", "nrot", "mean50.capped"))
+
+## rotations as the C entry takes them: every fit's (samples + 1) x nrot matrix row by row
+.roast_rotations <- function(rotations, n, nfit) {
+  if (is.null(rotations)) return(NULL)
+  rotations <- if (length(dim(rotations)) == 3L) rotations else array(as.matrix(rotations), c(dim(as.matrix(rotations)), 1L))
+  if (dim(rotations)[1] != n + 1L || dim(rotations)[3] != nfit) stop("plaid.roast: rotations must be (samples + 1) x nrot (x fits)")
+  storage.mode(rotations) <- "double"
+  aperm(rotations, c(2L, 1L, 3L))
+}
+
+.roast_call <- function(cs, D, nfit, use, K, set.statistic, nrot, seed, zscore, midp, rotations, ncon, sort.by) {
+  if (length(set.statistic) != 1L || !set.statistic %in% .roast_statistics)
+    stop("plaid.roast: set.statistic must be one of ", paste(.roast_statistics, collapse = ", "))
+  if (length(zscore) != 1L || !zscore %in% .roast_zscores)
+    stop("plaid.roast: zscore must be one of ", paste(.roast_zscores, collapse = ", "), " (the exact qnorm(pt()) is not offered)")
+  if (length(sort.by) != 1L || !sort.by %in% .roast_sorts) stop("plaid.roast: sort.by must be one of ", paste(.roast_sorts, collapse = ", "))
+  rot <- .roast_rotations(rotations, ncol(cs$X), nfit)
+  if (!is.null(rot)) nrot <- dim(rot)[1]
+  opts <- c(match(set.statistic, .roast_statistics) - 1L, match(zscore, .roast_zscores) - 1L, as.integer(nrot), as.integer(isTRUE(midp)))
+  .session()
+  r <- .Call("R_plaidhip_roast", .devices(), cs$X, D, nfit, use, K, cs$Gp, cs$Gi, opts, as.double(seed), rot, PACKAGE = "plaidhip")
+  out <- r[[1]]
+  dim(out) <- c(length(cs$names), 8L, ncon)
+  list(tables = lapply(seq_len(ncon), function(j) .roast_table(out[, , j], cs$names, sort.by)), hyper = r[[2]])
+}
+
+
+## plaid.roast(): limma's rotation gene-set test with sampled rotations (roast / mroast as pinned in include/plaidhip.h:
+## plaidhip_roast) of every set of G on the expression X (genes x samples) for one design.  The operands are plaid.fry()'s.
+## What it adds to plaid.fry(): a mixed test for any number of samples, and the set statistics "mean50" (the default),
+## "floormean" and "msq" beside "mean".  The rotations are drawn in sample space from `seed` and shared by every set and
+## contrast (as romer shares them; mroast draws per set), or given: rotations, (samples + 1) x nrot with row 1 = r0.
+## p = (b + 1) / (nrot + 1); midp takes the FDR on p - 0.5 / (nrot + 1).  Under "mean50" a set with more than 16,384 members
+## in the universe has NA p-values (hyper$mean50.capped = 1).
+## Returns list(tables = <named list, one data frame per contrast: sets x (NGenes, PropDown, PropUp, Direction, PValue, FDR,
+## PValue.Mixed, FDR.Mixed), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok, n.genes, nrot,
+## mean50.capped)).
+## Not offered: per-set rotations, romer, gene or array weights, trend.var, robust, a sparse X, na = "fit", the exact z-score.
+plaid.roast <- function(X, design, G, contrasts = NULL, use = NULL, set.statistic = "mean50", nrot = 1999, seed = 1,
+                        zscore = "hill", midp = TRUE, rotations = NULL, minSize = 1, maxSize = NULL, sort.by = "directional") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(cs$X)) stop("design must have one row per column of X")
+  cn <- if (is.null(colnames(design))) paste0("coef", seq_len(ncol(design))) else colnames(design)
+  if (!is.null(contrasts)) {
+    contrasts <- as.matrix(contrasts); storage.mode(contrasts) <- "double"
+    if (nrow(contrasts) != ncol(design)) stop("contrasts must have one row per coefficient")
+    cn <- if (is.null(colnames(contrasts))) as.character(seq_len(ncol(contrasts))) else colnames(contrasts)
+  }
+  if (!is.null(use)) {
+    if (length(use) != ncol(cs$X)) stop("use must have one entry per column of X")
+    use <- matrix(as.integer(!is.na(use) & use != 0), ncol = 1)
+  }
+  r <- .roast_call(cs, design, 1L, use, contrasts, set.statistic, nrot, seed, zscore, midp, rotations, length(cn), sort.by)
+  tables <- r$tables
+  names(tables) <- cn
+  list(tables = tables, hyper = .roast_hyper(r$hyper[, 1]))
+}
+
+
+## plaid.roast.contrasts(): plaid.roast() for every column of a contrast matrix Y (samples x contrasts; 0, 1, NA = the sample
+## takes no part) in ONE call, with the designs of plaid.limma.contrasts().  X is uploaded once.  Contrast j is fit number j:
+## its generated rotations are those of (seed, j - 1).
+plaid.roast.contrasts <- function(X, Y, G, B = NULL, set.statistic = "mean50", nrot = 1999, seed = 1, zscore = "hill",
+                                  midp = TRUE, rotations = NULL, minSize = 1, maxSize = NULL, sort.by = "directional") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  Y <- as.matrix(Y)
+  if (nrow(Y) != ncol(cs$X)) stop("Y must have one row per column of X")
+  if (!all(unique(as.vector(Y)) %in% c(0, 1, NA))) stop("elements of Y must be 0, 1 or NA")
+  if (!is.null(B)) {
+    B <- as.matrix(B); storage.mode(B) <- "double"
+    if (nrow(B) != ncol(cs$X)) stop("B must have one row per column of X")
+  }
+  D <- do.call(cbind, lapply(seq_len(ncol(Y)), function(j) cbind(1, ifelse(is.na(Y[, j]), 0, Y[, j]), B)))
+  storage.mode(D) <- "double"
+  p <- 2L + (if (is.null(B)) 0L else ncol(B))
+  K <- matrix(0, p, 1); K[2, 1] <- 1
+  use <- matrix(as.integer(!is.na(Y)), nrow(Y), ncol(Y))
+  cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
+  r <- .roast_call(cs, D, ncol(Y), use, K, set.statistic, nrot, seed, zscore, midp, rotations, ncol(Y), sort.by)
+  tables <- r$tables
+  hyper <- lapply(seq_len(ncol(Y)), function(j) .roast_hyper(r$hyper[, j]))
+  names(tables) <- names(hyper) <- cn
+  list(tables = tables, hyper = hyper)
+}
+
+
 ## plaid.intergenecor(): limma's interGeneCorrelation(X[set, ], design) for every set of G at once: the variance inflation
 ## factor of the set's mean, estimated from the residuals of its genes, and the mean pairwise correlation (VIF - 1) / (m - 1).
 ## Returns a matrix, sets x (NGenes, Correlation, VIF), in G's order.
