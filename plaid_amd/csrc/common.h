@@ -211,6 +211,9 @@ struct plaidhip_pair_plan {
   int32_t* d_meta_j = nullptr;
   double* d_meta_w = nullptr;
   double* d_meta_k = nullptr;
+  // a regp plan is planned with flex steps (geneset.cpp, plan_tile_flex): [slice][wavefront 0..15][lane][the wavefront's
+  // tile 0..7] one byte {source lane, is-host, has-host}; only the FLEX forms of the pair kernel walk such a plan
+  uint8_t* d_flex = nullptr;
 };
 
 // Scatter plan (sparse X): G transposed, gene-major.  The sets are dealt to `nch` chunks of `ch` accumulator slots (the

@@ -105,7 +105,12 @@ void color_bipartite(std::vector<Edge>& E, int D, int nV = 32) {
 struct TilePlan {
   int32_t steps = 0;                 // multiple of 8
   std::vector<uint16_t> idx;         // [step][lane 0..63]
+  // pair plan with flex steps (plan_tile_flex): per lane {source lane (6 bits), kFlexIsHost, kFlexHasHost}; all zero in a
+  // tile without long lanes
+  uint8_t flex[64] = {0};
+  int32_t nlong = 0;                 // long lanes = owner <-> host pairs of this (tile, slice)
 };
+constexpr uint8_t kFlexIsHost = 0x40, kFlexHasHost = 0x80;
 
 // Relative cost of one extra LDS pass (a 2-way conflict inside one lane group) against a whole
 // extra gather step; PLAIDHIP_CONFLICT_COST overrides it in the tools/ build (>= 1 disables conflicted steps).
@@ -404,11 +409,256 @@ void plan_tile_b128(int32_t g0, int32_t gs, const int32_t* Gp, const int32_t* Gi
     }
 }
 
+// The same tile with FLEX STEPS (register-partial plans only; the kernel's FLEX form).  Step 7 of every 8-step chunk
+// accumulates into an accumulator pair of its own, so what a lane reads there need not belong to its own set: a lane
+// whose list in this slice is short (at most 7T/8: a HOST) keeps its own genes on steps 0..6 of every chunk, and its
+// step-7 cells gather the overflow of one LONG lane of the tile, whose list exceeds the tile's T steps by at most T/8.
+// The tile then takes T steps where its longest lane alone would ask for up to 9T/8.  One host per long lane and one
+// long lane per host, matched longest overflow to shortest host; at the tile end the long lane pulls the host's flex
+// sum (TilePlan::flex).  The normal steps (7T/8 colours) and the flex steps (T/8 colours) are two ordinary Koenig
+// problems per 16-lane group: which genes of a lane that is no host go to its own flex steps (it needs L - 7T/8 of
+// them there), and which of a long lane's go to its host, is free, and is chosen to level the slot degrees of both
+// problems.  Among the multiples of 8 that admit this, T is the one of lowest cost by choose_steps' measure (steps +
+// conflict_cost x double-booked slot reads: a slot's reads beyond 7T/8 on the normal and beyond T/8 on the flex steps);
+// false: none costs less than the tile without flex steps, plan as before.  (The split below ends within the per-slot
+// bound sum(max(0, degree - T)) on every tile of the 5,000-set benchmark collection.  Fewer steps for the same lanes
+// mean fuller slots: with the sets in the lanes they had, that collection's plan booked 2,587 reads twice where it had
+// booked 780, for 810,496 slots; with the sets dealt to the 16-lane groups first (balance_tile_lanes) it books 692 and
+// has 798,720 slots, against 861,696 without flex steps.)
+bool plan_tile_flex(int32_t g0, int32_t gs, const int32_t* Gp, const int32_t* Gi, const int32_t* lane_set, TilePlan& tp) {
+  int qof[64], lof[64];
+  for (int q = 0; q < 4; ++q)
+    for (int l = 0; l < 16; ++l) { qof[kB128Groups[q][l]] = q; lof[kB128Groups[q][l]] = l; }
+  std::vector<uint16_t> by_slot[64][16];   // a lane's genes of this slice by 16-byte slot (gene mod 16)
+  int L[64], deg[4][16] = {{0}}, Lmax = 0;
+  for (int lane = 0; lane < 64; ++lane) {
+    L[lane] = 0;
+    const int32_t j = lane_set[lane];
+    if (j < 0) continue;
+    for (int32_t p = Gp[j]; p < Gp[j + 1]; ++p) {
+      const int32_t gene = Gi[p] - g0;
+      if (gene < 0 || gene >= gs) continue;
+      by_slot[lane][gene & 15].push_back((uint16_t)gene);
+      ++L[lane];
+      ++deg[qof[lane]][gene & 15];
+    }
+    Lmax = std::max(Lmax, L[lane]);
+  }
+  if (Lmax <= 8) return false;
+  const double cx = conflict_cost();
+  const int T0 = choose_steps(Lmax, &deg[0][0], 64);
+  int64_t excess0 = 0;
+  for (int k = 0; k < 64; ++k) excess0 += std::max(0, (&deg[0][0])[k] - T0);
+  const double cost0 = (double)T0 + cx * (double)excess0;
+
+  // what a candidate T decides: per lane and slot, how many of the genes stay on the lane's normal steps (the first
+  // `keep`), go to its own flex steps (the next `own`), and to its host's (the rest)
+  struct Split {
+    int T = 0;
+    int host_of[64], keep[64][16], own[64][16];
+    bool is_host[64];
+  };
+  Split best;
+  double best_cost = cost0;
+  std::vector<int> longs, cand;
+  for (int T = std::max(8, ((Lmax * 8 + 8) / 9) & ~7); T < ((Lmax + 7) & ~7); T += 8) {
+    const int Tn = T / 8 * 7, Tf = T / 8;
+    if (Lmax - T > Tf) continue;
+    longs.clear();
+    cand.clear();
+    for (int lane = 0; lane < 64; ++lane) {
+      if (L[lane] > T) longs.push_back(lane);
+      else if (L[lane] <= Tn) cand.push_back(lane);
+    }
+    if (longs.empty() || cand.size() < longs.size()) continue;
+    std::stable_sort(longs.begin(), longs.end(), [&](int a, int b) { return L[a] > L[b]; });
+    std::stable_sort(cand.begin(), cand.end(), [&](int a, int b) { return L[a] < L[b]; });
+    Split s;
+    s.T = T;
+    int degN[4][16], degF[4][16] = {{0}}, nown[64] = {0};
+    std::memcpy(degN, deg, sizeof(deg));
+    for (int lane = 0; lane < 64; ++lane) {
+      s.host_of[lane] = -1;
+      s.is_host[lane] = false;
+      for (int v = 0; v < 16; ++v) { s.keep[lane][v] = (int)by_slot[lane][v].size(); s.own[lane][v] = 0; }
+    }
+    for (size_t i = 0; i < longs.size(); ++i) { s.host_of[longs[i]] = cand[i]; s.is_host[cand[i]] = true; }
+    // one gene of `lane` off its normal steps, to the flex steps of lane `to` (itself or its host): from the slot whose
+    // flex degree there is still below Tf and whose normal degree here is the highest
+    auto move_one = [&](int lane, int to) {
+      const int q = qof[lane], qt = qof[to];
+      int bv = -1;
+      long bkey = 0;
+      for (int v = 0; v < 16; ++v) {
+        if (s.keep[lane][v] == 0) continue;
+        const long key = (degF[qt][v] < Tf ? 1000000L : 0L) + 1000L * degN[q][v] - degF[qt][v];
+        if (bv < 0 || key > bkey) { bv = v; bkey = key; }
+      }
+      --s.keep[lane][bv];
+      if (to == lane) { ++s.own[lane][bv]; ++nown[lane]; }
+      --degN[q][bv];
+      ++degF[qt][bv];
+    };
+    for (int lane : longs)
+      for (int k = L[lane] - T; k > 0; --k) move_one(lane, s.host_of[lane]);
+    for (int lane = 0; lane < 64; ++lane) {
+      if (s.is_host[lane]) continue;
+      const int guests = s.host_of[lane] >= 0 ? L[lane] - T : 0;
+      for (int k = L[lane] - guests - Tn; k > 0; --k) move_one(lane, lane);
+    }
+    // relief: an over-full normal slot gives reads to the flex steps of lanes that still have room there
+    for (int q = 0; q < 4; ++q)
+      for (int v = 0; v < 16; ++v)
+        for (int l = 0; l < 16 && degN[q][v] > Tn && degF[q][v] < Tf; ++l) {
+          const int lane = kB128Groups[q][l];
+          while (!s.is_host[lane] && s.keep[lane][v] > 0 && nown[lane] < Tf && degN[q][v] > Tn && degF[q][v] < Tf) {
+            --s.keep[lane][v]; ++s.own[lane][v]; ++nown[lane];
+            --degN[q][v]; ++degF[q][v];
+          }
+        }
+    int64_t excess = 0;
+    bool ok = true;
+    for (int q = 0; q < 4; ++q)
+      for (int v = 0; v < 16; ++v) {
+        if (degN[q][v] > 2 * Tn || degF[q][v] > 2 * Tf) ok = false;   // a slot has two read ports per step
+        excess += std::max(0, degN[q][v] - Tn) + std::max(0, degF[q][v] - Tf);
+      }
+    if (!ok) continue;
+    const double cost = (double)T + cx * (double)excess;
+    if (cost < best_cost) { best_cost = cost; best = s; }
+  }
+  if (best.T == 0) return false;
+
+  const int T = best.T, Tn = T / 8 * 7, Tf = T / 8;
+  std::vector<Edge> nrm[4], flx[4];
+  for (int q = 0; q < 4; ++q)
+    for (int l = 0; l < 16; ++l) {
+      const int lane = kB128Groups[q][l];
+      const int host = best.host_of[lane];
+      for (int v = 0; v < 16; ++v) {
+        const std::vector<uint16_t>& gl = by_slot[lane][v];
+        for (int k = 0; k < (int)gl.size(); ++k) {
+          if (k < best.keep[lane][v]) nrm[q].push_back(Edge{(uint8_t)l, (uint8_t)v, gl[k], -1});
+          else if (k < best.keep[lane][v] + best.own[lane][v]) flx[q].push_back(Edge{(uint8_t)l, (uint8_t)v, gl[k], -1});
+          else flx[qof[host]].push_back(Edge{(uint8_t)lof[host], (uint8_t)v, gl[k], -1});
+        }
+      }
+    }
+  tp.steps = T;
+  tp.idx.assign((size_t)T * 64, 0);
+  std::vector<uint8_t> used((size_t)T * 64, 0), filled((size_t)T * 64, 0);
+  for (int q = 0; q < 4; ++q)
+    for (int pass = 0; pass < 2; ++pass) {
+      std::vector<Edge>& E = pass ? flx[q] : nrm[q];
+      const int D = pass ? Tf : Tn;
+      int seen[16] = {0};
+      for (Edge& e : E)
+        if (seen[e.v]++ >= D) e.v = (uint8_t)(e.v + 16);   // second vertex of an over-full slot
+      color_bipartite(E, D, 32);
+      for (const Edge& e : E) {
+        const size_t st = pass ? (size_t)e.color * 8 + 7 : (size_t)(e.color / 7) * 8 + (size_t)(e.color % 7);
+        tp.idx[st * 64 + kB128Groups[q][e.u]] = e.gene;
+        filled[st * 64 + kB128Groups[q][e.u]] = 1;
+        used[st * 64 + q * 16 + (e.v & 15)] = 1;
+      }
+    }
+  for (int32_t st = 0; st < T; ++st)
+    for (int q = 0; q < 4; ++q) {
+      int slot = 0;
+      for (int l = 0; l < 16; ++l) {
+        const int lane = kB128Groups[q][l];
+        if (filled[(size_t)st * 64 + lane]) continue;
+        while (used[(size_t)st * 64 + q * 16 + slot]) ++slot;   // #free slots >= #idle lanes
+        const int r = ((slot - gs) % 16 + 16) % 16;
+        tp.idx[(size_t)st * 64 + lane] = (uint16_t)(gs + r);
+        ++slot;
+      }
+    }
+  tp.nlong = 0;
+  for (int lane = 0; lane < 64; ++lane) {
+    tp.flex[lane] = 0;
+    if (best.is_host[lane]) tp.flex[lane] = (uint8_t)(kFlexIsHost | lane);
+    if (best.host_of[lane] >= 0) { tp.flex[lane] = (uint8_t)(kFlexHasHost | best.host_of[lane]); ++tp.nlong; }
+  }
+  return true;
+}
+
+// Which of a tile's 64 sets sits in which lane is free: the lanes of a tile write 64 neighbouring rows of S whatever their
+// order.  Fewer steps for the same lanes mean fuller slots, so a tile that can take flex steps (some slice has a T below
+// its longest list with every overflow at most T/8 and a host per long lane; the lists' lengths do not depend on the
+// lanes) first deals its sets to the four 16-lane groups so that the slot degrees of the groups are level in every
+// slice: pairwise swaps between groups while they lower the sum of the squared degrees (at most eight sweeps).  A tile
+// without long lanes keeps the order it had.  starts / width: the gene slices.
+void balance_tile_lanes(int32_t g, const std::vector<int32_t>& starts, int32_t width, const int32_t* Gp, const int32_t* Gi,
+                        int32_t* lane_set) {
+  const int S = (int)starts.size();
+  const int W = S * 16;
+  std::vector<int32_t> cnt((size_t)64 * W, 0), len((size_t)64 * S, 0);
+  for (int lane = 0; lane < 64; ++lane) {
+    const int32_t j = lane_set[lane];
+    if (j < 0) continue;
+    for (int32_t p = Gp[j]; p < Gp[j + 1]; ++p) {
+      const int s = Gi[p] / width;
+      ++cnt[(size_t)lane * W + s * 16 + ((Gi[p] - starts[s]) & 15)];
+      ++len[(size_t)lane * S + s];
+    }
+  }
+  bool eligible = false;
+  for (int s = 0; s < S && !eligible; ++s) {
+    int Lmax = 0;
+    for (int lane = 0; lane < 64; ++lane) Lmax = std::max(Lmax, len[(size_t)lane * S + s]);
+    for (int T = std::max(8, ((Lmax * 8 + 8) / 9) & ~7); T < ((Lmax + 7) & ~7) && !eligible; T += 8) {
+      if (Lmax - T > T / 8) continue;
+      int nl = 0, nh = 0;
+      for (int lane = 0; lane < 64; ++lane) {
+        nl += len[(size_t)lane * S + s] > T;
+        nh += len[(size_t)lane * S + s] <= T / 8 * 7;
+      }
+      eligible = nl > 0 && nh >= nl;
+    }
+  }
+  if (!eligible) return;
+  int qof[64];
+  for (int q = 0; q < 4; ++q)
+    for (int l = 0; l < 16; ++l) qof[kB128Groups[q][l]] = q;
+  std::vector<int32_t> deg((size_t)4 * W, 0);
+  for (int lane = 0; lane < 64; ++lane)
+    for (int k = 0; k < W; ++k) deg[(size_t)qof[lane] * W + k] += cnt[(size_t)lane * W + k];
+  for (int sweep = 0; sweep < 8; ++sweep) {
+    bool moved = false;
+    for (int a = 0; a < 64; ++a)
+      for (int b = a + 1; b < 64; ++b) {
+        const int p = qof[a], q = qof[b];
+        if (p == q) continue;
+        const int32_t* ca = &cnt[(size_t)a * W];
+        const int32_t* cb = &cnt[(size_t)b * W];
+        const int32_t* P = &deg[(size_t)p * W];
+        const int32_t* Q = &deg[(size_t)q * W];
+        int64_t delta = 0;   // half the change of the sum of squares when the sets of lanes a and b change places
+        for (int k = 0; k < W; ++k) {
+          const int64_t d = cb[k] - ca[k];
+          delta += d * (P[k] - Q[k] + d);
+        }
+        if (delta >= 0) continue;
+        for (int k = 0; k < W; ++k) {
+          const int32_t d = cb[k] - ca[k];
+          deg[(size_t)p * W + k] += d;
+          deg[(size_t)q * W + k] -= d;
+          std::swap(cnt[(size_t)a * W + k], cnt[(size_t)b * W + k]);
+        }
+        std::swap(lane_set[a], lane_set[b]);
+        moved = true;
+      }
+    if (!moved) break;
+  }
+}
+
 struct PairSliceHost {
   int32_t g0 = 0, gs = 0;
   std::vector<uint16_t> idx;             // [chunk][lane][8]
   std::vector<int32_t> wave_chunk_off;   // waves + 1
   std::vector<int32_t> wtile_end;        // per wave-stream tile k (+ sentinel)
+  std::vector<uint8_t> flex;             // [k][lane] (TilePlan::flex; + sentinel), empty in a plan without flex steps
 };
 struct PairPlanHost {
   std::vector<PairSliceHost> slices;
@@ -417,7 +667,10 @@ struct PairPlanHost {
   std::vector<double> meta_w, meta_k;
   int64_t chunks = 0;
   bool regp = false;                     // dealt to kPairRegWaves wavefronts, at most kPairRegPartials tiles each
+  bool flex = false;                     // planned with flex steps (plan_tile_flex): every slice has its flex table
   int live_waves = 0;
+  std::vector<int32_t> ktile;            // wave-stream order -> tile (64 consecutive sets in decreasing size)
+  std::vector<int32_t> lane_set;         // [tile][lane] -> set or -1
 };
 
 // Tiles (lane <-> set) and the tile -> wavefront assignment are the SAME in every gene slice, so a
@@ -430,9 +683,12 @@ bool pair_plan_regp(int32_t g, int32_t m) {
   return g > kMaxLdsGenesPair && (m + 63) / 64 <= kPairRegWaves * kPairRegPartials;
 }
 
+// A register-partial plan is planned with flex steps (plan_tile_flex; `allow_flex` false: the probe's view of the plan
+// without them).
 void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi, int waves, PairPlanHost& pp,
-                     bool allow_regp = true) {
+                     bool allow_regp = true, bool allow_flex = true) {
   const bool regp = allow_regp && waves >= kPairRegWaves && pair_plan_regp(g, m);
+  const bool flex = regp && allow_flex;
   const int live = regp ? kPairRegWaves : waves;   // wavefronts that get tiles
   const int32_t nsl = (g + kMaxLdsGenesPair - 1) / kMaxLdsGenesPair;
   int32_t width = (g + nsl - 1) / nsl;
@@ -450,6 +706,24 @@ void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
   const int32_t tiles = (m + 63) / 64;
   std::vector<int32_t> lane_set((size_t)tiles * 64, -1);
   for (int32_t s = 0; s < m; ++s) lane_set[s] = order[s];
+  if (flex) {   // tiles that can take flex steps: sets dealt to the 16-lane groups for level slot degrees
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = std::max(1u, std::min(nt, 16u));
+    if (tiles < 8) nt = 1;
+    std::vector<std::thread> pool;
+    std::atomic<int> pool_failed{0};
+    for (unsigned w = 0; w < nt; ++w)
+      pool.emplace_back([&, w]() {
+        try {
+          for (int32_t t = (int32_t)w; t < tiles; t += (int32_t)nt)
+            balance_tile_lanes(g, starts, width, Gp, Gi, &lane_set[(size_t)t * 64]);
+        } catch (...) {
+          pool_failed.store(1);
+        }
+      });
+    for (auto& th : pool) th.join();
+    if (pool_failed.load()) throw std::bad_alloc();
+  }
   std::vector<std::vector<TilePlan>> plans(S, std::vector<TilePlan>(tiles));
   {
     unsigned nt = std::thread::hardware_concurrency();
@@ -463,7 +737,9 @@ void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
           for (int64_t u = (int64_t)w; u < (int64_t)tiles * S; u += nt) {
             const int si = (int)(u / tiles);
             const int32_t t = (int32_t)(u % tiles);
-            plan_tile_b128(starts[si], std::min(width, g - starts[si]), Gp, Gi, &lane_set[(size_t)t * 64], plans[si][t]);
+            const int32_t gsz = std::min(width, g - starts[si]);
+            if (!flex || !plan_tile_flex(starts[si], gsz, Gp, Gi, &lane_set[(size_t)t * 64], plans[si][t]))
+              plan_tile_b128(starts[si], gsz, Gp, Gi, &lane_set[(size_t)t * 64], plans[si][t]);
           }
         } catch (...) {
           pool_failed.store(1);
@@ -500,15 +776,18 @@ void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
     assign_tiles(tot, waves, mine, share);
   }
   pp.regp = regp;
+  pp.flex = flex;
   pp.live_waves = live;
   pp.wave_tile_off.assign(waves + 1, 0);
-  std::vector<int32_t> ktile;   // wave-stream order -> tile
+  std::vector<int32_t>& ktile = pp.ktile;   // wave-stream order -> tile
+  ktile.clear();
   for (int w = 0; w < waves; ++w) {
     pp.wave_tile_off[w] = (int32_t)ktile.size();
     for (int32_t t : mine[w]) ktile.push_back(t);
   }
   pp.wave_tile_off[waves] = (int32_t)ktile.size();
   const size_t nk = ktile.size() + 1;   // + sentinel
+  pp.lane_set = lane_set;
   pp.meta_j.assign(nk * 64, -1);
   pp.meta_w.assign(nk * 64, 0.0);
   pp.meta_k.assign(nk * 64, 0.0);
@@ -550,6 +829,10 @@ void build_pair_plan(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
         }
         c += tp.steps / 8;
       }
+    if (flex) {
+      ps.flex.assign(nk * 64, 0);
+      for (size_t k = 0; k + 1 < nk; ++k) std::memcpy(&ps.flex[k * 64], plans[si][ktile[k]].flex, 64);
+    }
   }
 }
 
@@ -699,6 +982,19 @@ extern "C" int plaidhip_geneset_create(plaidhip_ctx* ctx, int32_t g, int32_t m, 
       hd.push_back(plaidhip_pair_slice_dev{d.d_tile_idx, d.d_wave_chunk_off, d.d_wtile_end, d.g0, d.gs});
     if ((rc = upload(ctx, hd, &gs->pair.d_slices)) != PLAIDHIP_OK) goto fail;
     gs->pair.ktiles = pp.wave_tile_off[16];
+    if (pp.flex) {
+      // for the kernel: [slice][wavefront 0..15][lane] the bytes of the wavefront's (at most kPairRegPartials = 8) tiles, one
+      // 8-byte load per lane and slice
+      static_assert(kPairRegPartials == 8, "eight flex bytes per lane");
+      std::vector<uint8_t> fx(pp.slices.size() * 16 * 64 * 8, 0);
+      for (size_t si = 0; si < pp.slices.size(); ++si)
+        for (int w = 0; w < 16; ++w)
+          for (int32_t k = pp.wave_tile_off[w]; k < pp.wave_tile_off[w + 1]; ++k)
+            for (int l = 0; l < 64; ++l)
+              fx[((si * 16 + w) * 64 + l) * 8 + (size_t)(k - pp.wave_tile_off[w])] = pp.slices[si].flex[(size_t)k * 64 + l];
+      if ((rc = upload(ctx, fx, &gs->pair.d_flex)) != PLAIDHIP_OK) goto fail;
+      if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = PLAIDHIP_EHIP; goto fail; }   // (fx dies here)
+    }
     // (a register-partial plan needs no scratch; launch_colpair allocates one if the scratch form is pinned)
     if (gs->pair.slices.size() > 1 && !gs->pair.regp && (rc = alloc_pair_partial(ctx, gs)) != PLAIDHIP_OK) goto fail;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = PLAIDHIP_EHIP; goto fail; }
@@ -912,6 +1208,7 @@ extern "C" int plaidhip_geneset_destroy(plaidhip_geneset* gs) try {
   hipFree(gs->scatter.d_u);
   hipFree(gs->pair.d_slices);
   hipFree(gs->pair.d_partial);
+  hipFree(gs->pair.d_flex);
   for (plaidhip_pair_slice& d : gs->pair.slices) {
     hipFree(d.d_tile_idx);
     hipFree(d.d_wave_chunk_off);
@@ -940,16 +1237,57 @@ extern "C" int plaidhip_geneset_info(const plaidhip_geneset* gs, int64_t info[8]
 // out[3]=conflicts (two lanes of one ds_read_b128 lane group on the same 16-byte slot in one
 // step) out[4]=memberships scheduled for the wrong set / twice / out of slice.  out[5..7]: the register-partial form
 // (eligible, most tiles on one wavefront, wavefronts with tiles).
-extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
-                                              int32_t waves, int64_t out[8]) try {
-  PairPlanHost pp;
-  build_pair_plan(g, m, Gp, Gi, waves, pp);
-  int64_t found = 0, conflicts = 0, wrong = 0;
+namespace {
+// out[0..7] as plaidhip_debug_pair_plan_check documents; out[8] = padded gather slots per column pair, out[9] = owner <->
+// host pairs over all tiles and slices, out[10] = broken flex relations (an owner whose host is no host or not in its
+// tile, a host named twice or by nobody, an overflow above T/8 or not above 0, a host with more than 7T/8 genes of its
+// own).  A read on a flex step (step 7 of a chunk) of a host lane must belong to the host's OWNER, every other read to
+// the lane's own set -- so a host's own gene on a flex step or a guest gene on a normal step counts as wrong (out[4]).
+// pairs (may be null): up to `cap` times {slice, owner set, host set or -1 for a lane without a set, one gene (row of
+// X) that the host lane reads for the owner}.
+void check_pair_plan(const PairPlanHost& pp, int32_t m, const int32_t* Gp, const int32_t* Gi, int32_t waves, int64_t* out,
+                     int32_t* pairs, int64_t cap) {
+  int64_t found = 0, conflicts = 0, wrong = 0, npairs = 0, broken = 0;
   std::vector<uint8_t> seen((size_t)Gp[m], 0);
+  int32_t si = 0;
   for (const PairSliceHost& ps : pp.slices) {
+    auto in_slice = [&](int32_t j) {
+      if (j < 0) return (int64_t)0;
+      return (int64_t)(std::lower_bound(Gi + Gp[j], Gi + Gp[j + 1], ps.g0 + ps.gs) - std::lower_bound(Gi + Gp[j], Gi + Gp[j + 1], ps.g0));
+    };
     for (int w = 0; w < waves; ++w) {
       int32_t k = pp.wave_tile_off[w];
+      int owner_of[64];
+      int64_t pair_of[64];
+      bool fresh = true;
+      int32_t tile_begin = ps.wave_chunk_off[w];
       for (int32_t ch = ps.wave_chunk_off[w]; ch < ps.wave_chunk_off[w + 1]; ++ch) {
+        const uint8_t* fx = ps.flex.empty() ? nullptr : &ps.flex[(size_t)k * 64];
+        if (fresh) {
+          fresh = false;
+          for (int l = 0; l < 64; ++l) { owner_of[l] = -1; pair_of[l] = -1; }
+          if (fx != nullptr) {
+            const int64_t T = (int64_t)(ps.wtile_end[k] - tile_begin) * 8;
+            int hosts = 0, owners = 0;
+            for (int l = 0; l < 64; ++l) {
+              if (fx[l] & kFlexIsHost) ++hosts;
+              if (!(fx[l] & kFlexHasHost)) continue;
+              ++owners;
+              const int h = fx[l] & 63;
+              const int32_t jo = pp.meta_j[(size_t)k * 64 + l], jh = pp.meta_j[(size_t)k * 64 + h];
+              if ((fx[l] & kFlexIsHost) || !(fx[h] & kFlexIsHost) || owner_of[h] >= 0 || jo < 0) { ++broken; continue; }
+              owner_of[h] = l;
+              const int64_t over = in_slice(jo) - T;
+              if (over <= 0 || over > T / 8 || in_slice(jh) > T / 8 * 7) ++broken;
+              if (pairs != nullptr && npairs < cap) {
+                pairs[4 * npairs] = si; pairs[4 * npairs + 1] = jo; pairs[4 * npairs + 2] = jh; pairs[4 * npairs + 3] = -1;
+                pair_of[h] = npairs;
+              }
+              ++npairs;
+            }
+            if (hosts != owners) ++broken;
+          }
+        }
         for (int e = 0; e < 8; ++e) {
           for (int q = 0; q < 4; ++q) {
             uint32_t slots = 0;
@@ -960,19 +1298,23 @@ extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_
               if (slots & (1u << (id & 15))) ++conflicts;
               slots |= 1u << (id & 15);
               if (id >= ps.gs) continue;
-              const int32_t j = pp.meta_j[(size_t)k * 64 + lane];
+              int from = lane;
+              if (e == 7 && fx != nullptr && (fx[lane] & kFlexIsHost)) from = owner_of[lane];
+              const int32_t j = from < 0 ? -1 : pp.meta_j[(size_t)k * 64 + from];
               if (j < 0) { ++wrong; continue; }
               const int32_t* lo = std::lower_bound(Gi + Gp[j], Gi + Gp[j + 1], ps.g0 + id);
               if (lo == Gi + Gp[j + 1] || *lo != ps.g0 + id || seen[lo - Gi]) { ++wrong; continue; }
               seen[lo - Gi] = 1;
               ++found;
+              if (from != lane && pair_of[lane] >= 0 && pairs[4 * pair_of[lane] + 3] < 0) pairs[4 * pair_of[lane] + 3] = ps.g0 + id;
             }
           }
         }
-        if (ch + 1 == ps.wtile_end[k]) ++k;
+        if (ch + 1 == ps.wtile_end[k]) { ++k; fresh = true; tile_begin = ch + 1; }
       }
       if (k != pp.wave_tile_off[w + 1]) ++wrong;
     }
+    ++si;
   }
   out[0] = (int64_t)pp.slices.size();
   out[1] = pp.chunks;
@@ -984,6 +1326,37 @@ extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_
   out[5] = pp.regp ? 1 : 0;     // dealt to kPairRegWaves wavefronts for the register-partial form of the kernel
   out[6] = most;                // tiles of the wavefront with the most (regp: <= kPairRegPartials)
   out[7] = pp.live_waves;       // wavefronts that may have tiles
+  if (pairs != nullptr || cap < 0) {   // (the eight-word entry below passes neither)
+    out[8] = pp.chunks * 64 * 8;
+    out[9] = npairs;
+    out[10] = broken;
+  } else {
+    out[4] += broken;
+  }
+}
+}  // namespace
+
+extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi,
+                                              int32_t waves, int64_t out[8]) try {
+  PairPlanHost pp;
+  build_pair_plan(g, m, Gp, Gi, waves, pp);
+  check_pair_plan(pp, m, Gp, Gi, waves, out, nullptr, 0);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// The same with the flex steps in view: out[16] (check_pair_plan; out[11] = microseconds the plan took to build), the
+// owner <-> host pairs in `pairs` (4 x cap words; out[9] says how many there are), and `flex` 0 for the plan the same
+// collection gets without flex steps -- the slot count and the double-booked reads (out[3]) to hold this plan against.
+extern "C" int plaidhip_debug_pair_flex_probe(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi, int32_t waves,
+                                              int32_t flex, int64_t out[16], int32_t* pairs, int64_t cap) try {
+  PairPlanHost pp;
+  const auto t0 = std::chrono::steady_clock::now();
+  build_pair_plan(g, m, Gp, Gi, waves, pp, true, flex != 0);
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  std::memset(out, 0, 16 * sizeof(int64_t));
+  check_pair_plan(pp, m, Gp, Gi, waves, out, pairs, pairs != nullptr ? cap : -1);
+  out[11] = (int64_t)(sec * 1e6);
+  out[12] = pp.flex ? 1 : 0;
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 

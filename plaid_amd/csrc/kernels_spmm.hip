@@ -438,7 +438,12 @@ struct SpmmPairArgs {
   // this launch's statistic and beta x kappa (the column's mean score is alpha * sum_i x[i, c] u[i] + beta * kappa: the
   // workgroup stages every x[i, c] anyway), the calibration {offset, half width, ignore-zero}, per (column, wavefront) a
   // slice of `med_capc` candidate scores and the counts {below, zero, NaN, candidates}; med_pred: the predicted means (out)
-  const double* med_u;
+  // (FLEX, which no MED form is: one byte per (slice, wavefront, lane, tile of the wavefront) of a plan with flex steps,
+  // geneset.cpp plan_tile_flex -- in med_u's place, so that the kernel arguments of the other forms stay where they were)
+  union {
+    const double* med_u;
+    const unsigned char* flex;
+  };
   double med_beta_kappa;
   const double* med_cal;
   double* med_pred;
@@ -469,7 +474,13 @@ __device__ __forceinline__ f64x2 lds_pair_at(uint32_t byte_off) {
 // bracket sits around the column's MEAN score, which the workgroup computes from the X it stages: sum_i x[i, c] u[i].
 // PNT: the partial sums of the slice before are read with non-temporal loads (a compile-time form: hipcc merges the two
 // arms of a run-time choice into ONE plain load).
-template <bool STAMP, int ABL = 0, bool CSC_X = false, bool MED = false, bool PNT = false, int BLOCK = 1024, bool REGP = false>
+// FLEX: the plan has flex steps (geneset.cpp, plan_tile_flex; every register-partial plan).  Step 7 of every index chunk adds
+// into an accumulator pair of its own, g: in a HOST lane those cells hold the overflow of one long lane of the tile, in every
+// other lane the lane's own genes.  At a tile end a host leaves g out of its own sum (a select, no arithmetic: a guest's NaN
+// or Inf never meets the host's score) and a lane with a host pulls the host's g across the wavefront (ds_bpermute_b32).  No
+// instruction more per gather; the forms without FLEX are what they were, instruction for instruction.
+template <bool STAMP, int ABL = 0, bool CSC_X = false, bool MED = false, bool PNT = false, int BLOCK = 1024, bool REGP = false,
+          bool FLEX = false>
 __global__ void __launch_bounds__(BLOCK)
 spmm_colpair_f64(SpmmPairArgs a) {
   constexpr int NI = (kMaxLdsGenesPair / 2 + BLOCK - 1) / BLOCK;   // 16-byte loads per lane and column that cover a slice
@@ -477,6 +488,8 @@ spmm_colpair_f64(SpmmPairArgs a) {
   static_assert(!(MED && CSC_X), "the classifying epilogue is built for dense X");
   static_assert(!MED || (BLOCK == 1024 && !REGP), "the classifying epilogue sums 16 wavefronts and meets no register-partial plan");
   static_assert(!REGP || !PNT, "no scratch to read in the register-partial form");
+  static_assert(!FLEX || (BLOCK == kPairRegWaves * 64 && !MED && ABL == 0), "flex steps: 168 vector registers, plain forms only");
+  static_assert(!REGP || FLEX, "every register-partial plan has flex steps");
   if (spec_guard(a.spec, a.spec_gen, a.flags)) return;
   if constexpr (CSC_X) {
     if (a.sparse_cells != 0 && ((int64_t)a.Xp[a.n] - a.Xp[0]) * 8 < a.sparse_cells) return;
@@ -716,6 +729,18 @@ spmm_colpair_f64(SpmmPairArgs a) {
 #define PLAIDHIP_ADD4(V)                                                       \
   a0 += (V##0).x; b0 += (V##0).y; a1 += (V##1).x; b1 += (V##1).y;                       \
   a2 += (V##2).x; b2 += (V##2).y; a3 += (V##3).x; b3 += (V##3).y;
+/* FLEX: the seven own steps of a chunk rotate over a0..a2 and the flex step (the last of the second half) has a3 / b3 --  \
+   a fifth accumulator pair does not fit 168 vector registers */
+#define PLAIDHIP_ADD4A(V)                                                      \
+  if constexpr (FLEX) {                                                        \
+    a0 += (V##0).x; b0 += (V##0).y; a1 += (V##1).x; b1 += (V##1).y;            \
+    a2 += (V##2).x; b2 += (V##2).y; a0 += (V##3).x; b0 += (V##3).y;            \
+  } else { PLAIDHIP_ADD4(V) }
+#define PLAIDHIP_ADD4B(V)                                                      \
+  if constexpr (FLEX) {                                                        \
+    a1 += (V##0).x; b1 += (V##0).y; a2 += (V##1).x; b2 += (V##1).y;            \
+    a0 += (V##2).x; b0 += (V##2).y; a3 += (V##3).x; b3 += (V##3).y;            \
+  } else { PLAIDHIP_ADD4(V) }
 #define PLAIDHIP_EPI(sum, cc, out_)                                            \
   {                                                                            \
     const double w_ = is_mean ? mw : 1.0;                                      \
@@ -756,8 +781,31 @@ spmm_colpair_f64(SpmmPairArgs a) {
   }
 #define PLAIDHIP_TILE_END(chv)                                                                 \
   if ((chv) + 1 == next_end) { /* wave-uniform: tile finished */                               \
-    const double sumA = ((a0 + a1) + (a2 + a3)) + old.x;                                       \
-    const double sumB = ((b0 + b1) + (b2 + b3)) + old.y;                                       \
+    double sumA, sumB;                                                                         \
+    if constexpr (FLEX) {   /* a3 / b3: the flex sums */                                       \
+      double ownA_ = (a0 + a1) + a2;                                                           \
+      double ownB_ = (b0 + b1) + b2;                                                           \
+      const uint32_t fb = (uint32_t)(fx >> ((k - tk_begin) * 8));                              \
+      if (__ballot((fb & 0x80u) != 0u) == 0ull) {   /* wave-uniform: nobody has a host in this tile */ \
+        ownA_ += a3;                                                                           \
+        ownB_ += b3;                                                                           \
+      } else {                                                                                 \
+      const int src_ = (int)((fb & 63u) << 2);                                                 \
+      const double pullA_ = __hiloint2double(__builtin_amdgcn_ds_bpermute(src_, __double2hiint(a3)),  \
+                                             __builtin_amdgcn_ds_bpermute(src_, __double2loint(a3))); \
+      const double pullB_ = __hiloint2double(__builtin_amdgcn_ds_bpermute(src_, __double2hiint(b3)),  \
+                                             __builtin_amdgcn_ds_bpermute(src_, __double2loint(b3))); \
+      ownA_ += (fb & 0x40u) ? 0.0 : a3;                                                        \
+      ownB_ += (fb & 0x40u) ? 0.0 : b3;                                                        \
+      ownA_ += (fb & 0x80u) ? pullA_ : 0.0;                                                    \
+      ownB_ += (fb & 0x80u) ? pullB_ : 0.0;                                                    \
+      }                                                                                        \
+      sumA = ownA_ + old.x;                                                                    \
+      sumB = ownB_ + old.y;                                                                    \
+    } else {                                                                                   \
+      sumA = ((a0 + a1) + (a2 + a3)) + old.x;                                                  \
+      sumB = ((b0 + b1) + (b2 + b3)) + old.y;                                                  \
+    }                                                                                          \
     if (!last) {                                                                               \
       if constexpr (REGP) {                                                                    \
         PLAIDHIP_RSLOT_PUT(k - tk_begin, (f64x2{sumA, sumB}))                                  \
@@ -798,6 +846,7 @@ spmm_colpair_f64(SpmmPairArgs a) {
       } else old = (PH_PAIR_PLD_NT || PNT) ? __builtin_nontemporal_load(src_) : *src_;     \
     }                                                                                          \
     a0 = a1 = a2 = a3 = b0 = b1 = b2 = b3 = 0.0;                                               \
+                                                                                         \
   }
         // 8 index chunks (8 KiB per wave) in flight: the lists come from L2 (~1 us away under load)
         u32x4 qa = PLAIDHIP_LOADQ(0);
@@ -819,6 +868,11 @@ spmm_colpair_f64(SpmmPairArgs a) {
           mw = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.meta_w) + (int64_t)k * 512 + moff8);
           mk = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.meta_k) + (int64_t)k * 512 + moff8);
         }
+        // FLEX: this lane's flex bytes of the wavefront's (at most eight) tiles in this slice -- one load in front of the loop
+        // (a load per tile would have the tile end wait for the index loads issued behind it)
+        unsigned long long fx = 0ull;
+        if constexpr (FLEX)
+          fx = *(__attribute__((address_space(1))) const unsigned long long*)((gptr_u8)a.flex + ((int64_t)(si * 16 + wave) * 64) * 8 + lane_o * 8u);
         f64x2 old = f64x2{0.0, 0.0};
         if constexpr (REGP) {
           if (!first) old = r0;
@@ -835,13 +889,13 @@ spmm_colpair_f64(SpmmPairArgs a) {
 #define PLAIDHIP_STEP(qcur, qnext, rel, chv)                                             \
   PLAIDHIP_GATHER4B(qcur)                                                                \
   qcur = PLAIDHIP_LOADQ(rel);                                                            \
-  PLAIDHIP_ADD4(va)                                                                      \
+  PLAIDHIP_ADD4A(va)                                                                     \
   PLAIDHIP_GATHER4A(qnext) /* first half of the next chunk (spare chunks exist behind the stream) */ \
-  PLAIDHIP_ADD4(vb)                                                                      \
+  PLAIDHIP_ADD4B(vb)                                                                     \
   PLAIDHIP_TILE_END(chv)
 #define PLAIDHIP_STEP_TAIL(qcur, qnext)                                                  \
   if (ch < ch_end) {                                                                     \
-    PLAIDHIP_GATHER4B(qcur) PLAIDHIP_ADD4(va) PLAIDHIP_GATHER4A(qnext) PLAIDHIP_ADD4(vb) \
+    PLAIDHIP_GATHER4B(qcur) PLAIDHIP_ADD4A(va) PLAIDHIP_GATHER4A(qnext) PLAIDHIP_ADD4B(vb)\
     PLAIDHIP_TILE_END(ch)                                                                \
     ++ch;                                                                                \
   }
@@ -868,6 +922,8 @@ spmm_colpair_f64(SpmmPairArgs a) {
 #undef PLAIDHIP_GATHER4A
 #undef PLAIDHIP_GATHER4B
 #undef PLAIDHIP_ADD4
+#undef PLAIDHIP_ADD4A
+#undef PLAIDHIP_ADD4B
 #undef PLAIDHIP_TILE_END
 #undef PLAIDHIP_EPI
 #undef PLAIDHIP_MED_CLASSIFY
@@ -2237,11 +2293,12 @@ static int launch_colpair(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const d
   for (const plaidhip_pair_slice& sl : pl.slices) gmax = sl.gs > gmax ? sl.gs : gmax;
   const size_t smem = (size_t)(gmax + kPadSlotsPair) * 16;
   // A plan built for kPairRegWaves wavefronts with at most kPairRegPartials tiles each (geneset.cpp) runs at 768 threads with
-  // the partial sums of the slices in registers: no scratch, no store and no load at the tile ends.  Option value 4 pins
-  // the 1,024-thread scratch form on the same plan (its last four wavefronts then have no tiles): same tiles, same sums.
+  // the partial sums of the slices in registers: no scratch, no store and no load at the tile ends.  Such a plan has flex
+  // steps (geneset.cpp, plan_tile_flex), which only the FLEX forms of the kernel walk.  Option value 4 pins the scratch form
+  // on the same plan, also at 768 threads (the 1,024-thread forms have no register for the flex sums): same tiles, same sums.
   const bool regp = pl.regp && ctx->opt_dense_kernel != 4 && (g_ablate == 0 || g_ablate == 4);
-  if (regp && med != nullptr) {
-    set_error("pair kernel: the classifying epilogue met a register-partial plan (%d sets)", gs->m);
+  if (pl.regp && (pl.d_flex == nullptr || med != nullptr)) {
+    set_error("pair kernel: a register-partial plan (%d sets) %s", gs->m, med != nullptr ? "met the classifying epilogue" : "has no flex table");
     return PLAIDHIP_EINVAL;
   }
   if (!regp && pl.slices.size() > 1 && pl.d_partial == nullptr) {
@@ -2281,6 +2338,7 @@ static int launch_colpair(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const d
   a.flags = flags;
   a.spec = spec;
   a.spec_gen = spec_gen;
+  a.flex = pl.d_flex;
   int per_cu = (int)(kLdsBytes / smem);
   if (per_cu > 2) per_cu = 2;
   if (per_cu < 1) per_cu = 1;
@@ -2290,8 +2348,8 @@ static int launch_colpair(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const d
   if (regp) {
     a.partial = nullptr;
     if (Xp != nullptr) {   // sparse X
-      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, true>));
-      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, true>), dim3(grid),
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, true, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, true, true>), dim3(grid),
                          dim3(kPairRegWaves * 64), smem, ctx->stream, a);
     }
 #ifdef PLAIDHIP_DIAG
@@ -2300,8 +2358,18 @@ static int launch_colpair(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const d
 #undef PH_DIAG_SECTION
 #endif
     else {
-      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, true>));
-      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, true>), dim3(grid),
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, true, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, true, true>), dim3(grid),
+                         dim3(kPairRegWaves * 64), smem, ctx->stream, a);
+    }
+  } else if (pl.regp) {   // the scratch form pinned on a plan with flex steps (the reference the tests hold the register form to)
+    if (Xp != nullptr) {
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, false, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, true, false, false, kPairRegWaves * 64, false, true>), dim3(grid),
+                         dim3(kPairRegWaves * 64), smem, ctx->stream, a);
+    } else {
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, false, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<false, 0, false, false, false, kPairRegWaves * 64, false, true>), dim3(grid),
                          dim3(kPairRegWaves * 64), smem, ctx->stream, a);
     }
   } else if (med != nullptr) {   // dense X, medians selected on the fly

@@ -117,8 +117,8 @@ void debug_set_ablation(int mode, void* dbg) { g_ablate = mode; g_dbg = static_c
 #if PH_DIAG_SECTION == 15
     else if (g_ablate == 4) {   // in-kernel stamps of the 768-thread register-partial form (tools/ only)
       a.dbg = g_dbg;
-      PH_FULL_LDS(ctx, (&spmm_colpair_f64<true, 0, false, false, false, kPairRegWaves * 64, true>));
-      hipLaunchKernelGGL((spmm_colpair_f64<true, 0, false, false, false, kPairRegWaves * 64, true>), dim3(grid),
+      PH_FULL_LDS(ctx, (&spmm_colpair_f64<true, 0, false, false, false, kPairRegWaves * 64, true, true>));
+      hipLaunchKernelGGL((spmm_colpair_f64<true, 0, false, false, false, kPairRegWaves * 64, true, true>), dim3(grid),
                          dim3(kPairRegWaves * 64), smem, ctx->stream, a);
     }
 #endif
