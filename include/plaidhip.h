@@ -1273,9 +1273,10 @@ int plaidhip_zscore_multi(const int* devices, int ndev, const int32_t* Xp, const
  *     each may be NULL.  `fit` is the number its messages name.
  *   plaidhip_limma_finish (host only): step 3 and the output from E ([W][rows]), rss ([nfit][rows]), nf (nfit), v
  *     (p x q x nfit) and u (q x nfit).  Tails and Benjamini-Hochberg are dealt to at most 8 host threads.
- * Not offered: trend = TRUE and robust = TRUE; array or observation weights; the B-statistic and the F-statistic; a
- * dgCMatrix input; fusing a scorer with the test so that the scores never leave the device.  In plaidhip_limma a NaN in a
- * used sample makes the row NaN; plaidhip_limma_na (below) refits such a row on the samples it has.
+ * Not offered: trend = TRUE and robust = TRUE; the B-statistic and the F-statistic; a dgCMatrix input; fusing a scorer with
+ * the test so that the scores never leave the device.  In plaidhip_limma a NaN in a used sample makes the row NaN;
+ * plaidhip_limma_na (below) refits such a row on the samples it has; plaidhip_limma_w (below) takes array and observation
+ * weights.
  *
  * plaidhip_limma_na / _na_multi: na = "fit", limma's handling of per-row missing values (lmFit refits a row with NA on the
  * samples it has) and gx.limma's max.na.  The operands of plaidhip_limma plus max_na, and dfres.  DESIGN.md section 24.
@@ -1323,7 +1324,116 @@ int plaidhip_zscore_multi(const int* devices, int ndev, const int32_t* Xp, const
  *     in ascending c; Ep: E' (p); nobs = |obs|; v: p x q.  Writes gamma (p), u (q), *ok and the pivots d_k (p, may be
  *     NULL; NaN past the pivot that broke the rule).
  *   plaidhip_limma_finish_na (host only): plaidhip_limma_finish with drow ([nfit][rows]: d_r, NaN for a row that is not
- *     fitted) and urow ([nfit q][rows]) in place of u, and hyper nfit x 5. */
+ *     fitted) and urow ([nfit q][rows]) in place of u, and hyper nfit x 5.
+ *
+ * plaidhip_limma_w / _w_multi: lmFit with precision weights -- limma's `weights` (observation weights: voom's, or quality
+ * weights from upstream) and array weights -- then eBayes and topTable as above.  DESIGN.md section 28.  The operands of
+ * plaidhip_limma_na plus Wt (rows x n doubles, column-major, may be NULL) and aw (n doubles, may be NULL); both NULL is
+ * PLAIDHIP_EINVAL (plaidhip_limma and plaidhip_limma_na are the entries without weights).  The outputs are those of
+ * plaidhip_limma_na: out, hyper (nfit x 5) and dfres.  A missing value is a weight of 0: this is the general case of na = "fit".
+ * - Effective weight: omega_rc = Wt[r, c] * aw[c], one rounded product; a NULL operand counts as 1.0 and no product is taken.
+ * - Live observations: (r, c) is live in fit f iff c is in sel_f, x_rc == x_rc, and 0 < omega_rc < +Inf.  As in limma, a
+ *   weight that is zero, negative, NaN or infinite makes the observation missing.  A live +-Inf VALUE makes the row NaN in
+ *   that fit, as above.
+ * - max_na keeps its meaning: the share of NaN in x over all n columns; weights do not count.
+ * - The basis: Q_f, R_f and v_j are exactly step 1 of plaidhip_limma, the UNWEIGHTED QR of the design; the weights enter
+ *   per row.  Per fit, a table of n x p (p + 1) / 2 products pi_c,kl = q_ck * q_cl (l <= k), each rounded once.
+ * - Per row, on the device (kernels_lmfit_w.hip); every sum runs over the columns of a block of 128 in ascending order from
+ *   0.0 and the blocks are added in ascending order, the rule of step 2:
+ *     H_kl = live ? fma(omega_rc, pi_c,kl, .) : unchanged                  (l <= k)
+ *     b_k  = live ? fma(y_rc, q_ck, .) : unchanged,   y_rc = omega_rc * x_rc rounded once
+ *     M'   = step 2's chain with the select "c in sel and x == x" and the weight 1 / n_f, IGNORING omega
+ *     AveExpr = (M' * (double)n_f) / (double)count, count the size of that select
+ *   (limma's rowMeans(y, na.rm = TRUE): a value with a zero weight still counts in AveExpr).
+ * - The solve: H = L L', L y = b, L' gamma = y, u_j and logFC = v_j' gamma by the inline functions of csrc/lmfit_na.h that
+ *   na = "fit" uses, in their order.  The pivot rule is RELATIVE here: the row is not estimable when a pivot d_k <=
+ *   1e-10 * H_kk (one rounded product; H_kk the diagonal entry before elimination) or d_k is NaN.  H scales with the
+ *   weights, and scaling all weights by a power of two commutes with every rounding, so it changes no logFC bit and no
+ *   decision.  (na = "fit" keeps its absolute rule, to the bit: the factorisation takes the tolerance as a parameter.)
+ * - Degrees of freedom: d_r = |live| - p; d_r < 1 is not estimable.  A pair that is not estimable, or whose row is above
+ *   max_na, is NaN in that fit and not ok.
+ * - Residuals: r_c is step 2's fma chain from x_c at gamma;  RSS = live ? fma(omega_rc, r_c * r_c, .) : unchanged, with
+ *   r_c * r_c rounded first;  s2 = RSS / d_r.
+ * - eBayes and the output: plaidhip_limma_finish_na as it stands, with drow = d_r and urow = the rows' u_j.
+ * - All weights 1 with no NaN is NOT the bits of plaidhip_limma (H is summed, not taken as I); it agrees with it within the
+ *   bound of DESIGN.md section 28, and the integers (dfres, n_ok, df.pooled) are equal.
+ * - p <= PLAIDHIP_LIMMA_NA_MAX_COEF.
+ * - Argument errors: those of plaidhip_limma_na in their order, with, after "max_na outside [0, 1] or NaN": Wt and aw both
+ *   NULL, then nfit (p (p + 1) / 2 + p + 1) weight columns in more than 65,535 tiles of PLAIDHIP_LIMMA_TILE.  The entries of
+ *   Wt and aw are not checked: what is not a positive finite number is a missing observation.
+ * - How: a table kernel (the products and the masks), one fused pass that reads x and omega once per column and tile of 8
+ *   of the nfit (p (p + 1) / 2 + p + 1) weight columns (pi, q and 1 / n_f are wave-uniform; the per-row factor is omega, y or
+ *   x by the column's kind), a count pass (|live|, the mean's count and the row's NaN as exact doubles that take the road of
+ *   the sums), the solve with one thread per (row, fit) and H in LDS, and the weighted RSS pass.  _w_multi: sample shards at
+ *   multiples of 128 columns; the sums and counts are handed from shard to shard as seeds, one device solves, and the RSS is
+ *   handed on likewise: every sharding, with more shards than samples too, has the one-device bits.  A failing shard reports
+ *   and nothing is written.
+ *   plaidhip_dev_limma_w_sums / _w_rss: the passes on device pointers, stream-ordered.  A and Wt: rows x n with the leading
+ *     dimension ld (Wt may be NULL), aw: n or NULL, Q / use / invn as plaidhip_dev_row_design_effects.  S: [nfit Wc][rows], Wc
+ *     = p (p + 1) / 2 + p + 1: fit f's triangle of H row by row, then b, then M'.  cnt (may be NULL): [2 nfit + 1][rows]:
+ *     |live| and the mean's count of every fit, then the row's NaN.  seed / seed_cnt (NULL: zeros): the sums of the shards
+ *     before this one.  _w_rss: rss [nfit][rows] at G ([nfit (p + 1)][rows]: gamma of every pair; the mean's row is not read).
+ *   plaidhip_limma_w_solve (host only): one row from its sums, the one copy of the arithmetic the device runs
+ *     (lmfit_w_row_solve).  Htri: H's lower triangle row by row (p (p + 1) / 2), b (p), nlive = |live|, v: p x q.  Writes
+ *     gamma (p), u (q), *ok and the pivots d_k (p, may be NULL; NaN past the pivot that broke the rule).
+ *   Both dev entries take Wt and aw both NULL as well (omega = 1.0 everywhere): they are passes, not the fit.
+ * Not offered (out of scope): weights in plaid.camera, plaid.fry and plaid.roast; voomWithQualityWeights, arrayWeights and
+ * duplicateCorrelation (estimating weights or correlations); trend and robust.
+ *
+ * plaidhip_voom / _voom_multi: plaid.voom(counts, design, lib.size = NULL, span = 0.5), limma's voom with normalize.method =
+ * "none" AS RECALLED: counts to log2-CPM and a precision weight for every observation from the mean-variance trend, for one
+ * design and all samples.  Its E and weights feed plaidhip_limma_w (limma's lmFit on an EList).  DESIGN.md section 28.
+ * Operands: counts rows x n doubles, column-major; design n x p, 1 <= p <= PLAIDHIP_LIMMA_MAX_COEF; lib_size n doubles or NULL.
+ * 1. The check, on the device before anything is written: every count is finite and >= 0, else PLAIDHIP_EINVAL.  Column
+ *    sums: thread t of 256 adds the rows t, t + 256, ... of the column in ascending order from 0.0 and the 256 partials are
+ *    folded in halves (s_t += s_{t + off}, off = 128, 64, ..., 1) -- exact for integer counts with sums < 2^53, whatever the
+ *    order.  lib.size L_c = lib_size[c], or the column sum when NULL.  Row sums: over the columns of a block of 128 in
+ *    ascending order from 0.0, the blocks added in ascending order; a row is "all zero" iff its row sum is 0.
+ * 2. E_rc = log2(((counts_rc + 0.5) / (L_c + 1.0)) * 1e6), in that operation order, on the device (its log2).
+ * 3. The unweighted fit of E on the design: steps 1 and 2 of plaidhip_limma give the effects E_k, the mean M and RSS;
+ *    s2 = RSS / (n - p).
+ * 4. Trend points, on the host: sx = M + (ml - log2(1e6)), ml = (sum over c ascending from 0.0 of log2(L_c + 1.0)) / n, and
+ *    sy = sqrt(sqrt(s2)), over the rows that are not all zero and have a finite s2, sorted by sx, ties in row order.  No
+ *    such row: PLAIDHIP_EINVAL.
+ * 5. lowess(sx, sy, f = span, iter = 3, delta = 0.01 * (max - min)) on the host: plaidhip_lowess below.
+ * 6. The knots are the anchor points of lowess's last pass -- where the local fit or a tie copy was made -- with their fitted
+ *    values, one per distinct x (the first): at most PLAIDHIP_VOOM_MAX_KNOTS, else PLAIDHIP_EINVAL (with this delta there are
+ *    at most 202: every second anchor lies more than delta beyond the one two back).  f(lambda): the end values outside the
+ *    knots (rule = 2: Y_0 for lambda <= X_0, Y_last for lambda >= X_last); else bisection (lo = 0, hi = last; mid = (lo + hi)
+ *    / 2 takes lo when X_mid <= lambda, else hi, until hi - lo = 1) finds the largest k with X_k <= lambda and
+ *    f = Y_k + (Y_{k+1} - Y_k) * ((lambda - X_k) / (X_{k+1} - X_k)), which is exactly Y_k at a knot.
+ * 7. Weights, on the device: mu_rc = the fma chain of Q[c, k] E_k in ascending k from 0.0; lambda_rc = mu_rc + offset_c with
+ *    offset_c = log2(L_c + 1.0) - log2(1e6) made on the host and returned; w_rc = 1.0 / ((f * f) * (f * f)).  limma goes
+ *    through 2^mu and back to the log scale; this stays on it (a stated deviation, a few ulp of lambda).  f <= 0 or NaN gives
+ *    the weight NaN, which plaidhip_limma_w treats as a missing observation.
+ * Outputs: E and W rows x n column-major; lib_out and offset n; knots_x and knots_y PLAIDHIP_VOOM_MAX_KNOTS doubles each (NaN
+ * past *nknots).  rows == 0 or n == 0: PLAIDHIP_OK with nothing written.  Nothing is written before every device pass of
+ * every shard is done.
+ * Argument errors, in this order, PLAIDHIP_EINVAL before any device is touched: bad dims; p outside
+ * 1..PLAIDHIP_LIMMA_MAX_COEF; span outside (0, 1] or NaN; a null design; a null counts or output; a lib_size entry that is not
+ * finite and >= 0; then the design's own faults as plaidhip_limma reports them.  Then, on the device: a bad count.
+ * plaidhip_voom_multi shards the SAMPLES at multiples of 128 columns: every pass is column-local except the check's flag, the
+ * row sums and the fit's sums, which are handed from shard to shard in the order of the one-device call; one shard fits the
+ * trend.  Every sharding, with more shards than samples too, has the one-device bits.
+ *   plaidhip_dev_voom_weights: step 7 on device pointers, stream-ordered: Q n x p, offset n, Eff [p + 1][rows] (the effects;
+ *     the last row is not read), the knots, W rows x n with leading dimension ldw.  nknots outside 1..PLAIDHIP_VOOM_MAX_KNOTS
+ *     is PLAIDHIP_EINVAL with nothing written.
+ *   plaidhip_lowess (host only): R's lowess AS RECALLED.  x ascending and finite, n >= 1; ys: n fitted values; anchor (may be
+ *     NULL): n flags, 1 where the last pass made a local fit or a tie copy.  ns = max(2, min(n, floor(f n + 1e-7))); robustness
+ *     weights start at 1; iter + 1 fitting passes.  A pass: i = 0, last = -1, window [nleft, nright] = [0, ns - 1]; while
+ *     nright < n - 1 and x_i - x_nleft > x_(nright+1) - x_i the window moves right by one; ys_i is the local fit (y_i if it
+ *     fails); the points between last and i get alpha ys_i + (1 - alpha) ys_last, alpha = (x_j - x_last) / (x_i - x_last);
+ *     last = i, cut = x_last + delta; scan forward from last + 1 until x > cut, a point with x == x_last copies ys and becomes
+ *     last; i = max(last + 1, stop - 1); the pass ends when last >= n - 1.  The local fit at xs: h = max(xs - x_nleft, x_nright
+ *     - xs); for j from nleft upward with r = |x_j - xs| <= 0.999 h: w_j = 1 if r <= 0.001 h, else t = r / h, u = 1 - (t t) t,
+ *     w_j = (u u) u, times the robustness weight from the second pass on; stop at the first x_j > xs outside 0.999 h; it fails
+ *     if sum w <= 0; else w is normalised and, if h > 0: a = sum w x, c = sum w ((x - a)(x - a)), and if sqrt(c) > 0.001 (x_max
+ *     - x_min): w_j *= ((xs - a) / c)(x_j - a) + 1; ys = sum w y.  After every pass but the last: res = y - ys; cmad = 6 median
+ *     |res| (the mean of the middle two for even n); stop if cmad < 1e-7 mean|res|; the robustness weight is 1 for |res| <=
+ *     0.001 cmad, (1 - (res / cmad)^2)^2 up to 0.999 cmad, 0 beyond.  Every sum ascending from 0.0, no fused operation.
+ * Not offered (out of scope): normalize.method other than "none"; voomWithQualityWeights, arrayWeights, duplicateCorrelation;
+ * trend and robust; a dgCMatrix of counts; weights in plaid.camera, plaid.fry and plaid.roast. */
+#define PLAIDHIP_VOOM_MAX_KNOTS 256
 #define PLAIDHIP_LIMMA_MAX_COEF 32
 #define PLAIDHIP_LIMMA_NA_MAX_COEF 10         /* 10 * 11 / 2 = 55 entries of the triangle <= the 64 lanes of a wavefront */
 #define PLAIDHIP_LIMMA_TILE 8
@@ -1353,6 +1463,30 @@ int plaidhip_limma_na_solve(int32_t p, int32_t nmis, const double* qmis, const d
 int plaidhip_limma_finish_na(int32_t rows, int32_t p, int32_t nfit, int32_t q, const double* E, const double* rss,
                              const int64_t* nf, const double* v, const double* drow, const double* urow, double* out,
                              double* hyper);
+int plaidhip_limma_w(plaidhip_ctx* ctx, const double* A, const double* Wt, const double* aw, int32_t rows, int32_t n,
+                     const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na,
+                     double* out, double* hyper, double* dfres);
+int plaidhip_limma_w_multi(const int* devices, int ndev, const double* A, const double* Wt, const double* aw, int32_t rows,
+                           int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q,
+                           double max_na, double* out, double* hyper, double* dfres);
+int plaidhip_dev_limma_w_sums(plaidhip_ctx* ctx, const double* A, const double* Wt, const double* aw, int64_t ld, int32_t rows,
+                              int32_t n, const double* Q, const int8_t* use, const double* invn, int32_t p, int32_t nfit,
+                              const double* seed, double* S, const double* seed_cnt, double* cnt);
+int plaidhip_dev_limma_w_rss(plaidhip_ctx* ctx, const double* A, const double* Wt, const double* aw, int64_t ld, int32_t rows,
+                             int32_t n, const double* Q, const int8_t* use, int32_t p, int32_t nfit, const double* G,
+                             const double* seed, double* rss);
+int plaidhip_limma_w_solve(int32_t p, const double* Htri, const double* b, int64_t nlive, const double* v, int32_t q,
+                           double* gamma, double* u, double* pivots, int32_t* ok);
+int plaidhip_voom(plaidhip_ctx* ctx, const double* counts, int32_t rows, int32_t n, const double* design, int32_t p,
+                  const double* lib_size, double span, double* E, double* W, double* lib_out, double* offset, double* knots_x,
+                  double* knots_y, int32_t* nknots);
+int plaidhip_voom_multi(const int* devices, int ndev, const double* counts, int32_t rows, int32_t n, const double* design,
+                        int32_t p, const double* lib_size, double span, double* E, double* W, double* lib_out, double* offset,
+                        double* knots_x, double* knots_y, int32_t* nknots);
+int plaidhip_dev_voom_weights(plaidhip_ctx* ctx, const double* Q, const double* offset, int32_t n, int32_t p, const double* Eff,
+                              int32_t rows, const double* knots_x, const double* knots_y, int32_t nknots, double* W, int64_t ldw);
+int plaidhip_lowess(const double* x, const double* y, int64_t n, double f, int32_t iter, double delta, double* ys,
+                    int8_t* anchor);
 
 /* plaid.camera(X, design, G, contrasts): limma's competitive gene-set test camera (Wu & Smyth 2012) for every set, contrast
  * and design -- the one common set test that corrects a set's p-value for the correlation between its genes.  The form is

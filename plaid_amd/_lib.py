@@ -175,6 +175,15 @@ SIGNATURES = {
     "plaidhip_limma_na": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _vp],
     "plaidhip_limma_na_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _vp],
     "plaidhip_limma_na_solve": [_i32, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+    "plaidhip_limma_w": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _vp],
+    "plaidhip_limma_w_multi": [_vp, _int, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _vp, _vp, _vp],
+    "plaidhip_limma_w_solve": [_i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+    "plaidhip_dev_limma_w_sums": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "plaidhip_dev_limma_w_rss": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "plaidhip_voom": [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_voom_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_dev_voom_weights": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64],
+    "plaidhip_lowess": [_vp, _vp, _i64, _f64, _i32, _f64, _vp, _vp],
     "plaidhip_limma_finish_na": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "plaidhip_camera": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _f64, _int, _vp, _vp],
     "plaidhip_camera_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _f64, _int, _vp, _vp],

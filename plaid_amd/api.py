@@ -887,18 +887,37 @@ def _limma_table(tab, rn, sort_by):
     return NamedMatrix(tab, rn, _LIMMA_NAMES + ["df.residual"][:tab.shape[1] - 6])
 
 
-def _limma_run(ctx, A, design, use, contrasts, na, max_na):
-    """(out rows x 6 or 7 x q x nfit, hyper, its names): under na = "fit" the rows' df.residual is the seventh column"""
-    if na == "propagate":
+def _limma_weights(S, weights):
+    """weights of plaid_limma as Context.limma takes them: a NamedMatrix or matrix in S's shape, or a vector over the samples"""
+    if weights is None:
+        return None
+    w = np.asarray(weights.values if isinstance(weights, NamedMatrix) else weights, dtype=np.float64)
+    if w.ndim == 2 and w.shape != S.values.shape:
+        raise ValueError("plaid.limma: a matrix of weights has the shape of S")
+    if w.ndim == 1 and w.shape[0] != S.values.shape[1]:
+        raise ValueError("plaid.limma: a vector of weights has one entry per sample")
+    if w.ndim not in (1, 2):
+        raise ValueError("plaid.limma: weights are a matrix in S's shape or a vector over the samples")
+    return w
+
+
+def _limma_run(ctx, A, design, use, contrasts, na, max_na, weights=None):
+    """(out rows x 6 or 7 x q x nfit, hyper, its names): under na = "fit" or with weights the rows' df.residual is the seventh
+    column"""
+    if na == "propagate" and weights is None:
         out, hyper = ctx.limma(A, design, use, contrasts)
         return out, hyper, _LIMMA_HYPER
-    out, hyper, dfres = ctx.limma(A, design, use, contrasts, na=na, max_na=max_na)
+    if weights is None:
+        out, hyper, dfres = ctx.limma(A, design, use, contrasts, na=na, max_na=max_na)
+    else:
+        out, hyper, dfres = ctx.limma(A, design, use, contrasts, na=na, max_na=max_na, weights=weights)
     dfr = np.broadcast_to(dfres[:, None, None, :], (out.shape[0], 1, out.shape[2], out.shape[3]))
     dfr = np.where(np.isnan(out[:, 5:6, :, :]), np.nan, dfr)
     return np.concatenate([out, dfr], axis=1), hyper, _LIMMA_HYPER_NA
 
 
-def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Context | None = None, na="propagate", max_na=0.2):
+def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Context | None = None, na="propagate", max_na=0.2,
+                weights=None):
     """plaid.limma(): limma's moderated t-test (lmFit + eBayes + topTable, as pinned in include/plaidhip.h) of every row of S
     -- a NamedMatrix of single-sample scores (sets x samples) or of expression (genes x samples) -- for one design (samples
     x coefficients; a NamedMatrix names the coefficients).  contrasts: coefficients x contrasts (a NamedMatrix names them),
@@ -910,7 +929,11 @@ def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Contex
     share max_na of NaN over all samples (gx.limma's max.na) is refitted on the samples it has, with its own df.residual
     and stdev.unscaled, and eBayes takes the unequal df; a row above max_na, or one that is not estimable on what it has,
     is NaN.  The tables then have a seventh column df.residual and hyper has df.pooled; at most 10 coefficients.
-    Not offered: trend, robust, weights, the B- and F-statistics, a sparse S."""
+    weights: None, a matrix in S's shape (observation weights, limma's `weights`: voom's, or quality weights from upstream) or
+    a vector over the samples (array weights).  The fit is then the weighted least squares of every row (plaidhip_limma_w): an
+    observation with a NaN value or a weight that is zero, negative, NaN or infinite is missing, as in limma; the tables are
+    those of na = "fit" (na = "propagate" then fits no row that holds a NaN); at most 10 coefficients.
+    Not offered: trend, robust, the B- and F-statistics, a sparse S; weights in the set tests."""
     S = as_named(S)
     if S.is_sparse:
         raise ValueError("plaid.limma: S must be dense")
@@ -927,20 +950,43 @@ def plaid_limma(S, design, contrasts=None, use=None, sort_by="none", ctx: Contex
         Kv = Kv[:, None] if Kv.ndim == 1 else Kv
         names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
     _limma_table(np.zeros((0, 6)), [], sort_by)   # (an unknown sort_by is refused before the device)
+    wts = _limma_weights(S, weights)              # (and weights of another shape)
     ctx = ctx or default_context()
-    out, hyper, hnames = _limma_run(ctx, S.values, Dv, use, Kv, na, max_na)
+    out, hyper, hnames = _limma_run(ctx, S.values, Dv, use, Kv, na, max_na, wts)
     tables = {nm: _limma_table(out[:, :, j, 0], S.rownames, sort_by) for j, nm in enumerate(names)}
     return tables, dict(zip(hnames, (float(x) for x in hyper[0])))
 
 
-def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = None, na="propagate", max_na=0.2):
+def plaid_voom(counts, design, lib_size=None, span=0.5, ctx: Context | None = None):
+    """plaid.voom(): limma's voom with normalize.method = "none" (as pinned in include/plaidhip.h: plaidhip_voom) of a counts
+    matrix (genes x samples, finite and >= 0) for one design (samples x coefficients).  lib_size: one entry per sample, None: the
+    column sums.  span: the lowess span of the mean-variance trend.  Returns a dict: E (NamedMatrix of log2-CPM), weights
+    (NamedMatrix of precision weights), lib.size, offset (log2(lib.size + 1) - log2(1e6)) and the trend's knots (knots.x,
+    knots.y).  plaid_limma(E, design, weights=weights) is limma's lmFit + eBayes on that EList.
+    Not offered: other normalize.method, voomWithQualityWeights, arrayWeights, duplicateCorrelation, sparse counts."""
+    S = as_named(counts)
+    if S.is_sparse:
+        raise ValueError("plaid.voom: counts must be dense")
+    Dv = np.asarray(design.values if isinstance(design, NamedMatrix) else design, dtype=np.float64)
+    if Dv.ndim != 2 or Dv.shape[0] != S.values.shape[1]:
+        raise ValueError("plaid.voom: design must be samples x coefficients, one row per column of counts")
+    if not (0.0 < float(span) <= 1.0):
+        raise ValueError("plaid.voom: span must lie in (0, 1]")
+    ctx = ctx or default_context()
+    r = ctx.voom(S.values, Dv, lib_size, span)
+    return {"E": NamedMatrix(r["E"], S.rownames, S.colnames), "weights": NamedMatrix(r["weights"], S.rownames, S.colnames),
+            "lib.size": r["lib_size"], "offset": r["offset"], "knots.x": r["knots_x"], "knots.y": r["knots_y"]}
+
+
+def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = None, na="propagate", max_na=0.2, weights=None):
     """plaid.limma.contrasts(): the reference's gx.limma(S, y, B, method = 1) for every column of the contrast matrix Y
     (samples x contrasts; 0, 1, and NaN or -1 for a sample that takes no part) in one call: contrast j fits the design
     [1, Y[, j], B] on the samples with a label and tests the coefficient of Y[, j].  B: batch covariates, samples x
     covariates, or None.  S is uploaded once and read ceil(C (p + 1) / 8) times for the effects, p = 2 + ncol(B).  Y: a
     NamedMatrix (its column names name the contrasts) or an array (contrasts "1", "2", ...).  Returns (tables, hyper):
     contrast name -> the NamedMatrix plaid_limma returns, and contrast name -> its hyper-parameters.  na, max_na: as
-    plaid_limma; with na = "fit" and max_na = 0.2 this is gx.limma(S, y, B, max.na = 0.2) on a matrix with missing values."""
+    plaid_limma; with na = "fit" and max_na = 0.2 this is gx.limma(S, y, B, max.na = 0.2) on a matrix with missing values.
+    weights: as plaid_limma, shared by the contrasts."""
     from .engine import contrast_labels
     S = as_named(S)
     if S.is_sparse:
@@ -964,8 +1010,9 @@ def plaid_limma_contrasts(S, Y, B=None, sort_by="none", ctx: Context | None = No
     K = np.zeros((p, 1))
     K[1, 0] = 1.0
     _limma_table(np.zeros((0, 6)), [], sort_by)
+    wts = _limma_weights(S, weights)
     ctx = ctx or default_context()
-    out, hyper, hnames = _limma_run(ctx, S.values, D, lab != -1, K, na, max_na)
+    out, hyper, hnames = _limma_run(ctx, S.values, D, lab != -1, K, na, max_na, wts)
     tables = {nm: _limma_table(out[:, :, 0, j], S.rownames, sort_by) for j, nm in enumerate(names)}
     return tables, {nm: dict(zip(hnames, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
 

@@ -1332,6 +1332,83 @@ int plaidhip_dev_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, 
   return dev_row_design_pass(ctx, "row_design_rss", A, ld, rows, n, Q, use, nullptr, p, nfit, E, true, seed, rss);
 } catch (...) { return plaidhip::on_exception(); }
 
+// plaid.voom: the one-device form of the sharded engine (shard_voom.cpp: voom_worker, kVoom)
+int plaidhip_voom(plaidhip_ctx* ctx, const double* counts, int32_t rows, int32_t n, const double* design, int32_t p,
+                  const double* lib_size, double span, double* E, double* W, double* lib_out, double* offset, double* knots_x,
+                  double* knots_y, int32_t* nknots) try {
+  return dispatch(on_context(ctx),
+                  voom_call(counts, rows, n, design, p, lib_size, span, E, W, lib_out, offset, knots_x, knots_y, nknots));
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.voom's weights pass on device pointers (kernels_voom.hip), stream-ordered
+int plaidhip_dev_voom_weights(plaidhip_ctx* ctx, const double* Q, const double* offset, int32_t n, int32_t p, const double* Eff,
+                              int32_t rows, const double* knots_x, const double* knots_y, int32_t nknots, double* W,
+                              int64_t ldw) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ldw >= rows, "voom_weights: bad shape rows=%d n=%d ldw=%lld", rows, n, (long long)ldw);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "voom_weights: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(nknots >= 1 && nknots <= PLAIDHIP_VOOM_MAX_KNOTS, "voom_weights: %d knots (1 <= knots <= %d)", nknots,
+             PLAIDHIP_VOOM_MAX_KNOTS);
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Q && offset && Eff && knots_x && knots_y && W, "voom_weights: null argument");
+  return launch_voom_weights(ctx, Q, offset, n, p, Eff, rows, knots_x, knots_y, nknots, W, ldw);
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.limma with weights: the one-device form of the sharded engine (shard_limma_w.cpp: limma_w_worker)
+int plaidhip_limma_w(plaidhip_ctx* ctx, const double* A, const double* Wt, const double* aw, int32_t rows, int32_t n,
+                     const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na,
+                     double* out, double* hyper, double* dfres) try {
+  return dispatch(on_context(ctx), limma_w_call(A, Wt, aw, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the two device passes of the weighted fit on device pointers (kernels_lmfit_w.hip).  The workspace holds the block partials,
+// then the masks, then the table of products; the counts' partials take the partials' place after the sums are reduced.
+static int dev_limma_w_pass(plaidhip_ctx* ctx, const char* what, const double* A, const double* Wt, const double* aw, int64_t ld,
+                            int32_t rows, int32_t n, const double* Q, const int8_t* use, const double* invn, int32_t p,
+                            int32_t nfit, const double* G, bool rss, const double* seed, double* out, const double* seed_cnt,
+                            double* cnt) {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && n >= 0 && ld >= rows && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS,
+             "%s: bad shape rows=%d n=%d ld=%lld nfit=%d (nfit <= %d)", what, rows, n, (long long)ld, nfit, PLAIDHIP_LIMMA_MAX_FITS);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "%s: p = %d coefficients (1 <= p <= %d)", what, p,
+             PLAIDHIP_LIMMA_NA_MAX_COEF);
+  PH_REQUIRE(n <= PLAIDHIP_LIMMA_MAX_SAMPLES, "%s: %d samples (at most %d)", what, n, PLAIDHIP_LIMMA_MAX_SAMPLES);
+  const int64_t W = (int64_t)nfit * lmfit_w_columns(p), C = 2 * (int64_t)nfit + 1, cols = rss ? nfit : std::max(W, C);
+  PH_REQUIRE(lmfit_tiles(W) <= 65535, "%s: %lld tiles of weight columns (at most 65535)", what, (long long)lmfit_tiles(W));
+  if (rows == 0 || nfit == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(out && (!rss || G) && (n == 0 || (A && Q && (rss || invn))), "%s: null argument", what);
+  const size_t part = ((size_t)row_design_ws_doubles(rows, n, cols) * 8 + 15) / 16 * 16;
+  const size_t mb = (size_t)lmfit_mask_bytes(n, W);
+  PH_TRY(ensure_workspace(ctx, part + mb + (size_t)lmfit_weight_bytes(n, W)));
+  double* ws = static_cast<double*>(ctx->ws);
+  void* masks = static_cast<char*>(ctx->ws) + part;
+  double* wt = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + part + mb);
+  PH_TRY(launch_lmfit_w_table(ctx, Q, use, invn, n, p, nfit, masks, wt));   // (the RSS pass reads the masks alone: invn may be null)
+  if (rss) {
+    PH_TRY(launch_row_design_w_rss(ctx, A, Wt, aw, ld, rows, n, Q, masks, p, nfit, G, ws));
+    return launch_reduce_blocks_flat(ctx, ws, (int64_t)nfit * rows, n, seed, out);
+  }
+  PH_TRY(launch_row_design_w_sums(ctx, A, Wt, aw, ld, rows, n, masks, wt, p, nfit, ws));
+  PH_TRY(launch_reduce_blocks_flat(ctx, ws, W * rows, n, seed, out));
+  if (cnt == nullptr) return PLAIDHIP_OK;
+  PH_TRY(launch_lmfit_w_counts(ctx, A, Wt, aw, ld, rows, n, use, nfit, ws));
+  return launch_reduce_blocks_flat(ctx, ws, C * rows, n, seed_cnt, cnt);
+}
+
+int plaidhip_dev_limma_w_sums(plaidhip_ctx* ctx, const double* A, const double* Wt, const double* aw, int64_t ld, int32_t rows,
+                              int32_t n, const double* Q, const int8_t* use, const double* invn, int32_t p, int32_t nfit,
+                              const double* seed, double* S, const double* seed_cnt, double* cnt) try {
+  return dev_limma_w_pass(ctx, "limma_w_sums", A, Wt, aw, ld, rows, n, Q, use, invn, p, nfit, nullptr, false, seed, S, seed_cnt,
+                          cnt);
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_limma_w_rss(plaidhip_ctx* ctx, const double* A, const double* Wt, const double* aw, int64_t ld, int32_t rows,
+                             int32_t n, const double* Q, const int8_t* use, int32_t p, int32_t nfit, const double* G,
+                             const double* seed, double* rss) try {
+  return dev_limma_w_pass(ctx, "limma_w_rss", A, Wt, aw, ld, rows, n, Q, use, nullptr, p, nfit, G, true, seed, rss, nullptr,
+                          nullptr);
+} catch (...) { return plaidhip::on_exception(); }
+
 int plaidhip_limma_tile(void) { return PLAIDHIP_LIMMA_TILE; }
 
 // plaid.camera: the one-device form of the sharded engine (shard_limma.cpp: limma_worker with kCamera, camera_tail)

@@ -12,7 +12,8 @@ namespace plaidhip {
 enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
-  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21, kFry = 22, kRoast = 23
+  kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21, kFry = 22, kRoast = 23,
+  kVoom = 24
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker's three
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -120,6 +121,23 @@ struct Call : Operands {
   int na_fit = 0;
   double max_na = 0.0;
   double* dfres = nullptr;
+  // plaid.limma with weights (plaidhip_limma_w): Wt rows x n observation weights and / or aw, n array weights (one of them
+  // may be null); max_na, dfres and hyper nfit x 5 as na = "fit"
+  int weighted = 0;
+  const double* Wt = nullptr;
+  const double* aw = nullptr;
+  // plaid.voom (kVoom): X is the counts (g rows x n samples), one design (n x ncoef), the library sizes (n, null: the column
+  // sums) and the span of the trend; E and W (g x n each), the library sizes used and the offsets (n each), the trend's
+  // knots (PLAIDHIP_VOOM_MAX_KNOTS each) and their number
+  const double* voom_lib = nullptr;
+  double voom_span = 0.5;
+  double* voom_E = nullptr;
+  double* voom_W = nullptr;
+  double* voom_lib_out = nullptr;
+  double* voom_off = nullptr;
+  double* voom_kx = nullptr;
+  double* voom_ky = nullptr;
+  int32_t* voom_nk = nullptr;
   // plaid.camera (kCamera): plaid.limma's operands (X genes x n, designs, use, K) and the sets; the fixed inter-gene
   // correlation (NaN: estimated from the residuals), allow.neg.cor; out m x 8 x q x nfit, hyper nfit x 6
   double inter_gene_cor = 0.0;
@@ -405,6 +423,37 @@ inline Call limma_na_call(const double* A, int32_t rows, int32_t n, const double
   k.na_fit = 1;
   k.max_na = max_na;
   k.dfres = dfres;
+  return k;
+}
+
+// plaid.limma with observation and / or array weights as pinned in include/plaidhip.h: plaidhip_limma_w
+inline Call limma_w_call(const double* A, const double* Wt, const double* aw, int32_t rows, int32_t n, const double* design,
+                         int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na, double* out,
+                         double* hyper, double* dfres) {
+  Call k = limma_call(A, rows, n, design, p, nfit, use, K, q, out, hyper);
+  k.weighted = 1;
+  k.Wt = Wt;
+  k.aw = aw;
+  k.max_na = max_na;
+  k.dfres = dfres;
+  return k;
+}
+
+// limma's voom (normalize.method = "none") as pinned in include/plaidhip.h: plaidhip_voom
+inline Call voom_call(const double* counts, int32_t rows, int32_t n, const double* design, int32_t p, const double* lib_size,
+                      double span, double* E, double* W, double* lib_out, double* offset, double* knots_x, double* knots_y,
+                      int32_t* nknots) {
+  Call k = limma_call(counts, rows, n, design, p, 1, nullptr, nullptr, p, nullptr, nullptr);
+  k.method = kVoom;
+  k.voom_lib = lib_size;
+  k.voom_span = span;
+  k.voom_E = E;
+  k.voom_W = W;
+  k.voom_lib_out = lib_out;
+  k.voom_off = offset;
+  k.voom_kx = knots_x;
+  k.voom_ky = knots_y;
+  k.voom_nk = nknots;
   return k;
 }
 

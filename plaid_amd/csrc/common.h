@@ -379,6 +379,33 @@ int launch_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, in
                               const double* d_wt, int32_t W, double* ws, bool na = false);
 int launch_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
                           const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws, bool na = false);
+// kernels_lmfit_w.hip (plaid.limma with weights, plaidhip_limma_w): fit f has lmfit_w_columns(p) = p (p + 1) / 2 + p + 1 weight
+// columns (the products q_ck q_cl, Q_f's columns, 1 / n_f); d_masks / d_wt: lmfit_mask_bytes / lmfit_weight_bytes of n and W =
+// nfit lmfit_w_columns(p), filled by launch_lmfit_w_table.  d_Wt: rows x n with A's leading dimension, or null; d_aw: n, or
+// null.  _w_sums: ws [nblk][W][rows]; _w_counts: ws [nblk][2 nfit + 1][rows] (live, the mean's select, then the row's NaN);
+// _w_solve: from the reduced sums d_S and counts d_cnt to d_G [nfit (p + 1)][rows], d_drow [nfit][rows], d_urow [nfit q][rows];
+// _w_rss: ws [nblk][nfit][rows] at d_G.  p <= PLAIDHIP_LIMMA_NA_MAX_COEF.
+int64_t lmfit_w_columns(int32_t p);
+int launch_lmfit_w_table(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_use, const double* d_invn, int32_t n, int32_t p,
+                         int32_t nfit, void* d_masks, double* d_wt);
+int launch_row_design_w_sums(plaidhip_ctx* ctx, const double* A, const double* d_Wt, const double* d_aw, int64_t ld, int32_t rows,
+                             int32_t n, const void* d_masks, const double* d_wt, int32_t p, int32_t nfit, double* ws);
+int launch_lmfit_w_counts(plaidhip_ctx* ctx, const double* A, const double* d_Wt, const double* d_aw, int64_t ld, int32_t rows,
+                          int32_t n, const int8_t* d_use, int32_t nfit, double* ws);
+int launch_lmfit_w_solve(plaidhip_ctx* ctx, const double* d_S, const double* d_cnt, const double* d_v, const double* d_nf,
+                         int32_t rows, int32_t n, int32_t p, int32_t nfit, int32_t q, double max_na, double* d_G, double* d_drow,
+                         double* d_urow);
+int launch_row_design_w_rss(plaidhip_ctx* ctx, const double* A, const double* d_Wt, const double* d_aw, int64_t ld, int32_t rows,
+                            int32_t n, const double* d_Q, const void* d_masks, int32_t p, int32_t nfit, const double* d_G,
+                            double* ws);
+// kernels_voom.hip (plaid.voom): the check with the column sums (d_bad: one zeroed word), the row sums' block partials [nblk][rows],
+// the log-CPM map, and the weights pass from the effects d_Eff [p + 1][rows], Q (n x p), the offsets (n) and nk knots
+int launch_voom_check(plaidhip_ctx* ctx, const double* X, int64_t ld, int32_t rows, int32_t n, double* d_colsum, uint32_t* d_bad);
+int launch_voom_rowsum(plaidhip_ctx* ctx, const double* X, int64_t ld, int32_t rows, int32_t n, double* part);
+int launch_voom_logcpm(plaidhip_ctx* ctx, const double* X, int64_t ld, int32_t rows, int32_t n, const double* d_lib, double* E,
+                       int64_t lde);
+int launch_voom_weights(plaidhip_ctx* ctx, const double* d_Q, const double* d_off, int32_t n, int32_t p, const double* d_Eff,
+                        int32_t rows, const double* d_kx, const double* d_ky, int32_t nk, double* W, int64_t ldw);
 // na = "fit" (plaidhip_limma_na): `na` above extends the select by x == x.  The count pass: cnt[b][r] = the NaN of row r in
 // column block b of 128 (d_off null; nblk x rows), then d_list[d_off[b][r] ..] = their columns (d_off: the exclusive prefix
 // sums of cnt, row by row and block by block within a row, so a row's columns lie together and ascend).

@@ -274,7 +274,7 @@ lmfit_na_solve_kernel(const int32_t* __restrict__ pairs, const int64_t* __restri
   if (lane == 0) {
     double ep[kNaP];
     for (int t = 0; t < p; ++t) ep[t] = e[(int64_t)t * rows];
-    ok = lmfit_na_factor_solve(p, H, kNaP, ep, gam) ? 1 : 0;
+    ok = lmfit_na_factor_solve(p, H, kNaP, ep, gam, nullptr, PLAIDHIP_LMNA_PIVOT_MIN, false) ? 1 : 0;
     const double nan = __builtin_nan("");
     for (int t = 0; t < p; ++t) e[(int64_t)t * rows] = ok ? gam[t] : nan;
     e[(int64_t)p * rows] = ok ? lmfit_na_mean(e[(int64_t)p * rows], nf[f], (double)nobs[blockIdx.x]) : nan;

@@ -15,6 +15,7 @@
 #endif
 
 #define PLAIDHIP_LMNA_PIVOT_MIN 1e-10   // a Cholesky pivot at or below it: the row is not estimable in the fit
+#define PLAIDHIP_LMW_PIVOT_REL 1e-10    // the weighted fit (plaidhip_limma_w): at or below it times H_kk, the diagonal before elimination
 
 namespace plaidhip {
 
@@ -35,9 +36,12 @@ PH_LMNA_HD inline double lmfit_na_gram_chain(const double* qk, const double* ql,
 
 // H (p x p, row-major with leading dimension ld; the lower triangle is read) -> L in its place, H = L L', Cholesky without
 // pivoting, row by row, every inner sum in ascending order; then L y = e and L' gamma = y.  e: p values; gamma: p values
-// (may be e).  Returns false -- and leaves gamma unwritten -- when a pivot is <= PLAIDHIP_LMNA_PIVOT_MIN or NaN.  piv (may be
+// (may be e).  Returns false -- and leaves gamma unwritten -- when a pivot d_k is <= the threshold or NaN.  The threshold is
+// `tol` itself (relative == false: na = "fit", whose H is I minus a downdate) or tol * H_kk, one rounded product with the
+// diagonal entry before elimination (relative == true: the weighted fit, whose H scales with the weights).  piv (may be
 // null): the pivots d_k as far as the factorisation went.
-PH_LMNA_HD inline bool lmfit_na_factor_solve(int p, double* H, int ld, const double* e, double* gamma, double* piv = nullptr) {
+PH_LMNA_HD inline bool lmfit_na_factor_solve(int p, double* H, int ld, const double* e, double* gamma, double* piv, double tol,
+                                             bool relative) {
 #pragma clang fp contract(off)
   for (int k = 0; k < p; ++k) {
     for (int l = 0; l < k; ++l) {
@@ -45,10 +49,12 @@ PH_LMNA_HD inline bool lmfit_na_factor_solve(int p, double* H, int ld, const dou
       for (int m = 0; m < l; ++m) s = fma(-H[k * ld + m], H[l * ld + m], s);
       H[k * ld + l] = s / H[l * ld + l];
     }
-    double d = H[k * ld + k];
+    const double hkk = H[k * ld + k];
+    double d = hkk;
     for (int m = 0; m < k; ++m) d = fma(-H[k * ld + m], H[k * ld + m], d);
     if (piv != nullptr) piv[k] = d;
-    if (!(d > PLAIDHIP_LMNA_PIVOT_MIN)) return false;
+    const double least = relative ? tol * hkk : tol;
+    if (!(d > least)) return false;
     H[k * ld + k] = sqrt(d);
   }
   for (int k = 0; k < p; ++k) {   // forward: y in gamma
@@ -82,6 +88,20 @@ PH_LMNA_HD inline double lmfit_na_unscaled(int p, const double* L, int ld, const
 PH_LMNA_HD inline double lmfit_na_mean(double Mp, double nf, double nobs) {
 #pragma clang fp contract(off)
   return (Mp * nf) / nobs;
+}
+
+// The weighted fit of one (row, fit) pair (include/plaidhip.h: plaidhip_limma_w), once for the device (kernels_lmfit_w.hip:
+// lmfit_w_solve_kernel) and the host (plaidhip_limma_w_solve).  H: p x p with leading dimension ld, its lower triangle holds
+// the weighted Gram sums on entry and L on return; g: b on entry, gamma on return; nlive: the live observations.  u[j *
+// ustride] takes stdev.unscaled of contrast j (v: p x q); w: p doubles of scratch.  Not estimable (a pivot at or below
+// PLAIDHIP_LMW_PIVOT_REL H_kk or NaN, or nlive - p < 1): false; u is not written, and g holds nothing to be used (gamma where only the
+// degrees of freedom were missing, b otherwise): the callers write NaN.
+PH_LMNA_HD inline bool lmfit_w_row_solve(int p, double* H, int ld, double* g, double nlive, const double* v, int q, double* u,
+                                         int64_t ustride, double* w, double* piv) {
+  const bool ok = lmfit_na_factor_solve(p, H, ld, g, g, piv, PLAIDHIP_LMW_PIVOT_REL, true) && nlive - (double)p >= 1.0;
+  if (!ok) return false;
+  for (int j = 0; j < q; ++j) u[j * ustride] = lmfit_na_unscaled(p, H, ld, v + (int64_t)j * p, w);
+  return true;
 }
 
 }  // namespace plaidhip

@@ -383,11 +383,20 @@ int check_limma_call(Call& c) {
                PLAIDHIP_LIMMA_NA_MAX_COEF);
     PH_REQUIRE(c.max_na >= 0.0 && c.max_na <= 1.0, "%s: max_na = %g (a share, 0 <= max_na <= 1)", who, c.max_na);
   }
+  if (c.weighted) {
+    PH_REQUIRE(p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "%s: p = %d coefficients with weights (p <= %d)", who, p,
+               PLAIDHIP_LIMMA_NA_MAX_COEF);
+    PH_REQUIRE(c.max_na >= 0.0 && c.max_na <= 1.0, "%s: max_na = %g (a share, 0 <= max_na <= 1)", who, c.max_na);
+    PH_REQUIRE(c.Wt != nullptr || c.aw != nullptr, "%s: weights: Wt and aw are both null (plaidhip_limma takes no weights)", who);
+    PH_REQUIRE(lmfit_tiles((int64_t)nfit * lmfit_w_columns(p)) <= 65535,
+               "%s: nfit = %d fits of p = %d coefficients with weights: %lld tiles of weight columns (at most 65535)", who, nfit,
+               p, (long long)lmfit_tiles((int64_t)nfit * lmfit_w_columns(p)));
+  }
   PH_REQUIRE(c.K != nullptr || q == p, "%s: q = %d without K (the p = %d unit vectors)", who, q, p);
   PH_REQUIRE(c.design != nullptr || nfit == 0, "%s: null design", who);
   PH_REQUIRE(rows == 0 || nfit == 0 || q == 0 || !sets || (c.X != nullptr && c.out != nullptr && c.hyper != nullptr),
              "%s: null A / out / hyper", who);
-  PH_REQUIRE(!c.na_fit || rows == 0 || nfit == 0 || q == 0 || c.dfres != nullptr, "%s: null dfres", who);
+  PH_REQUIRE((!c.na_fit && !c.weighted) || rows == 0 || nfit == 0 || q == 0 || c.dfres != nullptr, "%s: null dfres", who);
   if (c.K != nullptr)
     for (int64_t e = 0; e < (int64_t)p * q; ++e)
       PH_REQUIRE(std::isfinite(c.K[e]), "%s: K[%lld] = %g (the contrasts are finite)", who, (long long)e, c.K[e]);
@@ -418,6 +427,31 @@ int check_limma_call(Call& c) {
                         c.lm_Q2_off[(size_t)f] >= 0 ? c.lm_Q2.data() + c.lm_Q2_off[(size_t)f] : nullptr));
     c.lm_invn[(size_t)f] = 1.0 / (double)c.lm_nf[(size_t)f];
   }
+  return PLAIDHIP_OK;
+}
+
+// plaid.voom; the order is part of the contract (include/plaidhip.h).  The design is decomposed here, as plaid.limma's
+int check_voom_call(Call& c) {
+  const int32_t rows = c.g, n = c.n, p = c.ncoef;
+  PH_REQUIRE(rows >= 0 && n >= 0 && n <= PLAIDHIP_LIMMA_MAX_SAMPLES, "voom: bad dims rows=%d n=%d (n <= %d)", rows, n,
+             PLAIDHIP_LIMMA_MAX_SAMPLES);
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "voom: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
+  PH_REQUIRE(c.voom_span > 0.0 && c.voom_span <= 1.0, "voom: span = %g (0 < span <= 1)", c.voom_span);
+  PH_REQUIRE(c.design != nullptr, "voom: null design");
+  if (rows == 0 || n == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(c.X && c.voom_E && c.voom_W && c.voom_lib_out && c.voom_off && c.voom_kx && c.voom_ky && c.voom_nk,
+             "voom: null counts / E / weights / lib.size / offset / knots");
+  if (c.voom_lib != nullptr)
+    for (int32_t s = 0; s < n; ++s)
+      PH_REQUIRE(std::isfinite(c.voom_lib[s]) && c.voom_lib[s] >= 0.0, "voom: lib.size[%d] = %g (finite and >= 0)", s + 1,
+                 c.voom_lib[s]);
+  c.lm_Q.assign((size_t)n * p, 0.0);
+  c.lm_v.assign((size_t)p * p, 0.0);
+  c.lm_u.assign((size_t)p, 0.0);
+  c.lm_nf.assign(1, 0);
+  PH_TRY(limma_design("voom", c.design, n, p, nullptr, nullptr, p, 1, c.lm_Q.data(), nullptr, c.lm_v.data(), c.lm_u.data(),
+                      &c.lm_nf[0], nullptr));
+  c.lm_invn.assign(1, 1.0 / (double)c.lm_nf[0]);
   return PLAIDHIP_OK;
 }
 
@@ -534,6 +568,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kCamera: return check_camera_call(c);
     case kFry: return check_fry_call(c);
     case kRoast: return check_roast_call(c);
+    case kVoom: return check_voom_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
       return c.single ? PLAIDHIP_OK : check_gsea_ks_genes(c.g);
@@ -839,6 +874,35 @@ int plaidhip_limma_na_multi(const int* devices, int ndev, const double* A, int32
                             int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na, double* out,
                             double* hyper, double* dfres) try {
   return dispatch(on_devices(devices, ndev), limma_na_call(A, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_voom_multi(const int* devices, int ndev, const double* counts, int32_t rows, int32_t n, const double* design,
+                        int32_t p, const double* lib_size, double span, double* E, double* W, double* lib_out, double* offset,
+                        double* knots_x, double* knots_y, int32_t* nknots) try {
+  return dispatch(on_devices(devices, ndev),
+                  voom_call(counts, rows, n, design, p, lib_size, span, E, W, lib_out, offset, knots_x, knots_y, nknots));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_voom_sharded_on_one_device(int device, int nshards, int fail_shard, const double* counts, int32_t rows,
+                                              int32_t n, const double* design, int32_t p, const double* lib_size, double span,
+                                              double* E, double* W, double* lib_out, double* offset, double* knots_x,
+                                              double* knots_y, int32_t* nknots) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  voom_call(counts, rows, n, design, p, lib_size, span, E, W, lib_out, offset, knots_x, knots_y, nknots));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_w_multi(const int* devices, int ndev, const double* A, const double* Wt, const double* aw, int32_t rows,
+                           int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use, const double* K, int32_t q,
+                           double max_na, double* out, double* hyper, double* dfres) try {
+  return dispatch(on_devices(devices, ndev), limma_w_call(A, Wt, aw, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_limma_w_sharded_on_one_device(int device, int nshards, int fail_shard, const double* A, const double* Wt,
+                                                 const double* aw, int32_t rows, int32_t n, const double* design, int32_t p,
+                                                 int32_t nfit, const int8_t* use, const double* K, int32_t q, double max_na,
+                                                 double* out, double* hyper, double* dfres) try {
+  return dispatch(on_hook(device, nshards, fail_shard),
+                  limma_w_call(A, Wt, aw, rows, n, design, p, nfit, use, K, q, max_na, out, hyper, dfres));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_limma_na_sharded_on_one_device(int device, int nshards, int fail_shard, const double* A, int32_t rows,

@@ -388,10 +388,11 @@ Route route(const Call& c) {
     case kFisher: return {false, no_scores, nullptr, fisher_worker, nullptr};
     case kRankcor: return {false, no_scores, nullptr, rankcor_worker, nullptr};
     case kPlage: case kZscore: return {false, no_scores, nullptr, plage_worker, nullptr};
-    case kLimma: return {true, limma_empty, limma_prepare, limma_worker, limma_tail};
+    case kLimma: return {true, limma_empty, limma_prepare, c.weighted ? limma_w_worker : limma_worker, limma_tail};
     case kCamera: return {true, limma_empty, limma_prepare, limma_worker, camera_tail};
     case kFry: return {true, limma_empty, limma_prepare, limma_worker, fry_tail};
     case kRoast: return {false, limma_empty, roast_prepare, roast_worker, roast_tail};
+    case kVoom: return {true, voom_empty, voom_prepare, voom_worker, nullptr};
   }
   return {false, no_scores, nullptr, nullptr, nullptr};   // (no method at all: check_call has refused it)
 }

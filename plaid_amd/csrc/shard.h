@@ -98,7 +98,16 @@ struct Shared {
     std::vector<std::vector<int32_t>> na_cnt, na_list;
     std::vector<int32_t> na_pair;
     std::vector<double> na_d, na_u;
+    // with weights: the chained weighted sums [nfit Wc][rows] and counts [2 nfit + 1][rows]; shard 0's solve then fills
+    // effects (gamma and AveExpr), na_d and na_u
+    std::vector<double> wsum, wcnt;
   } limma;
+  // plaid.voom: a count that is not finite and >= 0 on any shard; every column's sum (each shard writes its block); the chained
+  // row sums [rows]; the library sizes used and the offsets; shard 0's knots (limma.effects / limma.rss take the unweighted fit)
+  struct Voom {
+    uint32_t bad = 0;
+    std::vector<double> colsum, rowsum, lib, off, kx, ky;
+  } voom;
   // plaid.camera: the chained sums over the samples of T^2, [nfit][m] (T = G'Z of every fit)
   struct Camera { std::vector<double> ss; } camera;
   // plaid.fry: the divisors [nfit][rows] (shard 0 makes them after the RSS chain); the chained residual effects of every
@@ -234,6 +243,14 @@ int fisher_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh)
 int rankcor_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);
 int plage_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);
 int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);              // shard_limma.cpp
+int limma_w_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);            // shard_limma_w.cpp
+int voom_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);               // shard_voom.cpp
+bool voom_empty(const Call& c);
+void voom_prepare(Shared& sh, const Call& c, int ndev);
+// the trend of plaid.voom on the host (include/plaidhip.h, steps 4 - 6): the knots from M, s2 and the row sums; EINVAL
+// without a row to fit it on
+int voom_trend_knots(int32_t rows, const double* M, const double* s2, const double* rowsum, const double* lib, int32_t n,
+                     double span, std::vector<double>& kx, std::vector<double>& ky);
 bool limma_empty(const Call& c);
 void limma_prepare(Shared& sh, const Call& c, int ndev);
 int limma_tail(plaidhip_ctx* first, const Call& c, Shared& sh);

@@ -323,6 +323,10 @@ void limma_prepare(Shared& sh, const Call& c, int ndev) {
   }
   sh.limma.effects.assign((size_t)c.nfit * (c.ncoef + 1) * c.g, 0.0);
   sh.limma.rss.assign((size_t)c.nfit * c.g, 0.0);
+  if (c.weighted) {
+    sh.limma.wsum.assign((size_t)c.nfit * (size_t)lmfit_w_columns(c.ncoef) * c.g, 0.0);
+    sh.limma.wcnt.assign((2 * (size_t)c.nfit + 1) * c.g, 0.0);
+  }
   if (c.na_fit) {
     sh.limma.na_cnt.resize((size_t)ndev);
     sh.limma.na_list.resize((size_t)ndev);
@@ -332,7 +336,7 @@ void limma_prepare(Shared& sh, const Call& c, int ndev) {
 
 // plaid.limma after the workers: eBayes and the tables, on the host from the chained sums
 int limma_tail(plaidhip_ctx*, const Call& c, Shared& sh) {
-  if (!c.na_fit)
+  if (!c.na_fit && !c.weighted)
     return plaidhip_limma_finish(c.g, c.ncoef, c.nfit, c.nq, sh.limma.effects.data(), sh.limma.rss.data(), c.lm_nf.data(),
                                  c.lm_v.data(), c.lm_u.data(), c.out, c.hyper);
   PH_TRY(plaidhip_limma_finish_na(c.g, c.ncoef, c.nfit, c.nq, sh.limma.effects.data(), sh.limma.rss.data(), c.lm_nf.data(),

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "fry.h"
 #include "lmfit_na.h"
+#include "lowess.h"
 #include "roast.h"
 
 namespace plaidhip {
@@ -798,11 +799,48 @@ int plaidhip_limma_na_solve(int32_t p, int32_t nmis, const double* qmis, const d
     for (int l = 0; l <= k; ++l) H[k * P + l] = (k == l ? 1.0 : 0.0) - lmfit_na_gram_chain(qmis + k, qmis + l, p, nmis);
   double piv[P];
   for (int k = 0; k < p; ++k) piv[k] = nan;
-  *ok = lmfit_na_factor_solve(p, H, P, Ep, gamma, piv) && nobs - p >= 1 ? 1 : 0;
+  *ok = lmfit_na_factor_solve(p, H, P, Ep, gamma, piv, PLAIDHIP_LMNA_PIVOT_MIN, false) && nobs - p >= 1 ? 1 : 0;
   if (!*ok)
     for (int k = 0; k < p; ++k) gamma[k] = nan;
   if (pivots != nullptr) std::copy(piv, piv + p, pivots);
   for (int32_t j = 0; j < q; ++j) u[j] = *ok ? lmfit_na_unscaled(p, H, P, v + (size_t)j * p, w) : nan;
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_lowess(const double* x, const double* y, int64_t n, double f, int32_t iter, double delta, double* ys,
+                    int8_t* anchor) try {
+  using namespace plaidhip;
+  PH_REQUIRE(n >= 1 && iter >= 0, "lowess: bad dims n=%lld iter=%d", (long long)n, iter);
+  PH_REQUIRE(x && y && ys, "lowess: null argument");
+  PH_REQUIRE(f > 0.0 && std::isfinite(f) && delta >= 0.0, "lowess: f = %g, delta = %g (f > 0, delta >= 0)", f, delta);
+  for (int64_t i = 0; i < n; ++i) {
+    PH_REQUIRE(std::isfinite(x[i]) && std::isfinite(y[i]), "lowess: point %lld is not finite", (long long)i + 1);
+    PH_REQUIRE(i == 0 || x[i] >= x[i - 1], "lowess: x is not ascending at point %lld", (long long)i + 1);
+  }
+  lowess_run(x, y, n, f, iter, delta, ys, anchor);
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_limma_w_solve(int32_t p, const double* Htri, const double* b, int64_t nlive, const double* v, int32_t q,
+                           double* gamma, double* u, double* pivots, int32_t* ok) try {
+  using namespace plaidhip;
+  PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_NA_MAX_COEF, "limma_w_solve: p = %d coefficients (1 <= p <= %d)", p,
+             PLAIDHIP_LIMMA_NA_MAX_COEF);
+  PH_REQUIRE(q >= 0 && nlive >= 0, "limma_w_solve: bad dims q=%d nlive=%lld", q, (long long)nlive);
+  PH_REQUIRE(Htri && b && (v || q == 0) && gamma && (u || q == 0) && ok, "limma_w_solve: null argument");
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  constexpr int P = PLAIDHIP_LIMMA_NA_MAX_COEF;
+  double H[P * P], g[P], w[P], piv[P];
+  for (int k = 0, j = 0; k < p; ++k) {
+    for (int l = 0; l <= k; ++l, ++j) H[k * P + l] = Htri[j];
+    g[k] = b[k];
+    piv[k] = nan;
+  }
+  *ok = lmfit_w_row_solve(p, H, P, g, (double)nlive, v, q, u, 1, w, piv) ? 1 : 0;
+  for (int k = 0; k < p; ++k) gamma[k] = *ok ? g[k] : nan;
+  if (!*ok)
+    for (int32_t j = 0; j < q; ++j) u[j] = nan;
+  if (pivots != nullptr) std::copy(piv, piv + p, pivots);
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }
 

@@ -606,9 +606,48 @@ def _limma_na(fn, head, A, design, use=None, contrasts=None, max_na=0.2, out=Non
     return out, hyper, dfres
 
 
-def _limma_any(fn, fn_na, head, A, design, use, contrasts, na, max_na):
+def limma_weights(rows, n, weights):
+    """weights as the C ABI takes them: (Wt rows x n float64 Fortran-ordered or None, aw n float64 or None).  weights: a rows x
+    n matrix (observation weights), a vector of n (array weights), or a pair (matrix, vector)"""
+    if isinstance(weights, tuple):
+        Wt, aw = weights
+    else:
+        w = np.asarray(weights, dtype=np.float64)
+        Wt, aw = (None, w) if w.ndim == 1 else (w, None)
+    if Wt is not None:
+        Wt = _as_f64_fortran(np.asarray(Wt, dtype=np.float64))
+        if Wt.shape != (rows, n):
+            raise ValueError("limma: observation weights must have the shape of the matrix, rows x samples")
+    if aw is not None:
+        aw = np.ascontiguousarray(np.asarray(aw, dtype=np.float64))
+        if aw.shape != (n,):
+            raise ValueError("limma: array weights must have one entry per sample")
+    return Wt, aw
+
+
+def _limma_w(fn, head, A, weights, design, use=None, contrasts=None, max_na=0.2, out=None, hyper=None, dfres=None):
+    """plaidhip_limma_w / _multi / the hook (weights): (out, hyper, dfres) as _limma_na returns them"""
+    A = _as_f64_fortran(A)
+    if A.ndim != 2:
+        raise ValueError("limma: the matrix must be rows x samples")
+    rows, n = A.shape
+    Wt, aw = limma_weights(rows, n, weights)
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    out = np.full((rows, 6, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 5), np.nan, dtype=np.float64) if hyper is None else hyper
+    dfres = np.full((rows, nfit), np.nan, dtype=np.float64, order="F") if dfres is None else dfres
+    check(fn(*head, _np_ptr(A), None if Wt is None else _np_ptr(Wt), None if aw is None else _np_ptr(aw), rows, n, _np_ptr(D), p,
+             nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K), q, float(max_na), _np_ptr(out),
+             _np_ptr(hyper), _np_ptr(dfres)))
+    return out, hyper, dfres
+
+
+def _limma_any(fn, fn_na, head, A, design, use, contrasts, na, max_na, weights=None, fn_w=None):
     if na not in LIMMA_NA:
         raise ValueError(f"limma: na must be one of {LIMMA_NA}")
+    if weights is not None:   # (limma's rule: a NaN or a weight that is not positive and finite is a missing observation)
+        return _limma_w(fn_w, head, A, weights, design, use, contrasts, max_na if na == "fit" else 0.0)
     if na == "fit":
         return _limma_na(fn_na, head, A, design, use, contrasts, max_na)
     return _limma(fn, head, A, design, use, contrasts)
@@ -628,6 +667,68 @@ def limma_na_solve(qmis, Ep, nobs, v) -> dict:
     ok = C.c_int32(-7)
     check(_lib.load().plaidhip_limma_na_solve(p, qmis.shape[0], _np_ptr(qmis), _np_ptr(Ep), int(nobs), _np_ptr(v), q,
                                               _np_ptr(gamma), _np_ptr(u), _np_ptr(piv), C.cast(C.byref(ok), C.c_void_p)))
+    return {"gamma": gamma, "u": u, "pivots": piv, "ok": bool(ok.value)}
+
+
+VOOM_MAX_KNOTS = 256
+
+
+def _voom(fn, head, counts, design, lib_size=None, span=0.5, out=None):
+    """plaidhip_voom / _multi / the hook: dict of E and weights (rows x samples), lib_size and offset (samples), knots_x and
+    knots_y (the trend's knots).  out: a dict of caller's buffers E, W, lib, off, kx, ky (the tests' sentinels)"""
+    A = _as_f64_fortran(counts)
+    if A.ndim != 2:
+        raise ValueError("voom: counts must be rows x samples")
+    rows, n = A.shape
+    D = np.asfortranarray(np.asarray(design, dtype=np.float64))
+    if D.ndim != 2 or D.shape[0] != n:
+        raise ValueError("voom: design must be samples x coefficients, one row per column of counts")
+    L = None
+    if lib_size is not None:
+        L = np.ascontiguousarray(np.asarray(lib_size, dtype=np.float64))
+        if L.shape != (n,):
+            raise ValueError("voom: lib_size must have one entry per sample")
+    o = out if out is not None else {}
+    E = o.get("E", np.full((rows, n), np.nan, order="F"))
+    W = o.get("W", np.full((rows, n), np.nan, order="F"))
+    lib, off = o.get("lib", np.full(n, np.nan)), o.get("off", np.full(n, np.nan))
+    kx, ky = o.get("kx", np.full(VOOM_MAX_KNOTS, np.nan)), o.get("ky", np.full(VOOM_MAX_KNOTS, np.nan))
+    nk = C.c_int32(0)
+    check(fn(*head, _np_ptr(A), rows, n, _np_ptr(D), D.shape[1], None if L is None else _np_ptr(L), float(span), _np_ptr(E),
+             _np_ptr(W), _np_ptr(lib), _np_ptr(off), _np_ptr(kx), _np_ptr(ky), C.cast(C.byref(nk), C.c_void_p)))
+    return {"E": E, "weights": W, "lib_size": lib, "offset": off, "knots_x": kx[:nk.value].copy(), "knots_y": ky[:nk.value].copy()}
+
+
+def lowess(x, y, f=2.0 / 3.0, iter=3, delta=None) -> dict:
+    """plaidhip_lowess on the host (no device is touched): R's lowess as pinned in include/plaidhip.h.  x ascending.  Returns
+    ys (the fitted values) and anchor (bool: where the last pass made a local fit or a tie copy)"""
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    if x.ndim != 1 or x.shape != y.shape:
+        raise ValueError("lowess: x and y are vectors of one length")
+    if delta is None:
+        delta = 0.01 * (x[-1] - x[0]) if len(x) else 0.0
+    ys, anchor = np.full(len(x), np.nan), np.zeros(len(x), dtype=np.int8)
+    check(_lib.load().plaidhip_lowess(_np_ptr(x), _np_ptr(y), len(x), float(f), int(iter), float(delta), _np_ptr(ys),
+                                      _np_ptr(anchor)))
+    return {"ys": ys, "anchor": anchor != 0}
+
+
+def limma_w_solve(Htri, b, nlive, v) -> dict:
+    """plaidhip_limma_w_solve on the host (no device is touched): the weighted fit of one row from its sums.  Htri: the lower
+    triangle of H row by row (p (p + 1) / 2); b (p); nlive: its live observations; v: p x q -> gamma (p), u (q), the Cholesky
+    pivots (p) and ok"""
+    b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
+    p = b.shape[0]
+    Htri = np.ascontiguousarray(np.asarray(Htri, dtype=np.float64))
+    if Htri.shape != (p * (p + 1) // 2,):
+        raise ValueError("limma_w_solve: Htri holds the p (p + 1) / 2 entries of the lower triangle")
+    v = np.asfortranarray(np.asarray(v, dtype=np.float64).reshape(p, -1))
+    q = v.shape[1]
+    gamma, u, piv = np.full(p, -7.0), np.full(q, -7.0), np.full(p, -7.0)
+    ok = C.c_int32(-7)
+    check(_lib.load().plaidhip_limma_w_solve(p, _np_ptr(Htri), _np_ptr(b), int(nlive), _np_ptr(v), q, _np_ptr(gamma), _np_ptr(u),
+                                             _np_ptr(piv), C.cast(C.byref(ok), C.c_void_p)))
     return {"gamma": gamma, "u": u, "pivots": piv, "ok": bool(ok.value)}
 
 
@@ -1361,15 +1462,36 @@ class Context:
         ns = nst.value
         return {"stages": ns, "status": end.value, "m": m_out[:ns].copy(), "s": s_out[:ns].copy(), "h": h_out[:ns].copy()}
 
-    def limma(self, A, design, use=None, contrasts=None, na="propagate", max_na=0.2):
+    def limma(self, A, design, use=None, contrasts=None, na="propagate", max_na=0.2, weights=None):
         """plaidhip_limma: moderated t-tests of the rows of A (rows x samples) for the designs (samples x p, or x p x nfit),
         the samples `use` leaves out (samples x nfit, None: none) and the contrasts (p x q, None: every coefficient):
         (out rows x 6 x q x nfit in LIMMA_COLUMNS, hyper nfit x 4 in LIMMA_HYPER).  na = "fit" (plaidhip_limma_na): rows with at
         most the share max_na of NaN are refitted on the samples they have, and the result is (out, hyper nfit x 5 in
         LIMMA_HYPER_NA, dfres rows x nfit: the df.residual of every fitted row, NaN for the others); at most
-        LIMMA_NA_MAX_COEF coefficients"""
+        LIMMA_NA_MAX_COEF coefficients.  weights (plaidhip_limma_w): a rows x samples matrix of observation weights, a vector
+        of array weights, or a pair of both; an observation with a NaN value or a weight that is not positive and finite is
+        missing, the result is that of na = "fit", and na = "propagate" stands for max_na = 0 (no row with a NaN is fitted)"""
         return _limma_any(self.lib.plaidhip_limma, self.lib.plaidhip_limma_na, (self.handle,), A, design, use, contrasts, na,
-                          max_na)
+                          max_na, weights, self.lib.plaidhip_limma_w)
+
+    def voom(self, counts, design, lib_size=None, span=0.5):
+        """plaidhip_voom: limma's voom (normalize.method = "none") of a counts matrix (rows x samples) for one design: dict of E
+        (log2-CPM), weights, lib_size, offset, knots_x, knots_y.  Context.limma(E, design, weights=weights) is the fit"""
+        return _voom(self.lib.plaidhip_voom, (self.handle,), counts, design, lib_size, span)
+
+    def dev_voom_weights(self, Q: int, offset: int, n: int, p: int, Eff: int, rows: int, kx: int, ky: int, nk: int, W: int, ldw: int):
+        """plaidhip_dev_voom_weights on device pointers: W rows x n (leading dimension ldw) from the effects Eff [p + 1][rows]"""
+        check(self.lib.plaidhip_dev_voom_weights(self.handle, Q, offset, n, p, Eff, rows, kx, ky, nk, W, ldw))
+
+    def dev_limma_w_sums(self, A: int, Wt, aw, ld: int, rows: int, n: int, Q: int, use, invn: int, p: int, nfit: int, seed, S: int,
+                         seed_cnt=None, cnt=None):
+        """plaidhip_dev_limma_w_sums on device pointers: S [nfit (p (p + 1) / 2 + p + 1)][rows], cnt [2 nfit + 1][rows] or None;
+        Wt, aw, use and the seeds may be None"""
+        check(self.lib.plaidhip_dev_limma_w_sums(self.handle, A, Wt, aw, ld, rows, n, Q, use, invn, p, nfit, seed, S, seed_cnt, cnt))
+
+    def dev_limma_w_rss(self, A: int, Wt, aw, ld: int, rows: int, n: int, Q: int, use, p: int, nfit: int, G: int, seed, rss: int):
+        """plaidhip_dev_limma_w_rss on device pointers: the weighted rss [nfit][rows] at G [nfit (p + 1)][rows]"""
+        check(self.lib.plaidhip_dev_limma_w_rss(self.handle, A, Wt, aw, ld, rows, n, Q, use, p, nfit, G, seed, rss))
 
     def dev_row_design_effects(self, A: int, ld: int, rows: int, n: int, Q: int, use, invn: int, p: int, nfit: int, seed, E: int):
         """plaidhip_dev_row_design_effects on device pointers: E [nfit (p + 1)][rows]; use and seed may be None"""
@@ -1693,11 +1815,17 @@ def camera_multi(X, design, Gp, Gi, use=None, contrasts=None, inter_gene_cor=0.0
     return _camera(*_multi("camera", devices), X, design, Gp, Gi, use, contrasts, inter_gene_cor, allow_neg_cor)
 
 
-def limma_multi(A, design, use=None, contrasts=None, devices=1, na="propagate", max_na=0.2):
+def limma_multi(A, design, use=None, contrasts=None, devices=1, na="propagate", max_na=0.2, weights=None):
     """plaid.limma (Context.limma) with the sample columns sharded over `devices`: the one-device bits.  Returns (out, hyper),
-    or with na = "fit" (out, hyper nfit x 5, dfres rows x nfit) as Context.limma does"""
+    or with na = "fit" or weights (out, hyper nfit x 5, dfres rows x nfit) as Context.limma does"""
     fn, head = _multi("limma", devices)
-    return _limma_any(fn, _multi("limma_na", devices)[0], head, A, design, use, contrasts, na, max_na)
+    return _limma_any(fn, _multi("limma_na", devices)[0], head, A, design, use, contrasts, na, max_na, weights,
+                      _multi("limma_w", devices)[0] if weights is not None else None)
+
+
+def voom_multi(counts, design, lib_size=None, span=0.5, devices=1):
+    """plaid.voom (Context.voom) with the sample columns sharded over `devices`: the one-device bits"""
+    return _voom(*_multi("voom", devices), counts, design, lib_size, span)
 
 
 def multi_finalize():

@@ -683,10 +683,30 @@ plaid.rankcor <- function(stat, G, use.rank = TRUE, compute.p = TRUE, ties = c("
 
 .limma_hyper <- function(h) stats::setNames(as.list(h), c("df.residual", "df.prior", "s2.prior", "n.ok", "df.pooled")[seq_along(h)])
 
+## weights of plaid.limma() as the shim takes them: list(Wt, aw), a double matrix in S's shape or NULL and a double vector
+## over the samples or NULL
+.limma_weights <- function(S, weights) {
+  if (is.null(weights)) return(NULL)
+  if (is.matrix(weights) || is.data.frame(weights)) {
+    weights <- as.matrix(weights); storage.mode(weights) <- "double"
+    if (!identical(dim(weights), dim(S))) stop("plaid.limma: a matrix of weights has the shape of S")
+    return(list(weights, NULL))
+  }
+  if (length(weights) != ncol(S)) stop("plaid.limma: a vector of weights has one entry per sample")
+  list(NULL, as.double(weights))
+}
+
 ## the library call behind both: na = "propagate" is plaidhip_limma; na = "fit" is plaidhip_limma_na, whose tables get the
-## rows' own df.residual as a seventh column (NA where the row is NA)
-.limma_call <- function(S, D, nfit, use, K, na, max.na, ncon, rn, sort.by) {
-  if (na == "propagate") {
+## rows' own df.residual as a seventh column (NA where the row is NA); with weights plaidhip_limma_w, whose result is that of
+## na = "fit" (na = "propagate" then stands for max.na = 0: no row with an NA is fitted)
+.limma_call <- function(S, D, nfit, use, K, na, max.na, ncon, rn, sort.by, weights = NULL) {
+  if (!is.null(weights)) {
+    if (na == "propagate") max.na <- 0
+    if (length(max.na) != 1L || is.na(max.na) || max.na < 0 || max.na > 1) stop("plaid.limma: max.na must be a share in [0, 1]")
+    r <- .Call("R_plaidhip_limma_w", .devices(), S, weights[[1]], weights[[2]], D, nfit, use, K, as.double(max.na),
+               PACKAGE = "plaidhip")
+    na <- "fit"
+  } else if (na == "propagate") {
     r <- .Call("R_plaidhip_limma", .devices(), S, D, nfit, use, K, PACKAGE = "plaidhip")
   } else {
     if (length(max.na) != 1L || is.na(max.na) || max.na < 0 || max.na > 1) stop("plaid.limma: max.na must be a share in [0, 1]")
@@ -709,8 +729,13 @@ plaid.rankcor <- function(stat, G, use.rank = TRUE, compute.p = TRUE, ties = c("
 ## handling -- a row with at most the share max.na of NA over all samples (gx.limma's max.na) is refitted on the samples it
 ## has, with its own df.residual (a seventh column of the tables) and stdev.unscaled, and eBayes takes the unequal df
 ## (hyper gains df.pooled); a row above max.na, or not estimable on what it has, is NA; at most 10 coefficients.
-## Not offered: trend, robust, weights, the B- and F-statistics, a sparse S.
-plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none", na = c("propagate", "fit"), max.na = 0.2) {
+## weights: NULL, a matrix in S's shape (observation weights, limma's `weights`: voom's, or quality weights from upstream) or a
+## vector over the samples (array weights): the weighted least squares of every row (plaidhip_limma_w).  An observation with
+## an NA value or a weight that is zero, negative, NA or infinite is missing, as in limma; the tables are those of na = "fit"
+## (na = "propagate" then fits no row that holds an NA); at most 10 coefficients.
+## Not offered: trend, robust, the B- and F-statistics, a sparse S; weights in the set tests.
+plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none", na = c("propagate", "fit"), max.na = 0.2,
+                        weights = NULL) {
   na <- match.arg(na)
   S <- as.matrix(S); storage.mode(S) <- "double"
   design <- as.matrix(design); storage.mode(design) <- "double"
@@ -727,11 +752,36 @@ plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none
   }
   rn <- if (is.null(rownames(S))) paste0("row", seq_len(nrow(S))) else rownames(S)
   if (length(sort.by) != 1L || !sort.by %in% .limma_sorts) stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", "))
+  weights <- .limma_weights(S, weights)
   .session()
-  r <- .limma_call(S, design, 1L, use, contrasts, na, max.na, length(cn), rn, sort.by)
+  r <- .limma_call(S, design, 1L, use, contrasts, na, max.na, length(cn), rn, sort.by, weights)
   tables <- r$tables
   names(tables) <- cn
   list(tables = tables, hyper = .limma_hyper(r$hyper[, 1]))
+}
+
+
+## plaid.voom(): limma's voom with normalize.method = "none" (as pinned in include/plaidhip.h: plaidhip_voom) of a counts matrix
+## (genes x samples, finite and >= 0) for one design.  lib.size: one entry per sample, NULL: the column sums.  span: the lowess
+## span of the mean-variance trend.  Returns list(E = <log2-CPM>, weights = <precision weights>, lib.size, offset =
+## log2(lib.size + 1) - log2(1e6), knots.x, knots.y = <the trend's knots>); plaid.limma(v$E, design, weights = v$weights) is
+## limma's lmFit + eBayes on that EList.  Not offered: other normalize.method, voomWithQualityWeights, arrayWeights,
+## duplicateCorrelation, a dgCMatrix of counts.
+plaid.voom <- function(counts, design, lib.size = NULL, span = 0.5) {
+  counts <- as.matrix(counts); storage.mode(counts) <- "double"
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(counts)) stop("design must have one row per column of counts")
+  if (!is.null(lib.size)) {
+    if (length(lib.size) != ncol(counts)) stop("lib.size must have one entry per column of counts")
+    lib.size <- as.double(lib.size)
+  }
+  if (length(span) != 1L || is.na(span) || span <= 0 || span > 1) stop("plaid.voom: span must lie in (0, 1]")
+  .session()
+  r <- .Call("R_plaidhip_voom", .devices(), counts, design, lib.size, as.double(span), PACKAGE = "plaidhip")
+  names(r) <- c("E", "weights", "lib.size", "offset", "knots.x", "knots.y")
+  dimnames(r$E) <- dimnames(r$weights) <- dimnames(counts)
+  names(r$lib.size) <- names(r$offset) <- colnames(counts)
+  r
 }
 
 
@@ -740,8 +790,9 @@ plaid.limma <- function(S, design, contrasts = NULL, use = NULL, sort.by = "none
 ## samples with a label and tests the coefficient of Y[, j].  B: batch covariates (samples x covariates) or NULL.  S is
 ## uploaded once and read ceiling(ncol(Y) * (p + 1) / 8) times for the effects.  Returns list(tables = <named list (the
 ## columns of Y) of plaid.limma() tables>, hyper = <named list of their hyper-parameters>).  na, max.na: as plaid.limma();
-## na = "fit" with max.na = 0.2 is gx.limma(S, y, B, max.na = 0.20) on a matrix with missing values.
-plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none", na = c("propagate", "fit"), max.na = 0.2) {
+## na = "fit" with max.na = 0.2 is gx.limma(S, y, B, max.na = 0.20) on a matrix with missing values.  weights: as plaid.limma(),
+## shared by the contrasts.
+plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none", na = c("propagate", "fit"), max.na = 0.2, weights = NULL) {
   na <- match.arg(na)
   S <- as.matrix(S); storage.mode(S) <- "double"
   Y <- as.matrix(Y)
@@ -759,8 +810,9 @@ plaid.limma.contrasts <- function(S, Y, B = NULL, sort.by = "none", na = c("prop
   cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
   rn <- if (is.null(rownames(S))) paste0("row", seq_len(nrow(S))) else rownames(S)
   if (length(sort.by) != 1L || !sort.by %in% .limma_sorts) stop("plaid.limma: sort.by must be one of ", paste(.limma_sorts, collapse = ", "))
+  weights <- .limma_weights(S, weights)
   .session()
-  r <- .limma_call(S, D, ncol(Y), use, K, na, max.na, ncol(Y), rn, sort.by)
+  r <- .limma_call(S, D, ncol(Y), use, K, na, max.na, ncol(Y), rn, sort.by, weights)
   tables <- r$tables
   hyper <- lapply(seq_len(ncol(Y)), function(j) .limma_hyper(r$hyper[, j]))
   names(tables) <- names(hyper) <- cn

@@ -891,6 +891,88 @@ SEXP R_plaidhip_limma_na(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use
   return res;
 }
 
+/* plaid.limma(weights = ): list(out, hyper, dfres) of plaidhip_limma_w -- R_plaidhip_limma_na's operands with Wt (a rows x n
+ * double matrix of observation weights, or NULL) and aw (n array weights, or NULL) after A; the R wrapper sends at least one */
+SEXP R_plaidhip_limma_w(SEXP devices, SEXP A, SEXP Wt, SEXP aw, SEXP design, SEXP nfit_, SEXP use, SEXP K, SEXP max_na_) {
+  const int rows = Rf_nrows(A), n = Rf_ncols(A), nfit = Rf_asInteger(nfit_);
+  const double max_na = Rf_asReal(max_na_);
+  if (nfit < 1 || Rf_nrows(design) != n || Rf_ncols(design) % nfit != 0)
+    Rf_error("plaid.limma: design must have one row per sample and the same number of columns for every fit");
+  const int p = Rf_ncols(design) / nfit;
+  const int q = Rf_isNull(K) ? p : Rf_ncols(K);
+  if (!Rf_isNull(K) && Rf_nrows(K) != p) Rf_error("plaid.limma: contrasts must have one row per coefficient");
+  if (!Rf_isNull(Wt) && (Rf_nrows(Wt) != rows || Rf_ncols(Wt) != n)) Rf_error("plaid.limma: a matrix of weights has the shape of S");
+  if (!Rf_isNull(aw) && LENGTH(aw) != n) Rf_error("plaid.limma: a vector of weights has one entry per sample");
+  int8_t* u8 = NULL;
+  if (!Rf_isNull(use)) {
+    if (Rf_nrows(use) != n || Rf_ncols(use) != nfit) Rf_error("plaid.limma: use must be samples x fits");
+    const size_t count = (size_t)n * (size_t)nfit;
+    const int* u = INTEGER(use);
+    u8 = (int8_t*)R_alloc(count > 0 ? count : 1, 1);
+    for (size_t e = 0; e < count; ++e) u8[e] = (int8_t)(u[e] != 0 && u[e] != NA_INTEGER);
+  }
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, rows, 6 * q * nfit));
+  SEXP hyper = PROTECT(Rf_allocMatrix(REALSXP, 5, nfit));
+  SEXP dfres = PROTECT(Rf_allocMatrix(REALSXP, rows, nfit));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, hyper);
+  SET_VECTOR_ELT(res, 2, dfres);
+  const double* Kp = Rf_isNull(K) ? NULL : REAL(K);
+  const double* Wp = Rf_isNull(Wt) ? NULL : REAL(Wt);
+  const double* ap = Rf_isNull(aw) ? NULL : REAL(aw);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_limma_w_multi(INTEGER(devices), LENGTH(devices), REAL(A), Wp, ap, rows, n, REAL(design), p, nfit, u8, Kp, q,
+                                max_na, REAL(out), REAL(hyper), REAL(dfres));
+  else
+    rc = plaidhip_limma_w(ctx(), REAL(A), Wp, ap, rows, n, REAL(design), p, nfit, u8, Kp, q, max_na, REAL(out), REAL(hyper),
+                          REAL(dfres));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(4);
+  return res;
+}
+
+/* plaid.voom(): list(E, weights, lib.size, offset, knots.x, knots.y) of plaidhip_voom -- counts a double genes x samples matrix,
+ * design samples x p, lib_size a double vector over the samples or NULL (the column sums), span the lowess span; several
+ * devices: the _multi entry */
+SEXP R_plaidhip_voom(SEXP devices, SEXP counts, SEXP design, SEXP lib_size, SEXP span_) {
+  const int rows = Rf_nrows(counts), n = Rf_ncols(counts), p = Rf_ncols(design);
+  const double span = Rf_asReal(span_);
+  if (Rf_nrows(design) != n) Rf_error("plaid.voom: design must have one row per column of counts");
+  if (!Rf_isNull(lib_size) && LENGTH(lib_size) != n) Rf_error("plaid.voom: lib.size must have one entry per sample");
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 6));
+  SEXP E = PROTECT(Rf_allocMatrix(REALSXP, rows, n));
+  SEXP W = PROTECT(Rf_allocMatrix(REALSXP, rows, n));
+  SEXP lib = PROTECT(Rf_allocVector(REALSXP, n));
+  SEXP off = PROTECT(Rf_allocVector(REALSXP, n));
+  double* kx = (double*)R_alloc(PLAIDHIP_VOOM_MAX_KNOTS, sizeof(double));
+  double* ky = (double*)R_alloc(PLAIDHIP_VOOM_MAX_KNOTS, sizeof(double));
+  int32_t nk = 0;
+  const double* lp = Rf_isNull(lib_size) ? NULL : REAL(lib_size);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_voom_multi(INTEGER(devices), LENGTH(devices), REAL(counts), rows, n, REAL(design), p, lp, span, REAL(E), REAL(W),
+                             REAL(lib), REAL(off), kx, ky, &nk);
+  else
+    rc = plaidhip_voom(ctx(), REAL(counts), rows, n, REAL(design), p, lp, span, REAL(E), REAL(W), REAL(lib), REAL(off), kx, ky, &nk);
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  SEXP kxs = PROTECT(Rf_allocVector(REALSXP, nk));
+  SEXP kys = PROTECT(Rf_allocVector(REALSXP, nk));
+  for (int i = 0; i < nk; ++i) {
+    REAL(kxs)[i] = kx[i];
+    REAL(kys)[i] = ky[i];
+  }
+  SET_VECTOR_ELT(res, 0, E);
+  SET_VECTOR_ELT(res, 1, W);
+  SET_VECTOR_ELT(res, 2, lib);
+  SET_VECTOR_ELT(res, 3, off);
+  SET_VECTOR_ELT(res, 4, kxs);
+  SET_VECTOR_ELT(res, 5, kys);
+  UNPROTECT(7);
+  return res;
+}
+
 /* plaid.rankcor(): list(out, tot) of plaidhip_rankcor -- out an m x 5c matrix (columns 5 l + 1 .. 5 l + 5 the columns of list
  * l; the caller gives it dim m x 5 x c), tot the c universe sizes.  stat: a g x c double matrix, NA / NaN: the gene takes no
  * part in that list; ties: 0 average, 1 min, 2 max; several devices: the _multi entry */
@@ -1006,6 +1088,8 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_fisher", (DL_FUNC)&R_plaidhip_fisher, 5},
     {"R_plaidhip_limma", (DL_FUNC)&R_plaidhip_limma, 6},
     {"R_plaidhip_limma_na", (DL_FUNC)&R_plaidhip_limma_na, 7},
+    {"R_plaidhip_limma_w", (DL_FUNC)&R_plaidhip_limma_w, 9},
+    {"R_plaidhip_voom", (DL_FUNC)&R_plaidhip_voom, 5},
     {"R_plaidhip_camera", (DL_FUNC)&R_plaidhip_camera, 10},
     {"R_plaidhip_fry", (DL_FUNC)&R_plaidhip_fry, 9},
     {"R_plaidhip_roast", (DL_FUNC)&R_plaidhip_roast, 11},
