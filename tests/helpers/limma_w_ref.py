@@ -335,6 +335,11 @@ def run_sharded(nshards, A, weights, design, use=None, contrasts=None, max_na=0.
 # ---- the cases the host and the GPU tests share -----------------------------------------------------------------------------------
 CASES = [(515, 300, 3, 3), (130, 131, 10, 2), (3, 130, 1, 1), (40, 7, 2, 1)]
 IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in CASES]
+# the instances and tiles CASES does not reach, at a dozen rows (12: every designated row; 11: odd, the 8-byte loads): p = 5 and
+# 8 (the 8-register residual kernel) and p = 9 (the first p past it); nfit = 9 (a second tile of 8 fits in the counts kernel,
+# holding one fit) and nfit = 17 (three of them; Wc = 3 and W = 51, so the tiles of 8 weight columns straddle fits)
+P_CASES = [(12, 131, 5, 1), (11, 131, 8, 2), (12, 131, 9, 1), (12, 40, 2, 9), (11, 40, 1, 17)]
+P_IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in P_CASES]
 # the designated rows (a case with fewer rows has those that fit): weights that make an observation missing at columns 0, 127,
 # 128 and n - 1 (zero, negative, NaN, +Inf); all weights zero within one group of fit 1 (not estimable); |live| = p in fit 1; a
 # live Inf value; NaN values beside the weights
@@ -387,3 +392,29 @@ def make_case(case):
 
 def fit_use(c, f):
     return None if c["use"] is None else c["use"][:, f]
+
+
+def case_designs(c, case):
+    """plaidhip_limma_design of every fit of a case (on the host)"""
+    from plaid_amd import engine
+    return [engine.limma_design(c["D"][:, :, f], fit_use(c, f), c["K"], fit=f + 1) for f in range(case[3])]
+
+
+def designated(c):
+    return set(c["role"].values())
+
+
+def assert_other_rows_are_far_from_the_rule(c, case):
+    """on the CPU: the smallest Cholesky pivot ratio d_k / H_kk of every row that is not designated exceeds 1e-3, so the
+    estimability rule is exercised only where the case plants it"""
+    rows, n, p, nfit = case
+    for f in range(nfit):
+        Q = c["des"][f]["Q"]
+        uf = fit_use(c, f)
+        for r in range(rows):
+            if r in designated(c):
+                continue
+            om = omega(c["Wt"][r], c["aw"])
+            live = live_mask(c["A"][r], om, uf)
+            H = (Q[live] * om[live, None]).T @ Q[live]
+            assert pivot_ratios(H[np.tril_indices(p)], p).min() > 1e-3, (r, f)

@@ -23,7 +23,10 @@ Integer-valued X in -8 .. 8.  What is checked, and against what:
 Shapes: n = 6, 127, 128, 130, 257 (no full block, one block less one, one block, a block and a tail, two blocks and a tail);
 g = 1, 2 (one thread's row pair, the 16-byte path), 3, 301 (an odd last row, the 8-byte path) and 600 (the 16-byte path past
 one workgroup of 512 rows); p = 1, 2, 4; nfit = 1 and 3 with different `use` columns and a NaN / Inf in a sample a fit leaves
-out; sets of 0, 1, 2, 64, 65 and g members; a constant gene (s2 below the 1e-8 floor) and a gene with a NaN in a used sample."""
+out; sets of 0, 1, 2, 64, 65 and g members; a constant gene (s2 below the 1e-8 floor) and a gene with a NaN in a used sample.
+For item 1 alone also P_CASES: p = 5 and 8, 9 and 16, 17 and 32 (both ends of the residual kernel's 8-, 16- and 32-register
+instances) on g = 3 and 4 at n = 40 and 70.  For plaidhip_dev_camera_sumsq alone a planted T of integers in -8 .. 8 with m =
+257 and 513 sets (past one and two workgroups of 256 sets), n = 130, leading dimension m + 3: the integer sum exactly."""
 import numpy as np
 import pytest
 
@@ -43,6 +46,10 @@ BOUND = {k: FACTOR * v for k, v in MEASURED.items()}
 # g, n, p, nfit
 CASES = [(301, 130, 2, 3), (301, 257, 4, 1), (3, 6, 1, 1), (2, 127, 2, 1), (1, 128, 1, 1), (301, 127, 1, 3), (600, 130, 2, 1)]
 IDS = ["x".join(str(v) for v in c) for c in CASES]
+# every register count of the residual kernel past p = 4 (p <= 8, 16, 32, both ends of each), on three genes (the 8-byte path)
+# and four (the 16-byte path): for test_z_is_the_host_entry_bit_for_bit alone
+P_CASES = [(3, 40, 5, 1), (4, 40, 8, 2), (3, 40, 9, 1), (4, 70, 16, 1), (3, 70, 17, 2), (4, 70, 32, 1)]
+P_IDS = ["x".join(str(v) for v in c) for c in P_CASES]
 
 
 def make_case(g, n, p, nfit):
@@ -148,7 +155,7 @@ def passes(hip_ctx):
     return get
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + P_CASES, ids=IDS + P_IDS)
 def test_z_is_the_host_entry_bit_for_bit(passes, case):
     X, D, use, sets, dv = passes(case)
     g, n, p, nfit = case
@@ -191,6 +198,32 @@ def test_sum_of_squares_against_exact_rationals(passes, case):
                 assert ss[s] == 0.0
             worst = max(worst, err / bound if bound > 0 else 0.0)
     print(f"[measure] sum of T^2 {case}: worst error / bound {worst:.3g}")
+
+
+@pytest.mark.parametrize("m", [257, 513])
+def test_sum_of_squares_of_a_planted_t_past_one_workgroup_of_sets(hip_ctx, m):
+    """plaidhip_dev_camera_sumsq alone: integers in -8 .. 8, so every square and every partial sum is an integer far below
+    2^53 and the result is numpy's integer sum exactly; m = 257 and 513 sets (a second and a third workgroup of 256, the last
+    holding one set), n = 130 (a column block and a tail of two), leading dimension m + 3"""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, ldt = 130, m + 3
+    rng = np.random.default_rng(m)
+    Ti = rng.integers(-8, 9, size=(m, n))
+    Td = torch.full((n, ldt), -7.0, dtype=torch.float64, device=dev)
+    Td[:, :m] = torch.from_numpy(np.ascontiguousarray(Ti.T.astype(np.float64))).to(dev)
+    ssd = torch.full((m + 5,), -7.0, dtype=torch.float64, device=dev)
+    half = torch.full((m + 5,), -7.0, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    hip_ctx.dev_camera_sumsq(Td.data_ptr(), ldt, m, n, None, ssd.data_ptr())
+    hip_ctx.dev_camera_sumsq(Td.data_ptr(), ldt, m, 128, None, half.data_ptr())           # the first block alone ...
+    hip_ctx.dev_camera_sumsq(Td.data_ptr() + 8 * ldt * 128, ldt, m, n - 128, half.data_ptr(), half.data_ptr())   # ... then the rest
+    hip_ctx.synchronize()
+    ss, chained = ssd.cpu().numpy(), half.cpu().numpy()
+    assert (ss[m:] == -7.0).all() and (chained[m:] == -7.0).all()                    # nothing past the last set is written
+    assert np.array_equal(ss[:m], (Ti * Ti).sum(axis=1).astype(np.float64))
+    assert np.array_equal(chained[:m].view(np.int64), ss[:m].view(np.int64))
+    assert (Td.cpu().numpy()[:, m:] == -7.0).all()
 
 
 @pytest.fixture(scope="module")

@@ -4,7 +4,9 @@ What is checked, and against what (DESIGN.md section 26 has the derivations and 
   1. Z' of plaidhip_dev_fry_residuals is equal bit for bit to plaidhip_fry_residual_row (the same inline functions, on the
      host) on the device's own effects and on the divisors plaidhip_fry_divisors makes of the device's own RSS: rows 7 (odd,
      the 8-byte path) and 8 (the 16-byte path); n = 5, 131, 260 (the tail of the unroll, one and two column-block crossings);
-     a `use` mask; p = 2 and 5; all three `standardize` values.
+     a `use` mask; p = 2 and 5; all three `standardize` values.  Shapes past these: p = 9 and 16, 17 and 32 (both ends of
+     the 16- and 32-register instances) at n = 40 and 70, and rows 515 and 514 (a second workgroup of 512 rows), each on
+     both load paths.
   2. The residual effects rho = Q2'z' at n_f = 131, p = 4 (d + 1 = 128: the cap, across a column block) against exact
      rationals on the device's own Z' within gamma_{128 + nblk} sum |q||z|: a block's chain of at most 128 fma carries
      gamma_128, the nblk block additions the rest.
@@ -38,6 +40,10 @@ BOUND = {k: fr.FACTOR * v for k, v in fr.MEASURED.items()}
 
 # rows, n, p, nfit (nfit = 2: the second fit leaves samples out)
 RES_CASES = [(7, 5, 2, 1), (8, 5, 2, 1), (8, 131, 5, 2), (7, 260, 2, 2), (8, 260, 5, 1), (7, 131, 4, 1)]
+# (appended only: test_residual_effects_against_exact_rationals takes RES_CASES[5]) the 16- and 32-register instances of the
+# residual kernel at both ends (p = 9, 16, 17, 32), and a second workgroup of 512 rows holding three rows and two, each on
+# both load paths
+RES_CASES += [(8, 40, 9, 1), (7, 70, 16, 2), (8, 70, 17, 1), (7, 70, 32, 1), (515, 131, 5, 2), (514, 131, 2, 1)]
 RES_IDS = ["x".join(str(v) for v in c) for c in RES_CASES]
 
 

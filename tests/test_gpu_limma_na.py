@@ -8,6 +8,10 @@
   6. every sharding has the one-device bits; a failing shard writes nothing
   7. plaid_limma_contrasts on the 50-cell fixture with 5 % NaN: every contrast is its own plaid_limma(na = "fit")
   8. the device's gamma and u are those of plaidhip_limma_na_solve on the same Q rows and E', bit for bit
+
+Shapes: CASES -- (rows, n, p, nfit) = (515, 300, 3, 3), (130, 131, 8, 2), (130, 300, 2, 3) -- and, for items 1, 2 and 5,
+P_CASES = (60, 131, 10, 1), (61, 131, 9, 2): p = 9 and 10 run the 16-register instance of the residual kernel with the NaN
+select, which no case with p <= 8 launches; 60 rows are the fewest that hold ROLE, SINGLES and SPREAD.
 """
 import numpy as np
 import pytest
@@ -25,6 +29,10 @@ U = lr.U
 # rows, n, p, nfit: past a 64-lane tile, odd (the narrow loads) and even (the wide ones); ragged past one and two blocks of 128
 CASES = [(515, 300, 3, 3), (130, 131, 8, 2), (130, 300, 2, 3)]
 IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in CASES]
+# past eight coefficients (p = 9, 10: the 16-register instance of the residual kernel with the NaN select), at the fewest rows that
+# hold ROLE, SINGLES and SPREAD; even and odd.  Held to na = "propagate", whose p = 9 is held to exact sums in test_gpu_limma.py
+P_CASES = [(60, 131, 10, 1), (61, 131, 9, 2)]
+P_IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in P_CASES]
 ROLE = {"c0": 0, "c127": 1, "c128": 2, "clast": 3, "four": 4, "group": 5, "all": 6, "unused": 7, "inf_used_nan": 8,
         "inf_unused": 9, "inf_used": 10, "above": 11, "p_left": 12}
 SINGLES = range(20, 40)       # one NaN per row, anywhere
@@ -86,7 +94,7 @@ def pair_state(c, r, f, max_na):
     return np.isnan(x).sum() / len(x) <= max_na, [int(t) for t in sel[np.isnan(x[sel])]], sel
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + P_CASES, ids=IDS + P_IDS)
 def test_without_missing_values_fit_is_propagate(hip_ctx, case):
     c = case_results(hip_ctx, case)
     out0, hyper0 = hip_ctx.limma(c["A0"], c["D"], c["use"], c["K"])
@@ -98,7 +106,7 @@ def test_without_missing_values_fit_is_propagate(hip_ctx, case):
     assert np.array_equal(hyper1[:, 4], hyper0[:, 3] * hyper0[:, 0])
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + P_CASES, ids=IDS + P_IDS)
 def test_complete_rows_keep_the_bits_of_propagate(hip_ctx, case):
     c = case_results(hip_ctx, case)
     rows, n, p, nfit = case
@@ -283,7 +291,7 @@ def test_the_device_follows_the_header_to_the_bit(hip_ctx):
     assert seen_not_ok == 1 and len(pairs) >= 10
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + P_CASES, ids=IDS + P_IDS)
 def test_rows_that_must_be_nan(hip_ctx, case):
     c = case_results(hip_ctx, case)
     rows, n, p, nfit = case

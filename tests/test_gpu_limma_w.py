@@ -8,6 +8,13 @@
   4. the old paths: no weights -> the old entries' bits; weights of 0 and 1 against na = "fit"; array weights against the same
      values as a matrix; all weights times 4; all weights 1 against plaidhip_limma
   5. every sharding has the one-device bits; a failing shard writes nothing
+
+Shapes: wr.CASES -- (rows, n, p, nfit) = (515, 300, 3, 3), (130, 131, 10, 2), (3, 130, 1, 1), (40, 7, 2, 1) -- and, for items
+1 and 3, wr.P_CASES: (12, 131, 5, 1), (11, 131, 8, 2) and (12, 131, 9, 1) for the 8-register instance of the residual kernel
+and the first p past it; (12, 40, 2, 9) and (11, 40, 1, 17) for a second and a third tile of 8 fits in the counts kernel, 9
+and 17 fits in the solve, and weight-column tiles that straddle fits (Wc = 3, W = 51).  12 rows hold every designated row, 11
+are odd (the 8-byte loads).  Item 3 runs on ALL rows and fits of P_CASES, item 1 on the first three of them;
+tests/test_limma_w_ref.py establishes what both presume of these inputs without a device.
 """
 import numpy as np
 import pytest
@@ -24,6 +31,7 @@ pytestmark = pytest.mark.gpu
 
 U = lr.U
 CASES, IDS = wr.CASES, wr.IDS
+P_CASES, P_IDS = wr.P_CASES, wr.P_IDS
 _CACHE = {}
 
 
@@ -52,27 +60,11 @@ def row_units(c, f, r, ref, eta):
     return wr.units(c["A"][r], om, des["Q"], list(sel), des["v"], ref, hinv, Hn, eta[0], eta[1]), sel
 
 
-def designated(c):
-    return set(c["role"].values())
+designated = wr.designated
+assert_other_rows_are_far_from_the_rule = wr.assert_other_rows_are_far_from_the_rule      # (tests/test_limma_w_ref.py runs it too)
 
 
-def assert_other_rows_are_far_from_the_rule(c, case):
-    """on the CPU: the smallest Cholesky pivot ratio d_k / H_kk of every row that is not designated exceeds 1e-3, so the
-    estimability rule is exercised only where the case plants it"""
-    rows, n, p, nfit = case
-    for f in range(nfit):
-        Q = c["des"][f]["Q"]
-        uf = wr.fit_use(c, f)
-        for r in range(rows):
-            if r in designated(c):
-                continue
-            om = wr.omega(c["Wt"][r], c["aw"])
-            live = wr.live_mask(c["A"][r], om, uf)
-            H = (Q[live] * om[live, None]).T @ Q[live]
-            assert wr.pivot_ratios(H[np.tril_indices(p)], p).min() > 1e-3, (r, f)
-
-
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + P_CASES[:3], ids=IDS + P_IDS[:3])
 def test_rows_against_the_exact_reference(hip_ctx, case):
     c = case_results(hip_ctx, case)
     rows, n, p, nfit = case
@@ -283,6 +275,69 @@ def test_the_device_follows_the_header_to_the_bit(hip_ctx):
                 assert rss[f, i] == wr.emulate_w_rss(c["A"][r], om, c["des"][f]["Q"], sel, [float(t) for t in G[f * (p + 1):f * (p + 1) + p, i]])
                 checked += 1
     assert checked == 9
+
+
+@pytest.mark.parametrize("case", P_CASES, ids=P_IDS)
+def test_every_p_instance_and_fit_tile_follows_the_header_to_the_bit(hip_ctx, case):
+    """the test above on ALL rows and fits of wr.P_CASES: the 8-register residual kernel (p = 5, 8), the first p past it (9),
+    and a second and a third tile of fits in the counts kernel (nfit = 9, 17).  H, b and M' of the device entry are the
+    emulation's chains and the counts are numpy's; the call's logFC is the fma chain v . gamma of plaidhip_limma_w_solve's
+    gamma on those sums and its t follows from that entry's u; dfres = |live| - p; sigma2 is the residual entry's RSS / d_r
+    and that RSS is the emulation's chain.  A row above max_na, and a pair that is not estimable, is NaN on both sides."""
+    c = case_results(hip_ctx, case)
+    rows, n, p, nfit = case
+    out, hyper, dfres = c["w"]
+    q = c["K"].shape[1]
+    Q = np.stack([d["Q"] for d in c["des"]], axis=2)
+    nf = np.array([d["nf"] for d in c["des"]], dtype=np.int64)
+    S, cnt = device_sums(hip_ctx, c["A"], c["Wt"], c["aw"], Q, c["use"], nf)
+    T, Wc = p * (p + 1) // 2, p * (p + 1) // 2 + p + 1
+    G = np.full((nfit * (p + 1), rows), np.nan)
+    fitted = np.isnan(c["A"]).sum(axis=1) / n <= 0.2
+    assert np.array_equal(cnt[2 * nfit], np.isnan(c["A"]).sum(axis=1))
+    seen_not_ok = 0
+    for f in range(nfit):
+        des, uf = c["des"][f], wr.fit_use(c, f)
+        sel = np.arange(n) if uf is None else np.flatnonzero(uf != 0)
+        for r in range(rows):
+            Htri, b, Mp = S[f * Wc:f * Wc + T, r], S[f * Wc + T:f * Wc + T + p, r], S[f * Wc + T + p, r]
+            om = wr.omega(c["Wt"][r], c["aw"])
+            assert cnt[2 * f, r] == wr.live_mask(c["A"][r], om, uf).sum(), (r, f)
+            assert cnt[2 * f + 1, r] == (~np.isnan(c["A"][r][sel])).sum(), (r, f)
+            eH, eb, eM, _, _ = wr.emulate_sums(c["A"][r], om, des["Q"], sel)
+            er.assert_same_bits(Htri, eH, f"H of row {r}, fit {f}")
+            er.assert_same_bits(b, eb, f"b of row {r}, fit {f}")
+            assert Mp == eM, (r, f)
+            got = engine.limma_w_solve(Htri, b, int(cnt[2 * f, r]), des["v"])
+            if not fitted[r] or not got["ok"] or not np.isfinite(b).all():
+                seen_not_ok += 1
+                assert np.isnan(out[r, :, :, f]).all() and np.isnan(dfres[r, f]), (r, f)
+                continue
+            d = cnt[2 * f, r] - p
+            assert dfres[r, f] == d
+            assert out[r, 1, 0, f] == (Mp * len(sel)) / cnt[2 * f + 1, r]
+            G[f * (p + 1):f * (p + 1) + p, r] = got["gamma"]
+            fc = nr.emulate_logfc(des["v"], [float(t) for t in got["gamma"]])
+            for j in range(q):
+                assert out[r, 0, j, f] == fc[j], (r, f, j)
+                t = fc[j] / (got["u"][j] * np.sqrt(_post(out[r, 5, j, f], float(d), hyper[f])))
+                assert out[r, 2, j, f] == t, (r, f, j, out[r, 2, j, f], t)
+    # fit 1 at least: |live| = p, the live Inf, the group without weight (p > 1), the row above max_na (12 rows)
+    assert seen_not_ok >= 2 + (p > 1) + (rows > wr.ROLE["above"])
+    rss = device_rss(hip_ctx, c["A"], c["Wt"], c["aw"], Q, c["use"], G)
+    checked = 0
+    for f in range(nfit):
+        uf = wr.fit_use(c, f)
+        sel = np.arange(n) if uf is None else np.flatnonzero(uf != 0)
+        for r in range(rows):
+            if np.isnan(G[f * (p + 1), r]):
+                continue
+            assert out[r, 5, 0, f] == rss[f, r] / dfres[r, f], (r, f)
+            om = wr.omega(c["Wt"][r], c["aw"])
+            gam = [float(t) for t in G[f * (p + 1):f * (p + 1) + p, r]]
+            assert rss[f, r] == wr.emulate_w_rss(c["A"][r], om, c["des"][f]["Q"], sel, gam), (r, f)
+            checked += 1
+    assert checked == nfit * rows - seen_not_ok
 
 
 def test_no_weights_is_the_old_entries_bits(hip_ctx):

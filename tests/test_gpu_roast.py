@@ -7,7 +7,9 @@ What is checked, and against what (DESIGN.md section 27 has the derivations and 
      prior and df0 = inf) within 4 x roast_ref.MEASURED["z"] of the 50-digit z, relative to max(1, |z|).  Rows 7 (the 8-byte
      path) and 8 (the 16-byte path); n = 5, 131, 260 with a `use` mask; p = 2 and 5; nrot = 1, 63, 64, 65, 130 with the
      chunk forced to 64 rotations (a second and a third launch); a constant gene, a gene outside the universe (NaN).  The
-     padding of the last tile and what follows Z are not written.
+     padding of the last tile and what follows Z are not written.  Shapes past these: rows 515 (the 8-byte path) and 514
+     (the 16-byte path), a second workgroup of 512 rows, with 65 rotations in chunks of 64 -- the device on all rows, the
+     50-digit form on the first three rows, the last two of workgroup 0 and the rows of workgroup 1, at the same bounds.
   2. roast_stat_kernel / roast_mean50_kernel bit for bit against roast_ref.stats_np (mean50: the pinned threshold form) on
      given z: sets of 0, 1, 2, 3, 63, 64, 65, 300 members, one at the mean50 cap and one above it; two identical values
      straddling tau, all-equal z, +-0.0, z of one sign only; 70 rotations (a full and a partial tile).
@@ -148,6 +150,51 @@ def test_rotate_kernel_against_the_50_digit_form(hip_ctx, case):
             whole = device_rotate(hip_ctx, fit, W, fit["d"], df0, s02, zscore, 0)       # the chunking changes no bit
             assert np.array_equal(whole.view(np.int64), got.view(np.int64))
     print(f"[rotate] {case}: worst z deviation {worst:.3g} (allowed {rr.FACTOR * rr.MEASURED['z']:.3g})")
+
+
+# a second workgroup of 512 rows, holding three rows (the 8-byte path) and two (the 16-byte path); 65 rotations in chunks of 64
+BLOCK_CASES = [(515, 131, 2, True, 65), (514, 131, 5, False, 65)]
+BLOCK_IDS = ["x".join(str(int(v)) for v in c) for c in BLOCK_CASES]
+
+
+@pytest.mark.parametrize("case", BLOCK_CASES, ids=BLOCK_IDS)
+def test_rotate_kernel_past_one_workgroup_of_rows(hip_ctx, case):
+    """the test above with the device on all rows and the 50-digit form on the first three rows, the last two of workgroup 0
+    and the rows of workgroup 1 (rows are independent: beta, the RSS and the residuals are sliced), at the same bounds.
+    Over the whole array: NaN exactly outside the universe, the last tile's padding and what follows Z unwritten
+    (device_rotate), and the chunked call bit for bit the whole one."""
+    rows, n, p, masked, nrot = case
+    X, D, use = rot_case(rows, n, p, masked)
+    fit = device_fit(hip_ctx, X, D, use)
+    W = engine.roast_rotations(D, use, 0, nrot, seed=case[1])
+    cols = sorted({k for k in (0, 1, 15, 16, 62, 63, 64) if k < nrot})
+    pick = sorted({0, 1, 2, 510, 511, 512, 513, rows - 1})
+    gam = (n + 1) * U / (1 - (n + 1) * U)
+    ok = fit["ok"]
+    okp = ok[pick]
+    assert not ok[rows - 1] and ok[2] and ok[510:rows - 1].all()                  # the NaN gene is the last row of workgroup 1
+    beta, rss, Rz = fit["beta"][pick], fit["rss"][pick], fit["Rz"][pick]
+    got = device_rotate(hip_ctx, fit, W, fit["d"], np.inf, 1.0, "none", 64)
+    Bm, _, Ba = rr.rotate_mp(beta, rss, Rz, W[:, cols], fit["d"], np.inf, 1.0, "none")
+    assert np.isnan(got[~ok]).all() and np.isfinite(got[ok]).all()
+    err = np.abs(got[pick][okp][:, cols] - Bm[okp])
+    print(f"[measure] rotate {case}: worst |B - exact| / bound = {np.max(err / np.maximum(gam * Ba[okp], 1e-300)):.3g}")
+    assert (err <= gam * Ba[okp]).all()
+    if use is not None:
+        assert (fit["Rz"][:, use == 0] == 0.0).all()
+    worst = 0.0
+    for zscore in ("hill", "none"):
+        for df0, s02 in ((fit["df0"], fit["s02"]), (np.inf, 0.75)):
+            got = device_rotate(hip_ctx, fit, W, fit["d"], df0, s02, zscore, 64)
+            _, zm, _ = rr.rotate_mp(beta, rss, Rz, W[:, cols], fit["d"], df0, s02, zscore)
+            assert np.isnan(got[~ok]).all()
+            dev = rr.rel_dev(got[pick][okp][:, cols], zm[okp])
+            worst = max(worst, dev)
+            assert dev <= rr.FACTOR * rr.MEASURED["z"], (zscore, df0, dev)
+            assert np.isfinite(got[pick][okp]).all() == np.isfinite(zm[okp]).all()
+            whole = device_rotate(hip_ctx, fit, W, fit["d"], df0, s02, zscore, 0)       # the chunking changes no bit
+            assert np.array_equal(whole.view(np.int64), got.view(np.int64))
+    print(f"[measure] rotate {case}: worst z deviation {worst:.3g} (allowed {rr.FACTOR * rr.MEASURED['z']:.3g})")
 
 
 # ---- the set statistics --------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,12 @@
   4. end to end: plaid_voom then plaid_limma(weights = ) against the same pins in numpy / mpmath with their own lowess
   5. a negative count, a NaN count and more than 256 planted knots are EINVAL with nothing written
   6. shards 1, 2, 3 have the one-device bits
+
+Shapes: whole calls at counts (600, 131) with p = 3 and (41, 6) with p = 2; items 3 and 6 also at (300, 40) with p = 9, where
+the unweighted fit and the weights pass run their 16-register instances.  plaidhip_dev_voom_weights alone on planted operands
+at p = 4, 5, 8, 9, 16, 17, 32 (both ends of every register count), 257 rows (a second workgroup of 256 that holds one row),
+129 samples (a column block and a tail of one), ldw = rows + 3 with the padding checked, the mean's row of the effects NaN.
+A bad count at rows 39 of 41, and at rows 300 and 599 of 600 (a thread's second and third trip in the check kernel).
 """
 import math
 
@@ -26,6 +32,11 @@ pytestmark = pytest.mark.gpu
 
 CASES = [(600, 131, 3), (41, 6, 2)]
 IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}" for c in CASES]
+# one whole call past eight coefficients: the unweighted fit and the weights pass both at their 16-register instance
+P9_CASES = [(300, 40, 9)]
+P9_IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}" for c in P9_CASES]
+# the planted operands: both ends of every register count of the weights kernel (p <= 4, 8, 16, 32)
+PLANTED_P = [4, 5, 8, 9, 16, 17, 32]
 # the device's log2 against the correctly rounded value on these inputs, in ulp: measured on the MI355X;
 # the test holds it to twice that, never less than 2 ulp and never more than 4
 LOG2_ULP_MEASURED = 1.0
@@ -83,19 +94,23 @@ def test_log_cpm_against_correctly_rounded_values(hip_ctx, case):
     assert worst <= LOG2_ULP_BOUND
 
 
-def device_weights(ctx, Q, offset, Eff, kx, ky, rows, sentinel=-7.0):
-    """(status, W rows x n) of plaidhip_dev_voom_weights; W holds the sentinel before the call"""
+def device_weights(ctx, Q, offset, Eff, kx, ky, rows, sentinel=-7.0, ldw=None):
+    """(status, W rows x n) of plaidhip_dev_voom_weights; W (leading dimension ldw, `rows` if None) holds the sentinel before
+    the call, and its padding past `rows` must hold it afterwards"""
     import torch
     dev = torch.device("cuda", 0)
     n, p = Q.shape
+    ldw = rows if ldw is None else ldw
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
     Qd, od, Ed, kxd, kyd = t(Q.T), t(offset), t(Eff), t(kx), t(ky)
-    W = torch.full((n, rows), sentinel, dtype=torch.float64, device=dev)
+    W = torch.full((n, ldw), sentinel, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
     status, _ = _status(lambda: ctx.dev_voom_weights(Qd.data_ptr(), od.data_ptr(), n, p, Ed.data_ptr(), rows, kxd.data_ptr(),
-                                                     kyd.data_ptr(), len(kx), W.data_ptr(), rows))
+                                                     kyd.data_ptr(), len(kx), W.data_ptr(), ldw))
     ctx.synchronize()
-    return status, W.cpu().numpy().T
+    Wh = W.cpu().numpy()
+    assert (Wh[:, rows:] == sentinel).all()                                       # the padding of W is not written
+    return status, Wh[:, :rows].T
 
 
 def device_effects(ctx, c):
@@ -105,7 +120,7 @@ def device_effects(ctx, c):
     return device_passes(ctx, np.asfortranarray(E), E.shape[0] + (E.shape[0] & 1), Q, None, np.array([E.shape[1]], dtype=np.int64))[0]
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + P9_CASES, ids=IDS + P9_IDS)
 def test_the_weights_pass_follows_the_header_to_the_bit(hip_ctx, case):
     c = case_results(hip_ctx, case)
     v = c["voom"]
@@ -128,6 +143,33 @@ def test_the_weights_pass_follows_the_header_to_the_bit(hip_ctx, case):
     assert (lam < kx[0]).any() and (lam > kx[-1]).any() and np.isin(lam, kx).sum() >= len(kx) and np.isnan(wp).any()
     on = np.isin(lam, kx[[0, 1, 2, 4]])
     assert np.array_equal(wp[on], [1.0 / ((f * f) * (f * f)) for f in ky[np.searchsorted(kx, lam[on])]])   # exactly Y_k at a knot
+
+
+@pytest.mark.parametrize("p", PLANTED_P, ids=[f"p{p}" for p in PLANTED_P])
+def test_the_weights_kernel_on_planted_operands_at_every_register_count(hip_ctx, p):
+    """plaidhip_dev_voom_weights alone: 257 rows (a second workgroup that holds one row), 129 samples (a column block and a
+    tail of one), W with leading dimension rows + 3, a random Q and offsets, and effects of six patterns -- row r carries
+    pattern r % 6, so the emulation of six rows is the reference of all 257.  The mean's row of Eff is NaN: the kernel does
+    not read it.  The knots are planted as above."""
+    rows, n, npat = 257, 129, 6
+    rng = np.random.default_rng([28, p])
+    Q, offset = rng.normal(size=(n, p)), rng.normal(size=n)
+    pat = rng.normal(size=(p, npat))
+    Eff = np.full((p + 1, rows), np.nan)
+    Eff[:p] = pat[:, np.arange(rows) % npat]
+    lam, _ = vr.emulate_weights(Q, offset, pat, [0.0], [1.0])                     # (lambda does not depend on the knots)
+    flat = np.sort(lam.ravel())
+    kx = np.unique(flat[np.linspace(len(flat) * 0.2, len(flat) * 0.8, 9).astype(int)])
+    ky = np.linspace(0.4, 1.6, len(kx))
+    ky[3] = -0.25
+    _, wp = vr.emulate_weights(Q, offset, pat, kx, ky)
+    assert (lam < kx[0]).any() and (lam > kx[-1]).any() and np.isin(lam, kx).sum() >= len(kx) and np.isnan(wp).any()
+    assert np.isfinite(wp[~np.isnan(wp)]).all() and not np.isnan(wp).all(axis=1).any()
+    status, W = device_weights(hip_ctx, Q, offset, Eff, kx, ky, rows, ldw=rows + 3)
+    assert status == _lib.OK
+    want = wp[np.arange(rows) % npat]
+    assert np.array_equal(np.isnan(W), np.isnan(want))                            # finite, or the planted NaN
+    er.assert_same_bits(W, want, f"planted operands, p = {p}")
 
 
 def test_end_to_end_against_the_pins_in_numpy(hip_ctx):
@@ -194,7 +236,24 @@ def test_error_paths_write_nothing(hip_ctx):
     assert status == _lib.OK and (W == 1.0).all()
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("where", ["row300-col0", "last-row-last-col"])
+def test_a_bad_count_on_a_threads_later_trip_writes_nothing(hip_ctx, where):
+    """the check kernel's 256 threads stride over the rows: of the 600-row case, row 300 is seen on a thread's second trip
+    and row 599 on its third"""
+    c = case_results(hip_ctx, CASES[0])
+    rows, n, p = CASES[0]
+    r, col = (300, 0) if where == "row300-col0" else (rows - 1, n - 1)
+    for bad in (-1.0, np.nan, np.inf):
+        counts = c["counts"].copy(order="F")
+        counts[r, col] = bad
+        out = dict(E=np.full((rows, n), -7.0, order="F"), W=np.full((rows, n), -7.0, order="F"), lib=np.full(n, -7.0),
+                   off=np.full(n, -7.0), kx=np.full(engine.VOOM_MAX_KNOTS, -7.0), ky=np.full(engine.VOOM_MAX_KNOTS, -7.0))
+        status, _ = _status(lambda: engine._voom(hip_ctx.lib.plaidhip_voom, (hip_ctx.handle,), counts, c["D"], out=out))
+        assert status == _lib.EINVAL and "finite and >= 0" in _lib.load().plaidhip_last_error_string().decode()
+        assert all((a == -7.0).all() for a in out.values())
+
+
+@pytest.mark.parametrize("case", CASES + P9_CASES, ids=IDS + P9_IDS)
 def test_every_sharding_has_the_one_device_bits(hip_ctx, case):
     c = case_results(hip_ctx, case)
     one = c["voom"]

@@ -7,6 +7,8 @@
      of two change no bit of gamma and no decision
   4. the emulation of the whole pinned order lies within the forward bound of section 28 of the 50-digit reference
   5. na = "fit" keeps its absolute rule: plaidhip_limma_na_solve against limma_na_ref's emulation on a pivot between the rules
+  6. limma_w_ref.P_CASES meet what tests/test_gpu_limma_w.py presumes of them: pivot ratios, the designated rows, the bound's
+     own condition
 """
 import numpy as np
 import pytest
@@ -134,6 +136,52 @@ def test_the_pinned_order_lies_within_the_derived_bound(p, kind):
     assert all(v <= 1.0 for v in dev.values()), dev
     ave = (Mp * len(sel)) / nseen
     assert abs(ave - float(ref["M"])) <= (len(sel) + 4) * lr.U * np.abs(x).mean()
+
+
+@pytest.mark.parametrize("case", wr.P_CASES, ids=wr.P_IDS)
+def test_the_p_cases_meet_what_the_device_tests_presume(case):
+    """wr.P_CASES, on the inputs and the references alone, so that tests/test_gpu_limma_w.py can only fail on the device's
+    numbers: every row that is not designated is far from the estimability rule; the designated rows behave as planted (a
+    weight that is not positive and finite only removes its observation; the group without weight, |live| = p and the live
+    Inf are not fitted in fit 1; the row above max_na in none); the integers of the plain-numpy rules agree with the
+    50-digit reference on which rows are fitted; the bound's own condition (wr.units asserts it) holds on every fitted row;
+    and the emulation of the pinned order lies within that bound"""
+    rows, n, p, nfit = case
+    c = wr.make_case(case)
+    c["des"] = wr.case_designs(c, case)
+    role = c["role"]
+    assert set(role) == {k for k, r in wr.ROLE.items() if r < rows} and (rows < 12 or len(role) == len(wr.ROLE))
+    wr.assert_other_rows_are_far_from_the_rule(c, case)
+    worst = {}
+    for f in range(nfit):
+        Df, uf, des = c["D"][:, :, f], wr.fit_use(c, f), c["des"][f]
+        sel = np.arange(n) if uf is None else np.flatnonzero(uf != 0)
+        okall, dall = wr.expected_integers(c["A"], c["Wt"], c["aw"], des["Q"], uf, 0.2)
+        refs = wr.limma_w_mp(c["A"], c["Wt"], c["aw"], Df, uf, c["K"], max_na=0.2, tail=False)
+        assert [ref is not None for ref in refs] == list(okall)
+        assert okall.sum() >= rows - len(role) and okall.sum() >= 3
+        for key in ("w_zero", "w_neg", "w_nan", "w_inf", "nan_beside"):
+            assert okall[role[key]], (key, f)
+        if f == 0:
+            assert not okall[role["p_left"]] and dall[role["p_left"]] == 0 and not okall[role["inf_live"]]
+            assert p == 1 or not okall[role["group"]]
+        if "above" in role:
+            assert not okall[role["above"]]
+        if case not in wr.P_CASES[:3]:
+            continue
+        eta = wr.basis_error(Df, uf, c["K"], des)
+        for r in np.flatnonzero(okall):
+            om = wr.omega(c["Wt"][r], c["aw"])
+            hinv, Hn = wr.exact_H(des["Q"], om, refs[r]["live"])
+            unit = wr.units(c["A"][r], om, des["Q"], list(sel), des["v"], refs[r], hinv, Hn, eta[0], eta[1])
+            Htri, b, _, nlive, _ = wr.emulate_sums(c["A"][r], om, des["Q"], sel)
+            ok, g, us, _ = wr.emulate_w_solve(Htri, b, nlive, des["v"])
+            assert ok and refs[r]["d"] == nlive - p == dall[r]
+            dev = nr.deviations(nr.emulate_logfc(des["v"], g), us, wr.emulate_w_rss(c["A"][r], om, des["Q"], sel, g), refs[r], unit)
+            assert all(v <= 1.0 for v in dev.values()), (r, f, dev)
+            worst = {k: max(v, worst.get(k, 0.0)) for k, v in dev.items()}
+    if worst:
+        print(f"[measure] {case}: the emulation's worst share of the bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
 
 
 def test_na_fit_keeps_its_absolute_rule():
