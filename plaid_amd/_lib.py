@@ -209,6 +209,14 @@ SIGNATURES = {
     "plaidhip_dev_roast_stats": [_vp, _vp, _i32, _vp, _vp, _i32, _int, _i32, _vp, _vp, _vp],
     "plaidhip_roast_rotations": [_vp, _i32, _i32, _vp, _i32, _i32, C.c_uint64, _vp],
     "plaidhip_roast_finish": [_i32, _i32, _i32, _i32, _int, _int, _vp, _vp, _vp, _vp, _vp],
+    "plaidhip_romer": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _int, _i32, C.c_uint64, _int, _vp, _vp,
+                       _vp, _vp],
+    "plaidhip_romer_multi": [_vp, _int, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _int, _i32, C.c_uint64,
+                             _int, _vp, _vp, _vp, _vp],
+    "plaidhip_dev_romer_keys": [_vp, _vp, _i32, _vp, _i32, _i64, _int, _i32, _i32, _vp, _vp, _vp, _vp],
+    "plaidhip_dev_romer_sides": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _int, _i32, _i32, _vp, _vp, _vp],
+    "plaidhip_romer_shrink": [_i32, _vp, _f64, _f64, _f64, _vp, _vp],
+    "plaidhip_romer_finish": [_i32, _i32, _i32, _i32, _int, _vp, _vp, _vp],
     "plaidhip_plaid_test_finish": [_i32, _i32, _vp, _vp, _f64, _f64, _vp, _i64, _i64, _int, _int, _vp],
     # host-only GMT text path (gmt.cpp)
     "plaidhip_gmt_read": [C.c_char_p, _int, _i64, C.POINTER(_vp)],

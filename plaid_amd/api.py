@@ -1255,7 +1255,8 @@ def plaid_roast(X, design, G, contrasts=None, use=None, set_statistic="mean50", 
     Returns (tables, hyper): contrast name -> NamedMatrix (sets x [NGenes, PropDown, PropUp, Direction (+1 Up, -1 Down),
     PValue, FDR, PValue.Mixed, FDR.Mixed]) ordered by `sort_by` ("directional", "mixed" or "none"; stable, NaN last), and
     plaid_limma's four values, n.genes, nrot and mean50.capped.
-    Not offered: per-set rotations, romer, gene or array weights, trend.var, robust, a sparse X, na = "fit"."""
+    Not offered: per-set rotations, gene or array weights, trend.var, robust, a sparse X, na = "fit"; romer is plaid_romer,
+    below."""
     from .engine import ROAST_HYPER, check_roast_options
     check_roast_options(set_statistic, zscore)
     if sort_by not in _ROAST_SORT:   # (before the device)
@@ -1313,6 +1314,101 @@ def plaid_roast_contrasts(X, Y, G, B=None, set_statistic="mean50", nrot=1999, se
     out, hyper = ctx.roast(Xs, D, Gp, Gi, lab != -1, K, set_statistic, nrot, seed, zscore, midp, rotations)
     tables = {nm: _roast_table(out[:, :, 0, j], rn, sort_by) for j, nm in enumerate(names)}
     return tables, {nm: dict(zip(ROAST_HYPER, (float(x) for x in hyper[j]))) for j, nm in enumerate(names)}
+
+
+_ROMER_NAMES = ["NGenes", "Up", "Down", "Mixed", "FDR.Up", "FDR.Down", "FDR.Mixed"]
+_ROMER_SORT = {"none": None, "up": 1, "down": 2, "mixed": 3}
+
+
+def _romer_table(tab, rn, sort_by):
+    """sets x 7 of the library -> the NamedMatrix plaid.romer returns, ordered by `sort_by`: "up", "down", "mixed" (that
+    p-value increasing) or "none"; stable, NaN last"""
+    rn = list(rn)
+    col = _ROMER_SORT[sort_by]
+    if col is not None:
+        o = np.argsort(tab[:, col], kind="stable")
+        tab, rn = tab[o, :], [rn[k] for k in o]
+    return NamedMatrix(np.ascontiguousarray(tab), rn, _ROMER_NAMES)
+
+
+def _romer_hyper(h, names):
+    from .engine import ROMER_HYPER
+    d = dict(zip(ROMER_HYPER, (float(x) for x in h[:8])))
+    d["proportion"] = {nm: float(h[8 + j]) for j, nm in enumerate(names)}
+    return d
+
+
+def plaid_romer(X, design, G, contrasts=None, use=None, set_statistic="mean", nrot=9999, seed=1, shrink_resid=True,
+                rotations=None, minSize=1, maxSize=None, sort_by="none", ctx: Context | None = None):
+    """plaid.romer(): limma's rotation GSEA (romer as pinned in include/plaidhip.h) of every set of G on the expression X for
+    one design; the operands are plaid_roast's.  It is the competitive test with a rotation null: under every rotation the
+    genes' moderated t are ranked among all genes and a set takes the sum of its members' ranks, so the null keeps the
+    gene-gene correlation.  set_statistic: "mean" (the default), "floormean" or "mean50".  shrink_resid (limma's default)
+    shrinks the observed effects by the empirical-Bayes posterior before rotating.  The rotations are drawn in sample space
+    from `seed` (plaid_roast's, shared by every set and contrast) -- or given: rotations, (samples + 1) x nrot with row 0 =
+    r0.  p = (b + 1) / (nrot + 1) from exact integer statistics.  Under "mean50" a set with more than 16,384 members in the
+    universe has NaN p-values (hyper["mean50.capped"] = 1).
+    Returns (tables, hyper): contrast name -> NamedMatrix (sets x [NGenes, Up, Down, Mixed, FDR.Up, FDR.Down, FDR.Mixed])
+    ordered by `sort_by` ("up", "down", "mixed" or "none"), and plaid_limma's four values, n.genes, nrot, mean50.capped,
+    nan.t and the proportion of non-null genes of every contrast (0 where not shrunk).
+    Not offered: array.weights, block / correlation, a sparse X, na = "fit", gene weights, trend, robust."""
+    from .engine import check_romer_options
+    check_romer_options(set_statistic)
+    if sort_by not in _ROMER_SORT:   # (before the device)
+        raise ValueError(f"plaid.romer: sort_by must be one of {sorted(_ROMER_SORT)}")
+    Xs, Gp, Gi, rn = _camera_sets("plaid.romer", X, G, minSize, maxSize)
+    Dn = design if isinstance(design, NamedMatrix) else None
+    Dv = np.asarray(Dn.values if Dn is not None else design, dtype=np.float64)
+    if Dv.ndim != 2:
+        raise ValueError("plaid.romer: design must be samples x coefficients")
+    coef = list(Dn.colnames) if Dn is not None else [f"coef{k + 1}" for k in range(Dv.shape[1])]
+    if contrasts is None:
+        Kv, names = None, coef
+    else:
+        Kn = contrasts if isinstance(contrasts, NamedMatrix) else None
+        Kv = np.asarray(Kn.values if Kn is not None else contrasts, dtype=np.float64)
+        Kv = Kv[:, None] if Kv.ndim == 1 else Kv
+        names = list(Kn.colnames) if Kn is not None else [str(j + 1) for j in range(Kv.shape[1])]
+    ctx = ctx or default_context()
+    out, hyper = ctx.romer(Xs, Dv, Gp, Gi, use, Kv, set_statistic, nrot, seed, shrink_resid, None, rotations)
+    tables = {nm: _romer_table(out[:, :, j, 0], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, _romer_hyper(hyper[0], names)
+
+
+def plaid_romer_contrasts(X, Y, G, B=None, set_statistic="mean", nrot=9999, seed=1, shrink_resid=True, rotations=None,
+                          minSize=1, maxSize=None, sort_by="none", ctx: Context | None = None):
+    """plaid.romer.contrasts(): plaid_romer for every column of the contrast matrix Y in one call, with the designs of
+    plaid_limma_contrasts: contrast j fits [1, Y[, j], B] on the samples with a label and tests the sets on the coefficient
+    of Y[, j].  X is uploaded once.  Contrast j is fit number j: its generated rotations are those of (seed, j), so its
+    table has the bits of plaid_romer on that contrast's design and samples only for j = 0 -- or for any j where
+    `rotations` ((samples + 1) x nrot x contrasts) are given.  Returns (tables, hyper) keyed by contrast name."""
+    from .engine import check_romer_options, contrast_labels
+    check_romer_options(set_statistic)
+    if sort_by not in _ROMER_SORT:
+        raise ValueError(f"plaid.romer: sort_by must be one of {sorted(_ROMER_SORT)}")
+    Xs, Gp, Gi, rn = _camera_sets("plaid.romer", X, G, minSize, maxSize)
+    n = Xs.shape[1]
+    Yn = Y if isinstance(Y, NamedMatrix) else None
+    lab = contrast_labels(Yn.values if Yn is not None else Y, n)
+    if not np.all(np.isin(lab, (0, 1, -1))):
+        raise ValueError("elements of Y must be 0, 1 or NA")
+    ncon = lab.shape[1]
+    names = list(Yn.colnames) if Yn is not None and Yn.colnames is not None else [str(j + 1) for j in range(ncon)]
+    Bv = np.zeros((n, 0)) if B is None else np.asarray(B.values if isinstance(B, NamedMatrix) else B, dtype=np.float64)
+    Bv = Bv[:, None] if Bv.ndim == 1 else Bv
+    if Bv.ndim != 2 or Bv.shape[0] != n:
+        raise ValueError("B must have one row per column of X")
+    p = 2 + Bv.shape[1]
+    D = np.empty((n, p, ncon), order="F")
+    D[:, 0, :] = 1.0
+    D[:, 1, :] = np.where(lab == 1, 1.0, 0.0)
+    D[:, 2:, :] = Bv[:, :, None]
+    K = np.zeros((p, 1))
+    K[1, 0] = 1.0
+    ctx = ctx or default_context()
+    out, hyper = ctx.romer(Xs, D, Gp, Gi, lab != -1, K, set_statistic, nrot, seed, shrink_resid, None, rotations)
+    tables = {nm: _romer_table(out[:, :, 0, j], rn, sort_by) for j, nm in enumerate(names)}
+    return tables, {nm: _romer_hyper(hyper[j], [nm]) for j, nm in enumerate(names)}
 
 
 def plaid_intergenecor(X, design, G, use=None, minSize=1, maxSize=None, ctx: Context | None = None):

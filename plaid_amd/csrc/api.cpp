@@ -11,6 +11,7 @@
 
 #include "call.h"
 #include "roast.h"
+#include "romer.h"
 
 namespace plaidhip {
 
@@ -1541,6 +1542,87 @@ int plaidhip_roast(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, con
                    double* hyper) try {
   return dispatch(on_context(ctx), roast_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic, zscore, nrot, seed,
                                               midp, rotations, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.romer: the one-device form of the sharded engine (shard_romer.cpp: romer_worker, romer_tail)
+int plaidhip_romer(plaidhip_ctx* ctx, const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit,
+                   const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                   int set_statistic, int32_t nrot, uint64_t seed, int shrink_resid, const double* shrink, const double* rotations,
+                   double* out, double* hyper) try {
+  return dispatch(on_context(ctx), romer_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic, nrot, seed,
+                                              shrink_resid, shrink, rotations, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+// the device passes of plaid.romer on device pointers (kernels_romer.hip); chunk: rotations per launch (a multiple of 64; 0: all)
+static int romer_dev_dims(const char* who, int32_t U, int64_t ldu, int set_statistic, int32_t nrot, int32_t chunk) {
+  PH_REQUIRE(U >= 0 && U <= PLAIDHIP_ROMER_MAX_GENES && ldu >= U, "%s: U = %d keys a column, ldu = %lld (U <= %d)", who, U,
+             (long long)ldu, PLAIDHIP_ROMER_MAX_GENES);
+  PH_REQUIRE(set_statistic >= 0 && set_statistic <= 2, "%s: set_statistic = %d (0 mean, 1 floormean, 2 mean50)", who, set_statistic);
+  PH_REQUIRE(nrot >= 1 && nrot <= PLAIDHIP_ROAST_MAX_ROTATIONS, "%s: nrot = %d (1 <= nrot <= %d)", who, nrot,
+             PLAIDHIP_ROAST_MAX_ROTATIONS);
+  PH_REQUIRE(chunk >= 0 && chunk % 64 == 0, "%s: chunk = %d rotations (a multiple of 64, or 0: all)", who, chunk);
+  return PLAIDHIP_OK;
+}
+
+int plaidhip_dev_romer_keys(plaidhip_ctx* ctx, const double* Z, int32_t rows, const int32_t* uidx, int32_t U, int64_t ldu,
+                            int set_statistic, int32_t nrot, int32_t chunk, double* Ka, double* Kb, double* Kc, uint32_t* flag) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(rows >= 0 && U <= rows, "romer_keys: rows = %d, U = %d", rows, U);
+  PH_TRY(romer_dev_dims("romer_keys", U, ldu, set_statistic, nrot, chunk));
+  if (U == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Z && uidx && Ka && Kc && (Kb || set_statistic != PLAIDHIP_ROMER_STAT_FLOORMEAN), "romer_keys: null argument");
+  const int32_t step = chunk == 0 ? (nrot + 63) / 64 * 64 : chunk;
+  for (int32_t k0 = 0; k0 < nrot; k0 += step) {
+    const int64_t off = (int64_t)k0 * ldu;
+    PH_TRY(launch_romer_keys(ctx, Z + (size_t)(k0 / 64) * rows * 64, rows, uidx, U, ldu, set_statistic, std::min(nrot - k0, step),
+                             Ka + off, Kb ? Kb + off : nullptr, Kc + off, flag));
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_dev_romer_sides(plaidhip_ctx* ctx, const double* Ra, const double* Rb, const double* Rc, int64_t ldu, int32_t U,
+                             const int32_t* Gp, const int32_t* Gi, int32_t m, int set_statistic, int32_t nrot, int32_t chunk,
+                             int64_t* stat, const int64_t* obs, int32_t* cnt) try {
+  PH_CTX(ctx);
+  PH_REQUIRE(m >= 0, "romer_sides: bad dims m=%d", m);
+  PH_TRY(romer_dev_dims("romer_sides", U, ldu, set_statistic, nrot, chunk));
+  PH_REQUIRE((obs == nullptr) == (cnt == nullptr), "romer_sides: obs and cnt go together");
+  if (m == 0 || U == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(Ra && Rc && (Rb || set_statistic != PLAIDHIP_ROMER_STAT_FLOORMEAN) && Gp && Gi && (stat || cnt),
+             "romer_sides: null argument");
+  const int32_t step = chunk == 0 ? nrot : chunk;
+  int32_t cls_cnt[2] = {0, 0};
+  DevBuf dsel, dS;
+  std::vector<int32_t> gp((size_t)m + 1), gi, sel;
+  plaidhip_geneset* gs = nullptr;
+  PH_HIP(hipMemcpyAsync(gp.data(), Gp, ((size_t)m + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PH_HIP(hipStreamSynchronize(ctx->stream));
+  if (set_statistic == PLAIDHIP_ROMER_STAT_MEAN50) {   // the size classes need the set sizes on the host
+    romer_mean50_classes(gp.data(), m, sel, cls_cnt);
+    PH_TRY(dsel.alloc((size_t)m * 4));
+    if (!sel.empty()) PH_HIP(hipMemcpyAsync(dsel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  } else {                                             // the rank crossprod needs the prepared collection
+    PH_REQUIRE(gp[0] == 0 && gp[(size_t)m] >= 0, "romer_sides: Gp[0] = %d, Gp[m] = %d", gp[0], gp[(size_t)m]);
+    gi.resize((size_t)gp[(size_t)m] + 1);
+    if (gp[(size_t)m] > 0) PH_HIP(hipMemcpy(gi.data(), Gi, (size_t)gp[(size_t)m] * 4, hipMemcpyDeviceToHost));
+    PH_TRY(plaidhip_geneset_create(ctx, U, m, gp.data(), gi.data(), &gs));
+    if (dS.alloc((size_t)romer_nkeys(set_statistic) * m * std::min(nrot, step) * 8) != PLAIDHIP_OK) {
+      plaidhip_geneset_destroy(gs);
+      return PLAIDHIP_ENOMEM;
+    }
+  }
+  const int saved = ctx->precision;
+  ctx->precision = PLAIDHIP_PRECISION_F64;
+  int rc = PLAIDHIP_OK;
+  for (int32_t k0 = 0; k0 < nrot && rc == PLAIDHIP_OK; k0 += step) {
+    const int64_t off = (int64_t)k0 * ldu;
+    rc = launch_romer_sides(ctx, gs, Ra + off, Rb ? Rb + off : nullptr, Rc + off, ldu, U, Gp, Gi, m, set_statistic,
+                            std::min(nrot - k0, step), k0, nrot, dsel.as<int32_t>(), cls_cnt, dS.as<double>(), stat, obs, cnt);
+  }
+  ctx->precision = saved;
+  hipStreamSynchronize(ctx->stream);   // (dsel, dS and the collection are released on return)
+  if (gs != nullptr) plaidhip_geneset_destroy(gs);
+  return rc;
 } catch (...) { return plaidhip::on_exception(); }
 
 // the device passes of plaid.roast on device pointers (kernels_roast.hip)

@@ -13,7 +13,7 @@ enum Method : int {
   kPlaid = 0, kSing = 1, kSsgsea = 2, kUcell = 3, kAucell = 4, kScse = 5, kGsva = 6, kPlaidTest = 7, kSsgseaExact = 8,
   kGsvaExact = 9, kSingExact = 10, kUcellExact = 11, kAucellExact = 12, kPlaidTestContrasts = 13, kGsea = 14, kFisher = 15,
   kLimma = 16, kRankcor = 17, kPlage = 18, kZscore = 19, kGseaMultilevel = 20, kCamera = 21, kFry = 22, kRoast = 23,
-  kVoom = 24
+  kVoom = 24, kRomer = 25
 };
 inline bool is_rank_sum(int method) { return method >= kPlaid && method <= kSsgsea; }   // shard_worker's three
 inline bool is_scorer(int method) { return method >= kUcell && method <= kGsva; }       // scorer_worker's own four
@@ -153,6 +153,10 @@ struct Call : Operands {
   int32_t nrot = 0;
   uint64_t roast_seed = 0;
   const double* rotations = nullptr;
+  // plaid.romer (kRomer): plaid.roast's operands (set_statistic 0..2 of romer.h, nrot, roast_seed, rotations); shrink_resid,
+  // the caller's factors (g x q x nfit, or null: computed where shrink_resid is set); out m x 7 x q x nfit, hyper nfit x (8 + q)
+  int shrink_resid = 1;
+  const double* shrink = nullptr;
 };
 
 // ---- one builder per scorer: its own parameters, nothing else ----------------------------------------------------------
@@ -499,6 +503,18 @@ inline Call roast_call(const double* X, int32_t g, int32_t n, const double* desi
   k.roast_seed = seed;
   k.midp = midp;
   k.rotations = rotations;
+  return k;
+}
+
+// limma's rotation GSEA on the ranks of the rotated moderated t as pinned in include/plaidhip.h: plaidhip_romer
+inline Call romer_call(const double* X, int32_t g, int32_t n, const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                       const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m, int set_statistic,
+                       int32_t nrot, uint64_t seed, int shrink_resid, const double* shrink, const double* rotations, double* out,
+                       double* hyper) {
+  Call k = roast_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic, 1, nrot, seed, 0, rotations, out, hyper);
+  k.method = kRomer;
+  k.shrink_resid = shrink_resid;
+  k.shrink = shrink;
   return k;
 }
 

@@ -449,6 +449,15 @@ int launch_roast_observed(plaidhip_ctx* ctx, const double* d_t, int32_t rows, do
 int launch_roast_stats(plaidhip_ctx* ctx, const double* Z, int32_t rows, const int32_t* d_Gp, const int32_t* d_Gi, int32_t m,
                        int set_statistic, int32_t k0, int32_t k1, int32_t nrot, const int32_t* d_sel, const int32_t* class_cnt,
                        double* d_stat, const double* d_obs, int32_t* d_cnt);
+// kernels_romer.hip (plaid.romer): the keys of one chunk of rotated t ([tile][rows][64]) over the universe's index list as
+// columns [nk][ldu]; from their average ranks the three int64 sides of every (set, rotation) and / or the counts against
+// d_obs (mean, floormean: the rank crossprod on gs into S; mean50: d_sel and class_cnt[2] from romer.h's size classes)
+int launch_romer_keys(plaidhip_ctx* ctx, const double* Z, int32_t rows, const int32_t* d_uidx, int32_t U, int64_t ldu,
+                      int set_statistic, int32_t nk, double* Ka, double* Kb, double* Kc, uint32_t* d_flag);
+int launch_romer_sides(plaidhip_ctx* ctx, const plaidhip_geneset* gs, const double* Ra, const double* Rb, const double* Rc,
+                       int64_t ldu, int32_t U, const int32_t* d_Gp, const int32_t* d_Gi, int32_t m, int set_statistic, int32_t nk,
+                       int32_t kbase, int32_t nrot, const int32_t* d_sel, const int32_t* class_cnt, double* S, int64_t* d_stat,
+                       const int64_t* d_obs, int32_t* d_cnt);
 // stats.cpp (plaid.roast): W ((n + 1) x nrot row-major) of one fit from its thin Q
 void roast_rotations(const double* Q, int32_t n, int32_t p, const int8_t* use, int32_t fit, int32_t nrot, uint64_t seed,
                      double* W);

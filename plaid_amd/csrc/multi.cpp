@@ -371,8 +371,8 @@ int check_plage_call(const Call& c) {
 // plaid.limma; the order is part of the contract (include/plaidhip.h).  Makes every fit's Q, v, u and n_f: the designs are
 // decomposed here, on the host, so that a design that cannot be fitted is refused before any device is touched
 int check_limma_call(Call& c) {
-  const char* who = c.method == kCamera ? "camera" : c.method == kFry ? "fry" : c.method == kRoast ? "roast" : "limma";
-  const bool sets = (c.method != kCamera && c.method != kFry && c.method != kRoast) || c.m != 0;   // (plaid.camera without sets writes nothing)
+  const char* who = c.method == kCamera ? "camera" : c.method == kFry ? "fry" : c.method == kRoast ? "roast" : c.method == kRomer ? "romer" : "limma";
+  const bool sets = (c.method != kCamera && c.method != kFry && c.method != kRoast && c.method != kRomer) || c.m != 0;   // (plaid.camera without sets writes nothing)
   const int32_t rows = c.g, n = c.n, p = c.ncoef, nfit = c.nfit, q = c.nq;
   PH_REQUIRE(rows >= 0 && n >= 0 && n <= PLAIDHIP_LIMMA_MAX_SAMPLES && nfit >= 0 && nfit <= PLAIDHIP_LIMMA_MAX_FITS && q >= 0,
              "%s: bad dims rows=%d n=%d nfit=%d q=%d (n <= %d, nfit <= %d)", who, rows, n, nfit, q, PLAIDHIP_LIMMA_MAX_SAMPLES,
@@ -458,7 +458,7 @@ int check_voom_call(Call& c) {
 // plaid.camera; the order is part of the contract (include/plaidhip.h): plaid.limma's checks in their order (the designs are
 // decomposed there), then the membership's as plaid.rankcor makes them, then the fixed correlation
 int check_camera_call(Call& c) {
-  const char* who = c.method == kFry ? "fry" : c.method == kRoast ? "roast" : "camera";
+  const char* who = c.method == kFry ? "fry" : c.method == kRoast ? "roast" : c.method == kRomer ? "romer" : "camera";
   PH_REQUIRE(c.m >= 0, "%s: bad dims m=%d", who, c.m);
   PH_TRY(check_limma_call(c));
   PH_REQUIRE(c.Gp != nullptr, "%s: null Gp", who);
@@ -472,7 +472,7 @@ int check_camera_call(Call& c) {
   PH_REQUIRE(c.Gi != nullptr || c.Gp[c.m] == 0, "%s: null Gi", who);
   for (int32_t e = 0; e < c.Gp[c.m]; ++e)
     PH_REQUIRE(c.Gi[e] >= 0 && c.Gi[e] < c.g, "%s: Gi[%d] = %d (rows are 0..%d)", who, e, c.Gi[e], c.g - 1);
-  if (c.method == kFry || c.method == kRoast) return PLAIDHIP_OK;
+  if (c.method == kFry || c.method == kRoast || c.method == kRomer) return PLAIDHIP_OK;
   PH_REQUIRE(std::isnan(c.inter_gene_cor) || (c.inter_gene_cor > -1.0 && c.inter_gene_cor < 1.0),
              "camera: inter_gene_cor = %g (a correlation inside (-1, 1), or NaN to estimate it)", c.inter_gene_cor);
   return PLAIDHIP_OK;
@@ -499,6 +499,22 @@ int check_roast_call(Call& c) {
   PH_REQUIRE(c.nrot >= 1, "roast: nrot = %d rotations (at least 1)", c.nrot);
   PH_REQUIRE(c.nrot <= PLAIDHIP_ROAST_MAX_ROTATIONS, "roast: nrot = %d rotations (at most %d)", c.nrot,
              PLAIDHIP_ROAST_MAX_ROTATIONS);
+  return PLAIDHIP_OK;
+}
+
+// plaid.romer; the order is part of the contract (include/plaidhip.h): plaid.roast's checks of the fit and of the membership,
+// then the set statistic and the number of rotations
+int check_romer_call(Call& c) {
+  PH_TRY(check_camera_call(c));
+  PH_REQUIRE(c.set_statistic >= 0 && c.set_statistic <= 2, "romer: set_statistic = %d (0 mean, 1 floormean, 2 mean50)",
+             c.set_statistic);
+  PH_REQUIRE(c.nrot >= 1, "romer: nrot = %d rotations (at least 1)", c.nrot);
+  PH_REQUIRE(c.nrot <= PLAIDHIP_ROAST_MAX_ROTATIONS, "romer: nrot = %d rotations (at most %d)", c.nrot,
+             PLAIDHIP_ROAST_MAX_ROTATIONS);
+  if (c.g > PLAIDHIP_ROMER_MAX_GENES) {
+    set_error("romer: %d genes (at most %d)", c.g, PLAIDHIP_ROMER_MAX_GENES);
+    return PLAIDHIP_EUNSUPPORTED;
+  }
   return PLAIDHIP_OK;
 }
 
@@ -568,6 +584,7 @@ int check_call(Call& c, int ndev, bool multi) {
     case kCamera: return check_camera_call(c);
     case kFry: return check_fry_call(c);
     case kRoast: return check_roast_call(c);
+    case kRomer: return check_romer_call(c);
     case kVoom: return check_voom_call(c);
     case kSsgseaExact:
       PH_TRY(check_ssgsea_exact_call(c, c.S_out));
@@ -957,6 +974,23 @@ int plaidhip_debug_roast_sharded_on_one_device(int device, int nshards, int fail
                                                const double* rotations, double* out, double* hyper) try {
   return dispatch(on_hook(device, nshards, fail_shard), roast_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic,
                                                                     zscore, nrot, seed, midp, rotations, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_romer_multi(const int* devices, int ndev, const double* X, int32_t g, int32_t n, const double* design, int32_t p,
+                         int32_t nfit, const int8_t* use, const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi,
+                         int32_t m, int set_statistic, int32_t nrot, uint64_t seed, int shrink_resid, const double* shrink,
+                         const double* rotations, double* out, double* hyper) try {
+  return dispatch(on_devices(devices, ndev), romer_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic, nrot, seed,
+                                                        shrink_resid, shrink, rotations, out, hyper));
+} catch (...) { return plaidhip::on_exception(); }
+
+int plaidhip_debug_romer_sharded_on_one_device(int device, int nshards, int fail_shard, const double* X, int32_t g, int32_t n,
+                                               const double* design, int32_t p, int32_t nfit, const int8_t* use,
+                                               const double* K, int32_t q, const int32_t* Gp, const int32_t* Gi, int32_t m,
+                                               int set_statistic, int32_t nrot, uint64_t seed, int shrink_resid,
+                                               const double* shrink, const double* rotations, double* out, double* hyper) try {
+  return dispatch(on_hook(device, nshards, fail_shard), romer_call(X, g, n, design, p, nfit, use, K, q, Gp, Gi, m, set_statistic,
+                                                                    nrot, seed, shrink_resid, shrink, rotations, out, hyper));
 } catch (...) { return plaidhip::on_exception(); }
 
 int plaidhip_debug_fisher_sharded_on_one_device(int device, int nshards, int fail_shard, const int8_t* sig, int32_t g, int32_t c,

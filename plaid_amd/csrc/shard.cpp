@@ -392,6 +392,7 @@ Route route(const Call& c) {
     case kCamera: return {true, limma_empty, limma_prepare, limma_worker, camera_tail};
     case kFry: return {true, limma_empty, limma_prepare, limma_worker, fry_tail};
     case kRoast: return {false, limma_empty, roast_prepare, roast_worker, roast_tail};
+    case kRomer: return {false, limma_empty, romer_prepare, romer_worker, romer_tail};
     case kVoom: return {true, voom_empty, voom_prepare, voom_worker, nullptr};
   }
   return {false, no_scores, nullptr, nullptr, nullptr};   // (no method at all: check_call has refused it)

@@ -123,6 +123,12 @@ struct Shared {
     std::vector<int32_t> cnt;
     std::vector<double> msize, ndown, nup, hyper;
   } roast;
+  // plaid.romer (roast.W takes the generated rotations): the counts added over the shards ([nfit q][m][3]), and from shard 0
+  // the set sizes and the hyperparameters ([nfit][8 + q])
+  struct Romer {
+    std::vector<int32_t> cnt;
+    std::vector<double> msize, hyper;
+  } romer;
   // plaid.gsea: the block partials [nblk][c][6][m] of all permutation blocks, each shard writing its own blocks; multilevel:
   // (qhat, log2err, stage, status) of every (list, set), NaN without a ruler, each shard writing the sets of its own rulers
   struct Gsea { std::vector<double> part, ml; } gsea;
@@ -259,6 +265,9 @@ int fry_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 int roast_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);
 void roast_prepare(Shared& sh, const Call& c, int ndev);
 int roast_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
+int romer_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh);              // shard_romer.cpp
+void romer_prepare(Shared& sh, const Call& c, int ndev);
+int romer_tail(plaidhip_ctx* first, const Call& c, Shared& sh);
 
 // ---- what the engine knows about a method on the run side (shard.cpp) --------------------------------------------------------
 struct Route {

@@ -310,7 +310,7 @@ int limma_worker(plaidhip_ctx* ctx, const Call& c, int ndev, int k, Shared& sh) 
 }
 
 bool limma_empty(const Call& c) {
-  return c.g == 0 || c.nfit == 0 || c.nq == 0 || ((c.method == kCamera || c.method == kFry || c.method == kRoast) && c.m == 0);
+  return c.g == 0 || c.nfit == 0 || c.nq == 0 || ((c.method == kCamera || c.method == kFry || c.method == kRoast || c.method == kRomer) && c.m == 0);
 }
 
 void limma_prepare(Shared& sh, const Call& c, int ndev) {

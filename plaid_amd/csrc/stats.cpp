@@ -10,6 +10,7 @@
 #include <limits>
 #include <numeric>
 #include <thread>
+#include <functional>
 #include <vector>
 
 #include "camera.h"
@@ -18,6 +19,7 @@
 #include "lmfit_na.h"
 #include "lowess.h"
 #include "roast.h"
+#include "romer.h"
 
 namespace plaidhip {
 
@@ -1105,6 +1107,127 @@ int plaidhip_roast_finish(int32_t m, int32_t nfit, int32_t q, int32_t nrot, int 
           o[(size_t)(c + 1) * M + s] = pv != pv ? nan : fm[s] > pv ? fm[s] : pv;
         }
       }
+    }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// 2 P(T_nu > |t|), with the normal limit for nu infinite or > 10^6 (plaid.romer's shrink)
+static double romer_two_sided(double t, double nu) {
+  return nu > 1e6 ? 2.0 * plaidhip::pnorm_upper(std::fabs(t)) : plaidhip::t_two_sided_p(t, nu);
+}
+
+// the q >= 0 with 2 P(T_nu > q) = p for 0 < p < 1: the normal quantile in the limit, else a bisection on the t tail (the
+// bracket is doubled up from 1; it ends when the midpoint is one of the ends)
+static double romer_upper_quantile(double p, double nu) {
+  if (nu > 1e6) return -plaidhip::qnorm_lower(0.5 * p);
+  double lo = 0.0, hi = 1.0;
+  while (plaidhip::t_two_sided_p(hi, nu) > p && hi < 1e300) {
+    lo = hi;
+    hi *= 2.0;
+  }
+  for (int it = 0; it < 200; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid == lo || mid == hi) break;
+    if (plaidhip::t_two_sided_p(mid, nu) > p) lo = mid;
+    else hi = mid;
+  }
+  return 0.5 * (lo + hi);
+}
+
+// plaid.romer's shrink (include/plaidhip.h: plaidhip_romer, "Shrink"): c_g of the U genes of one (fit, contrast) from their
+// moderated t, u = stdev.unscaled, the prior variance s0^2 and nu = df0 + d (may be infinite); *prop takes pi
+int plaidhip_romer_shrink(int32_t U, const double* t, double u, double s02, double nu, double* c, double* prop) try {
+  using namespace plaidhip;
+  PH_REQUIRE(U >= 0, "romer_shrink: U = %d", U);
+  PH_REQUIRE(u > 0.0 && std::isfinite(u), "romer_shrink: stdev.unscaled = %g", u);
+  PH_REQUIRE(nu > 0.0, "romer_shrink: df.total = %g", nu);
+  PH_REQUIRE(prop != nullptr, "romer_shrink: null prop");
+  *prop = 0.0;
+  if (U == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(t && c, "romer_shrink: null argument");
+  const size_t n = (size_t)U;
+  const double Ud = (double)U, u2 = u * u;
+  std::vector<double> tv(t, t + n);
+  for (size_t i = 0; i < n; ++i)
+    if (std::isnan(tv[i])) tv[i] = 0.0;   // (0 / 0: keyed as 0.0 on the device too)
+  t = tv.data();
+  // propTrueNull, "lfdr"
+  std::vector<double> p(n);
+  for (size_t i = 0; i < n; ++i) p[i] = romer_two_sided(t[i], nu);
+  std::sort(p.begin(), p.end(), std::greater<double>());
+  double acc = 0.0;
+  for (size_t j = 0; j < n; ++j) {
+    const double i = Ud - (double)j;
+    acc += i * std::min(Ud / i * p[j], 1.0);
+  }
+  const double pi = 1.0 - 2.0 * acc / (Ud * (Ud + 1.0));
+  *prop = pi;
+  if (!(pi > 0.0)) {
+    for (size_t i = 0; i < n; ++i) c[i] = 1.0;
+    return PLAIDHIP_OK;
+  }
+  // tmixture.vector
+  const double ntarget = std::ceil(0.5 * pi * Ud);
+  const size_t nt = (size_t)std::min(std::max(ntarget, 1.0), Ud);
+  const double P = std::max((double)nt / Ud, pi);
+  std::vector<double> at(n);
+  for (size_t i = 0; i < n; ++i) at[i] = std::fabs(t[i]);
+  std::partial_sort(at.begin(), at.begin() + (ptrdiff_t)nt, at.end(), std::greater<double>());
+  const double vlo = 0.01 / s02, vhi = 16.0 / s02;
+  double vsum = 0.0;
+  for (size_t r = 0; r < nt; ++r) {
+    const double p0 = romer_two_sided(at[r], nu);
+    const double pt = (((double)r + 0.5) / Ud - (1.0 - P) * p0) / P;
+    double v = 0.0;
+    if (pt > p0) {
+      const double qr = romer_upper_quantile(pt, nu), ratio = at[r] / qr;
+      v = u2 * (ratio * ratio - 1.0);
+    }
+    vsum += std::min(std::max(v, vlo), vhi);
+  }
+  const double v0 = vsum / (double)nt;
+  // ProbDE from the log-odds, then the factor
+  const double r = (u2 + v0) / u2;
+  const double prior = std::log(pi / (1.0 - pi)) - 0.5 * std::log(r);
+  for (size_t i = 0; i < n; ++i) {
+    double pde = 1.0;
+    if (pi < 1.0) {
+      const double t2 = t[i] * t[i];
+      const double kern = nu > 1e6 ? 0.5 * t2 * (1.0 - 1.0 / r) : 0.5 * (1.0 + nu) * std::log((t2 + nu) / (t2 / r + nu));
+      pde = 1.0 / (1.0 + std::exp(-(prior + kern)));
+      if (std::isnan(pde)) pde = 1.0;
+    }
+    c[i] = std::sqrt(u2 / (u2 + v0 * pde));
+  }
+  return PLAIDHIP_OK;
+} catch (...) { return plaidhip::on_exception(); }
+
+// plaid.romer's tables (include/plaidhip.h: plaidhip_romer, "Counts and tables") from the exact counts: cnt int32
+// [nfit q][m][3] (Up, Down, Mixed), msize m x nfit
+int plaidhip_romer_finish(int32_t m, int32_t nfit, int32_t q, int32_t nrot, int set_statistic, const int32_t* cnt,
+                          const double* msize, double* out) try {
+  using namespace plaidhip;
+  PH_REQUIRE(m >= 0 && nfit >= 0 && q >= 0, "romer_finish: bad dims m=%d nfit=%d q=%d", m, nfit, q);
+  PH_REQUIRE(set_statistic >= 0 && set_statistic <= 2, "romer_finish: set_statistic = %d (0 mean, 1 floormean, 2 mean50)",
+             set_statistic);
+  PH_REQUIRE(nrot >= 1, "romer_finish: nrot = %d (at least 1)", nrot);
+  if (m == 0 || nfit == 0 || q == 0) return PLAIDHIP_OK;
+  PH_REQUIRE(cnt && msize && out, "romer_finish: null argument");
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const size_t M = (size_t)m;
+  const double den = (double)nrot + 1.0;
+  for (int32_t f = 0; f < nfit; ++f)
+    for (int32_t j = 0; j < q; ++j) {
+      const size_t col = (size_t)f * q + j;
+      double* o = out + col * 7 * M;
+      const int32_t* b = cnt + col * 3 * M;
+      for (size_t s = 0; s < M; ++s) {
+        const double mm = msize[M * f + s];
+        const bool has = mm >= 1.0 && !(set_statistic == PLAIDHIP_ROMER_STAT_MEAN50 && mm > (double)PLAIDHIP_ROAST_MEAN50_MAX);
+        o[s] = mm;
+        for (int e = 0; e < 3; ++e) o[(size_t)(1 + e) * M + s] = has ? ((double)b[3 * s + e] + 1.0) / den : nan;
+      }
+      for (int e = 0; e < 3; ++e) p_adjust_fdr(o + (size_t)(1 + e) * M, m, o + (size_t)(4 + e) * M);
     }
   return PLAIDHIP_OK;
 } catch (...) { return plaidhip::on_exception(); }

@@ -1035,6 +1035,81 @@ def roast_finish(cnt, msize, ndown, nup, nrot, set_statistic="mean50", midp=True
     return out
 
 
+ROMER_COLUMNS = ("NGenes", "Up", "Down", "Mixed", "FDR.Up", "FDR.Down", "FDR.Mixed")
+ROMER_HYPER = LIMMA_HYPER + ("n.genes", "nrot", "mean50.capped", "nan.t")   # then pi of every contrast
+ROMER_STATISTIC = {"mean": 0, "floormean": 1, "mean50": 2}
+ROMER_MAX_GENES = 131072
+
+
+def check_romer_options(set_statistic):
+    """set_statistic as the C ABI takes it"""
+    if set_statistic not in ROMER_STATISTIC:
+        raise ValueError(f"romer: set_statistic must be one of {sorted(ROMER_STATISTIC)}")
+    return ROMER_STATISTIC[set_statistic]
+
+
+def _romer(fn, head, X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean", nrot=9999, seed=1, shrink_resid=True,
+           shrink=None, rotations=None, out=None, hyper=None):
+    """plaidhip_romer / _multi / the hook: (out, hyper) -- sets x 7 x q x nfit (ROMER_COLUMNS) and nfit x (8 + q) (ROMER_HYPER,
+    then pi of every contrast).  rotations: None (generated from `seed`) or (n + 1) x nrot (x nfit), row 0 = r0; shrink: None
+    or the factors, genes x q (x nfit)"""
+    X = _as_f64_fortran(X)
+    if X.ndim != 2:
+        raise ValueError("romer: the matrix must be genes x samples")
+    g, n = X.shape
+    D, U, K, q = limma_operands(n, design, use, contrasts)
+    p, nfit = D.shape[1], D.shape[2]
+    Gp, Gi = _as_i32(Gp), _as_i32(Gi)
+    m = len(Gp) - 1
+    stat = check_romer_options(set_statistic)
+    Wr = None
+    if rotations is not None:
+        Wr = np.asarray(rotations, dtype=np.float64)
+        Wr = Wr[:, :, None] if Wr.ndim == 2 else Wr
+        if Wr.ndim != 3 or Wr.shape[0] != n + 1 or Wr.shape[2] != nfit:
+            raise ValueError("romer: rotations must be (samples + 1) x nrot (x fits)")
+        nrot = Wr.shape[1]
+        Wr = np.ascontiguousarray(Wr.transpose(2, 0, 1))   # [fit][n + 1][nrot]
+    Sh = None
+    if shrink is not None:
+        Sh = np.asarray(shrink, dtype=np.float64)
+        Sh = Sh[:, None] if Sh.ndim == 1 else Sh
+        Sh = Sh[:, :, None] if Sh.ndim == 2 else Sh
+        if Sh.shape != (g, q, nfit):
+            raise ValueError("romer: shrink must be genes x contrasts (x fits)")
+        Sh = np.asfortranarray(Sh)
+    out = np.full((m, 7, q, nfit), np.nan, dtype=np.float64, order="F") if out is None else out
+    hyper = np.full((nfit, 8 + q), np.nan, dtype=np.float64) if hyper is None else hyper
+    check(fn(*head, _np_ptr(X), g, n, _np_ptr(D), p, nfit, None if U is None else _np_ptr(U), None if K is None else _np_ptr(K),
+             q, _np_ptr(Gp), _np_ptr(Gi), m, stat, int(nrot), int(seed), int(bool(shrink_resid)), None if Sh is None else _np_ptr(Sh),
+             None if Wr is None else _np_ptr(Wr), _np_ptr(out), _np_ptr(hyper)))
+    return out, hyper
+
+
+def romer_shrink(t, u, s02, nu):
+    """plaidhip_romer_shrink on the host (no device is touched): (c, pi) -- the factors of the genes with moderated t `t` of
+    one (fit, contrast) with stdev.unscaled u, prior variance s02 and nu = df.prior + df.residual (may be inf)"""
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    c = np.full(t.shape, np.nan)
+    prop = np.full(1, np.nan)
+    check(_lib.load().plaidhip_romer_shrink(len(t), _np_ptr(t), float(u), float(s02), float(nu), _np_ptr(c), _np_ptr(prop)))
+    return c, float(prop[0])
+
+
+def romer_finish(cnt, msize, nrot, set_statistic="mean"):
+    """plaidhip_romer_finish on the host: cnt sets x 3 (x q x nfit) integer counts (Up, Down, Mixed), msize sets (x nfit) ->
+    out sets x 7 x q x nfit"""
+    cnt = np.asarray(cnt)
+    cnt = cnt[:, :, None, None] if cnt.ndim == 2 else cnt
+    m, _, q, nfit = cnt.shape
+    cn = np.ascontiguousarray(cnt.transpose(3, 2, 0, 1), dtype=np.int32)   # [fit][contrast][set][3]
+    ms = np.asfortranarray(np.asarray(msize, dtype=np.float64).reshape((m, nfit), order="F"))
+    out = np.full((m, 7, q, nfit), -7.0, order="F")
+    check(_lib.load().plaidhip_romer_finish(m, nfit, q, int(nrot), ROMER_STATISTIC[set_statistic], _np_ptr(cn), _np_ptr(ms),
+                                            _np_ptr(out)))
+    return out
+
+
 class Context:
     """plaidhip_ctx: one device + one stream.  `stream` is a raw hipStream_t value (e.g.
     `torch.cuda.current_stream().cuda_stream`; 0 is the device's null stream, which is what torch's default
@@ -1520,6 +1595,25 @@ class Context:
         return _roast(self.lib.plaidhip_roast, (self.handle,), X, design, Gp, Gi, use, contrasts, set_statistic, nrot, seed,
                       zscore, midp, rotations)
 
+    def romer(self, X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean", nrot=9999, seed=1, shrink_resid=True,
+              shrink=None, rotations=None):
+        """plaidhip_romer: limma's rotation GSEA on the ranks of the rotated moderated t of the sets (Gp, Gi, aligned to the rows
+        of X), as Context.roast takes its operands.  Returns (out, hyper): sets x 7 x q x nfit (ROMER_COLUMNS), nfit x (8 + q)."""
+        return _romer(self.lib.plaidhip_romer, (self.handle,), X, design, Gp, Gi, use, contrasts, set_statistic, nrot, seed,
+                      shrink_resid, shrink, rotations)
+
+    def dev_romer_keys(self, Z: int, rows: int, uidx: int, U: int, ldu: int, set_statistic: int, nrot: int, chunk: int, Ka: int,
+                       Kb, Kc: int, flag):
+        """plaidhip_dev_romer_keys on device pointers: the keys of the universe's rotated t as columns [rotation][ldu]"""
+        check(self.lib.plaidhip_dev_romer_keys(self.handle, Z, rows, uidx, U, ldu, set_statistic, nrot, chunk, Ka, Kb, Kc, flag))
+
+    def dev_romer_sides(self, Ra: int, Rb, Rc: int, ldu: int, U: int, Gp: int, Gi: int, m: int, set_statistic: int, nrot: int,
+                        chunk: int, stat, obs, cnt):
+        """plaidhip_dev_romer_sides on device pointers, from the average ranks (doubles) of the key matrices: the three int64
+        sides (m x nrot x 3) and / or the counts against obs"""
+        check(self.lib.plaidhip_dev_romer_sides(self.handle, Ra, Rb, Rc, ldu, U, Gp, Gi, m, set_statistic, nrot, chunk, stat, obs,
+                                                cnt))
+
     def dev_roast_rotate(self, Rz: int, ldz: int, rows: int, n: int, beta: int, rss: int, W: int, ldw: int, nrot: int, d: float,
                          df0: float, s02: float, zscore: int, chunk: int, Z: int):
         """plaidhip_dev_roast_rotate on device pointers: z of every (gene, rotation) as [tile of 64][rows][64]"""
@@ -1807,6 +1901,13 @@ def roast_multi(X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean
                 rotations=None, devices=1):
     """plaid.roast (Context.roast) with the fit's sample columns sharded over `devices`: the one-device bits"""
     return _roast(*_multi("roast", devices), X, design, Gp, Gi, use, contrasts, set_statistic, nrot, seed, zscore, midp,
+                  rotations)
+
+
+def romer_multi(X, design, Gp, Gi, use=None, contrasts=None, set_statistic="mean", nrot=9999, seed=1, shrink_resid=True,
+                shrink=None, rotations=None, devices=1):
+    """plaid.romer (Context.romer) with the rotation tiles dealt to `devices`: the one-device bits"""
+    return _romer(*_multi("romer", devices), X, design, Gp, Gi, use, contrasts, set_statistic, nrot, seed, shrink_resid, shrink,
                   rotations)
 
 

@@ -1078,7 +1078,8 @@ plaid.fry.contrasts <- function(X, Y, G, B = NULL, standardize = "posterior.sd",
 ## Returns list(tables = <named list, one data frame per contrast: sets x (NGenes, PropDown, PropUp, Direction, PValue, FDR,
 ## PValue.Mixed, FDR.Mixed), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok, n.genes, nrot,
 ## mean50.capped)).
-## Not offered: per-set rotations, romer, gene or array weights, trend.var, robust, a sparse X, na = "fit", the exact z-score.
+## Not offered: per-set rotations, gene or array weights, trend.var, robust, a sparse X, na = "fit", the exact z-score; romer is
+## plaid.romer(), below.
 plaid.roast <- function(X, design, G, contrasts = NULL, use = NULL, set.statistic = "mean50", nrot = 1999, seed = 1,
                         zscore = "hill", midp = TRUE, rotations = NULL, minSize = 1, maxSize = NULL, sort.by = "directional") {
   cs <- .camera_sets(X, G, minSize, maxSize)
@@ -1123,6 +1124,99 @@ plaid.roast.contrasts <- function(X, Y, G, B = NULL, set.statistic = "mean50", n
   r <- .roast_call(cs, D, ncol(Y), use, K, set.statistic, nrot, seed, zscore, midp, rotations, ncol(Y), sort.by)
   tables <- r$tables
   hyper <- lapply(seq_len(ncol(Y)), function(j) .roast_hyper(r$hyper[, j]))
+  names(tables) <- names(hyper) <- cn
+  list(tables = tables, hyper = hyper)
+}
+
+
+.romer_statistics <- c("mean", "floormean", "mean50")
+.romer_sorts <- c("none", "up", "down", "mixed")
+
+.romer_table <- function(tab, rn, sort.by) {
+  tab <- matrix(tab, nrow = length(rn), ncol = 7L)
+  res <- data.frame(NGenes = tab[, 1], Up = tab[, 2], Down = tab[, 3], Mixed = tab[, 4], FDR.Up = tab[, 5], FDR.Down = tab[, 6],
+                    FDR.Mixed = tab[, 7], row.names = rn, stringsAsFactors = FALSE)
+  key <- switch(sort.by, none = NULL, up = res$Up, down = res$Down, mixed = res$Mixed)
+  if (!is.null(key)) res <- res[order(key), , drop = FALSE]
+  res
+}
+
+.romer_hyper <- function(h, cn) {
+  c(stats::setNames(as.list(h[1:8]), c("df.residual", "df.prior", "s2.prior", "n.ok", "n.genes", "nrot", "mean50.capped", "nan.t")),
+    list(proportion = stats::setNames(h[-(1:8)], cn)))
+}
+
+.romer_call <- function(cs, D, nfit, use, K, set.statistic, nrot, seed, shrink.resid, rotations, ncon, sort.by) {
+  if (length(set.statistic) != 1L || !set.statistic %in% .romer_statistics)
+    stop("plaid.romer: set.statistic must be one of ", paste(.romer_statistics, collapse = ", "))
+  if (length(sort.by) != 1L || !sort.by %in% .romer_sorts) stop("plaid.romer: sort.by must be one of ", paste(.romer_sorts, collapse = ", "))
+  rot <- .roast_rotations(rotations, ncol(cs$X), nfit)
+  if (!is.null(rot)) nrot <- dim(rot)[1]
+  opts <- c(match(set.statistic, .romer_statistics) - 1L, as.integer(nrot), as.integer(isTRUE(shrink.resid)))
+  .session()
+  r <- .Call("R_plaidhip_romer", .devices(), cs$X, D, nfit, use, K, cs$Gp, cs$Gi, opts, as.double(seed), rot, PACKAGE = "plaidhip")
+  out <- r[[1]]
+  dim(out) <- c(length(cs$names), 7L, ncon)
+  list(tables = lapply(seq_len(ncon), function(j) .romer_table(out[, , j], cs$names, sort.by)), hyper = r[[2]])
+}
+
+
+## plaid.romer(): limma's rotation GSEA (romer as pinned in include/plaidhip.h: plaidhip_romer) of every set of G on the
+## expression X (genes x samples) for one design.  The operands are plaid.roast()'s.  It is the COMPETITIVE test with a rotation
+## null: under every rotation the genes' moderated t are ranked among all genes and a set takes the sum of its members' ranks, so
+## the null keeps the gene-gene correlation.  set.statistic: "mean" (the default), "floormean" or "mean50".  shrink.resid
+## (limma's default) shrinks the observed effects by the empirical-Bayes posterior before rotating.  The rotations are
+## plaid.roast()'s, drawn in sample space from `seed` and shared by every set and contrast, or given: rotations, (samples + 1)
+## x nrot with row 1 = r0.  p = (b + 1) / (nrot + 1) from exact integer statistics.  Under "mean50" a set with more than 16,384
+## members in the universe has NA p-values (hyper$mean50.capped = 1).
+## Returns list(tables = <named list, one data frame per contrast: sets x (NGenes, Up, Down, Mixed, FDR.Up, FDR.Down,
+## FDR.Mixed), ordered by sort.by>, hyper = list(df.residual, df.prior, s2.prior, n.ok, n.genes, nrot, mean50.capped, nan.t,
+## proportion)).
+## Not offered: array.weights, block / correlation, a sparse X, na = "fit", gene weights, trend, robust.
+plaid.romer <- function(X, design, G, contrasts = NULL, use = NULL, set.statistic = "mean", nrot = 9999, seed = 1,
+                        shrink.resid = TRUE, rotations = NULL, minSize = 1, maxSize = NULL, sort.by = "none") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  design <- as.matrix(design); storage.mode(design) <- "double"
+  if (nrow(design) != ncol(cs$X)) stop("design must have one row per column of X")
+  cn <- if (is.null(colnames(design))) paste0("coef", seq_len(ncol(design))) else colnames(design)
+  if (!is.null(contrasts)) {
+    contrasts <- as.matrix(contrasts); storage.mode(contrasts) <- "double"
+    if (nrow(contrasts) != ncol(design)) stop("contrasts must have one row per coefficient")
+    cn <- if (is.null(colnames(contrasts))) as.character(seq_len(ncol(contrasts))) else colnames(contrasts)
+  }
+  if (!is.null(use)) {
+    if (length(use) != ncol(cs$X)) stop("use must have one entry per column of X")
+    use <- matrix(as.integer(!is.na(use) & use != 0), ncol = 1)
+  }
+  r <- .romer_call(cs, design, 1L, use, contrasts, set.statistic, nrot, seed, shrink.resid, rotations, length(cn), sort.by)
+  tables <- r$tables
+  names(tables) <- cn
+  list(tables = tables, hyper = .romer_hyper(r$hyper[, 1], cn))
+}
+
+
+## plaid.romer.contrasts(): plaid.romer() for every column of a contrast matrix Y (samples x contrasts; 0, 1, NA = the sample
+## takes no part) in ONE call, with the designs of plaid.limma.contrasts().  X is uploaded once.  Contrast j is fit number j:
+## its generated rotations are those of (seed, j - 1).
+plaid.romer.contrasts <- function(X, Y, G, B = NULL, set.statistic = "mean", nrot = 9999, seed = 1, shrink.resid = TRUE,
+                                  rotations = NULL, minSize = 1, maxSize = NULL, sort.by = "none") {
+  cs <- .camera_sets(X, G, minSize, maxSize)
+  Y <- as.matrix(Y)
+  if (nrow(Y) != ncol(cs$X)) stop("Y must have one row per column of X")
+  if (!all(unique(as.vector(Y)) %in% c(0, 1, NA))) stop("elements of Y must be 0, 1 or NA")
+  if (!is.null(B)) {
+    B <- as.matrix(B); storage.mode(B) <- "double"
+    if (nrow(B) != ncol(cs$X)) stop("B must have one row per column of X")
+  }
+  D <- do.call(cbind, lapply(seq_len(ncol(Y)), function(j) cbind(1, ifelse(is.na(Y[, j]), 0, Y[, j]), B)))
+  storage.mode(D) <- "double"
+  p <- 2L + (if (is.null(B)) 0L else ncol(B))
+  K <- matrix(0, p, 1); K[2, 1] <- 1
+  use <- matrix(as.integer(!is.na(Y)), nrow(Y), ncol(Y))
+  cn <- if (is.null(colnames(Y))) as.character(seq_len(ncol(Y))) else colnames(Y)
+  r <- .romer_call(cs, D, ncol(Y), use, K, set.statistic, nrot, seed, shrink.resid, rotations, ncol(Y), sort.by)
+  tables <- r$tables
+  hyper <- lapply(seq_len(ncol(Y)), function(j) .romer_hyper(r$hyper[, j], cn[j]))
   names(tables) <- names(hyper) <- cn
   list(tables = tables, hyper = hyper)
 }

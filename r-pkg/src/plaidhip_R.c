@@ -853,6 +853,56 @@ SEXP R_plaidhip_roast(SEXP devices, SEXP X, SEXP design, SEXP nfit_, SEXP use, S
   return res;
 }
 
+/* plaid.romer(): list(out, hyper) of plaidhip_romer -- out an m x (7 q nfit) matrix (the caller gives it dim m x 7 x q x nfit:
+ * NGenes, Up, Down, Mixed, FDR.Up, FDR.Down, FDR.Mixed), hyper (8 + q) x nfit (plaid.limma's four, n.genes, nrot, mean50.capped,
+ * nan.t, then pi of every contrast down a column).  X, design, use, K, Gp, Gi: as R_plaidhip_roast; opts: integer (set statistic
+ * 0..2, nrot, shrink.resid); seed: a whole number below 2^53; rotations: NULL (generated) or nrot x (n + 1) x nfit doubles, i.e.
+ * every fit's (n + 1) x nrot matrix row by row */
+SEXP R_plaidhip_romer(SEXP devices, SEXP X, SEXP design, SEXP nfit_, SEXP use, SEXP K, SEXP Gp, SEXP Gi, SEXP opts, SEXP seed_,
+                      SEXP rotations) {
+  const int g = Rf_nrows(X), n = Rf_ncols(X), nfit = Rf_asInteger(nfit_), m = LENGTH(Gp) - 1;
+  if (nfit < 1 || Rf_nrows(design) != n || Rf_ncols(design) % nfit != 0)
+    Rf_error("plaid.romer: design must have one row per sample and the same number of columns for every fit");
+  if (m < 0) Rf_error("plaid.romer: an empty column pointer");
+  if (LENGTH(opts) != 3) Rf_error("plaid.romer: opts must be (set statistic, nrot, shrink.resid)");
+  const int p = Rf_ncols(design) / nfit;
+  const int q = Rf_isNull(K) ? p : Rf_ncols(K);
+  if (!Rf_isNull(K) && Rf_nrows(K) != p) Rf_error("plaid.romer: contrasts must have one row per coefficient");
+  int8_t* u8 = NULL;
+  if (!Rf_isNull(use)) {
+    if (Rf_nrows(use) != n || Rf_ncols(use) != nfit) Rf_error("plaid.romer: use must be samples x fits");
+    const size_t count = (size_t)n * (size_t)nfit;
+    const int* u = INTEGER(use);
+    u8 = (int8_t*)R_alloc(count > 0 ? count : 1, 1);
+    for (size_t e = 0; e < count; ++e) u8[e] = (int8_t)(u[e] != 0 && u[e] != NA_INTEGER);
+  }
+  const int stat = INTEGER(opts)[0], nrot = INTEGER(opts)[1], shrink = INTEGER(opts)[2];
+  const double seed = Rf_asReal(seed_);
+  if (!(seed >= 0.0 && seed < 9007199254740992.0)) Rf_error("plaid.romer: seed must be a whole number in [0, 2^53)");
+  const double* rot = NULL;
+  if (!Rf_isNull(rotations)) {
+    if (nrot < 1 || (double)XLENGTH(rotations) != (double)nrot * ((double)n + 1.0) * (double)nfit)
+      Rf_error("plaid.romer: rotations must be (samples + 1) x nrot for every fit");
+    rot = REAL(rotations);
+  }
+  SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, m, 7 * q * nfit));
+  SEXP hyper = PROTECT(Rf_allocMatrix(REALSXP, 8 + q, nfit));
+  SET_VECTOR_ELT(res, 0, out);
+  SET_VECTOR_ELT(res, 1, hyper);
+  const double* Kp = Rf_isNull(K) ? NULL : REAL(K);
+  int rc;
+  if (LENGTH(devices) > 1)
+    rc = plaidhip_romer_multi(INTEGER(devices), LENGTH(devices), REAL(X), g, n, REAL(design), p, nfit, u8, Kp, q, INTEGER(Gp),
+                              INTEGER(Gi), m, stat, nrot, (uint64_t)seed, shrink, NULL, rot, REAL(out), REAL(hyper));
+  else
+    rc = plaidhip_romer(ctx(), REAL(X), g, n, REAL(design), p, nfit, u8, Kp, q, INTEGER(Gp), INTEGER(Gi), m, stat, nrot,
+                        (uint64_t)seed, shrink, NULL, rot, REAL(out), REAL(hyper));
+  if (rc != PLAIDHIP_OK) Rf_error("%s", plaidhip_last_error_string());
+  UNPROTECT(3);
+  return res;
+}
+
 /* plaid.limma(na = "fit"): list(out, hyper, dfres) of plaidhip_limma_na -- R_plaidhip_limma's operands and max_na; hyper 5 x
  * nfit (df.pooled last), dfres rows x nfit (the df.residual of every fitted row, NaN for the others) */
 SEXP R_plaidhip_limma_na(SEXP devices, SEXP A, SEXP design, SEXP nfit_, SEXP use, SEXP K, SEXP max_na_) {
@@ -1093,6 +1143,7 @@ static const R_CallMethodDef call_methods[] = {
     {"R_plaidhip_camera", (DL_FUNC)&R_plaidhip_camera, 10},
     {"R_plaidhip_fry", (DL_FUNC)&R_plaidhip_fry, 9},
     {"R_plaidhip_roast", (DL_FUNC)&R_plaidhip_roast, 11},
+    {"R_plaidhip_romer", (DL_FUNC)&R_plaidhip_romer, 11},
     {"R_plaidhip_rankcor", (DL_FUNC)&R_plaidhip_rankcor, 6},
     {"R_plaidhip_plage", (DL_FUNC)&R_plaidhip_plage, 11},
     {"R_plaidhip_zscore", (DL_FUNC)&R_plaidhip_zscore, 8},

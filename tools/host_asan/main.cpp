@@ -328,6 +328,51 @@ static void camera() {
   printf("  camera: the residual row at 1, 4 and 32 coefficients, the finish step over universes of 0 .. 400 genes, refused operands\n");
 }
 
+// plaid.romer's host half: the shrink over universes of 0 .. 400 genes (no non-null gene, a few, all; t with NaN and +-Inf;
+// finite and infinite df), and the tables from counts (empty sets, a set above the mean50 cap)
+static void romer() {
+  std::mt19937_64 rng(29);
+  std::normal_distribution<double> N(0.0, 1.0);
+  for (int U : {0, 1, 2, 3, 60, 400})
+    for (int kind = 0; kind < 4; ++kind) {
+      std::vector<double> t((size_t)U), c((size_t)U, -7.0);
+      for (int i = 0; i < U; ++i) t[(size_t)i] = N(rng) * (kind == 0 ? 0.2 : 1.0) + (kind >= 2 && i % (kind == 3 ? 1 : 4) == 0 ? 6.0 : 0.0);
+      if (U >= 3 && kind == 1) { t[0] = NAN; t[1] = INFINITY; t[2] = -INFINITY; }
+      double prop = -7.0;
+      const double nu = kind == 1 ? INFINITY : 9.5;
+      REQUIRE(plaidhip_romer_shrink(U, t.data(), 0.5, 1.25, nu, c.data(), &prop) == PLAIDHIP_OK);
+      REQUIRE(prop >= 0.0 || U > 0);
+      for (int i = 0; i < U; ++i) REQUIRE(c[(size_t)i] > 0.0 && c[(size_t)i] <= 1.0);
+    }
+  double prop = 0.0, one = 1.0;
+  REQUIRE(plaidhip_romer_shrink(1, &one, 0.0, 1.0, 5.0, &one, &prop) == PLAIDHIP_EINVAL);
+  REQUIRE(plaidhip_romer_shrink(1, nullptr, 1.0, 1.0, 5.0, &one, &prop) == PLAIDHIP_EINVAL);
+  for (int m : {0, 1, 7, 300}) {
+    const int nfit = 2, q = 2, nrot = 99;
+    std::vector<int32_t> cnt((size_t)3 * m * q * nfit);
+    std::vector<double> msize((size_t)m * nfit), out((size_t)m * 7 * q * nfit, -7.0);
+    for (auto& v : cnt) v = (int32_t)(rng() % (nrot + 1));
+    for (auto& v : msize) v = (double)(rng() % 40);
+    if (m >= 7) msize[3] = 16385.0;
+    for (int stat = 0; stat < 3; ++stat) {
+      REQUIRE(plaidhip_romer_finish(m, nfit, q, nrot, stat, cnt.data(), msize.data(), out.data()) == PLAIDHIP_OK);
+      for (size_t col = 0; col < (size_t)q * nfit; ++col)
+        for (int s = 0; s < m; ++s) {
+          const double* o = out.data() + col * 7 * m;
+          const double mm = msize[(col / q) * m + s];
+          REQUIRE(o[s] == mm);
+          for (int e = 0; e < 3; ++e) {
+            const double pv = o[(1 + e) * m + s], fdr = o[(4 + e) * m + s];
+            REQUIRE(std::isnan(pv) == (mm < 1.0 || (stat == 2 && mm > 16384.0)));
+            REQUIRE(std::isnan(pv) ? std::isnan(fdr) : (pv > 0.0 && pv <= 1.0 && fdr >= pv - 1e-15 && fdr <= 1.0));
+          }
+        }
+    }
+    REQUIRE(plaidhip_romer_finish(m, nfit, q, 0, 0, cnt.data(), msize.data(), out.data()) == PLAIDHIP_EINVAL);
+  }
+  printf("  romer: the shrink over universes of 0 .. 400 genes, the tables from counts, refused operands\n");
+}
+
 int main() {
   printf("[host-asan] planners\n");
   plans();
@@ -341,6 +386,8 @@ int main() {
   rankcor();
   printf("[host-asan] plaid.camera's residual row and finish\n");
   camera();
+  printf("[host-asan] plaid.romer's shrink and finish\n");
+  romer();
   printf("[host-asan] ok\n");
   return 0;
 }
