@@ -3,8 +3,8 @@
 // A contrast is a label per sample column: 0, 1, or "takes no part" (-1).  What differs between the contrasts is only
 // which accumulator a column's value is added to, and that is the same for every row of the column -- wavefront-uniform.
 // So the matrix (the score rows S, or dense X) is read once per tile of kContrastTile contrasts, not once per contrast:
-// a thread owns two adjacent rows, walks a block of kColBlock columns in ascending order, and keeps the two group
-// accumulators of every contrast of its tile in registers.
+// a thread owns two adjacent rows, walks a block of kRowColBlock columns in ascending order (row_pair.h), and keeps the
+// two group accumulators of every contrast of its tile in registers.
 //
 // The labels of a tile are two bit masks per column ("in group 0", "in group 1", bit t = contrast tile * T + t), built
 // once per call by contrast_masks_kernel and read through scalar loads; the bit positions are compile-time after
@@ -16,10 +16,10 @@
 // so a contrast without an excluded sample has the bits of the one-label kernels.  The select form matters: an excluded
 // column adds +0.0 whatever it holds (NaN, Inf).
 #include "common.h"
+#include "row_pair.h"
 
 namespace plaidhip {
 
-constexpr int kColBlock = 128;                       // kernels_stats.hip's column block: the same partials
 constexpr int kContrastTile = PLAIDHIP_CONTRAST_TILE;
 
 // masks[tile][c] = {bits of "Y[c, tile * T + t] == 0", bits of "== 1"}; Y: n x C column-major, leading dimension ldy
@@ -41,25 +41,20 @@ contrast_masks_kernel(const int32_t* __restrict__ Y, int64_t ldy, int32_t n, int
 
 // The block partials of the sums (kSsd false) or of the sums of squared deviations from mean ([C][2][rows]) of every
 // contrast of tile blockIdx.z, over the rows of S (rows x n, leading dimension ld) with v = (S[r, c] - med[c]) + add
-// applied on load (med == nullptr: v = S[r, c]).  part: [nblk][C][2][rows].  The load scheme is
-// row_group_shifted_partials_kernel's: kWide (rows and ld even, S 16-byte aligned) one 16-byte non-temporal load per
-// column for both rows, otherwise two 8-byte ones; kUn columns are loaded before the first of them is added.
+// applied on load (med == nullptr: v = S[r, c]).  part: [nblk][C][2][rows].  The walk is row_pair.h's (kUn = 8).
 template <bool kSsd, bool kWide>
 __global__ void __launch_bounds__(256)
 row_contrast_partials_kernel(const double* __restrict__ S, int64_t ld, int32_t rows, int32_t n,
                              const uint2* __restrict__ masks, int32_t C, const double* __restrict__ med, double add,
                              const double* __restrict__ mean, double* __restrict__ part) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
   constexpr int T = kContrastTile;
-  constexpr int kUn = 8;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kColBlock;
-  const int c1 = c0 + kColBlock < n ? c0 + kColBlock : n;
+  const RowPair g = row_pair_block(rows, n);
+  const int r = g.r;
   const int j0 = blockIdx.z * T;                      // the tile's first contrast
   const int nt = C - j0 < T ? C - j0 : T;             // its live contrasts (the others' masks are 0, nothing is written)
   const uint2* __restrict__ mk = masks + (int64_t)blockIdx.z * n;
   if (r >= rows) return;
-  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
+  const bool two = g.two;
   const bool shift = med != nullptr;
   double m0a[T], m1a[T], m0b[T], m1b[T];
   double s0a[T], s1a[T], s0b[T], s1b[T];
@@ -99,30 +94,7 @@ row_contrast_partials_kernel(const double* __restrict__ S, int64_t ld, int32_t r
       }
     }
   };
-  auto load = [&](int c, double& xa, double& xb) {
-    const double* p = S + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(p));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(p);
-      xb = two ? __builtin_nontemporal_load(p + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
-    double xa[kUn], xb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
-  }
-  for (; c < c1; ++c) {
-    double xa, xb;
-    load(c, xa, xb);
-    accumulate(c, xa, xb);
-  }
+  row_pair_walk<kWide, 8>(S, ld, g, accumulate);
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     if (t >= nt) break;
@@ -164,7 +136,7 @@ int64_t contrast_tiles(int32_t C) { return ((int64_t)C + kContrastTile - 1) / kC
 
 // doubles of the block partials [nblk][C][2][rows]
 int64_t row_contrast_ws_doubles(int32_t rows, int32_t n, int32_t C) {
-  const int64_t nblk = (n + kColBlock - 1) / kColBlock;
+  const int64_t nblk = (n + kRowColBlock - 1) / kRowColBlock;
   return 2 * (int64_t)rows * C * (nblk > 0 ? nblk : 1);
 }
 
@@ -187,25 +159,15 @@ int launch_row_contrast_partials(plaidhip_ctx* ctx, const double* S, int64_t ld,
                                  const void* d_masks, int32_t C, const double* d_med, double add, const double* d_mean,
                                  double* ws) {
   if (rows == 0 || n == 0 || C == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk, (unsigned)contrast_tiles(C));
   const uint2* mk = static_cast<const uint2*>(d_masks);
-  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
-  if (d_mean == nullptr) {
-    if (wide)
-      hipLaunchKernelGGL((row_contrast_partials_kernel<false, true>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n, mk, C,
-                         d_med, add, nullptr, ws);
-    else
-      hipLaunchKernelGGL((row_contrast_partials_kernel<false, false>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n, mk, C,
-                         d_med, add, nullptr, ws);
-  } else {
-    if (wide)
-      hipLaunchKernelGGL((row_contrast_partials_kernel<true, true>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n, mk, C,
-                         d_med, add, d_mean, ws);
-    else
-      hipLaunchKernelGGL((row_contrast_partials_kernel<true, false>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n, mk, C,
-                         d_med, add, d_mean, ws);
-  }
+  dispatch_flag(d_mean != nullptr, [&](auto ssd) {
+    dispatch_flag(row_pair_wide(rows, {ld}, {S}), [&](auto wide) {
+      hipLaunchKernelGGL((row_contrast_partials_kernel<decltype(ssd)::value, decltype(wide)::value>), grid, dim3(256), 0, ctx->stream,
+                         S, ld, rows, n, mk, C, d_med, add, d_mean, ws);
+    });
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
@@ -214,7 +176,7 @@ int launch_row_contrast_partials(plaidhip_ctx* ctx, const double* S, int64_t ld,
 int launch_reduce_blocks_flat(plaidhip_ctx* ctx, const double* ws, int64_t len, int32_t n, const double* d_seed,
                               double* d_out) {
   if (len == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   hipLaunchKernelGGL(reduce_blocks_flat_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, ws, len, nblk,
                      d_seed, d_out);
   PH_HIP(hipGetLastError());

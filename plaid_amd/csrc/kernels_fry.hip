@@ -1,9 +1,9 @@
 // plaid.fry: the device passes that plaid.camera does not already have (include/plaidhip.h: plaidhip_fry; DESIGN.md
 // section 26).
 //
-// fry_residual_kernel is camera_residual_kernel (kernels_camera.hip) with the gene's divisor read from c_g [nfit][rows]
-// (stats.cpp: fry_divisors) instead of derived from rss / d: the same thread and row geometry, the same chain
-// (camera_chain_step, ascending k from x_c), the same wide and narrow paths, 0.0 for a gene outside the universe.
+// fry_residual_kernel is camera_residual_kernel (kernels_camera.hip), the residual store of row_pair.h, with the gene's
+// divisor read from c_g [nfit][rows] (stats.cpp: fry_divisors) instead of derived from rss / d, and 0.0 for a gene outside
+// the universe (fry.h).
 // fry_gram_kernel, one workgroup per set: C = sum over the members of rho_g rho_g' (d x d), and for every contrast j the
 // border b_j = sum e_gj rho_g and a_j = sum e_gj^2 -- every entry one accumulator that takes the members in the set's own
 // order, product rounded, then added -- and from them tr M_j and |M_j|_F^2 in a fixed order.
@@ -11,101 +11,21 @@
 // held in LDS with an odd row stride) by cyclic two-sided Jacobi in the round-robin tournament order.
 #include "common.h"
 #include "fry.h"
+#include "row_pair.h"
 
 #pragma clang fp contract(off)
 
 namespace plaidhip {
-
-constexpr int kFryColBlock = 128;   // kernels_lmfit.hip's column block
-constexpr int kFryTile = PLAIDHIP_LIMMA_TILE;
 
 template <int kP, bool kWide>
 __global__ void __launch_bounds__(256)
 fry_residual_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const double* __restrict__ Q,
                     const uint32_t* __restrict__ masks, int32_t p, int32_t f, const double* __restrict__ E,
                     const double* __restrict__ cg, double* __restrict__ Z, int64_t ldz) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
-  constexpr int kUn = 8;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kFryColBlock;
-  const int c1 = c0 + kFryColBlock < n ? c0 + kFryColBlock : n;
-  const int64_t jm = (int64_t)f * (p + 1) + p;
-  const uint32_t* __restrict__ mk = masks + (jm / kFryTile) * n;
-  const int bit = (int)(jm % kFryTile);
-  const double* __restrict__ Qf = Q + (int64_t)f * p * n;
-  if (r >= rows) return;
-  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
-  double ea[kP], eb[kP];
-#pragma unroll
-  for (int k = 0; k < kP; ++k) {
-    ea[k] = eb[k] = 0.0;
-    if (k < p) {
-      const double* e = E + ((int64_t)f * (p + 1) + k) * rows;
-      ea[k] = e[r];
-      if (two) eb[k] = e[r + 1];
-    }
-  }
   const double* __restrict__ cf = cg + (int64_t)f * rows;
-  const double sa = cf[r];
-  const double sb = two ? cf[r + 1] : __builtin_nan("");
-  auto residuals = [&](int c, double xa, double xb) {
-    const bool in = ((mk[c] >> bit) & 1u) != 0;
-    double ra = xa, rb = xb;
-#pragma unroll
-    for (int k = 0; k < kP; ++k) {
-      if (k >= p) break;
-      const double qk = Qf[(int64_t)k * n + c];
-      ra = camera_chain_step(qk, ea[k], ra);
-      rb = camera_chain_step(qk, eb[k], rb);
-    }
-    const double za = fry_standardise(ra, sa, in), zb = fry_standardise(rb, sb, in);
-    double* o = Z + (int64_t)c * ldz + r;
-    if (kWide) {
-      f64x2_s v;
-      v.x = za;
-      v.y = zb;
-      *reinterpret_cast<f64x2_s*>(o) = v;
-    } else {
-      o[0] = za;
-      if (two) o[1] = zb;
-    }
-  };
-  auto load = [&](int c, double& xa, double& xb) {
-    const double* q = A + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(q);
-      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
-    double xa[kUn], xb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) residuals(c + u, xa[u], xb[u]);
-  }
-  for (; c < c1; ++c) {
-    double xa, xb;
-    load(c, xa, xb);
-    residuals(c, xa, xb);
-  }
-}
-
-template <int kP>
-static void launch_fry_residuals_p(plaidhip_ctx* ctx, bool wide, dim3 grid, const double* A, int64_t ld, int32_t rows, int32_t n,
-                                   const double* d_Q, const uint32_t* mk, int32_t p, int32_t f, const double* d_E,
-                                   const double* d_cg, double* Z, int64_t ldz) {
-  if (wide)
-    hipLaunchKernelGGL((fry_residual_kernel<kP, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, f, d_E, d_cg,
-                       Z, ldz);
-  else
-    hipLaunchKernelGGL((fry_residual_kernel<kP, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, f, d_E, d_cg,
-                       Z, ldz);
+  row_pair_residual_store<kP, kWide>(
+      A, ld, rows, n, Q, masks, p, f, E, Z, ldz, [&](int r) { return cf[r]; },
+      [](double r, double c, bool used) { return fry_standardise(r, c, used); });
 }
 
 // Z' (rows x n, leading dimension ldz >= rows) of fit f; the operands of launch_camera_residuals with d_cg [nfit][rows] in
@@ -114,15 +34,15 @@ int launch_fry_residuals(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t
                          const void* d_masks, int32_t p, int32_t f, const double* d_E, const double* d_cg, double* Z,
                          int64_t ldz) {
   if (rows == 0 || n == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kFryColBlock - 1) / kFryColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk);
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
-  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (ldz & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(Z) & 15u) == 0;
-  if (p <= 4) launch_fry_residuals_p<4>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, f, d_E, d_cg, Z, ldz);
-  else if (p <= 8) launch_fry_residuals_p<8>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, f, d_E, d_cg, Z, ldz);
-  else if (p <= 16) launch_fry_residuals_p<16>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, f, d_E, d_cg, Z, ldz);
-  else launch_fry_residuals_p<32>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, f, d_E, d_cg, Z, ldz);
+  dispatch_p(p, [&](auto kp) {
+    dispatch_flag(row_pair_wide(rows, {ld, ldz}, {A, Z}), [&](auto wide) {
+      hipLaunchKernelGGL((fry_residual_kernel<decltype(kp)::value, decltype(wide)::value>), grid, dim3(256), 0, ctx->stream, A, ld,
+                         rows, n, d_Q, mk, p, f, d_E, d_cg, Z, ldz);
+    });
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

@@ -6,8 +6,8 @@
 // columns of all fits lie side by side (fit f: columns f (p + 1) + 0 .. p - 1 are Q_f's, column f (p + 1) + p is the mean's)
 // and are cut into tiles of kTile; the weights of a column of A and the bits "this sample is used by the fit that owns tile
 // column t" are the same for every row -- wavefront-uniform, read through scalar loads.  A thread owns two adjacent rows,
-// walks a block of kColBlock columns in ascending order and keeps the tile's accumulators in registers, so A is read
-// ceil(W / kTile) times for the effects and nfit times for the residuals.  As in kernels_contrasts.hip:
+// walks a block of kRowColBlock columns in ascending order (the walk of row_pair.h) and keeps the tile's accumulators in
+// registers, so A is read ceil(W / kTile) times for the effects and nfit times for the residuals.  As in kernels_contrasts.hip:
 //     acc = in ? fma(x, w, acc) : acc          per column of the block, ascending (RSS: acc += in ? r * r : 0.0)
 //     part[block][column][row]
 //     blocks added in ascending order, from an optional seed (reduce_blocks_flat_kernel)
@@ -15,12 +15,12 @@
 // compiled with -ffp-contract=off (and says so below): the only fused operations are the fma written out.
 #include "common.h"
 #include "lmfit_na.h"
+#include "row_pair.h"
 
 #pragma clang fp contract(off)
 
 namespace plaidhip {
 
-constexpr int kLmColBlock = 128;   // kernels_contrasts.hip's column block (launch_reduce_blocks_flat counts in it)
 constexpr int kLmTile = PLAIDHIP_LIMMA_TILE;
 
 // masks[tile][c]: bit t = sample c is used by the fit of column tile * kTile + t (an 8-bit mask, kept in a 32-bit word so
@@ -52,26 +52,22 @@ lmfit_masks_kernel(const double* __restrict__ Q, const int8_t* __restrict__ use,
   masks[(int64_t)tile * n + c] = bits;
 }
 
-// The block partials part[nblk][W][rows] of the W weighted row sums, tile blockIdx.z.  The load scheme is
-// row_contrast_partials_kernel's: kWide (rows and ld even, A 16-byte aligned) one 16-byte non-temporal load per column for
-// both rows, otherwise two 8-byte ones; kUn columns are loaded before the first of them is used.
+// The block partials part[nblk][W][rows] of the W weighted row sums, tile blockIdx.z: the geometry and the load of row_pair.h
+// with the loop of row_pair_walk (kUn = 8) written out in the kernel, where it compiles to the code it had before the header.
 // kNa (na = "fit"): a NaN takes no part either -- the select is "c in sel and x_c == x_c", per row.
 template <bool kWide, bool kNa>
 __global__ void __launch_bounds__(256)
 row_design_effects_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const uint32_t* __restrict__ masks,
                           const double* __restrict__ wt, int32_t W, double* __restrict__ part) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
   constexpr int T = kLmTile;
-  constexpr int kUn = 8;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kLmColBlock;
-  const int c1 = c0 + kLmColBlock < n ? c0 + kLmColBlock : n;
+  const RowPair g = row_pair_block(rows, n);
+  const int r = g.r;
   const int j0 = blockIdx.z * T;                      // the tile's first column
   const int nt = W - j0 < T ? W - j0 : T;             // its live columns (the others' bits are 0, nothing is written)
   const uint32_t* __restrict__ mk = masks + (int64_t)blockIdx.z * n;
   const double* __restrict__ wk = wt + (int64_t)blockIdx.z * n * T;
   if (r >= rows) return;
-  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
+  const bool two = g.two;
   double a[T], b[T];
 #pragma unroll
   for (int t = 0; t < T; ++t) a[t] = b[t] = 0.0;
@@ -87,28 +83,19 @@ row_design_effects_kernel(const double* __restrict__ A, int64_t ld, int32_t rows
       b[t] = ib ? __builtin_fma(xb, wc, b[t]) : b[t];
     }
   };
-  auto load = [&](int c, double& xa, double& xb) {
-    const double* q = A + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(q);
-      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
+  // row_pair_walk<kWide, 8>(A, ld, g, accumulate), written out
+  constexpr int kUn = 8;
+  int c = g.c0;
+  for (; c + kUn <= g.c1; c += kUn) {
     double xa[kUn], xb[kUn];
 #pragma unroll
-    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
+    for (int u = 0; u < kUn; ++u) row_pair_load<kWide, true>(A + (int64_t)(c + u) * ld + r, two, xa[u], xb[u]);
 #pragma unroll
     for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
   }
-  for (; c < c1; ++c) {
+  for (; c < g.c1; ++c) {
     double xa, xb;
-    load(c, xa, xb);
+    row_pair_load<kWide, true>(A + (int64_t)c * ld + r, two, xa, xb);
     accumulate(c, xa, xb);
   }
 #pragma unroll
@@ -130,70 +117,26 @@ __global__ void __launch_bounds__(256)
 row_design_rss_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const double* __restrict__ Q,
                       const uint32_t* __restrict__ masks, int32_t p, int32_t nfit, const double* __restrict__ E,
                       double* __restrict__ part) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
-  constexpr int kUn = 8;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kLmColBlock;
-  const int c1 = c0 + kLmColBlock < n ? c0 + kLmColBlock : n;
-  const int f = blockIdx.z;
-  const int64_t jm = (int64_t)f * (p + 1) + p;        // the fit's mean column: its bit says "used by fit f"
-  const uint32_t* __restrict__ mk = masks + (jm / kLmTile) * n;
-  const int bit = (int)(jm % kLmTile);
+  const RowPair g = row_pair_block(rows, n);
+  const int r = g.r, f = blockIdx.z;
+  const RowPairFitBit used = row_pair_fit_bit(masks, (int64_t)f * (p + 1) + p, n);   // the fit's mean column
   const double* __restrict__ Qf = Q + (int64_t)f * p * n;
   if (r >= rows) return;
-  const bool two = r + 1 < rows;
   double ea[kP], eb[kP];
-#pragma unroll
-  for (int k = 0; k < kP; ++k) {
-    ea[k] = eb[k] = 0.0;
-    if (k < p) {
-      const double* e = E + ((int64_t)f * (p + 1) + k) * rows;
-      ea[k] = e[r];
-      if (two) eb[k] = e[r + 1];
-    }
-  }
+  row_pair_effects<kP>(E, f, p, rows, g, ea, eb);
   double sa = 0.0, sb = 0.0;
   auto accumulate = [&](int c, double xa, double xb) {
-    const bool in = ((mk[c] >> bit) & 1u) != 0;
+    const bool in = used(c);
     double ra = xa, rb = xb;
-#pragma unroll
-    for (int k = 0; k < kP; ++k) {
-      if (k >= p) break;
-      const double nq = -Qf[(int64_t)k * n + c];
-      ra = __builtin_fma(nq, ea[k], ra);
-      rb = __builtin_fma(nq, eb[k], rb);
-    }
+    row_pair_chain<kP>(Qf, n, c, p, ea, eb, ra, rb);
     const double qa = ra * ra, qb = rb * rb;
     sa += (kNa ? (in && xa == xa) : in) ? qa : 0.0;
     sb += (kNa ? (in && xb == xb) : in) ? qb : 0.0;
   };
-  auto load = [&](int c, double& xa, double& xb) {
-    const double* q = A + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(q);
-      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
-    double xa[kUn], xb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
-  }
-  for (; c < c1; ++c) {
-    double xa, xb;
-    load(c, xa, xb);
-    accumulate(c, xa, xb);
-  }
+  row_pair_walk<kWide, 8>(A, ld, g, accumulate);
   double* o = part + ((int64_t)blockIdx.y * nfit + f) * rows;
   o[r] = sa;
-  if (two) o[r + 1] = sb;
+  if (g.two) o[r + 1] = sb;
 }
 
 // ---- na = "fit" (include/plaidhip.h: plaidhip_limma_na) ---------------------------------------------------
@@ -209,8 +152,8 @@ __global__ void __launch_bounds__(256)
 lmfit_nan_rows_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n, const int64_t* __restrict__ off,
                       int32_t* __restrict__ cnt, int32_t* __restrict__ list) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kLmColBlock;
-  const int c1 = c0 + kLmColBlock < n ? c0 + kLmColBlock : n;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < n ? c0 + kRowColBlock : n;
   if (r >= rows) return;
   const int64_t slot = (int64_t)blockIdx.y * rows + r;
   int32_t k = 0;
@@ -291,7 +234,7 @@ lmfit_na_solve_kernel(const int32_t* __restrict__ pairs, const int64_t* __restri
 int launch_lmfit_nan_rows(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int64_t* d_off,
                           int32_t* d_cnt, int32_t* d_list) {
   if (rows == 0 || n == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(lmfit_nan_rows_kernel, dim3((rows + 255) / 256, (n + kLmColBlock - 1) / kLmColBlock), dim3(256), 0,
+  hipLaunchKernelGGL(lmfit_nan_rows_kernel, dim3((rows + 255) / 256, (n + kRowColBlock - 1) / kRowColBlock), dim3(256), 0,
                      ctx->stream, A, ld, rows, n, d_off, d_cnt, d_list);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
@@ -322,7 +265,7 @@ int64_t lmfit_tiles(int64_t W) { return (W + kLmTile - 1) / kLmTile; }
 
 // doubles of the block partials [nblk][cols][rows]
 int64_t row_design_ws_doubles(int32_t rows, int32_t n, int64_t cols) {
-  const int64_t nblk = (n + kLmColBlock - 1) / kLmColBlock;
+  const int64_t nblk = (n + kRowColBlock - 1) / kRowColBlock;
   return (int64_t)rows * cols * (nblk > 0 ? nblk : 1);
 }
 
@@ -344,49 +287,35 @@ int launch_lmfit_masks(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_use
 int launch_row_design_effects(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const void* d_masks,
                               const double* d_wt, int32_t W, double* ws, bool na) {
   if (rows == 0 || n == 0 || W == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kLmColBlock - 1) / kLmColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk, (unsigned)lmfit_tiles(W));
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
-  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
-  if (wide && na)
-    hipLaunchKernelGGL((row_design_effects_kernel<true, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
-  else if (wide)
-    hipLaunchKernelGGL((row_design_effects_kernel<true, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
-  else if (na)
-    hipLaunchKernelGGL((row_design_effects_kernel<false, true>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
-  else
-    hipLaunchKernelGGL((row_design_effects_kernel<false, false>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, mk, d_wt, W, ws);
+  dispatch_flag(row_pair_wide(rows, {ld}, {A}), [&](auto wide) {
+    dispatch_flag(na, [&](auto kna) {
+      hipLaunchKernelGGL((row_design_effects_kernel<decltype(wide)::value, decltype(kna)::value>), grid, dim3(256), 0, ctx->stream,
+                         A, ld, rows, n, mk, d_wt, W, ws);
+    });
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
-}
-
-template <int kP, bool kNa>
-static void launch_rss_p(plaidhip_ctx* ctx, bool wide, dim3 grid, const double* A, int64_t ld, int32_t rows, int32_t n,
-                         const double* d_Q, const uint32_t* mk, int32_t p, int32_t nfit, const double* d_E, double* ws) {
-  if (wide)
-    hipLaunchKernelGGL((row_design_rss_kernel<kP, true, kNa>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
-                       ws);
-  else
-    hipLaunchKernelGGL((row_design_rss_kernel<kP, false, kNa>), grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E,
-                       ws);
 }
 
 // ws: row_design_ws_doubles(rows, n, nfit) doubles, [nblk][nfit][rows]; d_E: [nfit (p + 1)][rows], the effects of all samples
 int launch_row_design_rss(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const double* d_Q,
                           const void* d_masks, int32_t p, int32_t nfit, const double* d_E, double* ws, bool na) {
   if (rows == 0 || n == 0 || nfit == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kLmColBlock - 1) / kLmColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk, nfit);
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
-  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
-  if (na) {
-    if (p <= 4) launch_rss_p<4, true>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-    else if (p <= 8) launch_rss_p<8, true>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-    else launch_rss_p<16, true>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);   // (p <= NA_MAX_COEF)
-  } else if (p <= 4) launch_rss_p<4, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-  else if (p <= 8) launch_rss_p<8, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-  else if (p <= 16) launch_rss_p<16, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
-  else launch_rss_p<32, false>(ctx, wide, grid, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+  const bool wide = row_pair_wide(rows, {ld}, {A});
+  auto launch = [&](auto kp, auto kna) {
+    dispatch_flag(wide, [&](auto w) {
+      hipLaunchKernelGGL((row_design_rss_kernel<decltype(kp)::value, decltype(w)::value, decltype(kna)::value>), grid, dim3(256), 0,
+                         ctx->stream, A, ld, rows, n, d_Q, mk, p, nfit, d_E, ws);
+    });
+  };
+  if (na) dispatch_p<16>(p, [&](auto kp) { launch(kp, std::true_type{}); });   // (p <= PLAIDHIP_LIMMA_NA_MAX_COEF)
+  else dispatch_p(p, [&](auto kp) { launch(kp, std::false_type{}); });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

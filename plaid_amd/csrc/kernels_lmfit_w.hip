@@ -1,8 +1,9 @@
 // plaid.limma with weights: the per-row weighted fit of include/plaidhip.h (plaidhip_limma_w).
 //
-// kernels_lmfit.hip with a second matrix beside A.  The basis stays the unweighted Q_f of the design; what a row needs of it
-// with its own weights omega_c are the Gram sums H_kl = sum_c omega_c q_ck q_cl (l <= k), b_k = sum_c (omega_c x_c) q_ck and
-// the mean's M', all over its live observations.  So fit f has Wc = p (p + 1) / 2 + p + 1 weight columns
+// kernels_lmfit.hip with a second matrix beside A (row_pair.h: row_pair_walk2).  The basis stays the unweighted Q_f of the
+// design; what a row needs of it with its own weights omega_c are the Gram sums H_kl = sum_c omega_c q_ck q_cl (l <= k),
+// b_k = sum_c (omega_c x_c) q_ck and the mean's M', all over its live observations.  So fit f has Wc = p (p + 1) / 2 + p + 1
+// weight columns
 //     [ pi_c,kl = q_ck q_cl, row by row of the triangle | q_ck | 1 / n_f ]
 // that are the same for every row -- wave-uniform, read through scalar loads -- and the per-row factor is omega, omega x or x
 // by the column's kind.  The columns of all fits lie side by side and are cut into tiles of kTile as in kernels_lmfit.hip:
@@ -14,6 +15,7 @@
 // -ffp-contract=off (and says so below): the only fused operations are the fma written out.
 #include "common.h"
 #include "lmfit_na.h"
+#include "row_pair.h"
 
 #pragma clang fp contract(off)
 
@@ -21,7 +23,6 @@ namespace plaidhip {
 
 namespace {
 
-constexpr int kWColBlock = 128;   // kernels_lmfit.hip's column block (launch_reduce_blocks_flat counts in it)
 constexpr int kWTile = PLAIDHIP_LIMMA_TILE;
 constexpr int kWP = PLAIDHIP_LIMMA_NA_MAX_COEF;
 constexpr int kWFitTile = 8;      // the fits whose counts share one read of A and the weights
@@ -73,26 +74,23 @@ lmfit_w_table_kernel(const double* __restrict__ Q, const int8_t* __restrict__ us
 }
 
 // The block partials part[nblk][W][rows] of the W = nfit Wc weighted row sums, tile blockIdx.z.  row_design_effects_kernel's
-// shape and load scheme (kWide: rows and ld even, A and Wt 16-byte aligned) with the per-row factor chosen by the column's
-// kind, which is wave-uniform: omega for a product column, y = omega * x (rounded once) for a column of Q, x for the mean's.
+// shape on the two-matrix walk of row_pair.h (kUn = 4; kWide: A and Wt 16-byte aligned) with the per-row factor chosen by the
+// column's kind, which is wave-uniform: omega for a product column, y = omega * x (rounded once) for a column of Q, x for the mean's.
 // kWt: the rows x n observation weights are there (same leading dimension as A); aw: the n array weights or null.
 template <bool kWide, bool kWt>
 __global__ void __launch_bounds__(256)
 row_design_w_sums_kernel(const double* __restrict__ A, const double* __restrict__ Wt, const double* __restrict__ aw, int64_t ld,
                          int32_t rows, int32_t n, const uint32_t* __restrict__ masks, const double* __restrict__ wt, int32_t W,
                          int32_t p, double* __restrict__ part) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
   constexpr int T = kWTile;
-  constexpr int kUn = 4;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kWColBlock;
-  const int c1 = c0 + kWColBlock < n ? c0 + kWColBlock : n;
+  const RowPair g = row_pair_block(rows, n);
+  const int r = g.r;
   const int j0 = blockIdx.z * T;
   const int nt = W - j0 < T ? W - j0 : T;
   const uint32_t* __restrict__ mk = masks + (int64_t)blockIdx.z * n;
   const double* __restrict__ wk = wt + (int64_t)blockIdx.z * n * T;
   if (r >= rows) return;
-  const bool two = r + 1 < rows;
+  const bool two = g.two;
   const int Wc = (int)w_cols(p), ntri = p * (p + 1) / 2;
   int kind[T];   // 0: a product column, 1: a column of Q, 2: the mean's (wave-uniform)
 #pragma unroll
@@ -122,35 +120,7 @@ row_design_w_sums_kernel(const double* __restrict__ A, const double* __restrict_
       b[t] = ib ? __builtin_fma(fb, wc, b[t]) : b[t];
     }
   };
-  auto load = [&](const double* M, int c, double& xa, double& xb) {
-    const double* q = M + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(q);
-      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
-    double xa[kUn], xb[kUn], wa[kUn], wb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) {
-      load(A, c + u, xa[u], xb[u]);
-      if (kWt) load(Wt, c + u, wa[u], wb[u]);
-      else wa[u] = wb[u] = 1.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u], wa[u], wb[u]);
-  }
-  for (; c < c1; ++c) {
-    double xa, xb, wa = 1.0, wb = 1.0;
-    load(A, c, xa, xb);
-    if (kWt) load(Wt, c, wa, wb);
-    accumulate(c, xa, xb, wa, wb);
-  }
+  row_pair_walk2<kWide, 4, kWt>(A, Wt, ld, g, accumulate);
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     if (t >= nt) break;
@@ -170,8 +140,8 @@ lmfit_w_counts_kernel(const double* __restrict__ A, const double* __restrict__ W
                       int32_t rows, int32_t n, const int8_t* __restrict__ use, int32_t nfit, double* __restrict__ part) {
   constexpr int F = kWFitTile;
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kWColBlock;
-  const int c1 = c0 + kWColBlock < n ? c0 + kWColBlock : n;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < n ? c0 + kRowColBlock : n;
   const int f0 = blockIdx.z * F;
   if (r >= rows) return;
   const bool has_aw = aw != nullptr;
@@ -252,78 +222,30 @@ __global__ void __launch_bounds__(256)
 row_design_w_rss_kernel(const double* __restrict__ A, const double* __restrict__ Wt, const double* __restrict__ aw, int64_t ld,
                         int32_t rows, int32_t n, const double* __restrict__ Q, const uint32_t* __restrict__ masks, int32_t p,
                         int32_t nfit, const double* __restrict__ G, double* __restrict__ part) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
-  constexpr int kUn = 4;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kWColBlock;
-  const int c1 = c0 + kWColBlock < n ? c0 + kWColBlock : n;
-  const int f = blockIdx.z;
-  const int64_t Wc = w_cols(p), jm = (int64_t)f * Wc + Wc - 1;   // the fit's mean column: its bit says "used by fit f"
-  const uint32_t* __restrict__ mk = masks + (jm / kWTile) * n;
-  const int bit = (int)(jm % kWTile);
+  const RowPair g = row_pair_block(rows, n);
+  const int r = g.r, f = blockIdx.z;
+  const int64_t Wc = w_cols(p);
+  const RowPairFitBit used = row_pair_fit_bit(masks, (int64_t)f * Wc + Wc - 1, n);   // the fit's mean column
   const double* __restrict__ Qf = Q + (int64_t)f * p * n;
   if (r >= rows) return;
-  const bool two = r + 1 < rows;
   const bool has_aw = aw != nullptr;
   double ea[kP], eb[kP];
-#pragma unroll
-  for (int k = 0; k < kP; ++k) {
-    ea[k] = eb[k] = 0.0;
-    if (k < p) {
-      const double* e = G + ((int64_t)f * (p + 1) + k) * rows;
-      ea[k] = e[r];
-      if (two) eb[k] = e[r + 1];
-    }
-  }
+  row_pair_effects<kP>(G, f, p, rows, g, ea, eb);
   double sa = 0.0, sb = 0.0;
   auto accumulate = [&](int c, double xa, double xb, double wa, double wb) {
-    const bool in = ((mk[c] >> bit) & 1u) != 0;
+    const bool in = used(c);
     const double awc = has_aw ? aw[c] : 1.0;
     const double oa = w_omega(kWt, wa, has_aw, awc), ob = w_omega(kWt, wb, has_aw, awc);
     double ra = xa, rb = xb;
-#pragma unroll
-    for (int k = 0; k < kP; ++k) {
-      if (k >= p) break;
-      const double nq = -Qf[(int64_t)k * n + c];
-      ra = __builtin_fma(nq, ea[k], ra);
-      rb = __builtin_fma(nq, eb[k], rb);
-    }
+    row_pair_chain<kP>(Qf, n, c, p, ea, eb, ra, rb);
     const double qa = ra * ra, qb = rb * rb;
     sa = in && w_live(xa, oa) ? __builtin_fma(oa, qa, sa) : sa;
     sb = in && w_live(xb, ob) ? __builtin_fma(ob, qb, sb) : sb;
   };
-  auto load = [&](const double* M, int c, double& xa, double& xb) {
-    const double* q = M + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(q));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(q);
-      xb = two ? __builtin_nontemporal_load(q + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
-    double xa[kUn], xb[kUn], wa[kUn], wb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) {
-      load(A, c + u, xa[u], xb[u]);
-      if (kWt) load(Wt, c + u, wa[u], wb[u]);
-      else wa[u] = wb[u] = 1.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u], wa[u], wb[u]);
-  }
-  for (; c < c1; ++c) {
-    double xa, xb, wa = 1.0, wb = 1.0;
-    load(A, c, xa, xb);
-    if (kWt) load(Wt, c, wa, wb);
-    accumulate(c, xa, xb, wa, wb);
-  }
+  row_pair_walk2<kWide, 4, kWt>(A, Wt, ld, g, accumulate);
   double* o = part + ((int64_t)blockIdx.y * nfit + f) * rows;
   o[r] = sa;
-  if (two) o[r + 1] = sb;
+  if (g.two) o[r + 1] = sb;
 }
 
 // ---- the launchers (common.h) -------------------------------------------------------------------------------------------------
@@ -341,11 +263,6 @@ int launch_lmfit_w_table(plaidhip_ctx* ctx, const double* d_Q, const int8_t* d_u
   return PLAIDHIP_OK;
 }
 
-static bool w_wide(const double* A, const double* Wt, int64_t ld, int32_t rows) {
-  return (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0 &&
-         (Wt == nullptr || (reinterpret_cast<uintptr_t>(Wt) & 15u) == 0);
-}
-
 // ws: row_design_ws_doubles(rows, n, W) doubles, [nblk][W][rows], W = nfit lmfit_w_columns(p); d_masks / d_wt:
 // launch_lmfit_w_table of the same n.  d_Wt: rows x n with A's leading dimension, or null; d_aw: n, or null.
 int launch_row_design_w_sums(plaidhip_ctx* ctx, const double* A, const double* d_Wt, const double* d_aw, int64_t ld, int32_t rows,
@@ -354,18 +271,15 @@ int launch_row_design_w_sums(plaidhip_ctx* ctx, const double* A, const double* d
   const int64_t W = (int64_t)nfit * w_cols(p), tiles = lmfit_tiles(W);
   PH_REQUIRE(p >= 1 && p <= kWP && tiles <= 65535 && W <= 2147483647, "limma_w: p = %d, %lld tiles of weight columns", p,
              (long long)tiles);
-  const int nblk = (n + kWColBlock - 1) / kWColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk, (unsigned)tiles);
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
-  const bool wide = w_wide(A, d_Wt, ld, rows), has = d_Wt != nullptr;
-#define PH_W_SUMS(WIDE, HAS)                                                                                                  \
-  hipLaunchKernelGGL((row_design_w_sums_kernel<WIDE, HAS>), grid, dim3(256), 0, ctx->stream, A, d_Wt, d_aw, ld, rows, n, mk, d_wt, \
-                     (int32_t)W, p, ws)
-  if (wide && has) PH_W_SUMS(true, true);
-  else if (wide) PH_W_SUMS(true, false);
-  else if (has) PH_W_SUMS(false, true);
-  else PH_W_SUMS(false, false);
-#undef PH_W_SUMS
+  dispatch_flag(row_pair_wide(rows, {ld}, {A, d_Wt}), [&](auto wide) {
+    dispatch_flag(d_Wt != nullptr, [&](auto has) {
+      hipLaunchKernelGGL((row_design_w_sums_kernel<decltype(wide)::value, decltype(has)::value>), grid, dim3(256), 0, ctx->stream, A,
+                         d_Wt, d_aw, ld, rows, n, mk, d_wt, (int32_t)W, p, ws);
+    });
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
@@ -374,7 +288,7 @@ int launch_row_design_w_sums(plaidhip_ctx* ctx, const double* A, const double* d
 int launch_lmfit_w_counts(plaidhip_ctx* ctx, const double* A, const double* d_Wt, const double* d_aw, int64_t ld, int32_t rows,
                           int32_t n, const int8_t* d_use, int32_t nfit, double* ws) {
   if (rows == 0 || n == 0 || nfit == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kWColBlock - 1) / kWColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 255) / 256, nblk, (nfit + kWFitTile - 1) / kWFitTile);
   if (d_Wt != nullptr)
     hipLaunchKernelGGL((lmfit_w_counts_kernel<true>), grid, dim3(256), 0, ctx->stream, A, d_Wt, d_aw, ld, rows, n, d_use, nfit, ws);
@@ -397,33 +311,23 @@ int launch_lmfit_w_solve(plaidhip_ctx* ctx, const double* d_S, const double* d_c
   return PLAIDHIP_OK;
 }
 
-template <int kP>
-static void launch_w_rss_p(plaidhip_ctx* ctx, bool wide, bool has, dim3 grid, const double* A, const double* d_Wt,
-                           const double* d_aw, int64_t ld, int32_t rows, int32_t n, const double* d_Q, const uint32_t* mk,
-                           int32_t p, int32_t nfit, const double* d_G, double* ws) {
-#define PH_W_RSS(WIDE, HAS)                                                                                                     \
-  hipLaunchKernelGGL((row_design_w_rss_kernel<kP, WIDE, HAS>), grid, dim3(256), 0, ctx->stream, A, d_Wt, d_aw, ld, rows, n, d_Q, mk, \
-                     p, nfit, d_G, ws)
-  if (wide && has) PH_W_RSS(true, true);
-  else if (wide) PH_W_RSS(true, false);
-  else if (has) PH_W_RSS(false, true);
-  else PH_W_RSS(false, false);
-#undef PH_W_RSS
-}
-
 // ws: row_design_ws_doubles(rows, n, nfit) doubles, [nblk][nfit][rows]; d_G: [nfit (p + 1)][rows], gamma of every pair
 int launch_row_design_w_rss(plaidhip_ctx* ctx, const double* A, const double* d_Wt, const double* d_aw, int64_t ld, int32_t rows,
                             int32_t n, const double* d_Q, const void* d_masks, int32_t p, int32_t nfit, const double* d_G,
                             double* ws) {
   if (rows == 0 || n == 0 || nfit == 0) return PLAIDHIP_OK;
   PH_REQUIRE(p >= 1 && p <= kWP && nfit <= 65535, "limma_w: p = %d, nfit = %d", p, nfit);
-  const int nblk = (n + kWColBlock - 1) / kWColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk, nfit);
   const uint32_t* mk = static_cast<const uint32_t*>(d_masks);
-  const bool wide = w_wide(A, d_Wt, ld, rows), has = d_Wt != nullptr;
-  if (p <= 4) launch_w_rss_p<4>(ctx, wide, has, grid, A, d_Wt, d_aw, ld, rows, n, d_Q, mk, p, nfit, d_G, ws);
-  else if (p <= 8) launch_w_rss_p<8>(ctx, wide, has, grid, A, d_Wt, d_aw, ld, rows, n, d_Q, mk, p, nfit, d_G, ws);
-  else launch_w_rss_p<kWP>(ctx, wide, has, grid, A, d_Wt, d_aw, ld, rows, n, d_Q, mk, p, nfit, d_G, ws);
+  dispatch_p<kWP>(p, [&](auto kp) {   // (4, 8 and kWP effects)
+    dispatch_flag(row_pair_wide(rows, {ld}, {A, d_Wt}), [&](auto wide) {
+      dispatch_flag(d_Wt != nullptr, [&](auto has) {
+        hipLaunchKernelGGL((row_design_w_rss_kernel<decltype(kp)::value, decltype(wide)::value, decltype(has)::value>), grid,
+                           dim3(256), 0, ctx->stream, A, d_Wt, d_aw, ld, rows, n, d_Q, mk, p, nfit, d_G, ws);
+      });
+    });
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

@@ -1,6 +1,6 @@
 // plaid.roast: the device passes (include/plaidhip.h: plaidhip_roast).
 //
-// roast_rotate_kernel: a thread holds two genes and 16 rotations.  It runs the sample loop once over the raw residuals
+// roast_rotate_kernel: a thread holds two genes and 16 rotations.  It runs the walk of row_pair.h once over the raw residuals
 // ([n][ldz], genes contiguous; kernels_fry.hip's residual pass with a divisor of 1.0), B = fma chain ascending from
 // beta r0, and fuses steps 3 and 4 (roast.h): z goes out as [tile of 64 rotations][gene][64], the layout whose 64
 // rotations of one gene the statistic kernels read with one 512-byte request.  The weights W ((n + 1) x ldw, row 0 = r0) are
@@ -14,6 +14,7 @@
 // #{stat_k >= stat_obs} with integer atomics.
 #include "common.h"
 #include "roast.h"
+#include "row_pair.h"
 
 #pragma clang fp contract(off)
 
@@ -27,11 +28,11 @@ __global__ void __launch_bounds__(256)
 roast_rotate_kernel(const double* __restrict__ Rz, int64_t ldz, int32_t rows, int32_t n, const double* __restrict__ beta,
                     const double* __restrict__ rss, const double* __restrict__ W, int64_t ldw, int32_t k0, int32_t k1,
                     RoastFit fit, int zscore, double* __restrict__ Z) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
+  const RowPair g = row_pair_columns(rows, 0, n);
+  const int r = g.r;
   const int kb = k0 + kRotPer * blockIdx.y;   // (k0 is a multiple of 64; ldw covers kb + 15)
   if (r >= rows) return;
-  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
+  const bool two = g.two;
   const double ba = beta[r], bb = two ? beta[r + 1] : 0.0;
   double a[kRotPer], b[kRotPer];
   const double* __restrict__ w0 = W + kb;
@@ -41,17 +42,6 @@ roast_rotate_kernel(const double* __restrict__ Rz, int64_t ldz, int32_t rows, in
     a[t] = ba * r0;
     b[t] = bb * r0;
   }
-  auto load = [&](int c, double& xa, double& xb) {
-    const double* q = Rz + (int64_t)c * ldz + r;
-    if (kWide) {
-      const f64x2_s v = *reinterpret_cast<const f64x2_s*>(q);
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = q[0];
-      xb = two ? q[1] : 0.0;
-    }
-  };
   auto step = [&](int c, double xa, double xb) {
     const double* __restrict__ wc = W + (int64_t)(c + 1) * ldw + kb;
 #pragma unroll
@@ -61,20 +51,7 @@ roast_rotate_kernel(const double* __restrict__ Rz, int64_t ldz, int32_t rows, in
       b[t] = roast_chain_step(xb, w, b[t]);
     }
   };
-  constexpr int kUn = 4;
-  int c = 0;
-  for (; c + kUn <= n; c += kUn) {
-    double xa[kUn], xb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) step(c + u, xa[u], xb[u]);
-  }
-  for (; c < n; ++c) {
-    double xa, xb;
-    load(c, xa, xb);
-    step(c, xa, xb);
-  }
+  row_pair_walk<kWide, 4, false>(Rz, ldz, g, step);   // plain loads: every blockIdx.y reads Rz again
   const double ra = rss[r], rb = two ? rss[r + 1] : 0.0;
   const int64_t tile = (kb - k0) / kRotTile;
   double* __restrict__ o = Z + (tile * rows + r) * kRotTile + (kb - k0) % kRotTile;
@@ -94,13 +71,10 @@ int launch_roast_rotate(plaidhip_ctx* ctx, const double* Rz, int64_t ldz, int32_
                         double* Z) {
   if (rows == 0 || k1 <= k0) return PLAIDHIP_OK;
   const dim3 grid((rows + 511) / 512, (k1 - k0 + kRotPer - 1) / kRotPer);
-  const bool wide = (rows & 1) == 0 && (ldz & 1) == 0 && (reinterpret_cast<uintptr_t>(Rz) & 15u) == 0;
-  if (wide)
-    hipLaunchKernelGGL((roast_rotate_kernel<true>), grid, dim3(256), 0, ctx->stream, Rz, ldz, rows, n, d_beta, d_rss, d_W, ldw, k0,
-                       k1, fit, zscore, Z);
-  else
-    hipLaunchKernelGGL((roast_rotate_kernel<false>), grid, dim3(256), 0, ctx->stream, Rz, ldz, rows, n, d_beta, d_rss, d_W, ldw,
-                       k0, k1, fit, zscore, Z);
+  dispatch_flag(row_pair_wide(rows, {ldz}, {Rz}), [&](auto wide) {
+    hipLaunchKernelGGL((roast_rotate_kernel<decltype(wide)::value>), grid, dim3(256), 0, ctx->stream, Rz, ldz, rows, n, d_beta, d_rss,
+                       d_W, ldw, k0, k1, fit, zscore, Z);
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }

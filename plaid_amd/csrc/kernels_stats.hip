@@ -6,23 +6,22 @@
 //   per-row group variances for the Welch tests Rfast::ttests(t(gsetX), ina = y + 1)   (:429)
 //
 // A is column-major (rows contiguous), so a thread owns a row and a workgroup walks a block of
-// columns: every load is coalesced.  Columns are cut into blocks of kColBlock; a block writes its
+// columns: every load is coalesced.  Columns are cut into blocks of kRowColBlock (row_pair.h); a block writes its
 // partial sums to [block][stat][row] and a second kernel adds the blocks in a fixed order
 // (deterministic, no atomics).  Variances are two-pass (sum of squared deviations from the group
 // mean), which is at least as accurate as the sum-of-squares formula of the reference.
 #include "common.h"
+#include "row_pair.h"
 
 namespace plaidhip {
-
-constexpr int kColBlock = 128;
 
 // pass 1: sums per group.  part: [nblk][2][rows]
 __global__ void __launch_bounds__(256)
 row_group_sums_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int32_t n,
                       const int32_t* __restrict__ y, double* __restrict__ part) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kColBlock;
-  const int c1 = c0 + kColBlock < n ? c0 + kColBlock : n;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < n ? c0 + kRowColBlock : n;
   double s0 = 0.0, s1 = 0.0;
   if (r < rows) {
     for (int c = c0; c < c1; ++c) {
@@ -43,8 +42,8 @@ row_group_ssd_kernel(const double* __restrict__ A, int64_t ld, int32_t rows, int
                      const int32_t* __restrict__ y, const double* __restrict__ mean,
                      double* __restrict__ part) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kColBlock;
-  const int c1 = c0 + kColBlock < n ? c0 + kColBlock : n;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < n ? c0 + kRowColBlock : n;
   if (r < rows) {
     const double m0 = mean[r], m1 = mean[rows + r];
     double q0 = 0.0, q1 = 0.0;
@@ -74,7 +73,7 @@ reduce_blocks_kernel(const double* __restrict__ part, int32_t rows, int32_t nblk
 
 // out[r] = seed[r] (0 without a seed) + part[0][0][r] + part[1][0][r] + ..., the blocks added in order: group 0 of
 // reduce_blocks_kernel, continued from where the previous column shard stopped.  A sample-sharded caller whose shards
-// start on block boundaries (multiples of kColBlock columns) and that chains them in column order adds exactly what
+// start on block boundaries (multiples of kRowColBlock columns) and that chains them in column order adds exactly what
 // reduce_blocks_kernel adds over all columns, in the same order; the scale step stays with the caller.
 __global__ void __launch_bounds__(256)
 reduce_blocks_seeded_kernel(const double* __restrict__ part, int32_t rows, int32_t nblk, const double* __restrict__ seed,
@@ -102,8 +101,8 @@ __device__ __forceinline__ void row_ztransform_body(double* __restrict__ A, int6
                                                     int32_t n_sd, const double* __restrict__ mean,
                                                     const double* __restrict__ ssd) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kColBlock;
-  const int c1 = c0 + kColBlock < ncols ? c0 + kColBlock : ncols;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < ncols ? c0 + kRowColBlock : ncols;
   if (r >= rows) return;
   const double mu = mean[r];
   const double den = 1e-8 + sqrt(ssd[r] / (double)(n_sd - 1));   // sd with n - 1 (NaN for a single sample, as in R)
@@ -124,7 +123,7 @@ row_ztransform_shard_kernel(double* __restrict__ A, int64_t ld, int32_t rows, in
 int launch_row_ztransform_shard(plaidhip_ctx* ctx, double* A, int64_t ld, int32_t rows, int32_t ncols, int32_t n_total,
                                 const double* d_mean, const double* d_ssd) {
   if (rows == 0 || ncols == 0) return PLAIDHIP_OK;
-  const int nblk = (ncols + kColBlock - 1) / kColBlock;
+  const int nblk = (ncols + kRowColBlock - 1) / kRowColBlock;
   hipLaunchKernelGGL(row_ztransform_shard_kernel, dim3((rows + 255) / 256, nblk), dim3(256), 0, ctx->stream, A, ld, rows,
                      ncols, n_total, d_mean, d_ssd);
   PH_HIP(hipGetLastError());
@@ -162,12 +161,12 @@ int launch_transpose_f64(plaidhip_ctx* ctx, const double* A, int64_t lda, int32_
 
 // Group means (and optionally sums of squared deviations) of every row of A.
 // d_mean: [2][rows] (group 0, group 1); d_ssd: [2][rows] or null.  n0 / n1: group sizes.
-// ws: scratch of at least 2 * rows * ceil(n / kColBlock) doubles.
+// ws: scratch of at least 2 * rows * ceil(n / kRowColBlock) doubles.
 int launch_row_group_moments(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n,
                              const int32_t* d_y, int64_t n0, int64_t n1, double* d_mean, double* d_ssd,
                              double* ws) {
   if (rows == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 255) / 256, nblk > 0 ? nblk : 1);
   const int red_blocks = (2 * rows + 255) / 256;
   if (n > 0) hipLaunchKernelGGL(row_group_sums_kernel, grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_y, ws);
@@ -186,7 +185,7 @@ int launch_row_group_moments(plaidhip_ctx* ctx, const double* A, int64_t ld, int
 int launch_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int32_t* d_y,
                          const double* d_mean, double* d_ssd, double* ws) {
   if (rows == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 255) / 256, nblk > 0 ? nblk : 1);
   const int red_blocks = (2 * rows + 255) / 256;
   if (n > 0) hipLaunchKernelGGL(row_group_ssd_kernel, grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_y, d_mean, ws);
@@ -197,11 +196,11 @@ int launch_row_group_ssd(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t
 }
 
 // the per-block partials of launch_row_group_moments over one column shard (sums; or, with d_mean, sums of squared
-// deviations from it), left in ws ([nblk][2][rows], nblk = ceil(n / kColBlock))
+// deviations from it), left in ws ([nblk][2][rows], nblk = ceil(n / kRowColBlock))
 int launch_row_group_partials(plaidhip_ctx* ctx, const double* A, int64_t ld, int32_t rows, int32_t n, const int32_t* d_y,
                               const double* d_mean, double* ws) {
   if (rows == 0 || n == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 255) / 256, nblk);
   if (d_mean == nullptr)
     hipLaunchKernelGGL(row_group_sums_kernel, grid, dim3(256), 0, ctx->stream, A, ld, rows, n, d_y, ws);
@@ -215,7 +214,7 @@ int launch_row_group_partials(plaidhip_ctx* ctx, const double* A, int64_t ld, in
 int launch_reduce_blocks_seeded(plaidhip_ctx* ctx, const double* ws, int32_t rows, int32_t n, const double* d_seed,
                                 double* d_out) {
   if (rows == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   hipLaunchKernelGGL(reduce_blocks_seeded_kernel, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, ws, rows, nblk, d_seed,
                      d_out);
   PH_HIP(hipGetLastError());
@@ -235,21 +234,16 @@ int launch_fold_change(plaidhip_ctx* ctx, const double* d_mean, int32_t rows, in
 // column blocks, the same per-row additions in ascending column order and the same [nblk][2][rows] output as the two
 // kernels above, so the seeded chain adds what the one-device entry adds after its in-place shift -- and the shifted S
 // is never written: two streaming reads of S replace the shift's read + write and the two passes after it.
-// A thread owns two adjacent rows; kWide (rows and ld even, S 16-byte aligned): one 16-byte non-temporal load per column
-// for both, otherwise two 8-byte ones.  kUn columns are loaded before the first of them is added (S is far larger than
-// the Infinity Cache: the loads of a wave must overlap).
+// A thread owns two adjacent rows: the walk of row_pair.h (kUn = 8).
 template <bool kSsd, bool kWide>
 __global__ void __launch_bounds__(256)
 row_group_shifted_partials_kernel(const double* __restrict__ S, int64_t ld, int32_t rows, int32_t n,
                                   const int32_t* __restrict__ y, const double* __restrict__ med, double add,
                                   const double* __restrict__ mean, double* __restrict__ part) {
-  typedef double f64x2_s __attribute__((ext_vector_type(2)));
-  constexpr int kUn = 8;
-  const int r = 2 * (blockIdx.x * 256 + threadIdx.x);
-  const int c0 = blockIdx.y * kColBlock;
-  const int c1 = c0 + kColBlock < n ? c0 + kColBlock : n;
+  const RowPair g = row_pair_block(rows, n);
+  const int r = g.r;
   if (r >= rows) return;
-  const bool two = r + 1 < rows;   // (false only for the last row of an odd `rows`: never kWide)
+  const bool two = g.two;
   const bool shift = med != nullptr;
   double m0a = 0.0, m1a = 0.0, m0b = 0.0, m1b = 0.0;
   if (kSsd) {
@@ -279,30 +273,7 @@ row_group_shifted_partials_kernel(const double* __restrict__ S, int64_t ld, int3
       s1b += lab == 1 ? vb : 0.0;
     }
   };
-  auto load = [&](int c, double& xa, double& xb) {
-    const double* p = S + (int64_t)c * ld + r;
-    if (kWide) {
-      const f64x2_s v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_s*>(p));
-      xa = v.x;
-      xb = v.y;
-    } else {
-      xa = __builtin_nontemporal_load(p);
-      xb = two ? __builtin_nontemporal_load(p + 1) : 0.0;
-    }
-  };
-  int c = c0;
-  for (; c + kUn <= c1; c += kUn) {
-    double xa[kUn], xb[kUn];
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) load(c + u, xa[u], xb[u]);
-#pragma unroll
-    for (int u = 0; u < kUn; ++u) accumulate(c + u, xa[u], xb[u]);
-  }
-  for (; c < c1; ++c) {
-    double xa, xb;
-    load(c, xa, xb);
-    accumulate(c, xa, xb);
-  }
+  row_pair_walk<kWide, 8>(S, ld, g, accumulate);
   double* p = part + (int64_t)blockIdx.y * 2 * rows;
   p[r] = s0a;
   p[rows + r] = s1a;
@@ -316,30 +287,20 @@ int launch_row_group_shifted_partials(plaidhip_ctx* ctx, const double* S, int64_
                                       const int32_t* d_y, const double* d_med, double add, const double* d_mean,
                                       double* ws) {
   if (rows == 0 || n == 0) return PLAIDHIP_OK;
-  const int nblk = (n + kColBlock - 1) / kColBlock;
+  const int nblk = (n + kRowColBlock - 1) / kRowColBlock;
   const dim3 grid((rows + 511) / 512, nblk);
-  const bool wide = (rows & 1) == 0 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
-  if (d_mean == nullptr) {
-    if (wide)
-      hipLaunchKernelGGL((row_group_shifted_partials_kernel<false, true>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
-                         d_y, d_med, add, nullptr, ws);
-    else
-      hipLaunchKernelGGL((row_group_shifted_partials_kernel<false, false>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
-                         d_y, d_med, add, nullptr, ws);
-  } else {
-    if (wide)
-      hipLaunchKernelGGL((row_group_shifted_partials_kernel<true, true>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
-                         d_y, d_med, add, d_mean, ws);
-    else
-      hipLaunchKernelGGL((row_group_shifted_partials_kernel<true, false>), grid, dim3(256), 0, ctx->stream, S, ld, rows, n,
-                         d_y, d_med, add, d_mean, ws);
-  }
+  dispatch_flag(d_mean != nullptr, [&](auto ssd) {
+    dispatch_flag(row_pair_wide(rows, {ld}, {S}), [&](auto wide) {
+      hipLaunchKernelGGL((row_group_shifted_partials_kernel<decltype(ssd)::value, decltype(wide)::value>), grid, dim3(256), 0,
+                         ctx->stream, S, ld, rows, n, d_y, d_med, add, d_mean, ws);
+    });
+  });
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
 }
 
 int64_t row_group_ws_doubles(int32_t rows, int32_t n) {
-  const int64_t nblk = (n + kColBlock - 1) / kColBlock;
+  const int64_t nblk = (n + kRowColBlock - 1) / kRowColBlock;
   return 2 * (int64_t)rows * (nblk > 0 ? nblk : 1);
 }
 

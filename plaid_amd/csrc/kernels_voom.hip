@@ -6,13 +6,13 @@
 //              interpolation, w = 1 / ((f f) (f f)); a thread keeps its row's p effects in registers
 // The unweighted fit between them is kernels_lmfit.hip's two passes.  Compiled with -ffp-contract=off (and says so below).
 #include "common.h"
+#include "row_pair.h"   // kRowColBlock: the one-row kernels below keep their own loops
 
 #pragma clang fp contract(off)
 
 namespace plaidhip {
 
 namespace {
-constexpr int kVColBlock = 128;
 constexpr int kVKnots = PLAIDHIP_VOOM_MAX_KNOTS;
 }  // namespace
 
@@ -44,8 +44,8 @@ voom_check_kernel(const double* __restrict__ X, int64_t ld, int32_t rows, double
 __global__ void __launch_bounds__(256)
 voom_rowsum_kernel(const double* __restrict__ X, int64_t ld, int32_t rows, int32_t n, double* __restrict__ part) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kVColBlock;
-  const int c1 = c0 + kVColBlock < n ? c0 + kVColBlock : n;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < n ? c0 + kRowColBlock : n;
   if (r >= rows) return;
   double s = 0.0;
   for (int c = c0; c < c1; ++c) s = s + X[(int64_t)c * ld + r];
@@ -92,8 +92,8 @@ voom_weights_kernel(const double* __restrict__ Q, const double* __restrict__ off
   }
   __syncthreads();
   const int r = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = blockIdx.y * kVColBlock;
-  const int c1 = c0 + kVColBlock < n ? c0 + kVColBlock : n;
+  const int c0 = blockIdx.y * kRowColBlock;
+  const int c1 = c0 + kRowColBlock < n ? c0 + kRowColBlock : n;
   if (r >= rows) return;
   double e[kP];
 #pragma unroll
@@ -121,7 +121,7 @@ int launch_voom_check(plaidhip_ctx* ctx, const double* X, int64_t ld, int32_t ro
 // part: row_design_ws_doubles(rows, n, 1) doubles, [nblk][rows]
 int launch_voom_rowsum(plaidhip_ctx* ctx, const double* X, int64_t ld, int32_t rows, int32_t n, double* part) {
   if (rows == 0 || n == 0) return PLAIDHIP_OK;
-  hipLaunchKernelGGL(voom_rowsum_kernel, dim3((rows + 255) / 256, (n + kVColBlock - 1) / kVColBlock), dim3(256), 0, ctx->stream, X,
+  hipLaunchKernelGGL(voom_rowsum_kernel, dim3((rows + 255) / 256, (n + kRowColBlock - 1) / kRowColBlock), dim3(256), 0, ctx->stream, X,
                      ld, rows, n, part);
   PH_HIP(hipGetLastError());
   return PLAIDHIP_OK;
@@ -140,7 +140,7 @@ int launch_voom_weights(plaidhip_ctx* ctx, const double* d_Q, const double* d_of
   if (rows == 0 || n == 0) return PLAIDHIP_OK;
   PH_REQUIRE(nk >= 1 && nk <= kVKnots, "voom: %d knots (1 <= knots <= %d)", nk, kVKnots);
   PH_REQUIRE(p >= 1 && p <= PLAIDHIP_LIMMA_MAX_COEF, "voom: p = %d coefficients (1 <= p <= %d)", p, PLAIDHIP_LIMMA_MAX_COEF);
-  const dim3 grid((rows + 255) / 256, (n + kVColBlock - 1) / kVColBlock);
+  const dim3 grid((rows + 255) / 256, (n + kRowColBlock - 1) / kRowColBlock);
 #define PH_VOOM_W(KP)                                                                                                        \
   hipLaunchKernelGGL((voom_weights_kernel<KP>), grid, dim3(256), 0, ctx->stream, d_Q, d_off, n, p, d_Eff, rows, d_kx, d_ky, nk, W, \
                      ldw)

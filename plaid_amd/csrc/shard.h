@@ -134,7 +134,7 @@ struct Shared {
   struct Gsea { std::vector<double> part, ml; } gsea;
 };
 
-// columns [lo, lo + nloc) of shard k: cut at multiples of kColBlock (kernels_stats.hip, 128 columns) for the methods whose
+// columns [lo, lo + nloc) of shard k: cut at multiples of kRowColBlock (row_pair.h, 128 columns) for the methods whose
 // chained row reductions add the block partials of the one-device call in the same order (route's block_cut); everything
 // else takes plaidhip_shard_bounds.
 void shard_columns(const Call& c, int ndev, int k, int32_t* lo, int32_t* nloc);

@@ -29,7 +29,7 @@ def sets(g, m, seed, kmin=2, kmax=300, force=()):
 
 
 # ------------------------------------------------------------------ dense X for rowtf = "z"
-# (g, n, seed): the rank kernel's size classes at n = 5 ... 9, then the column-block seams of kColBlock = 128 (and 300 for
+# (g, n, seed): the rank kernel's size classes at n = 5 ... 9, then the column-block seams of kRowColBlock = 128 (and 300 for
 # the shards) at g = 600; n = 105 is where fl(1 / n) * (1.25 n) != 1.25
 DENSE = {
     "g257": (257, 5, 1), "g2049": (2049, 6, 2), "g8193": (8193, 7, 3), "g12289": (12289, 8, 4), "g20449": (20449, 9, 5),

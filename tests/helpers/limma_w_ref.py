@@ -339,6 +339,9 @@ IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in CASES]
 # 8 (the 8-register residual kernel) and p = 9 (the first p past it); nfit = 9 (a second tile of 8 fits in the counts kernel,
 # holding one fit) and nfit = 17 (three of them; Wc = 3 and W = 51, so the tiles of 8 weight columns straddle fits)
 P_CASES = [(12, 131, 5, 1), (11, 131, 8, 2), (12, 131, 9, 1), (12, 40, 2, 9), (11, 40, 1, 17)]
+# (appended: P_CASES[:3] keeps its meaning) p = 9 on an odd number of rows: the last instance of the residual kernel (p past 8) on
+# the 8-byte loads, which no case above launches
+P_CASES += [(11, 131, 9, 1)]
 P_IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in P_CASES]
 # the designated rows (a case with fewer rows has those that fit): weights that make an observation missing at columns 0, 127,
 # 128 and n - 1 (zero, negative, NaN, +Inf); all weights zero within one group of fit 1 (not estimable); |live| = p in fit 1; a

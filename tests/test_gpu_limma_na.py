@@ -11,7 +11,8 @@
 
 Shapes: CASES -- (rows, n, p, nfit) = (515, 300, 3, 3), (130, 131, 8, 2), (130, 300, 2, 3) -- and, for items 1, 2 and 5,
 P_CASES = (60, 131, 10, 1), (61, 131, 9, 2): p = 9 and 10 run the 16-register instance of the residual kernel with the NaN
-select, which no case with p <= 8 launches; 60 rows are the fewest that hold ROLE, SINGLES and SPREAD.
+select, which no case with p <= 8 launches, and (61, 131, 8, 1): its 8-register instance on an odd number of rows (the 8-byte
+loads); 60 rows are the fewest that hold ROLE, SINGLES and SPREAD.
 """
 import numpy as np
 import pytest
@@ -32,6 +33,9 @@ IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in CASES]
 # past eight coefficients (p = 9, 10: the 16-register instance of the residual kernel with the NaN select), at the fewest rows that
 # hold ROLE, SINGLES and SPREAD; even and odd.  Held to na = "propagate", whose p = 9 is held to exact sums in test_gpu_limma.py
 P_CASES = [(60, 131, 10, 1), (61, 131, 9, 2)]
+# (appended) the 8-register instance with the NaN select on the 8-byte loads (5 <= p <= 8, odd rows), which no case above launches;
+# 131 columns: the walk crosses one block boundary and ends in a tail of 3
+P_CASES += [(61, 131, 8, 1)]
 P_IDS = [f"rows{c[0]}-n{c[1]}-p{c[2]}-nfit{c[3]}" for c in P_CASES]
 ROLE = {"c0": 0, "c127": 1, "c128": 2, "clast": 3, "four": 4, "group": 5, "all": 6, "unused": 7, "inf_used_nan": 8,
         "inf_unused": 9, "inf_used": 10, "above": 11, "p_left": 12}

@@ -13,7 +13,8 @@ Shapes: wr.CASES -- (rows, n, p, nfit) = (515, 300, 3, 3), (130, 131, 10, 2), (3
 1 and 3, wr.P_CASES: (12, 131, 5, 1), (11, 131, 8, 2) and (12, 131, 9, 1) for the 8-register instance of the residual kernel
 and the first p past it; (12, 40, 2, 9) and (11, 40, 1, 17) for a second and a third tile of 8 fits in the counts kernel, 9
 and 17 fits in the solve, and weight-column tiles that straddle fits (Wc = 3, W = 51).  12 rows hold every designated row, 11
-are odd (the 8-byte loads).  Item 3 runs on ALL rows and fits of P_CASES, item 1 on the first three of them;
+are odd (the 8-byte loads); (11, 131, 9, 1) for the residual kernel past p = 8 on the 8-byte loads.  Item 3 runs on ALL rows
+and fits of P_CASES, item 1 on the first three of them;
 tests/test_limma_w_ref.py establishes what both presume of these inputs without a device.
 """
 import numpy as np
