@@ -1249,6 +1249,7 @@ void check_pair_plan(const PairPlanHost& pp, int32_t m, const int32_t* Gp, const
                      int32_t* pairs, int64_t cap) {
   int64_t found = 0, conflicts = 0, wrong = 0, npairs = 0, broken = 0;
   std::vector<uint8_t> seen((size_t)Gp[m], 0);
+  std::vector<uint8_t> owners_at_every_end((size_t)waves, 1);   // out[13]
   int32_t si = 0;
   for (const PairSliceHost& ps : pp.slices) {
     auto in_slice = [&](int32_t j) {
@@ -1261,6 +1262,7 @@ void check_pair_plan(const PairPlanHost& pp, int32_t m, const int32_t* Gp, const
       int64_t pair_of[64];
       bool fresh = true;
       int32_t tile_begin = ps.wave_chunk_off[w];
+      int tiles_seen = 0, tiles_with_owner = 0;
       for (int32_t ch = ps.wave_chunk_off[w]; ch < ps.wave_chunk_off[w + 1]; ++ch) {
         const uint8_t* fx = ps.flex.empty() ? nullptr : &ps.flex[(size_t)k * 64];
         if (fresh) {
@@ -1286,7 +1288,9 @@ void check_pair_plan(const PairPlanHost& pp, int32_t m, const int32_t* Gp, const
               ++npairs;
             }
             if (hosts != owners) ++broken;
+            if (owners > 0) ++tiles_with_owner;
           }
+          ++tiles_seen;
         }
         for (int e = 0; e < 8; ++e) {
           for (int q = 0; q < 4; ++q) {
@@ -1313,6 +1317,7 @@ void check_pair_plan(const PairPlanHost& pp, int32_t m, const int32_t* Gp, const
         if (ch + 1 == ps.wtile_end[k]) { ++k; fresh = true; tile_begin = ch + 1; }
       }
       if (k != pp.wave_tile_off[w + 1]) ++wrong;
+      if (tiles_seen < 2 || tiles_with_owner != tiles_seen) owners_at_every_end[w] = 0;
     }
     ++si;
   }
@@ -1330,6 +1335,9 @@ void check_pair_plan(const PairPlanHost& pp, int32_t m, const int32_t* Gp, const
     out[8] = pp.chunks * 64 * 8;
     out[9] = npairs;
     out[10] = broken;
+    // wavefronts with two tiles or more whose EVERY tile has an owner in EVERY slice: consecutive tile ends with a pull,
+    // the last one of the slice included (tests/test_gpu_pair_tile_end.py)
+    out[13] = std::count(owners_at_every_end.begin(), owners_at_every_end.end(), (uint8_t)1);
   } else {
     out[4] += broken;
   }
@@ -1345,7 +1353,7 @@ extern "C" int plaidhip_debug_pair_plan_check(int32_t g, int32_t m, const int32_
 } catch (...) { return plaidhip::on_exception(); }
 
 // The same with the flex steps in view: out[16] (check_pair_plan; out[11] = microseconds the plan took to build), the
-// owner <-> host pairs in `pairs` (4 x cap words; out[9] says how many there are), and `flex` 0 for the plan the same
+// owner <-> host pairs in `pairs` (4 x cap words; out[9] says how many there are; out[13]: see there), and `flex` 0 for the plan the same
 // collection gets without flex steps -- the slot count and the double-booked reads (out[3]) to hold this plan against.
 extern "C" int plaidhip_debug_pair_flex_probe(int32_t g, int32_t m, const int32_t* Gp, const int32_t* Gi, int32_t waves,
                                               int32_t flex, int64_t out[16], int32_t* pairs, int64_t cap) try {

@@ -452,6 +452,8 @@ struct SpmmPairArgs {
   int32_t med_capc;
 };
 
+constexpr size_t kStampTileEndPlane = 131072;   // STAMP: 8-byte words into dbg (tools/bench_spmm.py allocates twice that)
+
 __device__ __forceinline__ uint32_t off16_lo(uint32_t q) {
   uint32_t r;
   asm("v_lshlrev_b32_sdwa %0, 4, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
@@ -494,7 +496,7 @@ spmm_colpair_f64(SpmmPairArgs a) {
   if constexpr (CSC_X) {
     if (a.sparse_cells != 0 && ((int64_t)a.Xp[a.n] - a.Xp[0]) * 8 < a.sparse_cells) return;
   }
-  unsigned long long t_stage = 0, t_gather = 0, t_wait = 0, t_all0 = 0;
+  unsigned long long t_stage = 0, t_gather = 0, t_wait = 0, t_all0 = 0, t_tend = 0;
   if constexpr (STAMP) t_all0 = __builtin_amdgcn_s_memtime();
   extern __shared__ __align__(16) unsigned char smem_raw[];
   f64x2* ent = reinterpret_cast<f64x2*>(smem_raw);
@@ -557,21 +559,22 @@ spmm_colpair_f64(SpmmPairArgs a) {
   // alive across the slices of a pair (slot = tile ordinal within the wavefront's stream); otherwise the workgroup's scratch
   const char* part = nullptr;
   if constexpr (!REGP) part = reinterpret_cast<const char*>(a.partial + (size_t)blockIdx.x * (size_t)(a.ktiles + 1) * 64);  // uniform
-  f64x2 r0, r1, r2, r3, r4, r5, r6, r7;
-  r0 = r1 = r2 = r3 = r4 = r5 = r6 = r7 = f64x2{0.0, 0.0};
-  static_assert(kPairRegPartials == 8, "register slots r0..r7");
-// wave-uniform slot choice (s_ is a scalar): once per tile and slice
-#define PLAIDHIP_RSLOT_PUT(s_, v_)                                                     \
-  switch (s_) {                                                                        \
-    case 0: r0 = (v_); break; case 1: r1 = (v_); break; case 2: r2 = (v_); break;      \
-    case 3: r3 = (v_); break; case 4: r4 = (v_); break; case 5: r5 = (v_); break;      \
-    case 6: r6 = (v_); break; default: r7 = (v_); break;                               \
+  typedef double f64x16 __attribute__((ext_vector_type(16)));
+  f64x16 rs = 0.0;   // slot s: {rs[2 s], rs[2 s + 1]} = the sums of columns A and B
+  static_assert(kPairRegPartials == 8, "register slots: one vector of 8 pairs");
+// wave-uniform slot choice, once per tile and slice: ONE vector value indexed by a scalar, which is a register-indexed move
+// (s_set_gpr_idx_on), not a branch tree over eight named pairs with a copy of all of them.  The ordinal behind a
+// wavefront's last tile (a read nothing uses) wraps to slot 0: an index past the vector would name other registers.
+#define PLAIDHIP_RSLOT_PUT(s_, va_, vb_)                                               \
+  {                                                                                    \
+    const int sl_ = __builtin_amdgcn_readfirstlane(s_) & (kPairRegPartials - 1);       \
+    rs[2 * sl_] = (va_);                                                               \
+    rs[2 * sl_ + 1] = (vb_);                                                           \
   }
 #define PLAIDHIP_RSLOT_GET(s_, o_)                                                     \
-  switch (s_) {                                                                        \
-    case 0: o_ = r0; break; case 1: o_ = r1; break; case 2: o_ = r2; break;            \
-    case 3: o_ = r3; break; case 4: o_ = r4; break; case 5: o_ = r5; break;            \
-    case 6: o_ = r6; break; default: o_ = r7; break;                                   \
+  {                                                                                    \
+    const int sl_ = __builtin_amdgcn_readfirstlane(s_) & (kPairRegPartials - 1);       \
+    o_ = f64x2{rs[2 * sl_], rs[2 * sl_ + 1]};                                          \
   }
 
   // MED: wave-uniform state of the pair being written (scalar registers)
@@ -782,6 +785,8 @@ spmm_colpair_f64(SpmmPairArgs a) {
 #define PLAIDHIP_TILE_END(chv)                                                                 \
   if ((chv) + 1 == next_end) { /* wave-uniform: tile finished */                               \
     double sumA, sumB;                                                                         \
+    unsigned long long te0_ = 0;                                                               \
+    if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); te0_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } \
     if constexpr (FLEX) {   /* a3 / b3: the flex sums */                                       \
       double ownA_ = (a0 + a1) + a2;                                                           \
       double ownB_ = (b0 + b1) + b2;                                                           \
@@ -806,9 +811,11 @@ spmm_colpair_f64(SpmmPairArgs a) {
       sumA = ((a0 + a1) + (a2 + a3)) + old.x;                                                  \
       sumB = ((b0 + b1) + (b2 + b3)) + old.y;                                                  \
     }                                                                                          \
+    /* (in the last slice too, where nothing reads the slot again: a put on one of two paths has the compiler copy \
+       the whole vector and copy it back where the paths meet) */                              \
+    if constexpr (REGP) { PLAIDHIP_RSLOT_PUT(k - tk_begin, sumA, sumB) }                       \
     if (!last) {                                                                               \
-      if constexpr (REGP) {                                                                    \
-        PLAIDHIP_RSLOT_PUT(k - tk_begin, (f64x2{sumA, sumB}))                                  \
+      if constexpr (REGP) {   /* (put above) */                                                \
       } else if (PH_PAIR_PSTORE) {                                                                 \
         f64x2* dst_ = reinterpret_cast<f64x2*>(const_cast<char*>(part) + (int64_t)PH_PAIR_PSLOT(k) * 1024 + ioff);  \
         if (PH_PAIR_PST_NT) __builtin_nontemporal_store(f64x2{sumA, sumB}, dst_);              \
@@ -846,7 +853,12 @@ spmm_colpair_f64(SpmmPairArgs a) {
       } else old = (PH_PAIR_PLD_NT || PNT) ? __builtin_nontemporal_load(src_) : *src_;     \
     }                                                                                          \
     a0 = a1 = a2 = a3 = b0 = b1 = b2 = b3 = 0.0;                                               \
-                                                                                         \
+    if constexpr (STAMP) {   /* the tile end's own cycles (both clock values are waited for behind the second read) */ \
+      asm volatile("" : "+v"(old.x), "+v"(old.y));   /* the slot read belongs to the tile end */ \
+      __builtin_amdgcn_sched_barrier(0);                                                       \
+      t_tend += __builtin_amdgcn_s_memtime() - te0_;                                           \
+      __builtin_amdgcn_sched_barrier(0);                                                       \
+    }                                                                                          \
   }
         // 8 index chunks (8 KiB per wave) in flight: the lists come from L2 (~1 us away under load)
         u32x4 qa = PLAIDHIP_LOADQ(0);
@@ -875,7 +887,7 @@ spmm_colpair_f64(SpmmPairArgs a) {
           fx = *(__attribute__((address_space(1))) const unsigned long long*)((gptr_u8)a.flex + ((int64_t)(si * 16 + wave) * 64) * 8 + lane_o * 8u);
         f64x2 old = f64x2{0.0, 0.0};
         if constexpr (REGP) {
-          if (!first) old = r0;
+          if (!first) old = f64x2{rs[0], rs[1]};
         } else if (!first && PH_PAIR_PLOAD) {
           const f64x2* src_ = reinterpret_cast<const f64x2*>(part + (int64_t)PH_PAIR_PSLOT(k) * 1024 + ioff);
           old = (PH_PAIR_PLD_NT || PNT) ? __builtin_nontemporal_load(src_) : *src_;
@@ -966,6 +978,9 @@ spmm_colpair_f64(SpmmPairArgs a) {
     if (lane == 0 && a.dbg != nullptr) {
       unsigned long long* d = a.dbg + ((size_t)blockIdx.x * (BLOCK / 64) + wave) * 4;
       d[0] = t_stage; d[1] = t_gather; d[2] = t_wait; d[3] = __builtin_amdgcn_s_memtime() - t_all0;
+      // a fourth bucket, part of `gather`: the cycles inside taken tile ends, in a plane of its own behind the four-word
+      // records of every form (tools/bench_spmm.py reads both)
+      a.dbg[kStampTileEndPlane + (size_t)blockIdx.x * (BLOCK / 64) + wave] = t_tend;
     }
   }
   if constexpr (MED) f |= med_fw;

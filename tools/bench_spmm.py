@@ -251,6 +251,13 @@ def main():
         print(f"  stamps (mean over {nwg} WGs x {waves} waves, cycles per launch): stage {d[:,:,0].mean():.0f} "
               f"({100*d[:,:,0].mean()/tot:.1f}%) gather {d[:,:,1].mean():.0f} ({100*d[:,:,1].mean()/tot:.1f}%) "
               f"end-barrier wait {d[:,:,2].mean():.0f} ({100*d[:,:,2].mean()/tot:.1f}%) total {tot:.0f}")
+        if a.ablate == 4 and a.kernel == "spmm" and g > 10224:
+            # the pair kernel's fourth bucket, a part of `gather`: cycles inside taken tile ends (one word per wavefront in a
+            # plane of its own, kStampTileEndPlane words into the buffer)
+            te = dbg.cpu().numpy()[131072: 131072 + nwg * waves].reshape(nwg, waves).astype(float)
+            print(f"  tile ends {te.mean():.0f} cycles ({100 * te.mean() / tot:.1f}% of the launch, "
+                  f"{100 * te.mean() / max(d[:, :, 1].mean(), 1.0):.1f}% of gather); per wave, mean over WGs: "
+                  f"{te.mean(axis=0).astype(int).tolist()}")
         print("  per-wave gather cycles, WG 0:", d[0, :, 1].astype(int).tolist())
         print("  per-wave wait   cycles, WG 0:", d[0, :, 2].astype(int).tolist())
         print("  per-wave gather cycles, mean over WGs:", d[:, :, 1].mean(axis=0).astype(int).tolist())
